@@ -8,18 +8,23 @@ batch 16 per GPU, T = 2000 linear-beta reverse steps.  A *step* is one reverse s
 --steps 2000 times one complete sample; images/s = N * B / (T * t_step).  `--config sr3_64_512` (configs[3], batch 4)
 and `--config ddpm_128` (configs[4], batch 32, unconditional) time the other BASELINE.json networks the same way.
 
-One JSON line on rank 0 (contract in the task statement) with these extra objects:
+One JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run does only what that
+line needs: set up, warm up, time exactly --steps graph replays, write --dump-outputs DIR if given, print.  With --full the
+line also carries these extra objects (each leg measured after the timed region, as before):
   roofline            -- dominant kernel (a halo-tile 3x3 conv instantiation on v_mfma_f32_32x32x2_f32): algorithmic
                          FLOPs per launch / average launch duration, measured with HIP events around every launch of
                          the plan (sr3_unet_forward_profile, on the stream the kernels run on) after the timed region.
   parity              -- the graph bench.py just timed, replayed once from a fixed (x, cond, t); its eps and x_{t-1}
                          against the CPU oracle on the same inputs and the same in-graph z (max abs difference).
-  cpu_baseline        -- the reference itself (subprocess importing $SR3_REFERENCE or /root/reference, kind
-                         "reference") or, where that tree does not exist (the GPU box), the CPU oracle (kind "port"),
+  cpu_baseline        -- the reference itself (subprocess importing the tree reference_root() finds, $SR3_REFERENCE
+                         first, kind "reference") or, where there is none, the CPU oracle (kind "port"),
                          timed on this node's host cores on a bounded sample; `.train` = training steps per image.
   torch_rocm_baseline -- the same oracle ops on `cuda` through stock PyTorch-ROCm (MIOpen / rocBLAS): "what you get by
                          default on this node".  Reported, never the target.
   train               -- BASELINE.json configs[2] / [4]: training step (p_losses + backward + Adam) images/s.
+  exact_fp32, other_configs -- the same step on the fp32 MFMA plan; bounded runs of the other BASELINE.json networks.
+--dump-outputs DIR: what the last timed step computed, DIR/x_prev.npy (the chains' images after it) and DIR/eps.npy, float32
+(over 64 MB in all: a fixed, seeded sample of whole images).  Inputs and weights are seeded: the same arguments give the same inputs.
 Multi-GPU: one process per GPU.  `python bench.py --gpus N` launches the N ranks itself (torch.distributed.run over
 127.0.0.1) when it is not already running under a launcher; under `python -m torch.distributed.run ... bench.py --gpus N`
 it uses the launcher's ranks (and refuses a WORLD_SIZE that differs from --gpus).  Sampling: independent image batches
@@ -626,6 +631,7 @@ def build_sampler(cfg_name, B, dev, rank, split_bf16=False, T=2000, exact_fp32=F
     cfg = CONFIGS[cfg_name]
     if STUB:
         S = cfg['size']
+        torch.manual_seed(1000 + rank)
         st = {'img': torch.randn(B, 3, S, S), 'step': torch.zeros(1, dtype=torch.int32), 'cond': None}
         st['graph'] = _StubGraph(st)
         return _StubNet(cfg_name), st
@@ -762,6 +768,27 @@ def time_replays(st, steps, warmup, T, dist, dev):
     return elapsed
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, st, rank, world):
+    """--dump-outputs: what the last timed replay computed -- x_{t-1} (the chains' images after the step) and that step's eps --
+    as float32 DIR/<name>.npy (rank r > 0: <name>_rank<r>.npy).  Over the budget (64 MB in all, shared by the ranks), a fixed,
+    seeded sample of whole images (batch rows, in batch order) of each array."""
+    import numpy as np
+    arrays = [(k, st.get(k)) for k in ('img', 'eps')]
+    arrays = [('x_prev' if k == 'img' else k, v) for k, v in arrays if v is not None]
+    budget = DUMP_LIMIT_BYTES // (len(arrays) * world)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = '' if rank == 0 else '_rank%d' % rank
+    for name, t in arrays:
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > budget:
+            rows = max(1, budget // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=rows, replace=False))]
+        np.save(os.path.join(out_dir, name + suffix + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def other_config_leg(cfg_name, dev, steps=50, warmup=3, T=2000, batch=None):
     """A bounded run of another BASELINE.json configuration (configs[3] SR3 64->512 at batch 4, configs[4] DDPM-128 at batch 32)
     for the driver's record: graph-replayed reverse steps, the parity of that graph against the CPU oracle, and the dominant
@@ -826,6 +853,11 @@ def main():
     ap.add_argument('--config', default='sr3_16_128', choices=sorted(CONFIGS),
                     help='BASELINE.json network: sr3_16_128 (configs[1], the headline; default), sr3_64_512 (configs[3]), ddpm_128 (configs[4])')
     ap.add_argument('--batch', type=int, default=0, help='images per GPU (default: the BASELINE.json batch of --config)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run the extra legs (parity, roofline, exact-fp32 / split legs, training, CPU and '
+                         'stock-PyTorch baselines, other configurations); the --no-* / --train-* / --split-leg options below refine them')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (x_prev, eps) as DIR/<name>.npy, float32')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-torch-baseline', action='store_true', help='skip the stock PyTorch-ROCm (MIOpen) leg')
     ap.add_argument('--no-roofline', action='store_true')
@@ -844,7 +876,7 @@ def main():
     ap.add_argument('--split-bf16', action='store_true',
                     help='experiment: run the HEADLINE leg with the split_bf16 plan option (dtype is then reported as '
                          '"f32 via 3xbf16 split MFMA"; the default is the exact-fp32 MFMA path)')
-    ap.add_argument('--train-steps', type=int, default=10, help='0 disables the training leg')
+    ap.add_argument('--train-steps', type=int, default=10, help='(--full) 0 disables the training leg')
     ap.add_argument('--train-batch', type=int, default=0, help='images per GPU (default: the BASELINE.json batch of --config)')
     ap.add_argument('--extra-leg-timeout', type=int, default=600,
                     help='seconds after which the roofline / split / train / baseline legs are abandoned and the line is printed')
@@ -898,6 +930,8 @@ def main():
     netG, st = build_sampler(a.config, B, dev, rank, a.split_bf16, T, a.exact_fp32, plan_opts)
     elapsed = time_replays(st, a.steps, a.warmup, T, dist, dev)
     finite = bool(torch.isfinite(st['img']).all().item())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, st, rank, world)
     ms_per_step = elapsed / a.steps * 1e3
     images_per_s = world * B / (T * ms_per_step * 1e-3)
 
@@ -932,6 +966,11 @@ def main():
             if note:
                 rec['note'] = note
             print(json.dumps(rec), flush=True)
+
+    if not a.full:                # a plain run: the headline line and nothing else
+        emit()
+        finish(dist)
+        return
 
     def watchdog():
         # an extra leg hung (e.g. a collective on a sick node): the headline measurement is already done -- print it
@@ -1017,6 +1056,10 @@ def main():
         torch.cuda.empty_cache()
     timer.cancel()
     emit()
+    finish(dist)
+
+
+def finish(dist):
     if dist:
         try:
             dist.barrier()

@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by running the REFERENCE itself (imported from
 /root/reference, CPU, fp32) on seeded inputs.  Run in the build container only:
 
-    python oracle/make_golden.py            # writes tests/golden/{sr3_tiny,ddpm_tiny,sr3_seam}.npz
+    python oracle/make_golden.py            # writes tests/golden/{sr3_tiny,ddpm_tiny,sr3_seam}.npz (over 900 KB: <name>.part<i>.npz)
 
 The reference cannot travel to the GPU box, so the vectors are committed; this script is
 the provenance.  Nothing in the reference is modified: RNG draws are made reproducible by
@@ -174,10 +174,44 @@ def build(name, opt, batch, seed, with_train=True, scale_weights=None):
         for k, p in netG.named_parameters():
             out['adam1/' + k] = p.detach().numpy().copy()
     os.makedirs(OUT, exist_ok=True)
-    path = os.path.join(OUT, name + '.npz')
-    np.savez_compressed(path, **out)
-    print(name, 'params', sum(p.numel() for p in netG.parameters()), '->', path,
-          '%.1f KB' % (os.path.getsize(path) / 1024))
+    paths = save_golden(name, out)
+    print(name, 'params', sum(p.numel() for p in netG.parameters()), '->', ', '.join(paths),
+          '%.1f KB' % (sum(os.path.getsize(p) for p in paths) / 1024))
+
+
+PART_BYTES = 900 * 1024        # committed files stay under 1 MiB: a larger record is written as <name>.part<i>.npz
+
+
+def save_golden(name, out):
+    """tests/helpers.py load_golden reads either form back."""
+    import glob
+    for old in glob.glob(os.path.join(OUT, name + '.part*.npz')) + glob.glob(os.path.join(OUT, name + '.npz')):
+        os.remove(old)
+    parts, cur, size = [], {}, 0
+    for k, v in out.items():
+        v = np.asarray(v)
+        if cur and size + v.nbytes > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += v.nbytes
+    parts.append(cur)
+    if len(parts) == 1:
+        paths = [os.path.join(OUT, name + '.npz')]
+    else:
+        paths = [os.path.join(OUT, '%s.part%d.npz' % (name, i)) for i in range(len(parts))]
+    for path, part in zip(paths, parts):
+        np.savez_compressed(path, **part)
+    return paths
+
+
+def load_golden(name):
+    import glob
+    g = {}
+    for p in sorted(glob.glob(os.path.join(OUT, name + '.part*.npz'))) or [os.path.join(OUT, name + '.npz')]:
+        with np.load(p) as z:
+            g.update((k, z[k]) for k in z.files)
+    return g
 
 
 def build_all(only=None):

@@ -1,4 +1,5 @@
 """Shared helpers for the test-suite (golden loading, tiny configs)."""
+import glob
 import os
 
 import numpy as np
@@ -28,8 +29,11 @@ CONDITIONAL = {'sr3_tiny': True, 'ddpm_tiny': False, 'sr3_seam': True, 'sr3_unco
 
 
 def load_golden(name):
-    z = np.load(os.path.join(GOLDEN, name + '.npz'))
-    g = {k: z[k] for k in z.files}
+    """<name>.npz, or its parts <name>.part<i>.npz (a record over the size limit of a committed file is stored split)."""
+    g = {}
+    for p in sorted(glob.glob(os.path.join(GOLDEN, name + '.part*.npz'))) or [os.path.join(GOLDEN, name + '.npz')]:
+        with np.load(p) as z:
+            g.update((k, z[k]) for k in z.files)
     sd = {k[3:]: torch.from_numpy(v) for k, v in g.items() if k.startswith('sd/')}
     return g, sd
 

@@ -1,8 +1,9 @@
 """Drop-in boundary conformance, CPU only.  Both trees call their package `model`, so the reference's call
 surface is read in a subprocess (tests/sig_dump.py) and compared with the drop-in's: every reference parameter list must be
 an exact PREFIX of ours (name, kind, default) and anything we add must be keyword-only with a default -- so every call
-the reference's sr.py / infer.py / sample.py can make binds identically.  Skipped where the reference tree is absent
-(the GPU box)."""
+the reference's sr.py / infer.py / sample.py can make binds identically.  The reference's side is the record in
+tests/golden/ref_boundary.json (oracle/make_golden_boundary.py); where a reference tree is present it is also read live and
+must still equal that record.  Only the test that runs the reference's own code needs the tree itself."""
 import json
 import os
 import subprocess
@@ -19,6 +20,11 @@ needs_ref = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, 'model', 'ne
                                reason='reference tree not present')
 
 
+def _golden():
+    with open(os.path.join(ROOT, 'tests', 'golden', 'ref_boundary.json')) as f:
+        return json.load(f)
+
+
 def _dump(root):
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'sig_dump.py'), root], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=300)
@@ -26,9 +32,10 @@ def _dump(root):
     return json.loads(r.stdout.decode().strip().splitlines()[-1])
 
 
-@needs_ref
 def test_public_signatures_match_reference():
-    ref, ours = _dump(REF), _dump(PKG)
+    ref, ours = _golden()['signatures'], _dump(PKG)
+    if os.path.isfile(os.path.join(REF, 'model', 'networks.py')):
+        assert _dump(REF) == ref, 'tests/golden/ref_boundary.json is stale: rerun oracle/make_golden_boundary.py'
     problems = []
 
     def check(name, a, b):
@@ -54,30 +61,19 @@ def test_public_signatures_match_reference():
     assert n >= 60          # DDPM (17 methods), both GaussianDiffusion classes, both UNets, factories
 
 
-@needs_ref
 @pytest.mark.parametrize('init_type', ['normal', 'kaiming', 'orthogonal'])
 def test_init_weights_schemes_draw_the_reference_weights(init_type):
-    """model/networks.py:14-77: same seed => same weights as the reference's `init_weights(netG, init_type)`."""
-    code = ('import sys, logging; sys.path.insert(0, %r); logging.disable(50); import torch; import model.networks as N;'
-            'from helpers_opt import opt; torch.manual_seed(5); net = N.define_G(opt()); torch.manual_seed(9);'
-            'N.init_weights(net, init_type=%r, scale=0.3, std=0.05);'
-            'torch.save({k: v for k, v in net.state_dict().items() if k.startswith("denoise_fn.")}, sys.argv[1])')
-    import tempfile
-    tmp = tempfile.mkdtemp()
-    with open(os.path.join(tmp, 'helpers_opt.py'), 'w') as f:
-        f.write('import sys\nsys.path.insert(0, %r)\nfrom helpers import opt_for\n'
-                'def opt():\n    o = opt_for("sr3_tiny", phase="val", gpu=False)\n    return o\n' % os.path.join(ROOT, 'tests'))
-    outs = {}
-    for tag, root in (('ref', REF), ('ours', PKG)):
-        out = os.path.join(tmp, tag + '.pth')
-        env = dict(os.environ, PYTHONPATH=tmp)
-        r = subprocess.run([sys.executable, '-c', code % (root, init_type), out], env=env, stdout=subprocess.PIPE,
-                           stderr=subprocess.PIPE, timeout=300)
-        assert r.returncode == 0, r.stderr.decode()[-800:]
-        outs[tag] = torch.load(out)
-    assert set(outs['ref']) == set(outs['ours'])
-    for k, v in outs['ref'].items():
-        assert torch.equal(v, outs['ours'][k]), k
+    """model/networks.py:14-77: same seed => same weights (bit for bit: sha256 of every tensor) as the reference's
+    `init_weights(netG, init_type)`."""
+    sys.path.insert(0, os.path.join(ROOT, 'oracle'))
+    import make_golden_boundary as G
+    ref = _golden()['init_weights'][init_type]
+    if os.path.isfile(os.path.join(REF, 'model', 'networks.py')):
+        assert G.init_digests(os.path.abspath(REF), init_type) == ref, 'tests/golden/ref_boundary.json is stale'
+    ours = G.init_digests(PKG, init_type)
+    assert set(ref) == set(ours)
+    for k, v in ref.items():
+        assert ours[k] == v, k
 
 
 def test_finetune_norm_raises_like_the_reference():
@@ -113,19 +109,21 @@ def test_reference_cpu_baseline_tool_runs(tmp_path):
     assert rec['kind'] == 'reference' and rec['value'] > 0 and rec['train']['value'] > 0, rec
 
 
-@needs_ref
 @pytest.mark.parametrize('name', ['sr3_16_128', 'sr3_64_512', 'ddpm_128'])
 def test_bench_configs_are_the_reference_json_configs(name):
     """bench.py's CONFIGS / config_opt restate the `model` subtree of the reference's JSON files (comments stripped as
     core/logger.py:21-33 does): same network, same schedules, same image size -- so the bench line measures the
     configuration BASELINE.json names."""
-    import re
     sys.path.insert(0, ROOT)
     import bench
     c = bench.CONFIGS[name]
-    with open(os.path.join(REF, c['ref_json'])) as f:
-        txt = '\n'.join(line.split('//')[0] for line in f)
-    ref = json.loads(txt)['model']
+    rec = _golden()['configs'][name]
+    assert rec['ref_json'] == c['ref_json']
+    if os.path.isfile(os.path.join(REF, c['ref_json'])):
+        with open(os.path.join(REF, c['ref_json'])) as f:
+            full = json.loads('\n'.join(line.split('//')[0] for line in f))
+        assert (full['model'], full['train']['optimizer']['lr']) == (rec['model'], rec['lr']), 'tests/golden/ref_boundary.json is stale'
+    ref = rec['model']
     got = bench.config_opt(name)['model']
     assert got['which_model_G'] == ref['which_model_G']
     for k, v in ref['unet'].items():
@@ -136,8 +134,7 @@ def test_bench_configs_are_the_reference_json_configs(name):
             assert got['beta_schedule'][ph][k] == ref['beta_schedule'][ph][k], (ph, k)
     assert got['diffusion']['image_size'] == ref['diffusion']['image_size'] == c['size']
     assert got['diffusion']['conditional'] == ref['diffusion']['conditional'] == c['conditional']
-    full = json.loads(txt)
-    assert abs(full['train']['optimizer']['lr'] - c['lr']) < 1e-12
+    assert abs(rec['lr'] - c['lr']) < 1e-12
 
 
 def test_committed_profile_summaries_cover_the_kernels_bench_reports():

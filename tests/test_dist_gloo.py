@@ -191,7 +191,7 @@ def test_bench_two_ranks_end_to_end_stub_engine():
     bench = os.path.join(ROOT, 'bench.py')
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env['SR3_BENCH_STUB'] = '1'
-    r = subprocess.run([sys.executable, bench, '--gpus', '2', '--steps', '5', '--warmup', '2', '--train-steps', '2', '--train-batch', '2',
+    r = subprocess.run([sys.executable, bench, '--gpus', '2', '--steps', '5', '--warmup', '2', '--full', '--train-steps', '2', '--train-batch', '2',
                         '--no-roofline', '--no-exact-leg', '--no-cpu-baseline', '--no-torch-baseline', '--no-other-configs'],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd='/tmp')
     assert r.returncode == 0, r.stderr[-600:]
@@ -208,6 +208,33 @@ def test_bench_two_ranks_end_to_end_stub_engine():
     assert tr['gradient_buckets_per_step'] == 12 and tr['gradient_buckets_walked'] == 12 * (2 + 2)     # 391 MB in 32 MB buckets
     assert tr['l_pix_last'] == 2.0                               # every gradient is 1.0 on each rank: the all-reduce summed them
     assert abs(tr['value'] - 2 * 2 / (tr['ms_per_step'] * 1e-3)) < 1e-6 * tr['value']
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A run without --full times the headline and nothing else (no training, parity or baseline leg); --dump-outputs writes
+    the last timed step's arrays as float32 .npy, and the same arguments give the same arrays (stub engine, one rank)."""
+    import json
+    import subprocess
+    import numpy as np
+    bench = os.path.join(ROOT, 'bench.py')
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
+    env['SR3_BENCH_STUB'] = '1'
+    outs = []
+    for run in range(2):
+        d = tmp_path / ('out%d' % run)
+        r = subprocess.run([sys.executable, bench, '--gpus', '1', '--steps', '7', '--warmup', '1', '--dump-outputs', str(d)],
+                           env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd='/tmp')
+        assert r.returncode == 0, r.stderr[-600:]
+        lines = [l for l in r.stdout.decode().splitlines() if l.startswith('{')]
+        assert len(lines) == 1, r.stdout[-600:]
+        rec = json.loads(lines[0])
+        assert rec['steps'] == 7 and rec['warmup'] == 1 and rec['ms_per_step'] > 0 and rec['higher_is_better'] is True
+        assert abs(rec['value'] - 16 / (2000 * rec['ms_per_step'] * 1e-3)) < 1e-6 * rec['value']
+        assert not {'train', 'parity', 'roofline', 'cpu_baseline', 'torch_rocm_baseline', 'exact_fp32', 'other_configs'} & set(rec)
+        x = np.load(str(d / 'x_prev.npy'))
+        assert x.dtype == np.float32 and x.shape == (16, 3, 128, 128)
+        outs.append(x)
+    assert np.array_equal(outs[0], outs[1])
 
 
 def _valwave_worker(rank, world, port, shapes, ret):

@@ -14,8 +14,8 @@ if [ "${2:-}" = "--with-tests" ]; then
   tail -2 $OUT/pytest_gpu.log
 fi
 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
-python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
-Q="--no-cpu-baseline --no-torch-baseline --train-steps 0 --no-split-leg --no-other-configs"
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+Q="--full --no-cpu-baseline --no-torch-baseline --train-steps 0 --no-split-leg --no-other-configs"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python bench.py --steps 200 --warmup 5 $Q > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 # counter passes (FETCH_SIZE, WRITE_SIZE, SQ set -- each its own run, --kernel-trace only; retried once: rocprofv3 --pmc has segfaulted
 # right after HSA initialisation on some boxes of the pool), then the same for the all-fp32-MFMA plan
@@ -28,7 +28,7 @@ python tools/torch_baseline_probe.py --config sr3_16_128 --batch 16 --steps 3 > 
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/torch_stats -o torch -- python tools/torch_baseline_probe.py --config sr3_16_128 --batch 16 --steps 5 > $OUT/torch_probe.log 2>&1
 if [ "${2:-}" != "--quick" ] && [ "${3:-}" != "--quick" ]; then
   # the multi-rank entry paths on this 1-GPU box: collective path forced on one rank and the launcher form the driver uses
-  D="--steps 20 --warmup 3 --train-steps 2 --no-cpu-baseline --no-torch-baseline --no-roofline --no-other-configs"
+  D="--full --steps 20 --warmup 3 --train-steps 2 --no-cpu-baseline --no-torch-baseline --no-roofline --no-other-configs"
   SR3_BENCH_FORCE_DIST=1 python bench.py --gpus 1 $D > $OUT/bench_force_dist.json 2> $OUT/bench_force_dist.err; echo "force_dist rc=$?"
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 $D > $OUT/bench_torchrun1.json 2> $OUT/bench_torchrun1.err; echo "torchrun rc=$?"
 fi
