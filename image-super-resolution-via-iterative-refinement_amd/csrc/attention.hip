@@ -469,12 +469,23 @@ int launch_attention_v2(const float* qkv, int B, int N, int C, int zsplit, float
 }
 }  // namespace
 
+namespace {
+inline bool attention_v2_fits(int N, int C) { return (N & 31) == 0 && N <= 1024 && (C % 128) == 0; }
+// LDS bytes of k_attention<nstage> for N tokens (score strip + staging buffers)
+inline size_t attention_v1_smem(int N, int nstage) { return ((size_t)32 * (((N + 31) & ~31) + 4) + (size_t)nstage * AT_STAGE) * sizeof(float); }
+}  // namespace
+
+bool attention_fits(int N, int C) {
+  if (N <= 0 || (C & 3)) return false;
+  return attention_v2_fits(N, C) || attention_v1_smem(N, 1) <= 160 * 1024;
+}
+
 int attention_forward(const float* qkv, int B, int N, int C, float* out, hipStream_t st, int split) {
   if (C & 3) { set_error("attention: C %% 4 != 0"); return SR3_E_UNSUPPORTED; }
   if ((double)B * N * 3.0 * C >= 2147483647.0) { set_error("attention: qkv exceeds 2^31 elements"); return SR3_E_UNSUPPORTED; }
   // the staging-free kernel wherever the shape allows it (SR3_ATTN_V1=1, read once: A/B knob for the profiles)
   static const bool force_v1 = [] { const char* e = getenv("SR3_ATTN_V1"); return e && e[0] == '1'; }();
-  if (!force_v1 && (N & 31) == 0 && N <= 1024 && (C % 128) == 0) {
+  if (!force_v1 && attention_v2_fits(N, C)) {
     const int qblocks = N / 32;
     int zsplit = 1;                                       // channel split of phase 3 (each split recomputes the score strip)
     while ((long)qblocks * B * zsplit < 256 && (C / (zsplit * 2)) % 128 == 0 && zsplit < 4) zsplit *= 2;
@@ -490,11 +501,9 @@ int attention_forward(const float* qkv, int B, int N, int C, float* out, hipStre
     if (tn == 2) return launch_attention_v2<1, 2>(qkv, B, N, C, zsplit, out, st, split != 0);
     return launch_attention_v2<1, 1>(qkv, B, N, C, zsplit, out, st, split != 0);
   }
-  const int Npad = (N + 31) & ~31;
-  const size_t strip = (size_t)32 * (Npad + 4);
   int nstage = 2;
-  size_t smem = (strip + 2 * (size_t)AT_STAGE) * sizeof(float);
-  if (smem > 160 * 1024) { nstage = 1; smem = (strip + (size_t)AT_STAGE) * sizeof(float); }
+  size_t smem = attention_v1_smem(N, 2);
+  if (smem > 160 * 1024) { nstage = 1; smem = attention_v1_smem(N, 1); }
   if (smem > 160 * 1024) { set_error("attention: N=%d does not fit the LDS score strip", N); return SR3_E_UNSUPPORTED; }
   const int qblocks = (N + 31) / 32;
   const int npan = (C + 127) / 128;

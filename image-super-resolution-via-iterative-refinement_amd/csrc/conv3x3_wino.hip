@@ -1036,15 +1036,17 @@ bool wino_geometry(const ConvParams& p, WinoGeom* g) {
   const int H = p.Ho, W = p.Wo;
   if (H != (p.Hs << p.ups) || W != (p.Ws << p.ups)) return false;
   // four whole 8 x 8 images per workgroup tile (split-K only: at least two 16-channel chunks)
-  const bool nb4 = H == 8 && W == 8 && p.ups == 0 && (p.B % 4) == 0 && p.C0 + p.C1 > WCK;
-  // wino_split == 2: the 8 x 16 pixel tile of conv3x3_wino2.hip (two four-wave workgroups per CU)
-  const bool w2 = p.wino_split == 2;
-  if (w2 && !wino2_fits(p)) return false;
+  // wino_split == 2: the 8 x 16 pixel tile of conv3x3_wino2.hip (two four-wave workgroups per CU); 3: its ragged form (any map size: the
+  // tile grid is rounded up, the kernel masks the overhang)
+  const bool w2r = p.wino_split == 3;
+  const bool w2 = p.wino_split == 2 || w2r;
+  const bool nb4 = !w2r && H == 8 && W == 8 && p.ups == 0 && (p.B % 4) == 0 && p.C0 + p.C1 > WCK;
+  if (w2r ? !wino2_ragged_fits(p) : (w2 && !wino2_fits(p))) return false;
   if (!w2 && !nb4 && (W < 16 || (W % 16) != 0 || (H % 16) != 0)) return false;
   g->TH = (nb4 || w2) ? 8 : 16; g->TW = nb4 ? 8 : 16; g->NB = nb4 ? 4 : 1;
   g->twt = 8; g->log_twt = 3;
   g->tpi = nb4 ? 16 : (w2 ? 32 : 64); g->log_tpi = nb4 ? 4 : (w2 ? 5 : 6);
-  g->tiles_w = nb4 ? 1 : W / 16; g->tiles_h = nb4 ? 1 : H / g->TH;
+  g->tiles_w = nb4 ? 1 : (W + 15) / 16; g->tiles_h = nb4 ? 1 : (H + g->TH - 1) / g->TH;     // (only the ragged form has a remainder)
   g->nbt = nb4 ? p.B / 4 : p.B;
   g->HPI = nb4 ? 100 : (w2 ? 180 : WHP);
   g->HP = nb4 ? 400 : (w2 ? 180 : WHP);
@@ -1097,7 +1099,7 @@ int conv3x3_wino_forward(const ConvParams& p, const float* ufrag, hipStream_t st
   if (g.NB != 1) { set_error("conv: the Winograd ablations cover the one-image tile only"); return SR3_E_BADARG; }    \
   SR3_WINO_LAUNCH3(D, false, false)
   if (p.drop_thresh != 0 && dbg != 0) { set_error("conv: the Winograd ablations have no dropout form"); return SR3_E_BADARG; }
-  if (p.wino_split == 2) return conv3x3_wino2_forward(p, g, ufrag, st);
+  if (p.wino_split >= 2) return conv3x3_wino2_forward(p, g, ufrag, st);
   if (p.wino_split && g.NB != 1 && p.drop_thresh != 0) {
     set_error("conv: the split-bf16 four-image Winograd tile has no dropout form");
     return SR3_E_UNSUPPORTED;

@@ -17,6 +17,9 @@
 // Workgroup tile: 32 Winograd tiles = 8 x 16 output pixels of one image (raw halo 10 x 18) x 64 output channels x all 16 positions.
 // The price is the filter traffic from L2 (a U fragment serves 32 tiles instead of 64); U never goes through LDS, as before.
 // One-image tile, maps >= 16 wide and a multiple of 8 high, no dropout form: everything else stays on conv3x3_wino.hip.
+// RAGGED instantiation (ConvParams::wino_split == 3, tile_cfg 23 at the ABI): the same kernel on maps of ANY size -- the tile grid is
+// ceil(W / 16) x ceil(H / 8), overhanging tile rows / columns read zeros (the staging's padding rule) and the epilogue masks every
+// pixel it stores, adds as a residual or counts in the statistics.  The arithmetic of a pixel that exists is the same.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -66,7 +69,7 @@ __device__ __forceinline__ float silu_v(float v) {      // (conv3x3_wino.hip: si
 // the 3-way split.
 // Global loads outside the main loop are unconditional and consumed in issue order (absent operands: a valid dummy address,
 // discarded by a select) -- the in-order vmcnt rule of conv3x3_wino.hip.
-template <int DBG>
+template <int DBG, bool RAGGED = false>
 __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, const WinoGeom g, const __bf16* __restrict__ ufrag) {
   extern __shared__ f32x4 smem_w2[];
   float* smem = reinterpret_cast<float*>(smem_w2);
@@ -423,6 +426,15 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
     const int ety = tq >> 1, etx0 = (tq & 1) * 4;
     const int e_cb = cb, e_b0 = b0, e_tix = th_i * g.tiles_w + tw_i, e_vtile = vtile;
     const size_t pix0 = ((size_t)b0 * H + (h0 + 2 * ety + fp)) * W + (w0 + 2 * etx0 + fq);   // tile k of the four: + 2 k pixels
+    // RAGGED: bit k = pixel k of the four exists (the tile may overhang the map to the right and below)
+    int pmask = 15;
+    if constexpr (RAGGED) {
+      const int ey = h0 + 2 * ety + fp, ex = w0 + 2 * etx0 + fq;
+      pmask = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) pmask |= (ey < H && ex + 2 * k < W) ? (1 << k) : 0;
+    }
+    auto pix_ok = [&](int k) { return !RAGGED || ((pmask >> k) & 1) != 0; };
     const bool has_next = vtile + (int)gridDim.x < ntiles;
     if (has_next) vtile += gridDim.x;
     // this tile's residual, both rounds: 8 loads (absent: a valid dummy address, discarded below)
@@ -433,7 +445,7 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
       const int ne = n < p.Cout ? n : 0;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const size_t pix = pix0 + 2 * k;
+        const size_t pix = pix_ok(k) ? pix0 + 2 * k : 0;           // (a pixel that does not exist: pixel 0, discarded below)
         const float* rp = dst + pix * p.Cout + ne;
         if (has_res) rp = (ne < p.RC0) ? p.res0 + pix * p.RC0 + ne : p.res1 + pix * p.RC1 + (ne - p.RC0);
         addv[nblk][k] = *reinterpret_cast<const f32x4*>(rp);
@@ -511,12 +523,12 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
           if (direct) {
             v += base[nblk];
             if (has_res) v += addv[nblk][k];
-            if (stats) {
+            if (stats && pix_ok(k)) {
 #pragma unroll
               for (int c = 0; c < 4; ++c) { const double dv = (double)v[c]; s1[nblk][c] += dv; s2[nblk][c] += dv * dv; }
             }
           }
-          if (nok) *reinterpret_cast<f32x4*>(dst + (pix0 + 2 * k) * p.Cout + n) = v;
+          if (nok && pix_ok(k)) *reinterpret_cast<f32x4*>(dst + (pix0 + 2 * k) * p.Cout + n) = v;
         }
       }
       if (nblk == 0) store_consts(cst + (par ^ 1) * VCST_F);      // ... and the constants go to LDS (the other parity)
@@ -562,6 +574,10 @@ bool wino2_fits(const ConvParams& p) {
   return p.ksize == 3 && p.stride == 1 && p.Ho == (p.Hs << p.ups) && p.Wo == (p.Ws << p.ups) && p.Wo >= 16 && (p.Wo % 16) == 0 &&
          (p.Ho % 8) == 0 && p.drop_thresh == 0;
 }
+// the RAGGED instantiation: every wino2_fits condition except the divisibility ones
+bool wino2_ragged_fits(const ConvParams& p) {
+  return p.ksize == 3 && p.stride == 1 && p.Ho == (p.Hs << p.ups) && p.Wo == (p.Ws << p.ups) && p.Ho >= 1 && p.Wo >= 1 && p.drop_thresh == 0;
+}
 
 int conv3x3_wino2_forward(const ConvParams& p, const WinoGeom& g, const float* ufrag, hipStream_t st) {
   if (g.NB != 1 || g.TH != 8 || p.drop_thresh != 0) { set_error("conv: the two-workgroup Winograd kernel covers the one-image 8 x 16 tile without dropout"); return SR3_E_UNSUPPORTED; }
@@ -585,6 +601,14 @@ int conv3x3_wino2_forward(const ConvParams& p, const WinoGeom& g, const float* u
     static std::atomic<uint64_t> done{0};                                                                             \
     if (int rc = ensure_max_lds(reinterpret_cast<const void*>(k_conv3x3_wino2<D>), 100 * 1024, done)) return rc;      \
     hipLaunchKernelGGL((k_conv3x3_wino2<D>), grid, dim3(VNT), lds_bytes, st, p, g, reinterpret_cast<const __bf16*>(ufrag)); \
+  }
+  if (p.wino_split == 3) {
+    if (dbg != 0) { set_error("conv: the ragged two-workgroup Winograd kernel has no ablation builds (SR3_WINO_DBG=%d)", dbg); return SR3_E_BADARG; }
+    static std::atomic<uint64_t> done{0};
+    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(k_conv3x3_wino2<0, true>), 100 * 1024, done)) return rc;
+    hipLaunchKernelGGL((k_conv3x3_wino2<0, true>), grid, dim3(VNT), lds_bytes, st, p, g, reinterpret_cast<const __bf16*>(ufrag));
+    SR3_LAUNCH_CHECK("k_conv3x3_wino2 (ragged)");
+    return SR3_OK;
   }
   switch (dbg) {
     case 0: SR3_W2_LAUNCH(0) break;

@@ -558,7 +558,7 @@ void conv_pick(const ConvParams& p, int& tile_cfg, int& ksplit) {
     const long tiles = wino_workgroups(p, wg);
     const int units = wino_chunks(p);
     const int maxck = wino_max_chunks_per_split(wg);
-    const long round = p.wino_split == 2 ? 512 : 256;
+    const long round = p.wino_split >= 2 ? 512 : 256;
     // (tried in round 6: no split from half a round on for the 8 x 16 tile -- 11 reduce launches fewer, the convs 0.13-0.24 ms slower:
     // a wash, profiles/r06_wino2_experiments.txt)
     int ks = 1;

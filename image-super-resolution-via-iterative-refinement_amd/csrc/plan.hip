@@ -280,6 +280,17 @@ struct Arena {
   }
 };
 
+// Does the RAGGED two-workgroup Winograd tile (tile_cfg 23) beat the kernel this conv would otherwise land on?  Measured inside the
+// forward of the SR3 16 -> 128 network, conv + reduce + statistics + fold against the same group on the fallback kernels
+// (profiles/geometry_wino_ragged_probe.txt): 0.24-0.57 of the fallback's time on every map that fills at
+// least a third of its rounded-up tile grid (8x12: 75 %, 44x32: 92 %, 22x16: 69 %, 11x8: 34 %, 8x8 upsampled: 50 %), 1.2-1.27 of it
+// on the 4x4 maps (12.5 %: seven eighths of every tile is padding, and the im2col kernel under 16-way split-K is not slower
+// there).  Nothing was measured between 12.5 % and 34 %: the threshold sits in the gap, at a quarter.
+static bool wino_ragged_wins(const ConvParams& c) {
+  const long padded = (long)((c.Ho + 7) / 8 * 8) * ((c.Wo + 15) / 16 * 16);
+  return 4L * c.Ho * c.Wo >= padded;
+}
+
 struct Builder {
   sr3_plan* P;
   int B;
@@ -391,13 +402,23 @@ struct Builder {
   // every 3x3 stride-1 conv the Winograd kernel covers runs on it (plan option `winograd`, default on), train-mode dropout
   // convs included; an explicit tile_cfg / split_bf16 keep the direct halo kernels (the fused res_conv segment has no
   // Winograd form: res_conv is then its own 1x1 GEMM)
-  bool wino_ok(const ConvParams& c, size_t w, bool has_x2, bool has_drop) {
-    if (!P->winograd || P->tile_cfg != 0 || P->split_bf16 || has_x2) return false;
-    if (has_drop && (c.C1 != 0 || c.ups != 0 || c.act == 0)) return false;    // the dropout form: single source, no upsampling
-    if (c.ksize != 3 || c.stride != 1 || !P->derived_of.count(w)) return false;
+  // 1: the tiles of today's rules (wino_geometry of the 8-wave kernel decides; Builder::conv then picks the instantiation);
+  // 2: only at a geometry other than image_size x image_size (so the native launch list never moves), inference plans: a map the rule
+  // above refuses on the two-workgroup kernel -- its plain form where the map is a whole multiple of the 8 x 16 tile, its RAGGED form
+  // (plan option wino_ragged) where wino_ragged_wins says the padded tile beats the fallback
+  int wino_mode(const ConvParams& c, size_t w, bool has_x2, bool has_drop) {
+    if (!P->winograd || P->tile_cfg != 0 || P->split_bf16 || has_x2) return 0;
+    if (has_drop && (c.C1 != 0 || c.ups != 0 || c.act == 0)) return 0;    // the dropout form: single source, no upsampling
+    if (c.ksize != 3 || c.stride != 1 || !P->derived_of.count(w)) return 0;
     WinoGeom wg;
-    return wino_geometry(c, &wg);
+    if (wino_geometry(c, &wg)) return 1;
+    if (train || has_drop || plan_native_geometry(P) || !P->wino_split || !P->wino2) return 0;
+    ConvParams r = c;
+    r.wino_split = wino2_fits(c) ? 2 : 3;
+    if (r.wino_split == 3 && !(P->wino_ragged && wino_ragged_wins(c))) return 0;
+    return wino_geometry(r, &wg) ? 2 : 0;
   }
+  bool wino_ok(const ConvParams& c, size_t w, bool has_x2, bool has_drop) { return wino_mode(c, w, has_x2, has_drop) != 0; }
   // generic conv over the virtual concat (x0|x1); residual is the concat view (r0|r1)
   int conv(int x0, int x1, int Cout, int ksize, int stride, int ups, int act_mode, size_t w, bool has_bias,
            size_t bias, int film_row, int r0, int r1, bool want_stats, int q0 = -1, int q1 = -1, size_t qw = 0,
@@ -431,6 +452,11 @@ struct Builder {
       if (P->split_bf16 && !train && o.tile_cfg == 0 && ksize == 3 && stride == 1 && Cout > 64 && halo_geometry(c, 10, &sg))
         o.tile_cfg = 10;
     }
+    if (wino_mode(c, w, q0 >= 0, o.has_drop) == 2) {
+      o.tile_cfg = 11;
+      c.wino_split = wino2_fits(c) ? 2 : 3;
+      o.wino_off = P->derived_of[w] + wino_weight_floats(Cout, C0 + C1);
+    } else
     if (wino_ok(c, w, q0 >= 0, o.has_drop)) {
       o.tile_cfg = 11;
       o.wino_off = P->derived_of[w];
@@ -558,6 +584,7 @@ struct Builder {
     // 1024-channel res_conv at 8x8: measured 43 TF): small-M layers keep res_conv as its own 1x1 GEMM
     return cfg >= 5 && ks == 1;
   }
+  std::string refused;     // inference: the first layer no kernel can run at this geometry (build_forward refuses the plan with it)
   int n_side = 0;          // plan option fork_side: ops handed to the side stream so far (Op::side_id)
   int res_block(int x0, int x1, const ResLayer& R) {
     fold(x0, x1, R.gn1_w, R.gn1_b);
@@ -593,6 +620,12 @@ struct Builder {
       const int o = make(R.cout, T[out].H, T[out].W);
       Op a; a.kind = OP_ATTN;
       a.a = T[qkv].off; a.b = T[o].off; a.i0 = T[out].H * T[out].W; a.i1 = R.cout;
+      if (!train && refused.empty() && !attention_fits(a.i0, R.cout)) {
+        char msg[256];
+        snprintf(msg, sizeof(msg), "attention of %s: the %d x %d level has %d tokens, more than the attention kernel holds in LDS", R.name.c_str(),
+                 T[out].H, T[out].W, a.i0);
+        refused = msg;
+      }
       ops.push_back(a);
       if (train) { Rec r; r.kind = R_ATTN; r.qkv = qkv; r.o = o; P->recs.push_back(r); }
       flops += 4.0 * B * (double)a.i0 * (double)a.i0 * R.cout;
@@ -611,7 +644,8 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
   const sr3_unet_desc& d = P->d;
   std::vector<Op>& ops = bld.ops;
   const int B = bld.B;
-  const int S = d.image_size, inner = d.inner_channel;
+  const int inner = d.inner_channel;
+  const int IH = bld.train ? d.image_size : plan_height(P), IW = bld.train ? d.image_size : plan_width(P);   // (training: native geometry only)
 
   { Op o; o.kind = OP_EMBED; ops.push_back(o); }
   bld.flops += 2.0 * B * (2.0 * 4 * inner * inner + (double)P->F * inner);
@@ -623,17 +657,17 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
   int cur = -1;
   for (auto& L : P->downs) {
     if (L.kind == 0) {
-      cur = bld.make(L.cout, S, S);
+      cur = bld.make(L.cout, IH, IW);
       Op o; o.kind = OP_CONV_IN;
       o.e = bld.T[cur].off; o.p0 = L.w; o.p1 = L.b;
-      o.i0 = d.in_channel - cond_channels; o.i1 = cond_channels; o.i2 = L.cout; o.i3 = S;
-      if (const int slices = P->fuse_stats ? conv_in_stat_slices(d.in_channel, S, S, L.cout) : 0) {
+      o.i0 = d.in_channel - cond_channels; o.i1 = cond_channels; o.i2 = L.cout; o.i3 = IH; o.i4 = IW;
+      if (const int slices = P->fuse_stats ? conv_in_stat_slices(d.in_channel, IH, IW, L.cout) : 0) {
         bld.stat_slot(cur, slices);          // the MFMA form writes the GroupNorm partials of its output itself
         o.has_ostat = true; o.f = bld.T[cur].stat_off;
       }
       ops.push_back(o);
       if (bld.train) { Rec r; r.kind = R_CONV_IN; r.out = cur; r.w = L.w; r.bias = L.b; P->recs.push_back(r); }
-      bld.flops += 2.0 * B * S * S * (double)L.cout * L.cin * 9;
+      bld.flops += 2.0 * B * IH * IW * (double)L.cout * L.cin * 9;
     } else if (L.kind == 1) {
       cur = bld.res_block(cur, -1, L.res);   // the input stays alive: it is a skip feature
     } else {
@@ -669,7 +703,7 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
   bld.fold(cur, -1, P->fin_gn_w, P->fin_gn_b);
   {
     Op o; o.kind = OP_CONV_OUT;
-    o.a = bld.T[cur].off; o.p0 = P->fin_w; o.p1 = P->fin_b; o.i0 = bld.T[cur].C; o.i1 = P->out_ch; o.i2 = S;
+    o.a = bld.T[cur].off; o.p0 = P->fin_w; o.p1 = P->fin_b; o.i0 = bld.T[cur].C; o.i1 = P->out_ch; o.i2 = IH; o.i3 = IW;
     o.ss_rel = bld.cur_ss;
     ops.push_back(o);
     if (bld.train) {
@@ -677,7 +711,7 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
       r.ss_off = bld.cur_ss; r.mr_off = bld.cur_mr; r.act = 2;
       P->recs.push_back(r);
     }
-    bld.flops += 2.0 * B * S * S * (double)P->out_ch * bld.T[cur].C * 9;
+    bld.flops += 2.0 * B * IH * IW * (double)P->out_ch * bld.T[cur].C * 9;
   }
 }
 
@@ -727,15 +761,23 @@ void layout_derived(sr3_plan* P) {
 }
 
 static int build_forward(sr3_plan* P, int B, int cond_channels) {
-  if (P->built_batch == B && P->built_cond == cond_channels) return SR3_OK;
+  if (P->built_batch == B && P->built_cond == cond_channels && P->built_h == plan_height(P) && P->built_w == plan_width(P)) return SR3_OK;
   const sr3_unet_desc& d = P->d;
   if (B <= 0) { set_error("batch must be > 0"); return SR3_E_BADARG; }
   if (cond_channels < 0 || cond_channels >= d.in_channel) { set_error("cond_channels %d out of range (in_channel %d)", cond_channels, d.in_channel); return SR3_E_BADARG; }
   P->ops.clear();
   P->taps.clear();
+  P->built_batch = -1;
   Builder bld(P, B);
   const int inner = d.inner_channel;
   walk_forward(P, bld, cond_channels);
+  if (!bld.refused.empty()) {
+    // a geometry no kernel can run is refused HERE, when the launch list is built: never after a launch has been enqueued
+    set_error("geometry %d x %d unsupported: %s", plan_height(P), plan_width(P), bld.refused.c_str());
+    P->ops.clear();
+    P->taps.clear();
+    return SR3_E_UNSUPPORTED;
+  }
   if (P->fork_side && !P->ops.empty() && P->ops[0].kind == OP_EMBED) {
     // ... and the embedding MLP + FiLM projections (first op, reads only the noise level): beside the input conv, joined by the first conv that
     // adds a FiLM row
@@ -756,6 +798,7 @@ static int build_forward(sr3_plan* P, int B, int cond_channels) {
   P->flops = bld.flops;
   P->built_batch = B;
   P->built_cond = cond_channels;
+  P->built_h = plan_height(P); P->built_w = plan_width(P);
   return SR3_OK;
 }
 
@@ -831,7 +874,7 @@ int run_forward(sr3_plan* P, const Regions& R, const float* x, const float* cond
         const int Ca = cond_channels > 0 ? cond_channels : o.i0;
         const float* b = cond_channels > 0 ? x : nullptr;
         const int Cb = cond_channels > 0 ? o.i0 : 0;
-        rc = conv_in_nchw(a, Ca, b, Cb, B, o.i3, o.i3, params + o.p0, params + o.p1, o.i2,
+        rc = conv_in_nchw(a, Ca, b, Cb, B, o.i3, o.i4, params + o.p0, params + o.p1, o.i2,
                           reinterpret_cast<float*>(ws + o.e),
                           o.has_ostat ? reinterpret_cast<double*>(ws + R.stats_off + o.f) : nullptr, st);
         break;
@@ -902,7 +945,7 @@ int run_forward(sr3_plan* P, const Regions& R, const float* x, const float* cond
         break;
       case OP_CONV_OUT:
         rc = conv_out_nchw(reinterpret_cast<const float*>(ws + o.a), reinterpret_cast<const float*>(ws + R.ss_off + o.ss_rel),
-                           B, o.i2, o.i2, o.i0, params + o.p0, params + o.p1, o.i1, eps_out, st, fuse);
+                           B, o.i2, o.i3, o.i0, params + o.p0, params + o.p1, o.i1, eps_out, st, fuse);
         break;
     }
     if (rc) return rc;
@@ -918,6 +961,11 @@ int run_forward(sr3_plan* P, const Regions& R, const float* x, const float* cond
 // a gradient mirror of the activation arena, and the scratch the backward walk needs
 // ---------------------------------------------------------------------------------------------
 int build_train(sr3_plan* P, int B, int cond_channels) {
+  if (!plan_native_geometry(P)) {
+    set_error("training runs at image_size x image_size only: the plan's geometry is %d x %d (sr3_plan_set_geometry(plan, 0, 0) restores %d x %d)",
+              plan_height(P), plan_width(P), P->d.image_size, P->d.image_size);
+    return SR3_E_UNSUPPORTED;
+  }
   if (P->train_batch == B && P->train_cond == cond_channels) return SR3_OK;
   const sr3_unet_desc& d = P->d;
   if (B <= 0) { set_error("batch must be > 0"); return SR3_E_BADARG; }
@@ -1125,7 +1173,7 @@ int sr3_plan_op_info(sr3_plan* plan, int batch, int index, sr3_op_info* out) {
   out->kind = (int)o.kind * 10;
   if (o.kind == OP_CONV) {
     const ConvParams& c = o.cp;
-    out->tile_cfg = (o.tile_cfg == 11 && o.cp.wino_split) ? 11 + o.cp.wino_split
+    out->tile_cfg = (o.tile_cfg == 11 && o.cp.wino_split == 3) ? 23 : (o.tile_cfg == 11 && o.cp.wino_split) ? 11 + o.cp.wino_split
                     : (o.tile_cfg >= 1 && o.tile_cfg <= 4 && o.cp.igemm_split) ? (o.has_wsplit ? 17 : 13) + o.tile_cfg : o.tile_cfg;
     out->ksplit = o.ksplit;
     out->ksize = c.ksize; out->stride = c.stride; out->upsample = c.ups;
@@ -1134,7 +1182,7 @@ int sr3_plan_op_info(sr3_plan* plan, int batch, int index, sr3_op_info* out) {
     out->fused_output_stats = o.has_ostat ? 1 : 0;
     out->flops = 2.0 * c.B * c.Ho * c.Wo * (double)c.Cout * ((double)out->cin * c.ksize * c.ksize + out->fused_res_conv_cin);
   } else if (o.kind == OP_CONV_IN) {
-    out->ksize = 3; out->stride = 1; out->cin = o.i0 + o.i1; out->cout = o.i2; out->h_out = out->w_out = o.i3;
+    out->ksize = 3; out->stride = 1; out->cin = o.i0 + o.i1; out->cout = o.i2; out->h_out = o.i3; out->w_out = o.i4;
     out->fused_output_stats = o.has_ostat ? 1 : 0;
   } else if (o.kind == OP_ATTN) {
     out->h_out = o.i0; out->cin = out->cout = o.i1;          // tokens, channels
@@ -1181,6 +1229,7 @@ int sr3_plan_set_option(sr3_plan* plan, const char* key, int value) {
   else if (!strcmp(key, "fold_fuse")) slot = &plan->fold_fuse;
   else if (!strcmp(key, "gemm_tile")) slot = &plan->gemm_tile;
   else if (!strcmp(key, "wino2")) slot = &plan->wino2;
+  else if (!strcmp(key, "wino_ragged")) slot = &plan->wino_ragged;
   else if (!strcmp(key, "loss_l2")) { const int prev = plan->loss_l2; plan->loss_l2 = value; return prev; }   // no rebuild
   if (!slot) { set_error("unknown option %s", key); return SR3_E_BADARG; }
 #ifndef SR3_EXPERIMENTS
@@ -1244,6 +1293,30 @@ int sr3_plan_prepare_derived(sr3_plan* plan, const float* params, void* stream) 
     if (rc) return rc;
   }
   plan->derived_from = params;
+  return SR3_OK;
+}
+
+int sr3_plan_set_geometry(sr3_plan* plan, int height, int width) {
+  if (!plan) { set_error("null plan"); return SR3_E_BADARG; }
+  const int div = 1 << (plan->d.n_mults - 1);
+  if (height == 0 && width == 0) {
+    height = width = plan->d.image_size;
+  } else if (height <= 0 || width <= 0 || (height % div) || (width % div)) {
+    set_error("geometry %d x %d: height and width must be positive multiples of %d (2^(n_mults-1): the UNet halves the image %d times)",
+              height, width, div, plan->d.n_mults - 1);
+    return SR3_E_BADARG;
+  }
+  const bool native = height == plan->d.image_size && width == plan->d.image_size;
+  const int h = native ? 0 : height, w = native ? 0 : width;
+  if (h == plan->geo_h && w == plan->geo_w) return SR3_OK;
+  plan->geo_h = h; plan->geo_w = w;
+  plan->built_batch = -1;            // the launch list is rebuilt; the derived filters do not depend on the geometry
+  return SR3_OK;
+}
+int sr3_plan_get_geometry(const sr3_plan* plan, int* height, int* width) {
+  if (!plan) { set_error("null plan"); return SR3_E_BADARG; }
+  if (height) *height = plan_height(plan);
+  if (width) *width = plan_width(plan);
   return SR3_OK;
 }
 
@@ -1342,6 +1415,7 @@ int sr3_unet_forward_profile(sr3_plan* plan, const float* x_nchw, const float* c
           else
           kind += base[(o.tile_cfg == 11 && o.cp.wino_split) ? 12 : o.tile_cfg] + ((o.tile_cfg >= 5 && o.has_x2) ? 2 : 0);
           if (o.tile_cfg == 11 && o.cp.wino_split == 2) kind += 20;                         // 575: the two-workgroups-per-CU split kernel (conv3x3_wino2.hip)
+          if (o.tile_cfg == 11 && o.cp.wino_split == 3) kind += 30;                         // 585: ... its ragged instantiation
           if (o.tile_cfg >= 1 && o.tile_cfg <= 4 && o.cp.igemm_split) kind += 600;           // 651-654: the im2col tiles on their 3 x bf16 split instantiation
           WinoGeom wg;
           if (o.tile_cfg == 11 && wino_geometry(o.cp, &wg) && wg.NB != 1) kind += 10;      // 465: the four-image 8x8 tile
@@ -1406,8 +1480,8 @@ int sr3_conv_f32(const float* src0, int C0, const float* src1, int C1, int B, in
   c.Cout = Cout; c.w = w; c.bias = bias; c.ss = ss; c.act = act; c.film = film; c.film_stride = film_stride;
   c.res0 = res0; c.res1 = res1; c.RC0 = res0 ? RC0 : 0; c.RC1 = res1 ? RC1 : 0;
   c.out = out; c.ostat = out_stats; c.ksplit = 1;
-  const bool wsplit = tile_cfg == 12 || tile_cfg == 13;     // tile 11 on the 3 x bf16 split instantiation (13: the 8 x 16 tile of conv3x3_wino2.hip)
-  if (wsplit) { c.wino_split = tile_cfg - 11; tile_cfg = 11; }
+  const bool wsplit = tile_cfg == 12 || tile_cfg == 13 || tile_cfg == 23;     // tile 11 on the 3 x bf16 split instantiation (13: the 8 x 16 tile of conv3x3_wino2.hip; 23: its ragged form)
+  if (wsplit) { c.wino_split = tile_cfg == 23 ? 3 : tile_cfg - 11; tile_cfg = 11; }
   if (tile_cfg >= 14 && tile_cfg <= 17) { c.igemm_split = 1; tile_cfg -= 13; }     // the im2col tiles 1-4 on their 3 x bf16 split instantiation
   if (tile_cfg >= 18 && tile_cfg <= 22) {
     // ... with the weights pre-split into bf16 planes (what a plan does, in its derived buffer): derived here, behind the split-K
@@ -1505,8 +1579,9 @@ size_t sr3_conv_scratch_bytes(int B, int Ho, int Wo, int Cin, int Cout, int ksiz
   ConvParams c;
   memset(&c, 0, sizeof(c));
   c.B = B; c.Ho = Ho; c.Wo = Wo; c.C0 = Cin; c.Cout = Cout; c.ksize = ksize;
-  if (tile_cfg >= 11 && tile_cfg <= 13) {      // Winograd: the geometry (hence the split) needs the stride-1 input dims; + the derived filters
+  if ((tile_cfg >= 11 && tile_cfg <= 13) || tile_cfg == 23) {      // Winograd: the geometry (hence the split) needs the stride-1 input dims; + the derived filters
     c.Hs = Ho; c.Ws = Wo; c.stride = 1;
+    if (tile_cfg == 23) c.wino_split = 3;      // (the ragged tile grid decides the automatic split)
     return conv_splitk_bytes(c, 11, ksplit) + wino_weight_floats(Cout, Cin, tile_cfg >= 12) * sizeof(float);
   }
   size_t extra = 0;
@@ -1538,6 +1613,7 @@ int sr3_conv_stats_slices(int B, int Hs, int Ws, int ups, int Cin, int Cout, int
   c.B = B; c.Hs = Hs; c.Ws = Ws; c.ups = ups; c.stride = 1; c.ksize = 3; c.Ho = Hs << ups; c.Wo = Ws << ups;
   c.Cout = Cout; c.C0 = Cin;
   if (tile_cfg == 12 || tile_cfg == 13) { c.wino_split = tile_cfg - 11; tile_cfg = 11; }     // (13: the 8 x 16 tile, its own slice count)
+  if (tile_cfg == 23) { c.wino_split = 3; tile_cfg = 11; }                                    // (its ragged form: ceil tile grid)
   if (tile_cfg >= 14 && tile_cfg <= 17) { c.igemm_split = 1; tile_cfg -= 13; }
   if (tile_cfg >= 18 && tile_cfg <= 21) { c.igemm_split = 1; tile_cfg -= 17; }
   conv_pick(c, tile_cfg, ksplit);

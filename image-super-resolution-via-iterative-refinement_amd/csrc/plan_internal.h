@@ -139,6 +139,10 @@ struct sr3_plan {
                              // round 6: the three launches of the C2 forward 171 -> 118 us)
   int gemm_n64 = 1;          // ... and the layers with Cout % 128 != 0 (Cout % 64 == 0: the res_convs of the 128 x 128 level, Downsample 64 -> 64) on
                              // its 64-column tile (waves 2 x 2); 0: they keep the im2col kernel
+  int wino_ragged = 1;       // inference plans at a geometry other than image_size x image_size: 3x3 stride-1 convs on maps that are not whole
+                             // multiples of the 8 x 16 tile on the two-workgroup kernel's RAGGED instantiation (tile_cfg 23) where the measured rule
+                             // (wino_ragged_wins, plan.hip) says so; 0: they fall back to the general kernels (A/B knob)
+  int geo_h = 0, geo_w = 0;  // sr3_plan_set_geometry: image height / width of the next forward (0: image_size)
   int fork_side = 0;         // res_conv (and the embedding MLP) on a side stream beside block1's conv: see Op::side_id; A/B knob
   hipStream_t side_stream = nullptr;          // fork_side: created at the first forked forward, on the device current then
   std::vector<hipEvent_t> fork_ev, join_ev;   // one pair per forked op of the compiled forward
@@ -163,6 +167,7 @@ struct sr3_plan {
   // compiled forward
   int built_batch = -1;
   int built_cond = -1;
+  int built_h = 0, built_w = 0;
   std::vector<Op> ops;
   std::vector<Tap> taps;
   size_t ws_bytes = 0;
@@ -188,6 +193,9 @@ struct sr3_plan {
 
 namespace sr3 {
 struct Builder;
+inline int plan_height(const sr3_plan* P) { return P->geo_h > 0 ? P->geo_h : P->d.image_size; }
+inline int plan_width(const sr3_plan* P) { return P->geo_w > 0 ? P->geo_w : P->d.image_size; }
+inline bool plan_native_geometry(const sr3_plan* P) { return plan_height(P) == P->d.image_size && plan_width(P) == P->d.image_size; }
 Regions infer_regions(const sr3_plan* P);
 int run_forward(sr3_plan* P, const Regions& R, const float* x, const float* cond, int cond_channels, const float* level,
                 const int64_t* tstep, const float* freq, const float* level_table, const int* step_dev,

@@ -190,6 +190,7 @@ struct ConvParams {
   const float* wino_u;
   int wino_split;      // 1: the filters are the 3 x bf16 split form and the kernel's SPLIT instantiation runs (tile_cfg 12 at the ABI);
                        // 2: the same filters on the two-workgroups-per-CU kernel of conv3x3_wino2.hip (tile_cfg 13; 8 x 16 pixel tile)
+                       // 3: ... on that kernel's RAGGED instantiation (tile_cfg 23): maps that are not whole multiples of the tile
   int igemm_split;     // im2col kernel (tile_cfg 1-4; 1x1 and stride-2 convs): 1 = its 3 x bf16 split instantiation (tile_cfg 14-17 at the ABI)
   int wgrad_split;     // weight gradient (wgrad.hip): 1 = the one-tap-per-workgroup kernel's 3 x bf16 split instantiation for the layers with > 64 channels on both sides
   const FoldTail* fold; // host side only (conv_forward): split-K convs -- the reduce runs as k_rows_fold and does the next op's GroupNorm fold too;
@@ -266,6 +267,7 @@ int conv3x3_wino_forward(const ConvParams& p, const float* ufrag, hipStream_t st
 // the 3 x bf16 split form as two independent four-wave workgroups per CU, 8 x 16 pixel tile (conv3x3_wino2.hip; ConvParams::wino_split == 2,
 // tile_cfg 13 at the ABI; wino_geometry gives that tile's geometry when wino_split == 2)
 bool wino2_fits(const ConvParams& p);
+bool wino2_ragged_fits(const ConvParams& p);     // wino_split == 3: wino2_fits without the divisibility conditions
 int conv3x3_wino2_forward(const ConvParams& p, const WinoGeom& g, const float* ufrag, hipStream_t st);
 
 // ---- small kernels ------------------------------------------------------------------------
@@ -320,6 +322,8 @@ int embed_forward(const EmbedParams& p, hipStream_t st);
 // single-head attention over NHWC qkv [B][N][3C] -> out [B][N][C]
 // split != 0: the staging-free kernel's 3 x bf16 split instantiation where the shape takes that kernel (fp32 MFMA otherwise)
 int attention_forward(const float* qkv, int B, int N, int C, float* out, hipStream_t st, int split = 0);
+// host predicate: can attention_forward run N tokens of C channels (the kernels keep a 32-query score strip over all N keys in LDS)?
+bool attention_fits(int N, int C);
 int p_sample_update(float* x, const float* eps, const float* z, StepTables tb, const int* step_dev,
                     const int64_t* t_per_sample, int step_host, int B, int per_image, hipStream_t st, bool clip = true);
 int step_decrement(int* step_dev, hipStream_t st);

@@ -64,6 +64,7 @@ class EngineDiffusion(nn.Module):
         self.use_graph = True          # hipGraph replay of the reverse step
         self.show_progress = True
         self._loop_cache = {}
+        self.max_cached_loops = 3      # reverse-loop states (buffers + workspace + captured graph) kept, one per (shape, launch list)
         # schedule_opt is accepted and ignored exactly like the reference ctor (diffusion.py:80-82)
 
     # ---- configuration -------------------------------------------------------------------------
@@ -183,7 +184,15 @@ class EngineDiffusion(nn.Module):
                       cond=None if cond_shape is None else torch.empty(cond_shape, device=dev),
                       step=torch.zeros(2, dtype=torch.int32, device=dev), graph=None, ws=E.Workspace(),      # [scratch, t]
                       gens=[torch.Generator(device=dev) for _ in range(shape[0])] if item_streams else None)
-            self._loop_cache = {key: st}       # keep one shape alive at a time
+            # keep the states of a few image sizes alive (a folder of mixed sizes alternates between them without recapturing);
+            # what was built for another arena / schedule / set of plan options can never be hit again: dropped
+            ctx = key[2:6]
+            live = set(un.plan._geometry_generation.values())
+            kept = [(k, v) for k, v in self._loop_cache.items() if k[2:6] == ctx and k[6] in live]
+            self._loop_cache = dict(kept[-(self.max_cached_loops - 1):] if self.max_cached_loops > 1 else [])
+            self._loop_cache[key] = st
+        else:
+            self._loop_cache[key] = self._loop_cache.pop(key)      # most recently used last
         return st
 
     @staticmethod
@@ -260,6 +269,11 @@ class EngineDiffusion(nn.Module):
                 raise L.Sr3Error('p_sample_loop: %d item_seeds for a batch of %d' % (len(item_seeds), shape[0]))
             if noise_seq is not None:
                 raise L.Sr3Error('p_sample_loop: item_seeds and noise_seq exclude each other')
+        if len(shape) != 4:
+            raise L.Sr3Error('p_sample_loop: a (B, C, H, W) image or shape is expected (got %s)' % (shape,))
+        # the image size comes from the input, as in the reference (`shape = x.shape`); the launch list -- and with it
+        # plan.generation, part of the state's key -- follows it
+        self.denoise_fn.plan.set_geometry(shape[2], shape[3])
         st = self._loop_state(shape, None if cond is None else shape, dev, item_streams=item_seeds is not None)
         self.denoise_fn.ensure_derived()       # a replayed graph does not pass through EngineUNet.forward
         if item_seeds is not None:

@@ -51,7 +51,13 @@ class Plan(object):
         L.check(self.lib.sr3_plan_create(C.byref(self.desc), C.byref(h)))
         self.handle = h
         self.options = {}          # plan options set through set_option (key -> value)
-        self.generation = 0        # bumped by every set_option: part of the reverse-loop graph cache key
+        self.generation = 0        # identifies the launch list: changes with every set_option and with the geometry -- part of the
+                                   # reverse-loop graph cache key.  A geometry seen before (under the same options) gets its old value back
+        self.options_epoch = 0     # bumped by set_option only: what the derived filters depend on (the geometry does not touch them)
+        self.divisor = 1 << (len(list(channel_mults)) - 1)
+        self.geometry = (self.image_size, self.image_size)
+        self._next_generation = 1
+        self._geometry_generation = {self.geometry: 0}
         self.param_floats = int(self.lib.sr3_plan_param_floats(h))
         self.table = []
         pi = L.ParamInfo()
@@ -73,8 +79,31 @@ class Plan(object):
         if rc < 0:
             L.check(rc)
         self.options[key] = int(value)
-        self.generation += 1       # anything compiled / captured against the previous options is stale
+        # anything compiled / captured against the previous options is stale, at every geometry
+        self.generation = self._next_generation
+        self._next_generation += 1
+        self._geometry_generation = {self.geometry: self.generation}
+        self.options_epoch += 1
         return rc
+
+    def set_geometry(self, height, width):
+        """Height and width of the images the next forward / reverse step / workspace query works on (sr3_plan_set_geometry);
+        (0, 0) restores image_size x image_size.  Host only."""
+        height, width = int(height), int(width)
+        if (height, width) == (0, 0):
+            height = width = self.image_size
+        if (height, width) == self.geometry:
+            return
+        if height <= 0 or width <= 0 or height % self.divisor or width % self.divisor:
+            raise L.Sr3Error('image size %d x %d: height and width must be positive multiples of %d (the UNet halves the image %d times)'
+                             % (height, width, self.divisor, self.desc.n_mults - 1))
+        L.check(self.lib.sr3_plan_set_geometry(self.handle, height, width))
+        self.geometry = (height, width)
+        gen = self._geometry_generation.get(self.geometry)
+        if gen is None:
+            gen = self._geometry_generation[self.geometry] = self._next_generation
+            self._next_generation += 1
+        self.generation = gen
 
     def workspace_bytes(self, batch):
         n = int(self.lib.sr3_workspace_bytes(self.handle, int(batch)))
@@ -149,6 +178,11 @@ class Workspace(object):
         return self.buf[off:off + need], need
 
 
+def _check_same_size(x, cond):
+    if cond is not None and (cond.dim() != 4 or cond.shape[0] != x.shape[0] or tuple(cond.shape[2:]) != tuple(x.shape[2:])):
+        raise L.Sr3Error('conditioning image %s and input %s differ in batch or size' % (tuple(cond.shape), tuple(x.shape)))
+
+
 def reverse_step(plan, arena, freq, ws, x, z, tables, step2, cond=None, level_table=None, clip_denoised=True, eps_out=None):
     """One whole reverse step in place on `x` (sr3_reverse_step): eps = UNet(cat([cond, x], 1), level(t)); x <- p_sample update;
     t <- t - 1, with t = step2[1] (int32 tensor of two).  `tables` = (a, b, c1, c2, sigma) schedule tables on the device."""
@@ -159,9 +193,11 @@ def reverse_step(plan, arena, freq, ws, x, z, tables, step2, cond=None, level_ta
     if cond is not None:
         cond = cond.contiguous()
         cc = cond.shape[1]
-    if x.shape[1] + cc != plan.in_channel or x.shape[1] != plan.out_channel or x.shape[2] != plan.image_size or x.shape[3] != plan.image_size:
-        raise L.Sr3Error('input shape %s (+%d cond channels) does not match the plan (in_channel %d, out_channel %d, size %d)'
-                         % (tuple(x.shape), cc, plan.in_channel, plan.out_channel, plan.image_size))
+    if x.dim() != 4 or x.shape[1] + cc != plan.in_channel or x.shape[1] != plan.out_channel:
+        raise L.Sr3Error('input shape %s (+%d cond channels) does not match the plan (in_channel %d, out_channel %d)'
+                         % (tuple(x.shape), cc, plan.in_channel, plan.out_channel))
+    _check_same_size(x, cond)
+    plan.set_geometry(x.shape[2], x.shape[3])
     if step2.dtype != torch.int32 or step2.numel() != 2 or step2.device != x.device:
         raise L.Sr3Error('step2 must be two int32 on the device of x')
     wsbuf, need = ws.get(plan, B, x.device)
@@ -186,9 +222,11 @@ def unet_forward(plan, arena, freq, ws, x, cond=None, noise_level=None, timestep
         cc = cond.shape[1]
     if x.dtype != torch.float32 or (cond is not None and cond.dtype != torch.float32):
         raise L.Sr3Error('fp32 tensors expected')
-    if x.shape[1] + cc != plan.in_channel or x.shape[2] != plan.image_size or x.shape[3] != plan.image_size:
-        raise L.Sr3Error('input shape %s (+%d cond channels) does not match the plan (in_channel %d, size %d)'
-                         % (tuple(x.shape), cc, plan.in_channel, plan.image_size))
+    if x.dim() != 4 or x.shape[1] + cc != plan.in_channel:
+        raise L.Sr3Error('input shape %s (+%d cond channels) does not match the plan (in_channel %d)'
+                         % (tuple(x.shape), cc, plan.in_channel))
+    _check_same_size(x, cond)
+    plan.set_geometry(x.shape[2], x.shape[3])
     if noise_level is not None:
         noise_level = noise_level.reshape(-1).contiguous().float()
         if noise_level.numel() != B:
@@ -199,7 +237,9 @@ def unet_forward(plan, arena, freq, ws, x, cond=None, noise_level=None, timestep
             raise L.Sr3Error('timestep must have one value per sample')
     wsbuf, need = ws.get(plan, B, x.device)
     if out is None:
-        out = torch.empty(B, plan.out_channel, plan.image_size, plan.image_size, device=x.device, dtype=torch.float32)
+        out = torch.empty(B, plan.out_channel, x.shape[2], x.shape[3], device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, plan.out_channel, x.shape[2], x.shape[3]) or not out.is_contiguous():
+        raise L.Sr3Error('out must be a contiguous %s tensor (got %s)' % ((B, plan.out_channel, x.shape[2], x.shape[3]), tuple(out.shape)))
     stream = torch.cuda.current_stream(x.device).cuda_stream
     L.check(plan.lib.sr3_unet_forward(plan.handle, L.ptr(x), L.ptr(cond), cc, L.ptr(noise_level), L.ptr(timestep),
                                       L.ptr(freq), L.ptr(level_table), L.ptr(step_dev), L.ptr(arena), L.ptr(wsbuf),

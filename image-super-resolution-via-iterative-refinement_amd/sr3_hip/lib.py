@@ -71,6 +71,8 @@ SIGNATURES = {
     'sr3_plan_num_taps': (_I, [_P]),
     'sr3_plan_tap_info': (_I, [_P, _I, C.c_char_p, _I, C.POINTER(_Z), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     'sr3_workspace_bytes': (_Z, [_P, _I]),
+    'sr3_plan_set_geometry': (_I, [_P, _I, _I]),
+    'sr3_plan_get_geometry': (_I, [_P, _PI, _PI]),
     'sr3_plan_derived_bytes': (_Z, [_P]),
     'sr3_plan_bind_derived': (_I, [_P, _P, _Z]),
     'sr3_plan_prepare_derived': (_I, [_P, _P, _P]),

@@ -105,7 +105,7 @@ class EngineUNet(nn.Module):
         arena = self.arena
         if not arena.is_cuda:
             return
-        key = (arena.data_ptr(), arena._version, self._weights_epoch, self.plan.generation)
+        key = (arena.data_ptr(), arena._version, self._weights_epoch, self.plan.options_epoch)
         if key == self._derived_key:
             return
         import ctypes as C
@@ -234,6 +234,9 @@ class EngineUNet(nn.Module):
         self.ensure_derived()          # the train plan's block1 / Upsample convs run on the Winograd kernel
         B = hr.shape[0]
         plan = self.plan
+        if tuple(hr.shape[2:]) != (plan.image_size, plan.image_size):
+            raise L.Sr3Error('training runs at image_size x image_size = %d x %d only (got HR %s)' % (plan.image_size, plan.image_size, tuple(hr.shape)))
+        plan.set_geometry(0, 0)        # (a validation pass may have left the plan at another image size)
         cc = 0 if cond is None else cond.shape[1]
         need = int(plan.lib.sr3_train_workspace_bytes(plan.handle, B, cc))
         if need == 0:

@@ -99,7 +99,7 @@ int sr3_plan_op_side(sr3_plan* plan, int batch, int index, int* side_id, int* wa
 /* algorithmic FLOPs (contractions only) of one forward for `batch` images */
 double sr3_plan_forward_flops(sr3_plan* plan, int batch);
 /* tuning knobs: key in {"fuse_stats", "fuse_res", "tile_cfg", "ksplit", "keep_all", "split_bf16", "winograd",
- * "wino_split", "wino_split8", "wino2", "gemm_split", "gemm2", "gemm_s2", "gemm_n64", "fork_side", "gemm_wpre", "gemm_tile", "fold_fuse", "wgrad_split", "attn_split",
+ * "wino_split", "wino_split8", "wino2", "wino_ragged", "gemm_split", "gemm2", "gemm_s2", "gemm_n64", "fork_side", "gemm_wpre", "gemm_tile", "fold_fuse", "wgrad_split", "attn_split",
  * "loss_l2"};
  * returns previous value.
  * wino_split (default 1): the Winograd convolutions that run on the kernel's one-image tile (maps >= 16x16) use its 3 x bf16
@@ -119,6 +119,10 @@ double sr3_plan_forward_flops(sr3_plan* plan, int batch);
  *   maps >= 16 wide in an inference plan, block1 / Upsample convs and the data gradients in a training plan -- run as TWO independent
  *   four-wave workgroups per CU on an 8 x 16 pixel tile (conv3x3_wino2.hip; reported as tile 13): same arithmetic and derived filters,
  *   a wave owns one transform column and all four rows.  0: the 8-wave kernel of conv3x3_wino.hip everywhere (tile 12).
+ * wino_ragged (default 1; needs wino_split and wino2; inference plans whose geometry is not image_size x image_size, see
+ *   sr3_plan_set_geometry): 3x3 stride-1 convolutions on maps that are not whole multiples of the 8 x 16 tile run on the two-workgroup
+ *   kernel's ragged instantiation (reported as tile 23: the tile grid is rounded up, the kernel masks the overhang) where the
+ *   measured rule of DESIGN.md says the padded tile beats the fallback.  0: they land on the general kernels (A/B knob).
  * gemm2 (default 1, round 6; needs gemm_split): 1x1 stride-1 convolutions with Cout % 128 == 0, channel counts % 32 == 0 and
  *   B * H * W % 64 == 0 (res_conv, attention qkv / out of the BASELINE networks) run as a plain GEMM on the same 3 x bf16 split
  *   arithmetic (gemm1x1.hip; reported as tile 22): 64 x 128 tile, weights pre-split in MFMA fragment order in the derived buffer
@@ -160,8 +164,21 @@ int sr3_plan_set_option(sr3_plan* plan, const char* key, int value);
 int sr3_plan_num_taps(sr3_plan* plan);
 int sr3_plan_tap_info(sr3_plan* plan, int index, char* name, int name_len, size_t* offset, int* C, int* H, int* W);
 
-/* Workspace bytes for sr3_unet_forward at this batch size (activations, statistics, FiLM table,
- * split-K slabs). */
+/* Geometry.  Height and width of the images the NEXT forward / reverse step / workspace query / plan inspection of this plan works
+ * on; (0, 0) restores image_size x image_size (the state after sr3_plan_create).  Both must be positive multiples of 2^(n_mults-1)
+ * (SR3_E_BADARG otherwise; the plan keeps its previous geometry).  The UNet is fully convolutional; attention placement stays where
+ * UNet.__init__ put it from image_size (reference behaviour: model/sr3_modules/unet.py:235-259 never looks at the size).  Host only:
+ * invalidates the built launch list (like an option change), not the derived filters.  Every layer picks its kernel through the same
+ * fits-predicates as at the native size and lands on the general kernels where nothing faster fits; a geometry NO kernel can run
+ * (an attention level with more tokens than the attention kernel holds in LDS) is refused with SR3_E_UNSUPPORTED and a message
+ * naming the level and its token count when the launch list is built -- by sr3_workspace_bytes (returns 0) / sr3_plan_num_ops
+ * (returns -1) / the forward itself before it enqueues anything.  Training is native-size only: sr3_train_workspace_bytes returns 0
+ * and sr3_train_step SR3_E_UNSUPPORTED while the geometry is not image_size x image_size. */
+int sr3_plan_set_geometry(sr3_plan* plan, int height, int width);
+int sr3_plan_get_geometry(const sr3_plan* plan, int* height, int* width);
+
+/* Workspace bytes for sr3_unet_forward at this batch size and the plan's current geometry (activations, statistics, FiLM
+ * table, split-K slabs). */
 /* Derived weights.  The inference plan runs its 3x3 stride-1 convolutions as Winograd F(2x2,3x3) (plan option
  * "winograd", default 1), which reads the transformed filters U = G g G^T from a caller-owned device buffer of
  * sr3_plan_derived_bytes bytes (16/9 of the 3x3 weights).  Bind it once (the pointer is kept, and baked into captured
@@ -181,8 +198,9 @@ int sr3_plan_invalidate_derived(sr3_plan* plan);
 size_t sr3_workspace_bytes(sr3_plan* plan, int batch);
 
 /* UNet.forward (model/sr3_modules/unet.py:235-259, model/ddpm_modules/unet.py:220-243).
- *   x_nchw    : (B, in_channel - cond_channels, S, S)  the noisy image
- *   cond_nchw : (B, cond_channels, S, S) or NULL -- the conditioning image; the engine consumes the
+ *   x_nchw    : (B, in_channel - cond_channels, H, W)  the noisy image; H x W = the plan's geometry (sr3_plan_set_geometry;
+ *               image_size x image_size unless set)
+ *   cond_nchw : (B, cond_channels, H, W) or NULL -- the conditioning image; the engine consumes the
  *               pair as the virtual concat torch.cat([cond, x], 1) (model/sr3_modules/diffusion.py:157)
  *   noise_level : (B) fp32, SR3 variant (the (B,1) tensor of diffusion.py:153-154), else NULL
  *   timestep  : (B) int64, DDPM variant, else NULL
@@ -190,7 +208,7 @@ size_t sr3_workspace_bytes(sr3_plan* plan, int batch);
  *   level_table/step_dev : optional graph-replay source of the conditioning value: when step_dev is
  *               non-NULL the level is level_table[*step_dev + 1] (SR3) or the timestep *step_dev (DDPM)
  *   params    : packed parameter arena (see sr3_plan_param_info)
- *   eps_out_nchw : (B, out_channel, S, S) */
+ *   eps_out_nchw : (B, out_channel, H, W) */
 int sr3_unet_forward(sr3_plan* plan, const float* x_nchw, const float* cond_nchw, int cond_channels,
                      const float* noise_level, const int64_t* timestep, const float* freq,
                      const float* level_table, const int* step_dev, const float* params,
@@ -234,7 +252,7 @@ int sr3_step_decrement(int* step_dev, void* stream);
  * = sr3_unet_forward + sr3_p_sample_step_ex + sr3_step_decrement, with the last two inside the output convolution's kernel (the thread
  * that produces an element of eps updates the same element of x; separately rounded operations, bit-identical to the three-call form):
  * two kernel nodes fewer per replayed step.
- *   x_nchw      : [B, C, S, S] the image, in / out
+ *   x_nchw      : [B, C, H, W] the image, in / out (H x W = the plan's geometry)
  *   step2_dev   : TWO ints.  step2_dev[1] = t of this step on entry (the caller sets it to T - 1 before the first step) and t - 1 on
  *                 completion; step2_dev[0] is scratch (the step's first kernel copies t there for its last one).  t must stay >= 0.
  *   level_table : SR3: level = level_table[t + 1] (sqrt_alphas_cumprod_prev); DDPM: ignored (the timestep is t)
@@ -252,7 +270,8 @@ int sr3_q_sample(const float* x0, const float* z, const float* ca, const float* 
 
 /* ---- training step ------------------------------------------------------------------------- */
 
-/* Workspace of sr3_train_step (activations kept for the backward, their gradient mirror, scratch). */
+/* Workspace of sr3_train_step (activations kept for the backward, their gradient mirror, scratch).  Training runs at
+ * image_size x image_size only: 0 (and a message) while sr3_plan_set_geometry has the plan at another geometry. */
 size_t sr3_train_workspace_bytes(sr3_plan* plan, int batch, int cond_channels);
 
 /* One training step up to the gradients: `l_pix = netG(data); l_pix.backward()` of
@@ -293,7 +312,9 @@ int sr3_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
  * derived into `scratch` by this entry point); tile_cfg 12 = the same kernel's 3 x bf16 split instantiation (one-image tile
  * only, and the four-image tile of the 8x8 maps; what plan option wino_split selects there), 13 = the same arithmetic as two
  * four-wave workgroups per CU on an 8 x 16 pixel tile (conv3x3_wino2.hip; W >= 16 and a multiple of 16, H a multiple of 8, no
- * dropout form; what plan option wino2 -- default on -- selects on maps >= 16 wide); tile_cfg 1-4 = the
+ * dropout form; what plan option wino2 -- default on -- selects on maps >= 16 wide), 23 = that kernel's ragged instantiation: any
+ * map size (tile grid ceil(W / 16) x ceil(H / 8), the overhang masked; same arithmetic, same filters; on a map that is a whole
+ * multiple of the tile the bits of 13; what plan option wino_ragged selects at a non-native geometry); tile_cfg 1-4 = the
  * im2col kernel's 128x128 / 128x64 / 64x64 / 64x128 tiles on the exact-fp32 MFMA, 14-17 = the same tiles on the 3 x bf16 split
  * instantiation with both operands split while they are staged (what plan option gemm_split selects: what a plan runs), 18-21 =
  * the same with the weights pre-split into bf16 planes in MFMA fragment order and read straight from global memory (plan option
@@ -302,7 +323,7 @@ int sr3_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
  * stride 1, or 3x3 stride 2 with one source, act 0 and an even map; no upsampling, Cout % 64 == 0, C0 and C1 % 32 == 0,
  * B * Ho * Wo % 64 == 0, Ho * Wo % 32 == 0, act 0 | 1; anything else is refused with "does not fit"; same pre-split weights as
  * 18-21, derived into `scratch`).
- * scratch: split-K slabs (+ the Winograd filters for tile_cfg 11-13, the pre-split weights for 18-22), sized by
+ * scratch: split-K slabs (+ the Winograd filters for tile_cfg 11-13 and 23, the pre-split weights for 18-22), sized by
  * sr3_conv_scratch_bytes. */
 int sr3_conv_f32(const float* src0, int C0, const float* src1, int C1, int B, int Hs, int Ws, int ups,
                  int stride, int ksize, int Cout, const float* w_ohwi, const float* bias, const float* ss,
