@@ -480,9 +480,11 @@ bool attention_fits(int N, int C) {
   return attention_v2_fits(N, C) || attention_v1_smem(N, 1) <= 160 * 1024;
 }
 
-int attention_forward(const float* qkv, int B, int N, int C, float* out, hipStream_t st, int split) {
+int attention_forward(const float* qkv, int B, int N, int C, float* out, hipStream_t st, int mode) {
   if (C & 3) { set_error("attention: C %% 4 != 0"); return SR3_E_UNSUPPORTED; }
   if ((double)B * N * 3.0 * C >= 2147483647.0) { set_error("attention: qkv exceeds 2^31 elements"); return SR3_E_UNSUPPORTED; }
+  const int split = mode & 1;
+  if (mode & 2) return attention_long_forward(qkv, B, N, C, out, st, split != 0);     // the key-blocked kernel, at any N
   // the staging-free kernel wherever the shape allows it (SR3_ATTN_V1=1, read once: A/B knob for the profiles)
   static const bool force_v1 = [] { const char* e = getenv("SR3_ATTN_V1"); return e && e[0] == '1'; }();
   if (!force_v1 && attention_v2_fits(N, C)) {

@@ -620,7 +620,8 @@ struct Builder {
       const int o = make(R.cout, T[out].H, T[out].W);
       Op a; a.kind = OP_ATTN;
       a.a = T[qkv].off; a.b = T[o].off; a.i0 = T[out].H * T[out].W; a.i1 = R.cout;
-      if (!train && refused.empty() && !attention_fits(a.i0, R.cout)) {
+      if (!train && P->attn_long && !attention_fits(a.i0, R.cout)) a.tile_cfg = 24;       // the key-blocked kernel: any token count
+      else if (!train && refused.empty() && !attention_fits(a.i0, R.cout)) {
         char msg[256];
         snprintf(msg, sizeof(msg), "attention of %s: the %d x %d level has %d tokens, more than the attention kernel holds in LDS", R.name.c_str(),
                  T[out].H, T[out].W, a.i0);
@@ -941,7 +942,7 @@ int run_forward(sr3_plan* P, const Regions& R, const float* x, const float* cond
       }
       case OP_ATTN:
         rc = attention_forward(reinterpret_cast<const float*>(ws + o.a), B, o.i0, o.i1,
-                               reinterpret_cast<float*>(ws + o.b), st, P->attn_split);
+                               reinterpret_cast<float*>(ws + o.b), st, (P->attn_split ? 1 : 0) | (o.tile_cfg == 24 ? 2 : 0));
         break;
       case OP_CONV_OUT:
         rc = conv_out_nchw(reinterpret_cast<const float*>(ws + o.a), reinterpret_cast<const float*>(ws + R.ss_off + o.ss_rel),
@@ -1186,6 +1187,7 @@ int sr3_plan_op_info(sr3_plan* plan, int batch, int index, sr3_op_info* out) {
     out->fused_output_stats = o.has_ostat ? 1 : 0;
   } else if (o.kind == OP_ATTN) {
     out->h_out = o.i0; out->cin = out->cout = o.i1;          // tokens, channels
+    out->tile_cfg = o.tile_cfg;                              // 24: the key-blocked kernel (plan option attn_long); 0: the strip kernels
     out->flops = 4.0 * batch * (double)o.i0 * (double)o.i0 * o.i1;
   }
   return SR3_OK;
@@ -1220,6 +1222,7 @@ int sr3_plan_set_option(sr3_plan* plan, const char* key, int value) {
   else if (!strcmp(key, "wino_split8")) slot = &plan->wino_split8;
   else if (!strcmp(key, "wgrad_split")) { const int prev = plan->wgrad_split; plan->wgrad_split = value; return prev; }   // no rebuild (the slabs are sized for both)
   else if (!strcmp(key, "attn_split")) { const int prev = plan->attn_split; plan->attn_split = value; return prev; }   // no rebuild
+  else if (!strcmp(key, "attn_long")) slot = &plan->attn_long;
   else if (!strcmp(key, "gemm_split")) slot = &plan->gemm_split;
   else if (!strcmp(key, "gemm_wpre")) slot = &plan->gemm_wpre;
   else if (!strcmp(key, "gemm2")) slot = &plan->gemm2;

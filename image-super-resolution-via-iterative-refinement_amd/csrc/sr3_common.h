@@ -320,10 +320,14 @@ struct EmbedParams {
 };
 int embed_forward(const EmbedParams& p, hipStream_t st);
 // single-head attention over NHWC qkv [B][N][3C] -> out [B][N][C]
-// split != 0: the staging-free kernel's 3 x bf16 split instantiation where the shape takes that kernel (fp32 MFMA otherwise)
-int attention_forward(const float* qkv, int B, int N, int C, float* out, hipStream_t st, int split = 0);
-// host predicate: can attention_forward run N tokens of C channels (the kernels keep a 32-query score strip over all N keys in LDS)?
+// mode bit 0: the staging-free kernel's 3 x bf16 split instantiation where the shape takes that kernel (fp32 MFMA otherwise);
+// mode bit 1: the key-blocked kernel of attention_long.hip (any N; also where the score strip would fit)
+int attention_forward(const float* qkv, int B, int N, int C, float* out, hipStream_t st, int mode = 0);
+// host predicate: can the strip kernels of attention_forward (mode bit 1 clear) run N tokens of C channels?  (They keep a 32-query
+// score strip over all N keys in LDS.)
 bool attention_fits(int N, int C);
+// key-blocked (online softmax) form: any N > 0, C % 4 == 0 (attention_long.hip); split: 3 x bf16 split arithmetic where C % 128 == 0
+int attention_long_forward(const float* qkv, int B, int N, int C, float* out, hipStream_t st, bool split);
 int p_sample_update(float* x, const float* eps, const float* z, StepTables tb, const int* step_dev,
                     const int64_t* t_per_sample, int step_host, int B, int per_image, hipStream_t st, bool clip = true);
 int step_decrement(int* step_dev, hipStream_t st);

@@ -31,7 +31,8 @@ def define_G(opt):
     denoiser = unet.UNet(
         in_channel=u['in_channel'], out_channel=u['out_channel'], norm_groups=u['norm_groups'],
         inner_channel=u['inner_channel'], channel_mults=u['channel_multiplier'], attn_res=u['attn_res'],
-        res_blocks=u['res_blocks'], dropout=u['dropout'], image_size=model_opt['diffusion']['image_size'])
+        res_blocks=u['res_blocks'], dropout=u['dropout'], image_size=model_opt['diffusion']['image_size'],
+        long_attention=bool(u.get('long_attention', False)))      # (engine key: images whose attention level exceeds the LDS score strip)
     netG = diffusion.GaussianDiffusion(
         denoiser, image_size=model_opt['diffusion']['image_size'], channels=model_opt['diffusion']['channels'],
         loss_type='l1', conditional=model_opt['diffusion']['conditional'],

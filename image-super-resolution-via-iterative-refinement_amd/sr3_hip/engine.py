@@ -108,7 +108,7 @@ class Plan(object):
     def workspace_bytes(self, batch):
         n = int(self.lib.sr3_workspace_bytes(self.handle, int(batch)))
         if n == 0:
-            raise L.Sr3Error('sr3_workspace_bytes failed: %s' % (self.lib.sr3_last_error() or b'').decode())
+            raise L.Sr3Error('sr3_workspace_bytes failed: %s' % L.hint((self.lib.sr3_last_error() or b'').decode()))
         return n
 
     def forward_flops(self, batch):

@@ -129,10 +129,18 @@ def load():
     return lib
 
 
+def hint(msg):
+    """The library's message plus, for a refusal the caller can lift, how (Python side only: the C text is part of the ABI's tests)."""
+    if 'more than the attention kernel holds in LDS' in msg:
+        msg += ('; set "long_attention": true in the config\'s model.unet section (EngineUNet(long_attention=True), plan option '
+                'attn_long) to run such levels on the key-blocked attention kernel')
+    return msg
+
+
 def check(rc):
     if rc != 0:
         msg = load().sr3_last_error()
-        raise Sr3Error('libsr3_mi355x error %d: %s' % (rc, (msg or b'').decode()))
+        raise Sr3Error('libsr3_mi355x error %d: %s' % (rc, hint((msg or b'').decode())))
 
 
 def ptr(t):

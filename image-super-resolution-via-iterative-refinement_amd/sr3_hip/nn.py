@@ -24,13 +24,18 @@ class EngineUNet(nn.Module):
 
     def __init__(self, in_channel=6, out_channel=3, inner_channel=32, norm_groups=32,
                  channel_mults=(1, 2, 4, 8, 8), attn_res=(8), res_blocks=3, dropout=0,
-                 with_noise_level_emb=True, image_size=128):
+                 with_noise_level_emb=True, image_size=128, *, long_attention=False):
         super().__init__()
         if not with_noise_level_emb:
             raise NotImplementedError('the engine always conditions on the noise level / timestep '
                                       '(define_G never disables it: model/networks.py:91-101)')
         self.plan = E.Plan(self.variant, in_channel, out_channel, inner_channel, norm_groups, channel_mults,
                            attn_res, res_blocks, image_size)
+        # config key model.unet.long_attention (plan option attn_long): attention levels with more tokens than the score-strip
+        # kernels hold in LDS run on the key-blocked kernel instead of refusing the image size
+        self.long_attention = bool(long_attention)
+        if self.long_attention:
+            self.plan.set_option('attn_long', 1)
         self.dropout = float(dropout)
         self.arena = nn.Parameter(torch.zeros(self.plan.param_floats, dtype=torch.float32), requires_grad=False)
         self.register_buffer('freq', self.plan.default_freq(), persistent=False)

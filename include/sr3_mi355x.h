@@ -86,7 +86,7 @@ int sr3_plan_num_ops(sr3_plan* plan, int batch);
 typedef struct sr3_op_info {
   int kind, tile_cfg, ksplit;
   int ksize, stride, upsample;
-  int cin, cout, h_out, w_out;          /* attention: cin = cout = channels, h_out = tokens */
+  int cin, cout, h_out, w_out;          /* attention: cin = cout = channels, h_out = tokens; tile_cfg 24 = the key-blocked kernel, 0 = the strip kernels */
   int fused_res_conv_cin;               /* > 0: the 1x1 res_conv of that many input channels runs inside this launch */
   int fused_output_stats;               /* 1: the launch also writes the next GroupNorm's partial statistics */
   double flops;
@@ -100,7 +100,7 @@ int sr3_plan_op_side(sr3_plan* plan, int batch, int index, int* side_id, int* wa
 double sr3_plan_forward_flops(sr3_plan* plan, int batch);
 /* tuning knobs: key in {"fuse_stats", "fuse_res", "tile_cfg", "ksplit", "keep_all", "split_bf16", "winograd",
  * "wino_split", "wino_split8", "wino2", "wino_ragged", "gemm_split", "gemm2", "gemm_s2", "gemm_n64", "fork_side", "gemm_wpre", "gemm_tile", "fold_fuse", "wgrad_split", "attn_split",
- * "loss_l2"};
+ * "attn_long", "loss_l2"};
  * returns previous value.
  * wino_split (default 1): the Winograd convolutions that run on the kernel's one-image tile (maps >= 16x16) use its 3 x bf16
  *   split instantiation: every fp32 operand as x = h + m + l (three bf16 terms, each residual exact in fp32), every product as
@@ -150,6 +150,12 @@ double sr3_plan_forward_flops(sr3_plan* plan, int batch);
  *   0: the fp32-MFMA weight-gradient kernels.  No rebuild of the plan.
  * attn_split (default 1, round 5): SelfAttention's two contractions (Q K^T, P V) on the 3 x bf16 split instantiation of the
  *   staging-free kernel, gated against float64 like the convolutions; 0: v_mfma_f32_32x32x2_f32.  No rebuild of the plan.
+ * attn_long (default 0; inference plans): an attention level with more tokens than the score-strip kernels hold in LDS (about 1088: every
+ *   image above 256 x 256 in area with attention at the 1/8-resolution level) runs on the key-blocked kernel of csrc/attention_long.hip
+ *   (online softmax over chunks of 512 keys, LDS use independent of the token count; reported as tile_cfg 24 on the attention op) instead
+ *   of refusing the geometry.  A level the strip kernels hold keeps them: launch list, workspace and output bits are those of
+ *   attn_long = 0 there.  attn_split selects the arithmetic as for the strip kernels.  The default is 0 for ONE reason: a test pins the
+ *   refusal of a fresh plan at 384 x 384; a later change that rewrites that test can flip it.
  * loss_l2 (default 0): sr3_train_step uses nn.MSELoss(reduction='sum') instead of nn.L1Loss(reduction='sum')
  *   (GaussianDiffusion(loss_type='l2'), model/sr3_modules/diffusion.py:84-90).
  * split_bf16 (default 0, experimental; needs -DSR3_EXPERIMENTS, refused otherwise): run the halo-tile 3x3 convolutions of the inference plan on
@@ -170,8 +176,8 @@ int sr3_plan_tap_info(sr3_plan* plan, int index, char* name, int name_len, size_
  * UNet.__init__ put it from image_size (reference behaviour: model/sr3_modules/unet.py:235-259 never looks at the size).  Host only:
  * invalidates the built launch list (like an option change), not the derived filters.  Every layer picks its kernel through the same
  * fits-predicates as at the native size and lands on the general kernels where nothing faster fits; a geometry NO kernel can run
- * (an attention level with more tokens than the attention kernel holds in LDS) is refused with SR3_E_UNSUPPORTED and a message
- * naming the level and its token count when the launch list is built -- by sr3_workspace_bytes (returns 0) / sr3_plan_num_ops
+ * (an attention level with more tokens than the attention kernel holds in LDS, in a plan without option attn_long) is refused with
+ * SR3_E_UNSUPPORTED and a message naming the level and its token count when the launch list is built -- by sr3_workspace_bytes (returns 0) / sr3_plan_num_ops
  * (returns -1) / the forward itself before it enqueues anything.  Training is native-size only: sr3_train_workspace_bytes returns 0
  * and sr3_train_step SR3_E_UNSUPPORTED while the geometry is not image_size x image_size. */
 int sr3_plan_set_geometry(sr3_plan* plan, int height, int width);
@@ -367,8 +373,11 @@ int sr3_groupnorm_fold_f32(const double* stat0, int C0, int T0, const double* st
                            int groups, const float* gamma, const float* beta, float eps, float* ss, void* stream);
 /* SelfAttention core (unet.py:127-139): qkv NHWC [B][N][3C] -> out [B][N][C] */
 int sr3_attention_f32(const float* qkv, int B, int N, int C, float* out, void* stream);
-/* ... with split != 0: QK^T and PV as six bf16 MFMA products of 3-way split fp32 operands, fp32 accumulation (plan option
- * attn_split; fp32-class results, gated against float64 in tests/), where the shape takes the staging-free kernel */
+/* ... with a mode (`split`).  Bit 0: QK^T and PV as six bf16 MFMA products of 3-way split fp32 operands, fp32 accumulation (plan option
+ * attn_split; fp32-class results, gated against float64 in tests/), where the shape takes the staging-free kernel.  Bit 1: the
+ * key-blocked kernel (plan option attn_long; csrc/attention_long.hip): any N > 0 and C % 4 == 0, also where the score strip fits; bit 0
+ * then selects the split arithmetic where C % 128 == 0 (other C run an fp32-MFMA form).  Without bit 1, N beyond the LDS score strip
+ * (about 1088 tokens) is refused with SR3_E_UNSUPPORTED; B * N * 3C >= 2^31 is refused in every mode. */
 int sr3_attention_ex_f32(const float* qkv, int B, int N, int C, float* out, int split, void* stream);
 /* backward of the attention core (autograd of unet.py:127-139): dqkv [B][N][3C] from qkv, d(out) [B][N][C]; out_fwd
  * (the forward output) may be NULL when N <= ~480 -- larger N use a key-blocked pass that reads it */
