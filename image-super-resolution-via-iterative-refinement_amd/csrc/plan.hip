@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "plan_internal.h"
+#include "tile_code.h"
 #include "train.h"
 
 namespace sr3 {
@@ -35,10 +36,6 @@ int hip_fail(hipError_t e, const char* what) {
   return (int)e > 0 ? (int)e : 1;
 }
 const char* last_error() { return g_err; }
-
-}  // namespace sr3
-
-namespace sr3 {
 
 // ---------------------------------------------------------------------------------------------
 // parameter table
@@ -291,6 +288,96 @@ static bool wino_ragged_wins(const ConvParams& c) {
   return 4L * c.Ho * c.Wo >= padded;
 }
 
+// Which 3x3 stride-1 convs run on the Winograd kernels (plan option `winograd`; 0: none), train-mode dropout convs included; an explicit
+// tile_cfg / split_bf16 keep the direct halo kernels (the fused res_conv segment has no Winograd form: res_conv is then its own 1x1 GEMM)
+// 1: the tiles of today's rules (wino_geometry of the 8-wave kernel decides, *wg is that geometry; choose_conv then picks the instantiation);
+// 2: only at a geometry other than image_size x image_size (so the native launch list never moves), inference plans: a map the rule
+// above refuses on the two-workgroup kernel -- its plain form where the map is a whole multiple of the 8 x 16 tile, its RAGGED form
+// (plan option wino_ragged) where wino_ragged_wins says the padded tile beats the fallback
+static int wino_mode(const sr3_plan* P, const ConvParams& c, size_t w, bool has_x2, bool has_drop, bool train, WinoGeom* wg) {
+  if (!P->winograd || P->tile_cfg != 0 || P->split_bf16 || has_x2) return 0;
+  if (has_drop && (c.C1 != 0 || c.ups != 0 || c.act == 0)) return 0;    // the dropout form: single source, no upsampling
+  if (c.ksize != 3 || c.stride != 1 || !P->derived_of.count(w)) return 0;
+  if (wino_geometry(c, wg)) return 1;
+  if (train || has_drop || plan_native_geometry(P) || !P->wino_split || !P->wino2) return 0;
+  ConvParams r = c;
+  r.wino_split = wino2_fits(c) ? 2 : 3;
+  if (r.wino_split == 3 && !(P->wino_ragged && wino_ragged_wins(c))) return 0;
+  return wino_geometry(r, wg) ? 2 : 0;
+}
+
+// The kernel one conv of a plan runs on: THE place where the planner decides it (Builder::conv only emits what this returns).
+struct ConvChoice {
+  int tile_cfg, ksplit;            // what conv_forward is called with
+  int wino_split, igemm_split;     // the ConvParams fields of these names
+  int wino_mode;                   // 0: the Winograd rule did not take the conv; 1 / 2: wino_mode above
+  size_t wino_off;                 // the Op fields of these names
+  bool has_wsplit; size_t wsplit_off;
+};
+// RULE_HEAD stops behind the first conv_pick, with neither the split_bf16 tile nor igemm_split: what Builder::fuses_res_conv has always asked
+enum ChoiceRule { RULE_FULL, RULE_HEAD };
+static ConvChoice choose_conv(const sr3_plan* P, ConvParams c, size_t w, bool has_x2, bool has_drop, bool train, ChoiceRule rule = RULE_FULL) {
+  ConvChoice ch = {P->tile_cfg, P->ksplit, 0, 0, 0, 0, false, 0};
+  const bool full = rule == RULE_FULL;
+  auto repick = [&](int tile) { ch.tile_cfg = tile; ch.ksplit = P->ksplit; conv_pick(c, ch.tile_cfg, ch.ksplit); };
+  // opt-in: the 3 x bf16 split MFMA instantiation of the 8-wave tile wherever it fits (inference plans only)
+  HaloGeom sg; WinoGeom wg;
+  if (full && P->split_bf16 && !train && ch.tile_cfg == 0 && c.ksize == 3 && c.stride == 1 && c.Cout > 64 && halo_geometry(c, 10, &sg)) ch.tile_cfg = 10;
+  ch.wino_mode = wino_mode(P, c, w, has_x2, has_drop, train, &wg);
+  if (ch.wino_mode) {
+    ch.tile_cfg = 11;
+    ch.wino_off = P->derived_of.at(w);
+    // plan option wino_split: the 3 x bf16 split instantiation where it exists (the one-image tile; training plan and train-mode
+    // dropout included); 2: the 8 x 16 tile of conv3x3_wino2.hip, 3: its ragged form.  Its filters sit behind the conv's fp32 ones
+    if (ch.wino_mode == 2) c.wino_split = wino2_fits(c) ? 2 : 3;
+    else if (P->wino_split && (wg.NB == 1 || (P->wino_split8 && !has_drop))) c.wino_split = (P->wino2 && !has_drop && wg.NB == 1) ? 2 : 1;
+    if (c.wino_split) ch.wino_off += wino_weight_floats(c.Cout, c.C0 + c.C1);
+  }
+  if (full) {
+    // read by conv_pick / conv_forward only when the conv lands on the im2col kernel; the 9-tap layers with Cout <= 64 (Downsample
+    // of the first level) stay on the fp32 MFMA, which is faster there (67 vs 81 us in the forward)
+    c.igemm_split = (P->gemm_split && !(c.ksize == 3 && c.Cout <= 64)) ? 1 : 0;
+    // (... unless the plain GEMM kernel takes the layer on its 64-column tile: plan options gemm2 + gemm_s2 + gemm_n64, below)
+    if (P->gemm_split && P->gemm2 && P->gemm_s2 && P->gemm_n64 && c.ksize == 3 && c.stride == 2 && P->wsplit_of.count(w) && gemm1x1_fits(c, 2)) c.igemm_split = 1;
+  }
+  conv_pick(c, ch.tile_cfg, ch.ksplit);
+  ch.wino_split = c.wino_split;
+  if (!full) return ch;
+  const bool presplit = c.igemm_split && P->wsplit_of.count(w);      // (a SPLIT conv whose pre-split weights the derived buffer holds)
+  if (P->gemm_tile >= 1 && P->gemm_tile <= 4 && ch.tile_cfg >= 1 && ch.tile_cfg <= 4 && P->tile_cfg == 0) repick(P->gemm_tile);       // A/B knob: one im2col tile for every conv of that kernel
+  if (presplit && ch.tile_cfg >= 1 && ch.tile_cfg <= 4 && P->gemm2 && P->tile_cfg == 0 && P->gemm_tile == 0) {
+    // plan option gemm2: 1x1 stride-1 convs -- and Downsample's 3x3 stride-2 ones -- the plain GEMM kernel fits (gemm1x1.hip)
+    if (gemm1x1_fits(c, 2) && (c.ksize == 1 || P->gemm_s2) && (!(c.Cout & 127) || P->gemm_n64)) { repick(22); ch.has_wsplit = true; }
+  }
+  if (presplit && ch.tile_cfg >= 1 && ch.tile_cfg <= 4 && P->gemm_wpre) ch.has_wsplit = true;       // the SPLIT tile reads its weights pre-split from the derived buffer
+  if (ch.has_wsplit) ch.wsplit_off = P->wsplit_of.at(w);
+  if (has_drop && ch.tile_cfg == 9) repick(5);       // no dropout instantiation of the 8-wave tile
+  // dropout convs on the 256x64 tile run its 8-wave form (conv3x3_halo_forward); SR3_DROP_CFG5 forces the
+  // half-empty 128x128 tile instead (A/B knob)
+  static const bool use5 = getenv("SR3_DROP_CFG5") != nullptr;
+  if (has_drop && ch.tile_cfg == 6 && use5) repick(5);
+  // opt-in: run the halo-tile convs on the 3 x bf16 split MFMA instantiations (inference plans only)
+  if (P->split_bf16 && !train && ch.tile_cfg == 5) ch.tile_cfg = 7;
+  else if (P->split_bf16 && !train && ch.tile_cfg == 9) ch.tile_cfg = 10;
+  else if (P->split_bf16 && !train && ch.tile_cfg == 6) ch.tile_cfg = 8;
+  ch.igemm_split = c.igemm_split;
+  return ch;
+}
+
+// One conv of the forward, for Builder::conv: sources and residuals are tensor handles (-1: absent), parameters arena offsets
+static constexpr size_t NO_PARAM = ~(size_t)0;
+struct ConvSpec {
+  int x0 = -1, x1 = -1;            // source: the virtual concat (x0|x1)
+  int Cout = 0, ksize = 3, stride = 1, ups = 0;
+  int act = 0;                     // ConvParams::act: what the prologue does with the GroupNorm fold in front of this conv
+  size_t w = 0, bias = NO_PARAM;
+  int film_row = -1;               // first row of the FiLM table added to the output
+  int r0 = -1, r1 = -1;            // residual: the concat view (r0|r1)
+  bool want_stats = false;         // a GroupNorm reads the output: fuse its statistics where the kernel can
+  int q0 = -1, q1 = -1; size_t qw = 0, qb = 0;       // fused 1x1 segment (res_conv) over (q0|q1); caller checked fuses_res_conv()
+  int drop_key = -1;               // train-mode dropout on the activated input: the layer's key (drop_layer_seed)
+};
+
 struct Builder {
   sr3_plan* P;
   int B;
@@ -356,193 +443,98 @@ struct Builder {
     return true;
   }
   void fold(int x0, int x1, size_t gamma, size_t beta) {
-    const int Cfu = T[x0].C + (x1 >= 0 ? T[x1].C : 0);
+    const int Cf = T[x0].C + (x1 >= 0 ? T[x1].C : 0);
+    // the tables this fold writes, whichever kernel does it: per-GroupNorm slots in training, the one shared region (offset 0) in inference
     size_t ss_rel = 0, mr_rel = 0;
-    auto take_slots = [&]() {
-      if (train) {
-        ss_rel = gn_cursor; gn_cursor += ((size_t)B * Cfu * 2 * sizeof(float) + 255) & ~(size_t)255;
-        mr_rel = mr_cursor; mr_cursor += ((size_t)B * P->d.norm_groups * 2 * sizeof(float) + 255) & ~(size_t)255;
-      }
-      cur_ss = ss_rel; cur_mr = mr_rel; cur_gamma = gamma; cur_beta = beta;
-      max_cin = std::max(max_cin, Cfu);
-    };
+    if (train) {
+      ss_rel = gn_cursor; gn_cursor += ((size_t)B * Cf * 2 * sizeof(float) + 255) & ~(size_t)255;
+      mr_rel = mr_cursor; mr_cursor += ((size_t)B * P->d.norm_groups * 2 * sizeof(float) + 255) & ~(size_t)255;
+    }
+    cur_ss = ss_rel; cur_mr = mr_rel; cur_gamma = gamma; cur_beta = beta;
+    max_cin = std::max(max_cin, Cf);
     if (P->fold_fuse && !ops.empty()) {
       // (a) the op just emitted is a split-K conv whose reduce writes the statistics of x0 / x1: its reduce folds too
       Op& L = ops.back();
-      if (last_conv_op == (int)ops.size() - 1 && L.kind == OP_CONV && L.ksplit > 1 && L.has_ostat && (last_conv_out == x0 || last_conv_out == x1)) {
-        take_slots();
-        if (fuse_fold_into(L, last_conv_out, x0, x1, gamma, beta, ss_rel, mr_rel, train)) return;
-        if (train) { gn_cursor = ss_rel; mr_cursor = mr_rel; }       // (not fused: the slots are taken again below)
-      }
+      if (last_conv_op == (int)ops.size() - 1 && L.kind == OP_CONV && L.ksplit > 1 && L.has_ostat && (last_conv_out == x0 || last_conv_out == x1) &&
+          fuse_fold_into(L, last_conv_out, x0, x1, gamma, beta, ss_rel, mr_rel, train)) return;
     }
     ensure_stats(x0);
     if (x1 >= 0) ensure_stats(x1);
-    if (P->fold_fuse && !ops.empty() && last_stats_op == (int)ops.size() - 1 && (last_stats_h == x0 || last_stats_h == x1)) {
-      // (b) ... or a stand-alone statistics pass of x0 / x1: it folds too
-      take_slots();
-      if (fuse_fold_into(ops.back(), last_stats_h, x0, x1, gamma, beta, ss_rel, mr_rel, train)) return;
-      if (train) { gn_cursor = ss_rel; mr_cursor = mr_rel; }
-    }
+    // (b) ... or a stand-alone statistics pass of x0 / x1: it folds too
+    if (P->fold_fuse && !ops.empty() && last_stats_op == (int)ops.size() - 1 && (last_stats_h == x0 || last_stats_h == x1) &&
+        fuse_fold_into(ops.back(), last_stats_h, x0, x1, gamma, beta, ss_rel, mr_rel, train)) return;
     Op o; o.kind = OP_FOLD;
     o.a = T[x0].stat_off; o.i0 = T[x0].C; o.i3 = T[x0].stat_T;
     o.has_st1 = x1 >= 0;
     if (x1 >= 0) { o.b = T[x1].stat_off; o.i1 = T[x1].C; o.i4 = T[x1].stat_T; }
     o.i2 = T[x0].H * T[x0].W;
     o.p0 = gamma; o.p1 = beta;
-    const int Cf = T[x0].C + (x1 >= 0 ? T[x1].C : 0);
-    if (train) {
-      o.ss_rel = gn_cursor; gn_cursor += ((size_t)B * Cf * 2 * sizeof(float) + 255) & ~(size_t)255;
-      o.mr_rel = mr_cursor; mr_cursor += ((size_t)B * P->d.norm_groups * 2 * sizeof(float) + 255) & ~(size_t)255;
-      o.has_mr = true;
-    }
-    cur_ss = o.ss_rel; cur_mr = o.mr_rel; cur_gamma = gamma; cur_beta = beta;
+    o.ss_rel = ss_rel; o.mr_rel = mr_rel; o.has_mr = train;
     ops.push_back(o);
-    max_cin = std::max(max_cin, Cf);
   }
-  // every 3x3 stride-1 conv the Winograd kernel covers runs on it (plan option `winograd`, default on), train-mode dropout
-  // convs included; an explicit tile_cfg / split_bf16 keep the direct halo kernels (the fused res_conv segment has no
-  // Winograd form: res_conv is then its own 1x1 GEMM)
-  // 1: the tiles of today's rules (wino_geometry of the 8-wave kernel decides; Builder::conv then picks the instantiation);
-  // 2: only at a geometry other than image_size x image_size (so the native launch list never moves), inference plans: a map the rule
-  // above refuses on the two-workgroup kernel -- its plain form where the map is a whole multiple of the 8 x 16 tile, its RAGGED form
-  // (plan option wino_ragged) where wino_ragged_wins says the padded tile beats the fallback
-  int wino_mode(const ConvParams& c, size_t w, bool has_x2, bool has_drop) {
-    if (!P->winograd || P->tile_cfg != 0 || P->split_bf16 || has_x2) return 0;
-    if (has_drop && (c.C1 != 0 || c.ups != 0 || c.act == 0)) return 0;    // the dropout form: single source, no upsampling
-    if (c.ksize != 3 || c.stride != 1 || !P->derived_of.count(w)) return 0;
-    WinoGeom wg;
-    if (wino_geometry(c, &wg)) return 1;
-    if (train || has_drop || plan_native_geometry(P) || !P->wino_split || !P->wino2) return 0;
-    ConvParams r = c;
-    r.wino_split = wino2_fits(c) ? 2 : 3;
-    if (r.wino_split == 3 && !(P->wino_ragged && wino_ragged_wins(c))) return 0;
-    return wino_geometry(r, &wg) ? 2 : 0;
-  }
-  bool wino_ok(const ConvParams& c, size_t w, bool has_x2, bool has_drop) { return wino_mode(c, w, has_x2, has_drop) != 0; }
-  // generic conv over the virtual concat (x0|x1); residual is the concat view (r0|r1)
-  int conv(int x0, int x1, int Cout, int ksize, int stride, int ups, int act_mode, size_t w, bool has_bias,
-           size_t bias, int film_row, int r0, int r1, bool want_stats, int q0 = -1, int q1 = -1, size_t qw = 0,
-           size_t qb = 0, int drop_key = -1) {
+  // generic conv over the virtual concat (x0|x1); residual is the concat view (r0|r1).  Emission only: choose_conv picks the kernel
+  int conv(const ConvSpec& s) {
+    const int x0 = s.x0, x1 = s.x1, Cout = s.Cout, ksize = s.ksize;
+    const bool has_bias = s.bias != NO_PARAM, has_q = s.q0 >= 0;
+    const size_t bias = has_bias ? s.bias : 0;
     const int C0 = T[x0].C, C1 = x1 >= 0 ? T[x1].C : 0;
-    const int Hi = T[x0].H << ups, Wi = T[x0].W << ups;
-    const int pad = ksize / 2;
-    const int Ho = (Hi + 2 * pad - ksize) / stride + 1, Wo = (Wi + 2 * pad - ksize) / stride + 1;
-    const int out = make(Cout, Ho, Wo);
     Op o; o.kind = OP_CONV;
     ConvParams& c = o.cp;
-    memset(&c, 0, sizeof(c));
-    c.C0 = C0; c.C1 = C1;
-    c.B = B; c.Hs = T[x0].H; c.Ws = T[x0].W; c.ups = ups; c.stride = stride; c.ksize = ksize;
-    c.Ho = Ho; c.Wo = Wo; c.Cout = Cout; c.act = act_mode;
-    c.film_stride = P->F;
-    c.RC0 = r0 >= 0 ? T[r0].C : 0; c.RC1 = r1 >= 0 ? T[r1].C : 0;
-    c.ksplit = 1;
+    c = conv_shape(B, T[x0].H, T[x0].W, s.ups, s.stride, ksize, C0, C1, Cout);
+    const int Ho = c.Ho, Wo = c.Wo;
+    const int out = make(Cout, Ho, Wo);
+    c.act = s.act; c.film_stride = P->F;
+    c.RC0 = s.r0 >= 0 ? T[s.r0].C : 0; c.RC1 = s.r1 >= 0 ? T[s.r1].C : 0;
     o.a = T[x0].off; o.has_src1 = x1 >= 0; if (x1 >= 0) o.b = T[x1].off;
-    o.p0 = w; o.has_bias = has_bias; o.p1 = bias;
-    o.has_film = film_row >= 0; o.i0 = film_row;
-    o.has_res = r0 >= 0; if (r0 >= 0) o.c = T[r0].off;
-    o.has_res1 = r1 >= 0; if (r1 >= 0) o.d = T[r1].off;
+    o.p0 = s.w; o.has_bias = has_bias; o.p1 = bias;
+    o.has_film = s.film_row >= 0; o.i0 = s.film_row;
+    o.has_res = s.r0 >= 0; if (s.r0 >= 0) o.c = T[s.r0].off;
+    o.has_res1 = s.r1 >= 0; if (s.r1 >= 0) o.d = T[s.r1].off;
     o.e = T[out].off;
-    o.tile_cfg = P->tile_cfg; o.ksplit = P->ksplit;
-    o.ss_rel = act_mode ? cur_ss : 0;
-    o.has_drop = train && drop_key >= 0; o.drop_key = (unsigned)(drop_key >= 0 ? drop_key : 0);
-    // opt-in: the 3 x bf16 split MFMA instantiation of the 8-wave tile wherever it fits (inference plans only)
-    {
-      HaloGeom sg;
-      if (P->split_bf16 && !train && o.tile_cfg == 0 && ksize == 3 && stride == 1 && Cout > 64 && halo_geometry(c, 10, &sg))
-        o.tile_cfg = 10;
-    }
-    if (wino_mode(c, w, q0 >= 0, o.has_drop) == 2) {
-      o.tile_cfg = 11;
-      c.wino_split = wino2_fits(c) ? 2 : 3;
-      o.wino_off = P->derived_of[w] + wino_weight_floats(Cout, C0 + C1);
-    } else
-    if (wino_ok(c, w, q0 >= 0, o.has_drop)) {
-      o.tile_cfg = 11;
-      o.wino_off = P->derived_of[w];
-      // plan option wino_split: the 3 x bf16 split instantiation where it exists (the one-image tile; training plan and
-      // train-mode dropout included); its filters sit behind the conv's fp32 ones
-      WinoGeom wg;
-      if (P->wino_split && wino_geometry(c, &wg) && (wg.NB == 1 || (P->wino_split8 && !o.has_drop))) {
-        c.wino_split = (P->wino2 && !o.has_drop && wg.NB == 1) ? 2 : 1;        // (2: the 8 x 16 tile of conv3x3_wino2.hip)
-        o.wino_off += wino_weight_floats(Cout, C0 + C1);
-      }
-    }
-    // read by conv_pick / conv_forward only when the conv lands on the im2col kernel; the 9-tap layers with Cout <= 64 (Downsample
-    // of the first level) stay on the fp32 MFMA, which is faster there (67 vs 81 us in the forward)
-    c.igemm_split = (P->gemm_split && !(ksize == 3 && Cout <= 64)) ? 1 : 0;
-    // (... unless the plain GEMM kernel takes the layer on its 64-column tile: plan options gemm2 + gemm_s2 + gemm_n64, below)
-    if (P->gemm_split && P->gemm2 && P->gemm_s2 && P->gemm_n64 && ksize == 3 && stride == 2 && P->wsplit_of.count(w) && gemm1x1_fits(c, 2)) c.igemm_split = 1;
-    conv_pick(c, o.tile_cfg, o.ksplit);
-    if (P->gemm_tile >= 1 && P->gemm_tile <= 4 && o.tile_cfg >= 1 && o.tile_cfg <= 4 && P->tile_cfg == 0) {
-      o.tile_cfg = P->gemm_tile; o.ksplit = P->ksplit;       // A/B knob: one im2col tile for every conv of that kernel
-      conv_pick(c, o.tile_cfg, o.ksplit);
-    }
-    if (c.igemm_split && o.tile_cfg >= 1 && o.tile_cfg <= 4 && P->gemm2 && P->tile_cfg == 0 && P->gemm_tile == 0 && P->wsplit_of.count(w)) {
-      // plan option gemm2: 1x1 stride-1 convs -- and Downsample's 3x3 stride-2 ones -- the plain GEMM kernel fits (gemm1x1.hip)
-      if (gemm1x1_fits(c, 2) && (ksize == 1 || P->gemm_s2) && (!(Cout & 127) || P->gemm_n64)) {
-        o.tile_cfg = 22; o.ksplit = P->ksplit;
-        conv_pick(c, o.tile_cfg, o.ksplit);
-        o.has_wsplit = true; o.wsplit_off = P->wsplit_of[w];
-      }
-    }
-    if (c.igemm_split && o.tile_cfg >= 1 && o.tile_cfg <= 4 && P->gemm_wpre && P->wsplit_of.count(w)) {
-      o.has_wsplit = true; o.wsplit_off = P->wsplit_of[w];       // the SPLIT tile reads its weights pre-split from the derived buffer
-    }
-    if (o.has_drop && o.tile_cfg == 9) {       // no dropout instantiation of the 8-wave tile
-      o.tile_cfg = 5; o.ksplit = P->ksplit;
-      conv_pick(c, o.tile_cfg, o.ksplit);
-    }
-    // dropout convs on the 256x64 tile run its 8-wave form (conv3x3_halo_forward); SR3_DROP_CFG5 forces the
-    // half-empty 128x128 tile instead (A/B knob)
-    static const bool use5 = getenv("SR3_DROP_CFG5") != nullptr;
-    if (o.has_drop && o.tile_cfg == 6 && use5) {
-      o.tile_cfg = 5; o.ksplit = P->ksplit;
-      conv_pick(c, o.tile_cfg, o.ksplit);
-    }
-    // opt-in: run the halo-tile convs on the 3 x bf16 split MFMA instantiations (inference plans only)
-    if (P->split_bf16 && !train && o.tile_cfg == 5) o.tile_cfg = 7;
-    else if (P->split_bf16 && !train && o.tile_cfg == 9) o.tile_cfg = 10;
-    else if (P->split_bf16 && !train && o.tile_cfg == 6) o.tile_cfg = 8;
+    o.ss_rel = s.act ? cur_ss : 0;
+    o.has_drop = train && s.drop_key >= 0; o.drop_key = (unsigned)(s.drop_key >= 0 ? s.drop_key : 0);
+    const ConvChoice ch = choose_conv(P, c, s.w, has_q, o.has_drop, train);
+    o.tile_cfg = ch.tile_cfg; o.ksplit = ch.ksplit; c.wino_split = ch.wino_split; c.igemm_split = ch.igemm_split;
+    o.wino_off = ch.wino_off; o.has_wsplit = ch.has_wsplit; o.wsplit_off = ch.wsplit_off;
     if (train) {
       Rec r;
-      r.kind = R_CONV; r.x0 = x0; r.x1 = x1; r.out = out; r.r0 = r0; r.r1 = r1; r.q0 = q0; r.q1 = q1;
-      r.ksize = ksize; r.stride = stride; r.ups = ups; r.act = act_mode; r.film_row = film_row;
-      r.w = w; r.bias = bias; r.has_bias = has_bias; r.qw = qw; r.qb = qb; r.has_q = q0 >= 0;
+      r.kind = R_CONV; r.x0 = x0; r.x1 = x1; r.out = out; r.r0 = s.r0; r.r1 = s.r1; r.q0 = s.q0; r.q1 = s.q1;
+      r.ksize = ksize; r.stride = s.stride; r.ups = s.ups; r.act = s.act; r.film_row = s.film_row;
+      r.w = s.w; r.bias = bias; r.has_bias = has_bias; r.qw = s.qw; r.qb = s.qb; r.has_q = has_q;
       r.gamma = cur_gamma; r.beta = cur_beta; r.ss_off = cur_ss; r.mr_off = cur_mr;
       r.has_drop = o.has_drop; r.drop_key = o.drop_key;
       P->recs.push_back(r);
       // scratch the backward of this conv needs
       const size_t cin = (size_t)(C0 + C1);
-      max_dA = std::max(max_dA, (size_t)B * Hi * Wi * cin * sizeof(float));
+      max_dA = std::max(max_dA, (size_t)B * (T[x0].H << s.ups) * (T[x0].W << s.ups) * cin * sizeof(float));
       max_wt = std::max(max_wt, (size_t)Cout * ksize * ksize * cin * sizeof(float));
-      if (q0 >= 0) {
-        const size_t cq = (size_t)T[q0].C + (q1 >= 0 ? T[q1].C : 0);
+      if (has_q) {
+        const size_t cq = (size_t)T[s.q0].C + (s.q1 >= 0 ? T[s.q1].C : 0);
         max_dq = std::max(max_dq, (size_t)B * Ho * Wo * cq * sizeof(float));
         max_wt = std::max(max_wt, (size_t)Cout * cq * sizeof(float));
       }
-      if (stride == 2) max_z = std::max(max_z, (size_t)B * 4 * Ho * Wo * Cout * sizeof(float));
+      if (s.stride == 2) max_z = std::max(max_z, (size_t)B * 4 * Ho * Wo * Cout * sizeof(float));
     }
-    if (q0 >= 0) {   // fused 1x1 segment (res_conv); caller checked can_fuse_x2()
-      c.x2_C0 = T[q0].C; c.x2_C1 = q1 >= 0 ? T[q1].C : 0;
-      o.has_x2 = true; o.g = T[q0].off; o.has_x21 = q1 >= 0; if (q1 >= 0) o.h = T[q1].off;
-      o.p2 = qw; o.p3 = qb;
+    if (has_q) {   // fused 1x1 segment (res_conv); caller checked fuses_res_conv()
+      c.x2_C0 = T[s.q0].C; c.x2_C1 = s.q1 >= 0 ? T[s.q1].C : 0;
+      o.has_x2 = true; o.g = T[s.q0].off; o.has_x21 = s.q1 >= 0; if (s.q1 >= 0) o.h = T[s.q1].off;
+      o.p2 = s.qw; o.p3 = s.qb;
       flops += 2.0 * B * Ho * Wo * (double)Cout * (double)(c.x2_C0 + c.x2_C1);
     }
     if (o.ksplit > 1) max_scratch = std::max(max_scratch, (size_t)o.ksplit * B * Ho * Wo * Cout * sizeof(float));
     // split-K convs leave the statistics to the (cheap, small-tensor) stand-alone pass
-    if (want_stats && P->fuse_stats && o.ksplit == 1 && o.tile_cfg == 11) {
+    if (s.want_stats && P->fuse_stats && o.ksplit == 1 && o.tile_cfg == 11) {
       WinoGeom wg;
       wino_geometry(c, &wg);
       stat_slot(out, wino_stats_slices(wg));
       o.has_ostat = true; o.f = T[out].stat_off;
-    } else if (want_stats && P->fuse_stats && o.ksplit == 1 && o.tile_cfg >= 5) {
+    } else if (s.want_stats && P->fuse_stats && o.ksplit == 1 && o.tile_cfg >= 5) {
       HaloGeom hg;
       if (halo_geometry(c, o.tile_cfg, &hg)) {
         stat_slot(out, halo_stats_slices(hg));
         o.has_ostat = true; o.f = T[out].stat_off;
       }
-    } else if (want_stats && P->fuse_stats && o.ksplit > 1) {
+    } else if (s.want_stats && P->fuse_stats && o.ksplit > 1) {
       const int rpb = splitk_rows_per_block(c, true);      // statistics come out of the split-K reduce
       if (rpb > 0) {
         stat_slot(out, (Ho * Wo) / rpb);
@@ -554,35 +546,16 @@ struct Builder {
     flops += 2.0 * B * Ho * Wo * (double)Cout * (double)(C0 + C1) * ksize * ksize;
     return out;
   }
-  // fork_side: is res_conv its own launch in this block (block2's conv has no fused 1x1 segment)?  Same rule as can_fuse_x2, asked before h1 exists
-  bool res_conv_is_own_launch(int x0, const ResLayer& R) {
-    if (!P->fuse_res) return true;
-    ConvParams c;
-    memset(&c, 0, sizeof(c));
-    c.C0 = R.cout; c.B = B; c.Hs = T[x0].H; c.Ws = T[x0].W; c.stride = 1; c.ksize = 3;
-    c.Ho = T[x0].H; c.Wo = T[x0].W; c.Cout = R.cout;
-    c.act = 2;
-    if (wino_ok(c, R.c2_w, false, train)) return true;
-    int cfg = P->tile_cfg, ks = P->ksplit;
-    conv_pick(c, cfg, ks);
-    return !(cfg >= 5 && ks == 1);
-  }
-  // can block2's conv run on the halo kernel (which can take res_conv as a second K-segment)?
-  bool can_fuse_x2(int h1, int Cout, size_t w) {
+  // Does block2's conv of this block -- on a map the size of tensor `at` -- take res_conv as a second K-segment?  Only the unsplit halo kernel:
+  // the Winograd kernel has no second segment (training plan included), and under split-K the fused segment runs in the last split only (50
+  // k-steps there vs 18 in the others for a 1024-channel res_conv at 8x8: measured 43 TF).  Otherwise res_conv is its own 1x1 GEMM and joins
+  // as a residual.  Asked by fork_side before h1 exists, and again when block2's conv is emitted: one rule, the head of choose_conv
+  bool fuses_res_conv(int at, const ResLayer& R) {
     if (!P->fuse_res) return false;
-    ConvParams c;
-    memset(&c, 0, sizeof(c));
-    c.C0 = T[h1].C; c.B = B; c.Hs = T[h1].H; c.Ws = T[h1].W; c.stride = 1; c.ksize = 3;
-    c.Ho = T[h1].H; c.Wo = T[h1].W; c.Cout = Cout;
-    // the Winograd kernel has no second K-segment: res_conv runs as its own 1x1 GEMM and joins as a residual (round 3: also
-    // in the training plan, whose block2 conv runs the Winograd kernel's dropout instantiation)
+    ConvParams c = conv_shape(B, T[at].H, T[at].W, 0, 1, 3, R.cout, 0, R.cout);
     c.act = 2;
-    if (wino_ok(c, w, false, train)) return false;
-    int cfg = P->tile_cfg, ks = P->ksplit;
-    conv_pick(c, cfg, ks);
-    // under split-K the fused segment runs in the last split only (50 k-steps there vs 18 in the others for a
-    // 1024-channel res_conv at 8x8: measured 43 TF): small-M layers keep res_conv as its own 1x1 GEMM
-    return cfg >= 5 && ks == 1;
+    const ConvChoice ch = choose_conv(P, c, R.c2_w, false, train, train, RULE_HEAD);
+    return !ch.wino_mode && ch.tile_cfg >= 5 && ch.ksplit == 1;
   }
   std::string refused;     // inference: the first layer no kernel can run at this geometry (build_forward refuses the plan with it)
   int n_side = 0;          // plan option fork_side: ops handed to the side stream so far (Op::side_id)
@@ -591,32 +564,37 @@ struct Builder {
     // plan option fork_side (inference): res_conv reads only the block input, so it is emitted HERE -- behind the fold, in front of block1's
     // conv -- and launched on the side stream; block2's conv, which adds it as its residual, waits for it.  Only unsplit: a split-K res_conv
     // would share the slab region with block1's conv.  (The fold stays where fold_fuse looks for it: behind the op that completes x.)
+    const ConvSpec res_conv = {.x0 = x0, .x1 = x1, .Cout = R.cout, .ksize = 1, .w = R.rc_w, .bias = R.rc_b};
     int r_side = -1, r_id = -1;
-    if (R.has_rc && P->fork_side && !train && res_conv_is_own_launch(x0, R)) {
-      r_side = conv(x0, x1, R.cout, 1, 1, 0, 0, R.rc_w, true, R.rc_b, -1, -1, -1, false);
+    if (R.has_rc && P->fork_side && !train && !fuses_res_conv(x0, R)) {
+      r_side = conv(res_conv);
       if (ops.back().kind == OP_CONV && ops.back().ksplit == 1) { r_id = n_side++; ops.back().side_id = r_id; }
     }
-    const int h1 = conv(x0, x1, R.cout, 3, 1, 0, 2, R.c1_w, true, R.c1_b, R.film_off, -1, -1, true);
+    const int h1 = conv({.x0 = x0, .x1 = x1, .Cout = R.cout, .act = 2, .w = R.c1_w, .bias = R.c1_b, .film_row = R.film_off, .want_stats = true});
     fold(h1, -1, R.gn2_w, R.gn2_b);
+    // block2's conv; what it adds: res_conv's output (its own launch), res_conv as a fused K-segment over the block input, or the input itself
+    ConvSpec block2 = {.x0 = h1, .Cout = R.cout, .act = 2, .w = R.c2_w, .bias = R.c2_b, .want_stats = true, .drop_key = R.film_off};
     int out;
     if (r_side >= 0) {
-      out = conv(h1, -1, R.cout, 3, 1, 0, 2, R.c2_w, true, R.c2_b, -1, r_side, -1, true, -1, -1, 0, 0, R.film_off);
+      block2.r0 = r_side;
+      out = conv(block2);
       if (r_id >= 0) ops[last_conv_op].wait_id = r_id;
       drop(r_side);
-    } else
-    if (R.has_rc && can_fuse_x2(h1, R.cout, R.c2_w)) {
-      out = conv(h1, -1, R.cout, 3, 1, 0, 2, R.c2_w, true, R.c2_b, -1, -1, -1, true, x0, x1, R.rc_w, R.rc_b, R.film_off);
+    } else if (R.has_rc && fuses_res_conv(h1, R)) {
+      block2.q0 = x0; block2.q1 = x1; block2.qw = R.rc_w; block2.qb = R.rc_b;
+      out = conv(block2);
     } else if (R.has_rc) {
-      const int r = conv(x0, x1, R.cout, 1, 1, 0, 0, R.rc_w, true, R.rc_b, -1, -1, -1, false);
-      out = conv(h1, -1, R.cout, 3, 1, 0, 2, R.c2_w, true, R.c2_b, -1, r, -1, true, -1, -1, 0, 0, R.film_off);
-      drop(r);
+      block2.r0 = conv(res_conv);
+      out = conv(block2);
+      drop(block2.r0);
     } else {
-      out = conv(h1, -1, R.cout, 3, 1, 0, 2, R.c2_w, true, R.c2_b, -1, x0, x1, true, -1, -1, 0, 0, R.film_off);
+      block2.r0 = x0; block2.r1 = x1;
+      out = conv(block2);
     }
     drop(h1);
     if (R.attn) {
       fold(out, -1, R.an_w, R.an_b);
-      const int qkv = conv(out, -1, 3 * R.cout, 1, 1, 0, 1, R.qkv_w, false, 0, -1, -1, -1, false);
+      const int qkv = conv({.x0 = out, .Cout = 3 * R.cout, .ksize = 1, .act = 1, .w = R.qkv_w});
       const int o = make(R.cout, T[out].H, T[out].W);
       Op a; a.kind = OP_ATTN;
       a.a = T[qkv].off; a.b = T[o].off; a.i0 = T[out].H * T[out].W; a.i1 = R.cout;
@@ -631,7 +609,7 @@ struct Builder {
       if (train) { Rec r; r.kind = R_ATTN; r.qkv = qkv; r.o = o; P->recs.push_back(r); }
       flops += 4.0 * B * (double)a.i0 * (double)a.i0 * R.cout;
       drop(qkv);
-      const int out2 = conv(o, -1, R.cout, 1, 1, 0, 0, R.ao_w, true, R.ao_b, -1, out, -1, true);
+      const int out2 = conv({.x0 = o, .Cout = R.cout, .ksize = 1, .w = R.ao_w, .bias = R.ao_b, .r0 = out, .want_stats = true});
       drop(o);
       drop(out);
       out = out2;
@@ -672,7 +650,7 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
     } else if (L.kind == 1) {
       cur = bld.res_block(cur, -1, L.res);   // the input stays alive: it is a skip feature
     } else {
-      cur = bld.conv(cur, -1, L.cout, 3, 2, 0, 0, L.w, true, L.b, -1, -1, -1, true);
+      cur = bld.conv({.x0 = cur, .Cout = L.cout, .stride = 2, .w = L.w, .bias = L.b, .want_stats = true});
     }
     feats.push_back(cur);
     tap(L.name, cur);
@@ -695,7 +673,7 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
       bld.drop(cur);
       bld.drop(skip);
     } else {
-      nxt = bld.conv(cur, -1, L.cout, 3, 1, 1, 0, L.w, true, L.b, -1, -1, -1, true);
+      nxt = bld.conv({.x0 = cur, .Cout = L.cout, .ups = 1, .w = L.w, .bias = L.b, .want_stats = true});
       bld.drop(cur);
     }
     cur = nxt;
@@ -735,7 +713,7 @@ void layout_derived(sr3_plan* P) {
       else if (L.kind == 3) reg(L.w, L.cout, L.cin);
     }
   // the im2col SPLIT tiles' weights, pre-split (plan option gemm_split): res_conv and the attention projections (1x1), Downsample
-  // (3x3 stride 2; Cout <= 64 stays on the fp32 MFMA: Builder::conv)
+  // (3x3 stride 2; Cout <= 64 stays on the fp32 MFMA: choose_conv)
   P->wsplits.clear();
   P->wsplit_of.clear();
   if (P->gemm_split && (P->gemm_wpre || P->gemm2)) {
@@ -991,22 +969,16 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
   size_t max_dA = bld.max_dA, max_wt = bld.max_wt, max_slab = 0, max_part = 0, max_dwtmp = 0, max_wu = 0;
   size_t max_bscratch = 0;                    // split-K slabs of the data-gradient convs
   for (const Rec& r : P->recs) {
-    ConvParams c;
-    memset(&c, 0, sizeof(c));
     if (r.kind == R_CONV) {
       const Tensor& x0 = P->ttens[r.x0];
       const Tensor& o = P->ttens[r.out];
-      c.C0 = x0.C; c.C1 = r.x1 >= 0 ? P->ttens[r.x1].C : 0; c.B = B; c.Hs = x0.H; c.Ws = x0.W; c.ups = r.ups;
-      c.stride = r.stride; c.ksize = r.ksize; c.Ho = o.H; c.Wo = o.W; c.Cout = o.C;
+      ConvParams c = conv_shape(B, x0.H, x0.W, r.ups, r.stride, r.ksize, x0.C, r.x1 >= 0 ? P->ttens[r.x1].C : 0, o.C);
       if (r.act) { c.C0 = c.C0 + c.C1; c.C1 = 0; }     // run time: the activated input is materialised (single source)
       max_slab = std::max(max_slab, wgrad_slab_bytes(c, nullptr));
       max_part = std::max(max_part, act_bwd_part_bytes(B, x0.H * x0.W, c.C0 + c.C1));
       max_part = std::max(max_part, (size_t)B * chan_stats_slices(B, o.H * o.W, o.C) * o.C * 2 * sizeof(double));
       // dgrad conv: src = dOut (or its zero-inserted version), Cout' = Cin
-      ConvParams g;
-      memset(&g, 0, sizeof(g));
-      g.C0 = o.C; g.B = B; g.Hs = x0.H << r.ups; g.Ws = x0.W << r.ups; g.stride = 1; g.ksize = r.ksize;
-      g.Ho = g.Hs; g.Wo = g.Ws; g.Cout = c.C0 + c.C1;
+      ConvParams g = conv_shape(B, x0.H << r.ups, x0.W << r.ups, 0, 1, r.ksize, o.C, 0, c.C0 + c.C1);
       g.igemm_split = (P->gemm_split && !(g.ksize == 3 && g.Cout <= 64)) ? 1 : 0;      // (what dgrad_conv launches with: train_plan.hip)
       max_bscratch = std::max(max_bscratch, conv_splitk_bytes(g, 0, 0));
       {   // the data gradient of a 3x3 conv runs on the Winograd kernel where it fits: its slabs and transformed filters
@@ -1018,35 +990,24 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
         }
       }
       if (r.has_q) {
-        ConvParams q;
-        memset(&q, 0, sizeof(q));
-        q.C0 = P->ttens[r.q0].C; q.C1 = r.q1 >= 0 ? P->ttens[r.q1].C : 0; q.B = B; q.Hs = o.H; q.Ws = o.W; q.stride = 1;
-        q.ksize = 1; q.Ho = o.H; q.Wo = o.W; q.Cout = o.C;
+        const ConvParams q = conv_shape(B, o.H, o.W, 0, 1, 1, P->ttens[r.q0].C, r.q1 >= 0 ? P->ttens[r.q1].C : 0, o.C);
         max_slab = std::max(max_slab, wgrad_slab_bytes(q, nullptr));
-        ConvParams gq;
-        memset(&gq, 0, sizeof(gq));
-        gq.C0 = o.C; gq.B = B; gq.Hs = o.H; gq.Ws = o.W; gq.stride = 1; gq.ksize = 1; gq.Ho = o.H; gq.Wo = o.W;
-        gq.Cout = q.C0 + q.C1;
-        max_bscratch = std::max(max_bscratch, conv_splitk_bytes(gq, 0, 0));
+        max_bscratch = std::max(max_bscratch, conv_splitk_bytes(conv_shape(B, o.H, o.W, 0, 1, 1, o.C, 0, q.C0 + q.C1), 0, 0));
       }
     } else if (r.kind == R_CONV_IN) {
-      c.C0 = 8; c.B = B; c.Hs = S; c.Ws = S; c.stride = 1; c.ksize = 3; c.Ho = S; c.Wo = S; c.Cout = P->ttens[r.out].C;
+      const ConvParams c = conv_shape(B, S, S, 0, 1, 3, 8, 0, P->ttens[r.out].C);
       max_slab = std::max(max_slab, wgrad_slab_bytes(c, nullptr));
       max_dwtmp = std::max(max_dwtmp, (size_t)c.Cout * 9 * 8 * sizeof(float));
       max_part = std::max(max_part, (size_t)B * chan_stats_slices(B, S * S, c.Cout) * c.Cout * 2 * sizeof(double));
     } else if (r.kind == R_CONV_OUT) {
       const Tensor& x0 = P->ttens[r.x0];
-      c.C0 = x0.C; c.B = B; c.Hs = S; c.Ws = S; c.stride = 1; c.ksize = 3; c.Ho = S; c.Wo = S; c.Cout = 4;
-      max_slab = std::max(max_slab, wgrad_slab_bytes(c, nullptr));
+      max_slab = std::max(max_slab, wgrad_slab_bytes(conv_shape(B, S, S, 0, 1, 3, x0.C, 0, 4), nullptr));
       max_dwtmp = std::max(max_dwtmp, (size_t)4 * 9 * x0.C * sizeof(float));
       max_dA = std::max(max_dA, (size_t)B * S * S * x0.C * sizeof(float));
       max_wt = std::max(max_wt, (size_t)x0.C * 9 * 4 * sizeof(float));
       max_part = std::max(max_part, act_bwd_part_bytes(B, S * S, x0.C));
       max_part = std::max(max_part, (size_t)B * chan_stats_slices(B, S * S, 4) * 4 * 2 * sizeof(double));
-      ConvParams g;
-      memset(&g, 0, sizeof(g));
-      g.C0 = 4; g.B = B; g.Hs = S; g.Ws = S; g.stride = 1; g.ksize = 3; g.Ho = S; g.Wo = S; g.Cout = x0.C;
-      max_bscratch = std::max(max_bscratch, conv_splitk_bytes(g, 0, 0));
+      max_bscratch = std::max(max_bscratch, conv_splitk_bytes(conv_shape(B, S, S, 0, 1, 3, 4, 0, x0.C), 0, 0));
     }
   }
   for (const Rec& r : P->recs)                // ... and the dK / dV slabs of the attention backward (attention_bwd.hip)
@@ -1174,8 +1135,7 @@ int sr3_plan_op_info(sr3_plan* plan, int batch, int index, sr3_op_info* out) {
   out->kind = (int)o.kind * 10;
   if (o.kind == OP_CONV) {
     const ConvParams& c = o.cp;
-    out->tile_cfg = (o.tile_cfg == 11 && o.cp.wino_split == 3) ? 23 : (o.tile_cfg == 11 && o.cp.wino_split) ? 11 + o.cp.wino_split
-                    : (o.tile_cfg >= 1 && o.tile_cfg <= 4 && o.cp.igemm_split) ? (o.has_wsplit ? 17 : 13) + o.tile_cfg : o.tile_cfg;
+    out->tile_cfg = tile_encode(o.tile_cfg, c.wino_split, c.igemm_split, o.has_wsplit);
     out->ksplit = o.ksplit;
     out->ksize = c.ksize; out->stride = c.stride; out->upsample = c.ups;
     out->cin = c.C0 + c.C1; out->cout = c.Cout; out->h_out = c.Ho; out->w_out = c.Wo;
@@ -1443,225 +1403,6 @@ int sr3_unet_forward_profile(sr3_plan* plan, const float* x_nchw, const float* c
   for (auto& e : ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : mid) if (e) (void)hipEventDestroy(e);
   return rc;
-}
-
-int sr3_p_sample_step(float* x, const float* eps, const float* z, const float* ta, const float* tb, const float* tc1,
-                      const float* tc2, const float* tsig, const int* step_dev, const int64_t* t_per_sample,
-                      int step_host, int batch, int elems_per_image, void* stream) {
-  if (!x || !eps || !ta || !tb || !tc1 || !tc2 || !tsig) { set_error("null argument"); return SR3_E_BADARG; }
-  StepTables t{ta, tb, tc1, tc2, tsig};
-  return p_sample_update(x, eps, z, t, step_dev, t_per_sample, step_host, batch, elems_per_image,
-                         static_cast<hipStream_t>(stream));
-}
-int sr3_p_sample_step_ex(float* x, const float* eps, const float* z, const float* ta, const float* tb, const float* tc1,
-                         const float* tc2, const float* tsig, const int* step_dev, const int64_t* t_per_sample,
-                         int step_host, int batch, int elems_per_image, int clip_denoised, void* stream) {
-  if (!x || !eps || !ta || !tb || !tc1 || !tc2 || !tsig) { set_error("null argument"); return SR3_E_BADARG; }
-  StepTables t{ta, tb, tc1, tc2, tsig};
-  return p_sample_update(x, eps, z, t, step_dev, t_per_sample, step_host, batch, elems_per_image,
-                         static_cast<hipStream_t>(stream), clip_denoised != 0);
-}
-int sr3_step_decrement(int* step_dev, void* stream) { return step_decrement(step_dev, static_cast<hipStream_t>(stream)); }
-int sr3_q_sample(const float* x0, const float* z, const float* ca, const float* cb, int batch, int elems_per_image,
-                 float* out, void* stream) {
-  if (!x0 || !z || !ca || !cb || !out) { set_error("null argument"); return SR3_E_BADARG; }
-  return q_sample(x0, z, ca, cb, batch, elems_per_image, out, static_cast<hipStream_t>(stream));
-}
-
-int sr3_conv_f32(const float* src0, int C0, const float* src1, int C1, int B, int Hs, int Ws, int ups, int stride,
-                 int ksize, int Cout, const float* w, const float* bias, const float* ss, int act, const float* film,
-                 int film_stride, const float* res0, int RC0, const float* res1, int RC1, float* out, double* out_stats,
-                 int tile_cfg, int ksplit, void* scratch, size_t scratch_bytes, void* stream) {
-  if (!src0 || !w || !out) { set_error("null argument"); return SR3_E_BADARG; }
-  ConvParams c;
-  memset(&c, 0, sizeof(c));
-  c.src0 = src0; c.src1 = src1; c.C0 = C0; c.C1 = src1 ? C1 : 0;
-  c.B = B; c.Hs = Hs; c.Ws = Ws; c.ups = ups; c.stride = stride; c.ksize = ksize;
-  const int pad = ksize / 2;
-  c.Ho = ((Hs << ups) + 2 * pad - ksize) / stride + 1;
-  c.Wo = ((Ws << ups) + 2 * pad - ksize) / stride + 1;
-  c.Cout = Cout; c.w = w; c.bias = bias; c.ss = ss; c.act = act; c.film = film; c.film_stride = film_stride;
-  c.res0 = res0; c.res1 = res1; c.RC0 = res0 ? RC0 : 0; c.RC1 = res1 ? RC1 : 0;
-  c.out = out; c.ostat = out_stats; c.ksplit = 1;
-  const bool wsplit = tile_cfg == 12 || tile_cfg == 13 || tile_cfg == 23;     // tile 11 on the 3 x bf16 split instantiation (13: the 8 x 16 tile of conv3x3_wino2.hip; 23: its ragged form)
-  if (wsplit) { c.wino_split = tile_cfg == 23 ? 3 : tile_cfg - 11; tile_cfg = 11; }
-  if (tile_cfg >= 14 && tile_cfg <= 17) { c.igemm_split = 1; tile_cfg -= 13; }     // the im2col tiles 1-4 on their 3 x bf16 split instantiation
-  if (tile_cfg >= 18 && tile_cfg <= 22) {
-    // ... with the weights pre-split into bf16 planes (what a plan does, in its derived buffer): derived here, behind the split-K
-    // slabs in `scratch` (sr3_conv_scratch_bytes accounts for them).  22: the 1x1 GEMM kernel of gemm1x1.hip (64 x 128 tile)
-    c.igemm_split = 1;
-    if (tile_cfg == 22 && !gemm1x1_fits(c, 2)) { set_error("conv: the 1x1 GEMM kernel (tile 22) does not fit this problem"); return SR3_E_UNSUPPORTED; }
-    if (tile_cfg <= 21) tile_cfg -= 17;
-    const size_t slab = conv_splitk_bytes(c, tile_cfg, ksplit);
-    const size_t wb = igemm_wsplit_floats(Cout, ksize * ksize, c.C0 + c.C1) * sizeof(float);
-    if (!scratch || scratch_bytes < slab + wb) { set_error("conv: scratch too small for the pre-split weights (%zu < %zu)", scratch_bytes, slab + wb); return SR3_E_NOMEM; }
-    float* q = reinterpret_cast<float*>(static_cast<char*>(scratch) + slab);
-    const int rc = igemm_split_weights(w, Cout, ksize * ksize, c.C0 + c.C1, q, static_cast<hipStream_t>(stream));
-    if (rc) return rc;
-    c.w_split = q;
-    scratch_bytes = slab;
-  }
-  if (tile_cfg == 11 && (ksize != 3 || stride != 1)) { set_error("conv: the Winograd kernel does not fit this problem (3x3 stride 1 only)"); return SR3_E_UNSUPPORTED; }
-  if (tile_cfg == 11) {
-    // Winograd form through the per-op entry: the transformed filters are derived here, behind the split-K slabs in
-    // `scratch` (sr3_conv_scratch_bytes accounts for them); a plan keeps them in its derived buffer instead.
-    const size_t slab = conv_splitk_bytes(c, tile_cfg, ksplit);
-    const size_t ub = wino_weight_floats(Cout, c.C0 + c.C1, wsplit) * sizeof(float);
-    if (!scratch || scratch_bytes < slab + ub || ksize != 3) { set_error("conv: Winograd scratch too small (%zu < %zu)", scratch_bytes, slab + ub); return SR3_E_NOMEM; }
-    float* u = reinterpret_cast<float*>(static_cast<char*>(scratch) + slab);
-    const int rc = wino_transform_weights(w, Cout, c.C0 + c.C1, u, static_cast<hipStream_t>(stream), wsplit);
-    if (rc) return rc;
-    c.wino_u = u;
-#ifdef SR3_WINO_ABLATIONS
-    // tooling build only: room behind the filters for the kernel's phase time stamps (SR3_WINO_DBG=64, tools/wino_phases.py)
-    if (scratch_bytes >= slab + ub + (1u << 20)) c.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(u) + ub);
-#endif
-    scratch_bytes = slab;
-  }
-  return conv_forward(c, tile_cfg, ksplit, static_cast<float*>(scratch), scratch_bytes, static_cast<hipStream_t>(stream));
-}
-int sr3_block_conv_f32(const float* src0, int C0, const float* src1, int C1, int B, int H, int W, int Cout,
-                       const float* w, const float* bias, const float* ss, int act, const float* film, int film_stride,
-                       const float* x2_src0, int x2_C0, const float* x2_src1, int x2_C1, const float* x2_w,
-                       const float* x2_bias, float* out, double* out_stats, int tile_cfg, int ksplit, void* scratch,
-                       size_t scratch_bytes, void* stream) {
-  if (!src0 || !w || !out || !x2_src0 || !x2_w) { set_error("null argument"); return SR3_E_BADARG; }
-  ConvParams c;
-  memset(&c, 0, sizeof(c));
-  c.src0 = src0; c.src1 = src1; c.C0 = C0; c.C1 = src1 ? C1 : 0;
-  c.B = B; c.Hs = H; c.Ws = W; c.stride = 1; c.ksize = 3; c.Ho = H; c.Wo = W;
-  c.Cout = Cout; c.w = w; c.bias = bias; c.ss = ss; c.act = act; c.film = film; c.film_stride = film_stride;
-  c.out = out; c.ostat = out_stats; c.ksplit = 1;
-  c.x2_src0 = x2_src0; c.x2_src1 = x2_src1; c.x2_C0 = x2_C0; c.x2_C1 = x2_src1 ? x2_C1 : 0; c.x2_w = x2_w; c.x2_bias = x2_bias;
-  return conv_forward(c, tile_cfg, ksplit, static_cast<float*>(scratch), scratch_bytes, static_cast<hipStream_t>(stream));
-}
-int sr3_conv_dropout_f32(const float* src0, int C0, int B, int H, int W, int Cout, const float* w, const float* bias,
-                         const float* ss, int act, const float* film, int film_stride, const float* res0, int RC0,
-                         const float* x2_src0, int x2_C0, const float* x2_src1, int x2_C1, const float* x2_w,
-                         const float* x2_bias, float* out, double* out_stats, int tile_cfg, int ksplit, void* scratch,
-                         size_t scratch_bytes, unsigned drop_seed, float drop_p, void* stream) {
-  if (!src0 || !w || !out || !ss) { set_error("null argument"); return SR3_E_BADARG; }
-  if (drop_p < 0.f || drop_p >= 1.f) { set_error("drop_p out of range"); return SR3_E_BADARG; }
-  ConvParams c;
-  memset(&c, 0, sizeof(c));
-  c.src0 = src0; c.C0 = C0;
-  c.B = B; c.Hs = H; c.Ws = W; c.stride = 1; c.ksize = 3; c.Ho = H; c.Wo = W;
-  c.Cout = Cout; c.w = w; c.bias = bias; c.ss = ss; c.act = act; c.film = film; c.film_stride = film_stride;
-  c.res0 = res0; c.RC0 = res0 ? RC0 : 0;
-  c.out = out; c.ostat = out_stats; c.ksplit = 1;
-  if (x2_src0) {
-    if (!x2_w) { set_error("x2_src0 needs x2_w"); return SR3_E_BADARG; }
-    c.x2_src0 = x2_src0; c.x2_src1 = x2_src1; c.x2_C0 = x2_C0; c.x2_C1 = x2_src1 ? x2_C1 : 0; c.x2_w = x2_w; c.x2_bias = x2_bias;
-  }
-  // same mapping p -> (threshold, scale) as sr3_train_step
-  c.drop_seed = drop_seed;
-  dropout_consts(drop_p, &c.drop_thresh, &c.drop_scale);
-  const bool wsplit = tile_cfg == 12;         // 12 = tile 11 on the 3 x bf16 split instantiation
-  if (wsplit) { tile_cfg = 11; c.wino_split = 1; }
-  if (tile_cfg == 11) {       // Winograd form: the transformed filters are derived here, behind the split-K slabs (as sr3_conv_f32)
-    if (c.x2_w) { set_error("conv: the Winograd kernel has no fused 1x1 segment"); return SR3_E_UNSUPPORTED; }
-    const size_t slab = conv_splitk_bytes(c, tile_cfg, ksplit);
-    const size_t ub = wino_weight_floats(Cout, C0, wsplit) * sizeof(float);
-    if (!scratch || scratch_bytes < slab + ub) { set_error("conv: Winograd scratch too small (%zu < %zu)", scratch_bytes, slab + ub); return SR3_E_NOMEM; }
-    float* u = reinterpret_cast<float*>(static_cast<char*>(scratch) + slab);
-    const int rc = wino_transform_weights(w, Cout, C0, u, static_cast<hipStream_t>(stream), wsplit);
-    if (rc) return rc;
-    c.wino_u = u;
-    scratch_bytes = slab;
-  }
-  return conv_forward(c, tile_cfg, ksplit, static_cast<float*>(scratch), scratch_bytes, static_cast<hipStream_t>(stream));
-}
-unsigned sr3_dropout_threshold(float drop_p, float* scale_out) {
-  unsigned t = 0;
-  float s = 1.f;
-  if (drop_p > 0.f && drop_p < 1.f) dropout_consts(drop_p, &t, &s);
-  if (scale_out) *scale_out = s;
-  return t;
-}
-size_t sr3_conv_scratch_bytes(int B, int Ho, int Wo, int Cin, int Cout, int ksize, int tile_cfg, int ksplit) {
-  ConvParams c;
-  memset(&c, 0, sizeof(c));
-  c.B = B; c.Ho = Ho; c.Wo = Wo; c.C0 = Cin; c.Cout = Cout; c.ksize = ksize;
-  if ((tile_cfg >= 11 && tile_cfg <= 13) || tile_cfg == 23) {      // Winograd: the geometry (hence the split) needs the stride-1 input dims; + the derived filters
-    c.Hs = Ho; c.Ws = Wo; c.stride = 1;
-    if (tile_cfg == 23) c.wino_split = 3;      // (the ragged tile grid decides the automatic split)
-    return conv_splitk_bytes(c, 11, ksplit) + wino_weight_floats(Cout, Cin, tile_cfg >= 12) * sizeof(float);
-  }
-  size_t extra = 0;
-  if (tile_cfg >= 14 && tile_cfg <= 17) { c.igemm_split = 1; tile_cfg -= 13; }
-  if (tile_cfg == 22) {      // the GEMM kernel: 1x1 stride 1, or 3x3 stride 2 (ksize 3); pre-split weights behind the slabs
-    c.igemm_split = 1;
-    if (ksize == 3) { c.Hs = 2 * Ho; c.Ws = 2 * Wo; c.stride = 2; }
-    else { c.Hs = Ho; c.Ws = Wo; c.stride = 1; }
-    return conv_splitk_bytes(c, tile_cfg, ksplit) + igemm_wsplit_floats(Cout, ksize * ksize, Cin) * sizeof(float);
-  }
-  if (tile_cfg >= 18 && tile_cfg <= 21) {      // + the pre-split weights behind the slabs
-    c.igemm_split = 1; tile_cfg -= 17;
-    extra = igemm_wsplit_floats(Cout, ksize * ksize, Cin) * sizeof(float);
-  }
-  // the entry does not know the stride: take the larger of the stride-1 (halo kernel eligible) and the im2col sizing
-  const size_t a = conv_splitk_bytes(c, tile_cfg, ksplit);
-  c.Hs = Ho; c.Ws = Wo; c.stride = 1;
-  const size_t b = conv_splitk_bytes(c, tile_cfg, ksplit);
-  return (a > b ? a : b) + extra;
-}
-int sr3_groupnorm_stats_f32(const float* x, int B, int HW, int C, double* stat, void* stream) {
-  if (!x || !stat) { set_error("null argument"); return SR3_E_BADARG; }
-  return chan_stats(x, B, HW, C, stat, static_cast<hipStream_t>(stream));
-}
-int sr3_groupnorm_stats_slices(int B, int HW, int C) { return chan_stats_slices(B, HW, C); }
-int sr3_conv_stats_slices(int B, int Hs, int Ws, int ups, int Cin, int Cout, int tile_cfg, int ksplit) {
-  ConvParams c;
-  memset(&c, 0, sizeof(c));
-  c.B = B; c.Hs = Hs; c.Ws = Ws; c.ups = ups; c.stride = 1; c.ksize = 3; c.Ho = Hs << ups; c.Wo = Ws << ups;
-  c.Cout = Cout; c.C0 = Cin;
-  if (tile_cfg == 12 || tile_cfg == 13) { c.wino_split = tile_cfg - 11; tile_cfg = 11; }     // (13: the 8 x 16 tile, its own slice count)
-  if (tile_cfg == 23) { c.wino_split = 3; tile_cfg = 11; }                                    // (its ragged form: ceil tile grid)
-  if (tile_cfg >= 14 && tile_cfg <= 17) { c.igemm_split = 1; tile_cfg -= 13; }
-  if (tile_cfg >= 18 && tile_cfg <= 21) { c.igemm_split = 1; tile_cfg -= 17; }
-  conv_pick(c, tile_cfg, ksplit);
-  if (ksplit > 1) {
-    const int rpb = splitk_rows_per_block(c, true);
-    return rpb > 0 ? (c.Ho * c.Wo) / rpb : 0;
-  }
-  if (tile_cfg == 11) {
-    WinoGeom wg;
-    return wino_geometry(c, &wg) ? wino_stats_slices(wg) : 0;
-  }
-  HaloGeom g;
-  if (tile_cfg < 5 || !halo_geometry(c, tile_cfg, &g)) return 0;
-  return halo_stats_slices(g);
-}
-int sr3_groupnorm_fold_f32(const double* stat0, int C0, int T0, const double* stat1, int C1, int T1, int B, int HW,
-                           int groups, const float* gamma, const float* beta, float eps, float* ss, void* stream) {
-  if (!stat0 || !gamma || !beta || !ss) { set_error("null argument"); return SR3_E_BADARG; }
-  return gn_finalize(stat0, C0, T0, stat1, stat1 ? C1 : 0, stat1 ? T1 : 0, B, HW, groups, gamma, beta, eps, ss,
-                     static_cast<hipStream_t>(stream));
-}
-int sr3_attention_f32(const float* qkv, int B, int N, int C, float* out, void* stream) {
-  if (!qkv || !out) { set_error("null argument"); return SR3_E_BADARG; }
-  return attention_forward(qkv, B, N, C, out, static_cast<hipStream_t>(stream));
-}
-int sr3_attention_ex_f32(const float* qkv, int B, int N, int C, float* out, int split, void* stream) {
-  if (!qkv || !out) { set_error("null argument"); return SR3_E_BADARG; }
-  return attention_forward(qkv, B, N, C, out, static_cast<hipStream_t>(stream), split);
-}
-int sr3_film_embed_f32(int variant, int B, int inner, const float* level, const int64_t* timestep, const float* freq,
-                       const float* w1, const float* b1, const float* w2, const float* b2, const float* wf,
-                       const float* bf, int F, float* temb_scratch, float* film_out, void* stream) {
-  EmbedParams e;
-  memset(&e, 0, sizeof(e));
-  e.variant = variant; e.B = B; e.inner = inner; e.level = level; e.tstep = timestep; e.freq = freq;
-  e.w1 = w1; e.b1 = b1; e.w2 = w2; e.b2 = b2; e.wf = wf; e.bf = bf; e.F = F; e.temb = temb_scratch; e.film = film_out;
-  return embed_forward(e, static_cast<hipStream_t>(stream));
-}
-int sr3_conv_in_f32(const float* a, int Ca, const float* b, int Cb, int B, int H, int W, const float* w,
-                    const float* bias, int Cout, float* out, void* stream) {
-  return conv_in_nchw(a, Ca, b, b ? Cb : 0, B, H, W, w, bias, Cout, out, nullptr, static_cast<hipStream_t>(stream));
-}
-int sr3_conv_out_f32(const float* x, const float* ss, int B, int H, int W, int C, const float* w, const float* bias,
-                     int Cout, float* out, void* stream) {
-  return conv_out_nchw(x, ss, B, H, W, C, w, bias, Cout, out, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

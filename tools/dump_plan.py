@@ -21,7 +21,9 @@ TILE = {1: 'im2col 128x128', 2: 'im2col 128x64', 3: 'im2col 64x64', 4: 'im2col 6
         14: 'im2col 128x128 3 x bf16 split', 15: 'im2col 128x64 3 x bf16 split', 16: 'im2col 64x64 3 x bf16 split',
         17: 'im2col 64x128 3 x bf16 split', 18: 'im2col 128x128 3 x bf16 split, pre-split weights',
         19: 'im2col 128x64 3 x bf16 split, pre-split weights', 20: 'im2col 64x64 3 x bf16 split, pre-split weights',
-        21: 'im2col 64x128 3 x bf16 split, pre-split weights'}
+        21: 'im2col 64x128 3 x bf16 split, pre-split weights', 22: 'GEMM 64x128 / 64x64 3 x bf16 split (gemm1x1.hip)',
+        23: 'Winograd F(2x2,3x3) 3 x bf16 split (4 waves, ragged)', 24: 'attention, key-blocked (attention_long.hip)'}
+# (names of the public tile_cfg numbers: the one copy outside the codec of csrc/tile_code.h)
 
 
 def main():
@@ -45,7 +47,7 @@ def main():
                 ' +1x1 res_conv(%d)' % o['fused_res_conv_cin'] if o['fused_res_conv_cin'] else '',
                 ' +stats' if o['fused_output_stats'] else '', o['flops'] / 1e9)
         elif o['kind'] == 60:
-            d = 'N = %d, d = %d  %7.2f GFLOP' % (o['h_out'], o['cin'], o['flops'] / 1e9)
+            d = 'N = %d, d = %d%s  %7.2f GFLOP' % (o['h_out'], o['cin'], '  ' + TILE[24] if o['tile_cfg'] == 24 else '', o['flops'] / 1e9)
         else:
             d = ''
         print('%3d  %-28s %s' % (i, KIND[o['kind']], d))
