@@ -291,7 +291,8 @@ static bool wino_ragged_wins(const ConvParams& c) {
 // Which 3x3 stride-1 convs run on the Winograd kernels (plan option `winograd`; 0: none), train-mode dropout convs included; an explicit
 // tile_cfg / split_bf16 keep the direct halo kernels (the fused res_conv segment has no Winograd form: res_conv is then its own 1x1 GEMM)
 // 1: the tiles of today's rules (wino_geometry of the 8-wave kernel decides, *wg is that geometry; choose_conv then picks the instantiation);
-// 2: only at a geometry other than image_size x image_size (so the native launch list never moves), inference plans: a map the rule
+// 2: only at a geometry other than image_size x image_size (so the native launch list never moves), inference plans and -- plan option
+// train_geom -- the training forward's convs without dropout: a map the rule
 // above refuses on the two-workgroup kernel -- its plain form where the map is a whole multiple of the 8 x 16 tile, its RAGGED form
 // (plan option wino_ragged) where wino_ragged_wins says the padded tile beats the fallback
 static int wino_mode(const sr3_plan* P, const ConvParams& c, size_t w, bool has_x2, bool has_drop, bool train, WinoGeom* wg) {
@@ -299,7 +300,7 @@ static int wino_mode(const sr3_plan* P, const ConvParams& c, size_t w, bool has_
   if (has_drop && (c.C1 != 0 || c.ups != 0 || c.act == 0)) return 0;    // the dropout form: single source, no upsampling
   if (c.ksize != 3 || c.stride != 1 || !P->derived_of.count(w)) return 0;
   if (wino_geometry(c, wg)) return 1;
-  if (train || has_drop || plan_native_geometry(P) || !P->wino_split || !P->wino2) return 0;
+  if ((train && !P->train_geom) || has_drop || plan_native_geometry(P) || !P->wino_split || !P->wino2) return 0;
   ConvParams r = c;
   r.wino_split = wino2_fits(c) ? 2 : 3;
   if (r.wino_split == 3 && !(P->wino_ragged && wino_ragged_wins(c))) return 0;
@@ -598,8 +599,9 @@ struct Builder {
       const int o = make(R.cout, T[out].H, T[out].W);
       Op a; a.kind = OP_ATTN;
       a.a = T[qkv].off; a.b = T[o].off; a.i0 = T[out].H * T[out].W; a.i1 = R.cout;
-      if (!train && P->attn_long && !attention_fits(a.i0, R.cout)) a.tile_cfg = 24;       // the key-blocked kernel: any token count
-      else if (!train && refused.empty() && !attention_fits(a.i0, R.cout)) {
+      const bool geo = !train || P->train_geom;       // (a training plan off the native geometry exists under train_geom only)
+      if (geo && P->attn_long && !attention_fits(a.i0, R.cout)) a.tile_cfg = 24;       // the key-blocked kernel: any token count
+      else if (geo && refused.empty() && !attention_fits(a.i0, R.cout)) {
         char msg[256];
         snprintf(msg, sizeof(msg), "attention of %s: the %d x %d level has %d tokens, more than the attention kernel holds in LDS", R.name.c_str(),
                  T[out].H, T[out].W, a.i0);
@@ -624,7 +626,8 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
   std::vector<Op>& ops = bld.ops;
   const int B = bld.B;
   const int inner = d.inner_channel;
-  const int IH = bld.train ? d.image_size : plan_height(P), IW = bld.train ? d.image_size : plan_width(P);   // (training: native geometry only)
+  const bool geo = !bld.train || P->train_geom;      // (training: native geometry only, unless plan option train_geom)
+  const int IH = geo ? plan_height(P) : d.image_size, IW = geo ? plan_width(P) : d.image_size;
 
   { Op o; o.kind = OP_EMBED; ops.push_back(o); }
   bld.flops += 2.0 * B * (2.0 * 4 * inner * inner + (double)P->F * inner);
@@ -939,22 +942,53 @@ int run_forward(sr3_plan* P, const Regions& R, const float* x, const float* cond
 // training plan: the same forward walk with every activation kept and persistent GroupNorm tables,
 // a gradient mirror of the activation arena, and the scratch the backward walk needs
 // ---------------------------------------------------------------------------------------------
+bool dgrad_wino(const sr3_plan* P, ConvParams& g, WinoGeom* wg, bool* split_filters) {
+  g.wino_split = 0;
+  *split_filters = false;
+  if (!P->winograd || g.ksize != 3) return false;
+  // the data gradient has neither a prologue nor dropout, so every 3x3 stride-1 / zero-inserted stride-2 layer with H, W multiples
+  // of 16 qualifies (and the four-image 8 x 8 tile); the one-image tile on its 3 x bf16 split instantiation, as the forward
+  if (wino_geometry(g, wg)) {
+    *split_filters = P->wino_split && wg->NB == 1;
+    g.wino_split = *split_filters ? (P->wino2 ? 2 : 1) : 0;      // (2: the 8 x 16 tile of conv3x3_wino2.hip)
+    return true;
+  }
+  // off the native geometry (plan option train_geom): the two-workgroup kernel on the maps that rule refuses, plain where the map is a
+  // whole multiple of its 8 x 16 tile, ragged where wino_ragged_wins -- wino_mode's rule for the forward
+  if (!P->train_geom || plan_native_geometry(P) || !P->wino_split || !P->wino2) return false;
+  g.wino_split = wino2_fits(g) ? 2 : 3;
+  if ((g.wino_split == 3 && !(P->wino_ragged && wino_ragged_wins(g))) || !wino_geometry(g, wg)) { g.wino_split = 0; return false; }
+  *split_filters = true;
+  return true;
+}
+
 int build_train(sr3_plan* P, int B, int cond_channels) {
-  if (!plan_native_geometry(P)) {
+  if (!P->train_geom && !plan_native_geometry(P)) {
     set_error("training runs at image_size x image_size only: the plan's geometry is %d x %d (sr3_plan_set_geometry(plan, 0, 0) restores %d x %d)",
               plan_height(P), plan_width(P), P->d.image_size, P->d.image_size);
     return SR3_E_UNSUPPORTED;
   }
-  if (P->train_batch == B && P->train_cond == cond_channels) return SR3_OK;
+  // (the geometry is the native one here unless train_geom; every option that changes the plan resets train_batch: sr3_plan_set_option)
+  const int IH = plan_height(P), IW = plan_width(P);
+  if (P->train_batch == B && P->train_cond == cond_channels && P->train_h == IH && P->train_w == IW) return SR3_OK;
   const sr3_unet_desc& d = P->d;
   if (B <= 0) { set_error("batch must be > 0"); return SR3_E_BADARG; }
   if (cond_channels < 0 || cond_channels >= d.in_channel) { set_error("cond_channels out of range"); return SR3_E_BADARG; }
   P->tops.clear();
   P->recs.clear();
+  P->train_batch = -1;
   Builder bld(P, B, true);
   walk_forward(P, bld, cond_channels);
+  if (!bld.refused.empty()) {
+    // as build_forward: a geometry no kernel can run is refused when the plan is built, never after a launch has been enqueued
+    set_error("training geometry %d x %d unsupported: %s", IH, IW, bld.refused.c_str());
+    P->tops.clear();
+    P->recs.clear();
+    return SR3_E_UNSUPPORTED;
+  }
   P->ttens = bld.T;
-  const int S = d.image_size, inner = d.inner_channel, G = d.norm_groups;
+  const size_t S2 = (size_t)IH * IW;
+  const int inner = d.inner_channel, G = d.norm_groups;
   auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
   size_t off = al(bld.act.high);
   P->t_act_bytes = off;
@@ -983,10 +1017,10 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
       max_bscratch = std::max(max_bscratch, conv_splitk_bytes(g, 0, 0));
       {   // the data gradient of a 3x3 conv runs on the Winograd kernel where it fits: its slabs and transformed filters
         WinoGeom wg;
-        if (P->winograd && r.ksize == 3 && wino_geometry(g, &wg)) {
-          g.wino_split = (P->wino_split && wg.NB == 1) ? (P->wino2 ? 2 : 1) : 0;      // (what dgrad_conv launches with: its split-K choice depends on it)
+        bool split_filters;
+        if (dgrad_wino(P, g, &wg, &split_filters)) {      // (sets g.wino_split: the split-K choice depends on it)
           max_bscratch = std::max(max_bscratch, conv_splitk_bytes(g, 11, 0));
-          max_wu = std::max(max_wu, wino_weight_floats(g.Cout, g.C0, P->wino_split && wg.NB == 1) * sizeof(float));
+          max_wu = std::max(max_wu, wino_weight_floats(g.Cout, g.C0, split_filters) * sizeof(float));
         }
       }
       if (r.has_q) {
@@ -995,19 +1029,19 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
         max_bscratch = std::max(max_bscratch, conv_splitk_bytes(conv_shape(B, o.H, o.W, 0, 1, 1, o.C, 0, q.C0 + q.C1), 0, 0));
       }
     } else if (r.kind == R_CONV_IN) {
-      const ConvParams c = conv_shape(B, S, S, 0, 1, 3, 8, 0, P->ttens[r.out].C);
+      const ConvParams c = conv_shape(B, IH, IW, 0, 1, 3, 8, 0, P->ttens[r.out].C);
       max_slab = std::max(max_slab, wgrad_slab_bytes(c, nullptr));
       max_dwtmp = std::max(max_dwtmp, (size_t)c.Cout * 9 * 8 * sizeof(float));
-      max_part = std::max(max_part, (size_t)B * chan_stats_slices(B, S * S, c.Cout) * c.Cout * 2 * sizeof(double));
+      max_part = std::max(max_part, (size_t)B * chan_stats_slices(B, IH * IW, c.Cout) * c.Cout * 2 * sizeof(double));
     } else if (r.kind == R_CONV_OUT) {
       const Tensor& x0 = P->ttens[r.x0];
-      max_slab = std::max(max_slab, wgrad_slab_bytes(conv_shape(B, S, S, 0, 1, 3, x0.C, 0, 4), nullptr));
+      max_slab = std::max(max_slab, wgrad_slab_bytes(conv_shape(B, IH, IW, 0, 1, 3, x0.C, 0, 4), nullptr));
       max_dwtmp = std::max(max_dwtmp, (size_t)4 * 9 * x0.C * sizeof(float));
-      max_dA = std::max(max_dA, (size_t)B * S * S * x0.C * sizeof(float));
+      max_dA = std::max(max_dA, (size_t)B * S2 * x0.C * sizeof(float));
       max_wt = std::max(max_wt, (size_t)x0.C * 9 * 4 * sizeof(float));
-      max_part = std::max(max_part, act_bwd_part_bytes(B, S * S, x0.C));
-      max_part = std::max(max_part, (size_t)B * chan_stats_slices(B, S * S, 4) * 4 * 2 * sizeof(double));
-      max_bscratch = std::max(max_bscratch, conv_splitk_bytes(conv_shape(B, S, S, 0, 1, 3, 4, 0, x0.C), 0, 0));
+      max_part = std::max(max_part, act_bwd_part_bytes(B, IH * IW, x0.C));
+      max_part = std::max(max_part, (size_t)B * chan_stats_slices(B, IH * IW, 4) * 4 * 2 * sizeof(double));
+      max_bscratch = std::max(max_bscratch, conv_splitk_bytes(conv_shape(B, IH, IW, 0, 1, 3, 4, 0, x0.C), 0, 0));
     }
   }
   for (const Rec& r : P->recs)                // ... and the dK / dV slabs of the attention backward (attention_bwd.hip)
@@ -1030,10 +1064,10 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
   P->t_part_off = off; off += al(max_part);
   P->t_gs_off = off; off += al((size_t)B * G * 2 * sizeof(double));
   P->t_dfilm_off = off; off += al((size_t)B * P->F * sizeof(float));
-  P->t_xnoisy_off = off; off += al((size_t)B * (d.in_channel - cond_channels) * S * S * sizeof(float));
-  P->t_eps_off = off; off += al((size_t)B * P->out_ch * S * S * sizeof(float));
-  P->t_geps_off = off; off += al((size_t)B * S * S * 4 * sizeof(float));
-  P->t_inpad_off = off; off += al((size_t)B * S * S * 8 * sizeof(float));
+  P->t_xnoisy_off = off; off += al((size_t)B * (d.in_channel - cond_channels) * S2 * sizeof(float));
+  P->t_eps_off = off; off += al((size_t)B * P->out_ch * S2 * sizeof(float));
+  P->t_geps_off = off; off += al((size_t)B * S2 * 4 * sizeof(float));
+  P->t_inpad_off = off; off += al((size_t)B * S2 * 8 * sizeof(float));
   P->t_dwtmp_off = off; off += al(4096 * sizeof(double)) + al(max_dwtmp);      // [loss partials | dw temp]
   P->t_embscr_off = off; off += al((size_t)B * (13 + 16) * inner * sizeof(float));     // (+ the 16 row chunks of k_film_bwd_input)
   // gradient-ready marks: t_unproc_max[k] = largest arena offset (exclusive end) among the parameters whose
@@ -1072,6 +1106,7 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
   P->t_ws_bytes = off;
   P->train_batch = B;
   P->train_cond = cond_channels;
+  P->train_h = IH; P->train_w = IW;
   return SR3_OK;
 }
 
@@ -1193,6 +1228,7 @@ int sr3_plan_set_option(sr3_plan* plan, const char* key, int value) {
   else if (!strcmp(key, "gemm_tile")) slot = &plan->gemm_tile;
   else if (!strcmp(key, "wino2")) slot = &plan->wino2;
   else if (!strcmp(key, "wino_ragged")) slot = &plan->wino_ragged;
+  else if (!strcmp(key, "train_geom")) slot = &plan->train_geom;
   else if (!strcmp(key, "loss_l2")) { const int prev = plan->loss_l2; plan->loss_l2 = value; return prev; }   // no rebuild
   if (!slot) { set_error("unknown option %s", key); return SR3_E_BADARG; }
 #ifndef SR3_EXPERIMENTS

@@ -145,6 +145,9 @@ struct sr3_plan {
   int wino_ragged = 1;       // inference plans at a geometry other than image_size x image_size: 3x3 stride-1 convs on maps that are not whole
                              // multiples of the 8 x 16 tile on the two-workgroup kernel's RAGGED instantiation (tile_cfg 23) where the measured rule
                              // (wino_ragged_wins, plan.hip) says so; 0: they fall back to the general kernels (A/B knob)
+  int train_geom = 0;        // training follows the plan's geometry (sr3_plan_set_geometry) too: sr3_train_workspace_bytes / sr3_train_step build the
+                             // training plan at plan_height x plan_width.  0: training is refused at any geometry but image_size x image_size.
+                             // Off by default ONLY because tests pin that refusal text; at the native geometry both values build the same plan
   int geo_h = 0, geo_w = 0;  // sr3_plan_set_geometry: image height / width of the next forward (0: image_size)
   int fork_side = 0;         // res_conv (and the embedding MLP) on a side stream beside block1's conv: see Op::side_id; A/B knob
   hipStream_t side_stream = nullptr;          // fork_side: created at the first forked forward, on the device current then
@@ -178,6 +181,7 @@ struct sr3_plan {
   double flops = 0;
   // ---- training step (train_plan.hip) ----
   int train_batch = -1, train_cond = -1;
+  int train_h = 0, train_w = 0;      // geometry the training plan was built for (with batch and cond_channels: its key; options reset train_batch)
   std::vector<Op> tops;              // forward ops in train mode (no buffer reuse, persistent GN tables)
   std::vector<sr3::Tensor> ttens;    // tensor table of the train forward
   std::vector<sr3::Rec> recs;
@@ -205,5 +209,9 @@ int run_forward(sr3_plan* P, const Regions& R, const float* x, const float* cond
                 const float* params, char* ws, float* eps_out, int B, hipStream_t st, hipEvent_t* ev, hipEvent_t* mid,
                 const DropCfg* drop = nullptr, const StepFuse* fuse = nullptr);
 int build_train(sr3_plan* P, int B, int cond_channels);
+// The Winograd form of one data-gradient conv `g` (dOut -> dA on the flipped-transposed filters), or false: the general kernels run it.
+// Sets g.wino_split to what the launch uses; *split_filters: the 3 x bf16 split form of the transformed filters.  ONE rule for
+// dgrad_conv (train_plan.hip), which launches by it, and build_train, which sizes the slabs and the filter region by it.
+bool dgrad_wino(const sr3_plan* P, ConvParams& g, WinoGeom* wg, bool* split_filters);
 void layout_derived(sr3_plan* P);
 }  // namespace sr3

@@ -43,19 +43,18 @@ int dgrad_conv(const TrainCtx& X, const float* g, int Cg, int H, int W, int ksiz
   memset(&c, 0, sizeof(c));
   c.src0 = g; c.C0 = Cg; c.B = X.B; c.Hs = H; c.Ws = W; c.stride = 1; c.ksize = ksize; c.Ho = H; c.Wo = W;
   c.Cout = Cin; c.w = wt; c.out = dA; c.ksplit = 1;
-  // 3x3: Winograd F(2x2,3x3) on the flipped-transposed filters where the geometry fits (the data gradient has neither a
-  // prologue nor dropout, so every 3x3 stride-1 / zero-inserted stride-2 layer with H, W multiples of 16 qualifies)
+  // 3x3: Winograd F(2x2,3x3) on the flipped-transposed filters where dgrad_wino (plan.hip) says so -- the rule build_train sized
+  // the slabs and the filter region by
   WinoGeom wg;
-  const bool split = X.P->wino_split != 0;            // (the one-image tile: the 3 x bf16 split instantiation, as the forward)
-  if (X.P->winograd && ksize == 3 && wino_geometry(c, &wg) &&
-      wino_weight_floats(Cin, Cg, split && wg.NB == 1) * sizeof(float) <= X.P->t_wu_bytes) {
+  bool split_filters;
+  if (dgrad_wino(X.P, c, &wg, &split_filters) && wino_weight_floats(Cin, Cg, split_filters) * sizeof(float) <= X.P->t_wu_bytes) {
     float* wu = X.at<float>(X.P->t_wu_off);
-    c.wino_split = (split && wg.NB == 1) ? (X.P->wino2 ? 2 : 1) : 0;      // (2: the 8 x 16 tile of conv3x3_wino2.hip)
-    rc = wino_transform_weights(wt, Cin, Cg, wu, X.st, c.wino_split != 0);
+    rc = wino_transform_weights(wt, Cin, Cg, wu, X.st, split_filters);
     if (rc) return rc;
     c.wino_u = wu;
     return conv_forward(c, 11, 0, X.at<float>(X.P->t_scratch_off), X.P->t_scratch_bytes, X.st);
   }
+  c.wino_split = 0;
   // 1x1 / 8x8 data gradients on the im2col kernel: its 3 x bf16 split instantiation, with the forward Builder's exclusion (9-tap
   // layers producing <= 64 channels stay on the fp32 MFMA: plan.hip, Builder::conv) -- build_train sizes the scratch with the same rule
   c.igemm_split = (X.P->gemm_split && !(ksize == 3 && c.Cout <= 64)) ? 1 : 0;
@@ -92,14 +91,15 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
               float* grads, char* ws, float* loss_out, float grad_scale, int B, hipStream_t st, float dropout_p,
               unsigned seed, int n_marks, const size_t* marks, void* const* mark_events) {
   const sr3_unet_desc& d = P->d;
-  const int S = d.image_size, G = d.norm_groups;
+  // image geometry of this step: build_train built the plan for it (the native one unless plan option train_geom)
+  const int IH = P->train_h, IW = P->train_w, S2 = IH * IW, G = d.norm_groups;
   const int xc = d.in_channel - cond_channels;
   TrainCtx X{P, ws, params, grads, B, st};
   int rc;
   // ---- q_sample + forward ----
   float* x_noisy = X.at<float>(P->t_xnoisy_off);
   float* eps = X.at<float>(P->t_eps_off);
-  rc = q_sample(hr, z, q_ca, q_cb, B, xc * S * S, x_noisy, st);
+  rc = q_sample(hr, z, q_ca, q_cb, B, xc * S2, x_noisy, st);
   if (rc) return rc;
   Regions R;
   R.ops = &P->tops; R.stats_off = P->t_stats_off; R.ss_off = P->t_gn_off; R.mr_off = P->t_misc_off;
@@ -113,7 +113,7 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
   // ---- loss and its gradient (NHWC, channel dim padded to 4) ----
   float* geps = X.at<float>(P->t_geps_off);
   double* lparts = X.at<double>(P->t_dwtmp_off);
-  rc = l1_loss_grad(z, eps, B, P->out_ch, S * S, 4, grad_scale, P->loss_l2 != 0, geps, lparts, loss_out, st);
+  rc = l1_loss_grad(z, eps, B, P->out_ch, S2, 4, grad_scale, P->loss_l2 != 0, geps, lparts, loss_out, st);
   if (rc) return rc;
   // ---- the activation-gradient mirror is NOT zeroed (round 6: 1.5 ms per step): the first contribution to a tensor's gradient in this
   // walk is a plain store (`first` below), later ones accumulate in stream order; the FiLM gradient table is zeroed ----
@@ -139,18 +139,18 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
       const Tensor& x0 = P->ttens[r.x0];
       const int C = x0.C;
       // bias (3 of the 4 padded columns are real; arena slots are 4-float aligned)
-      rc = colsums(geps, B, S * S, 4, part, grads + r.bias, nullptr, 0, st);
+      rc = colsums(geps, B, S2, 4, part, grads + r.bias, nullptr, 0, st);
       if (rc) return rc;
-      rc = dgrad_conv(X, geps, 4, S, S, 3, params + r.w, P->out_ch, C, dA);
+      rc = dgrad_conv(X, geps, 4, IH, IW, 3, params + r.w, P->out_ch, C, dA);
       if (rc) return rc;
-      rc = act_bwd(dA, X.act(r.x0), nullptr, C, 0, B, S * S, X.at<float>(P->t_gn_off + r.ss_off),
+      rc = act_bwd(dA, X.act(r.x0), nullptr, C, 0, B, S2, X.at<float>(P->t_gn_off + r.ss_off),
                    X.at<float>(P->t_misc_off + r.mr_off), G, 2, params + r.gamma, part, gs, grads + r.gamma,
                    grads + r.beta, X.grad(r.x0), nullptr, st, 0u, 0u, 1.f, X.at<float>(P->t_a_off), !first(r.x0), true);
       if (rc) return rc;
       ConvParams c;
       memset(&c, 0, sizeof(c));
       float* abuf = X.at<float>(P->t_a_off);        // (the activated input, written by act_bwd's first pass)
-      c.src0 = abuf; c.C0 = C; c.B = B; c.Hs = S; c.Ws = S; c.stride = 1; c.ksize = 3; c.Ho = S; c.Wo = S;
+      c.src0 = abuf; c.C0 = C; c.B = B; c.Hs = IH; c.Ws = IW; c.stride = 1; c.ksize = 3; c.Ho = IH; c.Wo = IW;
       c.Cout = 4;
       rc = wgrad_call(X, c, geps, dwtmp);
       if (rc) return rc;
@@ -169,13 +169,13 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
       const int Ca = cond_channels > 0 ? cond_channels : xc;
       const float* b2 = cond_channels > 0 ? x_noisy : nullptr;
       const int Cb = cond_channels > 0 ? xc : 0;
-      rc = nchw_to_nhwc_pad(a, Ca, b2, Cb, B, S * S, 8, inpad, st);
+      rc = nchw_to_nhwc_pad(a, Ca, b2, Cb, B, S2, 8, inpad, st);
       if (rc) return rc;
-      rc = colsums(X.grad(r.out), B, S * S, o.C, part, grads + r.bias, nullptr, 0, st);
+      rc = colsums(X.grad(r.out), B, S2, o.C, part, grads + r.bias, nullptr, 0, st);
       if (rc) return rc;
       ConvParams c;
       memset(&c, 0, sizeof(c));
-      c.src0 = inpad; c.C0 = 8; c.B = B; c.Hs = S; c.Ws = S; c.stride = 1; c.ksize = 3; c.Ho = S; c.Wo = S; c.Cout = o.C;
+      c.src0 = inpad; c.C0 = 8; c.B = B; c.Hs = IH; c.Ws = IW; c.stride = 1; c.ksize = 3; c.Ho = IH; c.Wo = IW; c.Cout = o.C;
       rc = wgrad_call(X, c, X.grad(r.out), dwtmp);
       if (rc) return rc;
       // compact [Cout][9][8] -> [Cout][9][in_channel]

@@ -370,27 +370,27 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_split(const ConvParams p,
 
 // ---------------------------------------------------------------------------------------------------
 // 9-tap variant for the 3x3 stride-1 convs (the bulk of the weight-gradient FLOPs).  A workgroup owns a
-// 64 x 64 (n, c) tile of ALL nine taps: per 32-pixel chunk (a row segment, or 2-4 whole rows of a narrow
-// map) it stages dOut[32][64] and the (rows+2) x (cols+2) halo of the materialised activated input ONCE and
+// 64 x 64 (n, c) tile of ALL nine taps: per 32-pixel chunk (RPC rows x Wc columns, Wc the largest of 32, 16, 8
+// that divides W -- a row segment of a wide map, 2-4 rows of a narrow or a non-power-of-two one) it stages
+// dOut[32][64] and the (rows+2) x (cols+2) halo of the materialised activated input ONCE and
 // every tap reads its B fragments from the halo at a shifted pixel -- 144 MFMAs per wave per barrier and
 // 3.5x fewer staged bytes per MFMA than one tap at a time.  a: [B,H,W,Cin] single source (k_apply_act).
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256, 2) void k_conv_wgrad9(const float* __restrict__ a, int Cin,
                                                          const float* __restrict__ dy, int Cout, int B, int H, int W,
-                                                         int logW, float* __restrict__ slabs, int chunks_per_split) {
+                                                         int logWc, float* __restrict__ slabs, int chunks_per_split) {
   constexpr int T = 64, LD = 68;
-  constexpr int HPX_MAX = 102;                       // 3 x 34 halo pixels (W >= 32); 4 x 18, 6 x 10 for W = 16, 8
+  constexpr int HPX_MAX = 102;                       // 3 x 34 halo pixels (Wc = 32); 4 x 18, 6 x 10 for Wc = 16, 8
   constexpr int HI = (HPX_MAX * 16 + 255) / 256;     // halo float4 items per thread (7)
   constexpr int STAGE = (32 + HPX_MAX) * LD;
   extern __shared__ f32x4 smem_v[];
   float* smem = reinterpret_cast<float*>(smem_v);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int Wc = W < 32 ? W : 32;                    // chunk = RPC rows x Wc columns = 32 pixels
-  const int logWc = logW < 5 ? logW : 5;
+  const int Wc = 1 << logWc;                         // chunk = RPC rows x Wc columns = 32 pixels (Wc divides W, RPC divides H: wgrad9_ok)
   const int RPC = 32 >> logWc;
   const int HWp = Wc + 2, HR = RPC + 2, HPX = HR * HWp;
-  const int cpr = W >> logWc;                        // chunks per image row (W >= 32) else 1
+  const int cpr = W / Wc;                            // chunks side by side in a band of RPC image rows (W need not be a power of two)
   const int chunks_per_img = (H * W) >> 5;
   const int nchunks = B * chunks_per_img;
   const int tiles_c = (Cin + T - 1) / T;
@@ -414,8 +414,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad9(const float* __restrict_
   auto load = [&](int chunk) {
     const int b = chunk / chunks_per_img;
     const int ci = chunk - b * chunks_per_img;
-    const int oh0 = (W >= 32) ? ci / cpr : ci * RPC;
-    const int ow0 = (W >= 32) ? (ci - (ci / cpr) * cpr) * 32 : 0;
+    const int band = ci / cpr;
+    const int oh0 = band * RPC;
+    const int ow0 = (ci - band * cpr) * Wc;
     const int c = tile_c * T + lq * 4;
     const int n = tile_n * T + lq * 4;
     const bool cv = c < Cin, nv = n < Cout;
@@ -519,14 +520,16 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ 
 namespace {
 inline int cdivw(int a, int b) { return (a + b - 1) / b; }
 inline int ilog2w(int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; }
-// the 9-tap kernel covers 3x3 stride-1 non-upsampled single-source convs on power-of-two maps with W >= 8
+// chunk width of the 9-tap kernel: the largest of 32, 16, 8 that divides the map width (0: none does)
+int wgrad9_chunk_w(int W) { return (W % 32) == 0 ? 32 : (W % 16) == 0 ? 16 : (W % 8) == 0 ? 8 : 0; }
+// the 9-tap kernel covers 3x3 stride-1 non-upsampled single-source convs on maps whose width is a multiple of 8 and whose
+// height is a multiple of the chunk's rows (32 / chunk width); a power of two is not required
 bool wgrad9_ok(const ConvParams& c) {
   if (c.ksize != 3 || c.stride != 1 || c.ups != 0 || c.C1 != 0 || c.act != 0) return false;
-  const int lw = ilog2w(c.Wo);
-  if (lw < 3 || c.Ho != c.Hs || c.Wo != c.Ws) return false;
-  const int Wc = c.Wo < 32 ? c.Wo : 32;
-  const int rpc = 32 / Wc;
-  return c.Ho % rpc == 0 && (c.Ho * c.Wo) % 32 == 0;
+  if (c.Ho != c.Hs || c.Wo != c.Ws || c.Ho < 1) return false;
+  const int Wc = wgrad9_chunk_w(c.Wo);
+  if (Wc == 0) return false;
+  return c.Ho % (32 / Wc) == 0;
 }
 // plan option wgrad_split: the one-tap-per-workgroup split kernel on its 128 x 128 tile, i.e. for every layer with more than 64
 // input and output channels (3x3 layers included); the 64-channel layers keep their kernels (the 64 x 64 split tile stages as
@@ -634,8 +637,8 @@ int conv_wgrad(const WgradParams& p, hipStream_t st) {
     static std::atomic<uint64_t> attr9_done{0};
     if (int rc9 = ensure_max_lds(reinterpret_cast<const void*>(k_conv_wgrad9), smem9, attr9_done)) return rc9;
     dim3 grid(cdivw(c.Cout, 64) * cdivw(Cin, 64), 1, ms);
-    hipLaunchKernelGGL(k_conv_wgrad9, grid, dim3(256), smem9, st, c.src0, Cin, p.dy, c.Cout, c.B, c.Ho, c.Wo, ilog2w(c.Wo),
-                       ms > 1 ? p.slabs : p.dw, cps);
+    hipLaunchKernelGGL(k_conv_wgrad9, grid, dim3(256), smem9, st, c.src0, Cin, p.dy, c.Cout, c.B, c.Ho, c.Wo,
+                       ilog2w(wgrad9_chunk_w(c.Wo)), ms > 1 ? p.slabs : p.dw, cps);
     SR3_LAUNCH_CHECK("k_conv_wgrad9");
     rc = SR3_OK;
   } else {

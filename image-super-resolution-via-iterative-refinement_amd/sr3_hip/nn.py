@@ -239,13 +239,27 @@ class EngineUNet(nn.Module):
         self.ensure_derived()          # the train plan's block1 / Upsample convs run on the Winograd kernel
         B = hr.shape[0]
         plan = self.plan
-        if tuple(hr.shape[2:]) != (plan.image_size, plan.image_size):
-            raise L.Sr3Error('training runs at image_size x image_size = %d x %d only (got HR %s)' % (plan.image_size, plan.image_size, tuple(hr.shape)))
-        plan.set_geometry(0, 0)        # (a validation pass may have left the plan at another image size)
+        # the image size comes from the batch, as in the reference (p_losses trains on whatever the loader yields; image_size is
+        # read by `sample` only): the training plan follows it (plan option train_geom, set when the first other size arrives)
+        if hr.dim() != 4:
+            raise L.Sr3Error('training: a (B, C, H, W) HR batch is expected (got %s)' % (tuple(hr.shape),))
+        H, W = int(hr.shape[2]), int(hr.shape[3])
+        if H <= 0 or W <= 0 or H % plan.divisor or W % plan.divisor:
+            raise L.Sr3Error('image size %d x %d: height and width must be positive multiples of %d (the UNet halves the image %d times)'
+                             % (H, W, plan.divisor, plan.desc.n_mults - 1))
+        if cond is not None and (cond.shape[0] != B or tuple(cond.shape[2:]) != (H, W)):
+            raise L.Sr3Error('training: the conditioning batch %s must have the batch and image size of HR %s'
+                             % (tuple(cond.shape), tuple(hr.shape)))
+        if tuple(z.shape) != tuple(hr.shape):
+            raise L.Sr3Error('training: the noise %s must have the shape of HR %s' % (tuple(z.shape), tuple(hr.shape)))
+        if (H, W) != (plan.image_size, plan.image_size) and not plan.options.get('train_geom'):
+            plan.set_option('train_geom', 1)
+            self.ensure_derived()      # (an option change invalidates the derived filters)
+        plan.set_geometry(H, W)        # (a validation pass or the previous batch may have left the plan at another image size)
         cc = 0 if cond is None else cond.shape[1]
         need = int(plan.lib.sr3_train_workspace_bytes(plan.handle, B, cc))
         if need == 0:
-            raise L.Sr3Error('sr3_train_workspace_bytes failed: %s' % (plan.lib.sr3_last_error() or b'').decode())
+            raise L.Sr3Error('training at image size %d x %d: %s' % (H, W, L.hint((plan.lib.sr3_last_error() or b'').decode())))
         ws = getattr(self, '_train_ws', None)
         if ws is None or ws.numel() < need + 256 or ws.device != dev:
             ws = self._train_ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)

@@ -100,7 +100,7 @@ int sr3_plan_op_side(sr3_plan* plan, int batch, int index, int* side_id, int* wa
 double sr3_plan_forward_flops(sr3_plan* plan, int batch);
 /* tuning knobs: key in {"fuse_stats", "fuse_res", "tile_cfg", "ksplit", "keep_all", "split_bf16", "winograd",
  * "wino_split", "wino_split8", "wino2", "wino_ragged", "gemm_split", "gemm2", "gemm_s2", "gemm_n64", "fork_side", "gemm_wpre", "gemm_tile", "fold_fuse", "wgrad_split", "attn_split",
- * "attn_long", "loss_l2"};
+ * "attn_long", "train_geom", "loss_l2"};
  * returns previous value.
  * wino_split (default 1): the Winograd convolutions that run on the kernel's one-image tile (maps >= 16x16) use its 3 x bf16
  *   split instantiation: every fp32 operand as x = h + m + l (three bf16 terms, each residual exact in fp32), every product as
@@ -156,6 +156,14 @@ double sr3_plan_forward_flops(sr3_plan* plan, int batch);
  *   of refusing the geometry.  A level the strip kernels hold keeps them: launch list, workspace and output bits are those of
  *   attn_long = 0 there.  attn_split selects the arithmetic as for the strip kernels.  The default is 0 for ONE reason: a test pins the
  *   refusal of a fresh plan at 384 x 384; a later change that rewrites that test can flip it.
+ * train_geom (default 0; training): sr3_train_workspace_bytes and sr3_train_step follow sr3_plan_set_geometry like the forward does: the
+ *   training plan is built for the plan's height x width (hr / cond / z are [B, C, height, width]) and cached by (batch, cond_channels,
+ *   height, width).  Its forward picks every conv through the inference planner's rule (the ragged Winograd tile 23 included, for the convs
+ *   without dropout), the data gradients through the same rule, the 3x3 weight gradients of the <= 64-channel layers keep the 9-tap
+ *   kernel on every map whose width is a multiple of 8; an attention level beyond the score strip needs attn_long (forward on the
+ *   key-blocked kernel, backward on its key-blocked path with the dK / dV slabs -- no atomics) and is refused without it.  At
+ *   image_size x image_size the launch list, the workspace and every bit of the result are those of train_geom = 0.  0: training is
+ *   refused at any other geometry.  The default is 0 only because tests pin that refusal; nothing else speaks against 1.
  * loss_l2 (default 0): sr3_train_step uses nn.MSELoss(reduction='sum') instead of nn.L1Loss(reduction='sum')
  *   (GaussianDiffusion(loss_type='l2'), model/sr3_modules/diffusion.py:84-90).
  * split_bf16 (default 0, experimental; needs -DSR3_EXPERIMENTS, refused otherwise): run the halo-tile 3x3 convolutions of the inference plan on
@@ -178,8 +186,9 @@ int sr3_plan_tap_info(sr3_plan* plan, int index, char* name, int name_len, size_
  * fits-predicates as at the native size and lands on the general kernels where nothing faster fits; a geometry NO kernel can run
  * (an attention level with more tokens than the attention kernel holds in LDS, in a plan without option attn_long) is refused with
  * SR3_E_UNSUPPORTED and a message naming the level and its token count when the launch list is built -- by sr3_workspace_bytes (returns 0) / sr3_plan_num_ops
- * (returns -1) / the forward itself before it enqueues anything.  Training is native-size only: sr3_train_workspace_bytes returns 0
- * and sr3_train_step SR3_E_UNSUPPORTED while the geometry is not image_size x image_size. */
+ * (returns -1) / the forward itself before it enqueues anything.  Training follows the geometry under plan option train_geom; without it
+ * training is native-size only: sr3_train_workspace_bytes returns 0 and sr3_train_step SR3_E_UNSUPPORTED while the geometry is not
+ * image_size x image_size. */
 int sr3_plan_set_geometry(sr3_plan* plan, int height, int width);
 int sr3_plan_get_geometry(const sr3_plan* plan, int* height, int* width);
 
@@ -276,8 +285,9 @@ int sr3_q_sample(const float* x0, const float* z, const float* ca, const float* 
 
 /* ---- training step ------------------------------------------------------------------------- */
 
-/* Workspace of sr3_train_step (activations kept for the backward, their gradient mirror, scratch).  Training runs at
- * image_size x image_size only: 0 (and a message) while sr3_plan_set_geometry has the plan at another geometry. */
+/* Workspace of sr3_train_step (activations kept for the backward, their gradient mirror, scratch) at the plan's geometry.  Without plan
+ * option train_geom training runs at image_size x image_size only: 0 (and a message) while sr3_plan_set_geometry has the plan at
+ * another geometry; with it, 0 only for a geometry no kernel can run (an attention level beyond the score strip without attn_long). */
 size_t sr3_train_workspace_bytes(sr3_plan* plan, int batch, int cond_channels);
 
 /* One training step up to the gradients: `l_pix = netG(data); l_pix.backward()` of
