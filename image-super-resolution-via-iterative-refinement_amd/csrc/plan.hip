@@ -283,7 +283,7 @@ struct Arena {
 // least a third of its rounded-up tile grid (8x12: 75 %, 44x32: 92 %, 22x16: 69 %, 11x8: 34 %, 8x8 upsampled: 50 %), 1.2-1.27 of it
 // on the 4x4 maps (12.5 %: seven eighths of every tile is padding, and the im2col kernel under 16-way split-K is not slower
 // there).  Nothing was measured between 12.5 % and 34 %: the threshold sits in the gap, at a quarter.
-static bool wino_ragged_wins(const ConvParams& c) {
+bool wino_ragged_wins(const ConvParams& c) {
   const long padded = (long)((c.Ho + 7) / 8 * 8) * ((c.Wo + 15) / 16 * 16);
   return 4L * c.Ho * c.Wo >= padded;
 }
@@ -335,9 +335,7 @@ static ConvChoice choose_conv(const sr3_plan* P, ConvParams c, size_t w, bool ha
     if (c.wino_split) ch.wino_off += wino_weight_floats(c.Cout, c.C0 + c.C1);
   }
   if (full) {
-    // read by conv_pick / conv_forward only when the conv lands on the im2col kernel; the 9-tap layers with Cout <= 64 (Downsample
-    // of the first level) stay on the fp32 MFMA, which is faster there (67 vs 81 us in the forward)
-    c.igemm_split = (P->gemm_split && !(c.ksize == 3 && c.Cout <= 64)) ? 1 : 0;
+    c.igemm_split = igemm_split_rule(P, c);      // (read by conv_pick / conv_forward only when the conv lands on the im2col kernel)
     // (... unless the plain GEMM kernel takes the layer on its 64-column tile: plan options gemm2 + gemm_s2 + gemm_n64, below)
     if (P->gemm_split && P->gemm2 && P->gemm_s2 && P->gemm_n64 && c.ksize == 3 && c.stride == 2 && P->wsplit_of.count(w) && gemm1x1_fits(c, 2)) c.igemm_split = 1;
   }
@@ -365,20 +363,6 @@ static ConvChoice choose_conv(const sr3_plan* P, ConvParams c, size_t w, bool ha
   return ch;
 }
 
-// One conv of the forward, for Builder::conv: sources and residuals are tensor handles (-1: absent), parameters arena offsets
-static constexpr size_t NO_PARAM = ~(size_t)0;
-struct ConvSpec {
-  int x0 = -1, x1 = -1;            // source: the virtual concat (x0|x1)
-  int Cout = 0, ksize = 3, stride = 1, ups = 0;
-  int act = 0;                     // ConvParams::act: what the prologue does with the GroupNorm fold in front of this conv
-  size_t w = 0, bias = NO_PARAM;
-  int film_row = -1;               // first row of the FiLM table added to the output
-  int r0 = -1, r1 = -1;            // residual: the concat view (r0|r1)
-  bool want_stats = false;         // a GroupNorm reads the output: fuse its statistics where the kernel can
-  int q0 = -1, q1 = -1; size_t qw = 0, qb = 0;       // fused 1x1 segment (res_conv) over (q0|q1); caller checked fuses_res_conv()
-  int drop_key = -1;               // train-mode dropout on the activated input: the layer's key (drop_layer_seed)
-};
-
 struct Builder {
   sr3_plan* P;
   int B;
@@ -393,7 +377,6 @@ struct Builder {
   size_t gn_cursor = 0, mr_cursor = 0;     // train: persistent per-GroupNorm tables
   size_t cur_ss = 0, cur_mr = 0;           // tables written by the most recent fold
   size_t cur_gamma = 0, cur_beta = 0;
-  size_t max_dA = 0, max_wt = 0, max_slab = 0, max_part = 0, max_z = 0, max_dq = 0;
   Builder(sr3_plan* p, int b, bool tr = false) : P(p), B(b), ops(tr ? p->tops : p->ops), train(tr) {}
 
   int make(int C, int H, int W) {
@@ -499,22 +482,9 @@ struct Builder {
     o.wino_off = ch.wino_off; o.has_wsplit = ch.has_wsplit; o.wsplit_off = ch.wsplit_off;
     if (train) {
       Rec r;
-      r.kind = R_CONV; r.x0 = x0; r.x1 = x1; r.out = out; r.r0 = s.r0; r.r1 = s.r1; r.q0 = s.q0; r.q1 = s.q1;
-      r.ksize = ksize; r.stride = s.stride; r.ups = s.ups; r.act = s.act; r.film_row = s.film_row;
-      r.w = s.w; r.bias = bias; r.has_bias = has_bias; r.qw = s.qw; r.qb = s.qb; r.has_q = has_q;
+      r.kind = R_CONV; r.s = s; r.out = out;
       r.gamma = cur_gamma; r.beta = cur_beta; r.ss_off = cur_ss; r.mr_off = cur_mr;
-      r.has_drop = o.has_drop; r.drop_key = o.drop_key;
       P->recs.push_back(r);
-      // scratch the backward of this conv needs
-      const size_t cin = (size_t)(C0 + C1);
-      max_dA = std::max(max_dA, (size_t)B * (T[x0].H << s.ups) * (T[x0].W << s.ups) * cin * sizeof(float));
-      max_wt = std::max(max_wt, (size_t)Cout * ksize * ksize * cin * sizeof(float));
-      if (has_q) {
-        const size_t cq = (size_t)T[s.q0].C + (s.q1 >= 0 ? T[s.q1].C : 0);
-        max_dq = std::max(max_dq, (size_t)B * Ho * Wo * cq * sizeof(float));
-        max_wt = std::max(max_wt, (size_t)Cout * cq * sizeof(float));
-      }
-      if (s.stride == 2) max_z = std::max(max_z, (size_t)B * 4 * Ho * Wo * Cout * sizeof(float));
     }
     if (has_q) {   // fused 1x1 segment (res_conv); caller checked fuses_res_conv()
       c.x2_C0 = T[s.q0].C; c.x2_C1 = s.q1 >= 0 ? T[s.q1].C : 0;
@@ -525,7 +495,7 @@ struct Builder {
     if (o.ksplit > 1) max_scratch = std::max(max_scratch, (size_t)o.ksplit * B * Ho * Wo * Cout * sizeof(float));
     // split-K convs leave the statistics to the (cheap, small-tensor) stand-alone pass
     if (s.want_stats && P->fuse_stats && o.ksplit == 1 && o.tile_cfg == 11) {
-      WinoGeom wg;
+      WinoGeom wg = {};      // (stays empty -- no slices -- where plan option tile_cfg forces tile 11 on a conv it does not fit)
       wino_geometry(c, &wg);
       stat_slot(out, wino_stats_slices(wg));
       o.has_ostat = true; o.f = T[out].stat_off;
@@ -648,7 +618,7 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
         o.has_ostat = true; o.f = bld.T[cur].stat_off;
       }
       ops.push_back(o);
-      if (bld.train) { Rec r; r.kind = R_CONV_IN; r.out = cur; r.w = L.w; r.bias = L.b; P->recs.push_back(r); }
+      if (bld.train) { Rec r; r.kind = R_CONV_IN; r.out = cur; r.s.w = L.w; r.s.bias = L.b; P->recs.push_back(r); }
       bld.flops += 2.0 * B * IH * IW * (double)L.cout * L.cin * 9;
     } else if (L.kind == 1) {
       cur = bld.res_block(cur, -1, L.res);   // the input stays alive: it is a skip feature
@@ -689,8 +659,8 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
     o.ss_rel = bld.cur_ss;
     ops.push_back(o);
     if (bld.train) {
-      Rec r; r.kind = R_CONV_OUT; r.x0 = cur; r.w = P->fin_w; r.bias = P->fin_b; r.gamma = P->fin_gn_w; r.beta = P->fin_gn_b;
-      r.ss_off = bld.cur_ss; r.mr_off = bld.cur_mr; r.act = 2;
+      Rec r; r.kind = R_CONV_OUT; r.s.x0 = cur; r.s.w = P->fin_w; r.s.bias = P->fin_b; r.s.act = 2; r.gamma = P->fin_gn_w; r.beta = P->fin_gn_b;
+      r.ss_off = bld.cur_ss; r.mr_off = bld.cur_mr;
       P->recs.push_back(r);
     }
     bld.flops += 2.0 * B * IH * IW * (double)P->out_ch * bld.T[cur].C * 9;
@@ -938,176 +908,17 @@ int run_forward(sr3_plan* P, const Regions& R, const float* x, const float* cond
   return SR3_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// training plan: the same forward walk with every activation kept and persistent GroupNorm tables,
-// a gradient mirror of the activation arena, and the scratch the backward walk needs
-// ---------------------------------------------------------------------------------------------
-bool dgrad_wino(const sr3_plan* P, ConvParams& g, WinoGeom* wg, bool* split_filters) {
-  g.wino_split = 0;
-  *split_filters = false;
-  if (!P->winograd || g.ksize != 3) return false;
-  // the data gradient has neither a prologue nor dropout, so every 3x3 stride-1 / zero-inserted stride-2 layer with H, W multiples
-  // of 16 qualifies (and the four-image 8 x 8 tile); the one-image tile on its 3 x bf16 split instantiation, as the forward
-  if (wino_geometry(g, wg)) {
-    *split_filters = P->wino_split && wg->NB == 1;
-    g.wino_split = *split_filters ? (P->wino2 ? 2 : 1) : 0;      // (2: the 8 x 16 tile of conv3x3_wino2.hip)
-    return true;
-  }
-  // off the native geometry (plan option train_geom): the two-workgroup kernel on the maps that rule refuses, plain where the map is a
-  // whole multiple of its 8 x 16 tile, ragged where wino_ragged_wins -- wino_mode's rule for the forward
-  if (!P->train_geom || plan_native_geometry(P) || !P->wino_split || !P->wino2) return false;
-  g.wino_split = wino2_fits(g) ? 2 : 3;
-  if ((g.wino_split == 3 && !(P->wino_ragged && wino_ragged_wins(g))) || !wino_geometry(g, wg)) { g.wino_split = 0; return false; }
-  *split_filters = true;
-  return true;
-}
-
-int build_train(sr3_plan* P, int B, int cond_channels) {
-  if (!P->train_geom && !plan_native_geometry(P)) {
-    set_error("training runs at image_size x image_size only: the plan's geometry is %d x %d (sr3_plan_set_geometry(plan, 0, 0) restores %d x %d)",
-              plan_height(P), plan_width(P), P->d.image_size, P->d.image_size);
-    return SR3_E_UNSUPPORTED;
-  }
-  // (the geometry is the native one here unless train_geom; every option that changes the plan resets train_batch: sr3_plan_set_option)
-  const int IH = plan_height(P), IW = plan_width(P);
-  if (P->train_batch == B && P->train_cond == cond_channels && P->train_h == IH && P->train_w == IW) return SR3_OK;
-  const sr3_unet_desc& d = P->d;
-  if (B <= 0) { set_error("batch must be > 0"); return SR3_E_BADARG; }
-  if (cond_channels < 0 || cond_channels >= d.in_channel) { set_error("cond_channels out of range"); return SR3_E_BADARG; }
+// the forward walk of the training plan (build_train, train_plan.hip)
+TrainWalk walk_train(sr3_plan* P, int B, int cond_channels) {
   P->tops.clear();
   P->recs.clear();
-  P->train_batch = -1;
   Builder bld(P, B, true);
   walk_forward(P, bld, cond_channels);
-  if (!bld.refused.empty()) {
-    // as build_forward: a geometry no kernel can run is refused when the plan is built, never after a launch has been enqueued
-    set_error("training geometry %d x %d unsupported: %s", IH, IW, bld.refused.c_str());
-    P->tops.clear();
-    P->recs.clear();
-    return SR3_E_UNSUPPORTED;
-  }
   P->ttens = bld.T;
-  const size_t S2 = (size_t)IH * IW;
-  const int inner = d.inner_channel, G = d.norm_groups;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t off = al(bld.act.high);
-  P->t_act_bytes = off;
-  off *= 2;                                   // gradients mirror the activations at +t_act_bytes
-  P->t_stats_off = off; off += al(bld.stats_cursor);
-  P->t_gn_off = off; off += al(bld.gn_cursor);
-  P->t_misc_off = off; off += al(bld.mr_cursor);           // mean / rstd tables
-  P->t_temb_off = off; off += al((size_t)B * inner * sizeof(float));
-  P->t_film_off = off; off += al((size_t)B * P->F * sizeof(float));
-  P->t_scratch_off = off; P->t_scratch_bytes = bld.max_scratch; off += al(bld.max_scratch);
-  // backward scratch
-  size_t max_dA = bld.max_dA, max_wt = bld.max_wt, max_slab = 0, max_part = 0, max_dwtmp = 0, max_wu = 0;
-  size_t max_bscratch = 0;                    // split-K slabs of the data-gradient convs
-  for (const Rec& r : P->recs) {
-    if (r.kind == R_CONV) {
-      const Tensor& x0 = P->ttens[r.x0];
-      const Tensor& o = P->ttens[r.out];
-      ConvParams c = conv_shape(B, x0.H, x0.W, r.ups, r.stride, r.ksize, x0.C, r.x1 >= 0 ? P->ttens[r.x1].C : 0, o.C);
-      if (r.act) { c.C0 = c.C0 + c.C1; c.C1 = 0; }     // run time: the activated input is materialised (single source)
-      max_slab = std::max(max_slab, wgrad_slab_bytes(c, nullptr));
-      max_part = std::max(max_part, act_bwd_part_bytes(B, x0.H * x0.W, c.C0 + c.C1));
-      max_part = std::max(max_part, (size_t)B * chan_stats_slices(B, o.H * o.W, o.C) * o.C * 2 * sizeof(double));
-      // dgrad conv: src = dOut (or its zero-inserted version), Cout' = Cin
-      ConvParams g = conv_shape(B, x0.H << r.ups, x0.W << r.ups, 0, 1, r.ksize, o.C, 0, c.C0 + c.C1);
-      g.igemm_split = (P->gemm_split && !(g.ksize == 3 && g.Cout <= 64)) ? 1 : 0;      // (what dgrad_conv launches with: train_plan.hip)
-      max_bscratch = std::max(max_bscratch, conv_splitk_bytes(g, 0, 0));
-      {   // the data gradient of a 3x3 conv runs on the Winograd kernel where it fits: its slabs and transformed filters
-        WinoGeom wg;
-        bool split_filters;
-        if (dgrad_wino(P, g, &wg, &split_filters)) {      // (sets g.wino_split: the split-K choice depends on it)
-          max_bscratch = std::max(max_bscratch, conv_splitk_bytes(g, 11, 0));
-          max_wu = std::max(max_wu, wino_weight_floats(g.Cout, g.C0, split_filters) * sizeof(float));
-        }
-      }
-      if (r.has_q) {
-        const ConvParams q = conv_shape(B, o.H, o.W, 0, 1, 1, P->ttens[r.q0].C, r.q1 >= 0 ? P->ttens[r.q1].C : 0, o.C);
-        max_slab = std::max(max_slab, wgrad_slab_bytes(q, nullptr));
-        max_bscratch = std::max(max_bscratch, conv_splitk_bytes(conv_shape(B, o.H, o.W, 0, 1, 1, o.C, 0, q.C0 + q.C1), 0, 0));
-      }
-    } else if (r.kind == R_CONV_IN) {
-      const ConvParams c = conv_shape(B, IH, IW, 0, 1, 3, 8, 0, P->ttens[r.out].C);
-      max_slab = std::max(max_slab, wgrad_slab_bytes(c, nullptr));
-      max_dwtmp = std::max(max_dwtmp, (size_t)c.Cout * 9 * 8 * sizeof(float));
-      max_part = std::max(max_part, (size_t)B * chan_stats_slices(B, IH * IW, c.Cout) * c.Cout * 2 * sizeof(double));
-    } else if (r.kind == R_CONV_OUT) {
-      const Tensor& x0 = P->ttens[r.x0];
-      max_slab = std::max(max_slab, wgrad_slab_bytes(conv_shape(B, IH, IW, 0, 1, 3, x0.C, 0, 4), nullptr));
-      max_dwtmp = std::max(max_dwtmp, (size_t)4 * 9 * x0.C * sizeof(float));
-      max_dA = std::max(max_dA, (size_t)B * S2 * x0.C * sizeof(float));
-      max_wt = std::max(max_wt, (size_t)x0.C * 9 * 4 * sizeof(float));
-      max_part = std::max(max_part, act_bwd_part_bytes(B, IH * IW, x0.C));
-      max_part = std::max(max_part, (size_t)B * chan_stats_slices(B, IH * IW, 4) * 4 * 2 * sizeof(double));
-      max_bscratch = std::max(max_bscratch, conv_splitk_bytes(conv_shape(B, IH, IW, 0, 1, 3, 4, 0, x0.C), 0, 0));
-    }
-  }
-  for (const Rec& r : P->recs)                // ... and the dK / dV slabs of the attention backward (attention_bwd.hip)
-    if (r.kind == R_ATTN) {
-      const Tensor& o = P->ttens[r.o];
-      max_bscratch = std::max(max_bscratch, attention_backward_scratch_bytes(B, o.H * o.W, o.C));
-    }
-  if (max_bscratch > P->t_scratch_bytes) {    // the forward's split-K region doubles as the backward's
-    off -= al(P->t_scratch_bytes);
-    P->t_scratch_bytes = max_bscratch;
-    off += al(max_bscratch);
-  }
-  P->t_dA_off = off; off += al(max_dA);
-  P->t_a_off = off; off += al(max_dA);       // materialised activated input of the weight-gradient GEMM
-  P->t_z_off = off; off += al(bld.max_z);
-  P->t_dq_off = off; off += al(bld.max_dq);
-  P->t_wt_off = off; off += al(max_wt);
-  P->t_wu_off = off; P->t_wu_bytes = max_wu; off += al(max_wu);
-  P->t_slab_off = off; off += al(max_slab);
-  P->t_part_off = off; off += al(max_part);
-  P->t_gs_off = off; off += al((size_t)B * G * 2 * sizeof(double));
-  P->t_dfilm_off = off; off += al((size_t)B * P->F * sizeof(float));
-  P->t_xnoisy_off = off; off += al((size_t)B * (d.in_channel - cond_channels) * S2 * sizeof(float));
-  P->t_eps_off = off; off += al((size_t)B * P->out_ch * S2 * sizeof(float));
-  P->t_geps_off = off; off += al((size_t)B * S2 * 4 * sizeof(float));
-  P->t_inpad_off = off; off += al((size_t)B * S2 * 8 * sizeof(float));
-  P->t_dwtmp_off = off; off += al(4096 * sizeof(double)) + al(max_dwtmp);      // [loss partials | dw temp]
-  P->t_embscr_off = off; off += al((size_t)B * (13 + 16) * inner * sizeof(float));     // (+ the 16 row chunks of k_film_bwd_input)
-  // gradient-ready marks: t_unproc_max[k] = largest arena offset (exclusive end) among the parameters whose
-  // gradients are still unwritten once records k .. end have been processed (records < k + the FiLM /
-  // embedding block at the arena head, which is written last)
-  {
-    const size_t nrec = P->recs.size();
-    P->t_unproc_max.assign(nrec + 1, 0);
-    size_t head_end = P->emb_b2 + (size_t)inner;
-    head_end = std::max(head_end, P->film_b + (size_t)P->F);
-    size_t run = head_end;
-    auto pend = [&](size_t off, size_t n) { return off + n; };
-    for (size_t k = 0; k < nrec; ++k) {
-      P->t_unproc_max[k] = run;
-      const Rec& r = P->recs[k];
-      size_t e = 0;
-      if (r.kind == R_ATTN) { /* no parameters */ }
-      else {
-        const int cout = r.kind == R_CONV_OUT ? P->out_ch : P->ttens[r.out >= 0 ? r.out : 0].C;
-        size_t cin = 0;
-        if (r.kind == R_CONV_IN) cin = d.in_channel;
-        else cin = (size_t)P->ttens[r.x0].C + (r.x1 >= 0 ? P->ttens[r.x1].C : 0);
-        e = std::max(e, pend(r.w, (size_t)cout * r.ksize * r.ksize * cin));
-        e = std::max(e, pend(r.bias, (size_t)cout));
-        if (r.act) { e = std::max(e, pend(r.gamma, cin)); e = std::max(e, pend(r.beta, cin)); }
-        if (r.has_q) {
-          const size_t cq = (size_t)P->ttens[r.q0].C + (r.q1 >= 0 ? P->ttens[r.q1].C : 0);
-          e = std::max(e, pend(r.qw, (size_t)cout * cq));
-          e = std::max(e, pend(r.qb, (size_t)cout));
-        }
-      }
-      run = std::max(run, e);
-    }
-    P->t_unproc_max[nrec] = run;
-  }
-  P->t_ws_bytes = off;
-  P->train_batch = B;
-  P->train_cond = cond_channels;
-  P->train_h = IH; P->train_w = IW;
-  return SR3_OK;
+  TrainWalk w;
+  w.act_high = bld.act.high; w.stats_bytes = bld.stats_cursor; w.gn_bytes = bld.gn_cursor; w.mr_bytes = bld.mr_cursor;
+  w.max_scratch = bld.max_scratch; w.refused = bld.refused;
+  return w;
 }
 
 }  // namespace sr3

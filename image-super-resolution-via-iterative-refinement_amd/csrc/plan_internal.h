@@ -79,18 +79,45 @@ struct Regions {
   size_t stats_off, ss_off, mr_off, temb_off, film_off, scratch_off, scratch_bytes;
 };
 
-// one logical operation of the forward, recorded for the backward walk (train mode)
+// One conv of the forward, for Builder::conv: sources and residuals are tensor handles (-1: absent), parameters arena offsets
+static constexpr size_t NO_PARAM = ~(size_t)0;
+struct ConvSpec {
+  int x0 = -1, x1 = -1;            // source: the virtual concat (x0|x1)
+  int Cout = 0, ksize = 3, stride = 1, ups = 0;
+  int act = 0;                     // ConvParams::act: what the prologue does with the GroupNorm fold in front of this conv
+  size_t w = 0, bias = NO_PARAM;
+  int film_row = -1;               // first row of the FiLM table added to the output
+  int r0 = -1, r1 = -1;            // residual: the concat view (r0|r1)
+  bool want_stats = false;         // a GroupNorm reads the output: fuse its statistics where the kernel can
+  int q0 = -1, q1 = -1; size_t qw = 0, qb = 0;       // fused 1x1 segment (res_conv) over (q0|q1); caller checked fuses_res_conv()
+  int drop_key = -1;               // train-mode dropout on the activated input: the layer's key (drop_layer_seed)
+};
+
+// One data-gradient conv of the backward (dOut -> dA on the flipped-transposed filters) as build_train resolved it: dgrad_conv
+// (train_plan.hip) launches exactly this
+enum WuKind { WU_NONE, WU_WINO, WU_WINO_SPLIT, WU_GEMM };     // the derived filters it reads from the t_wu region: none, Winograd
+                                                              // fp32 / 3 x bf16 split, the pre-split 1x1 weights of gemm1x1.hip
+struct Dgrad {
+  ConvParams c = {};               // shape, wino_split, igemm_split (pointers are bound at launch)
+  int tile = 0, ksplit = 0;        // what conv_forward is called with: tile 11, 22 or 0 (conv_pick chooses)
+  int wu = WU_NONE;
+};
+
+// one logical operation of the forward, recorded for the backward walk (train mode): what the forward walk emitted it from ...
 enum RecKind { R_CONV_IN, R_CONV, R_ATTN, R_CONV_OUT };
 struct Rec {
   int kind = R_CONV;
-  int x0 = -1, x1 = -1, out = -1, r0 = -1, r1 = -1, q0 = -1, q1 = -1;   // tensor handles
-  int ksize = 3, stride = 1, ups = 0, act = 0, film_row = -1;
-  size_t w = 0, bias = 0, qw = 0, qb = 0, gamma = 0, beta = 0;         // parameter arena offsets
-  bool has_bias = false, has_q = false;
-  size_t ss_off = 0, mr_off = 0;     // persistent GroupNorm tables of this conv's prologue (bytes in the workspace)
+  ConvSpec s;                        // (R_CONV_IN / R_CONV_OUT: x0, w, bias, act alone)
+  int out = -1;                      // tensor handle of the output
+  size_t gamma = 0, beta = 0;        // GroupNorm of this conv's prologue: parameter arena offsets ...
+  size_t ss_off = 0, mr_off = 0;     // ... and its persistent tables (bytes in the workspace)
   int qkv = -1, o = -1;              // attention
-  bool has_drop = false;             // block2 conv: train-mode dropout on its activated input
-  unsigned drop_key = 0;
+  // ... and its backward, resolved once by build_train (train_plan.hip): run_train only binds pointers and launches
+  ConvParams dw = {}, dqw = {};      // shape of the weight gradient: the conv's own, the fused res_conv segment's
+  Dgrad dx, dq;                      // data gradient: the conv's own (R_CONV, R_CONV_OUT), the fused segment's
+  bool acc_x0 = true, acc_x1 = true, acc_r0 = true, acc_r1 = true, acc_q0 = true, acc_q1 = true;     // false: the first write of that
+                                     // tensor's gradient in the backward walk, a plain store (the gradient mirror is not zeroed)
+  size_t param_end = 0;              // largest end offset of this record's parameters in the arena (gradient-ready marks)
 };
 
 struct DropCfg { unsigned seed, thresh; float scale; };
@@ -190,7 +217,7 @@ struct sr3_plan {
   size_t t_dA_off = 0, t_z_off = 0, t_dq_off = 0, t_wt_off = 0, t_slab_off = 0, t_part_off = 0, t_gs_off = 0;
   size_t t_dfilm_off = 0, t_misc_off = 0, t_xnoisy_off = 0, t_eps_off = 0, t_geps_off = 0, t_inpad_off = 0, t_dwtmp_off = 0;
   size_t t_ws_bytes = 0, t_embscr_off = 0, t_a_off = 0;
-  size_t t_wu_off = 0, t_wu_bytes = 0;   // Winograd-transformed filters of the data-gradient conv being run
+  size_t t_wu_off = 0, t_wu_bytes = 0;   // derived filters of the data-gradient conv being run (Dgrad::wu)
   std::vector<size_t> t_unproc_max;  // [ri]: max parameter end offset still unwritten before record ri-1 is processed
   int t_final_x = -1;                // tensor handle feeding the output Block
   size_t t_final_ss = 0, t_final_mr = 0;
@@ -208,10 +235,20 @@ int run_forward(sr3_plan* P, const Regions& R, const float* x, const float* cond
                 const int64_t* tstep, const float* freq, const float* level_table, const int* step_dev,
                 const float* params, char* ws, float* eps_out, int B, hipStream_t st, hipEvent_t* ev, hipEvent_t* mid,
                 const DropCfg* drop = nullptr, const StepFuse* fuse = nullptr);
-int build_train(sr3_plan* P, int B, int cond_channels);
-// The Winograd form of one data-gradient conv `g` (dOut -> dA on the flipped-transposed filters), or false: the general kernels run it.
-// Sets g.wino_split to what the launch uses; *split_filters: the 3 x bf16 split form of the transformed filters.  ONE rule for
-// dgrad_conv (train_plan.hip), which launches by it, and build_train, which sizes the slabs and the filter region by it.
-bool dgrad_wino(const sr3_plan* P, ConvParams& g, WinoGeom* wg, bool* split_filters);
+// The forward walk in train mode (plan.hip): fills P->tops, P->ttens and P->recs (every activation kept, persistent GroupNorm
+// tables) and returns what build_train lays the workspace out by
+struct TrainWalk {
+  size_t act_high = 0;                               // high-water mark of the activation arena
+  size_t stats_bytes = 0, gn_bytes = 0, mr_bytes = 0;     // statistics partials, GroupNorm scale/shift tables, mean/rstd tables
+  size_t max_scratch = 0;                            // largest split-K slab set of the forward
+  std::string refused;                               // non-empty: the first layer no kernel can run at this geometry
+};
+TrainWalk walk_train(sr3_plan* P, int B, int cond_channels);
+int build_train(sr3_plan* P, int B, int cond_channels);      // train_plan.hip
+bool wino_ragged_wins(const ConvParams& c);
+// Does a conv that lands on the im2col kernel run its 3 x bf16 split instantiation (plan option gemm_split)?  The 9-tap layers
+// with Cout <= 64 (Downsample of the first level) stay on the fp32 MFMA, which is faster there (67 vs 81 us in the forward).  ONE
+// rule for choose_conv (the forward) and choose_dgrad (the data gradients)
+inline int igemm_split_rule(const sr3_plan* P, const ConvParams& c) { return (P->gemm_split && !(c.ksize == 3 && c.Cout <= 64)) ? 1 : 0; }
 void layout_derived(sr3_plan* P);
 }  // namespace sr3

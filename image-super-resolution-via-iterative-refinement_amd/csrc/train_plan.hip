@@ -13,12 +13,249 @@
 // gradients live in a mirror of the activation arena and are accumulated in stream order.
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "plan_internal.h"
+#include "tile_code.h"
 #include "train.h"
 
 namespace sr3 {
+
+// ---------------------------------------------------------------------------------------------
+// training plan: the forward walk with every activation kept and persistent GroupNorm tables, a gradient mirror of the
+// activation arena, and the backward of every record resolved once -- shapes, kernels, store-or-accumulate -- so that ONE list
+// sizes the scratch regions here and is launched by run_train
+// ---------------------------------------------------------------------------------------------
+namespace {
+constexpr int IN_PAD = 8;      // the input conv's weight gradient reads the image with its channels padded to 8 (nchw_to_nhwc_pad)
+constexpr int OUT_PAD = 4;     // the output conv's gradients read dOut with its channels padded to 4 (l1_loss_grad)
+
+// shape of a record's weight gradient: the forward conv's own geometry
+ConvParams wgrad_shape(const sr3_plan* P, const Rec& r, int B) {
+  const std::vector<Tensor>& T = P->ttens;
+  if (r.kind == R_CONV_IN) return conv_shape(B, T[r.out].H, T[r.out].W, 0, 1, 3, IN_PAD, 0, T[r.out].C);
+  const Tensor& x0 = T[r.s.x0];
+  if (r.kind == R_CONV_OUT) return conv_shape(B, x0.H, x0.W, 0, 1, 3, x0.C, 0, OUT_PAD);
+  ConvParams c = conv_shape(B, x0.H, x0.W, r.s.ups, r.s.stride, r.s.ksize, x0.C, r.s.x1 >= 0 ? T[r.s.x1].C : 0, T[r.out].C);
+  if (r.s.act) { c.C0 += c.C1; c.C1 = 0; }      // the activated input is materialised by act_bwd: a single source
+  return c;
+}
+// ... of the fused res_conv segment's
+ConvParams wgrad_q_shape(const sr3_plan* P, const Rec& r, int B) {
+  const std::vector<Tensor>& T = P->ttens;
+  return conv_shape(B, T[r.out].H, T[r.out].W, 0, 1, 1, T[r.s.q0].C, r.s.q1 >= 0 ? T[r.s.q1].C : 0, T[r.out].C);
+}
+// shape of the data gradient of the forward conv `f`: dOut [B,H,W,f.Cout] (zero-inserted for a stride-2 conv, so H x W is the
+// forward conv's input map behind its upsampling) under a stride-1 conv producing f's input channels
+ConvParams dgrad_shape(const ConvParams& f) { return conv_shape(f.B, f.Hs << f.ups, f.Ws << f.ups, 0, 1, f.ksize, f.Cout, 0, f.C0 + f.C1); }
+
+// The Winograd form of one data-gradient conv `g`, or false: the general kernels run it.  Sets g.wino_split to what the launch
+// uses; *split_filters: the 3 x bf16 split form of the transformed filters.  THE Winograd rule of the backward (choose_dgrad)
+bool dgrad_wino(const sr3_plan* P, ConvParams& g, WinoGeom* wg, bool* split_filters) {
+  g.wino_split = 0;
+  *split_filters = false;
+  if (!P->winograd || g.ksize != 3) return false;
+  // the data gradient has neither a prologue nor dropout, so every 3x3 stride-1 / zero-inserted stride-2 layer with H, W multiples
+  // of 16 qualifies (and the four-image 8 x 8 tile); the one-image tile on its 3 x bf16 split instantiation, as the forward
+  if (wino_geometry(g, wg)) {
+    *split_filters = P->wino_split && wg->NB == 1;
+    g.wino_split = *split_filters ? (P->wino2 ? 2 : 1) : 0;      // (2: the 8 x 16 tile of conv3x3_wino2.hip)
+    return true;
+  }
+  // off the native geometry (plan option train_geom): the two-workgroup kernel on the maps that rule refuses, plain where the map is a
+  // whole multiple of its 8 x 16 tile, ragged where wino_ragged_wins -- wino_mode's rule for the forward
+  if (!P->train_geom || plan_native_geometry(P) || !P->wino_split || !P->wino2) return false;
+  g.wino_split = wino2_fits(g) ? 2 : 3;
+  if ((g.wino_split == 3 && !(P->wino_ragged && wino_ragged_wins(g))) || !wino_geometry(g, wg)) { g.wino_split = 0; return false; }
+  *split_filters = true;
+  return true;
+}
+
+size_t wu_bytes(const Dgrad& d) {
+  if (d.wu == WU_NONE) return 0;
+  return (d.wu == WU_GEMM ? igemm_wsplit_floats(d.c.Cout, 1, d.c.C0) : wino_weight_floats(d.c.Cout, d.c.C0, d.wu == WU_WINO_SPLIT)) * sizeof(float);
+}
+
+// The kernel of the data-gradient conv whose shape d.c holds: THE place where the backward decides it.  A kernel that reads derived
+// filters is taken where they fit `wu_cap` bytes, the 1x1 GEMM kernel where its split-K slabs fit `slab_cap` bytes too
+void choose_dgrad(const sr3_plan* P, Dgrad& d, size_t wu_cap, size_t slab_cap) {
+  ConvParams& c = d.c;
+  d.tile = 0; d.ksplit = 0; c.igemm_split = 0;
+  // 3x3: Winograd F(2x2,3x3) on the flipped-transposed filters where dgrad_wino says so
+  WinoGeom wg;
+  bool split_filters;
+  if (dgrad_wino(P, c, &wg, &split_filters)) {
+    d.tile = 11; d.wu = split_filters ? WU_WINO_SPLIT : WU_WINO;
+    if (wu_bytes(d) <= wu_cap) return;
+    d.tile = 0; c.wino_split = 0;
+  }
+  // 1x1 / 8x8 data gradients on the im2col kernel: its 3 x bf16 split instantiation by the forward's rule
+  c.igemm_split = igemm_split_rule(P, c);
+  // 1x1: the plain GEMM kernel where it fits (plan option gemm2; gemm1x1.hip), its pre-split weights derived from the transposed
+  // filters into the region the Winograd data gradients use for theirs
+  d.wu = WU_GEMM;
+  if (c.igemm_split && P->gemm2 && gemm1x1_fits(c, 2) && (!(c.Cout & 127) || P->gemm_n64) && wu_bytes(d) <= wu_cap) {
+    int t = 22, ks = 0;
+    conv_pick(c, t, ks);
+    if (ks == 1 || (size_t)ks * c.B * c.Ho * c.Wo * c.Cout * sizeof(float) <= slab_cap) { d.tile = 22; d.ksplit = ks; return; }
+  }
+  d.wu = WU_NONE;
+}
+
+// every data gradient of the record list, under the same caps
+void choose_dgrads(sr3_plan* P, size_t wu_cap, size_t slab_cap) {
+  for (Rec& r : P->recs) {
+    if (r.kind == R_CONV || r.kind == R_CONV_OUT) choose_dgrad(P, r.dx, wu_cap, slab_cap);
+    if (r.kind == R_CONV && r.s.q0 >= 0) choose_dgrad(P, r.dq, wu_cap, slab_cap);
+  }
+}
+
+// Shapes, parameter extents and the store-or-accumulate flags of every record's backward.  The activation-gradient mirror is NOT
+// zeroed (round 6: 1.5 ms per step): the first contribution to a tensor's gradient in the backward walk -- the records in reverse,
+// the destinations of a record in the order run_train writes them -- is a plain store, later ones accumulate in stream order
+int resolve_backward(sr3_plan* P, int B) {
+  const std::vector<Tensor>& T = P->ttens;
+  std::vector<char> seen(T.size(), 0);
+  auto acc = [&](int h) { if (h < 0) return true; const bool a = seen[h]; seen[h] = 1; return a; };
+  auto pend = [](size_t off, size_t n) { return off + n; };
+  for (int ri = (int)P->recs.size() - 1; ri >= 0; --ri) {
+    Rec& r = P->recs[ri];
+    const ConvSpec& s = r.s;
+    if (r.kind == R_ATTN) {
+      // attention_backward stores the qkv gradient: nothing may have written it before (with today's walk a qkv tensor has one consumer)
+      if (acc(r.qkv)) { set_error("train: the qkv gradient has an earlier writer"); return SR3_E_UNSUPPORTED; }
+      continue;
+    }
+    r.dw = wgrad_shape(P, r, B);
+    if (r.kind != R_CONV_IN) r.dx.c = dgrad_shape(r.dw);
+    if (r.kind == R_CONV) {
+      r.acc_r0 = acc(s.r0); r.acc_r1 = acc(s.r1);
+      if (s.q0 >= 0) {
+        r.dqw = wgrad_q_shape(P, r, B);
+        r.dq.c = dgrad_shape(r.dqw);
+        r.acc_q0 = acc(s.q0); r.acc_q1 = acc(s.q1);
+      }
+    }
+    if (r.kind != R_CONV_IN) { r.acc_x0 = acc(s.x0); r.acc_x1 = acc(s.x1); }
+    // parameters: the conv's own (the arena holds the real channel counts, not the padded ones), its GroupNorm's, res_conv's
+    const size_t cout = r.kind == R_CONV_OUT ? P->out_ch : r.dw.Cout, cin = r.kind == R_CONV_IN ? P->d.in_channel : r.dw.C0 + r.dw.C1;
+    r.param_end = pend(s.w, cout * s.ksize * s.ksize * cin);
+    if (s.bias != NO_PARAM) r.param_end = std::max(r.param_end, pend(s.bias, cout));
+    if (s.act) r.param_end = std::max({r.param_end, pend(r.gamma, cin), pend(r.beta, cin)});
+    if (s.q0 >= 0) r.param_end = std::max({r.param_end, pend(s.qw, cout * (r.dqw.C0 + r.dqw.C1)), pend(s.qb, cout)});
+  }
+  return SR3_OK;
+}
+}  // namespace
+
+int build_train(sr3_plan* P, int B, int cond_channels) {
+  if (!P->train_geom && !plan_native_geometry(P)) {
+    set_error("training runs at image_size x image_size only: the plan's geometry is %d x %d (sr3_plan_set_geometry(plan, 0, 0) restores %d x %d)",
+              plan_height(P), plan_width(P), P->d.image_size, P->d.image_size);
+    return SR3_E_UNSUPPORTED;
+  }
+  // (the geometry is the native one here unless train_geom; every option that changes the plan resets train_batch: sr3_plan_set_option)
+  const int IH = plan_height(P), IW = plan_width(P);
+  if (P->train_batch == B && P->train_cond == cond_channels && P->train_h == IH && P->train_w == IW) return SR3_OK;
+  const sr3_unet_desc& d = P->d;
+  if (B <= 0) { set_error("batch must be > 0"); return SR3_E_BADARG; }
+  if (cond_channels < 0 || cond_channels >= d.in_channel) { set_error("cond_channels out of range"); return SR3_E_BADARG; }
+  P->train_batch = -1;
+  const TrainWalk fw = walk_train(P, B, cond_channels);
+  // a plan is refused HERE, when it is built, never after a launch has been enqueued: a geometry no kernel can run (as build_forward) ...
+  int rc = SR3_OK;
+  if (!fw.refused.empty()) { set_error("training geometry %d x %d unsupported: %s", IH, IW, fw.refused.c_str()); rc = SR3_E_UNSUPPORTED; }
+  else rc = resolve_backward(P, B);      // ... and a record list the backward walk cannot run
+  if (rc) {
+    P->tops.clear();
+    P->recs.clear();
+    return rc;
+  }
+  choose_dgrads(P, ~(size_t)0, ~(size_t)0);      // every kernel the data gradients could run on: the regions are sized by these
+  const size_t S2 = (size_t)IH * IW;
+  const int inner = d.inner_channel, G = d.norm_groups;
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  auto raise = [](size_t& m, size_t v) { m = std::max(m, v); };
+  auto fbytes = [](const ConvParams& c, size_t channels) { return (size_t)c.B * c.Ho * c.Wo * channels * sizeof(float); };
+  // backward scratch: every region is the maximum over the resolved records
+  size_t max_dA = 0, max_z = 0, max_dq = 0, max_wt = 0, max_wu = 0, max_slab = 0, max_part = 0, max_dwtmp = 0;
+  size_t max_bscratch = 0;                    // split-K slabs of the data-gradient convs, dK / dV slabs of the attention backward
+  for (const Rec& r : P->recs) {
+    if (r.kind == R_ATTN) {
+      raise(max_bscratch, attention_backward_scratch_bytes(B, P->ttens[r.o].H * P->ttens[r.o].W, P->ttens[r.o].C));
+      continue;
+    }
+    const ConvParams& w = r.dw;
+    raise(max_slab, wgrad_slab_bytes(w, nullptr));
+    raise(max_part, (size_t)B * chan_stats_slices(B, w.Ho * w.Wo, w.Cout) * w.Cout * 2 * sizeof(double));      // colsums of dOut
+    if (r.kind != R_CONV) raise(max_dwtmp, (size_t)w.Cout * 9 * w.C0 * sizeof(float));       // padded filters, compacted into the arena
+    if (r.kind == R_CONV_IN) continue;
+    const ConvParams& g = r.dx.c;
+    raise(max_part, act_bwd_part_bytes(B, w.Hs * w.Ws, w.C0 + w.C1));
+    raise(max_dA, fbytes(g, g.Cout));
+    raise(max_wt, (size_t)g.C0 * g.ksize * g.ksize * g.Cout * sizeof(float));
+    if (w.stride == 2) raise(max_z, 4 * fbytes(w, w.Cout));
+    raise(max_bscratch, conv_splitk_bytes(g, 0, 0));
+    // KEPT QUIRK: only the Winograd data gradients of the R_CONV records size t_wu and the tile-11 slabs.  Neither the output conv's
+    // Winograd form nor any tile-22 data gradient is sized for: they run where some other layer made the regions large enough (below)
+    if (r.kind == R_CONV && r.dx.tile == 11) {
+      raise(max_bscratch, conv_splitk_bytes(g, 11, 0));
+      raise(max_wu, wu_bytes(r.dx));
+    }
+    if (r.s.q0 >= 0) {
+      raise(max_slab, wgrad_slab_bytes(r.dqw, nullptr));
+      raise(max_dq, fbytes(r.dq.c, r.dq.c.Cout));
+      raise(max_wt, (size_t)r.dq.c.C0 * r.dq.c.Cout * sizeof(float));
+      raise(max_bscratch, conv_splitk_bytes(r.dq.c, 0, 0));
+    }
+  }
+  size_t off = al(fw.act_high);
+  P->t_act_bytes = off;
+  off *= 2;                                   // gradients mirror the activations at +t_act_bytes
+  P->t_stats_off = off; off += al(fw.stats_bytes);
+  P->t_gn_off = off; off += al(fw.gn_bytes);
+  P->t_misc_off = off; off += al(fw.mr_bytes);             // mean / rstd tables
+  P->t_temb_off = off; off += al((size_t)B * inner * sizeof(float));
+  P->t_film_off = off; off += al((size_t)B * P->F * sizeof(float));
+  P->t_scratch_bytes = std::max(fw.max_scratch, max_bscratch);      // the forward's split-K region doubles as the backward's
+  P->t_scratch_off = off; off += al(P->t_scratch_bytes);
+  P->t_dA_off = off; off += al(max_dA);
+  P->t_a_off = off; off += al(max_dA);       // materialised activated input of the weight-gradient GEMM
+  P->t_z_off = off; off += al(max_z);
+  P->t_dq_off = off; off += al(max_dq);
+  P->t_wt_off = off; off += al(max_wt);
+  P->t_wu_off = off; P->t_wu_bytes = max_wu; off += al(max_wu);
+  P->t_slab_off = off; off += al(max_slab);
+  P->t_part_off = off; off += al(max_part);
+  P->t_gs_off = off; off += al((size_t)B * G * 2 * sizeof(double));
+  P->t_dfilm_off = off; off += al((size_t)B * P->F * sizeof(float));
+  P->t_xnoisy_off = off; off += al((size_t)B * (d.in_channel - cond_channels) * S2 * sizeof(float));
+  P->t_eps_off = off; off += al((size_t)B * P->out_ch * S2 * sizeof(float));
+  P->t_geps_off = off; off += al((size_t)B * S2 * OUT_PAD * sizeof(float));
+  P->t_inpad_off = off; off += al((size_t)B * S2 * IN_PAD * sizeof(float));
+  P->t_dwtmp_off = off; off += al(4096 * sizeof(double)) + al(max_dwtmp);      // [loss partials | dw temp]
+  P->t_embscr_off = off; off += al((size_t)B * (13 + 16) * inner * sizeof(float));     // (+ the 16 row chunks of k_film_bwd_input)
+  P->t_ws_bytes = off;
+  // KEPT QUIRK: THIS PASS settles the kernels that read derived filters nothing above sized for -- taken exactly where the filters fit
+  // t_wu and (tile 22) the slabs fit t_scratch as sized.  Sizing for them would move workspace sizes and kernel choices: a change of its own
+  choose_dgrads(P, P->t_wu_bytes, P->t_scratch_bytes);
+  // gradient-ready marks: t_unproc_max[k] = largest arena offset (exclusive end) among the parameters whose
+  // gradients are still unwritten once records k .. end have been processed (records < k + the FiLM /
+  // embedding block at the arena head, which is written last)
+  const size_t nrec = P->recs.size();
+  P->t_unproc_max.assign(nrec + 1, 0);
+  size_t run = std::max(P->emb_b2 + (size_t)inner, P->film_b + (size_t)P->F);
+  for (size_t k = 0; k < nrec; ++k) {
+    P->t_unproc_max[k] = run;
+    run = std::max(run, P->recs[k].param_end);
+  }
+  P->t_unproc_max[nrec] = run;
+  P->train_batch = B;
+  P->train_cond = cond_channels;
+  P->train_h = IH; P->train_w = IW;
+  return SR3_OK;
+}
 
 namespace {
 struct TrainCtx {
@@ -29,53 +266,30 @@ struct TrainCtx {
   int B;
   hipStream_t st;
   const float* act(int h) const { return reinterpret_cast<const float*>(ws + P->ttens[h].off); }
-  float* grad(int h) const { return reinterpret_cast<float*>(ws + P->t_act_bytes + P->ttens[h].off); }
+  float* grad(int h) const { return h >= 0 ? reinterpret_cast<float*>(ws + P->t_act_bytes + P->ttens[h].off) : nullptr; }
   template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(ws + off); }
 };
 
-// dOut [B,H,W,Cg] --(conv with flipped-transposed weights)--> dA [B,H,W,Cin]
-int dgrad_conv(const TrainCtx& X, const float* g, int Cg, int H, int W, int ksize, const float* w, int Cout_w, int Cin,
-               float* dA) {
+// dOut [B,H,W,Cg] --(conv with flipped-transposed weights)--> dA [B,H,W,Cin], on the kernel build_train chose; the arena holds
+// `Cout_w` <= Cg of the Cg filters (the output conv's padding)
+int dgrad_conv(const TrainCtx& X, const Dgrad& d, const float* g, const float* w, int Cout_w, float* dA) {
+  ConvParams c = d.c;
   float* wt = X.at<float>(X.P->t_wt_off);
-  int rc = w_flip_transpose(w, Cout_w, ksize * ksize, Cin, Cg, wt, X.st);
+  float* wu = X.at<float>(X.P->t_wu_off);
+  int rc = w_flip_transpose(w, Cout_w, c.ksize * c.ksize, c.Cout, c.C0, wt, X.st);
   if (rc) return rc;
-  ConvParams c;
-  memset(&c, 0, sizeof(c));
-  c.src0 = g; c.C0 = Cg; c.B = X.B; c.Hs = H; c.Ws = W; c.stride = 1; c.ksize = ksize; c.Ho = H; c.Wo = W;
-  c.Cout = Cin; c.w = wt; c.out = dA; c.ksplit = 1;
-  // 3x3: Winograd F(2x2,3x3) on the flipped-transposed filters where dgrad_wino (plan.hip) says so -- the rule build_train sized
-  // the slabs and the filter region by
-  WinoGeom wg;
-  bool split_filters;
-  if (dgrad_wino(X.P, c, &wg, &split_filters) && wino_weight_floats(Cin, Cg, split_filters) * sizeof(float) <= X.P->t_wu_bytes) {
-    float* wu = X.at<float>(X.P->t_wu_off);
-    rc = wino_transform_weights(wt, Cin, Cg, wu, X.st, split_filters);
-    if (rc) return rc;
-    c.wino_u = wu;
-    return conv_forward(c, 11, 0, X.at<float>(X.P->t_scratch_off), X.P->t_scratch_bytes, X.st);
-  }
-  c.wino_split = 0;
-  // 1x1 / 8x8 data gradients on the im2col kernel: its 3 x bf16 split instantiation, with the forward Builder's exclusion (9-tap
-  // layers producing <= 64 channels stay on the fp32 MFMA: plan.hip, Builder::conv) -- build_train sizes the scratch with the same rule
-  c.igemm_split = (X.P->gemm_split && !(ksize == 3 && c.Cout <= 64)) ? 1 : 0;
-  // 1x1: the plain GEMM kernel where it fits (plan option gemm2; gemm1x1.hip), its pre-split weights derived from the transposed filters
-  // into the region the Winograd data gradients use for theirs
-  if (c.igemm_split && X.P->gemm2 && gemm1x1_fits(c, 2) && (!(c.Cout & 127) || X.P->gemm_n64) && igemm_wsplit_floats(Cin, 1, Cg) * sizeof(float) <= X.P->t_wu_bytes) {
-    float* ws_ = X.at<float>(X.P->t_wu_off);
-    rc = igemm_split_weights(wt, Cin, 1, Cg, ws_, X.st);
-    if (rc) return rc;
-    c.w_split = ws_;
-    int t = 22, ks = 0;
-    conv_pick(c, t, ks);
-    if ((size_t)ks * X.B * H * W * Cin * sizeof(float) <= X.P->t_scratch_bytes || ks == 1)
-      return conv_forward(c, 22, ks, X.at<float>(X.P->t_scratch_off), X.P->t_scratch_bytes, X.st);
-    c.w_split = nullptr;
-  }
-  return conv_forward(c, 0, 0, X.at<float>(X.P->t_scratch_off), X.P->t_scratch_bytes, X.st);
+  c.src0 = g; c.w = wt; c.out = dA;
+  if (d.wu == WU_GEMM) { rc = igemm_split_weights(wt, c.Cout, 1, c.C0, wu, X.st); c.w_split = wu; }
+  else if (d.wu != WU_NONE) { rc = wino_transform_weights(wt, c.Cout, c.C0, wu, X.st, d.wu == WU_WINO_SPLIT); c.wino_u = wu; }
+  if (rc) return rc;
+  return conv_forward(c, d.tile, d.ksplit, X.at<float>(X.P->t_scratch_off), X.P->t_scratch_bytes, X.st);
 }
 
-int wgrad_call(const TrainCtx& X, ConvParams c, const float* dy, float* dw) {
+// weight gradient of the shape `c` over the sources src0 | src1.  wgrad_split is a no-rebuild option (the slabs are sized for both
+// values), so msplit is computed here
+int wgrad_call(const TrainCtx& X, ConvParams c, const float* src0, const float* src1, const float* dy, float* dw) {
   WgradParams wp;
+  c.src0 = src0; c.src1 = src1;
   c.wgrad_split = X.P->wgrad_split;
   wp.c = c;
   wp.dy = dy;
@@ -113,12 +327,10 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
   // ---- loss and its gradient (NHWC, channel dim padded to 4) ----
   float* geps = X.at<float>(P->t_geps_off);
   double* lparts = X.at<double>(P->t_dwtmp_off);
-  rc = l1_loss_grad(z, eps, B, P->out_ch, S2, 4, grad_scale, P->loss_l2 != 0, geps, lparts, loss_out, st);
+  rc = l1_loss_grad(z, eps, B, P->out_ch, S2, OUT_PAD, grad_scale, P->loss_l2 != 0, geps, lparts, loss_out, st);
   if (rc) return rc;
-  // ---- the activation-gradient mirror is NOT zeroed (round 6: 1.5 ms per step): the first contribution to a tensor's gradient in this
-  // walk is a plain store (`first` below), later ones accumulate in stream order; the FiLM gradient table is zeroed ----
-  std::vector<char> seen(P->ttens.size(), 0);
-  auto first = [&](int h) { if (h < 0) return false; const bool f = !seen[h]; seen[h] = 1; return f; };
+  // ---- the backward walk: the records in reverse, each as build_train resolved it.  The activation-gradient mirror is not zeroed
+  // (Rec::acc_*); the FiLM gradient table is ----
   float* dfilm = X.at<float>(P->t_dfilm_off);
   SR3_HIP(hipMemsetAsync(dfilm, 0, (size_t)B * P->F * sizeof(float), st));
 
@@ -135,129 +347,99 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
       ++next_mark;
     }
     const Rec& r = P->recs[ri];
+    const ConvSpec& s = r.s;
+    float* abuf = X.at<float>(P->t_a_off);        // the activated input of a conv, written by act_bwd's first pass
     if (r.kind == R_CONV_OUT) {
-      const Tensor& x0 = P->ttens[r.x0];
-      const int C = x0.C;
+      const int C = r.dw.C0;
       // bias (3 of the 4 padded columns are real; arena slots are 4-float aligned)
-      rc = colsums(geps, B, S2, 4, part, grads + r.bias, nullptr, 0, st);
+      rc = colsums(geps, B, S2, OUT_PAD, part, grads + s.bias, nullptr, 0, st);
       if (rc) return rc;
-      rc = dgrad_conv(X, geps, 4, IH, IW, 3, params + r.w, P->out_ch, C, dA);
+      rc = dgrad_conv(X, r.dx, geps, params + s.w, P->out_ch, dA);
       if (rc) return rc;
-      rc = act_bwd(dA, X.act(r.x0), nullptr, C, 0, B, S2, X.at<float>(P->t_gn_off + r.ss_off),
-                   X.at<float>(P->t_misc_off + r.mr_off), G, 2, params + r.gamma, part, gs, grads + r.gamma,
-                   grads + r.beta, X.grad(r.x0), nullptr, st, 0u, 0u, 1.f, X.at<float>(P->t_a_off), !first(r.x0), true);
+      rc = act_bwd(dA, X.act(s.x0), nullptr, C, 0, B, S2, X.at<float>(P->t_gn_off + r.ss_off),
+                   X.at<float>(P->t_misc_off + r.mr_off), G, s.act, params + r.gamma, part, gs, grads + r.gamma,
+                   grads + r.beta, X.grad(s.x0), nullptr, st, 0u, 0u, 1.f, abuf, r.acc_x0, true);
       if (rc) return rc;
-      ConvParams c;
-      memset(&c, 0, sizeof(c));
-      float* abuf = X.at<float>(P->t_a_off);        // (the activated input, written by act_bwd's first pass)
-      c.src0 = abuf; c.C0 = C; c.B = B; c.Hs = IH; c.Ws = IW; c.stride = 1; c.ksize = 3; c.Ho = IH; c.Wo = IW;
-      c.Cout = 4;
-      rc = wgrad_call(X, c, geps, dwtmp);
+      rc = wgrad_call(X, r.dw, abuf, nullptr, geps, dwtmp);
       if (rc) return rc;
-      SR3_HIP(hipMemcpyAsync(grads + r.w, dwtmp, (size_t)P->out_ch * 9 * C * sizeof(float), hipMemcpyDeviceToDevice, st));
+      SR3_HIP(hipMemcpyAsync(grads + s.w, dwtmp, (size_t)P->out_ch * 9 * C * sizeof(float), hipMemcpyDeviceToDevice, st));
     } else if (r.kind == R_ATTN) {
       const Tensor& o = P->ttens[r.o];
       // dK / dV through per-query-block slabs in the backward's scratch region, summed in block order: no atomics (round 6)
-      if (!first(r.qkv)) { set_error("train: the qkv gradient has an earlier writer"); return SR3_E_UNSUPPORTED; }     // (attention_backward stores)
       rc = attention_backward(X.act(r.qkv), X.grad(r.o), X.act(r.o), B, o.H * o.W, o.C, X.grad(r.qkv), st,
                               X.at<float>(P->t_scratch_off), P->t_scratch_bytes);
       if (rc) return rc;
     } else if (r.kind == R_CONV_IN) {
-      const Tensor& o = P->ttens[r.out];
+      const int Cout = r.dw.Cout;
       float* inpad = X.at<float>(P->t_inpad_off);
       const float* a = cond_channels > 0 ? cond : x_noisy;
       const int Ca = cond_channels > 0 ? cond_channels : xc;
       const float* b2 = cond_channels > 0 ? x_noisy : nullptr;
       const int Cb = cond_channels > 0 ? xc : 0;
-      rc = nchw_to_nhwc_pad(a, Ca, b2, Cb, B, S2, 8, inpad, st);
+      rc = nchw_to_nhwc_pad(a, Ca, b2, Cb, B, S2, IN_PAD, inpad, st);
       if (rc) return rc;
-      rc = colsums(X.grad(r.out), B, S2, o.C, part, grads + r.bias, nullptr, 0, st);
+      rc = colsums(X.grad(r.out), B, S2, Cout, part, grads + s.bias, nullptr, 0, st);
       if (rc) return rc;
-      ConvParams c;
-      memset(&c, 0, sizeof(c));
-      c.src0 = inpad; c.C0 = 8; c.B = B; c.Hs = IH; c.Ws = IW; c.stride = 1; c.ksize = 3; c.Ho = IH; c.Wo = IW; c.Cout = o.C;
-      rc = wgrad_call(X, c, X.grad(r.out), dwtmp);
+      rc = wgrad_call(X, r.dw, inpad, nullptr, X.grad(r.out), dwtmp);
       if (rc) return rc;
       // compact [Cout][9][8] -> [Cout][9][in_channel]
-      SR3_HIP(hipMemcpy2DAsync(grads + r.w, (size_t)d.in_channel * sizeof(float), dwtmp, 8 * sizeof(float),
-                               (size_t)d.in_channel * sizeof(float), (size_t)o.C * 9, hipMemcpyDeviceToDevice, st));
+      SR3_HIP(hipMemcpy2DAsync(grads + s.w, (size_t)d.in_channel * sizeof(float), dwtmp, IN_PAD * sizeof(float),
+                               (size_t)d.in_channel * sizeof(float), (size_t)Cout * 9, hipMemcpyDeviceToDevice, st));
     } else {
-      const Tensor& x0 = P->ttens[r.x0];
-      const Tensor& o = P->ttens[r.out];
-      const int C0 = x0.C, C1 = r.x1 >= 0 ? P->ttens[r.x1].C : 0, Cin = C0 + C1;
-      const int Ho = o.H, Wo = o.W, Cout = o.C;
+      const Tensor& x0 = P->ttens[s.x0];
+      const int C0 = x0.C, C1 = s.x1 >= 0 ? P->ttens[s.x1].C : 0;
+      const int Ho = r.dw.Ho, Wo = r.dw.Wo, Cout = r.dw.Cout;
+      const bool has_bias = s.bias != NO_PARAM, has_q = s.q0 >= 0;
       const float* g = X.grad(r.out);
-      const float* x0p = X.act(r.x0);
-      const float* x1p = r.x1 >= 0 ? X.act(r.x1) : nullptr;
-      float* d0 = X.grad(r.x0);
-      float* d1 = r.x1 >= 0 ? X.grad(r.x1) : nullptr;
+      const float* x0p = X.act(s.x0);
+      const float* x1p = s.x1 >= 0 ? X.act(s.x1) : nullptr;
       // 1. bias and FiLM gradients: column sums of dOut
-      if (r.has_bias || r.film_row >= 0 || r.has_q) {
-        rc = colsums(g, B, Ho * Wo, Cout, part, r.has_bias ? grads + r.bias : nullptr,
-                     r.film_row >= 0 ? dfilm + r.film_row : nullptr, P->F, st);
+      if (has_bias || s.film_row >= 0 || has_q) {
+        rc = colsums(g, B, Ho * Wo, Cout, part, has_bias ? grads + s.bias : nullptr,
+                     s.film_row >= 0 ? dfilm + s.film_row : nullptr, P->F, st);
         if (rc) return rc;
-        if (r.has_q)      // res_conv bias sees the same sums
-          SR3_HIP(hipMemcpyAsync(grads + r.qb, grads + r.bias, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (has_q)        // res_conv bias sees the same sums
+          SR3_HIP(hipMemcpyAsync(grads + s.qb, grads + s.bias, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, st));
       }
       // 2. identity residual
-      if (r.r0 >= 0) {
-        const bool a0 = !first(r.r0), a1 = !first(r.r1);
-        rc = grad_route(g, P->ttens[r.r0].C, r.r1 >= 0 ? P->ttens[r.r1].C : 0, B, Ho, Wo, 0, X.grad(r.r0),
-                        r.r1 >= 0 ? X.grad(r.r1) : nullptr, st, a0, a1);
+      if (s.r0 >= 0) {
+        rc = grad_route(g, P->ttens[s.r0].C, s.r1 >= 0 ? P->ttens[s.r1].C : 0, B, Ho, Wo, 0, X.grad(s.r0), X.grad(s.r1), st,
+                        r.acc_r0, r.acc_r1);
         if (rc) return rc;
       }
       // 3. fused res_conv segment
-      if (r.has_q) {
-        const int Q0 = P->ttens[r.q0].C, Q1 = r.q1 >= 0 ? P->ttens[r.q1].C : 0;
+      if (has_q) {
         float* dq = X.at<float>(P->t_dq_off);
-        rc = dgrad_conv(X, g, Cout, Ho, Wo, 1, params + r.qw, Cout, Q0 + Q1, dq);
+        rc = dgrad_conv(X, r.dq, g, params + s.qw, Cout, dq);
         if (rc) return rc;
-        const bool a0 = !first(r.q0), a1 = !first(r.q1);
-        rc = grad_route(dq, Q0, Q1, B, Ho, Wo, 0, X.grad(r.q0), r.q1 >= 0 ? X.grad(r.q1) : nullptr, st, a0, a1);
+        rc = grad_route(dq, r.dqw.C0, r.dqw.C1, B, Ho, Wo, 0, X.grad(s.q0), X.grad(s.q1), st, r.acc_q0, r.acc_q1);
         if (rc) return rc;
-        ConvParams c;
-        memset(&c, 0, sizeof(c));
-        c.src0 = X.act(r.q0); c.src1 = r.q1 >= 0 ? X.act(r.q1) : nullptr; c.C0 = Q0; c.C1 = Q1; c.B = B; c.Hs = Ho; c.Ws = Wo;
-        c.stride = 1; c.ksize = 1; c.Ho = Ho; c.Wo = Wo; c.Cout = Cout;
-        rc = wgrad_call(X, c, g, grads + r.qw);
+        rc = wgrad_call(X, r.dqw, X.act(s.q0), s.q1 >= 0 ? X.act(s.q1) : nullptr, g, grads + s.qw);
         if (rc) return rc;
       }
       // 4. main segment: data gradient
-      const int Hi = x0.H << r.ups, Wi = x0.W << r.ups;
       const float* gsrc = g;
-      if (r.stride == 2) {
+      if (s.stride == 2) {
         float* zb = X.at<float>(P->t_z_off);
         rc = zero_insert(g, B, Ho, Wo, Cout, zb, st);
         if (rc) return rc;
         gsrc = zb;
       }
-      rc = dgrad_conv(X, gsrc, Cout, Hi, Wi, r.ksize, params + r.w, Cout, Cin, dA);
+      rc = dgrad_conv(X, r.dx, gsrc, params + s.w, Cout, dA);
       if (rc) return rc;
-      const bool dropped = r.has_drop && dc.thresh != 0;
-      const unsigned lseed = drop_layer_seed(dc.seed, r.drop_key);
-      const bool acc0 = !first(r.x0), acc1 = !first(r.x1);
-      if (r.act) {
+      if (s.act) {
+        const bool dropped = s.drop_key >= 0 && dc.thresh != 0;
+        const unsigned lseed = drop_layer_seed(dc.seed, (unsigned)(s.drop_key >= 0 ? s.drop_key : 0));
         rc = act_bwd(dA, x0p, x1p, C0, C1, B, x0.H * x0.W, X.at<float>(P->t_gn_off + r.ss_off),
-                     X.at<float>(P->t_misc_off + r.mr_off), G, r.act, params + r.gamma, part, gs, grads + r.gamma,
-                     grads + r.beta, d0, d1, st, lseed, dropped ? dc.thresh : 0u, dc.scale, X.at<float>(P->t_a_off), acc0, acc1);
+                     X.at<float>(P->t_misc_off + r.mr_off), G, s.act, params + r.gamma, part, gs, grads + r.gamma,
+                     grads + r.beta, X.grad(s.x0), X.grad(s.x1), st, lseed, dropped ? dc.thresh : 0u, dc.scale, abuf, r.acc_x0, r.acc_x1);
       } else {
-        rc = grad_route(dA, C0, C1, B, x0.H, x0.W, r.ups, d0, d1, st, acc0, acc1);
+        rc = grad_route(dA, C0, C1, B, x0.H, x0.W, s.ups, X.grad(s.x0), X.grad(s.x1), st, r.acc_x0, r.acc_x1);
       }
       if (rc) return rc;
-      // 5. weight gradient
-      ConvParams c;
-      memset(&c, 0, sizeof(c));
-      c.B = B; c.Hs = x0.H; c.Ws = x0.W; c.ups = r.ups; c.stride = r.stride;
-      c.ksize = r.ksize; c.Ho = Ho; c.Wo = Wo; c.Cout = Cout;
-      if (r.act) {
-        // the activated (and dropped) input is materialised once instead of being recomputed per tap: by act_bwd's first pass
-        // above (round 6; it was a pass of its own over x, k_apply_act)
-        float* abuf = X.at<float>(P->t_a_off);
-        c.src0 = abuf; c.C0 = Cin; c.C1 = 0;
-      } else {
-        c.src0 = x0p; c.src1 = x1p; c.C0 = C0; c.C1 = C1;
-      }
-      rc = wgrad_call(X, c, g, grads + r.w);
+      // 5. weight gradient.  The activated (and dropped) input is materialised once instead of being recomputed per tap: by act_bwd's
+      // first pass above (round 6; it was a pass of its own over x, k_apply_act)
+      rc = s.act ? wgrad_call(X, r.dw, abuf, nullptr, g, grads + s.w) : wgrad_call(X, r.dw, x0p, x1p, g, grads + s.w);
       if (rc) return rc;
     }
   }

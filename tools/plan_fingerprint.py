@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Host-side fingerprint of everything the planner decides (no GPU needed): the launch list of every network under every plan
-option, batch size and geometry, and the per-op scratch / statistics-slice queries over a grid of shapes and ABI tile numbers.
+option, batch size and geometry, the per-op scratch / statistics-slice queries over a grid of shapes and ABI tile numbers, and
+the training workspace size (or refusal) of every network under train_geom at every geometry and option.
 
   python tools/plan_fingerprint.py --out full.jsonl          one JSON record per case (what to diff between two builds)
   python tools/plan_fingerprint.py --golden COMMIT           rewrite tests/golden/plan_fingerprint.json: per-case SHA-256 + size
@@ -33,6 +34,13 @@ OPTIONS = ([('default', None)]
            + [('fork_side', 1), ('attn_long', 1), ('keep_all', 1)]
            + [('gemm_tile', v) for v in (1, 2, 3, 4)] + [('tile_cfg', v) for v in (1, 2, 3, 4, 5, 6, 9, 11)]
            + [('ksplit', v) for v in (1, 2, 4)])
+# training plans (train_geom = 1): every network x batch x geometry under each of these, appended behind the cases above
+TRAIN_BATCHES = (1, 2, 4, 16, 64)
+TRAIN_TINY_GEOMETRIES = ((16, 24), (24, 16), (80, 64))       # the networks of tests/helpers.py, beside their native 16 x 16
+TRAIN_OPTIONS = ([('default', None)]
+                 + [(k, 0) for k in ('winograd', 'wino_split', 'wino2', 'wino_ragged', 'gemm_split', 'gemm2', 'gemm_n64', 'fuse_res',
+                                     'fuse_stats')]
+                 + [('tile_cfg', 5), ('ksplit', 1)])
 Q_BATCHES = (1, 4, 16)
 Q_MAPS = ((4, 4), (8, 8), (11, 8), (16, 16), (22, 16), (32, 32), (64, 64), (128, 128))
 Q_CHANNELS = (64, 128, 256, 320, 512, 1024)
@@ -84,6 +92,27 @@ def plan_case(args, geometry, option, value, batch):
     return rec
 
 
+def train_case(args, geometry, option, value, batch):
+    """The training workspace size of one plan under train_geom, or the whole refusal text; a refused plan is asked again
+    under attn_long."""
+    plan = E.Plan(*args)
+    lib, h = plan.lib, plan.handle
+    plan.set_option('train_geom', 1)
+    if option != 'default':
+        plan.set_option(option, value)
+    if geometry:
+        plan.set_geometry(*geometry)
+    cond = plan.in_channel - plan.out_channel if plan.in_channel > plan.out_channel else 0
+    rec = {'train_workspace_bytes': int(lib.sr3_train_workspace_bytes(h, batch, cond))}
+    if rec['train_workspace_bytes'] == 0:
+        rec['train_refused'] = last_error(lib)
+        plan.set_option('attn_long', 1)
+        rec['attn_long_train_workspace_bytes'] = int(lib.sr3_train_workspace_bytes(h, batch, cond))
+        if rec['attn_long_train_workspace_bytes'] == 0:
+            rec['attn_long_train_refused'] = last_error(lib)
+    return rec
+
+
 def query_case(lib, B, H, W):
     scratch, slices = [], []
     for cin in Q_CHANNELS:
@@ -111,6 +140,13 @@ def cases():
     for B in Q_BATCHES:
         for H, W in Q_MAPS:
             yield 'query/B%d/%dx%d' % (B, H, W), query_case(lib, B, H, W)
+    for name, args in networks():
+        for geometry in (None,) + GEOMETRIES.get(name, ()) + (TRAIN_TINY_GEOMETRIES if name in DESCS else ()):
+            for option, value in TRAIN_OPTIONS:
+                for batch in TRAIN_BATCHES:
+                    cid = 'train/%s/%s/%s/B%d' % (name, '%dx%d' % geometry if geometry else 'native',
+                                                  option if value is None else '%s=%d' % (option, value), batch)
+                    yield cid, train_case(args, geometry, option, value, batch)
 
 
 def dumps(rec):
