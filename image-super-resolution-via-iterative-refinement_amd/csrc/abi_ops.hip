@@ -65,7 +65,7 @@ int sr3_conv_f32(const float* src0, int C0, const float* src1, int C1, int B, in
   c.res0 = res0; c.res1 = res1; c.RC0 = res0 ? RC0 : 0; c.RC1 = res1 ? RC1 : 0;
   c.out = out; c.ostat = out_stats;
   const TileCode t = tile_decode(tile_cfg);
-  c.wino_split = t.wino_split; c.igemm_split = t.igemm_split; tile_cfg = t.tile;
+  c.wino_split = t.wino_split; c.wino_full = t.wino_full; c.igemm_split = t.igemm_split; tile_cfg = t.tile;
   if (t.wpre) {
     // the weights pre-split into bf16 planes (what a plan does, in its derived buffer): derived here
     if (tile_cfg == 22 && !gemm1x1_fits(c, 2)) { set_error("conv: the 1x1 GEMM kernel (tile 22) does not fit this problem"); return SR3_E_UNSUPPORTED; }

@@ -20,6 +20,7 @@
 // RAGGED instantiation (ConvParams::wino_split == 3, tile_cfg 23 at the ABI): the same kernel on maps of ANY size -- the tile grid is
 // ceil(W / 16) x ceil(H / 8), overhanging tile rows / columns read zeros (the staging's padding rule) and the epilogue masks every
 // pixel it stores, adds as a residual or counts in the statistics.  The arithmetic of a pixel that exists is the same.
+// UP instantiation (ups == 1, both forms): Upsample's conv runs nine of the sixteen positions -- see the kernel.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -69,7 +70,13 @@ __device__ __forceinline__ float silu_v(float v) {      // (conv3x3_wino.hip: si
 // the 3-way split.
 // Global loads outside the main loop are unconditional and consumed in issue order (absent operands: a valid dummy address,
 // discarded by a select) -- the in-order vmcnt rule of conv3x3_wino.hip.
-template <int DBG, bool RAGGED = false>
+// UP instantiation (ConvParams::ups == 1 without ConvParams::wino_full): the conv of a nearest x2 upsampled map.  The tile grid starts at
+// even output pixels, so a 4 x 4 patch covers upsampled rows 2m - 1 .. 2m + 2 = source rows m - 1, m, m, m + 1: patch rows (and columns)
+// 1 and 2 hold the same staged values -- padding replaces only row 0 or row 3, the maps being even -- and row 2 and column 2 of
+// B^T d B (d2 - d1) are exactly zero.  Seven of the sixteen positions multiply a zero operand: waves 0, 1 and 3 run rows 0, 1 and 3 (three
+// MFMA groups per chunk, three U slots, 96 accumulators), wave 2 stages, keeps the barriers and stores its share of the epilogue, and
+// nobody reads its exchange plane.  The additions that remain keep their order: same bits as the sixteen-position loop (finite filters).
+template <int DBG, bool RAGGED = false, bool UP = false>
 __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, const WinoGeom g, const __bf16* __restrict__ ufrag) {
   extern __shared__ f32x4 smem_w2[];
   float* smem = reinterpret_cast<float*>(smem_w2);
@@ -279,7 +286,10 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
 
   // ---- U fragments: two slots of [nblk][plane] bf16x8, a position (i, j) per slot, straight from global in fragment-major order
   // (k_wino_weights_split); slot s = i & 1 is refilled with position i + 2 right after position i's MFMA group ----
-  bf16x8 us[2][2][3];
+  // UP: three slots, one per row that is computed (0, 1, 3); behind a row's group the slot the group BEFORE it read is refilled -- two
+  // slots are live at any time, as above, and a fragment is in flight for one MFMA group
+  constexpr int NR = UP ? 3 : 4;  // rows of the column a wave accumulates: acc[a] is row a, UP: row (0, 1, 3)[a]
+  bf16x8 us[UP ? 3 : 2][2][3];
   const __bf16* ubase_s = nullptr;                  // set per tile (cout block), wave-uniform
   auto load_us = [&](int chunk, int i, int slot) {
     if ((DBG & 16) && chunk != c_begin) return;
@@ -294,7 +304,7 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
         us[slot][n][pl] = *(const __attribute__((address_space(1))) bf16x8*)(qn + (size_t)vo + pl * 1024);
     }
   };
-  f32x16 acc[4][2];             // [row i][nblk]
+  f32x16 acc[NR][2];            // [row][nblk]
   // half of the 12 MFMAs of position (i, j): product-major over the two n blocks (two independent accumulators between dependent
   // MFMAs), smallest terms first
   auto mfma_half = [&](int i, int slot, int half) {
@@ -356,19 +366,42 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
     // ================================ prologue ================================
     const float* cs_ = cst + par * VCST_F;
     ubase_s = ufrag + (size_t)cb * nch * 16 * (2 * VUS) + (size_t)wave * (2 * VUS);
+    const bool computes = !UP || wave != 2;                          // (wave-uniform; UP: wave 2 takes ONE branch around everything it skips)
+    auto stage_first = [&]() {
+      park_items();
+      store_raw(raw0, c_begin, rh, cs_);
+      if (nck > 1) store_raw(raw1, c_begin + 1, rh2, cs_);
+      load_raw(c2, rh);
+      __syncthreads();
+    };
+    auto stage_chunk = [&](float* rcur, int i) {
+      if (i + 2 < nck && !(DBG & 32)) {
+        fetch_items();
+        store_raw(rcur, c_begin + i + 2, rh, cs_);
+        if (i + 3 < nck) load_raw(c_begin + i + 3, rh);
+      }
+    };
+    auto zero_acc = [&]() {
+#pragma unroll
+      for (int a = 0; a < NR; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    };
+    if (!computes) {
+      // UP, wave 2: its transform column is zero.  It keeps the barriers and its quarter of the staging
+      stage_first();
+      for (int i = 0; i < nck; ++i) {
+        __syncthreads();
+        stage_chunk((i & 1) ? raw1 : raw0, i);
+      }
+      zero_acc();                           // (defined on this path too: nothing is carried from tile to tile)
+    } else {
     load_us(c_begin, 0, 0);
     load_us(c_begin, 1, 1);
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-    park_items();
-    store_raw(raw0, c_begin, rh, cs_);
-    if (nck > 1) store_raw(raw1, c_begin + 1, rh2, cs_);
-    load_raw(c2, rh);
-    __syncthreads();
+    zero_acc();
+    stage_first();
     {                                       // operand (chunk 0, position 0)
       rd4(raw0, 0, 0, ta);
       tlo = comb(0, ta);
@@ -382,6 +415,31 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
     // (c, 2); one workgroup barrier per chunk behind group (c, 2): raw[c & 1] is consumed -> chunk c + 2 is staged into it, and chunk
     // c + 1's raw tile (staged a chunk ago) is visible to the reads of group (c, 3).  The last chunk builds an operand nobody uses and
     // re-fetches its own U (straight-line code, unconditional loads).
+    // UP: three groups per chunk (rows 0, 1, 3; group a on accumulator a and U slot a).  Same raw-tile schedule: the tile of chunk c is read from group
+    // (c - 1, 3) to group (c, 1), the barrier stands behind group (c, 1).
+    if constexpr (UP) {
+      for (int i = 0; i < nck; ++i) {
+        float* rcur = (i & 1) ? raw1 : raw0;
+        const float* rnext = (i & 1) ? raw0 : raw1;
+        const int cn = c_begin + (i + 1 < nck ? i + 1 : i);
+        group_pre(rcur, 1);
+        group_run(0, 0, rcur, 1);
+        load_us(c_begin + i, 3, 2);
+        group_post(1);
+        group_pre(rcur, 3);
+        group_run(1, 1, rcur, 3);
+        load_us(cn, 0, 0);
+        group_post(3);
+        __builtin_amdgcn_sched_barrier(0);
+        __syncthreads();
+        stage_chunk(rcur, i);
+        __builtin_amdgcn_sched_barrier(0);
+        group_pre(rnext, 0);
+        group_run(2, 2, rnext, 0);
+        load_us(cn, 1, 1);
+        group_post(0);
+      }
+    } else {
     for (int i = 0; i < nck; ++i) {
       float* rcur = (i & 1) ? raw1 : raw0;
       const float* rnext = (i & 1) ? raw0 : raw1;
@@ -401,17 +459,15 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
       group_post(3);
       __builtin_amdgcn_sched_barrier(0);
       if (!(DBG & 512)) __syncthreads();             // (DBG & 512, timing only: no barrier in the loop)
-      if (i + 2 < nck && !(DBG & 32)) {
-        fetch_items();
-        store_raw(rcur, c_begin + i + 2, rh, cs_);
-        if (i + 3 < nck) load_raw(c_begin + i + 3, rh);
-      }
+      stage_chunk(rcur, i);
       __builtin_amdgcn_sched_barrier(0);
       group_pre(rnext, 0);
       group_run(3, 1, rnext, 0);
       load_us(cn, 1, 1);
       group_post(0);
     }
+    }
+    }   // computes
 
     // ================================ epilogue ================================
     // rows folded in registers (A^T = [1 1 1 0; 0 1 -1 -1]):  R_p = sum_i A^T[p][i] M_ij, then Y[p][q] = sum_j R_p(j) A[j][q] through LDS in a
@@ -454,7 +510,7 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
     if (DBG & 8) {                 // ablation: no epilogue (one store per thread keeps the accumulators live)
       float s = 0.f;
 #pragma unroll
-      for (int a = 0; a < 4; ++a)
+      for (int a = 0; a < NR; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -488,9 +544,11 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
     for (int nblk = 0; nblk < 2; ++nblk) {
       const int n = e_cb * VBN + nblk * 32 + nq * 4;
       const bool nok = n < p.Cout;
-      {
-        const f32x16 r0 = (acc[0][nblk] + acc[1][nblk]) + acc[2][nblk];
-        const f32x16 r1 = (acc[1][nblk] - acc[2][nblk]) - acc[3][nblk];
+      if (computes) {
+        // (UP: row 2 is zero -- R_0 = M_0 + M_1, R_1 = M_1 - M_3, the remaining additions in the order they always had)
+        f32x16 r0 = acc[0][nblk] + acc[1][nblk], r1;
+        if constexpr (UP) r1 = acc[1][nblk] - acc[2][nblk];
+        else { r0 = r0 + acc[2][nblk]; r1 = (acc[1][nblk] - acc[2][nblk]) - acc[3][nblk]; }
         // D layout: reg r of lane l -> tile (r & 3) + 4 (l >> 5) of tile row r >> 2, channel l & 31
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -514,7 +572,10 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
           const int nn = nq * 4 + jj;
           const float* rb_ = exch + fp * VEPL + nn * VETS + (nn >> 4) * 4 + 4 * tq;
           auto rd = [&](int j) { return *reinterpret_cast<const f32x4*>(rb_ + (j * 2) * VEPL); };
-          if (fq == 0) { const f32x4 a0 = rd(0), a1 = rd(1), a2 = rd(2); y[jj] = (a0 + a1) - a2; }
+          if constexpr (UP) {                                        // wave 2's plane is zero and is not written: its term drops out
+            if (fq == 0) { const f32x4 a0 = rd(0), a1 = rd(1); y[jj] = a0 + a1; }
+            else { const f32x4 a1 = rd(1), a3 = rd(3); y[jj] = a1 - a3; }
+          } else if (fq == 0) { const f32x4 a0 = rd(0), a1 = rd(1), a2 = rd(2); y[jj] = (a0 + a1) - a2; }
           else { const f32x4 a1 = rd(1), a2 = rd(2), a3 = rd(3); y[jj] = (a1 + a2) - a3; }
         }
 #pragma unroll
@@ -602,12 +663,24 @@ int conv3x3_wino2_forward(const ConvParams& p, const WinoGeom& g, const float* u
     if (int rc = ensure_max_lds(reinterpret_cast<const void*>(k_conv3x3_wino2<D>), 100 * 1024, done)) return rc;      \
     hipLaunchKernelGGL((k_conv3x3_wino2<D>), grid, dim3(VNT), lds_bytes, st, p, g, reinterpret_cast<const __bf16*>(ufrag)); \
   }
+#define SR3_W2_LAUNCH_T(R, U)                                                                                         \
+  {                                                                                                                   \
+    static std::atomic<uint64_t> done{0};                                                                             \
+    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(k_conv3x3_wino2<0, R, U>), 100 * 1024, done)) return rc; \
+    hipLaunchKernelGGL((k_conv3x3_wino2<0, R, U>), grid, dim3(VNT), lds_bytes, st, p, g, reinterpret_cast<const __bf16*>(ufrag)); \
+  }
+  // an upsampled source: the nine-position UP instantiation, unless the caller asks for all sixteen (plan option wino_up = 0, ABI tiles
+  // 25 / 26) or an ablation build runs (those exist for the sixteen-position loop only)
+  const bool up = p.ups == 1 && !p.wino_full && dbg == 0;
   if (p.wino_split == 3) {
     if (dbg != 0) { set_error("conv: the ragged two-workgroup Winograd kernel has no ablation builds (SR3_WINO_DBG=%d)", dbg); return SR3_E_BADARG; }
-    static std::atomic<uint64_t> done{0};
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(k_conv3x3_wino2<0, true>), 100 * 1024, done)) return rc;
-    hipLaunchKernelGGL((k_conv3x3_wino2<0, true>), grid, dim3(VNT), lds_bytes, st, p, g, reinterpret_cast<const __bf16*>(ufrag));
+    if (up) SR3_W2_LAUNCH_T(true, true) else SR3_W2_LAUNCH_T(true, false)
     SR3_LAUNCH_CHECK("k_conv3x3_wino2 (ragged)");
+    return SR3_OK;
+  }
+  if (up) {
+    SR3_W2_LAUNCH_T(false, true)
+    SR3_LAUNCH_CHECK("k_conv3x3_wino2 (upsample)");
     return SR3_OK;
   }
   switch (dbg) {
@@ -629,6 +702,7 @@ int conv3x3_wino2_forward(const ConvParams& p, const WinoGeom& g, const float* u
     default: set_error("conv: SR3_WINO_DBG=%d is not built for the two-workgroup Winograd kernel", dbg); return SR3_E_BADARG;
   }
 #undef SR3_W2_LAUNCH
+#undef SR3_W2_LAUNCH_T
   SR3_LAUNCH_CHECK("k_conv3x3_wino2");
   return SR3_OK;
 }

@@ -314,6 +314,7 @@ struct ConvChoice {
   int wino_mode;                   // 0: the Winograd rule did not take the conv; 1 / 2: wino_mode above
   size_t wino_off;                 // the Op fields of these names
   bool has_wsplit; size_t wsplit_off;
+  int wino_full = 0;               // ConvParams::wino_full
 };
 // RULE_HEAD stops behind the first conv_pick, with neither the split_bf16 tile nor igemm_split: what Builder::fuses_res_conv has always asked
 enum ChoiceRule { RULE_FULL, RULE_HEAD };
@@ -341,6 +342,8 @@ static ConvChoice choose_conv(const sr3_plan* P, ConvParams c, size_t w, bool ha
   }
   conv_pick(c, ch.tile_cfg, ch.ksplit);
   ch.wino_split = c.wino_split;
+  // plan option wino_up = 0 (A/B knob): Upsample's conv keeps all sixteen positions on the two-workgroup kernel (reported as tile 25 / 26)
+  ch.wino_full = (ch.tile_cfg == 11 && c.wino_split >= 2 && c.ups == 1 && !P->wino_up) ? 1 : 0;
   if (!full) return ch;
   const bool presplit = c.igemm_split && P->wsplit_of.count(w);      // (a SPLIT conv whose pre-split weights the derived buffer holds)
   if (P->gemm_tile >= 1 && P->gemm_tile <= 4 && ch.tile_cfg >= 1 && ch.tile_cfg <= 4 && P->tile_cfg == 0) repick(P->gemm_tile);       // A/B knob: one im2col tile for every conv of that kernel
@@ -478,7 +481,7 @@ struct Builder {
     o.ss_rel = s.act ? cur_ss : 0;
     o.has_drop = train && s.drop_key >= 0; o.drop_key = (unsigned)(s.drop_key >= 0 ? s.drop_key : 0);
     const ConvChoice ch = choose_conv(P, c, s.w, has_q, o.has_drop, train);
-    o.tile_cfg = ch.tile_cfg; o.ksplit = ch.ksplit; c.wino_split = ch.wino_split; c.igemm_split = ch.igemm_split;
+    o.tile_cfg = ch.tile_cfg; o.ksplit = ch.ksplit; c.wino_split = ch.wino_split; c.wino_full = ch.wino_full; c.igemm_split = ch.igemm_split;
     o.wino_off = ch.wino_off; o.has_wsplit = ch.has_wsplit; o.wsplit_off = ch.wsplit_off;
     if (train) {
       Rec r;
@@ -981,7 +984,7 @@ int sr3_plan_op_info(sr3_plan* plan, int batch, int index, sr3_op_info* out) {
   out->kind = (int)o.kind * 10;
   if (o.kind == OP_CONV) {
     const ConvParams& c = o.cp;
-    out->tile_cfg = tile_encode(o.tile_cfg, c.wino_split, c.igemm_split, o.has_wsplit);
+    out->tile_cfg = tile_encode(o.tile_cfg, c.wino_split, c.igemm_split, o.has_wsplit, c.wino_full);
     out->ksplit = o.ksplit;
     out->ksize = c.ksize; out->stride = c.stride; out->upsample = c.ups;
     out->cin = c.C0 + c.C1; out->cout = c.Cout; out->h_out = c.Ho; out->w_out = c.Wo;
@@ -1039,6 +1042,7 @@ int sr3_plan_set_option(sr3_plan* plan, const char* key, int value) {
   else if (!strcmp(key, "gemm_tile")) slot = &plan->gemm_tile;
   else if (!strcmp(key, "wino2")) slot = &plan->wino2;
   else if (!strcmp(key, "wino_ragged")) slot = &plan->wino_ragged;
+  else if (!strcmp(key, "wino_up")) slot = &plan->wino_up;
   else if (!strcmp(key, "train_geom")) slot = &plan->train_geom;
   else if (!strcmp(key, "loss_l2")) { const int prev = plan->loss_l2; plan->loss_l2 = value; return prev; }   // no rebuild
   if (!slot) { set_error("unknown option %s", key); return SR3_E_BADARG; }

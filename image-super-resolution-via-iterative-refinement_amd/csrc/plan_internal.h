@@ -172,6 +172,8 @@ struct sr3_plan {
   int wino_ragged = 1;       // inference plans at a geometry other than image_size x image_size: 3x3 stride-1 convs on maps that are not whole
                              // multiples of the 8 x 16 tile on the two-workgroup kernel's RAGGED instantiation (tile_cfg 23) where the measured rule
                              // (wino_ragged_wins, plan.hip) says so; 0: they fall back to the general kernels (A/B knob)
+  int wino_up = 1;           // Upsample's conv (ups = 1) on the two-workgroup Winograd kernel: its UP instantiation, which skips the seven of the sixteen
+                             // positions whose operand is exactly zero on a nearest x2 map (same bits); 0: all sixteen (tile_cfg 25 / 26; A/B knob)
   int train_geom = 0;        // training follows the plan's geometry (sr3_plan_set_geometry) too: sr3_train_workspace_bytes / sr3_train_step build the
                              // training plan at plan_height x plan_width.  0: training is refused at any geometry but image_size x image_size.
                              // Off by default ONLY because tests pin that refusal text; at the native geometry both values build the same plan

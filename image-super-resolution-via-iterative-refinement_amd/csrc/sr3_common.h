@@ -197,6 +197,8 @@ struct ConvParams {
                         // ostat then holds ONE partial per image
   const void* w_split; // igemm_split: the weights pre-split into bf16 planes by igemm_split_weights (tile_cfg 18-21 at the ABI; a plan
                        // keeps them in its derived buffer); null: the kernel splits the weights while it stages them
+  int wino_full;       // wino_split 2 / 3 with ups == 1: 1 = all sixteen Winograd positions (tile_cfg 25 / 26 at the ABI; plan option wino_up = 0);
+                       // 0: the UP instantiation of conv3x3_wino2.hip, which skips the seven positions whose operand is exactly zero
 };
 
 __device__ __forceinline__ unsigned hash32(unsigned x) {

@@ -9,18 +9,21 @@ namespace sr3 {
 //   0-11 the kernel tile itself (0: conv_pick chooses; 1-4 im2col; 5-10 halo; 11 Winograd, fp32 MFMA)
 //   12, 13, 23: tile 11 with ConvParams::wino_split 1, 2, 3 (3 x bf16 split: 8-wave kernel; 8 x 16 tile of conv3x3_wino2.hip; its ragged form)
 //   14-17: im2col tiles 1-4 with ConvParams::igemm_split (3 x bf16 split); 18-21: ... with pre-split weights (ConvParams::w_split)
+//   25, 26: 13 / 23 with ConvParams::wino_full (the sixteen-position loop even where ups = 1 would select the nine-position one; same bits)
 //   22: the plain GEMM kernel of gemm1x1.hip (always split, always pre-split weights); 24: attention ops only (attention_long.hip), passes through
 // The only place in the library that knows the numbers; the one other copy is the TILE name table of tools/dump_plan.py.
-struct TileCode { int tile; int wino_split; int igemm_split; bool wpre; };
+struct TileCode { int tile; int wino_split; int igemm_split; bool wpre; int wino_full = 0; };
 inline TileCode tile_decode(int abi_tile) {
   if (abi_tile == 12 || abi_tile == 13) return {11, abi_tile - 11, 0, false};
   if (abi_tile == 23) return {11, 3, 0, false};
+  if (abi_tile == 25 || abi_tile == 26) return {11, abi_tile - 23, 0, false, 1};
   if (abi_tile >= 14 && abi_tile <= 17) return {abi_tile - 13, 0, 1, false};
   if (abi_tile >= 18 && abi_tile <= 21) return {abi_tile - 17, 0, 1, true};
   if (abi_tile == 22) return {22, 0, 1, true};
   return {abi_tile, 0, 0, false};
 }
-inline int tile_encode(int tile, int wino_split, int igemm_split, bool has_wsplit) {
+inline int tile_encode(int tile, int wino_split, int igemm_split, bool has_wsplit, int wino_full = 0) {
+  if (tile == 11 && wino_split >= 2 && wino_full) return 23 + wino_split;
   if (tile == 11 && wino_split) return wino_split == 3 ? 23 : 11 + wino_split;
   if (tile >= 1 && tile <= 4 && igemm_split) return (has_wsplit ? 17 : 13) + tile;
   return tile;

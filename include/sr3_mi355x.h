@@ -99,7 +99,7 @@ int sr3_plan_op_side(sr3_plan* plan, int batch, int index, int* side_id, int* wa
 /* algorithmic FLOPs (contractions only) of one forward for `batch` images */
 double sr3_plan_forward_flops(sr3_plan* plan, int batch);
 /* tuning knobs: key in {"fuse_stats", "fuse_res", "tile_cfg", "ksplit", "keep_all", "split_bf16", "winograd",
- * "wino_split", "wino_split8", "wino2", "wino_ragged", "gemm_split", "gemm2", "gemm_s2", "gemm_n64", "fork_side", "gemm_wpre", "gemm_tile", "fold_fuse", "wgrad_split", "attn_split",
+ * "wino_split", "wino_split8", "wino2", "wino_ragged", "wino_up", "gemm_split", "gemm2", "gemm_s2", "gemm_n64", "fork_side", "gemm_wpre", "gemm_tile", "fold_fuse", "wgrad_split", "attn_split",
  * "attn_long", "train_geom", "loss_l2"};
  * returns previous value.
  * wino_split (default 1): the Winograd convolutions that run on the kernel's one-image tile (maps >= 16x16) use its 3 x bf16
@@ -123,6 +123,11 @@ double sr3_plan_forward_flops(sr3_plan* plan, int batch);
  *   sr3_plan_set_geometry): 3x3 stride-1 convolutions on maps that are not whole multiples of the 8 x 16 tile run on the two-workgroup
  *   kernel's ragged instantiation (reported as tile 23: the tile grid is rounded up, the kernel masks the overhang) where the
  *   measured rule of DESIGN.md says the padded tile beats the fallback.  0: they land on the general kernels (A/B knob).
+ * wino_up (default 1): Upsample's convolution (nearest x2, then 3x3) on the two-workgroup kernel runs that kernel's upsample
+ *   instantiation: on a nearest x2 map, row 2 and column 2 of the Winograd input transform are exactly zero, so seven of the sixteen
+ *   positions are skipped -- their MFMAs, operand builds and filter fragments.  Same bits as the sixteen-position loop for finite
+ *   filters (a filter holding inf / NaN is the one input where 0 x inf would differ); still reported as tile 13 / 23.  0: all sixteen
+ *   positions (reported as tile 25 / 26; A/B knob).
  * gemm2 (default 1, round 6; needs gemm_split): 1x1 stride-1 convolutions with Cout % 128 == 0, channel counts % 32 == 0 and
  *   B * H * W % 64 == 0 (res_conv, attention qkv / out of the BASELINE networks) run as a plain GEMM on the same 3 x bf16 split
  *   arithmetic (gemm1x1.hip; reported as tile 22): 64 x 128 tile, weights pre-split in MFMA fragment order in the derived buffer
@@ -330,7 +335,9 @@ int sr3_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
  * four-wave workgroups per CU on an 8 x 16 pixel tile (conv3x3_wino2.hip; W >= 16 and a multiple of 16, H a multiple of 8, no
  * dropout form; what plan option wino2 -- default on -- selects on maps >= 16 wide), 23 = that kernel's ragged instantiation: any
  * map size (tile grid ceil(W / 16) x ceil(H / 8), the overhang masked; same arithmetic, same filters; on a map that is a whole
- * multiple of the tile the bits of 13; what plan option wino_ragged selects at a non-native geometry); tile_cfg 1-4 = the
+ * multiple of the tile the bits of 13; what plan option wino_ragged selects at a non-native geometry); with ups = 1, 13 and 23 run
+ * the nine Winograd positions whose operand is not identically zero on a nearest x2 map, and 25 / 26 = 13 / 23 with all sixteen
+ * positions (same bits; what plan option wino_up = 0 selects; without upsampling 25 / 26 are 13 / 23); tile_cfg 1-4 = the
  * im2col kernel's 128x128 / 128x64 / 64x64 / 64x128 tiles on the exact-fp32 MFMA, 14-17 = the same tiles on the 3 x bf16 split
  * instantiation with both operands split while they are staged (what plan option gemm_split selects: what a plan runs), 18-21 =
  * the same with the weights pre-split into bf16 planes in MFMA fragment order and read straight from global memory (plan option

@@ -22,7 +22,9 @@ TILE = {1: 'im2col 128x128', 2: 'im2col 128x64', 3: 'im2col 64x64', 4: 'im2col 6
         17: 'im2col 64x128 3 x bf16 split', 18: 'im2col 128x128 3 x bf16 split, pre-split weights',
         19: 'im2col 128x64 3 x bf16 split, pre-split weights', 20: 'im2col 64x64 3 x bf16 split, pre-split weights',
         21: 'im2col 64x128 3 x bf16 split, pre-split weights', 22: 'GEMM 64x128 / 64x64 3 x bf16 split (gemm1x1.hip)',
-        23: 'Winograd F(2x2,3x3) 3 x bf16 split (4 waves, ragged)', 24: 'attention, key-blocked (attention_long.hip)'}
+        23: 'Winograd F(2x2,3x3) 3 x bf16 split (4 waves, ragged)', 24: 'attention, key-blocked (attention_long.hip)',
+        25: 'Winograd F(2x2,3x3) 3 x bf16 split (4 waves), all 16 positions on an upsampled map',
+        26: 'Winograd F(2x2,3x3) 3 x bf16 split (4 waves, ragged), all 16 positions on an upsampled map'}
 # (names of the public tile_cfg numbers: the one copy outside the codec of csrc/tile_code.h)
 
 
