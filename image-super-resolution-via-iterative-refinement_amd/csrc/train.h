@@ -27,6 +27,10 @@ int l1_loss_grad(const float* z, const float* e, int B, int Cc, int HW, int CP, 
                  double* loss_part, float* loss_out, hipStream_t st);
 int adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, int step,
               hipStream_t st);
+// the same update with the weights' moving average in the same pass (ema_mode 0 none | 1 ema = p | 2 ema += (p - ema)(1 - ema_decay));
+// arguments are checked by the ABI entry (sr3_adam_ema_step)
+int adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float b1, float b2, float eps,
+                  int step, float ema_decay, int ema_mode, hipStream_t st);
 int nchw_to_nhwc_pad(const float* a, int Ca, const float* b, int Cb, int B, int HW, int CP, float* out, hipStream_t st);
 
 // Weight gradient of a conv (wgrad.hip): dw[n][tap][c] = sum_m dy[m][n] * a_tap[m][c], a = prologue(x0|x1)

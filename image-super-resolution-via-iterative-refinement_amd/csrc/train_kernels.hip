@@ -306,6 +306,18 @@ __global__ __launch_bounds__(64) void k_sum_parts(const double* __restrict__ par
 
 // T12: fused Adam over the whole parameter arena (torch.optim.Adam defaults, model/model.py:39-40):
 // m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
+// Four elements, shared by k_adam and k_adam_ema.  The fused multiply-adds are written out: left to the compiler, which of the
+// two products of `v b2 + w2 g g` is fused depends on the code around the expression, and the two kernels must give the same bits.
+__device__ __forceinline__ void adam_vec4(f32x4& pv, const f32x4& gv, f32x4& mv, f32x4& vv, float w1, float b2, float w2,
+                                          float eps, float step, float bc2_sqrt) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    mv[e] = fmaf(gv[e] - mv[e], w1, mv[e]);                   // torch: exp_avg.lerp_(grad, 1 - beta1)
+    vv[e] = fmaf(vv[e], b2, w2 * gv[e] * gv[e]);              //        exp_avg_sq.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+    const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
+    pv[e] = fmaf(-step, mv[e] / denom, pv[e]);
+  }
+}
 __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                float* __restrict__ v, size_t n4, float w1, float b2, float w2, float eps,
                                                float step, float bc2_sqrt) {
@@ -314,16 +326,37 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float
     const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
     f32x4 mv = *reinterpret_cast<f32x4*>(m + i * 4);
     f32x4 vv = *reinterpret_cast<f32x4*>(v + i * 4);
+    adam_vec4(pv, gv, mv, vv, w1, b2, w2, eps, step, bc2_sqrt);
+    *reinterpret_cast<f32x4*>(p + i * 4) = pv;
+    *reinterpret_cast<f32x4*>(m + i * 4) = mv;
+    *reinterpret_cast<f32x4*>(v + i * 4) = vv;
+  }
+}
+
+// T12b: the same pass with the exponential moving average of the weights as one more stream over the arena.
+// MODE 0: Adam alone (no access to ema); 1: ema = p_new (the copy before step_start_ema); 2: ema += (p_new - ema) * we,
+// we = 1 - ema_decay -- the lerp form of exp_avg above: p_new == ema leaves ema unchanged exactly.  No atomics.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_adam_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, float* __restrict__ ema, size_t n4, float w1,
+                                                   float b2, float w2, float eps, float step, float bc2_sqrt, float we) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
+    f32x4 mv = *reinterpret_cast<f32x4*>(m + i * 4);
+    f32x4 vv = *reinterpret_cast<f32x4*>(v + i * 4);
+    f32x4 ev = {0.f, 0.f, 0.f, 0.f};
+    if (MODE == 2) ev = *reinterpret_cast<f32x4*>(ema + i * 4);
+    adam_vec4(pv, gv, mv, vv, w1, b2, w2, eps, step, bc2_sqrt);
+    if (MODE == 2) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      mv[e] = mv[e] + (gv[e] - mv[e]) * w1;                     // torch: exp_avg.lerp_(grad, 1 - beta1)
-      vv[e] = vv[e] * b2 + w2 * gv[e] * gv[e];                  //        exp_avg_sq.mul_(beta2).addcmul_(g, g, value=1 - beta2)
-      const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
-      pv[e] = pv[e] - step * (mv[e] / denom);
+      for (int e = 0; e < 4; ++e) ev[e] = fmaf(pv[e] - ev[e], we, ev[e]);
     }
     *reinterpret_cast<f32x4*>(p + i * 4) = pv;
     *reinterpret_cast<f32x4*>(m + i * 4) = mv;
     *reinterpret_cast<f32x4*>(v + i * 4) = vv;
+    if (MODE == 1) *reinterpret_cast<f32x4*>(ema + i * 4) = pv;
+    if (MODE == 2) *reinterpret_cast<f32x4*>(ema + i * 4) = ev;
   }
 }
 
@@ -472,19 +505,38 @@ int l1_loss_grad(const float* z, const float* e, int B, int Cc, int HW, int CP, 
   SR3_LAUNCH_CHECK("k_sum_parts");
   return SR3_OK;
 }
-int adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, int step,
-              hipStream_t st) {
-  if (n & 3) { set_error("adam: n %% 4"); return SR3_E_BADARG; }
-  // torch.optim.Adam evaluates 1 - beta, the bias corrections and the step size as Python floats (double) and rounds
-  // each ONCE to fp32 when it meets the tensor (meant_double: the decimal behind the ABI's fp32 hyper-parameters).
+namespace {
+// torch.optim.Adam evaluates 1 - beta, the bias corrections and the step size as Python floats (double) and rounds
+// each ONCE to fp32 when it meets the tensor (meant_double: the decimal behind the ABI's fp32 hyper-parameters).
+struct AdamScalars { float w1, b2, w2, eps, step_size, bc2s; };
+AdamScalars adam_scalars(float lr, float b1, float b2, float eps, int step) {
   const double b1d = meant_double(b1), b2d = meant_double(b2), lrd = meant_double(lr);
   const double bc1 = 1.0 - pow(b1d, (double)step);
   const double bc2 = 1.0 - pow(b2d, (double)step);
-  const float step_size = (float)(lrd / bc1);
-  const float bc2s = (float)sqrt(bc2);
-  hipLaunchKernelGGL(k_adam, dim3(ew_blocks(n / 4)), dim3(256), 0, st, p, g, m, v, n / 4, (float)(1.0 - b1d), (float)b2d,
-                     (float)(1.0 - b2d), (float)meant_double(eps), step_size, bc2s);
+  return {(float)(1.0 - b1d), (float)b2d, (float)(1.0 - b2d), (float)meant_double(eps), (float)(lrd / bc1), (float)sqrt(bc2)};
+}
+}  // namespace
+int adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, int step,
+              hipStream_t st) {
+  if (n & 3) { set_error("adam: n %% 4"); return SR3_E_BADARG; }
+  const AdamScalars a = adam_scalars(lr, b1, b2, eps, step);
+  hipLaunchKernelGGL(k_adam, dim3(ew_blocks(n / 4)), dim3(256), 0, st, p, g, m, v, n / 4, a.w1, a.b2, a.w2, a.eps, a.step_size,
+                     a.bc2s);
   SR3_LAUNCH_CHECK("k_adam");
+  return SR3_OK;
+}
+int adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float b1, float b2, float eps,
+                  int step, float ema_decay, int ema_mode, hipStream_t st) {
+  const AdamScalars a = adam_scalars(lr, b1, b2, eps, step);
+  const float we = (float)(1.0 - meant_double(ema_decay));      // 1 - decay in double, rounded once (as 1 - beta1 is)
+  const dim3 grid(ew_blocks(n / 4)), block(256);
+#define SR3_ADAM_EMA(MODE) \
+  hipLaunchKernelGGL(k_adam_ema<MODE>, grid, block, 0, st, p, g, m, v, ema, n / 4, a.w1, a.b2, a.w2, a.eps, a.step_size, a.bc2s, we)
+  if (ema_mode == 0) SR3_ADAM_EMA(0);
+  else if (ema_mode == 1) SR3_ADAM_EMA(1);
+  else SR3_ADAM_EMA(2);
+#undef SR3_ADAM_EMA
+  SR3_LAUNCH_CHECK("k_adam_ema");
   return SR3_OK;
 }
 int nchw_to_nhwc_pad(const float* a, int Ca, const float* b, int Cb, int B, int HW, int CP, float* out, hipStream_t st) {

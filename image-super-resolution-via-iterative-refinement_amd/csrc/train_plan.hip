@@ -503,4 +503,20 @@ int sr3_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
   return adam_step(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, static_cast<hipStream_t>(stream));
 }
 
+int sr3_adam_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, size_t n, float lr,
+                      float beta1, float beta2, float eps, int step, float ema_decay, int ema_mode, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq) { set_error("sr3_adam_ema_step: params / grads / exp_avg / exp_avg_sq is NULL"); return SR3_E_BADARG; }
+  if (ema_mode < 0 || ema_mode > 2) { set_error("sr3_adam_ema_step: ema_mode %d is outside 0..2", ema_mode); return SR3_E_BADARG; }
+  if (!ema && ema_mode != 0) { set_error("sr3_adam_ema_step: ema is NULL with ema_mode %d", ema_mode); return SR3_E_BADARG; }
+  if (!(ema_decay >= 0.f && ema_decay < 1.f)) { set_error("sr3_adam_ema_step: ema_decay %g is outside [0, 1)", (double)ema_decay); return SR3_E_BADARG; }
+  if (n & 3) { set_error("sr3_adam_ema_step: n %zu is not a multiple of 4", n); return SR3_E_BADARG; }
+  if (step < 1) { set_error("sr3_adam_ema_step: step %d < 1", step); return SR3_E_BADARG; }
+  if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)ema) & 15) {
+    set_error("sr3_adam_ema_step: misaligned pointer (16-byte vectors)");
+    return SR3_E_ALIGN;
+  }
+  return adam_ema_step(params, grads, exp_avg, exp_avg_sq, ema, n, lr, beta1, beta2, eps, step, ema_decay, ema_mode,
+                       static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -5,6 +5,7 @@ begin_step, begin_epoch, optG, log_dict, SR, data, schedule_phase; feed_data, op
 test, sample, set_loss, set_new_noise_schedule, get_current_log, get_current_visuals,
 print_network, save_network, load_network -- so sr.py / infer.py / sample.py run unchanged.
 """
+import contextlib
 import logging
 import os
 from collections import OrderedDict
@@ -28,6 +29,11 @@ class DDPM(BaseModel):
         self.data = None
         self.set_loss()
         self.set_new_noise_schedule(opt['model']['beta_schedule']['train'], schedule_phase='train')
+        # EMA of the weights: the reference's configs carry train.ema_scheduler {step_start_ema, update_ema_every, ema_decay} and never
+        # use it; here the engine key `enabled` (default false) switches it on.  Without it nothing below allocates, writes or reads anything
+        train_opt = opt.get('train') or {}
+        ema_opt = train_opt.get('ema_scheduler') or {}
+        self.ema_opt = dict(ema_opt) if ema_opt.get('enabled') else None
         if self.opt['phase'] == 'train':
             self.netG.train()
             if opt['model']['finetune_norm']:
@@ -39,7 +45,10 @@ class DDPM(BaseModel):
                     raise ValueError('optimizer got an empty parameter list')
                 raise NotImplementedError('finetune_norm over %d "transformer" parameters' % len(names))
             from sr3_hip.optim import make_optimizer
-            self.optG = make_optimizer(self.netG, lr=opt['train']['optimizer']['lr'])
+            if self.ema_opt is not None:
+                self.netG.denoise_fn.enable_ema()         # starts as the initial weights; load_network replaces it on a resume
+            self.optG = make_optimizer(self.netG, lr=opt['train']['optimizer']['lr'],
+                                       warmup_steps=int(opt['train']['optimizer'].get('warmup_steps') or 0), ema=self.ema_opt)
             self.log_dict = OrderedDict()
         self.load_network()
         # data parallel: equalise the replicas once (each process initialised its own weights; a resumed checkpoint is
@@ -64,9 +73,17 @@ class DDPM(BaseModel):
         self.optG.step()
         self.log_dict['l_pix'] = l_pix.item()
 
+    def _sampling_weights(self):
+        """Train phase with EMA enabled: validation and sampling run on the EMA weights (everything below netG's sampling loops,
+        the ValWave / SampleWave paths included, reads the arena this selects); training goes on with the live ones."""
+        un = self.netG.denoise_fn
+        if self.opt['phase'] == 'train' and self.ema_opt is not None and un.ema_arena is not None:
+            return un.use_weights('ema')
+        return contextlib.nullcontext()
+
     def test(self, continous=False):
         self.netG.eval()
-        with torch.no_grad():
+        with torch.no_grad(), self._sampling_weights():
             wave = self.data.get('_dp_wave') if isinstance(self.data, dict) else None
             if wave is not None:
                 # the validation loader groups consecutive items into waves (sr3_hip.dist.ValWave): the chains of a wave run once,
@@ -78,7 +95,7 @@ class DDPM(BaseModel):
 
     def sample(self, batch_size=1, continous=False):
         self.netG.eval()
-        with torch.no_grad():
+        with torch.no_grad(), self._sampling_weights():
             if _dist.dp_active():
                 if self._sam_wave is None:
                     self._sam_wave = _dist.SampleWave()
@@ -124,12 +141,21 @@ class DDPM(BaseModel):
     def _ckpt_paths(self, stem):
         return '{}_gen.pth'.format(stem), '{}_opt.pth'.format(stem)
 
+    @staticmethod
+    def _ema_path(stem):
+        return '{}_ema.pth'.format(stem)
+
     def save_network(self, epoch, iter_step):
         stem = os.path.join(self.opt['path']['checkpoint'], 'I{}_E{}'.format(iter_step, epoch))
         gen_path, opt_path = self._ckpt_paths(stem)
         if _dist.is_primary():          # replicas are identical: one writer
             state = OrderedDict((k, v.cpu()) for k, v in self.netG.state_dict().items())
             torch.save(state, gen_path)
+            if self.opt['phase'] == 'train' and self.ema_opt is not None:
+                # the key set, shapes and dtypes of *_gen.pth (schedule buffers included) with the EMA weights in the UNet's
+                # entries: renamed to *_gen.pth it loads anywhere a generator checkpoint does
+                state.update((k, v.cpu()) for k, v in self.netG.denoise_fn.ema_state_dict('denoise_fn.').items())
+                torch.save(state, self._ema_path(stem))
             torch.save({'epoch': epoch, 'iter': iter_step, 'scheduler': None,
                         'optimizer': self.optG.state_dict()}, opt_path)
             logger.info('Saved model in [{:s}] ...'.format(gen_path))
@@ -141,8 +167,21 @@ class DDPM(BaseModel):
             return
         logger.info('Loading pretrained model for G [{:s}] ...'.format(stem))
         gen_path, opt_path = self._ckpt_paths(stem)
-        self.netG.load_state_dict(torch.load(gen_path, map_location='cpu'),
-                                  strict=(not self.opt['model']['finetune_norm']))
+        ema_path = self._ema_path(stem)
+        strict = not self.opt['model']['finetune_norm']
+        if self.opt['phase'] != 'train' and self.ema_opt is not None:
+            # validation / inference with EMA enabled: the model's weights ARE the EMA weights
+            if not os.path.exists(ema_path):
+                raise FileNotFoundError('train.ema_scheduler.enabled is set but [{:s}] does not exist'.format(ema_path))
+            gen_path = ema_path
+        self.netG.load_state_dict(torch.load(gen_path, map_location='cpu'), strict=strict)
+        if self.opt['phase'] == 'train' and self.ema_opt is not None:
+            un = self.netG.denoise_fn
+            if os.path.exists(ema_path):
+                un.load_ema_state_dict(torch.load(ema_path, map_location='cpu'), prefix='denoise_fn.', strict=strict)
+            else:
+                logger.warning('EMA weights [{:s}] not found: the EMA starts from the loaded weights'.format(ema_path))
+                un.ema_from_weights()
         if self.opt['phase'] == 'train':
             ck = torch.load(opt_path, map_location='cpu')
             self.optG.load_state_dict(ck['optimizer'])

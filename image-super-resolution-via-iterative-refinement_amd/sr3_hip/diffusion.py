@@ -170,13 +170,13 @@ class EngineDiffusion(nn.Module):
 
     # ---- the reverse loop ------------------------------------------------------------------------
     def _loop_state(self, shape, cond_shape, dev, item_streams=False):
-        # a captured graph bakes in the arena, the freq table and the workspace pointer and the plan's launch list:
-        # key on all of them (plan.generation changes with every set_option); the workspace is private to the state.
+        # a captured graph bakes in the arena (the one in use: EngineUNet.use_weights), the freq table and the workspace pointer and
+        # the plan's launch list: key on all of them (plan.generation changes with every set_option); the workspace is private to the state.
         # item_streams: one torch generator per image of the batch (`item_seeds` of p_sample_loop) -- the generators are
         # registered with the captured graph, so they belong to the state and are re-seeded per loop
         un = self.denoise_fn
         key = (tuple(shape), None if cond_shape is None else tuple(cond_shape), str(dev), self.num_timesteps,
-               un.arena.data_ptr(), un.freq.data_ptr(), un.plan.generation, bool(item_streams))
+               un.weights().data_ptr(), un.freq.data_ptr(), un.plan.generation, bool(item_streams))
         st = self._loop_cache.get(key)
         if st is None:
             st = dict(img=torch.empty(shape, device=dev), z=torch.empty(shape, device=dev),
@@ -186,9 +186,11 @@ class EngineDiffusion(nn.Module):
                       gens=[torch.Generator(device=dev) for _ in range(shape[0])] if item_streams else None)
             # keep the states of a few image sizes alive (a folder of mixed sizes alternates between them without recapturing);
             # what was built for another arena / schedule / set of plan options can never be hit again: dropped
-            ctx = key[2:6]
+            # (with EMA weights the model has two arenas, and a state built on either can be hit again)
+            arenas = {un.arena.data_ptr()} | ({un.ema_arena.data_ptr()} if un.ema_arena is not None else set())
             live = set(un.plan._geometry_generation.values())
-            kept = [(k, v) for k, v in self._loop_cache.items() if k[2:6] == ctx and k[6] in live]
+            kept = [(k, v) for k, v in self._loop_cache.items()
+                    if k[2:4] == key[2:4] and k[4] in arenas and k[5] == key[5] and k[6] in live]
             self._loop_cache = dict(kept[-(self.max_cached_loops - 1):] if self.max_cached_loops > 1 else [])
             self._loop_cache[key] = st
         else:

@@ -141,6 +141,8 @@ def sync_replicas(unet, src=0):
         raise RuntimeError('sync_replicas: move the model to its GPU first')
     tdist.broadcast(arena, src)
     tdist.broadcast(unet.freq, src)
+    if getattr(unet, 'ema_arena', None) is not None:      # EMA weights: equal on every rank from here on without any per-step
+        tdist.broadcast(unet.ema_arena, src)              # communication (a deterministic function of identical parameters)
     unet.weights_changed()
 
 

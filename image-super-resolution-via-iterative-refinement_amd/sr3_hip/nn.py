@@ -5,6 +5,7 @@
 arguments, same `forward(x, time)`, same state-dict keys and shapes -- but it owns one packed
 parameter arena and every FLOP runs in libsr3_mi355x.so.
 """
+import contextlib
 import math
 from collections import OrderedDict
 
@@ -45,6 +46,11 @@ class EngineUNet(nn.Module):
         self._derived = None
         self._derived_key = None
         self._weights_epoch = 0
+        # exponential moving average of the weights (config train.ema_scheduler.enabled): a second arena-shaped tensor, allocated by
+        # enable_ema() only.  Neither a parameter nor a buffer: it is in no state dict and no parameter count; it has its own export
+        # (ema_state_dict).  Its address never changes (captured reverse loops bake it in); `use_weights` selects which arena runs
+        self.ema_arena = None
+        self._use_ema = False
         self.reset_parameters()
 
     # ---- initialisation: same distributions AND same RNG consumption order as the reference ----
@@ -95,6 +101,42 @@ class EngineUNet(nn.Module):
     def init_orthogonal(self):
         self.init_scheme('orthogonal')
 
+    # ---- the two sets of weights ---------------------------------------------------------------------
+    def enable_ema(self):
+        """Allocate the EMA arena (once) as a copy of the weights; +4 bytes per parameter of device memory."""
+        if self.ema_arena is None:
+            self.ema_arena = self.arena.data.clone()
+        return self.ema_arena
+
+    def ema_from_weights(self):
+        """ema <- weights, in place (the EMA's start value: the weights the model starts from)."""
+        self.enable_ema().copy_(self.arena.data)
+
+    def weights(self):
+        """The arena forward / reverse_step read: the live parameters, or the EMA inside `use_weights('ema')`."""
+        return self.ema_arena if self._use_ema else self.arena.data
+
+    @contextlib.contextmanager
+    def use_weights(self, which):
+        """Run forward / reverse_step (and everything built on them: the sampling loops) on 'ema' or 'live' weights.  The derived
+        filters follow through ensure_derived, which re-prepares them from the arena in use; training always reads and writes the
+        live arena and refuses to run inside an 'ema' selection."""
+        if which not in ('ema', 'live'):
+            raise ValueError("use_weights: 'ema' or 'live' (got %r)" % (which,))
+        if which == 'ema' and self.ema_arena is None:
+            raise L.Sr3Error('use_weights(\'ema\'): this model keeps no EMA weights (config train.ema_scheduler.enabled)')
+        prev, self._use_ema = self._use_ema, which == 'ema'
+        try:
+            yield self
+        finally:
+            self._use_ema = prev
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        if self.ema_arena is not None:         # (a plain attribute: nn.Module moves parameters and buffers only)
+            self.ema_arena = fn(self.ema_arena)
+        return self
+
     # ---- derived weights ---------------------------------------------------------------------------
     def weights_changed(self):
         """Engine-side writes to the arena through raw pointers (fused Adam) are invisible to torch's version counter:
@@ -104,10 +146,10 @@ class EngineUNet(nn.Module):
         L.check(self.plan.lib.sr3_plan_invalidate_derived(self.plan.handle))
 
     def ensure_derived(self):
-        """(Re)build the Winograd filters if the parameters moved or changed since the last build.  Views handed out by
-        named_parameters()/state-dict loading share the arena's version counter, so in-place edits through them are
-        seen; a no-op (one tuple compare) otherwise."""
-        arena = self.arena
+        """(Re)build the Winograd filters if the parameters moved or changed since the last build, or the other set of weights
+        (`use_weights`) was selected.  Views handed out by named_parameters()/state-dict loading share the arena's version
+        counter, so in-place edits through them are seen; a no-op (one tuple compare) otherwise."""
+        arena = self.weights()
         if not arena.is_cuda:
             return
         key = (arena.data_ptr(), arena._version, self._weights_epoch, self.plan.options_epoch)
@@ -135,11 +177,31 @@ class EngineUNet(nn.Module):
         for _, p in self.named_parameters():
             yield p
 
-    def _save_to_state_dict(self, destination, prefix, keep_vars):
+    def _export(self, arena, destination, prefix):
         if self.variant == 'ddpm':
             destination[prefix + 'time_mlp.0.inv_freq'] = self.freq.detach().clone()
         for e in self.plan.table:
-            destination[prefix + e['name']] = self.plan.view(self.arena.detach(), e).detach().clone().contiguous()
+            destination[prefix + e['name']] = self.plan.view(arena, e).detach().clone().contiguous()
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        self._export(self.arena.detach(), destination, prefix)
+
+    def ema_state_dict(self, prefix=''):
+        """The EMA weights under the keys, shapes and layouts (OIHW) of state_dict()."""
+        if self.ema_arena is None:
+            raise L.Sr3Error('ema_state_dict: this model keeps no EMA weights (config train.ema_scheduler.enabled)')
+        destination = OrderedDict()
+        self._export(self.ema_arena, destination, prefix)
+        return destination
+
+    def load_ema_state_dict(self, state_dict, prefix='', strict=True):
+        """Fill the EMA arena from a state dict of that form (keys outside `prefix` -- the schedule buffers of a `*_ema.pth`
+        -- are not this module's); the frequency table belongs to the live model and is not touched."""
+        missing, unexpected, errors = [], [], []
+        self._import(self.enable_ema(), state_dict, prefix, strict, missing, unexpected, errors, load_freq=False)
+        if errors or (strict and (missing or unexpected)):
+            raise RuntimeError('EMA weights: %s' % '; '.join(errors + ['missing %s' % k for k in missing]
+                                                            + ['unexpected %s' % k for k in unexpected]))
 
     def state_dict(self, *args, destination=None, prefix='', keep_vars=False):
         # reference key order: buffers of a submodule come after its parameters; rebuild in table order
@@ -150,6 +212,9 @@ class EngineUNet(nn.Module):
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
                               error_msgs):
+        self._import(self.arena.detach(), state_dict, prefix, strict, missing_keys, unexpected_keys, error_msgs)
+
+    def _import(self, arena, state_dict, prefix, strict, missing_keys, unexpected_keys, error_msgs, load_freq=True):
         known = set()
         for e in self.plan.table:
             key = prefix + e['name']
@@ -162,12 +227,13 @@ class EngineUNet(nn.Module):
                 error_msgs.append('size mismatch for %s: checkpoint %s vs model %s'
                                   % (key, tuple(src.shape), tuple(e['shape'])))
                 continue
-            self.plan.view(self.arena.detach(), e).copy_(src.to(self.arena.device, torch.float32))
+            self.plan.view(arena, e).copy_(src.to(arena.device, torch.float32))
         fkey = prefix + 'time_mlp.0.inv_freq'
         if self.variant == 'ddpm':
             known.add(fkey)
             if fkey in state_dict:
-                self.freq.copy_(state_dict[fkey].to(self.freq.device, torch.float32))
+                if load_freq:
+                    self.freq.copy_(state_dict[fkey].to(self.freq.device, torch.float32))
             else:
                 missing_keys.append(fkey)
         if strict:
@@ -189,14 +255,14 @@ class EngineUNet(nn.Module):
                 kw['noise_level'] = time
             else:
                 kw['timestep'] = time
-        return E.unet_forward(self.plan, self.arena.data, self.freq, self._ws if ws is None else ws, x, cond=cond,
+        return E.unet_forward(self.plan, self.weights(), self.freq, self._ws if ws is None else ws, x, cond=cond,
                               level_table=level_table, step_dev=step_dev, out=out, **kw)
 
     def reverse_step(self, x, z, tables, step2, *, cond=None, level_table=None, clip_denoised=True, eps_out=None, ws=None):
         """One whole iteration of the reverse loop in place on `x` (engine.reverse_step): what `GaussianDiffusion.p_sample_loop`
         captures into its hipGraph."""
         self.ensure_derived()
-        return E.reverse_step(self.plan, self.arena.data, self.freq, self._ws if ws is None else ws, x, z, tables, step2,
+        return E.reverse_step(self.plan, self.weights(), self.freq, self._ws if ws is None else ws, x, z, tables, step2,
                               cond=cond, level_table=level_table, clip_denoised=clip_denoised, eps_out=eps_out)
 
     # ---- training step (forward + backward inside the engine) ------------------------------------
@@ -236,6 +302,8 @@ class EngineUNet(nn.Module):
         dev = hr.device
         if dev.type != 'cuda':
             raise L.Sr3Error('training needs the model on a GPU; there is no CPU fallback')
+        if self._use_ema:
+            raise L.Sr3Error("training inside use_weights('ema'): the training step reads and updates the live weights")
         self.ensure_derived()          # the train plan's block1 / Upsample convs run on the Winograd kernel
         B = hr.shape[0]
         plan = self.plan

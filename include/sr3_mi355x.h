@@ -322,6 +322,26 @@ int sr3_train_step(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw,
 int sr3_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, float lr,
                   float beta1, float beta2, float eps, int step, void* stream);
 
+/* The same Adam step with the exponential moving average (EMA) of the weights updated in the same pass over the arena
+ * (config train.ema_scheduler; the SR3 paper samples from EMA weights).  params / exp_avg / exp_avg_sq come out
+ * bit-identical to sr3_adam_step on the same inputs in every mode (the per-element code is shared); no atomics.
+ *   ema       : arena-shaped fp32 buffer, in / out; may be NULL with ema_mode 0
+ *   ema_mode  : 0  no EMA work, ema is not touched;
+ *               1  ema = p_new, an exact copy (the steps before step_start_ema);
+ *               2  ema = ema + (p_new - ema) * w,  w = 1 - ema_decay evaluated in double from the decimal the fp32
+ *                  argument stands for and rounded once to fp32 (as 1 - beta1 is); p_new == ema leaves ema unchanged
+ *                  exactly.  An fp32 EMA drops an update smaller than half an ulp of ema (at decay 0.9999: a weight
+ *                  that moved by less than ~6e-4 relative since the EMA last followed it).
+ *   ema_decay : in [0, 1); read in mode 2 only, checked in every mode
+ * SR3_E_BADARG (nothing is launched, the message names the argument): a NULL params / grads / exp_avg / exp_avg_sq,
+ * NULL ema with ema_mode != 0, ema_mode outside 0..2, ema_decay outside [0, 1), n % 4 != 0, step < 1.  SR3_E_ALIGN: a
+ * pointer that is not 16-byte aligned.  As with sr3_adam_step the caller invalidates the derived filters afterwards
+ * (sr3_plan_invalidate_derived); filters prepared from `params` say nothing about `ema` and vice versa: a forward on
+ * the EMA weights prepares them from the EMA arena (the stale-filter check (c) above compares the pointers). */
+int sr3_adam_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, size_t n,
+                      float lr, float beta1, float beta2, float eps, int step, float ema_decay, int ema_mode,
+                      void* stream);
+
 /* ---- per-op entry points (unit tests, micro-benchmarks) ------------------------------------ */
 
 /* Block / Conv2d / Downsample / Upsample / res_conv / qkv / out as one implicit-GEMM call:
