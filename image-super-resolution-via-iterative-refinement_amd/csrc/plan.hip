@@ -91,29 +91,29 @@ static int build_structure(sr3_plan* P) {
   P->out_ch = out_ch;
 
   // ---- pass 1: topology (same walk as UNet.__init__) ----
-  struct Proto { int kind; int cin, cout, skip; bool attn; };
+  struct Proto { LayerKind kind; int cin, cout, skip; bool attn; };
   std::vector<Proto> pd, pm, pu;
   std::vector<int> feat;
   int pre = inner, now_res = d.image_size;
   feat.push_back(pre);
-  pd.push_back({0, d.in_channel, inner, 0, false});
+  pd.push_back({L_CONV_IN, d.in_channel, inner, 0, false});
   for (int ind = 0; ind < d.n_mults; ++ind) {
     const bool is_last = ind == d.n_mults - 1;
     const bool use_attn = in_list(d.attn_res, d.n_attn_res, now_res);
     const int cm = inner * d.channel_mults[ind];
     for (int r = 0; r < d.res_blocks; ++r) {
-      pd.push_back({1, pre, cm, 0, use_attn});
+      pd.push_back({L_RES, pre, cm, 0, use_attn});
       feat.push_back(cm);
       pre = cm;
     }
     if (!is_last) {
-      pd.push_back({2, pre, pre, 0, false});
+      pd.push_back({L_DOWN, pre, pre, 0, false});
       feat.push_back(pre);
       now_res /= 2;
     }
   }
-  pm.push_back({1, pre, pre, 0, true});
-  pm.push_back({1, pre, pre, 0, false});
+  pm.push_back({L_RES, pre, pre, 0, true});
+  pm.push_back({L_RES, pre, pre, 0, false});
   for (int ind = d.n_mults - 1; ind >= 0; --ind) {
     const bool is_last = ind < 1;
     const bool use_attn = in_list(d.attn_res, d.n_attn_res, now_res);
@@ -121,11 +121,11 @@ static int build_structure(sr3_plan* P) {
     for (int r = 0; r < d.res_blocks + 1; ++r) {
       const int skip = feat.back();
       feat.pop_back();
-      pu.push_back({1, pre + skip, cm, skip, use_attn});
+      pu.push_back({L_RES, pre + skip, cm, skip, use_attn});
       pre = cm;
     }
     if (!is_last) {
-      pu.push_back({3, pre, pre, 0, false});
+      pu.push_back({L_UP, pre, pre, 0, false});
       now_res *= 2;
     }
   }
@@ -134,7 +134,7 @@ static int build_structure(sr3_plan* P) {
   // ---- pass 2: arena.  FiLM projections first (contiguous => one GEMV for all blocks) ----
   size_t cur = 0;
   int F = 0;
-  auto count_f = [&](const std::vector<Proto>& v) { for (auto& p : v) if (p.kind == 1) F += p.cout; };
+  auto count_f = [&](const std::vector<Proto>& v) { for (auto& p : v) if (p.kind == L_RES) F += p.cout; };
   count_f(pd); count_f(pm); count_f(pu);
   P->F = F;
   P->film_w = cur; cur += (size_t)F * inner;
@@ -160,10 +160,10 @@ static int build_structure(sr3_plan* P) {
       L.name = nm;
       L.w = L.b = 0;
       std::string n = nm;
-      if (pr.kind == 0) {
+      if (pr.kind == L_CONV_IN) {
         L.w = add_conv(P, n + ".weight", pr.cout, pr.cin, 3, &cur);
         L.b = add_vec(P, n + ".bias", pr.cout, &cur);
-      } else if (pr.kind == 2 || pr.kind == 3) {
+      } else if (pr.kind == L_DOWN || pr.kind == L_UP) {
         L.w = add_conv(P, n + ".conv.weight", pr.cout, pr.cin, 3, &cur);
         L.b = add_vec(P, n + ".conv.bias", pr.cout, &cur);
       } else {
@@ -230,7 +230,7 @@ static int build_structure(sr3_plan* P) {
   bool ok = chk(P->fin_cin);
   for (auto* v : {&P->downs, &P->mid, &P->ups})
     for (auto& L : *v)
-      if (L.kind == 1) ok = ok && chk(L.res.cin) && chk(L.res.cout);
+      if (L.kind == L_RES) ok = ok && chk(L.res.cin) && chk(L.res.cout);
   if (!ok) { set_error("a GroupNorm channel count is not divisible by norm_groups=%d", d.norm_groups); return SR3_E_BADARG; }
   return SR3_OK;
 }
@@ -295,8 +295,8 @@ bool wino_ragged_wins(const ConvParams& c) {
 // train_geom -- the training forward's convs without dropout: a map the rule
 // above refuses on the two-workgroup kernel -- its plain form where the map is a whole multiple of the 8 x 16 tile, its RAGGED form
 // (plan option wino_ragged) where wino_ragged_wins says the padded tile beats the fallback
-static int wino_mode(const sr3_plan* P, const ConvParams& c, size_t w, bool has_x2, bool has_drop, bool train, WinoGeom* wg) {
-  if (!P->winograd || P->tile_cfg != 0 || P->split_bf16 || has_x2) return 0;
+static int wino_mode(const sr3_plan* P, const ConvParams& c, size_t w, bool has_q, bool has_drop, bool train, WinoGeom* wg) {
+  if (!P->winograd || P->tile_cfg != 0 || P->split_bf16 || has_q) return 0;
   if (has_drop && (c.C1 != 0 || c.ups != 0 || c.act == 0)) return 0;    // the dropout form: single source, no upsampling
   if (c.ksize != 3 || c.stride != 1 || !P->derived_of.count(w)) return 0;
   if (wino_geometry(c, wg)) return 1;
@@ -307,25 +307,18 @@ static int wino_mode(const sr3_plan* P, const ConvParams& c, size_t w, bool has_
   return wino_geometry(r, wg) ? 2 : 0;
 }
 
-// The kernel one conv of a plan runs on: THE place where the planner decides it (Builder::conv only emits what this returns).
-struct ConvChoice {
-  int tile_cfg, ksplit;            // what conv_forward is called with
-  int wino_split, igemm_split;     // the ConvParams fields of these names
-  int wino_mode;                   // 0: the Winograd rule did not take the conv; 1 / 2: wino_mode above
-  size_t wino_off;                 // the Op fields of these names
-  bool has_wsplit; size_t wsplit_off;
-  int wino_full = 0;               // ConvParams::wino_full
-};
-// RULE_HEAD stops behind the first conv_pick, with neither the split_bf16 tile nor igemm_split: what Builder::fuses_res_conv has always asked
+// The kernel one conv of a plan runs on (ConvChoice, plan_internal.h): THE place where the planner decides it (Builder::conv only emits what
+// this returns).  RULE_HEAD stops behind the first conv_pick, with neither the split_bf16 tile nor igemm_split: what Builder::fuses_res_conv
+// has always asked
 enum ChoiceRule { RULE_FULL, RULE_HEAD };
-static ConvChoice choose_conv(const sr3_plan* P, ConvParams c, size_t w, bool has_x2, bool has_drop, bool train, ChoiceRule rule = RULE_FULL) {
+static ConvChoice choose_conv(const sr3_plan* P, ConvParams c, size_t w, bool has_q, bool has_drop, bool train, ChoiceRule rule = RULE_FULL) {
   ConvChoice ch = {P->tile_cfg, P->ksplit, 0, 0, 0, 0, false, 0};
   const bool full = rule == RULE_FULL;
   auto repick = [&](int tile) { ch.tile_cfg = tile; ch.ksplit = P->ksplit; conv_pick(c, ch.tile_cfg, ch.ksplit); };
   // opt-in: the 3 x bf16 split MFMA instantiation of the 8-wave tile wherever it fits (inference plans only)
   HaloGeom sg; WinoGeom wg;
   if (full && P->split_bf16 && !train && ch.tile_cfg == 0 && c.ksize == 3 && c.stride == 1 && c.Cout > 64 && halo_geometry(c, 10, &sg)) ch.tile_cfg = 10;
-  ch.wino_mode = wino_mode(P, c, w, has_x2, has_drop, train, &wg);
+  ch.wino_mode = wino_mode(P, c, w, has_q, has_drop, train, &wg);
   if (ch.wino_mode) {
     ch.tile_cfg = 11;
     ch.wino_off = P->derived_of.at(w);
@@ -409,12 +402,12 @@ struct Builder {
     if (t.stats_done) return;
     stat_slot(h, chan_stats_slices(B, t.H * t.W, t.C));
     Op o; o.kind = OP_STATS;
-    o.a = t.off; o.b = t.stat_off; o.i0 = t.H * t.W; o.i1 = t.C;
+    o.stats = {t.off, t.stat_off, t.H * t.W, t.C};
     ops.push_back(o);
     last_stats_op = (int)ops.size() - 1; last_stats_h = h;
   }
   int last_conv_op = -1, last_conv_out = -1, last_stats_op = -1, last_stats_h = -1;
-  // plan option fold_fuse: can the kernel that completes `fresh` (one of x0 / x1) also do this fold?  Fills the op's FoldTail fields.
+  // plan option fold_fuse: can the kernel that completes `fresh` (one of x0 / x1) also do this fold?  Fills the op's `tail`.
   bool fuse_fold_into(Op& L, int fresh, int x0, int x1, size_t gamma, size_t beta, size_t ss_rel, size_t mr_rel, bool has_mr) {
     const int other = fresh == x0 ? x1 : x0;
     const int Cf = T[x0].C + (x1 >= 0 ? T[x1].C : 0);
@@ -422,10 +415,10 @@ struct Builder {
     if (!fold_tail_fits(T[fresh].C, Cf, c_off, P->d.norm_groups)) return false;
     if (other >= 0 && !T[other].stats_done) return false;
     L.fold_fused = true;
-    L.f_Ctot = Cf; L.f_coff = c_off;
-    L.f_has_o = other >= 0;
-    if (other >= 0) { L.f_ostat = T[other].stat_off; L.f_oC = T[other].C; L.f_oT = T[other].stat_T; L.f_ooff = fresh == x0 ? T[x0].C : 0; }
-    L.f_gamma = gamma; L.f_beta = beta; L.f_ss_rel = ss_rel; L.f_mr_rel = mr_rel; L.f_has_mr = has_mr;
+    FoldSpec& f = L.tail;
+    f.Ctot = Cf; f.c_off = c_off;
+    if (other >= 0) { f.ostat = T[other].stat_off; f.oC = T[other].C; f.oT = T[other].stat_T; f.o_off = fresh == x0 ? T[x0].C : 0; }
+    f.gamma = gamma; f.beta = beta; f.ss_rel = ss_rel; f.mr_rel = mr_rel; f.has_mr = has_mr;
     T[fresh].stat_T = 1;              // the fused kernel holds whole-image sums: one partial per image
     return true;
   }
@@ -442,7 +435,7 @@ struct Builder {
     if (P->fold_fuse && !ops.empty()) {
       // (a) the op just emitted is a split-K conv whose reduce writes the statistics of x0 / x1: its reduce folds too
       Op& L = ops.back();
-      if (last_conv_op == (int)ops.size() - 1 && L.kind == OP_CONV && L.ksplit > 1 && L.has_ostat && (last_conv_out == x0 || last_conv_out == x1) &&
+      if (last_conv_op == (int)ops.size() - 1 && L.kind == OP_CONV && L.conv.ch.ksplit > 1 && L.conv.ostat != NO_OFF && (last_conv_out == x0 || last_conv_out == x1) &&
           fuse_fold_into(L, last_conv_out, x0, x1, gamma, beta, ss_rel, mr_rel, train)) return;
     }
     ensure_stats(x0);
@@ -451,38 +444,37 @@ struct Builder {
     if (P->fold_fuse && !ops.empty() && last_stats_op == (int)ops.size() - 1 && (last_stats_h == x0 || last_stats_h == x1) &&
         fuse_fold_into(ops.back(), last_stats_h, x0, x1, gamma, beta, ss_rel, mr_rel, train)) return;
     Op o; o.kind = OP_FOLD;
-    o.a = T[x0].stat_off; o.i0 = T[x0].C; o.i3 = T[x0].stat_T;
-    o.has_st1 = x1 >= 0;
-    if (x1 >= 0) { o.b = T[x1].stat_off; o.i1 = T[x1].C; o.i4 = T[x1].stat_T; }
-    o.i2 = T[x0].H * T[x0].W;
-    o.p0 = gamma; o.p1 = beta;
-    o.ss_rel = ss_rel; o.mr_rel = mr_rel; o.has_mr = train;
+    Op::Fold& f = o.fold;
+    f.stat0 = T[x0].stat_off; f.C0 = T[x0].C; f.T0 = T[x0].stat_T;
+    if (x1 >= 0) { f.stat1 = T[x1].stat_off; f.C1 = T[x1].C; f.T1 = T[x1].stat_T; }
+    f.pixels = T[x0].H * T[x0].W;
+    f.gamma = gamma; f.beta = beta; f.has_mr = train;
+    o.ss_rel = ss_rel; o.mr_rel = mr_rel;
     ops.push_back(o);
   }
   // generic conv over the virtual concat (x0|x1); residual is the concat view (r0|r1).  Emission only: choose_conv picks the kernel
   int conv(const ConvSpec& s) {
-    const int x0 = s.x0, x1 = s.x1, Cout = s.Cout, ksize = s.ksize;
-    const bool has_bias = s.bias != NO_PARAM, has_q = s.q0 >= 0;
-    const size_t bias = has_bias ? s.bias : 0;
-    const int C0 = T[x0].C, C1 = x1 >= 0 ? T[x1].C : 0;
+    const int x0 = s.x0, x1 = s.x1, Cout = s.Cout;
+    const bool has_q = s.q0 >= 0;
+    auto off = [&](int h) { return h >= 0 ? T[h].off : NO_OFF; };
     Op o; o.kind = OP_CONV;
-    ConvParams& c = o.cp;
-    c = conv_shape(B, T[x0].H, T[x0].W, s.ups, s.stride, ksize, C0, C1, Cout);
+    Op::Conv& v = o.conv;
+    ConvParams& c = v.cp;
+    c = conv_shape(B, T[x0].H, T[x0].W, s.ups, s.stride, s.ksize, T[x0].C, x1 >= 0 ? T[x1].C : 0, Cout);
     const int Ho = c.Ho, Wo = c.Wo;
     const int out = make(Cout, Ho, Wo);
     c.act = s.act; c.film_stride = P->F;
     c.RC0 = s.r0 >= 0 ? T[s.r0].C : 0; c.RC1 = s.r1 >= 0 ? T[s.r1].C : 0;
-    o.a = T[x0].off; o.has_src1 = x1 >= 0; if (x1 >= 0) o.b = T[x1].off;
-    o.p0 = s.w; o.has_bias = has_bias; o.p1 = bias;
-    o.has_film = s.film_row >= 0; o.i0 = s.film_row;
-    o.has_res = s.r0 >= 0; if (s.r0 >= 0) o.c = T[s.r0].off;
-    o.has_res1 = s.r1 >= 0; if (s.r1 >= 0) o.d = T[s.r1].off;
-    o.e = T[out].off;
+    v.src0 = T[x0].off; v.src1 = off(x1);
+    v.w = s.w; v.bias = s.bias;
+    v.film_row = s.film_row;
+    v.res0 = off(s.r0); v.res1 = off(s.r1);
+    v.out = T[out].off;
     o.ss_rel = s.act ? cur_ss : 0;
-    o.has_drop = train && s.drop_key >= 0; o.drop_key = (unsigned)(s.drop_key >= 0 ? s.drop_key : 0);
-    const ConvChoice ch = choose_conv(P, c, s.w, has_q, o.has_drop, train);
-    o.tile_cfg = ch.tile_cfg; o.ksplit = ch.ksplit; c.wino_split = ch.wino_split; c.wino_full = ch.wino_full; c.igemm_split = ch.igemm_split;
-    o.wino_off = ch.wino_off; o.has_wsplit = ch.has_wsplit; o.wsplit_off = ch.wsplit_off;
+    v.has_drop = train && s.drop_key >= 0; v.drop_key = (unsigned)(s.drop_key >= 0 ? s.drop_key : 0);
+    v.ch = choose_conv(P, c, s.w, has_q, v.has_drop, train);
+    const ConvChoice& ch = v.ch;
+    c.wino_split = ch.wino_split; c.wino_full = ch.wino_full; c.igemm_split = ch.igemm_split;
     if (train) {
       Rec r;
       r.kind = R_CONV; r.s = s; r.out = out;
@@ -491,33 +483,26 @@ struct Builder {
     }
     if (has_q) {   // fused 1x1 segment (res_conv); caller checked fuses_res_conv()
       c.x2_C0 = T[s.q0].C; c.x2_C1 = s.q1 >= 0 ? T[s.q1].C : 0;
-      o.has_x2 = true; o.g = T[s.q0].off; o.has_x21 = s.q1 >= 0; if (s.q1 >= 0) o.h = T[s.q1].off;
-      o.p2 = s.qw; o.p3 = s.qb;
-      flops += 2.0 * B * Ho * Wo * (double)Cout * (double)(c.x2_C0 + c.x2_C1);
+      v.x2_src0 = T[s.q0].off; v.x2_src1 = off(s.q1);
+      v.x2_w = s.qw; v.x2_bias = s.qb;
     }
-    if (o.ksplit > 1) max_scratch = std::max(max_scratch, (size_t)o.ksplit * B * Ho * Wo * Cout * sizeof(float));
+    if (ch.ksplit > 1) max_scratch = std::max(max_scratch, (size_t)ch.ksplit * B * Ho * Wo * Cout * sizeof(float));
     // split-K convs leave the statistics to the (cheap, small-tensor) stand-alone pass
-    if (s.want_stats && P->fuse_stats && o.ksplit == 1 && o.tile_cfg == 11) {
+    auto writes_stats = [&](int parts) { stat_slot(out, parts); v.ostat = T[out].stat_off; };
+    if (s.want_stats && P->fuse_stats && ch.ksplit == 1 && ch.tile_cfg == 11) {
       WinoGeom wg = {};      // (stays empty -- no slices -- where plan option tile_cfg forces tile 11 on a conv it does not fit)
       wino_geometry(c, &wg);
-      stat_slot(out, wino_stats_slices(wg));
-      o.has_ostat = true; o.f = T[out].stat_off;
-    } else if (s.want_stats && P->fuse_stats && o.ksplit == 1 && o.tile_cfg >= 5) {
+      writes_stats(wino_stats_slices(wg));
+    } else if (s.want_stats && P->fuse_stats && ch.ksplit == 1 && ch.tile_cfg >= 5) {
       HaloGeom hg;
-      if (halo_geometry(c, o.tile_cfg, &hg)) {
-        stat_slot(out, halo_stats_slices(hg));
-        o.has_ostat = true; o.f = T[out].stat_off;
-      }
-    } else if (s.want_stats && P->fuse_stats && o.ksplit > 1) {
+      if (halo_geometry(c, ch.tile_cfg, &hg)) writes_stats(halo_stats_slices(hg));
+    } else if (s.want_stats && P->fuse_stats && ch.ksplit > 1) {
       const int rpb = splitk_rows_per_block(c, true);      // statistics come out of the split-K reduce
-      if (rpb > 0) {
-        stat_slot(out, (Ho * Wo) / rpb);
-        o.has_ostat = true; o.f = T[out].stat_off;
-      }
+      if (rpb > 0) writes_stats((Ho * Wo) / rpb);
     }
     ops.push_back(o);
     last_conv_op = (int)ops.size() - 1; last_conv_out = out;
-    flops += 2.0 * B * Ho * Wo * (double)Cout * (double)(C0 + C1) * ksize * ksize;
+    flops += conv_flops(c);
     return out;
   }
   // Does block2's conv of this block -- on a map the size of tensor `at` -- take res_conv as a second K-segment?  Only the unsplit halo kernel:
@@ -542,7 +527,7 @@ struct Builder {
     int r_side = -1, r_id = -1;
     if (R.has_rc && P->fork_side && !train && !fuses_res_conv(x0, R)) {
       r_side = conv(res_conv);
-      if (ops.back().kind == OP_CONV && ops.back().ksplit == 1) { r_id = n_side++; ops.back().side_id = r_id; }
+      if (ops.back().kind == OP_CONV && ops.back().conv.ch.ksplit == 1) { r_id = n_side++; ops.back().side_id = r_id; }
     }
     const int h1 = conv({.x0 = x0, .x1 = x1, .Cout = R.cout, .act = 2, .w = R.c1_w, .bias = R.c1_b, .film_row = R.film_off, .want_stats = true});
     fold(h1, -1, R.gn2_w, R.gn2_b);
@@ -571,18 +556,19 @@ struct Builder {
       const int qkv = conv({.x0 = out, .Cout = 3 * R.cout, .ksize = 1, .act = 1, .w = R.qkv_w});
       const int o = make(R.cout, T[out].H, T[out].W);
       Op a; a.kind = OP_ATTN;
-      a.a = T[qkv].off; a.b = T[o].off; a.i0 = T[out].H * T[out].W; a.i1 = R.cout;
+      const int tokens = T[out].H * T[out].W;
+      a.attn = {T[qkv].off, T[o].off, tokens, R.cout, 0};
       const bool geo = !train || P->train_geom;       // (a training plan off the native geometry exists under train_geom only)
-      if (geo && P->attn_long && !attention_fits(a.i0, R.cout)) a.tile_cfg = 24;       // the key-blocked kernel: any token count
-      else if (geo && refused.empty() && !attention_fits(a.i0, R.cout)) {
+      if (geo && P->attn_long && !attention_fits(tokens, R.cout)) a.attn.tile_cfg = 24;       // the key-blocked kernel: any token count
+      else if (geo && refused.empty() && !attention_fits(tokens, R.cout)) {
         char msg[256];
         snprintf(msg, sizeof(msg), "attention of %s: the %d x %d level has %d tokens, more than the attention kernel holds in LDS", R.name.c_str(),
-                 T[out].H, T[out].W, a.i0);
+                 T[out].H, T[out].W, tokens);
         refused = msg;
       }
       ops.push_back(a);
       if (train) { Rec r; r.kind = R_ATTN; r.qkv = qkv; r.o = o; P->recs.push_back(r); }
-      flops += 4.0 * B * (double)a.i0 * (double)a.i0 * R.cout;
+      flops += attn_flops(B, tokens, R.cout);
       drop(qkv);
       const int out2 = conv({.x0 = o, .Cout = R.cout, .ksize = 1, .w = R.ao_w, .bias = R.ao_b, .r0 = out, .want_stats = true});
       drop(o);
@@ -611,19 +597,20 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
   std::vector<int> feats;
   int cur = -1;
   for (auto& L : P->downs) {
-    if (L.kind == 0) {
+    if (L.kind == L_CONV_IN) {
       cur = bld.make(L.cout, IH, IW);
       Op o; o.kind = OP_CONV_IN;
-      o.e = bld.T[cur].off; o.p0 = L.w; o.p1 = L.b;
-      o.i0 = d.in_channel - cond_channels; o.i1 = cond_channels; o.i2 = L.cout; o.i3 = IH; o.i4 = IW;
+      Op::ConvIn& v = o.conv_in;
+      v.x_channels = d.in_channel - cond_channels; v.cond_channels = cond_channels; v.Cout = L.cout; v.H = IH; v.W = IW;
+      v.w = L.w; v.bias = L.b; v.out = bld.T[cur].off;
       if (const int slices = P->fuse_stats ? conv_in_stat_slices(d.in_channel, IH, IW, L.cout) : 0) {
         bld.stat_slot(cur, slices);          // the MFMA form writes the GroupNorm partials of its output itself
-        o.has_ostat = true; o.f = bld.T[cur].stat_off;
+        v.ostat = bld.T[cur].stat_off;
       }
       ops.push_back(o);
       if (bld.train) { Rec r; r.kind = R_CONV_IN; r.out = cur; r.s.w = L.w; r.s.bias = L.b; P->recs.push_back(r); }
       bld.flops += 2.0 * B * IH * IW * (double)L.cout * L.cin * 9;
-    } else if (L.kind == 1) {
+    } else if (L.kind == L_RES) {
       cur = bld.res_block(cur, -1, L.res);   // the input stays alive: it is a skip feature
     } else {
       cur = bld.conv({.x0 = cur, .Cout = L.cout, .stride = 2, .w = L.w, .bias = L.b, .want_stats = true});
@@ -642,7 +629,7 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
   }
   for (auto& L : P->ups) {
     int nxt;
-    if (L.kind == 1) {
+    if (L.kind == L_RES) {
       const int skip = feats.back();
       feats.pop_back();
       nxt = bld.res_block(cur, skip, L.res);
@@ -658,7 +645,7 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
   bld.fold(cur, -1, P->fin_gn_w, P->fin_gn_b);
   {
     Op o; o.kind = OP_CONV_OUT;
-    o.a = bld.T[cur].off; o.p0 = P->fin_w; o.p1 = P->fin_b; o.i0 = bld.T[cur].C; o.i1 = P->out_ch; o.i2 = IH; o.i3 = IW;
+    o.conv_out = {bld.T[cur].off, P->fin_w, P->fin_b, bld.T[cur].C, P->out_ch, IH, IW};
     o.ss_rel = bld.cur_ss;
     ops.push_back(o);
     if (bld.train) {
@@ -685,8 +672,8 @@ void layout_derived(sr3_plan* P) {
   };
   for (auto* v : {&P->downs, &P->mid, &P->ups})
     for (auto& L : *v) {
-      if (L.kind == 1) { reg(L.res.c1_w, L.res.cout, L.res.cin); reg(L.res.c2_w, L.res.cout, L.res.cout); }
-      else if (L.kind == 3) reg(L.w, L.cout, L.cin);
+      if (L.kind == L_RES) { reg(L.res.c1_w, L.res.cout, L.res.cin); reg(L.res.c2_w, L.res.cout, L.res.cout); }
+      else if (L.kind == L_UP) reg(L.w, L.cout, L.cin);
     }
   // the im2col SPLIT tiles' weights, pre-split (plan option gemm_split): res_conv and the attention projections (1x1), Downsample
   // (3x3 stride 2; Cout <= 64 stays on the fp32 MFMA: choose_conv)
@@ -702,10 +689,10 @@ void layout_derived(sr3_plan* P) {
     };
     for (auto* v : {&P->downs, &P->mid, &P->ups})
       for (auto& L : *v) {
-        if (L.kind == 1) {
+        if (L.kind == L_RES) {
           if (L.res.has_rc) regw(L.res.rc_w, L.res.cout, 1, L.res.cin);
           if (L.res.attn) { regw(L.res.qkv_w, 3 * L.res.cout, 1, L.res.cout); regw(L.res.ao_w, L.res.cout, 1, L.res.cout); }
-        } else if (L.kind == 2 && (L.cout > 64 || (P->gemm2 && P->gemm_s2 && P->gemm_n64 && L.cout == 64))) {
+        } else if (L.kind == L_DOWN && (L.cout > 64 || (P->gemm2 && P->gemm_s2 && P->gemm_n64 && L.cout == 64))) {
           regw(L.w, L.cout, 9, L.cin);
         }
       }
@@ -737,18 +724,19 @@ static int build_forward(sr3_plan* P, int B, int cond_channels) {
     // ... and the embedding MLP + FiLM projections (first op, reads only the noise level): beside the input conv, joined by the first conv that
     // adds a FiLM row
     for (Op& o : P->ops)
-      if (o.kind == OP_CONV && o.has_film) {
+      if (o.kind == OP_CONV && o.conv.film_row >= 0) {
         if (o.wait_id < 0) { o.wait_id = bld.n_side; P->ops[0].side_id = bld.n_side++; }
         break;
       }
   }
   // ---- fixed regions after the activation arena (high-water mark) ----
   size_t off = (bld.act.high + 255) & ~(size_t)255;
-  P->stats_off = off; P->stats_bytes = bld.stats_cursor; off += (bld.stats_cursor + 255) & ~(size_t)255;
-  P->ss_off = off; off += ((size_t)B * std::max(bld.max_cin, 4) * 2 * sizeof(float) + 255) & ~(size_t)255;
-  P->temb_off = off; off += ((size_t)B * inner * sizeof(float) + 255) & ~(size_t)255;
-  P->film_off = off; off += ((size_t)B * P->F * sizeof(float) + 255) & ~(size_t)255;
-  P->scratch_off = off; P->scratch_bytes = bld.max_scratch; off += (bld.max_scratch + 255) & ~(size_t)255;
+  Regions& R = P->regions;           // (no mean / rstd tables in inference: mr_off stays 0, no op has_mr)
+  R.stats_off = off; off += (bld.stats_cursor + 255) & ~(size_t)255;
+  R.ss_off = off; off += ((size_t)B * std::max(bld.max_cin, 4) * 2 * sizeof(float) + 255) & ~(size_t)255;
+  R.temb_off = off; off += ((size_t)B * inner * sizeof(float) + 255) & ~(size_t)255;
+  R.film_off = off; off += ((size_t)B * P->F * sizeof(float) + 255) & ~(size_t)255;
+  R.scratch_off = off; R.scratch_bytes = bld.max_scratch; off += (bld.max_scratch + 255) & ~(size_t)255;
   P->ws_bytes = off;
   P->flops = bld.flops;
   P->built_batch = B;
@@ -760,36 +748,35 @@ static int build_forward(sr3_plan* P, int B, int cond_channels) {
 // ---------------------------------------------------------------------------------------------
 // forward driver
 // ---------------------------------------------------------------------------------------------
-Regions infer_regions(const sr3_plan* P) {
-  Regions r;
-  r.ops = &P->ops; r.stats_off = P->stats_off; r.ss_off = P->ss_off; r.mr_off = 0; r.temb_off = P->temb_off;
-  r.film_off = P->film_off; r.scratch_off = P->scratch_off; r.scratch_bytes = P->scratch_bytes;
-  return r;
-}
+// pointer into the workspace / the arena for an optional offset (NO_OFF: null)
+template <typename T> static T* bind(char* base, size_t off) { return off == NO_OFF ? nullptr : reinterpret_cast<T*>(base + off); }
+static const float* bind(const float* params, size_t off) { return off == NO_OFF ? nullptr : params + off; }
 
-static FoldTail make_fold_tail(const Op& o, int groups, const float* params, char* ws, const Regions& R) {
+static FoldTail make_fold_tail(const FoldSpec& s, int groups, const float* params, char* ws, const Regions& R) {
   FoldTail f;
   memset(&f, 0, sizeof(f));
-  f.groups = groups; f.Ctot = o.f_Ctot; f.c_off = o.f_coff;
-  if (o.f_has_o) { f.ostat = reinterpret_cast<const double*>(ws + R.stats_off + o.f_ostat); f.oC = o.f_oC; f.oT = o.f_oT; f.o_off = o.f_ooff; }
-  f.gamma = params + o.f_gamma; f.beta = params + o.f_beta; f.eps = 1e-5f;
-  f.ss = reinterpret_cast<float*>(ws + R.ss_off + o.f_ss_rel);
-  f.mr = o.f_has_mr ? reinterpret_cast<float*>(ws + R.mr_off + o.f_mr_rel) : nullptr;
+  f.groups = groups; f.Ctot = s.Ctot; f.c_off = s.c_off;
+  f.ostat = bind<const double>(ws + R.stats_off, s.ostat); f.oC = s.oC; f.oT = s.oT; f.o_off = s.o_off;
+  f.gamma = params + s.gamma; f.beta = params + s.beta; f.eps = 1e-5f;
+  f.ss = reinterpret_cast<float*>(ws + R.ss_off + s.ss_rel);
+  f.mr = s.has_mr ? reinterpret_cast<float*>(ws + R.mr_off + s.mr_rel) : nullptr;
   return f;
 }
 
-int run_forward(sr3_plan* P, const Regions& R, const float* x, const float* cond, int cond_channels, const float* level,
+int run_forward(sr3_plan* P, bool train, const float* x, const float* cond, int cond_channels, const float* level,
                 const int64_t* tstep, const float* freq, const float* level_table, const int* step_dev,
                 const float* params, char* ws, float* eps_out, int B, hipStream_t st,
                 hipEvent_t* ev, hipEvent_t* mid, const DropCfg* drop, const StepFuse* fuse) {
   const sr3_unet_desc& d = P->d;
+  const Regions& R = train ? P->t_regions : P->regions;
   size_t op_index = 0;
   float* film = reinterpret_cast<float*>(ws + R.film_off);
+  char* const stats = ws + R.stats_off;
   // plan option fork_side: ops marked side_id run on the plan's side stream between a fork event (recorded on the caller's stream where the
   // op sits in the list) and a join event their consumer (wait_id) waits for; under per-op timing (ev) everything stays on one stream
-  const bool forking = !ev && R.ops == &P->ops;
+  const bool forking = !ev && !train;
   hipStream_t const main_st = st;
-  for (const Op& o : *R.ops) {
+  for (const Op& o : train ? P->tops : P->ops) {
     int rc = SR3_OK;
     st = main_st;
     if (ev) SR3_HIP(hipEventRecord(ev[op_index], st));
@@ -825,53 +812,56 @@ int run_forward(sr3_plan* P, const Regions& R, const float* x, const float* cond
       }
       case OP_CONV_IN: {
         // virtual concat order is [cond | x] (diffusion.py:157); unconditional: x only
+        const Op::ConvIn& v = o.conv_in;
         const float* a = cond_channels > 0 ? cond : x;
-        const int Ca = cond_channels > 0 ? cond_channels : o.i0;
+        const int Ca = cond_channels > 0 ? cond_channels : v.x_channels;
         const float* b = cond_channels > 0 ? x : nullptr;
-        const int Cb = cond_channels > 0 ? o.i0 : 0;
-        rc = conv_in_nchw(a, Ca, b, Cb, B, o.i3, o.i4, params + o.p0, params + o.p1, o.i2,
-                          reinterpret_cast<float*>(ws + o.e),
-                          o.has_ostat ? reinterpret_cast<double*>(ws + R.stats_off + o.f) : nullptr, st);
+        const int Cb = cond_channels > 0 ? v.x_channels : 0;
+        rc = conv_in_nchw(a, Ca, b, Cb, B, v.H, v.W, params + v.w, params + v.bias, v.Cout, bind<float>(ws, v.out),
+                          bind<double>(stats, v.ostat), st);
         break;
       }
-      case OP_STATS:
+      case OP_STATS: {
+        const Op::Stats& v = o.stats;
         if (o.fold_fused) {
-          FoldTail ft = make_fold_tail(o, d.norm_groups, params, ws, R);
-          rc = chan_stats_fold(reinterpret_cast<const float*>(ws + o.a), B, o.i0, o.i1, reinterpret_cast<double*>(ws + R.stats_off + o.b), ft, st);
+          FoldTail ft = make_fold_tail(o.tail, d.norm_groups, params, ws, R);
+          rc = chan_stats_fold(bind<const float>(ws, v.src), B, v.pixels, v.channels, bind<double>(stats, v.stat), ft, st);
           break;
         }
-        rc = chan_stats(reinterpret_cast<const float*>(ws + o.a), B, o.i0, o.i1,
-                        reinterpret_cast<double*>(ws + R.stats_off + o.b), st);
+        rc = chan_stats(bind<const float>(ws, v.src), B, v.pixels, v.channels, bind<double>(stats, v.stat), st);
         break;
-      case OP_FOLD:
-        rc = gn_finalize(reinterpret_cast<const double*>(ws + R.stats_off + o.a), o.i0, o.i3,
-                         o.has_st1 ? reinterpret_cast<const double*>(ws + R.stats_off + o.b) : nullptr,
-                         o.has_st1 ? o.i1 : 0, o.has_st1 ? o.i4 : 0, B, o.i2, d.norm_groups, params + o.p0,
-                         params + o.p1, 1e-5f, reinterpret_cast<float*>(ws + R.ss_off + o.ss_rel), st,
-                         o.has_mr ? reinterpret_cast<float*>(ws + R.mr_off + o.mr_rel) : nullptr);
+      }
+      case OP_FOLD: {
+        const Op::Fold& v = o.fold;
+        rc = gn_finalize(bind<const double>(stats, v.stat0), v.C0, v.T0, bind<const double>(stats, v.stat1), v.C1, v.T1, B, v.pixels,
+                         d.norm_groups, params + v.gamma, params + v.beta, 1e-5f, bind<float>(ws, R.ss_off + o.ss_rel), st,
+                         v.has_mr ? bind<float>(ws, R.mr_off + o.mr_rel) : nullptr);
         break;
+      }
       case OP_CONV: {
-        ConvParams c = o.cp;
-        c.src0 = reinterpret_cast<const float*>(ws + o.a);
-        c.src1 = o.has_src1 ? reinterpret_cast<const float*>(ws + o.b) : nullptr;
-        c.w = params + o.p0;
-        c.bias = o.has_bias ? params + o.p1 : nullptr;
-        c.ss = c.act ? reinterpret_cast<const float*>(ws + R.ss_off + o.ss_rel) : nullptr;
-        c.film = o.has_film ? film + o.i0 : nullptr;
-        c.res0 = o.has_res ? reinterpret_cast<const float*>(ws + o.c) : nullptr;
-        c.res1 = o.has_res1 ? reinterpret_cast<const float*>(ws + o.d) : nullptr;
-        c.out = reinterpret_cast<float*>(ws + o.e);
-        c.ostat = o.has_ostat ? reinterpret_cast<double*>(ws + R.stats_off + o.f) : nullptr;
-        if (drop && o.has_drop && drop->thresh != 0) {
-          c.drop_seed = drop_layer_seed(drop->seed, o.drop_key); c.drop_thresh = drop->thresh; c.drop_scale = drop->scale;
+        const Op::Conv& v = o.conv;
+        const ConvChoice& ch = v.ch;
+        ConvParams c = v.cp;
+        c.src0 = bind<const float>(ws, v.src0);
+        c.src1 = bind<const float>(ws, v.src1);
+        c.w = params + v.w;
+        c.bias = bind(params, v.bias);
+        c.ss = c.act ? bind<const float>(ws, R.ss_off + o.ss_rel) : nullptr;
+        c.film = v.film_row >= 0 ? film + v.film_row : nullptr;
+        c.res0 = bind<const float>(ws, v.res0);
+        c.res1 = bind<const float>(ws, v.res1);
+        c.out = bind<float>(ws, v.out);
+        c.ostat = bind<double>(stats, v.ostat);
+        if (drop && v.has_drop && drop->thresh != 0) {
+          c.drop_seed = drop_layer_seed(drop->seed, v.drop_key); c.drop_thresh = drop->thresh; c.drop_scale = drop->scale;
         }
-        if (o.has_x2) {
-          c.x2_src0 = reinterpret_cast<const float*>(ws + o.g);
-          c.x2_src1 = o.has_x21 ? reinterpret_cast<const float*>(ws + o.h) : nullptr;
-          c.x2_w = params + o.p2;
-          c.x2_bias = params + o.p3;
+        if (v.x2_src0 != NO_OFF) {
+          c.x2_src0 = bind<const float>(ws, v.x2_src0);
+          c.x2_src1 = bind<const float>(ws, v.x2_src1);
+          c.x2_w = params + v.x2_w;
+          c.x2_bias = params + v.x2_bias;
         }
-        if (o.tile_cfg == 11) {
+        if (ch.tile_cfg == 11) {
           if (!P->derived_ptr) { set_error("the plan's derived (Winograd) weights are not bound: call sr3_plan_bind_derived + sr3_plan_prepare_derived"); return SR3_E_BADARG; }
           // stale filters must fail loudly, not compute with the previous weights: the buffer has to have been prepared from
           // THIS arena, under the current options, and not invalidated since (sr3_plan_invalidate_derived after an optimizer step)
@@ -879,29 +869,33 @@ int run_forward(sr3_plan* P, const Regions& R, const float* x, const float* cond
             set_error("the plan's derived (Winograd) weights are stale or were prepared from another arena: call sr3_plan_prepare_derived");
             return SR3_E_BADARG;
           }
-          c.wino_u = P->derived_ptr + o.wino_off;
+          c.wino_u = P->derived_ptr + ch.wino_off;
         }
-        if (o.has_wsplit && ((o.tile_cfg >= 1 && o.tile_cfg <= 4) || o.tile_cfg == 22) && c.igemm_split) {
+        if (ch.has_wsplit && ((ch.tile_cfg >= 1 && ch.tile_cfg <= 4) || ch.tile_cfg == 22) && c.igemm_split) {
           if (!P->derived_ptr || P->derived_from != params) {
             set_error("the plan's derived (pre-split 1x1 / stride-2) weights are not bound or stale: call sr3_plan_bind_derived + sr3_plan_prepare_derived");
             return SR3_E_BADARG;
           }
-          c.w_split = P->derived_ptr + o.wsplit_off;
+          c.w_split = P->derived_ptr + ch.wsplit_off;
         }
-        if (mid && o.ksplit > 1) conv_set_mid_event(mid[op_index - 1]);
+        if (mid && ch.ksplit > 1) conv_set_mid_event(mid[op_index - 1]);
         FoldTail ft;
-        if (o.fold_fused) { ft = make_fold_tail(o, d.norm_groups, params, ws, R); c.fold = &ft; }
-        rc = conv_forward(c, o.tile_cfg, o.ksplit, reinterpret_cast<float*>(ws + R.scratch_off), R.scratch_bytes, st);
+        if (o.fold_fused) { ft = make_fold_tail(o.tail, d.norm_groups, params, ws, R); c.fold = &ft; }
+        rc = conv_forward(c, ch.tile_cfg, ch.ksplit, bind<float>(ws, R.scratch_off), R.scratch_bytes, st);
         break;
       }
-      case OP_ATTN:
-        rc = attention_forward(reinterpret_cast<const float*>(ws + o.a), B, o.i0, o.i1,
-                               reinterpret_cast<float*>(ws + o.b), st, (P->attn_split ? 1 : 0) | (o.tile_cfg == 24 ? 2 : 0));
+      case OP_ATTN: {
+        const Op::Attn& v = o.attn;
+        rc = attention_forward(bind<const float>(ws, v.qkv), B, v.tokens, v.channels, bind<float>(ws, v.out), st,
+                               (P->attn_split ? 1 : 0) | (v.tile_cfg == 24 ? 2 : 0));
         break;
-      case OP_CONV_OUT:
-        rc = conv_out_nchw(reinterpret_cast<const float*>(ws + o.a), reinterpret_cast<const float*>(ws + R.ss_off + o.ss_rel),
-                           B, o.i2, o.i3, o.i0, params + o.p0, params + o.p1, o.i1, eps_out, st, fuse);
+      }
+      case OP_CONV_OUT: {
+        const Op::ConvOut& v = o.conv_out;
+        rc = conv_out_nchw(bind<const float>(ws, v.src), bind<const float>(ws, R.ss_off + o.ss_rel), B, v.H, v.W, v.channels,
+                           params + v.w, params + v.bias, v.out_ch, eps_out, st, fuse);
         break;
+      }
     }
     if (rc) return rc;
     if (forking && o.side_id >= 0) SR3_HIP(hipEventRecord(P->join_ev[o.side_id], st));
@@ -983,21 +977,23 @@ int sr3_plan_op_info(sr3_plan* plan, int batch, int index, sr3_op_info* out) {
   memset(out, 0, sizeof(*out));
   out->kind = (int)o.kind * 10;
   if (o.kind == OP_CONV) {
-    const ConvParams& c = o.cp;
-    out->tile_cfg = tile_encode(o.tile_cfg, c.wino_split, c.igemm_split, o.has_wsplit, c.wino_full);
-    out->ksplit = o.ksplit;
+    const ConvParams& c = o.conv.cp;
+    const ConvChoice& ch = o.conv.ch;
+    out->tile_cfg = tile_encode(ch.tile_cfg, c.wino_split, c.igemm_split, ch.has_wsplit, c.wino_full);
+    out->ksplit = ch.ksplit;
     out->ksize = c.ksize; out->stride = c.stride; out->upsample = c.ups;
     out->cin = c.C0 + c.C1; out->cout = c.Cout; out->h_out = c.Ho; out->w_out = c.Wo;
-    out->fused_res_conv_cin = o.has_x2 ? c.x2_C0 + c.x2_C1 : 0;
-    out->fused_output_stats = o.has_ostat ? 1 : 0;
-    out->flops = 2.0 * c.B * c.Ho * c.Wo * (double)c.Cout * ((double)out->cin * c.ksize * c.ksize + out->fused_res_conv_cin);
+    out->fused_res_conv_cin = c.x2_C0 + c.x2_C1;             // (0 without the fused segment)
+    out->fused_output_stats = o.conv.ostat != NO_OFF ? 1 : 0;
+    out->flops = conv_flops(c);
   } else if (o.kind == OP_CONV_IN) {
-    out->ksize = 3; out->stride = 1; out->cin = o.i0 + o.i1; out->cout = o.i2; out->h_out = o.i3; out->w_out = o.i4;
-    out->fused_output_stats = o.has_ostat ? 1 : 0;
+    const Op::ConvIn& v = o.conv_in;
+    out->ksize = 3; out->stride = 1; out->cin = v.x_channels + v.cond_channels; out->cout = v.Cout; out->h_out = v.H; out->w_out = v.W;
+    out->fused_output_stats = v.ostat != NO_OFF ? 1 : 0;
   } else if (o.kind == OP_ATTN) {
-    out->h_out = o.i0; out->cin = out->cout = o.i1;          // tokens, channels
-    out->tile_cfg = o.tile_cfg;                              // 24: the key-blocked kernel (plan option attn_long); 0: the strip kernels
-    out->flops = 4.0 * batch * (double)o.i0 * (double)o.i0 * o.i1;
+    out->h_out = o.attn.tokens; out->cin = out->cout = o.attn.channels;
+    out->tile_cfg = o.attn.tile_cfg;                         // 24: the key-blocked kernel (plan option attn_long); 0: the strip kernels
+    out->flops = attn_flops(batch, o.attn.tokens, o.attn.channels);
   }
   return SR3_OK;
 }
@@ -1156,7 +1152,7 @@ int sr3_unet_forward(sr3_plan* plan, const float* x_nchw, const float* cond_nchw
   }
   if (plan->d.variant == SR3_VARIANT_SR3 && !noise_level && !step_dev) { set_error("SR3 variant needs noise_level or step_dev"); return SR3_E_BADARG; }
   if (plan->d.variant == SR3_VARIANT_DDPM && !timestep && !step_dev) { set_error("DDPM variant needs timestep or step_dev"); return SR3_E_BADARG; }
-  return run_forward(plan, infer_regions(plan), x_nchw, cond_nchw, cond_channels, noise_level, timestep, freq, level_table,
+  return run_forward(plan, false, x_nchw, cond_nchw, cond_channels, noise_level, timestep, freq, level_table,
                      step_dev, params, static_cast<char*>(workspace), eps_out_nchw, batch, static_cast<hipStream_t>(stream),
                      nullptr, nullptr);
 }
@@ -1182,7 +1178,7 @@ int sr3_reverse_step(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int 
   f.step_cur = step2_dev; f.step_next = step2_dev + 1; f.clip = clip_denoised;
   // the embedding kernel reads t from slot 1 and copies it to slot 0; the tail reads slot 0 and writes t - 1 to slot 1: no kernel
   // both reads and writes a slot, so no launch of the step races with another block of itself
-  return run_forward(plan, infer_regions(plan), x_nchw, cond_nchw, cond_channels, nullptr, nullptr, freq, level_table,
+  return run_forward(plan, false, x_nchw, cond_nchw, cond_channels, nullptr, nullptr, freq, level_table,
                      step2_dev + 1, params, static_cast<char*>(workspace), eps_out_nchw, batch, static_cast<hipStream_t>(stream),
                      nullptr, nullptr, nullptr, &f);
 }
@@ -1203,7 +1199,7 @@ int sr3_unet_forward_profile(sr3_plan* plan, const float* x_nchw, const float* c
       if (hipError_t err = hipEventCreate(&e); err != hipSuccess && !rc) rc = hip_fail(err, "hipEventCreate");
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (!rc)
-    rc = run_forward(plan, infer_regions(plan), x_nchw, cond_nchw, cond_channels, noise_level, timestep, freq, nullptr,
+    rc = run_forward(plan, false, x_nchw, cond_nchw, cond_channels, noise_level, timestep, freq, nullptr,
                      nullptr, params, static_cast<char*>(workspace), eps_out_nchw, batch, st, ev.data(), mid.data());
   if (!rc) {
     hipError_t e = hipEventSynchronize(ev[n]);
@@ -1219,31 +1215,32 @@ int sr3_unet_forward_profile(sr3_plan* plan, const float* x_nchw, const float* c
       double fl = 0.0;
       float red_ms = -1.f;
       if (o.kind == OP_CONV) {
+        const ConvParams& c = o.conv.cp;
+        const int tile = o.conv.ch.tile_cfg;
         // 51-54 im2col kernel tile configs; 55/56 halo-tile 3x3 kernel (57/58: with the fused 1x1 segment)
         //        155-158: the same four on the opt-in split-bf16 instantiations; 255/257: the 8-wave 256x128 tile
         //        (cfg 9), 355/357: its split-bf16 twin (cfg 10); 455: the Winograd F(2x2,3x3) kernel (cfg 11), 465: its four-image
         //        tile of the 8x8 maps, 555: its 3 x bf16 split instantiation (plan option wino_split)
         {
           static const int base[13] = {0, 1, 2, 3, 4, 5, 6, 105, 106, 205, 305, 405, 505};
-          if (o.tile_cfg == 22) kind += 182;                                               // 232: the 1x1 GEMM kernel (gemm1x1.hip)
+          if (tile == 22) kind += 182;                                               // 232: the 1x1 GEMM kernel (gemm1x1.hip)
           else
-          kind += base[(o.tile_cfg == 11 && o.cp.wino_split) ? 12 : o.tile_cfg] + ((o.tile_cfg >= 5 && o.has_x2) ? 2 : 0);
-          if (o.tile_cfg == 11 && o.cp.wino_split == 2) kind += 20;                         // 575: the two-workgroups-per-CU split kernel (conv3x3_wino2.hip)
-          if (o.tile_cfg == 11 && o.cp.wino_split == 3) kind += 30;                         // 585: ... its ragged instantiation
-          if (o.tile_cfg >= 1 && o.tile_cfg <= 4 && o.cp.igemm_split) kind += 600;           // 651-654: the im2col tiles on their 3 x bf16 split instantiation
+          kind += base[(tile == 11 && c.wino_split) ? 12 : tile] + ((tile >= 5 && o.conv.x2_src0 != NO_OFF) ? 2 : 0);
+          if (tile == 11 && c.wino_split == 2) kind += 20;                         // 575: the two-workgroups-per-CU split kernel (conv3x3_wino2.hip)
+          if (tile == 11 && c.wino_split == 3) kind += 30;                         // 585: ... its ragged instantiation
+          if (tile >= 1 && tile <= 4 && c.igemm_split) kind += 600;           // 651-654: the im2col tiles on their 3 x bf16 split instantiation
           WinoGeom wg;
-          if (o.tile_cfg == 11 && wino_geometry(o.cp, &wg) && wg.NB != 1) kind += 10;      // 465: the four-image 8x8 tile
+          if (tile == 11 && wino_geometry(c, &wg) && wg.NB != 1) kind += 10;      // 465: the four-image 8x8 tile
         }
-        const ConvParams& c = o.cp;
-        fl = 2.0 * c.B * c.Ho * c.Wo * (double)c.Cout * ((double)(c.C0 + c.C1) * c.ksize * c.ksize + (o.has_x2 ? c.x2_C0 + c.x2_C1 : 0));
-        if (o.ksplit > 1) {      // split the op into its GEMM kernel and its split-K reduce kernel
+        fl = conv_flops(c);
+        if (o.conv.ch.ksplit > 1) {      // split the op into its GEMM kernel and its split-K reduce kernel
           float a = 0.f;
           if (hipError_t e = hipEventElapsedTime(&a, ev[i], mid[i]); e != hipSuccess) { rc = hip_fail(e, "hipEventElapsedTime"); break; }
           red_ms = ms - a;
           ms = a;
         }
       } else if (o.kind == OP_ATTN) {
-        fl = 4.0 * batch * (double)o.i0 * (double)o.i0 * o.i1;
+        fl = attn_flops(batch, o.attn.tokens, o.attn.channels);
       }
       if (w + 2 > max_ops) { set_error("op buffer too small"); rc = SR3_E_NOMEM; break; }
       op_ms[w] = ms; op_kind[w] = kind; op_flops[w] = fl; ++w;

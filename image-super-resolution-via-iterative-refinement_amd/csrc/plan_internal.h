@@ -32,60 +32,100 @@ struct ResLayer {
   size_t an_w, an_b, qkv_w, ao_w, ao_b;
 };
 
+enum LayerKind { L_CONV_IN, L_RES, L_DOWN, L_UP };
 struct Layer {
-  int kind;  // 0 conv_in, 1 res, 2 down, 3 up
+  LayerKind kind;
   std::string name;
   int cin, cout;
   size_t w, b;  // conv_in / down / up
   ResLayer res;
 };
 
+// an optional workspace / arena offset that is absent (run_forward binds a null pointer for it)
+static constexpr size_t NO_OFF = ~(size_t)0;
+
+// The kernel one conv of a plan runs on, as choose_conv (plan.hip) decided it
+struct ConvChoice {
+  int tile_cfg, ksplit;            // what conv_forward is called with
+  int wino_split, igemm_split;     // the ConvParams fields of these names
+  int wino_mode;                   // 0: the Winograd rule did not take the conv; 1 / 2: wino_mode (plan.hip)
+  size_t wino_off;                 // tile_cfg 11: float offset of this conv's transformed filters in the derived buffer
+  bool has_wsplit;                 // im2col SPLIT tile / tile 22: its weights pre-split into bf16 planes sit in the derived buffer ...
+  size_t wsplit_off;               // ... at this float offset (ConvParams::w_split)
+  int wino_full = 0;               // ConvParams::wino_full
+};
+
+// The NEXT op's GroupNorm fold done by an op's last kernel (plan option fold_fuse): a split-K conv's reduce, or the stand-alone
+// statistics pass.  The host side of FoldTail (sr3_common.h): Builder::fuse_fold_into fills it, make_fold_tail binds it
+struct FoldSpec {
+  int Ctot = 0, c_off = 0;
+  size_t ostat = NO_OFF;           // the other concat source's partials (bytes in the statistics region; NO_OFF: single source)
+  int oC = 0, oT = 0, o_off = 0;
+  size_t gamma = 0, beta = 0;      // float offsets into the parameter arena
+  size_t ss_rel = 0, mr_rel = 0;   // the consumer's tables, as Op::ss_rel / mr_rel
+  bool has_mr = false;
+};
+
 // numeric values are part of sr3_unet_forward_profile's op_kind encoding (kind * 10)
 enum OpKind { OP_RESERVED, OP_EMBED, OP_CONV_IN, OP_STATS, OP_FOLD, OP_CONV, OP_ATTN, OP_CONV_OUT };
 
+// One launch of a compiled forward: the payload of its kind, and what several kinds share.  Activations are byte offsets into the
+// workspace, statistics partials byte offsets into its statistics region, parameters float offsets into the arena
 struct Op {
   OpKind kind;
-  // generic offsets (bytes into workspace unless noted)
-  size_t a = 0, b = 0, c = 0, d = 0, e = 0, f = 0, g = 0, h = 0;
-  size_t p0 = 0, p1 = 0, p2 = 0, p3 = 0;   // float offsets into the parameter arena
-  int i0 = 0, i1 = 0, i2 = 0, i3 = 0, i4 = 0, i5 = 0;
-  bool has_src1 = false, has_bias = false, has_film = false, has_res = false, has_res1 = false, has_ostat = false,
-       has_st1 = false, has_x2 = false, has_x21 = false;
+  struct ConvIn {
+    int x_channels = 0, cond_channels = 0, Cout = 0, H = 0, W = 0;
+    size_t w = 0, bias = 0, out = 0, ostat = NO_OFF;
+  } conv_in;
+  struct Stats { size_t src = 0, stat = 0; int pixels = 0, channels = 0; } stats;
+  struct Fold {                      // the partials of the virtual concat (stat0|stat1) -> the consumer's tables at ss_rel / mr_rel
+    size_t stat0 = 0, stat1 = NO_OFF;
+    int C0 = 0, C1 = 0, T0 = 0, T1 = 0, pixels = 0;      // channels, partials per image of either source
+    size_t gamma = 0, beta = 0;
+    bool has_mr = false;
+  } fold;
+  struct Conv {
+    ConvParams cp = {};              // geometry (pointers filled at launch)
+    ConvChoice ch = {};              // the kernel, as choose_conv returned it
+    size_t src0 = 0, src1 = NO_OFF, res0 = NO_OFF, res1 = NO_OFF, out = 0, ostat = NO_OFF;
+    size_t w = 0, bias = NO_OFF;
+    int film_row = -1;               // first row of the FiLM table added to the output (-1: none)
+    size_t x2_src0 = NO_OFF, x2_src1 = NO_OFF, x2_w = 0, x2_bias = 0;      // fused 1x1 segment (res_conv); x2_src0 == NO_OFF: none
+    bool has_drop = false;
+    unsigned drop_key = 0;
+  } conv;
+  struct Attn { size_t qkv = 0, out = 0; int tokens = 0, channels = 0, tile_cfg = 0; } attn;      // tile_cfg 24: the key-blocked kernel
+  struct ConvOut { size_t src = 0, w = 0, bias = 0; int channels = 0, out_ch = 0, H = 0, W = 0; } conv_out;
   size_t ss_rel = 0, mr_rel = 0;   // GroupNorm tables: offset inside the scale/shift region (0 in inference)
-  bool has_mr = false, has_drop = false;
-  unsigned drop_key = 0;
-  // the NEXT op's GroupNorm fold done by this op's last kernel (plan option fold_fuse; FoldTail in sr3_common.h): a split-K conv's
-  // reduce, or the stand-alone statistics pass
-  bool fold_fused = false, f_has_o = false, f_has_mr = false;
-  int f_Ctot = 0, f_coff = 0, f_oC = 0, f_oT = 0, f_ooff = 0;
-  size_t f_ostat = 0, f_gamma = 0, f_beta = 0, f_ss_rel = 0, f_mr_rel = 0;
-  ConvParams cp;                   // OP_CONV geometry (pointers filled at launch)
-  int tile_cfg = 0, ksplit = 0;
-  size_t wino_off = 0;             // tile_cfg 11: float offset of this conv's transformed filters in the derived buffer
+  bool fold_fused = false;         // OP_CONV (split-K) / OP_STATS: the last kernel does the fold `tail` too
+  FoldSpec tail;
   // plan option fork_side (inference plans): side_id >= 0 -- this op depends on nothing the ops between it and its consumer write, so it
   // is launched on the plan's side stream (forked from the caller's stream by an event, joined by event side_id); wait_id >= 0 -- the
   // caller's stream waits for join event wait_id before this op (the consumer).  Inside a stream capture the pair becomes a parallel
   // branch of the graph.
   int side_id = -1, wait_id = -1;
-  bool has_wsplit = false;         // im2col SPLIT tile: its weights pre-split into bf16 planes sit in the derived buffer ...
-  size_t wsplit_off = 0;           // ... at this float offset (ConvParams::w_split)
 };
+
+// every term is an integer far below 2^53: the sums over a launch list are exact in any order
+inline double conv_flops(const ConvParams& c) {
+  return 2.0 * c.B * c.Ho * c.Wo * (double)c.Cout * ((double)(c.C0 + c.C1) * c.ksize * c.ksize + (c.x2_C0 + c.x2_C1));
+}
+inline double attn_flops(int B, int tokens, int channels) { return 4.0 * B * (double)tokens * (double)tokens * channels; }
 
 struct Tap { std::string name; size_t off; int C, H, W; };
 
-// where the fixed regions of a compiled forward live inside the workspace
+// where the fixed regions of a compiled forward live inside the workspace: statistics partials, GroupNorm scale/shift tables, mean/rstd
+// tables (training only), time embedding, FiLM table, split-K slabs
 struct Regions {
-  const std::vector<Op>* ops;
-  size_t stats_off, ss_off, mr_off, temb_off, film_off, scratch_off, scratch_bytes;
+  size_t stats_off = 0, ss_off = 0, mr_off = 0, temb_off = 0, film_off = 0, scratch_off = 0, scratch_bytes = 0;
 };
 
 // One conv of the forward, for Builder::conv: sources and residuals are tensor handles (-1: absent), parameters arena offsets
-static constexpr size_t NO_PARAM = ~(size_t)0;
 struct ConvSpec {
   int x0 = -1, x1 = -1;            // source: the virtual concat (x0|x1)
   int Cout = 0, ksize = 3, stride = 1, ups = 0;
   int act = 0;                     // ConvParams::act: what the prologue does with the GroupNorm fold in front of this conv
-  size_t w = 0, bias = NO_PARAM;
+  size_t w = 0, bias = NO_OFF;
   int film_row = -1;               // first row of the FiLM table added to the output
   int r0 = -1, r1 = -1;            // residual: the concat view (r0|r1)
   bool want_stats = false;         // a GroupNorm reads the output: fuse its statistics where the kernel can
@@ -206,7 +246,7 @@ struct sr3_plan {
   std::vector<Op> ops;
   std::vector<Tap> taps;
   size_t ws_bytes = 0;
-  size_t stats_off = 0, stats_bytes = 0, ss_off = 0, temb_off = 0, film_off = 0, scratch_off = 0, scratch_bytes = 0;
+  Regions regions;
   double flops = 0;
   // ---- training step (train_plan.hip) ----
   int train_batch = -1, train_cond = -1;
@@ -215,9 +255,9 @@ struct sr3_plan {
   std::vector<sr3::Tensor> ttens;    // tensor table of the train forward
   std::vector<sr3::Rec> recs;
   size_t t_act_bytes = 0;            // activations; gradients mirror them at +t_act_bytes
-  size_t t_stats_off = 0, t_gn_off = 0, t_temb_off = 0, t_film_off = 0, t_scratch_off = 0, t_scratch_bytes = 0;
+  Regions t_regions;                 // ... of the train forward (its scratch region doubles as the backward's)
   size_t t_dA_off = 0, t_z_off = 0, t_dq_off = 0, t_wt_off = 0, t_slab_off = 0, t_part_off = 0, t_gs_off = 0;
-  size_t t_dfilm_off = 0, t_misc_off = 0, t_xnoisy_off = 0, t_eps_off = 0, t_geps_off = 0, t_inpad_off = 0, t_dwtmp_off = 0;
+  size_t t_dfilm_off = 0, t_xnoisy_off = 0, t_eps_off = 0, t_geps_off = 0, t_inpad_off = 0, t_dwtmp_off = 0;
   size_t t_ws_bytes = 0, t_embscr_off = 0, t_a_off = 0;
   size_t t_wu_off = 0, t_wu_bytes = 0;   // derived filters of the data-gradient conv being run (Dgrad::wu)
   std::vector<size_t> t_unproc_max;  // [ri]: max parameter end offset still unwritten before record ri-1 is processed
@@ -232,8 +272,8 @@ struct Builder;
 inline int plan_height(const sr3_plan* P) { return P->geo_h > 0 ? P->geo_h : P->d.image_size; }
 inline int plan_width(const sr3_plan* P) { return P->geo_w > 0 ? P->geo_w : P->d.image_size; }
 inline bool plan_native_geometry(const sr3_plan* P) { return plan_height(P) == P->d.image_size && plan_width(P) == P->d.image_size; }
-Regions infer_regions(const sr3_plan* P);
-int run_forward(sr3_plan* P, const Regions& R, const float* x, const float* cond, int cond_channels, const float* level,
+// replays P->ops over P->regions, or (train) P->tops over P->t_regions
+int run_forward(sr3_plan* P, bool train, const float* x, const float* cond, int cond_channels, const float* level,
                 const int64_t* tstep, const float* freq, const float* level_table, const int* step_dev,
                 const float* params, char* ws, float* eps_out, int B, hipStream_t st, hipEvent_t* ev, hipEvent_t* mid,
                 const DropCfg* drop = nullptr, const StepFuse* fuse = nullptr);

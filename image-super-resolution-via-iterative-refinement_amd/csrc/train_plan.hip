@@ -141,7 +141,7 @@ int resolve_backward(sr3_plan* P, int B) {
     // parameters: the conv's own (the arena holds the real channel counts, not the padded ones), its GroupNorm's, res_conv's
     const size_t cout = r.kind == R_CONV_OUT ? P->out_ch : r.dw.Cout, cin = r.kind == R_CONV_IN ? P->d.in_channel : r.dw.C0 + r.dw.C1;
     r.param_end = pend(s.w, cout * s.ksize * s.ksize * cin);
-    if (s.bias != NO_PARAM) r.param_end = std::max(r.param_end, pend(s.bias, cout));
+    if (s.bias != NO_OFF) r.param_end = std::max(r.param_end, pend(s.bias, cout));
     if (s.act) r.param_end = std::max({r.param_end, pend(r.gamma, cin), pend(r.beta, cin)});
     if (s.q0 >= 0) r.param_end = std::max({r.param_end, pend(s.qw, cout * (r.dqw.C0 + r.dqw.C1)), pend(s.qb, cout)});
   }
@@ -213,13 +213,14 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
   size_t off = al(fw.act_high);
   P->t_act_bytes = off;
   off *= 2;                                   // gradients mirror the activations at +t_act_bytes
-  P->t_stats_off = off; off += al(fw.stats_bytes);
-  P->t_gn_off = off; off += al(fw.gn_bytes);
-  P->t_misc_off = off; off += al(fw.mr_bytes);             // mean / rstd tables
-  P->t_temb_off = off; off += al((size_t)B * inner * sizeof(float));
-  P->t_film_off = off; off += al((size_t)B * P->F * sizeof(float));
-  P->t_scratch_bytes = std::max(fw.max_scratch, max_bscratch);      // the forward's split-K region doubles as the backward's
-  P->t_scratch_off = off; off += al(P->t_scratch_bytes);
+  Regions& R = P->t_regions;
+  R.stats_off = off; off += al(fw.stats_bytes);
+  R.ss_off = off; off += al(fw.gn_bytes);                  // per-GroupNorm scale / shift tables, kept for the backward
+  R.mr_off = off; off += al(fw.mr_bytes);                  // ... and mean / rstd tables
+  R.temb_off = off; off += al((size_t)B * inner * sizeof(float));
+  R.film_off = off; off += al((size_t)B * P->F * sizeof(float));
+  R.scratch_bytes = std::max(fw.max_scratch, max_bscratch);      // the forward's split-K region doubles as the backward's
+  R.scratch_off = off; off += al(R.scratch_bytes);
   P->t_dA_off = off; off += al(max_dA);
   P->t_a_off = off; off += al(max_dA);       // materialised activated input of the weight-gradient GEMM
   P->t_z_off = off; off += al(max_z);
@@ -239,7 +240,7 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
   P->t_ws_bytes = off;
   // KEPT QUIRK: THIS PASS settles the kernels that read derived filters nothing above sized for -- taken exactly where the filters fit
   // t_wu and (tile 22) the slabs fit t_scratch as sized.  Sizing for them would move workspace sizes and kernel choices: a change of its own
-  choose_dgrads(P, P->t_wu_bytes, P->t_scratch_bytes);
+  choose_dgrads(P, P->t_wu_bytes, R.scratch_bytes);
   // gradient-ready marks: t_unproc_max[k] = largest arena offset (exclusive end) among the parameters whose
   // gradients are still unwritten once records k .. end have been processed (records < k + the FiLM /
   // embedding block at the arena head, which is written last)
@@ -282,7 +283,7 @@ int dgrad_conv(const TrainCtx& X, const Dgrad& d, const float* g, const float* w
   if (d.wu == WU_GEMM) { rc = igemm_split_weights(wt, c.Cout, 1, c.C0, wu, X.st); c.w_split = wu; }
   else if (d.wu != WU_NONE) { rc = wino_transform_weights(wt, c.Cout, c.C0, wu, X.st, d.wu == WU_WINO_SPLIT); c.wino_u = wu; }
   if (rc) return rc;
-  return conv_forward(c, d.tile, d.ksplit, X.at<float>(X.P->t_scratch_off), X.P->t_scratch_bytes, X.st);
+  return conv_forward(c, d.tile, d.ksplit, X.at<float>(X.P->t_regions.scratch_off), X.P->t_regions.scratch_bytes, X.st);
 }
 
 // weight gradient of the shape `c` over the sources src0 | src1.  wgrad_split is a no-rebuild option (the slabs are sized for both
@@ -315,13 +316,10 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
   float* eps = X.at<float>(P->t_eps_off);
   rc = q_sample(hr, z, q_ca, q_cb, B, xc * S2, x_noisy, st);
   if (rc) return rc;
-  Regions R;
-  R.ops = &P->tops; R.stats_off = P->t_stats_off; R.ss_off = P->t_gn_off; R.mr_off = P->t_misc_off;
-  R.temb_off = P->t_temb_off; R.film_off = P->t_film_off; R.scratch_off = P->t_scratch_off; R.scratch_bytes = P->t_scratch_bytes;
   DropCfg dc;
   dc.seed = seed;
   dropout_consts(dropout_p, &dc.thresh, &dc.scale);
-  rc = run_forward(P, R, x_noisy, cond, cond_channels, level, tstep, freq, nullptr, nullptr, params, ws, eps, B, st, nullptr,
+  rc = run_forward(P, true, x_noisy, cond, cond_channels, level, tstep, freq, nullptr, nullptr, params, ws, eps, B, st, nullptr,
                    nullptr, &dc);
   if (rc) return rc;
   // ---- loss and its gradient (NHWC, channel dim padded to 4) ----
@@ -356,8 +354,8 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
       if (rc) return rc;
       rc = dgrad_conv(X, r.dx, geps, params + s.w, P->out_ch, dA);
       if (rc) return rc;
-      rc = act_bwd(dA, X.act(s.x0), nullptr, C, 0, B, S2, X.at<float>(P->t_gn_off + r.ss_off),
-                   X.at<float>(P->t_misc_off + r.mr_off), G, s.act, params + r.gamma, part, gs, grads + r.gamma,
+      rc = act_bwd(dA, X.act(s.x0), nullptr, C, 0, B, S2, X.at<float>(P->t_regions.ss_off + r.ss_off),
+                   X.at<float>(P->t_regions.mr_off + r.mr_off), G, s.act, params + r.gamma, part, gs, grads + r.gamma,
                    grads + r.beta, X.grad(s.x0), nullptr, st, 0u, 0u, 1.f, abuf, r.acc_x0, true);
       if (rc) return rc;
       rc = wgrad_call(X, r.dw, abuf, nullptr, geps, dwtmp);
@@ -367,7 +365,7 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
       const Tensor& o = P->ttens[r.o];
       // dK / dV through per-query-block slabs in the backward's scratch region, summed in block order: no atomics (round 6)
       rc = attention_backward(X.act(r.qkv), X.grad(r.o), X.act(r.o), B, o.H * o.W, o.C, X.grad(r.qkv), st,
-                              X.at<float>(P->t_scratch_off), P->t_scratch_bytes);
+                              X.at<float>(P->t_regions.scratch_off), P->t_regions.scratch_bytes);
       if (rc) return rc;
     } else if (r.kind == R_CONV_IN) {
       const int Cout = r.dw.Cout;
@@ -389,13 +387,13 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
       const Tensor& x0 = P->ttens[s.x0];
       const int C0 = x0.C, C1 = s.x1 >= 0 ? P->ttens[s.x1].C : 0;
       const int Ho = r.dw.Ho, Wo = r.dw.Wo, Cout = r.dw.Cout;
-      const bool has_bias = s.bias != NO_PARAM, has_q = s.q0 >= 0;
+      const bool bias_grad = s.bias != NO_OFF, has_q = s.q0 >= 0;
       const float* g = X.grad(r.out);
       const float* x0p = X.act(s.x0);
       const float* x1p = s.x1 >= 0 ? X.act(s.x1) : nullptr;
       // 1. bias and FiLM gradients: column sums of dOut
-      if (has_bias || s.film_row >= 0 || has_q) {
-        rc = colsums(g, B, Ho * Wo, Cout, part, has_bias ? grads + s.bias : nullptr,
+      if (bias_grad || s.film_row >= 0 || has_q) {
+        rc = colsums(g, B, Ho * Wo, Cout, part, bias_grad ? grads + s.bias : nullptr,
                      s.film_row >= 0 ? dfilm + s.film_row : nullptr, P->F, st);
         if (rc) return rc;
         if (has_q)        // res_conv bias sees the same sums
@@ -430,8 +428,8 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
       if (s.act) {
         const bool dropped = s.drop_key >= 0 && dc.thresh != 0;
         const unsigned lseed = drop_layer_seed(dc.seed, (unsigned)(s.drop_key >= 0 ? s.drop_key : 0));
-        rc = act_bwd(dA, x0p, x1p, C0, C1, B, x0.H * x0.W, X.at<float>(P->t_gn_off + r.ss_off),
-                     X.at<float>(P->t_misc_off + r.mr_off), G, s.act, params + r.gamma, part, gs, grads + r.gamma,
+        rc = act_bwd(dA, x0p, x1p, C0, C1, B, x0.H * x0.W, X.at<float>(P->t_regions.ss_off + r.ss_off),
+                     X.at<float>(P->t_regions.mr_off + r.mr_off), G, s.act, params + r.gamma, part, gs, grads + r.gamma,
                      grads + r.beta, X.grad(s.x0), X.grad(s.x1), st, lseed, dropped ? dc.thresh : 0u, dc.scale, abuf, r.acc_x0, r.acc_x1);
       } else {
         rc = grad_route(dA, C0, C1, B, x0.H, x0.W, s.ups, X.grad(s.x0), X.grad(s.x1), st, r.acc_x0, r.acc_x1);
