@@ -766,7 +766,7 @@ static FoldTail make_fold_tail(const FoldSpec& s, int groups, const float* param
 int run_forward(sr3_plan* P, bool train, const float* x, const float* cond, int cond_channels, const float* level,
                 const int64_t* tstep, const float* freq, const float* level_table, const int* step_dev,
                 const float* params, char* ws, float* eps_out, int B, hipStream_t st,
-                hipEvent_t* ev, hipEvent_t* mid, const DropCfg* drop, const StepFuse* fuse) {
+                hipEvent_t* ev, hipEvent_t* mid, const DropCfg* drop, const StepFuse* fuse, const int* t_map) {
   const sr3_unet_desc& d = P->d;
   const Regions& R = train ? P->t_regions : P->regions;
   size_t op_index = 0;
@@ -802,7 +802,7 @@ int run_forward(sr3_plan* P, bool train, const float* x, const float* cond, int 
         EmbedParams e;
         memset(&e, 0, sizeof(e));
         e.variant = d.variant; e.B = B; e.inner = d.inner_channel;
-        e.level = level; e.tstep = tstep; e.level_table = level_table; e.step_dev = step_dev; e.freq = freq;
+        e.level = level; e.tstep = tstep; e.level_table = level_table; e.step_dev = step_dev; e.t_map = t_map; e.freq = freq;
         e.step_out = fuse ? const_cast<int*>(fuse->step_cur) : nullptr;
         e.w1 = params + P->emb_w1; e.b1 = params + P->emb_b1; e.w2 = params + P->emb_w2; e.b2 = params + P->emb_b2;
         e.wf = params + P->film_w; e.bf = params + P->film_b; e.F = P->F;
@@ -1159,10 +1159,10 @@ int sr3_unet_forward(sr3_plan* plan, const float* x_nchw, const float* cond_nchw
 
 // One whole reverse step (include/sr3_mi355x.h): the forward above with the p_sample update and the counter decrement inside the
 // output conv's kernel -- two graph nodes fewer per step than sr3_unet_forward + sr3_p_sample_step + sr3_step_decrement.
-int sr3_reverse_step(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,
-                     const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
-                     const float* z_nchw, const float* ta, const float* tb, const float* tc1, const float* tc2, const float* tsig,
-                     int clip_denoised, float* eps_out_nchw, int batch, void* stream) {
+int sr3_reverse_step_ex(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,
+                        const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
+                        const float* z_nchw, const float* ta, const float* tb, const float* tc1, const float* tc2, const float* tsig,
+                        int clip_denoised, float* eps_out_nchw, int batch, void* stream, const int* t_map) {
   if (!plan || !x_nchw || !params || !workspace || !freq || !step2_dev || !ta || !tb || !tc1 || !tc2 || !tsig) { set_error("null argument"); return SR3_E_BADARG; }
   if (!cond_nchw) cond_channels = 0;
   const int rc = build_forward(plan, batch, cond_channels);
@@ -1180,7 +1180,15 @@ int sr3_reverse_step(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int 
   // both reads and writes a slot, so no launch of the step races with another block of itself
   return run_forward(plan, false, x_nchw, cond_nchw, cond_channels, nullptr, nullptr, freq, level_table,
                      step2_dev + 1, params, static_cast<char*>(workspace), eps_out_nchw, batch, static_cast<hipStream_t>(stream),
-                     nullptr, nullptr, nullptr, &f);
+                     nullptr, nullptr, nullptr, &f, t_map);
+}
+
+int sr3_reverse_step(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,
+                     const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
+                     const float* z_nchw, const float* ta, const float* tb, const float* tc1, const float* tc2, const float* tsig,
+                     int clip_denoised, float* eps_out_nchw, int batch, void* stream) {
+  return sr3_reverse_step_ex(plan, x_nchw, cond_nchw, cond_channels, freq, level_table, step2_dev, params, workspace, workspace_bytes,
+                             z_nchw, ta, tb, tc1, tc2, tsig, clip_denoised, eps_out_nchw, batch, stream, nullptr);
 }
 
 int sr3_unet_forward_profile(sr3_plan* plan, const float* x_nchw, const float* cond_nchw, int cond_channels,

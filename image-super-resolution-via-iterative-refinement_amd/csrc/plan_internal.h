@@ -276,7 +276,7 @@ inline bool plan_native_geometry(const sr3_plan* P) { return plan_height(P) == P
 int run_forward(sr3_plan* P, bool train, const float* x, const float* cond, int cond_channels, const float* level,
                 const int64_t* tstep, const float* freq, const float* level_table, const int* step_dev,
                 const float* params, char* ws, float* eps_out, int B, hipStream_t st, hipEvent_t* ev, hipEvent_t* mid,
-                const DropCfg* drop = nullptr, const StepFuse* fuse = nullptr);
+                const DropCfg* drop = nullptr, const StepFuse* fuse = nullptr, const int* t_map = nullptr);
 // The forward walk in train mode (plan.hip): fills P->tops, P->ttens and P->recs (every activation kept, persistent GroupNorm
 // tables) and returns what build_train lays the workspace out by
 struct TrainWalk {

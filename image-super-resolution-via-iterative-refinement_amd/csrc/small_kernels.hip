@@ -699,7 +699,7 @@ __global__ __launch_bounds__(256) void k_embed(const EmbedParams p) {
   if (p.variant == 0) {
     lv = p.step_dev ? p.level_table[p.step_dev[0] + 1] : p.level[b];
   } else {
-    lv = p.step_dev ? (float)p.step_dev[0] : (float)p.tstep[b];
+    lv = p.step_dev ? (float)(p.t_map ? p.t_map[p.step_dev[0]] : p.step_dev[0]) : (float)p.tstep[b];
   }
   if (p.step_out && b == 0 && tid == 0) p.step_out[0] = p.step_dev[0];      // (sr3_reverse_step: the slot the step's tail reads)
   for (int k = tid; k < half; k += 256) {

@@ -311,6 +311,7 @@ struct EmbedParams {
   const int64_t* tstep;   // [B] (ddpm) or null
   const float* level_table;  // sr3: level = level_table[step_dev[0] + 1] when step_dev != null
   const int* step_dev;    // device step counter (graph replay) or null
+  const int* t_map;       // ddpm, with step_dev: timestep = t_map[step_dev[0]] (a strided walk through the schedule); null: the counter itself
   int* step_out;          // optional: block 0 copies *step_dev here (sr3_reverse_step: the slot the step's tail kernel reads)
   const float* freq;      // [inner/2] frequency table
   const float* w1; const float* b1;   // [4*inner][inner], [4*inner]

@@ -10,6 +10,10 @@ Engine design (not the reference's): one reverse step = [z ~ N(0,I) in-graph] ->
 (conditioning read as a virtual concat; noise level taken from a device table indexed by a
 device-side step counter) -> fused x_{t-1} update -> counter decrement, captured once as a
 hipGraph and replayed T times; snapshots are graph-external device copies.
+
+Sampler (engine extension, `"sampler": {"type": "ddim", "steps": S, "eta": e}` in the schedule dict or `set_sampler`): the same
+captured step replayed S times over a strided walk through the schedule -- `sampler_tables` restates the DDIM update in the fused
+tail's linear form, so a sampler is five other coefficient tables, another level table and (DDPM) a step-index -> timestep map.
 """
 import ctypes as C
 
@@ -45,6 +49,51 @@ def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2,
     raise NotImplementedError(schedule)
 
 
+def sampler_tables(alphas_cumprod, steps, eta):
+    """Tables of a strided DDIM sampler (Song et al. 2021, eq. 12 and 16) in the form of the engine's fused step tail,
+
+        x0c = clip(a x - b eps) ;  x_new = c1 x0c + c2 x + sigma z,
+
+    which is the textbook update  sqrt(ap) x0c + d eps' + sigma z  with eps' = (x - sqrt(ab) x0c) / sqrt(1 - ab) re-derived from the
+    clipped x0 (the reference's clip_denoised semantics), d = sqrt(1 - ap - sigma^2): collecting x0c and x gives
+    c1 = sqrt(ap) - d sqrt(ab) / sqrt(1 - ab), c2 = d / sqrt(1 - ab).  ab = alphas_cumprod[tau[j]], ap = that of the next (smaller)
+    timestep of the walk and 1 after the last; sigma = eta sqrt((1 - ap) / (1 - ab)) sqrt(1 - ab / ap).  With steps = T and eta = 1 these
+    are the reference's posterior_mean_coef1/2 and sqrt(posterior_variance).
+
+    Pure numpy, float64, no device.  The step index j counts like the device counter: j = steps - 1 is the first step taken, j = 0 the
+    last.  Returns a dict: tau (int64, [S], strictly increasing, tau[0] = 0 and tau[S-1] = T - 1; S = 1: [T - 1]), a, b, c1, c2,
+    sigma ([S]) and level ([S + 1]: level[j + 1] = sqrt(alphas_cumprod[tau[j]]), the reference's sqrt_alphas_cumprod_prev[t + 1] at
+    t = tau[j]; level[0] = 1)."""
+    ac = np.asarray(alphas_cumprod, dtype=np.float64).reshape(-1)
+    T = int(ac.shape[0])
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)):
+        raise ValueError('sampler steps must be an integer (got %r)' % (steps,))
+    try:
+        eta = float(eta)
+    except (TypeError, ValueError):
+        raise ValueError('sampler eta must be a number (got %r)' % (eta,))
+    if not np.isfinite(eta) or not 0.0 <= eta <= 1.0:
+        raise ValueError('sampler eta must lie in [0, 1] (got %r)' % (eta,))
+    if T < 1 or not np.all(np.isfinite(ac)) or not np.all((ac > 0.0) & (ac < 1.0)):
+        raise ValueError('alphas_cumprod must be finite values in (0, 1)')
+    S = int(steps)
+    if S < 1 or S > T:
+        raise ValueError('sampler steps must lie in [1, %d] (got %d)' % (T, S))
+    tau = np.round(np.linspace(0, T - 1, S)).astype(np.int64) if S > 1 else np.array([T - 1], dtype=np.int64)
+    assert tau[-1] == T - 1 and (S == 1 or tau[0] == 0) and np.all(np.diff(tau) > 0), 'sampler walk is not strictly increasing'
+    ab = ac[tau]
+    ap = np.append(1.0, ab[:-1])
+    sigma = eta * np.sqrt((1.0 - ap) / (1.0 - ab)) * np.sqrt(1.0 - ab / ap)
+    d = np.sqrt(np.maximum(1.0 - ap - sigma ** 2, 0.0))
+    out = dict(tau=tau, a=np.sqrt(1.0 / ab), b=np.sqrt(1.0 / ab - 1), c1=np.sqrt(ap) - d * np.sqrt(ab) / np.sqrt(1.0 - ab),
+               c2=d / np.sqrt(1.0 - ab), sigma=sigma, level=np.append(1.0, np.sqrt(ab)))
+    if not all(np.all(np.isfinite(v)) for v in out.values()):
+        raise ValueError('sampler tables are not finite')
+    return out
+
+
+_SAMPLER_TABLES = ('a', 'b', 'c1', 'c2', 'sigma', 'level', 'tau')
+
 _BUFFERS = ('betas', 'alphas_cumprod', 'alphas_cumprod_prev', 'sqrt_alphas_cumprod',
             'sqrt_one_minus_alphas_cumprod', 'log_one_minus_alphas_cumprod', 'sqrt_recip_alphas_cumprod',
             'sqrt_recipm1_alphas_cumprod', 'posterior_variance', 'posterior_log_variance_clipped',
@@ -64,6 +113,7 @@ class EngineDiffusion(nn.Module):
         self.use_graph = True          # hipGraph replay of the reverse step
         self.show_progress = True
         self._loop_cache = {}
+        self.sampler = None            # None: the reference's ancestral loop; else {'type': 'ddim', 'steps': S, 'eta': e} (set_sampler)
         self.max_cached_loops = 3      # reverse-loop states (buffers + workspace + captured graph) kept, one per (shape, launch list)
         # schedule_opt is accepted and ignored exactly like the reference ctor (diffusion.py:80-82)
 
@@ -101,6 +151,36 @@ class EngineDiffusion(nn.Module):
         sig[0] = 0.0                                                             # `t > 0` branch / nonzero_mask
         self.register_buffer('_level_table', lvl.to(device), persistent=False)
         self.register_buffer('_sigma', sig.to(device), persistent=False)
+        self._alphas_cumprod64 = ac                                              # what a sampler's tables are computed from
+        self._loop_cache = {}
+        # engine key of the schedule dict: "sampler": {"type": "ddim", "steps": S, "eta": e}; absent / null: the ancestral loop
+        spec = schedule_opt.get('sampler') if hasattr(schedule_opt, 'get') else None
+        if spec is None:
+            self.set_sampler(None)
+        else:
+            kind = spec.get('type', 'ddim')
+            if kind != 'ddim':
+                raise NotImplementedError('sampler type %r (only "ddim")' % (kind,))
+            if spec.get('steps') is None:
+                raise ValueError('sampler: "steps" is required')
+            self.set_sampler(spec['steps'], spec.get('eta', 0.0))
+
+    def set_sampler(self, steps=None, eta=0.0):
+        """Sample in `steps` reverse steps over a strided walk through the current schedule (DDIM; eta = 0: deterministic, eta = 1 and
+        steps = T: the ancestral sampler's coefficients) -- or, steps None, go back to the reference's ancestral loop.  What
+        p_sample_loop and everything on top of it (sample, super_resolution, the validation waves) runs; p_sample, p_mean_variance and
+        p_losses keep the schedule's own timesteps."""
+        if steps is None:
+            tabs, self.sampler = None, None
+        else:
+            if getattr(self, '_alphas_cumprod64', None) is None:
+                raise RuntimeError('set_sampler needs a noise schedule (set_new_noise_schedule first)')
+            tabs = sampler_tables(self._alphas_cumprod64, steps, eta)
+            self.sampler = dict(type='ddim', steps=int(steps), eta=float(eta))
+        dev = self.betas.device if hasattr(self, 'betas') else None
+        for k in _SAMPLER_TABLES:                # the float64 tables rounded once to fp32; the walk as int32 (what k_embed reads)
+            t = None if tabs is None else torch.tensor(tabs[k], dtype=torch.int32 if k == 'tau' else torch.float32).to(dev)
+            self.register_buffer('_sampler_' + k, t, persistent=False)
         self._loop_cache = {}
 
     # ---- small reference helpers (API completeness; not on the hot path) -------------------------
@@ -176,7 +256,8 @@ class EngineDiffusion(nn.Module):
         # registered with the captured graph, so they belong to the state and are re-seeded per loop
         un = self.denoise_fn
         key = (tuple(shape), None if cond_shape is None else tuple(cond_shape), str(dev), self.num_timesteps,
-               un.weights().data_ptr(), un.freq.data_ptr(), un.plan.generation, bool(item_streams))
+               un.weights().data_ptr(), un.freq.data_ptr(), un.plan.generation, bool(item_streams),
+               None if self.sampler is None else (self.sampler['steps'], self.sampler['eta']))
         st = self._loop_cache.get(key)
         if st is None:
             st = dict(img=torch.empty(shape, device=dev), z=torch.empty(shape, device=dev),
@@ -212,12 +293,28 @@ class EngineDiffusion(nn.Module):
         """One iteration of the loop: z ~ N(0, 1) (torch's graph-safe Philox), then sr3_reverse_step -- UNet forward with the p_sample
         update and the counter decrement inside the output conv's kernel (round 6; before: three calls, two more graph nodes).
         st['eps'] keeps the step's eps for the parity checks that read it."""
+        if self.sampler is not None:
+            return self._one_sampler_step(st, draw_noise)
         if draw_noise:
             self._draw(st['z'], st['gens'])
         tables = (self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod, self.posterior_mean_coef1,
                   self.posterior_mean_coef2, self._sigma)
         self.denoise_fn.reverse_step(st['img'], st['z'], tables, st['step'], cond=st['cond'], level_table=self._level_table,
                                      clip_denoised=True, eps_out=st['eps'], ws=st['ws'])
+
+    def _one_sampler_step(self, st, draw_noise=True):
+        """The same call over the sampler's tables: the counter is the step index j, the SR3 level comes from the walk's level table,
+        the DDPM timestep from the map tau.  eta = 0: nothing is drawn and the step gets no z (st['z_used'] records it) -- a graph
+        captured from it has no RNG node."""
+        noisy = self.sampler['eta'] > 0.0
+        st['z_used'] = noisy
+        if noisy and draw_noise:
+            self._draw(st['z'], st['gens'])
+        tables = (self._sampler_a, self._sampler_b, self._sampler_c1, self._sampler_c2, self._sampler_sigma)
+        t_map = self._sampler_tau if self.variant == 'ddpm' else None
+        st['tables'] = (tables, self._sampler_level, t_map)        # a captured graph bakes their addresses in: they live as long as the state
+        self.denoise_fn.reverse_step(st['img'], st['z'] if noisy else None, tables, st['step'], cond=st['cond'],
+                                     level_table=self._sampler_level, clip_denoised=True, eps_out=st['eps'], ws=st['ws'], t_map=t_map)
 
     def _capture(self, st):
         dev = st['img'].device
@@ -253,11 +350,12 @@ class EngineDiffusion(nn.Module):
         consumed at step i (the parity tests); `item_seeds` (one int per image of the batch) gives every image its own noise
         stream -- x_T and every step's z of image i come from a generator seeded with item_seeds[i], so the image's chain does
         not depend on which batch it rides in (sr3_hip.dist.ValWave batches the validation items the reference's infer.py /
-        sr.py feed one by one, infer.py:67-71)."""
+        sr.py feed one by one, infer.py:67-71).  Under a sampler (set_sampler) the loop takes its S steps instead of T, i counts
+        the step index S-1 .. 0 (what `noise_seq` and the snapshot stride 1 | S // 10 go by), and eta = 0 draws x_T only."""
         dev = self.betas.device
         if dev.type != 'cuda':
             raise L.Sr3Error('p_sample_loop needs the model on a GPU (set gpu_ids); there is no CPU fallback')
-        T = self.num_timesteps
+        T = self.num_timesteps if self.sampler is None else self.sampler['steps']      # iterations of the loop
         inter = 1 | (T // 10)
         if not self.conditional:
             shape = tuple(x_in)

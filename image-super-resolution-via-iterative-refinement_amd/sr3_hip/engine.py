@@ -183,9 +183,12 @@ def _check_same_size(x, cond):
         raise L.Sr3Error('conditioning image %s and input %s differ in batch or size' % (tuple(cond.shape), tuple(x.shape)))
 
 
-def reverse_step(plan, arena, freq, ws, x, z, tables, step2, cond=None, level_table=None, clip_denoised=True, eps_out=None):
-    """One whole reverse step in place on `x` (sr3_reverse_step): eps = UNet(cat([cond, x], 1), level(t)); x <- p_sample update;
-    t <- t - 1, with t = step2[1] (int32 tensor of two).  `tables` = (a, b, c1, c2, sigma) schedule tables on the device."""
+def reverse_step(plan, arena, freq, ws, x, z, tables, step2, cond=None, level_table=None, clip_denoised=True, eps_out=None,
+                 t_map=None):
+    """One whole reverse step in place on `x` (sr3_reverse_step_ex): eps = UNet(cat([cond, x], 1), level(t)); x <- p_sample update;
+    t <- t - 1, with t = step2[1] (int32 tensor of two).  `tables` = (a, b, c1, c2, sigma) schedule tables on the device, indexed
+    by t like `level_table`.  `z` None: no noise is read (= 0).  `t_map` (int32 device tensor, one entry per value t takes): the
+    timestep the DDPM UNet is conditioned on at counter value t -- a sampler's walk through a subset of the timesteps; None: t."""
     if not x.is_cuda or not x.is_contiguous() or x.dtype != torch.float32:
         raise L.Sr3Error('reverse_step needs a contiguous fp32 GPU tensor (got %s, %s); there is no CPU fallback' % (x.device, x.dtype))
     B = x.shape[0]
@@ -203,9 +206,11 @@ def reverse_step(plan, arena, freq, ws, x, z, tables, step2, cond=None, level_ta
     wsbuf, need = ws.get(plan, B, x.device)
     stream = torch.cuda.current_stream(x.device).cuda_stream
     a, b, c1, c2, sg = tables
-    L.check(plan.lib.sr3_reverse_step(plan.handle, L.ptr(x), L.ptr(cond), cc, L.ptr(freq), L.ptr(level_table), L.ptr(step2),
-                                      L.ptr(arena), L.ptr(wsbuf), need, L.ptr(z), L.ptr(a), L.ptr(b), L.ptr(c1), L.ptr(c2), L.ptr(sg),
-                                      1 if clip_denoised else 0, L.ptr(eps_out), B, C.c_void_p(stream)))
+    if t_map is not None and (t_map.dtype != torch.int32 or not t_map.is_contiguous() or t_map.device != x.device):
+        raise L.Sr3Error('t_map must be a contiguous int32 tensor on the device of x')
+    L.check(plan.lib.sr3_reverse_step_ex(plan.handle, L.ptr(x), L.ptr(cond), cc, L.ptr(freq), L.ptr(level_table), L.ptr(step2),
+                                         L.ptr(arena), L.ptr(wsbuf), need, L.ptr(z), L.ptr(a), L.ptr(b), L.ptr(c1), L.ptr(c2), L.ptr(sg),
+                                         1 if clip_denoised else 0, L.ptr(eps_out), B, C.c_void_p(stream), L.ptr(t_map)))
     return x
 
 

@@ -277,11 +277,26 @@ int sr3_step_decrement(int* step_dev, void* stream);
  *                 completion; step2_dev[0] is scratch (the step's first kernel copies t there for its last one).  t must stay >= 0.
  *   level_table : SR3: level = level_table[t + 1] (sqrt_alphas_cumprod_prev); DDPM: ignored (the timestep is t)
  *   z_nchw      : the step's noise or NULL (= 0); tab_*: the schedule tables of sr3_p_sample_step (sigma[0] = 0 replaces `t > 0`)
- *   eps_out_nchw: NULL, or where to also store eps (parity checks) */
+ *   eps_out_nchw: NULL, or where to also store eps (parity checks)
+ * The counter is a STEP INDEX: tab_* and level_table are indexed by it, and nothing else in the step reads it.  In the reference's
+ * loop the index is the training timestep; a sampler that walks a subset of the timesteps passes tables built for its walk
+ * (one row per step taken) and counts its steps down instead -- see sr3_reverse_step_ex for the DDPM variant. */
 int sr3_reverse_step(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,
                      const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
                      const float* z_nchw, const float* tab_a, const float* tab_b, const float* tab_c1, const float* tab_c2,
                      const float* tab_sigma, int clip_denoised, float* eps_out_nchw, int batch, void* stream);
+/* sr3_reverse_step for a walk through a subset of the timesteps (a strided DDIM sampler: S steps over tau[0] < ... < tau[S-1]).
+ *   t_map : device array, one int per step index: the timestep the DDPM UNet is conditioned on when the counter reads that index
+ *           (t_map[j] = tau[j]; the embedding kernel reads t_map[step2_dev[1]]).  NULL: index = timestep, i.e. sr3_reverse_step.
+ *           The SR3 variant ignores it: its level_table, indexed by the step index (level_table[j + 1] = the level of tau[j]), already
+ *           is the map.
+ * tab_* and level_table are indexed by the step index j, exactly as in sr3_reverse_step; the caller sets step2_dev[1] = S - 1 before
+ * the first step and fills the tables with the coefficients of its update rule in the tail's form
+ *   x0 = clamp(a[j] x - b[j] eps) ; x = c1[j] x0 + c2[j] x + sigma[j] z. */
+int sr3_reverse_step_ex(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,
+                        const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
+                        const float* z_nchw, const float* tab_a, const float* tab_b, const float* tab_c1, const float* tab_c2,
+                        const float* tab_sigma, int clip_denoised, float* eps_out_nchw, int batch, void* stream, const int* t_map);
 
 /* q_sample (model/sr3_modules/diffusion.py:212-219; model/ddpm_modules/diffusion.py:259-267):
  * out = ca[b] * x0 + cb[b] * z */
