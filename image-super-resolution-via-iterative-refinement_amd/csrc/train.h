@@ -31,6 +31,16 @@ int adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, 
 // arguments are checked by the ABI entry (sr3_adam_ema_step)
 int adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float b1, float b2, float eps,
                   int step, float ema_decay, int ema_mode, hipStream_t st);
+// adam_ema_step on g * scale4[1] (a product rounded on its own), skipped as a whole -- nothing is written -- when scale4[2] == 0;
+// scale4: the four device floats grad_norm / grad_accumulate write.  Arguments are checked by the ABI entry (sr3_adam_ema_step_scaled)
+int adam_ema_step_scaled(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float b1, float b2,
+                         float eps, int step, float ema_decay, int ema_mode, const float* scale4, hipStream_t st);
+// Global L2 norm of g[0..n) on a fixed grid in fixed order (train_kernels.hip, T13): out4 = {norm, coef, finite flag, 0},
+// coef = min(1, max_norm / (norm + 1e-6)) (1 when max_norm <= 0); part: grad_norm_scratch_bytes(n) of doubles
+size_t grad_norm_scratch_bytes(size_t n);
+int grad_norm(const float* g, size_t n, float max_norm, double* part, float* out4, hipStream_t st);
+// acc = first ? g : acc + g; out4 != nullptr: also what grad_norm(acc) would write, from the same pass (bit-equal to it)
+int grad_accumulate(float* acc, const float* g, size_t n, bool first, float max_norm, double* part, float* out4, hipStream_t st);
 int nchw_to_nhwc_pad(const float* a, int Ca, const float* b, int Cb, int B, int HW, int CP, float* out, hipStream_t st);
 
 // Weight gradient of a conv (wgrad.hip): dw[n][tap][c] = sum_m dy[m][n] * a_tap[m][c], a = prologue(x0|x1)

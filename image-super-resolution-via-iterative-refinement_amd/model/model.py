@@ -47,8 +47,12 @@ class DDPM(BaseModel):
             from sr3_hip.optim import make_optimizer
             if self.ema_opt is not None:
                 self.netG.denoise_fn.enable_ema()         # starts as the initial weights; load_network replaces it on a resume
+            # engine keys of train.optimizer (absent in the reference's configs; absent = today's step): `accumulate` K micro-batches per
+            # optimizer step, `clip_grad_norm` the global gradient norm to clip to (sr3_hip/optim.py)
             self.optG = make_optimizer(self.netG, lr=opt['train']['optimizer']['lr'],
-                                       warmup_steps=int(opt['train']['optimizer'].get('warmup_steps') or 0), ema=self.ema_opt)
+                                       warmup_steps=int(opt['train']['optimizer'].get('warmup_steps') or 0), ema=self.ema_opt,
+                                       accumulate=opt['train']['optimizer'].get('accumulate'),
+                                       clip_grad_norm=opt['train']['optimizer'].get('clip_grad_norm'))
             self.log_dict = OrderedDict()
         self.load_network()
         # data parallel: equalise the replicas once (each process initialised its own weights; a resumed checkpoint is
@@ -71,7 +75,11 @@ class DDPM(BaseModel):
         # (the reference's `l_pix.sum() / int(b*c*h*w)` over DataParallel's gathered per-replica sums, :52-53)
         l_pix = l_pix.sum() / int(b * c * h * w * _dist.dp_world_size())
         self.optG.step()
-        self.log_dict['l_pix'] = l_pix.item()
+        gn = self.optG.last_grad_norm()
+        if gn is None:
+            self.log_dict['l_pix'] = l_pix.item()
+        else:       # clip_grad_norm: the norm of the last optimizer step taken, read in the same device-to-host copy as the loss
+            self.log_dict['l_pix'], self.log_dict['grad_norm'] = torch.stack([l_pix, gn]).tolist()
 
     def _sampling_weights(self):
         """Train phase with EMA enabled: validation and sampling run on the EMA weights (everything below netG's sampling loops,

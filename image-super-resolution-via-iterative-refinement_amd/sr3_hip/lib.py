@@ -90,6 +90,10 @@ SIGNATURES = {
                             _I, _P, _P, _I, _P]),
     'sr3_adam_step': (_I, [_P, _P, _P, _P, _Z, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P]),
     'sr3_adam_ema_step': (_I, [_P, _P, _P, _P, _P, _Z, C.c_float, C.c_float, C.c_float, C.c_float, _I, C.c_float, _I, _P]),
+    'sr3_adam_ema_step_scaled': (_I, [_P, _P, _P, _P, _P, _Z, C.c_float, C.c_float, C.c_float, C.c_float, _I, C.c_float, _I, _P, _P]),
+    'sr3_grad_norm_scratch_bytes': (_Z, [_Z]),
+    'sr3_grad_norm': (_I, [_P, _Z, C.c_float, _P, _Z, _P, _P]),
+    'sr3_grad_accumulate': (_I, [_P, _P, _Z, _I, C.c_float, _P, _Z, _P, _P]),
     'sr3_conv_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P,
                           _I, _I, _P, _Z, _P]),
     'sr3_block_conv_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I,

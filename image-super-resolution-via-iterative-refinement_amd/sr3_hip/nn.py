@@ -51,6 +51,8 @@ class EngineUNet(nn.Module):
         # (ema_state_dict).  Its address never changes (captured reverse loops bake it in); `use_weights` selects which arena runs
         self.ema_arena = None
         self._use_ema = False
+        # config train.optimizer.accumulate (set by EngineAdam): micro-batches per optimizer step; train_step scales its gradients by 1 / K
+        self.accumulate = 1
         self.reset_parameters()
 
     # ---- initialisation: same distributions AND same RNG consumption order as the reference ----
@@ -280,21 +282,44 @@ class EngineUNet(nn.Module):
         # data parallel (one process per GPU): gradients are summed over ranks, so the 1/(b c h w) factor
         # uses the GLOBAL batch (model/model.py:52-53 under DataParallel); buckets reduce as they get ready
         import torch.distributed as tdist
-        from . import dist as _dist
-        dp = _dist.dp_world_size() > 1 or ((getattr(self, 'force_dp', False) or _dist.force_collectives)
-                                          and tdist.is_available() and tdist.is_initialized())
+        dp = self.dp_reducing()
         red, marks = None, (0, None, None)
+        if self.accumulate > 1:        # the optimizer applies the sum of K micro-batch gradients: their mean
+            grad_scale = grad_scale / self.accumulate
         if dp:
-            from .dist import GradReducer
-            red = getattr(self, '_reducer', None)
-            if red is None or red.device != dev:
-                red = self._reducer = GradReducer(self.arena.numel(), dev, tdist)
+            red = self._grad_reducer(dev)
             grad_scale = grad_scale / tdist.get_world_size()
-            marks = red.mark_args()
+            if self.accumulate == 1:
+                marks = red.mark_args()
         self._engine_train_step(hr, cond, z, ca, cb, level, tstep, grad_scale, p_drop, drop_seed, marks, loss)
         if dp:
-            red.reduce(self.grad_arena, extra=[loss])
+            if self.accumulate == 1:
+                red.reduce(self.grad_arena, extra=[loss])
+            else:                      # the arena is reduced once per optimizer step, accumulated (reduce_arena): only the loss here
+                tdist.all_reduce(loss, op=tdist.ReduceOp.SUM)
         return loss[0]
+
+    def dp_reducing(self):
+        """True when train_step's gradients are summed over data-parallel ranks (more than one, or a forced 1-rank job)."""
+        import torch.distributed as tdist
+        from . import dist as _dist
+        return _dist.dp_world_size() > 1 or ((getattr(self, 'force_dp', False) or _dist.force_collectives)
+                                             and tdist.is_available() and tdist.is_initialized())
+
+    def _grad_reducer(self, dev):
+        import torch.distributed as tdist
+        from .dist import GradReducer
+        red = getattr(self, '_reducer', None)
+        if red is None or red.device != dev:
+            red = self._reducer = GradReducer(self.arena.numel(), dev, tdist)
+        return red
+
+    def reduce_arena(self, arena):
+        """Sum-all-reduce an arena-shaped tensor over the ranks, bucket by bucket on the current stream: the accumulated gradient
+        of K > 1 micro-batches, once per optimizer step (EngineAdam).  Not overlapped with the last backward."""
+        red = self._grad_reducer(arena.device)
+        for lo, hi in red.buckets:
+            red.dist.all_reduce(arena[lo:hi], op=red.dist.ReduceOp.SUM)
 
     def _engine_train_step(self, hr, cond, z, ca, cb, level, tstep, grad_scale, p_drop, drop_seed, marks, loss):
         """The sr3_train_step call itself (q_sample -> UNet forward -> loss -> backward, `marks` = the gradient-ready

@@ -357,6 +357,39 @@ int sr3_adam_ema_step(float* params, const float* grads, float* exp_avg, float* 
                       float lr, float beta1, float beta2, float eps, int step, float ema_decay, int ema_mode,
                       void* stream);
 
+/* Global L2 norm of the gradient arena, for clipping by it (config train.optimizer.clip_grad_norm): the device-side half of
+ * torch.nn.utils.clip_grad_norm_(params, max_norm), which the reference never calls -- no counterpart there.  No host
+ * synchronisation: four floats are written to out4_dev (16-byte aligned, caller-owned):
+ *   [0] norm = (float)sqrt(sum g^2), the sum in double;  [1] coef = min(1, max_norm / (norm + 1e-6f)) in fp32 (torch's clip
+ *   coefficient), 1 when max_norm <= 0 (norm only);  [2] 1.0f when the norm is finite, else 0.0f;  [3] 0.
+ * The grid is a compile-time constant (at most 512 blocks of 256 threads) and every sum has one order (thread: stride order;
+ * wave: xor shuffle; block: waves in order; blocks in index order), no atomics: the same bits on every run and every device.
+ * scratch: the blocks' partial sums, 8-byte aligned; the byte count comes from the query below (at most 4096).
+ * SR3_E_BADARG (nothing is launched, the message names the argument): NULL grads / scratch / out4_dev, n % 4 != 0, a NaN
+ * max_norm, scratch_bytes too small.  SR3_E_ALIGN: grads or out4_dev not 16-byte aligned, scratch not 8-byte aligned. */
+size_t sr3_grad_norm_scratch_bytes(size_t n);
+int sr3_grad_norm(const float* grads, size_t n, float max_norm, void* scratch, size_t scratch_bytes, float* out4_dev,
+                  void* stream);
+
+/* Gradient accumulation over micro-batches (config train.optimizer.accumulate; the reference steps once per loader batch -- no
+ * counterpart; what `loss.backward()` called K times without zero_grad() does to .grad in torch): acc = first ? g : acc + g,
+ * one fp32 add per element.  out4_dev != NULL: the norm / coef / flag of the RESULT as above, from the same pass -- bit-equal
+ * to the stand-alone norm entry on acc afterwards (same grid, same order); scratch / scratch_bytes / max_norm are read only
+ * then.  SR3_E_BADARG: NULL acc / g, n % 4 != 0, and with out4_dev the refusals of the norm entry.  SR3_E_ALIGN as there. */
+int sr3_grad_accumulate(float* acc, const float* g, size_t n, int first, float max_norm, void* scratch,
+                        size_t scratch_bytes, float* out4_dev, void* stream);
+
+/* sr3_adam_ema_step with the gradient scaled by scale4_dev[1] and the whole update skipped when scale4_dev[2] == 0 (scale4_dev:
+ * the four floats the two entries above write; no counterpart in the reference, which neither clips nor guards).  The scaled
+ * gradient is an fp32 product rounded on its own, so with coef == 1.0f params / exp_avg / exp_avg_sq / ema come out bit-identical
+ * to the unscaled entry, and with coef < 1 bit-identical to it on a gradient multiplied by coef in fp32 beforehand.  Flag 0 (a
+ * non-finite norm): nothing is written, every buffer keeps its bits -- where torch's clip_grad_norm_ would write NaN.
+ * Arguments and refusals as the unscaled entry; in addition SR3_E_BADARG for a NULL scale4_dev and SR3_E_ALIGN when it is not
+ * 16-byte aligned.  `step` is the host's count: it advances on a skipped step too (no host synchronisation). */
+int sr3_adam_ema_step_scaled(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, size_t n,
+                             float lr, float beta1, float beta2, float eps, int step, float ema_decay, int ema_mode,
+                             const float* scale4_dev, void* stream);
+
 /* ---- per-op entry points (unit tests, micro-benchmarks) ------------------------------------ */
 
 /* Block / Conv2d / Downsample / Upsample / res_conv / qkv / out as one implicit-GEMM call:
