@@ -14,6 +14,10 @@ hipGraph and replayed T times; snapshots are graph-external device copies.
 Sampler (engine extension, `"sampler": {"type": "ddim", "steps": S, "eta": e}` in the schedule dict or `set_sampler`): the same
 captured step replayed S times over a strided walk through the schedule -- `sampler_tables` restates the DDIM update in the fused
 tail's linear form, so a sampler is five other coefficient tables, another level table and (DDPM) a step-index -> timestep map.
+
+Tiling (engine extension, `"tiling": {"tile": 128 | [th, tw], "overlap": 32, "batch": 8}` next to it, or `set_tiling`): an image larger
+than the tile is sampled as one chain whose eps comes from overlapping tiles of that size -- per step: sr3_tile_gather + UNet forward
+per chunk of tiles, then sr3_tiled_step (blend + p_sample update + counter decrement) on the whole image (`p_sample_loop_tiled`).
 """
 import ctypes as C
 
@@ -23,6 +27,7 @@ from torch import nn
 
 from . import engine as E
 from . import lib as L
+from . import tiling as TL
 
 
 def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2, cosine_s=8e-3):
@@ -114,6 +119,7 @@ class EngineDiffusion(nn.Module):
         self.show_progress = True
         self._loop_cache = {}
         self.sampler = None            # None: the reference's ancestral loop; else {'type': 'ddim', 'steps': S, 'eta': e} (set_sampler)
+        self.tiling = None             # None: whole-image steps; else {'tile': (th, tw), 'overlap': o, 'batch': n | None} (set_tiling)
         self.max_cached_loops = 3      # reverse-loop states (buffers + workspace + captured graph) kept, one per (shape, launch list)
         # schedule_opt is accepted and ignored exactly like the reference ctor (diffusion.py:80-82)
 
@@ -153,6 +159,7 @@ class EngineDiffusion(nn.Module):
         self.register_buffer('_sigma', sig.to(device), persistent=False)
         self._alphas_cumprod64 = ac                                              # what a sampler's tables are computed from
         self._loop_cache = {}
+        self.tiling = None                                                       # (this phase's own "tiling" key is read below)
         # engine key of the schedule dict: "sampler": {"type": "ddim", "steps": S, "eta": e}; absent / null: the ancestral loop
         spec = schedule_opt.get('sampler') if hasattr(schedule_opt, 'get') else None
         if spec is None:
@@ -164,6 +171,13 @@ class EngineDiffusion(nn.Module):
             if spec.get('steps') is None:
                 raise ValueError('sampler: "steps" is required')
             self.set_sampler(spec['steps'], spec.get('eta', 0.0))
+        # engine key next to it: "tiling": {"tile": 128 | [th, tw], "overlap": 32, "batch": 8}; absent / null: whole-image steps
+        spec = schedule_opt.get('tiling') if hasattr(schedule_opt, 'get') else None
+        if spec is None:
+            self.set_tiling(None)
+        else:
+            t = TL.parse_tiling(spec, self.denoise_fn.plan.divisor)
+            self.set_tiling(t['tile'], t['overlap'], t['batch'])
 
     def set_sampler(self, steps=None, eta=0.0):
         """Sample in `steps` reverse steps over a strided walk through the current schedule (DDIM; eta = 0: deterministic, eta = 1 and
@@ -176,12 +190,32 @@ class EngineDiffusion(nn.Module):
             if getattr(self, '_alphas_cumprod64', None) is None:
                 raise RuntimeError('set_sampler needs a noise schedule (set_new_noise_schedule first)')
             tabs = sampler_tables(self._alphas_cumprod64, steps, eta)
+            self._check_tiled_sampler(True, getattr(self, 'tiling', None))
             self.sampler = dict(type='ddim', steps=int(steps), eta=float(eta))
         dev = self.betas.device if hasattr(self, 'betas') else None
         for k in _SAMPLER_TABLES:                # the float64 tables rounded once to fp32; the walk as int32 (what k_embed reads)
             t = None if tabs is None else torch.tensor(tabs[k], dtype=torch.int32 if k == 'tau' else torch.float32).to(dev)
             self.register_buffer('_sampler_' + k, t, persistent=False)
         self._loop_cache = {}
+
+    def set_tiling(self, tile=None, overlap=0, batch=None):
+        """Sample images larger than `tile` (an int, or (th, tw)) as one chain over overlapping tiles of that size, neighbours sharing
+        at least `overlap` pixels, `batch` tiles per UNet forward (None: all of them, at most 16) -- or, tile None, go back to
+        whole-image steps.  What p_sample_loop and everything on top of it runs for an input larger than the tile on either axis; an
+        input the tile covers takes today's loop."""
+        if tile is None:
+            self.tiling = None
+        else:
+            t = TL.parse_tiling(dict(tile=tile, overlap=overlap, batch=batch), self.denoise_fn.plan.divisor)
+            self._check_tiled_sampler(self.sampler is not None, t)
+            self.tiling = t
+        self._loop_cache = {}
+
+    def _check_tiled_sampler(self, sampler, tiling):
+        if sampler and tiling is not None and self.variant == 'ddpm':
+            raise NotImplementedError('tiled sampling of the DDPM variant under a DDIM sampler: the tiles run through sr3_unet_forward, '
+                                      'which has no step-index -> timestep map (t_map); use the ancestral sampler (set_sampler(None)) '
+                                      'or whole-image steps (set_tiling(None))')
 
     # ---- small reference helpers (API completeness; not on the hot path) -------------------------
     def predict_start_from_noise(self, x_t, t, noise):
@@ -249,7 +283,7 @@ class EngineDiffusion(nn.Module):
         return out
 
     # ---- the reverse loop ------------------------------------------------------------------------
-    def _loop_state(self, shape, cond_shape, dev, item_streams=False):
+    def _loop_state(self, shape, cond_shape, dev, item_streams=False, tiles=None):
         # a captured graph bakes in the arena (the one in use: EngineUNet.use_weights), the freq table and the workspace pointer and
         # the plan's launch list: key on all of them (plan.generation changes with every set_option); the workspace is private to the state.
         # item_streams: one torch generator per image of the batch (`item_seeds` of p_sample_loop) -- the generators are
@@ -257,7 +291,8 @@ class EngineDiffusion(nn.Module):
         un = self.denoise_fn
         key = (tuple(shape), None if cond_shape is None else tuple(cond_shape), str(dev), self.num_timesteps,
                un.weights().data_ptr(), un.freq.data_ptr(), un.plan.generation, bool(item_streams),
-               None if self.sampler is None else (self.sampler['steps'], self.sampler['eta']))
+               None if self.sampler is None else (self.sampler['steps'], self.sampler['eta']),
+               None if tiles is None else tiles['key'])      # tiled loop: ((tile_h, tile_w), overlap, tile_batch); the geometry is the tile's
         st = self._loop_cache.get(key)
         if st is None:
             st = dict(img=torch.empty(shape, device=dev), z=torch.empty(shape, device=dev),
@@ -265,6 +300,8 @@ class EngineDiffusion(nn.Module):
                       cond=None if cond_shape is None else torch.empty(cond_shape, device=dev),
                       step=torch.zeros(2, dtype=torch.int32, device=dev), graph=None, ws=E.Workspace(),      # [scratch, t]
                       gens=[torch.Generator(device=dev) for _ in range(shape[0])] if item_streams else None)
+            if tiles is not None:
+                self._tile_buffers(st, tiles, shape, cond_shape, dev)
             # keep the states of a few image sizes alive (a folder of mixed sizes alternates between them without recapturing);
             # what was built for another arena / schedule / set of plan options can never be hit again: dropped
             # (with EMA weights the model has two arenas, and a state built on either can be hit again)
@@ -277,6 +314,65 @@ class EngineDiffusion(nn.Module):
         else:
             self._loop_cache[key] = self._loop_cache.pop(key)      # most recently used last
         return st
+
+    def _tile_buffers(self, st, tiles, shape, cond_shape, dev):
+        """What a tiled loop's state holds besides the whole-image tensors: the grid's origins and windows on the device, the chunk
+        list, one chunk of image tiles, every tile of the conditioning image and of eps, and a workspace sized for the largest chunk."""
+        g = tiles['grid']
+        total = shape[0] * g.n_tiles
+        cb = min(tiles['batch'], total)
+        st['grid'] = g
+        st['chunks'] = [(f, min(cb, total - f)) for f in range(0, total, cb)]      # the last one may be short: it runs at its own batch
+        st['oy'] = torch.tensor(g.oy, dtype=torch.int32, device=dev)
+        st['ox'] = torch.tensor(g.ox, dtype=torch.int32, device=dev)
+        st['oy_host'] = (C.c_int * g.ny)(*g.oy)
+        st['ox_host'] = (C.c_int * g.nx)(*g.ox)
+        st['wy'] = torch.from_numpy(g.wy).to(dev)
+        st['wx'] = torch.from_numpy(g.wx).to(dev)
+        st['x_tiles'] = torch.empty((cb, shape[1], g.th, g.tw), device=dev)
+        st['cond_tiles'] = None if cond_shape is None else torch.empty((total, cond_shape[1], g.th, g.tw), device=dev)
+        st['eps_tiles'] = torch.empty((total, shape[1], g.th, g.tw), device=dev)
+        # one buffer for every chunk size: a captured graph bakes its address in, so it must not grow between two chunks
+        plan = self.denoise_fn.plan
+        need = max(plan.workspace_bytes(n) for n in sorted({n for _, n in st['chunks']}))
+        st['ws'].buf = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+
+    def _gather_tiles(self, st, src, dst, first, n):
+        """dst[:n] <- the tiles first .. first + n - 1 (global tile order) of the image batch src (sr3_tile_gather)."""
+        g = st['grid']
+        B, Cc, H, W = src.shape
+        L.check(L.load().sr3_tile_gather(L.ptr(src), B, Cc, H, W, L.ptr(st['oy']), g.ny, L.ptr(st['ox']), g.nx, int(first), int(n),
+                                         g.th, g.tw, L.ptr(dst), self._stream(src.device)))
+
+    def _one_tiled_step(self, st, draw_noise=True):
+        """One iteration of the tiled loop: z on the full image; per chunk of tiles, gather out of the running image and one UNet
+        forward at the tile geometry (level / timestep from the device counter); then the fused tail on the full image -- blend of the
+        tiles' eps, p_sample update, counter decrement (sr3_tiled_step).  st['eps'] keeps the blended eps."""
+        if self.sampler is None:
+            noisy = True
+            tables = (self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod, self.posterior_mean_coef1,
+                      self.posterior_mean_coef2, self._sigma)
+            level = self._level_table
+        else:
+            noisy = self.sampler['eta'] > 0.0
+            tables = (self._sampler_a, self._sampler_b, self._sampler_c1, self._sampler_c2, self._sampler_sigma)
+            level = self._sampler_level
+        st['z_used'] = noisy
+        st['tables'] = (tables, level)         # a captured graph bakes their addresses in: they live as long as the state
+        if noisy and draw_noise:
+            self._draw(st['z'], st['gens'])
+        g, img = st['grid'], st['img']
+        for first, n in st['chunks']:
+            xt = st['x_tiles'][:n]
+            self._gather_tiles(st, img, xt, first, n)
+            self.denoise_fn(xt, None, cond=None if st['cond_tiles'] is None else st['cond_tiles'][first:first + n],
+                            level_table=level, step_dev=st['step'][1:], out=st['eps_tiles'][first:first + n], ws=st['ws'])
+        B, Cc, H, W = img.shape
+        a, b, c1, c2, sg = tables
+        L.check(L.load().sr3_tiled_step(L.ptr(img), L.ptr(st['eps_tiles']), B, Cc, H, W, L.ptr(st['oy']), g.ny, L.ptr(st['ox']), g.nx,
+                                        L.ptr(st['wy']), L.ptr(st['wx']), g.th, g.tw, st['oy_host'], st['ox_host'],
+                                        L.ptr(st['z']) if noisy else None, L.ptr(a), L.ptr(b), L.ptr(c1), L.ptr(c2), L.ptr(sg),
+                                        L.ptr(st['step']), 1, L.ptr(st['eps']), self._stream(img.device)))
 
     @staticmethod
     def _draw(t, gens):
@@ -293,6 +389,8 @@ class EngineDiffusion(nn.Module):
         """One iteration of the loop: z ~ N(0, 1) (torch's graph-safe Philox), then sr3_reverse_step -- UNet forward with the p_sample
         update and the counter decrement inside the output conv's kernel (round 6; before: three calls, two more graph nodes).
         st['eps'] keeps the step's eps for the parity checks that read it."""
+        if st.get('grid') is not None:
+            return self._one_tiled_step(st, draw_noise)
         if self.sampler is not None:
             return self._one_sampler_step(st, draw_noise)
         if draw_noise:
@@ -346,6 +444,27 @@ class EngineDiffusion(nn.Module):
 
     @torch.no_grad()
     def p_sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None):
+        """The reverse loop (`_sample_loop`); with tiling set (set_tiling / the "tiling" key) an input larger than the tile on either axis
+        goes through the tiled loop instead."""
+        t = self.tiling
+        if t is not None:
+            shape = tuple(x_in) if not self.conditional else tuple(x_in.shape)
+            if len(shape) == 4 and (shape[2] > t['tile'][0] or shape[3] > t['tile'][1]):
+                return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, tiling=t)
+        return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds)
+
+    @torch.no_grad()
+    def p_sample_loop_tiled(self, x_in, continous=False, *, tile, overlap, tile_batch=None, x_T=None, noise_seq=None, item_seeds=None):
+        """p_sample_loop as ONE chain over overlapping tiles: at every step the UNet predicts eps on tiles of size `tile` (int or
+        (th, tw); an axis the tile covers has one tile of the image's size), `tile_batch` of them per forward (None: all, at most 16),
+        the predictions are blended by the separable ramp of sr3_hip.tiling.axis_window and one p_sample update moves the whole image.
+        Noise is drawn on the full image, so x_T / noise_seq / item_seeds, the return shapes and the snapshot stride are
+        p_sample_loop's.  The result is not the whole-image result and is not meant to be: every forward sees the token count and the
+        normalisation statistics of the training size.  With tile >= image on both axes it IS the whole-image loop, bit for bit."""
+        t = TL.parse_tiling(dict(tile=tile, overlap=overlap, batch=tile_batch), self.denoise_fn.plan.divisor)
+        return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, tiling=t)
+
+    def _sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None, tiling=None):
         """sr3 diffusion.py:176-200 / ddpm :200-230.  Extensions: `x_T` injects the initial draw, `noise_seq[i]` the noise
         consumed at step i (the parity tests); `item_seeds` (one int per image of the batch) gives every image its own noise
         stream -- x_T and every step's z of image i come from a generator seeded with item_seeds[i], so the image's chain does
@@ -373,8 +492,18 @@ class EngineDiffusion(nn.Module):
             raise L.Sr3Error('p_sample_loop: a (B, C, H, W) image or shape is expected (got %s)' % (shape,))
         # the image size comes from the input, as in the reference (`shape = x.shape`); the launch list -- and with it
         # plan.generation, part of the state's key -- follows it
-        self.denoise_fn.plan.set_geometry(shape[2], shape[3])
-        st = self._loop_state(shape, None if cond is None else shape, dev, item_streams=item_seeds is not None)
+        tiles = None
+        if tiling is not None:
+            # tiled: the plan runs at the TILE's geometry; everything is validated here, before anything is written
+            self._check_tiled_sampler(self.sampler is not None, tiling)
+            (th, tw), o = tiling['tile'], tiling['overlap']
+            grid = TL.TileGrid(shape[2], shape[3], th, tw, o, self.denoise_fn.plan.divisor)
+            batch = min(16, shape[0] * grid.n_tiles) if tiling['batch'] is None else int(tiling['batch'])
+            tiles = dict(grid=grid, batch=batch, key=((th, tw), o, batch))
+            self.denoise_fn.plan.set_geometry(grid.th, grid.tw)
+        else:
+            self.denoise_fn.plan.set_geometry(shape[2], shape[3])
+        st = self._loop_state(shape, None if cond is None else shape, dev, item_streams=item_seeds is not None, tiles=tiles)
         self.denoise_fn.ensure_derived()       # a replayed graph does not pass through EngineUNet.forward
         if item_seeds is not None:
             for g, v in zip(st['gens'], item_seeds):
@@ -387,6 +516,8 @@ class EngineDiffusion(nn.Module):
             st['img'].copy_(torch.randn(shape, device=dev))
         if cond is not None:
             st['cond'].copy_(cond)
+            if tiles is not None:              # the conditioning image does not change: cut into tiles once
+                self._gather_tiles(st, st['cond'], st['cond_tiles'], 0, st['cond_tiles'].shape[0])
         st['step'].fill_(T - 1)                # (slot 1 = t of the next step; slot 0 is the step's scratch copy)
         n_snap = sum(1 for i in range(T) if i % inter == 0)
         B = shape[0]

@@ -298,6 +298,40 @@ int sr3_reverse_step_ex(sr3_plan* plan, float* x_nchw, const float* cond_nchw, i
                         const float* z_nchw, const float* tab_a, const float* tab_b, const float* tab_c1, const float* tab_c2,
                         const float* tab_sigma, int clip_denoised, float* eps_out_nchw, int batch, void* stream, const int* t_map);
 
+/* ---- tiled sampling (engine extension; no reference counterpart) ------------------------------
+ * An image larger than the training size is sampled as ONE chain whose eps comes from overlapping tiles of the training size: per
+ * reverse step the tiles are cut out of the running image (sr3_tile_gather), the UNet predicts eps on batches of them
+ * (sr3_unet_forward with step_dev = step2_dev + 1) and sr3_tiled_step blends the predictions and applies the p_sample update to the
+ * whole image.  Tile order: (b * ny + iy) * nx + ix; tile (iy, ix) is the th x tw window at (oy[iy], ox[ix]).  Origins are any
+ * integers in [0, H - th] / [0, W - tw] (no alignment); what the kernels read from the device arrays is clamped into that range. */
+
+/* dst_tiles[i] = the window of tile first_tile + i, i < n_tiles (a contiguous range of the tile order: it may start and end inside
+ * an image), all `channels` channels: [n_tiles, channels, th, tw] out of src_nchw [batch, channels, height, width].  Bit copy.
+ * oy_dev [ny], ox_dev [nx]: device int arrays.  SR3_E_BADARG: NULL pointer, non-positive size, th > height, tw > width, a tile range
+ * outside [0, batch * ny * nx); SR3_E_UNSUPPORTED: batch * channels * height * width >= 2^31. */
+int sr3_tile_gather(const float* src_nchw, int batch, int channels, int height, int width, const int* oy_dev, int ny,
+                    const int* ox_dev, int nx, int first_tile, int n_tiles, int th, int tw, float* dst_tiles, void* stream);
+
+/* The tail of one tiled reverse step, in place on x_nchw [batch, channels, height, width]:
+ *   eps(p) = the covering tile's value unchanged where ONE tile covers pixel p (no multiply, no divide), else
+ *            (sum_i wy_i wx_i eps_i(p)) / (sum_i wy_i wx_i) over the covering tiles in ascending tile index, every product, sum and
+ *            the quotient rounded separately in fp32; wy_i = wy_dev[y - oy[iy]], wx_i = wx_dev[x - ox[ix]]  (wy_dev [th], wx_dev [tw] > 0)
+ *   x0 = a[j] x - b[j] eps ; clamp(-1, 1) if clip_denoised ; x = c1[j] x0 + c2[j] x + sigma[j] z      (sr3_p_sample_step_ex's operations)
+ * with j = step2_dev[1] on entry; step2_dev[1] = j - 1 on completion (step2_dev[0] is scratch, as in sr3_reverse_step).  With one
+ * tile of the image's size this is sr3_p_sample_step_ex + sr3_step_decrement bit for bit.
+ *   eps_tiles    : [batch * ny * nx, channels, th, tw]
+ *   oy_host/ox_host : NULL, or host copies of the origin lists for validation: each must start at 0, increase strictly, end at
+ *                  height - th / width - tw and leave no gap between consecutive tiles (SR3_E_BADARG otherwise)
+ *   z_nchw       : the step's noise or NULL (= 0); tab_*: as sr3_reverse_step; eps_out_nchw: NULL, or where the blended eps goes
+ * Gather form (a thread owns pixels and reads the tiles covering them): no atomics, bitwise reproducible.  Two launches.
+ * SR3_E_BADARG: NULL required pointer, non-positive size, th > height, tw > width, bad host origins; SR3_E_UNSUPPORTED:
+ * batch * channels * height * width >= 2^31; SR3_E_ALIGN: width % 4 == 0 and x / z / eps_out not 16-byte aligned.  Nothing is
+ * launched on a refusal. */
+int sr3_tiled_step(float* x_nchw, const float* eps_tiles, int batch, int channels, int height, int width, const int* oy_dev, int ny,
+                   const int* ox_dev, int nx, const float* wy_dev, const float* wx_dev, int th, int tw, const int* oy_host,
+                   const int* ox_host, const float* z_nchw, const float* tab_a, const float* tab_b, const float* tab_c1,
+                   const float* tab_c2, const float* tab_sigma, int* step2_dev, int clip_denoised, float* eps_out_nchw, void* stream);
+
 /* q_sample (model/sr3_modules/diffusion.py:212-219; model/ddpm_modules/diffusion.py:259-267):
  * out = ca[b] * x0 + cb[b] * z */
 int sr3_q_sample(const float* x0, const float* z, const float* ca, const float* cb, int batch,
