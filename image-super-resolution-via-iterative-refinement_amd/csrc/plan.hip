@@ -1159,10 +1159,12 @@ int sr3_unet_forward(sr3_plan* plan, const float* x_nchw, const float* cond_nchw
 
 // One whole reverse step (include/sr3_mi355x.h): the forward above with the p_sample update and the counter decrement inside the
 // output conv's kernel -- two graph nodes fewer per step than sr3_unet_forward + sr3_p_sample_step + sr3_step_decrement.
-int sr3_reverse_step_ex(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,
-                        const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
-                        const float* z_nchw, const float* ta, const float* tb, const float* tc1, const float* tc2, const float* tsig,
-                        int clip_denoised, float* eps_out_nchw, int batch, void* stream, const int* t_map) {
+// _hist: the multistep tail (tab_c3 and the history buffer, both or neither); _ex forwards here with neither.
+int sr3_reverse_step_hist(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,
+                          const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
+                          const float* z_nchw, const float* ta, const float* tb, const float* tc1, const float* tc2, const float* tsig,
+                          int clip_denoised, float* eps_out_nchw, int batch, void* stream, const int* t_map, const float* tc3,
+                          float* hist_nchw) {
   if (!plan || !x_nchw || !params || !workspace || !freq || !step2_dev || !ta || !tb || !tc1 || !tc2 || !tsig) { set_error("null argument"); return SR3_E_BADARG; }
   if (!cond_nchw) cond_channels = 0;
   const int rc = build_forward(plan, batch, cond_channels);
@@ -1173,14 +1175,32 @@ int sr3_reverse_step_ex(sr3_plan* plan, float* x_nchw, const float* cond_nchw, i
     return SR3_E_ALIGN;
   }
   if (plan->d.variant == SR3_VARIANT_SR3 && !level_table) { set_error("SR3 variant needs level_table"); return SR3_E_BADARG; }
+  if ((tc3 != nullptr) != (hist_nchw != nullptr)) { set_error("reverse_step: tab_c3 and hist_nchw go together (both or neither)"); return SR3_E_BADARG; }
+  if (hist_nchw) {
+    if ((uintptr_t)hist_nchw & 15) { set_error("misaligned pointer (hist: 16 B)"); return SR3_E_ALIGN; }
+    const size_t bytes = (size_t)batch * plan->d.out_channel * plan_height(plan) * plan_width(plan) * sizeof(float);
+    const uintptr_t h0 = (uintptr_t)hist_nchw;
+    for (const float* p : {static_cast<const float*>(x_nchw), static_cast<const float*>(eps_out_nchw)}) {
+      const uintptr_t p0 = (uintptr_t)p;
+      if (p && p0 < h0 + bytes && h0 < p0 + bytes) { set_error("reverse_step: hist_nchw overlaps x_nchw or eps_out_nchw"); return SR3_E_BADARG; }
+    }
+  }
   StepFuse f;
   f.x = x_nchw; f.z = z_nchw; f.tb = StepTables{ta, tb, tc1, tc2, tsig};
-  f.step_cur = step2_dev; f.step_next = step2_dev + 1; f.clip = clip_denoised;
+  f.step_cur = step2_dev; f.step_next = step2_dev + 1; f.clip = clip_denoised; f.c3 = tc3; f.hist = hist_nchw;
   // the embedding kernel reads t from slot 1 and copies it to slot 0; the tail reads slot 0 and writes t - 1 to slot 1: no kernel
   // both reads and writes a slot, so no launch of the step races with another block of itself
   return run_forward(plan, false, x_nchw, cond_nchw, cond_channels, nullptr, nullptr, freq, level_table,
                      step2_dev + 1, params, static_cast<char*>(workspace), eps_out_nchw, batch, static_cast<hipStream_t>(stream),
                      nullptr, nullptr, nullptr, &f, t_map);
+}
+
+int sr3_reverse_step_ex(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,
+                        const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
+                        const float* z_nchw, const float* ta, const float* tb, const float* tc1, const float* tc2, const float* tsig,
+                        int clip_denoised, float* eps_out_nchw, int batch, void* stream, const int* t_map) {
+  return sr3_reverse_step_hist(plan, x_nchw, cond_nchw, cond_channels, freq, level_table, step2_dev, params, workspace, workspace_bytes,
+                               z_nchw, ta, tb, tc1, tc2, tsig, clip_denoised, eps_out_nchw, batch, stream, t_map, nullptr, nullptr);
 }
 
 int sr3_reverse_step(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,

@@ -575,7 +575,9 @@ constexpr int OT_H = 8, OT_W = 32, OT_CK = 16, OT_LD = 20;
 // FUSE (sr3_reverse_step): the reverse-step update of the image this eps belongs to in the epilogue -- the element a thread produces IS the
 // element of eps the elementwise update (sr3 diffusion.py:141-149,162-174) needs, in the same NCHW position -- with k_p_sample_update's
 // separately rounded operations (bit-identical to the two-kernel form), and the loop counter's decrement by one thread
-template <int COUT, bool FULL, bool FUSE>
+// HIST (with FUSE; sr3_reverse_step_hist): the multistep tail -- + c3[t] * hist before the noise term, hist <- x0 -- as its own
+// instantiations, so the tail of the step without history carries no branch for it
+template <int COUT, bool FULL, bool FUSE, bool HIST>
 __global__ __launch_bounds__(256) void k_conv_out_nchw(const float* __restrict__ x, const float* __restrict__ ss,
                                                         int B, int H, int W, int C, const float* __restrict__ w,
                                                         const float* __restrict__ bias, int Cout,
@@ -633,10 +635,11 @@ __global__ __launch_bounds__(256) void k_conv_out_nchw(const float* __restrict__
   }
   const int oh = h0 + ty, ow = w0 + tx;
   int t = 0;
-  float ca = 0.f, cbb = 0.f, c1 = 0.f, c2 = 0.f, sg = 0.f;
+  float ca = 0.f, cbb = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f, sg = 0.f;
   if (FUSE) {
     t = f.step_cur[0];
     ca = f.tb.a[t]; cbb = f.tb.b[t]; c1 = f.tb.c1[t]; c2 = f.tb.c2[t]; sg = f.tb.sigma[t];
+    if (HIST) c3 = f.c3[t];
     if (blockIdx.x == 0 && tid == 0) f.step_next[0] = t - 1;       // (nobody reads this slot before the next step's first kernel)
   }
   if (oh < H && ow < W) {
@@ -649,7 +652,11 @@ __global__ __launch_bounds__(256) void k_conv_out_nchw(const float* __restrict__
         const float xv = f.x[idx], zv = f.z ? f.z[idx] : 0.f;
         float x0 = sub_rn(mul_rn(ca, xv), mul_rn(cbb, e));
         if (f.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-        const float mean = add_rn(mul_rn(c1, x0), mul_rn(c2, xv));
+        float mean = add_rn(mul_rn(c1, x0), mul_rn(c2, xv));
+        if (HIST) {                  // (this thread alone reads and writes the element's history)
+          mean = add_rn(mean, mul_rn(c3, f.hist[idx]));
+          f.hist[idx] = x0;
+        }
         f.x[idx] = add_rn(mean, mul_rn(zv, sg));
       }
     }
@@ -665,12 +672,15 @@ int conv_out_nchw(const float* x, const float* ss, int B, int H, int W, int C, c
   StepFuse f;
   memset(&f, 0, sizeof(f));
   if (fuse) f = *fuse;
-#define SR3_CO_LAUNCH3(N, FU, FS)                                                                                            \
-  hipLaunchKernelGGL((k_conv_out_nchw<N, FU, FS>), dim3(tiles), dim3(256), 0, st, x, ss, B, H, W, C, w, bias, Cout, out_nchw, f);
+  if (fuse && (fuse->hist != nullptr) != (fuse->c3 != nullptr)) { set_error("conv_out: the step's c3 table and history go together"); return SR3_E_BADARG; }
+  const bool hist = fuse && fuse->hist;
+#define SR3_CO_LAUNCH3(N, FU, FS, HI)                                                                                        \
+  hipLaunchKernelGGL((k_conv_out_nchw<N, FU, FS, HI>), dim3(tiles), dim3(256), 0, st, x, ss, B, H, W, C, w, bias, Cout, out_nchw, f);
+#define SR3_CO_LAUNCH2(N, FU)                                                                                                \
+  if (hist) { SR3_CO_LAUNCH3(N, FU, true, true) } else if (fuse) { SR3_CO_LAUNCH3(N, FU, true, false) } else { SR3_CO_LAUNCH3(N, FU, false, false) }
 #define SR3_CO_LAUNCH(N)                                                                                                    \
   {                                                                                                                          \
-    if (C % OT_CK == 0) { if (fuse) { SR3_CO_LAUNCH3(N, true, true) } else { SR3_CO_LAUNCH3(N, true, false) } }             \
-    else { if (fuse) { SR3_CO_LAUNCH3(N, false, true) } else { SR3_CO_LAUNCH3(N, false, false) } }                          \
+    if (C % OT_CK == 0) { SR3_CO_LAUNCH2(N, true) } else { SR3_CO_LAUNCH2(N, false) }                                       \
   }
   switch (Cout) {
     case 1: SR3_CO_LAUNCH(1) break;
@@ -679,6 +689,7 @@ int conv_out_nchw(const float* x, const float* ss, int B, int H, int W, int C, c
     default: SR3_CO_LAUNCH(4) break;
   }
 #undef SR3_CO_LAUNCH
+#undef SR3_CO_LAUNCH2
 #undef SR3_CO_LAUNCH3
   SR3_LAUNCH_CHECK("k_conv_out_nchw");
   return SR3_OK;
@@ -757,42 +768,88 @@ int embed_forward(const EmbedParams& p, hipStream_t st) {
 // reference's elementwise torch ops for the same eps.  t comes from a device counter (graph
 // replay), a per-sample int64 array (DDPM API) or the host.
 // ---------------------------------------------------------------------------------------------
-template <bool CLIP>
+// HIST (sr3_p_sample_step_hist): the multistep tail -- x <- (mean + c3_t hist) + sigma_t z, hist <- x0 (after the clamp), the element's
+// history read and written by the thread that owns the element.  V = 4: a thread owns four consecutive elements (per-image size % 4 == 0,
+// so the four lie in one image); V = 1: one element, any size.
+template <bool CLIP, bool HIST, int V>
 __global__ __launch_bounds__(256) void k_p_sample_update(float* __restrict__ x, const float* __restrict__ eps,
                                                           const float* __restrict__ z, StepTables tb,
                                                           const int* __restrict__ step_dev,
                                                           const int64_t* __restrict__ tps, int step_host,
-                                                          int per_image, size_t total4) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t e0 = i * 4;
+                                                          int per_image, size_t total, const float* __restrict__ tc3,
+                                                          float* __restrict__ hist) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t e0 = i * V;
     const int b = (int)(e0 / per_image);
     const int t = step_dev ? step_dev[0] : (tps ? (int)tps[b] : step_host);
     const float a = tb.a[t], bb = tb.b[t], c1 = tb.c1[t], c2 = tb.c2[t], sg = tb.sigma[t];
-    f32x4 xv = *reinterpret_cast<const f32x4*>(x + e0);
-    const f32x4 ev = *reinterpret_cast<const f32x4*>(eps + e0);
-    f32x4 zv = {0.f, 0.f, 0.f, 0.f};
-    if (z) zv = *reinterpret_cast<const f32x4*>(z + e0);
+    const float c3 = HIST ? tc3[t] : 0.f;
+    float xv[V], ev[V], zv[V], hv[V];
+    if constexpr (V == 4) {
+      const f32x4 xq = *reinterpret_cast<const f32x4*>(x + e0);
+      const f32x4 eq = *reinterpret_cast<const f32x4*>(eps + e0);
+      f32x4 zq = {0.f, 0.f, 0.f, 0.f}, hq = {0.f, 0.f, 0.f, 0.f};
+      if (z) zq = *reinterpret_cast<const f32x4*>(z + e0);
+      if (HIST) hq = *reinterpret_cast<const f32x4*>(hist + e0);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+      for (int k = 0; k < 4; ++k) { xv[k] = xq[k]; ev[k] = eq[k]; zv[k] = zq[k]; hv[k] = hq[k]; }
+    } else {
+      xv[0] = x[e0]; ev[0] = eps[e0]; zv[0] = z ? z[e0] : 0.f; hv[0] = HIST ? hist[e0] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
       float x0 = sub_rn(mul_rn(a, xv[k]), mul_rn(bb, ev[k]));
       if (CLIP) x0 = fminf(fmaxf(x0, -1.f), 1.f);          // clip_denoised (sr3 diffusion.py:162-163)
-      const float mean = add_rn(mul_rn(c1, x0), mul_rn(c2, xv[k]));
+      float mean = add_rn(mul_rn(c1, x0), mul_rn(c2, xv[k]));
+      if (HIST) { mean = add_rn(mean, mul_rn(c3, hv[k])); hv[k] = x0; }
       xv[k] = add_rn(mean, mul_rn(zv[k], sg));
     }
-    *reinterpret_cast<f32x4*>(x + e0) = xv;
+    if constexpr (V == 4) {
+      const f32x4 xo = {xv[0], xv[1], xv[2], xv[3]};
+      *reinterpret_cast<f32x4*>(x + e0) = xo;
+      if (HIST) {
+        const f32x4 ho = {hv[0], hv[1], hv[2], hv[3]};
+        *reinterpret_cast<f32x4*>(hist + e0) = ho;
+      }
+    } else {
+      x[e0] = xv[0];
+      if (HIST) hist[e0] = hv[0];
+    }
   }
 }
 
-int p_sample_update(float* x, const float* eps, const float* z, StepTables tb, const int* step_dev,
-                    const int64_t* t_per_sample, int step_host, int B, int per_image, hipStream_t st, bool clip) {
-  if (per_image & 3) { set_error("p_sample_update: per-image size %% 4 != 0"); return SR3_E_UNSUPPORTED; }
-  const size_t total4 = (size_t)B * per_image / 4;
-  int blocks = (int)((total4 + 255) / 256);
+template <bool CLIP, bool HIST>
+static void launch_p_sample_update(float* x, const float* eps, const float* z, const float* c3, float* hist, StepTables tb, const int* step_dev,
+                                   const int64_t* t_per_sample, int step_host, int per_image, size_t elems, bool vec, hipStream_t st) {
+  const size_t total = vec ? elems / 4 : elems;
+  int blocks = (int)((total + 255) / 256);
   if (blocks > 2048) blocks = 2048;
-  if (clip) hipLaunchKernelGGL(k_p_sample_update<true>, dim3(blocks), dim3(256), 0, st, x, eps, z, tb, step_dev, t_per_sample,
-                               step_host, per_image, total4);
-  else hipLaunchKernelGGL(k_p_sample_update<false>, dim3(blocks), dim3(256), 0, st, x, eps, z, tb, step_dev, t_per_sample,
-                          step_host, per_image, total4);
+  if (vec) hipLaunchKernelGGL((k_p_sample_update<CLIP, HIST, 4>), dim3(blocks), dim3(256), 0, st, x, eps, z, tb, step_dev,
+                              t_per_sample, step_host, per_image, total, c3, hist);
+  else hipLaunchKernelGGL((k_p_sample_update<CLIP, HIST, 1>), dim3(blocks), dim3(256), 0, st, x, eps, z, tb, step_dev,
+                          t_per_sample, step_host, per_image, total, c3, hist);
+}
+
+int p_sample_update(float* x, const float* eps, const float* z, StepTables tb, const int* step_dev,
+                    const int64_t* t_per_sample, int step_host, int B, int per_image, hipStream_t st, bool clip, const float* c3, float* hist) {
+  if ((hist != nullptr) != (c3 != nullptr)) { set_error("p_sample_update: the c3 table and the history go together (both or neither)"); return SR3_E_BADARG; }
+  const size_t elems = (size_t)B * per_image;
+  if (hist) {
+    const uintptr_t h0 = (uintptr_t)hist, h1 = h0 + elems * sizeof(float);
+    for (const float* p : {static_cast<const float*>(x), eps}) {
+      const uintptr_t p0 = (uintptr_t)p;
+      if (p0 < h1 && h0 < p0 + elems * sizeof(float)) { set_error("p_sample_update: the history overlaps x or eps"); return SR3_E_BADARG; }
+    }
+  }
+  // four elements per thread where an image is a whole number of quads and every tensor allows a 16-byte access; else one
+  const bool vec = (per_image & 3) == 0 && ((((uintptr_t)x | (uintptr_t)eps | (uintptr_t)z | (uintptr_t)hist) & 15) == 0);
+  if (clip) {
+    if (hist) launch_p_sample_update<true, true>(x, eps, z, c3, hist, tb, step_dev, t_per_sample, step_host, per_image, elems, vec, st);
+    else launch_p_sample_update<true, false>(x, eps, z, c3, hist, tb, step_dev, t_per_sample, step_host, per_image, elems, vec, st);
+  } else {
+    if (hist) launch_p_sample_update<false, true>(x, eps, z, c3, hist, tb, step_dev, t_per_sample, step_host, per_image, elems, vec, st);
+    else launch_p_sample_update<false, false>(x, eps, z, c3, hist, tb, step_dev, t_per_sample, step_host, per_image, elems, vec, st);
+  }
   SR3_LAUNCH_CHECK("k_p_sample_update");
   return SR3_OK;
 }

@@ -299,6 +299,9 @@ struct StepFuse {
   const int* step_cur;    // t of this step (written by the embedding kernel of the same forward)
   int* step_next;         // t of the next step
   int clip;
+  // multistep tail (both set or both null; behind the older fields, whose offsets the kernels without history keep): x <- ... + c3[t] hist
+  const float* c3;        // table of the previous x0's coefficient, indexed like tb
+  float* hist;            // the previous step's x0, same layout as x; read, then overwritten by this step's
 };
 // final Block: silu(gn(x)) -> conv3x3 C->Cout(<=4), NHWC in, NCHW out (out_nchw may be null when `fuse` is given)
 int conv_out_nchw(const float* x, const float* ss, int B, int H, int W, int C, const float* w,
@@ -332,7 +335,8 @@ bool attention_fits(int N, int C);
 // key-blocked (online softmax) form: any N > 0, C % 4 == 0 (attention_long.hip); split: 3 x bf16 split arithmetic where C % 128 == 0
 int attention_long_forward(const float* qkv, int B, int N, int C, float* out, hipStream_t st, bool split);
 int p_sample_update(float* x, const float* eps, const float* z, StepTables tb, const int* step_dev,
-                    const int64_t* t_per_sample, int step_host, int B, int per_image, hipStream_t st, bool clip = true);
+                    const int64_t* t_per_sample, int step_host, int B, int per_image, hipStream_t st, bool clip = true,
+                    const float* c3 = nullptr, float* hist = nullptr);
 int step_decrement(int* step_dev, hipStream_t st);
 // split3_pair self-test (small_kernels.hip): *bad_dev = number of elements whose three bf16 terms do not add back exactly
 int split3_selftest(int* bad_dev, hipStream_t st);

@@ -58,6 +58,8 @@ struct TiledStep {
   const int* step_cur;       // j of this step (k_step_copy put it there)
   int* step_next;            // j - 1 goes here
   int C, H, W, ny, nx, th, tw;
+  const float* c3;           // multistep tail (both set or both null): table of the previous x0's coefficient, indexed like tb
+  float* hist;               // ... and the previous step's x0, [B, C, H, W]
 };
 
 // the tiles covering coordinate p along one axis are a contiguous range of the (increasing) origin list
@@ -123,12 +125,14 @@ __device__ __forceinline__ f32x4 blend_quad(const TiledStep& s, int b, int c, in
 }
 
 // x <- p_sample update of (x, blended eps, z) at step index j = *step_cur; *step_next = j - 1.  V = 4: a thread owns four x positions
-// (W % 4 == 0, x / z / eps_out 16-byte aligned); V = 1: one.
-template <int V, bool CLIP>
+// (W % 4 == 0, x / z / eps_out / hist 16-byte aligned); V = 1: one.  HIST: the multistep tail of k_p_sample_update -- + c3[j] * hist before
+// the noise term, hist <- x0, by the thread that owns the element.
+template <int V, bool CLIP, bool HIST>
 __global__ __launch_bounds__(256) void k_tiled_step(TiledStep s, size_t total) {
   const int j = s.step_cur[0];
   if (blockIdx.x == 0 && threadIdx.x == 0) s.step_next[0] = j - 1;      // (nobody reads this slot before the next step's first kernel)
   const float a = s.tb.a[j], bb = s.tb.b[j], c1 = s.tb.c1[j], c2 = s.tb.c2[j], sg = s.tb.sigma[j];
+  const float c3 = HIST ? s.c3[j] : 0.f;
   const int wv = s.W / V;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int x0 = (int)(i % wv) * V;
@@ -139,7 +143,7 @@ __global__ __launch_bounds__(256) void k_tiled_step(TiledStep s, size_t total) {
     int iy0, iy1, ix0, ix1;
     cover(s.oy, s.ny, s.H, s.th, y, iy0, iy1);
     cover(s.ox, s.nx, s.W, s.tw, x0, ix0, ix1);
-    float ev[V], xv[V], zv[V];
+    float ev[V], xv[V], zv[V], hv[V];
     if constexpr (V == 4) {
       int jx0, jx1;
       cover(s.ox, s.nx, s.W, s.tw, x0 + 3, jx0, jx1);
@@ -160,27 +164,39 @@ __global__ __launch_bounds__(256) void k_tiled_step(TiledStep s, size_t total) {
       if (s.z) zq = *reinterpret_cast<const f32x4*>(s.z + e0);
 #pragma unroll
       for (int k = 0; k < V; ++k) { xv[k] = xq[k]; zv[k] = zq[k]; }
+      if (HIST) {
+        const f32x4 hq = *reinterpret_cast<const f32x4*>(s.hist + e0);
+#pragma unroll
+        for (int k = 0; k < V; ++k) hv[k] = hq[k];
+      }
     } else {
       ev[0] = blend_pixel(s, b, c, y, x0, iy0, iy1, ix0, ix1);
       xv[0] = s.x[e0];
       zv[0] = s.z ? s.z[e0] : 0.f;
+      if (HIST) hv[0] = s.hist[e0];
     }
 #pragma unroll
     for (int k = 0; k < V; ++k) {
       float p0 = sub_rn(mul_rn(a, xv[k]), mul_rn(bb, ev[k]));
       if (CLIP) p0 = fminf(fmaxf(p0, -1.f), 1.f);
-      const float mean = add_rn(mul_rn(c1, p0), mul_rn(c2, xv[k]));
+      float mean = add_rn(mul_rn(c1, p0), mul_rn(c2, xv[k]));
+      if (HIST) { mean = add_rn(mean, mul_rn(c3, hv[k])); hv[k] = p0; }
       xv[k] = add_rn(mean, mul_rn(zv[k], sg));
     }
     if constexpr (V == 4) {
       const f32x4 o = {xv[0], xv[1], xv[2], xv[3]};
       *reinterpret_cast<f32x4*>(s.x + e0) = o;
+      if (HIST) {
+        const f32x4 ho = {hv[0], hv[1], hv[2], hv[3]};
+        *reinterpret_cast<f32x4*>(s.hist + e0) = ho;
+      }
       if (s.eps_out) {
         const f32x4 eo = {ev[0], ev[1], ev[2], ev[3]};
         *reinterpret_cast<f32x4*>(s.eps_out + e0) = eo;
       }
     } else {
       s.x[e0] = xv[0];
+      if (HIST) s.hist[e0] = hv[0];
       if (s.eps_out) s.eps_out[e0] = ev[0];
     }
   }
@@ -235,10 +251,11 @@ int sr3_tile_gather(const float* src_nchw, int batch, int channels, int height, 
   return SR3_OK;
 }
 
-int sr3_tiled_step(float* x_nchw, const float* eps_tiles, int batch, int channels, int height, int width, const int* oy_dev, int ny,
-                   const int* ox_dev, int nx, const float* wy_dev, const float* wx_dev, int th, int tw, const int* oy_host,
-                   const int* ox_host, const float* z_nchw, const float* ta, const float* tb, const float* tc1, const float* tc2,
-                   const float* tsig, int* step2_dev, int clip_denoised, float* eps_out_nchw, void* stream) {
+int sr3_tiled_step_hist(float* x_nchw, const float* eps_tiles, int batch, int channels, int height, int width, const int* oy_dev, int ny,
+                        const int* ox_dev, int nx, const float* wy_dev, const float* wx_dev, int th, int tw, const int* oy_host,
+                        const int* ox_host, const float* z_nchw, const float* ta, const float* tb, const float* tc1, const float* tc2,
+                        const float* tsig, int* step2_dev, int clip_denoised, float* eps_out_nchw, void* stream, const float* tc3,
+                        float* hist_nchw) {
   if (!x_nchw || !eps_tiles || !oy_dev || !ox_dev || !wy_dev || !wx_dev || !ta || !tb || !tc1 || !tc2 || !tsig || !step2_dev) { set_error("tiled_step: null argument"); return SR3_E_BADARG; }
   if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || ny <= 0 || nx <= 0 || th <= 0 || tw <= 0) { set_error("tiled_step: sizes must be positive"); return SR3_E_BADARG; }
   if (th > height || tw > width) { set_error("tiled_step: tile %d x %d larger than the image %d x %d", th, tw, height, width); return SR3_E_BADARG; }
@@ -246,27 +263,45 @@ int sr3_tiled_step(float* x_nchw, const float* eps_tiles, int batch, int channel
   if (total >= ((size_t)1 << 31) || (size_t)batch * ny * nx >= ((size_t)1 << 31)) { set_error("tiled_step: image batch too large (B * C * H * W >= 2^31)"); return SR3_E_UNSUPPORTED; }
   if (oy_host) { if (const int rc = check_origins("y", oy_host, ny, height, th)) return rc; }
   if (ox_host) { if (const int rc = check_origins("x", ox_host, nx, width, tw)) return rc; }
+  if ((tc3 != nullptr) != (hist_nchw != nullptr)) { set_error("tiled_step: tab_c3 and hist_nchw go together (both or neither)"); return SR3_E_BADARG; }
+  if (hist_nchw) {
+    const uintptr_t h0 = (uintptr_t)hist_nchw, bytes = total * sizeof(float);
+    for (const float* p : {static_cast<const float*>(x_nchw), static_cast<const float*>(eps_out_nchw)}) {
+      const uintptr_t p0 = (uintptr_t)p;
+      if (p && p0 < h0 + bytes && h0 < p0 + bytes) { set_error("tiled_step: hist_nchw overlaps x_nchw or eps_out_nchw"); return SR3_E_BADARG; }
+    }
+  }
   TiledStep s;
   s.x = x_nchw; s.eps = eps_tiles; s.oy = oy_dev; s.ox = ox_dev; s.wy = wy_dev; s.wx = wx_dev; s.z = z_nchw; s.eps_out = eps_out_nchw;
+  s.c3 = tc3; s.hist = hist_nchw;
   s.tb = StepTables{ta, tb, tc1, tc2, tsig};
   s.step_cur = step2_dev; s.step_next = step2_dev + 1;
   s.C = channels; s.H = height; s.W = width; s.ny = ny; s.nx = nx; s.th = th; s.tw = tw;
   const bool vec = (width & 3) == 0;
-  if (vec && (((uintptr_t)x_nchw & 15) || ((uintptr_t)z_nchw & 15) || ((uintptr_t)eps_out_nchw & 15))) { set_error("tiled_step: misaligned pointer (x, z, eps_out: 16 B)"); return SR3_E_ALIGN; }
+  if (vec && (((uintptr_t)x_nchw & 15) || ((uintptr_t)z_nchw & 15) || ((uintptr_t)eps_out_nchw & 15) || ((uintptr_t)hist_nchw & 15))) { set_error("tiled_step: misaligned pointer (x, z, eps_out, hist: 16 B)"); return SR3_E_ALIGN; }
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(k_step_copy, dim3(1), dim3(64), 0, st, step2_dev);
   SR3_LAUNCH_CHECK("k_step_copy");
   const size_t work = vec ? total / 4 : total;
   const dim3 grid(grid_for(work));
-  if (vec) {
-    if (clip_denoised) hipLaunchKernelGGL((k_tiled_step<4, true>), grid, dim3(256), 0, st, s, work);
-    else hipLaunchKernelGGL((k_tiled_step<4, false>), grid, dim3(256), 0, st, s, work);
-  } else {
-    if (clip_denoised) hipLaunchKernelGGL((k_tiled_step<1, true>), grid, dim3(256), 0, st, s, work);
-    else hipLaunchKernelGGL((k_tiled_step<1, false>), grid, dim3(256), 0, st, s, work);
+#define SR3_TS_LAUNCH(V, HI)                                                                            \
+  {                                                                                                     \
+    if (clip_denoised) hipLaunchKernelGGL((k_tiled_step<V, true, HI>), grid, dim3(256), 0, st, s, work); \
+    else hipLaunchKernelGGL((k_tiled_step<V, false, HI>), grid, dim3(256), 0, st, s, work);              \
   }
+  if (vec) { if (hist_nchw) SR3_TS_LAUNCH(4, true) else SR3_TS_LAUNCH(4, false) }
+  else { if (hist_nchw) SR3_TS_LAUNCH(1, true) else SR3_TS_LAUNCH(1, false) }
+#undef SR3_TS_LAUNCH
   SR3_LAUNCH_CHECK("k_tiled_step");
   return SR3_OK;
+}
+
+int sr3_tiled_step(float* x_nchw, const float* eps_tiles, int batch, int channels, int height, int width, const int* oy_dev, int ny,
+                   const int* ox_dev, int nx, const float* wy_dev, const float* wx_dev, int th, int tw, const int* oy_host,
+                   const int* ox_host, const float* z_nchw, const float* ta, const float* tb, const float* tc1, const float* tc2,
+                   const float* tsig, int* step2_dev, int clip_denoised, float* eps_out_nchw, void* stream) {
+  return sr3_tiled_step_hist(x_nchw, eps_tiles, batch, channels, height, width, oy_dev, ny, ox_dev, nx, wy_dev, wx_dev, th, tw, oy_host,
+                             ox_host, z_nchw, ta, tb, tc1, tc2, tsig, step2_dev, clip_denoised, eps_out_nchw, stream, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -14,6 +14,8 @@ hipGraph and replayed T times; snapshots are graph-external device copies.
 Sampler (engine extension, `"sampler": {"type": "ddim", "steps": S, "eta": e}` in the schedule dict or `set_sampler`): the same
 captured step replayed S times over a strided walk through the schedule -- `sampler_tables` restates the DDIM update in the fused
 tail's linear form, so a sampler is five other coefficient tables, another level table and (DDPM) a step-index -> timestep map.
+`"type": "dpmpp_2m"` is the second-order multistep solver DPM-Solver++(2M) on a walk uniform in log-SNR (`"walk": "logsnr"`, its
+default; DDIM takes the key too): one more table, c3, and one image-sized buffer that carries the previous step's x0 (st['hist']).
 
 Tiling (engine extension, `"tiling": {"tile": 128 | [th, tw], "overlap": 32, "batch": 8}` next to it, or `set_tiling`): an image larger
 than the tile is sampled as one chain whose eps comes from overlapping tiles of that size -- per step: sr3_tile_gather + UNet forward
@@ -54,50 +56,119 @@ def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2,
     raise NotImplementedError(schedule)
 
 
-def sampler_tables(alphas_cumprod, steps, eta):
-    """Tables of a strided DDIM sampler (Song et al. 2021, eq. 12 and 16) in the form of the engine's fused step tail,
+def _check_walk_args(alphas_cumprod, steps):
+    ac = np.asarray(alphas_cumprod, dtype=np.float64).reshape(-1)
+    T = int(ac.shape[0])
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)):
+        raise ValueError('sampler steps must be an integer (got %r)' % (steps,))
+    if T < 1 or not np.all(np.isfinite(ac)) or not np.all((ac > 0.0) & (ac < 1.0)):
+        raise ValueError('alphas_cumprod must be finite values in (0, 1)')
+    S = int(steps)
+    if S < 1 or S > T:
+        raise ValueError('sampler steps must lie in [1, %d] (got %d)' % (T, S))
+    return ac, T, S
 
-        x0c = clip(a x - b eps) ;  x_new = c1 x0c + c2 x + sigma z,
 
-    which is the textbook update  sqrt(ap) x0c + d eps' + sigma z  with eps' = (x - sqrt(ab) x0c) / sqrt(1 - ab) re-derived from the
+def _half_logsnr(ac):
+    """lambda = log(alpha / sigma) = 0.5 log(ac / (1 - ac)): what a DPM-Solver steps in."""
+    return 0.5 * np.log(ac / (1.0 - ac))
+
+
+WALKS = ('time', 'logsnr')
+
+
+def sampler_walk(alphas_cumprod, steps, walk='time'):
+    """The timesteps a sampler visits: tau, int64 [S], strictly increasing, tau[0] = 0 and tau[S-1] = T - 1 (S = 1: [T - 1]).
+
+    walk = 'time': uniform in the timestep, round(linspace(0, T - 1, S)).  walk = 'logsnr': uniform in lambda_t = 0.5 log(ac_t /
+    (1 - ac_t)) -- tau[i] is the timestep whose lambda is nearest the i-th of S evenly spaced targets between lambda_0 and
+    lambda_{T-1}; both ends are pinned, one forward pass (tau[i] >= tau[i-1] + 1) makes the walk strictly increasing where the schedule
+    is too coarse for the targets (its first timesteps, where lambda moves fastest) and one backward pass (tau[i] <= tau[i+1] - 1)
+    takes back what the forward pass pushed past the top.  A multistep solver's extrapolation is only as good as the ratio of
+    consecutive lambda intervals is tame; on the 'time' walk the last intervals are enormous in lambda."""
+    ac, T, S = _check_walk_args(alphas_cumprod, steps)
+    if walk not in WALKS:
+        raise ValueError('sampler walk must be one of %s (got %r)' % (', '.join(repr(w) for w in WALKS), walk))
+    if S == 1:
+        return np.array([T - 1], dtype=np.int64)
+    if walk == 'time':
+        tau = np.round(np.linspace(0, T - 1, S)).astype(np.int64)
+    else:
+        lam = _half_logsnr(ac)
+        target = np.linspace(lam[0], lam[T - 1], S)
+        tau = np.array([int(np.argmin(np.abs(lam - v))) for v in target], dtype=np.int64)
+        tau[0], tau[S - 1] = 0, T - 1
+        for i in range(1, S):
+            tau[i] = max(tau[i], tau[i - 1] + 1)
+        tau[S - 1] = T - 1
+        for i in range(S - 2, -1, -1):
+            tau[i] = min(tau[i], tau[i + 1] - 1)
+    assert tau[-1] == T - 1 and tau[0] == 0 and np.all(np.diff(tau) > 0), 'sampler walk is not strictly increasing'
+    return tau
+
+
+SAMPLER_KINDS = ('ddim', 'dpmpp_2m')
+
+
+def sampler_tables(alphas_cumprod, steps, eta, *, kind='ddim', walk='time'):
+    """Tables of a sampler over a walk through the schedule (`sampler_walk`) in the form of the engine's fused step tail,
+
+        x0c = clip(a x - b eps) ;  x_new = c1 x0c + c2 x + c3 x0c_prev + sigma z.
+
+    kind = 'ddim' (Song et al. 2021, eq. 12 and 16; c3 = 0): the textbook update  sqrt(ap) x0c + d eps' + sigma z  with
+    eps' = (x - sqrt(ab) x0c) / sqrt(1 - ab) re-derived from the
     clipped x0 (the reference's clip_denoised semantics), d = sqrt(1 - ap - sigma^2): collecting x0c and x gives
     c1 = sqrt(ap) - d sqrt(ab) / sqrt(1 - ab), c2 = d / sqrt(1 - ab).  ab = alphas_cumprod[tau[j]], ap = that of the next (smaller)
     timestep of the walk and 1 after the last; sigma = eta sqrt((1 - ap) / (1 - ab)) sqrt(1 - ab / ap).  With steps = T and eta = 1 these
     are the reference's posterior_mean_coef1/2 and sqrt(posterior_variance).
 
+    kind = 'dpmpp_2m' (DPM-Solver++(2M), Lu et al. 2022, Algorithm 2, data prediction; eta must be 0): with lambda = 0.5 log(ac /
+    (1 - ac)), h = lambda(ap) - lambda(ab) and r = (the previous step's h) / h, the update is
+    x_new = sqrt(1 - ap) / sqrt(1 - ab) x - sqrt(ap) expm1(-h) D with D = (1 + 1 / (2r)) x0c - 1 / (2r) x0c_prev, so with
+    k = -sqrt(ap) expm1(-h): c1 = k (1 + 1 / (2r)), c2 = sqrt(1 - ap) / sqrt(1 - ab), c3 = -k / (2r).  The first step taken has no
+    history (c1 = k, c3 = 0: DDIM's step), and the last one goes to ap = 1, where lambda is infinite: c1 = 1, c2 = c3 = 0, DDIM's too.
+
     Pure numpy, float64, no device.  The step index j counts like the device counter: j = steps - 1 is the first step taken, j = 0 the
-    last.  Returns a dict: tau (int64, [S], strictly increasing, tau[0] = 0 and tau[S-1] = T - 1; S = 1: [T - 1]), a, b, c1, c2,
+    last.  Returns a dict: tau (`sampler_walk`), a, b, c1, c2, c3,
     sigma ([S]) and level ([S + 1]: level[j + 1] = sqrt(alphas_cumprod[tau[j]]), the reference's sqrt_alphas_cumprod_prev[t + 1] at
     t = tau[j]; level[0] = 1)."""
-    ac = np.asarray(alphas_cumprod, dtype=np.float64).reshape(-1)
-    T = int(ac.shape[0])
-    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)):
-        raise ValueError('sampler steps must be an integer (got %r)' % (steps,))
+    ac, T, S = _check_walk_args(alphas_cumprod, steps)
     try:
         eta = float(eta)
     except (TypeError, ValueError):
         raise ValueError('sampler eta must be a number (got %r)' % (eta,))
     if not np.isfinite(eta) or not 0.0 <= eta <= 1.0:
         raise ValueError('sampler eta must lie in [0, 1] (got %r)' % (eta,))
-    if T < 1 or not np.all(np.isfinite(ac)) or not np.all((ac > 0.0) & (ac < 1.0)):
-        raise ValueError('alphas_cumprod must be finite values in (0, 1)')
-    S = int(steps)
-    if S < 1 or S > T:
-        raise ValueError('sampler steps must lie in [1, %d] (got %d)' % (T, S))
-    tau = np.round(np.linspace(0, T - 1, S)).astype(np.int64) if S > 1 else np.array([T - 1], dtype=np.int64)
-    assert tau[-1] == T - 1 and (S == 1 or tau[0] == 0) and np.all(np.diff(tau) > 0), 'sampler walk is not strictly increasing'
+    if kind not in SAMPLER_KINDS:
+        raise ValueError('sampler kind must be one of %s (got %r)' % (', '.join(repr(k) for k in SAMPLER_KINDS), kind))
+    if kind == 'dpmpp_2m' and eta != 0.0:
+        raise ValueError('sampler kind \'dpmpp_2m\' is the deterministic solver: eta must be 0 (got %r)' % (eta,))
+    tau = sampler_walk(ac, S, walk)
     ab = ac[tau]
     ap = np.append(1.0, ab[:-1])
-    sigma = eta * np.sqrt((1.0 - ap) / (1.0 - ab)) * np.sqrt(1.0 - ab / ap)
-    d = np.sqrt(np.maximum(1.0 - ap - sigma ** 2, 0.0))
-    out = dict(tau=tau, a=np.sqrt(1.0 / ab), b=np.sqrt(1.0 / ab - 1), c1=np.sqrt(ap) - d * np.sqrt(ab) / np.sqrt(1.0 - ab),
-               c2=d / np.sqrt(1.0 - ab), sigma=sigma, level=np.append(1.0, np.sqrt(ab)))
+    if kind == 'ddim':
+        sigma = eta * np.sqrt((1.0 - ap) / (1.0 - ab)) * np.sqrt(1.0 - ab / ap)
+        d = np.sqrt(np.maximum(1.0 - ap - sigma ** 2, 0.0))
+        c1, c2, c3 = np.sqrt(ap) - d * np.sqrt(ab) / np.sqrt(1.0 - ab), d / np.sqrt(1.0 - ab), np.zeros(S)
+    else:
+        sigma, c1, c2, c3 = np.zeros(S), np.ones(S), np.zeros(S), np.zeros(S)
+        lam = _half_logsnr(ab)
+        for j in range(1, S):
+            h = _half_logsnr(ap[j]) - lam[j]
+            k = -np.sqrt(ap[j]) * np.expm1(-h)
+            c2[j] = np.sqrt(1.0 - ap[j]) / np.sqrt(1.0 - ab[j])
+            if j == S - 1:
+                c1[j] = k
+            else:
+                r = (lam[j] - lam[j + 1]) / h
+                c1[j], c3[j] = k * (1.0 + 1.0 / (2.0 * r)), -k / (2.0 * r)
+    out = dict(tau=tau, a=np.sqrt(1.0 / ab), b=np.sqrt(1.0 / ab - 1), c1=c1, c2=c2, c3=c3, sigma=sigma, level=np.append(1.0, np.sqrt(ab)))
     if not all(np.all(np.isfinite(v)) for v in out.values()):
         raise ValueError('sampler tables are not finite')
     return out
 
 
-_SAMPLER_TABLES = ('a', 'b', 'c1', 'c2', 'sigma', 'level', 'tau')
+_SAMPLER_TABLES = ('a', 'b', 'c1', 'c2', 'c3', 'sigma', 'level', 'tau')
 
 _BUFFERS = ('betas', 'alphas_cumprod', 'alphas_cumprod_prev', 'sqrt_alphas_cumprod',
             'sqrt_one_minus_alphas_cumprod', 'log_one_minus_alphas_cumprod', 'sqrt_recip_alphas_cumprod',
@@ -118,7 +189,8 @@ class EngineDiffusion(nn.Module):
         self.use_graph = True          # hipGraph replay of the reverse step
         self.show_progress = True
         self._loop_cache = {}
-        self.sampler = None            # None: the reference's ancestral loop; else {'type': 'ddim', 'steps': S, 'eta': e} (set_sampler)
+        self.sampler = None            # None: the reference's ancestral loop; else {'type': 'ddim', 'steps': S, 'eta': e} (set_sampler);
+                                       # type 'dpmpp_2m' or a walk other than 'time': also 'walk'
         self.tiling = None             # None: whole-image steps; else {'tile': (th, tw), 'overlap': o, 'batch': n | None} (set_tiling)
         self.max_cached_loops = 3      # reverse-loop states (buffers + workspace + captured graph) kept, one per (shape, launch list)
         # schedule_opt is accepted and ignored exactly like the reference ctor (diffusion.py:80-82)
@@ -160,17 +232,18 @@ class EngineDiffusion(nn.Module):
         self._alphas_cumprod64 = ac                                              # what a sampler's tables are computed from
         self._loop_cache = {}
         self.tiling = None                                                       # (this phase's own "tiling" key is read below)
-        # engine key of the schedule dict: "sampler": {"type": "ddim", "steps": S, "eta": e}; absent / null: the ancestral loop
+        # engine key of the schedule dict: "sampler": {"type": "ddim" | "dpmpp_2m", "steps": S, "eta": e, "walk": "time" | "logsnr"};
+        # absent / null: the ancestral loop
         spec = schedule_opt.get('sampler') if hasattr(schedule_opt, 'get') else None
         if spec is None:
             self.set_sampler(None)
         else:
             kind = spec.get('type', 'ddim')
-            if kind != 'ddim':
-                raise NotImplementedError('sampler type %r (only "ddim")' % (kind,))
+            if kind not in SAMPLER_KINDS:
+                raise NotImplementedError('sampler type %r (only %s)' % (kind, ', '.join('"%s"' % k for k in SAMPLER_KINDS)))
             if spec.get('steps') is None:
                 raise ValueError('sampler: "steps" is required')
-            self.set_sampler(spec['steps'], spec.get('eta', 0.0))
+            self.set_sampler(spec['steps'], spec.get('eta', 0.0), kind=kind, walk=spec.get('walk'))
         # engine key next to it: "tiling": {"tile": 128 | [th, tw], "overlap": 32, "batch": 8}; absent / null: whole-image steps
         spec = schedule_opt.get('tiling') if hasattr(schedule_opt, 'get') else None
         if spec is None:
@@ -179,9 +252,11 @@ class EngineDiffusion(nn.Module):
             t = TL.parse_tiling(spec, self.denoise_fn.plan.divisor)
             self.set_tiling(t['tile'], t['overlap'], t['batch'])
 
-    def set_sampler(self, steps=None, eta=0.0):
+    def set_sampler(self, steps=None, eta=0.0, *, kind='ddim', walk=None):
         """Sample in `steps` reverse steps over a strided walk through the current schedule (DDIM; eta = 0: deterministic, eta = 1 and
-        steps = T: the ancestral sampler's coefficients) -- or, steps None, go back to the reference's ancestral loop.  What
+        steps = T: the ancestral sampler's coefficients) -- or, steps None, go back to the reference's ancestral loop.  kind =
+        'dpmpp_2m': the second-order multistep solver DPM-Solver++(2M) (eta must be 0); walk: 'time' (uniform in the timestep, DDIM's
+        default) or 'logsnr' (uniform in log-SNR, the multistep solver's default -- on the 'time' walk it is worse than DDIM).  What
         p_sample_loop and everything on top of it (sample, super_resolution, the validation waves) runs; p_sample, p_mean_variance and
         p_losses keep the schedule's own timesteps."""
         if steps is None:
@@ -189,12 +264,20 @@ class EngineDiffusion(nn.Module):
         else:
             if getattr(self, '_alphas_cumprod64', None) is None:
                 raise RuntimeError('set_sampler needs a noise schedule (set_new_noise_schedule first)')
-            tabs = sampler_tables(self._alphas_cumprod64, steps, eta)
+            if kind not in SAMPLER_KINDS:
+                raise NotImplementedError('sampler type %r (only %s)' % (kind, ', '.join('"%s"' % k for k in SAMPLER_KINDS)))
+            if walk is None:
+                walk = 'logsnr' if kind == 'dpmpp_2m' else 'time'
+            tabs = sampler_tables(self._alphas_cumprod64, steps, eta, kind=kind, walk=walk)
             self._check_tiled_sampler(True, getattr(self, 'tiling', None))
-            self.sampler = dict(type='ddim', steps=int(steps), eta=float(eta))
+            self.sampler = dict(type=kind, steps=int(steps), eta=float(eta))
+            if kind != 'ddim' or walk != 'time':
+                self.sampler['walk'] = walk
+            if kind == 'ddim':
+                tabs = dict(tabs, c3=None)         # a one-step rule keeps no history: no table, no buffer, the kernels without it
         dev = self.betas.device if hasattr(self, 'betas') else None
         for k in _SAMPLER_TABLES:                # the float64 tables rounded once to fp32; the walk as int32 (what k_embed reads)
-            t = None if tabs is None else torch.tensor(tabs[k], dtype=torch.int32 if k == 'tau' else torch.float32).to(dev)
+            t = None if tabs is None or tabs[k] is None else torch.tensor(tabs[k], dtype=torch.int32 if k == 'tau' else torch.float32).to(dev)
             self.register_buffer('_sampler_' + k, t, persistent=False)
         self._loop_cache = {}
 
@@ -213,7 +296,7 @@ class EngineDiffusion(nn.Module):
 
     def _check_tiled_sampler(self, sampler, tiling):
         if sampler and tiling is not None and self.variant == 'ddpm':
-            raise NotImplementedError('tiled sampling of the DDPM variant under a DDIM sampler: the tiles run through sr3_unet_forward, '
+            raise NotImplementedError('tiled sampling of the DDPM variant under a sampler (DDIM, DPM-Solver++): the tiles run through sr3_unet_forward, '
                                       'which has no step-index -> timestep map (t_map); use the ancestral sampler (set_sampler(None)) '
                                       'or whole-image steps (set_tiling(None))')
 
@@ -291,7 +374,8 @@ class EngineDiffusion(nn.Module):
         un = self.denoise_fn
         key = (tuple(shape), None if cond_shape is None else tuple(cond_shape), str(dev), self.num_timesteps,
                un.weights().data_ptr(), un.freq.data_ptr(), un.plan.generation, bool(item_streams),
-               None if self.sampler is None else (self.sampler['steps'], self.sampler['eta']),
+               None if self.sampler is None else (self.sampler['steps'], self.sampler['eta'], self.sampler['type'],
+                                                  self.sampler.get('walk', 'time')),
                None if tiles is None else tiles['key'])      # tiled loop: ((tile_h, tile_w), overlap, tile_batch); the geometry is the tile's
         st = self._loop_cache.get(key)
         if st is None:
@@ -300,6 +384,8 @@ class EngineDiffusion(nn.Module):
                       cond=None if cond_shape is None else torch.empty(cond_shape, device=dev),
                       step=torch.zeros(2, dtype=torch.int32, device=dev), graph=None, ws=E.Workspace(),      # [scratch, t]
                       gens=[torch.Generator(device=dev) for _ in range(shape[0])] if item_streams else None)
+            if self.sampler is not None and self._sampler_c3 is not None:
+                st['hist'] = torch.zeros(shape, device=dev)      # a multistep sampler: the previous step's x0 (_sample_loop zero-fills it per chain)
             if tiles is not None:
                 self._tile_buffers(st, tiles, shape, cond_shape, dev)
             # keep the states of a few image sizes alive (a folder of mixed sizes alternates between them without recapturing);
@@ -357,8 +443,9 @@ class EngineDiffusion(nn.Module):
             noisy = self.sampler['eta'] > 0.0
             tables = (self._sampler_a, self._sampler_b, self._sampler_c1, self._sampler_c2, self._sampler_sigma)
             level = self._sampler_level
+        c3 = None if self.sampler is None else self._sampler_c3      # a multistep sampler: + the history, a whole-image buffer as z is
         st['z_used'] = noisy
-        st['tables'] = (tables, level)         # a captured graph bakes their addresses in: they live as long as the state
+        st['tables'] = (tables, level, c3)     # a captured graph bakes their addresses in: they live as long as the state
         if noisy and draw_noise:
             self._draw(st['z'], st['gens'])
         g, img = st['grid'], st['img']
@@ -369,10 +456,11 @@ class EngineDiffusion(nn.Module):
                             level_table=level, step_dev=st['step'][1:], out=st['eps_tiles'][first:first + n], ws=st['ws'])
         B, Cc, H, W = img.shape
         a, b, c1, c2, sg = tables
-        L.check(L.load().sr3_tiled_step(L.ptr(img), L.ptr(st['eps_tiles']), B, Cc, H, W, L.ptr(st['oy']), g.ny, L.ptr(st['ox']), g.nx,
-                                        L.ptr(st['wy']), L.ptr(st['wx']), g.th, g.tw, st['oy_host'], st['ox_host'],
-                                        L.ptr(st['z']) if noisy else None, L.ptr(a), L.ptr(b), L.ptr(c1), L.ptr(c2), L.ptr(sg),
-                                        L.ptr(st['step']), 1, L.ptr(st['eps']), self._stream(img.device)))
+        L.check(L.load().sr3_tiled_step_hist(L.ptr(img), L.ptr(st['eps_tiles']), B, Cc, H, W, L.ptr(st['oy']), g.ny, L.ptr(st['ox']), g.nx,
+                                             L.ptr(st['wy']), L.ptr(st['wx']), g.th, g.tw, st['oy_host'], st['ox_host'],
+                                             L.ptr(st['z']) if noisy else None, L.ptr(a), L.ptr(b), L.ptr(c1), L.ptr(c2), L.ptr(sg),
+                                             L.ptr(st['step']), 1, L.ptr(st['eps']), self._stream(img.device), L.ptr(c3),
+                                             None if c3 is None else L.ptr(st['hist'])))
 
     @staticmethod
     def _draw(t, gens):
@@ -403,16 +491,18 @@ class EngineDiffusion(nn.Module):
     def _one_sampler_step(self, st, draw_noise=True):
         """The same call over the sampler's tables: the counter is the step index j, the SR3 level comes from the walk's level table,
         the DDPM timestep from the map tau.  eta = 0: nothing is drawn and the step gets no z (st['z_used'] records it) -- a graph
-        captured from it has no RNG node."""
+        captured from it has no RNG node.  A multistep sampler passes its c3 table and the state's history buffer along."""
         noisy = self.sampler['eta'] > 0.0
         st['z_used'] = noisy
         if noisy and draw_noise:
             self._draw(st['z'], st['gens'])
         tables = (self._sampler_a, self._sampler_b, self._sampler_c1, self._sampler_c2, self._sampler_sigma)
         t_map = self._sampler_tau if self.variant == 'ddpm' else None
-        st['tables'] = (tables, self._sampler_level, t_map)        # a captured graph bakes their addresses in: they live as long as the state
+        c3 = self._sampler_c3
+        st['tables'] = (tables, self._sampler_level, t_map, c3)    # a captured graph bakes their addresses in: they live as long as the state
         self.denoise_fn.reverse_step(st['img'], st['z'] if noisy else None, tables, st['step'], cond=st['cond'],
-                                     level_table=self._sampler_level, clip_denoised=True, eps_out=st['eps'], ws=st['ws'], t_map=t_map)
+                                     level_table=self._sampler_level, clip_denoised=True, eps_out=st['eps'], ws=st['ws'], t_map=t_map,
+                                     c3=c3, hist=None if c3 is None else st['hist'])
 
     def _capture(self, st):
         dev = st['img'].device
@@ -423,6 +513,7 @@ class EngineDiffusion(nn.Module):
         gstate = [g.get_state() for g in gens]
         keep_img = st['img'].clone()
         keep_step = st['step'].clone()
+        keep_hist = st['hist'].clone() if st.get('hist') is not None else None
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -431,6 +522,8 @@ class EngineDiffusion(nn.Module):
         torch.cuda.synchronize(dev)
         st['img'].copy_(keep_img)
         st['step'].copy_(keep_step)
+        if keep_hist is not None:
+            st['hist'].copy_(keep_hist)
         torch.cuda.set_rng_state(rng, dev)
         for gen, gs in zip(gens, gstate):
             gen.set_state(gs)
@@ -518,6 +611,8 @@ class EngineDiffusion(nn.Module):
             st['cond'].copy_(cond)
             if tiles is not None:              # the conditioning image does not change: cut into tiles once
                 self._gather_tiles(st, st['cond'], st['cond_tiles'], 0, st['cond_tiles'].shape[0])
+        if st.get('hist') is not None:         # the first step's c3 is 0, but 0 * (whatever the last chain left, a NaN for one) is not 0
+            st['hist'].zero_()
         st['step'].fill_(T - 1)                # (slot 1 = t of the next step; slot 0 is the step's scratch copy)
         n_snap = sum(1 for i in range(T) if i % inter == 0)
         B = shape[0]

@@ -184,11 +184,13 @@ def _check_same_size(x, cond):
 
 
 def reverse_step(plan, arena, freq, ws, x, z, tables, step2, cond=None, level_table=None, clip_denoised=True, eps_out=None,
-                 t_map=None):
-    """One whole reverse step in place on `x` (sr3_reverse_step_ex): eps = UNet(cat([cond, x], 1), level(t)); x <- p_sample update;
+                 t_map=None, c3=None, hist=None):
+    """One whole reverse step in place on `x` (sr3_reverse_step_hist): eps = UNet(cat([cond, x], 1), level(t)); x <- p_sample update;
     t <- t - 1, with t = step2[1] (int32 tensor of two).  `tables` = (a, b, c1, c2, sigma) schedule tables on the device, indexed
     by t like `level_table`.  `z` None: no noise is read (= 0).  `t_map` (int32 device tensor, one entry per value t takes): the
-    timestep the DDPM UNet is conditioned on at counter value t -- a sampler's walk through a subset of the timesteps; None: t."""
+    timestep the DDPM UNet is conditioned on at counter value t -- a sampler's walk through a subset of the timesteps; None: t.
+    `c3`, `hist` (both or neither): a multistep sampler's table of the previous x0's coefficient and the buffer, shaped like `x`, that
+    carries that x0 from step to step (x <- ... + c3[t] hist; hist <- this step's x0)."""
     if not x.is_cuda or not x.is_contiguous() or x.dtype != torch.float32:
         raise L.Sr3Error('reverse_step needs a contiguous fp32 GPU tensor (got %s, %s); there is no CPU fallback' % (x.device, x.dtype))
     B = x.shape[0]
@@ -208,9 +210,12 @@ def reverse_step(plan, arena, freq, ws, x, z, tables, step2, cond=None, level_ta
     a, b, c1, c2, sg = tables
     if t_map is not None and (t_map.dtype != torch.int32 or not t_map.is_contiguous() or t_map.device != x.device):
         raise L.Sr3Error('t_map must be a contiguous int32 tensor on the device of x')
-    L.check(plan.lib.sr3_reverse_step_ex(plan.handle, L.ptr(x), L.ptr(cond), cc, L.ptr(freq), L.ptr(level_table), L.ptr(step2),
-                                         L.ptr(arena), L.ptr(wsbuf), need, L.ptr(z), L.ptr(a), L.ptr(b), L.ptr(c1), L.ptr(c2), L.ptr(sg),
-                                         1 if clip_denoised else 0, L.ptr(eps_out), B, C.c_void_p(stream), L.ptr(t_map)))
+    if hist is not None and (hist.dtype != torch.float32 or not hist.is_contiguous() or hist.device != x.device or hist.shape != x.shape):
+        raise L.Sr3Error('hist must be a contiguous fp32 tensor of the shape and on the device of x')
+    L.check(plan.lib.sr3_reverse_step_hist(plan.handle, L.ptr(x), L.ptr(cond), cc, L.ptr(freq), L.ptr(level_table), L.ptr(step2),
+                                           L.ptr(arena), L.ptr(wsbuf), need, L.ptr(z), L.ptr(a), L.ptr(b), L.ptr(c1), L.ptr(c2), L.ptr(sg),
+                                           1 if clip_denoised else 0, L.ptr(eps_out), B, C.c_void_p(stream), L.ptr(t_map), L.ptr(c3),
+                                           L.ptr(hist)))
     return x
 
 

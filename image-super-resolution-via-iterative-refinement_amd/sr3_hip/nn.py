@@ -261,12 +261,13 @@ class EngineUNet(nn.Module):
                               level_table=level_table, step_dev=step_dev, out=out, **kw)
 
     def reverse_step(self, x, z, tables, step2, *, cond=None, level_table=None, clip_denoised=True, eps_out=None, ws=None,
-                     t_map=None):
+                     t_map=None, c3=None, hist=None):
         """One whole iteration of the reverse loop in place on `x` (engine.reverse_step): what `GaussianDiffusion.p_sample_loop`
         captures into its hipGraph."""
         self.ensure_derived()
         return E.reverse_step(self.plan, self.weights(), self.freq, self._ws if ws is None else ws, x, z, tables, step2,
-                              cond=cond, level_table=level_table, clip_denoised=clip_denoised, eps_out=eps_out, t_map=t_map)
+                              cond=cond, level_table=level_table, clip_denoised=clip_denoised, eps_out=eps_out, t_map=t_map, c3=c3,
+                              hist=hist)
 
     # ---- training step (forward + backward inside the engine) ------------------------------------
     def train_step(self, hr, cond, z, ca, cb, level, tstep, grad_scale, drop_seed=None):

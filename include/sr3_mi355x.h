@@ -263,6 +263,18 @@ int sr3_p_sample_step_ex(float* x_nchw, const float* eps_nchw, const float* z_nc
                          const float* tab_b, const float* tab_c1, const float* tab_c2, const float* tab_sigma,
                          const int* step_dev, const int64_t* t_per_sample, int step_host, int batch,
                          int elems_per_image, int clip_denoised, void* stream);
+/* The tail of a MULTISTEP sampler (DPM-Solver++(2M) in the tail's linear form): the update also takes the previous step's x0,
+ *   x0 = a[t] x - b[t] eps ; clamp(-1,1) if clip_denoised ; x = ((c1[t] x0 + c2[t] x) + c3[t] hist) + sigma[t] z ; hist <- x0
+ * every product and sum rounded separately in fp32, in exactly that association.  hist_nchw has the layout of x_nchw; an element's
+ * history is read and then overwritten by the thread that owns the element.  The caller zero-fills it before a chain's first step
+ * (whose c3 is 0: 0 * NaN is NaN).  tab_c3 and hist_nchw are both set or both NULL; both NULL is sr3_p_sample_step_ex, bit for bit.
+ * Any elems_per_image (a size that is no multiple of 4, or a pointer off a 16-byte boundary, takes the one-element-per-thread form).
+ * SR3_E_BADARG: NULL required pointer, non-positive size, only one of tab_c3 / hist_nchw, hist_nchw overlapping x_nchw or eps_nchw.
+ * Nothing is launched on a refusal. */
+int sr3_p_sample_step_hist(float* x_nchw, const float* eps_nchw, const float* z_nchw, const float* tab_a,
+                           const float* tab_b, const float* tab_c1, const float* tab_c2, const float* tab_sigma,
+                           const int* step_dev, const int64_t* t_per_sample, int step_host, int batch,
+                           int elems_per_image, int clip_denoised, const float* tab_c3, float* hist_nchw, void* stream);
 /* *step_dev -= 1 on the stream (loop counter of p_sample_loop, diffusion.py:193, for graph replay) */
 int sr3_step_decrement(int* step_dev, void* stream);
 
@@ -297,6 +309,19 @@ int sr3_reverse_step_ex(sr3_plan* plan, float* x_nchw, const float* cond_nchw, i
                         const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
                         const float* z_nchw, const float* tab_a, const float* tab_b, const float* tab_c1, const float* tab_c2,
                         const float* tab_sigma, int clip_denoised, float* eps_out_nchw, int batch, void* stream, const int* t_map);
+/* sr3_reverse_step_ex with the multistep tail of sr3_p_sample_step_hist in the output convolution's epilogue (its own instantiations of
+ * that kernel: the step without history runs the code it ran before):
+ *   x0 = clamp(a[j] x - b[j] eps) ; x = ((c1[j] x0 + c2[j] x) + c3[j] hist) + sigma[j] z ; hist <- x0.
+ *   tab_c3    : one more table indexed by the step index j;  hist_nchw : [B, C, H, W], 16-byte aligned, in / out -- zero-filled by the
+ *               caller before a chain's first step.  Both set or both NULL (NULL: sr3_reverse_step_ex, bit for bit).
+ * Still one capturable call with the same kernel nodes.  Bit-identical to sr3_unet_forward + sr3_p_sample_step_hist + sr3_step_decrement.
+ * SR3_E_BADARG besides sr3_reverse_step_ex's: only one of tab_c3 / hist_nchw; hist_nchw overlapping x_nchw or eps_out_nchw (checked
+ * before any launch). */
+int sr3_reverse_step_hist(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,
+                          const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
+                          const float* z_nchw, const float* tab_a, const float* tab_b, const float* tab_c1, const float* tab_c2,
+                          const float* tab_sigma, int clip_denoised, float* eps_out_nchw, int batch, void* stream, const int* t_map,
+                          const float* tab_c3, float* hist_nchw);
 
 /* ---- tiled sampling (engine extension; no reference counterpart) ------------------------------
  * An image larger than the training size is sampled as ONE chain whose eps comes from overlapping tiles of the training size: per
@@ -331,6 +356,15 @@ int sr3_tiled_step(float* x_nchw, const float* eps_tiles, int batch, int channel
                    const int* ox_dev, int nx, const float* wy_dev, const float* wx_dev, int th, int tw, const int* oy_host,
                    const int* ox_host, const float* z_nchw, const float* tab_a, const float* tab_b, const float* tab_c1,
                    const float* tab_c2, const float* tab_sigma, int* step2_dev, int clip_denoised, float* eps_out_nchw, void* stream);
+/* sr3_tiled_step with the multistep tail: the blend first, then sr3_p_sample_step_hist's operations on the whole image.  tab_c3 /
+ * hist_nchw ([batch, channels, height, width], a whole-image buffer as z_nchw is): both set or both NULL (NULL: sr3_tiled_step, bit for
+ * bit).  SR3_E_BADARG besides sr3_tiled_step's: only one of the two; hist_nchw overlapping x_nchw or eps_out_nchw.  SR3_E_ALIGN: width
+ * % 4 == 0 and hist_nchw not 16-byte aligned.  Nothing is launched on a refusal. */
+int sr3_tiled_step_hist(float* x_nchw, const float* eps_tiles, int batch, int channels, int height, int width, const int* oy_dev, int ny,
+                        const int* ox_dev, int nx, const float* wy_dev, const float* wx_dev, int th, int tw, const int* oy_host,
+                        const int* ox_host, const float* z_nchw, const float* tab_a, const float* tab_b, const float* tab_c1,
+                        const float* tab_c2, const float* tab_sigma, int* step2_dev, int clip_denoised, float* eps_out_nchw, void* stream,
+                        const float* tab_c3, float* hist_nchw);
 
 /* q_sample (model/sr3_modules/diffusion.py:212-219; model/ddpm_modules/diffusion.py:259-267):
  * out = ca[b] * x0 + cb[b] * z */

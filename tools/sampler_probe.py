@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""What a replayed reverse step costs under the strided DDIM sampler (GaussianDiffusion.set_sampler) next to the ancestral step: the
+"""What a replayed reverse step costs under a sampler (GaussianDiffusion.set_sampler) next to the ancestral step: the
 captured step graph of the BASELINE config at its batch, replayed --replays times per leg and timed with HIP events -- the ancestral
-loop, the sampler at eta = 0 (no RNG node, no z read) and at eta = 0.5 -- legs interleaved --reps times, best and median per leg; then
+loop, the DDIM sampler at eta = 0 (no RNG node, no z read) and at eta = 0.5, and the multistep solver dpmpp_2m (eta = 0, plus one read
+and one write of the image-sized history in the output conv's epilogue) -- legs interleaved --reps times, best and median per leg; then
 the wall time of whole `super_resolution` chains of --chain steps (capture excluded).
     python tools/sampler_probe.py [--config sr3_16_128] [--replays 200] [--reps 3] [--chain 100]      (GPU box)"""
 import argparse
@@ -40,10 +41,11 @@ def main():
     shape = (B, 3, S, S)
     cond = (torch.rand(shape, device=dev) * 2 - 1) if cfg['conditional'] else None
     N = a.replays
-    legs = {'ancestral': None, 'ddim_eta0': (N, 0.0), 'ddim_eta0.5': (N, 0.5)}
+    legs = {'ancestral': dict(steps=None), 'ddim_eta0': dict(steps=N, eta=0.0), 'ddim_eta0.5': dict(steps=N, eta=0.5),
+            'dpmpp_2m': dict(steps=N, kind='dpmpp_2m')}
     states = {}
     for name, spec in legs.items():                      # one captured graph per leg, all alive at once
-        netG.set_sampler(*(spec or (None,)))
+        netG.set_sampler(**spec)
         st = netG._loop_state(shape, shape if cond is not None else None, dev)
         netG.denoise_fn.ensure_derived()
         if cond is not None:
@@ -54,6 +56,8 @@ def main():
     for rep in range(a.reps + 1):                        # (rep 0 warms up)
         for name, st in states.items():
             st['img'].copy_(torch.randn(shape, device=dev))
+            if st.get('hist') is not None:
+                st['hist'].zero_()
             st['step'].fill_(N - 1)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
@@ -69,8 +73,8 @@ def main():
     for name in legs:
         rec['ms_per_step_' + name] = {'best': min(ms[name]), 'median': statistics.median(ms[name])}
     arg = cond if cond is not None else shape
-    for eta in (0.0, 0.5):
-        netG.set_sampler(a.chain, eta)
+    for kind, eta in (('ddim', 0.0), ('ddim', 0.5), ('dpmpp_2m', 0.0)):
+        netG.set_sampler(a.chain, eta, kind=kind)
         netG.p_sample_loop(arg)                          # capture + one chain (warm)
         torch.cuda.synchronize()
         walls = []
@@ -80,7 +84,7 @@ def main():
             torch.cuda.synchronize()
             walls.append(time.perf_counter() - t0)
         assert bool(torch.isfinite(out).all())
-        rec['chain_%d_steps_eta%g_wall_s' % (a.chain, eta)] = {'best': min(walls), 'median': statistics.median(walls)}
+        rec['chain_%d_steps_%seta%g_wall_s' % (a.chain, '' if kind == 'ddim' else kind + '_', eta)] = {'best': min(walls), 'median': statistics.median(walls)}
     print(json.dumps(rec))
 
 
