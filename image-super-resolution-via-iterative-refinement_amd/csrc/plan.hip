@@ -1175,16 +1175,8 @@ int sr3_reverse_step_hist(sr3_plan* plan, float* x_nchw, const float* cond_nchw,
     return SR3_E_ALIGN;
   }
   if (plan->d.variant == SR3_VARIANT_SR3 && !level_table) { set_error("SR3 variant needs level_table"); return SR3_E_BADARG; }
-  if ((tc3 != nullptr) != (hist_nchw != nullptr)) { set_error("reverse_step: tab_c3 and hist_nchw go together (both or neither)"); return SR3_E_BADARG; }
-  if (hist_nchw) {
-    if ((uintptr_t)hist_nchw & 15) { set_error("misaligned pointer (hist: 16 B)"); return SR3_E_ALIGN; }
-    const size_t bytes = (size_t)batch * plan->d.out_channel * plan_height(plan) * plan_width(plan) * sizeof(float);
-    const uintptr_t h0 = (uintptr_t)hist_nchw;
-    for (const float* p : {static_cast<const float*>(x_nchw), static_cast<const float*>(eps_out_nchw)}) {
-      const uintptr_t p0 = (uintptr_t)p;
-      if (p && p0 < h0 + bytes && h0 < p0 + bytes) { set_error("reverse_step: hist_nchw overlaps x_nchw or eps_out_nchw"); return SR3_E_BADARG; }
-    }
-  }
+  const size_t image_bytes = (size_t)batch * plan->d.out_channel * plan_height(plan) * plan_width(plan) * sizeof(float);
+  if (const int rc = check_step_history("reverse_step", tc3, hist_nchw, x_nchw, eps_out_nchw, image_bytes, true)) return rc;
   StepFuse f;
   f.x = x_nchw; f.z = z_nchw; f.tb = StepTables{ta, tb, tc1, tc2, tsig};
   f.step_cur = step2_dev; f.step_next = step2_dev + 1; f.clip = clip_denoised; f.c3 = tc3; f.hist = hist_nchw;

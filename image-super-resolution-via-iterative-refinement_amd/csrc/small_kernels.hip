@@ -8,11 +8,6 @@
 namespace sr3 {
 
 __device__ __forceinline__ float silu_s(float v) { return SR3_SILU(v); }
-// separately rounded product / sum: the empty asm makes the value opaque so hipcc (default
-// -ffp-contract=fast) cannot fuse it into an fma -- bit parity with torch's elementwise ops.
-__device__ __forceinline__ float mul_rn(float a, float b) { float r = a * b; asm volatile("" : "+v"(r)); return r; }
-__device__ __forceinline__ float add_rn(float a, float b) { float r = a + b; asm volatile("" : "+v"(r)); return r; }
-__device__ __forceinline__ float sub_rn(float a, float b) { float r = a - b; asm volatile("" : "+v"(r)); return r; }
 
 // ---------------------------------------------------------------------------------------------
 // GroupNorm statistics (nn.GroupNorm, model/sr3_modules/unet.py:84,119) as PARTIAL per-(image,
@@ -573,10 +568,10 @@ int conv_in_nchw(const float* a, int Ca, const float* b, int Cb, int B, int H, i
 constexpr int OT_H = 8, OT_W = 32, OT_CK = 16, OT_LD = 20;
 // COUT: output channels (1..4); FULL: C is a multiple of the 16-channel chunk (no per-quad bound checks)
 // FUSE (sr3_reverse_step): the reverse-step update of the image this eps belongs to in the epilogue -- the element a thread produces IS the
-// element of eps the elementwise update (sr3 diffusion.py:141-149,162-174) needs, in the same NCHW position -- with k_p_sample_update's
-// separately rounded operations (bit-identical to the two-kernel form), and the loop counter's decrement by one thread
-// HIST (with FUSE; sr3_reverse_step_hist): the multistep tail -- + c3[t] * hist before the noise term, hist <- x0 -- as its own
-// instantiations, so the tail of the step without history carries no branch for it
+// element of eps the elementwise update needs, in the same NCHW position -- step_tail (sr3_common.h), as k_p_sample_update runs it
+// (bit-identical to the two-kernel form), and the loop counter's decrement by one thread
+// HIST (with FUSE; sr3_reverse_step_hist): the multistep tail as its own instantiations, so the tail of the step without history
+// carries no branch for it
 template <int COUT, bool FULL, bool FUSE, bool HIST>
 __global__ __launch_bounds__(256) void k_conv_out_nchw(const float* __restrict__ x, const float* __restrict__ ss,
                                                         int B, int H, int W, int C, const float* __restrict__ w,
@@ -634,12 +629,10 @@ __global__ __launch_bounds__(256) void k_conv_out_nchw(const float* __restrict__
     }
   }
   const int oh = h0 + ty, ow = w0 + tx;
-  int t = 0;
-  float ca = 0.f, cbb = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f, sg = 0.f;
+  StepCoef cf = {};
   if (FUSE) {
-    t = f.step_cur[0];
-    ca = f.tb.a[t]; cbb = f.tb.b[t]; c1 = f.tb.c1[t]; c2 = f.tb.c2[t]; sg = f.tb.sigma[t];
-    if (HIST) c3 = f.c3[t];
+    const int t = f.step_cur[0];
+    cf = load_step_coef<HIST>(f.tb, f.c3, t);
     if (blockIdx.x == 0 && tid == 0) f.step_next[0] = t - 1;       // (nobody reads this slot before the next step's first kernel)
   }
   if (oh < H && ow < W) {
@@ -648,16 +641,12 @@ __global__ __launch_bounds__(256) void k_conv_out_nchw(const float* __restrict__
       const size_t idx = (((size_t)b * Cout + co) * H + oh) * W + ow;
       const float e = acc[co] + (bias ? bias[co] : 0.f);
       if (!FUSE || out) out[idx] = e;
-      if (FUSE) {
+      if (FUSE) {                    // (this thread alone reads and writes the element's history)
         const float xv = f.x[idx], zv = f.z ? f.z[idx] : 0.f;
-        float x0 = sub_rn(mul_rn(ca, xv), mul_rn(cbb, e));
-        if (f.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-        float mean = add_rn(mul_rn(c1, x0), mul_rn(c2, xv));
-        if (HIST) {                  // (this thread alone reads and writes the element's history)
-          mean = add_rn(mean, mul_rn(c3, f.hist[idx]));
-          f.hist[idx] = x0;
-        }
-        f.x[idx] = add_rn(mean, mul_rn(zv, sg));
+        float hv = HIST ? f.hist[idx] : 0.f;
+        const float xn = step_tail<HIST>(cf, f.clip, xv, e, zv, hv);
+        if (HIST) f.hist[idx] = hv;
+        f.x[idx] = xn;
       }
     }
   }
@@ -672,7 +661,7 @@ int conv_out_nchw(const float* x, const float* ss, int B, int H, int W, int C, c
   StepFuse f;
   memset(&f, 0, sizeof(f));
   if (fuse) f = *fuse;
-  if (fuse && (fuse->hist != nullptr) != (fuse->c3 != nullptr)) { set_error("conv_out: the step's c3 table and history go together"); return SR3_E_BADARG; }
+  if (const int rc = check_step_history("conv_out", f.c3, f.hist, f.x, out_nchw, (size_t)B * Cout * H * W * sizeof(float))) return rc;
   const bool hist = fuse && fuse->hist;
 #define SR3_CO_LAUNCH3(N, FU, FS, HI)                                                                                        \
   hipLaunchKernelGGL((k_conv_out_nchw<N, FU, FS, HI>), dim3(tiles), dim3(256), 0, st, x, ss, B, H, W, C, w, bias, Cout, out_nchw, f);
@@ -761,16 +750,12 @@ int embed_forward(const EmbedParams& p, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Fused reverse step (sr3 diffusion.py:141-149,162-174; ddpm :151-198):
-//   x0 = a_t x - b_t eps ; clamp[-1,1] ; mean = c1_t x0 + c2_t x ; x <- mean + sigma_t z
-// sigma_t = exp(0.5 logvar_t) with sigma_0 := 0 (the reference's `t > 0` branch / nonzero_mask).
-// Each product/sum is rounded separately (no contraction) so the update is bit-identical to the
-// reference's elementwise torch ops for the same eps.  t comes from a device counter (graph
-// replay), a per-sample int64 array (DDPM API) or the host.
+// Fused reverse step: step_tail (sr3_common.h) on every element of x, with
+// sigma_t = exp(0.5 logvar_t) and sigma_0 := 0 (the reference's `t > 0` branch / nonzero_mask).
+// t comes from a device counter (graph replay), a per-sample int64 array (DDPM API) or the host.
 // ---------------------------------------------------------------------------------------------
-// HIST (sr3_p_sample_step_hist): the multistep tail -- x <- (mean + c3_t hist) + sigma_t z, hist <- x0 (after the clamp), the element's
-// history read and written by the thread that owns the element.  V = 4: a thread owns four consecutive elements (per-image size % 4 == 0,
-// so the four lie in one image); V = 1: one element, any size.
+// HIST (sr3_p_sample_step_hist): the multistep tail, the element's history read and written by the thread that owns the element.
+// V = 4: a thread owns four consecutive elements (per-image size % 4 == 0, so the four lie in one image); V = 1: one element, any size.
 template <bool CLIP, bool HIST, int V>
 __global__ __launch_bounds__(256) void k_p_sample_update(float* __restrict__ x, const float* __restrict__ eps,
                                                           const float* __restrict__ z, StepTables tb,
@@ -782,8 +767,7 @@ __global__ __launch_bounds__(256) void k_p_sample_update(float* __restrict__ x, 
     const size_t e0 = i * V;
     const int b = (int)(e0 / per_image);
     const int t = step_dev ? step_dev[0] : (tps ? (int)tps[b] : step_host);
-    const float a = tb.a[t], bb = tb.b[t], c1 = tb.c1[t], c2 = tb.c2[t], sg = tb.sigma[t];
-    const float c3 = HIST ? tc3[t] : 0.f;
+    const StepCoef cf = load_step_coef<HIST>(tb, tc3, t);
     float xv[V], ev[V], zv[V], hv[V];
     if constexpr (V == 4) {
       const f32x4 xq = *reinterpret_cast<const f32x4*>(x + e0);
@@ -797,13 +781,7 @@ __global__ __launch_bounds__(256) void k_p_sample_update(float* __restrict__ x, 
       xv[0] = x[e0]; ev[0] = eps[e0]; zv[0] = z ? z[e0] : 0.f; hv[0] = HIST ? hist[e0] : 0.f;
     }
 #pragma unroll
-    for (int k = 0; k < V; ++k) {
-      float x0 = sub_rn(mul_rn(a, xv[k]), mul_rn(bb, ev[k]));
-      if (CLIP) x0 = fminf(fmaxf(x0, -1.f), 1.f);          // clip_denoised (sr3 diffusion.py:162-163)
-      float mean = add_rn(mul_rn(c1, x0), mul_rn(c2, xv[k]));
-      if (HIST) { mean = add_rn(mean, mul_rn(c3, hv[k])); hv[k] = x0; }
-      xv[k] = add_rn(mean, mul_rn(zv[k], sg));
-    }
+    for (int k = 0; k < V; ++k) xv[k] = step_tail<HIST>(cf, CLIP, xv[k], ev[k], zv[k], hv[k]);
     if constexpr (V == 4) {
       const f32x4 xo = {xv[0], xv[1], xv[2], xv[3]};
       *reinterpret_cast<f32x4*>(x + e0) = xo;
@@ -832,15 +810,8 @@ static void launch_p_sample_update(float* x, const float* eps, const float* z, c
 
 int p_sample_update(float* x, const float* eps, const float* z, StepTables tb, const int* step_dev,
                     const int64_t* t_per_sample, int step_host, int B, int per_image, hipStream_t st, bool clip, const float* c3, float* hist) {
-  if ((hist != nullptr) != (c3 != nullptr)) { set_error("p_sample_update: the c3 table and the history go together (both or neither)"); return SR3_E_BADARG; }
   const size_t elems = (size_t)B * per_image;
-  if (hist) {
-    const uintptr_t h0 = (uintptr_t)hist, h1 = h0 + elems * sizeof(float);
-    for (const float* p : {static_cast<const float*>(x), eps}) {
-      const uintptr_t p0 = (uintptr_t)p;
-      if (p0 < h1 && h0 < p0 + elems * sizeof(float)) { set_error("p_sample_update: the history overlaps x or eps"); return SR3_E_BADARG; }
-    }
-  }
+  if (const int rc = check_step_history("p_sample_update", c3, hist, x, eps, elems * sizeof(float))) return rc;
   // four elements per thread where an image is a whole number of quads and every tensor allows a 16-byte access; else one
   const bool vec = (per_image & 3) == 0 && ((((uintptr_t)x | (uintptr_t)eps | (uintptr_t)z | (uintptr_t)hist) & 15) == 0);
   if (clip) {

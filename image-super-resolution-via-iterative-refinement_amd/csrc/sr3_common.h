@@ -290,8 +290,48 @@ int conv_in_nchw(const float* a, int Ca, const float* b, int Cb, int B, int H, i
                  const float* bias, int Cout, float* out, double* ostat, hipStream_t st);
 // fused reverse-step update (NCHW, elementwise): coef = {a, b, c1, c2, sigma} tables of length T
 struct StepTables { const float* a; const float* b; const float* c1; const float* c2; const float* sigma; };
-// the tail of one reverse step folded into the output conv's epilogue (sr3_reverse_step): x <- p_sample update(x, eps, z, t) with
-// t = *step_cur, the same separately rounded operations as k_p_sample_update (bit-identical), and *step_next = t - 1 (one thread)
+
+// ---- the tail of a reverse step (sr3 diffusion.py:141-149,162-174; ddpm :151-198), defined here once ----
+//   x0 = a_t x - b_t eps ; clamp[-1,1] ; mean = c1_t x0 + c2_t x (+ c3_t hist ; hist <- x0) ; x <- mean + sigma_t z
+// Every product, sum and difference is rounded on its own: the empty asm makes the value opaque, so hipcc (default
+// -ffp-contract=fast) cannot fuse it into an fma.  That makes the update bit-identical to the reference's elementwise torch ops for
+// the same eps -- and its three users (k_p_sample_update, the FUSE epilogue of k_conv_out_nchw, k_tiled_step) to one another.
+__device__ __forceinline__ float mul_rn(float a, float b) { float r = a * b; asm volatile("" : "+v"(r)); return r; }
+__device__ __forceinline__ float add_rn(float a, float b) { float r = a + b; asm volatile("" : "+v"(r)); return r; }
+__device__ __forceinline__ float sub_rn(float a, float b) { float r = a - b; asm volatile("" : "+v"(r)); return r; }
+struct StepCoef { float a, b, c1, c2, c3, sigma; };
+// row t of the tables; HIST false: no history, the c3 table is not read
+template <bool HIST>
+__device__ __forceinline__ StepCoef load_step_coef(const StepTables& tb, const float* c3, int t) {
+  return StepCoef{tb.a[t], tb.b[t], tb.c1[t], tb.c2[t], HIST ? c3[t] : 0.f, tb.sigma[t]};
+}
+// one element: returns the new x.  HIST (the multistep tail): + c3 hist before the noise term, then hist <- x0 (after the clamp);
+// the caller's thread owns the element's history, loads it before and stores it after.  clip: clip_denoised (sr3 diffusion.py:162-163)
+template <bool HIST>
+__device__ __forceinline__ float step_tail(const StepCoef& k, bool clip, float x, float eps, float z, float& hist) {
+  float x0 = sub_rn(mul_rn(k.a, x), mul_rn(k.b, eps));
+  if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+  float mean = add_rn(mul_rn(k.c1, x0), mul_rn(k.c2, x));
+  if (HIST) { mean = add_rn(mean, mul_rn(k.c3, hist)); hist = x0; }
+  return add_rn(mean, mul_rn(z, k.sigma));
+}
+// host check of a step's history arguments, before anything is launched: c3 and hist both or neither; hist (`bytes` long, as x and eps
+// are) overlaps neither x nor eps (eps may be null); align16: the caller's kernel needs hist 16-byte aligned
+inline int check_step_history(const char* who, const float* c3, const float* hist, const float* x, const float* eps, size_t bytes,
+                              bool align16 = false) {
+  if ((c3 != nullptr) != (hist != nullptr)) { set_error("%s: the c3 table and the history go together (both or neither)", who); return SR3_E_BADARG; }
+  if (!hist) return SR3_OK;
+  const uintptr_t h0 = (uintptr_t)hist;
+  if (align16 && (h0 & 15)) { set_error("misaligned pointer (hist: 16 B)"); return SR3_E_ALIGN; }
+  for (const float* p : {x, eps}) {
+    const uintptr_t p0 = (uintptr_t)p;
+    if (p && p0 < h0 + bytes && h0 < p0 + bytes) { set_error("%s: the history overlaps x or eps", who); return SR3_E_BADARG; }
+  }
+  return SR3_OK;
+}
+
+// the state of a step's tail behind a kernel that produces eps (the output conv's epilogue: sr3_reverse_step; the tile blend:
+// sr3_tiled_step): x <- step_tail(x, eps, z) at t = *step_cur, and *step_next = t - 1 (one thread)
 struct StepFuse {
   float* x;               // [B, Cout, H, W] in / out
   const float* z;         // noise or null (= 0)

@@ -12,11 +12,6 @@
 namespace sr3 {
 namespace {
 
-// separately rounded product / sum / difference (small_kernels.hip): the p_sample tail below is k_p_sample_update's, operation for operation
-__device__ __forceinline__ float mul_rn(float a, float b) { float r = a * b; asm volatile("" : "+v"(r)); return r; }
-__device__ __forceinline__ float add_rn(float a, float b) { float r = a + b; asm volatile("" : "+v"(r)); return r; }
-__device__ __forceinline__ float sub_rn(float a, float b) { float r = a - b; asm volatile("" : "+v"(r)); return r; }
-
 __device__ __forceinline__ int clamp_origin(int o, int L, int t) { return min(max(o, 0), L - t); }
 
 // four consecutive floats at p: one 16-byte load where p allows
@@ -48,18 +43,12 @@ __global__ __launch_bounds__(256) void k_tile_gather(const float* __restrict__ s
 }
 
 struct TiledStep {
-  float* x;                  // [B, C, H, W] in / out
+  StepFuse f;                // the step's tail on x [B, C, H, W]; step_cur: k_step_copy put j there (clip: the kernel's template argument rules)
   const float* eps;          // [B * ny * nx, C, th, tw]
   const int* oy; const int* ox;
   const float* wy; const float* wx;
-  const float* z;            // or null (= 0)
   float* eps_out;            // or null
-  StepTables tb;
-  const int* step_cur;       // j of this step (k_step_copy put it there)
-  int* step_next;            // j - 1 goes here
   int C, H, W, ny, nx, th, tw;
-  const float* c3;           // multistep tail (both set or both null): table of the previous x0's coefficient, indexed like tb
-  float* hist;               // ... and the previous step's x0, [B, C, H, W]
 };
 
 // the tiles covering coordinate p along one axis are a contiguous range of the (increasing) origin list
@@ -125,14 +114,14 @@ __device__ __forceinline__ f32x4 blend_quad(const TiledStep& s, int b, int c, in
 }
 
 // x <- p_sample update of (x, blended eps, z) at step index j = *step_cur; *step_next = j - 1.  V = 4: a thread owns four x positions
-// (W % 4 == 0, x / z / eps_out / hist 16-byte aligned); V = 1: one.  HIST: the multistep tail of k_p_sample_update -- + c3[j] * hist before
-// the noise term, hist <- x0, by the thread that owns the element.
+// (W % 4 == 0, x / z / eps_out / hist 16-byte aligned); V = 1: one.  The update is step_tail (sr3_common.h), as k_p_sample_update runs
+// it; HIST: its multistep tail, the history read and written by the thread that owns the element.
 template <int V, bool CLIP, bool HIST>
 __global__ __launch_bounds__(256) void k_tiled_step(TiledStep s, size_t total) {
-  const int j = s.step_cur[0];
-  if (blockIdx.x == 0 && threadIdx.x == 0) s.step_next[0] = j - 1;      // (nobody reads this slot before the next step's first kernel)
-  const float a = s.tb.a[j], bb = s.tb.b[j], c1 = s.tb.c1[j], c2 = s.tb.c2[j], sg = s.tb.sigma[j];
-  const float c3 = HIST ? s.c3[j] : 0.f;
+  const StepFuse& f = s.f;
+  const int j = f.step_cur[0];
+  if (blockIdx.x == 0 && threadIdx.x == 0) f.step_next[0] = j - 1;      // (nobody reads this slot before the next step's first kernel)
+  const StepCoef cf = load_step_coef<HIST>(f.tb, f.c3, j);
   const int wv = s.W / V;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int x0 = (int)(i % wv) * V;
@@ -159,44 +148,38 @@ __global__ __launch_bounds__(256) void k_tiled_step(TiledStep s, size_t total) {
           ev[k] = blend_pixel(s, b, c, y, x0 + k, iy0, iy1, jx0, jx1);
         }
       }
-      const f32x4 xq = *reinterpret_cast<const f32x4*>(s.x + e0);
+      const f32x4 xq = *reinterpret_cast<const f32x4*>(f.x + e0);
       f32x4 zq = {0.f, 0.f, 0.f, 0.f};
-      if (s.z) zq = *reinterpret_cast<const f32x4*>(s.z + e0);
+      if (f.z) zq = *reinterpret_cast<const f32x4*>(f.z + e0);
 #pragma unroll
       for (int k = 0; k < V; ++k) { xv[k] = xq[k]; zv[k] = zq[k]; }
       if (HIST) {
-        const f32x4 hq = *reinterpret_cast<const f32x4*>(s.hist + e0);
+        const f32x4 hq = *reinterpret_cast<const f32x4*>(f.hist + e0);
 #pragma unroll
         for (int k = 0; k < V; ++k) hv[k] = hq[k];
       }
     } else {
       ev[0] = blend_pixel(s, b, c, y, x0, iy0, iy1, ix0, ix1);
-      xv[0] = s.x[e0];
-      zv[0] = s.z ? s.z[e0] : 0.f;
-      if (HIST) hv[0] = s.hist[e0];
+      xv[0] = f.x[e0];
+      zv[0] = f.z ? f.z[e0] : 0.f;
+      if (HIST) hv[0] = f.hist[e0];
     }
 #pragma unroll
-    for (int k = 0; k < V; ++k) {
-      float p0 = sub_rn(mul_rn(a, xv[k]), mul_rn(bb, ev[k]));
-      if (CLIP) p0 = fminf(fmaxf(p0, -1.f), 1.f);
-      float mean = add_rn(mul_rn(c1, p0), mul_rn(c2, xv[k]));
-      if (HIST) { mean = add_rn(mean, mul_rn(c3, hv[k])); hv[k] = p0; }
-      xv[k] = add_rn(mean, mul_rn(zv[k], sg));
-    }
+    for (int k = 0; k < V; ++k) xv[k] = step_tail<HIST>(cf, CLIP, xv[k], ev[k], zv[k], hv[k]);
     if constexpr (V == 4) {
       const f32x4 o = {xv[0], xv[1], xv[2], xv[3]};
-      *reinterpret_cast<f32x4*>(s.x + e0) = o;
+      *reinterpret_cast<f32x4*>(f.x + e0) = o;
       if (HIST) {
         const f32x4 ho = {hv[0], hv[1], hv[2], hv[3]};
-        *reinterpret_cast<f32x4*>(s.hist + e0) = ho;
+        *reinterpret_cast<f32x4*>(f.hist + e0) = ho;
       }
       if (s.eps_out) {
         const f32x4 eo = {ev[0], ev[1], ev[2], ev[3]};
         *reinterpret_cast<f32x4*>(s.eps_out + e0) = eo;
       }
     } else {
-      s.x[e0] = xv[0];
-      if (HIST) s.hist[e0] = hv[0];
+      f.x[e0] = xv[0];
+      if (HIST) f.hist[e0] = hv[0];
       if (s.eps_out) s.eps_out[e0] = ev[0];
     }
   }
@@ -263,19 +246,10 @@ int sr3_tiled_step_hist(float* x_nchw, const float* eps_tiles, int batch, int ch
   if (total >= ((size_t)1 << 31) || (size_t)batch * ny * nx >= ((size_t)1 << 31)) { set_error("tiled_step: image batch too large (B * C * H * W >= 2^31)"); return SR3_E_UNSUPPORTED; }
   if (oy_host) { if (const int rc = check_origins("y", oy_host, ny, height, th)) return rc; }
   if (ox_host) { if (const int rc = check_origins("x", ox_host, nx, width, tw)) return rc; }
-  if ((tc3 != nullptr) != (hist_nchw != nullptr)) { set_error("tiled_step: tab_c3 and hist_nchw go together (both or neither)"); return SR3_E_BADARG; }
-  if (hist_nchw) {
-    const uintptr_t h0 = (uintptr_t)hist_nchw, bytes = total * sizeof(float);
-    for (const float* p : {static_cast<const float*>(x_nchw), static_cast<const float*>(eps_out_nchw)}) {
-      const uintptr_t p0 = (uintptr_t)p;
-      if (p && p0 < h0 + bytes && h0 < p0 + bytes) { set_error("tiled_step: hist_nchw overlaps x_nchw or eps_out_nchw"); return SR3_E_BADARG; }
-    }
-  }
+  if (const int rc = check_step_history("tiled_step", tc3, hist_nchw, x_nchw, eps_out_nchw, total * sizeof(float))) return rc;
   TiledStep s;
-  s.x = x_nchw; s.eps = eps_tiles; s.oy = oy_dev; s.ox = ox_dev; s.wy = wy_dev; s.wx = wx_dev; s.z = z_nchw; s.eps_out = eps_out_nchw;
-  s.c3 = tc3; s.hist = hist_nchw;
-  s.tb = StepTables{ta, tb, tc1, tc2, tsig};
-  s.step_cur = step2_dev; s.step_next = step2_dev + 1;
+  s.f = StepFuse{x_nchw, z_nchw, StepTables{ta, tb, tc1, tc2, tsig}, step2_dev, step2_dev + 1, clip_denoised, tc3, hist_nchw};
+  s.eps = eps_tiles; s.oy = oy_dev; s.ox = ox_dev; s.wy = wy_dev; s.wx = wx_dev; s.eps_out = eps_out_nchw;
   s.C = channels; s.H = height; s.W = width; s.ny = ny; s.nx = nx; s.th = th; s.tw = tw;
   const bool vec = (width & 3) == 0;
   if (vec && (((uintptr_t)x_nchw & 15) || ((uintptr_t)z_nchw & 15) || ((uintptr_t)eps_out_nchw & 15) || ((uintptr_t)hist_nchw & 15))) { set_error("tiled_step: misaligned pointer (x, z, eps_out, hist: 16 B)"); return SR3_E_ALIGN; }

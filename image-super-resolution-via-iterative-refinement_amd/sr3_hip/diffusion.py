@@ -110,6 +110,11 @@ def sampler_walk(alphas_cumprod, steps, walk='time'):
 SAMPLER_KINDS = ('ddim', 'dpmpp_2m')
 
 
+def _check_sampler_kind(kind):
+    if kind not in SAMPLER_KINDS:
+        raise NotImplementedError('sampler type %r (only %s)' % (kind, ', '.join('"%s"' % k for k in SAMPLER_KINDS)))
+
+
 def sampler_tables(alphas_cumprod, steps, eta, *, kind='ddim', walk='time'):
     """Tables of a sampler over a walk through the schedule (`sampler_walk`) in the form of the engine's fused step tail,
 
@@ -239,8 +244,7 @@ class EngineDiffusion(nn.Module):
             self.set_sampler(None)
         else:
             kind = spec.get('type', 'ddim')
-            if kind not in SAMPLER_KINDS:
-                raise NotImplementedError('sampler type %r (only %s)' % (kind, ', '.join('"%s"' % k for k in SAMPLER_KINDS)))
+            _check_sampler_kind(kind)              # (an unknown type is refused before a missing "steps")
             if spec.get('steps') is None:
                 raise ValueError('sampler: "steps" is required')
             self.set_sampler(spec['steps'], spec.get('eta', 0.0), kind=kind, walk=spec.get('walk'))
@@ -264,8 +268,7 @@ class EngineDiffusion(nn.Module):
         else:
             if getattr(self, '_alphas_cumprod64', None) is None:
                 raise RuntimeError('set_sampler needs a noise schedule (set_new_noise_schedule first)')
-            if kind not in SAMPLER_KINDS:
-                raise NotImplementedError('sampler type %r (only %s)' % (kind, ', '.join('"%s"' % k for k in SAMPLER_KINDS)))
+            _check_sampler_kind(kind)
             if walk is None:
                 walk = 'logsnr' if kind == 'dpmpp_2m' else 'time'
             tabs = sampler_tables(self._alphas_cumprod64, steps, eta, kind=kind, walk=walk)
@@ -318,7 +321,13 @@ class EngineDiffusion(nn.Module):
     def _stream(self, dev):
         return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
-    def _step_update(self, x, eps, z, step_dev=None, t_per_sample=None, step_host=0, clip_denoised=True):
+    def _step_update(self, x, eps, z, t=None, *, step_dev=None, t_per_sample=None, step_host=0, clip_denoised=True):
+        """x <- p_sample update of (x, eps, z) on the schedule's own tables (sr3_p_sample_step_ex).  `t`: a tensor of per-sample
+        timesteps or one int; or, by keyword, where the kernel takes it from: a device counter, a per-sample int64 tensor, the host."""
+        if torch.is_tensor(t):
+            t_per_sample = t.long().contiguous()
+        elif t is not None:
+            step_host = int(t)
         lib = L.load()
         per = x[0].numel()
         L.check(lib.sr3_p_sample_step_ex(L.ptr(x), L.ptr(eps), L.ptr(z), L.ptr(self.sqrt_recip_alphas_cumprod),
@@ -340,10 +349,7 @@ class EngineDiffusion(nn.Module):
     def p_mean_variance(self, x, t, clip_denoised: bool, condition_x=None):
         eps = self._eps(x, t, condition_x)
         mean = x.clone()
-        if torch.is_tensor(t):
-            self._step_update(mean, eps, None, t_per_sample=t.long().contiguous(), clip_denoised=clip_denoised)
-        else:
-            self._step_update(mean, eps, None, step_host=int(t), clip_denoised=clip_denoised)
+        self._step_update(mean, eps, None, t, clip_denoised=clip_denoised)
         return mean, self._coef('posterior_log_variance_clipped', t, x)
 
     @torch.no_grad()
@@ -359,10 +365,7 @@ class EngineDiffusion(nn.Module):
                 else:
                     noise = torch.randn_like(x)
         out = x.clone()
-        if torch.is_tensor(t):
-            self._step_update(out, eps, noise, t_per_sample=t.long().contiguous(), clip_denoised=clip_denoised)
-        else:
-            self._step_update(out, eps, noise, step_host=int(t), clip_denoised=clip_denoised)
+        self._step_update(out, eps, noise, t, clip_denoised=clip_denoised)
         return out
 
     # ---- the reverse loop ------------------------------------------------------------------------
@@ -430,38 +433,6 @@ class EngineDiffusion(nn.Module):
         L.check(L.load().sr3_tile_gather(L.ptr(src), B, Cc, H, W, L.ptr(st['oy']), g.ny, L.ptr(st['ox']), g.nx, int(first), int(n),
                                          g.th, g.tw, L.ptr(dst), self._stream(src.device)))
 
-    def _one_tiled_step(self, st, draw_noise=True):
-        """One iteration of the tiled loop: z on the full image; per chunk of tiles, gather out of the running image and one UNet
-        forward at the tile geometry (level / timestep from the device counter); then the fused tail on the full image -- blend of the
-        tiles' eps, p_sample update, counter decrement (sr3_tiled_step).  st['eps'] keeps the blended eps."""
-        if self.sampler is None:
-            noisy = True
-            tables = (self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod, self.posterior_mean_coef1,
-                      self.posterior_mean_coef2, self._sigma)
-            level = self._level_table
-        else:
-            noisy = self.sampler['eta'] > 0.0
-            tables = (self._sampler_a, self._sampler_b, self._sampler_c1, self._sampler_c2, self._sampler_sigma)
-            level = self._sampler_level
-        c3 = None if self.sampler is None else self._sampler_c3      # a multistep sampler: + the history, a whole-image buffer as z is
-        st['z_used'] = noisy
-        st['tables'] = (tables, level, c3)     # a captured graph bakes their addresses in: they live as long as the state
-        if noisy and draw_noise:
-            self._draw(st['z'], st['gens'])
-        g, img = st['grid'], st['img']
-        for first, n in st['chunks']:
-            xt = st['x_tiles'][:n]
-            self._gather_tiles(st, img, xt, first, n)
-            self.denoise_fn(xt, None, cond=None if st['cond_tiles'] is None else st['cond_tiles'][first:first + n],
-                            level_table=level, step_dev=st['step'][1:], out=st['eps_tiles'][first:first + n], ws=st['ws'])
-        B, Cc, H, W = img.shape
-        a, b, c1, c2, sg = tables
-        L.check(L.load().sr3_tiled_step_hist(L.ptr(img), L.ptr(st['eps_tiles']), B, Cc, H, W, L.ptr(st['oy']), g.ny, L.ptr(st['ox']), g.nx,
-                                             L.ptr(st['wy']), L.ptr(st['wx']), g.th, g.tw, st['oy_host'], st['ox_host'],
-                                             L.ptr(st['z']) if noisy else None, L.ptr(a), L.ptr(b), L.ptr(c1), L.ptr(c2), L.ptr(sg),
-                                             L.ptr(st['step']), 1, L.ptr(st['eps']), self._stream(img.device), L.ptr(c3),
-                                             None if c3 is None else L.ptr(st['hist'])))
-
     @staticmethod
     def _draw(t, gens):
         """t ~ N(0, 1): one draw for the batch from the default generator (the reference's torch.randn_like), or image i's slab
@@ -473,36 +444,48 @@ class EngineDiffusion(nn.Module):
             for i, g in enumerate(gens):
                 t[i].normal_(generator=g)
 
-    def _one_step(self, st, draw_noise=True):
-        """One iteration of the loop: z ~ N(0, 1) (torch's graph-safe Philox), then sr3_reverse_step -- UNet forward with the p_sample
-        update and the counter decrement inside the output conv's kernel (round 6; before: three calls, two more graph nodes).
-        st['eps'] keeps the step's eps for the parity checks that read it."""
-        if st.get('grid') is not None:
-            return self._one_tiled_step(st, draw_noise)
-        if self.sampler is not None:
-            return self._one_sampler_step(st, draw_noise)
-        if draw_noise:
-            self._draw(st['z'], st['gens'])
-        tables = (self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod, self.posterior_mean_coef1,
-                  self.posterior_mean_coef2, self._sigma)
-        self.denoise_fn.reverse_step(st['img'], st['z'], tables, st['step'], cond=st['cond'], level_table=self._level_table,
-                                     clip_denoised=True, eps_out=st['eps'], ws=st['ws'])
+    def _step_rule(self):
+        """What a step runs on: (the five tables of the tail, the SR3 level table, the DDPM step-index -> timestep map or None, the
+        multistep table c3 or None, whether noise is drawn).  The ancestral sampler is the rule made of the schedule's own buffers; a
+        sampler's (set_sampler) is its _sampler_* tables, indexed by the step index j, with the map tau for the DDPM variant and
+        noise only for eta > 0."""
+        if self.sampler is None:
+            return ((self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod, self.posterior_mean_coef1,
+                     self.posterior_mean_coef2, self._sigma), self._level_table, None, None, True)
+        return ((self._sampler_a, self._sampler_b, self._sampler_c1, self._sampler_c2, self._sampler_sigma), self._sampler_level,
+                self._sampler_tau if self.variant == 'ddpm' else None, self._sampler_c3, self.sampler['eta'] > 0.0)
 
-    def _one_sampler_step(self, st, draw_noise=True):
-        """The same call over the sampler's tables: the counter is the step index j, the SR3 level comes from the walk's level table,
-        the DDPM timestep from the map tau.  eta = 0: nothing is drawn and the step gets no z (st['z_used'] records it) -- a graph
-        captured from it has no RNG node.  A multistep sampler passes its c3 table and the state's history buffer along."""
-        noisy = self.sampler['eta'] > 0.0
+    def _one_step(self, st, draw_noise=True):
+        """One iteration of the loop on the rule of `_step_rule`: z ~ N(0, 1) (torch's graph-safe Philox) where the rule is noisy --
+        otherwise nothing is drawn and the step gets no z (st['z_used'] records it): a graph captured from it has no RNG node -- then
+        sr3_reverse_step: UNet forward with the p_sample update and the counter decrement inside the output conv's kernel.  A state
+        with a grid (the tiled loop) instead runs, per chunk of tiles, a gather out of the running image and one UNet forward at the
+        tile geometry (level / timestep from the device counter), then the fused tail on the full image -- blend of the tiles' eps,
+        p_sample update, counter decrement (sr3_tiled_step).  A multistep rule passes its c3 table and the state's history buffer
+        along.  st['eps'] keeps the step's (blended) eps for the parity checks that read it."""
+        tables, level, t_map, c3, noisy = rule = self._step_rule()
         st['z_used'] = noisy
+        st['tables'] = rule                    # a captured graph bakes their addresses in: they live as long as the state
         if noisy and draw_noise:
             self._draw(st['z'], st['gens'])
-        tables = (self._sampler_a, self._sampler_b, self._sampler_c1, self._sampler_c2, self._sampler_sigma)
-        t_map = self._sampler_tau if self.variant == 'ddpm' else None
-        c3 = self._sampler_c3
-        st['tables'] = (tables, self._sampler_level, t_map, c3)    # a captured graph bakes their addresses in: they live as long as the state
-        self.denoise_fn.reverse_step(st['img'], st['z'] if noisy else None, tables, st['step'], cond=st['cond'],
-                                     level_table=self._sampler_level, clip_denoised=True, eps_out=st['eps'], ws=st['ws'], t_map=t_map,
-                                     c3=c3, hist=None if c3 is None else st['hist'])
+        img, z = st['img'], st['z'] if noisy else None
+        hist = None if c3 is None else st['hist']
+        g = st.get('grid')
+        if g is None:
+            self.denoise_fn.reverse_step(img, z, tables, st['step'], cond=st['cond'], level_table=level, clip_denoised=True,
+                                         eps_out=st['eps'], ws=st['ws'], t_map=t_map, c3=c3, hist=hist)
+            return
+        assert t_map is None      # (_sample_loop refused it, _check_tiled_sampler: the tiles run through sr3_unet_forward, which has no t_map)
+        for first, n in st['chunks']:
+            xt = st['x_tiles'][:n]
+            self._gather_tiles(st, img, xt, first, n)
+            self.denoise_fn(xt, None, cond=None if st['cond_tiles'] is None else st['cond_tiles'][first:first + n],
+                            level_table=level, step_dev=st['step'][1:], out=st['eps_tiles'][first:first + n], ws=st['ws'])
+        B, Cc, H, W = img.shape
+        L.check(L.load().sr3_tiled_step_hist(L.ptr(img), L.ptr(st['eps_tiles']), B, Cc, H, W, L.ptr(st['oy']), g.ny, L.ptr(st['ox']), g.nx,
+                                             L.ptr(st['wy']), L.ptr(st['wx']), g.th, g.tw, st['oy_host'], st['ox_host'], L.ptr(z),
+                                             *[L.ptr(t) for t in tables], L.ptr(st['step']), 1, L.ptr(st['eps']),
+                                             self._stream(img.device), L.ptr(c3), L.ptr(hist)))
 
     def _capture(self, st):
         dev = st['img'].device

@@ -87,7 +87,7 @@ def main():
                 tiled_net._gather_tiles(st, st['img'], st['x_tiles'][:n], first, n)
 
         def tail():                                      # the step without its forwards and without a draw: sr3_tiled_step alone
-            tiled_net._one_tiled_step(st, draw_noise=False)
+            tiled_net._one_step(st, draw_noise=False)
         g_gather, g_tail = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(g_gather):
             gather_all()
