@@ -4,6 +4,9 @@
 
 namespace sr3 {
 
+// grid of an element-wise pass over n items: 256 threads a block, at most 8192 blocks (grid-stride loops)
+inline int ew_blocks(size_t n) { size_t b = (n + 255) / 256; return (int)(b > 8192 ? 8192 : (b ? b : 1)); }
+
 // GroupNorm(+SiLU) backward over the virtual concat (x0|x1): dA (grad w.r.t. the activated input) is
 // overwritten with du, partial sums go to `part`, group sums to gs[B][G][2], parameter gradients to
 // dgamma/dbeta[C], and dx0/dx1 (+=) receive the input gradient.  mr[B][G][2] = (mean, rstd).
@@ -25,22 +28,6 @@ int colsums(const float* g, int B, int HW, int C, double* part, float* dbias, fl
             hipStream_t st);
 int l1_loss_grad(const float* z, const float* e, int B, int Cc, int HW, int CP, float scale, bool l2, float* g_nhwc,
                  double* loss_part, float* loss_out, hipStream_t st);
-int adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, int step,
-              hipStream_t st);
-// the same update with the weights' moving average in the same pass (ema_mode 0 none | 1 ema = p | 2 ema += (p - ema)(1 - ema_decay));
-// arguments are checked by the ABI entry (sr3_adam_ema_step)
-int adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float b1, float b2, float eps,
-                  int step, float ema_decay, int ema_mode, hipStream_t st);
-// adam_ema_step on g * scale4[1] (a product rounded on its own), skipped as a whole -- nothing is written -- when scale4[2] == 0;
-// scale4: the four device floats grad_norm / grad_accumulate write.  Arguments are checked by the ABI entry (sr3_adam_ema_step_scaled)
-int adam_ema_step_scaled(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float b1, float b2,
-                         float eps, int step, float ema_decay, int ema_mode, const float* scale4, hipStream_t st);
-// Global L2 norm of g[0..n) on a fixed grid in fixed order (train_kernels.hip, T13): out4 = {norm, coef, finite flag, 0},
-// coef = min(1, max_norm / (norm + 1e-6)) (1 when max_norm <= 0); part: grad_norm_scratch_bytes(n) of doubles
-size_t grad_norm_scratch_bytes(size_t n);
-int grad_norm(const float* g, size_t n, float max_norm, double* part, float* out4, hipStream_t st);
-// acc = first ? g : acc + g; out4 != nullptr: also what grad_norm(acc) would write, from the same pass (bit-equal to it)
-int grad_accumulate(float* acc, const float* g, size_t n, bool first, float max_norm, double* part, float* out4, hipStream_t st);
 int nchw_to_nhwc_pad(const float* a, int Ca, const float* b, int Cb, int B, int HW, int CP, float* out, hipStream_t st);
 
 // Weight gradient of a conv (wgrad.hip): dw[n][tap][c] = sum_m dy[m][n] * a_tap[m][c], a = prologue(x0|x1)

@@ -1,8 +1,8 @@
 // Backward-pass helpers of the training step (DDPM.optimize_parameters, model/model.py:48-58:
 // p_losses -> backward -> Adam), HBM-bound: GroupNorm+SiLU backward (reduce / fold / apply),
 // gradient routing through the virtual concat / residual / nearest-upsample / stride-2 views,
-// weight re-layout for the data-gradient convolutions, bias / FiLM gradient sums, L1 loss and
-// the fused Adam update.  The contractions (dgrad, wgrad, attention backward) live in
+// weight re-layout for the data-gradient convolutions, bias / FiLM gradient sums and the L1 loss.
+// The optimizer's passes (Adam, gradient norm) are in optim.hip; the contractions (dgrad, wgrad, attention backward) live in
 // conv3x3_halo.hip / conv_igemm.hip (reused with transformed weights), wgrad.hip and
 // attention_bwd.hip.
 #include <math.h>
@@ -304,175 +304,6 @@ __global__ __launch_bounds__(64) void k_sum_parts(const double* __restrict__ par
   if (threadIdx.x == 0) out[0] = (float)s;
 }
 
-// T12: fused Adam over the whole parameter arena (torch.optim.Adam defaults, model/model.py:39-40):
-// m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
-// Four elements, shared by k_adam and k_adam_ema.  The fused multiply-adds are written out: left to the compiler, which of the
-// two products of `v b2 + w2 g g` is fused depends on the code around the expression, and the two kernels must give the same bits.
-__device__ __forceinline__ void adam_vec4(f32x4& pv, const f32x4& gv, f32x4& mv, f32x4& vv, float w1, float b2, float w2,
-                                          float eps, float step, float bc2_sqrt) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    mv[e] = fmaf(gv[e] - mv[e], w1, mv[e]);                   // torch: exp_avg.lerp_(grad, 1 - beta1)
-    vv[e] = fmaf(vv[e], b2, w2 * gv[e] * gv[e]);              //        exp_avg_sq.mul_(beta2).addcmul_(g, g, value=1 - beta2)
-    const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
-    pv[e] = fmaf(-step, mv[e] / denom, pv[e]);
-  }
-}
-__global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                               float* __restrict__ v, size_t n4, float w1, float b2, float w2, float eps,
-                                               float step, float bc2_sqrt) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
-    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
-    f32x4 mv = *reinterpret_cast<f32x4*>(m + i * 4);
-    f32x4 vv = *reinterpret_cast<f32x4*>(v + i * 4);
-    adam_vec4(pv, gv, mv, vv, w1, b2, w2, eps, step, bc2_sqrt);
-    *reinterpret_cast<f32x4*>(p + i * 4) = pv;
-    *reinterpret_cast<f32x4*>(m + i * 4) = mv;
-    *reinterpret_cast<f32x4*>(v + i * 4) = vv;
-  }
-}
-
-// T12b: the same pass with the exponential moving average of the weights as one more stream over the arena.
-// MODE 0: Adam alone (no access to ema); 1: ema = p_new (the copy before step_start_ema); 2: ema += (p_new - ema) * we,
-// we = 1 - ema_decay -- the lerp form of exp_avg above: p_new == ema leaves ema unchanged exactly.  No atomics.
-__device__ __forceinline__ void ema_lerp4(f32x4& ev, const f32x4& pv, float we) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) ev[e] = fmaf(pv[e] - ev[e], we, ev[e]);
-}
-template <int MODE>
-__global__ __launch_bounds__(256) void k_adam_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, float* __restrict__ ema, size_t n4, float w1,
-                                                   float b2, float w2, float eps, float step, float bc2_sqrt, float we) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
-    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
-    f32x4 mv = *reinterpret_cast<f32x4*>(m + i * 4);
-    f32x4 vv = *reinterpret_cast<f32x4*>(v + i * 4);
-    f32x4 ev = {0.f, 0.f, 0.f, 0.f};
-    if (MODE == 2) ev = *reinterpret_cast<f32x4*>(ema + i * 4);
-    adam_vec4(pv, gv, mv, vv, w1, b2, w2, eps, step, bc2_sqrt);
-    if (MODE == 2) ema_lerp4(ev, pv, we);
-    *reinterpret_cast<f32x4*>(p + i * 4) = pv;
-    *reinterpret_cast<f32x4*>(m + i * 4) = mv;
-    *reinterpret_cast<f32x4*>(v + i * 4) = vv;
-    if (MODE == 1) *reinterpret_cast<f32x4*>(ema + i * 4) = pv;
-    if (MODE == 2) *reinterpret_cast<f32x4*>(ema + i * 4) = ev;
-  }
-}
-
-// T12c: k_adam_ema on a gradient scaled by a device-side coefficient, guarded by a device-side flag (scale4 = the four floats
-// k_grad_norm_finish writes: norm, coef, finite flag, 0).  Every thread reads the same 16 bytes.  Flag 0: nothing is written.
-// The scaled gradient is a product rounded on its own: contraction is switched off for it, since this toolchain's __fmul_rn is a
-// plain `x * y` that the compiler may fold into the subtraction that follows.  coef == 1: the bits of k_adam_ema.
-__device__ __forceinline__ float fmul_rn_alone(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-template <int MODE>
-__global__ __launch_bounds__(256) void k_adam_ema_scaled(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                          float* __restrict__ v, float* __restrict__ ema, size_t n4, float w1,
-                                                          float b2, float w2, float eps, float step, float bc2_sqrt, float we,
-                                                          const float* __restrict__ scale4) {
-  const f32x4 sc = *reinterpret_cast<const f32x4*>(scale4);
-  if (sc[2] == 0.f) return;
-  const float coef = sc[1];
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    f32x4 pv = *reinterpret_cast<f32x4*>(p + i * 4);
-    f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
-    f32x4 mv = *reinterpret_cast<f32x4*>(m + i * 4);
-    f32x4 vv = *reinterpret_cast<f32x4*>(v + i * 4);
-    f32x4 ev = {0.f, 0.f, 0.f, 0.f};
-    if (MODE == 2) ev = *reinterpret_cast<f32x4*>(ema + i * 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) gv[e] = fmul_rn_alone(gv[e], coef);
-    adam_vec4(pv, gv, mv, vv, w1, b2, w2, eps, step, bc2_sqrt);
-    if (MODE == 2) ema_lerp4(ev, pv, we);
-    *reinterpret_cast<f32x4*>(p + i * 4) = pv;
-    *reinterpret_cast<f32x4*>(m + i * 4) = mv;
-    *reinterpret_cast<f32x4*>(v + i * 4) = vv;
-    if (MODE == 1) *reinterpret_cast<f32x4*>(ema + i * 4) = pv;
-    if (MODE == 2) *reinterpret_cast<f32x4*>(ema + i * 4) = ev;
-  }
-}
-
-// T13: global L2 norm of the gradient arena and accumulation of micro-batch gradients (config train.optimizer.clip_grad_norm /
-// accumulate).  The grid is FIXED -- min(GRAD_NORM_BLOCKS, ceil(n4 / 256)) blocks of 256 threads, whatever the device -- and every
-// sum has one order: a thread adds the squares of its vectors in stride order (elements 0..3 of each) in double, the 64 lanes of a
-// wave combine by __shfl_xor (32, 16, .., 1), the block's four waves are added in wave order through LDS, and one wave adds the
-// blocks' partial sums in index order.  The square of an fp32 is exact in double, so contraction cannot change a bit.  No atomics.
-constexpr int GRAD_NORM_BLOCKS = 512;
-static inline int grad_norm_blocks(size_t n4) { const size_t b = (n4 + 255) / 256; return (int)(b > GRAD_NORM_BLOCKS ? GRAD_NORM_BLOCKS : (b ? b : 1)); }
-
-__device__ __forceinline__ f32x4 ld4(const float* p, size_t i) { return *reinterpret_cast<const f32x4*>(p + i * 4); }
-__device__ __forceinline__ void st4(float* p, size_t i, const f32x4& x) { *reinterpret_cast<f32x4*>(p + i * 4) = x; }
-__device__ __forceinline__ void sqsum4(double& s, const f32x4& x) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) s += (double)x[e] * (double)x[e];
-}
-__device__ __forceinline__ void grad_sq_block_part(double s, double* __restrict__ part) {
-  __shared__ double red[4];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-}
-__global__ __launch_bounds__(256) void k_grad_sqnorm_parts(const float* __restrict__ g, size_t n4, double* __restrict__ part) {
-  double s = 0.0;
-  const size_t st = (size_t)gridDim.x * 256;
-  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  for (; i + 3 * st < n4; i += 4 * st) {       // four loads in flight; the squares are added in the order of the plain loop
-    const f32x4 a = ld4(g, i), b = ld4(g, i + st), c = ld4(g, i + 2 * st), d = ld4(g, i + 3 * st);
-    sqsum4(s, a); sqsum4(s, b); sqsum4(s, c); sqsum4(s, d);
-  }
-  for (; i < n4; i += st) sqsum4(s, ld4(g, i));
-  grad_sq_block_part(s, part);
-}
-// acc = g (FIRST) or acc + g: one fp32 add per element; NORM: also the partial sums of squares of the result, as k_grad_sqnorm_parts
-// would give them for it
-template <bool FIRST, bool NORM>
-__global__ __launch_bounds__(256) void k_grad_accumulate(float* __restrict__ acc, const float* __restrict__ g, size_t n4,
-                                                          double* __restrict__ part) {
-  double s = 0.0;
-  const size_t st = (size_t)gridDim.x * 256;
-  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  for (; i + 3 * st < n4; i += 4 * st) {
-    f32x4 a = ld4(g, i), b = ld4(g, i + st), c = ld4(g, i + 2 * st), d = ld4(g, i + 3 * st);
-    if (!FIRST) {
-      const f32x4 pa = ld4(acc, i), pb = ld4(acc, i + st), pc = ld4(acc, i + 2 * st), pd = ld4(acc, i + 3 * st);
-      a = pa + a; b = pb + b; c = pc + c; d = pd + d;
-    }
-    st4(acc, i, a); st4(acc, i + st, b); st4(acc, i + 2 * st, c); st4(acc, i + 3 * st, d);
-    if (NORM) { sqsum4(s, a); sqsum4(s, b); sqsum4(s, c); sqsum4(s, d); }
-  }
-  for (; i < n4; i += st) {
-    f32x4 r = ld4(g, i);
-    if (!FIRST) r = ld4(acc, i) + r;
-    st4(acc, i, r);
-    if (NORM) sqsum4(s, r);
-  }
-  if (NORM) grad_sq_block_part(s, part);
-}
-// one wave: out4 = {norm, coef, finite ? 1 : 0, 0}; coef as torch.nn.utils.clip_grad_norm_ forms it in fp32, 1 when max_norm <= 0
-__global__ __launch_bounds__(64) void k_grad_norm_finish(const double* __restrict__ part, int nparts, float max_norm,
-                                                          float* __restrict__ out4) {
-  __shared__ double sp[GRAD_NORM_BLOCKS];
-  for (int i = threadIdx.x; i < nparts; i += 64) sp[i] = part[i];
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  double s = 0.0;
-  for (int i = 0; i < nparts; ++i) s += sp[i];
-  const float norm = (float)sqrt(s);
-  float coef = 1.0f;
-  if (max_norm > 0.f) {
-    const float c = max_norm / (norm + 1e-6f);
-    coef = c < 1.0f ? c : 1.0f;
-  }
-  const f32x4 o = {norm, coef, isfinite(norm) ? 1.0f : 0.0f, 0.0f};
-  *reinterpret_cast<f32x4*>(out4) = o;
-}
-
 // NCHW (C <= 4) -> NHWC with the channel dim padded to CP (input of the first conv for its wgrad)
 __global__ __launch_bounds__(256) void k_nchw_to_nhwc_pad(const float* __restrict__ a, int Ca, const float* __restrict__ b2,
                                                            int Cb, int HW, int CP, float* __restrict__ out, size_t total) {
@@ -535,8 +366,6 @@ static void stats_geometry(int B, int HW, int C, int* LQ_, int* cblocks_, int* p
   ppb = ((ppb + PP - 1) / PP) * PP;
   *LQ_ = LQ; *cblocks_ = cblocks; *ppb_ = ppb; *slices_ = (HW + ppb - 1) / ppb;
 }
-
-static inline int ew_blocks(size_t n) { size_t b = (n + 255) / 256; return (int)(b > 8192 ? 8192 : (b ? b : 1)); }
 
 int act_bwd(float* dA, const float* x0, const float* x1, int C0, int C1, int B, int HW, const float* ss, const float* mr,
             int groups, int act, const float* gamma, double* part, double* gs, float* dgamma, float* dbeta, float* dx0,
@@ -617,76 +446,6 @@ int l1_loss_grad(const float* z, const float* e, int B, int Cc, int HW, int CP, 
   hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(64), 0, st, loss_part, blocks, loss_out);
   SR3_LAUNCH_CHECK("k_sum_parts");
   return SR3_OK;
-}
-namespace {
-// torch.optim.Adam evaluates 1 - beta, the bias corrections and the step size as Python floats (double) and rounds
-// each ONCE to fp32 when it meets the tensor (meant_double: the decimal behind the ABI's fp32 hyper-parameters).
-struct AdamScalars { float w1, b2, w2, eps, step_size, bc2s; };
-AdamScalars adam_scalars(float lr, float b1, float b2, float eps, int step) {
-  const double b1d = meant_double(b1), b2d = meant_double(b2), lrd = meant_double(lr);
-  const double bc1 = 1.0 - pow(b1d, (double)step);
-  const double bc2 = 1.0 - pow(b2d, (double)step);
-  return {(float)(1.0 - b1d), (float)b2d, (float)(1.0 - b2d), (float)meant_double(eps), (float)(lrd / bc1), (float)sqrt(bc2)};
-}
-}  // namespace
-int adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float b1, float b2, float eps, int step,
-              hipStream_t st) {
-  if (n & 3) { set_error("adam: n %% 4"); return SR3_E_BADARG; }
-  const AdamScalars a = adam_scalars(lr, b1, b2, eps, step);
-  hipLaunchKernelGGL(k_adam, dim3(ew_blocks(n / 4)), dim3(256), 0, st, p, g, m, v, n / 4, a.w1, a.b2, a.w2, a.eps, a.step_size,
-                     a.bc2s);
-  SR3_LAUNCH_CHECK("k_adam");
-  return SR3_OK;
-}
-int adam_ema_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float b1, float b2, float eps,
-                  int step, float ema_decay, int ema_mode, hipStream_t st) {
-  const AdamScalars a = adam_scalars(lr, b1, b2, eps, step);
-  const float we = (float)(1.0 - meant_double(ema_decay));      // 1 - decay in double, rounded once (as 1 - beta1 is)
-  const dim3 grid(ew_blocks(n / 4)), block(256);
-#define SR3_ADAM_EMA(MODE) \
-  hipLaunchKernelGGL(k_adam_ema<MODE>, grid, block, 0, st, p, g, m, v, ema, n / 4, a.w1, a.b2, a.w2, a.eps, a.step_size, a.bc2s, we)
-  if (ema_mode == 0) SR3_ADAM_EMA(0);
-  else if (ema_mode == 1) SR3_ADAM_EMA(1);
-  else SR3_ADAM_EMA(2);
-#undef SR3_ADAM_EMA
-  SR3_LAUNCH_CHECK("k_adam_ema");
-  return SR3_OK;
-}
-int adam_ema_step_scaled(float* p, const float* g, float* m, float* v, float* ema, size_t n, float lr, float b1, float b2,
-                         float eps, int step, float ema_decay, int ema_mode, const float* scale4, hipStream_t st) {
-  const AdamScalars a = adam_scalars(lr, b1, b2, eps, step);
-  const float we = (float)(1.0 - meant_double(ema_decay));
-  const dim3 grid(ew_blocks(n / 4)), block(256);
-#define SR3_ADAM_EMA_SCALED(MODE)                                                                                                  \
-  hipLaunchKernelGGL(k_adam_ema_scaled<MODE>, grid, block, 0, st, p, g, m, v, ema, n / 4, a.w1, a.b2, a.w2, a.eps, a.step_size, \
-                     a.bc2s, we, scale4)
-  if (ema_mode == 0) SR3_ADAM_EMA_SCALED(0);
-  else if (ema_mode == 1) SR3_ADAM_EMA_SCALED(1);
-  else SR3_ADAM_EMA_SCALED(2);
-#undef SR3_ADAM_EMA_SCALED
-  SR3_LAUNCH_CHECK("k_adam_ema_scaled");
-  return SR3_OK;
-}
-size_t grad_norm_scratch_bytes(size_t n) { return (size_t)grad_norm_blocks(n / 4) * sizeof(double); }
-static int grad_norm_finish(const double* part, int nparts, float max_norm, float* out4, hipStream_t st) {
-  hipLaunchKernelGGL(k_grad_norm_finish, dim3(1), dim3(64), 0, st, part, nparts, max_norm, out4);
-  SR3_LAUNCH_CHECK("k_grad_norm_finish");
-  return SR3_OK;
-}
-int grad_norm(const float* g, size_t n, float max_norm, double* part, float* out4, hipStream_t st) {
-  const int blocks = grad_norm_blocks(n / 4);
-  hipLaunchKernelGGL(k_grad_sqnorm_parts, dim3(blocks), dim3(256), 0, st, g, n / 4, part);
-  SR3_LAUNCH_CHECK("k_grad_sqnorm_parts");
-  return grad_norm_finish(part, blocks, max_norm, out4, st);
-}
-int grad_accumulate(float* acc, const float* g, size_t n, bool first, float max_norm, double* part, float* out4, hipStream_t st) {
-  const dim3 grid(grad_norm_blocks(n / 4)), block(256);
-#define SR3_GRAD_ACC(FIRST, NORM) hipLaunchKernelGGL((k_grad_accumulate<FIRST, NORM>), grid, block, 0, st, acc, g, n / 4, part)
-  if (out4) { if (first) SR3_GRAD_ACC(true, true); else SR3_GRAD_ACC(false, true); }
-  else { if (first) SR3_GRAD_ACC(true, false); else SR3_GRAD_ACC(false, false); }
-#undef SR3_GRAD_ACC
-  SR3_LAUNCH_CHECK("k_grad_accumulate");
-  return out4 ? grad_norm_finish(part, (int)grid.x, max_norm, out4, st) : SR3_OK;
 }
 int nchw_to_nhwc_pad(const float* a, int Ca, const float* b, int Cb, int B, int HW, int CP, float* out, hipStream_t st) {
   const size_t total = (size_t)B * HW;

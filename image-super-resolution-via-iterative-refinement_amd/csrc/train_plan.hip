@@ -495,84 +495,4 @@ int sr3_train_step(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw,
                    dropout_seed, (mark_offsets && mark_events) ? n_marks : 0, mark_offsets, mark_events);
 }
 
-int sr3_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1,
-                  float beta2, float eps, int step, void* stream) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || step < 1) { set_error("bad argument"); return SR3_E_BADARG; }
-  return adam_step(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, static_cast<hipStream_t>(stream));
-}
-
-int sr3_adam_ema_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, size_t n, float lr,
-                      float beta1, float beta2, float eps, int step, float ema_decay, int ema_mode, void* stream) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq) { set_error("sr3_adam_ema_step: params / grads / exp_avg / exp_avg_sq is NULL"); return SR3_E_BADARG; }
-  if (ema_mode < 0 || ema_mode > 2) { set_error("sr3_adam_ema_step: ema_mode %d is outside 0..2", ema_mode); return SR3_E_BADARG; }
-  if (!ema && ema_mode != 0) { set_error("sr3_adam_ema_step: ema is NULL with ema_mode %d", ema_mode); return SR3_E_BADARG; }
-  if (!(ema_decay >= 0.f && ema_decay < 1.f)) { set_error("sr3_adam_ema_step: ema_decay %g is outside [0, 1)", (double)ema_decay); return SR3_E_BADARG; }
-  if (n & 3) { set_error("sr3_adam_ema_step: n %zu is not a multiple of 4", n); return SR3_E_BADARG; }
-  if (step < 1) { set_error("sr3_adam_ema_step: step %d < 1", step); return SR3_E_BADARG; }
-  if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)ema) & 15) {
-    set_error("sr3_adam_ema_step: misaligned pointer (16-byte vectors)");
-    return SR3_E_ALIGN;
-  }
-  return adam_ema_step(params, grads, exp_avg, exp_avg_sq, ema, n, lr, beta1, beta2, eps, step, ema_decay, ema_mode,
-                       static_cast<hipStream_t>(stream));
-}
-
-int sr3_adam_ema_step_scaled(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, size_t n, float lr,
-                             float beta1, float beta2, float eps, int step, float ema_decay, int ema_mode,
-                             const float* scale4_dev, void* stream) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq) { set_error("sr3_adam_ema_step_scaled: params / grads / exp_avg / exp_avg_sq is NULL"); return SR3_E_BADARG; }
-  if (!scale4_dev) { set_error("sr3_adam_ema_step_scaled: scale4_dev is NULL"); return SR3_E_BADARG; }
-  if (ema_mode < 0 || ema_mode > 2) { set_error("sr3_adam_ema_step_scaled: ema_mode %d is outside 0..2", ema_mode); return SR3_E_BADARG; }
-  if (!ema && ema_mode != 0) { set_error("sr3_adam_ema_step_scaled: ema is NULL with ema_mode %d", ema_mode); return SR3_E_BADARG; }
-  if (!(ema_decay >= 0.f && ema_decay < 1.f)) { set_error("sr3_adam_ema_step_scaled: ema_decay %g is outside [0, 1)", (double)ema_decay); return SR3_E_BADARG; }
-  if (n & 3) { set_error("sr3_adam_ema_step_scaled: n %zu is not a multiple of 4", n); return SR3_E_BADARG; }
-  if (step < 1) { set_error("sr3_adam_ema_step_scaled: step %d < 1", step); return SR3_E_BADARG; }
-  if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)ema | (uintptr_t)scale4_dev) & 15) {
-    set_error("sr3_adam_ema_step_scaled: misaligned pointer (16-byte vectors)");
-    return SR3_E_ALIGN;
-  }
-  return adam_ema_step_scaled(params, grads, exp_avg, exp_avg_sq, ema, n, lr, beta1, beta2, eps, step, ema_decay, ema_mode,
-                              scale4_dev, static_cast<hipStream_t>(stream));
-}
-
-size_t sr3_grad_norm_scratch_bytes(size_t n) { return grad_norm_scratch_bytes(n); }
-
-int sr3_grad_norm(const float* grads, size_t n, float max_norm, void* scratch, size_t scratch_bytes, float* out4_dev,
-                  void* stream) {
-  if (!grads) { set_error("sr3_grad_norm: grads is NULL"); return SR3_E_BADARG; }
-  if (!scratch) { set_error("sr3_grad_norm: scratch is NULL"); return SR3_E_BADARG; }
-  if (!out4_dev) { set_error("sr3_grad_norm: out4_dev is NULL"); return SR3_E_BADARG; }
-  if (n & 3) { set_error("sr3_grad_norm: n %zu is not a multiple of 4", n); return SR3_E_BADARG; }
-  if (max_norm != max_norm) { set_error("sr3_grad_norm: max_norm is NaN"); return SR3_E_BADARG; }
-  if (scratch_bytes < grad_norm_scratch_bytes(n)) {
-    set_error("sr3_grad_norm: scratch_bytes %zu < %zu", scratch_bytes, grad_norm_scratch_bytes(n));
-    return SR3_E_BADARG;
-  }
-  if ((((uintptr_t)grads | (uintptr_t)out4_dev) & 15) || ((uintptr_t)scratch & 7)) {
-    set_error("sr3_grad_norm: misaligned pointer (grads / out4_dev: 16 bytes, scratch: 8)");
-    return SR3_E_ALIGN;
-  }
-  return grad_norm(grads, n, max_norm, static_cast<double*>(scratch), out4_dev, static_cast<hipStream_t>(stream));
-}
-
-int sr3_grad_accumulate(float* acc, const float* g, size_t n, int first, float max_norm, void* scratch, size_t scratch_bytes,
-                        float* out4_dev, void* stream) {
-  if (!acc) { set_error("sr3_grad_accumulate: acc is NULL"); return SR3_E_BADARG; }
-  if (!g) { set_error("sr3_grad_accumulate: g is NULL"); return SR3_E_BADARG; }
-  if (n & 3) { set_error("sr3_grad_accumulate: n %zu is not a multiple of 4", n); return SR3_E_BADARG; }
-  if (out4_dev) {      // the norm of the result rides along: its scratch is needed
-    if (!scratch) { set_error("sr3_grad_accumulate: scratch is NULL with out4_dev given"); return SR3_E_BADARG; }
-    if (max_norm != max_norm) { set_error("sr3_grad_accumulate: max_norm is NaN"); return SR3_E_BADARG; }
-    if (scratch_bytes < grad_norm_scratch_bytes(n)) {
-      set_error("sr3_grad_accumulate: scratch_bytes %zu < %zu", scratch_bytes, grad_norm_scratch_bytes(n));
-      return SR3_E_BADARG;
-    }
-  }
-  if ((((uintptr_t)acc | (uintptr_t)g | (uintptr_t)out4_dev) & 15) || (out4_dev && ((uintptr_t)scratch & 7))) {
-    set_error("sr3_grad_accumulate: misaligned pointer (acc / g / out4_dev: 16 bytes, scratch: 8)");
-    return SR3_E_ALIGN;
-  }
-  return grad_accumulate(acc, g, n, first != 0, max_norm, static_cast<double*>(scratch), out4_dev, static_cast<hipStream_t>(stream));
-}
-
 }  // extern "C"

@@ -160,21 +160,16 @@ class EngineAdam(object):
         if e is not None and (un.ema_arena is None or un.ema_arena.device != arena.device):
             raise L.Sr3Error('EMA is enabled but the UNet holds no EMA arena on %s (EngineUNet.enable_ema)' % arena.device)
         mode = 0 if e is None else ema_mode(self.step_count, e['step_start_ema'], e['update_ema_every'])
+        lib = L.load()
+        state = (L.ptr(arena), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq))
+        hyper = (arena.numel(), C.c_float(lr), C.c_float(d['betas'][0]), C.c_float(d['betas'][1]), C.c_float(d['eps']), self.step_count)
+        ema = (None if e is None else L.ptr(un.ema_arena),) + hyper + (C.c_float(0.0 if e is None else e['ema_decay']), mode)
         if self.clip_grad_norm is not None:
-            L.check(L.load().sr3_adam_ema_step_scaled(L.ptr(arena), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                                                      None if e is None else L.ptr(un.ema_arena), arena.numel(), C.c_float(lr),
-                                                      C.c_float(d['betas'][0]), C.c_float(d['betas'][1]), C.c_float(d['eps']),
-                                                      self.step_count, C.c_float(0.0 if e is None else e['ema_decay']), mode,
-                                                      L.ptr(self.norm4), stream))
+            L.check(lib.sr3_adam_ema_step_scaled(*state, *ema, L.ptr(self.norm4), stream))
         elif e is None:
-            L.check(L.load().sr3_adam_step(L.ptr(arena), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                                           arena.numel(), C.c_float(lr), C.c_float(d['betas'][0]),
-                                           C.c_float(d['betas'][1]), C.c_float(d['eps']), self.step_count, stream))
+            L.check(lib.sr3_adam_step(*state, *hyper, stream))
         else:
-            L.check(L.load().sr3_adam_ema_step(L.ptr(arena), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                                               L.ptr(un.ema_arena), arena.numel(), C.c_float(lr), C.c_float(d['betas'][0]),
-                                               C.c_float(d['betas'][1]), C.c_float(d['eps']), self.step_count,
-                                               C.c_float(e['ema_decay']), mode, stream))
+            L.check(lib.sr3_adam_ema_step(*state, *ema, stream))
         un.weights_changed()            # the Winograd filters of the inference plan are stale now
 
     # ---- checkpoint format: torch.optim.Adam's (model/model.py:137-142, 160-163) --------------------------

@@ -401,13 +401,15 @@ int sr3_train_step(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw,
                    int batch, void* stream);
 
 /* torch.optim.Adam step (model/model.py:39-40,55; defaults beta 0.9/0.999, eps 1e-8, no weight decay)
- * fused over the whole arena; `step` is the 1-based step count for the bias corrections. */
+ * fused over the whole arena; `step` is the 1-based step count for the bias corrections.
+ * SR3_E_BADARG (nothing is launched, the message names the argument): a NULL params / grads / exp_avg / exp_avg_sq,
+ * n % 4 != 0, step < 1.  SR3_E_ALIGN (nothing is launched): a pointer that is not 16-byte aligned. */
 int sr3_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, float lr,
                   float beta1, float beta2, float eps, int step, void* stream);
 
 /* The same Adam step with the exponential moving average (EMA) of the weights updated in the same pass over the arena
  * (config train.ema_scheduler; the SR3 paper samples from EMA weights).  params / exp_avg / exp_avg_sq come out
- * bit-identical to sr3_adam_step on the same inputs in every mode (the per-element code is shared); no atomics.
+ * bit-identical to sr3_adam_step on the same inputs in every mode (both run one kernel template); no atomics.
  *   ema       : arena-shaped fp32 buffer, in / out; may be NULL with ema_mode 0
  *   ema_mode  : 0  no EMA work, ema is not touched;
  *               1  ema = p_new, an exact copy (the steps before step_start_ema);

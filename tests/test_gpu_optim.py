@@ -169,6 +169,41 @@ def test_scaled_adam_bits(n, mode, step):
     torch.cuda.synchronize()
 
 
+def adam_plain(p, g, m, v, step, n=None):
+    return L.load().sr3_adam_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel() if n is None else n, f(HYPER['lr']), f(HYPER['b1']),
+                                  f(HYPER['b2']), f(HYPER['eps']), step, G.stream())
+
+
+# 8 388 612 = 4 * (8192 * 256 + 1): the capped grid wraps once and thread 0 alone takes a second vector
+@pytest.mark.parametrize('n', [4, 4 * (256 * 8192 + 1)])
+def test_three_adam_entries_are_one_pass(n):
+    """sr3_adam_step, sr3_adam_ema_step and sr3_adam_ema_step_scaled run one kernel template: the same bits in p / m / v through all
+    three in every EMA mode, the unscaled entry's ema through the scaled one at coef 1, nothing written at flag 0, and the plain
+    entry refuses a misaligned pointer as the other two do."""
+    step = 7
+    pad = adam_inputs(n + 4, 53 + n % 89)                        # four floats more: the views from element 1 are 4 bytes off
+    p, g, m, v, ema = (t[:n] for t in pad)
+    rp, rm, rv = p.clone(), m.clone(), v.clone()
+    L.check(adam_plain(rp, g, rm, rv, step))
+    assert not torch.equal(rp, p)
+    on = torch.tensor([55.0, 1.0, 1.0, 0.0], device=G.dev())
+    off = torch.tensor([55.0, 1.0, 0.0, 0.0], device=G.dev())
+    for mode in (0, 1, 2):
+        a, b, c = ([t.clone() for t in (p, m, v, ema)] for _ in range(3))
+        L.check(adam_ema(a, g, step, mode))
+        L.check(adam_ema(b, g, step, mode, scale4=on))
+        L.check(adam_ema(c, g, step, mode, scale4=off))
+        for got in (a, b):
+            assert all(torch.equal(bits(x), bits(y)) for x, y in zip(got[:3], (rp, rm, rv))), 'mode %d' % mode
+        assert torch.equal(bits(b[3]), bits(a[3])), 'ema, mode %d' % mode
+        assert all(torch.equal(bits(x), bits(y)) for x, y in zip(c, (p, m, v, ema))), 'flag 0 wrote something (mode %d)' % mode
+    keep = [t.clone() for t in pad]
+    rc = adam_plain(pad[0][1:n + 1], g, m, v, step)
+    assert rc == -3 and b'sr3_adam_step: misaligned' in L.load().sr3_last_error(), rc          # SR3_E_ALIGN
+    torch.cuda.synchronize()
+    assert all(torch.equal(bits(x), bits(y)) for x, y in zip(pad, keep)), 'a refused call wrote something'
+
+
 def test_bad_arguments_are_refused_and_touch_nothing():
     n = 1028
     lib = L.load()

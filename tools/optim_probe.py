@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """What the passes between the training step and Adam cost (config train.optimizer.accumulate / clip_grad_norm): on an arena of the
 BASELINE config's size, through the C ABI, timed with HIP events -- the global norm (sr3_grad_norm), the accumulate without and with
-the fused norm (sr3_grad_accumulate), the scaled Adam+EMA (sr3_adam_ema_step_scaled, mode 2) and the unscaled sr3_adam_ema_step on
-the same buffers -- legs interleaved --rounds times after --warmup calls each; median and p10-p90 per leg, GB/s = the bytes the
+the fused norm (sr3_grad_accumulate), the scaled Adam+EMA (sr3_adam_ema_step_scaled, mode 2), the unscaled sr3_adam_ema_step and the plain
+sr3_adam_step on the same buffers -- legs interleaved --rounds times after --warmup calls each; median and p10-p90 per leg, GB/s = the bytes the
 algorithm needs over the median.
     python tools/optim_probe.py [--config sr3_16_128] [--rounds 40] [--warmup 5]      (GPU box)"""
 import argparse
@@ -49,6 +49,7 @@ def main():
         'accumulate_fused_norm': (12, lambda: lib.sr3_grad_accumulate(L.ptr(acc), L.ptr(g), n, 0, f(1.0), L.ptr(scratch), nb, L.ptr(out4), st)),
         'adam_ema_scaled_mode2': (36, lambda: lib.sr3_adam_ema_step_scaled(*adam, L.ptr(one4), st)),
         'adam_ema_mode2': (36, lambda: lib.sr3_adam_ema_step(*adam, st)),
+        'adam': (28, lambda: lib.sr3_adam_step(*adam[:4], *adam[5:11], st)),
     }
     ms = {k: [] for k in legs}
     for rnd in range(a.warmup + a.rounds):
