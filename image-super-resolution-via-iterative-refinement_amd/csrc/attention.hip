@@ -11,17 +11,13 @@
 // LDS write) and double-buffered in LDS when the strip leaves room (NSTAGE = 2).  When the grid
 // would leave CUs idle, the channel panels of phase 3 are split over gridDim.z workgroups (each
 // recomputes the cheap score strip).
+// k_attention_v2's two contraction loops and the row softmax of both kernels are attention_core.h's; the LDS-staged loops of
+// k_attention are its own.
 #include <stdlib.h>
 
-#include "sr3_common.h"
+#include "attention_core.h"
 
 namespace sr3 {
-
-constexpr int AT_LDK = 36;    // Q/K staging row stride (32 + 4 pad floats)
-constexpr int AT_LDV = 132;   // V staging row stride (128 + 4)
-constexpr int AT_QK_STAGE = (32 + 128) * AT_LDK;
-constexpr int AT_V_STAGE = 32 * AT_LDV;
-constexpr int AT_STAGE = AT_QK_STAGE > AT_V_STAGE ? AT_QK_STAGE : AT_V_STAGE;
 
 template <int NSTAGE>
 __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv, int N, int C,
@@ -97,7 +93,7 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
           const int key = kb + wave * 32 + (lane & 31);
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int row = acc_row(r, 4 * (lane >> 5));
             S[row * LDS_S + key] = acc[r] / sqrt_c;
             acc[r] = 0.f;
           }
@@ -111,20 +107,7 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
 
   // ---------------- phase 2: row softmax over the N valid keys ----------------
   {
-    const int row = tid >> 3, sub = tid & 7;
-    float* sr = S + row * LDS_S;
-    float mx = -INFINITY;
-    for (int k = sub; k < N; k += 8) mx = fmaxf(mx, sr[k]);
-    mx = fmaxf(mx, __shfl_xor(mx, 1));
-    mx = fmaxf(mx, __shfl_xor(mx, 2));
-    mx = fmaxf(mx, __shfl_xor(mx, 4));
-    float sum = 0.f;
-    for (int k = sub; k < N; k += 8) { const float e = expf(sr[k] - mx); sr[k] = e; sum += e; }
-    sum += __shfl_xor(sum, 1);
-    sum += __shfl_xor(sum, 2);
-    sum += __shfl_xor(sum, 4);
-    for (int k = sub; k < N; k += 8) sr[k] = sr[k] / sum;
-    for (int k = N + sub; k < Npad; k += 8) sr[k] = 0.f;
+    strip_softmax(S, LDS_S, tid, N, Npad);
   }
   __syncthreads();
 
@@ -185,7 +168,7 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
           const int c = cp + wave * 32 + (lane & 31);
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int m = m0 + acc_row(r, 4 * (lane >> 5));
             if (m < N && c < C) out[((size_t)b * N + m) * C + c] = acc[r];
             acc[r] = 0.f;
           }
@@ -215,13 +198,6 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
 // The k order of both contractions is the one of k_attention (bitwise equal results).
 // Shapes: N % 32 == 0, N <= 1024, C % 128 == 0, (C / zsplit) % (128 TN) == 0; the rest stays on k_attention.
 // ---------------------------------------------------------------------------------------------------------------
-template <int TN> struct AtVec;
-template <> struct AtVec<1> { typedef float type; };
-template <> struct AtVec<2> { typedef float type __attribute__((ext_vector_type(2))); };
-template <> struct AtVec<4> { typedef f32x4 type; };
-template <int TN> __device__ __forceinline__ float at_elem(const typename AtVec<TN>::type& v, int t) { return v[t]; }
-template <> __device__ __forceinline__ float at_elem<1>(const float& v, int) { return v; }
-
 // SPLIT (round 5; plan option attn_split): both contractions on v_mfma_f32_32x32x16_bf16 with every fp32 operand as three bf16
 // terms and six products per fp32 product, fp32 accumulation -- the arithmetic of the SPLIT conv kernels (fp32-class results,
 // gated against float64 in tests/).  A lane's operand is then 8 consecutive k of its row: 32 contiguous bytes of its query / key
@@ -253,117 +229,26 @@ __global__ __launch_bounds__(256) void k_attention_v2(const float* __restrict__ 
   constexpr int D = 4;                                      // operand groups in flight
 
   // ---------------- phase 1 ----------------
-  if constexpr (SPLIT) {
-    const int KB = N >> 5, G = C >> 4;                      // groups of 16 channels = one bf16 MFMA k-step; G % 2 == 0 (C % 128 == 0)
-    const int k8 = (lane >> 5) * 8;
-    const float* qrow = base + (size_t)(m0 + ln) * rowstride + k8;
-    constexpr int DS = 2;
+  {
+    const int KB = N >> 5;
+    const int koff = SPLIT ? (lane >> 5) * 8 : kh;          // first channel of this lane's operand fragments
+    const float* qrow = base + (size_t)(m0 + ln) * rowstride + koff;
     for (int kb0 = wave * KP; kb0 < KB; kb0 += 4 * KP) {
       const float* krow[KP];
 #pragma unroll
-      for (int p = 0; p < KP; ++p) krow[p] = base + (size_t)(min(kb0 + p, KB - 1) * 32 + ln) * rowstride + C + k8;
+      for (int p = 0; p < KP; ++p) krow[p] = base + (size_t)(min(kb0 + p, KB - 1) * 32 + ln) * rowstride + C + koff;
       f32x16 acc[KP];
+      qk_scores<KP, SPLIT, false>(qrow, krow, C, acc);
 #pragma unroll
       for (int p = 0; p < KP; ++p)
-#pragma unroll
-        for (int r_ = 0; r_ < 16; ++r_) acc[p][r_] = 0.f;
-      f32x4 a[DS][2], k4[DS][KP][2];
-#pragma unroll
-      for (int d = 0; d < DS; ++d)
-#pragma unroll
-        for (int hlf = 0; hlf < 2; ++hlf) {
-          a[d][hlf] = *reinterpret_cast<const f32x4*>(qrow + d * 16 + hlf * 4);
-#pragma unroll
-          for (int p = 0; p < KP; ++p) k4[d][p][hlf] = *reinterpret_cast<const f32x4*>(krow[p] + d * 16 + hlf * 4);
-        }
-      for (int g0 = 0; g0 < G; g0 += DS) {
-#pragma unroll
-        for (int d = 0; d < DS; ++d) {
-          bf16x8 qa[3];
-          split3x8(a[d][0], a[d][1], qa[0], qa[1], qa[2]);
-#pragma unroll
-          for (int p = 0; p < KP; ++p) {
-            bf16x8 kb[3];
-            split3x8(k4[d][p][0], k4[d][p][1], kb[0], kb[1], kb[2]);
-            mfma_split6(qa, kb, acc[p]);
-          }
-          const int gn = min(g0 + d + DS, G - 1) * 16;        // (the tail re-fetches the last group: the loads stay unconditional)
-#pragma unroll
-          for (int hlf = 0; hlf < 2; ++hlf) {
-            a[d][hlf] = *reinterpret_cast<const f32x4*>(qrow + gn + hlf * 4);
-#pragma unroll
-            for (int p = 0; p < KP; ++p) k4[d][p][hlf] = *reinterpret_cast<const f32x4*>(krow[p] + gn + hlf * 4);
-          }
-        }
-      }
-#pragma unroll
-      for (int p = 0; p < KP; ++p) {
-        if (kb0 + p < KB) {
-          const int key = (kb0 + p) * 32 + ln;
-#pragma unroll
-          for (int r_ = 0; r_ < 16; ++r_) S[((r_ & 3) + 8 * (r_ >> 2) + kh) * LDS_S + key] = acc[p][r_] / sqrt_c;
-        }
-      }
-    }
-  } else {
-    const int KB = N >> 5, G = C >> 3;                      // G % D == 0 (C % 32 == 0: host)
-    const float* qrow = base + (size_t)(m0 + ln) * rowstride + kh;
-    for (int kb0 = wave * KP; kb0 < KB; kb0 += 4 * KP) {
-      const float* krow[KP];
-#pragma unroll
-      for (int p = 0; p < KP; ++p) krow[p] = base + (size_t)(min(kb0 + p, KB - 1) * 32 + ln) * rowstride + C + kh;
-      f32x16 acc[KP];
-#pragma unroll
-      for (int p = 0; p < KP; ++p)
-#pragma unroll
-        for (int r_ = 0; r_ < 16; ++r_) acc[p][r_] = 0.f;
-      f32x4 a[D], k4[D][KP];
-#pragma unroll
-      for (int d = 0; d < D; ++d) {
-        a[d] = *reinterpret_cast<const f32x4*>(qrow + d * 8);
-#pragma unroll
-        for (int p = 0; p < KP; ++p) k4[d][p] = *reinterpret_cast<const f32x4*>(krow[p] + d * 8);
-      }
-      for (int g0 = 0; g0 < G; g0 += D) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int p = 0; p < KP; ++p) acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[d][q], k4[d][p][q], acc[p], 0, 0, 0);
-          const int gn = min(g0 + d + D, G - 1) * 8;          // (the tail re-fetches the last group: the loads stay unconditional)
-          a[d] = *reinterpret_cast<const f32x4*>(qrow + gn);
-#pragma unroll
-          for (int p = 0; p < KP; ++p) k4[d][p] = *reinterpret_cast<const f32x4*>(krow[p] + gn);
-        }
-      }
-#pragma unroll
-      for (int p = 0; p < KP; ++p) {
-        if (kb0 + p < KB) {
-          const int key = (kb0 + p) * 32 + ln;
-#pragma unroll
-          for (int r_ = 0; r_ < 16; ++r_) S[((r_ & 3) + 8 * (r_ >> 2) + kh) * LDS_S + key] = acc[p][r_] / sqrt_c;
-        }
-      }
+        if (kb0 + p < KB) emit_scores(S, LDS_S, (kb0 + p) * 32 + ln, kh, acc[p], sqrt_c);
     }
   }
   __syncthreads();
 
   // ---------------- phase 2: row softmax ----------------
   {
-    const int row = tid >> 3, sub = tid & 7;
-    float* sr = S + row * LDS_S;
-    float mx = -INFINITY;
-    for (int k = sub; k < N; k += 8) mx = fmaxf(mx, sr[k]);
-    mx = fmaxf(mx, __shfl_xor(mx, 1));
-    mx = fmaxf(mx, __shfl_xor(mx, 2));
-    mx = fmaxf(mx, __shfl_xor(mx, 4));
-    float sum = 0.f;
-    for (int k = sub; k < N; k += 8) { const float e = expf(sr[k] - mx); sr[k] = e; sum += e; }
-    sum += __shfl_xor(sum, 1);
-    sum += __shfl_xor(sum, 2);
-    sum += __shfl_xor(sum, 4);
-    for (int k = sub; k < N; k += 8) sr[k] = sr[k] / sum;
+    strip_softmax(S, LDS_S, tid, N, N);
   }
   __syncthreads();
 
@@ -372,7 +257,6 @@ __global__ __launch_bounds__(256) void k_attention_v2(const float* __restrict__ 
     typedef typename AtVec<TN>::type vec_t;
     const int Cz = C / zsplit;
     const int cz0 = zi * Cz;
-    [[maybe_unused]] const int G = N >> 3;                    // G % D == 0 (N % 32 == 0)
     for (int cw = wave * 32 * TN; cw < Cz; cw += 4 * 32 * TN) {
       const int c0 = cz0 + cw;
       f32x16 acc[TN];
@@ -380,65 +264,17 @@ __global__ __launch_bounds__(256) void k_attention_v2(const float* __restrict__ 
       for (int t = 0; t < TN; ++t)
 #pragma unroll
         for (int r_ = 0; r_ < 16; ++r_) acc[t][r_] = 0.f;
-      if constexpr (SPLIT) {
-        const int k8 = (lane >> 5) * 8;
-        const int G16 = N >> 4;                               // groups of 16 keys; G16 % 2 == 0 (N % 32 == 0)
-        constexpr int DS = 2;
-        const float* vcol = base + 2 * C + c0 + TN * ln + (size_t)k8 * rowstride;     // key k8, this lane's TN channels
-        const float* prow = S + ln * LDS_S + k8;
-        vec_t vb[DS][8];
-#pragma unroll
-        for (int d = 0; d < DS; ++d)
-#pragma unroll
-          for (int q = 0; q < 8; ++q) vb[d][q] = *reinterpret_cast<const vec_t*>(vcol + (size_t)(d * 16 + q) * rowstride);
-        for (int g0 = 0; g0 < G16; g0 += DS) {
-#pragma unroll
-          for (int d = 0; d < DS; ++d) {
-            const f32x4 p0 = *reinterpret_cast<const f32x4*>(prow + (g0 + d) * 16);
-            const f32x4 p1 = *reinterpret_cast<const f32x4*>(prow + (g0 + d) * 16 + 4);
-            bf16x8 pa[3];
-            split3x8(p0, p1, pa[0], pa[1], pa[2]);
-#pragma unroll
-            for (int t = 0; t < TN; ++t) {
-              const f32x4 v0 = {at_elem<TN>(vb[d][0], t), at_elem<TN>(vb[d][1], t), at_elem<TN>(vb[d][2], t), at_elem<TN>(vb[d][3], t)};
-              const f32x4 v1 = {at_elem<TN>(vb[d][4], t), at_elem<TN>(vb[d][5], t), at_elem<TN>(vb[d][6], t), at_elem<TN>(vb[d][7], t)};
-              bf16x8 vv[3];
-              split3x8(v0, v1, vv[0], vv[1], vv[2]);
-              mfma_split6(pa, vv, acc[t]);
-            }
-            const size_t kn = (size_t)(min(g0 + d + DS, G16 - 1) * 16) * rowstride;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) vb[d][q] = *reinterpret_cast<const vec_t*>(vcol + kn + (size_t)q * rowstride);
-          }
-        }
-      }
-      if constexpr (!SPLIT) {
-        const float* vcol = base + 2 * C + c0 + TN * ln + (size_t)kh * rowstride;       // key kh, this lane's TN channels
-        const float* prow = S + ln * LDS_S + kh;
-        vec_t vb[D][4];
-#pragma unroll
-        for (int d = 0; d < D; ++d)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) vb[d][q] = *reinterpret_cast<const vec_t*>(vcol + (size_t)(d * 8 + q) * rowstride);
-        for (int g0 = 0; g0 < G; g0 += D) {
-#pragma unroll
-          for (int d = 0; d < D; ++d) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(prow + (g0 + d) * 8);
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-              for (int t = 0; t < TN; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q], at_elem<TN>(vb[d][q], t), acc[t], 0, 0, 0);
-            const size_t kn = (size_t)(min(g0 + d + D, G - 1) * 8) * rowstride;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) vb[d][q] = *reinterpret_cast<const vec_t*>(vcol + kn + (size_t)q * rowstride);
-          }
-        }
-  
-      }
+      constexpr int GK = SPLIT ? 16 : 8;                      // keys per operand group
+      const int koff = SPLIT ? (lane >> 5) * 8 : kh;
+      const float* vcol = base + 2 * C + c0 + TN * ln + (size_t)koff * rowstride;       // key koff, this lane's TN channels
+      pv_accumulate<TN, SPLIT>(S + ln * LDS_S + koff,
+          [&](int d, int q) { return *reinterpret_cast<const vec_t*>(vcol + (size_t)(d * GK + q) * rowstride); },
+          [&](int g, int q) { return *reinterpret_cast<const vec_t*>(vcol + (size_t)(g * GK) * rowstride + (size_t)q * rowstride); },
+          N >> (SPLIT ? 4 : 3), acc);
       float* orow = out + ((size_t)b * N + m0) * C + c0 + TN * ln;
 #pragma unroll
       for (int r_ = 0; r_ < 16; ++r_) {
-        const int row = (r_ & 3) + 8 * (r_ >> 2) + kh;
+        const int row = acc_row(r_, kh);
         vec_t o;
         if constexpr (TN == 1) o = acc[0][r_];
         else {
@@ -452,21 +288,23 @@ __global__ __launch_bounds__(256) void k_attention_v2(const float* __restrict__ 
 }
 
 namespace {
-template <int KP, int TN, bool SPLIT>
-int launch_attention_v2s(const float* qkv, int B, int N, int C, int zsplit, float* out, hipStream_t st) {
-  static std::atomic<uint64_t> done{0};
+// k_attention_v2<KP, TN, SPLIT> by (pairs, tn, split): one table, one launcher
+using AttnV2Kernel = decltype(&k_attention_v2<1, 1, false>);
+#define SR3_V2_ROW(KP) \
+  {{k_attention_v2<KP, 1, false>, k_attention_v2<KP, 1, true>}, {k_attention_v2<KP, 2, false>, k_attention_v2<KP, 2, true>}, \
+   {k_attention_v2<KP, 4, false>, k_attention_v2<KP, 4, true>}}
+int launch_attention_v2(bool pairs, int tn, bool split, const float* qkv, int B, int N, int C, int zsplit, float* out, hipStream_t st) {
+  static constexpr AttnV2Kernel kernels[2][3][2] = {SR3_V2_ROW(1), SR3_V2_ROW(2)};
+  static std::atomic<uint64_t> done[2][3][2];
+  const int ti = tn >> 1;                                   // 1, 2, 4 -> 0, 1, 2
+  const AttnV2Kernel kern = kernels[pairs][ti][split];
   const int smem = 32 * (N + 4) * (int)sizeof(float);
-  auto kern = k_attention_v2<KP, TN, SPLIT>;
-  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern), 160 * 1024, done)) return rc;
+  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern), 160 * 1024, done[pairs][ti][split])) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)((N / 32) * B * zsplit)), dim3(256), smem, st, qkv, B, N, C, zsplit, out);
   SR3_LAUNCH_CHECK("k_attention_v2");
   return SR3_OK;
 }
-template <int KP, int TN>
-int launch_attention_v2(const float* qkv, int B, int N, int C, int zsplit, float* out, hipStream_t st, bool split) {
-  return split ? launch_attention_v2s<KP, TN, true>(qkv, B, N, C, zsplit, out, st)
-               : launch_attention_v2s<KP, TN, false>(qkv, B, N, C, zsplit, out, st);
-}
+#undef SR3_V2_ROW
 }  // namespace
 
 namespace {
@@ -494,14 +332,7 @@ int attention_forward(const float* qkv, int B, int N, int C, float* out, hipStre
     const int Cz = C / zsplit;
     const int tn = (Cz % 512 == 0) ? 4 : ((Cz % 256 == 0) ? 2 : 1);
     const bool pairs = N / 32 >= 8;                       // two key blocks per wave and round share the Q fragment
-    if (pairs) {
-      if (tn == 4) return launch_attention_v2<2, 4>(qkv, B, N, C, zsplit, out, st, split != 0);
-      if (tn == 2) return launch_attention_v2<2, 2>(qkv, B, N, C, zsplit, out, st, split != 0);
-      return launch_attention_v2<2, 1>(qkv, B, N, C, zsplit, out, st, split != 0);
-    }
-    if (tn == 4) return launch_attention_v2<1, 4>(qkv, B, N, C, zsplit, out, st, split != 0);
-    if (tn == 2) return launch_attention_v2<1, 2>(qkv, B, N, C, zsplit, out, st, split != 0);
-    return launch_attention_v2<1, 1>(qkv, B, N, C, zsplit, out, st, split != 0);
+    return launch_attention_v2(pairs, tn, split != 0, qkv, B, N, C, zsplit, out, st);
   }
   int nstage = 2;
   size_t smem = attention_v1_smem(N, 2);

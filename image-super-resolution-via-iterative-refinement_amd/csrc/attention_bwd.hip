@@ -9,6 +9,7 @@
 // reproducible (round 6; the training plan always provides the slabs).  Without slabs (the per-op ABI entry called
 // with no scratch) the contributions are added with fp32 atomics as before -- dqkv is zeroed first.
 // Layouts as in attention.hip: qkv / dqkv [B][N][3C] (q|k|v), dout [B][N][C].  fp32 MFMA throughout.
+// Staging constants, the eight-lane reductions, acc_row and the non-blocked softmax come from attention_core.h.
 //
 // BLOCKED = true (N too large for two full-width strips in 160 KB of LDS, e.g. the N = 1024 mid block of
 // the 64 -> 512 configuration): the keys are processed in blocks of KB.  A pre-pass recomputes the scores block
@@ -17,15 +18,10 @@
 // accumulated in place across blocks (this workgroup owns them), dK / dV go out with atomics as before.
 #include <algorithm>
 
-#include "sr3_common.h"
+#include "attention_core.h"
 #include "train.h"
 
 namespace sr3 {
-
-constexpr int AB_LDK = 36;
-constexpr int AB_LDV = 132;
-constexpr int AB_QK_STAGE = (32 + 128) * AB_LDK;     // floats
-constexpr int AB_V_STAGE = 32 * AB_LDV;
 
 template <int NSTAGE, bool BLOCKED>
 __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__ qkv, const float* __restrict__ dout,
@@ -52,7 +48,7 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
   const int kh = (lane >> 5) * 4;
   const float sqrt_c = sqrtf((float)C);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  constexpr int QKS = (NSTAGE == 2) ? AB_QK_STAGE : 0;
+  constexpr int QKS = (NSTAGE == 2) ? AT_QK_STAGE : 0;
 
   // strip[row][key] = sum_c A[row][c] * Bm[key][c]  (A rows: a_ptr + m*a_stride, B rows: b_ptr + key*b_stride)
   auto strip_gemm = [&](const float* a_ptr, int a_stride, const float* b_ptr, int b_stride, float* strip, bool scale) {
@@ -77,11 +73,11 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
     };
     auto store = [&](int st) {
       float* Qs = stg + st * QKS;
-      float* Ks = Qs + 32 * AB_LDK;
-      *reinterpret_cast<f32x4*>(&Qs[lrow * AB_LDK + kq * 4]) = qok ? rq : zero;
+      float* Ks = Qs + 32 * AT_LDK;
+      *reinterpret_cast<f32x4*>(&Qs[lrow * AT_LDK + kq * 4]) = qok ? rq : zero;
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        *reinterpret_cast<f32x4*>(&Ks[(lrow + 32 * i) * AB_LDK + kq * 4]) = kok[i] ? rk[i] : zero;
+        *reinterpret_cast<f32x4*>(&Ks[(lrow + 32 * i) * AT_LDK + kq * 4]) = kok[i] ? rk[i] : zero;
     };
     f32x16 acc;
 #pragma unroll
@@ -98,11 +94,11 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
       const bool wave_active = (kb + wave * 32) < Npad;
       if (wave_active) {
         const float* Qs = stg + cur * QKS;
-        const float* Ks = Qs + 32 * AB_LDK;
+        const float* Ks = Qs + 32 * AT_LDK;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-          const f32x4 a = *reinterpret_cast<const f32x4*>(&Qs[(lane & 31) * AB_LDK + kk * 8 + kh]);
-          const f32x4 k4 = *reinterpret_cast<const f32x4*>(&Ks[(wave * 32 + (lane & 31)) * AB_LDK + kk * 8 + kh]);
+          const f32x4 a = *reinterpret_cast<const f32x4*>(&Qs[(lane & 31) * AT_LDK + kk * 8 + kh]);
+          const f32x4 k4 = *reinterpret_cast<const f32x4*>(&Ks[(wave * 32 + (lane & 31)) * AT_LDK + kk * 8 + kh]);
 #pragma unroll
           for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q], k4[q], acc, 0, 0, 0);
         }
@@ -110,7 +106,7 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
           const int key = kb + wave * 32 + (lane & 31);
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int row = acc_row(r, 4 * (lane >> 5));
             strip[row * LDS_S + key] = scale ? acc[r] / sqrt_c : acc[r];
             acc[r] = 0.f;
           }
@@ -133,14 +129,10 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
       const float* sr = P + row * LDS_S;
       float mx = m_run;
       for (int k = sub; k < NK; k += 8) mx = fmaxf(mx, sr[k]);
-      mx = fmaxf(mx, __shfl_xor(mx, 1));
-      mx = fmaxf(mx, __shfl_xor(mx, 2));
-      mx = fmaxf(mx, __shfl_xor(mx, 4));
+      mx = max8(mx);
       float sum = 0.f;
       for (int k = sub; k < NK; k += 8) sum += expf(sr[k] - mx);
-      sum += __shfl_xor(sum, 1);
-      sum += __shfl_xor(sum, 2);
-      sum += __shfl_xor(sum, 4);
+      sum = sum8(sum);
       l_run = l_run * expf(m_run - mx) + sum;
       m_run = mx;
     }
@@ -152,9 +144,7 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
         delta += g.x * o.x + g.y * o.y + g.z * o.z + g.w * o.w;
       }
     }
-    delta += __shfl_xor(delta, 1);
-    delta += __shfl_xor(delta, 2);
-    delta += __shfl_xor(delta, 4);
+    delta = sum8(delta);
   }
 
   const int nblocks = BLOCKED ? (N + KB - 1) / KB : 1;
@@ -164,25 +154,13 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
     Npad = (NK + 31) & ~31;
     // ---- A: P = softmax(Q K^T / sqrt(C)) (this block's keys) ----
     strip_gemm(base, rs3, base + C, rs3, P, true);
-    {
+    if constexpr (BLOCKED) {
       const int row = tid >> 3, sub = tid & 7;
       float* sr = P + row * LDS_S;
-      if constexpr (BLOCKED) {
-        for (int k = sub; k < NK; k += 8) sr[k] = expf(sr[k] - m_run) / l_run;
-      } else {
-        float mx = -INFINITY;
-        for (int k = sub; k < NK; k += 8) mx = fmaxf(mx, sr[k]);
-        mx = fmaxf(mx, __shfl_xor(mx, 1));
-        mx = fmaxf(mx, __shfl_xor(mx, 2));
-        mx = fmaxf(mx, __shfl_xor(mx, 4));
-        float sum = 0.f;
-        for (int k = sub; k < NK; k += 8) { const float e = expf(sr[k] - mx); sr[k] = e; sum += e; }
-        sum += __shfl_xor(sum, 1);
-        sum += __shfl_xor(sum, 2);
-        sum += __shfl_xor(sum, 4);
-        for (int k = sub; k < NK; k += 8) sr[k] = sr[k] / sum;
-      }
+      for (int k = sub; k < NK; k += 8) sr[k] = expf(sr[k] - m_run) / l_run;
       for (int k = NK + sub; k < Npad; k += 8) sr[k] = 0.f;
+    } else {
+      strip_softmax(P, LDS_S, tid, NK, Npad);
     }
     // ---- B: dP = dO V^T ----
     strip_gemm(dob, C, base + 2 * C, rs3, D, false);
@@ -195,9 +173,7 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
       if constexpr (!BLOCKED) {
         rs = 0.f;
         for (int k = sub; k < NK; k += 8) rs += dr[k] * pr[k];
-        rs += __shfl_xor(rs, 1);
-        rs += __shfl_xor(rs, 2);
-        rs += __shfl_xor(rs, 4);
+        rs = sum8(rs);
       }
       for (int k = sub; k < NK; k += 8) dr[k] = pr[k] * (dr[k] - rs) / sqrt_c;
       for (int k = NK + sub; k < Npad; k += 8) dr[k] = 0.f;
@@ -209,7 +185,7 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
       const int npan = (C + 127) / 128;
       const int nk = Npad / 32;
       const int nsteps = npan * nk;
-      constexpr int VS = (NSTAGE == 2) ? AB_V_STAGE : 0;
+      constexpr int VS = (NSTAGE == 2) ? AT_V_STAGE : 0;
       f32x4 rv[4];
       bool vok[4];
       auto load = [&](int s) {
@@ -227,7 +203,7 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
         float* Vs = stg + st * VS;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          *reinterpret_cast<f32x4*>(&Vs[((tid >> 5) + 8 * i) * AB_LDV + (tid & 31) * 4]) = vok[i] ? rv[i] : zero;
+          *reinterpret_cast<f32x4*>(&Vs[((tid >> 5) + 8 * i) * AT_LDV + (tid & 31) * 4]) = vok[i] ? rv[i] : zero;
       };
       f32x16 acc;
 #pragma unroll
@@ -249,7 +225,7 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
             const f32x4 a = *reinterpret_cast<const f32x4*>(&D[(lane & 31) * LDS_S + k0 + kk * 8 + kh]);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-              const float bv = Vs[(kk * 8 + kh + q) * AB_LDV + wave * 32 + (lane & 31)];
+              const float bv = Vs[(kk * 8 + kh + q) * AT_LDV + wave * 32 + (lane & 31)];
               acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q], bv, acc, 0, 0, 0);
             }
           }
@@ -257,7 +233,7 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
             const int c = cp + wave * 32 + (lane & 31);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-              const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+              const int m = m0 + acc_row(r, 4 * (lane >> 5));
               if (m < N && c < C) {
                 float* dst = dqb + (size_t)m * rs3 + c;         // rows owned by this workgroup: plain read-add-write
                 *dst = (BLOCKED && blk > 0) ? *dst + acc[r] : acc[r];
@@ -274,8 +250,8 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
 
     // ---- E: dK += (dS/sqrt(C))^T Q ; dV += P^T dO   (this workgroup's 32 rows, this block's keys) ----
     {
-      float* Qt = stg;                       // [32 rows][AB_LDV]
-      float* Ot = stg + AB_V_STAGE;          // [32 rows][AB_LDV]
+      float* Qt = stg;                       // [32 rows][AT_LDV]
+      float* Ot = stg + AT_V_STAGE;          // [32 rows][AT_LDV]
       const int npan = (C + 127) / 128;
       for (int pn = 0; pn < npan; ++pn) {
         const int cp = pn * 128;
@@ -288,8 +264,8 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
           const bool ok = m < N && c < C;
           const f32x4 qv = *reinterpret_cast<const f32x4*>(base + (ok ? m * rs3 + c : 0));
           const f32x4 ov = *reinterpret_cast<const f32x4*>(dob + (ok ? m * C + c : 0));
-          *reinterpret_cast<f32x4*>(&Qt[row * AB_LDV + (tid & 31) * 4]) = ok ? qv : zero;
-          *reinterpret_cast<f32x4*>(&Ot[row * AB_LDV + (tid & 31) * 4]) = ok ? ov : zero;
+          *reinterpret_cast<f32x4*>(&Qt[row * AT_LDV + (tid & 31) * 4]) = ok ? qv : zero;
+          *reinterpret_cast<f32x4*>(&Ot[row * AT_LDV + (tid & 31) * 4]) = ok ? ov : zero;
         }
         __syncthreads();
         const int c = cp + wave * 32 + (lane & 31);
@@ -303,15 +279,15 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
               const int row = 2 * kk + (lane >> 5);
               const float ds = D[row * LDS_S + kb + (lane & 31)];     // A[i = key][k = row]
               const float pp = P[row * LDS_S + kb + (lane & 31)];
-              const float qv = Qt[row * AB_LDV + wave * 32 + (lane & 31)];   // B[k = row][j = c]
-              const float ov = Ot[row * AB_LDV + wave * 32 + (lane & 31)];
+              const float qv = Qt[row * AT_LDV + wave * 32 + (lane & 31)];   // B[k = row][j = c]
+              const float ov = Ot[row * AT_LDV + wave * 32 + (lane & 31)];
               ak = __builtin_amdgcn_mfma_f32_32x32x2f32(ds, qv, ak, 0, 0, 0);
               av = __builtin_amdgcn_mfma_f32_32x32x2f32(pp, ov, av, 0, 0, 0);
             }
             if (c < C) {
 #pragma unroll
               for (int r = 0; r < 16; ++r) {
-                const int key = kb + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int key = kb + acc_row(r, 4 * (lane >> 5));
                 if (key < NK) {
                   if (slab) {
                     float* sl = slab + (((size_t)blockIdx.x * gridDim.y + b) * N + (kbase + key)) * (2 * C);
@@ -351,8 +327,8 @@ int attention_backward(const float* qkv, const float* dout, const float* out_fwd
   if (C & 3) { set_error("attention_bwd: C %% 4 != 0"); return SR3_E_UNSUPPORTED; }
   if ((double)B * N * 3.0 * C >= 2147483647.0) { set_error("attention_bwd: qkv exceeds 2^31 elements"); return SR3_E_UNSUPPORTED; }
   const size_t lds_max = 160 * 1024;
-  const size_t stage2 = 2 * (size_t)(AB_QK_STAGE > AB_V_STAGE ? AB_QK_STAGE : AB_V_STAGE);
-  const size_t stage1 = (size_t)(AB_QK_STAGE > 2 * AB_V_STAGE ? AB_QK_STAGE : 2 * AB_V_STAGE);
+  const size_t stage2 = 2 * (size_t)(AT_QK_STAGE > AT_V_STAGE ? AT_QK_STAGE : AT_V_STAGE);
+  const size_t stage1 = (size_t)(AT_QK_STAGE > 2 * AT_V_STAGE ? AT_QK_STAGE : 2 * AT_V_STAGE);
   const int Npad = (N + 31) & ~31;
   auto bytes = [](int width, size_t stage_f) { return ((size_t)64 * (width + 4) + stage_f) * sizeof(float); };
   int nstage = 2, KB = 0;

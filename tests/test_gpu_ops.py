@@ -560,19 +560,27 @@ def test_groupnorm_stats_and_fold(B, HW, C):
     G.assert_close(got, ref, tol=5e-6, what='gn fold')
 
 
-@pytest.mark.parametrize('B,N,C', [(2, 256, 512), (2, 64, 512), (3, 16, 256), (2, 64, 16), (1, 1024, 128)])
+# the last three are the smallest shapes the host rule sends to k_attention_v2<2,4,.>, <1,4,.> and <1,2,.> (qblocks * B >= 256 keeps the
+# channels of a workgroup unsplit): the TN = 4 strip form of the shared P V loop runs in no other per-op test
+@pytest.mark.parametrize('B,N,C', [(2, 256, 512), (2, 64, 512), (3, 16, 256), (2, 64, 16), (1, 1024, 128),
+                                   (8, 1024, 512), (40, 224, 512), (40, 224, 256)])
 def test_attention(B, N, C):
     lib = L.load()
     d = G.dev()
     qkv = _rand(B, N, 3 * C, seed=7)
-    out = torch.full((B, N, C), float('nan'), device=d)
     qd = qkv.to(d)
-    L.check(lib.sr3_attention_f32(L.ptr(qd), B, N, C, L.ptr(out), G.stream()))
-    torch.cuda.synchronize()
     q, k, v = qkv.double().split(C, dim=2)
     p = torch.softmax(q @ k.transpose(1, 2) / math.sqrt(C), -1)
     ref = p @ v
+    out = torch.full((B, N, C), float('nan'), device=d)
+    L.check(lib.sr3_attention_f32(L.ptr(qd), B, N, C, L.ptr(out), G.stream()))
+    torch.cuda.synchronize()
     G.assert_close(out.cpu(), ref, what='attention')
+    for mode in (0, 1):       # fp32 MFMA / 3 x bf16 split, both on the strip kernels
+        out = torch.full((B, N, C), float('nan'), device=d)
+        L.check(lib.sr3_attention_ex_f32(L.ptr(qd), B, N, C, L.ptr(out), mode, G.stream()))
+        torch.cuda.synchronize()
+        G.assert_close(out.cpu(), ref, what='attention mode %d' % mode)
 
 
 @pytest.mark.parametrize('B,N,C', [(16, 256, 512), (4, 64, 512), (2, 1024, 128), (8, 256, 256)], ids=['c2_16x16', 'c2_8x8', 'n1024', 'c256'])
