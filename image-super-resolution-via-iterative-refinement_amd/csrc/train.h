@@ -28,6 +28,20 @@ int colsums(const float* g, int B, int HW, int C, double* part, float* dbias, fl
             hipStream_t st);
 int l1_loss_grad(const float* z, const float* e, int B, int Cc, int HW, int CP, float scale, bool l2, float* g_nhwc,
                  double* loss_part, float* loss_out, hipStream_t st);
+// The training objective of one step (sr3_train_step_ex / sr3_loss_grad_f32): per-image target coefficients and weight (device, all
+// three or none: target z, weight 1) and the pixel loss
+enum { LOSS_L1 = 0, LOSS_L2 = 1, LOSS_HUBER = 2 };
+constexpr int LOSS_GRAD_BLOCKS = 256;      // blocks of the loss kernels = doubles of their partial-sum scratch
+struct Objective {
+  const float* tgt_z = nullptr; const float* tgt_x0 = nullptr; const float* weight = nullptr;
+  int kind = LOSS_L1;
+  float huber_delta = 1.f;
+};
+int check_objective_args(const char* who, const float* tgt_z, const float* tgt_x0, const float* weight, int loss_kind, int min_kind,
+                         float huber_delta);
+// loss sum and its gradient g [B,HW,CP] under `o`: l1_loss_grad's launch for target z / weight 1 / L1 or L2, else k_loss_grad
+int objective_loss_grad(const float* z, const float* hr, const float* e, const Objective& o, int B, int Cc, int HW, int CP, float scale,
+                        float* g_nhwc, double* loss_part, float* loss_out, hipStream_t st);
 int nchw_to_nhwc_pad(const float* a, int Ca, const float* b, int Cb, int B, int HW, int CP, float* out, hipStream_t st);
 
 // Weight gradient of a conv (wgrad.hip): dw[n][tap][c] = sum_m dy[m][n] * a_tap[m][c], a = prologue(x0|x1)

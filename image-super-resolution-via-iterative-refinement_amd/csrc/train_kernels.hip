@@ -296,6 +296,54 @@ __global__ __launch_bounds__(256) void k_l1_loss_grad(const float* __restrict__ 
   }
   if (threadIdx.x == 0) loss_part[blockIdx.x] = red[0];
 }
+// T11b: the generalised objective (v- / x0-prediction, Min-SNR weights, Huber).  Per image b the regression target is
+// ta[b] z + tb[b] hr and the weight w[b] (NULL tables: target z, weight 1; hr is read only with tb):
+//   d = (ta z + tb hr) - e ;  loss_part[block] = sum w rho(d) ;  g = -w rho'(d) scale
+// with rho = |d| (KIND 0, rho' = sign, 0 at 0), d^2 (1, 2d) or Huber(delta) (2: d^2 / 2 inside |d| <= delta, delta (|d| - delta / 2)
+// outside, rho' = clamp(d, -delta, delta)).  Geometry, layout of g and the reduction are k_l1_loss_grad's.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_loss_grad(const float* __restrict__ z, const float* __restrict__ hr,
+                                                    const float* __restrict__ e, const float* __restrict__ ta,
+                                                    const float* __restrict__ tb, const float* __restrict__ w, int B, int Cc,
+                                                    int HW, int CP, float scale, float delta, float* __restrict__ g_nhwc,
+                                                    double* __restrict__ loss_part) {
+  __shared__ double red[256];
+  double s = 0.0;
+  const size_t total = (size_t)B * HW;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / HW, p = i - b * HW;
+    const float az = ta ? ta[b] : 1.f, ax = tb ? tb[b] : 0.f, wb = w ? w[b] : 1.f;
+    const float ws = wb * scale;
+    double sp = 0.0;                            // this pixel's sum of rho(d): weighted once
+    for (int c = 0; c < CP; ++c) {
+      float gv = 0.f;
+      if (c < Cc) {
+        const size_t idx = (b * Cc + c) * HW + p;
+        const float d = (az * z[idx] + (tb ? ax * hr[idx] : 0.f)) - e[idx];
+        if (KIND == 1) {
+          sp += (double)d * (double)d;
+          gv = -2.f * d * ws;
+        } else if (KIND == 2) {
+          const double a = (double)fabsf(d), dl = (double)delta;
+          sp += a <= dl ? 0.5 * a * a : dl * (a - 0.5 * dl);
+          gv = -fminf(fmaxf(d, -delta), delta) * ws;
+        } else {
+          sp += (double)fabsf(d);
+          gv = d > 0.f ? -ws : (d < 0.f ? ws : 0.f);
+        }
+      }
+      g_nhwc[i * CP + c] = gv;
+    }
+    s += (double)wb * sp;
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int k = 128; k >= 1; k >>= 1) {
+    if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss_part[blockIdx.x] = red[0];
+}
 __global__ __launch_bounds__(64) void k_sum_parts(const double* __restrict__ part, int n, float* __restrict__ out) {
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 64) s += part[i];
@@ -447,6 +495,33 @@ int l1_loss_grad(const float* z, const float* e, int B, int Cc, int HW, int CP, 
   SR3_LAUNCH_CHECK("k_sum_parts");
   return SR3_OK;
 }
+// The refusals of the objective arguments of sr3_train_step_ex / sr3_loss_grad_f32 under the entry's own name (min_kind: -1 where a
+// plan's loss_l2 can stand in).  Nothing has been launched when this returns non-zero.
+int check_objective_args(const char* who, const float* tgt_z, const float* tgt_x0, const float* weight, int loss_kind, int min_kind,
+                         float huber_delta) {
+  const int given = (tgt_z != nullptr) + (tgt_x0 != nullptr) + (weight != nullptr);
+  if (given != 0 && given != 3) { set_error("%s: tgt_z / tgt_x0 / weight must be all NULL or all given (%d of 3 are)", who, given); return SR3_E_BADARG; }
+  if (loss_kind < min_kind || loss_kind > LOSS_HUBER) { set_error("%s: loss_kind %d is outside %d..2", who, loss_kind, min_kind); return SR3_E_BADARG; }
+  if (loss_kind == LOSS_HUBER && !(isfinite(huber_delta) && huber_delta > 0.f)) {
+    set_error("%s: huber_delta %g must be finite and > 0", who, (double)huber_delta);
+    return SR3_E_BADARG;
+  }
+  return SR3_OK;
+}
+// THE place that picks the loss kernel: target z, weight 1 and L1 / L2 is l1_loss_grad's launch as it always was; everything else
+// the generalised kernel on the same grid and the same two-stage sum
+int objective_loss_grad(const float* z, const float* hr, const float* e, const Objective& o, int B, int Cc, int HW, int CP, float scale,
+                        float* g_nhwc, double* loss_part, float* loss_out, hipStream_t st) {
+  if (!o.tgt_z && o.kind != LOSS_HUBER) return l1_loss_grad(z, e, B, Cc, HW, CP, scale, o.kind == LOSS_L2, g_nhwc, loss_part, loss_out, st);
+  const int blocks = LOSS_GRAD_BLOCKS;
+  static constexpr decltype(&k_loss_grad<0>) kernels[3] = {k_loss_grad<0>, k_loss_grad<1>, k_loss_grad<2>};
+  hipLaunchKernelGGL(kernels[o.kind], dim3(blocks), dim3(256), 0, st, z, hr, e, o.tgt_z, o.tgt_x0, o.weight, B, Cc, HW, CP, scale,
+                     o.huber_delta, g_nhwc, loss_part);
+  SR3_LAUNCH_CHECK("k_loss_grad");
+  hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(64), 0, st, loss_part, blocks, loss_out);
+  SR3_LAUNCH_CHECK("k_sum_parts");
+  return SR3_OK;
+}
 int nchw_to_nhwc_pad(const float* a, int Ca, const float* b, int Cb, int B, int HW, int CP, float* out, hipStream_t st) {
   const size_t total = (size_t)B * HW;
   hipLaunchKernelGGL(k_nchw_to_nhwc_pad, dim3(ew_blocks(total)), dim3(256), 0, st, a, Ca, b, Cb, HW, CP, out, total);
@@ -455,3 +530,21 @@ int nchw_to_nhwc_pad(const float* a, int Ca, const float* b, int Cb, int B, int 
 }
 
 }  // namespace sr3
+
+extern "C" size_t sr3_loss_grad_scratch_bytes(void) { return sr3::LOSS_GRAD_BLOCKS * sizeof(double); }
+extern "C" int sr3_loss_grad_f32(const float* z_nchw, const float* out_nchw, const float* hr_nchw, const float* tgt_z, const float* tgt_x0,
+                                 const float* weight, int batch, int channels, int pixels, int loss_kind, float huber_delta, float scale,
+                                 float* g_nhwc4, float* loss_sum_out, void* scratch, void* stream) {
+  using namespace sr3;
+  const char* who = "sr3_loss_grad_f32";
+  if (!z_nchw || !out_nchw || !g_nhwc4 || !loss_sum_out || !scratch) { set_error("%s: z_nchw / out_nchw / g_nhwc4 / loss_sum_out / scratch is NULL", who); return SR3_E_BADARG; }
+  if (const int rc = check_objective_args(who, tgt_z, tgt_x0, weight, loss_kind, 0, huber_delta)) return rc;
+  if (tgt_x0 && !hr_nchw) { set_error("%s: hr_nchw is NULL with tgt_x0 given", who); return SR3_E_BADARG; }
+  if (batch <= 0 || pixels <= 0) { set_error("%s: batch %d and pixels %d must be positive", who, batch, pixels); return SR3_E_BADARG; }
+  if (channels < 1 || channels > 4) { set_error("%s: channels %d is outside 1..4", who, channels); return SR3_E_BADARG; }
+  if ((uintptr_t)scratch & 7) { set_error("%s: scratch is not 8-byte aligned", who); return SR3_E_ALIGN; }
+  Objective o;
+  o.tgt_z = tgt_z; o.tgt_x0 = tgt_x0; o.weight = weight; o.kind = loss_kind; o.huber_delta = huber_delta;
+  return objective_loss_grad(z_nchw, hr_nchw, out_nchw, o, batch, channels, pixels, 4, scale, g_nhwc4, static_cast<double*>(scratch),
+                             loss_sum_out, static_cast<hipStream_t>(stream));
+}

@@ -304,7 +304,7 @@ int wgrad_call(const TrainCtx& X, ConvParams c, const float* src0, const float* 
 int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels, const float* z, const float* q_ca,
               const float* q_cb, const float* level, const int64_t* tstep, const float* freq, const float* params,
               float* grads, char* ws, float* loss_out, float grad_scale, int B, hipStream_t st, float dropout_p,
-              unsigned seed, int n_marks, const size_t* marks, void* const* mark_events) {
+              unsigned seed, int n_marks, const size_t* marks, void* const* mark_events, const Objective& obj) {
   const sr3_unet_desc& d = P->d;
   // image geometry of this step: build_train built the plan for it (the native one unless plan option train_geom)
   const int IH = P->train_h, IW = P->train_w, S2 = IH * IW, G = d.norm_groups;
@@ -325,7 +325,8 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
   // ---- loss and its gradient (NHWC, channel dim padded to 4) ----
   float* geps = X.at<float>(P->t_geps_off);
   double* lparts = X.at<double>(P->t_dwtmp_off);
-  rc = l1_loss_grad(z, eps, B, P->out_ch, S2, OUT_PAD, grad_scale, P->loss_l2 != 0, geps, lparts, loss_out, st);
+  // (target z, weight 1 and L1 / L2 -- sr3_train_step's objective -- is l1_loss_grad's launch: objective_loss_grad)
+  rc = objective_loss_grad(z, hr, eps, obj, B, P->out_ch, S2, OUT_PAD, grad_scale, geps, lparts, loss_out, st);
   if (rc) return rc;
   // ---- the backward walk: the records in reverse, each as build_train resolved it.  The activation-gradient mirror is not zeroed
   // (Rec::acc_*); the FiLM gradient table is ----
@@ -473,15 +474,17 @@ size_t sr3_train_workspace_bytes(sr3_plan* plan, int batch, int cond_channels) {
   return plan->t_ws_bytes;
 }
 
-int sr3_train_step(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels, const float* z_nchw,
-                   const float* q_ca, const float* q_cb, const float* noise_level, const int64_t* timestep,
-                   const float* freq, const float* params, float* grads, void* workspace, size_t workspace_bytes,
-                   float* loss_sum_out, float grad_scale, float dropout_p, unsigned dropout_seed, int n_marks,
-                   const size_t* mark_offsets, void* const* mark_events, int batch, void* stream) {
+int sr3_train_step_ex(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels, const float* z_nchw,
+                      const float* q_ca, const float* q_cb, const float* noise_level, const int64_t* timestep,
+                      const float* freq, const float* params, float* grads, void* workspace, size_t workspace_bytes,
+                      float* loss_sum_out, float grad_scale, float dropout_p, unsigned dropout_seed, int n_marks,
+                      const size_t* mark_offsets, void* const* mark_events, int batch, const float* tgt_z, const float* tgt_x0,
+                      const float* weight, int loss_kind, float huber_delta, void* stream) {
   if (!plan || !hr_nchw || !z_nchw || !q_ca || !q_cb || !freq || !params || !grads || !workspace || !loss_sum_out) {
     set_error("null argument");
     return SR3_E_BADARG;
   }
+  if (const int rc = check_objective_args("sr3_train_step_ex", tgt_z, tgt_x0, weight, loss_kind, -1, huber_delta)) return rc;
   if (!cond_nchw) cond_channels = 0;
   const int rc = build_train(plan, batch, cond_channels);
   if (rc) return rc;
@@ -490,9 +493,22 @@ int sr3_train_step(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw,
   if (plan->d.variant == SR3_VARIANT_SR3 && !noise_level) { set_error("SR3 variant needs noise_level"); return SR3_E_BADARG; }
   if (plan->d.variant == SR3_VARIANT_DDPM && !timestep) { set_error("DDPM variant needs timestep"); return SR3_E_BADARG; }
   if (dropout_p < 0.f || dropout_p >= 1.f) { set_error("dropout_p out of range"); return SR3_E_BADARG; }
+  Objective obj;
+  obj.tgt_z = tgt_z; obj.tgt_x0 = tgt_x0; obj.weight = weight; obj.huber_delta = huber_delta;
+  obj.kind = loss_kind < 0 ? (plan->loss_l2 != 0 ? LOSS_L2 : LOSS_L1) : loss_kind;      // -1: the plan's loss_l2
   return run_train(plan, hr_nchw, cond_nchw, cond_channels, z_nchw, q_ca, q_cb, noise_level, timestep, freq, params, grads,
                    static_cast<char*>(workspace), loss_sum_out, grad_scale, batch, static_cast<hipStream_t>(stream), dropout_p,
-                   dropout_seed, (mark_offsets && mark_events) ? n_marks : 0, mark_offsets, mark_events);
+                   dropout_seed, (mark_offsets && mark_events) ? n_marks : 0, mark_offsets, mark_events, obj);
+}
+
+int sr3_train_step(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels, const float* z_nchw,
+                   const float* q_ca, const float* q_cb, const float* noise_level, const int64_t* timestep,
+                   const float* freq, const float* params, float* grads, void* workspace, size_t workspace_bytes,
+                   float* loss_sum_out, float grad_scale, float dropout_p, unsigned dropout_seed, int n_marks,
+                   const size_t* mark_offsets, void* const* mark_events, int batch, void* stream) {
+  return sr3_train_step_ex(plan, hr_nchw, cond_nchw, cond_channels, z_nchw, q_ca, q_cb, noise_level, timestep, freq, params, grads,
+                           workspace, workspace_bytes, loss_sum_out, grad_scale, dropout_p, dropout_seed, n_marks, mark_offsets,
+                           mark_events, batch, nullptr, nullptr, nullptr, -1, 0.f, stream);
 }
 
 }  // extern "C"

@@ -164,8 +164,12 @@ class DDPM(BaseModel):
                 # entries: renamed to *_gen.pth it loads anywhere a generator checkpoint does
                 state.update((k, v.cpu()) for k, v in self.netG.denoise_fn.ema_state_dict('denoise_fn.').items())
                 torch.save(state, self._ema_path(stem))
-            torch.save({'epoch': epoch, 'iter': iter_step, 'scheduler': None,
-                        'optimizer': self.optG.state_dict()}, opt_path)
+            ck = {'epoch': epoch, 'iter': iter_step, 'scheduler': None, 'optimizer': self.optG.state_dict()}
+            if self.netG.prediction != 'eps':
+                # what the weights predict (model.diffusion.prediction): *_gen.pth keeps the reference's format, so the training state
+                # records it; an eps model's file has the reference's keys only
+                ck['engine'] = {'prediction': self.netG.prediction}
+            torch.save(ck, opt_path)
             logger.info('Saved model in [{:s}] ...'.format(gen_path))
         _dist.barrier()                 # nobody runs ahead (or resumes) before the files are complete
 
@@ -192,6 +196,10 @@ class DDPM(BaseModel):
                 un.ema_from_weights()
         if self.opt['phase'] == 'train':
             ck = torch.load(opt_path, map_location='cpu')
+            saved = (ck.get('engine') or {}).get('prediction', 'eps')
+            if saved != self.netG.prediction:
+                raise ValueError('[{:s}] was trained with prediction {!r} but the config\'s model.diffusion.prediction is {!r}'.format(
+                    opt_path, saved, self.netG.prediction))
             self.optG.load_state_dict(ck['optimizer'])
             self.begin_step = ck['iter']
             self.begin_epoch = ck['epoch']

@@ -20,6 +20,11 @@ default; DDIM takes the key too): one more table, c3, and one image-sized buffer
 Tiling (engine extension, `"tiling": {"tile": 128 | [th, tw], "overlap": 32, "batch": 8}` next to it, or `set_tiling`): an image larger
 than the tile is sampled as one chain whose eps comes from overlapping tiles of that size -- per step: sr3_tile_gather + UNet forward
 per chunk of tiles, then sr3_tiled_step (blend + p_sample update + counter decrement) on the whole image (`p_sample_loop_tiled`).
+
+Objective (engine extension, `"prediction": "eps" | "v" | "x0"` and `"loss": {"type", "delta", "weight", "gamma"}` in model.diffusion, or
+`set_prediction` / `set_objective`): what the network's output stands for and how the training loss weighs it.  Training hands per-image
+target coefficients and weights to sr3_train_step_ex (`prediction_coefs`, `loss_weights`); sampling changes the two tables a, b of the
+step tail's x0c = clip(a x - b out) and nothing else, in every loop.
 """
 import ctypes as C
 
@@ -115,7 +120,68 @@ def _check_sampler_kind(kind):
         raise NotImplementedError('sampler type %r (only %s)' % (kind, ', '.join('"%s"' % k for k in SAMPLER_KINDS)))
 
 
-def sampler_tables(alphas_cumprod, steps, eta, *, kind='ddim', walk='time'):
+PREDICTIONS = ('eps', 'v', 'x0')
+LOSS_TYPES = ('l1', 'l2', 'huber')          # the loss_kind numbers of sr3_train_step_ex, in order
+LOSS_WEIGHTS = ('uniform', 'min_snr')
+
+
+def _check_prediction(kind):
+    if kind not in PREDICTIONS:
+        raise ValueError('prediction must be one of %s (got %r)' % (', '.join(repr(k) for k in PREDICTIONS), kind))
+
+
+def _positive(name, v):
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be a number (got %r)' % (name, v))
+    if isinstance(v, bool) or not np.isfinite(f) or not f > 0.0:
+        raise ValueError('%s must be finite and > 0 (got %r)' % (name, v))
+    return f
+
+
+def prediction_coefs(kind, ca, cb):
+    """What the network's output `out` stands for at the noise level x = ca x0 + cb z (ca = sqrt(abar), cb = sqrt(1 - abar)), as the four
+    coefficients the engine reads:  x0 = x0_a x - x0_b out  (the step tail's a, b) and the training target  tgt_z z + tgt_x0 x0.
+
+        eps (the reference's; Ho et al. 2020):    out ~ z                 a, b = 1 / ca, cb / ca     target (1, 0)
+        v   (Salimans & Ho 2022):                 out ~ ca z - cb x0      a, b = ca, cb              target (ca, -cb)
+        x0:                                       out ~ x0                a, b = 0, -1               target (0, 1)
+
+    Pure numpy, float64, no device; ca and cb broadcast.  Returns (x0_a, x0_b, tgt_z, tgt_x0) as arrays of their shape.  (The eps row is
+    the schedule buffers' sqrt(1 / abar), sqrt(1 / abar - 1) as quotients: equal once rounded to the fp32 the engine's tables hold.)"""
+    _check_prediction(kind)
+    ca, cb = np.broadcast_arrays(np.asarray(ca, dtype=np.float64), np.asarray(cb, dtype=np.float64))
+    one, zero = np.ones_like(ca), np.zeros_like(ca)
+    if kind == 'eps':
+        return 1.0 / ca, cb / ca, one, zero
+    if kind == 'v':
+        return ca.copy(), cb.copy(), ca.copy(), -cb
+    return zero, -one, zero, one
+
+
+def loss_weights(kind, weight, gamma, ca):
+    """Per-noise-level weight of the training loss.  'uniform': 1.  'min_snr' (Min-SNR-gamma, Hang et al. 2023): min(SNR, gamma) divided
+    by SNR, SNR + 1 or 1 for an eps-, v- or x0-predicting network, SNR = ca^2 / (1 - ca^2) -- which weighs the implied x0 error by
+    min(SNR, gamma) whatever the network predicts.  Written as closed forms in g2 = ca^2 so that ca = 1 (SNR infinite: the first entry of
+    SR3's level table) stays finite:  eps  min(1, gamma (1 - g2) / g2);  v  min(g2, gamma (1 - g2));  x0  min(g2 / (1 - g2), gamma), gamma
+    at g2 = 1.  Pure numpy, float64, no device; `gamma` is read for 'min_snr' only."""
+    _check_prediction(kind)
+    if weight not in LOSS_WEIGHTS:
+        raise ValueError('loss weight must be one of %s (got %r)' % (', '.join(repr(k) for k in LOSS_WEIGHTS), weight))
+    g2 = np.asarray(ca, dtype=np.float64) ** 2
+    if weight == 'uniform':
+        return np.ones_like(g2)
+    gamma = _positive('loss gamma', gamma)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        if kind == 'eps':
+            return np.minimum(1.0, gamma * (1.0 - g2) / g2)
+        if kind == 'v':
+            return np.minimum(g2, gamma * (1.0 - g2))
+        return np.where(1.0 - g2 > 0.0, np.minimum(g2 / (1.0 - g2), gamma), gamma)
+
+
+def sampler_tables(alphas_cumprod, steps, eta, *, kind='ddim', walk='time', prediction='eps'):
     """Tables of a sampler over a walk through the schedule (`sampler_walk`) in the form of the engine's fused step tail,
 
         x0c = clip(a x - b eps) ;  x_new = c1 x0c + c2 x + c3 x0c_prev + sigma z.
@@ -133,6 +199,9 @@ def sampler_tables(alphas_cumprod, steps, eta, *, kind='ddim', walk='time'):
     k = -sqrt(ap) expm1(-h): c1 = k (1 + 1 / (2r)), c2 = sqrt(1 - ap) / sqrt(1 - ab), c3 = -k / (2r).  The first step taken has no
     history (c1 = k, c3 = 0: DDIM's step), and the last one goes to ap = 1, where lambda is infinite: c1 = 1, c2 = c3 = 0, DDIM's too.
 
+    prediction ('eps' | 'v' | 'x0', `prediction_coefs`): what the network's output stands for.  Only a and b change with it -- c1, c2, c3,
+    sigma, level and tau do not: DDIM re-derives eps from the clipped x0, and the multistep solver is already in data-prediction form.
+
     Pure numpy, float64, no device.  The step index j counts like the device counter: j = steps - 1 is the first step taken, j = 0 the
     last.  Returns a dict: tau (`sampler_walk`), a, b, c1, c2, c3,
     sigma ([S]) and level ([S + 1]: level[j + 1] = sqrt(alphas_cumprod[tau[j]]), the reference's sqrt_alphas_cumprod_prev[t + 1] at
@@ -148,6 +217,7 @@ def sampler_tables(alphas_cumprod, steps, eta, *, kind='ddim', walk='time'):
         raise ValueError('sampler kind must be one of %s (got %r)' % (', '.join(repr(k) for k in SAMPLER_KINDS), kind))
     if kind == 'dpmpp_2m' and eta != 0.0:
         raise ValueError('sampler kind \'dpmpp_2m\' is the deterministic solver: eta must be 0 (got %r)' % (eta,))
+    _check_prediction(prediction)
     tau = sampler_walk(ac, S, walk)
     ab = ac[tau]
     ap = np.append(1.0, ab[:-1])
@@ -167,7 +237,10 @@ def sampler_tables(alphas_cumprod, steps, eta, *, kind='ddim', walk='time'):
             else:
                 r = (lam[j] - lam[j + 1]) / h
                 c1[j], c3[j] = k * (1.0 + 1.0 / (2.0 * r)), -k / (2.0 * r)
-    out = dict(tau=tau, a=np.sqrt(1.0 / ab), b=np.sqrt(1.0 / ab - 1), c1=c1, c2=c2, c3=c3, sigma=sigma, level=np.append(1.0, np.sqrt(ab)))
+    a, b = np.sqrt(1.0 / ab), np.sqrt(1.0 / ab - 1)
+    if prediction != 'eps':
+        a, b = prediction_coefs(prediction, np.sqrt(ab), np.sqrt(1.0 - ab))[:2]
+    out = dict(tau=tau, a=a, b=b, c1=c1, c2=c2, c3=c3, sigma=sigma, level=np.append(1.0, np.sqrt(ab)))
     if not all(np.all(np.isfinite(v)) for v in out.values()):
         raise ValueError('sampler tables are not finite')
     return out
@@ -196,6 +269,9 @@ class EngineDiffusion(nn.Module):
         self._loop_cache = {}
         self.sampler = None            # None: the reference's ancestral loop; else {'type': 'ddim', 'steps': S, 'eta': e} (set_sampler);
                                        # type 'dpmpp_2m' or a walk other than 'time': also 'walk'
+        self.prediction = 'eps'        # what the network's output stands for: 'eps' (the reference's), 'v' or 'x0' (set_prediction)
+        self.objective = None          # None: the reference's loss (loss_type, unweighted); else {'type', 'delta', 'weight', 'gamma'} (set_objective)
+        self._train_tables = None      # DDPM variant: per-timestep (tgt_z, tgt_x0, weight) on the device, built on first use
         self.tiling = None             # None: whole-image steps; else {'tile': (th, tw), 'overlap': o, 'batch': n | None} (set_tiling)
         self.max_cached_loops = 3      # reverse-loop states (buffers + workspace + captured graph) kept, one per (shape, launch list)
         # schedule_opt is accepted and ignored exactly like the reference ctor (diffusion.py:80-82)
@@ -234,8 +310,12 @@ class EngineDiffusion(nn.Module):
         sig[0] = 0.0                                                             # `t > 0` branch / nonzero_mask
         self.register_buffer('_level_table', lvl.to(device), persistent=False)
         self.register_buffer('_sigma', sig.to(device), persistent=False)
+        # x0-prediction: x0c = clip(0 x + 1 out), the tail's a, b as two constant tables
+        self.register_buffer('_x0_a', torch.zeros(self.num_timesteps, device=device), persistent=False)
+        self.register_buffer('_x0_b', -torch.ones(self.num_timesteps, device=device), persistent=False)
         self._alphas_cumprod64 = ac                                              # what a sampler's tables are computed from
         self._loop_cache = {}
+        self._train_tables = None
         self.tiling = None                                                       # (this phase's own "tiling" key is read below)
         # engine key of the schedule dict: "sampler": {"type": "ddim" | "dpmpp_2m", "steps": S, "eta": e, "walk": "time" | "logsnr"};
         # absent / null: the ancestral loop
@@ -271,7 +351,7 @@ class EngineDiffusion(nn.Module):
             _check_sampler_kind(kind)
             if walk is None:
                 walk = 'logsnr' if kind == 'dpmpp_2m' else 'time'
-            tabs = sampler_tables(self._alphas_cumprod64, steps, eta, kind=kind, walk=walk)
+            tabs = sampler_tables(self._alphas_cumprod64, steps, eta, kind=kind, walk=walk, prediction=self.prediction)
             self._check_tiled_sampler(True, getattr(self, 'tiling', None))
             self.sampler = dict(type=kind, steps=int(steps), eta=float(eta))
             if kind != 'ddim' or walk != 'time':
@@ -282,6 +362,35 @@ class EngineDiffusion(nn.Module):
         for k in _SAMPLER_TABLES:                # the float64 tables rounded once to fp32; the walk as int32 (what k_embed reads)
             t = None if tabs is None or tabs[k] is None else torch.tensor(tabs[k], dtype=torch.int32 if k == 'tau' else torch.float32).to(dev)
             self.register_buffer('_sampler_' + k, t, persistent=False)
+        self._loop_cache = {}
+
+    def set_prediction(self, kind='eps'):
+        """What the network's output stands for (`prediction_coefs`): 'eps' (the reference's), 'v' or 'x0'.  Training regresses on that
+        target; every sampling path -- p_sample, p_mean_variance, the ancestral, DDIM, DPM-Solver++ and tiled loops -- reads the
+        matching a, b of x0c = clip(a x - b out).  A configured sampler's tables are rebuilt and every captured loop is dropped."""
+        _check_prediction(kind)
+        self.prediction = kind
+        self._train_tables = None
+        sp = self.sampler
+        if sp is not None:
+            self.set_sampler(sp['steps'], sp['eta'], kind=sp['type'], walk=sp.get('walk', 'time'))
+        self._loop_cache = {}
+
+    def set_objective(self, type='l1', delta=None, weight='uniform', gamma=None):
+        """The pixel loss of p_losses and its weight per noise level: type 'l1' | 'l2' | 'huber' (delta, default 1.0, for 'huber'
+        only), weight 'uniform' | 'min_snr' (`loss_weights`; gamma, default 5.0, for 'min_snr' only).  Sum-reduced, as the reference's."""
+        if type not in LOSS_TYPES:
+            raise ValueError('loss type must be one of %s (got %r)' % (', '.join(repr(k) for k in LOSS_TYPES), type))
+        if weight not in LOSS_WEIGHTS:
+            raise ValueError('loss weight must be one of %s (got %r)' % (', '.join(repr(k) for k in LOSS_WEIGHTS), weight))
+        if delta is not None and type != 'huber':
+            raise ValueError('loss delta is given (%r) but the loss type is %r, not \'huber\'' % (delta, type))
+        if gamma is not None and weight != 'min_snr':
+            raise ValueError('loss gamma is given (%r) but the loss weight is %r, not \'min_snr\'' % (gamma, weight))
+        delta = _positive('loss delta', 1.0 if delta is None else delta) if type == 'huber' else None
+        gamma = _positive('loss gamma', 5.0 if gamma is None else gamma) if weight == 'min_snr' else None
+        self.objective = dict(type=type, delta=delta, weight=weight, gamma=gamma)
+        self._train_tables = None
         self._loop_cache = {}
 
     def set_tiling(self, tile=None, overlap=0, batch=None):
@@ -330,14 +439,23 @@ class EngineDiffusion(nn.Module):
             step_host = int(t)
         lib = L.load()
         per = x[0].numel()
-        L.check(lib.sr3_p_sample_step_ex(L.ptr(x), L.ptr(eps), L.ptr(z), L.ptr(self.sqrt_recip_alphas_cumprod),
-                                         L.ptr(self.sqrt_recipm1_alphas_cumprod), L.ptr(self.posterior_mean_coef1),
+        a, b = self._x0_tables()
+        L.check(lib.sr3_p_sample_step_ex(L.ptr(x), L.ptr(eps), L.ptr(z), L.ptr(a), L.ptr(b), L.ptr(self.posterior_mean_coef1),
                                          L.ptr(self.posterior_mean_coef2), L.ptr(self._sigma), L.ptr(step_dev),
                                          L.ptr(t_per_sample), int(step_host), x.shape[0], per, 1 if clip_denoised else 0,
                                          self._stream(x.device)))
 
+    def _x0_tables(self):
+        """a, b of x0c = clip(a x - b out) on the schedule's own timesteps, by what the network predicts (`prediction_coefs`): eps -- the
+        reference's sqrt_recip / sqrt_recipm1 buffers; v -- sqrt(abar), sqrt(1 - abar), buffers too; x0 -- the constants 0, -1."""
+        if self.prediction == 'v':
+            return self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod
+        if self.prediction == 'x0':
+            return self._x0_a, self._x0_b
+        return self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod
+
     def _eps(self, x, t, condition_x):
-        """denoise_fn call of p_mean_variance (sr3 :151-160, ddpm :175-182)."""
+        """denoise_fn call of p_mean_variance (sr3 :151-160, ddpm :175-182): the network's output, whatever it predicts."""
         b = x.shape[0]
         if self.variant == 'sr3':
             level = torch.full((b,), float(np.float32(self.sqrt_alphas_cumprod_prev[t + 1])), dtype=torch.float32,
@@ -450,8 +568,7 @@ class EngineDiffusion(nn.Module):
         sampler's (set_sampler) is its _sampler_* tables, indexed by the step index j, with the map tau for the DDPM variant and
         noise only for eta > 0."""
         if self.sampler is None:
-            return ((self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod, self.posterior_mean_coef1,
-                     self.posterior_mean_coef2, self._sigma), self._level_table, None, None, True)
+            return (self._x0_tables() + (self.posterior_mean_coef1, self.posterior_mean_coef2, self._sigma), self._level_table, None, None, True)
         return ((self._sampler_a, self._sampler_b, self._sampler_c1, self._sampler_c2, self._sampler_sigma), self._sampler_level,
                 self._sampler_tau if self.variant == 'ddpm' else None, self._sampler_c3, self.sampler['eta'] > 0.0)
 
@@ -671,7 +788,8 @@ class EngineDiffusion(nn.Module):
                 tt = np.random.randint(1, self.num_timesteps + 1) if t is None else int(t)
                 gamma = torch.FloatTensor(np.random.uniform(self.sqrt_alphas_cumprod_prev[tt - 1],
                                                             self.sqrt_alphas_cumprod_prev[tt], size=b))
-            g = gamma.reshape(-1).float().to(dev)
+            gamma = gamma.reshape(-1).float()
+            g = gamma.to(dev)
             ca, cb = g, (1 - g ** 2).sqrt()
             level = g
         else:
@@ -683,7 +801,34 @@ class EngineDiffusion(nn.Module):
             noise = torch.randn_like(x_start)
         cond = x_in['SR'].contiguous() if self.conditional else None
         return un.train_step(x_start, cond, noise.contiguous(), ca.contiguous(), cb.contiguous(), level, tstep,
-                             grad_scale=1.0 / float(b * c * h * w), drop_seed=drop_seed)
+                             grad_scale=1.0 / float(b * c * h * w), drop_seed=drop_seed,
+                             objective=self._train_objective(tstep, gamma, dev))
+
+    def _train_objective(self, tstep, gamma, dev):
+        """The objective arguments of sr3_train_step_ex for one batch: (tgt_z, tgt_x0, weight, loss_kind, huber_delta), or None -- the
+        reference's step -- while neither set_prediction nor set_objective changed anything.  eps-prediction under a uniform weight
+        passes no tables (the launches of the reference's step).  SR3: the coefficients at the drawn levels, float64 on the host, one
+        copy of 3 x batch floats (`gamma`: the levels as p_losses drew them, on the host).  DDPM: a gather by `tstep` from per-timestep
+        tables kept on the device."""
+        ob = self.objective
+        if ob is None and self.prediction == 'eps':
+            return None
+        kind = -1 if ob is None else LOSS_TYPES.index(ob['type'])      # (-1: the plan's loss_l2, what set_loss configured)
+        delta = 0.0 if ob is None or ob['delta'] is None else ob['delta']
+        weight, wgamma = ('uniform', None) if ob is None else (ob['weight'], ob['gamma'])
+        if self.prediction == 'eps' and weight == 'uniform':
+            return None, None, None, kind, delta
+
+        def tables(ca):
+            cb = np.sqrt(np.maximum(1.0 - ca ** 2, 0.0))
+            return np.stack(prediction_coefs(self.prediction, ca, cb)[2:] + (loss_weights(self.prediction, weight, wgamma, ca),))
+        if self.variant == 'sr3':
+            tab = torch.tensor(tables(gamma.detach().double().cpu().numpy()), dtype=torch.float32).to(dev)
+        else:
+            if self._train_tables is None or self._train_tables.device != dev:
+                self._train_tables = torch.tensor(tables(np.sqrt(self._alphas_cumprod64)), dtype=torch.float32).to(dev)
+            tab = self._train_tables[:, tstep].contiguous()
+        return tab[0], tab[1], tab[2], kind, delta
 
     def forward(self, x, *args, **kwargs):
         return self.p_losses(x, *args, **kwargs)

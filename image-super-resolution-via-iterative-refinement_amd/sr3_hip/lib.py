@@ -93,6 +93,10 @@ SIGNATURES = {
     'sr3_train_workspace_bytes': (_Z, [_P, _I, _I]),
     'sr3_train_step': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, C.c_float, C.c_float, C.c_uint,
                             _I, _P, _P, _I, _P]),
+    'sr3_train_step_ex': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, C.c_float, C.c_float, C.c_uint,
+                               _I, _P, _P, _I, _P, _P, _P, _I, C.c_float, _P]),
+    'sr3_loss_grad_scratch_bytes': (_Z, []),
+    'sr3_loss_grad_f32': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P]),
     'sr3_adam_step': (_I, [_P, _P, _P, _P, _Z, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P]),
     'sr3_adam_ema_step': (_I, [_P, _P, _P, _P, _P, _Z, C.c_float, C.c_float, C.c_float, C.c_float, _I, C.c_float, _I, _P]),
     'sr3_adam_ema_step_scaled': (_I, [_P, _P, _P, _P, _P, _Z, C.c_float, C.c_float, C.c_float, C.c_float, _I, C.c_float, _I, _P, _P]),

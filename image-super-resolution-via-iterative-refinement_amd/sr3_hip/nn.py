@@ -270,9 +270,11 @@ class EngineUNet(nn.Module):
                               hist=hist)
 
     # ---- training step (forward + backward inside the engine) ------------------------------------
-    def train_step(self, hr, cond, z, ca, cb, level, tstep, grad_scale, drop_seed=None):
+    def train_step(self, hr, cond, z, ca, cb, level, tstep, grad_scale, drop_seed=None, objective=None):
         """One fused forward + backward: returns the sum-reduced loss (0-dim tensor, summed over all data-parallel
-        ranks) and leaves d(loss * grad_scale)/d params -- rank-summed -- in `grad_arena`."""
+        ranks) and leaves d(loss * grad_scale)/d params -- rank-summed -- in `grad_arena`.  `objective`: None (the network predicts
+        z, unweighted, the plan's loss) or (tgt_z, tgt_x0, weight, loss_kind, huber_delta) of sr3_train_step_ex, the first three
+        [B] device tensors or all None."""
         p_drop = self.dropout if self.training else 0.0
         if drop_seed is None:          # a fresh mask every step, drawn from torch's CPU generator
             drop_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_drop > 0 else 0
@@ -292,7 +294,8 @@ class EngineUNet(nn.Module):
             grad_scale = grad_scale / tdist.get_world_size()
             if self.accumulate == 1:
                 marks = red.mark_args()
-        self._engine_train_step(hr, cond, z, ca, cb, level, tstep, grad_scale, p_drop, drop_seed, marks, loss)
+        self._engine_train_step(hr, cond, z, ca, cb, level, tstep, grad_scale, p_drop, drop_seed, marks, loss,
+                                **({} if objective is None else {'objective': objective}))
         if dp:
             if self.accumulate == 1:
                 red.reduce(self.grad_arena, extra=[loss])
@@ -322,9 +325,9 @@ class EngineUNet(nn.Module):
         for lo, hi in red.buckets:
             red.dist.all_reduce(arena[lo:hi], op=red.dist.ReduceOp.SUM)
 
-    def _engine_train_step(self, hr, cond, z, ca, cb, level, tstep, grad_scale, p_drop, drop_seed, marks, loss):
-        """The sr3_train_step call itself (q_sample -> UNet forward -> loss -> backward, `marks` = the gradient-ready
-        events of the data-parallel buckets)."""
+    def _engine_train_step(self, hr, cond, z, ca, cb, level, tstep, grad_scale, p_drop, drop_seed, marks, loss, objective=None):
+        """The sr3_train_step_ex call itself (q_sample -> UNet forward -> loss -> backward, `marks` = the gradient-ready
+        events of the data-parallel buckets); objective None is sr3_train_step's (NULL, NULL, NULL, -1, 0)."""
         import ctypes as C
         dev = hr.device
         if dev.type != 'cuda':
@@ -362,10 +365,15 @@ class EngineUNet(nn.Module):
         wsv = ws[off:off + need]
         n_marks, offs, evs = marks
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        L.check(plan.lib.sr3_train_step(plan.handle, L.ptr(hr), L.ptr(cond), cc, L.ptr(z), L.ptr(ca), L.ptr(cb),
-                                        L.ptr(level), L.ptr(tstep), L.ptr(self.freq), L.ptr(self.arena.data),
-                                        L.ptr(self.grad_arena), L.ptr(wsv), need, L.ptr(loss), C.c_float(grad_scale),
-                                        C.c_float(p_drop), C.c_uint(drop_seed & 0xFFFFFFFF), n_marks, offs, evs, B, stream))
+        tgt_z, tgt_x0, weight, kind, delta = (None, None, None, -1, 0.0) if objective is None else objective
+        for t in (tgt_z, tgt_x0, weight):
+            if t is not None and (t.device != dev or t.dtype != torch.float32 or t.numel() != B or not t.is_contiguous()):
+                raise L.Sr3Error('training: tgt_z / tgt_x0 / weight must be contiguous fp32 tensors of %d elements on %s' % (B, dev))
+        L.check(plan.lib.sr3_train_step_ex(plan.handle, L.ptr(hr), L.ptr(cond), cc, L.ptr(z), L.ptr(ca), L.ptr(cb),
+                                           L.ptr(level), L.ptr(tstep), L.ptr(self.freq), L.ptr(self.arena.data),
+                                           L.ptr(self.grad_arena), L.ptr(wsv), need, L.ptr(loss), C.c_float(grad_scale),
+                                           C.c_float(p_drop), C.c_uint(drop_seed & 0xFFFFFFFF), n_marks, offs, evs, B,
+                                           L.ptr(tgt_z), L.ptr(tgt_x0), L.ptr(weight), int(kind), C.c_float(delta), stream))
 
     def named_gradients(self):
         """(reference key, gradient view in the reference shape) after a train_step."""

@@ -400,6 +400,38 @@ int sr3_train_step(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw,
                    unsigned dropout_seed, int n_marks, const size_t* mark_offsets, void* const* mark_events,
                    int batch, void* stream);
 
+/* sr3_train_step under another training objective (no counterpart in the reference, whose network predicts the noise under an
+ * unweighted L1 / L2): per image b the regression target is tgt_z[b] * z + tgt_x0[b] * hr and the loss weight is weight[b],
+ *   d = (tgt_z[b] * z + tgt_x0[b] * hr) - out ;  *loss_sum_out = sum weight[b] * rho(d) ;  grads = d(grad_scale * that) / d params.
+ * tgt_z / tgt_x0 / weight: `batch` floats each on the device, all three or none (all NULL: target z, weight 1).  v-prediction
+ * (Salimans & Ho 2022) is tgt_z = sqrt(abar), tgt_x0 = -sqrt(1 - abar); x0-prediction is (0, 1); Min-SNR-gamma weights (Hang et
+ * al. 2023) go in `weight` (sr3_hip.diffusion.prediction_coefs / loss_weights compute them).
+ * loss_kind: -1 the plan's loss_l2 option; 0 L1, rho = |d| (gradient 0 at d = 0); 1 L2, rho = d^2; 2 Huber, rho = d^2 / 2 for
+ * |d| <= huber_delta, else huber_delta * (|d| - huber_delta / 2) (torch.nn.HuberLoss(reduction='sum', delta)); huber_delta is read
+ * with loss_kind 2 only.  With the pointers NULL and loss_kind -1 / 0 / 1 the launches are sr3_train_step's, which IS this call with
+ * (NULL, NULL, NULL, -1, 0).  The loss sum keeps its fixed-order two-stage reduction in double: no atomics, the same bits every run.
+ * SR3_E_BADARG (nothing is launched, the message names the argument): only some of tgt_z / tgt_x0 / weight given, loss_kind
+ * outside -1..2, loss_kind 2 with a huber_delta that is not finite and > 0. */
+int sr3_train_step_ex(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels,
+                      const float* z_nchw, const float* q_ca, const float* q_cb, const float* noise_level,
+                      const int64_t* timestep, const float* freq, const float* params, float* grads,
+                      void* workspace, size_t workspace_bytes, float* loss_sum_out, float grad_scale, float dropout_p,
+                      unsigned dropout_seed, int n_marks, const size_t* mark_offsets, void* const* mark_events,
+                      int batch, const float* tgt_z, const float* tgt_x0, const float* weight, int loss_kind,
+                      float huber_delta, void* stream);
+
+/* The loss kernel of sr3_train_step_ex alone, on caller-owned tensors: z, out (the network output) and hr are NCHW
+ * [batch][channels][pixels], channels 1..4; g_nhwc4 [batch][pixels][4] receives -weight[b] * rho'(d) * scale with the lanes
+ * >= channels written 0, *loss_sum_out the weighted loss sum.  tgt_z / tgt_x0 / weight as above (hr_nchw may be NULL when they
+ * are); loss_kind 0..2 (there is no plan to defer to).  scratch: sr3_loss_grad_scratch_bytes() bytes, 8-byte aligned (the blocks'
+ * partial sums).  SR3_E_BADARG as above, and for a NULL tensor, batch / pixels <= 0, channels outside 1..4; SR3_E_ALIGN for a
+ * misaligned scratch. */
+size_t sr3_loss_grad_scratch_bytes(void);
+int sr3_loss_grad_f32(const float* z_nchw, const float* out_nchw, const float* hr_nchw, const float* tgt_z,
+                      const float* tgt_x0, const float* weight, int batch, int channels /* 1..4 */, int pixels,
+                      int loss_kind, float huber_delta, float scale, float* g_nhwc4, float* loss_sum_out,
+                      void* scratch /* sr3_loss_grad_scratch_bytes() */, void* stream);
+
 /* torch.optim.Adam step (model/model.py:39-40,55; defaults beta 0.9/0.999, eps 1e-8, no weight decay)
  * fused over the whole arena; `step` is the 1-based step count for the bias corrections.
  * SR3_E_BADARG (nothing is launched, the message names the argument): a NULL params / grads / exp_avg / exp_avg_sq,
