@@ -305,15 +305,25 @@ template <bool HIST>
 __device__ __forceinline__ StepCoef load_step_coef(const StepTables& tb, const float* c3, int t) {
   return StepCoef{tb.a[t], tb.b[t], tb.c1[t], tb.c2[t], HIST ? c3[t] : 0.f, tb.sigma[t]};
 }
-// one element: returns the new x.  HIST (the multistep tail): + c3 hist before the noise term, then hist <- x0 (after the clamp);
-// the caller's thread owns the element's history, loads it before and stores it after.  clip: clip_denoised (sr3 diffusion.py:162-163)
-template <bool HIST>
-__device__ __forceinline__ float step_tail(const StepCoef& k, bool clip, float x, float eps, float z, float& hist) {
+// one element in two halves, so that a rule for x0 (the block-mean projection of consistency.hip) has a place between them:
+//   step_x0: x0 = a x - b eps, clamped when clip (clip_denoised, sr3 diffusion.py:162-163)
+//   step_mix: returns the new x = ((c1 x0 + c2 x) + c3 hist) + sigma z.  HIST (the multistep tail): + c3 hist before the noise term, then
+//   hist <- x0; the caller's thread owns the element's history, loads it before and stores it after
+__device__ __forceinline__ float step_x0(const StepCoef& k, bool clip, float x, float eps) {
   float x0 = sub_rn(mul_rn(k.a, x), mul_rn(k.b, eps));
   if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+  return x0;
+}
+template <bool HIST>
+__device__ __forceinline__ float step_mix(const StepCoef& k, float x0, float x, float z, float& hist) {
   float mean = add_rn(mul_rn(k.c1, x0), mul_rn(k.c2, x));
   if (HIST) { mean = add_rn(mean, mul_rn(k.c3, hist)); hist = x0; }
   return add_rn(mean, mul_rn(z, k.sigma));
+}
+// ... and their composition: the whole tail of one element, what the three users above run
+template <bool HIST>
+__device__ __forceinline__ float step_tail(const StepCoef& k, bool clip, float x, float eps, float z, float& hist) {
+  return step_mix<HIST>(k, step_x0(k, clip, x, eps), x, z, hist);
 }
 // host check of a step's history arguments, before anything is launched: c3 and hist both or neither; hist (`bytes` long, as x and eps
 // are) overlaps neither x nor eps (eps may be null); align16: the caller's kernel needs hist 16-byte aligned
@@ -378,6 +388,8 @@ int p_sample_update(float* x, const float* eps, const float* z, StepTables tb, c
                     const int64_t* t_per_sample, int step_host, int B, int per_image, hipStream_t st, bool clip = true,
                     const float* c3 = nullptr, float* hist = nullptr);
 int step_decrement(int* step_dev, hipStream_t st);
+// step2[0] <- step2[1] (tiled.hip): the first launch of a step whose tail is a kernel of its own (sr3_tiled_step, sr3_consistent_step)
+int step_copy(int* step2, hipStream_t st);
 // split3_pair self-test (small_kernels.hip): *bad_dev = number of elements whose three bf16 terms do not add back exactly
 int split3_selftest(int* bad_dev, hipStream_t st);
 // q_sample (sr3: per-sample gamma; ddpm: a[t], s[t]) -> x_noisy ; l1 loss sum

@@ -205,6 +205,13 @@ int check_origins(const char* axis, const int* o, int n, int L, int t) {
 }
 
 }  // namespace
+
+int step_copy(int* step2, hipStream_t st) {
+  hipLaunchKernelGGL(k_step_copy, dim3(1), dim3(64), 0, st, step2);
+  SR3_LAUNCH_CHECK("k_step_copy");
+  return SR3_OK;
+}
+
 }  // namespace sr3
 
 using namespace sr3;
@@ -254,8 +261,7 @@ int sr3_tiled_step_hist(float* x_nchw, const float* eps_tiles, int batch, int ch
   const bool vec = (width & 3) == 0;
   if (vec && (((uintptr_t)x_nchw & 15) || ((uintptr_t)z_nchw & 15) || ((uintptr_t)eps_out_nchw & 15) || ((uintptr_t)hist_nchw & 15))) { set_error("tiled_step: misaligned pointer (x, z, eps_out, hist: 16 B)"); return SR3_E_ALIGN; }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_step_copy, dim3(1), dim3(64), 0, st, step2_dev);
-  SR3_LAUNCH_CHECK("k_step_copy");
+  if (const int rc = step_copy(step2_dev, st)) return rc;
   const size_t work = vec ? total / 4 : total;
   const dim3 grid(grid_for(work));
 #define SR3_TS_LAUNCH(V, HI)                                                                            \

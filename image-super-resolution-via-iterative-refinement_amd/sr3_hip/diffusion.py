@@ -25,6 +25,11 @@ Objective (engine extension, `"prediction": "eps" | "v" | "x0"` and `"loss": {"t
 `set_prediction` / `set_objective`): what the network's output stands for and how the training loss weighs it.  Training hands per-image
 target coefficients and weights to sr3_train_step_ex (`prediction_coefs`, `loss_weights`); sampling changes the two tables a, b of the
 step tail's x0c = clip(a x - b out) and nothing else, in every loop.
+
+Consistency (engine extension, `"consistency": {"block": 8, "strength": 1.0}` next to "sampler" / "tiling", or `set_consistency`): every
+step shifts each block x block block of the predicted x0 so that its mean is the target's -- the block means of the conditioning image,
+or `consistency_target=` -- before the posterior mix (the range / null-space projection for an average pool).  Per step: UNet forward
+with eps stored, then sr3_consistent_step (projection + p_sample update + counter decrement) in place of the fused tail.
 """
 import ctypes as C
 
@@ -138,6 +143,23 @@ def _positive(name, v):
     if isinstance(v, bool) or not np.isfinite(f) or not f > 0.0:
         raise ValueError('%s must be finite and > 0 (got %r)' % (name, v))
     return f
+
+
+CONSISTENCY_BLOCKS = (2, 4, 8, 16, 32)      # what sr3_consistent_step takes
+
+
+def block_means(x, block):
+    """The means of the block x block blocks of x [B, C, H, W] (a contiguous fp32 GPU tensor): [B, C, H / block, W / block], each summed
+    in double and rounded once (sr3_block_mean_f32).  max |block_means(SR, r) - block_means(cond, r)| is the consistency error of a
+    result."""
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
+        raise L.Sr3Error('block_means needs a (B, C, H, W) fp32 GPU tensor; there is no CPU fallback')
+    x = x.contiguous()
+    B, Cc, H, W = x.shape
+    block = int(block)
+    out = torch.empty((B, Cc, H // max(block, 1), W // max(block, 1)), device=x.device)
+    L.check(L.load().sr3_block_mean_f32(L.ptr(x), B, Cc, H, W, block, L.ptr(out), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+    return out
 
 
 def prediction_coefs(kind, ca, cb):
@@ -273,6 +295,7 @@ class EngineDiffusion(nn.Module):
         self.objective = None          # None: the reference's loss (loss_type, unweighted); else {'type', 'delta', 'weight', 'gamma'} (set_objective)
         self._train_tables = None      # DDPM variant: per-timestep (tgt_z, tgt_x0, weight) on the device, built on first use
         self.tiling = None             # None: whole-image steps; else {'tile': (th, tw), 'overlap': o, 'batch': n | None} (set_tiling)
+        self.consistency = None        # None: the network's x0 as it is; else {'block': r, 'strength': s} (set_consistency)
         self.max_cached_loops = 3      # reverse-loop states (buffers + workspace + captured graph) kept, one per (shape, launch list)
         # schedule_opt is accepted and ignored exactly like the reference ctor (diffusion.py:80-82)
 
@@ -317,6 +340,7 @@ class EngineDiffusion(nn.Module):
         self._loop_cache = {}
         self._train_tables = None
         self.tiling = None                                                       # (this phase's own "tiling" key is read below)
+        self.consistency = None                                                  # (and its "consistency" key)
         # engine key of the schedule dict: "sampler": {"type": "ddim" | "dpmpp_2m", "steps": S, "eta": e, "walk": "time" | "logsnr"};
         # absent / null: the ancestral loop
         spec = schedule_opt.get('sampler') if hasattr(schedule_opt, 'get') else None
@@ -335,6 +359,14 @@ class EngineDiffusion(nn.Module):
         else:
             t = TL.parse_tiling(spec, self.denoise_fn.plan.divisor)
             self.set_tiling(t['tile'], t['overlap'], t['batch'])
+        # and: "consistency": {"block": 8, "strength": 1.0}; absent / null: the network's x0 as it is
+        spec = schedule_opt.get('consistency') if hasattr(schedule_opt, 'get') else None
+        if spec is None:
+            self.set_consistency(None)
+        else:
+            if not hasattr(spec, 'get') or spec.get('block') is None:
+                raise ValueError('consistency: "block" is required (got %r)' % (spec,))
+            self.set_consistency(spec['block'], spec.get('strength', 1.0))
 
     def set_sampler(self, steps=None, eta=0.0, *, kind='ddim', walk=None):
         """Sample in `steps` reverse steps over a strided walk through the current schedule (DDIM; eta = 0: deterministic, eta = 1 and
@@ -353,6 +385,7 @@ class EngineDiffusion(nn.Module):
                 walk = 'logsnr' if kind == 'dpmpp_2m' else 'time'
             tabs = sampler_tables(self._alphas_cumprod64, steps, eta, kind=kind, walk=walk, prediction=self.prediction)
             self._check_tiled_sampler(True, getattr(self, 'tiling', None))
+            self._check_consistency(getattr(self, 'consistency', None), True, None)
             self.sampler = dict(type=kind, steps=int(steps), eta=float(eta))
             if kind != 'ddim' or walk != 'time':
                 self.sampler['walk'] = walk
@@ -403,8 +436,42 @@ class EngineDiffusion(nn.Module):
         else:
             t = TL.parse_tiling(dict(tile=tile, overlap=overlap, batch=batch), self.denoise_fn.plan.divisor)
             self._check_tiled_sampler(self.sampler is not None, t)
+            self._check_consistency(self.consistency, False, t)
             self.tiling = t
         self._loop_cache = {}
+
+    def set_consistency(self, block=None, strength=1.0):
+        """Sample images whose block means follow a target: every reverse step shifts each block x block block of the predicted x0 by
+        strength * (target mean - its mean) before the posterior mix (sr3_consistent_step; block in 2, 4, 8, 16, 32 and dividing the
+        image's height and width, strength in (0, 1]) -- or, block None, go back to the network's x0 as it is.  The target is the block
+        means of the conditioning image's first `channels` channels, or `consistency_target=` of p_sample_loop / super_resolution.  With
+        strength 1 a chain's result has the target's block means to rounding."""
+        if block is None:
+            self.consistency = None
+        else:
+            if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or int(block) not in CONSISTENCY_BLOCKS:
+                raise ValueError('consistency block must be one of %s (got %r)' % (', '.join(str(b) for b in CONSISTENCY_BLOCKS), block))
+            try:
+                lam = float(strength)
+            except (TypeError, ValueError):
+                raise ValueError('consistency strength must be a number (got %r)' % (strength,))
+            if isinstance(strength, bool) or not (0.0 < lam <= 1.0):
+                raise ValueError('consistency strength must lie in (0, 1] (got %r)' % (strength,))
+            c = dict(block=int(block), strength=lam)
+            self._check_consistency(c, self.sampler is not None, self.tiling)
+            self.consistency = c
+        self._loop_cache = {}
+
+    def _check_consistency(self, consistency, sampler, tiling):
+        if consistency is None:
+            return
+        if tiling is not None:
+            raise NotImplementedError('consistency with tiling: sr3_tiled_step owns the tail of a tiled step and has no projection in it; use '
+                                      'whole-image steps (set_tiling(None)) or switch consistency off (set_consistency(None))')
+        if sampler and self.variant == 'ddpm':
+            raise NotImplementedError('consistency of the DDPM variant under a sampler (DDIM, DPM-Solver++): the forward of a consistent step '
+                                      'runs through sr3_unet_forward, which has no step-index -> timestep map (t_map); use the ancestral '
+                                      'sampler (set_sampler(None)) or switch consistency off (set_consistency(None))')
 
     def _check_tiled_sampler(self, sampler, tiling):
         if sampler and tiling is not None and self.variant == 'ddpm':
@@ -487,7 +554,7 @@ class EngineDiffusion(nn.Module):
         return out
 
     # ---- the reverse loop ------------------------------------------------------------------------
-    def _loop_state(self, shape, cond_shape, dev, item_streams=False, tiles=None):
+    def _loop_state(self, shape, cond_shape, dev, item_streams=False, tiles=None, consistency=None):
         # a captured graph bakes in the arena (the one in use: EngineUNet.use_weights), the freq table and the workspace pointer and
         # the plan's launch list: key on all of them (plan.generation changes with every set_option); the workspace is private to the state.
         # item_streams: one torch generator per image of the batch (`item_seeds` of p_sample_loop) -- the generators are
@@ -497,6 +564,7 @@ class EngineDiffusion(nn.Module):
                un.weights().data_ptr(), un.freq.data_ptr(), un.plan.generation, bool(item_streams),
                None if self.sampler is None else (self.sampler['steps'], self.sampler['eta'], self.sampler['type'],
                                                   self.sampler.get('walk', 'time')),
+               None if consistency is None else (consistency['block'], consistency['strength']),
                None if tiles is None else tiles['key'])      # tiled loop: ((tile_h, tile_w), overlap, tile_batch); the geometry is the tile's
         st = self._loop_cache.get(key)
         if st is None:
@@ -509,6 +577,10 @@ class EngineDiffusion(nn.Module):
                 st['hist'] = torch.zeros(shape, device=dev)      # a multistep sampler: the previous step's x0 (_sample_loop zero-fills it per chain)
             if tiles is not None:
                 self._tile_buffers(st, tiles, shape, cond_shape, dev)
+            if consistency is not None:        # the target block means, and the setting the state (and its captured graph) was built for
+                r = consistency['block']
+                st['ymean'] = torch.zeros((shape[0], shape[1], shape[2] // r, shape[3] // r), device=dev)
+                st['consistency'] = dict(consistency)
             # keep the states of a few image sizes alive (a folder of mixed sizes alternates between them without recapturing);
             # what was built for another arena / schedule / set of plan options can never be hit again: dropped
             # (with EMA weights the model has two arenas, and a state built on either can be hit again)
@@ -578,8 +650,10 @@ class EngineDiffusion(nn.Module):
         sr3_reverse_step: UNet forward with the p_sample update and the counter decrement inside the output conv's kernel.  A state
         with a grid (the tiled loop) instead runs, per chunk of tiles, a gather out of the running image and one UNet forward at the
         tile geometry (level / timestep from the device counter), then the fused tail on the full image -- blend of the tiles' eps,
-        p_sample update, counter decrement (sr3_tiled_step).  A multistep rule passes its c3 table and the state's history buffer
-        along.  st['eps'] keeps the step's (blended) eps for the parity checks that read it."""
+        p_sample update, counter decrement (sr3_tiled_step).  A state with target block means (set_consistency) runs one UNet forward
+        that stores eps, then sr3_consistent_step: the block-mean projection of x0, the p_sample update and the counter decrement on the
+        whole image.  A multistep rule passes its c3 table and the state's history buffer along.  st['eps'] keeps the step's (blended)
+        eps for the parity checks that read it."""
         tables, level, t_map, c3, noisy = rule = self._step_rule()
         st['z_used'] = noisy
         st['tables'] = rule                    # a captured graph bakes their addresses in: they live as long as the state
@@ -588,6 +662,17 @@ class EngineDiffusion(nn.Module):
         img, z = st['img'], st['z'] if noisy else None
         hist = None if c3 is None else st['hist']
         g = st.get('grid')
+        cs = st.get('consistency')
+        if cs is not None:
+            # LR-consistent step: the forward stores eps (level / timestep from the device counter, as the tiled branch's), then the
+            # tail with the block-mean projection of x0 in it (sr3_consistent_step: counter copy + one kernel)
+            assert t_map is None and g is None      # (_check_consistency refused both)
+            self.denoise_fn(img, None, cond=st['cond'], level_table=level, step_dev=st['step'][1:], out=st['eps'], ws=st['ws'])
+            B, Cc, H, W = img.shape
+            L.check(L.load().sr3_consistent_step(L.ptr(img), L.ptr(st['eps']), L.ptr(z), L.ptr(st['ymean']), B, Cc, H, W, cs['block'],
+                                                 cs['strength'], *[L.ptr(t) for t in tables], L.ptr(st['step']), 1, L.ptr(c3),
+                                                 L.ptr(hist), self._stream(img.device)))
+            return
         if g is None:
             self.denoise_fn.reverse_step(img, z, tables, st['step'], cond=st['cond'], level_table=level, clip_denoised=True,
                                          eps_out=st['eps'], ws=st['ws'], t_map=t_map, c3=c3, hist=hist)
@@ -636,15 +721,17 @@ class EngineDiffusion(nn.Module):
         st['graph'] = g
 
     @torch.no_grad()
-    def p_sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None):
+    def p_sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None, consistency_target=None):
         """The reverse loop (`_sample_loop`); with tiling set (set_tiling / the "tiling" key) an input larger than the tile on either axis
-        goes through the tiled loop instead."""
+        goes through the tiled loop instead.  consistency_target: under set_consistency, the [B, C, H / block, W / block] block means to
+        steer towards instead of the conditioning image's (the dataset's real LR image when block is the scale factor)."""
         t = self.tiling
         if t is not None:
             shape = tuple(x_in) if not self.conditional else tuple(x_in.shape)
             if len(shape) == 4 and (shape[2] > t['tile'][0] or shape[3] > t['tile'][1]):
-                return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, tiling=t)
-        return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds)
+                return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, tiling=t,
+                                         consistency_target=consistency_target)
+        return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, consistency_target=consistency_target)
 
     @torch.no_grad()
     def p_sample_loop_tiled(self, x_in, continous=False, *, tile, overlap, tile_batch=None, x_T=None, noise_seq=None, item_seeds=None):
@@ -657,13 +744,22 @@ class EngineDiffusion(nn.Module):
         t = TL.parse_tiling(dict(tile=tile, overlap=overlap, batch=tile_batch), self.denoise_fn.plan.divisor)
         return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, tiling=t)
 
-    def _sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None, tiling=None):
+    def _sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None, tiling=None, consistency_target=None):
         """sr3 diffusion.py:176-200 / ddpm :200-230.  Extensions: `x_T` injects the initial draw, `noise_seq[i]` the noise
         consumed at step i (the parity tests); `item_seeds` (one int per image of the batch) gives every image its own noise
         stream -- x_T and every step's z of image i come from a generator seeded with item_seeds[i], so the image's chain does
         not depend on which batch it rides in (sr3_hip.dist.ValWave batches the validation items the reference's infer.py /
         sr.py feed one by one, infer.py:67-71).  Under a sampler (set_sampler) the loop takes its S steps instead of T, i counts
-        the step index S-1 .. 0 (what `noise_seq` and the snapshot stride 1 | S // 10 go by), and eta = 0 draws x_T only."""
+        the step index S-1 .. 0 (what `noise_seq` and the snapshot stride 1 | S // 10 go by), and eta = 0 draws x_T only.  Under
+        set_consistency every step is an LR-consistent one (`_one_step`), towards the block means of the conditioning image or
+        `consistency_target`."""
+        cs = self.consistency
+        if cs is None and consistency_target is not None:
+            raise ValueError('consistency_target is given but consistency is off (set_consistency / the "consistency" key)')
+        self._check_consistency(cs, self.sampler is not None, tiling)
+        if cs is not None and not self.conditional and consistency_target is None:
+            raise NotImplementedError('consistency on an unconditional model needs consistency_target=: there is no conditioning image to '
+                                      'take the block means from')
         dev = self.betas.device
         if dev.type != 'cuda':
             raise L.Sr3Error('p_sample_loop needs the model on a GPU (set gpu_ids); there is no CPU fallback')
@@ -685,6 +781,14 @@ class EngineDiffusion(nn.Module):
             raise L.Sr3Error('p_sample_loop: a (B, C, H, W) image or shape is expected (got %s)' % (shape,))
         # the image size comes from the input, as in the reference (`shape = x.shape`); the launch list -- and with it
         # plan.generation, part of the state's key -- follows it
+        if cs is not None:
+            r = cs['block']
+            if shape[2] % r or shape[3] % r:
+                raise L.Sr3Error('p_sample_loop: consistency block %d does not divide the image (%d x %d)' % (r, shape[2], shape[3]))
+            want = (shape[0], shape[1], shape[2] // r, shape[3] // r)
+            if consistency_target is not None and (not torch.is_tensor(consistency_target) or tuple(consistency_target.shape) != want):
+                raise L.Sr3Error('p_sample_loop: consistency_target must be a %s tensor of block means (got %s)'
+                                 % (want, tuple(getattr(consistency_target, 'shape', ())) or type(consistency_target).__name__))
         tiles = None
         if tiling is not None:
             # tiled: the plan runs at the TILE's geometry; everything is validated here, before anything is written
@@ -696,7 +800,7 @@ class EngineDiffusion(nn.Module):
             self.denoise_fn.plan.set_geometry(grid.th, grid.tw)
         else:
             self.denoise_fn.plan.set_geometry(shape[2], shape[3])
-        st = self._loop_state(shape, None if cond is None else shape, dev, item_streams=item_seeds is not None, tiles=tiles)
+        st = self._loop_state(shape, None if cond is None else shape, dev, item_streams=item_seeds is not None, tiles=tiles, consistency=cs)
         self.denoise_fn.ensure_derived()       # a replayed graph does not pass through EngineUNet.forward
         if item_seeds is not None:
             for g, v in zip(st['gens'], item_seeds):
@@ -711,6 +815,13 @@ class EngineDiffusion(nn.Module):
             st['cond'].copy_(cond)
             if tiles is not None:              # the conditioning image does not change: cut into tiles once
                 self._gather_tiles(st, st['cond'], st['cond_tiles'], 0, st['cond_tiles'].shape[0])
+        if cs is not None:                     # the target does not change over the chain: its block means once
+            if consistency_target is not None:
+                st['ymean'].copy_(consistency_target)
+            else:
+                B, Cc, H, W = shape
+                src = st['cond'] if st['cond'].shape[1] == Cc else st['cond'][:, :Cc].contiguous()
+                L.check(L.load().sr3_block_mean_f32(L.ptr(src), B, Cc, H, W, cs['block'], L.ptr(st['ymean']), self._stream(dev)))
         if st.get('hist') is not None:         # the first step's c3 is 0, but 0 * (whatever the last chain left, a NaN for one) is not 0
             st['hist'].zero_()
         st['step'].fill_(T - 1)                # (slot 1 = t of the next step; slot 0 is the step's scratch copy)
@@ -753,8 +864,8 @@ class EngineDiffusion(nn.Module):
         return self.p_sample_loop((batch_size, self.channels, self.image_size, self.image_size), continous, item_seeds=item_seeds)
 
     @torch.no_grad()
-    def super_resolution(self, x_in, continous=False, *, item_seeds=None):
-        return self.p_sample_loop(x_in, continous, item_seeds=item_seeds)
+    def super_resolution(self, x_in, continous=False, *, item_seeds=None, consistency_target=None):
+        return self.p_sample_loop(x_in, continous, item_seeds=item_seeds, consistency_target=consistency_target)
 
     # ---- forward process / loss --------------------------------------------------------------------
     def _q_sample_coef(self, x_start, ca, cb, noise):

@@ -366,6 +366,41 @@ int sr3_tiled_step_hist(float* x_nchw, const float* eps_tiles, int batch, int ch
                         const float* tab_c2, const float* tab_sigma, int* step2_dev, int clip_denoised, float* eps_out_nchw, void* stream,
                         const float* tab_c3, float* hist_nchw);
 
+/* ---- LR-consistent sampling (engine extension; no reference counterpart) ------------------------
+ * The range / null-space projection of DDNM (Wang et al. 2022) for the block x block average pool, in the tail of a reverse step: every
+ * step shifts each block of the predicted x0 so that its mean is the target's (times `strength`), and keeps the rest from the network. */
+
+/* dst_means[b, c, by, bx] = the mean of the block x block block (by, bx) of src_nchw [batch, channels, height, width], summed in double
+ * in a fixed order and rounded once: [batch, channels, height / block, width / block].  What sr3_consistent_step's targets are made
+ * with, and what measures a result's consistency error max |block_mean(SR) - block_mean(LR upsampled)|.  Any alignment (a width or
+ * block that is no multiple of 4, or a src_nchw off a 16-byte boundary, takes the one-element-per-thread form).
+ * SR3_E_BADARG: NULL src_nchw / dst_means, non-positive size, block not in {2, 4, 8, 16, 32} or not dividing both height and width,
+ * dst_means overlapping src_nchw; SR3_E_UNSUPPORTED: batch * channels * height * width >= 2^31.  Nothing is launched on a refusal. */
+int sr3_block_mean_f32(const float* src_nchw, int batch, int channels, int height, int width, int block, float* dst_means, void* stream);
+
+/* The tail of one LR-consistent reverse step, in place on x_nchw [batch, channels, height, width], with j = step2_dev[1] on entry,
+ * r = block, y = target_means [batch, channels, height / r, width / r]:
+ *   x0  = a[j] x - b[j] eps ; clamp(-1, 1) if clip_denoised          (sr3_p_sample_step_ex's operations; clamp first, then project:
+ *                                                                     the projected value may leave [-1, 1])
+ *   S   = sum over the r x r block of (double) x0                    (fixed order, no atomics)
+ *   d   = (float)((double) strength * ((double) y - S / (double)(r r)))      one rounding to fp32
+ *   x0' = x0 + d
+ *   x   = ((c1[j] x0' + c2[j] x) + c3[j] hist) + sigma[j] z ; hist <- x0'    (sr3_p_sample_step_hist's operations and association;
+ *                                                                             tab_c3 / hist_nchw both NULL: no history term)
+ * every fp32 product, sum and difference rounded separately.  step2_dev[1] = j - 1 on completion (step2_dev[0] is scratch, as in
+ * sr3_tiled_step).  With strength 1 the block means of x0' are the target's to rounding.  eps_nchw is the network's output for this
+ * step (sr3_unet_forward with step_dev = step2_dev + 1); z_nchw: the step's noise or NULL (= 0); tab_*: as sr3_reverse_step.
+ * Two launches; bitwise reproducible.  Any alignment (width % 4 != 0, block % 4 != 0 or a pointer off a 16-byte boundary takes the
+ * one-element-per-thread form, the same bits).
+ * SR3_E_BADARG (the message names the argument): NULL required pointer, non-positive size, block not in {2, 4, 8, 16, 32} or not
+ * dividing both height and width, strength NaN or outside (0, 1], only one of tab_c3 / hist_nchw, hist_nchw overlapping x_nchw or
+ * eps_nchw, target_means overlapping x_nchw; SR3_E_UNSUPPORTED: batch * channels * height * width >= 2^31.  Nothing is launched on a
+ * refusal. */
+int sr3_consistent_step(float* x_nchw, const float* eps_nchw, const float* z_nchw, const float* target_means, int batch, int channels,
+                        int height, int width, int block, float strength, const float* tab_a, const float* tab_b, const float* tab_c1,
+                        const float* tab_c2, const float* tab_sigma, int* step2_dev, int clip_denoised, const float* tab_c3,
+                        float* hist_nchw, void* stream);
+
 /* q_sample (model/sr3_modules/diffusion.py:212-219; model/ddpm_modules/diffusion.py:259-267):
  * out = ca[b] * x0 + cb[b] * z */
 int sr3_q_sample(const float* x0, const float* z, const float* ca, const float* cb, int batch,

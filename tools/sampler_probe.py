@@ -3,8 +3,10 @@
 captured step graph of the BASELINE config at its batch, replayed --replays times per leg and timed with HIP events -- the ancestral
 loop, the DDIM sampler at eta = 0 (no RNG node, no z read) and at eta = 0.5, and the multistep solver dpmpp_2m (eta = 0, plus one read
 and one write of the image-sized history in the output conv's epilogue) -- legs interleaved --reps times, best and median per leg; then
-the wall time of whole `super_resolution` chains of --chain steps (capture excluded).
-    python tools/sampler_probe.py [--config sr3_16_128] [--replays 200] [--reps 3] [--chain 100]      (GPU box)"""
+the wall time of whole `super_resolution` chains of --chain steps (capture excluded).  --consistency R adds a leg: dpmpp_2m with the
+block-mean projection of set_consistency(R) in its tail (three graph nodes -- forward with eps stored, counter copy, sr3_consistent_step
+-- in place of the fused step), next to the dpmpp_2m leg in every round.
+    python tools/sampler_probe.py [--config sr3_16_128] [--replays 200] [--reps 3] [--chain 100] [--consistency 8]      (GPU box)"""
 import argparse
 import json
 import os
@@ -22,6 +24,7 @@ def main():
     ap.add_argument('--replays', type=int, default=200)
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--chain', type=int, default=100)
+    ap.add_argument('--consistency', type=int, default=0, metavar='BLOCK', help='add the dpmpp_2m leg with set_consistency(BLOCK)')
     a = ap.parse_args()
     sys.path.insert(0, PKG)
     sys.path.insert(0, ROOT)
@@ -43,13 +46,21 @@ def main():
     N = a.replays
     legs = {'ancestral': dict(steps=None), 'ddim_eta0': dict(steps=N, eta=0.0), 'ddim_eta0.5': dict(steps=N, eta=0.5),
             'dpmpp_2m': dict(steps=N, kind='dpmpp_2m')}
+    if a.consistency:
+        assert cond is not None, '--consistency needs a conditional config'
+        legs['dpmpp_2m_consistency'] = dict(steps=N, kind='dpmpp_2m', consistency=a.consistency)
     states = {}
     for name, spec in legs.items():                      # one captured graph per leg, all alive at once
+        spec = dict(spec)
+        netG.set_consistency(spec.pop('consistency', None))
         netG.set_sampler(**spec)
-        st = netG._loop_state(shape, shape if cond is not None else None, dev)
+        st = netG._loop_state(shape, shape if cond is not None else None, dev, consistency=netG.consistency)
         netG.denoise_fn.ensure_derived()
         if cond is not None:
             st['cond'].copy_(cond)
+        if netG.consistency is not None:
+            from sr3_hip.diffusion import block_means
+            st['ymean'].copy_(block_means(cond, a.consistency))
         netG._capture(st)
         states[name] = st
     ms = {name: [] for name in legs}
@@ -72,6 +83,7 @@ def main():
     rec = {'what': 'sampler step', 'config': a.config, 'batch': B, 'replays': N, 'reps': a.reps}
     for name in legs:
         rec['ms_per_step_' + name] = {'best': min(ms[name]), 'median': statistics.median(ms[name])}
+    netG.set_consistency(None)
     arg = cond if cond is not None else shape
     for kind, eta in (('ddim', 0.0), ('ddim', 0.5), ('dpmpp_2m', 0.0)):
         netG.set_sampler(a.chain, eta, kind=kind)
