@@ -154,11 +154,6 @@ int check_blocks(const char* who, int batch, int channels, int height, int width
   return SR3_OK;
 }
 
-bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
 }  // namespace
 }  // namespace sr3
 

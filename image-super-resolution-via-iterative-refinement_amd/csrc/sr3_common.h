@@ -325,6 +325,11 @@ template <bool HIST>
 __device__ __forceinline__ float step_tail(const StepCoef& k, bool clip, float x, float eps, float z, float& hist) {
   return step_mix<HIST>(k, step_x0(k, clip, x, eps), x, z, hist);
 }
+// do the byte ranges [a, a + abytes) and [b, b + bbytes) share a byte?  (host side: the argument checks of the step tails)
+inline bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
 // host check of a step's history arguments, before anything is launched: c3 and hist both or neither; hist (`bytes` long, as x and eps
 // are) overlaps neither x nor eps (eps may be null); align16: the caller's kernel needs hist 16-byte aligned
 inline int check_step_history(const char* who, const float* c3, const float* hist, const float* x, const float* eps, size_t bytes,

@@ -39,13 +39,17 @@ def define_G(opt):
         schedule_opt=model_opt['beta_schedule']['train'])
     # engine keys of model.diffusion (absent in the reference's configs; absent = the reference's objective): "prediction": "eps" | "v" |
     # "x0", what the network's output stands for, and "loss": {"type": "l1" | "l2" | "huber", "delta", "weight": "uniform" | "min_snr",
-    # "gamma"} (sr3_hip/diffusion.py: set_prediction, set_objective).  *_gen.pth does not record them: the config carries them
+    # "gamma"} (sr3_hip/diffusion.py: set_prediction, set_objective); "cond_drop": p, the probability that a training image's conditioning
+    # is zeroed -- what a model needs to have seen for guided sampling (set_cond_drop).  *_gen.pth does not record them: the config
+    # carries them
     d = model_opt['diffusion']
     if d.get('prediction') is not None:
         netG.set_prediction(d['prediction'])
     loss = d.get('loss')
     if loss is not None:
         netG.set_objective(loss.get('type', 'l1'), loss.get('delta'), loss.get('weight', 'uniform'), loss.get('gamma'))
+    if d.get('cond_drop') is not None:
+        netG.set_cond_drop(d['cond_drop'])
     if opt['phase'] == 'train':
         init_weights(netG, init_type='orthogonal')
     return netG

@@ -30,6 +30,12 @@ Consistency (engine extension, `"consistency": {"block": 8, "strength": 1.0}` ne
 step shifts each block x block block of the predicted x0 so that its mean is the target's -- the block means of the conditioning image,
 or `consistency_target=` -- before the posterior mix (the range / null-space projection for an average pool).  Per step: UNet forward
 with eps stored, then sr3_consistent_step (projection + p_sample update + counter decrement) in place of the fused tail.
+
+Guidance (engine extension, `"guidance": {"scale": 1.5, "threshold": "dynamic", "percentile": 0.995}` next to "sampler", or `set_guidance`;
+`"cond_drop": p` in model.diffusion, or `set_cond_drop`, trains a model for it): classifier-free guidance -- two UNet forwards per step,
+on the conditioning image and on a zero one, combined as out_u + scale (out_c - out_u) before x0 is formed -- and what is done to x0
+where it leaves [-1, 1]: the static clamp, nothing, or dynamic thresholding (each image's x0 divided by its own percentile of |x0|).
+Per step: the forward(s) with the output stored, then sr3_guided_step in place of the fused tail.
 """
 import ctypes as C
 
@@ -160,6 +166,25 @@ def block_means(x, block):
     out = torch.empty((B, Cc, H // max(block, 1), W // max(block, 1)), device=x.device)
     L.check(L.load().sr3_block_mean_f32(L.ptr(x), B, Cc, H, W, block, L.ptr(out), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
     return out
+
+
+THRESHOLDS = ('none', 'static', 'dynamic')      # the mode numbers of sr3_guided_step, in order
+
+
+def quantile_rank(n, p):
+    """Where the p-quantile (p in [0, 1]) of n sorted values sits, as sr3_abs_quantile_f32 takes it: (rank_lo, frac) with
+    pos = p (n - 1), rank_lo = floor(pos), frac = pos - rank_lo in [0, 1), all in float64 (numpy.quantile's 'linear' rule).  Pure, no device."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 1:
+        raise ValueError('quantile_rank: n must be a positive integer (got %r)' % (n,))
+    try:
+        pf = float(p)
+    except (TypeError, ValueError):
+        raise ValueError('quantile_rank: p must be a number (got %r)' % (p,))
+    if isinstance(p, bool) or not 0.0 <= pf <= 1.0:
+        raise ValueError('quantile_rank: p must lie in [0, 1] (got %r)' % (p,))
+    pos = np.float64(pf) * np.float64(int(n) - 1)
+    rank_lo = int(np.floor(pos))
+    return rank_lo, float(pos - np.float64(rank_lo))
 
 
 def prediction_coefs(kind, ca, cb):
@@ -296,6 +321,9 @@ class EngineDiffusion(nn.Module):
         self._train_tables = None      # DDPM variant: per-timestep (tgt_z, tgt_x0, weight) on the device, built on first use
         self.tiling = None             # None: whole-image steps; else {'tile': (th, tw), 'overlap': o, 'batch': n | None} (set_tiling)
         self.consistency = None        # None: the network's x0 as it is; else {'block': r, 'strength': s} (set_consistency)
+        self.guidance = None           # None: one forward, the fused tail; else {'scale': w, 'threshold': mode, 'percentile': p} (set_guidance)
+        self.cond_drop = 0.0           # training: the probability that an image's conditioning is replaced by zeros (set_cond_drop)
+        self._cond_drop_buf = None     # ... and the buffer the dropped conditioning is written to
         self.max_cached_loops = 3      # reverse-loop states (buffers + workspace + captured graph) kept, one per (shape, launch list)
         # schedule_opt is accepted and ignored exactly like the reference ctor (diffusion.py:80-82)
 
@@ -341,6 +369,7 @@ class EngineDiffusion(nn.Module):
         self._train_tables = None
         self.tiling = None                                                       # (this phase's own "tiling" key is read below)
         self.consistency = None                                                  # (and its "consistency" key)
+        self.guidance = None                                                     # (and its "guidance" key)
         # engine key of the schedule dict: "sampler": {"type": "ddim" | "dpmpp_2m", "steps": S, "eta": e, "walk": "time" | "logsnr"};
         # absent / null: the ancestral loop
         spec = schedule_opt.get('sampler') if hasattr(schedule_opt, 'get') else None
@@ -367,6 +396,14 @@ class EngineDiffusion(nn.Module):
             if not hasattr(spec, 'get') or spec.get('block') is None:
                 raise ValueError('consistency: "block" is required (got %r)' % (spec,))
             self.set_consistency(spec['block'], spec.get('strength', 1.0))
+        # and: "guidance": {"scale": 1.5, "threshold": "static" | "none" | "dynamic", "percentile": 0.995}; absent / null: off
+        spec = schedule_opt.get('guidance') if hasattr(schedule_opt, 'get') else None
+        if spec is None:
+            self.set_guidance(None)
+        else:
+            if not hasattr(spec, 'get'):
+                raise ValueError('guidance: a dict of "scale", "threshold", "percentile" is expected (got %r)' % (spec,))
+            self.set_guidance(spec.get('scale', 1.0), spec.get('threshold', 'static'), spec.get('percentile', 0.995))
 
     def set_sampler(self, steps=None, eta=0.0, *, kind='ddim', walk=None):
         """Sample in `steps` reverse steps over a strided walk through the current schedule (DDIM; eta = 0: deterministic, eta = 1 and
@@ -386,6 +423,7 @@ class EngineDiffusion(nn.Module):
             tabs = sampler_tables(self._alphas_cumprod64, steps, eta, kind=kind, walk=walk, prediction=self.prediction)
             self._check_tiled_sampler(True, getattr(self, 'tiling', None))
             self._check_consistency(getattr(self, 'consistency', None), True, None)
+            self._check_guidance(getattr(self, 'guidance', None), True, None, None)
             self.sampler = dict(type=kind, steps=int(steps), eta=float(eta))
             if kind != 'ddim' or walk != 'time':
                 self.sampler['walk'] = walk
@@ -437,6 +475,7 @@ class EngineDiffusion(nn.Module):
             t = TL.parse_tiling(dict(tile=tile, overlap=overlap, batch=batch), self.denoise_fn.plan.divisor)
             self._check_tiled_sampler(self.sampler is not None, t)
             self._check_consistency(self.consistency, False, t)
+            self._check_guidance(self.guidance, False, t, None)
             self.tiling = t
         self._loop_cache = {}
 
@@ -459,8 +498,71 @@ class EngineDiffusion(nn.Module):
                 raise ValueError('consistency strength must lie in (0, 1] (got %r)' % (strength,))
             c = dict(block=int(block), strength=lam)
             self._check_consistency(c, self.sampler is not None, self.tiling)
+            self._check_guidance(self.guidance, False, None, c)
             self.consistency = c
         self._loop_cache = {}
+
+    def set_guidance(self, scale=None, threshold=None, percentile=0.995):
+        """Guided sampling: every reverse step combines the network's output on the conditioning image with its output on a zero
+        condition, out = out_u + scale (out_c - out_u) (classifier-free guidance; scale 1: the conditional output alone, and the second
+        forward is skipped), and treats the predicted x0 by `threshold`: 'static' (the default: the clamp to [-1, 1] every loop applies),
+        'none', or 'dynamic' -- each image's x0 clamped to +-s and divided by s, s = max(1, its `percentile`-quantile of |x0|)
+        (sr3_guided_step).  scale None and threshold None: off, back to the fused step.  A model follows the scale only if it has seen
+        empty conditions in training (set_cond_drop)."""
+        if scale is None and threshold is None:
+            self.guidance = None
+        else:
+            if scale is None:
+                scale = 1.0
+            if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not np.isfinite(float(scale)):
+                raise ValueError('guidance scale must be a finite number (got %r)' % (scale,))
+            if threshold is None:
+                threshold = 'static'
+            if threshold not in THRESHOLDS:
+                raise ValueError('guidance threshold must be one of %s (got %r)' % (', '.join(repr(k) for k in THRESHOLDS), threshold))
+            if threshold == 'dynamic':
+                try:
+                    pf = float(percentile)
+                except (TypeError, ValueError):
+                    raise ValueError('guidance percentile must be a number (got %r)' % (percentile,))
+                if isinstance(percentile, bool) or not 0.0 <= pf <= 1.0:
+                    raise ValueError('guidance percentile must lie in [0, 1] (got %r)' % (percentile,))
+                percentile = pf
+            else:
+                percentile = None
+            if not self.conditional:
+                raise ValueError('guidance on an unconditional model: there is no conditioning image to drop')
+            gd = dict(scale=float(scale), threshold=threshold, percentile=percentile)
+            self._check_guidance(gd, self.sampler is not None, self.tiling, self.consistency)
+            self.guidance = gd
+        self._loop_cache = {}
+
+    def set_cond_drop(self, p=0.0):
+        """Training for classifier-free guidance: with probability p (0 <= p < 1) an image's conditioning is replaced by zeros in
+        p_losses (sr3_cond_drop_f32), drawn per image after every other draw of the step.  0: off."""
+        try:
+            pf = float(p)
+        except (TypeError, ValueError):
+            raise ValueError('cond_drop must be a number (got %r)' % (p,))
+        if isinstance(p, bool) or not 0.0 <= pf < 1.0:
+            raise ValueError('cond_drop must lie in [0, 1) (got %r)' % (p,))
+        if pf > 0.0 and not self.conditional:
+            raise ValueError('cond_drop on an unconditional model: there is no conditioning image to drop')
+        self.cond_drop = pf
+
+    def _check_guidance(self, guidance, sampler, tiling, consistency):
+        if guidance is None:
+            return
+        if tiling is not None:
+            raise NotImplementedError('guidance with tiling: sr3_tiled_step owns the tail of a tiled step and combines no second forward; use '
+                                      'whole-image steps (set_tiling(None)) or switch guidance off (set_guidance(None))')
+        if consistency is not None:
+            raise NotImplementedError('guidance with consistency: sr3_guided_step and sr3_consistent_step each own the whole tail of a step; '
+                                      'switch one of them off (set_guidance(None) / set_consistency(None))')
+        if sampler and self.variant == 'ddpm':
+            raise NotImplementedError('guidance of the DDPM variant under a sampler (DDIM, DPM-Solver++): the forwards of a guided step '
+                                      'run through sr3_unet_forward, which has no step-index -> timestep map (t_map); use the ancestral '
+                                      'sampler (set_sampler(None)) or switch guidance off (set_guidance(None))')
 
     def _check_consistency(self, consistency, sampler, tiling):
         if consistency is None:
@@ -554,7 +656,7 @@ class EngineDiffusion(nn.Module):
         return out
 
     # ---- the reverse loop ------------------------------------------------------------------------
-    def _loop_state(self, shape, cond_shape, dev, item_streams=False, tiles=None, consistency=None):
+    def _loop_state(self, shape, cond_shape, dev, item_streams=False, tiles=None, consistency=None, guidance=None):
         # a captured graph bakes in the arena (the one in use: EngineUNet.use_weights), the freq table and the workspace pointer and
         # the plan's launch list: key on all of them (plan.generation changes with every set_option); the workspace is private to the state.
         # item_streams: one torch generator per image of the batch (`item_seeds` of p_sample_loop) -- the generators are
@@ -564,6 +666,7 @@ class EngineDiffusion(nn.Module):
                un.weights().data_ptr(), un.freq.data_ptr(), un.plan.generation, bool(item_streams),
                None if self.sampler is None else (self.sampler['steps'], self.sampler['eta'], self.sampler['type'],
                                                   self.sampler.get('walk', 'time')),
+               None if guidance is None else (guidance['scale'], guidance['threshold'], guidance['percentile']),
                None if consistency is None else (consistency['block'], consistency['strength']),
                None if tiles is None else tiles['key'])      # tiled loop: ((tile_h, tile_w), overlap, tile_batch); the geometry is the tile's
         st = self._loop_cache.get(key)
@@ -581,6 +684,8 @@ class EngineDiffusion(nn.Module):
                 r = consistency['block']
                 st['ymean'] = torch.zeros((shape[0], shape[1], shape[2] // r, shape[3] // r), device=dev)
                 st['consistency'] = dict(consistency)
+            if guidance is not None:
+                self._guidance_buffers(st, guidance, shape, cond_shape, dev)
             # keep the states of a few image sizes alive (a folder of mixed sizes alternates between them without recapturing);
             # what was built for another arena / schedule / set of plan options can never be hit again: dropped
             # (with EMA weights the model has two arenas, and a state built on either can be hit again)
@@ -593,6 +698,23 @@ class EngineDiffusion(nn.Module):
         else:
             self._loop_cache[key] = self._loop_cache.pop(key)      # most recently used last
         return st
+
+    def _guidance_buffers(self, st, guidance, shape, cond_shape, dev):
+        """What a guided loop's state holds besides the plain loop's: the setting it (and its captured graph) was built for, the zero
+        conditioning image and the second forward's output (scale != 1 only), the per-image thresholds, and for the dynamic threshold
+        x0 of the whole batch, the select's scratch and the ranks of the percentile."""
+        st['guidance'] = dict(guidance)
+        st['thr'] = torch.zeros(shape[0], device=dev)
+        st['cond0'] = st['eps_u'] = st['x0'] = st['qscratch'] = None
+        st['rank_lo'], st['frac'] = 0, 0.0
+        if guidance['scale'] != 1.0:
+            st['cond0'] = torch.zeros(cond_shape, device=dev)
+            st['eps_u'] = torch.zeros(shape, device=dev)
+        if guidance['threshold'] == 'dynamic':
+            n = int(shape[1] * shape[2] * shape[3])
+            st['rank_lo'], st['frac'] = quantile_rank(n, guidance['percentile'])
+            st['x0'] = torch.empty(shape, device=dev)
+            st['qscratch'] = torch.empty(int(L.load().sr3_abs_quantile_scratch_bytes(shape[0], n)), dtype=torch.uint8, device=dev)
 
     def _tile_buffers(self, st, tiles, shape, cond_shape, dev):
         """What a tiled loop's state holds besides the whole-image tensors: the grid's origins and windows on the device, the chunk
@@ -653,7 +775,9 @@ class EngineDiffusion(nn.Module):
         p_sample update, counter decrement (sr3_tiled_step).  A state with target block means (set_consistency) runs one UNet forward
         that stores eps, then sr3_consistent_step: the block-mean projection of x0, the p_sample update and the counter decrement on the
         whole image.  A multistep rule passes its c3 table and the state's history buffer along.  st['eps'] keeps the step's (blended)
-        eps for the parity checks that read it."""
+        eps for the parity checks that read it.  A state with a guidance setting (set_guidance) runs the forward with the output stored,
+        a second one on the zero conditioning image into st['eps_u'] unless the scale is 1, then sr3_guided_step: the two outputs
+        combined, the threshold rule on x0 (st['thr'] keeps each image's), the p_sample update and the counter decrement."""
         tables, level, t_map, c3, noisy = rule = self._step_rule()
         st['z_used'] = noisy
         st['tables'] = rule                    # a captured graph bakes their addresses in: they live as long as the state
@@ -672,6 +796,21 @@ class EngineDiffusion(nn.Module):
             L.check(L.load().sr3_consistent_step(L.ptr(img), L.ptr(st['eps']), L.ptr(z), L.ptr(st['ymean']), B, Cc, H, W, cs['block'],
                                                  cs['strength'], *[L.ptr(t) for t in tables], L.ptr(st['step']), 1, L.ptr(c3),
                                                  L.ptr(hist), self._stream(img.device)))
+            return
+        gd = st.get('guidance')
+        if gd is not None:
+            # guided step: one forward per condition, the same plan, batch and workspace, one after the other (level / timestep from
+            # the device counter, which only the tail's last kernel moves), then the tail (sr3_guided_step)
+            assert t_map is None and g is None      # (_check_guidance refused both)
+            self.denoise_fn(img, None, cond=st['cond'], level_table=level, step_dev=st['step'][1:], out=st['eps'], ws=st['ws'])
+            if st['eps_u'] is not None:
+                self.denoise_fn(img, None, cond=st['cond0'], level_table=level, step_dev=st['step'][1:], out=st['eps_u'], ws=st['ws'])
+            B, Cc, H, W = img.shape
+            qs = st['qscratch']
+            L.check(L.load().sr3_guided_step(L.ptr(img), L.ptr(st['eps']), L.ptr(st['eps_u']), gd['scale'], L.ptr(z), B, Cc, H, W,
+                                             *[L.ptr(t) for t in tables], L.ptr(c3), L.ptr(hist), L.ptr(st['step']),
+                                             THRESHOLDS.index(gd['threshold']), st['rank_lo'], st['frac'], L.ptr(st['x0']), L.ptr(qs),
+                                             0 if qs is None else qs.numel(), L.ptr(st['thr']), self._stream(img.device)))
             return
         if g is None:
             self.denoise_fn.reverse_step(img, z, tables, st['step'], cond=st['cond'], level_table=level, clip_denoised=True,
@@ -752,11 +891,13 @@ class EngineDiffusion(nn.Module):
         sr.py feed one by one, infer.py:67-71).  Under a sampler (set_sampler) the loop takes its S steps instead of T, i counts
         the step index S-1 .. 0 (what `noise_seq` and the snapshot stride 1 | S // 10 go by), and eta = 0 draws x_T only.  Under
         set_consistency every step is an LR-consistent one (`_one_step`), towards the block means of the conditioning image or
-        `consistency_target`."""
+        `consistency_target`.  Under set_guidance every step is a guided one."""
         cs = self.consistency
         if cs is None and consistency_target is not None:
             raise ValueError('consistency_target is given but consistency is off (set_consistency / the "consistency" key)')
         self._check_consistency(cs, self.sampler is not None, tiling)
+        gd = self.guidance
+        self._check_guidance(gd, self.sampler is not None, tiling, cs)
         if cs is not None and not self.conditional and consistency_target is None:
             raise NotImplementedError('consistency on an unconditional model needs consistency_target=: there is no conditioning image to '
                                       'take the block means from')
@@ -800,7 +941,8 @@ class EngineDiffusion(nn.Module):
             self.denoise_fn.plan.set_geometry(grid.th, grid.tw)
         else:
             self.denoise_fn.plan.set_geometry(shape[2], shape[3])
-        st = self._loop_state(shape, None if cond is None else shape, dev, item_streams=item_seeds is not None, tiles=tiles, consistency=cs)
+        st = self._loop_state(shape, None if cond is None else shape, dev, item_streams=item_seeds is not None, tiles=tiles, consistency=cs,
+                              guidance=gd)
         self.denoise_fn.ensure_derived()       # a replayed graph does not pass through EngineUNet.forward
         if item_seeds is not None:
             for g, v in zip(st['gens'], item_seeds):
@@ -884,11 +1026,13 @@ class EngineDiffusion(nn.Module):
         t = t_or_gamma.long()
         return self._q_sample_coef(x_start, self.sqrt_alphas_cumprod[t], self.sqrt_one_minus_alphas_cumprod[t], noise)
 
-    def p_losses(self, x_in, noise=None, *, gamma=None, t=None, drop_seed=None):
+    def p_losses(self, x_in, noise=None, *, gamma=None, t=None, drop_seed=None, cond_keep=None):
         """sr3 diffusion.py:221-246 / ddpm :278-294.  Draws (t, gamma, z) exactly as the reference does
         (numpy global RNG for the SR3 level, torch RNG for z / the DDPM timesteps) unless injected, then
         runs forward + backward in one engine call: returns the sum-reduced L1 loss (0-dim device tensor)
-        and leaves d(loss / (b c h w)) / d params in `denoise_fn.grad_arena` for the optimizer."""
+        and leaves d(loss / (b c h w)) / d params in `denoise_fn.grad_arena` for the optimizer.  Under set_cond_drop(p > 0) -- or with
+        `cond_keep`, one flag per image, injected -- the images whose flag is 0 train on a zero conditioning image; the flags are
+        drawn after every other draw, so a seed's (t, gamma, z) are those of the step without the key."""
         x_start = x_in['HR'].contiguous()
         b, c, h, w = x_start.shape
         dev = x_start.device
@@ -911,6 +1055,18 @@ class EngineDiffusion(nn.Module):
         if noise is None:
             noise = torch.randn_like(x_start)
         cond = x_in['SR'].contiguous() if self.conditional else None
+        if cond_keep is not None or self.cond_drop > 0.0:
+            if cond is None:
+                raise ValueError('cond_keep on an unconditional model: there is no conditioning image to drop')
+            keep = (torch.rand(b, device=dev) >= self.cond_drop) if cond_keep is None else torch.as_tensor(cond_keep, device=dev).reshape(-1) != 0
+            if keep.numel() != b:
+                raise L.Sr3Error('p_losses: %d cond_keep flags for a batch of %d' % (keep.numel(), b))
+            buf = self._cond_drop_buf
+            if buf is None or buf.shape != cond.shape or buf.device != dev:
+                buf = self._cond_drop_buf = torch.empty_like(cond)
+            keep = keep.to(torch.int32).contiguous()
+            L.check(L.load().sr3_cond_drop_f32(L.ptr(cond), L.ptr(keep), b, cond[0].numel(), L.ptr(buf), self._stream(dev)))
+            cond = buf
         return un.train_step(x_start, cond, noise.contiguous(), ca.contiguous(), cb.contiguous(), level, tstep,
                              grad_scale=1.0 / float(b * c * h * w), drop_seed=drop_seed,
                              objective=self._train_objective(tstep, gamma, dev))

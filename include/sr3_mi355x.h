@@ -401,6 +401,55 @@ int sr3_consistent_step(float* x_nchw, const float* eps_nchw, const float* z_nch
                         const float* tab_c2, const float* tab_sigma, int* step2_dev, int clip_denoised, const float* tab_c3,
                         float* hist_nchw, void* stream);
 
+/* ---- guided sampling (engine extension; no reference counterpart) --------------------------------
+ * Classifier-free guidance (Ho & Salimans 2022) and dynamic thresholding (Saharia et al. 2022, section 2.3) in the tail of a reverse
+ * step, and the conditioning dropout that trains a model for guidance.  Every entry checks its arguments on the host, names the
+ * offending one in sr3_last_error and launches nothing on a refusal; SR3_E_UNSUPPORTED: batch * (values per image) >= 2^31.  No host
+ * synchronisation, no allocation: capturable; the scratch is the caller's and initialised by the call's own kernels.  Integer counters
+ * only: bitwise reproducible. */
+
+/* dst[b] = keep_dev[b] ? src[b] : +0.0 for the `batch` images of `elems_per_image` values (keep_dev: `batch` int32 on the device): a bit
+ * copy of the kept images.  dst == src is the in-place form; any alignment (elems_per_image % 4 == 0 and both pointers 16-byte aligned
+ * take the 16-byte form, the same bits).  SR3_E_BADARG: NULL pointer, non-positive size, dst overlapping src partially or keep_dev. */
+int sr3_cond_drop_f32(const float* src, const int* keep_dev, int batch, int elems_per_image, float* dst, void* stream);
+
+/* out_dev[b] = the abs-quantile of the n values of image b of src [batch, n]: with v_lo, v_hi the rank_lo-th and (rank_lo + 1)-th
+ * smallest |src[b][i]| (0-based; v_hi = v_lo when rank_lo == n - 1),
+ *   out_dev[b] = (float)((double) v_lo + frac * ((double) v_hi - (double) v_lo))        one rounding
+ * (v_lo itself where v_hi == v_lo or frac == 0: the formula's value for finite data, and no inf - inf for an infinite v_lo).  The host
+ * derives the ranks from a percentile p in float64: pos = p (n - 1), rank_lo = floor(pos), frac = pos - rank_lo.  The selection is
+ * exact -- a radix select on the bit patterns  bits & 0x7fffffff, which order like the values: ties, +-0, denormals and +-inf come out
+ * exactly; a NaN sorts above inf.  n <= 8192: one workgroup per image, one launch, the scratch is not touched; larger: five launches,
+ * 4096 values per workgroup.  Any n >= 1, any alignment of src.
+ * scratch: sr3_abs_quantile_scratch_bytes(batch, n) bytes (0 for arguments the call would refuse), 4-byte aligned, contents arbitrary.
+ * SR3_E_BADARG: NULL src / out_dev / scratch, non-positive size, rank_lo outside [0, n), frac outside [0, 1), scratch_bytes too small,
+ * out_dev or scratch overlapping src or each other; SR3_E_ALIGN: scratch not 4-byte aligned. */
+size_t sr3_abs_quantile_scratch_bytes(int batch, int n);
+int sr3_abs_quantile_f32(const float* src, int batch, int n, int rank_lo, double frac, float* out_dev, void* scratch, size_t scratch_bytes,
+                         void* stream);
+
+/* The tail of one guided reverse step, in place on x_nchw [batch, channels, height, width], with j = step2_dev[1] on entry and
+ * n = channels * height * width:
+ *   out = out_c                                            (out_u NULL)
+ *   out = out_u + scale * (out_c - out_u)                  (out_c / out_u: the network's output on the real / on a zero condition)
+ *   x0  = a[j] x - b[j] out
+ *   mode 0: x0' = x0 ;  mode 1: x0' = clamp(x0, -1, 1)     (= clip_denoised)
+ *   mode 2: s_b = max(1, abs-quantile of image b's x0 at (rank_lo, frac), as sr3_abs_quantile_f32) ; x0' = clamp(x0, -s_b, s_b) / s_b
+ *   x   = ((c1[j] x0' + c2[j] x) + c3[j] hist) + sigma[j] z ; hist <- x0'      (tab_c3 / hist_nchw both NULL: no history term)
+ * every fp32 product, sum, difference and quotient rounded separately.  step2_dev[1] = j - 1 on completion (step2_dev[0] is scratch, as
+ * in sr3_tiled_step: only the last kernel writes slot 1).  z_nchw: the step's noise or NULL (= 0); tab_*: as sr3_reverse_step.
+ * Mode 2 only: x0_scratch [batch, channels, height, width] and q_scratch of sr3_abs_quantile_scratch_bytes(batch, n) bytes.
+ * thr_out_dev [batch] or NULL: receives s_b (mode 2) or 1.0.  Modes 0 and 1: two launches; mode 2: the counter copy, x0 into
+ * x0_scratch, the select's launches on it, the mix.  width % 4 == 0 and 16-byte aligned pointers take four values per thread, anything
+ * else one, the same bits.  out_u NULL in mode 1 is sr3_p_sample_step_hist + sr3_step_decrement, bit for bit.
+ * SR3_E_BADARG: NULL required pointer, non-positive size, mode outside 0..2, scale not finite, only one of tab_c3 / hist_nchw; mode 2:
+ * rank_lo outside [0, n), frac outside [0, 1), x0_scratch / q_scratch NULL or q_scratch_bytes too small; anything the step writes
+ * (x_nchw, hist_nchw, x0_scratch, q_scratch, thr_out_dev) overlapping another argument. */
+int sr3_guided_step(float* x_nchw, const float* out_c, const float* out_u, float scale, const float* z_nchw, int batch, int channels,
+                    int height, int width, const float* tab_a, const float* tab_b, const float* tab_c1, const float* tab_c2,
+                    const float* tab_sigma, const float* tab_c3, float* hist_nchw, int* step2_dev, int mode, int rank_lo, double frac,
+                    float* x0_scratch, void* q_scratch, size_t q_scratch_bytes, float* thr_out_dev, void* stream);
+
 /* q_sample (model/sr3_modules/diffusion.py:212-219; model/ddpm_modules/diffusion.py:259-267):
  * out = ca[b] * x0 + cb[b] * z */
 int sr3_q_sample(const float* x0, const float* z, const float* ca, const float* cb, int batch,

@@ -42,7 +42,7 @@ def main():
     names = demangle([r[1] for r in rows])
     print('file              vgpr+agpr  agpr  sgpr  scratch B  scratch instr (between first / last MFMA)  static LDS B  MFMA instr  kernel')
     for r, n in zip(rows, names):
-        n = re.sub(r'\(.*', '', n).replace('void ', '').replace('sr3::', '')
+        n = re.sub(r'\(.*', '', n.replace('(anonymous namespace)::', '')).replace('void ', '').replace('sr3::', '')
         print('%-17s %9d %5d %5d %10d %14d (%d) %25d %11d  %s' % (r[0], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], n))
     print('\nvgpr+agpr = .amdhsa_next_free_vgpr (unified file: 512 per SIMD lane; <= 256 => two waves per SIMD, <= 128 => four); dynamic LDS is'
           ' set at launch\n(ensure_max_lds) and not part of the descriptor.  A kernel whose scratch instructions all lie outside the MFMA range spills only in its'

@@ -5,8 +5,11 @@ loop, the DDIM sampler at eta = 0 (no RNG node, no z read) and at eta = 0.5, and
 and one write of the image-sized history in the output conv's epilogue) -- legs interleaved --reps times, best and median per leg; then
 the wall time of whole `super_resolution` chains of --chain steps (capture excluded).  --consistency R adds a leg: dpmpp_2m with the
 block-mean projection of set_consistency(R) in its tail (three graph nodes -- forward with eps stored, counter copy, sr3_consistent_step
--- in place of the fused step), next to the dpmpp_2m leg in every round.
-    python tools/sampler_probe.py [--config sr3_16_128] [--replays 200] [--reps 3] [--chain 100] [--consistency 8]      (GPU box)"""
+-- in place of the fused step), next to the dpmpp_2m leg in every round.  --guidance SCALE --threshold MODE (either may be given more
+than once, paired in order) adds a leg per pair: dpmpp_2m under set_guidance(SCALE, MODE) -- one forward (scale 1) or two, each with its
+output stored, then sr3_guided_step in place of the fused step; --no-chains skips the whole-chain timings.
+    python tools/sampler_probe.py [--config sr3_16_128] [--replays 200] [--reps 3] [--chain 100] [--consistency 8]
+                                  [--guidance 1.5 --threshold dynamic]                                                   (GPU box)"""
 import argparse
 import json
 import os
@@ -25,6 +28,10 @@ def main():
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--chain', type=int, default=100)
     ap.add_argument('--consistency', type=int, default=0, metavar='BLOCK', help='add the dpmpp_2m leg with set_consistency(BLOCK)')
+    ap.add_argument('--guidance', type=float, action='append', default=[], metavar='SCALE', help='add a dpmpp_2m leg with set_guidance(SCALE, MODE)')
+    ap.add_argument('--threshold', action='append', default=[], metavar='MODE', help='static (default) | none | dynamic, one per --guidance')
+    ap.add_argument('--percentile', type=float, default=0.995)
+    ap.add_argument('--no-chains', action='store_true', help='time the replayed steps only')
     a = ap.parse_args()
     sys.path.insert(0, PKG)
     sys.path.insert(0, ROOT)
@@ -49,12 +56,20 @@ def main():
     if a.consistency:
         assert cond is not None, '--consistency needs a conditional config'
         legs['dpmpp_2m_consistency'] = dict(steps=N, kind='dpmpp_2m', consistency=a.consistency)
+    for i, scale in enumerate(a.guidance):
+        assert cond is not None, '--guidance needs a conditional config'
+        mode = a.threshold[i] if i < len(a.threshold) else 'static'
+        legs['dpmpp_2m_guidance%g_%s' % (scale, mode)] = dict(steps=N, kind='dpmpp_2m', guidance=(scale, mode, a.percentile))
     states = {}
     for name, spec in legs.items():                      # one captured graph per leg, all alive at once
         spec = dict(spec)
+        netG.set_guidance(None)
         netG.set_consistency(spec.pop('consistency', None))
+        gd = spec.pop('guidance', None)
         netG.set_sampler(**spec)
-        st = netG._loop_state(shape, shape if cond is not None else None, dev, consistency=netG.consistency)
+        if gd is not None:
+            netG.set_guidance(*gd)
+        st = netG._loop_state(shape, shape if cond is not None else None, dev, consistency=netG.consistency, guidance=netG.guidance)
         netG.denoise_fn.ensure_derived()
         if cond is not None:
             st['cond'].copy_(cond)
@@ -84,6 +99,10 @@ def main():
     for name in legs:
         rec['ms_per_step_' + name] = {'best': min(ms[name]), 'median': statistics.median(ms[name])}
     netG.set_consistency(None)
+    netG.set_guidance(None)
+    if a.no_chains:
+        print(json.dumps(rec))
+        return
     arg = cond if cond is not None else shape
     for kind, eta in (('ddim', 0.0), ('ddim', 0.5), ('dpmpp_2m', 0.0)):
         netG.set_sampler(a.chain, eta, kind=kind)
