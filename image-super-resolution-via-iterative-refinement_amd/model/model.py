@@ -25,6 +25,7 @@ class DDPM(BaseModel):
         super(DDPM, self).__init__(opt)
         self.netG = self.set_device(networks.define_G(opt))
         self.schedule_phase = None
+        self._distill_state = None      # {'steps', 'walk'} of a distilled student: set by train.distill, or read from a checkpoint
         self.SR = None
         self.data = None
         self.set_loss()
@@ -55,6 +56,10 @@ class DDPM(BaseModel):
                                        clip_grad_norm=opt['train']['optimizer'].get('clip_grad_norm'))
             self.log_dict = OrderedDict()
         self.load_network()
+        # progressive distillation (engine key train.distill, absent by default: nothing below runs without it)
+        self.distiller = None
+        if self.opt['phase'] == 'train' and train_opt.get('distill') is not None:
+            self._setup_distillation(train_opt['distill'])
         # data parallel: equalise the replicas once (each process initialised its own weights; a resumed checkpoint is
         # already identical) -- the counterpart of DataParallel's per-step replicate (model/networks.py:113-115)
         self._sam_wave = None
@@ -69,7 +74,7 @@ class DDPM(BaseModel):
     def optimize_parameters(self):
         self.optG.zero_grad()
         # forward + backward run inside the engine; the gradients already carry the 1/(b*c*h*w) factor
-        l_pix = self.netG(self.data)
+        l_pix = self.netG(self.data) if self.distiller is None else self.distiller.step(self.data)
         b, c, h, w = self.data['HR'].shape
         # data parallel: the engine returns the loss summed over ALL ranks, so normalise by the global element count
         # (the reference's `l_pix.sum() / int(b*c*h*w)` over DataParallel's gathered per-replica sums, :52-53)
@@ -80,6 +85,45 @@ class DDPM(BaseModel):
             self.log_dict['l_pix'] = l_pix.item()
         else:       # clip_grad_norm: the norm of the last optimizer step taken, read in the same device-to-host copy as the loss
             self.log_dict['l_pix'], self.log_dict['grad_norm'] = torch.stack([l_pix, gn]).tolist()
+
+    def _setup_distillation(self, dopt):
+        """train.distill = {"teacher": "<checkpoint prefix>", "steps": N, "walk": "logsnr", "guidance_scale": null}: build the frozen teacher
+        from <prefix>_gen.pth -- a second network of this config, on its own plan and arena -- and the Distiller that optimize_parameters
+        steps in place of p_losses (sr3_hip/distill.py).  A teacher that is itself a distilled student recorded its walk in
+        <prefix>_opt.pth (engine.distill.walk): that list is this round's teacher walk, which is how rounds chain.  Without a
+        resume_state the student starts from the teacher's weights."""
+        from sr3_hip import lib as L
+        from sr3_hip.distill import Distiller
+        if not hasattr(dopt, 'get') or dopt.get('teacher') is None or dopt.get('steps') is None:
+            raise ValueError('train.distill: "teacher" (a checkpoint prefix) and "steps" are required (got %r)' % (dopt,))
+        if self.device.type != 'cuda':
+            raise L.Sr3Error('train.distill needs the model on a GPU (set gpu_ids); there is no CPU fallback')
+        gen_path, opt_path = self._ckpt_paths(dopt['teacher'])
+        sd = torch.load(gen_path, map_location='cpu')
+        engine = (torch.load(opt_path, map_location='cpu').get('engine') or {}) if os.path.exists(opt_path) else {}
+        t_opt = dict(self.opt, phase='val')            # (no initialisation draws: the weights come from the checkpoint)
+        teacher = self.set_device(networks.define_G(t_opt))
+        sched = self.opt['model']['beta_schedule']['train']
+        teacher.set_new_noise_schedule({k: sched[k] for k in ('schedule', 'n_timestep', 'linear_start', 'linear_end')}, self.device)
+        teacher.set_prediction(engine.get('prediction', 'eps'))
+        teacher.load_state_dict(sd, strict=True)
+        teacher.eval()
+        walk = (engine.get('distill') or {}).get('walk')
+        if walk is None:
+            walk = dopt.get('walk') or 'logsnr'
+        self.distiller = Distiller(self.netG, teacher, int(dopt['steps']), walk=walk, guidance_scale=dopt.get('guidance_scale'))
+        self._distill_state = self.distiller.state()
+        if self.opt['path']['resume_state'] is None:
+            self.netG.load_state_dict(sd, strict=True)
+            if self.ema_opt is not None:
+                self.netG.denoise_fn.ema_from_weights()
+        logger.info('Distilling [{:s}] ({:d} steps) into {:d} steps'.format(gen_path, 2 * self.distiller.steps, self.distiller.steps))
+
+    def _apply_distilled_sampler(self, schedule_opt):
+        """A distilled student is sampled on its own walk (DDIM, eta 0) wherever the phase's config names no sampler."""
+        ds = self._distill_state
+        if ds is not None and (not hasattr(schedule_opt, 'get') or schedule_opt.get('sampler') is None):
+            self.netG.set_sampler(int(ds['steps']), 0.0, kind='ddim', walk=list(ds['walk']))
 
     def _sampling_weights(self):
         """Train phase with EMA enabled: validation and sampling run on the EMA weights (everything below netG's sampling loops,
@@ -119,6 +163,7 @@ class DDPM(BaseModel):
         if self.schedule_phase is None or self.schedule_phase != schedule_phase:
             self.schedule_phase = schedule_phase
             self.netG.set_new_noise_schedule(schedule_opt, self.device)
+            self._apply_distilled_sampler(schedule_opt)
 
     # ---- reporting -----------------------------------------------------------------------------
     def get_current_log(self):
@@ -169,6 +214,10 @@ class DDPM(BaseModel):
                 # what the weights predict (model.diffusion.prediction): *_gen.pth keeps the reference's format, so the training state
                 # records it; an eps model's file has the reference's keys only
                 ck['engine'] = {'prediction': self.netG.prediction}
+            if self._distill_state is not None:
+                # a distilled student: the chain it was trained for -- what it is sampled on, and the next round's teacher walk
+                ck.setdefault('engine', {})['distill'] = {'steps': int(self._distill_state['steps']),
+                                                          'walk': [int(v) for v in self._distill_state['walk']]}
             torch.save(ck, opt_path)
             logger.info('Saved model in [{:s}] ...'.format(gen_path))
         _dist.barrier()                 # nobody runs ahead (or resumes) before the files are complete
@@ -194,6 +243,12 @@ class DDPM(BaseModel):
             else:
                 logger.warning('EMA weights [{:s}] not found: the EMA starts from the loaded weights'.format(ema_path))
                 un.ema_from_weights()
+        if self.opt['phase'] != 'train' and os.path.exists(opt_path):
+            # a distilled student's training state records its chain: sampled on it unless the config names a sampler
+            ds = (torch.load(opt_path, map_location='cpu').get('engine') or {}).get('distill')
+            if ds is not None:
+                self._distill_state = {'steps': int(ds['steps']), 'walk': [int(v) for v in ds['walk']]}
+                self._apply_distilled_sampler(self.opt['model']['beta_schedule'].get(self.schedule_phase))
         if self.opt['phase'] == 'train':
             ck = torch.load(opt_path, map_location='cpu')
             saved = (ck.get('engine') or {}).get('prediction', 'eps')

@@ -16,6 +16,7 @@ captured step replayed S times over a strided walk through the schedule -- `samp
 tail's linear form, so a sampler is five other coefficient tables, another level table and (DDPM) a step-index -> timestep map.
 `"type": "dpmpp_2m"` is the second-order multistep solver DPM-Solver++(2M) on a walk uniform in log-SNR (`"walk": "logsnr"`, its
 default; DDIM takes the key too): one more table, c3, and one image-sized buffer that carries the previous step's x0 (st['hist']).
+"walk" may also be an explicit list of timesteps (strictly increasing, ending at T - 1): the chain of a distilled student (sr3_hip/distill.py).
 
 Tiling (engine extension, `"tiling": {"tile": 128 | [th, tw], "overlap": 32, "batch": 8}` next to it, or `set_tiling`): an image larger
 than the tile is sampled as one chain whose eps comes from overlapping tiles of that size -- per step: sr3_tile_gather + UNet forward
@@ -93,8 +94,34 @@ def _half_logsnr(ac):
 WALKS = ('time', 'logsnr')
 
 
+def _explicit_walk(alphas_cumprod, steps, walk):
+    """A walk given as a list or array of timesteps: checked, returned as int64 [S].  `steps` None: the list's length."""
+    try:
+        arr = np.asarray(walk)
+    except (TypeError, ValueError):
+        arr = None
+    if arr is None or arr.ndim != 1 or arr.size == 0 or arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError('sampler walk must be one of %s or a non-empty list of integer timesteps (got %r)'
+                         % (', '.join(repr(w) for w in WALKS), walk))
+    tau = arr.astype(np.int64)
+    ac, T, S = _check_walk_args(alphas_cumprod, int(tau.shape[0]) if steps is None else steps)
+    if tau.shape[0] != S:
+        raise ValueError('sampler walk has %d timesteps but steps is %d' % (tau.shape[0], S))
+    if tau.min() < 0 or tau.max() > T - 1:
+        raise ValueError('sampler walk must lie in [0, %d] (got %s)' % (T - 1, tau.tolist()))
+    if np.any(np.diff(tau) <= 0):
+        raise ValueError('sampler walk must be strictly increasing (got %s)' % (tau.tolist(),))
+    if tau[-1] != T - 1:
+        raise ValueError('sampler walk must end at T - 1 = %d (got %d)' % (T - 1, tau[-1]))
+    return tau
+
+
 def sampler_walk(alphas_cumprod, steps, walk='time'):
     """The timesteps a sampler visits: tau, int64 [S], strictly increasing, tau[0] = 0 and tau[S-1] = T - 1 (S = 1: [T - 1]).
+
+    walk = a list or array of timesteps: that walk itself, checked -- strictly increasing integers in [0, T - 1], the last one T - 1, as
+    many as `steps` (None: however many there are); a ValueError names the fault.  Its first timestep need not be 0: the walk of a
+    distilled student (sr3_hip.distill) is every second timestep of its teacher's.
 
     walk = 'time': uniform in the timestep, round(linspace(0, T - 1, S)).  walk = 'logsnr': uniform in lambda_t = 0.5 log(ac_t /
     (1 - ac_t)) -- tau[i] is the timestep whose lambda is nearest the i-th of S evenly spaced targets between lambda_0 and
@@ -102,6 +129,8 @@ def sampler_walk(alphas_cumprod, steps, walk='time'):
     is too coarse for the targets (its first timesteps, where lambda moves fastest) and one backward pass (tau[i] <= tau[i+1] - 1)
     takes back what the forward pass pushed past the top.  A multistep solver's extrapolation is only as good as the ratio of
     consecutive lambda intervals is tame; on the 'time' walk the last intervals are enormous in lambda."""
+    if not isinstance(walk, str):
+        return _explicit_walk(alphas_cumprod, steps, walk)
     ac, T, S = _check_walk_args(alphas_cumprod, steps)
     if walk not in WALKS:
         raise ValueError('sampler walk must be one of %s (got %r)' % (', '.join(repr(w) for w in WALKS), walk))
@@ -252,7 +281,10 @@ def sampler_tables(alphas_cumprod, steps, eta, *, kind='ddim', walk='time', pred
     Pure numpy, float64, no device.  The step index j counts like the device counter: j = steps - 1 is the first step taken, j = 0 the
     last.  Returns a dict: tau (`sampler_walk`), a, b, c1, c2, c3,
     sigma ([S]) and level ([S + 1]: level[j + 1] = sqrt(alphas_cumprod[tau[j]]), the reference's sqrt_alphas_cumprod_prev[t + 1] at
-    t = tau[j]; level[0] = 1)."""
+    t = tau[j]; level[0] = 1).  walk: 'time', 'logsnr' or an explicit list of timesteps (`sampler_walk`; `steps` may then be None)."""
+    if not isinstance(walk, str):
+        walk = _explicit_walk(alphas_cumprod, steps, walk)
+        steps = int(walk.shape[0])
     ac, T, S = _check_walk_args(alphas_cumprod, steps)
     try:
         eta = float(eta)
@@ -370,7 +402,7 @@ class EngineDiffusion(nn.Module):
         self.tiling = None                                                       # (this phase's own "tiling" key is read below)
         self.consistency = None                                                  # (and its "consistency" key)
         self.guidance = None                                                     # (and its "guidance" key)
-        # engine key of the schedule dict: "sampler": {"type": "ddim" | "dpmpp_2m", "steps": S, "eta": e, "walk": "time" | "logsnr"};
+        # engine key of the schedule dict: "sampler": {"type": "ddim" | "dpmpp_2m", "steps": S, "eta": e, "walk": "time" | "logsnr" | [t, ...]};
         # absent / null: the ancestral loop
         spec = schedule_opt.get('sampler') if hasattr(schedule_opt, 'get') else None
         if spec is None:
@@ -409,7 +441,8 @@ class EngineDiffusion(nn.Module):
         """Sample in `steps` reverse steps over a strided walk through the current schedule (DDIM; eta = 0: deterministic, eta = 1 and
         steps = T: the ancestral sampler's coefficients) -- or, steps None, go back to the reference's ancestral loop.  kind =
         'dpmpp_2m': the second-order multistep solver DPM-Solver++(2M) (eta must be 0); walk: 'time' (uniform in the timestep, DDIM's
-        default) or 'logsnr' (uniform in log-SNR, the multistep solver's default -- on the 'time' walk it is worse than DDIM).  What
+        default), 'logsnr' (uniform in log-SNR, the multistep solver's default -- on the 'time' walk it is worse than DDIM) or an explicit
+        list of `steps` timesteps (`sampler_walk`; kept in self.sampler['walk'] as a list of ints).  What
         p_sample_loop and everything on top of it (sample, super_resolution, the validation waves) runs; p_sample, p_mean_variance and
         p_losses keep the schedule's own timesteps."""
         if steps is None:
@@ -420,6 +453,8 @@ class EngineDiffusion(nn.Module):
             _check_sampler_kind(kind)
             if walk is None:
                 walk = 'logsnr' if kind == 'dpmpp_2m' else 'time'
+            elif not isinstance(walk, str):        # an explicit walk (a distilled student's): checked, then kept as a list of ints
+                walk = [int(v) for v in sampler_walk(self._alphas_cumprod64, steps, walk)]
             tabs = sampler_tables(self._alphas_cumprod64, steps, eta, kind=kind, walk=walk, prediction=self.prediction)
             self._check_tiled_sampler(True, getattr(self, 'tiling', None))
             self._check_consistency(getattr(self, 'consistency', None), True, None)
@@ -665,7 +700,8 @@ class EngineDiffusion(nn.Module):
         key = (tuple(shape), None if cond_shape is None else tuple(cond_shape), str(dev), self.num_timesteps,
                un.weights().data_ptr(), un.freq.data_ptr(), un.plan.generation, bool(item_streams),
                None if self.sampler is None else (self.sampler['steps'], self.sampler['eta'], self.sampler['type'],
-                                                  self.sampler.get('walk', 'time')),
+                                                  self.sampler.get('walk', 'time') if isinstance(self.sampler.get('walk', 'time'), str)
+                                                  else tuple(self.sampler['walk'])),
                None if guidance is None else (guidance['scale'], guidance['threshold'], guidance['percentile']),
                None if consistency is None else (consistency['block'], consistency['strength']),
                None if tiles is None else tiles['key'])      # tiled loop: ((tile_h, tile_w), overlap, tile_batch); the geometry is the tile's

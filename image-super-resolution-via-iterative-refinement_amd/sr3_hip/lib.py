@@ -95,6 +95,8 @@ SIGNATURES = {
     'sr3_abs_quantile_scratch_bytes': (_Z, [_I, _I]),
     'sr3_abs_quantile_f32': (_I, [_P, _I, _I, _I, C.c_double, _P, _P, _Z, _P]),
     'sr3_guided_step': (_I, [_P, _P, _P, _F, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_double, _P, _P, _Z, _P, _P]),
+    'sr3_teacher_step_f32': (_I, [_P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    'sr3_distill_target_f32': (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     'sr3_q_sample': (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     'sr3_train_workspace_bytes': (_Z, [_P, _I, _I]),
     'sr3_train_step': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, C.c_float, C.c_float, C.c_uint,

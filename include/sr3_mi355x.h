@@ -450,6 +450,35 @@ int sr3_guided_step(float* x_nchw, const float* out_c, const float* out_u, float
                     const float* tab_sigma, const float* tab_c3, float* hist_nchw, int* step2_dev, int mode, int rank_lo, double frac,
                     float* x0_scratch, void* q_scratch, size_t q_scratch_bytes, float* thr_out_dev, void* stream);
 
+/* ---- progressive distillation (engine extension; no reference counterpart) ------------------------
+ * Salimans & Ho 2022: a frozen teacher takes two deterministic DDIM steps, the student learns to land on the same point in one.  The two
+ * entries are the elementwise passes between the teacher's forwards (sr3_unet_forward) and the student's step (sr3_train_step_ex).
+ * Images are [batch, elems_per_image] fp32; every coefficient is a device array of `batch` fp32 values the host computed in float64
+ * and rounded once.  Every product, sum and difference is rounded separately; no division, no atomics: bitwise reproducible.  One
+ * launch each; elems_per_image % 4 == 0 and 16-byte aligned image pointers take four values per thread, anything else one, the same
+ * bits.  No host synchronisation, no allocation: capturable.  The arguments are checked on the host, the offending one is named in
+ * sr3_last_error and nothing is launched on a refusal.  SR3_E_BADARG: NULL required pointer, non-positive size, a non-finite scale
+ * with out_u given, an output overlapping an input or the other output; SR3_E_UNSUPPORTED: batch * elems_per_image >= 2^31. */
+
+/* One teacher step:
+ *   out    = out_c                                  (out_u NULL)
+ *   out    = out_u + scale * (out_c - out_u)        (out_c / out_u: the output on the real / on a zero condition; sr3_guided_step's)
+ *   x0     = a[b] x - b[b] out ; clamp(-1, 1) if clip_denoised
+ *   x0_out <- x0 ;  x_next <- c1[b] x0 + c2[b] x
+ * x_next == x is the in-place form (allowed; a partial overlap is not). */
+int sr3_teacher_step_f32(const float* x, const float* out_c, const float* out_u, float scale, const float* a, const float* b,
+                         const float* c1, const float* c2, int batch, int elems_per_image, int clip_denoised, float* x_next,
+                         float* x0_out, void* stream);
+
+/* The teacher's second step fused with the student's regression target (the point the teacher lands on is never written):
+ *   x0b     = clamp?(a[b] x_mid - b[b] out)         (out combined as above)
+ *   x_tgt   <- w1[b] x0_first + w2[b] x0b           (w1 + w2 = 1: a convex combination of the teacher's two x0 predictions)
+ *   eps_tgt <- s1[b] z_t - s2[b] x_tgt              (s1 = 1 / sigma_t, s2 = alpha_t / sigma_t: z_t = alpha_t x_tgt + sigma_t eps_tgt) */
+int sr3_distill_target_f32(const float* z_t, const float* x_mid, const float* out_c, const float* out_u, float scale,
+                           const float* x0_first, const float* a, const float* b, const float* w1, const float* w2, const float* s1,
+                           const float* s2, int batch, int elems_per_image, int clip_denoised, float* x_tgt, float* eps_tgt,
+                           void* stream);
+
 /* q_sample (model/sr3_modules/diffusion.py:212-219; model/ddpm_modules/diffusion.py:259-267):
  * out = ca[b] * x0 + cb[b] * z */
 int sr3_q_sample(const float* x0, const float* z, const float* ca, const float* cb, int batch,
