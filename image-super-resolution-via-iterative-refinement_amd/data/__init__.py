@@ -1,7 +1,9 @@
 '''create dataset and dataloader -- drop-in for the reference's data/__init__.py (create_dataloader, create_dataset:
 same arguments), with the per-sample float transform moved onto the MI355X: the torch DataLoader collates uint8
 batches, DeviceBatches turns each into the reference's batch dict ({'HR', 'SR', ['LR'], 'Index'}: fp32 NCHW in
-[-1, 1]) already resident on the device, which DDPM.feed_data then takes as is.'''
+[-1, 1]) already resident on the device, which DDPM.feed_data then takes as is.  Engine extensions: a dataset block with a
+"degrade" key trains from an HR-only folder -- the LR / SR images are made on the device per batch (data/degrade.py,
+data/HR_dataset.py) -- and "mode": "LR" super-resolves a folder of plain LR images.'''
 import logging
 import os
 
@@ -34,15 +36,53 @@ class DeviceBatches(object):
                 self.epoch = _dist.resume_epoch      # a resumed run continues the reshuffle sequence
             sampler.set_epoch(self.epoch)
         self.epoch += 1
+        lr_scale = getattr(self.dataset, 'lr_scale', None)
         for batch in self.loader:
             flip = batch.pop('flip', None)
+            if 'deg' in batch:
+                batch = self._degraded(batch)
+            elif lr_scale is not None:
+                batch = self._upscaled(batch, lr_scale)
             out = {}
             for k, v in batch.items():
                 if torch.is_tensor(v) and v.dtype == torch.uint8 and v.dim() == 4:
                     out[k] = Util.u8_batch_to_f32(v, flip, self.min_max, self.device)
                 else:
                     out[k] = v
+            if lr_scale is not None:
+                out['HR'] = out['SR']        # no ground truth: the conditioning image stands in (infer.py saves it as it is)
             yield out
+
+    def _on_device(self, t):
+        dev = self.device
+        if dev is None and torch.cuda.is_available():
+            dev = torch.device('cuda', torch.cuda.current_device())
+        return t if dev is None else t.to(dev, non_blocking=True)      # (no GPU: the engine call that follows says so)
+
+    def _degraded(self, batch):
+        """A batch of an HR-only folder (data/HR_dataset.py: HRCropDataset): uint8 crops plus each sample's degradation draws ->
+        the uint8 HR / SR (/ LR) batch of a prepared dataset, made on the device (data/degrade.py).  The noise: training draws from
+        the device's default generator; validation from a device generator seeded seed + index, the same on every pass."""
+        from data.degrade import degrade_batch
+        cfg, hr = self.dataset.degrade, self._on_device(batch['HR'])
+        gen = None
+        if self.dataset.split != 'train':
+            if hr.shape[0] != 1:
+                raise ValueError('validation batches of an HR-only folder hold one image (the per-index noise stream)')
+            gen = torch.Generator(device=hr.device).manual_seed(cfg['seed'] + int(batch['Index'][0]))
+        lr, sr = degrade_batch(hr, batch['deg'], cfg, generator=gen)
+        out = {'HR': hr, 'SR': sr, 'Index': batch['Index']}
+        if self.dataset.need_LR:
+            out['LR'] = lr
+        return out
+
+    def _upscaled(self, batch, scale):
+        """"mode": "LR" (data/HR_dataset.py: LRFolderDataset): the conditioning image is the LR image resized by `scale`."""
+        from data.prepare_data import resize_batch
+        from data.degrade import _RESAMPLE
+        lr = self._on_device(batch['LR'])
+        sr = resize_batch(lr, (lr.shape[1] * scale, lr.shape[2] * scale), _RESAMPLE[self.dataset.resample])
+        return {'SR': sr, 'LR': lr, 'Index': batch['Index']}
 
     def __iter__(self):
         _, world = _dp()
@@ -67,6 +107,10 @@ class DeviceBatches(object):
                 b['_dp_wave'], b['_dp_pos'] = wave, pos
                 yield b
         for b in self._device_batches():
+            if group and b['SR'].shape != group[0]['SR'].shape:      # a wave holds items of one size ("mode": "LR" folders mix them)
+                yield from flush()
+                first += len(group)
+                group = []
             group.append(b)
             if len(group) == world * chain:
                 yield from flush()
@@ -116,9 +160,16 @@ def create_dataloader(dataset, dataset_opt, phase, device=None):
 def create_dataset(dataset_opt, phase):
     '''create dataset'''
     mode = dataset_opt['mode']
-    from data.LRHR_dataset import LRHRDataset as D
-    dataset = D(dataroot=dataset_opt['dataroot'], datatype=dataset_opt['datatype'], l_resolution=dataset_opt['l_resolution'],
-                r_resolution=dataset_opt['r_resolution'], split=phase, data_len=dataset_opt['data_len'],
-                need_LR=(mode == 'LRHR'))
+    args = dict(dataroot=dataset_opt['dataroot'], datatype=dataset_opt['datatype'], l_resolution=dataset_opt['l_resolution'],
+                r_resolution=dataset_opt['r_resolution'], split=phase, data_len=dataset_opt['data_len'])
+    if mode == 'LR':                         # a folder of plain LR images to super-resolve
+        from data.HR_dataset import LRFolderDataset
+        dataset = LRFolderDataset(resample=dataset_opt.get('resample', 'bicubic'), **args)
+    elif 'degrade' in dataset_opt:           # an HR-only folder: crops, degraded on the device
+        from data.HR_dataset import HRCropDataset
+        dataset = HRCropDataset(need_LR=(mode == 'LRHR'), degrade=dataset_opt['degrade'], **args)
+    else:
+        from data.LRHR_dataset import LRHRDataset as D
+        dataset = D(need_LR=(mode == 'LRHR'), **args)
     logging.getLogger('base').info('Dataset [{:s} - {:s}] is created.'.format(dataset.__class__.__name__, dataset_opt['name']))
     return dataset

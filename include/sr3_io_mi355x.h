@@ -75,6 +75,31 @@ size_t sr3_resize_scratch_bytes(int n_images, int H, int W, int C, int OH, int O
 int sr3_resize_u8(const uint8_t* in_hwc, int n_images, int H, int W, int C, int OH, int OW, int resample, void* scratch,
                   size_t scratch_bytes, uint8_t* out_hwc, void* stream);
 
+/* The degradation between an HR crop and its conditioning images (data/degrade.py of the package: blur -> resize down ->
+ * noise -> resize up), for training from an HR-only folder.  Both entries check their arguments before anything is launched
+ * (SR3_E_BADARG, sr3_last_error names the argument), take the caller's stream, and use no atomics.
+ *
+ * sr3_blur_u8: per-image 2-D correlation of n_images uint8 (H, W, C) images.  weights is (n_images, k, k) int32 on the device,
+ * 16-bit fixed point: image i is filtered with ITS k x k kernel, whose entries the caller makes sum to 65536 (each |w| < 2^23).
+ * Border: reflect-101 (np.pad mode 'reflect').  For every pixel and channel
+ *     acc = sum_{dy, dx} w[i][dy][dx] * in[reflect(y + dy - k/2)][reflect(x + dx - k/2)]            (int32)
+ *     out = clamp((acc + 32768) >> 16, 0, 255)                                                      (arithmetic shift)
+ * Integer arithmetic: the result does not depend on the order of the sum.  An image whose kernel is the delta (centre tap 65536,
+ * every other 0) is copied, which is the same bytes.
+ * SR3_E_BADARG: NULL in_hwc / weights / out_hwc; n_images outside 1..65535; H or W not positive; C not 1 or 3; k even, < 1 or
+ * > 21; k / 2 >= min(H, W) (the reflection would leave the image); out_hwc overlapping in_hwc (in == out included). */
+int sr3_blur_u8(const uint8_t* in_hwc, int n_images, int H, int W, int C, const int32_t* weights, int k, uint8_t* out_hwc,
+                void* stream);
+
+/* sr3_noise_u8: additive Gaussian noise on n_images uint8 images of elems_per_image bytes each.  sigma is (n_images) fp32 in
+ * 8-bit levels, z has the shape of `in`, fp32 (the caller's standard normal draws):
+ *     t = sigma[i] * z;  v = (float)in + t      (each rounded on its own: no fma)
+ *     out = clamp(rintf(v), 0, 255)             (round half to even)
+ * sigma[i] == 0 copies image i whatever z holds.  out == in runs in place.
+ * SR3_E_BADARG: NULL in / sigma / z / out; n_images outside 1..65535; elems_per_image 0; out overlapping in without being it. */
+int sr3_noise_u8(const uint8_t* in, int n_images, size_t elems_per_image, const float* sigma, const float* z, uint8_t* out,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,106 @@
+#!/usr/bin/env python3
+"""What the on-device degradation of an HR-only training batch costs: data.degrade.degrade_batch at batch 64,
+128 x 128 -> 16 x 16 -> 128 x 128, 21 x 21 anisotropic blur and noise on for every sample -- timed with HIP events around the whole
+call (weights made on the host, uploaded, four kernels' worth of work), --warmup calls, then --rounds timed ones; median and
+p10-p90.  The blur kernel alone is timed the same way.  Next to it the same chain restated with NumPy + Pillow (the 441-tap
+shifted accumulate of tests/test_degrade_cpu.py, Image.resize, fp32 noise) over --threads CPU threads, wall clock.
+    python tools/degrade_probe.py [--batch 64] [--rounds 30] [--warmup 5] [--threads 16] [--step-ms 123.8]      (GPU box)"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, 'image-super-resolution-via-iterative-refinement_amd')
+
+
+def spread(ms):
+    s = sorted(ms)
+    return {'median_ms': round(statistics.median(s), 4), 'p10_ms': round(s[len(s) // 10], 4), 'p90_ms': round(s[(len(s) * 9) // 10], 4),
+            'n': len(s)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=64)
+    ap.add_argument('--rounds', type=int, default=30)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--threads', type=int, default=16)
+    ap.add_argument('--cpu-rounds', type=int, default=5)
+    ap.add_argument('--step-ms', type=float, default=123.8, help='the training step the cost is compared with (BASELINE config, batch 64)')
+    a = ap.parse_args()
+    sys.path.insert(0, PKG)
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    from PIL import Image
+    import data.degrade as D
+    assert torch.cuda.is_available(), 'degrade_probe needs a GPU'
+    assert a.rounds >= 20, 'at least 20 timed repetitions'
+    R, Lr, k, n = 128, 16, 21, a.batch
+    cfg = D.degrade_config({'blur': {'kernel': k, 'sigma': [0.2, 3.0], 'anisotropic': True}, 'noise': {'sigma': [1, 25]}}, Lr)
+    torch.manual_seed(0)
+    rng = np.random.RandomState(0)
+    hr = rng.randint(0, 256, size=(n, R, R, 3)).astype(np.uint8)
+    deg = torch.stack([D.draw_deg(cfg) for _ in range(n)])
+    assert bool((deg[:, 0] == 1).all()) and bool((deg[:, 4] > 0).all())
+    z = torch.randn(n, Lr, Lr, 3, generator=torch.Generator().manual_seed(1))
+    dev = torch.device('cuda', 0)
+    hr_d, z_d = torch.from_numpy(hr).to(dev), z.to(dev)
+    w_d = torch.from_numpy(np.stack([D.blur_weights(r[1], r[2], r[3], k) for r in deg.double().numpy()])).to(dev)
+
+    def timed(call):
+        ms = []
+        for rnd in range(a.warmup + a.rounds):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            call()
+            e1.record()
+            e1.synchronize()
+            if rnd >= a.warmup:
+                ms.append(e0.elapsed_time(e1))
+        return spread(ms)
+
+    gpu = timed(lambda: D.degrade_batch(hr_d, deg, cfg, z=z_d))
+    blur = timed(lambda: D.blur_batch(hr_d, w_d))
+    lr_d, sr_d = D.degrade_batch(hr_d, deg, cfg, z=z_d)
+
+    # the same chain on the CPU: NumPy blur (int64 shifted accumulate) -> Pillow -> NumPy fp32 noise -> Pillow, one image per task
+    d64, zn = deg.double().numpy(), z.numpy()
+
+    def one(i):
+        w = D.blur_weights(d64[i][1], d64[i][2], d64[i][3], k)
+        r = k // 2
+        p = np.pad(hr[i].astype(np.int64), ((r, r), (r, r), (0, 0)), mode='reflect')
+        acc = np.zeros(hr[i].shape, dtype=np.int64)
+        for dy in range(k):
+            for dx in range(k):
+                acc += int(w[dy, dx]) * p[dy:dy + R, dx:dx + R]
+        x = np.clip((acc + 32768) >> 16, 0, 255).astype(np.uint8)
+        lr = np.asarray(Image.fromarray(x).resize((Lr, Lr), Image.BICUBIC))
+        v = lr.astype(np.float32) + np.float32(d64[i][4]) * zn[i]
+        lr = np.clip(np.rint(v), 0, 255).astype(np.uint8)
+        return lr, np.asarray(Image.fromarray(lr).resize((R, R), Image.BICUBIC))
+
+    cpu_ms = []
+    with ThreadPoolExecutor(a.threads) as pool:
+        for rnd in range(1 + a.cpu_rounds):
+            t0 = time.perf_counter()
+            ref = list(pool.map(one, range(n)))
+            if rnd:
+                cpu_ms.append((time.perf_counter() - t0) * 1e3)
+    same = all(np.array_equal(lr_d[i].cpu().numpy(), ref[i][0]) and np.array_equal(sr_d[i].cpu().numpy(), ref[i][1]) for i in range(n))
+    cpu = spread(cpu_ms)
+    out = {'probe': 'degrade_batch', 'device': torch.cuda.get_device_name(0), 'batch': n, 'r_resolution': R, 'l_resolution': Lr, 'kernel': k,
+           'gpu_degrade_batch': gpu, 'gpu_blur_only': blur, 'cpu_numpy_pillow': dict(cpu, threads=a.threads),
+           'device_equals_cpu_chain': bool(same), 'step_ms': a.step_ms,
+           'gpu_share_of_step': round(gpu['median_ms'] / a.step_ms, 5), 'cpu_share_of_step': round(cpu['median_ms'] / a.step_ms, 3)}
+    print(json.dumps(out))
+    assert same, 'the device chain and the NumPy + Pillow chain differ'
+
+
+if __name__ == '__main__':
+    main()
