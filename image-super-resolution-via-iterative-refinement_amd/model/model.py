@@ -133,6 +133,20 @@ class DDPM(BaseModel):
             return un.use_weights('ema')
         return contextlib.nullcontext()
 
+    def _backprojection_target(self):
+        """Under the "backprojection" key: the batch's real LR image (data['LR'], [B, C, H / scale, W / scale]) as the chain's target;
+        None -- the down-sampled conditioning image -- when the key is off or the batch carries no LR image of that shape."""
+        bp = getattr(self.netG, 'backprojection', None)
+        lr = self.data.get('LR') if isinstance(self.data, dict) else None
+        sr = self.data.get('SR') if isinstance(self.data, dict) else None
+        if bp is None or not torch.is_tensor(lr) or not torch.is_tensor(sr) or lr.dim() != 4 or sr.dim() != 4:
+            return None
+        s = bp['scale']
+        B, _, H, W = sr.shape
+        if H % s or W % s or tuple(lr.shape) != (B, self.netG.channels, H // s, W // s):
+            return None
+        return lr
+
     def test(self, continous=False):
         self.netG.eval()
         with torch.no_grad(), self._sampling_weights():
@@ -142,7 +156,11 @@ class DDPM(BaseModel):
                 # a rank's items as one batch (and, data parallel, dealt over the ranks); every caller gets its item's image back
                 self.SR = wave.result(self.netG, self.data['_dp_pos'], continous)
             else:
-                self.SR = self.netG.super_resolution(self.data['SR'], continous)
+                lr = self._backprojection_target()
+                if lr is None:
+                    self.SR = self.netG.super_resolution(self.data['SR'], continous)
+                else:
+                    self.SR = self.netG.super_resolution(self.data['SR'], continous, backprojection_target=lr)
         self.netG.train()
 
     def sample(self, batch_size=1, continous=False):

@@ -37,6 +37,12 @@ Guidance (engine extension, `"guidance": {"scale": 1.5, "threshold": "dynamic", 
 on the conditioning image and on a zero one, combined as out_u + scale (out_c - out_u) before x0 is formed -- and what is done to x0
 where it leaves [-1, 1]: the static clamp, nothing, or dynamic thresholding (each image's x0 divided by its own percentile of |x0|).
 Per step: the forward(s) with the output stored, then sr3_guided_step in place of the fused tail.
+
+Back-projection (engine extension, `"backprojection": {"scale": 8, "iterations": 2, "strength": 1.0, "resample": "bicubic"}` next to
+"sampler", or `set_backprojection`): every step runs `iterations` rounds of x0 <- x0 + strength * U(y - D(x0)) on the predicted x0 before
+the posterior mix, D / U = Pillow's antialiased resize down / up by `scale` (the resize the datasets are made with; `resample_tables`
+makes its tables on the host), y = the LR image (`backprojection_target=`) or the down-sampled conditioning image.  Per step: UNet
+forward with eps stored, then sr3_backproject_step in place of the fused tail.  A contraction, not a projection.
 """
 import ctypes as C
 
@@ -197,6 +203,92 @@ def block_means(x, block):
     return out
 
 
+RESAMPLES = ('bicubic', 'bilinear')      # the filters of resample_tables: Pillow's BICUBIC (a = -0.5, support 2) and BILINEAR (support 1)
+BACKPROJECTION_KEYS = ('scale', 'iterations', 'strength', 'resample')
+
+
+def _resample_filter(resample):
+    if resample == 'bicubic':
+        def f(x):
+            x = np.abs(x)
+            a = -0.5
+            return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0,
+                            np.where(x < 2.0, (((x - 5.0) * x + 8.0) * x - 4.0) * a, 0.0))
+        return f, 2.0
+    if resample == 'bilinear':
+        return (lambda x: np.where(np.abs(x) < 1.0, 1.0 - np.abs(x), 0.0)), 1.0
+    raise ValueError('resample must be one of %s (got %r)' % (', '.join(repr(k) for k in RESAMPLES), resample))
+
+
+def resample_tables(in_size, out_size, resample='bicubic'):
+    """The banded matrix of Pillow's resize of one axis from in_size to out_size elements (Image.resize with BICUBIC / BILINEAR; its
+    precompute_coeffs rule, evaluated in float64): the filter's support scaled by max(in / out, 1) (the antialiasing of a down-sample),
+    output xx centred at (xx + 0.5) in / out, taps xmin = max(int(c - support + 0.5), 0) up to xmax = min(int(c + support + 0.5), in),
+    weights normalised by their sum.  -> (bounds int32 [out, 2] = (first tap, count), weights fp32 [out, ksize], rounded once from
+    float64 and zero past the count): what sr3_resample_f32 / sr3_backproject_step take.  Pure NumPy, no device."""
+    for name, v in (('in_size', in_size), ('out_size', out_size)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+            raise ValueError('resample_tables: %s must be a positive integer (got %r)' % (name, v))
+    filt, support = _resample_filter(resample)
+    in_size, out_size = int(in_size), int(out_size)
+    scale = np.float64(in_size) / np.float64(out_size)
+    fscale = max(scale, np.float64(1.0))
+    support = np.float64(support) * fscale
+    ksize = int(np.ceil(support)) * 2 + 1
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    w64 = np.zeros((out_size, ksize), dtype=np.float64)
+    for xx in range(out_size):
+        c = (np.float64(xx) + 0.5) * scale
+        xmin = max(int(c - support + 0.5), 0)
+        xmax = min(int(c + support + 0.5), in_size)
+        n = xmax - xmin
+        w = filt((np.arange(n, dtype=np.float64) + xmin - c + 0.5) / fscale)
+        s = w.sum()
+        if s != 0.0:
+            w = w / s
+        bounds[xx] = (xmin, n)
+        w64[xx, :n] = w
+    return bounds, w64.astype(np.float32)      # (ksize = Pillow's: 2 ceil(support) + 1, an upper bound of every row's count)
+
+
+def _resample_device_tables(in_hw, out_hw, resample, dev):
+    """the four tables of one 2-D resample on the device: (bounds_h, weights_h, bounds_v, weights_v); horizontal = the width axis"""
+    out = []
+    for i, o in ((in_hw[1], out_hw[1]), (in_hw[0], out_hw[0])):
+        b, w = resample_tables(i, o, resample)
+        out += [torch.from_numpy(b).to(dev), torch.from_numpy(w).to(dev)]
+    return tuple(out)
+
+
+def resample_f32(x, out_hw, resample='bicubic', tables=None):
+    """Pillow's resize of the planes of x [B, C, H, W] (a contiguous fp32 GPU tensor) to out_hw = (OH, OW), in fp32 on the device
+    (sr3_resample_f32; the tables of `resample_tables`, or `tables` = the four device tensors made for this geometry before)."""
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
+        raise L.Sr3Error('resample_f32 needs a (B, C, H, W) fp32 GPU tensor; there is no CPU fallback')
+    x = x.contiguous()
+    B, Cc, H, W = x.shape
+    OH, OW = int(out_hw[0]), int(out_hw[1])
+    bh, wh, bv, wv = tables if tables is not None else _resample_device_tables((H, W), (OH, OW), resample, x.device)
+    out = torch.empty((B, Cc, OH, OW), device=x.device)
+    tmp = torch.empty((B, Cc, H, OW), device=x.device)
+    L.check(L.load().sr3_resample_f32(L.ptr(x), B * Cc, H, W, L.ptr(out), OH, OW, L.ptr(bh), L.ptr(wh), wh.shape[1], L.ptr(bv), L.ptr(wv),
+                                      wv.shape[1], L.ptr(tmp), None, None, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+    return out
+
+
+def backprojection_error(sr, y_lr, scale, resample='bicubic'):
+    """max |D(sr) - y_lr|: how far the result sr [B, C, H, W] is from the LR image y_lr [B, C, H / scale, W / scale] under the dataset's
+    down-sample D (Pillow's resize, sr3_resample_f32).  fp32 GPU tensors."""
+    if not torch.is_tensor(sr) or sr.dim() != 4:
+        raise L.Sr3Error('backprojection_error needs a (B, C, H, W) fp32 GPU tensor; there is no CPU fallback')
+    scale = int(scale)
+    B, Cc, H, W = sr.shape
+    if scale < 1 or H % scale or W % scale or tuple(y_lr.shape) != (B, Cc, H // scale, W // scale):
+        raise L.Sr3Error('backprojection_error: y_lr must be a %s tensor (got %s)' % ((B, Cc, H // max(scale, 1), W // max(scale, 1)), tuple(y_lr.shape)))
+    d = resample_f32(sr, (H // scale, W // scale), resample)
+    return float((d - y_lr.to(d.device, torch.float32)).abs().max())
+
+
 THRESHOLDS = ('none', 'static', 'dynamic')      # the mode numbers of sr3_guided_step, in order
 
 
@@ -354,6 +446,7 @@ class EngineDiffusion(nn.Module):
         self.tiling = None             # None: whole-image steps; else {'tile': (th, tw), 'overlap': o, 'batch': n | None} (set_tiling)
         self.consistency = None        # None: the network's x0 as it is; else {'block': r, 'strength': s} (set_consistency)
         self.guidance = None           # None: one forward, the fused tail; else {'scale': w, 'threshold': mode, 'percentile': p} (set_guidance)
+        self.backprojection = None     # None: the network's x0 as it is; else {'scale': s, 'iterations': K, 'strength': l, 'resample': f} (set_backprojection)
         self.cond_drop = 0.0           # training: the probability that an image's conditioning is replaced by zeros (set_cond_drop)
         self._cond_drop_buf = None     # ... and the buffer the dropped conditioning is written to
         self.max_cached_loops = 3      # reverse-loop states (buffers + workspace + captured graph) kept, one per (shape, launch list)
@@ -402,6 +495,7 @@ class EngineDiffusion(nn.Module):
         self.tiling = None                                                       # (this phase's own "tiling" key is read below)
         self.consistency = None                                                  # (and its "consistency" key)
         self.guidance = None                                                     # (and its "guidance" key)
+        self.backprojection = None                                               # (and its "backprojection" key)
         # engine key of the schedule dict: "sampler": {"type": "ddim" | "dpmpp_2m", "steps": S, "eta": e, "walk": "time" | "logsnr" | [t, ...]};
         # absent / null: the ancestral loop
         spec = schedule_opt.get('sampler') if hasattr(schedule_opt, 'get') else None
@@ -436,6 +530,19 @@ class EngineDiffusion(nn.Module):
             if not hasattr(spec, 'get'):
                 raise ValueError('guidance: a dict of "scale", "threshold", "percentile" is expected (got %r)' % (spec,))
             self.set_guidance(spec.get('scale', 1.0), spec.get('threshold', 'static'), spec.get('percentile', 0.995))
+        # and: "backprojection": {"scale": 8, "iterations": 2, "strength": 1.0, "resample": "bicubic"}; absent / null: off
+        spec = schedule_opt.get('backprojection') if hasattr(schedule_opt, 'get') else None
+        if spec is None:
+            self.set_backprojection(None)
+        else:
+            if not hasattr(spec, 'get') or not hasattr(spec, 'keys'):
+                raise ValueError('backprojection: a dict of "scale", "iterations", "strength", "resample" is expected (got %r)' % (spec,))
+            for k in spec.keys():
+                if k not in BACKPROJECTION_KEYS:
+                    raise ValueError('backprojection: unknown key %r (known: %s)' % (k, ', '.join('"%s"' % n for n in BACKPROJECTION_KEYS)))
+            if spec.get('scale') is None:
+                raise ValueError('backprojection: "scale" is required (got %r)' % (spec,))
+            self.set_backprojection(spec['scale'], spec.get('iterations', 1), spec.get('strength', 1.0), spec.get('resample', 'bicubic'))
 
     def set_sampler(self, steps=None, eta=0.0, *, kind='ddim', walk=None):
         """Sample in `steps` reverse steps over a strided walk through the current schedule (DDIM; eta = 0: deterministic, eta = 1 and
@@ -459,6 +566,7 @@ class EngineDiffusion(nn.Module):
             self._check_tiled_sampler(True, getattr(self, 'tiling', None))
             self._check_consistency(getattr(self, 'consistency', None), True, None)
             self._check_guidance(getattr(self, 'guidance', None), True, None, None)
+            self._check_backprojection(getattr(self, 'backprojection', None), True, None, None, None)
             self.sampler = dict(type=kind, steps=int(steps), eta=float(eta))
             if kind != 'ddim' or walk != 'time':
                 self.sampler['walk'] = walk
@@ -511,6 +619,7 @@ class EngineDiffusion(nn.Module):
             self._check_tiled_sampler(self.sampler is not None, t)
             self._check_consistency(self.consistency, False, t)
             self._check_guidance(self.guidance, False, t, None)
+            self._check_backprojection(self.backprojection, False, t, None, None)
             self.tiling = t
         self._loop_cache = {}
 
@@ -534,6 +643,7 @@ class EngineDiffusion(nn.Module):
             c = dict(block=int(block), strength=lam)
             self._check_consistency(c, self.sampler is not None, self.tiling)
             self._check_guidance(self.guidance, False, None, c)
+            self._check_backprojection(self.backprojection, False, None, c, None)
             self.consistency = c
         self._loop_cache = {}
 
@@ -569,7 +679,36 @@ class EngineDiffusion(nn.Module):
                 raise ValueError('guidance on an unconditional model: there is no conditioning image to drop')
             gd = dict(scale=float(scale), threshold=threshold, percentile=percentile)
             self._check_guidance(gd, self.sampler is not None, self.tiling, self.consistency)
+            self._check_backprojection(self.backprojection, False, None, None, gd)
             self.guidance = gd
+        self._loop_cache = {}
+
+    def set_backprojection(self, scale=None, iterations=1, strength=1.0, resample='bicubic'):
+        """Sample images that agree with a low-resolution target under the resize the datasets are made with: every reverse step runs
+        `iterations` rounds of x0 <- x0 + strength * U(y - D(x0)) on the predicted x0 before the posterior mix (iterative
+        back-projection; sr3_backproject_step), D = Pillow's antialiased `resample` ('bicubic' | 'bilinear') down-sample by `scale`
+        (an int >= 2 dividing the image's height and width), U the same resize back up -- or, scale None, go back to the network's x0
+        as it is.  iterations in 1..16, strength in (0, 2).  The target y is `backprojection_target=` of p_sample_loop /
+        super_resolution (the dataset's real LR image), or D of the conditioning image's first `channels` channels.  A contraction,
+        not a projection: the LR residual shrinks with every round and does not vanish."""
+        if scale is None:
+            self.backprojection = None
+        else:
+            if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or int(scale) < 2:
+                raise ValueError('backprojection scale must be an integer >= 2 (got %r)' % (scale,))
+            if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 1 <= int(iterations) <= 16:
+                raise ValueError('backprojection iterations must be an integer in 1..16 (got %r)' % (iterations,))
+            try:
+                lam = float(strength)
+            except (TypeError, ValueError):
+                raise ValueError('backprojection strength must be a number (got %r)' % (strength,))
+            if isinstance(strength, bool) or not (0.0 < lam < 2.0):
+                raise ValueError('backprojection strength must lie in (0, 2) (got %r)' % (strength,))
+            if not isinstance(resample, str) or resample not in RESAMPLES:
+                raise ValueError('backprojection resample must be one of %s (got %r)' % (', '.join(repr(k) for k in RESAMPLES), resample))
+            bp = dict(scale=int(scale), iterations=int(iterations), strength=lam, resample=resample)
+            self._check_backprojection(bp, self.sampler is not None, self.tiling, self.consistency, self.guidance)
+            self.backprojection = bp
         self._loop_cache = {}
 
     def set_cond_drop(self, p=0.0):
@@ -609,6 +748,23 @@ class EngineDiffusion(nn.Module):
             raise NotImplementedError('consistency of the DDPM variant under a sampler (DDIM, DPM-Solver++): the forward of a consistent step '
                                       'runs through sr3_unet_forward, which has no step-index -> timestep map (t_map); use the ancestral '
                                       'sampler (set_sampler(None)) or switch consistency off (set_consistency(None))')
+
+    def _check_backprojection(self, backprojection, sampler, tiling, consistency, guidance):
+        if backprojection is None:
+            return
+        if tiling is not None:
+            raise NotImplementedError('back-projection with tiling: sr3_tiled_step owns the tail of a tiled step and has no back-projection in '
+                                      'it; use whole-image steps (set_tiling(None)) or switch back-projection off (set_backprojection(None))')
+        if consistency is not None:
+            raise NotImplementedError('back-projection with consistency: sr3_backproject_step and sr3_consistent_step each own the whole tail '
+                                      'of a step; switch one of them off (set_backprojection(None) / set_consistency(None))')
+        if guidance is not None:
+            raise NotImplementedError('back-projection with guidance: sr3_backproject_step and sr3_guided_step each own the whole tail of a '
+                                      'step; switch one of them off (set_backprojection(None) / set_guidance(None))')
+        if sampler and self.variant == 'ddpm':
+            raise NotImplementedError('back-projection of the DDPM variant under a sampler (DDIM, DPM-Solver++): the forward of a back-projected '
+                                      'step runs through sr3_unet_forward, which has no step-index -> timestep map (t_map); use the ancestral '
+                                      'sampler (set_sampler(None)) or switch back-projection off (set_backprojection(None))')
 
     def _check_tiled_sampler(self, sampler, tiling):
         if sampler and tiling is not None and self.variant == 'ddpm':
@@ -691,7 +847,7 @@ class EngineDiffusion(nn.Module):
         return out
 
     # ---- the reverse loop ------------------------------------------------------------------------
-    def _loop_state(self, shape, cond_shape, dev, item_streams=False, tiles=None, consistency=None, guidance=None):
+    def _loop_state(self, shape, cond_shape, dev, item_streams=False, tiles=None, consistency=None, guidance=None, backprojection=None):
         # a captured graph bakes in the arena (the one in use: EngineUNet.use_weights), the freq table and the workspace pointer and
         # the plan's launch list: key on all of them (plan.generation changes with every set_option); the workspace is private to the state.
         # item_streams: one torch generator per image of the batch (`item_seeds` of p_sample_loop) -- the generators are
@@ -702,6 +858,7 @@ class EngineDiffusion(nn.Module):
                None if self.sampler is None else (self.sampler['steps'], self.sampler['eta'], self.sampler['type'],
                                                   self.sampler.get('walk', 'time') if isinstance(self.sampler.get('walk', 'time'), str)
                                                   else tuple(self.sampler['walk'])),
+               None if backprojection is None else tuple(backprojection[k] for k in BACKPROJECTION_KEYS),
                None if guidance is None else (guidance['scale'], guidance['threshold'], guidance['percentile']),
                None if consistency is None else (consistency['block'], consistency['strength']),
                None if tiles is None else tiles['key'])      # tiled loop: ((tile_h, tile_w), overlap, tile_batch); the geometry is the tile's
@@ -722,6 +879,8 @@ class EngineDiffusion(nn.Module):
                 st['consistency'] = dict(consistency)
             if guidance is not None:
                 self._guidance_buffers(st, guidance, shape, cond_shape, dev)
+            if backprojection is not None:
+                self._backprojection_buffers(st, backprojection, shape, dev)
             # keep the states of a few image sizes alive (a folder of mixed sizes alternates between them without recapturing);
             # what was built for another arena / schedule / set of plan options can never be hit again: dropped
             # (with EMA weights the model has two arenas, and a state built on either can be hit again)
@@ -751,6 +910,17 @@ class EngineDiffusion(nn.Module):
             st['rank_lo'], st['frac'] = quantile_rank(n, guidance['percentile'])
             st['x0'] = torch.empty(shape, device=dev)
             st['qscratch'] = torch.empty(int(L.load().sr3_abs_quantile_scratch_bytes(shape[0], n)), dtype=torch.uint8, device=dev)
+
+    def _backprojection_buffers(self, st, bp, shape, dev):
+        """What a back-projected loop's state holds besides the plain loop's: the setting it (and its captured graph) was built for, the
+        LR target, the four tables of the down-sample and of the up-sample (`resample_tables`) and the step's scratch."""
+        B, Cc, H, W = shape
+        s = bp['scale']
+        st['backprojection'] = dict(bp)
+        st['y_lr'] = torch.zeros((B, Cc, H // s, W // s), device=dev)
+        st['bp_down'] = _resample_device_tables((H, W), (H // s, W // s), bp['resample'], dev)
+        st['bp_up'] = _resample_device_tables((H // s, W // s), (H, W), bp['resample'], dev)
+        st['bp_scratch'] = torch.empty(int(L.load().sr3_backproject_scratch_bytes(B, Cc, H, W, s)), dtype=torch.uint8, device=dev)
 
     def _tile_buffers(self, st, tiles, shape, cond_shape, dev):
         """What a tiled loop's state holds besides the whole-image tensors: the grid's origins and windows on the device, the chunk
@@ -848,6 +1018,21 @@ class EngineDiffusion(nn.Module):
                                              THRESHOLDS.index(gd['threshold']), st['rank_lo'], st['frac'], L.ptr(st['x0']), L.ptr(qs),
                                              0 if qs is None else qs.numel(), L.ptr(st['thr']), self._stream(img.device)))
             return
+        bp = st.get('backprojection')
+        if bp is not None:
+            # back-projected step: the forward stores eps (level / timestep from the device counter), then the tail with the
+            # back-projection rounds on x0 in it (sr3_backproject_step: counter copy + 1 + 3 K kernels)
+            assert t_map is None and g is None      # (_check_backprojection refused both)
+            self.denoise_fn(img, None, cond=st['cond'], level_table=level, step_dev=st['step'][1:], out=st['eps'], ws=st['ws'])
+            B, Cc, H, W = img.shape
+            axes = []
+            for tb in (st['bp_down'], st['bp_up']):
+                axes += [L.ptr(tb[0]), L.ptr(tb[1]), tb[1].shape[1], L.ptr(tb[2]), L.ptr(tb[3]), tb[3].shape[1]]
+            L.check(L.load().sr3_backproject_step(L.ptr(img), L.ptr(st['eps']), L.ptr(z), L.ptr(st['y_lr']), B, Cc, H, W, bp['scale'],
+                                                  bp['iterations'], bp['strength'], *axes, *[L.ptr(t) for t in tables], L.ptr(st['step']),
+                                                  1, L.ptr(c3), L.ptr(hist), L.ptr(st['bp_scratch']), st['bp_scratch'].numel(),
+                                                  self._stream(img.device)))
+            return
         if g is None:
             self.denoise_fn.reverse_step(img, z, tables, st['step'], cond=st['cond'], level_table=level, clip_denoised=True,
                                          eps_out=st['eps'], ws=st['ws'], t_map=t_map, c3=c3, hist=hist)
@@ -874,7 +1059,16 @@ class EngineDiffusion(nn.Module):
         keep_img = st['img'].clone()
         keep_step = st['step'].clone()
         keep_hist = st['hist'].clone() if st.get('hist') is not None else None
-        side = torch.cuda.Stream(dev)
+        g = torch.cuda.CUDAGraph()
+        cap = None
+        if st.get('backprojection') is not None:
+            # a back-projected state warms up on the stream its capture runs on (torch's shared capture stream): it takes no stream
+            # of its own out of the pool, so which pool stream -- and with it which hardware queue -- anything created later in
+            # the process gets does not depend on how many such states were captured before
+            cap = torch.cuda.graph(g)
+            side = cap.capture_stream
+        else:
+            side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             self._one_step(st)
@@ -887,26 +1081,29 @@ class EngineDiffusion(nn.Module):
         torch.cuda.set_rng_state(rng, dev)
         for gen, gs in zip(gens, gstate):
             gen.set_state(gs)
-        g = torch.cuda.CUDAGraph()
         for gen in gens:                       # (the default generator registers itself at capture_begin; these do not)
             g.register_generator_state(gen)
-        with torch.cuda.graph(g):
+        with (cap if cap is not None else torch.cuda.graph(g)):
             self._one_step(st)
         # capture does not execute; state is untouched
         st['graph'] = g
 
     @torch.no_grad()
-    def p_sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None, consistency_target=None):
+    def p_sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None, consistency_target=None,
+                      backprojection_target=None):
         """The reverse loop (`_sample_loop`); with tiling set (set_tiling / the "tiling" key) an input larger than the tile on either axis
         goes through the tiled loop instead.  consistency_target: under set_consistency, the [B, C, H / block, W / block] block means to
-        steer towards instead of the conditioning image's (the dataset's real LR image when block is the scale factor)."""
+        steer towards instead of the conditioning image's (the dataset's real LR image when block is the scale factor).
+        backprojection_target: under set_backprojection, the [B, C, H / scale, W / scale] LR image, in the model's range, to steer
+        towards instead of the down-sampled conditioning image (the dataset's real LR image)."""
         t = self.tiling
         if t is not None:
             shape = tuple(x_in) if not self.conditional else tuple(x_in.shape)
             if len(shape) == 4 and (shape[2] > t['tile'][0] or shape[3] > t['tile'][1]):
                 return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, tiling=t,
-                                         consistency_target=consistency_target)
-        return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, consistency_target=consistency_target)
+                                         consistency_target=consistency_target, backprojection_target=backprojection_target)
+        return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, consistency_target=consistency_target,
+                                 backprojection_target=backprojection_target)
 
     @torch.no_grad()
     def p_sample_loop_tiled(self, x_in, continous=False, *, tile, overlap, tile_batch=None, x_T=None, noise_seq=None, item_seeds=None):
@@ -919,7 +1116,8 @@ class EngineDiffusion(nn.Module):
         t = TL.parse_tiling(dict(tile=tile, overlap=overlap, batch=tile_batch), self.denoise_fn.plan.divisor)
         return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, tiling=t)
 
-    def _sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None, tiling=None, consistency_target=None):
+    def _sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None, tiling=None, consistency_target=None,
+                     backprojection_target=None):
         """sr3 diffusion.py:176-200 / ddpm :200-230.  Extensions: `x_T` injects the initial draw, `noise_seq[i]` the noise
         consumed at step i (the parity tests); `item_seeds` (one int per image of the batch) gives every image its own noise
         stream -- x_T and every step's z of image i come from a generator seeded with item_seeds[i], so the image's chain does
@@ -927,7 +1125,8 @@ class EngineDiffusion(nn.Module):
         sr.py feed one by one, infer.py:67-71).  Under a sampler (set_sampler) the loop takes its S steps instead of T, i counts
         the step index S-1 .. 0 (what `noise_seq` and the snapshot stride 1 | S // 10 go by), and eta = 0 draws x_T only.  Under
         set_consistency every step is an LR-consistent one (`_one_step`), towards the block means of the conditioning image or
-        `consistency_target`.  Under set_guidance every step is a guided one."""
+        `consistency_target`.  Under set_guidance every step is a guided one.  Under set_backprojection every step is a back-projected
+        one, towards `backprojection_target` or the down-sampled conditioning image."""
         cs = self.consistency
         if cs is None and consistency_target is not None:
             raise ValueError('consistency_target is given but consistency is off (set_consistency / the "consistency" key)')
@@ -937,6 +1136,13 @@ class EngineDiffusion(nn.Module):
         if cs is not None and not self.conditional and consistency_target is None:
             raise NotImplementedError('consistency on an unconditional model needs consistency_target=: there is no conditioning image to '
                                       'take the block means from')
+        bp = self.backprojection
+        if bp is None and backprojection_target is not None:
+            raise ValueError('backprojection_target is given but back-projection is off (set_backprojection / the "backprojection" key)')
+        self._check_backprojection(bp, self.sampler is not None, tiling, cs, gd)
+        if bp is not None and not self.conditional and backprojection_target is None:
+            raise NotImplementedError('back-projection on an unconditional model needs backprojection_target=: there is no conditioning '
+                                      'image to down-sample')
         dev = self.betas.device
         if dev.type != 'cuda':
             raise L.Sr3Error('p_sample_loop needs the model on a GPU (set gpu_ids); there is no CPU fallback')
@@ -966,6 +1172,14 @@ class EngineDiffusion(nn.Module):
             if consistency_target is not None and (not torch.is_tensor(consistency_target) or tuple(consistency_target.shape) != want):
                 raise L.Sr3Error('p_sample_loop: consistency_target must be a %s tensor of block means (got %s)'
                                  % (want, tuple(getattr(consistency_target, 'shape', ())) or type(consistency_target).__name__))
+        if bp is not None:
+            s = bp['scale']
+            if shape[2] % s or shape[3] % s:
+                raise L.Sr3Error('p_sample_loop: backprojection scale %d does not divide the image (%d x %d)' % (s, shape[2], shape[3]))
+            want = (shape[0], shape[1], shape[2] // s, shape[3] // s)
+            if backprojection_target is not None and (not torch.is_tensor(backprojection_target) or tuple(backprojection_target.shape) != want):
+                raise L.Sr3Error('p_sample_loop: backprojection_target must be a %s LR image (got %s)'
+                                 % (want, tuple(getattr(backprojection_target, 'shape', ())) or type(backprojection_target).__name__))
         tiles = None
         if tiling is not None:
             # tiled: the plan runs at the TILE's geometry; everything is validated here, before anything is written
@@ -978,7 +1192,7 @@ class EngineDiffusion(nn.Module):
         else:
             self.denoise_fn.plan.set_geometry(shape[2], shape[3])
         st = self._loop_state(shape, None if cond is None else shape, dev, item_streams=item_seeds is not None, tiles=tiles, consistency=cs,
-                              guidance=gd)
+                              guidance=gd, backprojection=bp)
         self.denoise_fn.ensure_derived()       # a replayed graph does not pass through EngineUNet.forward
         if item_seeds is not None:
             for g, v in zip(st['gens'], item_seeds):
@@ -1000,6 +1214,13 @@ class EngineDiffusion(nn.Module):
                 B, Cc, H, W = shape
                 src = st['cond'] if st['cond'].shape[1] == Cc else st['cond'][:, :Cc].contiguous()
                 L.check(L.load().sr3_block_mean_f32(L.ptr(src), B, Cc, H, W, cs['block'], L.ptr(st['ymean']), self._stream(dev)))
+        if bp is not None:                     # the LR target does not change over the chain: the conditioning image down-sampled once
+            if backprojection_target is not None:
+                st['y_lr'].copy_(backprojection_target)
+            else:
+                B, Cc, H, W = shape
+                src = st['cond'] if st['cond'].shape[1] == Cc else st['cond'][:, :Cc].contiguous()
+                st['y_lr'].copy_(resample_f32(src, tuple(st['y_lr'].shape[2:]), bp['resample'], tables=st['bp_down']))
         if st.get('hist') is not None:         # the first step's c3 is 0, but 0 * (whatever the last chain left, a NaN for one) is not 0
             st['hist'].zero_()
         st['step'].fill_(T - 1)                # (slot 1 = t of the next step; slot 0 is the step's scratch copy)
@@ -1042,8 +1263,9 @@ class EngineDiffusion(nn.Module):
         return self.p_sample_loop((batch_size, self.channels, self.image_size, self.image_size), continous, item_seeds=item_seeds)
 
     @torch.no_grad()
-    def super_resolution(self, x_in, continous=False, *, item_seeds=None, consistency_target=None):
-        return self.p_sample_loop(x_in, continous, item_seeds=item_seeds, consistency_target=consistency_target)
+    def super_resolution(self, x_in, continous=False, *, item_seeds=None, consistency_target=None, backprojection_target=None):
+        return self.p_sample_loop(x_in, continous, item_seeds=item_seeds, consistency_target=consistency_target,
+                                  backprojection_target=backprojection_target)
 
     # ---- forward process / loss --------------------------------------------------------------------
     def _q_sample_coef(self, x_start, ca, cb, noise):

@@ -401,6 +401,56 @@ int sr3_consistent_step(float* x_nchw, const float* eps_nchw, const float* z_nch
                         const float* tab_c2, const float* tab_sigma, int* step2_dev, int clip_denoised, const float* tab_c3,
                         float* hist_nchw, void* stream);
 
+/* ---- back-projection sampling (engine extension; no reference counterpart) -----------------------
+ * Iterative back-projection (Irani & Peleg 1991; the low-pass swap of ILVR, Choi et al. 2021, applied to x0) in the tail of a reverse
+ * step, under the resize the datasets are made with: Pillow's antialiased bicubic / bilinear resample, as fp32 planes.  A resample of
+ * one axis (in -> out elements) is given by two tables the HOST computes (sr3_hip.diffusion.resample_tables: Pillow's precompute_coeffs
+ * in float64, rounded once): bounds, int [out, 2] = (first tap, count), and weights, float [out, ksize], zero past the count.  One
+ * output value is  acc = +0 ; for t ascending: acc = acc + src[first + t] * w[t], every product and every sum rounded separately (no
+ * fma), one thread per value, no atomics: bitwise reproducible.  (first, count) are clamped on the device -- first into [0, in], count
+ * into [0, min(ksize, in - first)] -- so no table can take a kernel outside its tensors.  No host synchronisation, no allocation:
+ * capturable. */
+
+/* dst [planes, out_height, out_width] = the resample of src [planes, height, width]: the horizontal pass into tmp [planes, height,
+ * out_width], then the vertical pass (Pillow's order).  *_dev: device tables; bounds_h_host / bounds_v_host: optional host copies of the
+ * bounds, checked before the launch (every row inside [0, in] with 1 <= count <= ksize).  Any alignment (the vertical pass moves 16
+ * bytes a thread where out_width % 4 == 0 and tmp and dst are 16-byte aligned; the same bits otherwise).  Two launches.
+ * SR3_E_BADARG (the message names the argument): NULL src / dst / tmp / device table, non-positive size, ksize_h / ksize_v < 1, dst or
+ * tmp overlapping src, each other or a table, a bad host bounds row; SR3_E_UNSUPPORTED: planes * height * width (or the element count
+ * of tmp or dst) >= 2^31.  Nothing is launched on a refusal. */
+int sr3_resample_f32(const float* src, int planes, int height, int width, float* dst, int out_height, int out_width,
+                     const int* bounds_h_dev, const float* weights_h_dev, int ksize_h, const int* bounds_v_dev,
+                     const float* weights_v_dev, int ksize_v, float* tmp, const int* bounds_h_host, const int* bounds_v_host,
+                     void* stream);
+
+/* bytes of scratch sr3_backproject_step needs (x0, the horizontal pass's intermediate, the LR residual); 0 for sizes the step refuses */
+size_t sr3_backproject_scratch_bytes(int batch, int channels, int height, int width, int scale);
+
+/* The tail of one back-projected reverse step, in place on x_nchw [batch, channels, height, width], with j = step2_dev[1] on entry,
+ * s = scale, y = y_lr [batch, channels, height / s, width / s] the LR target, D the resample (height, width) -> (height / s, width / s)
+ * of the down_* tables and U the resample back of the up_* tables (each as sr3_resample_f32 defines it):
+ *   x0 = a[j] x - b[j] eps ; clamp(-1, 1) if clip_denoised                  (clamp first, as sr3_consistent_step)
+ *   `iterations` times:   r = y - D(x0) ;  x0 = x0 + strength * U(r)        (each operation rounded separately)
+ *   x  = ((c1[j] x0 + c2[j] x) + c3[j] hist) + sigma[j] z ; hist <- x0      (sr3_p_sample_step_hist's operations and association;
+ *                                                                            tab_c3 / hist_nchw both NULL: no history term)
+ * step2_dev[1] = j - 1 on completion (step2_dev[0] is scratch, as in sr3_tiled_step).  A contraction towards D(x0) = y, not a projection:
+ * the residual shrinks with every iteration and does not vanish.  eps_nchw is the network's output for this step (sr3_unet_forward with
+ * step_dev = step2_dev + 1); z_nchw: the step's noise or NULL (= 0); tab_*: as sr3_reverse_step.  scratch: the caller's,
+ * sr3_backproject_scratch_bytes bytes, written before it is read.  2 + 3 * iterations launches; bitwise reproducible.  Any alignment
+ * (width % 4 != 0 or a pointer off a 16-byte boundary takes the one-element-per-thread form, the same bits).
+ * SR3_E_BADARG (the message names the argument): NULL required pointer, non-positive size, scale < 2 or not dividing both height and
+ * width, iterations outside 1..16, strength NaN or outside (0, 2), a ksize < 1, only one of tab_c3 / hist_nchw, hist_nchw overlapping
+ * x_nchw or eps_nchw, NULL or too small scratch, anything written (x_nchw, hist_nchw, scratch, step2_dev) overlapping another argument;
+ * SR3_E_ALIGN: scratch not 4-byte aligned; SR3_E_UNSUPPORTED: batch * channels * height * width >= 2^31.  Nothing is launched on a
+ * refusal. */
+int sr3_backproject_step(float* x_nchw, const float* eps_nchw, const float* z_nchw, const float* y_lr, int batch, int channels, int height,
+                         int width, int scale, int iterations, float strength, const int* down_bounds_h, const float* down_weights_h,
+                         int down_ksize_h, const int* down_bounds_v, const float* down_weights_v, int down_ksize_v,
+                         const int* up_bounds_h, const float* up_weights_h, int up_ksize_h, const int* up_bounds_v,
+                         const float* up_weights_v, int up_ksize_v, const float* tab_a, const float* tab_b, const float* tab_c1,
+                         const float* tab_c2, const float* tab_sigma, int* step2_dev, int clip_denoised, const float* tab_c3,
+                         float* hist_nchw, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- guided sampling (engine extension; no reference counterpart) --------------------------------
  * Classifier-free guidance (Ho & Salimans 2022) and dynamic thresholding (Saharia et al. 2022, section 2.3) in the tail of a reverse
  * step, and the conditioning dropout that trains a model for guidance.  Every entry checks its arguments on the host, names the

@@ -7,9 +7,11 @@ the wall time of whole `super_resolution` chains of --chain steps (capture exclu
 block-mean projection of set_consistency(R) in its tail (three graph nodes -- forward with eps stored, counter copy, sr3_consistent_step
 -- in place of the fused step), next to the dpmpp_2m leg in every round.  --guidance SCALE --threshold MODE (either may be given more
 than once, paired in order) adds a leg per pair: dpmpp_2m under set_guidance(SCALE, MODE) -- one forward (scale 1) or two, each with its
-output stored, then sr3_guided_step in place of the fused step; --no-chains skips the whole-chain timings.
+output stored, then sr3_guided_step in place of the fused step; --no-chains skips the whole-chain timings.  --backprojection S
+--bp-iterations K (K may be given more than once) adds a leg per K: dpmpp_2m under set_backprojection(S, K) -- the forward with eps
+stored, then sr3_backproject_step (2 + 3 K launches) in place of the fused step.
     python tools/sampler_probe.py [--config sr3_16_128] [--replays 200] [--reps 3] [--chain 100] [--consistency 8]
-                                  [--guidance 1.5 --threshold dynamic]                                                   (GPU box)"""
+                                  [--guidance 1.5 --threshold dynamic] [--backprojection 8 --bp-iterations 1 --bp-iterations 2]   (GPU box)"""
 import argparse
 import json
 import os
@@ -31,6 +33,8 @@ def main():
     ap.add_argument('--guidance', type=float, action='append', default=[], metavar='SCALE', help='add a dpmpp_2m leg with set_guidance(SCALE, MODE)')
     ap.add_argument('--threshold', action='append', default=[], metavar='MODE', help='static (default) | none | dynamic, one per --guidance')
     ap.add_argument('--percentile', type=float, default=0.995)
+    ap.add_argument('--backprojection', type=int, default=0, metavar='SCALE', help='add dpmpp_2m legs with set_backprojection(SCALE, K)')
+    ap.add_argument('--bp-iterations', type=int, action='append', default=[], metavar='K', help='one leg per K (default: 1)')
     ap.add_argument('--no-chains', action='store_true', help='time the replayed steps only')
     a = ap.parse_args()
     sys.path.insert(0, PKG)
@@ -60,22 +64,34 @@ def main():
         assert cond is not None, '--guidance needs a conditional config'
         mode = a.threshold[i] if i < len(a.threshold) else 'static'
         legs['dpmpp_2m_guidance%g_%s' % (scale, mode)] = dict(steps=N, kind='dpmpp_2m', guidance=(scale, mode, a.percentile))
+    if a.backprojection:
+        assert cond is not None, '--backprojection needs a conditional config'
+        for k in (a.bp_iterations or [1]):
+            legs['dpmpp_2m_backprojection%d_K%d' % (a.backprojection, k)] = dict(steps=N, kind='dpmpp_2m', backprojection=(a.backprojection, k))
     states = {}
     for name, spec in legs.items():                      # one captured graph per leg, all alive at once
         spec = dict(spec)
         netG.set_guidance(None)
+        netG.set_backprojection(None)
         netG.set_consistency(spec.pop('consistency', None))
         gd = spec.pop('guidance', None)
+        bp = spec.pop('backprojection', None)
         netG.set_sampler(**spec)
         if gd is not None:
             netG.set_guidance(*gd)
-        st = netG._loop_state(shape, shape if cond is not None else None, dev, consistency=netG.consistency, guidance=netG.guidance)
+        if bp is not None:
+            netG.set_backprojection(*bp)
+        st = netG._loop_state(shape, shape if cond is not None else None, dev, consistency=netG.consistency, guidance=netG.guidance,
+                              backprojection=netG.backprojection)
         netG.denoise_fn.ensure_derived()
         if cond is not None:
             st['cond'].copy_(cond)
         if netG.consistency is not None:
             from sr3_hip.diffusion import block_means
             st['ymean'].copy_(block_means(cond, a.consistency))
+        if netG.backprojection is not None:
+            from sr3_hip.diffusion import resample_f32
+            st['y_lr'].copy_(resample_f32(cond, tuple(st['y_lr'].shape[2:]), tables=st['bp_down']))
         netG._capture(st)
         states[name] = st
     ms = {name: [] for name in legs}
@@ -100,6 +116,7 @@ def main():
         rec['ms_per_step_' + name] = {'best': min(ms[name]), 'median': statistics.median(ms[name])}
     netG.set_consistency(None)
     netG.set_guidance(None)
+    netG.set_backprojection(None)
     if a.no_chains:
         print(json.dumps(rec))
         return
