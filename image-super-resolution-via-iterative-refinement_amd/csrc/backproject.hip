@@ -29,9 +29,7 @@
 // vertical taps cover, the horizontal sum over that row's <= ksize_h taps in the order above, and then their vertical sum in the order
 // above -- the values the two-pass definition keeps in its intermediate, the same bits, without the intermediate or its launch.  r is
 // 1 / s^2 of the image and stays in the cache.  No LDS: there is no launch left for it to remove.
-#include <string.h>
-
-#include "sr3_common.h"
+#include "step_tail.h"
 
 namespace sr3 {
 namespace {
@@ -115,16 +113,12 @@ __global__ __launch_bounds__(256) void k_bp_x0(const float* __restrict__ x, cons
   if (i >= total) return;
   const StepCoef cf = load_step_coef<false>(tb, nullptr, step_cur[0]);
   const size_t e = (size_t)i * V;
-  if constexpr (V == 4) {
-    const f32x4 xq = *reinterpret_cast<const f32x4*>(x + e);
-    const f32x4 eq = *reinterpret_cast<const f32x4*>(eps + e);
-    f32x4 o;
+  float xv[V], ev[V], o[V];
+  load_v<V>(x + e, xv);
+  load_v<V>(eps + e, ev);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = step_x0(cf, CLIP, xq[k], eq[k]);
-    *reinterpret_cast<f32x4*>(x0 + e) = o;
-  } else {
-    x0[e] = step_x0(cf, CLIP, x[e], eps[e]);
-  }
+  for (int k = 0; k < V; ++k) o[k] = step_x0(cf, CLIP, xv[k], ev[k]);
+  store_v<V>(x0 + e, o);
 }
 
 struct BpUp {
@@ -153,11 +147,7 @@ __global__ __launch_bounds__(256) void k_bp_up(BpUp s) {
   const StepFuse& f = s.f;
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
   StepCoef cf = {};
-  if (LAST) {
-    const int j = f.step_cur[0];
-    if (i == 0) f.step_next[0] = j - 1;      // (nobody reads this slot before the next step's first kernel)
-    cf = load_step_coef<HIST>(f.tb, f.c3, j);
-  }
+  if (LAST) cf = tail_begin<HIST>(f, i == 0);
   if (i >= s.total) return;
   const unsigned W = (unsigned)s.uh.out, H = (unsigned)s.uv.out;
   const unsigned wq = W / V;
@@ -169,53 +159,18 @@ __global__ __launch_bounds__(256) void k_bp_up(BpUp s) {
   const float* rp = s.r + (size_t)p * s.uv.in * s.uh.in;
   const size_t e = (size_t)i * V;
   float x0v[V], xv[V], zv[V], hv[V];
-  if constexpr (V == 4) {
-    const f32x4 q = *reinterpret_cast<const f32x4*>(s.x0 + e);
-    f32x4 xq4 = {0.f, 0.f, 0.f, 0.f}, zq = {0.f, 0.f, 0.f, 0.f}, hq = {0.f, 0.f, 0.f, 0.f};
-    if (LAST) {
-      xq4 = *reinterpret_cast<const f32x4*>(f.x + e);
-      if (f.z) zq = *reinterpret_cast<const f32x4*>(f.z + e);
-      if (HIST) hq = *reinterpret_cast<const f32x4*>(f.hist + e);
-    }
+  load_v<V>(s.x0 + e, x0v);
+  if (LAST) tail_load<HIST, V>(f, e, xv, zv, hv);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { x0v[k] = q[k]; xv[k] = xq4[k]; zv[k] = zq[k]; hv[k] = hq[k]; }
-  } else {
-    x0v[0] = s.x0[e];
-    xv[0] = LAST ? f.x[e] : 0.f; zv[0] = (LAST && f.z) ? f.z[e] : 0.f; hv[0] = (LAST && HIST) ? f.hist[e] : 0.f;
-  }
-#pragma unroll
-  for (int k = 0; k < V; ++k) {
-    const float u = up_value(s, rp, vfirst, vcount, wv, (int)(xq * V + k));
-    x0v[k] = add_rn(x0v[k], mul_rn(s.strength, u));
-    if (LAST) xv[k] = step_mix<HIST>(cf, x0v[k], xv[k], zv[k], hv[k]);
-  }
-  if constexpr (V == 4) {
-    if (LAST) {
-      const f32x4 xo = {xv[0], xv[1], xv[2], xv[3]};
-      *reinterpret_cast<f32x4*>(f.x + e) = xo;
-      if (HIST) {
-        const f32x4 ho = {hv[0], hv[1], hv[2], hv[3]};
-        *reinterpret_cast<f32x4*>(f.hist + e) = ho;
-      }
-    } else {
-      const f32x4 o = {x0v[0], x0v[1], x0v[2], x0v[3]};
-      *reinterpret_cast<f32x4*>(s.x0 + e) = o;
-    }
-  } else {
-    if (LAST) {
-      f.x[e] = xv[0];
-      if (HIST) f.hist[e] = hv[0];
-    } else {
-      s.x0[e] = x0v[0];
-    }
-  }
+  for (int k = 0; k < V; ++k) x0v[k] = add_rn(x0v[k], mul_rn(s.strength, up_value(s, rp, vfirst, vcount, wv, (int)(xq * V + k))));
+  if (LAST) tail_mix_store<HIST, V>(f, cf, e, x0v, xv, zv, hv);
+  else store_v<V>(s.x0 + e, x0v);
 }
 
 inline dim3 grid_of(size_t items) { return dim3((unsigned)((items + 255) / 256)); }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline size_t round4(size_t floats) { return (floats + 3) & ~(size_t)3; }
 
-const size_t LIMIT = (size_t)1 << 31;
+const size_t LIMIT = (size_t)1 << 31;      // (sr3_resample_f32's three limits; the step's is check_image_limit)
 
 // the two passes of one resample, planes [planes, H, W] -> [planes, OH, OW] through tmp [planes, H, OW]; y: RESID target or null
 int launch_resample(const float* src, float* dst, float* tmp, const float* y, int planes, int H, int W, int OH, int OW, const Axis& h,
@@ -224,15 +179,11 @@ int launch_resample(const float* src, float* dst, float* tmp, const float* y, in
   hipLaunchKernelGGL(k_resample_h, grid_of(n_tmp), dim3(256), 0, st, src, tmp, h, (unsigned)n_tmp);
   SR3_LAUNCH_CHECK("k_resample_h");
   const size_t n_dst = (size_t)planes * OH * OW;
-  const bool vec = (OW & 3) == 0 && aligned16(tmp) && aligned16(dst) && (!y || aligned16(y));
+  const bool vec = (OW & 3) == 0 && vec16(tmp, dst, y);
   const size_t items = vec ? n_dst / 4 : n_dst;
-  if (y) {
-    if (vec) hipLaunchKernelGGL((k_resample_v<true, 4>), grid_of(items), dim3(256), 0, st, tmp, dst, y, v, OW, (unsigned)items);
-    else hipLaunchKernelGGL((k_resample_v<true, 1>), grid_of(items), dim3(256), 0, st, tmp, dst, y, v, OW, (unsigned)items);
-  } else {
-    if (vec) hipLaunchKernelGGL((k_resample_v<false, 4>), grid_of(items), dim3(256), 0, st, tmp, dst, y, v, OW, (unsigned)items);
-    else hipLaunchKernelGGL((k_resample_v<false, 1>), grid_of(items), dim3(256), 0, st, tmp, dst, y, v, OW, (unsigned)items);
-  }
+  dispatch_bools([&](auto resid, auto v4) {
+    hipLaunchKernelGGL((k_resample_v<resid(), v4() ? 4 : 1>), grid_of(items), dim3(256), 0, st, tmp, dst, y, v, OW, (unsigned)items);
+  }, y != nullptr, vec);
   SR3_LAUNCH_CHECK("k_resample_v");
   return SR3_OK;
 }
@@ -251,15 +202,11 @@ int check_host_bounds(const char* who, const char* name, const int* b, int out, 
 
 // the sizes of the step, before anything is launched; *total = B * C * H * W
 int check_bp_sizes(const char* who, int batch, int channels, int height, int width, int scale, size_t* total) {
-  if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0) {
-    set_error("%s: batch, channels, height and width must be positive (got %d, %d, %d, %d)", who, batch, channels, height, width);
-    return SR3_E_BADARG;
-  }
+  if (const int rc = check_image_dims(who, batch, channels, height, width)) return rc;
   if (scale < 2) { set_error("%s: scale must be at least 2 (got %d)", who, scale); return SR3_E_BADARG; }
   if (height % scale || width % scale) { set_error("%s: scale %d does not divide height %d and width %d", who, scale, height, width); return SR3_E_BADARG; }
   *total = (size_t)batch * channels * height * width;
-  if (*total >= LIMIT) { set_error("%s: image batch too large (batch * channels * height * width >= 2^31)", who); return SR3_E_UNSUPPORTED; }
-  return SR3_OK;
+  return check_image_limit(who, *total);
 }
 
 struct BpLayout { size_t x0, tmp, r, floats; };      // offsets in floats, each a multiple of 4 (16 bytes)
@@ -283,11 +230,9 @@ int sr3_resample_f32(const float* src, int planes, int height, int width, float*
                      const int* bounds_h_dev, const float* weights_h_dev, int ksize_h, const int* bounds_v_dev,
                      const float* weights_v_dev, int ksize_v, float* tmp, const int* bounds_h_host, const int* bounds_v_host,
                      void* stream) {
-  const struct { const void* p; const char* name; } req[] = {{src, "src"}, {dst, "dst"}, {bounds_h_dev, "bounds_h_dev"},
-      {weights_h_dev, "weights_h_dev"}, {bounds_v_dev, "bounds_v_dev"}, {weights_v_dev, "weights_v_dev"}, {tmp, "tmp"}};
-  for (const auto& q : req) {
-    if (!q.p) { set_error("resample: %s is NULL", q.name); return SR3_E_BADARG; }
-  }
+  const Req req[] = {{src, "src"}, {dst, "dst"}, {bounds_h_dev, "bounds_h_dev"}, {weights_h_dev, "weights_h_dev"}, {bounds_v_dev, "bounds_v_dev"},
+      {weights_v_dev, "weights_v_dev"}, {tmp, "tmp"}};
+  if (const int rc = check_required("resample", req)) return rc;
   if (planes <= 0 || height <= 0 || width <= 0 || out_height <= 0 || out_width <= 0) {
     set_error("resample: planes, height, width, out_height and out_width must be positive (got %d, %d, %d, %d, %d)", planes, height, width,
               out_height, out_width);
@@ -335,13 +280,11 @@ int sr3_backproject_step(float* x_nchw, const float* eps_nchw, const float* z_nc
                          const float* tab_c2, const float* tab_sigma, int* step2_dev, int clip_denoised, const float* tab_c3,
                          float* hist_nchw, void* scratch, size_t scratch_bytes, void* stream) {
   const char* who = "backproject_step";
-  const struct { const void* p; const char* name; } req[] = {{x_nchw, "x_nchw"}, {eps_nchw, "eps_nchw"}, {y_lr, "y_lr"},
+  const Req req[] = {{x_nchw, "x_nchw"}, {eps_nchw, "eps_nchw"}, {y_lr, "y_lr"},
       {down_bounds_h, "down_bounds_h"}, {down_weights_h, "down_weights_h"}, {down_bounds_v, "down_bounds_v"}, {down_weights_v, "down_weights_v"},
       {up_bounds_h, "up_bounds_h"}, {up_weights_h, "up_weights_h"}, {up_bounds_v, "up_bounds_v"}, {up_weights_v, "up_weights_v"},
       {tab_a, "tab_a"}, {tab_b, "tab_b"}, {tab_c1, "tab_c1"}, {tab_c2, "tab_c2"}, {tab_sigma, "tab_sigma"}, {step2_dev, "step2_dev"}};
-  for (const auto& q : req) {
-    if (!q.p) { set_error("%s: %s is NULL", who, q.name); return SR3_E_BADARG; }
-  }
+  if (const int rc = check_required(who, req)) return rc;
   size_t total = 0;
   if (const int rc = check_bp_sizes(who, batch, channels, height, width, scale, &total)) return rc;
   if (iterations < 1 || iterations > 16) { set_error("%s: iterations must lie in 1..16 (got %d)", who, iterations); return SR3_E_BADARG; }
@@ -363,24 +306,17 @@ int sr3_backproject_step(float* x_nchw, const float* eps_nchw, const float* z_nc
   const int OH = height / scale, OW = width / scale;
   const size_t n_lr = total / scale / scale;
   // what the call writes (x, hist, scratch, the counter) against everything else it is given
-  const struct { const void* p; size_t bytes; const char* name; } wr[] = {{x_nchw, bytes, "x_nchw"}, {hist_nchw, hist_nchw ? bytes : 0, "hist_nchw"},
-      {scratch, lay.floats * sizeof(float), "scratch"}, {step2_dev, 2 * sizeof(int), "step2_dev"}};
-  const struct { const void* p; size_t bytes; const char* name; } all[] = {{x_nchw, bytes, "x_nchw"}, {eps_nchw, bytes, "eps_nchw"},
-      {z_nchw, z_nchw ? bytes : 0, "z_nchw"}, {y_lr, n_lr * sizeof(float), "y_lr"}, {hist_nchw, hist_nchw ? bytes : 0, "hist_nchw"},
-      {scratch, lay.floats * sizeof(float), "scratch"}, {step2_dev, 2 * sizeof(int), "step2_dev"},
-      {down_bounds_h, (size_t)OW * 2 * sizeof(int), "down_bounds_h"}, {down_weights_h, (size_t)OW * down_ksize_h * sizeof(float), "down_weights_h"},
-      {down_bounds_v, (size_t)OH * 2 * sizeof(int), "down_bounds_v"}, {down_weights_v, (size_t)OH * down_ksize_v * sizeof(float), "down_weights_v"},
-      {up_bounds_h, (size_t)width * 2 * sizeof(int), "up_bounds_h"}, {up_weights_h, (size_t)width * up_ksize_h * sizeof(float), "up_weights_h"},
-      {up_bounds_v, (size_t)height * 2 * sizeof(int), "up_bounds_v"}, {up_weights_v, (size_t)height * up_ksize_v * sizeof(float), "up_weights_v"},
-      {tab_a, sizeof(float), "tab_a"}, {tab_b, sizeof(float), "tab_b"}, {tab_c1, sizeof(float), "tab_c1"}, {tab_c2, sizeof(float), "tab_c2"},
-      {tab_sigma, sizeof(float), "tab_sigma"}, {tab_c3, tab_c3 ? sizeof(float) : 0, "tab_c3"}};
-  for (const auto& w : wr) {
-    if (!w.bytes) continue;
-    for (const auto& o : all) {
-      if (!o.bytes || !strcmp(o.name, w.name)) continue;      // (the entry itself)
-      if (overlaps(w.p, w.bytes, o.p, o.bytes)) { set_error("%s: %s overlaps %s", who, w.name, o.name); return SR3_E_BADARG; }
-    }
-  }
+  const size_t fl = sizeof(float);
+  const Buf bufs[] = {{x_nchw, bytes, "x_nchw", true}, {eps_nchw, bytes, "eps_nchw", false}, {z_nchw, bytes, "z_nchw", false},
+      {y_lr, n_lr * fl, "y_lr", false}, {hist_nchw, bytes, "hist_nchw", true}, {scratch, lay.floats * fl, "scratch", true},
+      {step2_dev, 2 * sizeof(int), "step2_dev", true},
+      {down_bounds_h, (size_t)OW * 2 * sizeof(int), "down_bounds_h", false}, {down_weights_h, (size_t)OW * down_ksize_h * fl, "down_weights_h", false},
+      {down_bounds_v, (size_t)OH * 2 * sizeof(int), "down_bounds_v", false}, {down_weights_v, (size_t)OH * down_ksize_v * fl, "down_weights_v", false},
+      {up_bounds_h, (size_t)width * 2 * sizeof(int), "up_bounds_h", false}, {up_weights_h, (size_t)width * up_ksize_h * fl, "up_weights_h", false},
+      {up_bounds_v, (size_t)height * 2 * sizeof(int), "up_bounds_v", false}, {up_weights_v, (size_t)height * up_ksize_v * fl, "up_weights_v", false},
+      {tab_a, fl, "tab_a", false}, {tab_b, fl, "tab_b", false}, {tab_c1, fl, "tab_c1", false}, {tab_c2, fl, "tab_c2", false},
+      {tab_sigma, fl, "tab_sigma", false}, {tab_c3, fl, "tab_c3", false}};
+  if (const int rc = check_overlaps(who, bufs)) return rc;
   float* sc = static_cast<float*>(scratch);
   float* x0 = sc + lay.x0;
   float* tmp = sc + lay.tmp;
@@ -388,19 +324,14 @@ int sr3_backproject_step(float* x_nchw, const float* eps_nchw, const float* z_nc
   const int planes = batch * channels;
   const Axis dh{down_bounds_h, down_weights_h, down_ksize_h, width, OW};
   const Axis dv{down_bounds_v, down_weights_v, down_ksize_v, height, OH};
-  const bool vec = (width & 3) == 0 && aligned16(scratch) &&
-                   ((((uintptr_t)x_nchw | (uintptr_t)eps_nchw | (uintptr_t)z_nchw | (uintptr_t)hist_nchw) & 15) == 0);
+  const bool vec = (width & 3) == 0 && vec16(scratch, x_nchw, eps_nchw, z_nchw, hist_nchw);
   const size_t items = vec ? total / 4 : total;
   const StepTables tb{tab_a, tab_b, tab_c1, tab_c2, tab_sigma};
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (const int rc = step_copy(step2_dev, st)) return rc;
-  if (vec) {
-    if (clip_denoised) hipLaunchKernelGGL((k_bp_x0<true, 4>), grid_of(items), dim3(256), 0, st, x_nchw, eps_nchw, x0, tb, step2_dev, (unsigned)items);
-    else hipLaunchKernelGGL((k_bp_x0<false, 4>), grid_of(items), dim3(256), 0, st, x_nchw, eps_nchw, x0, tb, step2_dev, (unsigned)items);
-  } else {
-    if (clip_denoised) hipLaunchKernelGGL((k_bp_x0<true, 1>), grid_of(items), dim3(256), 0, st, x_nchw, eps_nchw, x0, tb, step2_dev, (unsigned)items);
-    else hipLaunchKernelGGL((k_bp_x0<false, 1>), grid_of(items), dim3(256), 0, st, x_nchw, eps_nchw, x0, tb, step2_dev, (unsigned)items);
-  }
+  dispatch_bools([&](auto clip, auto v4) {
+    hipLaunchKernelGGL((k_bp_x0<clip(), v4() ? 4 : 1>), grid_of(items), dim3(256), 0, st, x_nchw, eps_nchw, x0, tb, step2_dev, (unsigned)items);
+  }, clip_denoised != 0, vec);
   SR3_LAUNCH_CHECK("k_bp_x0");
   BpUp s;
   s.f = StepFuse{x_nchw, z_nchw, tb, step2_dev, step2_dev + 1, clip_denoised, tab_c3, hist_nchw};
@@ -411,14 +342,10 @@ int sr3_backproject_step(float* x_nchw, const float* eps_nchw, const float* z_nc
   for (int it = 0; it < iterations; ++it) {
     if (const int rc = launch_resample(x0, r, tmp, y_lr, planes, height, width, OH, OW, dh, dv, st)) return rc;
     if (it + 1 < iterations) {
-      if (vec) hipLaunchKernelGGL((k_bp_up<false, false, 4>), grid_of(items), dim3(256), 0, st, s);
-      else hipLaunchKernelGGL((k_bp_up<false, false, 1>), grid_of(items), dim3(256), 0, st, s);
-    } else if (vec) {
-      if (hist_nchw) hipLaunchKernelGGL((k_bp_up<true, true, 4>), grid_of(items), dim3(256), 0, st, s);
-      else hipLaunchKernelGGL((k_bp_up<true, false, 4>), grid_of(items), dim3(256), 0, st, s);
+      dispatch_bools([&](auto v4) { hipLaunchKernelGGL((k_bp_up<false, false, v4() ? 4 : 1>), grid_of(items), dim3(256), 0, st, s); }, vec);
     } else {
-      if (hist_nchw) hipLaunchKernelGGL((k_bp_up<true, true, 1>), grid_of(items), dim3(256), 0, st, s);
-      else hipLaunchKernelGGL((k_bp_up<true, false, 1>), grid_of(items), dim3(256), 0, st, s);
+      dispatch_bools([&](auto hist, auto v4) { hipLaunchKernelGGL((k_bp_up<true, hist(), v4() ? 4 : 1>), grid_of(items), dim3(256), 0, st, s); },
+                     hist_nchw != nullptr, vec);
     }
     SR3_LAUNCH_CHECK("k_bp_up");
   }

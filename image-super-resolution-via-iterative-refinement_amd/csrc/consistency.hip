@@ -17,13 +17,13 @@
 // so d, rounded once, is the value a NumPy restatement gets, and the step is bitwise reproducible run to run.
 //
 // Work split: a thread owns V consecutive columns (V = 4 as one 16-byte access where W % 4 == 0, r % 4 == 0 and every pointer is
-// 16-byte aligned; V = 1 otherwise) of one strip of r image rows of one (b, c) plane, lanes along x, so a row of the strip is read as
-// one contiguous segment by consecutive lanes.  It adds its columns down the strip in row order; the n = r / V lanes of a block -- n is
+// 16-byte aligned, step_tail.h's vec16; V = 1 otherwise) of one strip of r image rows of one (b, c) plane, lanes along x, so a row of
+// the strip is read as one contiguous segment by consecutive lanes.  It adds its columns down the strip in row order; the n = r / V lanes of a block -- n is
 // a power of two <= 32, and the lanes are consecutive and aligned to n, so they sit in one wavefront -- combine with a fixed
 // __shfl_xor tree, after which every lane of the block holds the same S (a + b == b + a at every level).  x0 is not kept (r V values
 // per thread: up to 128 registers): the second pass computes it again from the same operands, the same bits, and the strip's x and
 // eps come out of the cache.  One thread per item, no grid-stride loop: there are fewer than 2^31 items.
-#include "sr3_common.h"
+#include "step_tail.h"
 
 namespace sr3 {
 namespace {
@@ -54,13 +54,10 @@ __global__ __launch_bounds__(256) void k_block_mean(const float* __restrict__ sr
   if (act) {
     const float* p = src + s * r * W + (size_t)lx * V;
     for (int y = 0; y < r; ++y, p += W) {
-      if constexpr (V == 4) {
-        const f32x4 q = *reinterpret_cast<const f32x4*>(p);
+      float v[V];
+      load_v<V>(p, v);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) S += (double)q[k];
-      } else {
-        S += (double)p[0];
-      }
+      for (int k = 0; k < V; ++k) S += (double)v[k];
     }
   }
   S = block_reduce(S, n);
@@ -79,9 +76,7 @@ struct ConsistentStep {
 template <bool CLIP, bool HIST, int V>
 __global__ __launch_bounds__(256) void k_consistent_step(ConsistentStep s) {
   const StepFuse& f = s.f;
-  const int j = f.step_cur[0];
-  if (blockIdx.x == 0 && threadIdx.x == 0) f.step_next[0] = j - 1;      // (nobody reads this slot before the next step's first kernel)
-  const StepCoef cf = load_step_coef<HIST>(f.tb, f.c3, j);
+  const StepCoef cf = tail_begin<HIST>(f, blockIdx.x == 0 && threadIdx.x == 0);
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool act = i < s.total;
   int lx = 0;
@@ -92,14 +87,11 @@ __global__ __launch_bounds__(256) void k_consistent_step(ConsistentStep s) {
     const float* px = f.x + e0;
     const float* pe = s.eps + e0;
     for (int y = 0; y < s.r; ++y, px += s.W, pe += s.W) {
-      if constexpr (V == 4) {
-        const f32x4 xq = *reinterpret_cast<const f32x4*>(px);
-        const f32x4 eq = *reinterpret_cast<const f32x4*>(pe);
+      float xv[V], ev[V];
+      load_v<V>(px, xv);
+      load_v<V>(pe, ev);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) S += (double)step_x0(cf, CLIP, xq[k], eq[k]);
-      } else {
-        S += (double)step_x0(cf, CLIP, px[0], pe[0]);
-      }
+      for (int k = 0; k < V; ++k) S += (double)step_x0(cf, CLIP, xv[k], ev[k]);
     }
   }
   S = block_reduce(S, s.n);
@@ -110,48 +102,22 @@ __global__ __launch_bounds__(256) void k_consistent_step(ConsistentStep s) {
   const float delta = (float)((double)s.strength * (yv - mean));
   size_t e = e0;
   for (int y = 0; y < s.r; ++y, e += s.W) {
-    float xv[V], ev[V], zv[V], hv[V];
-    if constexpr (V == 4) {
-      const f32x4 xq = *reinterpret_cast<const f32x4*>(f.x + e);
-      const f32x4 eq = *reinterpret_cast<const f32x4*>(s.eps + e);
-      f32x4 zq = {0.f, 0.f, 0.f, 0.f}, hq = {0.f, 0.f, 0.f, 0.f};
-      if (f.z) zq = *reinterpret_cast<const f32x4*>(f.z + e);
-      if (HIST) hq = *reinterpret_cast<const f32x4*>(f.hist + e);
+    float xv[V], ev[V], zv[V], hv[V], x0[V];
+    load_v<V>(s.eps + e, ev);
+    tail_load<HIST, V>(f, e, xv, zv, hv);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) { xv[k] = xq[k]; ev[k] = eq[k]; zv[k] = zq[k]; hv[k] = hq[k]; }
-    } else {
-      xv[0] = f.x[e]; ev[0] = s.eps[e]; zv[0] = f.z ? f.z[e] : 0.f; hv[0] = HIST ? f.hist[e] : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      const float x0p = add_rn(step_x0(cf, CLIP, xv[k], ev[k]), delta);
-      xv[k] = step_mix<HIST>(cf, x0p, xv[k], zv[k], hv[k]);
-    }
-    if constexpr (V == 4) {
-      const f32x4 xo = {xv[0], xv[1], xv[2], xv[3]};
-      *reinterpret_cast<f32x4*>(f.x + e) = xo;
-      if (HIST) {
-        const f32x4 ho = {hv[0], hv[1], hv[2], hv[3]};
-        *reinterpret_cast<f32x4*>(f.hist + e) = ho;
-      }
-    } else {
-      f.x[e] = xv[0];
-      if (HIST) f.hist[e] = hv[0];
-    }
+    for (int k = 0; k < V; ++k) x0[k] = add_rn(step_x0(cf, CLIP, xv[k], ev[k]), delta);
+    tail_mix_store<HIST, V>(f, cf, e, x0, xv, zv, hv);
   }
 }
 
 // the size arguments both entries share, before anything is launched; *total = B * C * H * W
 int check_blocks(const char* who, int batch, int channels, int height, int width, int block, size_t* total) {
-  if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0) {
-    set_error("%s: batch, channels, height and width must be positive (got %d, %d, %d, %d)", who, batch, channels, height, width);
-    return SR3_E_BADARG;
-  }
+  if (const int rc = check_image_dims(who, batch, channels, height, width)) return rc;
   if (block != 2 && block != 4 && block != 8 && block != 16 && block != 32) { set_error("%s: block must be 2, 4, 8, 16 or 32 (got %d)", who, block); return SR3_E_BADARG; }
   if (height % block || width % block) { set_error("%s: block %d does not divide height %d and width %d", who, block, height, width); return SR3_E_BADARG; }
   *total = (size_t)batch * channels * height * width;
-  if (*total >= ((size_t)1 << 31)) { set_error("%s: image batch too large (batch * channels * height * width >= 2^31)", who); return SR3_E_UNSUPPORTED; }
-  return SR3_OK;
+  return check_image_limit(who, *total);
 }
 
 }  // namespace
@@ -168,7 +134,7 @@ int sr3_block_mean_f32(const float* src_nchw, int batch, int channels, int heigh
   if (const int rc = check_blocks("block_mean", batch, channels, height, width, block, &total)) return rc;
   if (overlaps(src_nchw, total * sizeof(float), dst_means, total / ((size_t)block * block) * sizeof(float))) { set_error("block_mean: dst_means overlaps src_nchw"); return SR3_E_BADARG; }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool vec = (width & 3) == 0 && (block & 3) == 0 && ((uintptr_t)src_nchw & 15) == 0;
+  const bool vec = (width & 3) == 0 && (block & 3) == 0 && vec16(src_nchw);
   const size_t items = vec ? total / block / 4 : total / block;
   const dim3 grid((unsigned)((items + 255) / 256));
   if (vec) hipLaunchKernelGGL(k_block_mean<4>, grid, dim3(256), 0, st, src_nchw, dst_means, width, block, block / 4, items);
@@ -181,19 +147,16 @@ int sr3_consistent_step(float* x_nchw, const float* eps_nchw, const float* z_nch
                         int height, int width, int block, float strength, const float* tab_a, const float* tab_b, const float* tab_c1,
                         const float* tab_c2, const float* tab_sigma, int* step2_dev, int clip_denoised, const float* tab_c3,
                         float* hist_nchw, void* stream) {
-  const struct { const void* p; const char* name; } req[] = {{x_nchw, "x_nchw"}, {eps_nchw, "eps_nchw"}, {target_means, "target_means"},
-      {tab_a, "tab_a"}, {tab_b, "tab_b"}, {tab_c1, "tab_c1"}, {tab_c2, "tab_c2"}, {tab_sigma, "tab_sigma"}, {step2_dev, "step2_dev"}};
-  for (const auto& q : req) {
-    if (!q.p) { set_error("consistent_step: %s is NULL", q.name); return SR3_E_BADARG; }
-  }
+  const Req req[] = {{x_nchw, "x_nchw"}, {eps_nchw, "eps_nchw"}, {target_means, "target_means"}, {tab_a, "tab_a"}, {tab_b, "tab_b"},
+      {tab_c1, "tab_c1"}, {tab_c2, "tab_c2"}, {tab_sigma, "tab_sigma"}, {step2_dev, "step2_dev"}};
+  if (const int rc = check_required("consistent_step", req)) return rc;
   size_t total = 0;
   if (const int rc = check_blocks("consistent_step", batch, channels, height, width, block, &total)) return rc;
   if (!(strength > 0.f && strength <= 1.f)) { set_error("consistent_step: strength must lie in (0, 1] (got %g)", (double)strength); return SR3_E_BADARG; }
   const size_t bytes = total * sizeof(float);
   if (const int rc = check_step_history("consistent_step", tab_c3, hist_nchw, x_nchw, eps_nchw, bytes)) return rc;
   if (overlaps(x_nchw, bytes, target_means, bytes / ((size_t)block * block))) { set_error("consistent_step: target_means overlaps x_nchw"); return SR3_E_BADARG; }
-  const bool vec = (width & 3) == 0 && (block & 3) == 0 &&
-                   ((((uintptr_t)x_nchw | (uintptr_t)eps_nchw | (uintptr_t)z_nchw | (uintptr_t)hist_nchw) & 15) == 0);
+  const bool vec = (width & 3) == 0 && (block & 3) == 0 && vec16(x_nchw, eps_nchw, z_nchw, hist_nchw);
   ConsistentStep s;
   s.f = StepFuse{x_nchw, z_nchw, StepTables{tab_a, tab_b, tab_c1, tab_c2, tab_sigma}, step2_dev, step2_dev + 1, clip_denoised, tab_c3, hist_nchw};
   s.eps = eps_nchw; s.y = target_means; s.W = width; s.r = block; s.n = vec ? block / 4 : block; s.strength = strength;
@@ -201,14 +164,9 @@ int sr3_consistent_step(float* x_nchw, const float* eps_nchw, const float* z_nch
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (const int rc = step_copy(step2_dev, st)) return rc;
   const dim3 grid((unsigned)((s.total + 255) / 256));
-#define SR3_CS_LAUNCH(V, HI)                                                                          \
-  {                                                                                                   \
-    if (clip_denoised) hipLaunchKernelGGL((k_consistent_step<true, HI, V>), grid, dim3(256), 0, st, s); \
-    else hipLaunchKernelGGL((k_consistent_step<false, HI, V>), grid, dim3(256), 0, st, s);              \
-  }
-  if (vec) { if (hist_nchw) SR3_CS_LAUNCH(4, true) else SR3_CS_LAUNCH(4, false) }
-  else { if (hist_nchw) SR3_CS_LAUNCH(1, true) else SR3_CS_LAUNCH(1, false) }
-#undef SR3_CS_LAUNCH
+  dispatch_bools([&](auto clip, auto hist, auto v4) {
+    hipLaunchKernelGGL((k_consistent_step<clip(), hist(), v4() ? 4 : 1>), grid, dim3(256), 0, st, s);
+  }, clip_denoised != 0, hist_nchw != nullptr, vec);
   SR3_LAUNCH_CHECK("k_consistent_step");
   return SR3_OK;
 }

@@ -4,7 +4,7 @@
 //
 //   the teacher's step (n = values per image, every coefficient one fp32 per image):
 //     out    = out_c                                                one forward (out_u NULL)
-//     out    = add_rn(out_u, mul_rn(scale, sub_rn(out_c, out_u)))   two forwards, sr3_guided_step's association
+//     out    = add_rn(out_u, mul_rn(scale, sub_rn(out_c, out_u)))   two forwards: guided_out of step_tail.h, sr3_guided_step's
 //     x0     = sub_rn(mul_rn(a[b], x), mul_rn(b[b], out)) ; clamp(-1, 1) if clip_denoised        (step_x0 of sr3_common.h)
 //     x0_out <- x0 ;  x_next <- add_rn(mul_rn(c1[b], x0), mul_rn(c2[b], x))
 //
@@ -14,10 +14,11 @@
 //     x_tgt   <- add_rn(mul_rn(w1[b], x0_first), mul_rn(w2[b], x0b))
 //     eps_tgt <- sub_rn(mul_rn(s1[b], z_t), mul_rn(s2[b], x_tgt))
 //
-// Both are HBM-bound: one launch each, a thread owns four consecutive values of one image as one 16-byte access (n % 4 == 0 and every
-// image pointer 16-byte aligned) or one value; the same operations on the same operands either way, so the same bits.  No division,
-// no atomics, no fused multiply-add: the host computed every coefficient in float64 and rounded it once.
-#include "sr3_common.h"
+// Both are HBM-bound: one launch each, a thread owns four consecutive values of one image as one 16-byte access or one value (n % 4 == 0
+// and step_tail.h's vec16 / load_v / store_v); the same operations on the same operands either way, so the same bits.  No division,
+// no atomics, no fused multiply-add: the host computed every coefficient in float64 and rounded it once.  The argument checks are
+// step_tail.h's (check_required, one Buf table under check_overlaps; x_next == x is its in-place pair).
+#include "step_tail.h"
 
 namespace sr3 {
 namespace {
@@ -41,28 +42,8 @@ struct DistillArgs {
   unsigned per, total;       // values per image, of the batch
 };
 
-template <int V>
-__device__ __forceinline__ void load_v(const float* p, float (&v)[V]) {
-  if constexpr (V == 4) {
-    const f32x4 q = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = q[k];
-  } else {
-    v[0] = p[0];
-  }
-}
-template <int V>
-__device__ __forceinline__ void store_v(float* p, const float (&v)[V]) {
-  if constexpr (V == 4) {
-    const f32x4 q = {v[0], v[1], v[2], v[3]};
-    *reinterpret_cast<f32x4*>(p) = q;
-  } else {
-    p[0] = v[0];
-  }
-}
-
 __device__ __forceinline__ float teacher_x0(const DistillArgs& s, float a, float b, float x, float oc, float ou) {
-  const float out = s.out_u ? add_rn(ou, mul_rn(s.scale, sub_rn(oc, ou))) : oc;
+  const float out = guided_out(s.out_u != nullptr, s.scale, oc, ou);
   float x0 = sub_rn(mul_rn(a, x), mul_rn(b, out));
   if (s.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
   return x0;
@@ -110,28 +91,6 @@ __global__ __launch_bounds__(256) void k_distill_target(DistillArgs s) {
   store_v<V>(s.o2 + e, et);
 }
 
-struct Buf { const void* p; size_t bytes; const char* name; bool written; };
-
-// the checks both entries share, before anything is launched.  bufs: every argument that is memory (a null optional one is skipped);
-// in_place: the one pair (written, read) that may be the same buffer, exactly, or -1s
-int check_distill(const char* who, const Buf* bufs, int n, int w_same, int r_same) {
-  for (int i = 0; i < n; ++i) {
-    const Buf& w = bufs[i];
-    if (!w.p || !w.written) continue;
-    for (int j = 0; j < n; ++j) {
-      const Buf& o = bufs[j];
-      if (!o.p || j == i || (o.written && j < i)) continue;              // (a pair of outputs is looked at once)
-      if (i == w_same && j == r_same && w.p == o.p) continue;
-      if (overlaps(w.p, w.bytes, o.p, o.bytes)) {
-        if (i == w_same && j == r_same) set_error("%s: %s overlaps %s partially (%s == %s is the in-place form)", who, w.name, o.name, w.name, o.name);
-        else set_error("%s: %s overlaps %s", who, w.name, o.name);
-        return SR3_E_BADARG;
-      }
-    }
-  }
-  return SR3_OK;
-}
-
 int check_sizes(const char* who, int batch, int elems_per_image, const float* out_u, float scale) {
   if (batch <= 0 || elems_per_image <= 0) { set_error("%s: batch and elems_per_image must be positive (got %d, %d)", who, batch, elems_per_image); return SR3_E_BADARG; }
   if ((size_t)batch * (size_t)elems_per_image >= ((size_t)1 << 31)) { set_error("%s: image batch too large (batch * elems_per_image >= 2^31)", who); return SR3_E_UNSUPPORTED; }
@@ -148,26 +107,21 @@ extern "C" {
 
 int sr3_teacher_step_f32(const float* x, const float* out_c, const float* out_u, float scale, const float* a, const float* b, const float* c1,
                          const float* c2, int batch, int elems_per_image, int clip_denoised, float* x_next, float* x0_out, void* stream) {
-  const struct { const void* p; const char* name; } req[] = {{x, "x"}, {out_c, "out_c"}, {a, "a"}, {b, "b"}, {c1, "c1"}, {c2, "c2"},
-      {x_next, "x_next"}, {x0_out, "x0_out"}};
-  for (const auto& q : req) {
-    if (!q.p) { set_error("teacher_step: %s is NULL", q.name); return SR3_E_BADARG; }
-  }
+  const Req req[] = {{x, "x"}, {out_c, "out_c"}, {a, "a"}, {b, "b"}, {c1, "c1"}, {c2, "c2"}, {x_next, "x_next"}, {x0_out, "x0_out"}};
+  if (const int rc = check_required("teacher_step", req)) return rc;
   if (const int rc = check_sizes("teacher_step", batch, elems_per_image, out_u, scale)) return rc;
   const size_t total = (size_t)batch * (size_t)elems_per_image, bytes = total * sizeof(float), cbytes = (size_t)batch * sizeof(float);
   const Buf bufs[] = {{x_next, bytes, "x_next", true}, {x0_out, bytes, "x0_out", true}, {x, bytes, "x", false}, {out_c, bytes, "out_c", false},
       {out_u, bytes, "out_u", false}, {a, cbytes, "a", false}, {b, cbytes, "b", false}, {c1, cbytes, "c1", false}, {c2, cbytes, "c2", false}};
-  if (const int rc = check_distill("teacher_step", bufs, 9, 0, 2)) return rc;
-  const bool vec = (elems_per_image & 3) == 0 &&
-                   ((((uintptr_t)x | (uintptr_t)out_c | (uintptr_t)out_u | (uintptr_t)x_next | (uintptr_t)x0_out) & 15) == 0);
+  if (const int rc = check_overlaps("teacher_step", bufs, -1, 0, 2)) return rc;
+  const bool vec = (elems_per_image & 3) == 0 && vec16(x, out_c, out_u, x_next, x0_out);
   DistillArgs s = {};
   s.x = x; s.out_c = out_c; s.out_u = out_u; s.scale = scale; s.a = a; s.b = b; s.p1 = c1; s.p2 = c2;
   s.o1 = x_next; s.o2 = x0_out; s.clip = clip_denoised != 0; s.per = (unsigned)elems_per_image; s.total = (unsigned)total;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned items = (unsigned)(vec ? total / 4 : total);
   const dim3 grid((items + 255) / 256);
-  if (vec) hipLaunchKernelGGL(k_teacher_step<4>, grid, dim3(256), 0, st, s);
-  else hipLaunchKernelGGL(k_teacher_step<1>, grid, dim3(256), 0, st, s);
+  dispatch_bools([&](auto v4) { hipLaunchKernelGGL((k_teacher_step<v4() ? 4 : 1>), grid, dim3(256), 0, st, s); }, vec);
   SR3_LAUNCH_CHECK("k_teacher_step");
   return SR3_OK;
 }
@@ -175,19 +129,16 @@ int sr3_teacher_step_f32(const float* x, const float* out_c, const float* out_u,
 int sr3_distill_target_f32(const float* z_t, const float* x_mid, const float* out_c, const float* out_u, float scale, const float* x0_first,
                            const float* a, const float* b, const float* w1, const float* w2, const float* s1, const float* s2, int batch,
                            int elems_per_image, int clip_denoised, float* x_tgt, float* eps_tgt, void* stream) {
-  const struct { const void* p; const char* name; } req[] = {{z_t, "z_t"}, {x_mid, "x_mid"}, {out_c, "out_c"}, {x0_first, "x0_first"},
-      {a, "a"}, {b, "b"}, {w1, "w1"}, {w2, "w2"}, {s1, "s1"}, {s2, "s2"}, {x_tgt, "x_tgt"}, {eps_tgt, "eps_tgt"}};
-  for (const auto& q : req) {
-    if (!q.p) { set_error("distill_target: %s is NULL", q.name); return SR3_E_BADARG; }
-  }
+  const Req req[] = {{z_t, "z_t"}, {x_mid, "x_mid"}, {out_c, "out_c"}, {x0_first, "x0_first"}, {a, "a"}, {b, "b"}, {w1, "w1"}, {w2, "w2"},
+      {s1, "s1"}, {s2, "s2"}, {x_tgt, "x_tgt"}, {eps_tgt, "eps_tgt"}};
+  if (const int rc = check_required("distill_target", req)) return rc;
   if (const int rc = check_sizes("distill_target", batch, elems_per_image, out_u, scale)) return rc;
   const size_t total = (size_t)batch * (size_t)elems_per_image, bytes = total * sizeof(float), cbytes = (size_t)batch * sizeof(float);
   const Buf bufs[] = {{x_tgt, bytes, "x_tgt", true}, {eps_tgt, bytes, "eps_tgt", true}, {z_t, bytes, "z_t", false}, {x_mid, bytes, "x_mid", false},
       {out_c, bytes, "out_c", false}, {out_u, bytes, "out_u", false}, {x0_first, bytes, "x0_first", false}, {a, cbytes, "a", false},
       {b, cbytes, "b", false}, {w1, cbytes, "w1", false}, {w2, cbytes, "w2", false}, {s1, cbytes, "s1", false}, {s2, cbytes, "s2", false}};
-  if (const int rc = check_distill("distill_target", bufs, 13, -1, -1)) return rc;
-  const bool vec = (elems_per_image & 3) == 0 && ((((uintptr_t)z_t | (uintptr_t)x_mid | (uintptr_t)out_c | (uintptr_t)out_u | (uintptr_t)x0_first |
-                                                    (uintptr_t)x_tgt | (uintptr_t)eps_tgt) & 15) == 0);
+  if (const int rc = check_overlaps("distill_target", bufs)) return rc;
+  const bool vec = (elems_per_image & 3) == 0 && vec16(z_t, x_mid, out_c, out_u, x0_first, x_tgt, eps_tgt);
   DistillArgs s = {};
   s.x = x_mid; s.out_c = out_c; s.out_u = out_u; s.scale = scale; s.a = a; s.b = b; s.p1 = w1; s.p2 = w2;
   s.z_t = z_t; s.x0_first = x0_first; s.s1 = s1; s.s2 = s2;
@@ -195,8 +146,7 @@ int sr3_distill_target_f32(const float* z_t, const float* x_mid, const float* ou
   hipStream_t st = static_cast<hipStream_t>(stream);
   const unsigned items = (unsigned)(vec ? total / 4 : total);
   const dim3 grid((items + 255) / 256);
-  if (vec) hipLaunchKernelGGL(k_distill_target<4>, grid, dim3(256), 0, st, s);
-  else hipLaunchKernelGGL(k_distill_target<1>, grid, dim3(256), 0, st, s);
+  dispatch_bools([&](auto v4) { hipLaunchKernelGGL((k_distill_target<v4() ? 4 : 1>), grid, dim3(256), 0, st, s); }, vec);
   SR3_LAUNCH_CHECK("k_distill_target");
   return SR3_OK;
 }

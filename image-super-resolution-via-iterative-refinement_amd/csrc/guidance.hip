@@ -26,7 +26,7 @@
 // chunk in LDS, the non-empty bins added to the image's global histogram; each workgroup first chooses the earlier passes' bins from
 // the global histograms the earlier launches completed: 2048 + 1024 counters out of the L2, no hand-off inside a launch), k_q_out.
 // A NaN is a key above inf's; every index is a masked digit, so whatever the values are the kernels stay inside their buffers.
-#include "sr3_common.h"
+#include "step_tail.h"
 
 namespace sr3 {
 namespace {
@@ -273,28 +273,7 @@ struct GuidedStep {
 };
 
 __device__ __forceinline__ float guided_x0(const GuidedStep& s, const StepCoef& cf, float x, float oc, float ou) {
-  const float out = s.out_u ? add_rn(ou, mul_rn(s.scale, sub_rn(oc, ou))) : oc;
-  return step_x0(cf, false, x, out);
-}
-
-template <int V>
-__device__ __forceinline__ void load_v(const float* p, float (&v)[V]) {
-  if constexpr (V == 4) {
-    const f32x4 q = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = q[k];
-  } else {
-    v[0] = p[0];
-  }
-}
-template <int V>
-__device__ __forceinline__ void store_v(float* p, const float (&v)[V]) {
-  if constexpr (V == 4) {
-    const f32x4 q = {v[0], v[1], v[2], v[3]};
-    *reinterpret_cast<f32x4*>(p) = q;
-  } else {
-    p[0] = v[0];
-  }
+  return step_x0(cf, false, x, guided_out(s.out_u != nullptr, s.scale, oc, ou));
 }
 
 // x0 of the guided output into the scratch (mode 2: the select needs the whole image's x0 before any of it is thresholded)
@@ -313,19 +292,17 @@ __global__ __launch_bounds__(256) void k_guided_x0(GuidedStep s) {
   store_v<V>(s.x0 + e, ov);
 }
 
-// the rule for x0 and the posterior mix; the last kernel of the step: the only one that writes the counter's slot 1
+// the rule for x0 and the posterior mix; the last kernel of the step: the only one that writes the counter's slot 1 (tail_begin)
 template <bool HIST, int V>
 __global__ __launch_bounds__(256) void k_guided_mix(GuidedStep s) {
   const StepFuse& f = s.f;
-  const int j = f.step_cur[0];
-  if (blockIdx.x == 0 && threadIdx.x == 0) f.step_next[0] = j - 1;      // (nobody reads this slot before the next step's first kernel)
-  const StepCoef cf = load_step_coef<HIST>(f.tb, f.c3, j);
+  const StepCoef cf = tail_begin<HIST>(f, blockIdx.x == 0 && threadIdx.x == 0);
   const unsigned e = (blockIdx.x * 256u + threadIdx.x) * V;
   if (e >= s.total) return;
   const unsigned b = e / s.per;                                         // (V = 4: per % 4 == 0, a quad lies in one image)
   const float sb = s.mode == 2 ? fmaxf(1.f, s.q[b]) : 1.f;
   if (s.thr && e == b * s.per) s.thr[b] = sb;
-  float xv[V], x0[V], zv[V] = {}, hv[V] = {};
+  float xv[V], x0[V], zv[V], hv[V];
   load_v<V>(f.x + e, xv);
   if (s.mode == 2) {
     load_v<V>(s.x0 + e, x0);
@@ -341,12 +318,8 @@ __global__ __launch_bounds__(256) void k_guided_mix(GuidedStep s) {
       if (s.mode == 1) x0[k] = fminf(fmaxf(x0[k], -1.f), 1.f);
     }
   }
-  if (f.z) load_v<V>(f.z + e, zv);
-  if (HIST) load_v<V>(f.hist + e, hv);
-#pragma unroll
-  for (int k = 0; k < V; ++k) xv[k] = step_mix<HIST>(cf, x0[k], xv[k], zv[k], hv[k]);
-  store_v<V>(f.x + e, xv);
-  if (HIST) store_v<V>(f.hist + e, hv);
+  tail_load_zh<HIST, V>(f, e, zv, hv);
+  tail_mix_store<HIST, V>(f, cf, e, x0, xv, zv, hv);
 }
 
 }  // namespace
@@ -366,13 +339,14 @@ int sr3_cond_drop_f32(const float* src, const int* keep_dev, int batch, int elem
   if (dst != src && overlaps(src, total * sizeof(float), dst, total * sizeof(float))) { set_error("cond_drop: dst overlaps src partially (dst == src is the in-place form)"); return SR3_E_BADARG; }
   if (overlaps(keep_dev, (size_t)batch * sizeof(int), dst, total * sizeof(float))) { set_error("cond_drop: dst overlaps keep_dev"); return SR3_E_BADARG; }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool vec = (elems_per_image & 3) == 0 && ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0);
+  const bool vec = (elems_per_image & 3) == 0 && vec16(src, dst);
   const unsigned items = (unsigned)(vec ? total / 4 : total);
   const dim3 grid((items + 255) / 256);
   const unsigned* s = reinterpret_cast<const unsigned*>(src);
   unsigned* d = reinterpret_cast<unsigned*>(dst);
-  if (vec) hipLaunchKernelGGL(k_cond_drop<4>, grid, dim3(256), 0, st, s, keep_dev, (unsigned)elems_per_image, d, (unsigned)total);
-  else hipLaunchKernelGGL(k_cond_drop<1>, grid, dim3(256), 0, st, s, keep_dev, (unsigned)elems_per_image, d, (unsigned)total);
+  dispatch_bools([&](auto v4) {
+    hipLaunchKernelGGL((k_cond_drop<v4() ? 4 : 1>), grid, dim3(256), 0, st, s, keep_dev, (unsigned)elems_per_image, d, (unsigned)total);
+  }, vec);
   SR3_LAUNCH_CHECK("k_cond_drop");
   return SR3_OK;
 }
@@ -400,44 +374,30 @@ int sr3_guided_step(float* x_nchw, const float* out_c, const float* out_u, float
                     int height, int width, const float* tab_a, const float* tab_b, const float* tab_c1, const float* tab_c2,
                     const float* tab_sigma, const float* tab_c3, float* hist_nchw, int* step2_dev, int mode, int rank_lo, double frac,
                     float* x0_scratch, void* q_scratch, size_t q_scratch_bytes, float* thr_out_dev, void* stream) {
-  const struct { const void* p; const char* name; } req[] = {{x_nchw, "x_nchw"}, {out_c, "out_c"}, {tab_a, "tab_a"}, {tab_b, "tab_b"},
-      {tab_c1, "tab_c1"}, {tab_c2, "tab_c2"}, {tab_sigma, "tab_sigma"}, {step2_dev, "step2_dev"}};
-  for (const auto& q : req) {
-    if (!q.p) { set_error("guided_step: %s is NULL", q.name); return SR3_E_BADARG; }
-  }
-  if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0) {
-    set_error("guided_step: batch, channels, height and width must be positive (got %d, %d, %d, %d)", batch, channels, height, width);
-    return SR3_E_BADARG;
-  }
+  const char* who = "guided_step";
+  const Req req[] = {{x_nchw, "x_nchw"}, {out_c, "out_c"}, {tab_a, "tab_a"}, {tab_b, "tab_b"}, {tab_c1, "tab_c1"}, {tab_c2, "tab_c2"},
+      {tab_sigma, "tab_sigma"}, {step2_dev, "step2_dev"}};
+  if (const int rc = check_required(who, req)) return rc;
+  if (const int rc = check_image_dims(who, batch, channels, height, width)) return rc;
   const size_t per = (size_t)channels * height * width, total = (size_t)batch * per;
-  if (per >= ((size_t)1 << 31) || total >= ((size_t)1 << 31)) { set_error("guided_step: image batch too large (batch * channels * height * width >= 2^31)"); return SR3_E_UNSUPPORTED; }
-  if (mode < 0 || mode > 2) { set_error("guided_step: mode must be 0 (none), 1 (static) or 2 (dynamic) (got %d)", mode); return SR3_E_BADARG; }
-  if (!(scale - scale == 0.f)) { set_error("guided_step: scale must be finite (got %g)", (double)scale); return SR3_E_BADARG; }
+  if (const int rc = check_image_limit(who, total)) return rc;
+  if (mode < 0 || mode > 2) { set_error("%s: mode must be 0 (none), 1 (static) or 2 (dynamic) (got %d)", who, mode); return SR3_E_BADARG; }
+  if (!(scale - scale == 0.f)) { set_error("%s: scale must be finite (got %g)", who, (double)scale); return SR3_E_BADARG; }
   const size_t bytes = total * sizeof(float);
   if (mode == 2) {
-    if (!x0_scratch) { set_error("guided_step: x0_scratch is NULL (mode 2 needs it)"); return SR3_E_BADARG; }
-    if (const int rc = check_quantile("guided_step", batch, (int)per, rank_lo, frac, q_scratch, q_scratch_bytes)) return rc;
+    if (!x0_scratch) { set_error("%s: x0_scratch is NULL (mode 2 needs it)", who); return SR3_E_BADARG; }
+    if (const int rc = check_quantile(who, batch, (int)per, rank_lo, frac, q_scratch, q_scratch_bytes)) return rc;
   }
-  if (const int rc = check_step_history("guided_step", tab_c3, hist_nchw, x_nchw, out_c, bytes)) return rc;
+  if (const int rc = check_step_history(who, tab_c3, hist_nchw, x_nchw, out_c, bytes)) return rc;
   // what the step writes (x, the history, the two scratch buffers, the thresholds) shares no byte with anything else it touches
   const size_t qbytes = q_scratch_words(batch) * sizeof(unsigned);
-  const struct { const void* p; size_t bytes; const char* name; bool written; } buf[] = {
+  const Buf buf[] = {
       {x_nchw, bytes, "x_nchw", true}, {hist_nchw, bytes, "hist_nchw", true}, {mode == 2 ? x0_scratch : nullptr, bytes, "x0_scratch", true},
       {mode == 2 ? q_scratch : nullptr, qbytes, "q_scratch", true}, {thr_out_dev, (size_t)batch * sizeof(float), "thr_out_dev", true},
       {out_c, bytes, "out_c", false}, {out_u, bytes, "out_u", false}, {z_nchw, bytes, "z_nchw", false},
       {step2_dev, 2 * sizeof(int), "step2_dev", true}};
-  for (const auto& w : buf) {
-    if (!w.p || !w.written) continue;
-    for (const auto& o : buf) {
-      if (o.p && &o != &w && overlaps(w.p, w.bytes, o.p, o.bytes)) {
-        const bool w_names = &w != &buf[0];      // (name the other argument where one of the two is x itself)
-        set_error("guided_step: %s overlaps %s", w_names ? w.name : o.name, w_names ? o.name : w.name);
-        return SR3_E_BADARG;
-      }
-    }
-  }
-  const bool vec = (width & 3) == 0 && ((((uintptr_t)x_nchw | (uintptr_t)out_c | (uintptr_t)out_u | (uintptr_t)z_nchw | (uintptr_t)hist_nchw |
-                                          (uintptr_t)(mode == 2 ? x0_scratch : nullptr)) & 15) == 0);
+  if (const int rc = check_overlaps(who, buf, 0)) return rc;      // (named_last: the other argument is named where one of the two is x itself)
+  const bool vec = (width & 3) == 0 && vec16(x_nchw, out_c, out_u, z_nchw, hist_nchw, mode == 2 ? x0_scratch : nullptr);
   GuidedStep s;
   s.f = StepFuse{x_nchw, z_nchw, StepTables{tab_a, tab_b, tab_c1, tab_c2, tab_sigma}, step2_dev, step2_dev + 1, mode == 1, tab_c3, hist_nchw};
   s.out_c = out_c; s.out_u = out_u; s.scale = scale; s.mode = mode;
@@ -449,13 +409,12 @@ int sr3_guided_step(float* x_nchw, const float* out_c, const float* out_u, float
   const unsigned items = (unsigned)(vec ? total / 4 : total);
   const dim3 grid((items + 255) / 256);
   if (mode == 2) {
-    if (vec) hipLaunchKernelGGL(k_guided_x0<4>, grid, dim3(256), 0, st, s);
-    else hipLaunchKernelGGL(k_guided_x0<1>, grid, dim3(256), 0, st, s);
+    dispatch_bools([&](auto v4) { hipLaunchKernelGGL((k_guided_x0<v4() ? 4 : 1>), grid, dim3(256), 0, st, s); }, vec);
     SR3_LAUNCH_CHECK("k_guided_x0");
     if (const int rc = abs_quantile(x0_scratch, batch, (int)per, rank_lo, frac, static_cast<float*>(q_scratch), q_scratch, st)) return rc;
   }
-  if (vec) { if (hist_nchw) hipLaunchKernelGGL((k_guided_mix<true, 4>), grid, dim3(256), 0, st, s); else hipLaunchKernelGGL((k_guided_mix<false, 4>), grid, dim3(256), 0, st, s); }
-  else { if (hist_nchw) hipLaunchKernelGGL((k_guided_mix<true, 1>), grid, dim3(256), 0, st, s); else hipLaunchKernelGGL((k_guided_mix<false, 1>), grid, dim3(256), 0, st, s); }
+  dispatch_bools([&](auto hist, auto v4) { hipLaunchKernelGGL((k_guided_mix<hist(), v4() ? 4 : 1>), grid, dim3(256), 0, st, s); },
+                 hist_nchw != nullptr, vec);
   SR3_LAUNCH_CHECK("k_guided_mix");
   return SR3_OK;
 }

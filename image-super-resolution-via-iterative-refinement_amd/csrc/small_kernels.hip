@@ -3,7 +3,7 @@
 // timestep embedding with every FiLM projection, and the fused reverse-step / q_sample updates.
 #include <string.h>
 
-#include "sr3_common.h"
+#include "step_tail.h"
 
 namespace sr3 {
 
@@ -768,44 +768,16 @@ __global__ __launch_bounds__(256) void k_p_sample_update(float* __restrict__ x, 
     const int b = (int)(e0 / per_image);
     const int t = step_dev ? step_dev[0] : (tps ? (int)tps[b] : step_host);
     const StepCoef cf = load_step_coef<HIST>(tb, tc3, t);
-    float xv[V], ev[V], zv[V], hv[V];
-    if constexpr (V == 4) {
-      const f32x4 xq = *reinterpret_cast<const f32x4*>(x + e0);
-      const f32x4 eq = *reinterpret_cast<const f32x4*>(eps + e0);
-      f32x4 zq = {0.f, 0.f, 0.f, 0.f}, hq = {0.f, 0.f, 0.f, 0.f};
-      if (z) zq = *reinterpret_cast<const f32x4*>(z + e0);
-      if (HIST) hq = *reinterpret_cast<const f32x4*>(hist + e0);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { xv[k] = xq[k]; ev[k] = eq[k]; zv[k] = zq[k]; hv[k] = hq[k]; }
-    } else {
-      xv[0] = x[e0]; ev[0] = eps[e0]; zv[0] = z ? z[e0] : 0.f; hv[0] = HIST ? hist[e0] : 0.f;
-    }
+    float xv[V], ev[V], zv[V] = {}, hv[V] = {};
+    load_v<V>(x + e0, xv);
+    load_v<V>(eps + e0, ev);
+    if (z) load_v<V>(z + e0, zv);
+    if (HIST) load_v<V>(hist + e0, hv);
 #pragma unroll
     for (int k = 0; k < V; ++k) xv[k] = step_tail<HIST>(cf, CLIP, xv[k], ev[k], zv[k], hv[k]);
-    if constexpr (V == 4) {
-      const f32x4 xo = {xv[0], xv[1], xv[2], xv[3]};
-      *reinterpret_cast<f32x4*>(x + e0) = xo;
-      if (HIST) {
-        const f32x4 ho = {hv[0], hv[1], hv[2], hv[3]};
-        *reinterpret_cast<f32x4*>(hist + e0) = ho;
-      }
-    } else {
-      x[e0] = xv[0];
-      if (HIST) hist[e0] = hv[0];
-    }
+    store_v<V>(x + e0, xv);
+    if (HIST) store_v<V>(hist + e0, hv);
   }
-}
-
-template <bool CLIP, bool HIST>
-static void launch_p_sample_update(float* x, const float* eps, const float* z, const float* c3, float* hist, StepTables tb, const int* step_dev,
-                                   const int64_t* t_per_sample, int step_host, int per_image, size_t elems, bool vec, hipStream_t st) {
-  const size_t total = vec ? elems / 4 : elems;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  if (vec) hipLaunchKernelGGL((k_p_sample_update<CLIP, HIST, 4>), dim3(blocks), dim3(256), 0, st, x, eps, z, tb, step_dev,
-                              t_per_sample, step_host, per_image, total, c3, hist);
-  else hipLaunchKernelGGL((k_p_sample_update<CLIP, HIST, 1>), dim3(blocks), dim3(256), 0, st, x, eps, z, tb, step_dev,
-                          t_per_sample, step_host, per_image, total, c3, hist);
 }
 
 int p_sample_update(float* x, const float* eps, const float* z, StepTables tb, const int* step_dev,
@@ -813,14 +785,14 @@ int p_sample_update(float* x, const float* eps, const float* z, StepTables tb, c
   const size_t elems = (size_t)B * per_image;
   if (const int rc = check_step_history("p_sample_update", c3, hist, x, eps, elems * sizeof(float))) return rc;
   // four elements per thread where an image is a whole number of quads and every tensor allows a 16-byte access; else one
-  const bool vec = (per_image & 3) == 0 && ((((uintptr_t)x | (uintptr_t)eps | (uintptr_t)z | (uintptr_t)hist) & 15) == 0);
-  if (clip) {
-    if (hist) launch_p_sample_update<true, true>(x, eps, z, c3, hist, tb, step_dev, t_per_sample, step_host, per_image, elems, vec, st);
-    else launch_p_sample_update<true, false>(x, eps, z, c3, hist, tb, step_dev, t_per_sample, step_host, per_image, elems, vec, st);
-  } else {
-    if (hist) launch_p_sample_update<false, true>(x, eps, z, c3, hist, tb, step_dev, t_per_sample, step_host, per_image, elems, vec, st);
-    else launch_p_sample_update<false, false>(x, eps, z, c3, hist, tb, step_dev, t_per_sample, step_host, per_image, elems, vec, st);
-  }
+  const bool vec = (per_image & 3) == 0 && vec16(x, eps, z, hist);
+  const size_t total = vec ? elems / 4 : elems;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 2048) blocks = 2048;
+  dispatch_bools([&](auto cl, auto hi, auto v4) {
+    hipLaunchKernelGGL((k_p_sample_update<cl(), hi(), v4() ? 4 : 1>), dim3(blocks), dim3(256), 0, st, x, eps, z, tb, step_dev, t_per_sample,
+                       step_host, per_image, total, c3, hist);
+  }, clip, hist != nullptr, vec);
   SR3_LAUNCH_CHECK("k_p_sample_update");
   return SR3_OK;
 }

@@ -7,7 +7,7 @@
 // positions as one 16-byte access where the address allows (checked per access, on the address itself) and as four scalar accesses
 // otherwise; the side that is always aligned (the tile batch of the gather; x, z and eps_out of the step) is always a vector access.
 // Origins read from the device arrays are clamped into [0, L - t], so no origin, however wrong, makes a kernel leave its tensors.
-#include "sr3_common.h"
+#include "step_tail.h"
 
 namespace sr3 {
 namespace {
@@ -113,15 +113,13 @@ __device__ __forceinline__ f32x4 blend_quad(const TiledStep& s, int b, int c, in
   return r;
 }
 
-// x <- p_sample update of (x, blended eps, z) at step index j = *step_cur; *step_next = j - 1.  V = 4: a thread owns four x positions
-// (W % 4 == 0, x / z / eps_out / hist 16-byte aligned); V = 1: one.  The update is step_tail (sr3_common.h), as k_p_sample_update runs
-// it; HIST: its multistep tail, the history read and written by the thread that owns the element.
+// x <- p_sample update of (x, blended eps, z) at step index j = *step_cur; *step_next = j - 1 (tail_begin).  V = 4: a thread owns four x
+// positions (W % 4 == 0, x / z / eps_out / hist 16-byte aligned); V = 1: one.  The update is step_x0 and the element I/O of step_tail.h,
+// as every tail runs them; HIST: the multistep tail.
 template <int V, bool CLIP, bool HIST>
 __global__ __launch_bounds__(256) void k_tiled_step(TiledStep s, size_t total) {
   const StepFuse& f = s.f;
-  const int j = f.step_cur[0];
-  if (blockIdx.x == 0 && threadIdx.x == 0) f.step_next[0] = j - 1;      // (nobody reads this slot before the next step's first kernel)
-  const StepCoef cf = load_step_coef<HIST>(f.tb, f.c3, j);
+  const StepCoef cf = tail_begin<HIST>(f, blockIdx.x == 0 && threadIdx.x == 0);
   const int wv = s.W / V;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int x0 = (int)(i % wv) * V;
@@ -132,7 +130,7 @@ __global__ __launch_bounds__(256) void k_tiled_step(TiledStep s, size_t total) {
     int iy0, iy1, ix0, ix1;
     cover(s.oy, s.ny, s.H, s.th, y, iy0, iy1);
     cover(s.ox, s.nx, s.W, s.tw, x0, ix0, ix1);
-    float ev[V], xv[V], zv[V], hv[V];
+    float ev[V], xv[V], zv[V], hv[V], x0v[V];
     if constexpr (V == 4) {
       int jx0, jx1;
       cover(s.ox, s.nx, s.W, s.tw, x0 + 3, jx0, jx1);
@@ -148,40 +146,14 @@ __global__ __launch_bounds__(256) void k_tiled_step(TiledStep s, size_t total) {
           ev[k] = blend_pixel(s, b, c, y, x0 + k, iy0, iy1, jx0, jx1);
         }
       }
-      const f32x4 xq = *reinterpret_cast<const f32x4*>(f.x + e0);
-      f32x4 zq = {0.f, 0.f, 0.f, 0.f};
-      if (f.z) zq = *reinterpret_cast<const f32x4*>(f.z + e0);
-#pragma unroll
-      for (int k = 0; k < V; ++k) { xv[k] = xq[k]; zv[k] = zq[k]; }
-      if (HIST) {
-        const f32x4 hq = *reinterpret_cast<const f32x4*>(f.hist + e0);
-#pragma unroll
-        for (int k = 0; k < V; ++k) hv[k] = hq[k];
-      }
     } else {
       ev[0] = blend_pixel(s, b, c, y, x0, iy0, iy1, ix0, ix1);
-      xv[0] = f.x[e0];
-      zv[0] = f.z ? f.z[e0] : 0.f;
-      if (HIST) hv[0] = f.hist[e0];
     }
+    tail_load<HIST, V>(f, e0, xv, zv, hv);
 #pragma unroll
-    for (int k = 0; k < V; ++k) xv[k] = step_tail<HIST>(cf, CLIP, xv[k], ev[k], zv[k], hv[k]);
-    if constexpr (V == 4) {
-      const f32x4 o = {xv[0], xv[1], xv[2], xv[3]};
-      *reinterpret_cast<f32x4*>(f.x + e0) = o;
-      if (HIST) {
-        const f32x4 ho = {hv[0], hv[1], hv[2], hv[3]};
-        *reinterpret_cast<f32x4*>(f.hist + e0) = ho;
-      }
-      if (s.eps_out) {
-        const f32x4 eo = {ev[0], ev[1], ev[2], ev[3]};
-        *reinterpret_cast<f32x4*>(s.eps_out + e0) = eo;
-      }
-    } else {
-      f.x[e0] = xv[0];
-      if (HIST) f.hist[e0] = hv[0];
-      if (s.eps_out) s.eps_out[e0] = ev[0];
-    }
+    for (int k = 0; k < V; ++k) x0v[k] = step_x0(cf, CLIP, xv[k], ev[k]);
+    tail_mix_store<HIST, V>(f, cf, e0, x0v, xv, zv, hv);
+    if (s.eps_out) store_v<V>(s.eps_out + e0, ev);
   }
 }
 
@@ -259,19 +231,14 @@ int sr3_tiled_step_hist(float* x_nchw, const float* eps_tiles, int batch, int ch
   s.eps = eps_tiles; s.oy = oy_dev; s.ox = ox_dev; s.wy = wy_dev; s.wx = wx_dev; s.eps_out = eps_out_nchw;
   s.C = channels; s.H = height; s.W = width; s.ny = ny; s.nx = nx; s.th = th; s.tw = tw;
   const bool vec = (width & 3) == 0;
-  if (vec && (((uintptr_t)x_nchw & 15) || ((uintptr_t)z_nchw & 15) || ((uintptr_t)eps_out_nchw & 15) || ((uintptr_t)hist_nchw & 15))) { set_error("tiled_step: misaligned pointer (x, z, eps_out, hist: 16 B)"); return SR3_E_ALIGN; }
+  if (vec && !vec16(x_nchw, z_nchw, eps_out_nchw, hist_nchw)) { set_error("tiled_step: misaligned pointer (x, z, eps_out, hist: 16 B)"); return SR3_E_ALIGN; }
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (const int rc = step_copy(step2_dev, st)) return rc;
   const size_t work = vec ? total / 4 : total;
   const dim3 grid(grid_for(work));
-#define SR3_TS_LAUNCH(V, HI)                                                                            \
-  {                                                                                                     \
-    if (clip_denoised) hipLaunchKernelGGL((k_tiled_step<V, true, HI>), grid, dim3(256), 0, st, s, work); \
-    else hipLaunchKernelGGL((k_tiled_step<V, false, HI>), grid, dim3(256), 0, st, s, work);              \
-  }
-  if (vec) { if (hist_nchw) SR3_TS_LAUNCH(4, true) else SR3_TS_LAUNCH(4, false) }
-  else { if (hist_nchw) SR3_TS_LAUNCH(1, true) else SR3_TS_LAUNCH(1, false) }
-#undef SR3_TS_LAUNCH
+  dispatch_bools([&](auto v4, auto clip, auto hist) {
+    hipLaunchKernelGGL((k_tiled_step<v4() ? 4 : 1, clip(), hist()>), grid, dim3(256), 0, st, s, work);
+  }, vec, clip_denoised != 0, hist_nchw != nullptr);
   SR3_LAUNCH_CHECK("k_tiled_step");
   return SR3_OK;
 }

@@ -27,22 +27,19 @@ Objective (engine extension, `"prediction": "eps" | "v" | "x0"` and `"loss": {"t
 target coefficients and weights to sr3_train_step_ex (`prediction_coefs`, `loss_weights`); sampling changes the two tables a, b of the
 step tail's x0c = clip(a x - b out) and nothing else, in every loop.
 
-Consistency (engine extension, `"consistency": {"block": 8, "strength": 1.0}` next to "sampler" / "tiling", or `set_consistency`): every
-step shifts each block x block block of the predicted x0 so that its mean is the target's -- the block means of the conditioning image,
-or `consistency_target=` -- before the posterior mix (the range / null-space projection for an average pool).  Per step: UNet forward
-with eps stored, then sr3_consistent_step (projection + p_sample update + counter decrement) in place of the fused tail.
-
-Guidance (engine extension, `"guidance": {"scale": 1.5, "threshold": "dynamic", "percentile": 0.995}` next to "sampler", or `set_guidance`;
-`"cond_drop": p` in model.diffusion, or `set_cond_drop`, trains a model for it): classifier-free guidance -- two UNet forwards per step,
-on the conditioning image and on a zero one, combined as out_u + scale (out_c - out_u) before x0 is formed -- and what is done to x0
-where it leaves [-1, 1]: the static clamp, nothing, or dynamic thresholding (each image's x0 divided by its own percentile of |x0|).
-Per step: the forward(s) with the output stored, then sr3_guided_step in place of the fused tail.
-
-Back-projection (engine extension, `"backprojection": {"scale": 8, "iterations": 2, "strength": 1.0, "resample": "bicubic"}` next to
-"sampler", or `set_backprojection`): every step runs `iterations` rounds of x0 <- x0 + strength * U(y - D(x0)) on the predicted x0 before
-the posterior mix, D / U = Pillow's antialiased resize down / up by `scale` (the resize the datasets are made with; `resample_tables`
-makes its tables on the host), y = the LR image (`backprojection_target=`) or the down-sampled conditioning image.  Per step: UNet
-forward with eps stored, then sr3_backproject_step in place of the fused tail.  A contraction, not a projection.
+Rules on x0 (engine extensions, keys next to "sampler" / "tiling" or the setters; sr3_hip/x0_rules.py holds each rule once): what is done
+to the predicted x0 before the posterior mix.  Per step: UNet forward with the output stored, then the rule's entry in place of the fused
+tail.  The rules exclude one another and tiling -- each owns the whole tail of a step.
+  `"consistency": {"block": 8, "strength": 1.0}` / `set_consistency`: every step shifts each block x block block of x0 so that its mean is
+    the target's -- the block means of the conditioning image, or `consistency_target=` (the range / null-space projection for an
+    average pool; sr3_consistent_step).
+  `"guidance": {"scale": 1.5, "threshold": "dynamic", "percentile": 0.995}` / `set_guidance` (`"cond_drop": p` in model.diffusion, or
+    `set_cond_drop`, trains a model for it): classifier-free guidance -- two forwards per step, on the conditioning image and on a zero
+    one, combined as out_u + scale (out_c - out_u) before x0 is formed -- and what is done to x0 where it leaves [-1, 1]: the static
+    clamp, nothing, or dynamic thresholding (each image's x0 divided by its own percentile of |x0|; sr3_guided_step).
+  `"backprojection": {"scale": 8, "iterations": 2, "strength": 1.0, "resample": "bicubic"}` / `set_backprojection`: `iterations` rounds of
+    x0 <- x0 + strength * U(y - D(x0)), D / U = Pillow's antialiased resize down / up by `scale` (`resample_tables`), y = the LR image
+    (`backprojection_target=`) or the down-sampled conditioning image (sr3_backproject_step).  A contraction, not a projection.
 """
 import ctypes as C
 
@@ -53,6 +50,9 @@ from torch import nn
 from . import engine as E
 from . import lib as L
 from . import tiling as TL
+from . import x0_rules as X
+from .x0_rules import (BACKPROJECTION_KEYS, CONSISTENCY_BLOCKS, RESAMPLES, THRESHOLDS, backprojection_error, block_means,      # noqa: F401
+                       quantile_rank, resample_f32, resample_tables)                                                          # (their old home)
 
 
 def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2, cosine_s=8e-3):
@@ -184,128 +184,6 @@ def _positive(name, v):
     if isinstance(v, bool) or not np.isfinite(f) or not f > 0.0:
         raise ValueError('%s must be finite and > 0 (got %r)' % (name, v))
     return f
-
-
-CONSISTENCY_BLOCKS = (2, 4, 8, 16, 32)      # what sr3_consistent_step takes
-
-
-def block_means(x, block):
-    """The means of the block x block blocks of x [B, C, H, W] (a contiguous fp32 GPU tensor): [B, C, H / block, W / block], each summed
-    in double and rounded once (sr3_block_mean_f32).  max |block_means(SR, r) - block_means(cond, r)| is the consistency error of a
-    result."""
-    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
-        raise L.Sr3Error('block_means needs a (B, C, H, W) fp32 GPU tensor; there is no CPU fallback')
-    x = x.contiguous()
-    B, Cc, H, W = x.shape
-    block = int(block)
-    out = torch.empty((B, Cc, H // max(block, 1), W // max(block, 1)), device=x.device)
-    L.check(L.load().sr3_block_mean_f32(L.ptr(x), B, Cc, H, W, block, L.ptr(out), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
-    return out
-
-
-RESAMPLES = ('bicubic', 'bilinear')      # the filters of resample_tables: Pillow's BICUBIC (a = -0.5, support 2) and BILINEAR (support 1)
-BACKPROJECTION_KEYS = ('scale', 'iterations', 'strength', 'resample')
-
-
-def _resample_filter(resample):
-    if resample == 'bicubic':
-        def f(x):
-            x = np.abs(x)
-            a = -0.5
-            return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0,
-                            np.where(x < 2.0, (((x - 5.0) * x + 8.0) * x - 4.0) * a, 0.0))
-        return f, 2.0
-    if resample == 'bilinear':
-        return (lambda x: np.where(np.abs(x) < 1.0, 1.0 - np.abs(x), 0.0)), 1.0
-    raise ValueError('resample must be one of %s (got %r)' % (', '.join(repr(k) for k in RESAMPLES), resample))
-
-
-def resample_tables(in_size, out_size, resample='bicubic'):
-    """The banded matrix of Pillow's resize of one axis from in_size to out_size elements (Image.resize with BICUBIC / BILINEAR; its
-    precompute_coeffs rule, evaluated in float64): the filter's support scaled by max(in / out, 1) (the antialiasing of a down-sample),
-    output xx centred at (xx + 0.5) in / out, taps xmin = max(int(c - support + 0.5), 0) up to xmax = min(int(c + support + 0.5), in),
-    weights normalised by their sum.  -> (bounds int32 [out, 2] = (first tap, count), weights fp32 [out, ksize], rounded once from
-    float64 and zero past the count): what sr3_resample_f32 / sr3_backproject_step take.  Pure NumPy, no device."""
-    for name, v in (('in_size', in_size), ('out_size', out_size)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
-            raise ValueError('resample_tables: %s must be a positive integer (got %r)' % (name, v))
-    filt, support = _resample_filter(resample)
-    in_size, out_size = int(in_size), int(out_size)
-    scale = np.float64(in_size) / np.float64(out_size)
-    fscale = max(scale, np.float64(1.0))
-    support = np.float64(support) * fscale
-    ksize = int(np.ceil(support)) * 2 + 1
-    bounds = np.zeros((out_size, 2), dtype=np.int32)
-    w64 = np.zeros((out_size, ksize), dtype=np.float64)
-    for xx in range(out_size):
-        c = (np.float64(xx) + 0.5) * scale
-        xmin = max(int(c - support + 0.5), 0)
-        xmax = min(int(c + support + 0.5), in_size)
-        n = xmax - xmin
-        w = filt((np.arange(n, dtype=np.float64) + xmin - c + 0.5) / fscale)
-        s = w.sum()
-        if s != 0.0:
-            w = w / s
-        bounds[xx] = (xmin, n)
-        w64[xx, :n] = w
-    return bounds, w64.astype(np.float32)      # (ksize = Pillow's: 2 ceil(support) + 1, an upper bound of every row's count)
-
-
-def _resample_device_tables(in_hw, out_hw, resample, dev):
-    """the four tables of one 2-D resample on the device: (bounds_h, weights_h, bounds_v, weights_v); horizontal = the width axis"""
-    out = []
-    for i, o in ((in_hw[1], out_hw[1]), (in_hw[0], out_hw[0])):
-        b, w = resample_tables(i, o, resample)
-        out += [torch.from_numpy(b).to(dev), torch.from_numpy(w).to(dev)]
-    return tuple(out)
-
-
-def resample_f32(x, out_hw, resample='bicubic', tables=None):
-    """Pillow's resize of the planes of x [B, C, H, W] (a contiguous fp32 GPU tensor) to out_hw = (OH, OW), in fp32 on the device
-    (sr3_resample_f32; the tables of `resample_tables`, or `tables` = the four device tensors made for this geometry before)."""
-    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
-        raise L.Sr3Error('resample_f32 needs a (B, C, H, W) fp32 GPU tensor; there is no CPU fallback')
-    x = x.contiguous()
-    B, Cc, H, W = x.shape
-    OH, OW = int(out_hw[0]), int(out_hw[1])
-    bh, wh, bv, wv = tables if tables is not None else _resample_device_tables((H, W), (OH, OW), resample, x.device)
-    out = torch.empty((B, Cc, OH, OW), device=x.device)
-    tmp = torch.empty((B, Cc, H, OW), device=x.device)
-    L.check(L.load().sr3_resample_f32(L.ptr(x), B * Cc, H, W, L.ptr(out), OH, OW, L.ptr(bh), L.ptr(wh), wh.shape[1], L.ptr(bv), L.ptr(wv),
-                                      wv.shape[1], L.ptr(tmp), None, None, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
-    return out
-
-
-def backprojection_error(sr, y_lr, scale, resample='bicubic'):
-    """max |D(sr) - y_lr|: how far the result sr [B, C, H, W] is from the LR image y_lr [B, C, H / scale, W / scale] under the dataset's
-    down-sample D (Pillow's resize, sr3_resample_f32).  fp32 GPU tensors."""
-    if not torch.is_tensor(sr) or sr.dim() != 4:
-        raise L.Sr3Error('backprojection_error needs a (B, C, H, W) fp32 GPU tensor; there is no CPU fallback')
-    scale = int(scale)
-    B, Cc, H, W = sr.shape
-    if scale < 1 or H % scale or W % scale or tuple(y_lr.shape) != (B, Cc, H // scale, W // scale):
-        raise L.Sr3Error('backprojection_error: y_lr must be a %s tensor (got %s)' % ((B, Cc, H // max(scale, 1), W // max(scale, 1)), tuple(y_lr.shape)))
-    d = resample_f32(sr, (H // scale, W // scale), resample)
-    return float((d - y_lr.to(d.device, torch.float32)).abs().max())
-
-
-THRESHOLDS = ('none', 'static', 'dynamic')      # the mode numbers of sr3_guided_step, in order
-
-
-def quantile_rank(n, p):
-    """Where the p-quantile (p in [0, 1]) of n sorted values sits, as sr3_abs_quantile_f32 takes it: (rank_lo, frac) with
-    pos = p (n - 1), rank_lo = floor(pos), frac = pos - rank_lo in [0, 1), all in float64 (numpy.quantile's 'linear' rule).  Pure, no device."""
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 1:
-        raise ValueError('quantile_rank: n must be a positive integer (got %r)' % (n,))
-    try:
-        pf = float(p)
-    except (TypeError, ValueError):
-        raise ValueError('quantile_rank: p must be a number (got %r)' % (p,))
-    if isinstance(p, bool) or not 0.0 <= pf <= 1.0:
-        raise ValueError('quantile_rank: p must lie in [0, 1] (got %r)' % (p,))
-    pos = np.float64(pf) * np.float64(int(n) - 1)
-    rank_lo = int(np.floor(pos))
-    return rank_lo, float(pos - np.float64(rank_lo))
 
 
 def prediction_coefs(kind, ca, cb):
@@ -493,9 +371,8 @@ class EngineDiffusion(nn.Module):
         self._loop_cache = {}
         self._train_tables = None
         self.tiling = None                                                       # (this phase's own "tiling" key is read below)
-        self.consistency = None                                                  # (and its "consistency" key)
-        self.guidance = None                                                     # (and its "guidance" key)
-        self.backprojection = None                                               # (and its "backprojection" key)
+        for r in X.RULES:                                                        # (and the rules' keys)
+            setattr(self, r.name, None)
         # engine key of the schedule dict: "sampler": {"type": "ddim" | "dpmpp_2m", "steps": S, "eta": e, "walk": "time" | "logsnr" | [t, ...]};
         # absent / null: the ancestral loop
         spec = schedule_opt.get('sampler') if hasattr(schedule_opt, 'get') else None
@@ -514,35 +391,10 @@ class EngineDiffusion(nn.Module):
         else:
             t = TL.parse_tiling(spec, self.denoise_fn.plan.divisor)
             self.set_tiling(t['tile'], t['overlap'], t['batch'])
-        # and: "consistency": {"block": 8, "strength": 1.0}; absent / null: the network's x0 as it is
-        spec = schedule_opt.get('consistency') if hasattr(schedule_opt, 'get') else None
-        if spec is None:
-            self.set_consistency(None)
-        else:
-            if not hasattr(spec, 'get') or spec.get('block') is None:
-                raise ValueError('consistency: "block" is required (got %r)' % (spec,))
-            self.set_consistency(spec['block'], spec.get('strength', 1.0))
-        # and: "guidance": {"scale": 1.5, "threshold": "static" | "none" | "dynamic", "percentile": 0.995}; absent / null: off
-        spec = schedule_opt.get('guidance') if hasattr(schedule_opt, 'get') else None
-        if spec is None:
-            self.set_guidance(None)
-        else:
-            if not hasattr(spec, 'get'):
-                raise ValueError('guidance: a dict of "scale", "threshold", "percentile" is expected (got %r)' % (spec,))
-            self.set_guidance(spec.get('scale', 1.0), spec.get('threshold', 'static'), spec.get('percentile', 0.995))
-        # and: "backprojection": {"scale": 8, "iterations": 2, "strength": 1.0, "resample": "bicubic"}; absent / null: off
-        spec = schedule_opt.get('backprojection') if hasattr(schedule_opt, 'get') else None
-        if spec is None:
-            self.set_backprojection(None)
-        else:
-            if not hasattr(spec, 'get') or not hasattr(spec, 'keys'):
-                raise ValueError('backprojection: a dict of "scale", "iterations", "strength", "resample" is expected (got %r)' % (spec,))
-            for k in spec.keys():
-                if k not in BACKPROJECTION_KEYS:
-                    raise ValueError('backprojection: unknown key %r (known: %s)' % (k, ', '.join('"%s"' % n for n in BACKPROJECTION_KEYS)))
-            if spec.get('scale') is None:
-                raise ValueError('backprojection: "scale" is required (got %r)' % (spec,))
-            self.set_backprojection(spec['scale'], spec.get('iterations', 1), spec.get('strength', 1.0), spec.get('resample', 'bicubic'))
+        # and the rules on x0, each under its own key (x0_rules.py: the keys, which are required, the defaults); absent / null: off
+        for r in X.RULES:
+            spec = schedule_opt.get(r.name) if hasattr(schedule_opt, 'get') else None
+            getattr(self, r.setter)(*(() if spec is None else r.parse(spec)))
 
     def set_sampler(self, steps=None, eta=0.0, *, kind='ddim', walk=None):
         """Sample in `steps` reverse steps over a strided walk through the current schedule (DDIM; eta = 0: deterministic, eta = 1 and
@@ -564,9 +416,7 @@ class EngineDiffusion(nn.Module):
                 walk = [int(v) for v in sampler_walk(self._alphas_cumprod64, steps, walk)]
             tabs = sampler_tables(self._alphas_cumprod64, steps, eta, kind=kind, walk=walk, prediction=self.prediction)
             self._check_tiled_sampler(True, getattr(self, 'tiling', None))
-            self._check_consistency(getattr(self, 'consistency', None), True, None)
-            self._check_guidance(getattr(self, 'guidance', None), True, None, None)
-            self._check_backprojection(getattr(self, 'backprojection', None), True, None, None, None)
+            self._check_rules({}, True, None)
             self.sampler = dict(type=kind, steps=int(steps), eta=float(eta))
             if kind != 'ddim' or walk != 'time':
                 self.sampler['walk'] = walk
@@ -617,9 +467,7 @@ class EngineDiffusion(nn.Module):
         else:
             t = TL.parse_tiling(dict(tile=tile, overlap=overlap, batch=batch), self.denoise_fn.plan.divisor)
             self._check_tiled_sampler(self.sampler is not None, t)
-            self._check_consistency(self.consistency, False, t)
-            self._check_guidance(self.guidance, False, t, None)
-            self._check_backprojection(self.backprojection, False, t, None, None)
+            self._check_rules({}, False, t)
             self.tiling = t
         self._loop_cache = {}
 
@@ -629,23 +477,7 @@ class EngineDiffusion(nn.Module):
         image's height and width, strength in (0, 1]) -- or, block None, go back to the network's x0 as it is.  The target is the block
         means of the conditioning image's first `channels` channels, or `consistency_target=` of p_sample_loop / super_resolution.  With
         strength 1 a chain's result has the target's block means to rounding."""
-        if block is None:
-            self.consistency = None
-        else:
-            if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or int(block) not in CONSISTENCY_BLOCKS:
-                raise ValueError('consistency block must be one of %s (got %r)' % (', '.join(str(b) for b in CONSISTENCY_BLOCKS), block))
-            try:
-                lam = float(strength)
-            except (TypeError, ValueError):
-                raise ValueError('consistency strength must be a number (got %r)' % (strength,))
-            if isinstance(strength, bool) or not (0.0 < lam <= 1.0):
-                raise ValueError('consistency strength must lie in (0, 1] (got %r)' % (strength,))
-            c = dict(block=int(block), strength=lam)
-            self._check_consistency(c, self.sampler is not None, self.tiling)
-            self._check_guidance(self.guidance, False, None, c)
-            self._check_backprojection(self.backprojection, False, None, c, None)
-            self.consistency = c
-        self._loop_cache = {}
+        self._set_rule(X.CONSISTENCY, block, strength)
 
     def set_guidance(self, scale=None, threshold=None, percentile=0.995):
         """Guided sampling: every reverse step combines the network's output on the conditioning image with its output on a zero
@@ -654,34 +486,7 @@ class EngineDiffusion(nn.Module):
         'none', or 'dynamic' -- each image's x0 clamped to +-s and divided by s, s = max(1, its `percentile`-quantile of |x0|)
         (sr3_guided_step).  scale None and threshold None: off, back to the fused step.  A model follows the scale only if it has seen
         empty conditions in training (set_cond_drop)."""
-        if scale is None and threshold is None:
-            self.guidance = None
-        else:
-            if scale is None:
-                scale = 1.0
-            if isinstance(scale, bool) or not isinstance(scale, (int, float, np.integer, np.floating)) or not np.isfinite(float(scale)):
-                raise ValueError('guidance scale must be a finite number (got %r)' % (scale,))
-            if threshold is None:
-                threshold = 'static'
-            if threshold not in THRESHOLDS:
-                raise ValueError('guidance threshold must be one of %s (got %r)' % (', '.join(repr(k) for k in THRESHOLDS), threshold))
-            if threshold == 'dynamic':
-                try:
-                    pf = float(percentile)
-                except (TypeError, ValueError):
-                    raise ValueError('guidance percentile must be a number (got %r)' % (percentile,))
-                if isinstance(percentile, bool) or not 0.0 <= pf <= 1.0:
-                    raise ValueError('guidance percentile must lie in [0, 1] (got %r)' % (percentile,))
-                percentile = pf
-            else:
-                percentile = None
-            if not self.conditional:
-                raise ValueError('guidance on an unconditional model: there is no conditioning image to drop')
-            gd = dict(scale=float(scale), threshold=threshold, percentile=percentile)
-            self._check_guidance(gd, self.sampler is not None, self.tiling, self.consistency)
-            self._check_backprojection(self.backprojection, False, None, None, gd)
-            self.guidance = gd
-        self._loop_cache = {}
+        self._set_rule(X.GUIDANCE, scale, threshold, percentile)
 
     def set_backprojection(self, scale=None, iterations=1, strength=1.0, resample='bicubic'):
         """Sample images that agree with a low-resolution target under the resize the datasets are made with: every reverse step runs
@@ -691,24 +496,14 @@ class EngineDiffusion(nn.Module):
         as it is.  iterations in 1..16, strength in (0, 2).  The target y is `backprojection_target=` of p_sample_loop /
         super_resolution (the dataset's real LR image), or D of the conditioning image's first `channels` channels.  A contraction,
         not a projection: the LR residual shrinks with every round and does not vanish."""
-        if scale is None:
-            self.backprojection = None
-        else:
-            if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or int(scale) < 2:
-                raise ValueError('backprojection scale must be an integer >= 2 (got %r)' % (scale,))
-            if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 1 <= int(iterations) <= 16:
-                raise ValueError('backprojection iterations must be an integer in 1..16 (got %r)' % (iterations,))
-            try:
-                lam = float(strength)
-            except (TypeError, ValueError):
-                raise ValueError('backprojection strength must be a number (got %r)' % (strength,))
-            if isinstance(strength, bool) or not (0.0 < lam < 2.0):
-                raise ValueError('backprojection strength must lie in (0, 2) (got %r)' % (strength,))
-            if not isinstance(resample, str) or resample not in RESAMPLES:
-                raise ValueError('backprojection resample must be one of %s (got %r)' % (', '.join(repr(k) for k in RESAMPLES), resample))
-            bp = dict(scale=int(scale), iterations=int(iterations), strength=lam, resample=resample)
-            self._check_backprojection(bp, self.sampler is not None, self.tiling, self.consistency, self.guidance)
-            self.backprojection = bp
+        self._set_rule(X.BACKPROJECTION, scale, iterations, strength, resample)
+
+    def _set_rule(self, rule, *args):
+        """the body of set_consistency / set_guidance / set_backprojection: the rule's validation, the compatibility check, the attribute"""
+        cfg = rule.validate(self, *args)
+        if cfg is not None:
+            self._check_rules({rule.name: cfg}, self.sampler is not None, self.tiling)
+        setattr(self, rule.name, cfg)
         self._loop_cache = {}
 
     def set_cond_drop(self, p=0.0):
@@ -724,47 +519,12 @@ class EngineDiffusion(nn.Module):
             raise ValueError('cond_drop on an unconditional model: there is no conditioning image to drop')
         self.cond_drop = pf
 
-    def _check_guidance(self, guidance, sampler, tiling, consistency):
-        if guidance is None:
-            return
-        if tiling is not None:
-            raise NotImplementedError('guidance with tiling: sr3_tiled_step owns the tail of a tiled step and combines no second forward; use '
-                                      'whole-image steps (set_tiling(None)) or switch guidance off (set_guidance(None))')
-        if consistency is not None:
-            raise NotImplementedError('guidance with consistency: sr3_guided_step and sr3_consistent_step each own the whole tail of a step; '
-                                      'switch one of them off (set_guidance(None) / set_consistency(None))')
-        if sampler and self.variant == 'ddpm':
-            raise NotImplementedError('guidance of the DDPM variant under a sampler (DDIM, DPM-Solver++): the forwards of a guided step '
-                                      'run through sr3_unet_forward, which has no step-index -> timestep map (t_map); use the ancestral '
-                                      'sampler (set_sampler(None)) or switch guidance off (set_guidance(None))')
-
-    def _check_consistency(self, consistency, sampler, tiling):
-        if consistency is None:
-            return
-        if tiling is not None:
-            raise NotImplementedError('consistency with tiling: sr3_tiled_step owns the tail of a tiled step and has no projection in it; use '
-                                      'whole-image steps (set_tiling(None)) or switch consistency off (set_consistency(None))')
-        if sampler and self.variant == 'ddpm':
-            raise NotImplementedError('consistency of the DDPM variant under a sampler (DDIM, DPM-Solver++): the forward of a consistent step '
-                                      'runs through sr3_unet_forward, which has no step-index -> timestep map (t_map); use the ancestral '
-                                      'sampler (set_sampler(None)) or switch consistency off (set_consistency(None))')
-
-    def _check_backprojection(self, backprojection, sampler, tiling, consistency, guidance):
-        if backprojection is None:
-            return
-        if tiling is not None:
-            raise NotImplementedError('back-projection with tiling: sr3_tiled_step owns the tail of a tiled step and has no back-projection in '
-                                      'it; use whole-image steps (set_tiling(None)) or switch back-projection off (set_backprojection(None))')
-        if consistency is not None:
-            raise NotImplementedError('back-projection with consistency: sr3_backproject_step and sr3_consistent_step each own the whole tail '
-                                      'of a step; switch one of them off (set_backprojection(None) / set_consistency(None))')
-        if guidance is not None:
-            raise NotImplementedError('back-projection with guidance: sr3_backproject_step and sr3_guided_step each own the whole tail of a '
-                                      'step; switch one of them off (set_backprojection(None) / set_guidance(None))')
-        if sampler and self.variant == 'ddpm':
-            raise NotImplementedError('back-projection of the DDPM variant under a sampler (DDIM, DPM-Solver++): the forward of a back-projected '
-                                      'step runs through sr3_unet_forward, which has no step-index -> timestep map (t_map); use the ancestral '
-                                      'sampler (set_sampler(None)) or switch back-projection off (set_backprojection(None))')
+    def _check_rules(self, new, sampler, tiling):
+        """The one compatibility check of the rules on x0 (x0_rules.check_rule: "X with tiling", "X with Y", "X of the DDPM variant under
+        a sampler"), over the settings as they are with `new` (name -> setting) in place of its names'."""
+        cfgs = dict({r.name: getattr(self, r.name, None) for r in X.RULES}, **new)
+        for r in X.RULES:
+            X.check_rule(r, cfgs, sampler and self.variant == 'ddpm', tiling)
 
     def _check_tiled_sampler(self, sampler, tiling):
         if sampler and tiling is not None and self.variant == 'ddpm':
@@ -853,14 +613,13 @@ class EngineDiffusion(nn.Module):
         # item_streams: one torch generator per image of the batch (`item_seeds` of p_sample_loop) -- the generators are
         # registered with the captured graph, so they belong to the state and are re-seeded per loop
         un = self.denoise_fn
+        cfgs = dict(consistency=consistency, guidance=guidance, backprojection=backprojection)
         key = (tuple(shape), None if cond_shape is None else tuple(cond_shape), str(dev), self.num_timesteps,
                un.weights().data_ptr(), un.freq.data_ptr(), un.plan.generation, bool(item_streams),
                None if self.sampler is None else (self.sampler['steps'], self.sampler['eta'], self.sampler['type'],
                                                   self.sampler.get('walk', 'time') if isinstance(self.sampler.get('walk', 'time'), str)
                                                   else tuple(self.sampler['walk'])),
-               None if backprojection is None else tuple(backprojection[k] for k in BACKPROJECTION_KEYS),
-               None if guidance is None else (guidance['scale'], guidance['threshold'], guidance['percentile']),
-               None if consistency is None else (consistency['block'], consistency['strength']),
+               *[r.key(cfgs[r.name]) for r in reversed(X.RULES)],      # back-projection, guidance, consistency
                None if tiles is None else tiles['key'])      # tiled loop: ((tile_h, tile_w), overlap, tile_batch); the geometry is the tile's
         st = self._loop_cache.get(key)
         if st is None:
@@ -873,14 +632,10 @@ class EngineDiffusion(nn.Module):
                 st['hist'] = torch.zeros(shape, device=dev)      # a multistep sampler: the previous step's x0 (_sample_loop zero-fills it per chain)
             if tiles is not None:
                 self._tile_buffers(st, tiles, shape, cond_shape, dev)
-            if consistency is not None:        # the target block means, and the setting the state (and its captured graph) was built for
-                r = consistency['block']
-                st['ymean'] = torch.zeros((shape[0], shape[1], shape[2] // r, shape[3] // r), device=dev)
-                st['consistency'] = dict(consistency)
-            if guidance is not None:
-                self._guidance_buffers(st, guidance, shape, cond_shape, dev)
-            if backprojection is not None:
-                self._backprojection_buffers(st, backprojection, shape, dev)
+            for r in X.RULES:                  # the setting the state (and its captured graph) was built for, and the rule's buffers
+                if cfgs[r.name] is not None:
+                    st[r.name] = dict(cfgs[r.name])
+                    r.buffers(st, st[r.name], shape, cond_shape, dev)
             # keep the states of a few image sizes alive (a folder of mixed sizes alternates between them without recapturing);
             # what was built for another arena / schedule / set of plan options can never be hit again: dropped
             # (with EMA weights the model has two arenas, and a state built on either can be hit again)
@@ -893,34 +648,6 @@ class EngineDiffusion(nn.Module):
         else:
             self._loop_cache[key] = self._loop_cache.pop(key)      # most recently used last
         return st
-
-    def _guidance_buffers(self, st, guidance, shape, cond_shape, dev):
-        """What a guided loop's state holds besides the plain loop's: the setting it (and its captured graph) was built for, the zero
-        conditioning image and the second forward's output (scale != 1 only), the per-image thresholds, and for the dynamic threshold
-        x0 of the whole batch, the select's scratch and the ranks of the percentile."""
-        st['guidance'] = dict(guidance)
-        st['thr'] = torch.zeros(shape[0], device=dev)
-        st['cond0'] = st['eps_u'] = st['x0'] = st['qscratch'] = None
-        st['rank_lo'], st['frac'] = 0, 0.0
-        if guidance['scale'] != 1.0:
-            st['cond0'] = torch.zeros(cond_shape, device=dev)
-            st['eps_u'] = torch.zeros(shape, device=dev)
-        if guidance['threshold'] == 'dynamic':
-            n = int(shape[1] * shape[2] * shape[3])
-            st['rank_lo'], st['frac'] = quantile_rank(n, guidance['percentile'])
-            st['x0'] = torch.empty(shape, device=dev)
-            st['qscratch'] = torch.empty(int(L.load().sr3_abs_quantile_scratch_bytes(shape[0], n)), dtype=torch.uint8, device=dev)
-
-    def _backprojection_buffers(self, st, bp, shape, dev):
-        """What a back-projected loop's state holds besides the plain loop's: the setting it (and its captured graph) was built for, the
-        LR target, the four tables of the down-sample and of the up-sample (`resample_tables`) and the step's scratch."""
-        B, Cc, H, W = shape
-        s = bp['scale']
-        st['backprojection'] = dict(bp)
-        st['y_lr'] = torch.zeros((B, Cc, H // s, W // s), device=dev)
-        st['bp_down'] = _resample_device_tables((H, W), (H // s, W // s), bp['resample'], dev)
-        st['bp_up'] = _resample_device_tables((H // s, W // s), (H, W), bp['resample'], dev)
-        st['bp_scratch'] = torch.empty(int(L.load().sr3_backproject_scratch_bytes(B, Cc, H, W, s)), dtype=torch.uint8, device=dev)
 
     def _tile_buffers(self, st, tiles, shape, cond_shape, dev):
         """What a tiled loop's state holds besides the whole-image tensors: the grid's origins and windows on the device, the chunk
@@ -978,12 +705,10 @@ class EngineDiffusion(nn.Module):
         sr3_reverse_step: UNet forward with the p_sample update and the counter decrement inside the output conv's kernel.  A state
         with a grid (the tiled loop) instead runs, per chunk of tiles, a gather out of the running image and one UNet forward at the
         tile geometry (level / timestep from the device counter), then the fused tail on the full image -- blend of the tiles' eps,
-        p_sample update, counter decrement (sr3_tiled_step).  A state with target block means (set_consistency) runs one UNet forward
-        that stores eps, then sr3_consistent_step: the block-mean projection of x0, the p_sample update and the counter decrement on the
-        whole image.  A multistep rule passes its c3 table and the state's history buffer along.  st['eps'] keeps the step's (blended)
-        eps for the parity checks that read it.  A state with a guidance setting (set_guidance) runs the forward with the output stored,
-        a second one on the zero conditioning image into st['eps_u'] unless the scale is 1, then sr3_guided_step: the two outputs
-        combined, the threshold rule on x0 (st['thr'] keeps each image's), the p_sample update and the counter decrement."""
+        p_sample update, counter decrement (sr3_tiled_step).  A state with a rule on x0 (x0_rules.py: set_consistency, set_guidance,
+        set_backprojection) runs one UNet forward that stores its output in st['eps'], then the rule's tail on the whole image in place
+        of the fused one.  A multistep rule passes its c3 table and the state's history buffer along.  st['eps'] keeps the step's
+        (blended) eps for the parity checks that read it."""
         tables, level, t_map, c3, noisy = rule = self._step_rule()
         st['z_used'] = noisy
         st['tables'] = rule                    # a captured graph bakes their addresses in: they live as long as the state
@@ -992,46 +717,16 @@ class EngineDiffusion(nn.Module):
         img, z = st['img'], st['z'] if noisy else None
         hist = None if c3 is None else st['hist']
         g = st.get('grid')
-        cs = st.get('consistency')
-        if cs is not None:
-            # LR-consistent step: the forward stores eps (level / timestep from the device counter, as the tiled branch's), then the
-            # tail with the block-mean projection of x0 in it (sr3_consistent_step: counter copy + one kernel)
-            assert t_map is None and g is None      # (_check_consistency refused both)
-            self.denoise_fn(img, None, cond=st['cond'], level_table=level, step_dev=st['step'][1:], out=st['eps'], ws=st['ws'])
-            B, Cc, H, W = img.shape
-            L.check(L.load().sr3_consistent_step(L.ptr(img), L.ptr(st['eps']), L.ptr(z), L.ptr(st['ymean']), B, Cc, H, W, cs['block'],
-                                                 cs['strength'], *[L.ptr(t) for t in tables], L.ptr(st['step']), 1, L.ptr(c3),
-                                                 L.ptr(hist), self._stream(img.device)))
-            return
-        gd = st.get('guidance')
-        if gd is not None:
-            # guided step: one forward per condition, the same plan, batch and workspace, one after the other (level / timestep from
-            # the device counter, which only the tail's last kernel moves), then the tail (sr3_guided_step)
-            assert t_map is None and g is None      # (_check_guidance refused both)
-            self.denoise_fn(img, None, cond=st['cond'], level_table=level, step_dev=st['step'][1:], out=st['eps'], ws=st['ws'])
-            if st['eps_u'] is not None:
-                self.denoise_fn(img, None, cond=st['cond0'], level_table=level, step_dev=st['step'][1:], out=st['eps_u'], ws=st['ws'])
-            B, Cc, H, W = img.shape
-            qs = st['qscratch']
-            L.check(L.load().sr3_guided_step(L.ptr(img), L.ptr(st['eps']), L.ptr(st['eps_u']), gd['scale'], L.ptr(z), B, Cc, H, W,
-                                             *[L.ptr(t) for t in tables], L.ptr(c3), L.ptr(hist), L.ptr(st['step']),
-                                             THRESHOLDS.index(gd['threshold']), st['rank_lo'], st['frac'], L.ptr(st['x0']), L.ptr(qs),
-                                             0 if qs is None else qs.numel(), L.ptr(st['thr']), self._stream(img.device)))
-            return
-        bp = st.get('backprojection')
-        if bp is not None:
-            # back-projected step: the forward stores eps (level / timestep from the device counter), then the tail with the
-            # back-projection rounds on x0 in it (sr3_backproject_step: counter copy + 1 + 3 K kernels)
-            assert t_map is None and g is None      # (_check_backprojection refused both)
-            self.denoise_fn(img, None, cond=st['cond'], level_table=level, step_dev=st['step'][1:], out=st['eps'], ws=st['ws'])
-            B, Cc, H, W = img.shape
-            axes = []
-            for tb in (st['bp_down'], st['bp_up']):
-                axes += [L.ptr(tb[0]), L.ptr(tb[1]), tb[1].shape[1], L.ptr(tb[2]), L.ptr(tb[3]), tb[3].shape[1]]
-            L.check(L.load().sr3_backproject_step(L.ptr(img), L.ptr(st['eps']), L.ptr(z), L.ptr(st['y_lr']), B, Cc, H, W, bp['scale'],
-                                                  bp['iterations'], bp['strength'], *axes, *[L.ptr(t) for t in tables], L.ptr(st['step']),
-                                                  1, L.ptr(c3), L.ptr(hist), L.ptr(st['bp_scratch']), st['bp_scratch'].numel(),
-                                                  self._stream(img.device)))
+        x0_rule = next((r for r in X.RULES if st.get(r.name) is not None), None)
+        if x0_rule is not None:
+            # the forward stores its output (level / timestep from the device counter, which only the tail's last kernel moves), then
+            # the rule's tail: what it does to x0, the p_sample update and the counter decrement
+            assert t_map is None and g is None      # (_check_rules refused both)
+
+            def forward(cond, out):
+                self.denoise_fn(img, None, cond=cond, level_table=level, step_dev=st['step'][1:], out=out, ws=st['ws'])
+            forward(st['cond'], st['eps'])
+            x0_rule.tail(st, st[x0_rule.name], z, tables, c3, hist, forward)
             return
         if g is None:
             self.denoise_fn.reverse_step(img, z, tables, st['step'], cond=st['cond'], level_table=level, clip_denoised=True,
@@ -1061,10 +756,8 @@ class EngineDiffusion(nn.Module):
         keep_hist = st['hist'].clone() if st.get('hist') is not None else None
         g = torch.cuda.CUDAGraph()
         cap = None
-        if st.get('backprojection') is not None:
-            # a back-projected state warms up on the stream its capture runs on (torch's shared capture stream): it takes no stream
-            # of its own out of the pool, so which pool stream -- and with it which hardware queue -- anything created later in
-            # the process gets does not depend on how many such states were captured before
+        if any(r.warm_on_capture_stream and st.get(r.name) is not None for r in X.RULES):
+            # the warm-up runs on the stream the capture runs on (torch's shared capture stream): see x0_rules.Backprojection
             cap = torch.cuda.graph(g)
             side = cap.capture_stream
         else:
@@ -1127,22 +820,15 @@ class EngineDiffusion(nn.Module):
         set_consistency every step is an LR-consistent one (`_one_step`), towards the block means of the conditioning image or
         `consistency_target`.  Under set_guidance every step is a guided one.  Under set_backprojection every step is a back-projected
         one, towards `backprojection_target` or the down-sampled conditioning image."""
-        cs = self.consistency
-        if cs is None and consistency_target is not None:
-            raise ValueError('consistency_target is given but consistency is off (set_consistency / the "consistency" key)')
-        self._check_consistency(cs, self.sampler is not None, tiling)
-        gd = self.guidance
-        self._check_guidance(gd, self.sampler is not None, tiling, cs)
-        if cs is not None and not self.conditional and consistency_target is None:
-            raise NotImplementedError('consistency on an unconditional model needs consistency_target=: there is no conditioning image to '
-                                      'take the block means from')
-        bp = self.backprojection
-        if bp is None and backprojection_target is not None:
-            raise ValueError('backprojection_target is given but back-projection is off (set_backprojection / the "backprojection" key)')
-        self._check_backprojection(bp, self.sampler is not None, tiling, cs, gd)
-        if bp is not None and not self.conditional and backprojection_target is None:
-            raise NotImplementedError('back-projection on an unconditional model needs backprojection_target=: there is no conditioning '
-                                      'image to down-sample')
+        cfgs = {r.name: getattr(self, r.name) for r in X.RULES}
+        targets = dict(consistency=consistency_target, backprojection=backprojection_target)
+        for r in X.RULES:
+            if cfgs[r.name] is None and targets.get(r.name) is not None:
+                raise ValueError('%s is given but %s is off (%s / the "%s" key)' % (r.target_kw, r.noun, r.setter, r.name))
+            X.check_rule(r, cfgs, self.sampler is not None and self.variant == 'ddpm', tiling)
+            if cfgs[r.name] is not None and r.target_kw is not None and not self.conditional and targets[r.name] is None:
+                raise NotImplementedError('%s on an unconditional model needs %s=: there is no conditioning image to %s'
+                                          % (r.noun, r.target_kw, r.target_from))
         dev = self.betas.device
         if dev.type != 'cuda':
             raise L.Sr3Error('p_sample_loop needs the model on a GPU (set gpu_ids); there is no CPU fallback')
@@ -1164,22 +850,9 @@ class EngineDiffusion(nn.Module):
             raise L.Sr3Error('p_sample_loop: a (B, C, H, W) image or shape is expected (got %s)' % (shape,))
         # the image size comes from the input, as in the reference (`shape = x.shape`); the launch list -- and with it
         # plan.generation, part of the state's key -- follows it
-        if cs is not None:
-            r = cs['block']
-            if shape[2] % r or shape[3] % r:
-                raise L.Sr3Error('p_sample_loop: consistency block %d does not divide the image (%d x %d)' % (r, shape[2], shape[3]))
-            want = (shape[0], shape[1], shape[2] // r, shape[3] // r)
-            if consistency_target is not None and (not torch.is_tensor(consistency_target) or tuple(consistency_target.shape) != want):
-                raise L.Sr3Error('p_sample_loop: consistency_target must be a %s tensor of block means (got %s)'
-                                 % (want, tuple(getattr(consistency_target, 'shape', ())) or type(consistency_target).__name__))
-        if bp is not None:
-            s = bp['scale']
-            if shape[2] % s or shape[3] % s:
-                raise L.Sr3Error('p_sample_loop: backprojection scale %d does not divide the image (%d x %d)' % (s, shape[2], shape[3]))
-            want = (shape[0], shape[1], shape[2] // s, shape[3] // s)
-            if backprojection_target is not None and (not torch.is_tensor(backprojection_target) or tuple(backprojection_target.shape) != want):
-                raise L.Sr3Error('p_sample_loop: backprojection_target must be a %s LR image (got %s)'
-                                 % (want, tuple(getattr(backprojection_target, 'shape', ())) or type(backprojection_target).__name__))
+        for r in X.RULES:
+            if cfgs[r.name] is not None:
+                r.check_target(cfgs[r.name], shape, targets.get(r.name))
         tiles = None
         if tiling is not None:
             # tiled: the plan runs at the TILE's geometry; everything is validated here, before anything is written
@@ -1191,8 +864,7 @@ class EngineDiffusion(nn.Module):
             self.denoise_fn.plan.set_geometry(grid.th, grid.tw)
         else:
             self.denoise_fn.plan.set_geometry(shape[2], shape[3])
-        st = self._loop_state(shape, None if cond is None else shape, dev, item_streams=item_seeds is not None, tiles=tiles, consistency=cs,
-                              guidance=gd, backprojection=bp)
+        st = self._loop_state(shape, None if cond is None else shape, dev, item_streams=item_seeds is not None, tiles=tiles, **cfgs)
         self.denoise_fn.ensure_derived()       # a replayed graph does not pass through EngineUNet.forward
         if item_seeds is not None:
             for g, v in zip(st['gens'], item_seeds):
@@ -1207,20 +879,9 @@ class EngineDiffusion(nn.Module):
             st['cond'].copy_(cond)
             if tiles is not None:              # the conditioning image does not change: cut into tiles once
                 self._gather_tiles(st, st['cond'], st['cond_tiles'], 0, st['cond_tiles'].shape[0])
-        if cs is not None:                     # the target does not change over the chain: its block means once
-            if consistency_target is not None:
-                st['ymean'].copy_(consistency_target)
-            else:
-                B, Cc, H, W = shape
-                src = st['cond'] if st['cond'].shape[1] == Cc else st['cond'][:, :Cc].contiguous()
-                L.check(L.load().sr3_block_mean_f32(L.ptr(src), B, Cc, H, W, cs['block'], L.ptr(st['ymean']), self._stream(dev)))
-        if bp is not None:                     # the LR target does not change over the chain: the conditioning image down-sampled once
-            if backprojection_target is not None:
-                st['y_lr'].copy_(backprojection_target)
-            else:
-                B, Cc, H, W = shape
-                src = st['cond'] if st['cond'].shape[1] == Cc else st['cond'][:, :Cc].contiguous()
-                st['y_lr'].copy_(resample_f32(src, tuple(st['y_lr'].shape[2:]), bp['resample'], tables=st['bp_down']))
+        for r in X.RULES:                      # a rule's target does not change over the chain: made once
+            if cfgs[r.name] is not None:
+                r.prepare(st, cfgs[r.name], shape, targets.get(r.name), dev)
         if st.get('hist') is not None:         # the first step's c3 is 0, but 0 * (whatever the last chain left, a NaN for one) is not 0
             st['hist'].zero_()
         st['step'].fill_(T - 1)                # (slot 1 = t of the next step; slot 0 is the step's scratch copy)
