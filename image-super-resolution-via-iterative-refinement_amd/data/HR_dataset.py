@@ -2,8 +2,9 @@
 data/LRHR_dataset.py):
 
   HRCropDataset   -- training / validation from an HR-only folder of images of any size: __getitem__ decodes and slices an
-                     (R, R, 3) uint8 crop and draws the sample's flip and degradation numbers; the LR and SR images are made on
-                     the MI355X for the whole batch (data/degrade.py, data/__init__.py: DeviceBatches).
+                     (R, R, 3) uint8 crop and draws the sample's flip and degradation numbers (five; six, the last the JPEG
+                     quality, when the config has a "jpeg" block); the LR and SR images are made on the MI355X for the whole
+                     batch (data/degrade.py, data/__init__.py: DeviceBatches).
   LRFolderDataset -- "mode": "LR": a folder of plain low-resolution images to super-resolve; DeviceBatches resizes each by the
                      config's scale to make the conditioning image.
 """

@@ -61,7 +61,8 @@ class DeviceBatches(object):
 
     def _degraded(self, batch):
         """A batch of an HR-only folder (data/HR_dataset.py: HRCropDataset): uint8 crops plus each sample's degradation draws ->
-        the uint8 HR / SR (/ LR) batch of a prepared dataset, made on the device (data/degrade.py).  The noise: training draws from
+        the uint8 HR / SR (/ LR) batch of a prepared dataset, made on the device (data/degrade.py: blur, resize, noise, JPEG, resize;
+        'deg' is (n, 5), or (n, 6) with the JPEG qualities when the config has a "jpeg" block).  The noise: training draws from
         the device's default generator; validation from a device generator seeded seed + index, the same on every pass."""
         from data.degrade import degrade_batch
         cfg, hr = self.dataset.degrade, self._on_device(batch['HR'])

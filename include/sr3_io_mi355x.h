@@ -76,7 +76,7 @@ int sr3_resize_u8(const uint8_t* in_hwc, int n_images, int H, int W, int C, int 
                   size_t scratch_bytes, uint8_t* out_hwc, void* stream);
 
 /* The degradation between an HR crop and its conditioning images (data/degrade.py of the package: blur -> resize down ->
- * noise -> resize up), for training from an HR-only folder.  Both entries check their arguments before anything is launched
+ * noise -> JPEG -> resize up), for training from an HR-only folder.  The entries check their arguments before anything is launched
  * (SR3_E_BADARG, sr3_last_error names the argument), take the caller's stream, and use no atomics.
  *
  * sr3_blur_u8: per-image 2-D correlation of n_images uint8 (H, W, C) images.  weights is (n_images, k, k) int32 on the device,
@@ -99,6 +99,35 @@ int sr3_blur_u8(const uint8_t* in_hwc, int n_images, int H, int W, int C, const 
  * SR3_E_BADARG: NULL in / sigma / z / out; n_images outside 1..65535; elems_per_image 0; out overlapping in without being it. */
 int sr3_noise_u8(const uint8_t* in, int n_images, size_t elems_per_image, const float* sigma, const float* z, uint8_t* out,
                  void* stream);
+
+/* sr3_jpeg_u8: the lossy half of a JPEG round trip -- what PIL's Image.save(buf, 'JPEG', quality=q, subsampling=s) followed by
+ * Image.open does to the bytes (libjpeg's default "islow" integer DCT, fancy up-sampling; no entropy coder: nothing is written) -- of
+ * n_images uint8 (H, W, C) images, C = 3 (RGB) or 1 (greyscale), any H, W >= 1.  quality is (n_images) int32 on the device: a
+ * value <= 0 copies image i unchanged, any other is clamped to 1..100.  subsampling is Pillow's number, 0 = 4:4:4 or 2 = 4:2:0
+ * (ignored for C == 1).  All in 32-bit integers, >> arithmetic, DESCALE(x, n) = (x + (1 << (n - 1))) >> n, FIX(v) = int(v * 65536 + 0.5):
+ *     Y  = (FIX(.299) R + FIX(.587) G + FIX(.114) B + 32768) >> 16
+ *     Cb = (-FIX(.16874) R - FIX(.33126) G + FIX(.5) B + (128 << 16) + 32767) >> 16
+ *     Cr = (FIX(.5) R - FIX(.41869) G - FIX(.08131) B + (128 << 16) + 32767) >> 16
+ *   padding: Y, and every plane at 4:4:4, by replicating the last column and row up to a multiple of 8.  Chroma at 4:2:0: the
+ *     full-resolution plane is replicated to a multiple of 16 columns and to an EVEN row count only, down-sampled
+ *     (a + b + c + d + bias) >> 2 per 2 x 2 cell (bias 1 in even output columns, 2 in odd ones), and then the down-sampled plane's
+ *     last row is replicated to a multiple of 8 rows
+ *   per 8 x 8 block of samples - 128: forward DCT (Loeffler-Ligtenberg-Moschytz, 13-bit constants; rows then columns; outputs 0 and 4
+ *     << 2 resp. DESCALE(., 2), the others DESCALE(., 11) resp. DESCALE(., 15)), which leaves 8 x the coefficient v;
+ *     t = clamp((base * s + 50) / 100, 1, 255) from the Annex K table of the plane, s = 5000 / q (q < 50) or 200 - 2 q;
+ *     c = sign(v) * ((|v| + (8 t >> 1)) / (8 t)) * t;  inverse DCT (columns DESCALE(., 11), rows DESCALE(., 18)); + 128; clamp
+ *   4:2:0 up-sampling over the ceil(H/2) x ceil(W/2) real chroma samples: s = 3 * this row + the nearer neighbour row, then
+ *     (3 s[this] + s[previous] + 8) >> 4 in even columns, (3 s[this] + s[next] + 7) >> 4 in odd ones, indices clamped
+ *     R = Y + ((FIX(1.402) (Cr - 128) + 32768) >> 16);  B = Y + ((FIX(1.772) (Cb - 128) + 32768) >> 16)
+ *     G = Y + ((-FIX(.34414) (Cb - 128) - FIX(.71414) (Cr - 128) + 32768) >> 16);  each clamped to 0..255
+ * Bit-exact with Pillow on libjpeg-turbo and with the NumPy restatement (tests/test_jpeg_cpu.py).  scratch holds the decoded planes
+ * between the two kernels, sr3_jpeg_scratch_bytes(...) bytes (0 for a geometry the call refuses); out_hwc == in_hwc runs in place.
+ * SR3_E_BADARG: NULL in_hwc / quality / out_hwc / scratch; n_images outside 1..65535; H or W not positive; C not 1 or 3;
+ * subsampling not 0 or 2 when C == 3; n_images * H * W * C >= 2^31; scratch_bytes below the query; out_hwc overlapping in_hwc without
+ * being it; scratch overlapping either. */
+size_t sr3_jpeg_scratch_bytes(int n_images, int H, int W, int C, int subsampling);
+int sr3_jpeg_u8(const uint8_t* in_hwc, int n_images, int H, int W, int C, const int32_t* quality, int subsampling,
+                uint8_t* out_hwc, void* scratch, size_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }

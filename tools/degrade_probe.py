@@ -3,7 +3,9 @@
 128 x 128 -> 16 x 16 -> 128 x 128, 21 x 21 anisotropic blur and noise on for every sample -- timed with HIP events around the whole
 call (weights made on the host, uploaded, four kernels' worth of work), --warmup calls, then --rounds timed ones; median and
 p10-p90.  The blur kernel alone is timed the same way.  Next to it the same chain restated with NumPy + Pillow (the 441-tap
-shifted accumulate of tests/test_degrade_cpu.py, Image.resize, fp32 noise) over --threads CPU threads, wall clock.
+shifted accumulate of tests/test_degrade_cpu.py, Image.resize, fp32 noise) over --threads CPU threads, wall clock.  The JPEG link
+(data.degrade.jpeg_batch, 4:2:0, per-image qualities in 30..95) is timed on its own on an LR batch of 64 x 16 x 16 x 3 and on one of
+16 x 128 x 128 x 3, next to the Pillow save / open loop over the same threads, with the byte equality of the two.
     python tools/degrade_probe.py [--batch 64] [--rounds 30] [--warmup 5] [--threads 16] [--step-ms 123.8]      (GPU box)"""
 import argparse
 import json
@@ -94,12 +96,43 @@ def main():
                 cpu_ms.append((time.perf_counter() - t0) * 1e3)
     same = all(np.array_equal(lr_d[i].cpu().numpy(), ref[i][0]) and np.array_equal(sr_d[i].cpu().numpy(), ref[i][1]) for i in range(n))
     cpu = spread(cpu_ms)
-    out = {'probe': 'degrade_batch', 'device': torch.cuda.get_device_name(0), 'batch': n, 'r_resolution': R, 'l_resolution': Lr, 'kernel': k,
+
+    # the JPEG link alone: sr3_jpeg_u8 (4:2:0, qualities 30..95 drawn per image) against the Pillow loop it stands for -- save to a
+    # buffer, open, one image per task over the same threads -- on an LR batch of the training geometry and on a larger one
+    import io
+
+    def pil_jpeg(img, q):
+        buf = io.BytesIO()
+        Image.fromarray(img).save(buf, 'JPEG', quality=int(q), subsampling=2)
+        return np.asarray(Image.open(io.BytesIO(buf.getvalue())))
+
+    jpeg = []
+    with ThreadPoolExecutor(a.threads) as pool:
+        for nj, side in ((64, 16), (16, 128)):
+            imgs = rng.randint(0, 256, size=(nj, side, side, 3)).astype(np.uint8)
+            imgs[:, :side // 2] = imgs[:, :side // 2] // 64 * 64          # (flat-ish halves: not every block is noise)
+            qs = rng.randint(30, 96, size=nj).astype(np.int32)
+            imgs_d, qs_d = torch.from_numpy(imgs).to(dev), torch.from_numpy(qs).to(dev)
+            got = D.jpeg_batch(imgs_d, qs_d, '4:2:0').cpu().numpy()
+            t_gpu = timed(lambda: D.jpeg_batch(imgs_d, qs_d, '4:2:0'))
+            ms = []
+            for rnd in range(1 + a.cpu_rounds):
+                t0 = time.perf_counter()
+                ref_j = list(pool.map(pil_jpeg, imgs, qs))
+                if rnd:
+                    ms.append((time.perf_counter() - t0) * 1e3)
+            jpeg.append({'batch': nj, 'side': side, 'gpu_jpeg_batch': t_gpu, 'cpu_pillow_loop': dict(spread(ms), threads=a.threads),
+                         'device_equals_pillow': bool(np.array_equal(got, np.stack(ref_j)))})
+    from PIL import features
+    turbo = bool(features.check_feature('libjpeg_turbo'))
+    out = {'probe': 'degrade_batch', 'jpeg': jpeg, 'pillow_on_libjpeg_turbo': turbo, 'device': torch.cuda.get_device_name(0), 'batch': n, 'r_resolution': R, 'l_resolution': Lr, 'kernel': k,
            'gpu_degrade_batch': gpu, 'gpu_blur_only': blur, 'cpu_numpy_pillow': dict(cpu, threads=a.threads),
            'device_equals_cpu_chain': bool(same), 'step_ms': a.step_ms,
            'gpu_share_of_step': round(gpu['median_ms'] / a.step_ms, 5), 'cpu_share_of_step': round(cpu['median_ms'] / a.step_ms, 3)}
     print(json.dumps(out))
     assert same, 'the device chain and the NumPy + Pillow chain differ'
+    # (a Pillow on another libjpeg may round differently: the report says so, the committed fixture of tests/golden is the gate)
+    assert not turbo or all(j['device_equals_pillow'] for j in jpeg), 'sr3_jpeg_u8 and the Pillow round trip differ'
 
 
 if __name__ == '__main__':
