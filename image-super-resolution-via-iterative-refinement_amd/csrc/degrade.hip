@@ -3,6 +3,8 @@
 //   sr3_blur_u8 : per-image k x k correlation in 16-bit fixed point, reflect-101 border, integer arithmetic => the result does not
 //                 depend on the summation order and equals the NumPy restatement bit for bit
 //   sr3_noise_u8: out = clamp(rint(in + sigma_i * z)), separately rounded fp32 multiply and add, round-half-even
+//   sr3_noise_ex_u8: the same with a per-image mode -- Gaussian or Poisson (shot) noise, per channel or one value per pixel (gray); the
+//                 Poisson draw is a binary search of an integer CDF table => equals the NumPy restatement bit for bit
 //   sr3_jpeg_u8 : the lossy half of a JPEG round trip on the LR image (between the noise and the resize up), libjpeg's integer arithmetic
 //                 as Pillow drives it => equals Pillow's save / open bytes and the NumPy restatement bit for bit
 #include <stdint.h>
@@ -124,6 +126,62 @@ __global__ __launch_bounds__(256) void k_noise_u8(const unsigned char* in, size_
     }
     ob[i] = v;
   }
+}
+
+// k = #{j : row[j] <= r} of a non-decreasing row of kmax entries: at most ceil(log2(kmax + 1)) probes (9 of the 384-column Poisson table)
+__device__ __forceinline__ int count_le(const int* __restrict__ row, int kmax, int r) {
+  int lo = 0, hi = kmax;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (row[mid] <= r) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ unsigned char noise_clamp(float f) { return (unsigned char)fminf(fmaxf(rintf(f), 0.f), 255.f); }
+
+// One thread per pixel; the thread owns the pixel's C bytes, reads them before it writes them (in and out may be the same buffer:
+// neither pointer is __restrict__).  A pixel is C bytes at byte offset C * p and its draws C words at word offset C * p: for C == 3
+// nothing wider than a byte resp. a dword is aligned, for C == 1 there is one of each -- so the accesses are the natural ones.
+// mode (low two bits): bit 0 = gray (one draw per pixel), bit 1 = Poisson.  A mode whose draws are absent (z resp. r / table NULL)
+// copies, as strength 0 does: nothing is dereferenced that the caller did not pass.
+template <int C>
+__global__ __launch_bounds__(256) void k_noise_ex_u8(const unsigned char* in, int HW, const int* __restrict__ mode,
+                                                     const float* __restrict__ strength, const float* __restrict__ z,
+                                                     const int* __restrict__ r, const int* __restrict__ table, int kmax, unsigned char* out) {
+  const int img = blockIdx.y;
+  const unsigned pu = blockIdx.x * 256u + threadIdx.x;
+  if (pu >= (unsigned)HW) return;                // (n * H * W * C < 2^31: the host checked)
+  const size_t o = ((size_t)img * HW + pu) * C;
+  int v[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) v[c] = in[o + c];
+  const float s = strength[img];
+  const int m = mode[img] & 3;
+  const bool gray = m & 1, poisson = m & 2;
+  if (s != 0.f && !poisson && z) {
+    float zz[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) zz[c] = z[o + (gray ? 0 : c)];
+#pragma unroll
+    for (int c = 0; c < C; ++c) v[c] = noise_clamp(add_rn((float)v[c], mul_rn(s, zz[c])));
+  } else if (s != 0.f && poisson && r && table) {
+    if (gray && C == 3) {
+      const int Y = (19595 * v[0] + 38470 * v[1] + 7471 * v[2] + 32768) >> 16;      // the JPEG kernel's luma (FIX(.299), ...): <= 255
+      const int k = count_le(table + (size_t)Y * kmax, kmax, r[o]);
+      const float d = mul_rn(s, (float)(k - Y));
+#pragma unroll
+      for (int c = 0; c < C; ++c) v[c] = noise_clamp(add_rn((float)v[c], d));
+    } else {
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const int k = count_le(table + (size_t)v[c] * kmax, kmax, r[o + c]);
+        v[c] = noise_clamp(add_rn((float)v[c], mul_rn(s, (float)(k - v[c]))));
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < C; ++c) out[o + c] = (unsigned char)v[c];
 }
 
 // ---- JPEG: libjpeg's lossy half as Pillow drives it ("islow" integer DCT, fancy up-sampling), without the entropy coder ----
@@ -393,6 +451,35 @@ int sr3_noise_u8(const uint8_t* in, int n_images, size_t elems_per_image, const 
   const size_t b = (elems_per_image + 255) / 256;
   hipLaunchKernelGGL(k_noise_u8, dim3((unsigned)(b > 1024 ? 1024 : b), n_images), dim3(256), 0, st, in, elems_per_image, sigma, z, out);
   SR3_LAUNCH_CHECK("k_noise_u8");
+  return SR3_OK;
+}
+
+int sr3_noise_ex_u8(const uint8_t* in_hwc, int n_images, int H, int W, int C, const int32_t* mode, const float* strength, const float* z,
+                    const int32_t* r, const int32_t* table, int kmax, uint8_t* out_hwc, void* stream) {
+  if (!in_hwc) { set_error("noise_ex_u8: in_hwc is NULL"); return SR3_E_BADARG; }
+  if (!mode) { set_error("noise_ex_u8: mode is NULL"); return SR3_E_BADARG; }
+  if (!strength) { set_error("noise_ex_u8: strength is NULL"); return SR3_E_BADARG; }
+  if (!out_hwc) { set_error("noise_ex_u8: out_hwc is NULL"); return SR3_E_BADARG; }
+  if (n_images <= 0 || n_images > 65535) { set_error("noise_ex_u8: n_images %d outside 1..65535", n_images); return SR3_E_BADARG; }
+  if (H <= 0) { set_error("noise_ex_u8: H %d is not positive", H); return SR3_E_BADARG; }
+  if (W <= 0) { set_error("noise_ex_u8: W %d is not positive", W); return SR3_E_BADARG; }
+  if (C != 1 && C != 3) { set_error("noise_ex_u8: C %d is not 1 or 3", C); return SR3_E_BADARG; }
+  if ((double)n_images * H * W * C >= 2147483648.0) {
+    set_error("noise_ex_u8: %d images of %d x %d x %d are 2^31 bytes or more", n_images, H, W, C);
+    return SR3_E_BADARG;
+  }
+  if (table && (kmax < 1 || kmax > 1024)) { set_error("noise_ex_u8: kmax %d outside 1..1024 (the table's columns)", kmax); return SR3_E_BADARG; }
+  const size_t bytes = (size_t)n_images * H * W * C;
+  if (in_hwc != out_hwc && overlaps(in_hwc, bytes, out_hwc, bytes)) {
+    set_error("noise_ex_u8: out_hwc overlaps in_hwc partially (in place means out_hwc == in_hwc)");
+    return SR3_E_BADARG;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int HW = H * W;
+  const dim3 grid((unsigned)(((size_t)HW + 255) / 256), n_images);
+  if (C == 3) hipLaunchKernelGGL(k_noise_ex_u8<3>, grid, dim3(256), 0, st, in_hwc, HW, mode, strength, z, r, table, kmax, out_hwc);
+  else hipLaunchKernelGGL(k_noise_ex_u8<1>, grid, dim3(256), 0, st, in_hwc, HW, mode, strength, z, r, table, kmax, out_hwc);
+  SR3_LAUNCH_CHECK("k_noise_ex_u8");
   return SR3_OK;
 }
 

@@ -1,7 +1,7 @@
-// Bicubic / bilinear resampling of uint8 images exactly as Pillow's ImagingResample does it (the arithmetic behind
+// Bicubic / bilinear / box resampling of uint8 images exactly as Pillow's ImagingResample does it (the arithmetic behind
 // data/prepare_data.py:17-40: torchvision.transforms.functional.resize(PIL image, size, Image.BICUBIC) ->
 // PIL.Image.resize): per output index a window [xmin, xmin + n) of normalised double-precision bicubic
-// (a = -0.5) weights, scaled by max(scale, 1) for antialiased down-sampling, converted to 22-bit fixed point,
+// (a = -0.5; bilinear: the triangle; box: 1 on (-0.5, 0.5]) weights, scaled by max(scale, 1) for antialiased down-sampling, converted to 22-bit fixed point,
 // a horizontal pass then a vertical pass over the uint8 intermediate, each rounding with +2^21 >> 22 and
 // clamping to [0, 255].  Integer arithmetic throughout => bit-exact with Pillow (pinned against Pillow itself,
 // which this image ships; tests/test_gpu_io.py, tests/test_oracle_io.py).
@@ -36,14 +36,21 @@ __device__ double bilinear(double x) {
   return x < 1.0 ? dsub(1.0, x) : 0.0;
 }
 
+// Pillow Resample.c box_filter
+__device__ double box(double x) { return (x > -0.5 && x <= 0.5) ? 1.0 : 0.0; }
+
+// FILTER is Pillow's number: 2 = BILINEAR (support 1), 3 = BICUBIC (support 2), 4 = BOX (support 0.5)
+template <int FILTER>
+__host__ __device__ constexpr double filter_support() { return FILTER == 3 ? 2.0 : (FILTER == 2 ? 1.0 : 0.5); }
+
 // precompute_coeffs + normalize_coeffs_8bpc for one axis: thread xx fills bounds[xx] = {xmin, n} and kk[xx][ksize]
-template <bool CUBIC>
+template <int FILTER>
 __global__ void k_resample_coeffs(int in_size, int out_size, int ksize, int* __restrict__ bounds, int* __restrict__ kk) {
   const int xx = blockIdx.x * blockDim.x + threadIdx.x;
   if (xx >= out_size) return;
   const double scale = ddiv((double)in_size, (double)out_size);
   const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = dmul(CUBIC ? 2.0 : 1.0, filterscale);
+  const double support = dmul(filter_support<FILTER>(), filterscale);
   const double center = dmul(dadd((double)xx, 0.5), scale);          // in0 = 0
   const double ss = ddiv(1.0, filterscale);
   int xmin = (int)dadd(dsub(center, support), 0.5);
@@ -55,7 +62,7 @@ __global__ void k_resample_coeffs(int in_size, int out_size, int ksize, int* __r
   double ww = 0.0;
   auto weight = [&](int x) {
     const double arg = dmul(dadd(dsub((double)(x + xmin), center), 0.5), ss);
-    return CUBIC ? bicubic(arg) : bilinear(arg);
+    return FILTER == 3 ? bicubic(arg) : (FILTER == 2 ? bilinear(arg) : box(arg));
   };
   for (int x = 0; x < xmax; ++x) ww = dadd(ww, weight(x));
   for (int x = 0; x < ksize; ++x) {
@@ -105,17 +112,24 @@ __global__ __launch_bounds__(256) void k_resample_pass(const unsigned char* __re
   }
 }
 
-int ksize_for(int in_size, int out_size, bool cubic) {
+int ksize_for(int in_size, int out_size, int filter) {
   double scale = (double)in_size / out_size;
   if (scale < 1.0) scale = 1.0;
-  return (int)ceil((cubic ? 2.0 : 1.0) * scale) * 2 + 1;
+  return (int)ceil((filter == 3 ? 2.0 : (filter == 2 ? 1.0 : 0.5)) * scale) * 2 + 1;
+}
+
+void launch_coeffs(int filter, int in_size, int out_size, int ksize, int* bounds, int* kk, hipStream_t st) {
+  const dim3 grid((out_size + 63) / 64), block(64);
+  if (filter == 3) hipLaunchKernelGGL(k_resample_coeffs<3>, grid, block, 0, st, in_size, out_size, ksize, bounds, kk);
+  else if (filter == 2) hipLaunchKernelGGL(k_resample_coeffs<2>, grid, block, 0, st, in_size, out_size, ksize, bounds, kk);
+  else hipLaunchKernelGGL(k_resample_coeffs<4>, grid, block, 0, st, in_size, out_size, ksize, bounds, kk);
 }
 
 struct Layout { size_t bx, kx, by, ky, tmp, total; int ksx, ksy; };
-Layout layout(int n, int H, int W, int C, int OH, int OW, bool cubic) {
+Layout layout(int n, int H, int W, int C, int OH, int OW, int filter) {
   Layout l;
   auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  l.ksx = ksize_for(W, OW, cubic); l.ksy = ksize_for(H, OH, cubic);
+  l.ksx = ksize_for(W, OW, filter); l.ksy = ksize_for(H, OH, filter);
   size_t off = 0;
   l.bx = off; off += al((size_t)OW * 2 * sizeof(int));
   l.kx = off; off += al((size_t)OW * l.ksx * sizeof(int));
@@ -135,16 +149,18 @@ extern "C" {
 
 size_t sr3_resize_scratch_bytes(int n_images, int H, int W, int C, int OH, int OW) {
   if (n_images <= 0 || H <= 0 || W <= 0 || C <= 0 || OH <= 0 || OW <= 0) return 0;
-  return layout(n_images, H, W, C, OH, OW, true).total;      // the bicubic tables are the larger ones
+  return layout(n_images, H, W, C, OH, OW, 3).total;         // the bicubic tables are the largest (support 2 against 1 and 0.5)
 }
 
 int sr3_resize_u8(const uint8_t* in_hwc, int n_images, int H, int W, int C, int OH, int OW, int resample, void* scratch,
                   size_t scratch_bytes, uint8_t* out_hwc, void* stream) {
-  if (resample != 2 && resample != 3) { set_error("resize: resample must be 2 (PIL BILINEAR) or 3 (PIL BICUBIC)"); return SR3_E_UNSUPPORTED; }
-  const bool cubic = resample == 3;
+  if (resample != 2 && resample != 3 && resample != 4) {
+    set_error("resize: resample must be 2 (PIL BILINEAR), 3 (PIL BICUBIC) or 4 (PIL BOX)");
+    return SR3_E_UNSUPPORTED;
+  }
   if (!in_hwc || !out_hwc || !scratch) { set_error("null argument"); return SR3_E_BADARG; }
   if (n_images <= 0 || H <= 0 || W <= 0 || C <= 0 || OH <= 0 || OW <= 0) { set_error("resize: bad shape"); return SR3_E_BADARG; }
-  const Layout l = layout(n_images, H, W, C, OH, OW, cubic);
+  const Layout l = layout(n_images, H, W, C, OH, OW, resample);
   if (scratch_bytes < l.total) { set_error("resize: scratch too small (%zu < %zu)", scratch_bytes, l.total); return SR3_E_NOMEM; }
   if (((uintptr_t)scratch & 255)) { set_error("resize: scratch must be 256-byte aligned"); return SR3_E_ALIGN; }
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -160,16 +176,14 @@ int sr3_resize_u8(const uint8_t* in_hwc, int n_images, int H, int W, int C, int 
   }
   const unsigned char* src = in_hwc;
   if (need_h) {
-    if (cubic) hipLaunchKernelGGL(k_resample_coeffs<true>, dim3((OW + 63) / 64), dim3(64), 0, st, W, OW, l.ksx, bx, kx);
-    else hipLaunchKernelGGL(k_resample_coeffs<false>, dim3((OW + 63) / 64), dim3(64), 0, st, W, OW, l.ksx, bx, kx);
+    launch_coeffs(resample, W, OW, l.ksx, bx, kx, st);
     unsigned char* dst = need_v ? tmp : out_hwc;
     hipLaunchKernelGGL(k_resample_pass<0>, dim3(blocks((size_t)H * OW * C), n_images), dim3(256), 0, st, src, H, W, C, H, OW, bx, kx,
                        l.ksx, dst);
     src = dst;
   }
   if (need_v) {
-    if (cubic) hipLaunchKernelGGL(k_resample_coeffs<true>, dim3((OH + 63) / 64), dim3(64), 0, st, H, OH, l.ksy, by, ky);
-    else hipLaunchKernelGGL(k_resample_coeffs<false>, dim3((OH + 63) / 64), dim3(64), 0, st, H, OH, l.ksy, by, ky);
+    launch_coeffs(resample, H, OH, l.ksy, by, ky, st);
     hipLaunchKernelGGL(k_resample_pass<1>, dim3(blocks((size_t)OH * OW * C), n_images), dim3(256), 0, st, src, H, OW, C, OH, OW, by, ky,
                        l.ksy, out_hwc);
   }

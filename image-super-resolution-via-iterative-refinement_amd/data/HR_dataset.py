@@ -3,7 +3,7 @@ data/LRHR_dataset.py):
 
   HRCropDataset   -- training / validation from an HR-only folder of images of any size: __getitem__ decodes and slices an
                      (R, R, 3) uint8 crop and draws the sample's flip and degradation numbers (five; six, the last the JPEG
-                     quality, when the config has a "jpeg" block); the LR and SR images are made on the MI355X for the whole
+                     quality, when the config has a "jpeg" block; plus the twenty of 'deg2' when it has a second-order key); the LR and SR images are made on the MI355X for the whole
                      batch (data/degrade.py, data/__init__.py: DeviceBatches).
   LRFolderDataset -- "mode": "LR": a folder of plain low-resolution images to super-resolve; DeviceBatches resizes each by the
                      config's scale to make the conditioning image.
@@ -13,7 +13,7 @@ from PIL import Image
 from torch.utils.data import Dataset
 
 import data.util as Util
-from data.degrade import degrade_config, draw_deg
+from data.degrade import degrade_config, draw_deg, draw_deg2
 
 
 class HRCropDataset(Dataset):
@@ -47,12 +47,15 @@ class HRCropDataset(Dataset):
             top = int(torch.randint(0, H - R + 1, (1,)).item())
             left = int(torch.randint(0, W - R + 1, (1,)).item())
             flip = bool(torch.rand(1).item() < 0.5)
-            deg = draw_deg(self.degrade)
+            gen = None
         else:
             # the validation set is the same images on every pass: centre crop, no flip, draws seeded by the index
             top, left, flip = (H - R) // 2, (W - R) // 2, False
-            deg = draw_deg(self.degrade, torch.Generator().manual_seed(self.degrade['seed'] + index))
-        return {'HR': img[top:top + R, left:left + R].contiguous(), 'Index': index, 'flip': flip, 'deg': deg}
+            gen = torch.Generator().manual_seed(self.degrade['seed'] + index)
+        item = {'HR': img[top:top + R, left:left + R].contiguous(), 'Index': index, 'flip': flip, 'deg': draw_deg(self.degrade, gen)}
+        if self.degrade['extended']:              # a second-order config: twenty more numbers, drawn right behind the first
+            item['deg2'] = draw_deg2(self.degrade, gen)
+        return item
 
 
 class LRFolderDataset(Dataset):

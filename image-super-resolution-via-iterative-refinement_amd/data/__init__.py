@@ -71,7 +71,7 @@ class DeviceBatches(object):
             if hr.shape[0] != 1:
                 raise ValueError('validation batches of an HR-only folder hold one image (the per-index noise stream)')
             gen = torch.Generator(device=hr.device).manual_seed(cfg['seed'] + int(batch['Index'][0]))
-        lr, sr = degrade_batch(hr, batch['deg'], cfg, generator=gen)
+        lr, sr = degrade_batch(hr, batch['deg'], cfg, generator=gen, deg2=batch.get('deg2'))      # ('deg2': a second-order config's draws)
         out = {'HR': hr, 'SR': sr, 'Index': batch['Index']}
         if self.dataset.need_LR:
             out['LR'] = lr

@@ -1,6 +1,6 @@
 """Drop-in for the reference's data/prepare_data.py (resize_and_convert, image_convert_bytes, resize_multiple,
 resize_worker, prepare and the same command line) with the resampling on the MI355X: csrc/resize.hip reproduces
-Pillow's BICUBIC / BILINEAR `Image.resize` bit for bit, so the LR / HR / SR triplets are byte-identical to the
+Pillow's BICUBIC / BILINEAR (and, for the degradation chain, BOX) `Image.resize` bit for bit, so the LR / HR / SR triplets are byte-identical to the
 reference's.  torchvision's `resize` (smaller edge -> size, aspect kept) and `center_crop` are restated here
 (torchvision is not needed).  Engine extension: `resize_batch` resizes a whole uint8 batch in one call; `prepare`
 runs in one process (the GPU does the arithmetic; `n_worker` is accepted and ignored)."""
@@ -16,7 +16,7 @@ from PIL import Image
 
 from sr3_hip import lib as L
 
-_RESAMPLE = {Image.BILINEAR: 2, Image.BICUBIC: 3, 2: 2, 3: 3}
+_RESAMPLE = {Image.BILINEAR: 2, Image.BICUBIC: 3, Image.BOX: 4, 2: 2, 3: 3, 4: 4}
 
 
 def _device():
@@ -28,7 +28,7 @@ def _device():
 def resize_batch(batch_u8, out_hw, resample=Image.BICUBIC):
     """(n, H, W, C) uint8 tensor (host or device) -> (n, OH, OW, C) uint8 on the device, = PIL resize per image."""
     if resample not in _RESAMPLE:
-        raise NotImplementedError('resample %r: only Image.BICUBIC and Image.BILINEAR are built' % (resample,))
+        raise NotImplementedError('resample %r: only Image.BICUBIC, Image.BILINEAR and Image.BOX are built' % (resample,))
     dev = batch_u8.device if batch_u8.is_cuda else _device()
     b = batch_u8.to(dev).contiguous()
     n, H, W, Cc = b.shape

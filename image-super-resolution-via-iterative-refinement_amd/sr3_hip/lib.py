@@ -57,6 +57,7 @@ SIGNATURES = {
     'sr3_images_u8_to_f32': (_I, [_P, _I, _I, _I, _I, _P, _F, _F, _P, _P]),
     'sr3_blur_u8': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P]),
     'sr3_noise_u8': (_I, [_P, _I, _Z, _P, _P, _P, _P]),
+    'sr3_noise_ex_u8': (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P]),
     'sr3_jpeg_scratch_bytes': (_Z, [_I, _I, _I, _I, _I]),
     'sr3_jpeg_u8': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _Z, _P]),
     'sr3_version': (_I, []),

@@ -66,7 +66,8 @@ int sr3_images_u8_to_f32(const uint8_t* in_hwc, int n_images, int H, int W, int 
 
 /* Data preparation (data/prepare_data.py:17-40 resize_and_convert / resize_multiple): PIL.Image.resize(size,
  * resample) of n_images uint8 (H, W, C) images to (OH, OW, C) for resample = 3 (Image.BICUBIC, the default of
- * prepare_data.py) or 2 (Image.BILINEAR, its `--resample bilinear`), bit-exact with Pillow's ImagingResample
+ * prepare_data.py), 2 (Image.BILINEAR, its `--resample bilinear`) or 4 (Image.BOX: support 0.5, 1 on (-0.5, 0.5]; the degradation
+ * chain's third filter), bit-exact with Pillow's ImagingResample
  * (double-precision filter weights -- bicubic a = -0.5 -- over a support scaled by max(in/out, 1), normalised, 22-bit fixed
  * point, horizontal then vertical pass over a uint8 intermediate, each with round-to-nearest and clamp).  The
  * smaller-edge / centre-crop logic of torchvision's resize + center_crop lives in the Python mirror
@@ -99,6 +100,27 @@ int sr3_blur_u8(const uint8_t* in_hwc, int n_images, int H, int W, int C, const 
  * SR3_E_BADARG: NULL in / sigma / z / out; n_images outside 1..65535; elems_per_image 0; out overlapping in without being it. */
 int sr3_noise_u8(const uint8_t* in, int n_images, size_t elems_per_image, const float* sigma, const float* z, uint8_t* out,
                  void* stream);
+
+/* sr3_noise_ex_u8: noise on n_images uint8 (H, W, C) images, C = 1 or 3, with a per-image kind.  mode is (n_images) int32 on the
+ * device, of which the low two bits are read: 0 Gaussian per channel, 1 Gaussian gray, 2 Poisson per channel, 3 Poisson gray (gray:
+ * one draw per pixel serves its channels).  strength is (n_images) fp32: the Gaussian sigma in 8-bit levels resp. the Poisson
+ * scale; strength[i] == 0 copies image i whatever z and r hold.  z (fp32) and r (int32, the caller's integers uniform in
+ * [0, 2^31 - 1)) have the shape of the images; table is (256, kmax) int32, row v non-decreasing:
+ * table[v][j] = min(floor(CDF_Poisson(lambda = v)(j) * 2^31), 2^31 - 1)  (data/degrade.py: poisson_table, kmax 384).  One thread per
+ * pixel; for the pixel's bytes v[c], every fp32 operation rounded on its own (no fma), rintf = round half to even:
+ *     0:  out[c] = clamp(rintf(v[c] + strength * z[c]), 0, 255)                                   (sr3_noise_u8's arithmetic)
+ *     1:  the same with z[0] for every c
+ *     2:  k = #{j : table[v[c]][j] <= r[c]}  (binary search);  out[c] = clamp(rintf(v[c] + strength * (float)(k - v[c])), 0, 255)
+ *     3:  Y = (19595 v[0] + 38470 v[1] + 7471 v[2] + 32768) >> 16  (sr3_jpeg_u8's luma);  k = #{j : table[Y][j] <= r[0]};
+ *         out[c] = clamp(rintf(v[c] + strength * (float)(k - Y)), 0, 255)
+ *     C == 1: 1 is 0 and 3 is 2.
+ * z may be NULL when no image has a Gaussian mode with nonzero strength, r and table when none has a Poisson mode with nonzero
+ * strength (an image whose draws are missing is copied: nothing absent is dereferenced).  out_hwc == in_hwc runs in place.  mode and
+ * strength live on the device, so the entry checks what it can see without reading them.
+ * SR3_E_BADARG: NULL in_hwc / mode / strength / out_hwc; n_images outside 1..65535; H or W not positive; C not 1 or 3;
+ * n_images * H * W * C >= 2^31; a non-NULL table with kmax outside 1..1024; out_hwc overlapping in_hwc without being it. */
+int sr3_noise_ex_u8(const uint8_t* in_hwc, int n_images, int H, int W, int C, const int32_t* mode, const float* strength,
+                    const float* z, const int32_t* r, const int32_t* table, int kmax, uint8_t* out_hwc, void* stream);
 
 /* sr3_jpeg_u8: the lossy half of a JPEG round trip -- what PIL's Image.save(buf, 'JPEG', quality=q, subsampling=s) followed by
  * Image.open does to the bytes (libjpeg's default "islow" integer DCT, fancy up-sampling; no entropy coder: nothing is written) -- of

@@ -6,7 +6,8 @@ p10-p90.  The blur kernel alone is timed the same way.  Next to it the same chai
 shifted accumulate of tests/test_degrade_cpu.py, Image.resize, fp32 noise) over --threads CPU threads, wall clock.  The JPEG link
 (data.degrade.jpeg_batch, 4:2:0, per-image qualities in 30..95) is timed on its own on an LR batch of 64 x 16 x 16 x 3 and on one of
 16 x 128 x 128 x 3, next to the Pillow save / open loop over the same threads, with the byte equality of the two.
-    python tools/degrade_probe.py [--batch 64] [--rounds 30] [--warmup 5] [--threads 16] [--step-ms 123.8]      (GPU box)"""
+    python tools/degrade_probe.py [--batch 64] [--rounds 30] [--warmup 5] [--threads 16] [--step-ms 123.8]      (GPU box)
+--second [--mid 64] times the second-order chain of DESIGN.md 3.4c instead, next to the first-order one (second_order below)."""
 import argparse
 import json
 import os
@@ -25,8 +26,64 @@ def spread(ms):
             'n': len(s)}
 
 
+def second_order(a):
+    """--second: the two-round chain at batch 64, 128 -> M = 64 -> 16 -> 128 with every stage on for every sample --
+    a 21-tap blur (half the batch sinc) and noise in all four modes in both rounds, both JPEGs, the final sinc in both orders -- next
+    to the first-order chain (blur, noise, JPEG) on the same crops, each timed as the whole degrade_batch call."""
+    import numpy as np
+    import torch
+    import data.degrade as D
+    assert torch.cuda.is_available(), 'degrade_probe needs a GPU'
+    assert a.rounds >= 20, 'at least 20 timed repetitions'
+    R, Lr, M, k, n = 128, 16, a.mid, 21, a.batch
+    blur = {'kernel': k, 'sigma': [0.2, 3.0], 'anisotropic': True}
+    one = {'blur': blur, 'noise': {'sigma': [1, 25]}, 'jpeg': {'quality': [30, 95]}}
+    two = dict(one, sinc={'prob': 0.5}, shot={'prob': 0.5}, gray_noise=0.5,
+               second=dict(one, mid=[M, M], resample=['box', 'bilinear', 'bicubic'], sinc={'prob': 0.5}, shot={'prob': 0.5}, gray_noise=0.5,
+                           final_sinc={'kernel': 7}))
+    cfg1, cfg2 = D.degrade_config(one, Lr), D.degrade_config(two, Lr)
+    torch.manual_seed(0)
+    dev = torch.device('cuda', 0)
+    hr = torch.from_numpy(np.random.RandomState(0).randint(0, 256, size=(n, R, R, 3)).astype(np.uint8)).to(dev)
+    deg = torch.stack([D.draw_deg(cfg2) for _ in range(n)])
+    deg2 = torch.stack([D.draw_deg2(cfg2) for _ in range(n)])
+    assert bool((deg[:, 0] == 1).all() and (deg[:, 4] > 0).all() and (deg[:, 5] > 0).all())
+    assert bool((deg2[:, 7] == 1).all() and (deg2[:, 13] > 0).all() and (deg2[:, 16] > 0).all() and (deg2[:, 17] == 1).all())
+    g = torch.Generator(device=dev).manual_seed(1)
+    z, z2 = torch.randn(n, M, M, 3, device=dev, generator=g), torch.randn(n, Lr, Lr, 3, device=dev, generator=g)
+    r = torch.randint(0, 2 ** 31 - 1, (n, M, M, 3), dtype=torch.int32, device=dev, generator=g)
+    r2 = torch.randint(0, 2 ** 31 - 1, (n, Lr, Lr, 3), dtype=torch.int32, device=dev, generator=g)
+
+    def timed(call):
+        ms = []
+        for rnd in range(a.warmup + a.rounds):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            call()
+            e1.record()
+            e1.synchronize()
+            if rnd >= a.warmup:
+                ms.append(e0.elapsed_time(e1))
+        return spread(ms)
+
+    t2 = timed(lambda: D.degrade_batch(hr, deg, cfg2, z=z, deg2=deg2, r=r, z2=z2, r2=r2))
+    t2_drawn = timed(lambda: D.degrade_batch(hr, deg, cfg2, deg2=deg2))                 # the loader's call: the noise drawn inside
+    t1 = timed(lambda: D.degrade_batch(hr, deg, cfg1, z=z2))
+    a1, b1 = D.degrade_batch(hr, deg, cfg2, z=z, deg2=deg2, r=r, z2=z2, r2=r2)
+    a2, b2 = D.degrade_batch(hr, deg, cfg2, z=z, deg2=deg2, r=r, z2=z2, r2=r2)
+    out = {'probe': 'degrade_batch_second', 'device': torch.cuda.get_device_name(0), 'batch': n, 'r_resolution': R, 'mid': M, 'l_resolution': Lr,
+           'kernel': k, 'modes_round1': sorted(set(deg2[:, 2].tolist())), 'modes_round2': sorted(set(deg2[:, 14].tolist())),
+           'final_orders': sorted(set(deg2[:, 19].tolist())), 'gpu_second_order': t2, 'gpu_second_order_drawing_noise': t2_drawn,
+           'gpu_first_order': t1, 'repeatable': bool(torch.equal(a1, a2) and torch.equal(b1, b2)), 'step_ms': a.step_ms,
+           'second_share_of_step': round(t2_drawn['median_ms'] / a.step_ms, 5), 'first_share_of_step': round(t1['median_ms'] / a.step_ms, 5)}
+    print(json.dumps(out))
+    assert out['repeatable'], 'two calls with the same draws differ'
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--second', action='store_true', help='time the second-order chain (and the first-order one beside it) instead')
+    ap.add_argument('--mid', type=int, default=64, help='--second: the intermediate size M')
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--rounds', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
@@ -36,6 +93,8 @@ def main():
     a = ap.parse_args()
     sys.path.insert(0, PKG)
     sys.path.insert(0, ROOT)
+    if a.second:
+        return second_order(a)
     import numpy as np
     import torch
     from PIL import Image
