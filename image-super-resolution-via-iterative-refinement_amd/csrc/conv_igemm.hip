@@ -143,15 +143,18 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm(const ConvParams p) {
     }
   };
   // WPRE: the B fragments of k-step `it` for this wave's n blocks: w_split[n block][it][K = 16 step 2][plane 3][lane 64][8 bf16]
-  // (igemm_split_weights; zero outside Cout / Cin, so no bounds here)
+  // (igemm_split_weights; zero outside Cout / Cin inside a block, so no bounds there.  The buffer holds ceil(Cout / 32) blocks, not a
+  // whole number of tiles: where the last tile overhangs them -- Cout = 320 on a 128-wide tile -- its blocks past the end read the last
+  // block again; their columns are n >= Cout and never stored)
   const int wave_n_ = (tid >> 6) & 1;
+  const int nb_last = ((p.Cout + 31) >> 5) - 1;
   auto load_bfrag = [&](auto set_tag, int it) {
     constexpr int S = decltype(set_tag)::value;
     if constexpr (WPRE) {
       const int nb0 = (tile_n * BN + wave_n_ * WN) >> 5;
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
-        const bf16x8* q = reinterpret_cast<const bf16x8*>(p.w_split) + ((size_t)(nb0 + j) * total + it) * (2 * 3 * 64) + lane;
+        const bf16x8* q = reinterpret_cast<const bf16x8*>(p.w_split) + ((size_t)min(nb0 + j, nb_last) * total + it) * (2 * 3 * 64) + lane;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll

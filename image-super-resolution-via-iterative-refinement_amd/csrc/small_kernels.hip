@@ -425,7 +425,7 @@ __global__ __launch_bounds__(256) void k_conv_in_nchw(const float* __restrict__ 
 // registers) is loaded once per wave and reused for `bpw` pixel blocks.  Epilogue: + bias, NHWC stores (a register's 32
 // lanes = 32 consecutive channels of a pixel), and the per-(image, slice, channel) GroupNorm partial sums in double --
 // the stand-alone statistics pass over this 67 MB tensor goes away (slice = the bpw blocks of one wave).
-// Needs W % 32 == 0, Cout = 32 NB, CIN in {3, 6}.
+// Needs W % 32 == 0, Cout = 32 NB, CIN in {3, 6, 9} (conv_in_bpw).
 // ---------------------------------------------------------------------------------------------
 template <int CIN, int NB>
 __global__ __launch_bounds__(256) void k_conv_in_mfma(const float* __restrict__ a, int Ca, const float* __restrict__ bsrc,
@@ -522,8 +522,18 @@ __global__ __launch_bounds__(256) void k_conv_in_mfma(const float* __restrict__ 
 }
 
 // 32-pixel blocks per wave of the MFMA form (0: the shape stays on the VALU kernel); also the statistics slices per image
+// The one place that decides which form a shape runs on.  9 input channels (a self-conditioned model: K = 81, KS = 41 filter registers
+// per 32 output channels plus two 41-register A buffers): the NBs listed in CONV_IN9_NB, the others stay on the VALU kernel.  All
+// four are listed: none spills (156 / 264 / 304 / 349 registers) and each measured faster than the VALU kernel plus the
+// statistics pass at its layer shape
+#ifdef SR3_CONV_IN9_VALU      // A/B builds only (tools/selfcond_probe.py --valu-lib): every 9-channel shape on the VALU kernel + statistics pass
+static constexpr bool CONV_IN9_NB[5] = {false, false, false, false, false};
+#else
+static constexpr bool CONV_IN9_NB[5] = {false, true, true, true, true};
+#endif
 static int conv_in_bpw(int Cin, int H, int W, int Cout) {
-  if ((Cin != 3 && Cin != 6) || (W & 31) || (Cout & 31) || Cout > 128 || Cout < 32) return 0;
+  if ((Cin != 3 && Cin != 6 && Cin != 9) || (W & 31) || (Cout & 31) || Cout > 128 || Cout < 32) return 0;
+  if (Cin == 9 && !CONV_IN9_NB[Cout / 32]) return 0;
   const int bpi = H * W / 32;
   return (bpi % 4 == 0) ? 4 : 1;
 }
@@ -541,12 +551,13 @@ int conv_in_nchw(const float* a, int Ca, const float* b, int Cb, int B, int H, i
 #define SR3_CI(CIN, NB) hipLaunchKernelGGL((k_conv_in_mfma<CIN, NB>), grid, dim3(256), 0, st, a, Ca, b, Cb, B, H, W, w, bias, out, ostat, bpw, T)
     const int nb = Cout / 32;
     if (Ca + Cb == 6) { if (nb == 1) SR3_CI(6, 1); else if (nb == 2) SR3_CI(6, 2); else if (nb == 3) SR3_CI(6, 3); else SR3_CI(6, 4); }
+    else if (Ca + Cb == 9) { if (nb == 1) SR3_CI(9, 1); else if (nb == 2) SR3_CI(9, 2); else if (nb == 3) SR3_CI(9, 3); else SR3_CI(9, 4); }
     else { if (nb == 1) SR3_CI(3, 1); else if (nb == 2) SR3_CI(3, 2); else if (nb == 3) SR3_CI(3, 3); else SR3_CI(3, 4); }
 #undef SR3_CI
     SR3_LAUNCH_CHECK("k_conv_in_mfma");
     return SR3_OK;
   }
-  if (ostat) { set_error("conv_in: fused output statistics need the MFMA form (W %% 32 == 0, Cout %% 32 == 0, 3 or 6 input channels)"); return SR3_E_UNSUPPORTED; }
+  if (ostat) { set_error("conv_in: fused output statistics need the MFMA form (W %% 32 == 0, Cout %% 32 == 0, 3, 6 or 9 input channels)"); return SR3_E_UNSUPPORTED; }
   if (Cout & 3) { set_error("conv_in: Cout %% 4 != 0"); return SR3_E_UNSUPPORTED; }
   const int CoutP = (Cout + 63) & ~63;
   const size_t smem = (size_t)9 * (Ca + Cb) * CoutP * sizeof(float);

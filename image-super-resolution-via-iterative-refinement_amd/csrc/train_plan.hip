@@ -28,13 +28,16 @@ namespace sr3 {
 // sizes the scratch regions here and is launched by run_train
 // ---------------------------------------------------------------------------------------------
 namespace {
-constexpr int IN_PAD = 8;      // the input conv's weight gradient reads the image with its channels padded to 8 (nchw_to_nhwc_pad)
+// the input conv's weight gradient reads the image with its channels padded to a multiple of 4 the wgrad kernels take
+// (nchw_to_nhwc_pad): 8 up to 8 input channels -- every model without self-conditioning keeps its workspace bytes -- 16 above
+// (the plan accepts in_channel <= 16)
+inline int in_pad(int in_channel) { return in_channel <= 8 ? 8 : 16; }
 constexpr int OUT_PAD = 4;     // the output conv's gradients read dOut with its channels padded to 4 (l1_loss_grad)
 
 // shape of a record's weight gradient: the forward conv's own geometry
 ConvParams wgrad_shape(const sr3_plan* P, const Rec& r, int B) {
   const std::vector<Tensor>& T = P->ttens;
-  if (r.kind == R_CONV_IN) return conv_shape(B, T[r.out].H, T[r.out].W, 0, 1, 3, IN_PAD, 0, T[r.out].C);
+  if (r.kind == R_CONV_IN) return conv_shape(B, T[r.out].H, T[r.out].W, 0, 1, 3, in_pad(P->d.in_channel), 0, T[r.out].C);
   const Tensor& x0 = T[r.s.x0];
   if (r.kind == R_CONV_OUT) return conv_shape(B, x0.H, x0.W, 0, 1, 3, x0.C, 0, OUT_PAD);
   ConvParams c = conv_shape(B, x0.H, x0.W, r.s.ups, r.s.stride, r.s.ksize, x0.C, r.s.x1 >= 0 ? T[r.s.x1].C : 0, T[r.out].C);
@@ -234,7 +237,7 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
   P->t_xnoisy_off = off; off += al((size_t)B * (d.in_channel - cond_channels) * S2 * sizeof(float));
   P->t_eps_off = off; off += al((size_t)B * P->out_ch * S2 * sizeof(float));
   P->t_geps_off = off; off += al((size_t)B * S2 * OUT_PAD * sizeof(float));
-  P->t_inpad_off = off; off += al((size_t)B * S2 * IN_PAD * sizeof(float));
+  P->t_inpad_off = off; off += al((size_t)B * S2 * in_pad(d.in_channel) * sizeof(float));
   P->t_dwtmp_off = off; off += al(4096 * sizeof(double)) + al(max_dwtmp);      // [loss partials | dw temp]
   P->t_embscr_off = off; off += al((size_t)B * (13 + 16) * inner * sizeof(float));     // (+ the 16 row chunks of k_film_bwd_input)
   P->t_ws_bytes = off;
@@ -375,14 +378,15 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
       const int Ca = cond_channels > 0 ? cond_channels : xc;
       const float* b2 = cond_channels > 0 ? x_noisy : nullptr;
       const int Cb = cond_channels > 0 ? xc : 0;
-      rc = nchw_to_nhwc_pad(a, Ca, b2, Cb, B, S2, IN_PAD, inpad, st);
+      const int CP = in_pad(d.in_channel);
+      rc = nchw_to_nhwc_pad(a, Ca, b2, Cb, B, S2, CP, inpad, st);
       if (rc) return rc;
       rc = colsums(X.grad(r.out), B, S2, Cout, part, grads + s.bias, nullptr, 0, st);
       if (rc) return rc;
       rc = wgrad_call(X, r.dw, inpad, nullptr, X.grad(r.out), dwtmp);
       if (rc) return rc;
-      // compact [Cout][9][8] -> [Cout][9][in_channel]
-      SR3_HIP(hipMemcpy2DAsync(grads + s.w, (size_t)d.in_channel * sizeof(float), dwtmp, IN_PAD * sizeof(float),
+      // compact [Cout][9][CP] -> [Cout][9][in_channel]
+      SR3_HIP(hipMemcpy2DAsync(grads + s.w, (size_t)d.in_channel * sizeof(float), dwtmp, CP * sizeof(float),
                                (size_t)d.in_channel * sizeof(float), (size_t)Cout * 9, hipMemcpyDeviceToDevice, st));
     } else {
       const Tensor& x0 = P->ttens[s.x0];

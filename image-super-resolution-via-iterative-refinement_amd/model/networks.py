@@ -50,6 +50,11 @@ def define_G(opt):
         netG.set_objective(loss.get('type', 'l1'), loss.get('delta'), loss.get('weight', 'uniform'), loss.get('gamma'))
     if d.get('cond_drop') is not None:
         netG.set_cond_drop(d['cond_drop'])
+    # "self_condition": {"prob": 0.5} | true -- the network reads its own last x0 as extra input channels (set_self_condition; unet.in_channel
+    # is then conditioning channels + 2 x channels)
+    if d.get('self_condition') is not None:
+        from sr3_hip.diffusion import parse_self_condition
+        netG.set_self_condition(parse_self_condition(d['self_condition']))
     if opt['phase'] == 'train':
         init_weights(netG, init_type='orthogonal')
     return netG

@@ -27,6 +27,12 @@ Objective (engine extension, `"prediction": "eps" | "v" | "x0"` and `"loss": {"t
 target coefficients and weights to sr3_train_step_ex (`prediction_coefs`, `loss_weights`); sampling changes the two tables a, b of the
 step tail's x0c = clip(a x - b out) and nothing else, in every loop.
 
+Self-conditioning (engine extension, `"self_condition": {"prob": 0.5}` in model.diffusion or `set_self_condition`; Chen et al. 2022): the
+network reads its own previous estimate of x0 as `channels` extra input channels, [LR | last x0 | x].  Training: a first, gradient-free
+inference forward on zero self-conditioning channels supplies the clamped x0 of a random part of the batch (sr3_selfcond_x0_f32, per
+image), then the same engine call as before.  Sampling: every step runs forward -> sr3_selfcond_x0_f32 (the device counter's row, in
+place into the state's cond) -> the tail, captured as it is; what is fed back is the network's own clamped x0 before any rule on x0.
+
 Rules on x0 (engine extensions, keys next to "sampler" / "tiling" or the setters; sr3_hip/x0_rules.py holds each rule once): what is done
 to the predicted x0 before the posterior mix.  Per step: UNet forward with the output stored, then the rule's entry in place of the fused
 tail.  The rules exclude one another and tiling -- each owns the whole tail of a step.
@@ -186,6 +192,25 @@ def _positive(name, v):
     return f
 
 
+SELF_CONDITION_PROB = 0.5      # the default of the config key (Chen et al. 2022 train half of the batch self-conditioned)
+
+
+def parse_self_condition(spec):
+    """The config key model.diffusion.self_condition -> the argument of set_self_condition: {"prob": p} -> p, true or {} -> the default
+    0.5, absent / null / false -> None (off)."""
+    if spec is None or spec is False:
+        return None
+    if spec is True:
+        return SELF_CONDITION_PROB
+    if not hasattr(spec, 'get') or not hasattr(spec, 'keys'):
+        raise ValueError('self_condition: true or a dict with "prob" is expected (got %r)' % (spec,))
+    for k in spec.keys():
+        if k != 'prob':
+            raise ValueError('self_condition: unknown key %r (known: "prob")' % (k,))
+    p = spec.get('prob')
+    return SELF_CONDITION_PROB if p is None else p
+
+
 def prediction_coefs(kind, ca, cb):
     """What the network's output `out` stands for at the noise level x = ca x0 + cb z (ca = sqrt(abar), cb = sqrt(1 - abar)), as the four
     coefficients the engine reads:  x0 = x0_a x - x0_b out  (the step tail's a, b) and the training target  tgt_z z + tgt_x0 x0.
@@ -327,6 +352,8 @@ class EngineDiffusion(nn.Module):
         self.backprojection = None     # None: the network's x0 as it is; else {'scale': s, 'iterations': K, 'strength': l, 'resample': f} (set_backprojection)
         self.cond_drop = 0.0           # training: the probability that an image's conditioning is replaced by zeros (set_cond_drop)
         self._cond_drop_buf = None     # ... and the buffer the dropped conditioning is written to
+        self.self_condition = None     # None: off; else {'prob': p}: the network reads its own last x0 as extra input channels (set_self_condition)
+        self._self_cond_buf = None     # training: the [B, Cl + C, H, W] conditioning tensor of a self-conditioned step
         self.max_cached_loops = 3      # reverse-loop states (buffers + workspace + captured graph) kept, one per (shape, launch list)
         # schedule_opt is accepted and ignored exactly like the reference ctor (diffusion.py:80-82)
 
@@ -417,6 +444,7 @@ class EngineDiffusion(nn.Module):
             tabs = sampler_tables(self._alphas_cumprod64, steps, eta, kind=kind, walk=walk, prediction=self.prediction)
             self._check_tiled_sampler(True, getattr(self, 'tiling', None))
             self._check_rules({}, True, None)
+            self._check_self_condition(self.self_condition is not None, True, None, None)
             self.sampler = dict(type=kind, steps=int(steps), eta=float(eta))
             if kind != 'ddim' or walk != 'time':
                 self.sampler['walk'] = walk
@@ -468,6 +496,7 @@ class EngineDiffusion(nn.Module):
             t = TL.parse_tiling(dict(tile=tile, overlap=overlap, batch=batch), self.denoise_fn.plan.divisor)
             self._check_tiled_sampler(self.sampler is not None, t)
             self._check_rules({}, False, t)
+            self._check_self_condition(self.self_condition is not None, False, t, None)
             self.tiling = t
         self._loop_cache = {}
 
@@ -503,6 +532,8 @@ class EngineDiffusion(nn.Module):
         cfg = rule.validate(self, *args)
         if cfg is not None:
             self._check_rules({rule.name: cfg}, self.sampler is not None, self.tiling)
+            if rule is X.GUIDANCE:
+                self._check_self_condition(self.self_condition is not None, False, None, cfg)
         setattr(self, rule.name, cfg)
         self._loop_cache = {}
 
@@ -518,6 +549,45 @@ class EngineDiffusion(nn.Module):
         if pf > 0.0 and not self.conditional:
             raise ValueError('cond_drop on an unconditional model: there is no conditioning image to drop')
         self.cond_drop = pf
+
+    def set_self_condition(self, prob=None):
+        """Self-conditioning (Chen et al. 2022, "Analog Bits"): the network reads its own previous estimate of x0 as `channels` extra
+        input channels behind the conditioning image, so the UNet's in_channel is conditioning channels + 2 channels (9 for conditional
+        SR3, 6 for an unconditional model).  prob in [0, 1] (config key model.diffusion.self_condition: {"prob": 0.5}, or true for that
+        default): in p_losses each image is self-conditioned with that probability -- a first, gradient-free forward on zero
+        self-conditioning channels supplies its clamped x0 -- and every sampling chain feeds each step the x0 of the step before, at no
+        extra forward.  prob None: off.  Not built (NotImplementedError, here or when the loop starts): with tiling, with guidance, with
+        train.distill, the DDPM variant under a sampler."""
+        if prob is None:
+            self.self_condition = None
+        else:
+            pf = X._number('self_condition prob', prob, lambda f: 0.0 <= f <= 1.0, 'lie in [0, 1]')
+            lr = self.channels if self.conditional else 0
+            have, want = int(self.denoise_fn.plan.in_channel), lr + 2 * self.channels
+            if have != want:
+                raise ValueError('self-conditioning needs a UNet with in_channel %d (%d conditioning + 2 x %d image channels); this one has '
+                                 'in_channel %d' % (want, lr, self.channels, have))
+            self._check_self_condition(True, self.sampler is not None, self.tiling, self.guidance)
+            self.self_condition = dict(prob=pf)
+        self._self_cond_buf = None
+        self._loop_cache = {}
+
+    def _check_self_condition(self, on, sampler, tiling, guidance):
+        """What self-conditioning does not go with (the style of x0_rules.check_rule); DESIGN.md section 6 says what each would need."""
+        if not on:
+            return
+        off = 'switch self-conditioning off (set_self_condition(None))'
+        if tiling is not None:
+            raise NotImplementedError('self-conditioning with tiling: the conditioning tiles are gathered once per chain and sr3_tiled_step '
+                                      'writes no x0 back into them; use whole-image steps (set_tiling(None)) or %s' % off)
+        if guidance is not None:
+            raise NotImplementedError('self-conditioning with guidance: the second forward and the guided x0 live inside sr3_guided_step, '
+                                      'behind the point where sr3_selfcond_x0_f32 reads the output; switch one of them off '
+                                      '(set_self_condition(None) / set_guidance(None))')
+        if sampler and self.variant == 'ddpm':
+            raise NotImplementedError('self-conditioning of the DDPM variant under a sampler (DDIM, DPM-Solver++): the forward of a '
+                                      'self-conditioned step runs through sr3_unet_forward, which has no step-index -> timestep map (t_map); '
+                                      'use the ancestral sampler (set_sampler(None)) or %s' % off)
 
     def _check_rules(self, new, sampler, tiling):
         """The one compatibility check of the rules on x0 (x0_rules.check_rule: "X with tiling", "X with Y", "X of the DDPM variant under
@@ -607,7 +677,8 @@ class EngineDiffusion(nn.Module):
         return out
 
     # ---- the reverse loop ------------------------------------------------------------------------
-    def _loop_state(self, shape, cond_shape, dev, item_streams=False, tiles=None, consistency=None, guidance=None, backprojection=None):
+    def _loop_state(self, shape, cond_shape, dev, item_streams=False, tiles=None, consistency=None, guidance=None, backprojection=None,
+                    self_condition=False):
         # a captured graph bakes in the arena (the one in use: EngineUNet.use_weights), the freq table and the workspace pointer and
         # the plan's launch list: key on all of them (plan.generation changes with every set_option); the workspace is private to the state.
         # item_streams: one torch generator per image of the batch (`item_seeds` of p_sample_loop) -- the generators are
@@ -621,6 +692,8 @@ class EngineDiffusion(nn.Module):
                                                   else tuple(self.sampler['walk'])),
                *[r.key(cfgs[r.name]) for r in reversed(X.RULES)],      # back-projection, guidance, consistency
                None if tiles is None else tiles['key'])      # tiled loop: ((tile_h, tile_w), overlap, tile_batch); the geometry is the tile's
+        if self_condition:                     # (appended, so that a plain model's key stays what it was)
+            key += ('self_condition',)
         st = self._loop_cache.get(key)
         if st is None:
             st = dict(img=torch.empty(shape, device=dev), z=torch.empty(shape, device=dev),
@@ -632,6 +705,7 @@ class EngineDiffusion(nn.Module):
                 st['hist'] = torch.zeros(shape, device=dev)      # a multistep sampler: the previous step's x0 (_sample_loop zero-fills it per chain)
             if tiles is not None:
                 self._tile_buffers(st, tiles, shape, cond_shape, dev)
+            st['self_condition'] = bool(self_condition)      # cond is [B, Cl + C, H, W]: the LR channels, then the last step's x0
             for r in X.RULES:                  # the setting the state (and its captured graph) was built for, and the rule's buffers
                 if cfgs[r.name] is not None:
                     st[r.name] = dict(cfgs[r.name])
@@ -707,7 +781,9 @@ class EngineDiffusion(nn.Module):
         tile geometry (level / timestep from the device counter), then the fused tail on the full image -- blend of the tiles' eps,
         p_sample update, counter decrement (sr3_tiled_step).  A state with a rule on x0 (x0_rules.py: set_consistency, set_guidance,
         set_backprojection) runs one UNet forward that stores its output in st['eps'], then the rule's tail on the whole image in place
-        of the fused one.  A multistep rule passes its c3 table and the state's history buffer along.  st['eps'] keeps the step's
+        of the fused one.  A self-conditioned state (set_self_condition) runs unfused too: forward, then sr3_selfcond_x0_f32 writes the
+        step's x0 into the self-conditioning channels of st['cond'] for the next step's forward, then the tail.  What is fed back is the
+        network's own clamped x0, clamp(a x - b out), before any rule on x0 touches it: that is what it was trained on.  A multistep rule passes its c3 table and the state's history buffer along.  st['eps'] keeps the step's
         (blended) eps for the parity checks that read it."""
         tables, level, t_map, c3, noisy = rule = self._step_rule()
         st['z_used'] = noisy
@@ -718,6 +794,24 @@ class EngineDiffusion(nn.Module):
         hist = None if c3 is None else st['hist']
         g = st.get('grid')
         x0_rule = next((r for r in X.RULES if st.get(r.name) is not None), None)
+        if st.get('self_condition'):
+            # unfused, because x0 must be taken before x is overwritten: the forward stores its output, sr3_selfcond_x0_f32 writes
+            # clamp(a x - b out) at the device counter's row into the last C channels of cond in place -- the network's own x0, before
+            # any rule touches it: what it was trained on -- then the tail: the rule's own, or the plain update and the decrement
+            # (bit-identical to the fused call, include/sr3_mi355x.h)
+            assert t_map is None and g is None and x0_rule is not X.GUIDANCE      # (_check_self_condition refused them)
+            lib, cond, step = L.load(), st['cond'], st['step'][1:]
+            B, Cc, H, W = img.shape
+            self.denoise_fn(img, None, cond=cond, level_table=level, step_dev=step, out=st['eps'], ws=st['ws'])
+            L.check(lib.sr3_selfcond_x0_f32(L.ptr(img), L.ptr(st['eps']), L.ptr(tables[0]), L.ptr(tables[1]), L.ptr(step), None, 1, B, Cc, H, W,
+                                            L.ptr(cond), cond.shape[1], cond.shape[1] - Cc, self._stream(img.device)))
+            if x0_rule is not None:
+                x0_rule.tail(st, st[x0_rule.name], z, tables, c3, hist, None)
+            else:
+                L.check(lib.sr3_p_sample_step_hist(L.ptr(img), L.ptr(st['eps']), L.ptr(z), *[L.ptr(t) for t in tables], L.ptr(step), None, 0,
+                                                   B, Cc * H * W, 1, L.ptr(c3), L.ptr(hist), self._stream(img.device)))
+                L.check(lib.sr3_step_decrement(L.ptr(step), self._stream(img.device)))
+            return
         if x0_rule is not None:
             # the forward stores its output (level / timestep from the device counter, which only the tail's last kernel moves), then
             # the rule's tail: what it does to x0, the p_sample update and the counter decrement
@@ -754,6 +848,7 @@ class EngineDiffusion(nn.Module):
         keep_img = st['img'].clone()
         keep_step = st['step'].clone()
         keep_hist = st['hist'].clone() if st.get('hist') is not None else None
+        keep_cond = st['cond'].clone() if st.get('self_condition') else None      # (the warm-up step writes its x0 into it)
         g = torch.cuda.CUDAGraph()
         cap = None
         if any(r.warm_on_capture_stream and st.get(r.name) is not None for r in X.RULES):
@@ -771,6 +866,8 @@ class EngineDiffusion(nn.Module):
         st['step'].copy_(keep_step)
         if keep_hist is not None:
             st['hist'].copy_(keep_hist)
+        if keep_cond is not None:
+            st['cond'].copy_(keep_cond)
         torch.cuda.set_rng_state(rng, dev)
         for gen, gs in zip(gens, gstate):
             gen.set_state(gs)
@@ -829,6 +926,8 @@ class EngineDiffusion(nn.Module):
             if cfgs[r.name] is not None and r.target_kw is not None and not self.conditional and targets[r.name] is None:
                 raise NotImplementedError('%s on an unconditional model needs %s=: there is no conditioning image to %s'
                                           % (r.noun, r.target_kw, r.target_from))
+        selfc = self.self_condition is not None
+        self._check_self_condition(selfc, self.sampler is not None, tiling, cfgs.get('guidance'))
         dev = self.betas.device
         if dev.type != 'cuda':
             raise L.Sr3Error('p_sample_loop needs the model on a GPU (set gpu_ids); there is no CPU fallback')
@@ -864,7 +963,10 @@ class EngineDiffusion(nn.Module):
             self.denoise_fn.plan.set_geometry(grid.th, grid.tw)
         else:
             self.denoise_fn.plan.set_geometry(shape[2], shape[3])
-        st = self._loop_state(shape, None if cond is None else shape, dev, item_streams=item_seeds is not None, tiles=tiles, **cfgs)
+        cond_shape = None if cond is None else shape
+        if selfc:      # the state's cond: the LR channels (none for an unconditional model), then the last step's x0
+            cond_shape = (shape[0], (0 if cond is None else shape[1]) + shape[1]) + shape[2:]
+        st = self._loop_state(shape, cond_shape, dev, item_streams=item_seeds is not None, tiles=tiles, self_condition=selfc, **cfgs)
         self.denoise_fn.ensure_derived()       # a replayed graph does not pass through EngineUNet.forward
         if item_seeds is not None:
             for g, v in zip(st['gens'], item_seeds):
@@ -875,7 +977,11 @@ class EngineDiffusion(nn.Module):
             self._draw(st['img'], st['gens'])
         else:
             st['img'].copy_(torch.randn(shape, device=dev))
-        if cond is not None:
+        if selfc:                              # the LR channels once, and no estimate of x0 yet
+            st['cond'].zero_()
+            if cond is not None:
+                st['cond'][:, :shape[1]].copy_(cond)
+        elif cond is not None:
             st['cond'].copy_(cond)
             if tiles is not None:              # the conditioning image does not change: cut into tiles once
                 self._gather_tiles(st, st['cond'], st['cond_tiles'], 0, st['cond_tiles'].shape[0])
@@ -888,7 +994,7 @@ class EngineDiffusion(nn.Module):
         n_snap = sum(1 for i in range(T) if i % inter == 0)
         B = shape[0]
         ret = torch.empty((B * (n_snap + 1),) + shape[1:], device=dev)
-        ret[:B].copy_(st['cond'] if cond is not None else st['img'])
+        ret[:B].copy_(cond if selfc and cond is not None else st['cond'] if cond is not None else st['img'])
         use_graph = self.use_graph and noise_seq is None
         if use_graph and st['graph'] is None:
             self._capture(st)
@@ -945,13 +1051,17 @@ class EngineDiffusion(nn.Module):
         t = t_or_gamma.long()
         return self._q_sample_coef(x_start, self.sqrt_alphas_cumprod[t], self.sqrt_one_minus_alphas_cumprod[t], noise)
 
-    def p_losses(self, x_in, noise=None, *, gamma=None, t=None, drop_seed=None, cond_keep=None):
+    def p_losses(self, x_in, noise=None, *, gamma=None, t=None, drop_seed=None, cond_keep=None, self_cond=None):
         """sr3 diffusion.py:221-246 / ddpm :278-294.  Draws (t, gamma, z) exactly as the reference does
         (numpy global RNG for the SR3 level, torch RNG for z / the DDPM timesteps) unless injected, then
         runs forward + backward in one engine call: returns the sum-reduced L1 loss (0-dim device tensor)
         and leaves d(loss / (b c h w)) / d params in `denoise_fn.grad_arena` for the optimizer.  Under set_cond_drop(p > 0) -- or with
         `cond_keep`, one flag per image, injected -- the images whose flag is 0 train on a zero conditioning image; the flags are
-        drawn after every other draw, so a seed's (t, gamma, z) are those of the step without the key."""
+        drawn after every other draw, so a seed's (t, gamma, z) are those of the step without the key.  Under set_self_condition the
+        step trains on a [B, Cl + C, H, W] conditioning tensor: one flag per image, drawn after all of those (torch.rand(b) < prob) or
+        injected as `self_cond`; where any is set, one inference-mode forward on cat(LR, 0) at the step's own x_noisy -- no dropout, no
+        gradient: that is the method -- and sr3_selfcond_x0_f32 writes the flagged images' clamped x0 into the last C channels; then the
+        same engine call on the same (t, z).  cond_drop zeroes the LR channels only."""
         x_start = x_in['HR'].contiguous()
         b, c, h, w = x_start.shape
         dev = x_start.device
@@ -986,9 +1096,47 @@ class EngineDiffusion(nn.Module):
             keep = keep.to(torch.int32).contiguous()
             L.check(L.load().sr3_cond_drop_f32(L.ptr(cond), L.ptr(keep), b, cond[0].numel(), L.ptr(buf), self._stream(dev)))
             cond = buf
+        if self_cond is not None or self.self_condition is not None:
+            cond = self._self_condition_input(x_start, cond, noise, ca, cb, level, tstep, gamma, self_cond)
         return un.train_step(x_start, cond, noise.contiguous(), ca.contiguous(), cb.contiguous(), level, tstep,
                              grad_scale=1.0 / float(b * c * h * w), drop_seed=drop_seed,
                              objective=self._train_objective(tstep, gamma, dev))
+
+    def _self_condition_input(self, x_start, cond, noise, ca, cb, level, tstep, gamma, self_cond):
+        """The conditioning tensor of a self-conditioned training step, [B, Cl + C, H, W] in a buffer this module owns: `cond` (the LR
+        channels, already through cond_drop; None: an unconditional model), then zeros -- or, for the images whose flag is set, the
+        clamped x0 of a first forward on exactly that tensor.  The flags are the step's last draw."""
+        if self.self_condition is None:
+            raise ValueError('self_cond is given but self-conditioning is off (set_self_condition / the "self_condition" key)')
+        b, c, h, w = x_start.shape
+        dev = x_start.device
+        if self_cond is None:
+            flags = torch.rand(b, device=dev) < self.self_condition['prob']
+        else:
+            flags = torch.as_tensor(self_cond, device=dev).reshape(-1) != 0
+            if flags.numel() != b:
+                raise L.Sr3Error('p_losses: %d self_cond flags for a batch of %d' % (flags.numel(), b))
+        cl = 0 if cond is None else cond.shape[1]
+        buf = self._self_cond_buf
+        if buf is None or tuple(buf.shape) != (b, cl + c, h, w) or buf.device != dev:
+            buf = self._self_cond_buf = torch.empty((b, cl + c, h, w), device=dev)
+        buf.zero_()
+        if cond is not None:
+            buf[:, :cl].copy_(cond)
+        if not bool(flags.any()):              # (one flag byte to the host: the first pass is skipped where nobody needs it)
+            return buf
+        un = self.denoise_fn
+        with torch.no_grad():
+            x_noisy = self._q_sample_coef(x_start, ca, cb, noise)      # sr3_q_sample: the x_noisy the training step forms itself
+            out = un(x_noisy, level if self.variant == 'sr3' else tstep, cond=buf)
+        # a, b of x0 = a x - b out at the drawn levels, float64 on the host, rounded once (`prediction_coefs`)
+        ca64 = gamma.detach().double().cpu().numpy() if self.variant == 'sr3' else np.sqrt(self._alphas_cumprod64[tstep.cpu().numpy()])
+        ab = np.stack(prediction_coefs(self.prediction, ca64, np.sqrt(np.maximum(1.0 - ca64 ** 2, 0.0)))[:2])
+        ab = torch.tensor(ab, dtype=torch.float32).to(dev)
+        keep = flags.to(torch.int32).contiguous()
+        L.check(L.load().sr3_selfcond_x0_f32(L.ptr(x_noisy), L.ptr(out), L.ptr(ab[0]), L.ptr(ab[1]), None, L.ptr(keep), 1, b, c, h, w,
+                                             L.ptr(buf), cl + c, cl, self._stream(dev)))
+        return buf
 
     def _train_objective(self, tstep, gamma, dev):
         """The objective arguments of sr3_train_step_ex for one batch: (tgt_z, tgt_x0, weight, loss_kind, huber_delta), or None -- the

@@ -110,6 +110,11 @@ class Distiller(object):
     [-1, 1], as its sampling loop clamps them.  The teacher runs through its inference forward only and is never written."""
 
     def __init__(self, student, teacher, steps, walk='logsnr', guidance_scale=None, clip=True):
+        for what, m in (('student', student), ('teacher', teacher)):      # (a setting is refused before the device is looked at)
+            if getattr(m, 'self_condition', None) is not None:
+                raise NotImplementedError('self-conditioning with train.distill: the teacher\'s two steps and the student\'s pass run without a '
+                                          'first pass and write no x0 back (sr3_teacher_step_f32, sr3_distill_target_f32); switch '
+                                          'self-conditioning off (set_self_condition(None)) on the %s' % what)
         for what, m in (('student', student), ('teacher', teacher)):
             if not isinstance(m, EngineDiffusion) or getattr(m, '_alphas_cumprod64', None) is None:
                 raise ValueError('Distiller: the %s must be an EngineDiffusion with a noise schedule' % what)

@@ -463,6 +463,24 @@ int sr3_backproject_step(float* x_nchw, const float* eps_nchw, const float* z_nc
  * take the 16-byte form, the same bits).  SR3_E_BADARG: NULL pointer, non-positive size, dst overlapping src partially or keep_dev. */
 int sr3_cond_drop_f32(const float* src, const int* keep_dev, int batch, int elems_per_image, float* dst, void* stream);
 
+/* Self-conditioning (Chen et al. 2022, "Analog Bits", section 3.2): the network's own estimate of x0, written into `channels` channels of
+ * its conditioning tensor for the next forward to read.
+ *   x0 = a[row] x - b[row] out ; clamp(-1, 1) if clip        (sr3_p_sample_step's operations: every product and the difference rounded
+ *                                                             separately in fp32 -- bit for bit the x0 a step tail forms from the same x, out)
+ *   dst[b][dst_first_channel + c] = keep_dev[b] ? x0[b][c] : +0.0      for c < channels; every other channel of dst is left untouched
+ * x_nchw, out_nchw: [batch, channels, height, width]; dst_nchw: [batch, dst_channels, height, width].  step_dev non-NULL: row = *step_dev
+ * for the whole batch, read on the device -- the sampling form: capturable, behind sr3_unet_forward and in front of the step's tail, which
+ * alone moves the counter.  step_dev NULL: row = b, tab_a / tab_b hold `batch` rows -- the training form, coefficients per image.
+ * keep_dev: `batch` int32 on the device, or NULL (every image kept); a dropped image's x and out are not read.  width % 4 == 0 with
+ * x_nchw, out_nchw and dst_nchw 16-byte aligned takes the 16-byte form, anything else the one-element form: the same bits.  Plain
+ * stores, no atomics, no host synchronisation.  SR3_E_BADARG: NULL x_nchw / out_nchw / tab_a / tab_b / dst_nchw, non-positive batch,
+ * channels, height, width or dst_channels, negative dst_first_channel, dst_first_channel + channels > dst_channels, dst_nchw overlapping
+ * any other argument; SR3_E_UNSUPPORTED: batch * dst_channels * height * width >= 2^31.  Each message names the argument; nothing is
+ * launched on a refusal. */
+int sr3_selfcond_x0_f32(const float* x_nchw, const float* out_nchw, const float* tab_a, const float* tab_b, const int* step_dev,
+                        const int* keep_dev, int clip, int batch, int channels, int height, int width, float* dst_nchw,
+                        int dst_channels, int dst_first_channel, void* stream);
+
 /* out_dev[b] = the abs-quantile of the n values of image b of src [batch, n]: with v_lo, v_hi the rank_lo-th and (rank_lo + 1)-th
  * smallest |src[b][i]| (0-based; v_hi = v_lo when rank_lo == n - 1),
  *   out_dev[b] = (float)((double) v_lo + frac * ((double) v_hi - (double) v_lo))        one rounding
