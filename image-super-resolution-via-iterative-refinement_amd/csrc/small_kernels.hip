@@ -425,7 +425,7 @@ __global__ __launch_bounds__(256) void k_conv_in_nchw(const float* __restrict__ 
 // registers) is loaded once per wave and reused for `bpw` pixel blocks.  Epilogue: + bias, NHWC stores (a register's 32
 // lanes = 32 consecutive channels of a pixel), and the per-(image, slice, channel) GroupNorm partial sums in double --
 // the stand-alone statistics pass over this 67 MB tensor goes away (slice = the bpw blocks of one wave).
-// Needs W % 32 == 0, Cout = 32 NB, CIN in {3, 6, 9} (conv_in_bpw).
+// Needs W % 32 == 0, Cout = 32 NB, CIN in {3, 6, 7, 9} (conv_in_bpw).
 // ---------------------------------------------------------------------------------------------
 template <int CIN, int NB>
 __global__ __launch_bounds__(256) void k_conv_in_mfma(const float* __restrict__ a, int Ca, const float* __restrict__ bsrc,
@@ -531,9 +531,18 @@ static constexpr bool CONV_IN9_NB[5] = {false, false, false, false, false};
 #else
 static constexpr bool CONV_IN9_NB[5] = {false, true, true, true, true};
 #endif
+// 7 input channels (noise conditioning augmentation with a level plane, [LR | level | x]: K = 63, KS = 32 filter registers per 32 output
+// channels plus two 32-register A buffers, fewer than the 9-channel form): the NBs listed in CONV_IN7_NB, by the same two rules --
+// no spill, and measured faster than the VALU kernel plus the statistics pass at its layer shape
+#ifdef SR3_CONV_IN7_VALU      // A/B builds only (tools/condaug_probe.py --valu-lib): every 7-channel shape on the VALU kernel + statistics pass
+static constexpr bool CONV_IN7_NB[5] = {false, false, false, false, false};
+#else
+static constexpr bool CONV_IN7_NB[5] = {false, true, true, true, true};
+#endif
 static int conv_in_bpw(int Cin, int H, int W, int Cout) {
-  if ((Cin != 3 && Cin != 6 && Cin != 9) || (W & 31) || (Cout & 31) || Cout > 128 || Cout < 32) return 0;
+  if ((Cin != 3 && Cin != 6 && Cin != 7 && Cin != 9) || (W & 31) || (Cout & 31) || Cout > 128 || Cout < 32) return 0;
   if (Cin == 9 && !CONV_IN9_NB[Cout / 32]) return 0;
+  if (Cin == 7 && !CONV_IN7_NB[Cout / 32]) return 0;
   const int bpi = H * W / 32;
   return (bpi % 4 == 0) ? 4 : 1;
 }
@@ -549,15 +558,20 @@ int conv_in_nchw(const float* a, int Ca, const float* b, int Cb, int B, int H, i
     const long tasks = (long)B * T;
     const dim3 grid((unsigned)((tasks + 3) / 4));
 #define SR3_CI(CIN, NB) hipLaunchKernelGGL((k_conv_in_mfma<CIN, NB>), grid, dim3(256), 0, st, a, Ca, b, Cb, B, H, W, w, bias, out, ostat, bpw, T)
+#define SR3_CI_NB(CIN) do { if (nb == 1) SR3_CI(CIN, 1); else if (nb == 2) SR3_CI(CIN, 2); else if (nb == 3) SR3_CI(CIN, 3); else SR3_CI(CIN, 4); } while (0)
     const int nb = Cout / 32;
-    if (Ca + Cb == 6) { if (nb == 1) SR3_CI(6, 1); else if (nb == 2) SR3_CI(6, 2); else if (nb == 3) SR3_CI(6, 3); else SR3_CI(6, 4); }
-    else if (Ca + Cb == 9) { if (nb == 1) SR3_CI(9, 1); else if (nb == 2) SR3_CI(9, 2); else if (nb == 3) SR3_CI(9, 3); else SR3_CI(9, 4); }
-    else { if (nb == 1) SR3_CI(3, 1); else if (nb == 2) SR3_CI(3, 2); else if (nb == 3) SR3_CI(3, 3); else SR3_CI(3, 4); }
+    switch (Ca + Cb) {                     // (conv_in_bpw let nothing else through)
+      case 3: SR3_CI_NB(3); break;
+      case 6: SR3_CI_NB(6); break;
+      case 7: SR3_CI_NB(7); break;
+      default: SR3_CI_NB(9); break;
+    }
+#undef SR3_CI_NB
 #undef SR3_CI
     SR3_LAUNCH_CHECK("k_conv_in_mfma");
     return SR3_OK;
   }
-  if (ostat) { set_error("conv_in: fused output statistics need the MFMA form (W %% 32 == 0, Cout %% 32 == 0, 3, 6 or 9 input channels)"); return SR3_E_UNSUPPORTED; }
+  if (ostat) { set_error("conv_in: fused output statistics need the MFMA form (W %% 32 == 0, Cout %% 32 == 0, 3, 6, 7 or 9 input channels)"); return SR3_E_UNSUPPORTED; }
   if (Cout & 3) { set_error("conv_in: Cout %% 4 != 0"); return SR3_E_UNSUPPORTED; }
   const int CoutP = (Cout + 63) & ~63;
   const size_t smem = (size_t)9 * (Ca + Cb) * CoutP * sizeof(float);

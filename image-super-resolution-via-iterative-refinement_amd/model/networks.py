@@ -55,6 +55,11 @@ def define_G(opt):
     if d.get('self_condition') is not None:
         from sr3_hip.diffusion import parse_self_condition
         netG.set_self_condition(parse_self_condition(d['self_condition']))
+    # "cond_augment": {"max_level": 0.5, "sample_level": 0.1, "level_channel": true} -- the network reads the conditioning image diffused to
+    # a level of its own, and that level as one more input plane (set_cond_augment; unet.in_channel is then conditioning channels + 1 + channels)
+    if d.get('cond_augment') is not None:
+        from sr3_hip.diffusion import parse_cond_augment
+        netG.set_cond_augment(**parse_cond_augment(d['cond_augment']))
     if opt['phase'] == 'train':
         init_weights(netG, init_type='orthogonal')
     return netG

@@ -33,6 +33,13 @@ inference forward on zero self-conditioning channels supplies the clamped x0 of 
 image), then the same engine call as before.  Sampling: every step runs forward -> sr3_selfcond_x0_f32 (the device counter's row, in
 place into the state's cond) -> the tail, captured as it is; what is fed back is the network's own clamped x0 before any rule on x0.
 
+Noise conditioning augmentation (engine extension, `"cond_augment": {"max_level": 0.5, "sample_level": 0.1, "level_channel": true}` in
+model.diffusion or `set_cond_augment`; Ho et al. 2021, Sahak et al. 2023): the network reads the conditioning image diffused to a level s
+of its own, a c + s eps with a = sqrt(1 - s^2), and -- with the level channel -- s as one more input plane, [LR | level | x].  Training
+draws s per image up to max_level (sr3_cond_augment_f32, which applies cond_drop in the same call); sampling builds the state's cond
+once per chain at sample_level, so no step changes.  Whatever reads the conditioning image as data -- the first snapshot, the rules'
+targets -- reads the clean one.
+
 Rules on x0 (engine extensions, keys next to "sampler" / "tiling" or the setters; sr3_hip/x0_rules.py holds each rule once): what is done
 to the predicted x0 before the posterior mix.  Per step: UNet forward with the output stored, then the rule's entry in place of the fused
 tail.  The rules exclude one another and tiling -- each owns the whole tail of a step.
@@ -211,6 +218,34 @@ def parse_self_condition(spec):
     return SELF_CONDITION_PROB if p is None else p
 
 
+COND_AUGMENT_KEYS = ('max_level', 'sample_level', 'level_channel')
+
+
+def parse_cond_augment(spec):
+    """The config key model.diffusion.cond_augment -> the keyword arguments of set_cond_augment: {"max_level": m, "sample_level": s,
+    "level_channel": bool} ("max_level" required; sample_level 0.0 and level_channel true where absent), absent / null -> max_level
+    None (off)."""
+    if spec is None:
+        return dict(max_level=None)
+    if not hasattr(spec, 'get') or not hasattr(spec, 'keys'):
+        raise ValueError('cond_augment: a dict with "max_level" is expected (got %r)' % (spec,))
+    for k in spec.keys():
+        if k not in COND_AUGMENT_KEYS:
+            raise ValueError('cond_augment: unknown key %r (known: %s)' % (k, ', '.join('"%s"' % n for n in COND_AUGMENT_KEYS)))
+    if spec.get('max_level') is None:
+        raise ValueError('cond_augment: "max_level" is required')
+    return dict(max_level=spec['max_level'], sample_level=spec.get('sample_level', 0.0), level_channel=spec.get('level_channel', True))
+
+
+def cond_level_coefs(s):
+    """(a, s) of the augmented conditioning image a c + s eps as two fp32 tensors: s (numbers or a tensor, on any device) rounded to fp32
+    first, then a = sqrt(1 - s^2) in float64 of that fp32 s, rounded once -- so a^2 + s^2 is 1 to fp32 rounding, and s = 0 gives a = 1
+    exactly.  Every operation is a correctly rounded IEEE one: the host and the device give the same bits."""
+    s32 = torch.as_tensor(s, dtype=torch.float32).reshape(-1).contiguous()
+    a32 = (1.0 - s32.double() ** 2).sqrt().float()
+    return a32, s32
+
+
 def prediction_coefs(kind, ca, cb):
     """What the network's output `out` stands for at the noise level x = ca x0 + cb z (ca = sqrt(abar), cb = sqrt(1 - abar)), as the four
     coefficients the engine reads:  x0 = x0_a x - x0_b out  (the step tail's a, b) and the training target  tgt_z z + tgt_x0 x0.
@@ -354,6 +389,8 @@ class EngineDiffusion(nn.Module):
         self._cond_drop_buf = None     # ... and the buffer the dropped conditioning is written to
         self.self_condition = None     # None: off; else {'prob': p}: the network reads its own last x0 as extra input channels (set_self_condition)
         self._self_cond_buf = None     # training: the [B, Cl + C, H, W] conditioning tensor of a self-conditioned step
+        self.cond_augment = None       # None: off; else {'max_level': m, 'sample_level': s, 'level_channel': bool} (set_cond_augment)
+        self._cond_aug_buf = None      # training: the [B, Cl (+ 1), H, W] augmented conditioning tensor
         self.max_cached_loops = 3      # reverse-loop states (buffers + workspace + captured graph) kept, one per (shape, launch list)
         # schedule_opt is accepted and ignored exactly like the reference ctor (diffusion.py:80-82)
 
@@ -562,6 +599,7 @@ class EngineDiffusion(nn.Module):
             self.self_condition = None
         else:
             pf = X._number('self_condition prob', prob, lambda f: 0.0 <= f <= 1.0, 'lie in [0, 1]')
+            self._check_cond_augment(self.cond_augment, True)      # (before the channel count: the two ask for different ones)
             lr = self.channels if self.conditional else 0
             have, want = int(self.denoise_fn.plan.in_channel), lr + 2 * self.channels
             if have != want:
@@ -588,6 +626,46 @@ class EngineDiffusion(nn.Module):
             raise NotImplementedError('self-conditioning of the DDPM variant under a sampler (DDIM, DPM-Solver++): the forward of a '
                                       'self-conditioned step runs through sr3_unet_forward, which has no step-index -> timestep map (t_map); '
                                       'use the ancestral sampler (set_sampler(None)) or %s' % off)
+
+    def set_cond_augment(self, max_level=None, sample_level=0.0, level_channel=True):
+        """Noise conditioning augmentation (Ho et al. 2021, "Cascaded Diffusion Models"; Sahak et al. 2023): the network reads the
+        conditioning image c diffused to a level of its own, sqrt(1 - s^2) c + s eps, s the noise's standard deviation.  In p_losses
+        every image draws s = max_level * U[0, 1); every sampling chain applies s = sample_level once, after x_T is drawn (0: the clean
+        image, nothing is drawn).  Both lie in [0, 1).  level_channel True: the network is told s as one more input plane, [LR | level
+        | x], so the UNet's in_channel is conditioning channels + 1 + channels (7 for SR3); False ("blind"): in_channel stays and only
+        the LR channels are noised -- an existing checkpoint can be sampled with it.  The first snapshot of a chain and the targets of
+        set_consistency / set_backprojection are made from the clean image.  max_level None: off.  Config key
+        model.diffusion.cond_augment.  Not built (NotImplementedError, here or when the loop starts): the level channel together with
+        self-conditioning, train.distill."""
+        if max_level is None:
+            self.cond_augment = None
+        else:
+            in_range = lambda f: 0.0 <= f < 1.0
+            cfg = dict(max_level=X._number('cond_augment max_level', max_level, in_range, 'lie in [0, 1)'),
+                       sample_level=X._number('cond_augment sample_level', sample_level, in_range, 'lie in [0, 1)'))
+            if not isinstance(level_channel, (bool, np.bool_)):
+                raise ValueError('cond_augment level_channel must be true or false (got %r)' % (level_channel,))
+            cfg['level_channel'] = bool(level_channel)
+            if not self.conditional:
+                raise ValueError('cond_augment on an unconditional model: there is no conditioning image to augment')
+            self._check_cond_augment(cfg, self.self_condition is not None)
+            if cfg['level_channel']:
+                have, want = int(self.denoise_fn.plan.in_channel), 2 * self.channels + 1
+                if have != want:
+                    raise ValueError('cond_augment with the level channel needs a UNet with in_channel %d (%d conditioning + 1 level + %d '
+                                     'image channels); this one has in_channel %d' % (want, self.channels, self.channels, have))
+            self.cond_augment = cfg
+        self._cond_aug_buf = None
+        self._loop_cache = {}
+
+    @staticmethod
+    def _check_cond_augment(cfg, self_condition):
+        """What noise conditioning augmentation does not go with; DESIGN.md section 6 says what it would need."""
+        if cfg is not None and cfg['level_channel'] and self_condition:
+            raise NotImplementedError('cond_augment with the level channel together with self-conditioning: a 10-channel input [LR | level '
+                                      '| last x0 | x], for which the input conv has no MFMA form and no model was measured; use the blind '
+                                      'form ("level_channel": false) or switch one of them off (set_cond_augment(None) / '
+                                      'set_self_condition(None))')
 
     def _check_rules(self, new, sampler, tiling):
         """The one compatibility check of the rules on x0 (x0_rules.check_rule: "X with tiling", "X with Y", "X of the DDPM variant under
@@ -678,7 +756,7 @@ class EngineDiffusion(nn.Module):
 
     # ---- the reverse loop ------------------------------------------------------------------------
     def _loop_state(self, shape, cond_shape, dev, item_streams=False, tiles=None, consistency=None, guidance=None, backprojection=None,
-                    self_condition=False):
+                    self_condition=False, cond_augment=False):
         # a captured graph bakes in the arena (the one in use: EngineUNet.use_weights), the freq table and the workspace pointer and
         # the plan's launch list: key on all of them (plan.generation changes with every set_option); the workspace is private to the state.
         # item_streams: one torch generator per image of the batch (`item_seeds` of p_sample_loop) -- the generators are
@@ -694,6 +772,8 @@ class EngineDiffusion(nn.Module):
                None if tiles is None else tiles['key'])      # tiled loop: ((tile_h, tile_w), overlap, tile_batch); the geometry is the tile's
         if self_condition:                     # (appended, so that a plain model's key stays what it was)
             key += ('self_condition',)
+        if cond_augment:                       # (appended too: the state's cond is the augmented tensor, made once per chain)
+            key += ('cond_augment',)
         st = self._loop_cache.get(key)
         if st is None:
             st = dict(img=torch.empty(shape, device=dev), z=torch.empty(shape, device=dev),
@@ -706,6 +786,7 @@ class EngineDiffusion(nn.Module):
             if tiles is not None:
                 self._tile_buffers(st, tiles, shape, cond_shape, dev)
             st['self_condition'] = bool(self_condition)      # cond is [B, Cl + C, H, W]: the LR channels, then the last step's x0
+            st['cond_augment'] = bool(cond_augment)          # cond holds the augmented LR channels (and the level plane behind them)
             for r in X.RULES:                  # the setting the state (and its captured graph) was built for, and the rule's buffers
                 if cfgs[r.name] is not None:
                     st[r.name] = dict(cfgs[r.name])
@@ -880,23 +961,26 @@ class EngineDiffusion(nn.Module):
 
     @torch.no_grad()
     def p_sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None, consistency_target=None,
-                      backprojection_target=None):
+                      backprojection_target=None, cond_noise=None):
         """The reverse loop (`_sample_loop`); with tiling set (set_tiling / the "tiling" key) an input larger than the tile on either axis
         goes through the tiled loop instead.  consistency_target: under set_consistency, the [B, C, H / block, W / block] block means to
         steer towards instead of the conditioning image's (the dataset's real LR image when block is the scale factor).
         backprojection_target: under set_backprojection, the [B, C, H / scale, W / scale] LR image, in the model's range, to steer
-        towards instead of the down-sampled conditioning image (the dataset's real LR image)."""
+        towards instead of the down-sampled conditioning image (the dataset's real LR image).  cond_noise: under set_cond_augment, the
+        noise added to the conditioning image at sample_level, injected instead of drawn."""
         t = self.tiling
         if t is not None:
             shape = tuple(x_in) if not self.conditional else tuple(x_in.shape)
             if len(shape) == 4 and (shape[2] > t['tile'][0] or shape[3] > t['tile'][1]):
                 return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, tiling=t,
-                                         consistency_target=consistency_target, backprojection_target=backprojection_target)
+                                         consistency_target=consistency_target, backprojection_target=backprojection_target,
+                                         cond_noise=cond_noise)
         return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, consistency_target=consistency_target,
-                                 backprojection_target=backprojection_target)
+                                 backprojection_target=backprojection_target, cond_noise=cond_noise)
 
     @torch.no_grad()
-    def p_sample_loop_tiled(self, x_in, continous=False, *, tile, overlap, tile_batch=None, x_T=None, noise_seq=None, item_seeds=None):
+    def p_sample_loop_tiled(self, x_in, continous=False, *, tile, overlap, tile_batch=None, x_T=None, noise_seq=None, item_seeds=None,
+                            cond_noise=None):
         """p_sample_loop as ONE chain over overlapping tiles: at every step the UNet predicts eps on tiles of size `tile` (int or
         (th, tw); an axis the tile covers has one tile of the image's size), `tile_batch` of them per forward (None: all, at most 16),
         the predictions are blended by the separable ramp of sr3_hip.tiling.axis_window and one p_sample update moves the whole image.
@@ -904,10 +988,10 @@ class EngineDiffusion(nn.Module):
         p_sample_loop's.  The result is not the whole-image result and is not meant to be: every forward sees the token count and the
         normalisation statistics of the training size.  With tile >= image on both axes it IS the whole-image loop, bit for bit."""
         t = TL.parse_tiling(dict(tile=tile, overlap=overlap, batch=tile_batch), self.denoise_fn.plan.divisor)
-        return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, tiling=t)
+        return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, tiling=t, cond_noise=cond_noise)
 
     def _sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None, tiling=None, consistency_target=None,
-                     backprojection_target=None):
+                     backprojection_target=None, cond_noise=None):
         """sr3 diffusion.py:176-200 / ddpm :200-230.  Extensions: `x_T` injects the initial draw, `noise_seq[i]` the noise
         consumed at step i (the parity tests); `item_seeds` (one int per image of the batch) gives every image its own noise
         stream -- x_T and every step's z of image i come from a generator seeded with item_seeds[i], so the image's chain does
@@ -916,7 +1000,10 @@ class EngineDiffusion(nn.Module):
         the step index S-1 .. 0 (what `noise_seq` and the snapshot stride 1 | S // 10 go by), and eta = 0 draws x_T only.  Under
         set_consistency every step is an LR-consistent one (`_one_step`), towards the block means of the conditioning image or
         `consistency_target`.  Under set_guidance every step is a guided one.  Under set_backprojection every step is a back-projected
-        one, towards `backprojection_target` or the down-sampled conditioning image."""
+        one, towards `backprojection_target` or the down-sampled conditioning image.  Under set_cond_augment the state's cond is built
+        once per chain, after x_T is drawn, from the clean conditioning image at sample_level (sr3_cond_augment_f32; the noise from the
+        chain's own source -- the per-item generators, torch.randn, or `cond_noise`); the first snapshot and the rules' targets are the
+        clean image's."""
         cfgs = {r.name: getattr(self, r.name) for r in X.RULES}
         targets = dict(consistency=consistency_target, backprojection=backprojection_target)
         for r in X.RULES:
@@ -928,6 +1015,10 @@ class EngineDiffusion(nn.Module):
                                           % (r.noun, r.target_kw, r.target_from))
         selfc = self.self_condition is not None
         self._check_self_condition(selfc, self.sampler is not None, tiling, cfgs.get('guidance'))
+        aug = self.cond_augment
+        self._check_cond_augment(aug, selfc)
+        if cond_noise is not None and aug is None:
+            raise ValueError('cond_noise is given but noise conditioning augmentation is off (set_cond_augment / the "cond_augment" key)')
         dev = self.betas.device
         if dev.type != 'cuda':
             raise L.Sr3Error('p_sample_loop needs the model on a GPU (set gpu_ids); there is no CPU fallback')
@@ -966,7 +1057,12 @@ class EngineDiffusion(nn.Module):
         cond_shape = None if cond is None else shape
         if selfc:      # the state's cond: the LR channels (none for an unconditional model), then the last step's x0
             cond_shape = (shape[0], (0 if cond is None else shape[1]) + shape[1]) + shape[2:]
-        st = self._loop_state(shape, cond_shape, dev, item_streams=item_seeds is not None, tiles=tiles, self_condition=selfc, **cfgs)
+        elif aug is not None and aug['level_channel']:      # the (augmented) LR channels, then the level plane
+            cond_shape = (shape[0], shape[1] + 1) + shape[2:]
+        if cond_noise is not None and (tuple(cond_noise.shape) != shape or cond_noise.device != dev or cond_noise.dtype != torch.float32):
+            raise L.Sr3Error('p_sample_loop: cond_noise must be an fp32 tensor of the conditioning image\'s shape %s on %s' % (shape, dev))
+        st = self._loop_state(shape, cond_shape, dev, item_streams=item_seeds is not None, tiles=tiles, self_condition=selfc,
+                              cond_augment=aug is not None, **cfgs)
         self.denoise_fn.ensure_derived()       # a replayed graph does not pass through EngineUNet.forward
         if item_seeds is not None:
             for g, v in zip(st['gens'], item_seeds):
@@ -981,20 +1077,24 @@ class EngineDiffusion(nn.Module):
             st['cond'].zero_()
             if cond is not None:
                 st['cond'][:, :shape[1]].copy_(cond)
+        elif aug is not None and aug['level_channel']:      # the clean LR channels for the rules below; the augmented ones replace them
+            st['cond'][:, :shape[1]].copy_(cond)
         elif cond is not None:
             st['cond'].copy_(cond)
-            if tiles is not None:              # the conditioning image does not change: cut into tiles once
-                self._gather_tiles(st, st['cond'], st['cond_tiles'], 0, st['cond_tiles'].shape[0])
-        for r in X.RULES:                      # a rule's target does not change over the chain: made once
-            if cfgs[r.name] is not None:
+        for r in X.RULES:                     # a rule's target does not change over the chain: made once -- from the clean
+            if cfgs[r.name] is not None:       # conditioning image: st['cond'] is augmented only behind this
                 r.prepare(st, cfgs[r.name], shape, targets.get(r.name), dev)
+        if aug is not None:
+            self._augment_sampling_cond(st, aug, cond, cond_noise)
+        if tiles is not None and cond is not None:      # the conditioning tensor does not change over the chain: cut into tiles once
+            self._gather_tiles(st, st['cond'], st['cond_tiles'], 0, st['cond_tiles'].shape[0])
         if st.get('hist') is not None:         # the first step's c3 is 0, but 0 * (whatever the last chain left, a NaN for one) is not 0
             st['hist'].zero_()
         st['step'].fill_(T - 1)                # (slot 1 = t of the next step; slot 0 is the step's scratch copy)
         n_snap = sum(1 for i in range(T) if i % inter == 0)
         B = shape[0]
         ret = torch.empty((B * (n_snap + 1),) + shape[1:], device=dev)
-        ret[:B].copy_(cond if selfc and cond is not None else st['cond'] if cond is not None else st['img'])
+        ret[:B].copy_(cond if (selfc or aug is not None) and cond is not None else st['cond'] if cond is not None else st['img'])
         use_graph = self.use_graph and noise_seq is None
         if use_graph and st['graph'] is None:
             self._capture(st)
@@ -1025,14 +1125,35 @@ class EngineDiffusion(nn.Module):
             return st['img'].clone()            # ddpm diffusion.py:215 returns img, ignoring `continous`
         return ret if continous else ret[-1]
 
+    def _augment_sampling_cond(self, st, aug, cond, cond_noise):
+        """The LR channels of st['cond'] (and the level plane behind them) <- the clean `cond` at sample_level, once per chain.  Level 0
+        draws nothing: the blind form leaves the clean copy that is there, the level-channel form writes a zero plane."""
+        s, plane = aug['sample_level'], aug['level_channel']
+        if s == 0.0 and not plane:
+            return
+        B, Cl, H, W = cond.shape
+        dev = cond.device
+        eps = None
+        if s > 0.0:
+            eps = cond_noise
+            if eps is None:
+                eps = torch.empty_like(cond)
+                self._draw(eps, st['gens'])      # (behind x_T in every stream: x_T is what it is without the key)
+            eps = eps.contiguous()
+        a_dev, s_dev = (t.to(dev) for t in cond_level_coefs([s] * B))
+        dst = st['cond']
+        L.check(L.load().sr3_cond_augment_f32(L.ptr(cond), L.ptr(eps), L.ptr(a_dev), L.ptr(s_dev), None, 1 if plane else 0, L.ptr(dst),
+                                              dst.shape[1], 0, B, Cl, H, W, self._stream(dev)))
+
     @torch.no_grad()
     def sample(self, batch_size=1, continous=False, *, item_seeds=None):
         return self.p_sample_loop((batch_size, self.channels, self.image_size, self.image_size), continous, item_seeds=item_seeds)
 
     @torch.no_grad()
-    def super_resolution(self, x_in, continous=False, *, item_seeds=None, consistency_target=None, backprojection_target=None):
+    def super_resolution(self, x_in, continous=False, *, item_seeds=None, consistency_target=None, backprojection_target=None,
+                         cond_noise=None):
         return self.p_sample_loop(x_in, continous, item_seeds=item_seeds, consistency_target=consistency_target,
-                                  backprojection_target=backprojection_target)
+                                  backprojection_target=backprojection_target, cond_noise=cond_noise)
 
     # ---- forward process / loss --------------------------------------------------------------------
     def _q_sample_coef(self, x_start, ca, cb, noise):
@@ -1051,7 +1172,8 @@ class EngineDiffusion(nn.Module):
         t = t_or_gamma.long()
         return self._q_sample_coef(x_start, self.sqrt_alphas_cumprod[t], self.sqrt_one_minus_alphas_cumprod[t], noise)
 
-    def p_losses(self, x_in, noise=None, *, gamma=None, t=None, drop_seed=None, cond_keep=None, self_cond=None):
+    def p_losses(self, x_in, noise=None, *, gamma=None, t=None, drop_seed=None, cond_keep=None, self_cond=None, cond_level=None,
+                 cond_noise=None):
         """sr3 diffusion.py:221-246 / ddpm :278-294.  Draws (t, gamma, z) exactly as the reference does
         (numpy global RNG for the SR3 level, torch RNG for z / the DDPM timesteps) unless injected, then
         runs forward + backward in one engine call: returns the sum-reduced L1 loss (0-dim device tensor)
@@ -1061,7 +1183,11 @@ class EngineDiffusion(nn.Module):
         step trains on a [B, Cl + C, H, W] conditioning tensor: one flag per image, drawn after all of those (torch.rand(b) < prob) or
         injected as `self_cond`; where any is set, one inference-mode forward on cat(LR, 0) at the step's own x_noisy -- no dropout, no
         gradient: that is the method -- and sr3_selfcond_x0_f32 writes the flagged images' clamped x0 into the last C channels; then the
-        same engine call on the same (t, z).  cond_drop zeroes the LR channels only."""
+        same engine call on the same (t, z).  cond_drop zeroes the LR channels only.  Under set_cond_augment the step trains on the
+        conditioning image diffused to a level per image: s = max_level * torch.rand(b), then eps = randn_like(cond), drawn behind
+        cond_drop's flags and in front of self-conditioning's (or injected as `cond_level`, one level in [0, 1) per image, and
+        `cond_noise`); sr3_cond_augment_f32 writes sqrt(1 - s^2) cond + s eps -- and, with the level channel, the plane of s behind it --
+        into a buffer this module owns, zeroing the images cond_drop dropped, level plane included, in the same call."""
         x_start = x_in['HR'].contiguous()
         b, c, h, w = x_start.shape
         dev = x_start.device
@@ -1084,16 +1210,20 @@ class EngineDiffusion(nn.Module):
         if noise is None:
             noise = torch.randn_like(x_start)
         cond = x_in['SR'].contiguous() if self.conditional else None
+        keep = None
         if cond_keep is not None or self.cond_drop > 0.0:
             if cond is None:
                 raise ValueError('cond_keep on an unconditional model: there is no conditioning image to drop')
             keep = (torch.rand(b, device=dev) >= self.cond_drop) if cond_keep is None else torch.as_tensor(cond_keep, device=dev).reshape(-1) != 0
             if keep.numel() != b:
                 raise L.Sr3Error('p_losses: %d cond_keep flags for a batch of %d' % (keep.numel(), b))
+            keep = keep.to(torch.int32).contiguous()
+        if cond_level is not None or cond_noise is not None or self.cond_augment is not None:
+            cond = self._cond_augment_input(cond, keep, cond_level, cond_noise)      # (cond_drop applied in the same call)
+        elif keep is not None:
             buf = self._cond_drop_buf
             if buf is None or buf.shape != cond.shape or buf.device != dev:
                 buf = self._cond_drop_buf = torch.empty_like(cond)
-            keep = keep.to(torch.int32).contiguous()
             L.check(L.load().sr3_cond_drop_f32(L.ptr(cond), L.ptr(keep), b, cond[0].numel(), L.ptr(buf), self._stream(dev)))
             cond = buf
         if self_cond is not None or self.self_condition is not None:
@@ -1101,6 +1231,38 @@ class EngineDiffusion(nn.Module):
         return un.train_step(x_start, cond, noise.contiguous(), ca.contiguous(), cb.contiguous(), level, tstep,
                              grad_scale=1.0 / float(b * c * h * w), drop_seed=drop_seed,
                              objective=self._train_objective(tstep, gamma, dev))
+
+    def _cond_augment_input(self, cond, keep, cond_level, cond_noise):
+        """The conditioning tensor of a training step under noise conditioning augmentation, [B, Cl (+ 1), H, W] in a buffer this module
+        owns: sqrt(1 - s^2) cond + s eps per image, then the level plane; all zeros for the images whose `keep` flag (int32 on the
+        device, or None) is 0.  The levels, then the noise, are the step's draws behind cond_drop's."""
+        aug = self.cond_augment
+        if aug is None:
+            raise ValueError('cond_level / cond_noise is given but noise conditioning augmentation is off (set_cond_augment / the '
+                             '"cond_augment" key)')
+        b, cl, h, w = cond.shape
+        dev = cond.device
+        if cond_level is None:
+            level = aug['max_level'] * torch.rand(b, device=dev)
+        else:
+            level = torch.as_tensor(cond_level, dtype=torch.float32).reshape(-1)
+            if level.numel() != b:
+                raise L.Sr3Error('p_losses: %d cond_level values for a batch of %d' % (level.numel(), b))
+            if not bool(((level >= 0.0) & (level < 1.0)).all()):
+                raise ValueError('cond_level must lie in [0, 1) (got %r)' % (level.tolist(),))
+            level = level.to(dev)
+        if cond_noise is None:
+            cond_noise = torch.randn_like(cond)
+        elif tuple(cond_noise.shape) != tuple(cond.shape) or cond_noise.device != dev or cond_noise.dtype != torch.float32:
+            raise L.Sr3Error('p_losses: cond_noise must be an fp32 tensor of the conditioning image\'s shape %s on %s' % (tuple(cond.shape), dev))
+        a_dev, s_dev = cond_level_coefs(level)
+        plane = 1 if aug['level_channel'] else 0
+        buf = self._cond_aug_buf
+        if buf is None or tuple(buf.shape) != (b, cl + plane, h, w) or buf.device != dev:
+            buf = self._cond_aug_buf = torch.empty((b, cl + plane, h, w), device=dev)
+        L.check(L.load().sr3_cond_augment_f32(L.ptr(cond), L.ptr(cond_noise.contiguous()), L.ptr(a_dev), L.ptr(s_dev), L.ptr(keep), plane,
+                                              L.ptr(buf), cl + plane, 0, b, cl, h, w, self._stream(dev)))
+        return buf
 
     def _self_condition_input(self, x_start, cond, noise, ca, cb, level, tstep, gamma, self_cond):
         """The conditioning tensor of a self-conditioned training step, [B, Cl + C, H, W] in a buffer this module owns: `cond` (the LR

@@ -101,6 +101,16 @@ def _same_network(s, t):
             and ps.in_channel == pt.in_channel and ps.out_channel == pt.out_channel)
 
 
+def _refuse_cond_augment(student, teacher):
+    """noise conditioning augmentation is not built into the distillation step (when a Distiller is made, and again at every step: the
+    setting may be switched on behind it)"""
+    for what, m in (('student', student), ('teacher', teacher)):
+        if getattr(m, 'cond_augment', None) is not None:
+            raise NotImplementedError('cond_augment with train.distill: teacher and student read the conditioning batch as it is given '
+                                      '(Distiller.step draws no level and makes no augmented tensor, and both would have to read the '
+                                      'same one); switch noise conditioning augmentation off (set_cond_augment(None)) on the %s' % what)
+
+
 class Distiller(object):
     """One round of progressive distillation: `step` trains `student` (an EngineDiffusion on a GPU) to do in one DDIM step what the
     frozen `teacher` -- a second network of the same variant, geometry and conditioning, with its own plan, arena and derived weights --
@@ -115,6 +125,7 @@ class Distiller(object):
                 raise NotImplementedError('self-conditioning with train.distill: the teacher\'s two steps and the student\'s pass run without a '
                                           'first pass and write no x0 back (sr3_teacher_step_f32, sr3_distill_target_f32); switch '
                                           'self-conditioning off (set_self_condition(None)) on the %s' % what)
+        _refuse_cond_augment(student, teacher)
         for what, m in (('student', student), ('teacher', teacher)):
             if not isinstance(m, EngineDiffusion) or getattr(m, '_alphas_cumprod64', None) is None:
                 raise ValueError('Distiller: the %s must be an EngineDiffusion with a noise schedule' % what)
@@ -184,6 +195,7 @@ class Distiller(object):
         kernels, then the student's train_step.  Returns the sum-reduced loss (0-dim device tensor) and leaves the gradients in the
         student's grad_arena, exactly as p_losses does."""
         st, te = self.student, self.teacher
+        _refuse_cond_augment(st, te)
         dev = self.device
         x_start = data['HR']
         if not torch.is_tensor(x_start) or x_start.device != dev or x_start.dim() != 4 or x_start.dtype != torch.float32:

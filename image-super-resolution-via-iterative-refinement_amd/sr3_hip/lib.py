@@ -102,6 +102,7 @@ SIGNATURES = {
                                   _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _Z, _P]),
     'sr3_cond_drop_f32': (_I, [_P, _P, _I, _I, _P, _P]),
     'sr3_selfcond_x0_f32': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
+    'sr3_cond_augment_f32': (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     'sr3_abs_quantile_scratch_bytes': (_Z, [_I, _I]),
     'sr3_abs_quantile_f32': (_I, [_P, _I, _I, _I, C.c_double, _P, _P, _Z, _P]),
     'sr3_guided_step': (_I, [_P, _P, _P, _F, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_double, _P, _P, _Z, _P, _P]),

@@ -481,6 +481,26 @@ int sr3_selfcond_x0_f32(const float* x_nchw, const float* out_nchw, const float*
                         const int* keep_dev, int clip, int batch, int channels, int height, int width, float* dst_nchw,
                         int dst_channels, int dst_first_channel, void* stream);
 
+/* Noise conditioning augmentation (Ho et al. 2021, "Cascaded Diffusion Models", section 4.2; Sahak et al. 2023): the conditioning image
+ * diffused to a level of its own, written into `channels` channels of the tensor the network reads, with the level as one more plane.
+ *   aug = s[b] == 0 ? src : a[b] src + s[b] eps              (both products and the sum rounded separately in fp32, no contraction;
+ *                                                             s = the noise's standard deviation, a = sqrt(1 - s^2), both the host's)
+ *   dst[b][dst_first_channel + c]        = keep_dev[b] ? aug  : +0.0      for c < channels
+ *   dst[b][dst_first_channel + channels] = keep_dev[b] ? s[b] : +0.0      with level_channel != 0 only
+ * and every other channel of dst is left untouched.  src_nchw, eps_nchw: [batch, channels, height, width]; dst_nchw: [batch,
+ * dst_channels, height, width]; a_dev, s_dev: `batch` fp32 on the device; keep_dev: `batch` int32 on the device, or NULL (every image
+ * kept).  eps_nchw NULL is the form that reads no noise: the channels are copied (a_dev is not read and may be NULL), the level plane is
+ * still s.  An image at s[b] == 0 is a bit copy of src and its eps is not read; a dropped image's src and eps are not read, and its level
+ * plane is +0.0 too -- the all-zero tensor the second forward of a guided step reads.  height * width % 4 == 0 with src_nchw, eps_nchw
+ * and dst_nchw 16-byte aligned takes the 16-byte form, anything else the one-element form: the same bits.  One launch, plain stores, no
+ * atomics, no host synchronisation.  Checked in this order, nothing launched on a refusal, each message names the argument --
+ * SR3_E_BADARG: NULL src_nchw / s_dev / dst_nchw, NULL a_dev with eps_nchw given, non-positive batch, channels, height or width,
+ * non-positive dst_channels, negative dst_first_channel, dst_first_channel + channels (+ 1 with the level channel) > dst_channels;
+ * SR3_E_UNSUPPORTED: batch * dst_channels * height * width >= 2^31; SR3_E_BADARG: dst_nchw overlapping any other argument. */
+int sr3_cond_augment_f32(const float* src_nchw, const float* eps_nchw, const float* a_dev, const float* s_dev, const int* keep_dev,
+                         int level_channel, float* dst_nchw, int dst_channels, int dst_first_channel, int batch, int channels,
+                         int height, int width, void* stream);
+
 /* out_dev[b] = the abs-quantile of the n values of image b of src [batch, n]: with v_lo, v_hi the rank_lo-th and (rank_lo + 1)-th
  * smallest |src[b][i]| (0-based; v_hi = v_lo when rank_lo == n - 1),
  *   out_dev[b] = (float)((double) v_lo + frac * ((double) v_hi - (double) v_lo))        one rounding
