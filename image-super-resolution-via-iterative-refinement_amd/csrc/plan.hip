@@ -83,7 +83,8 @@ static int build_structure(sr3_plan* P) {
   if (d.norm_groups <= 0) { set_error("norm_groups must be > 0"); return SR3_E_BADARG; }
   if (d.in_channel <= 0 || d.in_channel > 16) { set_error("in_channel %d unsupported", d.in_channel); return SR3_E_UNSUPPORTED; }
   const int out_ch = d.out_channel > 0 ? d.out_channel : d.in_channel;
-  if (out_ch > 4) { set_error("out_channel %d > 4 unsupported", out_ch); return SR3_E_UNSUPPORTED; }
+  // 6 and 8: a prediction and its variance head (2C of C = 3 / 4), runnable under plan option var_channels alone (check_out_rows)
+  if (out_ch > 4 && out_ch != 6 && out_ch != 8) { set_error("out_channel %d > 4 unsupported", out_ch); return SR3_E_UNSUPPORTED; }
   if ((d.image_size >> (d.n_mults - 1)) < 1 || (d.image_size & ((1 << (d.n_mults - 1)) - 1))) {
     set_error("image_size %d not divisible by 2^%d", d.image_size, d.n_mults - 1);
     return SR3_E_BADARG;
@@ -703,6 +704,7 @@ void layout_derived(sr3_plan* P) {
 }
 
 static int build_forward(sr3_plan* P, int B, int cond_channels) {
+  if (const int rc = check_out_rows(P)) return rc;
   if (P->built_batch == B && P->built_cond == cond_channels && P->built_h == plan_height(P) && P->built_w == plan_width(P)) return SR3_OK;
   const sr3_unet_desc& d = P->d;
   if (B <= 0) { set_error("batch must be > 0"); return SR3_E_BADARG; }
@@ -766,7 +768,7 @@ static FoldTail make_fold_tail(const FoldSpec& s, int groups, const float* param
 int run_forward(sr3_plan* P, bool train, const float* x, const float* cond, int cond_channels, const float* level,
                 const int64_t* tstep, const float* freq, const float* level_table, const int* step_dev,
                 const float* params, char* ws, float* eps_out, int B, hipStream_t st,
-                hipEvent_t* ev, hipEvent_t* mid, const DropCfg* drop, const StepFuse* fuse, const int* t_map) {
+                hipEvent_t* ev, hipEvent_t* mid, const DropCfg* drop, const StepFuse* fuse, const int* t_map, bool full_out) {
   const sr3_unet_desc& d = P->d;
   const Regions& R = train ? P->t_regions : P->regions;
   size_t op_index = 0;
@@ -892,8 +894,9 @@ int run_forward(sr3_plan* P, bool train, const float* x, const float* cond, int 
       }
       case OP_CONV_OUT: {
         const Op::ConvOut& v = o.conv_out;
+        // the prediction rows alone -- the first rows of the same filters and bias -- unless all rows are asked for
         rc = conv_out_nchw(bind<const float>(ws, v.src), bind<const float>(ws, R.ss_off + o.ss_rel), B, v.H, v.W, v.channels,
-                           params + v.w, params + v.bias, v.out_ch, eps_out, st, fuse);
+                           params + v.w, params + v.bias, (train || full_out) ? v.out_ch : v.out_ch - P->var_channels, eps_out, st, fuse);
         break;
       }
     }
@@ -1041,6 +1044,13 @@ int sr3_plan_set_option(sr3_plan* plan, const char* key, int value) {
   else if (!strcmp(key, "wino_up")) slot = &plan->wino_up;
   else if (!strcmp(key, "train_geom")) slot = &plan->train_geom;
   else if (!strcmp(key, "loss_l2")) { const int prev = plan->loss_l2; plan->loss_l2 = value; return prev; }   // no rebuild
+  else if (!strcmp(key, "var_channels")) {
+    if (value != 0 && value * 2 != plan->out_ch) {
+      set_error("var_channels %d: 0 or half of out_channel %d (the variance head of a learned-variance model)", value, plan->out_ch);
+      return SR3_E_BADARG;
+    }
+    slot = &plan->var_channels;
+  }
   if (!slot) { set_error("unknown option %s", key); return SR3_E_BADARG; }
 #ifndef SR3_EXPERIMENTS
   if (slot == &plan->split_bf16 && value != 0) {
@@ -1137,10 +1147,10 @@ size_t sr3_workspace_bytes(sr3_plan* plan, int batch) {
   return plan->ws_bytes;
 }
 
-int sr3_unet_forward(sr3_plan* plan, const float* x_nchw, const float* cond_nchw, int cond_channels,
-                     const float* noise_level, const int64_t* timestep, const float* freq, const float* level_table,
-                     const int* step_dev, const float* params, void* workspace, size_t workspace_bytes,
-                     float* eps_out_nchw, int batch, void* stream) {
+static int unet_forward_rows(sr3_plan* plan, const float* x_nchw, const float* cond_nchw, int cond_channels,
+                             const float* noise_level, const int64_t* timestep, const float* freq, const float* level_table,
+                             const int* step_dev, const float* params, void* workspace, size_t workspace_bytes,
+                             float* eps_out_nchw, int batch, void* stream, bool full_out, const int* t_map = nullptr) {
   if (!plan || !x_nchw || !params || !workspace || !eps_out_nchw || !freq) { set_error("null argument"); return SR3_E_BADARG; }
   if (!cond_nchw) cond_channels = 0;
   const int rc = build_forward(plan, batch, cond_channels);
@@ -1154,7 +1164,24 @@ int sr3_unet_forward(sr3_plan* plan, const float* x_nchw, const float* cond_nchw
   if (plan->d.variant == SR3_VARIANT_DDPM && !timestep && !step_dev) { set_error("DDPM variant needs timestep or step_dev"); return SR3_E_BADARG; }
   return run_forward(plan, false, x_nchw, cond_nchw, cond_channels, noise_level, timestep, freq, level_table,
                      step_dev, params, static_cast<char*>(workspace), eps_out_nchw, batch, static_cast<hipStream_t>(stream),
-                     nullptr, nullptr);
+                     nullptr, nullptr, nullptr, nullptr, t_map, full_out);
+}
+
+int sr3_unet_forward(sr3_plan* plan, const float* x_nchw, const float* cond_nchw, int cond_channels,
+                     const float* noise_level, const int64_t* timestep, const float* freq, const float* level_table,
+                     const int* step_dev, const float* params, void* workspace, size_t workspace_bytes,
+                     float* eps_out_nchw, int batch, void* stream) {
+  return unet_forward_rows(plan, x_nchw, cond_nchw, cond_channels, noise_level, timestep, freq, level_table, step_dev, params, workspace,
+                           workspace_bytes, eps_out_nchw, batch, stream, false);
+}
+// ... with the variance head: eps_out_nchw is [B, out_channel, H, W] (plan option var_channels; without it the same call as above)
+int sr3_unet_forward_full(sr3_plan* plan, const float* x_nchw, const float* cond_nchw, int cond_channels,
+                          const float* noise_level, const int64_t* timestep, const float* freq, const float* level_table,
+                          const int* step_dev, const float* params, void* workspace, size_t workspace_bytes,
+                          float* eps_out_nchw, int batch, void* stream, const int* t_map) {
+  if (t_map && !step_dev) { set_error("sr3_unet_forward_full: t_map goes with step_dev"); return SR3_E_BADARG; }
+  return unet_forward_rows(plan, x_nchw, cond_nchw, cond_channels, noise_level, timestep, freq, level_table, step_dev, params, workspace,
+                           workspace_bytes, eps_out_nchw, batch, stream, true, t_map);
 }
 
 // One whole reverse step (include/sr3_mi355x.h): the forward above with the p_sample update and the counter decrement inside the
@@ -1175,7 +1202,7 @@ int sr3_reverse_step_hist(sr3_plan* plan, float* x_nchw, const float* cond_nchw,
     return SR3_E_ALIGN;
   }
   if (plan->d.variant == SR3_VARIANT_SR3 && !level_table) { set_error("SR3 variant needs level_table"); return SR3_E_BADARG; }
-  const size_t image_bytes = (size_t)batch * plan->d.out_channel * plan_height(plan) * plan_width(plan) * sizeof(float);
+  const size_t image_bytes = (size_t)batch * (plan->d.out_channel - plan->var_channels) * plan_height(plan) * plan_width(plan) * sizeof(float);
   if (const int rc = check_step_history("reverse_step", tc3, hist_nchw, x_nchw, eps_out_nchw, image_bytes, true)) return rc;
   StepFuse f;
   f.x = x_nchw; f.z = z_nchw; f.tb = StepTables{ta, tb, tc1, tc2, tsig};

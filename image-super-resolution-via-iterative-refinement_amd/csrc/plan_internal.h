@@ -178,6 +178,10 @@ struct sr3_plan {
   std::vector<Layer> downs, mid, ups;
   size_t fin_gn_w = 0, fin_gn_b = 0, fin_w = 0, fin_b = 0;
   int fin_cin = 0, out_ch = 0;
+  int var_channels = 0;      // learned reverse-process variance (plan option var_channels): the last var_channels of the out_ch filter rows
+                             // are the variance head v, the first out_ch - var_channels the prediction.  0 or out_ch / 2.  Inference
+                             // forwards and every step tail run the prediction rows alone (the filters are [co][9][C]: the first rows of
+                             // the same buffer) unless the caller asks for all rows; the training forward always runs all of them
   // options
   int fuse_stats = 1, fuse_res = 1, tile_cfg = 0, ksplit = 0, keep_all = 0, split_bf16 = 0;
   int winograd = 1;          // 3x3 stride-1 convs of the inference plan on the Winograd F(2x2,3x3) kernel (conv3x3_wino.hip)
@@ -271,12 +275,19 @@ namespace sr3 {
 struct Builder;
 inline int plan_height(const sr3_plan* P) { return P->geo_h > 0 ? P->geo_h : P->d.image_size; }
 inline int plan_width(const sr3_plan* P) { return P->geo_w > 0 ? P->geo_w : P->d.image_size; }
+inline int plan_image_channels(const sr3_plan* P) { return P->out_ch - P->var_channels; }      // channels of x, z, eps of a step
+// more than 4 output rows exist only as a prediction with its variance head: refused where a launch list is built
+inline int check_out_rows(const sr3_plan* P) {
+  if (P->out_ch > 4 && P->var_channels == 0) { set_error("out_channel %d > 4 unsupported", P->out_ch); return SR3_E_UNSUPPORTED; }
+  return SR3_OK;
+}
 inline bool plan_native_geometry(const sr3_plan* P) { return plan_height(P) == P->d.image_size && plan_width(P) == P->d.image_size; }
 // replays P->ops over P->regions, or (train) P->tops over P->t_regions
 int run_forward(sr3_plan* P, bool train, const float* x, const float* cond, int cond_channels, const float* level,
                 const int64_t* tstep, const float* freq, const float* level_table, const int* step_dev,
                 const float* params, char* ws, float* eps_out, int B, hipStream_t st, hipEvent_t* ev, hipEvent_t* mid,
-                const DropCfg* drop = nullptr, const StepFuse* fuse = nullptr, const int* t_map = nullptr);
+                const DropCfg* drop = nullptr, const StepFuse* fuse = nullptr, const int* t_map = nullptr, bool full_out = false);
+// (full_out: eps_out takes all out_ch rows of the output conv -- the variance head too; the training forward always does)
 // The forward walk in train mode (plan.hip): fills P->tops, P->ttens and P->recs (every activation kept, persistent GroupNorm
 // tables) and returns what build_train lays the workspace out by
 struct TrainWalk {

@@ -591,7 +591,7 @@ int conv_in_nchw(const float* a, int Ca, const float* b, int Cb, int B, int H, i
 // accumulates its pixel's Cout outputs from LDS.  Writes NCHW (the public layout of eps).
 // ---------------------------------------------------------------------------------------------
 constexpr int OT_H = 8, OT_W = 32, OT_CK = 16, OT_LD = 20;
-// COUT: output channels (1..4); FULL: C is a multiple of the 16-channel chunk (no per-quad bound checks)
+// COUT: output channels (1..4; 6 and 8, the learned-variance heads 2C of C = 3 / 4, without FUSE: no tail is fused onto them); FULL: C is a multiple of the 16-channel chunk (no per-quad bound checks)
 // FUSE (sr3_reverse_step): the reverse-step update of the image this eps belongs to in the epilogue -- the element a thread produces IS the
 // element of eps the elementwise update needs, in the same NCHW position -- step_tail (sr3_common.h), as k_p_sample_update runs it
 // (bit-identical to the two-kernel form), and the loop counter's decrement by one thread
@@ -612,7 +612,7 @@ __global__ __launch_bounds__(256) void k_conv_out_nchw(const float* __restrict__
   bid -= b * tiles_w * tiles_h;
   const int th = bid / tiles_w, tw = bid - th * tiles_w;
   const int h0 = th * OT_H, w0 = tw * OT_W;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  float acc[COUT <= 4 ? 4 : COUT] = {};     // (four slots up to four rows, as ever: those instantiations compile to what they did)
   constexpr int NPIX = (OT_H + 2) * (OT_W + 2);
   for (int c0 = 0; c0 < C; c0 += OT_CK) {
     __syncthreads();
@@ -679,7 +679,9 @@ __global__ __launch_bounds__(256) void k_conv_out_nchw(const float* __restrict__
 
 int conv_out_nchw(const float* x, const float* ss, int B, int H, int W, int C, const float* w, const float* bias,
                   int Cout, float* out_nchw, hipStream_t st, const StepFuse* fuse) {
-  if (Cout > 4 || Cout < 1) { set_error("conv_out: Cout %d > 4 unsupported", Cout); return SR3_E_UNSUPPORTED; }
+  const bool wide = Cout == 6 || Cout == 8;      // a prediction and its variance head; 5 and 7 are no 2C of a supported C
+  if ((Cout > 4 && !wide) || Cout < 1) { set_error("conv_out: Cout %d > 4 unsupported", Cout); return SR3_E_UNSUPPORTED; }
+  if (wide && fuse) { set_error("conv_out: no fused step tail on Cout %d (launch the prediction rows alone)", Cout); return SR3_E_UNSUPPORTED; }
   if (C & 3) { set_error("conv_out: C %% 4 != 0"); return SR3_E_UNSUPPORTED; }
   if (!fuse && !out_nchw) { set_error("conv_out: null output"); return SR3_E_BADARG; }
   const int tiles = ((W + OT_W - 1) / OT_W) * ((H + OT_H - 1) / OT_H) * B;
@@ -700,7 +702,9 @@ int conv_out_nchw(const float* x, const float* ss, int B, int H, int W, int C, c
     case 1: SR3_CO_LAUNCH(1) break;
     case 2: SR3_CO_LAUNCH(2) break;
     case 3: SR3_CO_LAUNCH(3) break;
-    default: SR3_CO_LAUNCH(4) break;
+    case 4: SR3_CO_LAUNCH(4) break;
+    case 6: if (C % OT_CK == 0) { SR3_CO_LAUNCH3(6, true, false, false) } else { SR3_CO_LAUNCH3(6, false, false, false) } break;
+    default: if (C % OT_CK == 0) { SR3_CO_LAUNCH3(8, true, false, false) } else { SR3_CO_LAUNCH3(8, false, false, false) } break;
   }
 #undef SR3_CO_LAUNCH
 #undef SR3_CO_LAUNCH2

@@ -36,12 +36,23 @@ struct Objective {
   const float* tgt_z = nullptr; const float* tgt_x0 = nullptr; const float* weight = nullptr;
   int kind = LOSS_L1;
   float huber_delta = 1.f;
+  // learned reverse-process variance (sr3_train_step_ex2 / sr3_hybrid_loss_grad_f32): per image the HYB_STRIDE scalars of the drawn step
+  // (device; null: the objective above alone) and the weight lambda of L_vlb
+  const float* hyb = nullptr;
+  float lambda = 0.f;
 };
+// one image's row of Objective::hyb: x0 = a x_t - b out ; posterior mean c1 x0 + c2 x_t ; log beta, log beta~ (clipped) of the step ;
+// last != 0: the walk's last step (the discretised log-likelihood instead of the KL term)
+enum { HYB_A = 0, HYB_B, HYB_C1, HYB_C2, HYB_LOG_BETA, HYB_LOG_BETA_TILDE, HYB_LAST, HYB_STRIDE = 8 };
 int check_objective_args(const char* who, const float* tgt_z, const float* tgt_x0, const float* weight, int loss_kind, int min_kind,
                          float huber_delta);
 // loss sum and its gradient g [B,HW,CP] under `o`: l1_loss_grad's launch for target z / weight 1 / L1 or L2, else k_loss_grad
 int objective_loss_grad(const float* z, const float* hr, const float* e, const Objective& o, int B, int Cc, int HW, int CP, float scale,
                         float* g_nhwc, double* loss_part, float* loss_out, hipStream_t st);
+// the hybrid loss L_simple + lambda L_vlb of a network with a variance head (e: [B, 2 Cc, HW]; x_t: [B, Cc, HW]): g [B, HW, CP >= 2 Cc],
+// loss_out[0] = sum w rho(d) + lambda sum vlb, vlb_out[0] (may be null) = sum vlb in bits.  loss_part: 2 * LOSS_GRAD_BLOCKS doubles
+int hybrid_loss_grad(const float* z, const float* hr, const float* xt, const float* e, const Objective& o, int B, int Cc, int HW, int CP,
+                     float scale, float* g_nhwc, double* loss_part, float* loss_out, float* vlb_out, hipStream_t st);
 int nchw_to_nhwc_pad(const float* a, int Ca, const float* b, int Cb, int B, int HW, int CP, float* out, hipStream_t st);
 
 // Weight gradient of a conv (wgrad.hip): dw[n][tap][c] = sum_m dy[m][n] * a_tap[m][c], a = prologue(x0|x1)

@@ -344,6 +344,104 @@ __global__ __launch_bounds__(256) void k_loss_grad(const float* __restrict__ z, 
   }
   if (threadIdx.x == 0) loss_part[blockIdx.x] = red[0];
 }
+// T11c: the hybrid loss of a learned reverse-process variance (Nichol & Dhariwal 2021).  e is [B, 2 Cc, HW]: channels
+// 0 .. Cc - 1 the prediction, under k_loss_grad's objective, term for term (the same d, rho, g: bit-identical lanes); channels Cc ..
+// 2 Cc - 1 the raw variance head v.  Per image the scalars of the drawn step (train.h: HYB_*).  Per element, all fp32:
+//   x0^ = a x_t - b out (no clamp) ; mu_theta = c1 x0^ + c2 x_t, a constant here: no L_vlb gradient reaches the prediction lanes
+//   f = (v + 1) / 2 ; lv = f log beta + (1 - f) log beta~                         log sigma_theta^2
+//   not last:  vlb = KL(N(mu_q, beta~) || N(mu_theta, e^lv)) / ln 2,  mu_q - mu_theta = c1 (x0 - x0^)
+//   last:      vlb = -log2 of the mass N(mu_theta, e^lv) puts on the bin x0 +- 1/255 (open below -0.999 and above 0.999), with
+//              Phi(u) = (1 + tanh(sqrt(2 / pi) (u + 0.044715 u^3))) / 2 and logs of max(., 1e-12)
+//   g lane Cc + c = lambda scale d vlb / d v, in closed form; lanes >= 2 Cc are 0
+// loss_part[block] = sum w rho(d) + lambda sum vlb, loss_part[gridDim.x + block] = sum vlb: double partials, fixed order, no atomics.
+struct VlbScal { float a, b, c1, c2, lb, lt; bool last; };
+__device__ __forceinline__ float approx_cdf(float u, float* pdf) {
+  constexpr float K = 0.7978845608028654f;      // sqrt(2 / pi)
+  const float th = tanhf(K * (u + 0.044715f * u * u * u));
+  *pdf = 0.5f * (1.f - th * th) * K * (1.f + 3.f * 0.044715f * u * u);
+  return 0.5f * (1.f + th);
+}
+__device__ __forceinline__ float vlb_elem(const VlbScal& k, float x0, float xt, float o, float v, float* dv) {
+  constexpr float RLN2 = 1.4426950408889634f;
+  const float x0h = k.a * xt - k.b * o;
+  const float f = 0.5f * (v + 1.f);
+  const float lv = f * k.lb + (1.f - f) * k.lt;
+  const float dlv = 0.5f * (k.lb - k.lt);      // d lv / d v
+  if (!k.last) {
+    const float d = k.c1 * (x0 - x0h);
+    const float r = expf(k.lt - lv), q = d * d * expf(-lv);
+    *dv = 0.5f * (1.f - r - q) * dlv * RLN2;
+    return 0.5f * (-1.f + lv - k.lt + r + q) * RLN2;
+  }
+  const float cx = x0 - (k.c1 * x0h + k.c2 * xt), inv = expf(-0.5f * lv);
+  const float up = inv * (cx + 1.f / 255.f), um = inv * (cx - 1.f / 255.f);
+  float pp, pm;
+  const float cp = approx_cdf(up, &pp), cm = approx_cdf(um, &pm);
+  // d u / d lv = -u / 2 for either bound; a clamped log has no gradient
+  float arg, darg;
+  if (x0 < -0.999f) { arg = cp; darg = pp * (-0.5f * up); }
+  else if (x0 > 0.999f) { arg = 1.f - cm; darg = pm * (0.5f * um); }
+  else { arg = cp - cm; darg = pp * (-0.5f * up) + pm * (0.5f * um); }
+  const bool open = arg >= 1e-12f;
+  *dv = open ? -(darg / arg) * dlv * RLN2 : 0.f;
+  return -logf(open ? arg : 1e-12f) * RLN2;
+}
+template <int KIND>
+__global__ __launch_bounds__(256) void k_hybrid_loss_grad(const float* __restrict__ z, const float* __restrict__ hr,
+                                                           const float* __restrict__ xt, const float* __restrict__ e,
+                                                           const float* __restrict__ ta, const float* __restrict__ tb,
+                                                           const float* __restrict__ w, const float* __restrict__ hyb, int B, int Cc,
+                                                           int HW, int CP, float scale, float delta, float lambda,
+                                                           float* __restrict__ g_nhwc, double* __restrict__ loss_part) {
+  __shared__ double red[256];
+  double s = 0.0, sv = 0.0;
+  const size_t total = (size_t)B * HW;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / HW, p = i - b * HW;
+    const float az = ta ? ta[b] : 1.f, ax = tb ? tb[b] : 0.f, wb = w ? w[b] : 1.f;
+    const float ws = wb * scale, ls = lambda * scale;
+    const float* hs = hyb + b * HYB_STRIDE;
+    const VlbScal k = {hs[HYB_A], hs[HYB_B], hs[HYB_C1], hs[HYB_C2], hs[HYB_LOG_BETA], hs[HYB_LOG_BETA_TILDE], hs[HYB_LAST] != 0.f};
+    double sp = 0.0, vp = 0.0;
+    for (int c = 0; c < CP; ++c) {
+      float gv = 0.f;
+      if (c < Cc) {                             // (k_loss_grad's lane, term for term)
+        const size_t idx = (b * 2 * Cc + c) * HW + p, ix = (b * Cc + c) * HW + p;
+        const float d = (az * z[ix] + (tb ? ax * hr[ix] : 0.f)) - e[idx];
+        if (KIND == 1) {
+          sp += (double)d * (double)d;
+          gv = -2.f * d * ws;
+        } else if (KIND == 2) {
+          const double a = (double)fabsf(d), dl = (double)delta;
+          sp += a <= dl ? 0.5 * a * a : dl * (a - 0.5 * dl);
+          gv = -fminf(fmaxf(d, -delta), delta) * ws;
+        } else {
+          sp += (double)fabsf(d);
+          gv = d > 0.f ? -ws : (d < 0.f ? ws : 0.f);
+        }
+      } else if (c < 2 * Cc) {
+        const int ci = c - Cc;
+        const size_t ix = (b * Cc + ci) * HW + p;
+        float dv;
+        vp += (double)vlb_elem(k, hr[ix], xt[ix], e[(b * 2 * Cc + ci) * HW + p], e[(b * 2 * Cc + c) * HW + p], &dv);
+        gv = ls * dv;
+      }
+      g_nhwc[i * CP + c] = gv;
+    }
+    s += (double)wb * sp + (double)lambda * vp;
+    sv += vp;
+  }
+  for (int pass = 0; pass < 2; ++pass) {
+    __syncthreads();
+    red[threadIdx.x] = pass ? sv : s;
+    __syncthreads();
+    for (int m = 128; m >= 1; m >>= 1) {
+      if ((int)threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) loss_part[pass * gridDim.x + blockIdx.x] = red[0];
+  }
+}
 __global__ __launch_bounds__(64) void k_sum_parts(const double* __restrict__ part, int n, float* __restrict__ out) {
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += 64) s += part[i];
@@ -522,6 +620,21 @@ int objective_loss_grad(const float* z, const float* hr, const float* e, const O
   SR3_LAUNCH_CHECK("k_sum_parts");
   return SR3_OK;
 }
+int hybrid_loss_grad(const float* z, const float* hr, const float* xt, const float* e, const Objective& o, int B, int Cc, int HW, int CP,
+                     float scale, float* g_nhwc, double* loss_part, float* loss_out, float* vlb_out, hipStream_t st) {
+  const int blocks = LOSS_GRAD_BLOCKS;
+  static constexpr decltype(&k_hybrid_loss_grad<0>) kernels[3] = {k_hybrid_loss_grad<0>, k_hybrid_loss_grad<1>, k_hybrid_loss_grad<2>};
+  hipLaunchKernelGGL(kernels[o.kind], dim3(blocks), dim3(256), 0, st, z, hr, xt, e, o.tgt_z, o.tgt_x0, o.weight, o.hyb, B, Cc, HW, CP,
+                     scale, o.huber_delta, o.lambda, g_nhwc, loss_part);
+  SR3_LAUNCH_CHECK("k_hybrid_loss_grad");
+  hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(64), 0, st, loss_part, blocks, loss_out);
+  SR3_LAUNCH_CHECK("k_sum_parts");
+  if (vlb_out) {
+    hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(64), 0, st, loss_part + blocks, blocks, vlb_out);
+    SR3_LAUNCH_CHECK("k_sum_parts");
+  }
+  return SR3_OK;
+}
 int nchw_to_nhwc_pad(const float* a, int Ca, const float* b, int Cb, int B, int HW, int CP, float* out, hipStream_t st) {
   const size_t total = (size_t)B * HW;
   hipLaunchKernelGGL(k_nchw_to_nhwc_pad, dim3(ew_blocks(total)), dim3(256), 0, st, a, Ca, b, Cb, HW, CP, out, total);
@@ -547,4 +660,27 @@ extern "C" int sr3_loss_grad_f32(const float* z_nchw, const float* out_nchw, con
   o.tgt_z = tgt_z; o.tgt_x0 = tgt_x0; o.weight = weight; o.kind = loss_kind; o.huber_delta = huber_delta;
   return objective_loss_grad(z_nchw, hr_nchw, out_nchw, o, batch, channels, pixels, 4, scale, g_nhwc4, static_cast<double*>(scratch),
                              loss_sum_out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t sr3_hybrid_loss_grad_scratch_bytes(void) { return 2 * sr3::LOSS_GRAD_BLOCKS * sizeof(double); }
+extern "C" int sr3_hybrid_loss_grad_f32(const float* z_nchw, const float* out_nchw, const float* hr_nchw, const float* xt_nchw,
+                                        const float* tgt_z, const float* tgt_x0, const float* weight, const float* step_scalars,
+                                        float vlb_lambda, int batch, int channels, int pixels, int loss_kind, float huber_delta, float scale,
+                                        float* g_nhwc8, float* loss_sum_out, float* vlb_sum_out, void* scratch, void* stream) {
+  using namespace sr3;
+  const char* who = "sr3_hybrid_loss_grad_f32";
+  if (!z_nchw || !out_nchw || !hr_nchw || !xt_nchw || !step_scalars || !g_nhwc8 || !loss_sum_out || !scratch) {
+    set_error("%s: z_nchw / out_nchw / hr_nchw / xt_nchw / step_scalars / g_nhwc8 / loss_sum_out / scratch is NULL", who);
+    return SR3_E_BADARG;
+  }
+  if (const int rc = check_objective_args(who, tgt_z, tgt_x0, weight, loss_kind, 0, huber_delta)) return rc;
+  if (batch <= 0 || pixels <= 0) { set_error("%s: batch %d and pixels %d must be positive", who, batch, pixels); return SR3_E_BADARG; }
+  if (channels < 1 || channels > 4) { set_error("%s: channels %d is outside 1..4", who, channels); return SR3_E_BADARG; }
+  if (!(isfinite(vlb_lambda) && vlb_lambda >= 0.f)) { set_error("%s: vlb_lambda %g must be finite and >= 0", who, (double)vlb_lambda); return SR3_E_BADARG; }
+  if ((uintptr_t)scratch & 7) { set_error("%s: scratch is not 8-byte aligned", who); return SR3_E_ALIGN; }
+  Objective o;
+  o.tgt_z = tgt_z; o.tgt_x0 = tgt_x0; o.weight = weight; o.kind = loss_kind; o.huber_delta = huber_delta;
+  o.hyb = step_scalars; o.lambda = vlb_lambda;
+  return hybrid_loss_grad(z_nchw, hr_nchw, xt_nchw, out_nchw, o, batch, channels, pixels, 8, scale, g_nhwc8, static_cast<double*>(scratch),
+                          loss_sum_out, vlb_sum_out, static_cast<hipStream_t>(stream));
 }

@@ -11,6 +11,7 @@
 //   bias / FiLM     = per-channel sums of dOut (partial sums, fixed order).
 // Every parameter gradient is written exactly once (no accumulation across ops), activation
 // gradients live in a mirror of the activation arena and are accumulated in stream order.
+#include <math.h>
 #include <string.h>
 
 #include <algorithm>
@@ -32,14 +33,16 @@ namespace {
 // (nchw_to_nhwc_pad): 8 up to 8 input channels -- every model without self-conditioning keeps its workspace bytes -- 16 above
 // (the plan accepts in_channel <= 16)
 inline int in_pad(int in_channel) { return in_channel <= 8 ? 8 : 16; }
-constexpr int OUT_PAD = 4;     // the output conv's gradients read dOut with its channels padded to 4 (l1_loss_grad)
+// the output conv's gradients read dOut with its channels padded to a multiple of 4 (l1_loss_grad): 4 up to 4 output rows -- every
+// model without a variance head keeps its launches and its workspace bytes -- 8 above (6 or 8 rows: a prediction and its variance head)
+inline int out_pad(const sr3_plan* P) { return P->out_ch <= 4 ? 4 : 8; }
 
 // shape of a record's weight gradient: the forward conv's own geometry
 ConvParams wgrad_shape(const sr3_plan* P, const Rec& r, int B) {
   const std::vector<Tensor>& T = P->ttens;
   if (r.kind == R_CONV_IN) return conv_shape(B, T[r.out].H, T[r.out].W, 0, 1, 3, in_pad(P->d.in_channel), 0, T[r.out].C);
   const Tensor& x0 = T[r.s.x0];
-  if (r.kind == R_CONV_OUT) return conv_shape(B, x0.H, x0.W, 0, 1, 3, x0.C, 0, OUT_PAD);
+  if (r.kind == R_CONV_OUT) return conv_shape(B, x0.H, x0.W, 0, 1, 3, x0.C, 0, out_pad(P));
   ConvParams c = conv_shape(B, x0.H, x0.W, r.s.ups, r.s.stride, r.s.ksize, x0.C, r.s.x1 >= 0 ? T[r.s.x1].C : 0, T[r.out].C);
   if (r.s.act) { c.C0 += c.C1; c.C1 = 0; }      // the activated input is materialised by act_bwd: a single source
   return c;
@@ -153,6 +156,7 @@ int resolve_backward(sr3_plan* P, int B) {
 }  // namespace
 
 int build_train(sr3_plan* P, int B, int cond_channels) {
+  if (const int rc = check_out_rows(P)) return rc;
   if (!P->train_geom && !plan_native_geometry(P)) {
     set_error("training runs at image_size x image_size only: the plan's geometry is %d x %d (sr3_plan_set_geometry(plan, 0, 0) restores %d x %d)",
               plan_height(P), plan_width(P), P->d.image_size, P->d.image_size);
@@ -236,7 +240,7 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
   P->t_dfilm_off = off; off += al((size_t)B * P->F * sizeof(float));
   P->t_xnoisy_off = off; off += al((size_t)B * (d.in_channel - cond_channels) * S2 * sizeof(float));
   P->t_eps_off = off; off += al((size_t)B * P->out_ch * S2 * sizeof(float));
-  P->t_geps_off = off; off += al((size_t)B * S2 * OUT_PAD * sizeof(float));
+  P->t_geps_off = off; off += al((size_t)B * S2 * out_pad(P) * sizeof(float));
   P->t_inpad_off = off; off += al((size_t)B * S2 * in_pad(d.in_channel) * sizeof(float));
   P->t_dwtmp_off = off; off += al(4096 * sizeof(double)) + al(max_dwtmp);      // [loss partials | dw temp]
   P->t_embscr_off = off; off += al((size_t)B * (13 + 16) * inner * sizeof(float));     // (+ the 16 row chunks of k_film_bwd_input)
@@ -307,7 +311,7 @@ int wgrad_call(const TrainCtx& X, ConvParams c, const float* src0, const float* 
 int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels, const float* z, const float* q_ca,
               const float* q_cb, const float* level, const int64_t* tstep, const float* freq, const float* params,
               float* grads, char* ws, float* loss_out, float grad_scale, int B, hipStream_t st, float dropout_p,
-              unsigned seed, int n_marks, const size_t* marks, void* const* mark_events, const Objective& obj) {
+              unsigned seed, int n_marks, const size_t* marks, void* const* mark_events, const Objective& obj, float* vlb_out) {
   const sr3_unet_desc& d = P->d;
   // image geometry of this step: build_train built the plan for it (the native one unless plan option train_geom)
   const int IH = P->train_h, IW = P->train_w, S2 = IH * IW, G = d.norm_groups;
@@ -329,7 +333,11 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
   float* geps = X.at<float>(P->t_geps_off);
   double* lparts = X.at<double>(P->t_dwtmp_off);
   // (target z, weight 1 and L1 / L2 -- sr3_train_step's objective -- is l1_loss_grad's launch: objective_loss_grad)
-  rc = objective_loss_grad(z, hr, eps, obj, B, P->out_ch, S2, OUT_PAD, grad_scale, geps, lparts, loss_out, st);
+  const int OUT_PAD = out_pad(P);
+  if (obj.hyb)      // a variance head: L_simple on the prediction rows + lambda L_vlb on the variance rows, one kernel (train_kernels.hip)
+    rc = hybrid_loss_grad(z, hr, x_noisy, eps, obj, B, plan_image_channels(P), S2, OUT_PAD, grad_scale, geps, lparts, loss_out, vlb_out, st);
+  else
+    rc = objective_loss_grad(z, hr, eps, obj, B, P->out_ch, S2, OUT_PAD, grad_scale, geps, lparts, loss_out, st);
   if (rc) return rc;
   // ---- the backward walk: the records in reverse, each as build_train resolved it.  The activation-gradient mirror is not zeroed
   // (Rec::acc_*); the FiLM gradient table is ----
@@ -353,7 +361,7 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
     float* abuf = X.at<float>(P->t_a_off);        // the activated input of a conv, written by act_bwd's first pass
     if (r.kind == R_CONV_OUT) {
       const int C = r.dw.C0;
-      // bias (3 of the 4 padded columns are real; arena slots are 4-float aligned)
+      // bias (3 of the 4 padded columns are real -- 6 of 8 with a variance head; arena slots are 4-float aligned)
       rc = colsums(geps, B, S2, OUT_PAD, part, grads + s.bias, nullptr, 0, st);
       if (rc) return rc;
       rc = dgrad_conv(X, r.dx, geps, params + s.w, P->out_ch, dA);
@@ -478,17 +486,19 @@ size_t sr3_train_workspace_bytes(sr3_plan* plan, int batch, int cond_channels) {
   return plan->t_ws_bytes;
 }
 
-int sr3_train_step_ex(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels, const float* z_nchw,
-                      const float* q_ca, const float* q_cb, const float* noise_level, const int64_t* timestep,
-                      const float* freq, const float* params, float* grads, void* workspace, size_t workspace_bytes,
-                      float* loss_sum_out, float grad_scale, float dropout_p, unsigned dropout_seed, int n_marks,
-                      const size_t* mark_offsets, void* const* mark_events, int batch, const float* tgt_z, const float* tgt_x0,
-                      const float* weight, int loss_kind, float huber_delta, void* stream) {
+// the body of sr3_train_step_ex (step_scalars null) and sr3_train_step_ex2: `who` names the entry in the objective's refusals
+static int train_step_body(const char* who, sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels, const float* z_nchw,
+                           const float* q_ca, const float* q_cb, const float* noise_level, const int64_t* timestep,
+                           const float* freq, const float* params, float* grads, void* workspace, size_t workspace_bytes,
+                           float* loss_sum_out, float grad_scale, float dropout_p, unsigned dropout_seed, int n_marks,
+                           const size_t* mark_offsets, void* const* mark_events, int batch, const float* tgt_z, const float* tgt_x0,
+                           const float* weight, int loss_kind, float huber_delta, const float* step_scalars, float vlb_lambda,
+                           float* vlb_sum_out, void* stream) {
   if (!plan || !hr_nchw || !z_nchw || !q_ca || !q_cb || !freq || !params || !grads || !workspace || !loss_sum_out) {
     set_error("null argument");
     return SR3_E_BADARG;
   }
-  if (const int rc = check_objective_args("sr3_train_step_ex", tgt_z, tgt_x0, weight, loss_kind, -1, huber_delta)) return rc;
+  if (const int rc = check_objective_args(who, tgt_z, tgt_x0, weight, loss_kind, -1, huber_delta)) return rc;
   if (!cond_nchw) cond_channels = 0;
   const int rc = build_train(plan, batch, cond_channels);
   if (rc) return rc;
@@ -497,12 +507,43 @@ int sr3_train_step_ex(sr3_plan* plan, const float* hr_nchw, const float* cond_nc
   if (plan->d.variant == SR3_VARIANT_SR3 && !noise_level) { set_error("SR3 variant needs noise_level"); return SR3_E_BADARG; }
   if (plan->d.variant == SR3_VARIANT_DDPM && !timestep) { set_error("DDPM variant needs timestep"); return SR3_E_BADARG; }
   if (dropout_p < 0.f || dropout_p >= 1.f) { set_error("dropout_p out of range"); return SR3_E_BADARG; }
+  if ((plan->var_channels > 0) != (step_scalars != nullptr)) {
+    set_error("%s: the plan's variance rows (var_channels %d) and step_scalars go together (sr3_train_step_ex2 trains them)", who, plan->var_channels);
+    return SR3_E_BADARG;
+  }
+  if (step_scalars && !(isfinite(vlb_lambda) && vlb_lambda >= 0.f)) { set_error("%s: vlb_lambda %g must be finite and >= 0", who, (double)vlb_lambda); return SR3_E_BADARG; }
   Objective obj;
+  obj.hyb = step_scalars; obj.lambda = vlb_lambda;
   obj.tgt_z = tgt_z; obj.tgt_x0 = tgt_x0; obj.weight = weight; obj.huber_delta = huber_delta;
   obj.kind = loss_kind < 0 ? (plan->loss_l2 != 0 ? LOSS_L2 : LOSS_L1) : loss_kind;      // -1: the plan's loss_l2
   return run_train(plan, hr_nchw, cond_nchw, cond_channels, z_nchw, q_ca, q_cb, noise_level, timestep, freq, params, grads,
                    static_cast<char*>(workspace), loss_sum_out, grad_scale, batch, static_cast<hipStream_t>(stream), dropout_p,
-                   dropout_seed, (mark_offsets && mark_events) ? n_marks : 0, mark_offsets, mark_events, obj);
+                   dropout_seed, (mark_offsets && mark_events) ? n_marks : 0, mark_offsets, mark_events, obj, vlb_sum_out);
+}
+
+int sr3_train_step_ex(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels, const float* z_nchw,
+                      const float* q_ca, const float* q_cb, const float* noise_level, const int64_t* timestep,
+                      const float* freq, const float* params, float* grads, void* workspace, size_t workspace_bytes,
+                      float* loss_sum_out, float grad_scale, float dropout_p, unsigned dropout_seed, int n_marks,
+                      const size_t* mark_offsets, void* const* mark_events, int batch, const float* tgt_z, const float* tgt_x0,
+                      const float* weight, int loss_kind, float huber_delta, void* stream) {
+  return train_step_body("sr3_train_step_ex", plan, hr_nchw, cond_nchw, cond_channels, z_nchw, q_ca, q_cb, noise_level, timestep, freq, params,
+                         grads, workspace, workspace_bytes, loss_sum_out, grad_scale, dropout_p, dropout_seed, n_marks, mark_offsets,
+                         mark_events, batch, tgt_z, tgt_x0, weight, loss_kind, huber_delta, nullptr, 0.f, nullptr, stream);
+}
+
+// ... of a plan with a variance head (plan option var_channels): the hybrid loss (sr3_hybrid_loss_grad_f32) in place of the pixel loss
+int sr3_train_step_ex2(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels, const float* z_nchw,
+                       const float* q_ca, const float* q_cb, const float* noise_level, const int64_t* timestep,
+                       const float* freq, const float* params, float* grads, void* workspace, size_t workspace_bytes,
+                       float* loss_sum_out, float grad_scale, float dropout_p, unsigned dropout_seed, int n_marks,
+                       const size_t* mark_offsets, void* const* mark_events, int batch, const float* tgt_z, const float* tgt_x0,
+                       const float* weight, int loss_kind, float huber_delta, const float* step_scalars, float vlb_lambda,
+                       float* vlb_sum_out, void* stream) {
+  if (!step_scalars) { set_error("sr3_train_step_ex2: step_scalars is NULL"); return SR3_E_BADARG; }
+  return train_step_body("sr3_train_step_ex2", plan, hr_nchw, cond_nchw, cond_channels, z_nchw, q_ca, q_cb, noise_level, timestep, freq, params,
+                         grads, workspace, workspace_bytes, loss_sum_out, grad_scale, dropout_p, dropout_seed, n_marks, mark_offsets,
+                         mark_events, batch, tgt_z, tgt_x0, weight, loss_kind, huber_delta, step_scalars, vlb_lambda, vlb_sum_out, stream);
 }
 
 int sr3_train_step(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels, const float* z_nchw,

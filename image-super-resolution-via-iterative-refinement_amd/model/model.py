@@ -81,10 +81,17 @@ class DDPM(BaseModel):
         l_pix = l_pix.sum() / int(b * c * h * w * _dist.dp_world_size())
         self.optG.step()
         gn = self.optG.last_grad_norm()
-        if gn is None:
+        # learned variance: L_vlb of the step in bits per dimension (the engine's sum is over every rank's batch)
+        vlb = getattr(self.netG, 'last_vlb', None) if getattr(self.netG, 'learned_variance', None) is not None else None
+        names, vals = ['l_pix'], [l_pix]
+        if gn is not None:      # clip_grad_norm: the norm of the last optimizer step taken, read in the same device-to-host copy as the loss
+            names.append('grad_norm'), vals.append(gn)
+        if vlb is not None:
+            names.append('l_vlb'), vals.append(vlb / _dist.dp_world_size())
+        if len(vals) == 1:
             self.log_dict['l_pix'] = l_pix.item()
-        else:       # clip_grad_norm: the norm of the last optimizer step taken, read in the same device-to-host copy as the loss
-            self.log_dict['l_pix'], self.log_dict['grad_norm'] = torch.stack([l_pix, gn]).tolist()
+        else:
+            self.log_dict.update(zip(names, torch.stack([v.reshape(()).float() for v in vals]).tolist()))
 
     def _setup_distillation(self, dopt):
         """train.distill = {"teacher": "<checkpoint prefix>", "steps": N, "walk": "logsnr", "guidance_scale": null}: build the frozen teacher
@@ -96,6 +103,9 @@ class DDPM(BaseModel):
         from sr3_hip.distill import Distiller
         if not hasattr(dopt, 'get') or dopt.get('teacher') is None or dopt.get('steps') is None:
             raise ValueError('train.distill: "teacher" (a checkpoint prefix) and "steps" are required (got %r)' % (dopt,))
+        if getattr(self.netG, 'learned_variance', None) is not None:
+            raise NotImplementedError('train.distill of a learned-variance model: the student\'s step trains the pixel loss alone and has no '
+                                      'target for the variance rows; distil a model without model.diffusion.learned_variance')
         if self.device.type != 'cuda':
             raise L.Sr3Error('train.distill needs the model on a GPU (set gpu_ids); there is no CPU fallback')
         gen_path, opt_path = self._ckpt_paths(dopt['teacher'])

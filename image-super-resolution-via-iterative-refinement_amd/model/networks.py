@@ -28,11 +28,22 @@ def define_G(opt):
     u = model_opt['unet']
     if ('norm_groups' not in u) or u['norm_groups'] is None:
         u['norm_groups'] = 32
+    # engine key model.diffusion.learned_variance: {"lambda": 0.001} -- the UNet emits 2 x channels rows, the prediction and a variance head
+    # (set_learned_variance); without the key an out_channel above 4 is refused as ever
+    lv = model_opt['diffusion'].get('learned_variance')
+    if lv is not None and lv is not False:
+        want = 2 * int(model_opt['diffusion']['channels'])
+        if int(u['out_channel']) != want:
+            raise ValueError('learned_variance needs unet.out_channel = %d (2 x %d image channels: the prediction and the variance head); '
+                             'the config has out_channel %d' % (want, int(model_opt['diffusion']['channels']), int(u['out_channel'])))
+    else:
+        lv = None
     denoiser = unet.UNet(
         in_channel=u['in_channel'], out_channel=u['out_channel'], norm_groups=u['norm_groups'],
         inner_channel=u['inner_channel'], channel_mults=u['channel_multiplier'], attn_res=u['attn_res'],
         res_blocks=u['res_blocks'], dropout=u['dropout'], image_size=model_opt['diffusion']['image_size'],
-        long_attention=bool(u.get('long_attention', False)))      # (engine key: images whose attention level exceeds the LDS score strip)
+        long_attention=bool(u.get('long_attention', False)),      # (engine key: images whose attention level exceeds the LDS score strip)
+        **({} if lv is None else {'learned_variance': True}))
     netG = diffusion.GaussianDiffusion(
         denoiser, image_size=model_opt['diffusion']['image_size'], channels=model_opt['diffusion']['channels'],
         loss_type='l1', conditional=model_opt['diffusion']['conditional'],
@@ -50,6 +61,9 @@ def define_G(opt):
         netG.set_objective(loss.get('type', 'l1'), loss.get('delta'), loss.get('weight', 'uniform'), loss.get('gamma'))
     if d.get('cond_drop') is not None:
         netG.set_cond_drop(d['cond_drop'])
+    if lv is not None:
+        from sr3_hip.diffusion import parse_learned_variance
+        netG.set_learned_variance(parse_learned_variance(lv))
     # "self_condition": {"prob": 0.5} | true -- the network reads its own last x0 as extra input channels (set_self_condition; unet.in_channel
     # is then conditioning channels + 2 x channels)
     if d.get('self_condition') is not None:

@@ -40,6 +40,15 @@ draws s per image up to max_level (sr3_cond_augment_f32, which applies cond_drop
 once per chain at sample_level, so no step changes.  Whatever reads the conditioning image as data -- the first snapshot, the rules'
 targets -- reads the clean one.
 
+Learned reverse-process variance (engine extension, `"learned_variance": {"lambda": 0.001}` in model.diffusion with unet.out_channel =
+2 x channels, or `set_learned_variance`; Nichol & Dhariwal 2021): the network's second half of output channels is a per-pixel v that
+interpolates log sigma^2 between log beta and log beta~ of the step.  Training: the hybrid loss L_simple + lambda L_vlb
+(sr3_train_step_ex2) at a step drawn ON the schedule's grid -- for the SR3 variant gamma = sqrt_alphas_cumprod_prev[t], not a uniform
+draw between two grid values, because q(x_{t-1} | x_t, x0) exists on the grid only (the one change to the draws, under the key alone).
+Sampling: `"sampler": {"type": "ancestral", "steps": S}` (no sampler block: all T steps) is the respaced DDPM walk (`ancestral_tables`);
+every step runs forward (2C channels) -> sr3_learned_var_step.  Every other sampler and rule runs on such a network with its table
+sigma: their forwards launch the prediction rows of the output conv alone.
+
 Rules on x0 (engine extensions, keys next to "sampler" / "tiling" or the setters; sr3_hip/x0_rules.py holds each rule once): what is done
 to the predicted x0 before the posterior mix.  Per step: UNet forward with the output stored, then the rule's entry in place of the fused
 tail.  The rules exclude one another and tiling -- each owns the whole tail of a step.
@@ -355,7 +364,104 @@ def sampler_tables(alphas_cumprod, steps, eta, *, kind='ddim', walk='time', pred
     return out
 
 
-_SAMPLER_TABLES = ('a', 'b', 'c1', 'c2', 'c3', 'sigma', 'level', 'tau')
+LEARNED_VARIANCE_LAMBDA = 0.001      # the default of the config key (Nichol & Dhariwal 2021, section 3.1)
+
+
+def parse_learned_variance(spec):
+    """The config key model.diffusion.learned_variance -> the argument of set_learned_variance: {"lambda": l} -> l, true or {} -> the
+    default 0.001, absent / null / false -> None (off)."""
+    if spec is None or spec is False:
+        return None
+    if spec is True:
+        return LEARNED_VARIANCE_LAMBDA
+    if not hasattr(spec, 'get') or not hasattr(spec, 'keys'):
+        raise ValueError('learned_variance: true or a dict with "lambda" is expected (got %r)' % (spec,))
+    for k in spec.keys():
+        if k != 'lambda':
+            raise ValueError('learned_variance: unknown key %r (known: "lambda")' % (k,))
+    lam = spec.get('lambda')
+    return LEARNED_VARIANCE_LAMBDA if lam is None else lam
+
+
+def ancestral_tables(alphas_cumprod, steps, *, walk='time', prediction='eps'):
+    """Tables of the respaced DDPM walk (Nichol & Dhariwal 2021, section 4) over `sampler_walk`'s timesteps tau, in the form of the
+    step tail: with ab_j = alphas_cumprod[tau[j]] and ab_{-1} = 1,
+
+        beta'_j = 1 - ab_j / ab_{j-1} ;  beta~'_j = beta'_j (1 - ab_{j-1}) / (1 - ab_j)
+        c1 = beta'_j sqrt(ab_{j-1}) / (1 - ab_j) ;  c2 = (1 - ab_{j-1}) sqrt(1 - beta'_j) / (1 - ab_j)      the posterior's mean
+
+    a, b as `sampler_tables` (by `prediction`); sigma = sqrt(beta~'), 0 at j = 0 -- the fixed small variance, which the learned-variance
+    tail reads only for that zero: the mark of the walk's last step; log_beta = log beta', log_beta_tilde = log beta~' with entry 0
+    set to entry 1 (beta~'_0 = 0; the Improved-DDPM convention, not log 1e-20; a one-step walk: log beta'_0).  steps = T gives the
+    schedule's own betas and posterior_mean_coef1/2.  Pure numpy, float64, no device.  Returns a dict: tau, a, b, c1, c2, sigma,
+    log_beta, log_beta_tilde ([S]) and level ([S + 1], as `sampler_tables`)."""
+    if not isinstance(walk, str):
+        walk = _explicit_walk(alphas_cumprod, steps, walk)
+        steps = int(walk.shape[0])
+    ac, T, S = _check_walk_args(alphas_cumprod, steps)
+    _check_prediction(prediction)
+    tau = sampler_walk(ac, S, walk)
+    ab = ac[tau]
+    ap = np.append(1.0, ab[:-1])
+    beta = 1.0 - ab / ap
+    bt = beta * (1.0 - ap) / (1.0 - ab)
+    c1, c2 = beta * np.sqrt(ap) / (1.0 - ab), (1.0 - ap) * np.sqrt(1.0 - beta) / (1.0 - ab)
+    sigma = np.sqrt(bt)
+    sigma[0] = 0.0
+    log_beta = np.log(beta)
+    with np.errstate(divide='ignore'):
+        log_bt = np.log(bt)
+    log_bt[0] = log_bt[1] if S > 1 else log_beta[0]
+    a, b = np.sqrt(1.0 / ab), np.sqrt(1.0 / ab - 1)
+    if prediction != 'eps':
+        a, b = prediction_coefs(prediction, np.sqrt(ab), np.sqrt(1.0 - ab))[:2]
+    out = dict(tau=tau, a=a, b=b, c1=c1, c2=c2, sigma=sigma, log_beta=log_beta, log_beta_tilde=log_bt, level=np.append(1.0, np.sqrt(ab)))
+    if not all(np.all(np.isfinite(v)) for v in out.values()):
+        raise ValueError('ancestral tables are not finite')
+    return out
+
+
+def hybrid_step_scalars(tables, t):
+    """The rows of sr3_train_step_ex2's step_scalars for the steps `t` (ints, 0-based, into `ancestral_tables(ac, T)`): float64 [n, 8]
+    = {a, b, c1, c2, log beta, log beta~ (clipped), last, 0}, last = 1 at t = 0."""
+    t = np.asarray(t, dtype=np.int64).reshape(-1)
+    out = np.zeros((t.shape[0], 8), dtype=np.float64)
+    for k, name in enumerate(('a', 'b', 'c1', 'c2', 'log_beta', 'log_beta_tilde')):
+        out[:, k] = np.asarray(tables[name], dtype=np.float64)[t]
+    out[:, 6] = (t == 0).astype(np.float64)
+    return out
+
+
+def widen_for_learned_variance(state):
+    """An existing checkpoint -> one a learned-variance network of twice the output rows loads: C zero rows are appended to
+    final_conv.block.3.weight and to its bias (C = the rows they have; v = 0 everywhere: sigma^2 the geometric midpoint of beta and beta~),
+    every other entry is kept.  `state`: a *_gen.pth state dict (any key prefix), or the dict of a *_opt.pth -- there the Adam moments
+    of those two parameters, the last two of the parameter table, are widened with zeros.  Returns a new dict; tensors that do not
+    change are shared with the input."""
+    def rows(t):
+        return torch.cat([t, torch.zeros_like(t)], 0)
+    if isinstance(state, dict) and 'optimizer' in state:
+        out = dict(state)
+        opt = dict(state['optimizer'])
+        st = dict(opt.get('state') or {})
+        for i in sorted(st.keys())[-2:]:       # final_conv.block.3.weight, .bias: the last two entries of the table
+            st[i] = {k: (rows(v) if k in ('exp_avg', 'exp_avg_sq') else v) for k, v in st[i].items()}
+        opt['state'] = st
+        out['optimizer'] = opt
+        return out
+    out = type(state)()
+    hit = 0
+    for k, v in state.items():
+        if k.endswith('final_conv.block.3.weight') or k.endswith('final_conv.block.3.bias'):
+            v = rows(v)
+            hit += 1
+        out[k] = v
+    if hit == 0:
+        raise ValueError('widen_for_learned_variance: no final_conv.block.3.weight / .bias in the state dict')
+    return out
+
+
+_SAMPLER_TABLES = ('a', 'b', 'c1', 'c2', 'c3', 'sigma', 'level', 'tau', 'log_beta', 'log_beta_tilde')
 
 _BUFFERS = ('betas', 'alphas_cumprod', 'alphas_cumprod_prev', 'sqrt_alphas_cumprod',
             'sqrt_one_minus_alphas_cumprod', 'log_one_minus_alphas_cumprod', 'sqrt_recip_alphas_cumprod',
@@ -391,6 +497,9 @@ class EngineDiffusion(nn.Module):
         self._self_cond_buf = None     # training: the [B, Cl + C, H, W] conditioning tensor of a self-conditioned step
         self.cond_augment = None       # None: off; else {'max_level': m, 'sample_level': s, 'level_channel': bool} (set_cond_augment)
         self._cond_aug_buf = None      # training: the [B, Cl (+ 1), H, W] augmented conditioning tensor
+        self.learned_variance = None   # None: off; else {'lambda': l}: the network's last `channels` output rows are the variance head (set_learned_variance)
+        self._hyb_table = None         # training: per-timestep rows of sr3_train_step_ex2's step_scalars on the device, built on first use
+        self.last_vlb = None           # the last p_losses' L_vlb in bits per dimension (0-dim device tensor) under the key
         self.max_cached_loops = 3      # reverse-loop states (buffers + workspace + captured graph) kept, one per (shape, launch list)
         # schedule_opt is accepted and ignored exactly like the reference ctor (diffusion.py:80-82)
 
@@ -440,14 +549,17 @@ class EngineDiffusion(nn.Module):
         # engine key of the schedule dict: "sampler": {"type": "ddim" | "dpmpp_2m", "steps": S, "eta": e, "walk": "time" | "logsnr" | [t, ...]};
         # absent / null: the ancestral loop
         spec = schedule_opt.get('sampler') if hasattr(schedule_opt, 'get') else None
+        self._hyb_table = None
         if spec is None:
-            self.set_sampler(None)
+            # (a learned-variance model without a sampler block: the ancestral walk over all T steps, on its own sigma)
+            self.set_sampler(None) if self.learned_variance is None else self.set_sampler(self.num_timesteps, kind='ancestral')
         else:
             kind = spec.get('type', 'ddim')
-            _check_sampler_kind(kind)              # (an unknown type is refused before a missing "steps")
+            if kind != 'ancestral':
+                _check_sampler_kind(kind)          # (an unknown type is refused before a missing "steps")
             if spec.get('steps') is None:
                 raise ValueError('sampler: "steps" is required')
-            self.set_sampler(spec['steps'], spec.get('eta', 0.0), kind=kind, walk=spec.get('walk'))
+            self.set_sampler(spec['steps'], spec.get('eta', 1.0 if kind == 'ancestral' else 0.0), kind=kind, walk=spec.get('walk'))
         # engine key next to it: "tiling": {"tile": 128 | [th, tw], "overlap": 32, "batch": 8}; absent / null: whole-image steps
         spec = schedule_opt.get('tiling') if hasattr(schedule_opt, 'get') else None
         if spec is None:
@@ -467,9 +579,26 @@ class EngineDiffusion(nn.Module):
         default), 'logsnr' (uniform in log-SNR, the multistep solver's default -- on the 'time' walk it is worse than DDIM) or an explicit
         list of `steps` timesteps (`sampler_walk`; kept in self.sampler['walk'] as a list of ints).  What
         p_sample_loop and everything on top of it (sample, super_resolution, the validation waves) runs; p_sample, p_mean_variance and
-        p_losses keep the schedule's own timesteps."""
+        p_losses keep the schedule's own timesteps.  kind = 'ancestral' (a learned-variance model only, set_learned_variance): the
+        respaced DDPM walk of `ancestral_tables`, every step drawn with the network's own sigma (sr3_learned_var_step); eta is not read."""
         if steps is None:
             tabs, self.sampler = None, None
+        elif kind == 'ancestral':
+            if getattr(self, '_alphas_cumprod64', None) is None:
+                raise RuntimeError('set_sampler needs a noise schedule (set_new_noise_schedule first)')
+            if self.learned_variance is None:
+                raise ValueError('sampler type "ancestral" is the learned-variance walk and needs model.diffusion.learned_variance '
+                                 '(set_learned_variance); on a fixed variance the strided ancestral sampler is '
+                                 '{"type": "ddim", "steps": S, "eta": 1.0}')
+            if walk is None:
+                walk = 'time'
+            elif not isinstance(walk, str):
+                walk = [int(v) for v in sampler_walk(self._alphas_cumprod64, steps, walk)]
+            tabs = dict(ancestral_tables(self._alphas_cumprod64, steps, walk=walk, prediction=self.prediction), c3=None)
+            self._check_learned_variance(sampler='ancestral')
+            self.sampler = dict(type='ancestral', steps=int(steps), eta=1.0)
+            if walk != 'time':
+                self.sampler['walk'] = walk
         else:
             if getattr(self, '_alphas_cumprod64', None) is None:
                 raise RuntimeError('set_sampler needs a noise schedule (set_new_noise_schedule first)')
@@ -489,7 +618,7 @@ class EngineDiffusion(nn.Module):
                 tabs = dict(tabs, c3=None)         # a one-step rule keeps no history: no table, no buffer, the kernels without it
         dev = self.betas.device if hasattr(self, 'betas') else None
         for k in _SAMPLER_TABLES:                # the float64 tables rounded once to fp32; the walk as int32 (what k_embed reads)
-            t = None if tabs is None or tabs[k] is None else torch.tensor(tabs[k], dtype=torch.int32 if k == 'tau' else torch.float32).to(dev)
+            t = None if tabs is None or tabs.get(k) is None else torch.tensor(tabs[k], dtype=torch.int32 if k == 'tau' else torch.float32).to(dev)
             self.register_buffer('_sampler_' + k, t, persistent=False)
         self._loop_cache = {}
 
@@ -500,6 +629,7 @@ class EngineDiffusion(nn.Module):
         _check_prediction(kind)
         self.prediction = kind
         self._train_tables = None
+        self._hyb_table = None
         sp = self.sampler
         if sp is not None:
             self.set_sampler(sp['steps'], sp['eta'], kind=sp['type'], walk=sp.get('walk', 'time'))
@@ -531,6 +661,7 @@ class EngineDiffusion(nn.Module):
             self.tiling = None
         else:
             t = TL.parse_tiling(dict(tile=tile, overlap=overlap, batch=batch), self.denoise_fn.plan.divisor)
+            self._check_learned_variance(tiling=t)
             self._check_tiled_sampler(self.sampler is not None, t)
             self._check_rules({}, False, t)
             self._check_self_condition(self.self_condition is not None, False, t, None)
@@ -568,6 +699,7 @@ class EngineDiffusion(nn.Module):
         """the body of set_consistency / set_guidance / set_backprojection: the rule's validation, the compatibility check, the attribute"""
         cfg = rule.validate(self, *args)
         if cfg is not None:
+            self._check_learned_variance(rules={rule.name: cfg})
             self._check_rules({rule.name: cfg}, self.sampler is not None, self.tiling)
             if rule is X.GUIDANCE:
                 self._check_self_condition(self.self_condition is not None, False, None, cfg)
@@ -599,6 +731,7 @@ class EngineDiffusion(nn.Module):
             self.self_condition = None
         else:
             pf = X._number('self_condition prob', prob, lambda f: 0.0 <= f <= 1.0, 'lie in [0, 1]')
+            self._check_learned_variance(self_condition=True)
             self._check_cond_augment(self.cond_augment, True)      # (before the channel count: the two ask for different ones)
             lr = self.channels if self.conditional else 0
             have, want = int(self.denoise_fn.plan.in_channel), lr + 2 * self.channels
@@ -657,6 +790,54 @@ class EngineDiffusion(nn.Module):
             self.cond_augment = cfg
         self._cond_aug_buf = None
         self._loop_cache = {}
+
+    def set_learned_variance(self, lam=LEARNED_VARIANCE_LAMBDA):
+        """Learned reverse-process variance (Nichol & Dhariwal 2021, "Improved DDPM"): the UNet's out_channel is 2 x channels -- the
+        prediction, read under `prediction` as ever, then a per-pixel v with log sigma^2 = f log beta + (1 - f) log beta~, f = (v + 1) /
+        2.  lam >= 0 (config key model.diffusion.learned_variance: {"lambda": 0.001}, or true for that default): p_losses trains the
+        hybrid loss L_simple + lam L_vlb at a step drawn on the schedule's grid, and logs L_vlb in bits per dimension (`last_vlb`).
+        Sampling: the "ancestral" sampler (`set_sampler(S, kind='ancestral')`; what a schedule without a sampler block gets, over all
+        T steps) draws every step with the network's sigma; every other sampler and rule runs on the prediction rows with its table
+        sigma.  lam None: off.  Not built (NotImplementedError, here or when the loop starts): the ancestral sampler together with
+        tiling, consistency, guidance, back-projection or self-conditioning; train.distill."""
+        if lam is None:
+            self.learned_variance = None
+            if self.sampler is not None and self.sampler['type'] == 'ancestral':
+                self.set_sampler(None)
+        else:
+            lf = X._number('learned_variance lambda', lam, lambda f: f >= 0.0, 'be >= 0')
+            have, want = int(self.denoise_fn.plan.out_channel), 2 * self.channels
+            if have != want or int(self.denoise_fn.plan.var_channels) != self.channels:
+                raise ValueError('learned_variance needs a UNet with out_channel %d (2 x %d image channels: the prediction and the '
+                                 'variance head) built for it; this one has out_channel %d%s'
+                                 % (want, self.channels, have, '' if have != want else ' without the variance head (learned_variance=True)'))
+            self.learned_variance = {'lambda': lf}
+            if self.sampler is None and getattr(self, '_alphas_cumprod64', None) is not None:
+                self.set_sampler(self.num_timesteps, kind='ancestral')
+        self._hyb_table = None
+        self._loop_cache = {}
+
+    def _check_learned_variance(self, sampler=None, tiling=None, rules=None, self_condition=None):
+        """What the learned-variance tail -- the "ancestral" sampler -- does not go with, over the settings as they are with the given ones
+        in place of theirs; DESIGN.md section 6 says what each would need.  Every one of them runs on a learned-variance network under
+        a DDIM or DPM-Solver++ sampler, with that sampler's table sigma."""
+        sp = getattr(self, 'sampler', None)
+        kind = sampler if sampler is not None else (None if sp is None else sp['type'])
+        if kind != 'ancestral':
+            return
+        how = ('; sample with {"type": "ddim", "steps": S, "eta": e} (set_sampler), which runs it on the prediction rows with the '
+               'table sigma')
+        if (tiling if tiling is not None else getattr(self, 'tiling', None)) is not None:
+            raise NotImplementedError('the learned-variance ancestral sampler with tiling: sr3_tiled_step blends eps tiles and has no '
+                                      'variance input' + how)
+        cfgs = dict({r.name: getattr(self, r.name, None) for r in X.RULES}, **(rules or {}))
+        for r in X.RULES:
+            if cfgs[r.name] is not None:
+                raise NotImplementedError('the learned-variance ancestral sampler with %s: the rule owns the whole tail of a step and '
+                                          'draws with the table sigma' % r.name + how)
+        if (self_condition if self_condition is not None else getattr(self, 'self_condition', None) is not None):
+            raise NotImplementedError('the learned-variance ancestral sampler with self-conditioning: sr3_selfcond_x0_f32 reads a '
+                                      'C-channel output' + how)
 
     @staticmethod
     def _check_cond_augment(cfg, self_condition):
@@ -781,6 +962,8 @@ class EngineDiffusion(nn.Module):
                       cond=None if cond_shape is None else torch.empty(cond_shape, device=dev),
                       step=torch.zeros(2, dtype=torch.int32, device=dev), graph=None, ws=E.Workspace(),      # [scratch, t]
                       gens=[torch.Generator(device=dev) for _ in range(shape[0])] if item_streams else None)
+            if self.sampler is not None and self.sampler['type'] == 'ancestral':
+                st['out2'] = torch.empty((shape[0], 2 * shape[1]) + tuple(shape[2:]), device=dev)      # the prediction and the variance head
             if self.sampler is not None and self._sampler_c3 is not None:
                 st['hist'] = torch.zeros(shape, device=dev)      # a multistep sampler: the previous step's x0 (_sample_loop zero-fills it per chain)
             if tiles is not None:
@@ -892,6 +1075,17 @@ class EngineDiffusion(nn.Module):
                 L.check(lib.sr3_p_sample_step_hist(L.ptr(img), L.ptr(st['eps']), L.ptr(z), *[L.ptr(t) for t in tables], L.ptr(step), None, 0,
                                                    B, Cc * H * W, 1, L.ptr(c3), L.ptr(hist), self._stream(img.device)))
                 L.check(lib.sr3_step_decrement(L.ptr(step), self._stream(img.device)))
+            return
+        if st.get('out2') is not None:
+            # learned variance: the forward stores all 2C rows (level / timestep from the device counter, which only the tail moves),
+            # then the tail draws with the network's own sigma (sr3_learned_var_step)
+            assert g is None and x0_rule is None and c3 is None      # (_check_learned_variance refused them)
+            B, Cc, H, W = img.shape
+            self.denoise_fn(img, None, cond=st['cond'], level_table=level, step_dev=st['step'][1:], out=st['out2'], ws=st['ws'],
+                            full=True, t_map=t_map)
+            L.check(L.load().sr3_learned_var_step(L.ptr(img), L.ptr(st['out2']), L.ptr(z), B, Cc, H, W, *[L.ptr(t) for t in tables],
+                                                  L.ptr(self._sampler_log_beta), L.ptr(self._sampler_log_beta_tilde), L.ptr(st['step']),
+                                                  1, None, None, self._stream(img.device)))
             return
         if x0_rule is not None:
             # the forward stores its output (level / timestep from the device counter, which only the tail's last kernel moves), then
@@ -1014,6 +1208,7 @@ class EngineDiffusion(nn.Module):
                 raise NotImplementedError('%s on an unconditional model needs %s=: there is no conditioning image to %s'
                                           % (r.noun, r.target_kw, r.target_from))
         selfc = self.self_condition is not None
+        self._check_learned_variance(tiling=tiling)
         self._check_self_condition(selfc, self.sampler is not None, tiling, cfgs.get('guidance'))
         aug = self.cond_augment
         self._check_cond_augment(aug, selfc)
@@ -1193,8 +1388,20 @@ class EngineDiffusion(nn.Module):
         dev = x_start.device
         un = self.denoise_fn           # (a CPU tensor is refused by the engine call: there is no CPU fallback)
         level = tstep = None
+        lv = self.learned_variance
+        hyb_t = None                   # under the key: the drawn step of every image, 0-based, on the schedule's grid
         if self.variant == 'sr3':
-            if gamma is None:
+            if lv is not None:
+                # q(x_{t-1} | x_t, x0) exists on the grid only: gamma is the level the sampler feeds at step t, not a uniform draw
+                # between two grid values -- the one change to the draws, under the key alone
+                if gamma is not None:
+                    raise ValueError('p_losses under learned_variance draws gamma on the schedule\'s grid: inject t (1 .. T), not gamma')
+                tt = np.random.randint(1, self.num_timesteps + 1) if t is None else int(t)
+                if not 1 <= tt <= self.num_timesteps:
+                    raise ValueError('p_losses: t must lie in [1, %d] (got %d)' % (self.num_timesteps, tt))
+                gamma = torch.FloatTensor(np.full(b, self.sqrt_alphas_cumprod_prev[tt]))
+                hyb_t = torch.full((b,), tt - 1, dtype=torch.long, device=dev)
+            elif gamma is None:
                 tt = np.random.randint(1, self.num_timesteps + 1) if t is None else int(t)
                 gamma = torch.FloatTensor(np.random.uniform(self.sqrt_alphas_cumprod_prev[tt - 1],
                                                             self.sqrt_alphas_cumprod_prev[tt], size=b))
@@ -1207,6 +1414,7 @@ class EngineDiffusion(nn.Module):
                 t = torch.randint(0, self.num_timesteps, (b,), device=dev).long()
             tstep = t.long().to(dev)
             ca, cb = self.sqrt_alphas_cumprod[tstep], self.sqrt_one_minus_alphas_cumprod[tstep]
+            hyb_t = tstep if lv is not None else None
         if noise is None:
             noise = torch.randn_like(x_start)
         cond = x_in['SR'].contiguous() if self.conditional else None
@@ -1228,9 +1436,21 @@ class EngineDiffusion(nn.Module):
             cond = buf
         if self_cond is not None or self.self_condition is not None:
             cond = self._self_condition_input(x_start, cond, noise, ca, cb, level, tstep, gamma, self_cond)
-        return un.train_step(x_start, cond, noise.contiguous(), ca.contiguous(), cb.contiguous(), level, tstep,
+        if lv is None:
+            return un.train_step(x_start, cond, noise.contiguous(), ca.contiguous(), cb.contiguous(), level, tstep,
+                                 grad_scale=1.0 / float(b * c * h * w), drop_seed=drop_seed,
+                                 objective=self._train_objective(tstep, gamma, dev))
+        # the hybrid loss: per image the scalars of its step -- the x0 rule, the posterior's coefficients, log beta, log beta~ (clipped),
+        # the last-step flag -- from the walk over all T steps (`ancestral_tables`, float64, rounded once), gathered on the device
+        if self._hyb_table is None or self._hyb_table.device != dev:
+            tabs = ancestral_tables(self._alphas_cumprod64, self.num_timesteps, prediction=self.prediction)
+            self._hyb_table = torch.tensor(hybrid_step_scalars(tabs, np.arange(self.num_timesteps)), dtype=torch.float32).to(dev)
+        scal = self._hyb_table[hyb_t].contiguous()
+        loss = un.train_step(x_start, cond, noise.contiguous(), ca.contiguous(), cb.contiguous(), level, tstep,
                              grad_scale=1.0 / float(b * c * h * w), drop_seed=drop_seed,
-                             objective=self._train_objective(tstep, gamma, dev))
+                             objective=self._train_objective(tstep, gamma, dev), hybrid=(scal, lv['lambda']))
+        self.last_vlb = un.last_vlb / float(b * c * h * w)      # bits per dimension (the sum is over every rank's batch: see model.py)
+        return loss
 
     def _cond_augment_input(self, cond, keep, cond_level, cond_noise):
         """The conditioning tensor of a training step under noise conditioning augmentation, [B, Cl (+ 1), H, W] in a buffer this module

@@ -45,6 +45,7 @@ class Plan(object):
         self.in_channel = int(in_channel)
         self.out_channel = int(out_channel if out_channel is not None else in_channel)
         self.image_size = int(image_size)
+        self.var_channels = 0      # plan option var_channels: the last rows of the output conv that are a learned-variance head
         self.desc = make_desc(variant, in_channel, out_channel, inner_channel, norm_groups, channel_mults,
                               attn_res, res_blocks, image_size)
         h = C.c_void_p()
@@ -79,6 +80,8 @@ class Plan(object):
         if rc < 0:
             L.check(rc)
         self.options[key] = int(value)
+        if key == 'var_channels':
+            self.var_channels = int(value)
         # anything compiled / captured against the previous options is stale, at every geometry
         self.generation = self._next_generation
         self._next_generation += 1
@@ -104,6 +107,11 @@ class Plan(object):
             gen = self._geometry_generation[self.geometry] = self._next_generation
             self._next_generation += 1
         self.generation = gen
+
+    @property
+    def image_channels(self):
+        """Channels of x, z and eps of a step: out_channel without the variance head."""
+        return self.out_channel - self.var_channels
 
     def workspace_bytes(self, batch):
         n = int(self.lib.sr3_workspace_bytes(self.handle, int(batch)))
@@ -198,9 +206,9 @@ def reverse_step(plan, arena, freq, ws, x, z, tables, step2, cond=None, level_ta
     if cond is not None:
         cond = cond.contiguous()
         cc = cond.shape[1]
-    if x.dim() != 4 or x.shape[1] + cc != plan.in_channel or x.shape[1] != plan.out_channel:
+    if x.dim() != 4 or x.shape[1] + cc != plan.in_channel or x.shape[1] != plan.image_channels:
         raise L.Sr3Error('input shape %s (+%d cond channels) does not match the plan (in_channel %d, out_channel %d)'
-                         % (tuple(x.shape), cc, plan.in_channel, plan.out_channel))
+                         % (tuple(x.shape), cc, plan.in_channel, plan.image_channels))
     _check_same_size(x, cond)
     plan.set_geometry(x.shape[2], x.shape[3])
     if step2.dtype != torch.int32 or step2.numel() != 2 or step2.device != x.device:
@@ -220,8 +228,10 @@ def reverse_step(plan, arena, freq, ws, x, z, tables, step2, cond=None, level_ta
 
 
 def unet_forward(plan, arena, freq, ws, x, cond=None, noise_level=None, timestep=None, level_table=None,
-                 step_dev=None, out=None):
-    """eps = UNet(cat([cond, x], 1), level)   (all tensors on the GPU, fp32, NCHW contiguous)."""
+                 step_dev=None, out=None, full=False, t_map=None):
+    """eps = UNet(cat([cond, x], 1), level)   (all tensors on the GPU, fp32, NCHW contiguous).  `full` (a plan with a variance head,
+    option var_channels): all out_channel rows -- the prediction, then the variance head (sr3_unet_forward_full); otherwise the
+    prediction rows alone.  `t_map` (with `full` and step_dev, DDPM variant): the timestep is t_map[*step_dev]."""
     if not x.is_cuda:
         raise L.Sr3Error('the MI355X engine only runs on a GPU tensor (got %s); there is no CPU fallback' % x.device)
     B = x.shape[0]
@@ -246,11 +256,19 @@ def unet_forward(plan, arena, freq, ws, x, cond=None, noise_level=None, timestep
         if timestep.numel() != B:
             raise L.Sr3Error('timestep must have one value per sample')
     wsbuf, need = ws.get(plan, B, x.device)
+    rows = plan.out_channel if full else plan.image_channels
     if out is None:
-        out = torch.empty(B, plan.out_channel, x.shape[2], x.shape[3], device=x.device, dtype=torch.float32)
-    elif tuple(out.shape) != (B, plan.out_channel, x.shape[2], x.shape[3]) or not out.is_contiguous():
-        raise L.Sr3Error('out must be a contiguous %s tensor (got %s)' % ((B, plan.out_channel, x.shape[2], x.shape[3]), tuple(out.shape)))
+        out = torch.empty(B, rows, x.shape[2], x.shape[3], device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, rows, x.shape[2], x.shape[3]) or not out.is_contiguous():
+        raise L.Sr3Error('out must be a contiguous %s tensor (got %s)' % ((B, rows, x.shape[2], x.shape[3]), tuple(out.shape)))
     stream = torch.cuda.current_stream(x.device).cuda_stream
+    if t_map is not None and (not full or t_map.dtype != torch.int32 or not t_map.is_contiguous() or t_map.device != x.device):
+        raise L.Sr3Error('t_map goes with full=True and must be a contiguous int32 tensor on the device of x')
+    if full:
+        L.check(plan.lib.sr3_unet_forward_full(plan.handle, L.ptr(x), L.ptr(cond), cc, L.ptr(noise_level), L.ptr(timestep),
+                                               L.ptr(freq), L.ptr(level_table), L.ptr(step_dev), L.ptr(arena), L.ptr(wsbuf),
+                                               need, L.ptr(out), B, C.c_void_p(stream), L.ptr(t_map)))
+        return out
     L.check(plan.lib.sr3_unet_forward(plan.handle, L.ptr(x), L.ptr(cond), cc, L.ptr(noise_level), L.ptr(timestep),
                                       L.ptr(freq), L.ptr(level_table), L.ptr(step_dev), L.ptr(arena), L.ptr(wsbuf),
                                       need, L.ptr(out), B, C.c_void_p(stream)))

@@ -83,6 +83,7 @@ SIGNATURES = {
     'sr3_plan_prepare_derived': (_I, [_P, _P, _P]),
     'sr3_plan_invalidate_derived': (_I, [_P]),
     'sr3_unet_forward': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _P]),
+    'sr3_unet_forward_full': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _P, _P]),
     'sr3_unet_forward_profile': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _Z, _P, _I, _P, _I, _P, _P, _P, _P]),
     'sr3_p_sample_step': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     'sr3_p_sample_step_ex': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
@@ -103,6 +104,7 @@ SIGNATURES = {
     'sr3_cond_drop_f32': (_I, [_P, _P, _I, _I, _P, _P]),
     'sr3_selfcond_x0_f32': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
     'sr3_cond_augment_f32': (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'sr3_learned_var_step': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     'sr3_abs_quantile_scratch_bytes': (_Z, [_I, _I]),
     'sr3_abs_quantile_f32': (_I, [_P, _I, _I, _I, C.c_double, _P, _P, _Z, _P]),
     'sr3_guided_step': (_I, [_P, _P, _P, _F, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_double, _P, _P, _Z, _P, _P]),
@@ -114,6 +116,10 @@ SIGNATURES = {
                             _I, _P, _P, _I, _P]),
     'sr3_train_step_ex': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, C.c_float, C.c_float, C.c_uint,
                                _I, _P, _P, _I, _P, _P, _P, _I, C.c_float, _P]),
+    'sr3_train_step_ex2': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, C.c_float, C.c_float, C.c_uint,
+                                _I, _P, _P, _I, _P, _P, _P, _I, C.c_float, _P, C.c_float, _P, _P]),
+    'sr3_hybrid_loss_grad_scratch_bytes': (_Z, []),
+    'sr3_hybrid_loss_grad_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_float, _I, _I, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
     'sr3_loss_grad_scratch_bytes': (_Z, []),
     'sr3_loss_grad_f32': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P]),
     'sr3_adam_step': (_I, [_P, _P, _P, _P, _Z, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P]),

@@ -25,7 +25,7 @@ class EngineUNet(nn.Module):
 
     def __init__(self, in_channel=6, out_channel=3, inner_channel=32, norm_groups=32,
                  channel_mults=(1, 2, 4, 8, 8), attn_res=(8), res_blocks=3, dropout=0,
-                 with_noise_level_emb=True, image_size=128, *, long_attention=False):
+                 with_noise_level_emb=True, image_size=128, *, long_attention=False, learned_variance=False):
         super().__init__()
         if not with_noise_level_emb:
             raise NotImplementedError('the engine always conditions on the noise level / timestep '
@@ -37,6 +37,15 @@ class EngineUNet(nn.Module):
         self.long_attention = bool(long_attention)
         if self.long_attention:
             self.plan.set_option('attn_long', 1)
+        # config key model.diffusion.learned_variance (plan option var_channels): the second half of the out_channel rows is the variance
+        # head.  Without it a plan with more than 4 output rows builds no launch list: refused here, by the library, in its words
+        self.learned_variance = bool(learned_variance)
+        if self.learned_variance:
+            if self.plan.out_channel % 2:
+                raise ValueError('learned_variance needs an even out_channel (got %d)' % self.plan.out_channel)
+            self.plan.set_option('var_channels', self.plan.out_channel // 2)
+        elif self.plan.out_channel > 4:
+            L.check(self.plan.lib.sr3_plan_op_info(self.plan.handle, 1, 0, L.OpInfo()))
         self.dropout = float(dropout)
         self.arena = nn.Parameter(torch.zeros(self.plan.param_floats, dtype=torch.float32), requires_grad=False)
         self.register_buffer('freq', self.plan.default_freq(), persistent=False)
@@ -244,14 +253,16 @@ class EngineUNet(nn.Module):
                     unexpected_keys.append(k)
 
     # ---- forward ---------------------------------------------------------------------------
-    def forward(self, x, time, *, cond=None, level_table=None, step_dev=None, out=None, ws=None):
+    def forward(self, x, time, *, cond=None, level_table=None, step_dev=None, out=None, ws=None, full=False, t_map=None):
         """eps = UNet(x, time).  `x` may already contain the conditioning channels (reference call
         convention `denoise_fn(torch.cat([cond, x], 1), level)`), or they can be passed separately as
         `cond`, which the input conv reads as a virtual concat (nothing is materialised).  `ws`: a caller-owned
         engine.Workspace (the captured reverse loop keeps its own so no other call can move the buffer its graph
-        has baked in)."""
+        has baked in).  `full`: a learned-variance network's variance rows too, [B, 2C, H, W] (engine.unet_forward)."""
         self.ensure_derived()
         kw = {}
+        if full:
+            kw.update(full=True, t_map=t_map)
         if step_dev is None:
             if self.variant == 'sr3':
                 kw['noise_level'] = time
@@ -270,11 +281,12 @@ class EngineUNet(nn.Module):
                               hist=hist)
 
     # ---- training step (forward + backward inside the engine) ------------------------------------
-    def train_step(self, hr, cond, z, ca, cb, level, tstep, grad_scale, drop_seed=None, objective=None):
+    def train_step(self, hr, cond, z, ca, cb, level, tstep, grad_scale, drop_seed=None, objective=None, hybrid=None):
         """One fused forward + backward: returns the sum-reduced loss (0-dim tensor, summed over all data-parallel
         ranks) and leaves d(loss * grad_scale)/d params -- rank-summed -- in `grad_arena`.  `objective`: None (the network predicts
         z, unweighted, the plan's loss) or (tgt_z, tgt_x0, weight, loss_kind, huber_delta) of sr3_train_step_ex, the first three
-        [B] device tensors or all None."""
+        [B] device tensors or all None.  `hybrid` (a learned-variance network): (step_scalars [B, 8] fp32 on the device, lambda) of
+        sr3_train_step_ex2 -- the loss is then L_simple + lambda L_vlb, and `last_vlb` holds the sum of L_vlb in bits (rank-summed)."""
         p_drop = self.dropout if self.training else 0.0
         if drop_seed is None:          # a fresh mask every step, drawn from torch's CPU generator
             drop_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_drop > 0 else 0
@@ -294,13 +306,21 @@ class EngineUNet(nn.Module):
             grad_scale = grad_scale / tdist.get_world_size()
             if self.accumulate == 1:
                 marks = red.mark_args()
-        self._engine_train_step(hr, cond, z, ca, cb, level, tstep, grad_scale, p_drop, drop_seed, marks, loss,
-                                **({} if objective is None else {'objective': objective}))
+        kw = {} if objective is None else {'objective': objective}
+        self.last_vlb = None
+        if hybrid is not None:
+            vlb = torch.zeros(1, device=dev)
+            kw['hybrid'] = (hybrid[0], float(hybrid[1]), vlb)
+        self._engine_train_step(hr, cond, z, ca, cb, level, tstep, grad_scale, p_drop, drop_seed, marks, loss, **kw)
+        sums = [loss] if hybrid is None else [loss, vlb]
         if dp:
             if self.accumulate == 1:
-                red.reduce(self.grad_arena, extra=[loss])
+                red.reduce(self.grad_arena, extra=sums)
             else:                      # the arena is reduced once per optimizer step, accumulated (reduce_arena): only the loss here
-                tdist.all_reduce(loss, op=tdist.ReduceOp.SUM)
+                for t in sums:
+                    tdist.all_reduce(t, op=tdist.ReduceOp.SUM)
+        if hybrid is not None:
+            self.last_vlb = vlb[0]
         return loss[0]
 
     def dp_reducing(self):
@@ -325,7 +345,8 @@ class EngineUNet(nn.Module):
         for lo, hi in red.buckets:
             red.dist.all_reduce(arena[lo:hi], op=red.dist.ReduceOp.SUM)
 
-    def _engine_train_step(self, hr, cond, z, ca, cb, level, tstep, grad_scale, p_drop, drop_seed, marks, loss, objective=None):
+    def _engine_train_step(self, hr, cond, z, ca, cb, level, tstep, grad_scale, p_drop, drop_seed, marks, loss, objective=None,
+                           hybrid=None):
         """The sr3_train_step_ex call itself (q_sample -> UNet forward -> loss -> backward, `marks` = the gradient-ready
         events of the data-parallel buckets); objective None is sr3_train_step's (NULL, NULL, NULL, -1, 0)."""
         import ctypes as C
@@ -369,6 +390,17 @@ class EngineUNet(nn.Module):
         for t in (tgt_z, tgt_x0, weight):
             if t is not None and (t.device != dev or t.dtype != torch.float32 or t.numel() != B or not t.is_contiguous()):
                 raise L.Sr3Error('training: tgt_z / tgt_x0 / weight must be contiguous fp32 tensors of %d elements on %s' % (B, dev))
+        if hybrid is not None:         # a learned-variance network: the hybrid loss, sr3_train_step_ex2
+            scal, lam, vlb = hybrid
+            if scal.device != dev or scal.dtype != torch.float32 or tuple(scal.shape) != (B, 8) or not scal.is_contiguous():
+                raise L.Sr3Error('training: step_scalars must be a contiguous fp32 [%d, 8] tensor on %s' % (B, dev))
+            L.check(plan.lib.sr3_train_step_ex2(plan.handle, L.ptr(hr), L.ptr(cond), cc, L.ptr(z), L.ptr(ca), L.ptr(cb),
+                                                L.ptr(level), L.ptr(tstep), L.ptr(self.freq), L.ptr(self.arena.data),
+                                                L.ptr(self.grad_arena), L.ptr(wsv), need, L.ptr(loss), C.c_float(grad_scale),
+                                                C.c_float(p_drop), C.c_uint(drop_seed & 0xFFFFFFFF), n_marks, offs, evs, B,
+                                                L.ptr(tgt_z), L.ptr(tgt_x0), L.ptr(weight), int(kind), C.c_float(delta),
+                                                L.ptr(scal), C.c_float(lam), L.ptr(vlb), stream))
+            return
         L.check(plan.lib.sr3_train_step_ex(plan.handle, L.ptr(hr), L.ptr(cond), cc, L.ptr(z), L.ptr(ca), L.ptr(cb),
                                            L.ptr(level), L.ptr(tstep), L.ptr(self.freq), L.ptr(self.arena.data),
                                            L.ptr(self.grad_arena), L.ptr(wsv), need, L.ptr(loss), C.c_float(grad_scale),

@@ -100,7 +100,7 @@ int sr3_plan_op_side(sr3_plan* plan, int batch, int index, int* side_id, int* wa
 double sr3_plan_forward_flops(sr3_plan* plan, int batch);
 /* tuning knobs: key in {"fuse_stats", "fuse_res", "tile_cfg", "ksplit", "keep_all", "split_bf16", "winograd",
  * "wino_split", "wino_split8", "wino2", "wino_ragged", "wino_up", "gemm_split", "gemm2", "gemm_s2", "gemm_n64", "fork_side", "gemm_wpre", "gemm_tile", "fold_fuse", "wgrad_split", "attn_split",
- * "attn_long", "train_geom", "loss_l2"};
+ * "attn_long", "train_geom", "loss_l2", "var_channels"};
  * returns previous value.
  * wino_split (default 1): the Winograd convolutions that run on the kernel's one-image tile (maps >= 16x16) use its 3 x bf16
  *   split instantiation: every fp32 operand as x = h + m + l (three bf16 terms, each residual exact in fp32), every product as
@@ -169,6 +169,13 @@ double sr3_plan_forward_flops(sr3_plan* plan, int batch);
  *   key-blocked kernel, backward on its key-blocked path with the dK / dV slabs -- no atomics) and is refused without it.  At
  *   image_size x image_size the launch list, the workspace and every bit of the result are those of train_geom = 0.  0: training is
  *   refused at any other geometry.  The default is 0 only because tests pin that refusal; nothing else speaks against 1.
+ * var_channels (default 0): learned reverse-process variance (Nichol & Dhariwal 2021).  0, or half of out_channel (SR3_E_BADARG otherwise):
+ *   the last var_channels filter rows of the output conv are the variance head v, the first out_channel - var_channels the prediction,
+ *   and x / z / eps of every step are [B, out_channel - var_channels, H, W].  sr3_unet_forward and every reverse-step entry launch the
+ *   output conv on the prediction rows alone (the first rows of the same filters: the bits of the network made of those rows), so every
+ *   sampler runs on such a checkpoint with its table sigma; sr3_unet_forward_full returns all rows (for sr3_learned_var_step), the
+ *   training forward always computes them (sr3_train_step_ex2).  A plan with out_channel 6 or 8 can be created without it but builds no
+ *   launch list: SR3_E_UNSUPPORTED "out_channel %d > 4 unsupported", as sr3_plan_create says for every other out_channel above 4.
  * loss_l2 (default 0): sr3_train_step uses nn.MSELoss(reduction='sum') instead of nn.L1Loss(reduction='sum')
  *   (GaussianDiffusion(loss_type='l2'), model/sr3_modules/diffusion.py:84-90).
  * split_bf16 (default 0, experimental; needs -DSR3_EXPERIMENTS, refused otherwise): run the halo-tile 3x3 convolutions of the inference plan on
@@ -234,6 +241,15 @@ int sr3_unet_forward(sr3_plan* plan, const float* x_nchw, const float* cond_nchw
                      const float* level_table, const int* step_dev, const float* params,
                      void* workspace, size_t workspace_bytes, float* eps_out_nchw, int batch,
                      void* stream);
+
+/* The same forward with every output row: eps_out_nchw is (B, out_channel, H, W), the prediction channels followed by the variance
+ * head of a plan under option var_channels (without the option: sr3_unet_forward's call).  t_map (with step_dev; DDPM variant): the
+ * timestep is t_map[*step_dev], as in sr3_reverse_step_ex; NULL: *step_dev. */
+int sr3_unet_forward_full(sr3_plan* plan, const float* x_nchw, const float* cond_nchw, int cond_channels,
+                          const float* noise_level, const int64_t* timestep, const float* freq,
+                          const float* level_table, const int* step_dev, const float* params,
+                          void* workspace, size_t workspace_bytes, float* eps_out_nchw, int batch,
+                          void* stream, const int* t_map);
 
 /* Same forward, run eagerly with a hipEvent pair around every launch of the plan (events are
  * recorded on `stream`).  Measurement aid for bench.py's roofline leg; not capturable.
@@ -538,6 +554,24 @@ int sr3_guided_step(float* x_nchw, const float* out_c, const float* out_u, float
                     const float* tab_sigma, const float* tab_c3, float* hist_nchw, int* step2_dev, int mode, int rank_lo, double frac,
                     float* x0_scratch, void* q_scratch, size_t q_scratch_bytes, float* thr_out_dev, void* stream);
 
+/* ---- learned reverse-process variance (engine extension; Nichol & Dhariwal 2021, "Improved DDPM") ------------------------
+ * The tail of an ancestral step whose sigma the network predicts.  out_nchw [batch, 2 * channels, height, width]: the prediction
+ * channels, then the raw variance channels v (sr3_unet_forward_full).  With j = step2_dev[1] on entry:
+ *   x0    = a[j] x - b[j] out_c ; clamp(-1, 1) if clip_denoised
+ *   mean  = c1[j] x0 + c2[j] x                                   (bit-identical to sr3_p_sample_step's mean)
+ *   f     = (v + 1) / 2 ; sigma = exp((f * tab_log_beta[j] + (1 - f) * tab_log_beta_tilde[j]) / 2), 0 where tab_sigma[j] == 0
+ *   x     = mean + sigma z                                       (z_nchw NULL: zeros)
+ * every product, sum and difference of the mean and of sigma z rounded separately; sigma itself is plain fp32.  step2_dev[1] = j - 1
+ * on completion (step2_dev[0] is scratch, as in sr3_tiled_step).  Two launches (the counter copy, the tail); height * width % 4 == 0
+ * and 16-byte aligned pointers take four values per thread, anything else one, the same bits.  Capturable.  The arguments are checked
+ * in this order and nothing is launched on a refusal: a NULL required pointer (SR3_E_BADARG, named); a non-positive size
+ * (SR3_E_BADARG); 2 * batch * channels * height * width >= 2^31 (SR3_E_UNSUPPORTED); tab_c3 or hist_nchw given (SR3_E_UNSUPPORTED: a
+ * multistep rule has no learned-variance form); x_nchw or step2_dev overlapping another argument (SR3_E_BADARG). */
+int sr3_learned_var_step(float* x_nchw, const float* out_nchw, const float* z_nchw, int batch, int channels, int height, int width,
+                         const float* tab_a, const float* tab_b, const float* tab_c1, const float* tab_c2, const float* tab_sigma,
+                         const float* tab_log_beta, const float* tab_log_beta_tilde, int* step2_dev, int clip_denoised,
+                         const float* tab_c3, float* hist_nchw, void* stream);
+
 /* ---- progressive distillation (engine extension; no reference counterpart) ------------------------
  * Salimans & Ho 2022: a frozen teacher takes two deterministic DDIM steps, the student learns to land on the same point in one.  The two
  * entries are the elementwise passes between the teacher's forwards (sr3_unet_forward) and the student's step (sr3_train_step_ex).
@@ -632,6 +666,38 @@ int sr3_loss_grad_f32(const float* z_nchw, const float* out_nchw, const float* h
                       const float* tgt_x0, const float* weight, int batch, int channels /* 1..4 */, int pixels,
                       int loss_kind, float huber_delta, float scale, float* g_nhwc4, float* loss_sum_out,
                       void* scratch /* sr3_loss_grad_scratch_bytes() */, void* stream);
+
+/* sr3_train_step_ex of a plan with a variance head (plan option var_channels; out_channel = 2 C): the hybrid loss
+ * L_simple + vlb_lambda * L_vlb of Nichol & Dhariwal 2021 in place of the pixel loss.  step_scalars: per image 8 floats on the device,
+ *   {a, b, c1, c2, log beta, log beta~, last, 0}:  x0^ = a x_t - b out_c (not clamped) ; mu_theta = c1 x0^ + c2 x_t, a constant -- no
+ *   L_vlb gradient reaches the prediction rows ; mu_q = c1 hr + c2 x_t ; log sigma_theta^2 = f log beta + (1 - f) log beta~ with
+ *   f = (v + 1) / 2 ; last != 0 marks the walk's last step.  Per element, in bits:
+ *     not last:  KL(N(mu_q, beta~) || N(mu_theta, sigma_theta^2)) / ln 2
+ *     last:      -log2 of the mass of N(mu_theta, sigma_theta^2) on the bin hr +- 1/255 (open below -0.999 and above 0.999), with
+ *                Phi(u) = (1 + tanh(sqrt(2 / pi) (u + 0.044715 u^3))) / 2 and logs of max(., 1e-12)
+ *   *loss_sum_out = sum weight[b] rho(d) + vlb_lambda * sum vlb  (so one grad_scale = 1 / (b c h w) makes both terms means) ;
+ *   *vlb_sum_out (may be NULL) = sum vlb.  The prediction rows' loss and gradient are sr3_train_step_ex's, term for term; the variance
+ *   rows receive vlb_lambda * grad_scale * d vlb / d v in closed form.  Fixed-order two-stage sums in double: the same bits every run.
+ * SR3_E_BADARG besides sr3_train_step_ex's: step_scalars NULL, a plan without var_channels (and sr3_train_step / _ex on a plan with
+ * it), vlb_lambda negative or not finite. */
+int sr3_train_step_ex2(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels,
+                       const float* z_nchw, const float* q_ca, const float* q_cb, const float* noise_level,
+                       const int64_t* timestep, const float* freq, const float* params, float* grads,
+                       void* workspace, size_t workspace_bytes, float* loss_sum_out, float grad_scale, float dropout_p,
+                       unsigned dropout_seed, int n_marks, const size_t* mark_offsets, void* const* mark_events,
+                       int batch, const float* tgt_z, const float* tgt_x0, const float* weight, int loss_kind,
+                       float huber_delta, const float* step_scalars, float vlb_lambda, float* vlb_sum_out, void* stream);
+
+/* The loss kernel of sr3_train_step_ex2 alone: out_nchw is [batch][2 * channels][pixels], z / hr / xt [batch][channels][pixels],
+ * channels 1..4; g_nhwc8 [batch][pixels][8]: lanes 0 .. channels - 1 as sr3_loss_grad_f32's (bit-identical), lanes channels ..
+ * 2 * channels - 1 = vlb_lambda * scale * d vlb / d v, the rest 0.  scratch: sr3_hybrid_loss_grad_scratch_bytes() bytes, 8-byte
+ * aligned.  Refusals as sr3_loss_grad_f32's, and for a NULL hr / xt / step_scalars or a vlb_lambda that is negative or not finite. */
+size_t sr3_hybrid_loss_grad_scratch_bytes(void);
+int sr3_hybrid_loss_grad_f32(const float* z_nchw, const float* out_nchw, const float* hr_nchw, const float* xt_nchw,
+                             const float* tgt_z, const float* tgt_x0, const float* weight, const float* step_scalars,
+                             float vlb_lambda, int batch, int channels /* 1..4 */, int pixels, int loss_kind, float huber_delta,
+                             float scale, float* g_nhwc8, float* loss_sum_out, float* vlb_sum_out,
+                             void* scratch /* sr3_hybrid_loss_grad_scratch_bytes() */, void* stream);
 
 /* torch.optim.Adam step (model/model.py:39-40,55; defaults beta 0.9/0.999, eps 1e-8, no weight decay)
  * fused over the whole arena; `step` is the 1-based step count for the bias corrections.
