@@ -198,6 +198,12 @@ int sr3_groupnorm_fold_f32(const double* stat0, int C0, int T0, const double* st
   return gn_finalize(stat0, C0, T0, stat1, stat1 ? C1 : 0, stat1 ? T1 : 0, B, HW, groups, gamma, beta, eps, ss,
                      static_cast<hipStream_t>(stream));
 }
+int sr3_groupnorm_fold_mr_f32(const double* stat0, int C0, int T0, const double* stat1, int C1, int T1, int B, int HW,
+                              int groups, const float* gamma, const float* beta, float eps, float* ss, float* mr, void* stream) {
+  if (!stat0 || !gamma || !beta || !ss || !mr) { set_error("null argument"); return SR3_E_BADARG; }
+  return gn_finalize(stat0, C0, T0, stat1, stat1 ? C1 : 0, stat1 ? T1 : 0, B, HW, groups, gamma, beta, eps, ss,
+                     static_cast<hipStream_t>(stream), mr);
+}
 int sr3_attention_f32(const float* qkv, int B, int N, int C, float* out, void* stream) {
   if (!qkv || !out) { set_error("null argument"); return SR3_E_BADARG; }
   return attention_forward(qkv, B, N, C, out, static_cast<hipStream_t>(stream));

@@ -6,6 +6,8 @@ namespace sr3 {
 
 // grid of an element-wise pass over n items: 256 threads a block, at most 8192 blocks (grid-stride loops)
 inline int ew_blocks(size_t n) { size_t b = (n + 255) / 256; return (int)(b > 8192 ? 8192 : (b ? b : 1)); }
+// the regions a per-op entry cuts its caller's scratch into start on 256-byte boundaries, as the regions of the step's workspace do
+inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // GroupNorm(+SiLU) backward over the virtual concat (x0|x1): dA (grad w.r.t. the activated input) is
 // overwritten with du, partial sums go to `part`, group sums to gs[B][G][2], parameter gradients to

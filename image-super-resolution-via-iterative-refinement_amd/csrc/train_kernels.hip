@@ -644,6 +644,79 @@ int nchw_to_nhwc_pad(const float* a, int Ca, const float* b, int Cb, int B, int 
 
 }  // namespace sr3
 
+// ---- the backward walk's own kernels on caller-owned tensors: each entry checks its arguments, then calls what run_train calls ----
+namespace {
+int check_gn_bwd_shape(const char* who, int C0, int C1, int B, int HW, int groups) {
+  using namespace sr3;
+  if (B <= 0 || HW <= 0 || C0 <= 0 || C1 < 0 || groups <= 0) { set_error("%s: batch %d, pixels %d, channels %d | %d and groups %d must be positive (C1 >= 0)", who, B, HW, C0, C1, groups); return SR3_E_BADARG; }
+  if ((C0 & 3) || (C1 & 3)) { set_error("%s: channel counts must be multiples of 4 (C0 %d, C1 %d)", who, C0, C1); return SR3_E_UNSUPPORTED; }
+  if ((C0 + C1) % groups) { set_error("%s: %d channels do not divide into %d groups", who, C0 + C1, groups); return SR3_E_UNSUPPORTED; }
+  if ((double)B * HW * (double)(C0 + C1) >= 2147483647.0) { set_error("%s: tensor exceeds 2^31 elements", who); return SR3_E_UNSUPPORTED; }
+  return SR3_OK;
+}
+}  // namespace
+
+extern "C" size_t sr3_groupnorm_act_bwd_scratch_bytes(int B, int HW, int C, int groups) {
+  using namespace sr3;
+  if (check_gn_bwd_shape("sr3_groupnorm_act_bwd_scratch_bytes", C, 0, B, HW, groups)) return 0;
+  return al256(act_bwd_part_bytes(B, HW, C)) + (size_t)B * groups * 2 * sizeof(double);
+}
+extern "C" int sr3_groupnorm_act_bwd_f32(float* dA, const float* x0, int C0, const float* x1, int C1, int B, int HW, const float* ss,
+                                         const float* mr, int groups, int act, const float* gamma, unsigned drop_seed, float drop_p,
+                                         float* dgamma, float* dbeta, float* dx0, int acc0, float* dx1, int acc1, float* aout,
+                                         void* scratch, size_t scratch_bytes, void* stream) {
+  using namespace sr3;
+  const char* who = "sr3_groupnorm_act_bwd_f32";
+  if (!dA || !x0 || !ss || !mr || !gamma || !dgamma || !dbeta || !dx0 || !scratch || (C1 > 0 && (!x1 || !dx1))) {
+    set_error("%s: dA / x0 / ss / mr / gamma / dgamma / dbeta / dx0 / scratch (or x1 / dx1 with C1 > 0) is NULL", who);
+    return SR3_E_BADARG;
+  }
+  if (const int rc = check_gn_bwd_shape(who, C0, C1, B, HW, groups)) return rc;
+  if (act != 1 && act != 2) { set_error("%s: act %d is outside 1..2", who, act); return SR3_E_BADARG; }
+  if (!(drop_p >= 0.f && drop_p < 1.f)) { set_error("%s: drop_p out of range", who); return SR3_E_BADARG; }
+  if ((uintptr_t)scratch & 7) { set_error("%s: scratch is not 8-byte aligned", who); return SR3_E_ALIGN; }
+  const size_t part = al256(act_bwd_part_bytes(B, HW, C0 + C1)), need = part + (size_t)B * groups * 2 * sizeof(double);
+  if (scratch_bytes < need) { set_error("%s: scratch too small (%zu < %zu)", who, scratch_bytes, need); return SR3_E_NOMEM; }
+  unsigned thresh;
+  float scale;
+  dropout_consts(drop_p, &thresh, &scale);       // the step's mapping p -> (threshold, scale)
+  char* s = static_cast<char*>(scratch);
+  return act_bwd(dA, x0, x1, C0, C1, B, HW, ss, mr, groups, act, gamma, reinterpret_cast<double*>(s), reinterpret_cast<double*>(s + part),
+                 dgamma, dbeta, dx0, dx1, static_cast<hipStream_t>(stream), drop_seed, thresh, scale, aout, acc0 != 0, acc1 != 0);
+}
+
+extern "C" int sr3_grad_route_f32(const float* g, int C0, int C1, int B, int Hs, int Ws, int ups, float* d0, int acc0, float* d1, int acc1,
+                                  void* stream) {
+  using namespace sr3;
+  const char* who = "sr3_grad_route_f32";
+  if (!g || !d0 || (C1 > 0 && !d1)) { set_error("%s: g / d0 (or d1 with C1 > 0) is NULL", who); return SR3_E_BADARG; }
+  if (B <= 0 || Hs <= 0 || Ws <= 0 || C0 <= 0 || C1 < 0) { set_error("%s: batch %d, map %d x %d and channels %d | %d must be positive (C1 >= 0)", who, B, Hs, Ws, C0, C1); return SR3_E_BADARG; }
+  if (ups != 0 && ups != 1) { set_error("%s: ups %d is outside 0..1", who, ups); return SR3_E_BADARG; }
+  if ((C0 & 3) || (C1 & 3)) { set_error("%s: channel counts must be multiples of 4 (C0 %d, C1 %d)", who, C0, C1); return SR3_E_UNSUPPORTED; }
+  if ((double)B * (Hs << ups) * (Ws << ups) * (double)(C0 + C1) >= 2147483647.0) { set_error("%s: tensor exceeds 2^31 elements", who); return SR3_E_UNSUPPORTED; }
+  return grad_route(g, C0, C1, B, Hs, Ws, ups, d0, d1, static_cast<hipStream_t>(stream), acc0 != 0, acc1 != 0);
+}
+
+extern "C" size_t sr3_colsums_scratch_bytes(int B, int HW, int C) {
+  using namespace sr3;
+  if (B <= 0 || HW <= 0 || C <= 0 || (C & 3)) return 0;
+  return (size_t)B * chan_stats_slices(B, HW, C) * C * 2 * sizeof(double);
+}
+extern "C" int sr3_colsums_f32(const float* g, int B, int HW, int C, float* dbias, float* dfilm, int film_stride, void* scratch,
+                               size_t scratch_bytes, void* stream) {
+  using namespace sr3;
+  const char* who = "sr3_colsums_f32";
+  if (!g || !scratch || (!dbias && !dfilm)) { set_error("%s: g / scratch is NULL, or both of dbias / dfilm are", who); return SR3_E_BADARG; }
+  if (B <= 0 || HW <= 0 || C <= 0) { set_error("%s: batch %d, pixels %d and channels %d must be positive", who, B, HW, C); return SR3_E_BADARG; }
+  if (C & 3) { set_error("%s: channel count must be a multiple of 4 (C %d)", who, C); return SR3_E_UNSUPPORTED; }
+  if (dfilm && film_stride < C) { set_error("%s: film_stride %d is below the channel count %d", who, film_stride, C); return SR3_E_BADARG; }
+  if ((double)B * HW * (double)C >= 2147483647.0) { set_error("%s: tensor exceeds 2^31 elements", who); return SR3_E_UNSUPPORTED; }
+  if ((uintptr_t)scratch & 7) { set_error("%s: scratch is not 8-byte aligned", who); return SR3_E_ALIGN; }
+  const size_t need = sr3_colsums_scratch_bytes(B, HW, C);
+  if (scratch_bytes < need) { set_error("%s: scratch too small (%zu < %zu)", who, scratch_bytes, need); return SR3_E_NOMEM; }
+  return colsums(g, B, HW, C, static_cast<double*>(scratch), dbias, dfilm, film_stride, static_cast<hipStream_t>(stream));
+}
+
 extern "C" size_t sr3_loss_grad_scratch_bytes(void) { return sr3::LOSS_GRAD_BLOCKS * sizeof(double); }
 extern "C" int sr3_loss_grad_f32(const float* z_nchw, const float* out_nchw, const float* hr_nchw, const float* tgt_z, const float* tgt_x0,
                                  const float* weight, int batch, int channels, int pixels, int loss_kind, float huber_delta, float scale,

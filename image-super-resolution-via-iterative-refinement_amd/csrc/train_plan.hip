@@ -266,6 +266,14 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
 }
 
 namespace {
+// the buffers of one data-gradient conv: run_train binds the regions of its workspace, sr3_conv_dgrad_f32 the caller's scratch
+struct DgradBufs {
+  float* wt;            // the flipped-transposed filters [Cin][taps][Cg]
+  float* wu;            // the derived filters of Dgrad::wu (not read with WU_NONE)
+  float* z;             // the zero-inserted dOut of a stride-2 conv [B, 2 Ho, 2 Wo, Cg] (not read at stride 1)
+  float* slabs;         // split-K slabs
+  size_t slab_bytes;
+};
 struct TrainCtx {
   sr3_plan* P;
   char* ws;
@@ -276,21 +284,30 @@ struct TrainCtx {
   const float* act(int h) const { return reinterpret_cast<const float*>(ws + P->ttens[h].off); }
   float* grad(int h) const { return h >= 0 ? reinterpret_cast<float*>(ws + P->t_act_bytes + P->ttens[h].off) : nullptr; }
   template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(ws + off); }
+  DgradBufs dgrad_bufs() const {
+    return DgradBufs{at<float>(P->t_wt_off), at<float>(P->t_wu_off), at<float>(P->t_z_off), at<float>(P->t_regions.scratch_off),
+                     P->t_regions.scratch_bytes};
+  }
 };
 
-// dOut [B,H,W,Cg] --(conv with flipped-transposed weights)--> dA [B,H,W,Cin], on the kernel build_train chose; the arena holds
-// `Cout_w` <= Cg of the Cg filters (the output conv's padding)
-int dgrad_conv(const TrainCtx& X, const Dgrad& d, const float* g, const float* w, int Cout_w, float* dA) {
+// dOut [B,H,W,Cg] --(conv with flipped-transposed weights)--> dA [B,H,W,Cin], on the kernel choose_dgrad chose; the arena holds
+// `Cout_w` <= Cg of the Cg filters (the output conv's padding).  stride 2: dOut is [B,Ho,Wo,Cg] and is zero-inserted first
+int dgrad_conv(const Dgrad& d, int stride, int Ho, int Wo, const float* g, const float* w, int Cout_w, float* dA, const DgradBufs& b,
+               hipStream_t st) {
   ConvParams c = d.c;
-  float* wt = X.at<float>(X.P->t_wt_off);
-  float* wu = X.at<float>(X.P->t_wu_off);
-  int rc = w_flip_transpose(w, Cout_w, c.ksize * c.ksize, c.Cout, c.C0, wt, X.st);
+  int rc;
+  if (stride == 2) {
+    rc = zero_insert(g, c.B, Ho, Wo, c.C0, b.z, st);
+    if (rc) return rc;
+    g = b.z;
+  }
+  rc = w_flip_transpose(w, Cout_w, c.ksize * c.ksize, c.Cout, c.C0, b.wt, st);
   if (rc) return rc;
-  c.src0 = g; c.w = wt; c.out = dA;
-  if (d.wu == WU_GEMM) { rc = igemm_split_weights(wt, c.Cout, 1, c.C0, wu, X.st); c.w_split = wu; }
-  else if (d.wu != WU_NONE) { rc = wino_transform_weights(wt, c.Cout, c.C0, wu, X.st, d.wu == WU_WINO_SPLIT); c.wino_u = wu; }
+  c.src0 = g; c.w = b.wt; c.out = dA;
+  if (d.wu == WU_GEMM) { rc = igemm_split_weights(b.wt, c.Cout, 1, c.C0, b.wu, st); c.w_split = b.wu; }
+  else if (d.wu != WU_NONE) { rc = wino_transform_weights(b.wt, c.Cout, c.C0, b.wu, st, d.wu == WU_WINO_SPLIT); c.wino_u = b.wu; }
   if (rc) return rc;
-  return conv_forward(c, d.tile, d.ksplit, X.at<float>(X.P->t_regions.scratch_off), X.P->t_regions.scratch_bytes, X.st);
+  return conv_forward(c, d.tile, d.ksplit, b.slabs, b.slab_bytes, st);
 }
 
 // weight gradient of the shape `c` over the sources src0 | src1.  wgrad_split is a no-rebuild option (the slabs are sized for both
@@ -364,7 +381,7 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
       // bias (3 of the 4 padded columns are real -- 6 of 8 with a variance head; arena slots are 4-float aligned)
       rc = colsums(geps, B, S2, OUT_PAD, part, grads + s.bias, nullptr, 0, st);
       if (rc) return rc;
-      rc = dgrad_conv(X, r.dx, geps, params + s.w, P->out_ch, dA);
+      rc = dgrad_conv(r.dx, 1, r.dw.Ho, r.dw.Wo, geps, params + s.w, P->out_ch, dA, X.dgrad_bufs(), st);
       if (rc) return rc;
       rc = act_bwd(dA, X.act(s.x0), nullptr, C, 0, B, S2, X.at<float>(P->t_regions.ss_off + r.ss_off),
                    X.at<float>(P->t_regions.mr_off + r.mr_off), G, s.act, params + r.gamma, part, gs, grads + r.gamma,
@@ -421,7 +438,7 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
       // 3. fused res_conv segment
       if (has_q) {
         float* dq = X.at<float>(P->t_dq_off);
-        rc = dgrad_conv(X, r.dq, g, params + s.qw, Cout, dq);
+        rc = dgrad_conv(r.dq, 1, Ho, Wo, g, params + s.qw, Cout, dq, X.dgrad_bufs(), st);
         if (rc) return rc;
         rc = grad_route(dq, r.dqw.C0, r.dqw.C1, B, Ho, Wo, 0, X.grad(s.q0), X.grad(s.q1), st, r.acc_q0, r.acc_q1);
         if (rc) return rc;
@@ -429,14 +446,7 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
         if (rc) return rc;
       }
       // 4. main segment: data gradient
-      const float* gsrc = g;
-      if (s.stride == 2) {
-        float* zb = X.at<float>(P->t_z_off);
-        rc = zero_insert(g, B, Ho, Wo, Cout, zb, st);
-        if (rc) return rc;
-        gsrc = zb;
-      }
-      rc = dgrad_conv(X, r.dx, gsrc, params + s.w, Cout, dA);
+      rc = dgrad_conv(r.dx, s.stride, Ho, Wo, g, params + s.w, Cout, dA, X.dgrad_bufs(), st);
       if (rc) return rc;
       if (s.act) {
         const bool dropped = s.drop_key >= 0 && dc.thresh != 0;
@@ -476,9 +486,88 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
   return SR3_OK;
 }
 
+// ---- the data gradient of one conv on caller-owned tensors (sr3_conv_dgrad_f32): run_train's choose_dgrad and dgrad_conv ----
+namespace {
+// the argument checks of the two entries and the shape of the forward conv; nothing is launched
+int dgrad_entry_shape(const char* who, const sr3_plan* plan, int B, int Hs, int Ws, int ups, int stride, int ksize, int Cin, int CoutP,
+                      ConvParams* f) {
+  if (!plan) { set_error("%s: plan is NULL", who); return SR3_E_BADARG; }
+  if (B <= 0 || Hs <= 0 || Ws <= 0 || Cin <= 0 || CoutP <= 0) { set_error("%s: batch %d, map %d x %d and channels %d -> %d must be positive", who, B, Hs, Ws, Cin, CoutP); return SR3_E_BADARG; }
+  if ((ups != 0 && ups != 1) || (stride != 1 && stride != 2) || (ksize != 1 && ksize != 3)) {
+    set_error("%s: ups %d / stride %d / ksize %d out of range (ups 0 | 1, stride 1 | 2, ksize 1 | 3)", who, ups, stride, ksize);
+    return SR3_E_BADARG;
+  }
+  if (ups && stride == 2) { set_error("%s: an upsampled stride-2 conv is unsupported", who); return SR3_E_UNSUPPORTED; }
+  if ((Cin & 3) || (CoutP & 3)) { set_error("%s: channel counts must be multiples of 4 (Cin %d, CoutP %d)", who, Cin, CoutP); return SR3_E_UNSUPPORTED; }
+  // dgrad_shape takes the data gradient's map to be the forward input's, zero_insert writes [2 Ho, 2 Wo]: they agree on even maps only
+  if (stride == 2 && ((Hs & 1) || (Ws & 1))) { set_error("%s: a stride-2 conv needs an even input map (%d x %d)", who, Hs, Ws); return SR3_E_UNSUPPORTED; }
+  if ((double)B * (Hs << ups) * (Ws << ups) * (double)(Cin > CoutP ? Cin : CoutP) >= 2147483647.0) { set_error("%s: tensor exceeds 2^31 elements", who); return SR3_E_UNSUPPORTED; }
+  *f = conv_shape(B, Hs, Ws, ups, stride, ksize, Cin, 0, CoutP);
+  return SR3_OK;
+}
+// THE layout of the entry's scratch: [wt | z | slabs], byte offsets; `slabs` is also the bytes in front of the split-K slabs
+struct DgradScratch {
+  size_t z, slabs;
+  explicit DgradScratch(const ConvParams& f) {
+    z = al256((size_t)f.Cout * f.ksize * f.ksize * f.C0 * sizeof(float));
+    slabs = z + al256(f.stride == 2 ? (size_t)f.B * f.Hs * f.Ws * f.Cout * sizeof(float) : 0);
+  }
+  DgradBufs bind(void* scratch, size_t scratch_bytes, void* derived) const {
+    char* s = static_cast<char*>(scratch);
+    return DgradBufs{reinterpret_cast<float*>(s), static_cast<float*>(derived), reinterpret_cast<float*>(s + z),
+                     reinterpret_cast<float*>(s + slabs), scratch_bytes - slabs};
+  }
+};
+}  // namespace
+
 }  // namespace sr3
 
 extern "C" {
+
+size_t sr3_conv_dgrad_scratch_bytes(sr3_plan* plan, int B, int Hs, int Ws, int ups, int stride, int ksize, int Cin, int CoutP,
+                                    size_t* derived_bytes, size_t* base_bytes) {
+  if (derived_bytes) *derived_bytes = 0;
+  if (base_bytes) *base_bytes = 0;
+  ConvParams f;
+  if (dgrad_entry_shape("sr3_conv_dgrad_scratch_bytes", plan, B, Hs, Ws, ups, stride, ksize, Cin, CoutP, &f)) return 0;
+  Dgrad d;
+  d.c = dgrad_shape(f);
+  choose_dgrad(plan, d, ~(size_t)0, ~(size_t)0);       // the kernel it runs with room for everything ...
+  size_t slabs = conv_splitk_bytes(d.c, d.tile, d.ksplit);
+  if (derived_bytes) *derived_bytes = wu_bytes(d);
+  choose_dgrad(plan, d, 0, 0);                         // ... and the general one it falls back to without
+  slabs = std::max(slabs, conv_splitk_bytes(d.c, d.tile, d.ksplit));
+  const DgradScratch lay(f);
+  if (base_bytes) *base_bytes = lay.slabs;
+  return lay.slabs + al256(slabs);
+}
+
+int sr3_conv_dgrad_f32(sr3_plan* plan, const float* dy, const float* w_ohwi, int Cout_w, int CoutP, int B, int Hs, int Ws, int ups,
+                       int stride, int ksize, int Cin, float* dA, void* scratch, size_t scratch_bytes, void* derived,
+                       size_t derived_bytes, int* tile_out, int* ksplit_out, int* derived_kind_out, void* stream) {
+  const char* who = "sr3_conv_dgrad_f32";
+  ConvParams f;
+  if (const int rc = dgrad_entry_shape(who, plan, B, Hs, Ws, ups, stride, ksize, Cin, CoutP, &f)) return rc;
+  if (!dy || !w_ohwi || !dA || !scratch) { set_error("%s: dy / w_ohwi / dA / scratch is NULL", who); return SR3_E_BADARG; }
+  if (Cout_w <= 0 || Cout_w > CoutP) { set_error("%s: Cout_w %d is outside 1..CoutP (%d)", who, Cout_w, CoutP); return SR3_E_BADARG; }
+  if (((uintptr_t)scratch & 255) || ((uintptr_t)derived & 255)) { set_error("%s: scratch / derived is not 256-byte aligned", who); return SR3_E_ALIGN; }
+  const DgradScratch lay(f);
+  if (scratch_bytes < lay.slabs) { set_error("%s: scratch too small (%zu < %zu)", who, scratch_bytes, lay.slabs); return SR3_E_NOMEM; }
+  const DgradBufs bufs = lay.bind(scratch, scratch_bytes, derived);
+  Dgrad d;
+  d.c = dgrad_shape(f);
+  // choose_dgrad's caps are what the caller passed: derived filters that do not fit -- or split-K slabs of the GEMM kernel that do
+  // not -- send the conv to the general kernels, whose own slabs must fit
+  choose_dgrad(plan, d, derived ? derived_bytes : 0, bufs.slab_bytes);
+  const size_t slabs = conv_splitk_bytes(d.c, d.tile, d.ksplit);
+  if (bufs.slab_bytes < slabs) { set_error("%s: scratch too small (%zu < %zu)", who, scratch_bytes, lay.slabs + slabs); return SR3_E_NOMEM; }
+  int tile = d.tile, ks = d.ksplit;
+  conv_pick(d.c, tile, ks);                            // (what conv_forward resolves tile 0 / ksplit 0 to)
+  if (tile_out) *tile_out = tile_encode(tile, d.c.wino_split, d.c.igemm_split, false);
+  if (ksplit_out) *ksplit_out = ks;
+  if (derived_kind_out) *derived_kind_out = d.wu;
+  return dgrad_conv(d, stride, f.Ho, f.Wo, dy, w_ohwi, Cout_w, dA, bufs, static_cast<hipStream_t>(stream));
+}
 
 size_t sr3_train_workspace_bytes(sr3_plan* plan, int batch, int cond_channels) {
   if (!plan) return 0;

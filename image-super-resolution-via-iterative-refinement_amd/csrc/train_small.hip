@@ -2,6 +2,8 @@
 // (PositionalEncoding -> Linear -> Swish -> Linear, FeatureWiseAffine / mlp Linear;
 // sr3 unet.py:18-50,179-184, ddpm unet.py:19-34,81-84,165-170).  Tiny tensors (F = 8384 rows of 64):
 // latency-bound, written for clarity.  Summation over the batch is in a fixed order.
+#include <string.h>
+
 #include "sr3_common.h"
 #include "train.h"
 
@@ -161,3 +163,33 @@ int embed_backward(const EmbedBwdParams& p, hipStream_t st) {
 }
 
 }  // namespace sr3
+
+// embed_backward on caller-owned tensors: the scratch is the step's B * 29 * inner floats
+extern "C" size_t sr3_embed_bwd_scratch_bytes(int B, int inner) {
+  if (B <= 0 || inner <= 0) return 0;
+  return (size_t)B * 29 * inner * sizeof(float);
+}
+extern "C" int sr3_embed_bwd_f32(int variant, int B, int inner, int F, const float* level, const int64_t* timestep, const float* freq,
+                                 const float* w1, const float* b1, const float* w2, const float* b2, const float* wf, const float* dfilm,
+                                 float* dw1, float* db1, float* dw2, float* db2, float* dwf, float* dbf, void* scratch,
+                                 size_t scratch_bytes, void* stream) {
+  using namespace sr3;
+  const char* who = "sr3_embed_bwd_f32";
+  if (!freq || !w1 || !b1 || !w2 || !b2 || !wf || !dfilm || !dw1 || !db1 || !dw2 || !db2 || !dwf || !dbf || !scratch) {
+    set_error("%s: freq / w1 / b1 / w2 / b2 / wf / dfilm / dw1 / db1 / dw2 / db2 / dwf / dbf / scratch is NULL", who);
+    return SR3_E_BADARG;
+  }
+  if (variant != SR3_VARIANT_SR3 && variant != SR3_VARIANT_DDPM) { set_error("%s: variant %d is outside 0..1", who, variant); return SR3_E_BADARG; }
+  if (variant == SR3_VARIANT_SR3 ? !level : !timestep) { set_error("%s: the %s is NULL", who, variant == SR3_VARIANT_SR3 ? "noise level" : "timestep"); return SR3_E_BADARG; }
+  if (B <= 0 || inner < 2 || F <= 0) { set_error("%s: batch %d, inner %d (>= 2) and F %d must be positive", who, B, inner, F); return SR3_E_BADARG; }
+  if ((uintptr_t)scratch & 3) { set_error("%s: scratch is not 4-byte aligned", who); return SR3_E_ALIGN; }
+  const size_t need = sr3_embed_bwd_scratch_bytes(B, inner);
+  if (scratch_bytes < need) { set_error("%s: scratch too small (%zu < %zu)", who, scratch_bytes, need); return SR3_E_NOMEM; }
+  EmbedBwdParams e;
+  memset(&e, 0, sizeof(e));
+  e.variant = variant; e.B = B; e.inner = inner; e.F = F; e.level = level; e.tstep = timestep; e.freq = freq;
+  e.w1 = w1; e.b1 = b1; e.w2 = w2; e.b2 = b2; e.wf = wf; e.dfilm = dfilm;
+  e.dw1 = dw1; e.db1 = db1; e.dw2 = dw2; e.db2 = db2; e.dwf = dwf; e.dbf = dbf;
+  e.scratch = static_cast<float*>(scratch);
+  return embed_backward(e, static_cast<hipStream_t>(stream));
+}

@@ -140,6 +140,17 @@ SIGNATURES = {
     'sr3_groupnorm_stats_slices': (_I, [_I, _I, _I]),
     'sr3_conv_stats_slices': (_I, [_I, _I, _I, _I, _I, _I, _I, _I]),
     'sr3_groupnorm_fold_f32': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, C.c_float, _P, _P]),
+    'sr3_groupnorm_fold_mr_f32': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, C.c_float, _P, _P, _P]),
+    'sr3_groupnorm_act_bwd_scratch_bytes': (_Z, [_I, _I, _I, _I]),
+    'sr3_groupnorm_act_bwd_f32': (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _I, _I, _P, C.c_uint, C.c_float, _P, _P, _P, _I, _P, _I, _P,
+                                       _P, _Z, _P]),
+    'sr3_conv_dgrad_scratch_bytes': (_Z, [_P, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),
+    'sr3_conv_dgrad_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _Z, _P, _Z, _PI, _PI, _PI, _P]),
+    'sr3_grad_route_f32': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P]),
+    'sr3_colsums_scratch_bytes': (_Z, [_I, _I, _I]),
+    'sr3_colsums_f32': (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _Z, _P]),
+    'sr3_embed_bwd_scratch_bytes': (_Z, [_I, _I]),
+    'sr3_embed_bwd_f32': (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'sr3_attention_f32': (_I, [_P, _I, _I, _I, _P, _P]),
     'sr3_attention_ex_f32': (_I, [_P, _I, _I, _I, _P, _I, _P]),
     'sr3_film_embed_f32': (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),

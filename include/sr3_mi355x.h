@@ -853,6 +853,75 @@ size_t sr3_conv_wgrad_scratch_bytes(int B, int Hs, int Ws, int ups, int stride, 
 int sr3_conv_wgrad_f32(const float* src0, int C0, const float* src1, int C1, int B, int Hs, int Ws, int ups, int stride, int ksize,
                        int Cout, const float* ss, int act, const float* dy, float* dw_ohwi, int split, void* scratch,
                        size_t scratch_bytes, void* stream);
+/* sr3_groupnorm_fold_f32 that also keeps mr[B][groups][2] = (mean, rstd) per (image, group): what the training forward keeps
+ * for the GroupNorm backward below. */
+int sr3_groupnorm_fold_mr_f32(const double* stat0, int C0, int T0, const double* stat1, int C1, int T1, int B, int HW,
+                              int groups, const float* gamma, const float* beta, float eps, float* ss, float* mr, void* stream);
+
+/* ---- the training backward's own kernels, per op (autograd of `l_pix.backward()`, model/model.py:50-54): each entry runs the
+ * functions sr3_train_step's backward walk runs, on caller-owned tensors.  Every entry checks its arguments on the host and launches
+ * nothing on a refusal: SR3_E_BADARG for a NULL required pointer (the second source's with C1 > 0 too), a non-positive size or an
+ * argument out of its range, SR3_E_UNSUPPORTED for a well-formed problem the kernels do not take -- a channel count that is no multiple
+ * of 4, channels % groups != 0, a tensor of 2^31 elements, an odd map under a stride-2 conv, an upsampled stride-2 conv --,
+ * SR3_E_NOMEM for a scratch that is too small, SR3_E_ALIGN for a misaligned scratch.  Fixed-order sums, no atomics: the same bits
+ * every run. */
+
+/* Backward of GroupNorm (+ SiLU with act 2; act 1: the affine alone) (+ dropout) in front of a conv (Block, unet.py:80-91), over the
+ * virtual concat x = (x0 | x1), NHWC [B][HW][C0 | C1].  dA [B][HW][C0 + C1], the gradient w.r.t. the activated (and dropped) input,
+ * is REWRITTEN IN PLACE with du, the gradient w.r.t. u = x * scale + shift.  ss [B][C][2] and mr [B][groups][2] are the forward's
+ * tables (sr3_groupnorm_fold_mr_f32).  drop_seed is the layer's seed and drop_p the probability, mapped to (threshold, scale) as by
+ * sr3_dropout_threshold; the mask is sr3_conv_dropout_f32's, over the NHWC index of the concat.  Outputs: dgamma, dbeta [C]
+ * (overwritten); dx0 / dx1 (C1 0: one source, x1 and dx1 are not read), accumulated into where acc0 / acc1 != 0, plain stores otherwise; aout (may be NULL)
+ * [B][HW][C] = dropout(act(u)), the conv's input as the weight gradient reads it.  scratch: 8-byte aligned,
+ * sr3_groupnorm_act_bwd_scratch_bytes(B, HW, C0 + C1, groups) bytes (0 for a shape the entry refuses). */
+size_t sr3_groupnorm_act_bwd_scratch_bytes(int B, int HW, int C, int groups);
+int sr3_groupnorm_act_bwd_f32(float* dA, const float* x0, int C0, const float* x1, int C1, int B, int HW, const float* ss,
+                              const float* mr, int groups, int act, const float* gamma, unsigned drop_seed, float drop_p,
+                              float* dgamma, float* dbeta, float* dx0, int acc0, float* dx1, int acc1, float* aout,
+                              void* scratch, size_t scratch_bytes, void* stream);
+
+/* Data gradient of one convolution, the "main segment" of the backward walk: dy [B, Ho, Wo, CoutP] (the forward conv's output
+ * gradient; Ho x Wo from Hs, Ws, ups, stride, ksize as in sr3_conv_f32) -> dA [B, Hs << ups, Ws << ups, Cin], the gradient w.r.t.
+ * the conv's (upsampled) input, before it is routed to the sources.  w_ohwi [Cout_w][ksize^2][Cin] holds Cout_w <= CoutP filters:
+ * the filters are flipped and transposed with the missing rows zero (the output conv's 3 -> 4 / 6 -> 8 padding; the lanes of dy
+ * beyond Cout_w then contribute exactly 0 whatever finite value they hold), dy is zero-inserted for stride 2 (even Hs, Ws only:
+ * SR3_E_UNSUPPORTED otherwise), and the same conv kernels run on the result.  `plan` gives the options and the geometry state the
+ * step's choice reads (winograd, wino_split, wino2, wino_ragged, gemm_split, gemm2, gemm_n64, train_geom and whether the plan's
+ * geometry is the native one); nothing else of the plan is touched.  scratch: 256-byte aligned, sr3_conv_dgrad_scratch_bytes bytes;
+ * derived: 256-byte aligned room for the derived filters of the chosen kernel (*derived_bytes of the query; may be NULL / 0; *base_bytes of the
+ * query, may be NULL: the bytes of the scratch in front of its split-K slabs -- a scratch of exactly that size has room for no slab).  As in
+ * the step, derived filters that do not fit send the conv to the general kernels; a scratch below what the kernel then needs is
+ * refused.  *tile_out: the tile_cfg number of sr3_conv_f32 the conv ran on, *ksplit_out its split-K factor, *derived_kind_out 0 none,
+ * 1 Winograd fp32, 2 Winograd 3 x bf16 split, 3 the pre-split 1x1 weights (each may be NULL). */
+size_t sr3_conv_dgrad_scratch_bytes(sr3_plan* plan, int B, int Hs, int Ws, int ups, int stride, int ksize, int Cin, int CoutP,
+                                    size_t* derived_bytes, size_t* base_bytes);
+int sr3_conv_dgrad_f32(sr3_plan* plan, const float* dy, const float* w_ohwi, int Cout_w, int CoutP, int B, int Hs, int Ws, int ups,
+                       int stride, int ksize, int Cin, float* dA, void* scratch, size_t scratch_bytes, void* derived,
+                       size_t derived_bytes, int* tile_out, int* ksplit_out, int* derived_kind_out, void* stream);
+
+/* Routing of a gradient g [B, Hs << ups, Ws << ups, C0 + C1] to the two sources of a virtual concat, d0 [B, Hs, Ws, C0] and d1
+ * [B, Hs, Ws, C1] (C1 0: one source, d1 is not read): ups 1 sums the 2 x 2 children of a source pixel, ((a + b) + c) + d in row-major order (the
+ * backward of the nearest x2 upsample); acc0 / acc1 != 0 adds the destination's old value last, 0 is a plain store. */
+int sr3_grad_route_f32(const float* g, int C0, int C1, int B, int Hs, int Ws, int ups, float* d0, int acc0, float* d1, int acc1,
+                       void* stream);
+
+/* Column sums of g [B][HW][C], accumulated in double and rounded once: dbias[c] = the sum over images and pixels (the bias
+ * gradient), dfilm[b * film_stride + c] = the sum over the pixels of image b (a conv's rows of the FiLM gradient table; film_stride
+ * >= C, every other element of the table is left untouched).  Either may be NULL, not both.  scratch: 8-byte aligned,
+ * sr3_colsums_scratch_bytes bytes. */
+size_t sr3_colsums_scratch_bytes(int B, int HW, int C);
+int sr3_colsums_f32(const float* g, int B, int HW, int C, float* dbias, float* dfilm, int film_stride, void* scratch,
+                    size_t scratch_bytes, void* stream);
+
+/* Backward of sr3_film_embed_f32: dfilm [B][F] -> the gradients of the embedding MLP (dw1 [4 inner][inner], db1, dw2
+ * [inner][4 inner], db2) and of the FiLM projections (dwf [F][inner], dbf [F]), all overwritten; the forward is recomputed from
+ * level / timestep and freq.  inner must divide 256 (SR3_E_UNSUPPORTED otherwise).  scratch: sr3_embed_bwd_scratch_bytes bytes. */
+size_t sr3_embed_bwd_scratch_bytes(int B, int inner);
+int sr3_embed_bwd_f32(int variant, int B, int inner, int F, const float* level, const int64_t* timestep, const float* freq,
+                      const float* w1, const float* b1, const float* w2, const float* b2, const float* wf, const float* dfilm,
+                      float* dw1, float* db1, float* dw2, float* db2, float* dwf, float* dbf, void* scratch, size_t scratch_bytes,
+                      void* stream);
+
 /* noise-level / timestep embedding + MLP + all FiLM rows (unet.py:18-50,179-184): see sr3_common.h */
 int sr3_film_embed_f32(int variant, int B, int inner, const float* level, const int64_t* timestep,
                        const float* freq, const float* w1, const float* b1, const float* w2, const float* b2,
