@@ -27,6 +27,13 @@ int derive_behind_slabs(const ConvParams& c, int tile, int ksplit, Derive kind, 
                                      : wino_transform_weights(c.w, c.Cout, Cin, *out, st, kind == DERIVE_WINO_SPLIT);
 }
 
+// the scratch of the per-op conv entries: split-K slabs with the derived filters behind them, laid out as a plan lays out its 256-byte
+// aligned regions -- checked before anything is derived into it
+int check_scratch_aligned(const void* scratch) {
+  if ((uintptr_t)scratch & 255) { set_error("conv: scratch is not 256-byte aligned"); return SR3_E_ALIGN; }
+  return SR3_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -69,6 +76,7 @@ int sr3_conv_f32(const float* src0, int C0, const float* src1, int C1, int B, in
                  int film_stride, const float* res0, int RC0, const float* res1, int RC1, float* out, double* out_stats,
                  int tile_cfg, int ksplit, void* scratch, size_t scratch_bytes, void* stream) {
   if (!src0 || !w || !out) { set_error("null argument"); return SR3_E_BADARG; }
+  if (const int rc = check_scratch_aligned(scratch)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   ConvParams c = conv_shape(B, Hs, Ws, ups, stride, ksize, C0, src1 ? C1 : 0, Cout);
   c.src0 = src0; c.src1 = src1; c.w = w; c.bias = bias; c.ss = ss; c.act = act; c.film = film; c.film_stride = film_stride;
@@ -106,6 +114,7 @@ int sr3_block_conv_f32(const float* src0, int C0, const float* src1, int C1, int
                        const float* x2_bias, float* out, double* out_stats, int tile_cfg, int ksplit, void* scratch,
                        size_t scratch_bytes, void* stream) {
   if (!src0 || !w || !out || !x2_src0 || !x2_w) { set_error("null argument"); return SR3_E_BADARG; }
+  if (const int rc = check_scratch_aligned(scratch)) return rc;
   ConvParams c = conv_shape(B, H, W, 0, 1, 3, C0, src1 ? C1 : 0, Cout);
   c.src0 = src0; c.src1 = src1; c.w = w; c.bias = bias; c.ss = ss; c.act = act; c.film = film; c.film_stride = film_stride;
   c.out = out; c.ostat = out_stats;
@@ -119,6 +128,7 @@ int sr3_conv_dropout_f32(const float* src0, int C0, int B, int H, int W, int Cou
                          size_t scratch_bytes, unsigned drop_seed, float drop_p, void* stream) {
   if (!src0 || !w || !out || !ss) { set_error("null argument"); return SR3_E_BADARG; }
   if (drop_p < 0.f || drop_p >= 1.f) { set_error("drop_p out of range"); return SR3_E_BADARG; }
+  if (const int rc = check_scratch_aligned(scratch)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   ConvParams c = conv_shape(B, H, W, 0, 1, 3, C0, 0, Cout);
   c.src0 = src0; c.w = w; c.bias = bias; c.ss = ss; c.act = act; c.film = film; c.film_stride = film_stride;

@@ -372,5 +372,6 @@ extern "C" size_t sr3_attention_bwd_scratch_bytes(int B, int N, int C) { return 
 extern "C" int sr3_attention_bwd_ex_f32(const float* qkv, const float* dout, const float* out_fwd, int B, int N, int C, float* dqkv,
                                         void* scratch, size_t scratch_bytes, void* stream) {
   if (!qkv || !dout || !dqkv || !scratch) { sr3::set_error("null argument"); return SR3_E_BADARG; }
+  if ((uintptr_t)scratch & 15) { sr3::set_error("attention_bwd: scratch is not 16-byte aligned"); return SR3_E_ALIGN; }
   return sr3::attention_backward(qkv, dout, out_fwd, B, N, C, dqkv, static_cast<hipStream_t>(stream), static_cast<float*>(scratch), scratch_bytes);
 }

@@ -260,6 +260,7 @@ int sr3_ssim_u8(const uint8_t* a_hwc, const uint8_t* b_hwc, int n_images, int H,
   if (H < 11 || W < 11 || C <= 0 || n_images <= 0) { set_error("ssim: images must be at least 11 x 11"); return SR3_E_BADARG; }
   const size_t need = sr3_ssim_scratch_bytes(n_images, H, W, C);
   if (scratch_bytes < need) { set_error("ssim: scratch too small (%zu < %zu)", scratch_bytes, need); return SR3_E_NOMEM; }
+  if ((uintptr_t)scratch & 7) { set_error("ssim: scratch is not 8-byte aligned (the blocks' partial sums are doubles)"); return SR3_E_ALIGN; }
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int blocks = (int)(need / sizeof(double) / n_images);
   static const Gauss11 gk = gaussian11();
@@ -283,6 +284,7 @@ int sr3_eval_psnr_ssim_f32(const float* sr_nchw, const float* hr_nchw, int n_ima
   if (!(hi > lo)) { set_error("eval: bad range"); return SR3_E_BADARG; }
   const size_t need = sr3_eval_scratch_bytes(n_images, C, H, W);
   if (need == 0 || scratch_bytes < need) { set_error("eval: scratch too small (%zu < %zu)", scratch_bytes, need); return SR3_E_NOMEM; }
+  if ((uintptr_t)scratch & 7) { set_error("eval: scratch is not 8-byte aligned (the SSIM partial sums behind the two images are doubles)"); return SR3_E_ALIGN; }
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t per = (size_t)C * H * W;
   const size_t img = ((size_t)n_images * per + 255) & ~(size_t)255;

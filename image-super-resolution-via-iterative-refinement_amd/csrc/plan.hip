@@ -1082,10 +1082,11 @@ int sr3_plan_tap_info(sr3_plan* plan, int index, char* name, int name_len, size_
 size_t sr3_plan_derived_bytes(const sr3_plan* plan) { return plan ? plan->derived_floats * sizeof(float) : 0; }
 int sr3_plan_bind_derived(sr3_plan* plan, void* buffer, size_t bytes) {
   if (!plan) { set_error("null plan"); return SR3_E_BADARG; }
-  if (buffer && (bytes < plan->derived_floats * sizeof(float) || ((uintptr_t)buffer & 15))) {
-    set_error("derived buffer too small or misaligned (%zu < %zu)", bytes, plan->derived_floats * sizeof(float));
+  if (buffer && bytes < plan->derived_floats * sizeof(float)) {
+    set_error("derived buffer too small (%zu < %zu)", bytes, plan->derived_floats * sizeof(float));
     return SR3_E_NOMEM;
   }
+  if ((uintptr_t)buffer & 15) { set_error("derived buffer is not 16-byte aligned"); return SR3_E_ALIGN; }
   plan->derived_ptr = static_cast<float*>(buffer);
   plan->derived_bound_bytes = buffer ? bytes : 0;
   plan->derived_from = nullptr;               // a freshly bound buffer holds nothing yet

@@ -357,7 +357,8 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
     rc = objective_loss_grad(z, hr, eps, obj, B, P->out_ch, S2, OUT_PAD, grad_scale, geps, lparts, loss_out, st);
   if (rc) return rc;
   // ---- the backward walk: the records in reverse, each as build_train resolved it.  The activation-gradient mirror is not zeroed
-  // (Rec::acc_*); the FiLM gradient table is ----
+  // (Rec::acc_*).  The FiLM gradient table is, as a precaution only: every row of it belongs to exactly one conv, whose colsums below
+  // stores it, so with today's walk no element of the table is read before it is written ----
   float* dfilm = X.at<float>(P->t_dfilm_off);
   SR3_HIP(hipMemsetAsync(dfilm, 0, (size_t)B * P->F * sizeof(float), st));
 
@@ -560,7 +561,10 @@ int sr3_conv_dgrad_f32(sr3_plan* plan, const float* dy, const float* w_ohwi, int
   // not -- send the conv to the general kernels, whose own slabs must fit
   choose_dgrad(plan, d, derived ? derived_bytes : 0, bufs.slab_bytes);
   const size_t slabs = conv_splitk_bytes(d.c, d.tile, d.ksplit);
-  if (bufs.slab_bytes < slabs) { set_error("%s: scratch too small (%zu < %zu)", who, scratch_bytes, lay.slabs + slabs); return SR3_E_NOMEM; }
+  // the query rounds the slabs up to 256 bytes, and so does this check: what is refused is exactly a scratch below the chosen kernel's
+  // query.  (choose_dgrad above is capped by the unrounded room, so a scratch less than 256 bytes short of the rounded size is refused
+  // here instead of running: such a caller is below the query either way)
+  if (bufs.slab_bytes < al256(slabs)) { set_error("%s: scratch too small (%zu < %zu)", who, scratch_bytes, lay.slabs + al256(slabs)); return SR3_E_NOMEM; }
   int tile = d.tile, ks = d.ksplit;
   conv_pick(d.c, tile, ks);                            // (what conv_forward resolves tile 0 / ksplit 0 to)
   if (tile_out) *tile_out = tile_encode(tile, d.c.wino_split, d.c.igemm_split, false);

@@ -683,6 +683,7 @@ extern "C" int sr3_conv_wgrad_f32(const float* src0, int C0, const float* src1, 
   wgrad_fill(wp.c, src0, C0, src1, C1, B, Hs, Ws, ups, stride, ksize, Cout, ss, act, split);
   wp.dy = dy; wp.dw = dw_ohwi; wp.slabs = static_cast<float*>(scratch);
   const size_t need = sr3::wgrad_slab_bytes(wp.c, &wp.msplit);
+  if (wp.msplit > 1 && scratch && ((uintptr_t)scratch & 15)) { sr3::set_error("wgrad: scratch is not 16-byte aligned"); return SR3_E_ALIGN; }
   if (wp.msplit > 1 && (!scratch || scratch_bytes < need)) { sr3::set_error("wgrad: scratch too small (%zu < %zu)", scratch_bytes, need); return SR3_E_NOMEM; }
   return sr3::conv_wgrad(wp, static_cast<hipStream_t>(stream));
 }

@@ -43,7 +43,9 @@ int sr3_sse_u8(const uint8_t* a, const uint8_t* b, int n_images, size_t bytes_pe
 /* ssim / calculate_ssim (core/metrics.py:53-93) of n_images HWC uint8 image pairs: 11 x 11 window =
  * outer(g, g), g = cv2.getGaussianKernel(11, 1.5); mu / sigma maps over the valid region [5:-5, 5:-5]; mean of the SSIM
  * map over all valid pixels and channels (calculate_ssim's 3-channel branch averages three identical whole-image
- * values, :85-88, i.e. the same number).  ssim_out[i] is a double on the device. */
+ * values, :85-88, i.e. the same number).  ssim_out[i] is a double on the device.  scratch: sr3_ssim_scratch_bytes bytes (SR3_E_NOMEM
+ * below that), 8-byte aligned (SR3_E_ALIGN): the blocks' partial sums, written before they are read (the buffer contract of
+ * include/sr3_mi355x.h at sr3_workspace_bytes holds for every scratch of this header). */
 size_t sr3_ssim_scratch_bytes(int n_images, int H, int W, int C);
 int sr3_ssim_u8(const uint8_t* a_hwc, const uint8_t* b_hwc, int n_images, int H, int W, int C, void* scratch,
                 size_t scratch_bytes, double* ssim_out, void* stream);
@@ -51,7 +53,7 @@ int sr3_ssim_u8(const uint8_t* a_hwc, const uint8_t* b_hwc, int n_images, int H,
 /* The validation loop's per-image chain (sr.py:119-145: tensor2img(SR), tensor2img(HR), calculate_psnr,
  * [calculate_ssim in eval.py / infer.py]) fused on the device for a batch of fp32 NCHW tensors in [lo, hi]: quantise
  * both to uint8 HWC exactly as tensor2img does, then the two reductions above.  Only n_images * 16 bytes return to the
- * host instead of two fp32 images per sample. */
+ * host instead of two fp32 images per sample.  scratch: sr3_eval_scratch_bytes bytes, 8-byte aligned (SR3_E_NOMEM / SR3_E_ALIGN). */
 size_t sr3_eval_scratch_bytes(int n_images, int C, int H, int W);
 int sr3_eval_psnr_ssim_f32(const float* sr_nchw, const float* hr_nchw, int n_images, int C, int H, int W, float lo,
                            float hi, void* scratch, size_t scratch_bytes, unsigned long long* sse_out, double* ssim_out,

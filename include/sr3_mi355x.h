@@ -204,8 +204,6 @@ int sr3_plan_tap_info(sr3_plan* plan, int index, char* name, int name_len, size_
 int sr3_plan_set_geometry(sr3_plan* plan, int height, int width);
 int sr3_plan_get_geometry(const sr3_plan* plan, int* height, int* width);
 
-/* Workspace bytes for sr3_unet_forward at this batch size and the plan's current geometry (activations, statistics, FiLM
- * table, split-K slabs). */
 /* Derived weights.  The inference plan runs its 3x3 stride-1 convolutions as Winograd F(2x2,3x3) (plan option
  * "winograd", default 1), which reads the transformed filters U = G g G^T from a caller-owned device buffer of
  * sr3_plan_derived_bytes bytes (16/9 of the 3x3 weights).  Bind it once (the pointer is kept, and baked into captured
@@ -217,11 +215,23 @@ int sr3_plan_get_geometry(const sr3_plan* plan, int* height, int* width);
  * sr3_plan_derived_bytes and un-binds a buffer that is now too small), or (e) sr3_plan_invalidate_derived was called
  * after the last prepare.  The library cannot see writes to the arena (sr3_adam_step takes no plan): a caller that
  * updates parameters in place calls sr3_plan_invalidate_derived right after the update and prepares again before the
- * next forward. */
+ * next forward.  The buffer contract at sr3_workspace_bytes holds for this buffer too: exactly sr3_plan_derived_bytes bytes, 16-byte
+ * aligned (SR3_E_NOMEM / SR3_E_ALIGN from sr3_plan_bind_derived otherwise), prior contents irrelevant -- sr3_plan_prepare_derived writes
+ * every byte a forward reads. */
 size_t sr3_plan_derived_bytes(const sr3_plan* plan);
 int sr3_plan_bind_derived(sr3_plan* plan, void* buffer, size_t bytes);
 int sr3_plan_prepare_derived(sr3_plan* plan, const float* params, void* stream);
 int sr3_plan_invalidate_derived(sr3_plan* plan);
+/* sr3_workspace_bytes: workspace bytes for sr3_unet_forward / sr3_reverse_step* at this batch size and the plan's current geometry
+ * (activations, statistics, FiLM table, split-K slabs).
+ * THE BUFFER CONTRACT of every caller-owned workspace, derived buffer and scratch of this library (tests/test_gpu_workspace_contract.py,
+ * tests/test_gpu_scratch_contract.py, tests/test_scratch_contract_cpu.py):
+ *   1. a buffer of exactly the queried byte count is enough (aligned as the entry states: 256 bytes for a workspace);
+ *   2. nothing outside it is written;
+ *   3. what it held before the call does not matter -- zeros, NaN patterns, the leftovers of another batch size, geometry or plan: the
+ *      results are the same bits.  No zeroing is ever needed, and none should be done (it is a pass over HBM per call).
+ * A buffer below the query, or a misaligned one, is refused on the host before anything is launched (SR3_E_NOMEM naming both sizes /
+ * SR3_E_ALIGN; the few entries that document SR3_E_BADARG for a small scratch keep that code). */
 size_t sr3_workspace_bytes(sr3_plan* plan, int batch);
 
 /* UNet.forward (model/sr3_modules/unet.py:235-259, model/ddpm_modules/unet.py:220-243).
@@ -610,7 +620,9 @@ int sr3_q_sample(const float* x0, const float* z, const float* ca, const float* 
 
 /* Workspace of sr3_train_step (activations kept for the backward, their gradient mirror, scratch) at the plan's geometry.  Without plan
  * option train_geom training runs at image_size x image_size only: 0 (and a message) while sr3_plan_set_geometry has the plan at
- * another geometry; with it, 0 only for a geometry no kernel can run (an attention level beyond the score strip without attn_long). */
+ * another geometry; with it, 0 only for a geometry no kernel can run (an attention level beyond the score strip without attn_long).
+ * The buffer contract at sr3_workspace_bytes holds: exactly this many bytes, nothing outside them written, prior contents irrelevant
+ * (the activation-gradient mirror is not zeroed: every tensor's first writer stores). */
 size_t sr3_train_workspace_bytes(sr3_plan* plan, int batch, int cond_channels);
 
 /* One training step up to the gradients: `l_pix = netG(data); l_pix.backward()` of
@@ -620,7 +632,10 @@ size_t sr3_train_workspace_bytes(sr3_plan* plan, int batch, int cond_channels);
  *   *loss_sum_out = sum |z - eps| ; grads = d(grad_scale * loss_sum) / d params
  * (grad_scale = 1 / (b*c*h*w), model.py:52-53).  The random draws (t / gamma, z) are made by the caller
  * (torch / numpy RNG, as in the reference) and passed in.  `grads` has the layout of the parameter
- * arena and is overwritten.  dropout_p > 0 applies nn.Dropout(p) between Swish and the conv of every
+ * arena and is overwritten: every float of [0, sr3_plan_param_floats) is written, whatever the arena held (NaN included).  That covers
+ * the arena's padding floats, which belong to no parameter -- the output conv's bias slot is 4 floats wide (8 with a variance head) and
+ * receives the column sums of all lanes of dOut, whose pad lanes are 0: they come out +0, so sr3_grad_norm and the Adam entries can take
+ * the whole arena length.  dropout_p > 0 applies nn.Dropout(p) between Swish and the conv of every
  * block2 (unet.py:83-88,100-101) with a counter-based mask: activated element i (NHWC linear index) of
  * the block with FiLM row offset k is kept iff hash32(i*0x9E3779B9 + dropout_seed + (k+1)*0x632BE5AB) >=
  * p*2^32 and scaled by 1/(1-p); the mask is regenerated, never stored, by the backward.
@@ -784,7 +799,9 @@ int sr3_adam_ema_step_scaled(float* params, const float* grads, float* exp_avg, 
  * B * Ho * Wo % 64 == 0, Ho * Wo % 32 == 0, act 0 | 1; anything else is refused with "does not fit"; same pre-split weights as
  * 18-21, derived into `scratch`).
  * scratch: split-K slabs (+ the Winograd filters for tile_cfg 11-13 and 23, the pre-split weights for 18-22), sized by
- * sr3_conv_scratch_bytes. */
+ * sr3_conv_scratch_bytes, 256-byte aligned (SR3_E_ALIGN otherwise, for the three conv entries).  For this and every per-op scratch
+ * below the buffer contract at sr3_workspace_bytes holds: exactly the queried bytes, nothing outside them written, prior contents
+ * irrelevant (split-K slabs, statistics slices and padded lanes are written before they are read). */
 int sr3_conv_f32(const float* src0, int C0, const float* src1, int C1, int B, int Hs, int Ws, int ups,
                  int stride, int ksize, int Cout, const float* w_ohwi, const float* bias, const float* ss,
                  int act, const float* film, int film_stride, const float* res0, int RC0, const float* res1,
@@ -839,7 +856,8 @@ int sr3_attention_bwd_f32(const float* qkv, const float* dout, const float* out_
                           void* stream);
 /* ... bitwise reproducible: every 32-query block hands its dK / dV contribution to a slab of its own in `scratch`
  * (sr3_attention_bwd_scratch_bytes(B, N, C) = ceil(N / 32) * B * N * 2C floats) and a second kernel sums the slabs in block
- * order -- no atomics, no memset (sr3_attention_bwd_f32 adds with fp32 atomics).  What sr3_train_step runs. */
+ * order -- no atomics, no memset (sr3_attention_bwd_f32 adds with fp32 atomics).  What sr3_train_step runs.  scratch: 16-byte aligned
+ * (SR3_E_ALIGN), at least the queried bytes (SR3_E_NOMEM). */
 size_t sr3_attention_bwd_scratch_bytes(int B, int N, int C);
 int sr3_attention_bwd_ex_f32(const float* qkv, const float* dout, const float* out_fwd, int B, int N, int C, float* dqkv,
                              void* scratch, size_t scratch_bytes, void* stream);
@@ -848,7 +866,8 @@ int sr3_attention_bwd_ex_f32(const float* qkv, const float* dout, const float* o
  * (virtual concat, optionally x2-upsampled, optionally GroupNorm-affine / SiLU-activated: act, ss as in sr3_conv_f32) input.
  * dy NHWC [B, Ho, Wo, Cout]; dw OHWI [Cout][ksize^2][C0 + C1], overwritten.  split != 0: the 3 x bf16 split kernel where it applies
  * (more than 64 channels on both sides; plan option wgrad_split), else the fp32-MFMA kernels.  scratch: the per-pixel-range slabs
- * (sr3_conv_wgrad_scratch_bytes), summed in double in a fixed order. */
+ * (sr3_conv_wgrad_scratch_bytes), summed in double in a fixed order; 16-byte aligned (SR3_E_ALIGN), at least the queried bytes where the
+ * shape splits its pixels (SR3_E_NOMEM). */
 size_t sr3_conv_wgrad_scratch_bytes(int B, int Hs, int Ws, int ups, int stride, int ksize, int C0, int C1, int Cout, int split);
 int sr3_conv_wgrad_f32(const float* src0, int C0, const float* src1, int C1, int B, int Hs, int Ws, int ups, int stride, int ksize,
                        int Cout, const float* ss, int act, const float* dy, float* dw_ohwi, int split, void* scratch,

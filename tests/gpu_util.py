@@ -29,9 +29,10 @@ def ohwi(w):      # OIHW -> OHWI contiguous
 
 
 def conv_call(src0, src1, w, bias=None, ss=None, act=0, film=None, res0=None, res1=None, ups=0, stride=1,
-              tile_cfg=0, ksplit=0, want_stats=False):
+              tile_cfg=0, ksplit=0, want_stats=False, guard=None):
     """All tensor args are CPU fp32 in reference layouts: src NCHW, w OIHW, ss [B,Cin,2], film [B,Cout],
-    res NCHW.  Returns (out NCHW cpu, stats [B,Cout,2] cpu double or None)."""
+    res NCHW.  Returns (out NCHW cpu, stats [B,Cout,2] cpu double or None).  guard (a fill byte): the scratch is exactly the queried
+    size inside a tests/guarded.py buffer filled with that byte, whose bands must come back intact."""
     lib = L.load()
     d = dev()
     B, C0, Hs, Ws = src0.shape
@@ -52,12 +53,19 @@ def conv_call(src0, src1, w, bias=None, ss=None, act=0, film=None, res0=None, re
         Tst = int(lib.sr3_conv_stats_slices(B, Hs, Ws, ups, Cin, Cout, tile_cfg, ksplit))
         stats = torch.full((B, max(Tst, 1), Cout, 2), float('nan'), dtype=torch.float64, device=d)
     nb = int(lib.sr3_conv_scratch_bytes(B, Ho, Wo, Cin, Cout, k, tile_cfg, ksplit))
-    scratch = torch.empty(max(nb, 16), dtype=torch.uint8, device=d)
+    guarded = None
+    if guard is None:
+        scratch = torch.empty(max(nb, 16), dtype=torch.uint8, device=d)
+    else:
+        from guarded import Guarded
+        guarded = Guarded(nb, guard, d)
+        scratch = guarded.view()
     L.check(lib.sr3_conv_f32(L.ptr(s0), C0, L.ptr(s1), C1, B, Hs, Ws, ups, stride, k, Cout, L.ptr(wd), L.ptr(bd),
                              L.ptr(ssd), act, L.ptr(fd), 0 if film is None else film.shape[1], L.ptr(r0),
                              0 if res0 is None else res0.shape[1], L.ptr(r1), 0 if res1 is None else res1.shape[1],
                              L.ptr(out), L.ptr(stats), tile_cfg, ksplit, L.ptr(scratch), nb, stream()))
     torch.cuda.synchronize()
+    assert guarded is None or guarded.intact(), 'sr3_conv_f32 wrote outside its %d scratch bytes' % nb
     return nchw(out).cpu(), (None if stats is None else stats.cpu().sum(1))
 
 
