@@ -42,6 +42,7 @@ struct Objective {
   // (device; null: the objective above alone) and the weight lambda of L_vlb
   const float* hyb = nullptr;
   float lambda = 0.f;
+  const float* vlb_w = nullptr;      // per image, lambda * vlb_w[b] in place of lambda (sr3_train_step_ex3's vlb_weight; null: lambda)
 };
 // one image's row of Objective::hyb: x0 = a x_t - b out ; posterior mean c1 x0 + c2 x_t ; log beta, log beta~ (clipped) of the step ;
 // last != 0: the walk's last step (the discretised log-likelihood instead of the KL term)
@@ -56,6 +57,14 @@ int objective_loss_grad(const float* z, const float* hr, const float* e, const O
 int hybrid_loss_grad(const float* z, const float* hr, const float* xt, const float* e, const Objective& o, int B, int Cc, int HW, int CP,
                      float scale, float* g_nhwc, double* loss_part, float* loss_out, float* vlb_out, hipStream_t st);
 int nchw_to_nhwc_pad(const float* a, int Ca, const float* b, int Cb, int B, int HW, int CP, float* out, hipStream_t st);
+// Per-image terms of the variational bound (vlb_eval.hip): vb_out / mse_out [b * ostride] (rows: a row index per image;
+// step2: the device step counter, one row for all images and row j of [table_rows, B] outputs; both null: image b reads row b) = the
+// mean over C P of the bound's term in bits and of (x0 - x0^)^2.  Two launches; part: vlb_terms_scratch(B) bytes of block partials
+int vlb_terms(const float* x0, const float* xt, const float* out, const float* table, int table_rows, const int* rows, int* step2,
+              int var_mode, bool clip, int B, int C, int OC, int P, float* vb_out, float* mse_out, int ostride, double* part, hipStream_t st);
+size_t vlb_terms_scratch(int batch);
+// sr3_train_step_ex3: where the step's per-image terms go (out null: none are computed), and the rows' table where the objective has none
+struct PerImage { float* out = nullptr; double* part = nullptr; const float* scal = nullptr; };
 
 // Weight gradient of a conv (wgrad.hip): dw[n][tap][c] = sum_m dy[m][n] * a_tap[m][c], a = prologue(x0|x1)
 // recomputed on the fly (same ConvParams geometry as the forward; p.out / p.w unused).

@@ -354,6 +354,8 @@ __global__ __launch_bounds__(256) void k_loss_grad(const float* __restrict__ z, 
 //              Phi(u) = (1 + tanh(sqrt(2 / pi) (u + 0.044715 u^3))) / 2 and logs of max(., 1e-12)
 //   g lane Cc + c = lambda scale d vlb / d v, in closed form; lanes >= 2 Cc are 0
 // loss_part[block] = sum w rho(d) + lambda sum vlb, loss_part[gridDim.x + block] = sum vlb: double partials, fixed order, no atomics.
+// vw (sr3_train_step_ex3's vlb_weight; null: 1): per image, lambda vw[b] stands where lambda does -- in the variance lanes and in the
+// first sum; the second sum stays the plain sum of vlb.
 struct VlbScal { float a, b, c1, c2, lb, lt; bool last; };
 __device__ __forceinline__ float approx_cdf(float u, float* pdf) {
   constexpr float K = 0.7978845608028654f;      // sqrt(2 / pi)
@@ -392,14 +394,16 @@ __global__ __launch_bounds__(256) void k_hybrid_loss_grad(const float* __restric
                                                            const float* __restrict__ ta, const float* __restrict__ tb,
                                                            const float* __restrict__ w, const float* __restrict__ hyb, int B, int Cc,
                                                            int HW, int CP, float scale, float delta, float lambda,
-                                                           float* __restrict__ g_nhwc, double* __restrict__ loss_part) {
+                                                           float* __restrict__ g_nhwc, double* __restrict__ loss_part,
+                                                           const float* __restrict__ vw) {
   __shared__ double red[256];
   double s = 0.0, sv = 0.0;
   const size_t total = (size_t)B * HW;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const size_t b = i / HW, p = i - b * HW;
     const float az = ta ? ta[b] : 1.f, ax = tb ? tb[b] : 0.f, wb = w ? w[b] : 1.f;
-    const float ws = wb * scale, ls = lambda * scale;
+    const float lam = vw ? lambda * vw[b] : lambda;      // (vw: a per-image weight of L_vlb; null: lambda as it is -- the same operations)
+    const float ws = wb * scale, ls = lam * scale;
     const float* hs = hyb + b * HYB_STRIDE;
     const VlbScal k = {hs[HYB_A], hs[HYB_B], hs[HYB_C1], hs[HYB_C2], hs[HYB_LOG_BETA], hs[HYB_LOG_BETA_TILDE], hs[HYB_LAST] != 0.f};
     double sp = 0.0, vp = 0.0;
@@ -428,7 +432,7 @@ __global__ __launch_bounds__(256) void k_hybrid_loss_grad(const float* __restric
       }
       g_nhwc[i * CP + c] = gv;
     }
-    s += (double)wb * sp + (double)lambda * vp;
+    s += (double)wb * sp + (double)lam * vp;
     sv += vp;
   }
   for (int pass = 0; pass < 2; ++pass) {
@@ -625,7 +629,7 @@ int hybrid_loss_grad(const float* z, const float* hr, const float* xt, const flo
   const int blocks = LOSS_GRAD_BLOCKS;
   static constexpr decltype(&k_hybrid_loss_grad<0>) kernels[3] = {k_hybrid_loss_grad<0>, k_hybrid_loss_grad<1>, k_hybrid_loss_grad<2>};
   hipLaunchKernelGGL(kernels[o.kind], dim3(blocks), dim3(256), 0, st, z, hr, xt, e, o.tgt_z, o.tgt_x0, o.weight, o.hyb, B, Cc, HW, CP,
-                     scale, o.huber_delta, o.lambda, g_nhwc, loss_part);
+                     scale, o.huber_delta, o.lambda, g_nhwc, loss_part, o.vlb_w);
   SR3_LAUNCH_CHECK("k_hybrid_loss_grad");
   hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(64), 0, st, loss_part, blocks, loss_out);
   SR3_LAUNCH_CHECK("k_sum_parts");

@@ -328,7 +328,8 @@ int wgrad_call(const TrainCtx& X, ConvParams c, const float* src0, const float* 
 int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels, const float* z, const float* q_ca,
               const float* q_cb, const float* level, const int64_t* tstep, const float* freq, const float* params,
               float* grads, char* ws, float* loss_out, float grad_scale, int B, hipStream_t st, float dropout_p,
-              unsigned seed, int n_marks, const size_t* marks, void* const* mark_events, const Objective& obj, float* vlb_out) {
+              unsigned seed, int n_marks, const size_t* marks, void* const* mark_events, const Objective& obj, float* vlb_out,
+              const PerImage& pi = PerImage()) {
   const sr3_unet_desc& d = P->d;
   // image geometry of this step: build_train built the plan for it (the native one unless plan option train_geom)
   const int IH = P->train_h, IW = P->train_w, S2 = IH * IW, G = d.norm_groups;
@@ -356,6 +357,12 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
   else
     rc = objective_loss_grad(z, hr, eps, obj, B, P->out_ch, S2, OUT_PAD, grad_scale, geps, lparts, loss_out, st);
   if (rc) return rc;
+  if (pi.out) {     // sr3_train_step_ex3: the per-image terms of the bound on the step's own x_noisy and output, while both are live
+    const int Cc = plan_image_channels(P);
+    rc = vlb_terms(hr, x_noisy, eps, pi.scal, B, nullptr, nullptr, obj.hyb ? 0 : 1, false, B, Cc, obj.hyb ? 2 * Cc : Cc, S2, pi.out, pi.out + 1, 2,
+                   pi.part, st);
+    if (rc) return rc;
+  }
   // ---- the backward walk: the records in reverse, each as build_train resolved it.  The activation-gradient mirror is not zeroed
   // (Rec::acc_*).  The FiLM gradient table is, as a precaution only: every row of it belongs to exactly one conv, whose colsums below
   // stores it, so with today's walk no element of the table is read before it is written ----
@@ -586,7 +593,8 @@ static int train_step_body(const char* who, sr3_plan* plan, const float* hr_nchw
                            float* loss_sum_out, float grad_scale, float dropout_p, unsigned dropout_seed, int n_marks,
                            const size_t* mark_offsets, void* const* mark_events, int batch, const float* tgt_z, const float* tgt_x0,
                            const float* weight, int loss_kind, float huber_delta, const float* step_scalars, float vlb_lambda,
-                           float* vlb_sum_out, void* stream) {
+                           float* vlb_sum_out, void* stream, bool ex3 = false, float* per_image_out = nullptr, void* pi_scratch = nullptr,
+                           size_t pi_scratch_bytes = 0, const float* vlb_weight = nullptr) {
   if (!plan || !hr_nchw || !z_nchw || !q_ca || !q_cb || !freq || !params || !grads || !workspace || !loss_sum_out) {
     set_error("null argument");
     return SR3_E_BADARG;
@@ -600,6 +608,20 @@ static int train_step_body(const char* who, sr3_plan* plan, const float* hr_nchw
   if (plan->d.variant == SR3_VARIANT_SR3 && !noise_level) { set_error("SR3 variant needs noise_level"); return SR3_E_BADARG; }
   if (plan->d.variant == SR3_VARIANT_DDPM && !timestep) { set_error("DDPM variant needs timestep"); return SR3_E_BADARG; }
   if (dropout_p < 0.f || dropout_p >= 1.f) { set_error("dropout_p out of range"); return SR3_E_BADARG; }
+  PerImage pi;
+  if (ex3 && per_image_out) {
+    if (!pi_scratch) { set_error("%s: scratch is NULL with per_image_out given", who); return SR3_E_BADARG; }
+    const size_t need = vlb_terms_scratch(batch);
+    if (pi_scratch_bytes < need) { set_error("%s: scratch too small (%zu < %zu)", who, pi_scratch_bytes, need); return SR3_E_NOMEM; }
+    if (overlaps(per_image_out, (size_t)batch * 2 * sizeof(float), pi_scratch, need)) { set_error("%s: per_image_out overlaps scratch", who); return SR3_E_BADARG; }
+    if (overlaps(workspace, plan->t_ws_bytes, per_image_out, (size_t)batch * 2 * sizeof(float)) || overlaps(workspace, plan->t_ws_bytes, pi_scratch, need)) {
+      set_error("%s: per_image_out / scratch overlaps the workspace", who);
+      return SR3_E_BADARG;
+    }
+    if ((uintptr_t)pi_scratch & 7) { set_error("%s: scratch is not 8-byte aligned", who); return SR3_E_ALIGN; }
+    pi.out = per_image_out; pi.part = static_cast<double*>(pi_scratch); pi.scal = step_scalars;
+  }
+  if (ex3 && plan->var_channels == 0) step_scalars = nullptr;      // no variance head: sr3_train_step_ex's objective; the rows serve the terms alone
   if ((plan->var_channels > 0) != (step_scalars != nullptr)) {
     set_error("%s: the plan's variance rows (var_channels %d) and step_scalars go together (sr3_train_step_ex2 trains them)", who, plan->var_channels);
     return SR3_E_BADARG;
@@ -607,11 +629,12 @@ static int train_step_body(const char* who, sr3_plan* plan, const float* hr_nchw
   if (step_scalars && !(isfinite(vlb_lambda) && vlb_lambda >= 0.f)) { set_error("%s: vlb_lambda %g must be finite and >= 0", who, (double)vlb_lambda); return SR3_E_BADARG; }
   Objective obj;
   obj.hyb = step_scalars; obj.lambda = vlb_lambda;
+  obj.vlb_w = step_scalars ? vlb_weight : nullptr;      // (a plan without a variance head has no L_vlb to weight)
   obj.tgt_z = tgt_z; obj.tgt_x0 = tgt_x0; obj.weight = weight; obj.huber_delta = huber_delta;
   obj.kind = loss_kind < 0 ? (plan->loss_l2 != 0 ? LOSS_L2 : LOSS_L1) : loss_kind;      // -1: the plan's loss_l2
   return run_train(plan, hr_nchw, cond_nchw, cond_channels, z_nchw, q_ca, q_cb, noise_level, timestep, freq, params, grads,
                    static_cast<char*>(workspace), loss_sum_out, grad_scale, batch, static_cast<hipStream_t>(stream), dropout_p,
-                   dropout_seed, (mark_offsets && mark_events) ? n_marks : 0, mark_offsets, mark_events, obj, vlb_sum_out);
+                   dropout_seed, (mark_offsets && mark_events) ? n_marks : 0, mark_offsets, mark_events, obj, vlb_sum_out, pi);
 }
 
 int sr3_train_step_ex(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels, const float* z_nchw,
@@ -637,6 +660,23 @@ int sr3_train_step_ex2(sr3_plan* plan, const float* hr_nchw, const float* cond_n
   return train_step_body("sr3_train_step_ex2", plan, hr_nchw, cond_nchw, cond_channels, z_nchw, q_ca, q_cb, noise_level, timestep, freq, params,
                          grads, workspace, workspace_bytes, loss_sum_out, grad_scale, dropout_p, dropout_seed, n_marks, mark_offsets,
                          mark_events, batch, tgt_z, tgt_x0, weight, loss_kind, huber_delta, step_scalars, vlb_lambda, vlb_sum_out, stream);
+}
+
+// sr3_train_step_ex2 (a plan with a variance head) or sr3_train_step_ex (one without: fixed small variance) with the per-image terms of
+// the bound behind the loss kernel: the same launches, and one pair of sr3_vlb_terms_f32's where per_image_out is given
+int sr3_train_step_ex3(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels, const float* z_nchw,
+                       const float* q_ca, const float* q_cb, const float* noise_level, const int64_t* timestep,
+                       const float* freq, const float* params, float* grads, void* workspace, size_t workspace_bytes,
+                       float* loss_sum_out, float grad_scale, float dropout_p, unsigned dropout_seed, int n_marks,
+                       const size_t* mark_offsets, void* const* mark_events, int batch, const float* tgt_z, const float* tgt_x0,
+                       const float* weight, int loss_kind, float huber_delta, const float* step_scalars, float vlb_lambda,
+                       float* vlb_sum_out, float* per_image_out, void* scratch, size_t scratch_bytes, const float* vlb_weight,
+                       void* stream) {
+  if (!step_scalars) { set_error("sr3_train_step_ex3: step_scalars is NULL"); return SR3_E_BADARG; }
+  return train_step_body("sr3_train_step_ex3", plan, hr_nchw, cond_nchw, cond_channels, z_nchw, q_ca, q_cb, noise_level, timestep, freq, params,
+                         grads, workspace, workspace_bytes, loss_sum_out, grad_scale, dropout_p, dropout_seed, n_marks, mark_offsets,
+                         mark_events, batch, tgt_z, tgt_x0, weight, loss_kind, huber_delta, step_scalars, vlb_lambda, vlb_sum_out, stream, true,
+                         per_image_out, scratch, scratch_bytes, vlb_weight);
 }
 
 int sr3_train_step(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels, const float* z_nchw,

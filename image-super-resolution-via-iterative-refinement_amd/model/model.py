@@ -81,6 +81,8 @@ class DDPM(BaseModel):
         l_pix = l_pix.sum() / int(b * c * h * w * _dist.dp_world_size())
         self.optG.step()
         gn = self.optG.last_grad_norm()
+        if getattr(self.netG, 't_sampler', None) is not None and self.distiller is None:
+            self.netG.flush_t_sampler()      # the step's per-image terms into the history: [B] floats, next to the loss's own copy below
         # learned variance: L_vlb of the step in bits per dimension (the engine's sum is over every rank's batch)
         vlb = getattr(self.netG, 'last_vlb', None) if getattr(self.netG, 'learned_variance', None) is not None else None
         names, vals = ['l_pix'], [l_pix]
@@ -173,6 +175,15 @@ class DDPM(BaseModel):
                     self.SR = self.netG.super_resolution(self.data['SR'], continous, backprojection_target=lr)
         self.netG.train()
 
+    def calc_bpd(self, steps=None):
+        """The variational bound of the fed batch by timestep (EngineDiffusion.calc_bpd_loop): a dict of vb [B, S], x0_mse [B, S],
+        prior_bpd [B], total_bpd [B] in bits per dimension; on the EMA weights where the train phase keeps them."""
+        self.netG.eval()
+        with torch.no_grad(), self._sampling_weights():
+            out = self.netG.calc_bpd_loop(self.data if self.netG.conditional else self.data['HR'], steps=steps)
+        self.netG.train()
+        return out
+
     def sample(self, batch_size=1, continous=False):
         self.netG.eval()
         with torch.no_grad(), self._sampling_weights():
@@ -246,6 +257,10 @@ class DDPM(BaseModel):
                 # a distilled student: the chain it was trained for -- what it is sampled on, and the next round's teacher walk
                 ck.setdefault('engine', {})['distill'] = {'steps': int(self._distill_state['steps']),
                                                           'walk': [int(v) for v in self._distill_state['walk']]}
+            if getattr(self.netG, 't_sampler', None) is not None:
+                # the loss-aware timestep sampler's history (this rank's), under the key alone
+                self.netG.flush_t_sampler()
+                ck['t_sampler'] = {k: torch.from_numpy(v) if hasattr(v, 'dtype') else v for k, v in self.netG.t_sampler.state_dict().items()}
             torch.save(ck, opt_path)
             logger.info('Saved model in [{:s}] ...'.format(gen_path))
         _dist.barrier()                 # nobody runs ahead (or resumes) before the files are complete
@@ -284,6 +299,8 @@ class DDPM(BaseModel):
                 raise ValueError('[{:s}] was trained with prediction {!r} but the config\'s model.diffusion.prediction is {!r}'.format(
                     opt_path, saved, self.netG.prediction))
             self.optG.load_state_dict(ck['optimizer'])
+            if getattr(self.netG, 't_sampler', None) is not None and ck.get('t_sampler') is not None:
+                self.netG.t_sampler.load_state_dict(ck['t_sampler'])
             self.begin_step = ck['iter']
             self.begin_epoch = ck['epoch']
             _dist.resume_epoch = int(ck['epoch'])

@@ -64,6 +64,11 @@ def define_G(opt):
     if lv is not None:
         from sr3_hip.diffusion import parse_learned_variance
         netG.set_learned_variance(parse_learned_variance(lv))
+    # "t_sampler": {"type": "loss_second_moment", "history": 10, "uniform": 0.001} -- p_losses draws t by its loss (set_t_sampler; behind
+    # learned_variance, which an SR3 model needs for it); absent: uniform draws, today's launches and checkpoint keys
+    if d.get('t_sampler') is not None and d.get('t_sampler') is not False:
+        from sr3_hip.t_sampler import parse_t_sampler
+        netG.set_t_sampler(**parse_t_sampler(d['t_sampler']))
     # "self_condition": {"prob": 0.5} | true -- the network reads its own last x0 as extra input channels (set_self_condition; unet.in_channel
     # is then conditioning channels + 2 x channels)
     if d.get('self_condition') is not None:

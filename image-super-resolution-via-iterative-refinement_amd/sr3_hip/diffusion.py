@@ -49,6 +49,13 @@ Sampling: `"sampler": {"type": "ancestral", "steps": S}` (no sampler block: all 
 every step runs forward (2C channels) -> sr3_learned_var_step.  Every other sampler and rule runs on such a network with its table
 sigma: their forwards launch the prediction rows of the output conv alone.
 
+The variational bound by timestep (engine extension; Nichol & Dhariwal 2021): `calc_bpd_loop` walks x0 through all S steps of the
+respaced walk -- q_sample at the step (sr3_q_sample_step_f32), one inference-mode forward, the per-image term of the bound
+(sr3_vlb_terms_f32) -- captured once and replayed, and returns bits per dimension per image and step, the prior term and their sum.
+`"t_sampler": {"type": "loss_second_moment", "history": 10, "uniform": 0.001}` in model.diffusion, or `set_t_sampler`: p_losses draws
+t with p_t proportional to sqrt(E[L_t^2]) of the per-image terms the training step returns (sr3_train_step_ex3) and weights the loss
+by 1 / (T p_t) (sr3_hip/t_sampler.py).  It needs draws on the schedule's grid: the DDPM variant, or SR3 under learned_variance.
+
 Rules on x0 (engine extensions, keys next to "sampler" / "tiling" or the setters; sr3_hip/x0_rules.py holds each rule once): what is done
 to the predicted x0 before the posterior mix.  Per step: UNet forward with the output stored, then the rule's entry in place of the fused
 tail.  The rules exclude one another and tiling -- each owns the whole tail of a step.
@@ -71,6 +78,7 @@ from torch import nn
 
 from . import engine as E
 from . import lib as L
+from . import t_sampler as TS
 from . import tiling as TL
 from . import x0_rules as X
 from .x0_rules import (BACKPROJECTION_KEYS, CONSISTENCY_BLOCKS, RESAMPLES, THRESHOLDS, backprojection_error, block_means,      # noqa: F401
@@ -500,6 +508,10 @@ class EngineDiffusion(nn.Module):
         self.learned_variance = None   # None: off; else {'lambda': l}: the network's last `channels` output rows are the variance head (set_learned_variance)
         self._hyb_table = None         # training: per-timestep rows of sr3_train_step_ex2's step_scalars on the device, built on first use
         self.last_vlb = None           # the last p_losses' L_vlb in bits per dimension (0-dim device tensor) under the key
+        self.t_sampler = None          # None: t is drawn uniformly; else a t_sampler.LossSecondMomentResampler (set_t_sampler)
+        self._t_pending = None         # under t_sampler: (the drawn steps, the step's per-image terms on the device) not yet in the history
+        self._t_sampler_cfg = None     # the parsed key; the resamplers made from it, one per schedule length
+        self._t_samplers = {}
         self.max_cached_loops = 3      # reverse-loop states (buffers + workspace + captured graph) kept, one per (shape, launch list)
         # schedule_opt is accepted and ignored exactly like the reference ctor (diffusion.py:80-82)
 
@@ -542,6 +554,8 @@ class EngineDiffusion(nn.Module):
         self.register_buffer('_x0_b', -torch.ones(self.num_timesteps, device=device), persistent=False)
         self._alphas_cumprod64 = ac                                              # what a sampler's tables are computed from
         self._loop_cache = {}
+        self.flush_t_sampler()
+        self._bind_t_sampler()                                                   # (the history is per schedule length)
         self._train_tables = None
         self.tiling = None                                                       # (this phase's own "tiling" key is read below)
         for r in X.RULES:                                                        # (and the rules' keys)
@@ -801,6 +815,8 @@ class EngineDiffusion(nn.Module):
         sigma.  lam None: off.  Not built (NotImplementedError, here or when the loop starts): the ancestral sampler together with
         tiling, consistency, guidance, back-projection or self-conditioning; train.distill."""
         if lam is None:
+            if getattr(self, 't_sampler', None) is not None and self.variant == 'sr3':
+                raise ValueError('t_sampler on an SR3 model needs learned_variance: switch it off first (set_t_sampler(None))')
             self.learned_variance = None
             if self.sampler is not None and self.sampler['type'] == 'ancestral':
                 self.set_sampler(None)
@@ -816,6 +832,43 @@ class EngineDiffusion(nn.Module):
                 self.set_sampler(self.num_timesteps, kind='ancestral')
         self._hyb_table = None
         self._loop_cache = {}
+
+    def set_t_sampler(self, type=None, history=TS.T_SAMPLER_HISTORY, uniform=TS.T_SAMPLER_UNIFORM):
+        """Loss-aware timestep sampling (config key model.diffusion.t_sampler: {"type": "loss_second_moment", "history": 10, "uniform":
+        0.001}): p_losses draws t from p_t proportional to sqrt(E[L_t^2]) over the last `history` per-image terms of the bound at every
+        step, mixed with `uniform` / T, and multiplies the per-image loss weight -- and, on a learned-variance model, L_vlb's own per-image weight (sr3_train_step_ex3's
+        vlb_weight) -- by 1 / (T p_t); uniform until every step has `history`
+        entries.  The step runs through sr3_train_step_ex3 and its per-image terms enter the history (`flush_t_sampler`, one small
+        device-to-host copy, made where the loss is read).  type None: off -- every draw and launch as without the key.  Needs draws on
+        the schedule's grid: the DDPM variant, or SR3 under learned_variance (set it first)."""
+        if type is None:
+            self.t_sampler, self._t_pending, self._t_sampler_cfg, self._t_samplers = None, None, None, {}
+            return
+        cfg = TS.parse_t_sampler(dict(type=type, history=history, uniform=uniform))
+        if self.variant == 'sr3' and self.learned_variance is None:
+            raise ValueError('t_sampler on a plain SR3 model: its training level is drawn between two grid values of the schedule, and '
+                             'x_t between two grid levels has no posterior, so the bound has no term there; it applies to the DDPM '
+                             'variant, or to SR3 together with model.diffusion.learned_variance (which draws on the grid)')
+        self._t_sampler_cfg, self._t_samplers, self._t_pending = cfg, {}, None
+        self._bind_t_sampler()
+
+    def _bind_t_sampler(self):
+        """The history belongs to a schedule length: one resampler per T met (a validation schedule of another length in between does
+        not cost the training schedule its history), made when the schedule is known."""
+        cfg, T = self._t_sampler_cfg, getattr(self, 'num_timesteps', None)
+        if cfg is None or T is None:
+            self.t_sampler = None
+            return
+        if T not in self._t_samplers:
+            self._t_samplers[T] = TS.LossSecondMomentResampler(T, cfg['history'], cfg['uniform'])
+        self.t_sampler, self._t_pending = self._t_samplers[T], None
+
+    def flush_t_sampler(self):
+        """Feed the last step's per-image terms (still on the device) into the history: [B] floats to the host."""
+        if self.t_sampler is not None and self._t_pending is not None:
+            t, terms = self._t_pending
+            self._t_pending = None
+            self.t_sampler.update(t.cpu().numpy(), terms[:, 0].detach().cpu().numpy())
 
     def _check_learned_variance(self, sampler=None, tiling=None, rules=None, self_condition=None):
         """What the learned-variance tail -- the "ancestral" sampler -- does not go with, over the settings as they are with the given ones
@@ -981,7 +1034,10 @@ class EngineDiffusion(nn.Module):
             live = set(un.plan._geometry_generation.values())
             kept = [(k, v) for k, v in self._loop_cache.items()
                     if k[2:4] == key[2:4] and k[4] in arenas and k[5] == key[5] and k[6] in live]
-            self._loop_cache = dict(kept[-(self.max_cached_loops - 1):] if self.max_cached_loops > 1 else [])
+            # (calc_bpd_loop's states keep the same fields at the same positions and are pruned by them, but count against a limit of
+            # their own, `_bpd_state`: an evaluation does not cost a sampling graph its place, nor the other way round)
+            bpd, kept = [e for e in kept if e[0][0] == 'bpd'], [e for e in kept if e[0][0] != 'bpd']
+            self._loop_cache = dict(bpd + (kept[-(self.max_cached_loops - 1):] if self.max_cached_loops > 1 else []))
             self._loop_cache[key] = st
         else:
             self._loop_cache[key] = self._loop_cache.pop(key)      # most recently used last
@@ -1350,6 +1406,163 @@ class EngineDiffusion(nn.Module):
         return self.p_sample_loop(x_in, continous, item_seeds=item_seeds, consistency_target=consistency_target,
                                   backprojection_target=backprojection_target, cond_noise=cond_noise)
 
+    # ---- the variational bound by timestep ----------------------------------------------------------
+    def _bpd_state(self, shape, cond_shape, dev, S, clip, item_streams):
+        """The state of calc_bpd_loop: buffers, the walk's tables on the device, a private workspace and the captured graph, in
+        `_loop_cache` under a key of its own -- ('bpd', ...): a string where a sampling key has the image shape, so the two cannot
+        collide; positions 2..6 are what `_loop_state` prunes by (device, T, arena, freq table, launch list)."""
+        un = self.denoise_fn
+        var_mode = 0 if self.learned_variance is not None else 1
+        aug = self.cond_augment
+        key = ('bpd', tuple(shape), str(dev), self.num_timesteps, un.weights().data_ptr(), un.freq.data_ptr(), un.plan.generation,
+               None if cond_shape is None else tuple(cond_shape), int(S), bool(clip), var_mode, self.prediction, bool(item_streams),
+               None if aug is None else (aug['sample_level'], aug['level_channel']))
+        st = self._loop_cache.get(key)
+        if st is not None:
+            self._loop_cache[key] = self._loop_cache.pop(key)
+            return st
+        B, Cc = shape[0], shape[1]
+        tabs = ancestral_tables(self._alphas_cumprod64, S, prediction=self.prediction)
+        ab = np.asarray(tabs['level'], dtype=np.float64)[1:] ** 2
+
+        def f32(a):
+            return torch.tensor(np.asarray(a, dtype=np.float64), dtype=torch.float32).to(dev)
+        nb = int(L.load().sr3_vlb_terms_partials_bytes(B))
+        st = dict(x0=torch.empty(shape, device=dev), z=torch.empty(shape, device=dev), xt=torch.empty(shape, device=dev),
+                  out=torch.empty((B, Cc if var_mode else 2 * Cc) + tuple(shape[2:]), device=dev),
+                  cond=None if cond_shape is None else torch.empty(cond_shape, device=dev),
+                  step=torch.zeros(2, dtype=torch.int32, device=dev), graph=None, ws=E.Workspace(),
+                  gens=[torch.Generator(device=dev) for _ in range(B)] if item_streams else None,
+                  vb=torch.empty((S, B), device=dev), mse=torch.empty((S, B), device=dev), prior=torch.empty(B, device=dev),
+                  scratch=torch.empty(nb // 8, dtype=torch.float64, device=dev), scratch_bytes=nb,
+                  hyb=f32(hybrid_step_scalars(tabs, np.arange(S))), ca=f32(tabs['level'][1:]), cb=f32(np.sqrt(1.0 - ab)),
+                  level=f32(tabs['level']), tau=torch.tensor(tabs['tau'], dtype=torch.int32).to(dev),
+                  abar_last=float(ab[-1]), S=int(S), clip=bool(clip), var_mode=var_mode, replays=0)
+        # at most max_cached_loops states of this kind, and none built for another device / schedule, an arena that is gone or a launch
+        # list that no longer exists (`_loop_state`'s rule); the sampling states are not counted and not touched
+        arenas = {un.arena.data_ptr()} | ({un.ema_arena.data_ptr()} if un.ema_arena is not None else set())
+        live = set(un.plan._geometry_generation.values())
+        kept = [(k, v) for k, v in self._loop_cache.items() if k[0] != 'bpd']
+        mine = [(k, v) for k, v in self._loop_cache.items()
+                if k[0] == 'bpd' and k[2:4] == key[2:4] and k[4] in arenas and k[5] == key[5] and k[6] in live]
+        self._loop_cache = dict(kept + (mine[-(self.max_cached_loops - 1):] if self.max_cached_loops > 1 else []))
+        self._loop_cache[key] = st
+        return st
+
+    def _bpd_step(self, st, draw_noise=True):
+        """One iteration of calc_bpd_loop at j = the device counter: z, x_t = ca[j] x0 + cb[j] z, the forward at the step's level /
+        timestep in inference mode, the per-image terms into row j -- whose second launch moves the counter to j - 1."""
+        lib, dev = L.load(), st['x0'].device
+        B, Cc, H, W = st['x0'].shape
+        if draw_noise:
+            self._draw(st['z'], st['gens'])
+        step = st['step'][1:]
+        L.check(lib.sr3_q_sample_step_f32(L.ptr(st['x0']), L.ptr(st['z']), L.ptr(st['ca']), L.ptr(st['cb']), st['S'], L.ptr(step), B,
+                                          Cc * H * W, L.ptr(st['xt']), self._stream(dev)))
+        self.denoise_fn(st['xt'], None, cond=st['cond'], level_table=st['level'], step_dev=step, out=st['out'], ws=st['ws'], full=True,
+                        t_map=st['tau'] if self.variant == 'ddpm' else None)
+        L.check(lib.sr3_vlb_terms_f32(L.ptr(st['x0']), L.ptr(st['xt']), L.ptr(st['out']), st['out'].shape[1], L.ptr(st['hyb']), st['S'],
+                                      None, L.ptr(st['step']), st['var_mode'], 1 if st['clip'] else 0, B, Cc, H * W, L.ptr(st['vb']),
+                                      L.ptr(st['mse']), L.ptr(st['scratch']), st['scratch_bytes'], self._stream(dev)))
+
+    def _bpd_capture(self, st):
+        """`_capture` for the evaluation step: one eager step on a side stream first, RNG and counter restored, then the capture."""
+        dev = st['x0'].device
+        rng = torch.cuda.get_rng_state(dev)
+        gens = st['gens'] or []
+        gstate = [g.get_state() for g in gens]
+        keep_step = st['step'].clone()
+        g = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._bpd_step(st)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        st['step'].copy_(keep_step)
+        torch.cuda.set_rng_state(rng, dev)
+        for gen, gs in zip(gens, gstate):
+            gen.set_state(gs)
+        for gen in gens:
+            g.register_generator_state(gen)
+        with torch.cuda.graph(g):
+            self._bpd_step(st)
+        st['graph'] = g
+
+    @torch.no_grad()
+    def calc_bpd_loop(self, x_in, *, steps=None, clip_denoised=True, noise_seq=None, item_seeds=None):
+        """The variational bound of the model on a batch, split by timestep (improved-diffusion's calc_bpd_loop): for j = S - 1 .. 0 of
+        the respaced walk (`ancestral_tables`; steps None: all T), x_t ~ q(x_t | x0), one forward in inference mode, and per image the
+        KL of the true posterior against the model's step in bits per dimension -- the discretised log-likelihood at j = 0 -- with the
+        network's own variance (a learned-variance model) or the fixed small one (sigma^2 = beta~).  x_in: the HR batch (unconditional)
+        or {'HR', 'SR'}.  z is drawn as the samplers draw it; `noise_seq[j]` injects step j's, `item_seeds` gives image i its own
+        stream, so its numbers do not depend on the batch it rode in.  One iteration is captured once and replayed (use_graph).
+        Returns device tensors: vb [B, S], x0_mse [B, S], prior_bpd [B] (KL(q(x_S | x0) || N(0, I))), total_bpd [B] = sum_j vb + prior,
+        the row sum taken in double.  Under cond_augment the conditioning image is diffused once, at sample_level.  Not defined here
+        (NotImplementedError): a self-conditioned model, whose step reads its own last x0; tiling."""
+        if self.self_condition is not None:
+            raise NotImplementedError('calc_bpd_loop of a self-conditioned model: every step of this walk starts from a fresh x_t ~ q(x_t | '
+                                      'x0), so there is no last x0 to feed back, and the bound of a model that reads one is not defined '
+                                      'by this loop')
+        if self.tiling is not None:
+            raise NotImplementedError('calc_bpd_loop with tiling: the bound is the whole-image model\'s; evaluate with set_tiling(None)')
+        aug = self.cond_augment
+        dev = self.betas.device
+        if dev.type != 'cuda':
+            raise L.Sr3Error('calc_bpd_loop needs the model on a GPU (set gpu_ids); there is no CPU fallback')
+        hr = x_in['HR'] if isinstance(x_in, dict) else x_in
+        x0 = hr.to(dev, torch.float32).contiguous()
+        cond = x_in['SR'].to(dev, torch.float32).contiguous() if self.conditional else None
+        shape = tuple(x0.shape)
+        if len(shape) != 4 or (cond is not None and tuple(cond.shape) != shape):
+            raise L.Sr3Error('calc_bpd_loop: (B, C, H, W) images are expected, HR and SR of one shape (got %s%s)'
+                             % (shape, '' if cond is None else ' and %s' % (tuple(cond.shape),)))
+        S = self.num_timesteps if steps is None else int(steps)
+        if not 1 <= S <= self.num_timesteps:
+            raise ValueError('calc_bpd_loop: steps must lie in [1, %d] (got %r)' % (self.num_timesteps, steps))
+        B = shape[0]
+        if item_seeds is not None:
+            item_seeds = [int(v) for v in item_seeds]
+            if len(item_seeds) != B:
+                raise L.Sr3Error('calc_bpd_loop: %d item_seeds for a batch of %d' % (len(item_seeds), B))
+            if noise_seq is not None:
+                raise L.Sr3Error('calc_bpd_loop: item_seeds and noise_seq exclude each other')
+        self.denoise_fn.plan.set_geometry(shape[2], shape[3])
+        cond_shape = None if cond is None else shape
+        if cond is not None and aug is not None and aug['level_channel']:
+            cond_shape = (B, shape[1] + 1) + shape[2:]
+        st = self._bpd_state(shape, cond_shape, dev, S, clip_denoised, item_seeds is not None)
+        self.denoise_fn.ensure_derived()
+        lib, stream = L.load(), self._stream(dev)
+        if item_seeds is not None:
+            for g, v in zip(st['gens'], item_seeds):
+                g.manual_seed(v)
+        st['x0'].copy_(x0)
+        if cond is not None:
+            st['cond'][:, :shape[1]].copy_(cond)
+            if aug is not None:
+                self._augment_sampling_cond(st, aug, cond, None)
+        # the prior term: KL(q(x_S | x0) || N(0, I)) from abar of the walk's last step, float64 on the host, rounded once
+        ab = st['abar_last']
+        L.check(lib.sr3_prior_bpd_f32(L.ptr(st['x0']), B, x0[0].numel(), C.c_float(np.sqrt(ab)), C.c_float(1.0 - ab),
+                                      C.c_float(np.log(1.0 - ab)), L.ptr(st['prior']), L.ptr(st['scratch']), st['scratch_bytes'], stream))
+        st['step'].fill_(S - 1)
+        use_graph = self.use_graph and noise_seq is None
+        if use_graph and st['graph'] is None:
+            self._bpd_capture(st)
+        for j in reversed(range(S)):
+            if use_graph:
+                st['graph'].replay()
+                st['replays'] += 1
+            elif noise_seq is not None:
+                st['z'].copy_(noise_seq[j])
+                self._bpd_step(st, draw_noise=False)
+            else:
+                self._bpd_step(st)
+        vb = st['vb'].t().contiguous()
+        total = (vb.double().sum(1) + st['prior'].double()).float()
+        return dict(vb=vb, x0_mse=st['mse'].t().contiguous(), prior_bpd=st['prior'].clone(), total_bpd=total)
+
     # ---- forward process / loss --------------------------------------------------------------------
     def _q_sample_coef(self, x_start, ca, cb, noise):
         out = torch.empty_like(x_start)
@@ -1390,8 +1603,21 @@ class EngineDiffusion(nn.Module):
         level = tstep = None
         lv = self.learned_variance
         hyb_t = None                   # under the key: the drawn step of every image, 0-based, on the schedule's grid
+        ts = self.t_sampler
+        if ts is not None:
+            self.flush_t_sampler()     # (a caller that never read the last step's terms: they enter the history before p is formed)
+            ts_p = ts.probabilities()
         if self.variant == 'sr3':
-            if lv is not None:
+            if lv is not None and ts is not None:
+                # (set_t_sampler refused a plain SR3 model) one step per batch from p, where the reference's single randint stood
+                if gamma is not None:
+                    raise ValueError('p_losses under learned_variance draws gamma on the schedule\'s grid: inject t (1 .. T), not gamma')
+                tt = int(np.random.choice(self.num_timesteps, p=ts_p)) + 1 if t is None else int(t)
+                if not 1 <= tt <= self.num_timesteps:
+                    raise ValueError('p_losses: t must lie in [1, %d] (got %d)' % (self.num_timesteps, tt))
+                gamma = torch.FloatTensor(np.full(b, self.sqrt_alphas_cumprod_prev[tt]))
+                hyb_t = torch.full((b,), tt - 1, dtype=torch.long, device=dev)
+            elif lv is not None:
                 # q(x_{t-1} | x_t, x0) exists on the grid only: gamma is the level the sampler feeds at step t, not a uniform draw
                 # between two grid values -- the one change to the draws, under the key alone
                 if gamma is not None:
@@ -1410,11 +1636,14 @@ class EngineDiffusion(nn.Module):
             ca, cb = g, (1 - g ** 2).sqrt()
             level = g
         else:
-            if t is None:
+            if t is None and ts is not None:      # per image from p (torch's generator on the device, as the uniform draw it replaces)
+                t = torch.multinomial(torch.tensor(ts_p, dtype=torch.float64, device=dev), b, replacement=True)
+            elif t is None:
                 t = torch.randint(0, self.num_timesteps, (b,), device=dev).long()
             tstep = t.long().to(dev)
             ca, cb = self.sqrt_alphas_cumprod[tstep], self.sqrt_one_minus_alphas_cumprod[tstep]
-            hyb_t = tstep if lv is not None else None
+            hyb_t = tstep if lv is not None or ts is not None else None
+
         if noise is None:
             noise = torch.randn_like(x_start)
         cond = x_in['SR'].contiguous() if self.conditional else None
@@ -1436,7 +1665,7 @@ class EngineDiffusion(nn.Module):
             cond = buf
         if self_cond is not None or self.self_condition is not None:
             cond = self._self_condition_input(x_start, cond, noise, ca, cb, level, tstep, gamma, self_cond)
-        if lv is None:
+        if lv is None and ts is None:
             return un.train_step(x_start, cond, noise.contiguous(), ca.contiguous(), cb.contiguous(), level, tstep,
                                  grad_scale=1.0 / float(b * c * h * w), drop_seed=drop_seed,
                                  objective=self._train_objective(tstep, gamma, dev))
@@ -1446,10 +1675,28 @@ class EngineDiffusion(nn.Module):
             tabs = ancestral_tables(self._alphas_cumprod64, self.num_timesteps, prediction=self.prediction)
             self._hyb_table = torch.tensor(hybrid_step_scalars(tabs, np.arange(self.num_timesteps)), dtype=torch.float32).to(dev)
         scal = self._hyb_table[hyb_t].contiguous()
+        objective = self._train_objective(tstep, gamma, dev)
+        kw = {}
+        if ts is not None:
+            # the loss of a step drawn with p_t is weighted by 1 / (T p_t): into the per-image weight table, which is made here where
+            # the objective had none (target z, weight 1, the configured loss)
+            wt = torch.tensor(ts.weights(np.arange(ts.T), ts_p), dtype=torch.float32).to(dev)[hyb_t].contiguous()
+            if objective is None or objective[0] is None:
+                kind, delta = (-1, 0.0) if objective is None else objective[3:]
+                objective = (torch.ones(b, device=dev), torch.zeros(b, device=dev), wt, kind, delta)
+            else:
+                objective = (objective[0], objective[1], (objective[2] * wt).contiguous()) + tuple(objective[3:])
+            kw['per_image'] = scal
+        if lv is not None:
+            kw['hybrid'] = (scal, lv['lambda'])
+            if ts is not None:             # ... and into L_vlb's own table: the objective's `weight` reaches L_simple alone
+                kw['vlb_weight'] = wt
         loss = un.train_step(x_start, cond, noise.contiguous(), ca.contiguous(), cb.contiguous(), level, tstep,
-                             grad_scale=1.0 / float(b * c * h * w), drop_seed=drop_seed,
-                             objective=self._train_objective(tstep, gamma, dev), hybrid=(scal, lv['lambda']))
-        self.last_vlb = un.last_vlb / float(b * c * h * w)      # bits per dimension (the sum is over every rank's batch: see model.py)
+                             grad_scale=1.0 / float(b * c * h * w), drop_seed=drop_seed, objective=objective, **kw)
+        if lv is not None:
+            self.last_vlb = un.last_vlb / float(b * c * h * w)      # bits per dimension (the sum is over every rank's batch: see model.py)
+        if ts is not None:
+            self._t_pending = (hyb_t, un.last_per_image)
         return loss
 
     def _cond_augment_input(self, cond, keep, cond_level, cond_noise):

@@ -118,6 +118,12 @@ SIGNATURES = {
                                _I, _P, _P, _I, _P, _P, _P, _I, C.c_float, _P]),
     'sr3_train_step_ex2': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, C.c_float, C.c_float, C.c_uint,
                                 _I, _P, _P, _I, _P, _P, _P, _I, C.c_float, _P, C.c_float, _P, _P]),
+    'sr3_train_step_ex3': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, C.c_float, C.c_float, C.c_uint,
+                                _I, _P, _P, _I, _P, _P, _P, _I, C.c_float, _P, C.c_float, _P, _P, _P, _Z, _P, _P]),
+    'sr3_vlb_terms_partials_bytes': (_Z, [_I]),
+    'sr3_vlb_terms_f32': (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    'sr3_prior_bpd_f32': (_I, [_P, _I, _I, C.c_float, C.c_float, C.c_float, _P, _P, _Z, _P]),
+    'sr3_q_sample_step_f32': (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _P, _P]),
     'sr3_hybrid_loss_grad_scratch_bytes': (_Z, []),
     'sr3_hybrid_loss_grad_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_float, _I, _I, _I, _I, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
     'sr3_loss_grad_scratch_bytes': (_Z, []),

@@ -281,12 +281,18 @@ class EngineUNet(nn.Module):
                               hist=hist)
 
     # ---- training step (forward + backward inside the engine) ------------------------------------
-    def train_step(self, hr, cond, z, ca, cb, level, tstep, grad_scale, drop_seed=None, objective=None, hybrid=None):
+    def train_step(self, hr, cond, z, ca, cb, level, tstep, grad_scale, drop_seed=None, objective=None, hybrid=None, per_image=None,
+                   vlb_weight=None):
         """One fused forward + backward: returns the sum-reduced loss (0-dim tensor, summed over all data-parallel
         ranks) and leaves d(loss * grad_scale)/d params -- rank-summed -- in `grad_arena`.  `objective`: None (the network predicts
         z, unweighted, the plan's loss) or (tgt_z, tgt_x0, weight, loss_kind, huber_delta) of sr3_train_step_ex, the first three
         [B] device tensors or all None.  `hybrid` (a learned-variance network): (step_scalars [B, 8] fp32 on the device, lambda) of
-        sr3_train_step_ex2 -- the loss is then L_simple + lambda L_vlb, and `last_vlb` holds the sum of L_vlb in bits (rank-summed)."""
+        sr3_train_step_ex2 -- the loss is then L_simple + lambda L_vlb, and `last_vlb` holds the sum of L_vlb in bits (rank-summed).
+        `per_image` (the loss-aware timestep sampler): the step_scalars [B, 8] of the drawn steps -- hybrid's own where both are given --
+        sends the step through sr3_train_step_ex3, and `last_per_image` holds this rank's [B, 2] = {vb in bits / dim, x0 mse}; a pair
+        (step_scalars, out) writes them into the caller's [B, 2] fp32 tensor.  `vlb_weight` (with per_image and hybrid; [B] fp32 on
+        the device): per image, lambda * vlb_weight[b] weights L_vlb -- the importance weight of a step drawn by its loss, which the
+        objective's `weight` carries to L_simple alone."""
         p_drop = self.dropout if self.training else 0.0
         if drop_seed is None:          # a fresh mask every step, drawn from torch's CPU generator
             drop_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_drop > 0 else 0
@@ -311,6 +317,13 @@ class EngineUNet(nn.Module):
         if hybrid is not None:
             vlb = torch.zeros(1, device=dev)
             kw['hybrid'] = (hybrid[0], float(hybrid[1]), vlb)
+        self.last_per_image = None
+        if per_image is not None:
+            kw['per_image'] = tuple(per_image) if isinstance(per_image, (tuple, list)) else (per_image, torch.empty((hr.shape[0], 2), device=dev))
+            if vlb_weight is not None:
+                kw['per_image'] += (vlb_weight,)
+        elif vlb_weight is not None:
+            raise L.Sr3Error('training: vlb_weight goes with per_image (sr3_train_step_ex3)')
         self._engine_train_step(hr, cond, z, ca, cb, level, tstep, grad_scale, p_drop, drop_seed, marks, loss, **kw)
         sums = [loss] if hybrid is None else [loss, vlb]
         if dp:
@@ -321,6 +334,8 @@ class EngineUNet(nn.Module):
                     tdist.all_reduce(t, op=tdist.ReduceOp.SUM)
         if hybrid is not None:
             self.last_vlb = vlb[0]
+        if per_image is not None:
+            self.last_per_image = kw['per_image'][1]
         return loss[0]
 
     def dp_reducing(self):
@@ -346,7 +361,7 @@ class EngineUNet(nn.Module):
             red.dist.all_reduce(arena[lo:hi], op=red.dist.ReduceOp.SUM)
 
     def _engine_train_step(self, hr, cond, z, ca, cb, level, tstep, grad_scale, p_drop, drop_seed, marks, loss, objective=None,
-                           hybrid=None):
+                           hybrid=None, per_image=None):
         """The sr3_train_step_ex call itself (q_sample -> UNet forward -> loss -> backward, `marks` = the gradient-ready
         events of the data-parallel buckets); objective None is sr3_train_step's (NULL, NULL, NULL, -1, 0)."""
         import ctypes as C
@@ -390,6 +405,28 @@ class EngineUNet(nn.Module):
         for t in (tgt_z, tgt_x0, weight):
             if t is not None and (t.device != dev or t.dtype != torch.float32 or t.numel() != B or not t.is_contiguous()):
                 raise L.Sr3Error('training: tgt_z / tgt_x0 / weight must be contiguous fp32 tensors of %d elements on %s' % (B, dev))
+        if per_image is not None:      # the step's per-image terms of the bound too: sr3_train_step_ex3 (with or without a variance head)
+            scal, out, vw = (tuple(per_image) + (None,))[:3]
+            if tuple(out.shape) != (B, 2) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+                raise L.Sr3Error('training: per_image_out must be a contiguous fp32 [%d, 2] tensor on %s' % (B, dev))
+            if vw is not None and (hybrid is None or vw.device != dev or vw.dtype != torch.float32 or vw.numel() != B or not vw.is_contiguous()):
+                raise L.Sr3Error('training: vlb_weight goes with hybrid and must be a contiguous fp32 tensor of %d elements on %s' % (B, dev))
+            lam, vlb = (0.0, None) if hybrid is None else hybrid[1:]
+            if scal.device != dev or scal.dtype != torch.float32 or tuple(scal.shape) != (B, 8) or not scal.is_contiguous():
+                raise L.Sr3Error('training: step_scalars must be a contiguous fp32 [%d, 8] tensor on %s' % (B, dev))
+            if hybrid is not None and hybrid[0] is not scal:
+                raise L.Sr3Error('training: per_image and hybrid must share one step_scalars tensor')
+            nb = int(plan.lib.sr3_vlb_terms_partials_bytes(B))
+            sc = getattr(self, '_vlb_scratch', None)
+            if sc is None or sc.numel() != nb // 8 or sc.device != dev:
+                sc = self._vlb_scratch = torch.empty(nb // 8, dtype=torch.float64, device=dev)
+            L.check(plan.lib.sr3_train_step_ex3(plan.handle, L.ptr(hr), L.ptr(cond), cc, L.ptr(z), L.ptr(ca), L.ptr(cb),
+                                                L.ptr(level), L.ptr(tstep), L.ptr(self.freq), L.ptr(self.arena.data),
+                                                L.ptr(self.grad_arena), L.ptr(wsv), need, L.ptr(loss), C.c_float(grad_scale),
+                                                C.c_float(p_drop), C.c_uint(drop_seed & 0xFFFFFFFF), n_marks, offs, evs, B,
+                                                L.ptr(tgt_z), L.ptr(tgt_x0), L.ptr(weight), int(kind), C.c_float(delta),
+                                                L.ptr(scal), C.c_float(lam), L.ptr(vlb), L.ptr(out), L.ptr(sc), nb, L.ptr(vw), stream))
+            return
         if hybrid is not None:         # a learned-variance network: the hybrid loss, sr3_train_step_ex2
             scal, lam, vlb = hybrid
             if scal.device != dev or scal.dtype != torch.float32 or tuple(scal.shape) != (B, 8) or not scal.is_contiguous():

@@ -714,6 +714,78 @@ int sr3_hybrid_loss_grad_f32(const float* z_nchw, const float* out_nchw, const f
                              float scale, float* g_nhwc8, float* loss_sum_out, float* vlb_sum_out,
                              void* scratch /* sr3_hybrid_loss_grad_scratch_bytes() */, void* stream);
 
+/* ---- the variational bound by timestep (engine extension; Nichol & Dhariwal 2021) ------------------------
+ * Per-image terms of the bound from (x0, x_t, the network's output, the step's scalars): what an evaluation walk adds up to bits per
+ * dimension, and what a loss-aware timestep sampler reads back from a training step.
+ *   x0, x_t [batch, channels, pixels]; out [batch, out_channels, pixels]: the prediction planes, then (var_mode 0) the variance planes v
+ *   table [table_rows, 8]: rows {a, b, c1, c2, log beta, log beta~ (clipped), last, 0} (sr3_train_step_ex2's step_scalars layout)
+ *   the row of image b: table[rows_per_image[b]] (the training form), or table[j] for every image with j = step2_dev[1] (the evaluation
+ *   form); exactly one of the two is given.  A row index outside [0, table_rows) gives that image NaN (rows_per_image) or writes no
+ *   output (step2_dev); nothing is read or written out of bounds.
+ *   var_mode 0: learned, out_channels = 2 * channels; 1: fixed small, v = -1 (log sigma^2 = log beta~); 2: fixed large, v = +1
+ *   (log sigma^2 = log beta); out_channels = channels for 1 and 2.
+ * Per element, all fp32, sr3_train_step_ex2's term in the same operation order:
+ *   x0^ = a x_t - b out_c ; clamp(-1, 1) if clip_denoised ; f = (v + 1) / 2 ; lv = f log beta + (1 - f) log beta~
+ *   last == 0:  vlb = (-1 + lv - log beta~ + exp(log beta~ - lv) + (c1 (x0 - x0^))^2 exp(-lv)) / 2 / ln 2
+ *   last != 0:  vlb = -log2 max(mass, 1e-12), the mass of N(c1 x0^ + c2 x_t, e^lv) on the bin x0 +- 1/255 (open below -0.999 and above
+ *               0.999), Phi(u) = (1 + tanh(sqrt(2 / pi) (u + 0.044715 u^3))) / 2
+ *   vb_out[b] = mean over channels * pixels of vlb (bits / dim) ; x0_mse_out[b] = mean of (x0 - x0^)^2.
+ * With step2_dev both outputs are [table_rows, batch] and row j is written; the second launch then sets step2_dev[1] = j - 1, so the
+ * pair drives a captured loop.  step2_dev is the loops' counter pair: slot 1 is the counter; slot 0, the scratch copy of the steps that
+ * begin with a copy launch (sr3_tiled_step), is neither read nor written here -- every reader of the step runs before the second
+ * launch and reads slot 1.
+ * Sums in double in a fixed order: 16 block partials per image into `scratch` (a thread adds its elements in index order, a block
+ * folds its threads in a fixed tree), then one block adds each image's partials in index order.  No atomics: the same bits every run.
+ * channels * pixels % 4 == 0 with 16-byte aligned image pointers reads 16 bytes per access, anything else one float: the same bits.
+ * scratch: sr3_vlb_terms_partials_bytes(batch) bytes, 8-byte aligned; the buffer contract at sr3_workspace_bytes holds (exactly this
+ * size, prior contents irrelevant).  Two launches, no host synchronisation: capturable.  Checked in this order, nothing is launched
+ * on a refusal and the message names the argument: a NULL required pointer (SR3_E_BADARG); both or neither of rows_per_image /
+ * step2_dev (SR3_E_BADARG); a non-positive size, var_mode outside 0..2, out_channels not matching var_mode (SR3_E_BADARG);
+ * batch * out_channels * pixels >= 2^31 (SR3_E_UNSUPPORTED); scratch_bytes too small (SR3_E_NOMEM); an output, the scratch or
+ * step2_dev overlapping another argument (SR3_E_BADARG); a misaligned scratch (SR3_E_ALIGN). */
+size_t sr3_vlb_terms_partials_bytes(int batch);
+int sr3_vlb_terms_f32(const float* x0, const float* x_t, const float* out, int out_channels, const float* table, int table_rows,
+                      const int* rows_per_image, int* step2_dev, int var_mode, int clip_denoised, int batch, int channels, int pixels,
+                      float* vb_out, float* x0_mse_out, void* scratch /* sr3_vlb_terms_partials_bytes(batch) */, size_t scratch_bytes,
+                      void* stream);
+
+/* The prior term of the bound: out[b] = mean over elems_per_image of KL(N(sqrt_abar x0, var) || N(0, 1)) / ln 2
+ *   = (-1 - log_var + var + (sqrt_abar x0)^2) / 2 / ln 2 per element in fp32, with abar of the walk's last step: sqrt_abar = sqrt(abar),
+ * var = 1 - abar, log_var = log(1 - abar), evaluated by the host in float64 and rounded once.  Reduction, scratch
+ * (sr3_vlb_terms_partials_bytes(batch)), access widths and the order of the checks as sr3_vlb_terms_f32's; a scalar that is not finite
+ * is SR3_E_BADARG. */
+int sr3_prior_bpd_f32(const float* x0, int batch, int elems_per_image, float sqrt_abar, float var, float log_var, float* out,
+                      void* scratch, size_t scratch_bytes, void* stream);
+
+/* sr3_q_sample indexed by the device step counter, so that a captured loop can noise x0 afresh each step:
+ *   out = tab_ca[j] * x0 + tab_cb[j] * z,  j = step_dev[0]
+ * products and sum rounded separately: sr3_q_sample's bits with ca[b] = tab_ca[j], cb[b] = tab_cb[j].  j outside [0, table_rows)
+ * writes nothing.  One launch; batch * elems_per_image % 4 == 0 with 16-byte aligned pointers takes four values per thread, anything
+ * else one, the same bits.  Checks in order: NULL pointer, non-positive size (SR3_E_BADARG); batch * elems_per_image >= 2^31
+ * (SR3_E_UNSUPPORTED); out overlapping an input (SR3_E_BADARG). */
+int sr3_q_sample_step_f32(const float* x0, const float* z, const float* tab_ca, const float* tab_cb, int table_rows, const int* step_dev,
+                          int batch, int elems_per_image, float* out, void* stream);
+
+/* sr3_train_step_ex2 that also returns the step's per-image terms of the bound: per_image_out [batch, 2] = {vb, x0_mse} of
+ * sr3_vlb_terms_f32 on the step's own x_noisy and output (clip_denoised 0, image b on row b of step_scalars), one launch pair behind the
+ * loss kernel; scratch: sr3_vlb_terms_partials_bytes(batch) bytes, 8-byte aligned.  Every launch of sr3_train_step_ex2 runs unchanged,
+ * so loss, vlb sum and gradients are its bits.  It also takes a plan WITHOUT a variance head: then the step is sr3_train_step_ex's
+ * (vlb_lambda and vlb_sum_out are not read) and the terms are var_mode 1's; step_scalars is required either way.  per_image_out NULL:
+ * sr3_train_step_ex2 / sr3_train_step_ex, the same launches.  vlb_weight (`batch` floats on the device, or NULL = 1; read with a
+ * variance head only): per image, vlb_lambda * vlb_weight[b] stands where vlb_lambda does -- *loss_sum_out = sum weight[b] rho(d) +
+ * vlb_lambda sum_b vlb_weight[b] vlb_b, the variance rows receive vlb_lambda vlb_weight[b] grad_scale d vlb / d v; *vlb_sum_out stays
+ * the plain sum.  What an importance-sampled step needs: `weight` reaches L_simple alone, so 1 / (T p_t) goes into both tables.  NULL
+ * passes the kernel the same arguments as sr3_train_step_ex2 does: the same operations, the same bits.  SR3_E_BADARG besides theirs: scratch NULL with per_image_out given,
+ * per_image_out or scratch overlapping each other or the workspace; SR3_E_NOMEM: scratch_bytes too small; SR3_E_ALIGN: scratch. */
+int sr3_train_step_ex3(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels,
+                       const float* z_nchw, const float* q_ca, const float* q_cb, const float* noise_level,
+                       const int64_t* timestep, const float* freq, const float* params, float* grads,
+                       void* workspace, size_t workspace_bytes, float* loss_sum_out, float grad_scale, float dropout_p,
+                       unsigned dropout_seed, int n_marks, const size_t* mark_offsets, void* const* mark_events,
+                       int batch, const float* tgt_z, const float* tgt_x0, const float* weight, int loss_kind,
+                       float huber_delta, const float* step_scalars, float vlb_lambda, float* vlb_sum_out,
+                       float* per_image_out, void* scratch, size_t scratch_bytes, const float* vlb_weight, void* stream);
+
 /* torch.optim.Adam step (model/model.py:39-40,55; defaults beta 0.9/0.999, eps 1e-8, no weight decay)
  * fused over the whole arena; `step` is the 1-based step count for the bias corrections.
  * SR3_E_BADARG (nothing is launched, the message names the argument): a NULL params / grads / exp_avg / exp_avg_sq,
