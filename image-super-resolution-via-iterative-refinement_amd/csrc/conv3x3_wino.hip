@@ -254,7 +254,8 @@ int wino_transform_weights(const float* w_ohwi, int Cout, int Cin, float* ufrag,
 // hh + hm + mh + mm + hl + lh on v_mfma_f32_32x32x16_bf16 with fp32 accumulation -- the dropped terms are <= 2^-24 of a product
 // (fp32-class results, conv3x3_halo.hip's MODE 1 applied to the Winograd domain): U comes pre-split from the derived buffer
 // (k_wino_weights_split), V is split in registers right after the transform.  Plan option `wino_split`; gated by tests.
-template <int DBG, bool DROP, bool NB4, bool SPLIT>
+// WT (plan option store_wt, bit 1; the four-image split form the default plans run): the epilogue's 16-byte stores written through L2
+template <int DBG, bool DROP, bool NB4, bool SPLIT, bool WT = false>
 __global__ __launch_bounds__(WNT, 1) void k_conv3x3_wino(const ConvParams p, const WinoGeom g,
                                                          const float* __restrict__ ufrag) {
   using GE = WGeo<NB4>;
@@ -628,6 +629,7 @@ __global__ __launch_bounds__(WNT, 1) void k_conv3x3_wino(const ConvParams p, con
   const size_t Mtot = (size_t)p.B * H * W;
   float* dst = direct ? p.out : p.partial + (size_t)blockIdx.y * Mtot * p.Cout;
   if (DBG & 64) dst = p.out;
+  const WtDst wdst = wt_dst(dst, Mtot * p.Cout * sizeof(float), WT);
 
   for (;;) {
     // ================================ prologue ================================
@@ -866,7 +868,8 @@ __global__ __launch_bounds__(WNT, 1) void k_conv3x3_wino(const ConvParams p, con
     // the next tile (the last one re-fetches itself: the loads stay unconditional)
     const bool has_next = vtile + (int)gridDim.x < ntiles;
     if (has_next) vtile += gridDim.x;
-    // this tile's residual, both rounds: 8 loads (absent: a valid dummy address, discarded below)
+    // this tile's residual, both rounds: 8 loads (absent: the one-line dummy, discarded below; -DSR3_WINO_PREREAD, A/B builds: this thread's
+    // part of the output it is about to write, as before)
     f32x4 addv[2][4];
 #pragma unroll
     for (int nblk = 0; nblk < 2; ++nblk) {
@@ -875,7 +878,11 @@ __global__ __launch_bounds__(WNT, 1) void k_conv3x3_wino(const ConvParams p, con
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const size_t pix = pix0 + 2 * k;
+#ifdef SR3_WINO_PREREAD
         const float* rp = dst + pix * p.Cout + ne;
+#else
+        const float* rp = dummy;
+#endif
         if (has_res) rp = (ne < p.RC0) ? p.res0 + pix * p.RC0 + ne : p.res1 + pix * p.RC1 + (ne - p.RC0);
         addv[nblk][k] = *reinterpret_cast<const f32x4*>(rp);
       }
@@ -977,7 +984,7 @@ __global__ __launch_bounds__(WNT, 1) void k_conv3x3_wino(const ConvParams p, con
               for (int c = 0; c < 4; ++c) { const double dv = (double)v[c]; s1[nblk][c] += dv; s2[nblk][c] += dv * dv; }
             }
           }
-          if (nok) *reinterpret_cast<f32x4*>(dst + (pix0 + 2 * k) * p.Cout + n) = v;
+          if (nok) store16(wdst, (pix0 + 2 * k) * p.Cout + n, v);
         }
       }
       if (nblk == 0) store_consts(cst + (par ^ 1) * W_CST_F);      // ... and the constants go to LDS (the other parity)
@@ -1107,6 +1114,11 @@ int conv3x3_wino_forward(const ConvParams& p, const float* ufrag, hipStream_t st
   switch (dbg) {
     case 0:
       if (p.wino_split && p.drop_thresh != 0) { SR3_WINO_LAUNCH4(0, true, false, true) }
+      else if (p.wino_split && g.NB != 1 && (p.store_wt & STORE_WT_WINO)) {
+        static std::atomic<uint64_t> done{0};
+        if (int rc = ensure_max_lds(reinterpret_cast<const void*>(k_conv3x3_wino<0, false, true, true, true>), W_SMEM, done)) return rc;
+        hipLaunchKernelGGL((k_conv3x3_wino<0, false, true, true, true>), grid, dim3(WNT), W_SMEM, st, p, g, ufrag);
+      }
       else if (p.wino_split && g.NB != 1) { SR3_WINO_LAUNCH4(0, false, true, true) }
       else if (p.wino_split) { SR3_WINO_LAUNCH4(0, false, false, true) }
       else if (p.drop_thresh != 0) { SR3_WINO_LAUNCH2(0, true) } else { SR3_WINO_LAUNCH2(0, false) }

@@ -76,7 +76,9 @@ __device__ __forceinline__ float silu_v(float v) {      // (conv3x3_wino.hip: si
 // B^T d B (d2 - d1) are exactly zero.  Seven of the sixteen positions multiply a zero operand: waves 0, 1 and 3 run rows 0, 1 and 3 (three
 // MFMA groups per chunk, three U slots, 96 accumulators), wave 2 stages, keeps the barriers and stores its share of the epilogue, and
 // nobody reads its exchange plane.  The additions that remain keep their order: same bits as the sixteen-position loop (finite filters).
-template <int DBG, bool RAGGED = false, bool UP = false>
+// WT (plan option store_wt, bit 0): the epilogue's 16-byte stores -- outputs and split-K slabs -- are written through L2 (sr3_common.h: store16).
+// A template parameter, not a branch: a wave-uniform branch around every store cost the step more than a third of what the stores save.
+template <int DBG, bool RAGGED = false, bool UP = false, bool WT = false>
 __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, const WinoGeom g, const __bf16* __restrict__ ufrag) {
   extern __shared__ f32x4 smem_w2[];
   float* smem = reinterpret_cast<float*>(smem_w2);
@@ -349,6 +351,7 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
   const bool has_res = direct && p.res0 != nullptr;
   const size_t Mtot = (size_t)p.B * H * W;
   float* dst = direct ? p.out : p.partial + (size_t)blockIdx.y * Mtot * p.Cout;
+  const WtDst wdst = wt_dst(dst, Mtot * p.Cout * sizeof(float), WT);
 
   // ---- first tile: constants, raw chunks 0 and 1 ------------------------------------------------------------------
   int vtile = blockIdx.x;
@@ -493,7 +496,8 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
     auto pix_ok = [&](int k) { return !RAGGED || ((pmask >> k) & 1) != 0; };
     const bool has_next = vtile + (int)gridDim.x < ntiles;
     if (has_next) vtile += gridDim.x;
-    // this tile's residual, both rounds: 8 loads (absent: a valid dummy address, discarded below)
+    // this tile's residual, both rounds: 8 loads (absent: the one-line dummy, discarded below; -DSR3_WINO_PREREAD, A/B builds: this thread's
+    // part of the output it is about to write, as before -- a sweep of the whole output or slab through HBM for nothing)
     f32x4 addv[2][4];
 #pragma unroll
     for (int nblk = 0; nblk < 2; ++nblk) {
@@ -502,7 +506,11 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const size_t pix = pix_ok(k) ? pix0 + 2 * k : 0;           // (a pixel that does not exist: pixel 0, discarded below)
+#ifdef SR3_WINO_PREREAD
         const float* rp = dst + pix * p.Cout + ne;
+#else
+        const float* rp = dummy;
+#endif
         if (has_res) rp = (ne < p.RC0) ? p.res0 + pix * p.RC0 + ne : p.res1 + pix * p.RC1 + (ne - p.RC0);
         addv[nblk][k] = *reinterpret_cast<const f32x4*>(rp);
       }
@@ -589,7 +597,7 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
               for (int c = 0; c < 4; ++c) { const double dv = (double)v[c]; s1[nblk][c] += dv; s2[nblk][c] += dv * dv; }
             }
           }
-          if (nok && pix_ok(k)) *reinterpret_cast<f32x4*>(dst + (pix0 + 2 * k) * p.Cout + n) = v;
+          if (nok && pix_ok(k)) store16(wdst, (pix0 + 2 * k) * p.Cout + n, v);
         }
       }
       if (nblk == 0) store_consts(cst + (par ^ 1) * VCST_F);      // ... and the constants go to LDS (the other parity)
@@ -663,12 +671,13 @@ int conv3x3_wino2_forward(const ConvParams& p, const WinoGeom& g, const float* u
     if (int rc = ensure_max_lds(reinterpret_cast<const void*>(k_conv3x3_wino2<D>), 100 * 1024, done)) return rc;      \
     hipLaunchKernelGGL((k_conv3x3_wino2<D>), grid, dim3(VNT), lds_bytes, st, p, g, reinterpret_cast<const __bf16*>(ufrag)); \
   }
-#define SR3_W2_LAUNCH_T(R, U)                                                                                         \
+#define SR3_W2_LAUNCH_W(R, U, W)                                                                                      \
   {                                                                                                                   \
     static std::atomic<uint64_t> done{0};                                                                             \
-    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(k_conv3x3_wino2<0, R, U>), 100 * 1024, done)) return rc; \
-    hipLaunchKernelGGL((k_conv3x3_wino2<0, R, U>), grid, dim3(VNT), lds_bytes, st, p, g, reinterpret_cast<const __bf16*>(ufrag)); \
+    if (int rc = ensure_max_lds(reinterpret_cast<const void*>(k_conv3x3_wino2<0, R, U, W>), 100 * 1024, done)) return rc; \
+    hipLaunchKernelGGL((k_conv3x3_wino2<0, R, U, W>), grid, dim3(VNT), lds_bytes, st, p, g, reinterpret_cast<const __bf16*>(ufrag)); \
   }
+#define SR3_W2_LAUNCH_T(R, U) if (p.store_wt & STORE_WT_WINO2) SR3_W2_LAUNCH_W(R, U, true) else SR3_W2_LAUNCH_W(R, U, false)
   // an upsampled source: the nine-position UP instantiation, unless the caller asks for all sixteen (plan option wino_up = 0, ABI tiles
   // 25 / 26) or an ablation build runs (those exist for the sixteen-position loop only)
   const bool up = p.ups == 1 && !p.wino_full && dbg == 0;
@@ -684,7 +693,7 @@ int conv3x3_wino2_forward(const ConvParams& p, const WinoGeom& g, const float* u
     return SR3_OK;
   }
   switch (dbg) {
-    case 0: SR3_W2_LAUNCH(0) break;
+    case 0: SR3_W2_LAUNCH_T(false, false) break;
 #ifdef SR3_WINO_ABLATIONS
     case 1: SR3_W2_LAUNCH(1) break;
     case 4: SR3_W2_LAUNCH(4) break;
@@ -703,6 +712,7 @@ int conv3x3_wino2_forward(const ConvParams& p, const WinoGeom& g, const float* u
   }
 #undef SR3_W2_LAUNCH
 #undef SR3_W2_LAUNCH_T
+#undef SR3_W2_LAUNCH_W
   SR3_LAUNCH_CHECK("k_conv3x3_wino2");
   return SR3_OK;
 }

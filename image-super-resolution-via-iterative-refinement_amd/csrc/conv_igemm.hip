@@ -371,6 +371,7 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const ConvParams p, int r
   const int nq = p.Cout >> 2;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t row0 = (size_t)blockIdx.x * rpb;
+  const WtDst wdst = wt_dst(p.out, M * p.Cout * sizeof(float), (p.store_wt & STORE_WT_REDUCE) != 0);    // plan option store_wt (sr3_common.h)
   for (int q0 = 0; q0 < nq; q0 += 64) {
     const int q = q0 + lane;
     const int n = q * 4;
@@ -397,7 +398,7 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const ConvParams p, int r
           if (n < p.RC0) v += *reinterpret_cast<const f32x4*>(p.res0 + m * p.RC0 + n);
           else v += *reinterpret_cast<const f32x4*>(p.res1 + m * p.RC1 + (n - p.RC0));
         }
-        *reinterpret_cast<f32x4*>(p.out + m * p.Cout + n) = v;
+        store16(wdst, m * p.Cout + n, v);
         if (p.ostat) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) { const double dv = (double)v[e]; s1[e] += dv; s2[e] += dv * dv; }
@@ -654,6 +655,8 @@ int conv_forward(const ConvParams& pin, int tile_cfg, int ksplit, float* scratch
   }
   conv_pick(p, tile_cfg, ksplit);
   p.ksplit = ksplit;
+  // write-through stores are buffer stores with 32-bit offsets: an output, or a set of slabs, of 4 GiB or more keeps plain stores
+  if (!store_wt_fits((size_t)ksplit * p.B * p.Ho * p.Wo * p.Cout * sizeof(float))) p.store_wt = 0;
   if (p.ostat && ksplit == 1 && (tile_cfg < 5 || tile_cfg >= 22)) { set_error("conv: fused output statistics need the halo kernel or split-K"); return SR3_E_UNSUPPORTED; }
   if (p.ostat && ksplit > 1 && splitk_rows_per_block(p, true) == 0) { set_error("conv: Ho*Wo does not allow fused split-K statistics"); return SR3_E_UNSUPPORTED; }
   { static const char* e = getenv("SR3_CONV_DBG"); p.dbg = e ? atoi(e) : 0; }

@@ -854,6 +854,7 @@ int run_forward(sr3_plan* P, bool train, const float* x, const float* cond, int 
         c.res1 = bind<const float>(ws, v.res1);
         c.out = bind<float>(ws, v.out);
         c.ostat = bind<double>(stats, v.ostat);
+        c.store_wt = P->store_wt;
         if (drop && v.has_drop && drop->thresh != 0) {
           c.drop_seed = drop_layer_seed(drop->seed, v.drop_key); c.drop_thresh = drop->thresh; c.drop_scale = drop->scale;
         }
@@ -1016,6 +1017,7 @@ double sr3_plan_forward_flops(sr3_plan* plan, int batch) {
   if (build_forward(plan, batch, cond)) return -1;
   return plan->flops;
 }
+int sr3_store_wt_fits(size_t bytes) { return store_wt_fits(bytes) ? 1 : 0; }
 int sr3_plan_set_option(sr3_plan* plan, const char* key, int value) {
   if (!plan || !key) return SR3_E_BADARG;
   int* slot = nullptr;
@@ -1030,6 +1032,10 @@ int sr3_plan_set_option(sr3_plan* plan, const char* key, int value) {
   else if (!strcmp(key, "wino_split8")) slot = &plan->wino_split8;
   else if (!strcmp(key, "wgrad_split")) { const int prev = plan->wgrad_split; plan->wgrad_split = value; return prev; }   // no rebuild (the slabs are sized for both)
   else if (!strcmp(key, "attn_split")) { const int prev = plan->attn_split; plan->attn_split = value; return prev; }   // no rebuild
+  else if (!strcmp(key, "store_wt")) {   // no rebuild (read at launch)
+    if (value < 0 || value > STORE_WT_ALL) { set_error("store_wt %d: a mask of bits 0-2 (0 .. %d)", value, (int)STORE_WT_ALL); return SR3_E_BADARG; }
+    const int prev = plan->store_wt; plan->store_wt = value; return prev;
+  }
   else if (!strcmp(key, "attn_long")) slot = &plan->attn_long;
   else if (!strcmp(key, "gemm_split")) slot = &plan->gemm_split;
   else if (!strcmp(key, "gemm_wpre")) slot = &plan->gemm_wpre;

@@ -218,6 +218,9 @@ struct sr3_plan {
                              // (wino_ragged_wins, plan.hip) says so; 0: they fall back to the general kernels (A/B knob)
   int wino_up = 1;           // Upsample's conv (ups = 1) on the two-workgroup Winograd kernel: its UP instantiation, which skips the seven of the sixteen
                              // positions whose operand is exactly zero on a nearest x2 map (same bits); 0: all sixteen (tile_cfg 25 / 26; A/B knob)
+  int store_wt = 3;          // STORE_WT_* bits (sr3_common.h), one per kernel family: its 16-byte epilogue stores are written through L2 (sc1), so the
+                             // kernel boundary behind it has no dirty lines to write back.  Same bits under every value; read at launch, no rebuild;
+                             // 0 = plain stores everywhere.  Default: the families that measured faster (profiles/store_wt_ab.txt)
   int train_geom = 0;        // training follows the plan's geometry (sr3_plan_set_geometry) too: sr3_train_workspace_bytes / sr3_train_step build the
                              // training plan at plan_height x plan_width.  0: training is refused at any geometry but image_size x image_size.
                              // Off by default ONLY because tests pin that refusal text; at the native geometry both values build the same plan

@@ -192,6 +192,8 @@ __global__ __launch_bounds__(256) void k_rows_fold(const ConvParams p, const Fol
     const int n = a_lo + 4 * tq;
     const size_t M = (size_t)p.B * HW;
     f32x4 cb = {0.f, 0.f, 0.f, 0.f};
+    // REDUCE: the output written through L2 where plan option store_wt says so (sr3_common.h)
+    const WtDst wdst = wt_dst(p.out, M * p.Cout * sizeof(float), REDUCE && (p.store_wt & STORE_WT_REDUCE) != 0);
     if constexpr (REDUCE) {
       if (p.bias) cb += *reinterpret_cast<const f32x4*>(p.bias + n);
       if (p.x2_w && p.x2_bias) cb += *reinterpret_cast<const f32x4*>(p.x2_bias + n);
@@ -214,7 +216,7 @@ __global__ __launch_bounds__(256) void k_rows_fold(const ConvParams p, const Fol
           if (n < p.RC0) v += *reinterpret_cast<const f32x4*>(p.res0 + m * p.RC0 + n);
           else v += *reinterpret_cast<const f32x4*>(p.res1 + m * p.RC1 + (n - p.RC0));
         }
-        *reinterpret_cast<f32x4*>(p.out + m * p.Cout + n) = v;
+        store16(wdst, m * p.Cout + n, v);
       } else {
         v = *reinterpret_cast<const f32x4*>(x + m * C + n);
       }

@@ -70,6 +70,35 @@ __device__ __forceinline__ void mfma_split6(const bf16x8 (&a)[3], const bf16x8 (
   for (int q = 0; q < 6; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[q]], b[PB[q]], acc, 0, 0, 0);
 }
 
+// ---- 16-byte stores of an epilogue, plain or written through L2 (plan option store_wt) ----
+// A plain store leaves its line dirty in the XCD's L2, and the kernel boundary behind it writes those lines back before the next kernel
+// starts; a write-through store (sc1) sends the bytes on while the kernel still runs and leaves nothing to flush.  Only 16-byte stores
+// are written through: narrower sc1 stores cost a fabric write each.  The write-through form is a buffer store (one 32-bit byte offset
+// from a wave-uniform base; the compiler counts it in vmcnt like any other store; `wt` a compile-time constant in the big kernels), so a tensor -- or a set of split-K slabs -- of 4 GiB
+// or more keeps plain stores: store_wt_fits, decided on the host.  Bits of ConvParams::store_wt / plan option store_wt, one per family:
+enum {
+  STORE_WT_WINO2 = 1,      // k_conv3x3_wino2, every instantiation: outputs and split-K slabs
+  STORE_WT_WINO = 2,       // k_conv3x3_wino, the 8-wave kernel: the four-image split-K form of the 8 x 8 maps (what the default plans run): slabs
+  STORE_WT_REDUCE = 4,     // k_rows_fold<true> and k_splitk_reduce: the reduced output
+  STORE_WT_ALL = 7,
+};
+inline bool store_wt_fits(size_t bytes) { return bytes < ((size_t)1 << 32); }
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+struct WtDst {
+  __amdgpu_buffer_rsrc_t rsrc;
+  float* base;
+  bool wt;                 // wave-uniform
+};
+// base: wave-uniform; bytes < 4 GiB when wt (host: store_wt_fits)
+__device__ __forceinline__ WtDst wt_dst(float* base, size_t bytes, bool wt) {
+  return WtDst{__builtin_amdgcn_make_buffer_rsrc(base, 0, wt ? (int)(unsigned)bytes : 0, 0x00020000), base, wt};
+}
+// base[elem .. elem + 3] = v (16-byte aligned)
+__device__ __forceinline__ void store16(const WtDst& d, size_t elem, const f32x4 v) {
+  if (d.wt) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), d.rsrc, (int)(unsigned)(elem * sizeof(float)), 0, /*aux: sc1*/ 16);
+  else *reinterpret_cast<f32x4*>(d.base + elem) = v;
+}
+
 // sigmoid / SiLU of the staging and activation-backward steps: libm expf (1 ulp) and the hardware reciprocal v_rcp_f32
 // (1 ulp).  Measured against float64 autograd at batch 64 (profiles/r04_grad_probe.txt): parameter gradients are within 5e-7
 // of float64 with these, the same as with an IEEE division (-DSR3_EXACT_ACT, A/B builds only) and as stock PyTorch-ROCm.
@@ -199,6 +228,8 @@ struct ConvParams {
                        // keeps them in its derived buffer); null: the kernel splits the weights while it stages them
   int wino_full;       // wino_split 2 / 3 with ups == 1: 1 = all sixteen Winograd positions (tile_cfg 25 / 26 at the ABI; plan option wino_up = 0);
                        // 0: the UP instantiation of conv3x3_wino2.hip, which skips the seven positions whose operand is exactly zero
+  int store_wt;        // STORE_WT_* bits (above): which kernels of this conv write their 16-byte stores through L2; 0: plain stores everywhere.
+                       // Set per launch from the plan option; conv_forward clears the write-through bits where store_wt_fits says no
 };
 
 __device__ __forceinline__ unsigned hash32(unsigned x) {

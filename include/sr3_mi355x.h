@@ -98,9 +98,12 @@ int sr3_plan_op_info(sr3_plan* plan, int batch, int index, sr3_op_info* out);
 int sr3_plan_op_side(sr3_plan* plan, int batch, int index, int* side_id, int* wait_id);
 /* algorithmic FLOPs (contractions only) of one forward for `batch` images */
 double sr3_plan_forward_flops(sr3_plan* plan, int batch);
+/* host predicate of plan option store_wt: may a tensor (or a set of split-K slabs) of `bytes` bytes be written with write-through buffer
+ * stores (32-bit offsets: bytes < 4 GiB)?  1 yes, 0: plain stores. */
+int sr3_store_wt_fits(size_t bytes);
 /* tuning knobs: key in {"fuse_stats", "fuse_res", "tile_cfg", "ksplit", "keep_all", "split_bf16", "winograd",
  * "wino_split", "wino_split8", "wino2", "wino_ragged", "wino_up", "gemm_split", "gemm2", "gemm_s2", "gemm_n64", "fork_side", "gemm_wpre", "gemm_tile", "fold_fuse", "wgrad_split", "attn_split",
- * "attn_long", "train_geom", "loss_l2", "var_channels"};
+ * "attn_long", "store_wt", "train_geom", "loss_l2", "var_channels"};
  * returns previous value.
  * wino_split (default 1): the Winograd convolutions that run on the kernel's one-image tile (maps >= 16x16) use its 3 x bf16
  *   split instantiation: every fp32 operand as x = h + m + l (three bf16 terms, each residual exact in fp32), every product as
@@ -161,6 +164,12 @@ double sr3_plan_forward_flops(sr3_plan* plan, int batch);
  *   of refusing the geometry.  A level the strip kernels hold keeps them: launch list, workspace and output bits are those of
  *   attn_long = 0 there.  attn_split selects the arithmetic as for the strip kernels.  The default is 0 for ONE reason: a test pins the
  *   refusal of a fresh plan at 384 x 384; a later change that rewrites that test can flip it.
+ * store_wt (default 3; a mask, 0 .. 7): which kernels write their 16-byte epilogue stores THROUGH L2 (buffer stores with sc1) instead of
+ *   leaving the lines dirty for the kernel boundary to write back: 1 the two-workgroup Winograd kernel (outputs and split-K slabs),
+ *   2 the 8-wave Winograd kernel, 4 the split-K reduce kernels (k_rows_fold, k_splitk_reduce).  The other 16-byte epilogues of the
+ *   flagship plan do not exist: the plain GEMM and the input conv store 4 bytes per lane, attention 8 at its batch-16 shape.
+ *   Every value gives the same bits; read at launch, no rebuild of the plan.  A
+ *   tensor or slab set of 4 GiB or more keeps plain stores (sr3_store_wt_fits).  What was measured: DESIGN.md section 3.2c.
  * train_geom (default 0; training): sr3_train_workspace_bytes and sr3_train_step follow sr3_plan_set_geometry like the forward does: the
  *   training plan is built for the plan's height x width (hr / cond / z are [B, C, height, width]) and cached by (batch, cond_channels,
  *   height, width).  Its forward picks every conv through the inference planner's rule (the ragged Winograd tile 23 included, for the convs
