@@ -1,5 +1,6 @@
 // Single-head self-attention core of SelfAttention.forward (model/sr3_modules/unet.py:127-139):
-//   S = Q K^T / sqrt(C) ; P = softmax_keys(S) ; O = P V          (n_head == 1, head dim == C)
+//   S = Q K^T / sqrt(C) ; P = softmax_keys(S) ; O = P V          (n_head == 1, head dim == C; more heads: attention_heads.hip, which
+//   runs head widths other than 64 / 32 on the MH instantiations of the kernels below)
 // qkv is the NHWC output of the 1x1 qkv conv: [B][N][3C] with q | k | v along channels
 // (the reference's `.view(b, 1, 3C, h, w).chunk(3, dim=2)`), O is [B][N][C].
 //
@@ -19,9 +20,12 @@
 
 namespace sr3 {
 
-template <int NSTAGE>
+// MH (multi-head, attention_heads.hip's dispatch): C is ONE head's width d and blockIdx.y the (image, head) pair; head h owns
+// channels [3 d h, 3 d (h + 1)) of a qkv row as q | k | v and [d h, d (h + 1)) of an out row, the rows keep the strides of all
+// heads * d channels, and the scale stays sqrt(heads * d).  MH = false compiles to the single-head code as it was.
+template <int NSTAGE, bool MH>
 __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv, int N, int C,
-                                                    float* __restrict__ out) {
+                                                    float* __restrict__ out, int heads) {
   extern __shared__ f32x4 smem_v[];
   float* smem = reinterpret_cast<float*>(smem_v);
   const int Npad = (N + 31) & ~31;
@@ -30,13 +34,14 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
   float* stg = smem + 32 * LDS_S;       // NSTAGE staging buffers
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.y;
+  const int b = MH ? blockIdx.y / heads : blockIdx.y, hd = MH ? blockIdx.y % heads : 0;
+  const int Ct = MH ? C * heads : C;              // channels of an out row
   const int m0 = blockIdx.x * 32;
-  const int rowstride = 3 * C;
-  const float* base = qkv + (size_t)b * N * rowstride;
+  const int rowstride = 3 * Ct;
+  const float* base = qkv + (size_t)b * N * rowstride + (MH ? hd * 3 * C : 0);
   const int kq = tid & 7, lrow = tid >> 3;        // loaders: 8 float4 per 32-channel row
   const int kh = (lane >> 5) * 4;
-  const float sqrt_c = sqrtf((float)C);
+  const float sqrt_c = sqrtf((float)Ct);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 
   // ---------------- phase 1: S = Q K^T / sqrt(C) ----------------
@@ -169,7 +174,7 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int m = m0 + acc_row(r, 4 * (lane >> 5));
-            if (m < N && c < C) out[((size_t)b * N + m) * C + c] = acc[r];
+            if (m < N && c < C) out[((size_t)b * N + m) * Ct + (MH ? hd * C : 0) + c] = acc[r];
             acc[r] = 0.f;
           }
         }
@@ -203,9 +208,11 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
 // gated against float64 in tests/).  A lane's operand is then 8 consecutive k of its row: 32 contiguous bytes of its query / key
 // row (phase 1), 8 probabilities of the strip and 8 keys' worth of its TN channels (phase 3), split in registers; D = 2 groups
 // of 16 k in flight.
-template <int KP, int TN, bool SPLIT>
+// MH: as k_attention's -- C is one head's width, B the number of (image, head) pairs (the XCD mapping keeps a PAIR on one XCD: its K / V
+// are what its workgroups share).
+template <int KP, int TN, bool SPLIT, bool MH>
 __global__ __launch_bounds__(256) void k_attention_v2(const float* __restrict__ qkv, int B, int N, int C, int zsplit,
-                                                       float* __restrict__ out) {
+                                                       float* __restrict__ out, int heads) {
   extern __shared__ f32x4 smem_v[];
   float* S = reinterpret_cast<float*>(smem_v);              // [32][N + 4]
   const int LDS_S = N + 4;
@@ -222,10 +229,13 @@ __global__ __launch_bounds__(256) void k_attention_v2(const float* __restrict__ 
     r = blockIdx.x % per_img;
   }
   const int m0 = (r % qblocks) * 32, zi = r / qblocks;
-  const int rowstride = 3 * C;
-  const float* base = qkv + (size_t)b * N * rowstride;
+  int hd = 0;
+  if constexpr (MH) { hd = b % heads; b /= heads; }
+  const int Ct = MH ? C * heads : C;                        // channels of an out row
+  const int rowstride = 3 * Ct;
+  const float* base = qkv + (size_t)b * N * rowstride + (MH ? hd * 3 * C : 0);
   const int ln = lane & 31, kh = (lane >> 5) * 4;
-  const float sqrt_c = sqrtf((float)C);
+  const float sqrt_c = sqrtf((float)Ct);
   constexpr int D = 4;                                      // operand groups in flight
 
   // ---------------- phase 1 ----------------
@@ -271,7 +281,7 @@ __global__ __launch_bounds__(256) void k_attention_v2(const float* __restrict__ 
           [&](int d, int q) { return *reinterpret_cast<const vec_t*>(vcol + (size_t)(d * GK + q) * rowstride); },
           [&](int g, int q) { return *reinterpret_cast<const vec_t*>(vcol + (size_t)(g * GK) * rowstride + (size_t)q * rowstride); },
           N >> (SPLIT ? 4 : 3), acc);
-      float* orow = out + ((size_t)b * N + m0) * C + c0 + TN * ln;
+      float* orow = out + ((size_t)b * N + m0) * Ct + (MH ? hd * C : 0) + c0 + TN * ln;
 #pragma unroll
       for (int r_ = 0; r_ < 16; ++r_) {
         const int row = acc_row(r_, kh);
@@ -281,7 +291,7 @@ __global__ __launch_bounds__(256) void k_attention_v2(const float* __restrict__ 
 #pragma unroll
           for (int t = 0; t < TN; ++t) o[t] = acc[t][r_];
         }
-        *reinterpret_cast<vec_t*>(orow + (size_t)row * C) = o;
+        *reinterpret_cast<vec_t*>(orow + (size_t)row * Ct) = o;
       }
     }
   }
@@ -289,18 +299,21 @@ __global__ __launch_bounds__(256) void k_attention_v2(const float* __restrict__ 
 
 namespace {
 // k_attention_v2<KP, TN, SPLIT> by (pairs, tn, split): one table, one launcher
-using AttnV2Kernel = decltype(&k_attention_v2<1, 1, false>);
-#define SR3_V2_ROW(KP) \
-  {{k_attention_v2<KP, 1, false>, k_attention_v2<KP, 1, true>}, {k_attention_v2<KP, 2, false>, k_attention_v2<KP, 2, true>}, \
-   {k_attention_v2<KP, 4, false>, k_attention_v2<KP, 4, true>}}
-int launch_attention_v2(bool pairs, int tn, bool split, const float* qkv, int B, int N, int C, int zsplit, float* out, hipStream_t st) {
-  static constexpr AttnV2Kernel kernels[2][3][2] = {SR3_V2_ROW(1), SR3_V2_ROW(2)};
-  static std::atomic<uint64_t> done[2][3][2];
+// (heads > 1: the MH instantiations, C one head's width and B the (image, head) pairs)
+using AttnV2Kernel = decltype(&k_attention_v2<1, 1, false, false>);
+#define SR3_V2_ROW(KP, MH) \
+  {{k_attention_v2<KP, 1, false, MH>, k_attention_v2<KP, 1, true, MH>}, {k_attention_v2<KP, 2, false, MH>, k_attention_v2<KP, 2, true, MH>}, \
+   {k_attention_v2<KP, 4, false, MH>, k_attention_v2<KP, 4, true, MH>}}
+int launch_attention_v2(bool pairs, int tn, bool split, const float* qkv, int B, int N, int C, int zsplit, float* out, hipStream_t st,
+                        int heads = 1) {
+  static constexpr AttnV2Kernel kernels[2][2][3][2] = {{SR3_V2_ROW(1, false), SR3_V2_ROW(2, false)}, {SR3_V2_ROW(1, true), SR3_V2_ROW(2, true)}};
+  static std::atomic<uint64_t> done[2][2][3][2];
   const int ti = tn >> 1;                                   // 1, 2, 4 -> 0, 1, 2
-  const AttnV2Kernel kern = kernels[pairs][ti][split];
+  const bool mh = heads > 1;
+  const AttnV2Kernel kern = kernels[mh][pairs][ti][split];
   const int smem = 32 * (N + 4) * (int)sizeof(float);
-  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern), 160 * 1024, done[pairs][ti][split])) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((N / 32) * B * zsplit)), dim3(256), smem, st, qkv, B, N, C, zsplit, out);
+  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern), 160 * 1024, done[mh][pairs][ti][split])) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((N / 32) * B * zsplit)), dim3(256), smem, st, qkv, B, N, C, zsplit, out, heads);
   SR3_LAUNCH_CHECK("k_attention_v2");
   return SR3_OK;
 }
@@ -318,11 +331,28 @@ bool attention_fits(int N, int C) {
   return attention_v2_fits(N, C) || attention_v1_smem(N, 1) <= 160 * 1024;
 }
 
+namespace {
+// the strip kernels for `heads` heads of C channels each (heads == 1: the single-head instantiations; otherwise B counts (image, head) pairs)
+int attention_strip(const float* qkv, int B, int N, int C, float* out, hipStream_t st, int split, int heads);
+}  // namespace
+
 int attention_forward(const float* qkv, int B, int N, int C, float* out, hipStream_t st, int mode) {
   if (C & 3) { set_error("attention: C %% 4 != 0"); return SR3_E_UNSUPPORTED; }
   if ((double)B * N * 3.0 * C >= 2147483647.0) { set_error("attention: qkv exceeds 2^31 elements"); return SR3_E_UNSUPPORTED; }
   const int split = mode & 1;
   if (mode & 2) return attention_long_forward(qkv, B, N, C, out, st, split != 0);     // the key-blocked kernel, at any N
+  return attention_strip(qkv, B, N, C, out, st, split, 1);
+}
+
+// heads > 1 on the generalised kernels (attention_heads.hip dispatches: its own kernel takes the 64- and 32-channel heads first)
+int attention_forward_strided(const float* qkv, int B, int N, int C, int heads, float* out, hipStream_t st, int mode) {
+  const int d = C / heads;
+  if (mode & 2) return attention_long_forward(qkv, B, N, d, out, st, (mode & 1) != 0, heads);
+  return attention_strip(qkv, B * heads, N, d, out, st, mode & 1, heads);
+}
+
+namespace {
+int attention_strip(const float* qkv, int B, int N, int C, float* out, hipStream_t st, int split, int heads) {
   // the staging-free kernel wherever the shape allows it (SR3_ATTN_V1=1, read once: A/B knob for the profiles)
   static const bool force_v1 = [] { const char* e = getenv("SR3_ATTN_V1"); return e && e[0] == '1'; }();
   if (!force_v1 && attention_v2_fits(N, C)) {
@@ -332,7 +362,7 @@ int attention_forward(const float* qkv, int B, int N, int C, float* out, hipStre
     const int Cz = C / zsplit;
     const int tn = (Cz % 512 == 0) ? 4 : ((Cz % 256 == 0) ? 2 : 1);
     const bool pairs = N / 32 >= 8;                       // two key blocks per wave and round share the Q fragment
-    return launch_attention_v2(pairs, tn, split != 0, qkv, B, N, C, zsplit, out, st);
+    return launch_attention_v2(pairs, tn, split != 0, qkv, B, N, C, zsplit, out, st, heads);
   }
   int nstage = 2;
   size_t smem = attention_v1_smem(N, 2);
@@ -342,13 +372,15 @@ int attention_forward(const float* qkv, int B, int N, int C, float* out, hipStre
   const int npan = (C + 127) / 128;
   int zsplit = 1;
   while (zsplit * 2 <= npan && (long)qblocks * B * zsplit < 256) zsplit *= 2;
-  static std::atomic<uint64_t> attr_done[3];
-  auto kern = nstage == 2 ? k_attention<2> : k_attention<1>;
+  static std::atomic<uint64_t> attr_done[2][3];
+  const bool mh = heads > 1;
+  auto kern = mh ? (nstage == 2 ? k_attention<2, true> : k_attention<1, true>) : (nstage == 2 ? k_attention<2, false> : k_attention<1, false>);
   // the attribute is an upper bound: allow the whole 160 KB LDS once per (instantiation, device)
-  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done[nstage])) return rc;
-  hipLaunchKernelGGL(kern, dim3(qblocks, B, zsplit), dim3(256), smem, st, qkv, N, C, out);
+  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_done[mh][nstage])) return rc;
+  hipLaunchKernelGGL(kern, dim3(qblocks, B, zsplit), dim3(256), smem, st, qkv, N, C, out, heads);
   SR3_LAUNCH_CHECK("k_attention");
   return SR3_OK;
 }
+}  // namespace
 
 }  // namespace sr3

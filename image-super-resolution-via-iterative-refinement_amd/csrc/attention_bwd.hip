@@ -23,10 +23,14 @@
 
 namespace sr3 {
 
-template <int NSTAGE, bool BLOCKED>
+//
+// MH (multi-head; the layout of attention.hip's MH kernels): C is ONE head's width d, blockIdx.y the (image, head) pair; qkv / dqkv
+// rows keep the stride 3 heads d and dout / o_fwd rows heads d, head h at channel 3 d h / d h; the scale stays sqrt(heads d).  A head's
+// dK | dV go to columns [2 d h, 2 d (h + 1)) of its image's slab rows, so the slab total is the single-head one.
+template <int NSTAGE, bool BLOCKED, bool MH>
 __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                         const float* __restrict__ o_fwd, int N, int C, int KB,
-                                                        float* __restrict__ dqkv, float* __restrict__ slab) {
+                                                        float* __restrict__ dqkv, float* __restrict__ slab, int heads) {
   extern __shared__ f32x4 smem_v[];
   float* smem = reinterpret_cast<float*>(smem_v);
   const int LDS_S = (BLOCKED ? KB : ((N + 31) & ~31)) + 4;
@@ -38,15 +42,16 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
   float* stg = smem + 64 * LDS_S;         // staging
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.y;
+  const int b = MH ? blockIdx.y / heads : blockIdx.y, hd = MH ? blockIdx.y % heads : 0;
+  const int Ct = MH ? C * heads : C;      // channels of a dout row
   const int m0 = blockIdx.x * 32;
-  const int rs3 = 3 * C;
-  const float* base = qkv + (size_t)b * N * rs3;
-  const float* dob = dout + (size_t)b * N * C;
-  float* dqb = dqkv + (size_t)b * N * rs3;
+  const int rs3 = 3 * Ct;
+  const float* base = qkv + (size_t)b * N * rs3 + (MH ? hd * 3 * C : 0);
+  const float* dob = dout + (size_t)b * N * Ct + (MH ? hd * C : 0);
+  float* dqb = dqkv + (size_t)b * N * rs3 + (MH ? hd * 3 * C : 0);
   const int kq = tid & 7, lrow = tid >> 3;
   const int kh = (lane >> 5) * 4;
-  const float sqrt_c = sqrtf((float)C);
+  const float sqrt_c = sqrtf((float)Ct);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   constexpr int QKS = (NSTAGE == 2) ? AT_QK_STAGE : 0;
 
@@ -139,8 +144,8 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
     const int m = m0 + row;
     if (m < N) {
       for (int c = sub * 4; c < C; c += 32) {
-        const f32x4 g = *reinterpret_cast<const f32x4*>(dob + (size_t)m * C + c);
-        const f32x4 o = *reinterpret_cast<const f32x4*>(o_fwd + ((size_t)b * N + m) * C + c);
+        const f32x4 g = *reinterpret_cast<const f32x4*>(dob + (size_t)m * Ct + c);
+        const f32x4 o = *reinterpret_cast<const f32x4*>(o_fwd + ((size_t)b * N + m) * Ct + (MH ? hd * C : 0) + c);
         delta += g.x * o.x + g.y * o.y + g.z * o.z + g.w * o.w;
       }
     }
@@ -163,7 +168,7 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
       strip_softmax(P, LDS_S, tid, NK, Npad);
     }
     // ---- B: dP = dO V^T ----
-    strip_gemm(dob, C, base + 2 * C, rs3, D, false);
+    strip_gemm(dob, Ct, base + 2 * C, rs3, D, false);
     // ---- C: dS / sqrt(C) = P o (dP - rowsum(dP o P)) / sqrt(C)  (rows m >= N have dO = 0 => dS = 0) ----
     {
       const int row = tid >> 3, sub = tid & 7;
@@ -263,7 +268,7 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
           const int m = m0 + row;
           const bool ok = m < N && c < C;
           const f32x4 qv = *reinterpret_cast<const f32x4*>(base + (ok ? m * rs3 + c : 0));
-          const f32x4 ov = *reinterpret_cast<const f32x4*>(dob + (ok ? m * C + c : 0));
+          const f32x4 ov = *reinterpret_cast<const f32x4*>(dob + (ok ? m * Ct + c : 0));
           *reinterpret_cast<f32x4*>(&Qt[row * AT_LDV + (tid & 31) * 4]) = ok ? qv : zero;
           *reinterpret_cast<f32x4*>(&Ot[row * AT_LDV + (tid & 31) * 4]) = ok ? ov : zero;
         }
@@ -290,7 +295,7 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
                 const int key = kb + acc_row(r, 4 * (lane >> 5));
                 if (key < NK) {
                   if (slab) {
-                    float* sl = slab + (((size_t)blockIdx.x * gridDim.y + b) * N + (kbase + key)) * (2 * C);
+                    float* sl = slab + (((size_t)blockIdx.x * (MH ? gridDim.y / heads : gridDim.y) + b) * N + (kbase + key)) * (2 * Ct) + (MH ? hd * 2 * C : 0);
                     sl[c] = ak[r];
                     sl[C + c] = av[r];
                   } else {
@@ -308,7 +313,10 @@ __global__ __launch_bounds__(256) void k_attention_bwd(const float* __restrict__
 }
 
 // dK / dV = the query blocks' slabs summed in block order (fixed order: bitwise reproducible); one thread per (b, key, channel quad of 2C)
-__global__ __launch_bounds__(256) void k_attn_dkv_reduce(const float* __restrict__ slab, int nqb, int B, int N, int C, float* __restrict__ dqkv) {
+// MH: C is the full channel count, d one head's width -- slab columns [2 d h, 2 d (h + 1)) are head h's dK | dV, which belong at
+// channel 3 d h + d of the dqkv row (a quad never straddles: d % 4 == 0).
+template <bool MH>
+__global__ __launch_bounds__(256) void k_attn_dkv_reduce(const float* __restrict__ slab, int nqb, int B, int N, int C, float* __restrict__ dqkv, int d) {
   const size_t quads = (size_t)B * N * (2 * C / 4);
   const size_t per = (size_t)B * N * 2 * C;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < quads; i += (size_t)gridDim.x * blockDim.x) {
@@ -316,16 +324,25 @@ __global__ __launch_bounds__(256) void k_attn_dkv_reduce(const float* __restrict
     const int c = (int)(i - row * (2 * C / 4)) * 4;
     f32x4 a = *reinterpret_cast<const f32x4*>(slab + i * 4);
     for (int q = 1; q < nqb; ++q) a += *reinterpret_cast<const f32x4*>(slab + (size_t)q * per + i * 4);
-    *reinterpret_cast<f32x4*>(dqkv + row * (3 * C) + C + c) = a;
+    if constexpr (MH) {
+      const int hd = c / (2 * d);
+      *reinterpret_cast<f32x4*>(dqkv + row * (3 * C) + hd * 3 * d + d + (c - hd * 2 * d)) = a;
+    } else {
+      *reinterpret_cast<f32x4*>(dqkv + row * (3 * C) + C + c) = a;
+    }
   }
 }
 
 size_t attention_backward_scratch_bytes(int B, int N, int C) { return (size_t)((N + 31) / 32) * B * N * 2 * C * sizeof(float); }
 
 int attention_backward(const float* qkv, const float* dout, const float* out_fwd, int B, int N, int C, float* dqkv, hipStream_t st,
-                       float* scratch, size_t scratch_bytes) {
+                       float* scratch, size_t scratch_bytes, int heads) {
   if (C & 3) { set_error("attention_bwd: C %% 4 != 0"); return SR3_E_UNSUPPORTED; }
   if ((double)B * N * 3.0 * C >= 2147483647.0) { set_error("attention_bwd: qkv exceeds 2^31 elements"); return SR3_E_UNSUPPORTED; }
+  if (int rc = attention_heads_check("attention_bwd", C, heads)) return rc;
+  const bool mh = heads > 1;
+  if (mh && !scratch) { set_error("attention_bwd: %d heads need the dK / dV slabs (scratch)", heads); return SR3_E_BADARG; }
+  const int d = C / heads;                 // the kernels' channel count: one head's width
   const size_t lds_max = 160 * 1024;
   const size_t stage2 = 2 * (size_t)(AT_QK_STAGE > AT_V_STAGE ? AT_QK_STAGE : AT_V_STAGE);
   const size_t stage1 = (size_t)(AT_QK_STAGE > 2 * AT_V_STAGE ? AT_QK_STAGE : 2 * AT_V_STAGE);
@@ -345,17 +362,18 @@ int attention_backward(const float* qkv, const float* dout, const float* out_fwd
   const bool slabs = scratch != nullptr && scratch_bytes >= attention_backward_scratch_bytes(B, N, C);
   if (scratch && !slabs) { set_error("attention_bwd: scratch too small for the dK / dV slabs (%zu < %zu)", scratch_bytes, attention_backward_scratch_bytes(B, N, C)); return SR3_E_NOMEM; }
   if (!slabs) SR3_HIP(hipMemsetAsync(dqkv, 0, (size_t)B * N * 3 * C * sizeof(float), st));        // (atomics path only)
-  static std::atomic<uint64_t> attr_done[3];
+  static std::atomic<uint64_t> attr_done[2][3];
   const int which = KB ? 2 : nstage - 1;
-  auto kern = KB ? k_attention_bwd<2, true> : (nstage == 2 ? k_attention_bwd<2, false> : k_attention_bwd<1, false>);
+  auto kern = mh ? (KB ? k_attention_bwd<2, true, true> : (nstage == 2 ? k_attention_bwd<2, false, true> : k_attention_bwd<1, false, true>))
+                 : (KB ? k_attention_bwd<2, true, false> : (nstage == 2 ? k_attention_bwd<2, false, false> : k_attention_bwd<1, false, false>));
   // the attribute is an upper bound: allow the whole LDS once per (instantiation, device)
-  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern), (int)lds_max, attr_done[which])) return rc;
-  hipLaunchKernelGGL(kern, dim3((N + 31) / 32, B), dim3(256), smem, st, qkv, dout, out_fwd, N, C, KB, dqkv, slabs ? scratch : nullptr);
+  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern), (int)lds_max, attr_done[mh][which])) return rc;
+  hipLaunchKernelGGL(kern, dim3((N + 31) / 32, B * heads), dim3(256), smem, st, qkv, dout, out_fwd, N, d, KB, dqkv, slabs ? scratch : nullptr, heads);
   SR3_LAUNCH_CHECK("k_attention_bwd");
   if (slabs) {
     const size_t quads = (size_t)B * N * (2 * C / 4);
     int blocks = (int)std::min<size_t>((quads + 255) / 256, 8192);
-    hipLaunchKernelGGL(k_attn_dkv_reduce, dim3(blocks), dim3(256), 0, st, scratch, (N + 31) / 32, B, N, C, dqkv);
+    hipLaunchKernelGGL(mh ? k_attn_dkv_reduce<true> : k_attn_dkv_reduce<false>, dim3(blocks), dim3(256), 0, st, scratch, (N + 31) / 32, B, N, C, dqkv, d);
     SR3_LAUNCH_CHECK("k_attn_dkv_reduce");
   }
   return SR3_OK;

@@ -1,8 +1,8 @@
-// The loops the attention kernels share (device code only; included by attention.hip, attention_long.hip, attention_bwd.hip).
+// The loops the attention kernels share (device code only; included by attention.hip, attention_long.hip, attention_heads.hip, attention_bwd.hip).
 // A kernel keeps its signature, LDS layout, grid mapping, barriers and epilogue, and composes:
-//   qk_scores + emit_scores   scores of KP 32-key blocks, Q / K fragments straight from global memory   (k_attention_v2, k_attention_long)
-//   pv_accumulate             acc += P_strip V, V fragments straight from global memory                   (k_attention_v2, k_attention_long)
-//   strip_softmax             exact row softmax of a strip, eight lanes per row                           (k_attention, k_attention_v2, k_attention_bwd)
+//   qk_scores + emit_scores   scores of KP 32-key blocks, Q / K fragments straight from global memory   (k_attention_v2, k_attention_long, k_attention_heads)
+//   pv_accumulate             acc += P_strip V, V fragments straight from global memory                   (k_attention_v2, k_attention_long, k_attention_heads)
+//   strip_softmax             exact row softmax of a strip, eight lanes per row                           (k_attention, k_attention_v2, k_attention_heads, k_attention_bwd)
 //   max8 / sum8, acc_row, AtVec<TN>, AT_* staging constants                                               (all)
 // Every function keeps ONE order of additions: kernels that share a function share its bits.
 // The LDS-staged loops of k_attention, k_attention_long_gen and k_attention_bwd are NOT here: no common form keeps the register

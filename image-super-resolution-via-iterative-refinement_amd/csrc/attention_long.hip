@@ -50,20 +50,23 @@ __device__ __forceinline__ void al_chunk_softmax(float* S, float* alpha_s, int t
   if (sub == 0) alpha_s[row] = alpha;
 }
 
-template <int TN, bool SPLIT>
+// MH (both kernels): as k_attention's -- C is one head's width, blockIdx.x / qblocks the (image, head) pair.
+template <int TN, bool SPLIT, bool MH>
 __global__ __launch_bounds__(256, 2) void k_attention_long(const float* __restrict__ qkv, int N, int C, int qblocks,
-                                                            float* __restrict__ out) {
+                                                            float* __restrict__ out, int heads) {
   extern __shared__ f32x4 smem_v[];
   float* S = reinterpret_cast<float*>(smem_v);              // [32][AL_LDS]
   float* alpha_s = S + AL_STRIP;                            // [32] this chunk's rescale factors
   float* l_s = alpha_s + 32;                                // [32] final sums
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.x / qblocks, m0 = (blockIdx.x % qblocks) * 32;
-  const int rowstride = 3 * C;
-  const float* base = qkv + (size_t)b * N * rowstride;
+  const int bh = blockIdx.x / qblocks, m0 = (blockIdx.x % qblocks) * 32;
+  const int b = MH ? bh / heads : bh, hd = MH ? bh % heads : 0;
+  const int Ct = MH ? C * heads : C;                        // channels of an out row
+  const int rowstride = 3 * Ct;
+  const float* base = qkv + (size_t)b * N * rowstride + (MH ? hd * 3 * C : 0);
   const int ln = lane & 31, kh = (lane >> 5) * 4;
   const int koff = SPLIT ? (lane >> 5) * 8 : kh;            // first k of this lane's operand fragments
-  const float sqrt_c = sqrtf((float)C);
+  const float sqrt_c = sqrtf((float)Ct);
   constexpr int KP = 2;                                     // key blocks per wave and round (they share the Q fragment)
   constexpr int GK = SPLIT ? 16 : 8;                        // keys per operand group of phase 3
   typedef typename AtVec<TN>::type vec_t;
@@ -122,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_long(const float* __restri
   // ---------------- epilogue: O = acc / l ----------------
   if ((tid & 7) == 0) l_s[tid >> 3] = l_run;
   __syncthreads();
-  float* orow = out + ((size_t)b * N + m0) * C + c0 + TN * ln;
+  float* orow = out + ((size_t)b * N + m0) * Ct + (MH ? hd * C : 0) + c0 + TN * ln;
 #pragma unroll
   for (int r_ = 0; r_ < 16; ++r_) {
     const int row = acc_row(r_, kh);
@@ -133,7 +136,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_long(const float* __restri
 #pragma unroll
       for (int t = 0; t < TN; ++t) o[t] = acc[t][r_] / l;
     }
-    if (m0 + row < N) *reinterpret_cast<vec_t*>(orow + (size_t)row * C) = o;
+    if (m0 + row < N) *reinterpret_cast<vec_t*>(orow + (size_t)row * Ct) = o;
   }
 }
 
@@ -141,21 +144,24 @@ __global__ __launch_bounds__(256, 2) void k_attention_long(const float* __restri
 // Any C % 4 == 0: k_attention's LDS-staged fp32-MFMA form (single staging buffer) with the chunk walk.  gridDim.y = 128-channel
 // panels of the output; each recomputes the scores (these shapes are the small test networks').
 // ---------------------------------------------------------------------------------------------------------------
+template <bool MH>
 __global__ __launch_bounds__(256) void k_attention_long_gen(const float* __restrict__ qkv, int N, int C, int qblocks,
-                                                             float* __restrict__ out) {
+                                                             float* __restrict__ out, int heads) {
   extern __shared__ f32x4 smem_v[];
   float* S = reinterpret_cast<float*>(smem_v);              // [32][AL_LDS]
   float* stg = S + AL_STRIP;                                // [AT_STAGE]
   float* alpha_s = stg + AT_STAGE;                         // [32]
   float* l_s = alpha_s + 32;                                // [32]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.x / qblocks, m0 = (blockIdx.x % qblocks) * 32;
+  const int bh = blockIdx.x / qblocks, m0 = (blockIdx.x % qblocks) * 32;
+  const int b = MH ? bh / heads : bh, hd = MH ? bh % heads : 0;
+  const int Ct = MH ? C * heads : C;                        // channels of an out row
   const int cp = blockIdx.y * 128;                          // this workgroup's channel panel
-  const int rowstride = 3 * C;
-  const float* base = qkv + (size_t)b * N * rowstride;
+  const int rowstride = 3 * Ct;
+  const float* base = qkv + (size_t)b * N * rowstride + (MH ? hd * 3 * C : 0);
   const int kq = tid & 7, lrow = tid >> 3;                  // loaders: 8 float4 per 32-channel row
   const int ln = lane & 31, kh = (lane >> 5) * 4;
-  const float sqrt_c = sqrtf((float)C);
+  const float sqrt_c = sqrtf((float)Ct);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   const int nc = (C + 31) / 32;
   const bool wave_out = (cp + wave * 32) < C;
@@ -287,30 +293,35 @@ __global__ __launch_bounds__(256) void k_attention_long_gen(const float* __restr
   for (int r = 0; r < 16; ++r) {
     const int row = acc_row(r, kh);
     const int m = m0 + row;
-    if (wave_out && m < N && c < C) out[((size_t)b * N + m) * C + c] = acc[r] / l_s[row];
+    if (wave_out && m < N && c < C) out[((size_t)b * N + m) * Ct + (MH ? hd * C : 0) + c] = acc[r] / l_s[row];
   }
 }
 
 namespace {
 // k_attention_long<TN, SPLIT> by (tn, split): one table, one launcher
-int launch_attention_long(int tn, bool split, const float* qkv, int B, int N, int C, int zsplit, float* out, hipStream_t st) {
-  using Kernel = decltype(&k_attention_long<1, false>);
-  static constexpr Kernel kernels[3][2] = {{k_attention_long<1, false>, k_attention_long<1, true>},
-                                           {k_attention_long<2, false>, k_attention_long<2, true>},
-                                           {k_attention_long<4, false>, k_attention_long<4, true>}};
-  static std::atomic<uint64_t> done[3][2];
+#define SR3_AL_ROWS(MH) \
+  {{k_attention_long<1, false, MH>, k_attention_long<1, true, MH>}, {k_attention_long<2, false, MH>, k_attention_long<2, true, MH>}, \
+   {k_attention_long<4, false, MH>, k_attention_long<4, true, MH>}}
+int launch_attention_long(int tn, bool split, const float* qkv, int B, int N, int C, int zsplit, float* out, hipStream_t st, int heads) {
+  using Kernel = decltype(&k_attention_long<1, false, false>);
+  static constexpr Kernel kernels[2][3][2] = {SR3_AL_ROWS(false), SR3_AL_ROWS(true)};
+  static std::atomic<uint64_t> done[2][3][2];
   const int ti = tn >> 1;                                   // 1, 2, 4 -> 0, 1, 2
-  const Kernel kern = kernels[ti][split];
+  const bool mh = heads > 1;
+  const Kernel kern = kernels[mh][ti][split];
   const int smem = (AL_STRIP + 64) * (int)sizeof(float);
-  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern), smem, done[ti][split])) return rc;
+  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern), smem, done[mh][ti][split])) return rc;
   const int qblocks = (N + 31) / 32;
-  hipLaunchKernelGGL(kern, dim3((unsigned)qblocks * B, zsplit), dim3(256), smem, st, qkv, N, C, qblocks, out);
+  hipLaunchKernelGGL(kern, dim3((unsigned)qblocks * B, zsplit), dim3(256), smem, st, qkv, N, C, qblocks, out, heads);
   SR3_LAUNCH_CHECK("k_attention_long");
   return SR3_OK;
 }
+#undef SR3_AL_ROWS
 }  // namespace
 
-int attention_long_forward(const float* qkv, int B, int N, int C, float* out, hipStream_t st, bool split) {
+// heads > 1: C is one head's width (the rows hold heads * C channels), every (image, head) pair a grid entry of its own
+int attention_long_forward(const float* qkv, int B, int N, int C, float* out, hipStream_t st, bool split, int heads) {
+  B *= heads;
   if (B <= 0 || N <= 0 || C <= 0 || (C & 3)) { set_error("attention: needs B, N > 0 and C %% 4 == 0"); return SR3_E_UNSUPPORTED; }
   const int qblocks = (N + 31) / 32;
   if (C % 128 == 0) {
@@ -319,12 +330,14 @@ int attention_long_forward(const float* qkv, int B, int N, int C, float* out, hi
     int cz = (C % 512 == 0) ? 512 : ((C % 256 == 0) ? 256 : 128);
     while ((long)qblocks * B * (C / cz) < 256 && cz > 128) cz >>= 1;
     const int zsplit = C / cz;
-    return launch_attention_long(cz / 128, split, qkv, B, N, C, zsplit, out, st);
+    return launch_attention_long(cz / 128, split, qkv, B, N, C, zsplit, out, st, heads);
   }
-  static std::atomic<uint64_t> done{0};
+  static std::atomic<uint64_t> done[2];
+  const bool mh = heads > 1;
+  auto kern = mh ? k_attention_long_gen<true> : k_attention_long_gen<false>;
   const int smem = (AL_STRIP + AT_STAGE + 64) * (int)sizeof(float);
-  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(k_attention_long_gen), smem, done)) return rc;
-  hipLaunchKernelGGL(k_attention_long_gen, dim3((unsigned)qblocks * B, (C + 127) / 128), dim3(256), smem, st, qkv, N, C, qblocks, out);
+  if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern), smem, done[mh])) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)qblocks * B, (C + 127) / 128), dim3(256), smem, st, qkv, N, C, qblocks, out, heads);
   SR3_LAUNCH_CHECK("k_attention_long_gen");
   return SR3_OK;
 }

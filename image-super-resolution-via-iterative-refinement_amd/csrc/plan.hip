@@ -558,7 +558,7 @@ struct Builder {
       const int o = make(R.cout, T[out].H, T[out].W);
       Op a; a.kind = OP_ATTN;
       const int tokens = T[out].H * T[out].W;
-      a.attn = {T[qkv].off, T[o].off, tokens, R.cout, 0};
+      a.attn = {T[qkv].off, T[o].off, tokens, R.cout, 0, plan_attn_heads(P, R.cout)};
       const bool geo = !train || P->train_geom;       // (a training plan off the native geometry exists under train_geom only)
       if (geo && P->attn_long && !attention_fits(tokens, R.cout)) a.attn.tile_cfg = 24;       // the key-blocked kernel: any token count
       else if (geo && refused.empty() && !attention_fits(tokens, R.cout)) {
@@ -568,7 +568,7 @@ struct Builder {
         refused = msg;
       }
       ops.push_back(a);
-      if (train) { Rec r; r.kind = R_ATTN; r.qkv = qkv; r.o = o; P->recs.push_back(r); }
+      if (train) { Rec r; r.kind = R_ATTN; r.qkv = qkv; r.o = o; r.heads = a.attn.heads; P->recs.push_back(r); }
       flops += attn_flops(B, tokens, R.cout);
       drop(qkv);
       const int out2 = conv({.x0 = o, .Cout = R.cout, .ksize = 1, .w = R.ao_w, .bias = R.ao_b, .r0 = out, .want_stats = true});
@@ -889,8 +889,9 @@ int run_forward(sr3_plan* P, bool train, const float* x, const float* cond, int 
       }
       case OP_ATTN: {
         const Op::Attn& v = o.attn;
-        rc = attention_forward(bind<const float>(ws, v.qkv), B, v.tokens, v.channels, bind<float>(ws, v.out), st,
-                               (P->attn_split ? 1 : 0) | (v.tile_cfg == 24 ? 2 : 0));
+        // (one head: attention_forward's launches; more: attention_heads.hip)
+        rc = attention_forward_heads(bind<const float>(ws, v.qkv), B, v.tokens, v.channels, v.heads, bind<float>(ws, v.out), st,
+                                     (P->attn_split ? 1 : 0) | (v.tile_cfg == 24 ? 2 : 0));
         break;
       }
       case OP_CONV_OUT: {
@@ -1056,6 +1057,27 @@ int sr3_plan_set_option(sr3_plan* plan, const char* key, int value) {
       return SR3_E_BADARG;
     }
     slot = &plan->var_channels;
+  }
+  else if (!strcmp(key, "attn_heads") || !strcmp(key, "attn_head_dim")) {
+    const bool dim = !strcmp(key, "attn_head_dim");
+    if (dim ? value < 0 : value < 1) { set_error("%s %d: needs a value >= %d", key, value, dim ? 0 : 1); return SR3_E_BADARG; }
+    if (dim ? (value > 0 && plan->attn_heads != 1) : (value != 1 && plan->attn_head_dim != 0)) {
+      set_error("%s %d: attn_heads (%d) and attn_head_dim (%d) are mutually exclusive", key, value, plan->attn_heads, plan->attn_head_dim);
+      return SR3_E_BADARG;
+    }
+    // every attention level must take it: the channels divide, and a head's width is a multiple of 4
+    for (const std::vector<Layer>* grp : {&plan->downs, &plan->mid, &plan->ups})
+      for (const Layer& L : *grp) {
+        if (L.kind != L_RES || !L.res.attn || (dim && value == 0)) continue;
+        const int C = L.res.cout;
+        const int d = dim ? value : (C % value ? 0 : C / value);
+        if (d == 0 || C % d || (d & 3)) {
+          if (dim) set_error("attn_head_dim %d: the attention of %s has %d channels (needs a multiple of 4 that divides them)", value, L.res.name.c_str(), C);
+          else set_error("attn_heads %d: the attention of %s has %d channels (needs a divisor with a head width that is a multiple of 4)", value, L.res.name.c_str(), C);
+          return SR3_E_BADARG;
+        }
+      }
+    slot = dim ? &plan->attn_head_dim : &plan->attn_heads;
   }
   if (!slot) { set_error("unknown option %s", key); return SR3_E_BADARG; }
 #ifndef SR3_EXPERIMENTS

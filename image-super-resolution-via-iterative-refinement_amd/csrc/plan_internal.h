@@ -94,7 +94,7 @@ struct Op {
     bool has_drop = false;
     unsigned drop_key = 0;
   } conv;
-  struct Attn { size_t qkv = 0, out = 0; int tokens = 0, channels = 0, tile_cfg = 0; } attn;      // tile_cfg 24: the key-blocked kernel
+  struct Attn { size_t qkv = 0, out = 0; int tokens = 0, channels = 0, tile_cfg = 0, heads = 1; } attn;      // tile_cfg 24: the key-blocked kernel
   struct ConvOut { size_t src = 0, w = 0, bias = 0; int channels = 0, out_ch = 0, H = 0, W = 0; } conv_out;
   size_t ss_rel = 0, mr_rel = 0;   // GroupNorm tables: offset inside the scale/shift region (0 in inference)
   bool fold_fused = false;         // OP_CONV (split-K) / OP_STATS: the last kernel does the fold `tail` too
@@ -151,7 +151,7 @@ struct Rec {
   int out = -1;                      // tensor handle of the output
   size_t gamma = 0, beta = 0;        // GroupNorm of this conv's prologue: parameter arena offsets ...
   size_t ss_off = 0, mr_off = 0;     // ... and its persistent tables (bytes in the workspace)
-  int qkv = -1, o = -1;              // attention
+  int qkv = -1, o = -1, heads = 1;   // attention
   // ... and its backward, resolved once by build_train (train_plan.hip): run_train only binds pointers and launches
   ConvParams dw = {}, dqw = {};      // shape of the weight gradient: the conv's own, the fused res_conv segment's
   Dgrad dx, dq;                      // data gradient: the conv's own (R_CONV, R_CONV_OUT), the fused segment's
@@ -196,6 +196,9 @@ struct sr3_plan {
   int attn_long = 0;         // inference plans: an attention level the score-strip kernels cannot hold (!attention_fits) runs on the key-blocked
                              // kernel of attention_long.hip (tile_cfg 24) instead of refusing the geometry; levels the strip kernels hold keep them.
                              // Off by default ONLY because a test pins the refusal text of a fresh plan; nothing else speaks against 1
+  int attn_heads = 1;        // multi-head SelfAttention (attention_heads.hip): heads of every attention level ...
+  int attn_head_dim = 0;     // ... or (0 = off) the width of a head, the count being the level's channels / attn_head_dim.  Mutually exclusive;
+                             // sr3_plan_set_option refuses a value a level cannot take, so plan_attn_heads always divides
   int gemm_tile = 0;         // A/B knob: force this im2col tile (1-4) on every conv of that kernel; 0 = conv_pick's choice
   int gemm_split = 1;        // the im2col kernel (1x1 and stride-2 convs) on its 3 x bf16 split instantiations (conv_igemm.hip)
   int gemm_wpre = 0;         // 1: ... reading their weights pre-split AND in MFMA fragment order from the derived buffer, straight from global
@@ -278,6 +281,8 @@ namespace sr3 {
 struct Builder;
 inline int plan_height(const sr3_plan* P) { return P->geo_h > 0 ? P->geo_h : P->d.image_size; }
 inline int plan_width(const sr3_plan* P) { return P->geo_w > 0 ? P->geo_w : P->d.image_size; }
+// heads of an attention level of `channels` channels (plan options attn_heads / attn_head_dim)
+inline int plan_attn_heads(const sr3_plan* P, int channels) { return P->attn_head_dim > 0 ? channels / P->attn_head_dim : P->attn_heads; }
 inline int plan_image_channels(const sr3_plan* P) { return P->out_ch - P->var_channels; }      // channels of x, z, eps of a step
 // more than 4 output rows exist only as a prediction with its variance head: refused where a launch list is built
 inline int check_out_rows(const sr3_plan* P) {

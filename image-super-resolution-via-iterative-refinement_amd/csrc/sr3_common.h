@@ -419,7 +419,18 @@ int attention_forward(const float* qkv, int B, int N, int C, float* out, hipStre
 // score strip over all N keys in LDS.)
 bool attention_fits(int N, int C);
 // key-blocked (online softmax) form: any N > 0, C % 4 == 0 (attention_long.hip); split: 3 x bf16 split arithmetic where C % 128 == 0
-int attention_long_forward(const float* qkv, int B, int N, int C, float* out, hipStream_t st, bool split);
+// heads > 1: C is ONE head's width here (the rows hold heads * C channels; the multi-head layout below)
+int attention_long_forward(const float* qkv, int B, int N, int C, float* out, hipStream_t st, bool split, int heads = 1);
+// multi-head attention (the reference SelfAttention's n_head; attention_heads.hip): H = heads heads of d = C / heads channels over the
+// same tensors -- head h owns channels [3 d h, 3 d (h + 1)) of a qkv row as q | k | v and [d h, d (h + 1)) of an out row, its scores
+// are Q_h K_h^T / sqrt(C) (the FULL C) with a softmax of their own.  heads == 1 is attention_forward (same launches).  mode bits 0
+// and 1 as there; bit 2 keeps 64- and 32-channel heads off k_attention_heads (the generalised kernels instead: a measurement knob).
+// Needs heads >= 1, C % heads == 0, d % 4 == 0.
+int attention_forward_heads(const float* qkv, int B, int N, int C, int heads, float* out, hipStream_t st, int mode = 0);
+// ... its fall-back onto the MH instantiations of the single-head kernels (attention.hip, attention_long.hip), heads > 1
+int attention_forward_strided(const float* qkv, int B, int N, int C, int heads, float* out, hipStream_t st, int mode);
+// host check both head entries share: SR3_OK, or the refusal with its message
+int attention_heads_check(const char* who, int C, int heads);
 int p_sample_update(float* x, const float* eps, const float* z, StepTables tb, const int* step_dev,
                     const int64_t* t_per_sample, int step_host, int B, int per_image, hipStream_t st, bool clip = true,
                     const float* c3 = nullptr, float* hist = nullptr);

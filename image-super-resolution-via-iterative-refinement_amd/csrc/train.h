@@ -84,7 +84,8 @@ int conv_wgrad(const WgradParams& p, hipStream_t st);
 // scratch (attention_backward_scratch_bytes): dK / dV slabs per query block, summed in order -- no atomics, no memset; null: fp32 atomics
 size_t attention_backward_scratch_bytes(int B, int N, int C);
 int attention_backward(const float* qkv, const float* dout, const float* out_fwd, int B, int N, int C, float* dqkv, hipStream_t st,
-                       float* scratch = nullptr, size_t scratch_bytes = 0);
+                       float* scratch = nullptr, size_t scratch_bytes = 0, int heads = 1);
+// (heads > 1: the multi-head layout of attention_forward_heads, C the full channel count; needs the slabs -- scratch is not optional)
 
 // Embedding / FiLM backward (small): see train_small.hip
 struct EmbedBwdParams {

@@ -402,7 +402,7 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
       const Tensor& o = P->ttens[r.o];
       // dK / dV through per-query-block slabs in the backward's scratch region, summed in block order: no atomics (round 6)
       rc = attention_backward(X.act(r.qkv), X.grad(r.o), X.act(r.o), B, o.H * o.W, o.C, X.grad(r.qkv), st,
-                              X.at<float>(P->t_regions.scratch_off), P->t_regions.scratch_bytes);
+                              X.at<float>(P->t_regions.scratch_off), P->t_regions.scratch_bytes, r.heads);
       if (rc) return rc;
     } else if (r.kind == R_CONV_IN) {
       const int Cout = r.dw.Cout;

@@ -38,7 +38,14 @@ def define_G(opt):
                              'the config has out_channel %d' % (want, int(model_opt['diffusion']['channels']), int(u['out_channel'])))
     else:
         lv = None
+    # engine keys model.unet.n_head / model.unet.head_dim: multi-head SelfAttention (the reference module's n_head, which its constructors
+    # never expose) -- n_head heads at every attention level, or heads of head_dim channels each (ADM's num_head_channels).  Absent = one
+    # head.  The weights keep their shapes, so *_gen.pth does not record the head count: the config carries it
+    heads = {k: int(u[k]) for k in ('n_head', 'head_dim') if u.get(k) is not None}
+    if len(heads) == 2:
+        raise ValueError('model.unet.n_head (%d) and model.unet.head_dim (%d) are mutually exclusive: set one' % (heads['n_head'], heads['head_dim']))
     denoiser = unet.UNet(
+        **heads,
         in_channel=u['in_channel'], out_channel=u['out_channel'], norm_groups=u['norm_groups'],
         inner_channel=u['inner_channel'], channel_mults=u['channel_multiplier'], attn_res=u['attn_res'],
         res_blocks=u['res_blocks'], dropout=u['dropout'], image_size=model_opt['diffusion']['image_size'],

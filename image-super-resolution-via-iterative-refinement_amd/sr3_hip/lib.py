@@ -160,6 +160,8 @@ SIGNATURES = {
     'sr3_embed_bwd_f32': (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'sr3_attention_f32': (_I, [_P, _I, _I, _I, _P, _P]),
     'sr3_attention_ex_f32': (_I, [_P, _I, _I, _I, _P, _I, _P]),
+    'sr3_attention_heads_f32': (_I, [_P, _I, _I, _I, _I, _P, _I, _P]),
+    'sr3_attention_bwd_heads_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _Z, _P]),
     'sr3_film_embed_f32': (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     'sr3_conv_in_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
     'sr3_conv_out_f32': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P]),

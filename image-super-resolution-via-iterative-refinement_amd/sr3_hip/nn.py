@@ -25,7 +25,7 @@ class EngineUNet(nn.Module):
 
     def __init__(self, in_channel=6, out_channel=3, inner_channel=32, norm_groups=32,
                  channel_mults=(1, 2, 4, 8, 8), attn_res=(8), res_blocks=3, dropout=0,
-                 with_noise_level_emb=True, image_size=128, *, long_attention=False, learned_variance=False):
+                 with_noise_level_emb=True, image_size=128, *, long_attention=False, learned_variance=False, n_head=1, head_dim=None):
         super().__init__()
         if not with_noise_level_emb:
             raise NotImplementedError('the engine always conditions on the noise level / timestep '
@@ -37,6 +37,18 @@ class EngineUNet(nn.Module):
         self.long_attention = bool(long_attention)
         if self.long_attention:
             self.plan.set_option('attn_long', 1)
+        # config keys model.unet.n_head / model.unet.head_dim (plan options attn_heads / attn_head_dim): multi-head SelfAttention, n_head
+        # heads at every attention level or heads of head_dim channels each.  The weights keep their shapes: the head count is the
+        # config's to carry, no checkpoint records it.  A value a level cannot take is refused by the library, in its words
+        if head_dim is not None and int(n_head) != 1:
+            raise ValueError('n_head (%d) and head_dim (%d) are mutually exclusive: set one' % (int(n_head), int(head_dim)))
+        self.n_head, self.head_dim = int(n_head), (None if head_dim is None else int(head_dim))
+        if self.head_dim is not None:
+            if self.head_dim < 1:
+                raise ValueError('head_dim must be a positive channel count (got %d)' % self.head_dim)
+            self.plan.set_option('attn_head_dim', self.head_dim)
+        elif self.n_head != 1:
+            self.plan.set_option('attn_heads', self.n_head)
         # config key model.diffusion.learned_variance (plan option var_channels): the second half of the out_channel rows is the variance
         # head.  Without it a plan with more than 4 output rows builds no launch list: refused here, by the library, in its words
         self.learned_variance = bool(learned_variance)
@@ -451,8 +463,9 @@ class EngineUNet(nn.Module):
 
     def extra_repr(self):
         d = self.plan.desc
-        return 'variant=%s, in=%d, out=%d, inner=%d, groups=%d, mults=%s, attn_res=%s, res_blocks=%d, image=%d, ' \
+        heads = 'head_dim=%d' % self.head_dim if self.head_dim is not None else 'n_head=%d' % self.n_head
+        return 'variant=%s, in=%d, out=%d, inner=%d, groups=%d, mults=%s, attn_res=%s, %s, res_blocks=%d, image=%d, ' \
                'params=%d (packed arena, libsr3_mi355x)' % (
                    self.variant, d.in_channel, d.out_channel, d.inner_channel, d.norm_groups,
-                   list(d.channel_mults[:d.n_mults]), list(d.attn_res[:d.n_attn_res]), d.res_blocks, d.image_size,
+                   list(d.channel_mults[:d.n_mults]), list(d.attn_res[:d.n_attn_res]), heads, d.res_blocks, d.image_size,
                    sum(e['numel'] for e in self.plan.table))

@@ -103,7 +103,7 @@ double sr3_plan_forward_flops(sr3_plan* plan, int batch);
 int sr3_store_wt_fits(size_t bytes);
 /* tuning knobs: key in {"fuse_stats", "fuse_res", "tile_cfg", "ksplit", "keep_all", "split_bf16", "winograd",
  * "wino_split", "wino_split8", "wino2", "wino_ragged", "wino_up", "gemm_split", "gemm2", "gemm_s2", "gemm_n64", "fork_side", "gemm_wpre", "gemm_tile", "fold_fuse", "wgrad_split", "attn_split",
- * "attn_long", "store_wt", "train_geom", "loss_l2", "var_channels"};
+ * "attn_long", "store_wt", "train_geom", "loss_l2", "var_channels", "attn_heads", "attn_head_dim"};
  * returns previous value.
  * wino_split (default 1): the Winograd convolutions that run on the kernel's one-image tile (maps >= 16x16) use its 3 x bf16
  *   split instantiation: every fp32 operand as x = h + m + l (three bf16 terms, each residual exact in fp32), every product as
@@ -164,6 +164,13 @@ int sr3_store_wt_fits(size_t bytes);
  *   of refusing the geometry.  A level the strip kernels hold keeps them: launch list, workspace and output bits are those of
  *   attn_long = 0 there.  attn_split selects the arithmetic as for the strip kernels.  The default is 0 for ONE reason: a test pins the
  *   refusal of a fresh plan at 384 x 384; a later change that rewrites that test can flip it.
+ * attn_heads (default 1) / attn_head_dim (default 0 = off): multi-head SelfAttention (the reference module's n_head; sr3_attention_heads_f32
+ *   has the layout).  attn_heads = H: every attention level runs H heads of C / H channels.  attn_head_dim = d: every level runs C / d
+ *   heads of d channels, so levels of different width get different head counts (ADM's num_head_channels).  Mutually exclusive: setting
+ *   one while the other is on is SR3_E_BADARG.  A value some attention level cannot take (C not divisible, head width not a multiple of
+ *   4) is SR3_E_BADARG with the level and its channels in the message; the plan keeps its previous value.  The weights keep their
+ *   shapes, the launch list its length and kinds; the attention ops carry their head count to the forward and the training backward.
+ *   With both at their defaults every launch and bit is the single-head one.  Rebuilds the launch list.
  * store_wt (default 3; a mask, 0 .. 7): which kernels write their 16-byte epilogue stores THROUGH L2 (buffer stores with sc1) instead of
  *   leaving the lines dirty for the kernel boundary to write back: 1 the two-workgroup Winograd kernel (outputs and split-K slabs),
  *   2 the 8-wave Winograd kernel, 4 the split-K reduce kernels (k_rows_fold, k_splitk_reduce).  The other 16-byte epilogues of the
@@ -942,6 +949,21 @@ int sr3_attention_bwd_f32(const float* qkv, const float* dout, const float* out_
 size_t sr3_attention_bwd_scratch_bytes(int B, int N, int C);
 int sr3_attention_bwd_ex_f32(const float* qkv, const float* dout, const float* out_fwd, int B, int N, int C, float* dqkv,
                              void* scratch, size_t scratch_bytes, void* stream);
+/* Multi-head SelfAttention core (the reference module's n_head, unet.py:113-142): `heads` heads of d = C / heads channels over the same
+ * tensors.  Head h owns channels [3 d h, 3 d (h + 1)) of a qkv row as q_h | k_h | v_h (the module's view (b, n_head, 3 d, h, w)) and
+ * channels [d h, d (h + 1)) of an out row; S_h = Q_h K_h^T / sqrt(C) -- the FULL C, as in the module --, P_h = softmax over keys,
+ * O_h = P_h V_h.  heads == 1: the launches and bits of sr3_attention_ex_f32 in every mode.  mode bits 0 (split arithmetic) and 1
+ * (key-blocked kernel) as there; bit 2 keeps 64- and 32-channel heads off their own kernel (a measurement knob).  Kernels: d = 64 / 32
+ * on k_attention_heads (csrc/attention_heads.hip; fp32-MFMA and split instantiations, any N the score strip holds, ragged included),
+ * d % 128 == 0 on the staging-free kernels, every other d % 4 == 0 on the LDS-staged fp32-MFMA kernel, every d under bit 1.
+ * Refused: heads < 1 or C % heads != 0 (SR3_E_BADARG), (C / heads) % 4 != 0 (SR3_E_UNSUPPORTED), B * N * 3C >= 2^31, B * heads > 65535,
+ * N beyond the score strip without bit 1 (SR3_E_UNSUPPORTED) -- each with the numbers in sr3_last_error(). */
+int sr3_attention_heads_f32(const float* qkv, int B, int N, int C, int heads, float* out, int mode, void* stream);
+/* ... its backward, in the slab form of sr3_attention_bwd_ex_f32 (fp32 MFMA; no atomics, no memset: bitwise reproducible).  scratch:
+ * sr3_attention_bwd_scratch_bytes(B, N, C) bytes -- the slab total does not depend on heads --, 16-byte aligned (SR3_E_ALIGN), not
+ * shorter (SR3_E_NOMEM).  heads == 1: the bits of sr3_attention_bwd_ex_f32.  Refusals as the forward's. */
+int sr3_attention_bwd_heads_f32(const float* qkv, const float* dout, const float* out_fwd, int B, int N, int C, int heads, float* dqkv,
+                                void* scratch, size_t scratch_bytes, void* stream);
 /* Weight gradient of one convolution (autograd of nn.Conv2d inside `l_pix.backward()`, model/model.py:50-54), per op -- what
  * sr3_train_step runs per layer: dw[n][tap][c] = sum over output pixels of dy[m][n] * a_tap[m][c], with a = the convolution's
  * (virtual concat, optionally x2-upsampled, optionally GroupNorm-affine / SiLU-activated: act, ss as in sr3_conv_f32) input.
