@@ -69,7 +69,7 @@ def define_G(opt):
     if d.get('cond_drop') is not None:
         netG.set_cond_drop(d['cond_drop'])
     if lv is not None:
-        from sr3_hip.diffusion import parse_learned_variance
+        from sr3_hip.schedules import parse_learned_variance
         netG.set_learned_variance(parse_learned_variance(lv))
     # "t_sampler": {"type": "loss_second_moment", "history": 10, "uniform": 0.001} -- p_losses draws t by its loss (set_t_sampler; behind
     # learned_variance, which an SR3 model needs for it); absent: uniform draws, today's launches and checkpoint keys
@@ -79,12 +79,12 @@ def define_G(opt):
     # "self_condition": {"prob": 0.5} | true -- the network reads its own last x0 as extra input channels (set_self_condition; unet.in_channel
     # is then conditioning channels + 2 x channels)
     if d.get('self_condition') is not None:
-        from sr3_hip.diffusion import parse_self_condition
+        from sr3_hip.schedules import parse_self_condition
         netG.set_self_condition(parse_self_condition(d['self_condition']))
     # "cond_augment": {"max_level": 0.5, "sample_level": 0.1, "level_channel": true} -- the network reads the conditioning image diffused to
     # a level of its own, and that level as one more input plane (set_cond_augment; unet.in_channel is then conditioning channels + 1 + channels)
     if d.get('cond_augment') is not None:
-        from sr3_hip.diffusion import parse_cond_augment
+        from sr3_hip.schedules import parse_cond_augment
         netG.set_cond_augment(**parse_cond_augment(d['cond_augment']))
     if opt['phase'] == 'train':
         init_weights(netG, init_type='orthogonal')

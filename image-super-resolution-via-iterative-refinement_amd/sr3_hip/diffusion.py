@@ -11,22 +11,6 @@ Engine design (not the reference's): one reverse step = [z ~ N(0,I) in-graph] ->
 device-side step counter) -> fused x_{t-1} update -> counter decrement, captured once as a
 hipGraph and replayed T times; snapshots are graph-external device copies.
 
-Sampler (engine extension, `"sampler": {"type": "ddim", "steps": S, "eta": e}` in the schedule dict or `set_sampler`): the same
-captured step replayed S times over a strided walk through the schedule -- `sampler_tables` restates the DDIM update in the fused
-tail's linear form, so a sampler is five other coefficient tables, another level table and (DDPM) a step-index -> timestep map.
-`"type": "dpmpp_2m"` is the second-order multistep solver DPM-Solver++(2M) on a walk uniform in log-SNR (`"walk": "logsnr"`, its
-default; DDIM takes the key too): one more table, c3, and one image-sized buffer that carries the previous step's x0 (st['hist']).
-"walk" may also be an explicit list of timesteps (strictly increasing, ending at T - 1): the chain of a distilled student (sr3_hip/distill.py).
-
-Tiling (engine extension, `"tiling": {"tile": 128 | [th, tw], "overlap": 32, "batch": 8}` next to it, or `set_tiling`): an image larger
-than the tile is sampled as one chain whose eps comes from overlapping tiles of that size -- per step: sr3_tile_gather + UNet forward
-per chunk of tiles, then sr3_tiled_step (blend + p_sample update + counter decrement) on the whole image (`p_sample_loop_tiled`).
-
-Objective (engine extension, `"prediction": "eps" | "v" | "x0"` and `"loss": {"type", "delta", "weight", "gamma"}` in model.diffusion, or
-`set_prediction` / `set_objective`): what the network's output stands for and how the training loss weighs it.  Training hands per-image
-target coefficients and weights to sr3_train_step_ex (`prediction_coefs`, `loss_weights`); sampling changes the two tables a, b of the
-step tail's x0c = clip(a x - b out) and nothing else, in every loop.
-
 Self-conditioning (engine extension, `"self_condition": {"prob": 0.5}` in model.diffusion or `set_self_condition`; Chen et al. 2022): the
 network reads its own previous estimate of x0 as `channels` extra input channels, [LR | last x0 | x].  Training: a first, gradient-free
 inference forward on zero self-conditioning channels supplies the clamped x0 of a random part of the batch (sr3_selfcond_x0_f32, per
@@ -52,24 +36,13 @@ sigma: their forwards launch the prediction rows of the output conv alone.
 The variational bound by timestep (engine extension; Nichol & Dhariwal 2021): `calc_bpd_loop` walks x0 through all S steps of the
 respaced walk -- q_sample at the step (sr3_q_sample_step_f32), one inference-mode forward, the per-image term of the bound
 (sr3_vlb_terms_f32) -- captured once and replayed, and returns bits per dimension per image and step, the prior term and their sum.
-`"t_sampler": {"type": "loss_second_moment", "history": 10, "uniform": 0.001}` in model.diffusion, or `set_t_sampler`: p_losses draws
-t with p_t proportional to sqrt(E[L_t^2]) of the per-image terms the training step returns (sr3_train_step_ex3) and weights the loss
-by 1 / (T p_t) (sr3_hip/t_sampler.py).  It needs draws on the schedule's grid: the DDPM variant, or SR3 under learned_variance.
+`set_t_sampler` (sr3_hip/t_sampler.py) draws the training steps by those terms; it needs draws on the schedule's grid: the DDPM variant,
+or SR3 under learned_variance.
 
-Rules on x0 (engine extensions, keys next to "sampler" / "tiling" or the setters; sr3_hip/x0_rules.py holds each rule once): what is done
-to the predicted x0 before the posterior mix.  Per step: UNet forward with the output stored, then the rule's entry in place of the fused
-tail.  The rules exclude one another and tiling -- each owns the whole tail of a step.
-  `"consistency": {"block": 8, "strength": 1.0}` / `set_consistency`: every step shifts each block x block block of x0 so that its mean is
-    the target's -- the block means of the conditioning image, or `consistency_target=` (the range / null-space projection for an
-    average pool; sr3_consistent_step).
-  `"guidance": {"scale": 1.5, "threshold": "dynamic", "percentile": 0.995}` / `set_guidance` (`"cond_drop": p` in model.diffusion, or
-    `set_cond_drop`, trains a model for it): classifier-free guidance -- two forwards per step, on the conditioning image and on a zero
-    one, combined as out_u + scale (out_c - out_u) before x0 is formed -- and what is done to x0 where it leaves [-1, 1]: the static
-    clamp, nothing, or dynamic thresholding (each image's x0 divided by its own percentile of |x0|; sr3_guided_step).
-  `"backprojection": {"scale": 8, "iterations": 2, "strength": 1.0, "resample": "bicubic"}` / `set_backprojection`: `iterations` rounds of
-    x0 <- x0 + strength * U(y - D(x0)), D / U = Pillow's antialiased resize down / up by `scale` (`resample_tables`), y = the LR image
-    (`backprojection_target=`) or the down-sampled conditioning image (sr3_backproject_step).  A contraction, not a projection.
+The samplers' and the objective's tables (`set_sampler`, `set_prediction` / `set_objective`) are sr3_hip/schedules.py, the tile layout
+(`set_tiling`) sr3_hip/tiling.py, the rules on x0 (`set_consistency`, `set_guidance`, `set_backprojection`) sr3_hip/x0_rules.py.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -83,398 +56,14 @@ from . import tiling as TL
 from . import x0_rules as X
 from .x0_rules import (BACKPROJECTION_KEYS, CONSISTENCY_BLOCKS, RESAMPLES, THRESHOLDS, backprojection_error, block_means,      # noqa: F401
                        quantile_rank, resample_f32, resample_tables)                                                          # (their old home)
+from .schedules import (COND_AUGMENT_KEYS, LEARNED_VARIANCE_LAMBDA, LOSS_TYPES, LOSS_WEIGHTS, PREDICTIONS, SAMPLER_KINDS,     # noqa: F401
+                        SELF_CONDITION_PROB, WALKS, _BUFFERS, _SAMPLER_TABLES, _check_prediction, _check_sampler_kind, _positive,
+                        ancestral_tables, cond_level_coefs, hybrid_step_scalars, loss_weights, make_beta_schedule, parse_cond_augment,
+                        parse_learned_variance, parse_self_condition, prediction_coefs, sampler_tables, sampler_walk,
+                        widen_for_learned_variance)                                                                           # (theirs too)
 
 
-def make_beta_schedule(schedule, n_timestep, linear_start=1e-4, linear_end=2e-2, cosine_s=8e-3):
-    """float64 beta schedules named as in the reference (diffusion.py:12-49)."""
-    if schedule == 'linear':
-        return np.linspace(linear_start, linear_end, n_timestep, dtype=np.float64)
-    if schedule == 'quad':
-        return np.linspace(linear_start ** 0.5, linear_end ** 0.5, n_timestep, dtype=np.float64) ** 2
-    if schedule in ('warmup10', 'warmup50'):
-        frac = 0.1 if schedule == 'warmup10' else 0.5
-        betas = np.full(n_timestep, linear_end, dtype=np.float64)
-        n = int(n_timestep * frac)
-        betas[:n] = np.linspace(linear_start, linear_end, n, dtype=np.float64)
-        return betas
-    if schedule == 'const':
-        return np.full(n_timestep, linear_end, dtype=np.float64)
-    if schedule == 'jsd':
-        return 1.0 / np.linspace(n_timestep, 1, n_timestep, dtype=np.float64)
-    if schedule == 'cosine':
-        steps = torch.arange(n_timestep + 1, dtype=torch.float64) / n_timestep + cosine_s
-        ac = torch.cos(steps / (1 + cosine_s) * np.pi / 2).pow(2)
-        ac = ac / ac[0]
-        return (1 - ac[1:] / ac[:-1]).clamp(max=0.999).numpy()
-    raise NotImplementedError(schedule)
-
-
-def _check_walk_args(alphas_cumprod, steps):
-    ac = np.asarray(alphas_cumprod, dtype=np.float64).reshape(-1)
-    T = int(ac.shape[0])
-    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)):
-        raise ValueError('sampler steps must be an integer (got %r)' % (steps,))
-    if T < 1 or not np.all(np.isfinite(ac)) or not np.all((ac > 0.0) & (ac < 1.0)):
-        raise ValueError('alphas_cumprod must be finite values in (0, 1)')
-    S = int(steps)
-    if S < 1 or S > T:
-        raise ValueError('sampler steps must lie in [1, %d] (got %d)' % (T, S))
-    return ac, T, S
-
-
-def _half_logsnr(ac):
-    """lambda = log(alpha / sigma) = 0.5 log(ac / (1 - ac)): what a DPM-Solver steps in."""
-    return 0.5 * np.log(ac / (1.0 - ac))
-
-
-WALKS = ('time', 'logsnr')
-
-
-def _explicit_walk(alphas_cumprod, steps, walk):
-    """A walk given as a list or array of timesteps: checked, returned as int64 [S].  `steps` None: the list's length."""
-    try:
-        arr = np.asarray(walk)
-    except (TypeError, ValueError):
-        arr = None
-    if arr is None or arr.ndim != 1 or arr.size == 0 or arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
-        raise ValueError('sampler walk must be one of %s or a non-empty list of integer timesteps (got %r)'
-                         % (', '.join(repr(w) for w in WALKS), walk))
-    tau = arr.astype(np.int64)
-    ac, T, S = _check_walk_args(alphas_cumprod, int(tau.shape[0]) if steps is None else steps)
-    if tau.shape[0] != S:
-        raise ValueError('sampler walk has %d timesteps but steps is %d' % (tau.shape[0], S))
-    if tau.min() < 0 or tau.max() > T - 1:
-        raise ValueError('sampler walk must lie in [0, %d] (got %s)' % (T - 1, tau.tolist()))
-    if np.any(np.diff(tau) <= 0):
-        raise ValueError('sampler walk must be strictly increasing (got %s)' % (tau.tolist(),))
-    if tau[-1] != T - 1:
-        raise ValueError('sampler walk must end at T - 1 = %d (got %d)' % (T - 1, tau[-1]))
-    return tau
-
-
-def sampler_walk(alphas_cumprod, steps, walk='time'):
-    """The timesteps a sampler visits: tau, int64 [S], strictly increasing, tau[0] = 0 and tau[S-1] = T - 1 (S = 1: [T - 1]).
-
-    walk = a list or array of timesteps: that walk itself, checked -- strictly increasing integers in [0, T - 1], the last one T - 1, as
-    many as `steps` (None: however many there are); a ValueError names the fault.  Its first timestep need not be 0: the walk of a
-    distilled student (sr3_hip.distill) is every second timestep of its teacher's.
-
-    walk = 'time': uniform in the timestep, round(linspace(0, T - 1, S)).  walk = 'logsnr': uniform in lambda_t = 0.5 log(ac_t /
-    (1 - ac_t)) -- tau[i] is the timestep whose lambda is nearest the i-th of S evenly spaced targets between lambda_0 and
-    lambda_{T-1}; both ends are pinned, one forward pass (tau[i] >= tau[i-1] + 1) makes the walk strictly increasing where the schedule
-    is too coarse for the targets (its first timesteps, where lambda moves fastest) and one backward pass (tau[i] <= tau[i+1] - 1)
-    takes back what the forward pass pushed past the top.  A multistep solver's extrapolation is only as good as the ratio of
-    consecutive lambda intervals is tame; on the 'time' walk the last intervals are enormous in lambda."""
-    if not isinstance(walk, str):
-        return _explicit_walk(alphas_cumprod, steps, walk)
-    ac, T, S = _check_walk_args(alphas_cumprod, steps)
-    if walk not in WALKS:
-        raise ValueError('sampler walk must be one of %s (got %r)' % (', '.join(repr(w) for w in WALKS), walk))
-    if S == 1:
-        return np.array([T - 1], dtype=np.int64)
-    if walk == 'time':
-        tau = np.round(np.linspace(0, T - 1, S)).astype(np.int64)
-    else:
-        lam = _half_logsnr(ac)
-        target = np.linspace(lam[0], lam[T - 1], S)
-        tau = np.array([int(np.argmin(np.abs(lam - v))) for v in target], dtype=np.int64)
-        tau[0], tau[S - 1] = 0, T - 1
-        for i in range(1, S):
-            tau[i] = max(tau[i], tau[i - 1] + 1)
-        tau[S - 1] = T - 1
-        for i in range(S - 2, -1, -1):
-            tau[i] = min(tau[i], tau[i + 1] - 1)
-    assert tau[-1] == T - 1 and tau[0] == 0 and np.all(np.diff(tau) > 0), 'sampler walk is not strictly increasing'
-    return tau
-
-
-SAMPLER_KINDS = ('ddim', 'dpmpp_2m')
-
-
-def _check_sampler_kind(kind):
-    if kind not in SAMPLER_KINDS:
-        raise NotImplementedError('sampler type %r (only %s)' % (kind, ', '.join('"%s"' % k for k in SAMPLER_KINDS)))
-
-
-PREDICTIONS = ('eps', 'v', 'x0')
-LOSS_TYPES = ('l1', 'l2', 'huber')          # the loss_kind numbers of sr3_train_step_ex, in order
-LOSS_WEIGHTS = ('uniform', 'min_snr')
-
-
-def _check_prediction(kind):
-    if kind not in PREDICTIONS:
-        raise ValueError('prediction must be one of %s (got %r)' % (', '.join(repr(k) for k in PREDICTIONS), kind))
-
-
-def _positive(name, v):
-    try:
-        f = float(v)
-    except (TypeError, ValueError):
-        raise ValueError('%s must be a number (got %r)' % (name, v))
-    if isinstance(v, bool) or not np.isfinite(f) or not f > 0.0:
-        raise ValueError('%s must be finite and > 0 (got %r)' % (name, v))
-    return f
-
-
-SELF_CONDITION_PROB = 0.5      # the default of the config key (Chen et al. 2022 train half of the batch self-conditioned)
-
-
-def parse_self_condition(spec):
-    """The config key model.diffusion.self_condition -> the argument of set_self_condition: {"prob": p} -> p, true or {} -> the default
-    0.5, absent / null / false -> None (off)."""
-    if spec is None or spec is False:
-        return None
-    if spec is True:
-        return SELF_CONDITION_PROB
-    if not hasattr(spec, 'get') or not hasattr(spec, 'keys'):
-        raise ValueError('self_condition: true or a dict with "prob" is expected (got %r)' % (spec,))
-    for k in spec.keys():
-        if k != 'prob':
-            raise ValueError('self_condition: unknown key %r (known: "prob")' % (k,))
-    p = spec.get('prob')
-    return SELF_CONDITION_PROB if p is None else p
-
-
-COND_AUGMENT_KEYS = ('max_level', 'sample_level', 'level_channel')
-
-
-def parse_cond_augment(spec):
-    """The config key model.diffusion.cond_augment -> the keyword arguments of set_cond_augment: {"max_level": m, "sample_level": s,
-    "level_channel": bool} ("max_level" required; sample_level 0.0 and level_channel true where absent), absent / null -> max_level
-    None (off)."""
-    if spec is None:
-        return dict(max_level=None)
-    if not hasattr(spec, 'get') or not hasattr(spec, 'keys'):
-        raise ValueError('cond_augment: a dict with "max_level" is expected (got %r)' % (spec,))
-    for k in spec.keys():
-        if k not in COND_AUGMENT_KEYS:
-            raise ValueError('cond_augment: unknown key %r (known: %s)' % (k, ', '.join('"%s"' % n for n in COND_AUGMENT_KEYS)))
-    if spec.get('max_level') is None:
-        raise ValueError('cond_augment: "max_level" is required')
-    return dict(max_level=spec['max_level'], sample_level=spec.get('sample_level', 0.0), level_channel=spec.get('level_channel', True))
-
-
-def cond_level_coefs(s):
-    """(a, s) of the augmented conditioning image a c + s eps as two fp32 tensors: s (numbers or a tensor, on any device) rounded to fp32
-    first, then a = sqrt(1 - s^2) in float64 of that fp32 s, rounded once -- so a^2 + s^2 is 1 to fp32 rounding, and s = 0 gives a = 1
-    exactly.  Every operation is a correctly rounded IEEE one: the host and the device give the same bits."""
-    s32 = torch.as_tensor(s, dtype=torch.float32).reshape(-1).contiguous()
-    a32 = (1.0 - s32.double() ** 2).sqrt().float()
-    return a32, s32
-
-
-def prediction_coefs(kind, ca, cb):
-    """What the network's output `out` stands for at the noise level x = ca x0 + cb z (ca = sqrt(abar), cb = sqrt(1 - abar)), as the four
-    coefficients the engine reads:  x0 = x0_a x - x0_b out  (the step tail's a, b) and the training target  tgt_z z + tgt_x0 x0.
-
-        eps (the reference's; Ho et al. 2020):    out ~ z                 a, b = 1 / ca, cb / ca     target (1, 0)
-        v   (Salimans & Ho 2022):                 out ~ ca z - cb x0      a, b = ca, cb              target (ca, -cb)
-        x0:                                       out ~ x0                a, b = 0, -1               target (0, 1)
-
-    Pure numpy, float64, no device; ca and cb broadcast.  Returns (x0_a, x0_b, tgt_z, tgt_x0) as arrays of their shape.  (The eps row is
-    the schedule buffers' sqrt(1 / abar), sqrt(1 / abar - 1) as quotients: equal once rounded to the fp32 the engine's tables hold.)"""
-    _check_prediction(kind)
-    ca, cb = np.broadcast_arrays(np.asarray(ca, dtype=np.float64), np.asarray(cb, dtype=np.float64))
-    one, zero = np.ones_like(ca), np.zeros_like(ca)
-    if kind == 'eps':
-        return 1.0 / ca, cb / ca, one, zero
-    if kind == 'v':
-        return ca.copy(), cb.copy(), ca.copy(), -cb
-    return zero, -one, zero, one
-
-
-def loss_weights(kind, weight, gamma, ca):
-    """Per-noise-level weight of the training loss.  'uniform': 1.  'min_snr' (Min-SNR-gamma, Hang et al. 2023): min(SNR, gamma) divided
-    by SNR, SNR + 1 or 1 for an eps-, v- or x0-predicting network, SNR = ca^2 / (1 - ca^2) -- which weighs the implied x0 error by
-    min(SNR, gamma) whatever the network predicts.  Written as closed forms in g2 = ca^2 so that ca = 1 (SNR infinite: the first entry of
-    SR3's level table) stays finite:  eps  min(1, gamma (1 - g2) / g2);  v  min(g2, gamma (1 - g2));  x0  min(g2 / (1 - g2), gamma), gamma
-    at g2 = 1.  Pure numpy, float64, no device; `gamma` is read for 'min_snr' only."""
-    _check_prediction(kind)
-    if weight not in LOSS_WEIGHTS:
-        raise ValueError('loss weight must be one of %s (got %r)' % (', '.join(repr(k) for k in LOSS_WEIGHTS), weight))
-    g2 = np.asarray(ca, dtype=np.float64) ** 2
-    if weight == 'uniform':
-        return np.ones_like(g2)
-    gamma = _positive('loss gamma', gamma)
-    with np.errstate(divide='ignore', invalid='ignore'):
-        if kind == 'eps':
-            return np.minimum(1.0, gamma * (1.0 - g2) / g2)
-        if kind == 'v':
-            return np.minimum(g2, gamma * (1.0 - g2))
-        return np.where(1.0 - g2 > 0.0, np.minimum(g2 / (1.0 - g2), gamma), gamma)
-
-
-def sampler_tables(alphas_cumprod, steps, eta, *, kind='ddim', walk='time', prediction='eps'):
-    """Tables of a sampler over a walk through the schedule (`sampler_walk`) in the form of the engine's fused step tail,
-
-        x0c = clip(a x - b eps) ;  x_new = c1 x0c + c2 x + c3 x0c_prev + sigma z.
-
-    kind = 'ddim' (Song et al. 2021, eq. 12 and 16; c3 = 0): the textbook update  sqrt(ap) x0c + d eps' + sigma z  with
-    eps' = (x - sqrt(ab) x0c) / sqrt(1 - ab) re-derived from the
-    clipped x0 (the reference's clip_denoised semantics), d = sqrt(1 - ap - sigma^2): collecting x0c and x gives
-    c1 = sqrt(ap) - d sqrt(ab) / sqrt(1 - ab), c2 = d / sqrt(1 - ab).  ab = alphas_cumprod[tau[j]], ap = that of the next (smaller)
-    timestep of the walk and 1 after the last; sigma = eta sqrt((1 - ap) / (1 - ab)) sqrt(1 - ab / ap).  With steps = T and eta = 1 these
-    are the reference's posterior_mean_coef1/2 and sqrt(posterior_variance).
-
-    kind = 'dpmpp_2m' (DPM-Solver++(2M), Lu et al. 2022, Algorithm 2, data prediction; eta must be 0): with lambda = 0.5 log(ac /
-    (1 - ac)), h = lambda(ap) - lambda(ab) and r = (the previous step's h) / h, the update is
-    x_new = sqrt(1 - ap) / sqrt(1 - ab) x - sqrt(ap) expm1(-h) D with D = (1 + 1 / (2r)) x0c - 1 / (2r) x0c_prev, so with
-    k = -sqrt(ap) expm1(-h): c1 = k (1 + 1 / (2r)), c2 = sqrt(1 - ap) / sqrt(1 - ab), c3 = -k / (2r).  The first step taken has no
-    history (c1 = k, c3 = 0: DDIM's step), and the last one goes to ap = 1, where lambda is infinite: c1 = 1, c2 = c3 = 0, DDIM's too.
-
-    prediction ('eps' | 'v' | 'x0', `prediction_coefs`): what the network's output stands for.  Only a and b change with it -- c1, c2, c3,
-    sigma, level and tau do not: DDIM re-derives eps from the clipped x0, and the multistep solver is already in data-prediction form.
-
-    Pure numpy, float64, no device.  The step index j counts like the device counter: j = steps - 1 is the first step taken, j = 0 the
-    last.  Returns a dict: tau (`sampler_walk`), a, b, c1, c2, c3,
-    sigma ([S]) and level ([S + 1]: level[j + 1] = sqrt(alphas_cumprod[tau[j]]), the reference's sqrt_alphas_cumprod_prev[t + 1] at
-    t = tau[j]; level[0] = 1).  walk: 'time', 'logsnr' or an explicit list of timesteps (`sampler_walk`; `steps` may then be None)."""
-    if not isinstance(walk, str):
-        walk = _explicit_walk(alphas_cumprod, steps, walk)
-        steps = int(walk.shape[0])
-    ac, T, S = _check_walk_args(alphas_cumprod, steps)
-    try:
-        eta = float(eta)
-    except (TypeError, ValueError):
-        raise ValueError('sampler eta must be a number (got %r)' % (eta,))
-    if not np.isfinite(eta) or not 0.0 <= eta <= 1.0:
-        raise ValueError('sampler eta must lie in [0, 1] (got %r)' % (eta,))
-    if kind not in SAMPLER_KINDS:
-        raise ValueError('sampler kind must be one of %s (got %r)' % (', '.join(repr(k) for k in SAMPLER_KINDS), kind))
-    if kind == 'dpmpp_2m' and eta != 0.0:
-        raise ValueError('sampler kind \'dpmpp_2m\' is the deterministic solver: eta must be 0 (got %r)' % (eta,))
-    _check_prediction(prediction)
-    tau = sampler_walk(ac, S, walk)
-    ab = ac[tau]
-    ap = np.append(1.0, ab[:-1])
-    if kind == 'ddim':
-        sigma = eta * np.sqrt((1.0 - ap) / (1.0 - ab)) * np.sqrt(1.0 - ab / ap)
-        d = np.sqrt(np.maximum(1.0 - ap - sigma ** 2, 0.0))
-        c1, c2, c3 = np.sqrt(ap) - d * np.sqrt(ab) / np.sqrt(1.0 - ab), d / np.sqrt(1.0 - ab), np.zeros(S)
-    else:
-        sigma, c1, c2, c3 = np.zeros(S), np.ones(S), np.zeros(S), np.zeros(S)
-        lam = _half_logsnr(ab)
-        for j in range(1, S):
-            h = _half_logsnr(ap[j]) - lam[j]
-            k = -np.sqrt(ap[j]) * np.expm1(-h)
-            c2[j] = np.sqrt(1.0 - ap[j]) / np.sqrt(1.0 - ab[j])
-            if j == S - 1:
-                c1[j] = k
-            else:
-                r = (lam[j] - lam[j + 1]) / h
-                c1[j], c3[j] = k * (1.0 + 1.0 / (2.0 * r)), -k / (2.0 * r)
-    a, b = np.sqrt(1.0 / ab), np.sqrt(1.0 / ab - 1)
-    if prediction != 'eps':
-        a, b = prediction_coefs(prediction, np.sqrt(ab), np.sqrt(1.0 - ab))[:2]
-    out = dict(tau=tau, a=a, b=b, c1=c1, c2=c2, c3=c3, sigma=sigma, level=np.append(1.0, np.sqrt(ab)))
-    if not all(np.all(np.isfinite(v)) for v in out.values()):
-        raise ValueError('sampler tables are not finite')
-    return out
-
-
-LEARNED_VARIANCE_LAMBDA = 0.001      # the default of the config key (Nichol & Dhariwal 2021, section 3.1)
-
-
-def parse_learned_variance(spec):
-    """The config key model.diffusion.learned_variance -> the argument of set_learned_variance: {"lambda": l} -> l, true or {} -> the
-    default 0.001, absent / null / false -> None (off)."""
-    if spec is None or spec is False:
-        return None
-    if spec is True:
-        return LEARNED_VARIANCE_LAMBDA
-    if not hasattr(spec, 'get') or not hasattr(spec, 'keys'):
-        raise ValueError('learned_variance: true or a dict with "lambda" is expected (got %r)' % (spec,))
-    for k in spec.keys():
-        if k != 'lambda':
-            raise ValueError('learned_variance: unknown key %r (known: "lambda")' % (k,))
-    lam = spec.get('lambda')
-    return LEARNED_VARIANCE_LAMBDA if lam is None else lam
-
-
-def ancestral_tables(alphas_cumprod, steps, *, walk='time', prediction='eps'):
-    """Tables of the respaced DDPM walk (Nichol & Dhariwal 2021, section 4) over `sampler_walk`'s timesteps tau, in the form of the
-    step tail: with ab_j = alphas_cumprod[tau[j]] and ab_{-1} = 1,
-
-        beta'_j = 1 - ab_j / ab_{j-1} ;  beta~'_j = beta'_j (1 - ab_{j-1}) / (1 - ab_j)
-        c1 = beta'_j sqrt(ab_{j-1}) / (1 - ab_j) ;  c2 = (1 - ab_{j-1}) sqrt(1 - beta'_j) / (1 - ab_j)      the posterior's mean
-
-    a, b as `sampler_tables` (by `prediction`); sigma = sqrt(beta~'), 0 at j = 0 -- the fixed small variance, which the learned-variance
-    tail reads only for that zero: the mark of the walk's last step; log_beta = log beta', log_beta_tilde = log beta~' with entry 0
-    set to entry 1 (beta~'_0 = 0; the Improved-DDPM convention, not log 1e-20; a one-step walk: log beta'_0).  steps = T gives the
-    schedule's own betas and posterior_mean_coef1/2.  Pure numpy, float64, no device.  Returns a dict: tau, a, b, c1, c2, sigma,
-    log_beta, log_beta_tilde ([S]) and level ([S + 1], as `sampler_tables`)."""
-    if not isinstance(walk, str):
-        walk = _explicit_walk(alphas_cumprod, steps, walk)
-        steps = int(walk.shape[0])
-    ac, T, S = _check_walk_args(alphas_cumprod, steps)
-    _check_prediction(prediction)
-    tau = sampler_walk(ac, S, walk)
-    ab = ac[tau]
-    ap = np.append(1.0, ab[:-1])
-    beta = 1.0 - ab / ap
-    bt = beta * (1.0 - ap) / (1.0 - ab)
-    c1, c2 = beta * np.sqrt(ap) / (1.0 - ab), (1.0 - ap) * np.sqrt(1.0 - beta) / (1.0 - ab)
-    sigma = np.sqrt(bt)
-    sigma[0] = 0.0
-    log_beta = np.log(beta)
-    with np.errstate(divide='ignore'):
-        log_bt = np.log(bt)
-    log_bt[0] = log_bt[1] if S > 1 else log_beta[0]
-    a, b = np.sqrt(1.0 / ab), np.sqrt(1.0 / ab - 1)
-    if prediction != 'eps':
-        a, b = prediction_coefs(prediction, np.sqrt(ab), np.sqrt(1.0 - ab))[:2]
-    out = dict(tau=tau, a=a, b=b, c1=c1, c2=c2, sigma=sigma, log_beta=log_beta, log_beta_tilde=log_bt, level=np.append(1.0, np.sqrt(ab)))
-    if not all(np.all(np.isfinite(v)) for v in out.values()):
-        raise ValueError('ancestral tables are not finite')
-    return out
-
-
-def hybrid_step_scalars(tables, t):
-    """The rows of sr3_train_step_ex2's step_scalars for the steps `t` (ints, 0-based, into `ancestral_tables(ac, T)`): float64 [n, 8]
-    = {a, b, c1, c2, log beta, log beta~ (clipped), last, 0}, last = 1 at t = 0."""
-    t = np.asarray(t, dtype=np.int64).reshape(-1)
-    out = np.zeros((t.shape[0], 8), dtype=np.float64)
-    for k, name in enumerate(('a', 'b', 'c1', 'c2', 'log_beta', 'log_beta_tilde')):
-        out[:, k] = np.asarray(tables[name], dtype=np.float64)[t]
-    out[:, 6] = (t == 0).astype(np.float64)
-    return out
-
-
-def widen_for_learned_variance(state):
-    """An existing checkpoint -> one a learned-variance network of twice the output rows loads: C zero rows are appended to
-    final_conv.block.3.weight and to its bias (C = the rows they have; v = 0 everywhere: sigma^2 the geometric midpoint of beta and beta~),
-    every other entry is kept.  `state`: a *_gen.pth state dict (any key prefix), or the dict of a *_opt.pth -- there the Adam moments
-    of those two parameters, the last two of the parameter table, are widened with zeros.  Returns a new dict; tensors that do not
-    change are shared with the input."""
-    def rows(t):
-        return torch.cat([t, torch.zeros_like(t)], 0)
-    if isinstance(state, dict) and 'optimizer' in state:
-        out = dict(state)
-        opt = dict(state['optimizer'])
-        st = dict(opt.get('state') or {})
-        for i in sorted(st.keys())[-2:]:       # final_conv.block.3.weight, .bias: the last two entries of the table
-            st[i] = {k: (rows(v) if k in ('exp_avg', 'exp_avg_sq') else v) for k, v in st[i].items()}
-        opt['state'] = st
-        out['optimizer'] = opt
-        return out
-    out = type(state)()
-    hit = 0
-    for k, v in state.items():
-        if k.endswith('final_conv.block.3.weight') or k.endswith('final_conv.block.3.bias'):
-            v = rows(v)
-            hit += 1
-        out[k] = v
-    if hit == 0:
-        raise ValueError('widen_for_learned_variance: no final_conv.block.3.weight / .bias in the state dict')
-    return out
-
-
-_SAMPLER_TABLES = ('a', 'b', 'c1', 'c2', 'c3', 'sigma', 'level', 'tau', 'log_beta', 'log_beta_tilde')
-
-_BUFFERS = ('betas', 'alphas_cumprod', 'alphas_cumprod_prev', 'sqrt_alphas_cumprod',
-            'sqrt_one_minus_alphas_cumprod', 'log_one_minus_alphas_cumprod', 'sqrt_recip_alphas_cumprod',
-            'sqrt_recipm1_alphas_cumprod', 'posterior_variance', 'posterior_log_variance_clipped',
-            'posterior_mean_coef1', 'posterior_mean_coef2')
+_CacheEnv = collections.namedtuple('_CacheEnv', 'device T arena freq generation')      # EngineDiffusion._cache_env
 
 
 class EngineDiffusion(nn.Module):
@@ -597,39 +186,29 @@ class EngineDiffusion(nn.Module):
         respaced DDPM walk of `ancestral_tables`, every step drawn with the network's own sigma (sr3_learned_var_step); eta is not read."""
         if steps is None:
             tabs, self.sampler = None, None
-        elif kind == 'ancestral':
+        else:
             if getattr(self, '_alphas_cumprod64', None) is None:
                 raise RuntimeError('set_sampler needs a noise schedule (set_new_noise_schedule first)')
-            if self.learned_variance is None:
+            if kind != 'ancestral':
+                _check_sampler_kind(kind)
+            elif self.learned_variance is None:
                 raise ValueError('sampler type "ancestral" is the learned-variance walk and needs model.diffusion.learned_variance '
                                  '(set_learned_variance); on a fixed variance the strided ancestral sampler is '
                                  '{"type": "ddim", "steps": S, "eta": 1.0}')
             if walk is None:
-                walk = 'time'
-            elif not isinstance(walk, str):
-                walk = [int(v) for v in sampler_walk(self._alphas_cumprod64, steps, walk)]
-            tabs = dict(ancestral_tables(self._alphas_cumprod64, steps, walk=walk, prediction=self.prediction), c3=None)
-            self._check_learned_variance(sampler='ancestral')
-            self.sampler = dict(type='ancestral', steps=int(steps), eta=1.0)
-            if walk != 'time':
-                self.sampler['walk'] = walk
-        else:
-            if getattr(self, '_alphas_cumprod64', None) is None:
-                raise RuntimeError('set_sampler needs a noise schedule (set_new_noise_schedule first)')
-            _check_sampler_kind(kind)
-            if walk is None:
                 walk = 'logsnr' if kind == 'dpmpp_2m' else 'time'
             elif not isinstance(walk, str):        # an explicit walk (a distilled student's): checked, then kept as a list of ints
                 walk = [int(v) for v in sampler_walk(self._alphas_cumprod64, steps, walk)]
-            tabs = sampler_tables(self._alphas_cumprod64, steps, eta, kind=kind, walk=walk, prediction=self.prediction)
-            self._check_tiled_sampler(True, getattr(self, 'tiling', None))
-            self._check_rules({}, True, None)
-            self._check_self_condition(self.self_condition is not None, True, None, None)
-            self.sampler = dict(type=kind, steps=int(steps), eta=float(eta))
-            if kind != 'ddim' or walk != 'time':
-                self.sampler['walk'] = walk
-            if kind == 'ddim':
+            if kind == 'ancestral':
+                tabs, eta = ancestral_tables(self._alphas_cumprod64, steps, walk=walk, prediction=self.prediction), 1.0
+            else:
+                tabs = sampler_tables(self._alphas_cumprod64, steps, eta, kind=kind, walk=walk, prediction=self.prediction)
+            if kind != 'dpmpp_2m':
                 tabs = dict(tabs, c3=None)         # a one-step rule keeps no history: no table, no buffer, the kernels without it
+            self._check_settings(sampler=kind)
+            self.sampler = dict(type=kind, steps=int(steps), eta=float(eta))
+            if kind == 'dpmpp_2m' or walk != 'time':
+                self.sampler['walk'] = walk
         dev = self.betas.device if hasattr(self, 'betas') else None
         for k in _SAMPLER_TABLES:                # the float64 tables rounded once to fp32; the walk as int32 (what k_embed reads)
             t = None if tabs is None or tabs.get(k) is None else torch.tensor(tabs[k], dtype=torch.int32 if k == 'tau' else torch.float32).to(dev)
@@ -675,10 +254,7 @@ class EngineDiffusion(nn.Module):
             self.tiling = None
         else:
             t = TL.parse_tiling(dict(tile=tile, overlap=overlap, batch=batch), self.denoise_fn.plan.divisor)
-            self._check_learned_variance(tiling=t)
-            self._check_tiled_sampler(self.sampler is not None, t)
-            self._check_rules({}, False, t)
-            self._check_self_condition(self.self_condition is not None, False, t, None)
+            self._check_settings(tiling=t)
             self.tiling = t
         self._loop_cache = {}
 
@@ -713,10 +289,7 @@ class EngineDiffusion(nn.Module):
         """the body of set_consistency / set_guidance / set_backprojection: the rule's validation, the compatibility check, the attribute"""
         cfg = rule.validate(self, *args)
         if cfg is not None:
-            self._check_learned_variance(rules={rule.name: cfg})
-            self._check_rules({rule.name: cfg}, self.sampler is not None, self.tiling)
-            if rule is X.GUIDANCE:
-                self._check_self_condition(self.self_condition is not None, False, None, cfg)
+            self._check_settings(**{rule.name: cfg})
         setattr(self, rule.name, cfg)
         self._loop_cache = {}
 
@@ -745,34 +318,18 @@ class EngineDiffusion(nn.Module):
             self.self_condition = None
         else:
             pf = X._number('self_condition prob', prob, lambda f: 0.0 <= f <= 1.0, 'lie in [0, 1]')
-            self._check_learned_variance(self_condition=True)
-            self._check_cond_augment(self.cond_augment, True)      # (before the channel count: the two ask for different ones)
-            lr = self.channels if self.conditional else 0
-            have, want = int(self.denoise_fn.plan.in_channel), lr + 2 * self.channels
-            if have != want:
-                raise ValueError('self-conditioning needs a UNet with in_channel %d (%d conditioning + 2 x %d image channels); this one has '
-                                 'in_channel %d' % (want, lr, self.channels, have))
-            self._check_self_condition(True, self.sampler is not None, self.tiling, self.guidance)
+
+            def channels():
+                lr = self.channels if self.conditional else 0
+                have, want = int(self.denoise_fn.plan.in_channel), lr + 2 * self.channels
+                if have != want:
+                    raise ValueError('self-conditioning needs a UNet with in_channel %d (%d conditioning + 2 x %d image channels); this one has '
+                                     'in_channel %d' % (want, lr, self.channels, have))
+            # (the channel count behind cond_augment's clause -- the two ask for different ones -- and in front of self-conditioning's own)
+            self._check_settings(self_condition=True, before=('self_condition', channels))
             self.self_condition = dict(prob=pf)
         self._self_cond_buf = None
         self._loop_cache = {}
-
-    def _check_self_condition(self, on, sampler, tiling, guidance):
-        """What self-conditioning does not go with (the style of x0_rules.check_rule); DESIGN.md section 6 says what each would need."""
-        if not on:
-            return
-        off = 'switch self-conditioning off (set_self_condition(None))'
-        if tiling is not None:
-            raise NotImplementedError('self-conditioning with tiling: the conditioning tiles are gathered once per chain and sr3_tiled_step '
-                                      'writes no x0 back into them; use whole-image steps (set_tiling(None)) or %s' % off)
-        if guidance is not None:
-            raise NotImplementedError('self-conditioning with guidance: the second forward and the guided x0 live inside sr3_guided_step, '
-                                      'behind the point where sr3_selfcond_x0_f32 reads the output; switch one of them off '
-                                      '(set_self_condition(None) / set_guidance(None))')
-        if sampler and self.variant == 'ddpm':
-            raise NotImplementedError('self-conditioning of the DDPM variant under a sampler (DDIM, DPM-Solver++): the forward of a '
-                                      'self-conditioned step runs through sr3_unet_forward, which has no step-index -> timestep map (t_map); '
-                                      'use the ancestral sampler (set_sampler(None)) or %s' % off)
 
     def set_cond_augment(self, max_level=None, sample_level=0.0, level_channel=True):
         """Noise conditioning augmentation (Ho et al. 2021, "Cascaded Diffusion Models"; Sahak et al. 2023): the network reads the
@@ -795,7 +352,7 @@ class EngineDiffusion(nn.Module):
             cfg['level_channel'] = bool(level_channel)
             if not self.conditional:
                 raise ValueError('cond_augment on an unconditional model: there is no conditioning image to augment')
-            self._check_cond_augment(cfg, self.self_condition is not None)
+            self._check_settings(cond_augment=cfg)
             if cfg['level_channel']:
                 have, want = int(self.denoise_fn.plan.in_channel), 2 * self.channels + 1
                 if have != want:
@@ -870,46 +427,59 @@ class EngineDiffusion(nn.Module):
             self._t_pending = None
             self.t_sampler.update(t.cpu().numpy(), terms[:, 0].detach().cpu().numpy())
 
-    def _check_learned_variance(self, sampler=None, tiling=None, rules=None, self_condition=None):
-        """What the learned-variance tail -- the "ancestral" sampler -- does not go with, over the settings as they are with the given ones
-        in place of theirs; DESIGN.md section 6 says what each would need.  Every one of them runs on a learned-variance network under
-        a DDIM or DPM-Solver++ sampler, with that sampler's table sigma."""
-        sp = getattr(self, 'sampler', None)
-        kind = sampler if sampler is not None else (None if sp is None else sp['type'])
-        if kind != 'ancestral':
-            return
-        how = ('; sample with {"type": "ddim", "steps": S, "eta": e} (set_sampler), which runs it on the prediction rows with the '
-               'table sigma')
-        if (tiling if tiling is not None else getattr(self, 'tiling', None)) is not None:
-            raise NotImplementedError('the learned-variance ancestral sampler with tiling: sr3_tiled_step blends eps tiles and has no '
-                                      'variance input' + how)
-        cfgs = dict({r.name: getattr(self, r.name, None) for r in X.RULES}, **(rules or {}))
-        for r in X.RULES:
-            if cfgs[r.name] is not None:
-                raise NotImplementedError('the learned-variance ancestral sampler with %s: the rule owns the whole tail of a step and '
-                                          'draws with the table sigma' % r.name + how)
-        if (self_condition if self_condition is not None else getattr(self, 'self_condition', None) is not None):
-            raise NotImplementedError('the learned-variance ancestral sampler with self-conditioning: sr3_selfcond_x0_f32 reads a '
-                                      'C-channel output' + how)
-
-    @staticmethod
-    def _check_cond_augment(cfg, self_condition):
-        """What noise conditioning augmentation does not go with; DESIGN.md section 6 says what it would need."""
-        if cfg is not None and cfg['level_channel'] and self_condition:
+    def _check_settings(self, before=None, **override):
+        """The one compatibility check of the settings: NotImplementedError where the settings as they are, with `override` in place of
+        theirs -- sampler (its type or None), tiling, consistency / guidance / backprojection (each rule's setting), self_condition (on or
+        off), cond_augment -- hold a pair that is not built; DESIGN.md section 6 says what each would need.  Every setter calls it with
+        its own new value, `_sample_shape` with the tiling the loop was handed.  The clauses in order: the learned-variance tail (the
+        "ancestral" sampler), cond_augment's level channel, the rules on x0 (x0_rules.check_rule), self-conditioning, tiled sampling of
+        the DDPM variant.  before = (clause, call): the caller's own validation, made in front of that clause ('self_condition' |
+        'tiled_sampler') where its place among the refusals is a promise (tests/settings_matrix.json)."""
+        s = dict({r.name: getattr(self, r.name) for r in X.RULES}, sampler=None if self.sampler is None else self.sampler['type'],
+                 tiling=self.tiling, self_condition=self.self_condition is not None, cond_augment=self.cond_augment)
+        assert set(override) <= set(s), override
+        s.update(override)
+        tiling, selfc, aug = s['tiling'], s['self_condition'], s['cond_augment']
+        ddpm_sampler = s['sampler'] is not None and self.variant == 'ddpm'
+        if s['sampler'] == 'ancestral':
+            # every one of these runs on a learned-variance network under a DDIM or DPM-Solver++ sampler, with that sampler's table sigma
+            how = ('; sample with {"type": "ddim", "steps": S, "eta": e} (set_sampler), which runs it on the prediction rows with the '
+                   'table sigma')
+            if tiling is not None:
+                raise NotImplementedError('the learned-variance ancestral sampler with tiling: sr3_tiled_step blends eps tiles and has no '
+                                          'variance input' + how)
+            for r in X.RULES:
+                if s[r.name] is not None:
+                    raise NotImplementedError('the learned-variance ancestral sampler with %s: the rule owns the whole tail of a step and '
+                                              'draws with the table sigma' % r.name + how)
+            if selfc:
+                raise NotImplementedError('the learned-variance ancestral sampler with self-conditioning: sr3_selfcond_x0_f32 reads a '
+                                          'C-channel output' + how)
+        if aug is not None and aug['level_channel'] and selfc:
             raise NotImplementedError('cond_augment with the level channel together with self-conditioning: a 10-channel input [LR | level '
                                       '| last x0 | x], for which the input conv has no MFMA form and no model was measured; use the blind '
                                       'form ("level_channel": false) or switch one of them off (set_cond_augment(None) / '
                                       'set_self_condition(None))')
-
-    def _check_rules(self, new, sampler, tiling):
-        """The one compatibility check of the rules on x0 (x0_rules.check_rule: "X with tiling", "X with Y", "X of the DDPM variant under
-        a sampler"), over the settings as they are with `new` (name -> setting) in place of its names'."""
-        cfgs = dict({r.name: getattr(self, r.name, None) for r in X.RULES}, **new)
-        for r in X.RULES:
-            X.check_rule(r, cfgs, sampler and self.variant == 'ddpm', tiling)
-
-    def _check_tiled_sampler(self, sampler, tiling):
-        if sampler and tiling is not None and self.variant == 'ddpm':
+        for r in X.RULES:                      # "X with tiling", "X with Y", "X of the DDPM variant under a sampler"
+            X.check_rule(r, s, ddpm_sampler, tiling)
+        if before is not None and before[0] == 'self_condition':
+            before[1]()
+        if selfc:
+            off = 'switch self-conditioning off (set_self_condition(None))'
+            if tiling is not None:
+                raise NotImplementedError('self-conditioning with tiling: the conditioning tiles are gathered once per chain and sr3_tiled_step '
+                                          'writes no x0 back into them; use whole-image steps (set_tiling(None)) or %s' % off)
+            if s['guidance'] is not None:
+                raise NotImplementedError('self-conditioning with guidance: the second forward and the guided x0 live inside sr3_guided_step, '
+                                          'behind the point where sr3_selfcond_x0_f32 reads the output; switch one of them off '
+                                          '(set_self_condition(None) / set_guidance(None))')
+            if ddpm_sampler:
+                raise NotImplementedError('self-conditioning of the DDPM variant under a sampler (DDIM, DPM-Solver++): the forward of a '
+                                          'self-conditioned step runs through sr3_unet_forward, which has no step-index -> timestep map (t_map); '
+                                          'use the ancestral sampler (set_sampler(None)) or %s' % off)
+        if before is not None and before[0] == 'tiled_sampler':
+            before[1]()
+        if ddpm_sampler and tiling is not None:
             raise NotImplementedError('tiled sampling of the DDPM variant under a sampler (DDIM, DPM-Solver++): the tiles run through sr3_unet_forward, '
                                       'which has no step-index -> timestep map (t_map); use the ancestral sampler (set_sampler(None)) '
                                       'or whole-image steps (set_tiling(None))')
@@ -989,16 +559,41 @@ class EngineDiffusion(nn.Module):
         return out
 
     # ---- the reverse loop ------------------------------------------------------------------------
+    def _cache_env(self, dev):
+        """What a captured graph bakes in besides its own buffers: the device, the schedule length, the arena in use
+        (EngineUNet.use_weights), the freq table and the plan's launch list (plan.generation changes with every set_option).  A
+        sampling key and a 'bpd' key both hold these five at positions 2 .. 6."""
+        un = self.denoise_fn
+        return _CacheEnv(str(dev), self.num_timesteps, un.weights().data_ptr(), un.freq.data_ptr(), un.plan.generation)
+
+    def _cached(self, key, new=None):
+        """`_loop_cache`'s one door.  new None: the state under `key`, moved to the most recently used end, or None.  Else: `new` goes in
+        behind at most max_cached_loops - 1 states of its own kind (sampling | 'bpd': an evaluation does not cost a sampling graph its
+        place, nor the other way round; a folder of mixed sizes alternates between a few states without recapturing), and what can never
+        be hit again is dropped: a state of another device or schedule, of an arena that is gone (with EMA weights the model has two)
+        or of a launch list that no longer exists."""
+        if new is None:
+            st = self._loop_cache.get(key)
+            if st is not None:
+                self._loop_cache[key] = self._loop_cache.pop(key)
+            return st
+        un, env, bpd = self.denoise_fn, _CacheEnv(*key[2:7]), key[0] == 'bpd'
+        arenas = {un.arena.data_ptr()} | ({un.ema_arena.data_ptr()} if un.ema_arena is not None else set())
+        live = set(un.plan._geometry_generation.values())
+        kept = [(k, v) for k, v in self._loop_cache.items() for e in [_CacheEnv(*k[2:7])]
+                if e.device == env.device and e.T == env.T and e.arena in arenas and e.freq == env.freq and e.generation in live]
+        mine, others = [e for e in kept if (e[0][0] == 'bpd') == bpd], [e for e in kept if (e[0][0] == 'bpd') != bpd]
+        self._loop_cache = dict(others + (mine[-(self.max_cached_loops - 1):] if self.max_cached_loops > 1 else []))
+        self._loop_cache[key] = new
+        return new
+
     def _loop_state(self, shape, cond_shape, dev, item_streams=False, tiles=None, consistency=None, guidance=None, backprojection=None,
                     self_condition=False, cond_augment=False):
-        # a captured graph bakes in the arena (the one in use: EngineUNet.use_weights), the freq table and the workspace pointer and
-        # the plan's launch list: key on all of them (plan.generation changes with every set_option); the workspace is private to the state.
+        # the buffers of a chain, a workspace private to the state and the captured graph, under a key of everything the graph bakes in.
         # item_streams: one torch generator per image of the batch (`item_seeds` of p_sample_loop) -- the generators are
         # registered with the captured graph, so they belong to the state and are re-seeded per loop
-        un = self.denoise_fn
         cfgs = dict(consistency=consistency, guidance=guidance, backprojection=backprojection)
-        key = (tuple(shape), None if cond_shape is None else tuple(cond_shape), str(dev), self.num_timesteps,
-               un.weights().data_ptr(), un.freq.data_ptr(), un.plan.generation, bool(item_streams),
+        key = (tuple(shape), None if cond_shape is None else tuple(cond_shape), *self._cache_env(dev), bool(item_streams),
                None if self.sampler is None else (self.sampler['steps'], self.sampler['eta'], self.sampler['type'],
                                                   self.sampler.get('walk', 'time') if isinstance(self.sampler.get('walk', 'time'), str)
                                                   else tuple(self.sampler['walk'])),
@@ -1008,40 +603,29 @@ class EngineDiffusion(nn.Module):
             key += ('self_condition',)
         if cond_augment:                       # (appended too: the state's cond is the augmented tensor, made once per chain)
             key += ('cond_augment',)
-        st = self._loop_cache.get(key)
-        if st is None:
-            st = dict(img=torch.empty(shape, device=dev), z=torch.empty(shape, device=dev),
-                      eps=torch.empty(shape, device=dev),
-                      cond=None if cond_shape is None else torch.empty(cond_shape, device=dev),
-                      step=torch.zeros(2, dtype=torch.int32, device=dev), graph=None, ws=E.Workspace(),      # [scratch, t]
-                      gens=[torch.Generator(device=dev) for _ in range(shape[0])] if item_streams else None)
-            if self.sampler is not None and self.sampler['type'] == 'ancestral':
-                st['out2'] = torch.empty((shape[0], 2 * shape[1]) + tuple(shape[2:]), device=dev)      # the prediction and the variance head
-            if self.sampler is not None and self._sampler_c3 is not None:
-                st['hist'] = torch.zeros(shape, device=dev)      # a multistep sampler: the previous step's x0 (_sample_loop zero-fills it per chain)
-            if tiles is not None:
-                self._tile_buffers(st, tiles, shape, cond_shape, dev)
-            st['self_condition'] = bool(self_condition)      # cond is [B, Cl + C, H, W]: the LR channels, then the last step's x0
-            st['cond_augment'] = bool(cond_augment)          # cond holds the augmented LR channels (and the level plane behind them)
-            for r in X.RULES:                  # the setting the state (and its captured graph) was built for, and the rule's buffers
-                if cfgs[r.name] is not None:
-                    st[r.name] = dict(cfgs[r.name])
-                    r.buffers(st, st[r.name], shape, cond_shape, dev)
-            # keep the states of a few image sizes alive (a folder of mixed sizes alternates between them without recapturing);
-            # what was built for another arena / schedule / set of plan options can never be hit again: dropped
-            # (with EMA weights the model has two arenas, and a state built on either can be hit again)
-            arenas = {un.arena.data_ptr()} | ({un.ema_arena.data_ptr()} if un.ema_arena is not None else set())
-            live = set(un.plan._geometry_generation.values())
-            kept = [(k, v) for k, v in self._loop_cache.items()
-                    if k[2:4] == key[2:4] and k[4] in arenas and k[5] == key[5] and k[6] in live]
-            # (calc_bpd_loop's states keep the same fields at the same positions and are pruned by them, but count against a limit of
-            # their own, `_bpd_state`: an evaluation does not cost a sampling graph its place, nor the other way round)
-            bpd, kept = [e for e in kept if e[0][0] == 'bpd'], [e for e in kept if e[0][0] != 'bpd']
-            self._loop_cache = dict(bpd + (kept[-(self.max_cached_loops - 1):] if self.max_cached_loops > 1 else []))
-            self._loop_cache[key] = st
-        else:
-            self._loop_cache[key] = self._loop_cache.pop(key)      # most recently used last
-        return st
+        st = self._cached(key)
+        if st is not None:
+            return st
+        st = dict(img=torch.empty(shape, device=dev), z=torch.empty(shape, device=dev),
+                  eps=torch.empty(shape, device=dev),
+                  cond=None if cond_shape is None else torch.empty(cond_shape, device=dev),
+                  step=torch.zeros(2, dtype=torch.int32, device=dev), graph=None, ws=E.Workspace(),      # [scratch, t]
+                  gens=[torch.Generator(device=dev) for _ in range(shape[0])] if item_streams else None)
+        if self.sampler is not None and self.sampler['type'] == 'ancestral':
+            st['out2'] = torch.empty((shape[0], 2 * shape[1]) + tuple(shape[2:]), device=dev)      # the prediction and the variance head
+        if self.sampler is not None and self._sampler_c3 is not None:
+            st['hist'] = torch.zeros(shape, device=dev)      # a multistep sampler: the previous step's x0 (_begin_chain zero-fills it per chain)
+        if tiles is not None:
+            self._tile_buffers(st, tiles, shape, cond_shape, dev)
+        st['self_condition'] = bool(self_condition)      # cond is [B, Cl + C, H, W]: the LR channels, then the last step's x0
+        st['cond_augment'] = bool(cond_augment)          # cond holds the augmented LR channels (and the level plane behind them)
+        for r in X.RULES:                  # the setting the state (and its captured graph) was built for, and the rule's buffers
+            if cfgs[r.name] is not None:
+                st[r.name] = dict(cfgs[r.name])
+                r.buffers(st, st[r.name], shape, cond_shape, dev)
+        # what one step writes that a chain reads again: `_capture` puts these back behind its warm-up step
+        st['dirty'] = ('img', 'step') + (('hist',) if 'hist' in st else ()) + (('cond',) if self_condition else ())
+        return self._cached(key, st)
 
     def _tile_buffers(self, st, tiles, shape, cond_shape, dev):
         """What a tiled loop's state holds besides the whole-image tensors: the grid's origins and windows on the device, the chunk
@@ -1094,70 +678,81 @@ class EngineDiffusion(nn.Module):
                 self._sampler_tau if self.variant == 'ddpm' else None, self._sampler_c3, self.sampler['eta'] > 0.0)
 
     def _one_step(self, st, draw_noise=True):
-        """One iteration of the loop on the rule of `_step_rule`: z ~ N(0, 1) (torch's graph-safe Philox) where the rule is noisy --
-        otherwise nothing is drawn and the step gets no z (st['z_used'] records it): a graph captured from it has no RNG node -- then
-        sr3_reverse_step: UNet forward with the p_sample update and the counter decrement inside the output conv's kernel.  A state
-        with a grid (the tiled loop) instead runs, per chunk of tiles, a gather out of the running image and one UNet forward at the
-        tile geometry (level / timestep from the device counter), then the fused tail on the full image -- blend of the tiles' eps,
-        p_sample update, counter decrement (sr3_tiled_step).  A state with a rule on x0 (x0_rules.py: set_consistency, set_guidance,
-        set_backprojection) runs one UNet forward that stores its output in st['eps'], then the rule's tail on the whole image in place
-        of the fused one.  A self-conditioned state (set_self_condition) runs unfused too: forward, then sr3_selfcond_x0_f32 writes the
-        step's x0 into the self-conditioning channels of st['cond'] for the next step's forward, then the tail.  What is fed back is the
-        network's own clamped x0, clamp(a x - b out), before any rule on x0 touches it: that is what it was trained on.  A multistep rule passes its c3 table and the state's history buffer along.  st['eps'] keeps the step's
-        (blended) eps for the parity checks that read it."""
-        tables, level, t_map, c3, noisy = rule = self._step_rule()
+        """One iteration of the loop: the rule's tables (`_step_rule`), z ~ N(0, 1) (torch's graph-safe Philox) where the rule is noisy --
+        otherwise nothing is drawn and the step gets no z (st['z_used'] records it): a graph captured from it has no RNG node -- then the
+        step form the state was built for, one of the five `_step_*` below.  A multistep rule passes its c3 table and the state's
+        history buffer along.  st['eps'] keeps the step's (blended) eps for the parity checks that read it."""
+        rule = self._step_rule()
+        c3, noisy = rule[3:]
         st['z_used'] = noisy
         st['tables'] = rule                    # a captured graph bakes their addresses in: they live as long as the state
         if noisy and draw_noise:
             self._draw(st['z'], st['gens'])
-        img, z = st['img'], st['z'] if noisy else None
-        hist = None if c3 is None else st['hist']
-        g = st.get('grid')
         x0_rule = next((r for r in X.RULES if st.get(r.name) is not None), None)
-        if st.get('self_condition'):
-            # unfused, because x0 must be taken before x is overwritten: the forward stores its output, sr3_selfcond_x0_f32 writes
-            # clamp(a x - b out) at the device counter's row into the last C channels of cond in place -- the network's own x0, before
-            # any rule touches it: what it was trained on -- then the tail: the rule's own, or the plain update and the decrement
-            # (bit-identical to the fused call, include/sr3_mi355x.h)
-            assert t_map is None and g is None and x0_rule is not X.GUIDANCE      # (_check_self_condition refused them)
-            lib, cond, step = L.load(), st['cond'], st['step'][1:]
-            B, Cc, H, W = img.shape
-            self.denoise_fn(img, None, cond=cond, level_table=level, step_dev=step, out=st['eps'], ws=st['ws'])
-            L.check(lib.sr3_selfcond_x0_f32(L.ptr(img), L.ptr(st['eps']), L.ptr(tables[0]), L.ptr(tables[1]), L.ptr(step), None, 1, B, Cc, H, W,
-                                            L.ptr(cond), cond.shape[1], cond.shape[1] - Cc, self._stream(img.device)))
-            if x0_rule is not None:
-                x0_rule.tail(st, st[x0_rule.name], z, tables, c3, hist, None)
-            else:
-                L.check(lib.sr3_p_sample_step_hist(L.ptr(img), L.ptr(st['eps']), L.ptr(z), *[L.ptr(t) for t in tables], L.ptr(step), None, 0,
-                                                   B, Cc * H * W, 1, L.ptr(c3), L.ptr(hist), self._stream(img.device)))
-                L.check(lib.sr3_step_decrement(L.ptr(step), self._stream(img.device)))
-            return
-        if st.get('out2') is not None:
-            # learned variance: the forward stores all 2C rows (level / timestep from the device counter, which only the tail moves),
-            # then the tail draws with the network's own sigma (sr3_learned_var_step)
-            assert g is None and x0_rule is None and c3 is None      # (_check_learned_variance refused them)
-            B, Cc, H, W = img.shape
-            self.denoise_fn(img, None, cond=st['cond'], level_table=level, step_dev=st['step'][1:], out=st['out2'], ws=st['ws'],
-                            full=True, t_map=t_map)
-            L.check(L.load().sr3_learned_var_step(L.ptr(img), L.ptr(st['out2']), L.ptr(z), B, Cc, H, W, *[L.ptr(t) for t in tables],
-                                                  L.ptr(self._sampler_log_beta), L.ptr(self._sampler_log_beta_tilde), L.ptr(st['step']),
-                                                  1, None, None, self._stream(img.device)))
-            return
-        if x0_rule is not None:
-            # the forward stores its output (level / timestep from the device counter, which only the tail's last kernel moves), then
-            # the rule's tail: what it does to x0, the p_sample update and the counter decrement
-            assert t_map is None and g is None      # (_check_rules refused both)
+        form = (self._step_selfcond if st.get('self_condition') else self._step_learned_var if st.get('out2') is not None else
+                self._step_rule_tail if x0_rule is not None else self._step_fused if st.get('grid') is None else self._step_tiled)
+        form(st, rule, st['z'] if noisy else None, None if c3 is None else st['hist'], x0_rule)
 
-            def forward(cond, out):
-                self.denoise_fn(img, None, cond=cond, level_table=level, step_dev=st['step'][1:], out=out, ws=st['ws'])
-            forward(st['cond'], st['eps'])
-            x0_rule.tail(st, st[x0_rule.name], z, tables, c3, hist, forward)
-            return
-        if g is None:
-            self.denoise_fn.reverse_step(img, z, tables, st['step'], cond=st['cond'], level_table=level, clip_denoised=True,
-                                         eps_out=st['eps'], ws=st['ws'], t_map=t_map, c3=c3, hist=hist)
-            return
-        assert t_map is None      # (_sample_loop refused it, _check_tiled_sampler: the tiles run through sr3_unet_forward, which has no t_map)
+    def _step_selfcond(self, st, rule, z, hist, x0_rule):
+        """A self-conditioned state (set_self_condition), unfused because x0 must be taken before x is overwritten: the forward stores
+        its output, sr3_selfcond_x0_f32 writes clamp(a x - b out) at the device counter's row into the last C channels of st['cond'] in
+        place, for the next step's forward -- the network's own clamped x0, before any rule on x0 touches it: what it was trained on --
+        then the tail: the rule's own, or sr3_p_sample_step_hist and sr3_step_decrement (bit-identical to the fused call,
+        include/sr3_mi355x.h)."""
+        tables, level, t_map, c3, _ = rule
+        assert t_map is None and st.get('grid') is None and x0_rule is not X.GUIDANCE      # (_check_settings refused them)
+        lib, img, cond, step = L.load(), st['img'], st['cond'], st['step'][1:]
+        B, Cc, H, W = img.shape
+        self.denoise_fn(img, None, cond=cond, level_table=level, step_dev=step, out=st['eps'], ws=st['ws'])
+        L.check(lib.sr3_selfcond_x0_f32(L.ptr(img), L.ptr(st['eps']), L.ptr(tables[0]), L.ptr(tables[1]), L.ptr(step), None, 1, B, Cc, H, W,
+                                        L.ptr(cond), cond.shape[1], cond.shape[1] - Cc, self._stream(img.device)))
+        if x0_rule is not None:
+            x0_rule.tail(st, st[x0_rule.name], z, tables, c3, hist, None)
+        else:
+            L.check(lib.sr3_p_sample_step_hist(L.ptr(img), L.ptr(st['eps']), L.ptr(z), *[L.ptr(t) for t in tables], L.ptr(step), None, 0,
+                                               B, Cc * H * W, 1, L.ptr(c3), L.ptr(hist), self._stream(img.device)))
+            L.check(lib.sr3_step_decrement(L.ptr(step), self._stream(img.device)))
+
+    def _step_learned_var(self, st, rule, z, hist, x0_rule):
+        """The "ancestral" sampler of a learned-variance model: the forward stores all 2C rows in st['out2'] (level / timestep from the
+        device counter, which only the tail moves), then sr3_learned_var_step draws with the network's own sigma."""
+        tables, level, t_map, c3, _ = rule
+        assert st.get('grid') is None and x0_rule is None and c3 is None      # (_check_settings refused them)
+        img = st['img']
+        B, Cc, H, W = img.shape
+        self.denoise_fn(img, None, cond=st['cond'], level_table=level, step_dev=st['step'][1:], out=st['out2'], ws=st['ws'],
+                        full=True, t_map=t_map)
+        L.check(L.load().sr3_learned_var_step(L.ptr(img), L.ptr(st['out2']), L.ptr(z), B, Cc, H, W, *[L.ptr(t) for t in tables],
+                                              L.ptr(self._sampler_log_beta), L.ptr(self._sampler_log_beta_tilde), L.ptr(st['step']),
+                                              1, None, None, self._stream(img.device)))
+
+    def _step_rule_tail(self, st, rule, z, hist, x0_rule):
+        """A state with a rule on x0 (x0_rules.py: set_consistency, set_guidance, set_backprojection): one UNet forward that stores its
+        output in st['eps'] (level / timestep from the device counter, which only the tail's last kernel moves), then the rule's tail
+        on the whole image in place of the fused one: what it does to x0, the p_sample update and the counter decrement."""
+        tables, level, t_map, c3, _ = rule
+        assert t_map is None and st.get('grid') is None      # (_check_settings refused both)
+        img = st['img']
+
+        def forward(cond, out):
+            self.denoise_fn(img, None, cond=cond, level_table=level, step_dev=st['step'][1:], out=out, ws=st['ws'])
+        forward(st['cond'], st['eps'])
+        x0_rule.tail(st, st[x0_rule.name], z, tables, c3, hist, forward)
+
+    def _step_fused(self, st, rule, z, hist, x0_rule):
+        """The plain step, one engine call (sr3_reverse_step): UNet forward with the p_sample update and the counter decrement inside
+        the output conv's kernel."""
+        tables, level, t_map, c3, _ = rule
+        self.denoise_fn.reverse_step(st['img'], z, tables, st['step'], cond=st['cond'], level_table=level, clip_denoised=True,
+                                     eps_out=st['eps'], ws=st['ws'], t_map=t_map, c3=c3, hist=hist)
+
+    def _step_tiled(self, st, rule, z, hist, x0_rule):
+        """A state with a grid (the tiled loop): per chunk of tiles a gather out of the running image (sr3_tile_gather) and one UNet
+        forward at the tile geometry (level / timestep from the device counter), then the fused tail on the full image -- blend of the
+        tiles' eps, p_sample update, counter decrement (sr3_tiled_step_hist)."""
+        tables, level, t_map, c3, _ = rule
+        assert t_map is None      # (_check_settings refused it: the tiles run through sr3_unet_forward, which has no t_map)
+        img, g = st['img'], st['grid']
         for first, n in st['chunks']:
             xt = st['x_tiles'][:n]
             self._gather_tiles(st, img, xt, first, n)
@@ -1169,45 +764,86 @@ class EngineDiffusion(nn.Module):
                                              *[L.ptr(t) for t in tables], L.ptr(st['step']), 1, L.ptr(st['eps']),
                                              self._stream(img.device), L.ptr(c3), L.ptr(hist)))
 
-    def _capture(self, st):
-        dev = st['img'].device
-        # one eager step on scratch data first (lazy kernel attributes, allocator warm-up), with the
-        # RNG state restored afterwards so a seed reproduces the reference's draw sequence
+    def _capture(self, st, step=None):
+        """st['graph'] <- one `step(st)` (None: `_one_step`) captured as a hipGraph.  One eager step first (lazy kernel attributes,
+        allocator warm-up) on a side stream -- or, where a rule asks for it, on the stream the capture runs on (torch's shared capture
+        stream): see x0_rules.Backprojection -- behind which the tensors the state declares dirty, the default RNG state and the
+        per-item generators are put back, so a seed reproduces the reference's draw sequence."""
+        step = self._one_step if step is None else step
+        dev = st['step'].device
         rng = torch.cuda.get_rng_state(dev)
         gens = st['gens'] or []
         gstate = [g.get_state() for g in gens]
-        keep_img = st['img'].clone()
-        keep_step = st['step'].clone()
-        keep_hist = st['hist'].clone() if st.get('hist') is not None else None
-        keep_cond = st['cond'].clone() if st.get('self_condition') else None      # (the warm-up step writes its x0 into it)
+        keep = [(st[k], st[k].clone()) for k in st['dirty']]
         g = torch.cuda.CUDAGraph()
         cap = None
         if any(r.warm_on_capture_stream and st.get(r.name) is not None for r in X.RULES):
-            # the warm-up runs on the stream the capture runs on (torch's shared capture stream): see x0_rules.Backprojection
             cap = torch.cuda.graph(g)
             side = cap.capture_stream
         else:
             side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            self._one_step(st)
+            step(st)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
-        st['img'].copy_(keep_img)
-        st['step'].copy_(keep_step)
-        if keep_hist is not None:
-            st['hist'].copy_(keep_hist)
-        if keep_cond is not None:
-            st['cond'].copy_(keep_cond)
+        for t, saved in keep:
+            t.copy_(saved)
         torch.cuda.set_rng_state(rng, dev)
         for gen, gs in zip(gens, gstate):
             gen.set_state(gs)
         for gen in gens:                       # (the default generator registers itself at capture_begin; these do not)
             g.register_generator_state(gen)
         with (cap if cap is not None else torch.cuda.graph(g)):
-            self._one_step(st)
+            step(st)
         # capture does not execute; state is untouched
         st['graph'] = g
+
+    def _run_steps(self, st, n, step, z_of=None, after=None, progress=False):
+        """The n iterations i = n - 1 .. 0 of a chain on a state whose counter stands at n - 1: replays of the state's graph (captured
+        here on first use) under use_graph, else eager calls of `step`; z_of (the injected noise of the parity tests: i -> step i's z,
+        or None for zeros) makes the loop eager and the step draw nothing.  after(i): what the caller does behind each step."""
+        use_graph = self.use_graph and z_of is None
+        if use_graph and st['graph'] is None:
+            self._capture(st, step)
+        it = reversed(range(n))
+        if progress:
+            try:
+                from tqdm import tqdm
+                it = tqdm(it, desc='sampling loop time step', total=n)
+            except ImportError:
+                pass
+        for i in it:
+            if use_graph:
+                st['graph'].replay()
+                if 'replays' in st:
+                    st['replays'] += 1
+            elif z_of is not None:
+                z = z_of(i)
+                st['z'].zero_() if z is None else st['z'].copy_(z)
+                step(st, draw_noise=False)
+            else:
+                step(st)
+            if after is not None:
+                after(i)
+
+    @staticmethod
+    def _item_seeds(who, item_seeds, noise_seq, batch):
+        """`item_seeds` as a list of ints, one per image, or None; it excludes an injected noise sequence"""
+        if item_seeds is None:
+            return None
+        item_seeds = [int(v) for v in item_seeds]
+        if len(item_seeds) != batch:
+            raise L.Sr3Error('%s: %d item_seeds for a batch of %d' % (who, len(item_seeds), batch))
+        if noise_seq is not None:
+            raise L.Sr3Error('%s: item_seeds and noise_seq exclude each other' % who)
+        return item_seeds
+
+    @staticmethod
+    def _seed_items(st, item_seeds):
+        if item_seeds is not None:
+            for g, v in zip(st['gens'], item_seeds):
+                g.manual_seed(v)
 
     @torch.no_grad()
     def p_sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None, consistency_target=None,
@@ -1221,12 +857,10 @@ class EngineDiffusion(nn.Module):
         t = self.tiling
         if t is not None:
             shape = tuple(x_in) if not self.conditional else tuple(x_in.shape)
-            if len(shape) == 4 and (shape[2] > t['tile'][0] or shape[3] > t['tile'][1]):
-                return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, tiling=t,
-                                         consistency_target=consistency_target, backprojection_target=backprojection_target,
-                                         cond_noise=cond_noise)
-        return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, consistency_target=consistency_target,
-                                 backprojection_target=backprojection_target, cond_noise=cond_noise)
+            if not (len(shape) == 4 and (shape[2] > t['tile'][0] or shape[3] > t['tile'][1])):
+                t = None                       # (an input the tile covers takes the whole-image loop)
+        return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, tiling=t,
+                                 consistency_target=consistency_target, backprojection_target=backprojection_target, cond_noise=cond_noise)
 
     @torch.no_grad()
     def p_sample_loop_tiled(self, x_in, continous=False, *, tile, overlap, tile_batch=None, x_T=None, noise_seq=None, item_seeds=None,
@@ -1248,45 +882,62 @@ class EngineDiffusion(nn.Module):
         not depend on which batch it rides in (sr3_hip.dist.ValWave batches the validation items the reference's infer.py /
         sr.py feed one by one, infer.py:67-71).  Under a sampler (set_sampler) the loop takes its S steps instead of T, i counts
         the step index S-1 .. 0 (what `noise_seq` and the snapshot stride 1 | S // 10 go by), and eta = 0 draws x_T only.  Under
-        set_consistency every step is an LR-consistent one (`_one_step`), towards the block means of the conditioning image or
-        `consistency_target`.  Under set_guidance every step is a guided one.  Under set_backprojection every step is a back-projected
-        one, towards `backprojection_target` or the down-sampled conditioning image.  Under set_cond_augment the state's cond is built
-        once per chain, after x_T is drawn, from the clean conditioning image at sample_level (sr3_cond_augment_f32; the noise from the
-        chain's own source -- the per-item generators, torch.randn, or `cond_noise`); the first snapshot and the rules' targets are the
-        clean image's."""
+        a rule on x0 every step is that rule's (`_one_step`), towards its target (p_sample_loop).  Under set_cond_augment the state's
+        cond is built once per chain, after x_T is drawn, from the clean conditioning image at sample_level (sr3_cond_augment_f32; the
+        noise from the chain's own source -- the per-item generators, torch.randn, or `cond_noise`); the first snapshot and the rules'
+        targets are the clean image's.  Three parts: `_sample_shape` checks and sizes, `_begin_chain` fills the state, `_run_steps`
+        runs it."""
         cfgs = {r.name: getattr(self, r.name) for r in X.RULES}
         targets = dict(consistency=consistency_target, backprojection=backprojection_target)
+        cond, shape, cond_shape, tiles, item_seeds = self._sample_shape(x_in, cfgs, targets, tiling, noise_seq, item_seeds, cond_noise)
+        dev, selfc, aug = self.betas.device, self.self_condition is not None, self.cond_augment
+        T = self.num_timesteps if self.sampler is None else self.sampler['steps']      # iterations of the loop
+        st = self._loop_state(shape, cond_shape, dev, item_streams=item_seeds is not None, tiles=tiles, self_condition=selfc,
+                              cond_augment=aug is not None, **cfgs)
+        self._begin_chain(st, T, cond, cfgs, targets, x_T, item_seeds, cond_noise)
+        inter = 1 | (T // 10)
+        B = shape[0]
+        ret = torch.empty((B * (sum(1 for i in range(T) if i % inter == 0) + 1),) + shape[1:], device=dev)
+        ret[:B].copy_(cond if (selfc or aug is not None) and cond is not None else st['cond'] if cond is not None else st['img'])
+        k = [1]
+
+        def snapshot(i):
+            if i % inter == 0:
+                ret[k[0] * B:(k[0] + 1) * B].copy_(st['img'])
+                k[0] += 1
+        z_of = None if noise_seq is None else (lambda i: noise_seq[i] if i > 0 or self.variant == 'ddpm' else None)
+        self._run_steps(st, T, self._one_step, z_of, snapshot, progress=self.show_progress)
+        if (not self.conditional) and self.variant == 'ddpm':
+            return st['img'].clone()            # ddpm diffusion.py:215 returns img, ignoring `continous`
+        return ret if continous else ret[-1]
+
+    def _sample_shape(self, x_in, cfgs, targets, tiling, noise_seq, item_seeds, cond_noise):
+        """The first part of `_sample_loop`: everything is validated here, before anything is written -- the targets, the settings against
+        the tiling the loop was handed, the device, the shapes -- and the plan is set to the geometry the forwards run at (the tile's,
+        under tiling).  -> (the conditioning image on the device or None, the image shape, the shape of the state's cond, the tiled
+        loop's grid / batch / key or None, item_seeds as ints)."""
         for r in X.RULES:
             if cfgs[r.name] is None and targets.get(r.name) is not None:
                 raise ValueError('%s is given but %s is off (%s / the "%s" key)' % (r.target_kw, r.noun, r.setter, r.name))
-            X.check_rule(r, cfgs, self.sampler is not None and self.variant == 'ddpm', tiling)
-            if cfgs[r.name] is not None and r.target_kw is not None and not self.conditional and targets[r.name] is None:
-                raise NotImplementedError('%s on an unconditional model needs %s=: there is no conditioning image to %s'
-                                          % (r.noun, r.target_kw, r.target_from))
-        selfc = self.self_condition is not None
-        self._check_learned_variance(tiling=tiling)
-        self._check_self_condition(selfc, self.sampler is not None, tiling, cfgs.get('guidance'))
-        aug = self.cond_augment
-        self._check_cond_augment(aug, selfc)
-        if cond_noise is not None and aug is None:
-            raise ValueError('cond_noise is given but noise conditioning augmentation is off (set_cond_augment / the "cond_augment" key)')
-        dev = self.betas.device
-        if dev.type != 'cuda':
-            raise L.Sr3Error('p_sample_loop needs the model on a GPU (set gpu_ids); there is no CPU fallback')
-        T = self.num_timesteps if self.sampler is None else self.sampler['steps']      # iterations of the loop
-        inter = 1 | (T // 10)
+        aug, dev = self.cond_augment, self.betas.device
+
+        def own():                            # (the loop's own refusals stand in front of the last clause, as they always have)
+            for r in X.RULES:
+                if cfgs[r.name] is not None and r.target_kw is not None and not self.conditional and targets[r.name] is None:
+                    raise NotImplementedError('%s on an unconditional model needs %s=: there is no conditioning image to %s'
+                                              % (r.noun, r.target_kw, r.target_from))
+            if cond_noise is not None and aug is None:
+                raise ValueError('cond_noise is given but noise conditioning augmentation is off (set_cond_augment / the "cond_augment" key)')
+            if dev.type != 'cuda':
+                raise L.Sr3Error('p_sample_loop needs the model on a GPU (set gpu_ids); there is no CPU fallback')
+        self._check_settings(tiling=tiling, before=('tiled_sampler', own))
         if not self.conditional:
             shape = tuple(x_in)
             cond = None
         else:
             cond = x_in.to(dev, torch.float32).contiguous()
             shape = tuple(cond.shape)
-        if item_seeds is not None:
-            item_seeds = [int(v) for v in item_seeds]
-            if len(item_seeds) != shape[0]:
-                raise L.Sr3Error('p_sample_loop: %d item_seeds for a batch of %d' % (len(item_seeds), shape[0]))
-            if noise_seq is not None:
-                raise L.Sr3Error('p_sample_loop: item_seeds and noise_seq exclude each other')
+        item_seeds = self._item_seeds('p_sample_loop', item_seeds, noise_seq, shape[0])
         if len(shape) != 4:
             raise L.Sr3Error('p_sample_loop: a (B, C, H, W) image or shape is expected (got %s)' % (shape,))
         # the image size comes from the input, as in the reference (`shape = x.shape`); the launch list -- and with it
@@ -1295,9 +946,7 @@ class EngineDiffusion(nn.Module):
             if cfgs[r.name] is not None:
                 r.check_target(cfgs[r.name], shape, targets.get(r.name))
         tiles = None
-        if tiling is not None:
-            # tiled: the plan runs at the TILE's geometry; everything is validated here, before anything is written
-            self._check_tiled_sampler(self.sampler is not None, tiling)
+        if tiling is not None:                 # tiled: the plan runs at the TILE's geometry
             (th, tw), o = tiling['tile'], tiling['overlap']
             grid = TL.TileGrid(shape[2], shape[3], th, tw, o, self.denoise_fn.plan.divisor)
             batch = min(16, shape[0] * grid.n_tiles) if tiling['batch'] is None else int(tiling['batch'])
@@ -1306,25 +955,28 @@ class EngineDiffusion(nn.Module):
         else:
             self.denoise_fn.plan.set_geometry(shape[2], shape[3])
         cond_shape = None if cond is None else shape
-        if selfc:      # the state's cond: the LR channels (none for an unconditional model), then the last step's x0
+        if self.self_condition is not None:      # the state's cond: the LR channels (none for an unconditional model), then the last step's x0
             cond_shape = (shape[0], (0 if cond is None else shape[1]) + shape[1]) + shape[2:]
         elif aug is not None and aug['level_channel']:      # the (augmented) LR channels, then the level plane
             cond_shape = (shape[0], shape[1] + 1) + shape[2:]
         if cond_noise is not None and (tuple(cond_noise.shape) != shape or cond_noise.device != dev or cond_noise.dtype != torch.float32):
             raise L.Sr3Error('p_sample_loop: cond_noise must be an fp32 tensor of the conditioning image\'s shape %s on %s' % (shape, dev))
-        st = self._loop_state(shape, cond_shape, dev, item_streams=item_seeds is not None, tiles=tiles, self_condition=selfc,
-                              cond_augment=aug is not None, **cfgs)
+        return cond, shape, cond_shape, tiles, item_seeds
+
+    def _begin_chain(self, st, T, cond, cfgs, targets, x_T, item_seeds, cond_noise):
+        """The second part: the state at the start of a chain of T steps, in the order every chain has made its draws and writes in --
+        the generators seeded, x_T, the state's cond, the rules' targets (from the clean conditioning image), the augmentation, the
+        conditioning tiles, a zero history, the counter."""
+        shape, dev, aug = tuple(st['img'].shape), st['img'].device, self.cond_augment
         self.denoise_fn.ensure_derived()       # a replayed graph does not pass through EngineUNet.forward
-        if item_seeds is not None:
-            for g, v in zip(st['gens'], item_seeds):
-                g.manual_seed(v)
+        self._seed_items(st, item_seeds)
         if x_T is not None:
             st['img'].copy_(x_T)
         elif item_seeds is not None:
             self._draw(st['img'], st['gens'])
         else:
             st['img'].copy_(torch.randn(shape, device=dev))
-        if selfc:                              # the LR channels once, and no estimate of x0 yet
+        if st['self_condition']:               # the LR channels once, and no estimate of x0 yet
             st['cond'].zero_()
             if cond is not None:
                 st['cond'][:, :shape[1]].copy_(cond)
@@ -1337,44 +989,11 @@ class EngineDiffusion(nn.Module):
                 r.prepare(st, cfgs[r.name], shape, targets.get(r.name), dev)
         if aug is not None:
             self._augment_sampling_cond(st, aug, cond, cond_noise)
-        if tiles is not None and cond is not None:      # the conditioning tensor does not change over the chain: cut into tiles once
+        if st.get('grid') is not None and cond is not None:      # the conditioning tensor does not change over the chain: cut into tiles once
             self._gather_tiles(st, st['cond'], st['cond_tiles'], 0, st['cond_tiles'].shape[0])
         if st.get('hist') is not None:         # the first step's c3 is 0, but 0 * (whatever the last chain left, a NaN for one) is not 0
             st['hist'].zero_()
         st['step'].fill_(T - 1)                # (slot 1 = t of the next step; slot 0 is the step's scratch copy)
-        n_snap = sum(1 for i in range(T) if i % inter == 0)
-        B = shape[0]
-        ret = torch.empty((B * (n_snap + 1),) + shape[1:], device=dev)
-        ret[:B].copy_(cond if (selfc or aug is not None) and cond is not None else st['cond'] if cond is not None else st['img'])
-        use_graph = self.use_graph and noise_seq is None
-        if use_graph and st['graph'] is None:
-            self._capture(st)
-        it = reversed(range(T))
-        if self.show_progress:
-            try:
-                from tqdm import tqdm
-                it = tqdm(it, desc='sampling loop time step', total=T)
-            except ImportError:
-                pass
-        k = 1
-        for i in it:
-            if use_graph:
-                st['graph'].replay()
-            else:
-                if noise_seq is not None:
-                    if i > 0 or self.variant == 'ddpm':
-                        st['z'].copy_(noise_seq[i])
-                    else:
-                        st['z'].zero_()
-                    self._one_step(st, draw_noise=False)
-                else:
-                    self._one_step(st)
-            if i % inter == 0:
-                ret[k * B:(k + 1) * B].copy_(st['img'])
-                k += 1
-        if (not self.conditional) and self.variant == 'ddpm':
-            return st['img'].clone()            # ddpm diffusion.py:215 returns img, ignoring `continous`
-        return ret if continous else ret[-1]
 
     def _augment_sampling_cond(self, st, aug, cond, cond_noise):
         """The LR channels of st['cond'] (and the level plane behind them) <- the clean `cond` at sample_level, once per chain.  Level 0
@@ -1410,16 +1029,14 @@ class EngineDiffusion(nn.Module):
     def _bpd_state(self, shape, cond_shape, dev, S, clip, item_streams):
         """The state of calc_bpd_loop: buffers, the walk's tables on the device, a private workspace and the captured graph, in
         `_loop_cache` under a key of its own -- ('bpd', ...): a string where a sampling key has the image shape, so the two cannot
-        collide; positions 2..6 are what `_loop_state` prunes by (device, T, arena, freq table, launch list)."""
-        un = self.denoise_fn
+        collide; positions 2..6 are `_cache_env`'s, as in a sampling key."""
         var_mode = 0 if self.learned_variance is not None else 1
         aug = self.cond_augment
-        key = ('bpd', tuple(shape), str(dev), self.num_timesteps, un.weights().data_ptr(), un.freq.data_ptr(), un.plan.generation,
+        key = ('bpd', tuple(shape), *self._cache_env(dev),
                None if cond_shape is None else tuple(cond_shape), int(S), bool(clip), var_mode, self.prediction, bool(item_streams),
                None if aug is None else (aug['sample_level'], aug['level_channel']))
-        st = self._loop_cache.get(key)
+        st = self._cached(key)
         if st is not None:
-            self._loop_cache[key] = self._loop_cache.pop(key)
             return st
         B, Cc = shape[0], shape[1]
         tabs = ancestral_tables(self._alphas_cumprod64, S, prediction=self.prediction)
@@ -1437,17 +1054,9 @@ class EngineDiffusion(nn.Module):
                   scratch=torch.empty(nb // 8, dtype=torch.float64, device=dev), scratch_bytes=nb,
                   hyb=f32(hybrid_step_scalars(tabs, np.arange(S))), ca=f32(tabs['level'][1:]), cb=f32(np.sqrt(1.0 - ab)),
                   level=f32(tabs['level']), tau=torch.tensor(tabs['tau'], dtype=torch.int32).to(dev),
-                  abar_last=float(ab[-1]), S=int(S), clip=bool(clip), var_mode=var_mode, replays=0)
-        # at most max_cached_loops states of this kind, and none built for another device / schedule, an arena that is gone or a launch
-        # list that no longer exists (`_loop_state`'s rule); the sampling states are not counted and not touched
-        arenas = {un.arena.data_ptr()} | ({un.ema_arena.data_ptr()} if un.ema_arena is not None else set())
-        live = set(un.plan._geometry_generation.values())
-        kept = [(k, v) for k, v in self._loop_cache.items() if k[0] != 'bpd']
-        mine = [(k, v) for k, v in self._loop_cache.items()
-                if k[0] == 'bpd' and k[2:4] == key[2:4] and k[4] in arenas and k[5] == key[5] and k[6] in live]
-        self._loop_cache = dict(kept + (mine[-(self.max_cached_loops - 1):] if self.max_cached_loops > 1 else []))
-        self._loop_cache[key] = st
-        return st
+                  abar_last=float(ab[-1]), S=int(S), clip=bool(clip), var_mode=var_mode, replays=0,
+                  dirty=('step',))             # (a step reads nothing else that it wrote: `_capture`)
+        return self._cached(key, st)
 
     def _bpd_step(self, st, draw_noise=True):
         """One iteration of calc_bpd_loop at j = the device counter: z, x_t = ca[j] x0 + cb[j] z, the forward at the step's level /
@@ -1464,30 +1073,6 @@ class EngineDiffusion(nn.Module):
         L.check(lib.sr3_vlb_terms_f32(L.ptr(st['x0']), L.ptr(st['xt']), L.ptr(st['out']), st['out'].shape[1], L.ptr(st['hyb']), st['S'],
                                       None, L.ptr(st['step']), st['var_mode'], 1 if st['clip'] else 0, B, Cc, H * W, L.ptr(st['vb']),
                                       L.ptr(st['mse']), L.ptr(st['scratch']), st['scratch_bytes'], self._stream(dev)))
-
-    def _bpd_capture(self, st):
-        """`_capture` for the evaluation step: one eager step on a side stream first, RNG and counter restored, then the capture."""
-        dev = st['x0'].device
-        rng = torch.cuda.get_rng_state(dev)
-        gens = st['gens'] or []
-        gstate = [g.get_state() for g in gens]
-        keep_step = st['step'].clone()
-        g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            self._bpd_step(st)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        st['step'].copy_(keep_step)
-        torch.cuda.set_rng_state(rng, dev)
-        for gen, gs in zip(gens, gstate):
-            gen.set_state(gs)
-        for gen in gens:
-            g.register_generator_state(gen)
-        with torch.cuda.graph(g):
-            self._bpd_step(st)
-        st['graph'] = g
 
     @torch.no_grad()
     def calc_bpd_loop(self, x_in, *, steps=None, clip_denoised=True, noise_seq=None, item_seeds=None):
@@ -1521,12 +1106,7 @@ class EngineDiffusion(nn.Module):
         if not 1 <= S <= self.num_timesteps:
             raise ValueError('calc_bpd_loop: steps must lie in [1, %d] (got %r)' % (self.num_timesteps, steps))
         B = shape[0]
-        if item_seeds is not None:
-            item_seeds = [int(v) for v in item_seeds]
-            if len(item_seeds) != B:
-                raise L.Sr3Error('calc_bpd_loop: %d item_seeds for a batch of %d' % (len(item_seeds), B))
-            if noise_seq is not None:
-                raise L.Sr3Error('calc_bpd_loop: item_seeds and noise_seq exclude each other')
+        item_seeds = self._item_seeds('calc_bpd_loop', item_seeds, noise_seq, B)
         self.denoise_fn.plan.set_geometry(shape[2], shape[3])
         cond_shape = None if cond is None else shape
         if cond is not None and aug is not None and aug['level_channel']:
@@ -1534,9 +1114,7 @@ class EngineDiffusion(nn.Module):
         st = self._bpd_state(shape, cond_shape, dev, S, clip_denoised, item_seeds is not None)
         self.denoise_fn.ensure_derived()
         lib, stream = L.load(), self._stream(dev)
-        if item_seeds is not None:
-            for g, v in zip(st['gens'], item_seeds):
-                g.manual_seed(v)
+        self._seed_items(st, item_seeds)
         st['x0'].copy_(x0)
         if cond is not None:
             st['cond'][:, :shape[1]].copy_(cond)
@@ -1547,18 +1125,7 @@ class EngineDiffusion(nn.Module):
         L.check(lib.sr3_prior_bpd_f32(L.ptr(st['x0']), B, x0[0].numel(), C.c_float(np.sqrt(ab)), C.c_float(1.0 - ab),
                                       C.c_float(np.log(1.0 - ab)), L.ptr(st['prior']), L.ptr(st['scratch']), st['scratch_bytes'], stream))
         st['step'].fill_(S - 1)
-        use_graph = self.use_graph and noise_seq is None
-        if use_graph and st['graph'] is None:
-            self._bpd_capture(st)
-        for j in reversed(range(S)):
-            if use_graph:
-                st['graph'].replay()
-                st['replays'] += 1
-            elif noise_seq is not None:
-                st['z'].copy_(noise_seq[j])
-                self._bpd_step(st, draw_noise=False)
-            else:
-                self._bpd_step(st)
+        self._run_steps(st, S, self._bpd_step, None if noise_seq is None else noise_seq.__getitem__)
         vb = st['vb'].t().contiguous()
         total = (vb.double().sum(1) + st['prior'].double()).float()
         return dict(vb=vb, x0_mse=st['mse'].t().contiguous(), prior_bpd=st['prior'].clone(), total_bpd=total)
@@ -1608,21 +1175,16 @@ class EngineDiffusion(nn.Module):
             self.flush_t_sampler()     # (a caller that never read the last step's terms: they enter the history before p is formed)
             ts_p = ts.probabilities()
         if self.variant == 'sr3':
-            if lv is not None and ts is not None:
-                # (set_t_sampler refused a plain SR3 model) one step per batch from p, where the reference's single randint stood
-                if gamma is not None:
-                    raise ValueError('p_losses under learned_variance draws gamma on the schedule\'s grid: inject t (1 .. T), not gamma')
-                tt = int(np.random.choice(self.num_timesteps, p=ts_p)) + 1 if t is None else int(t)
-                if not 1 <= tt <= self.num_timesteps:
-                    raise ValueError('p_losses: t must lie in [1, %d] (got %d)' % (self.num_timesteps, tt))
-                gamma = torch.FloatTensor(np.full(b, self.sqrt_alphas_cumprod_prev[tt]))
-                hyb_t = torch.full((b,), tt - 1, dtype=torch.long, device=dev)
-            elif lv is not None:
+            if lv is not None:
                 # q(x_{t-1} | x_t, x0) exists on the grid only: gamma is the level the sampler feeds at step t, not a uniform draw
-                # between two grid values -- the one change to the draws, under the key alone
+                # between two grid values -- the one change to the draws, under the key alone.  Under t_sampler (set_t_sampler refused a
+                # plain SR3 model) the one step per batch comes from p, where the reference's single randint stood
                 if gamma is not None:
                     raise ValueError('p_losses under learned_variance draws gamma on the schedule\'s grid: inject t (1 .. T), not gamma')
-                tt = np.random.randint(1, self.num_timesteps + 1) if t is None else int(t)
+                if t is not None:
+                    tt = int(t)
+                else:
+                    tt = np.random.randint(1, self.num_timesteps + 1) if ts is None else int(np.random.choice(self.num_timesteps, p=ts_p)) + 1
                 if not 1 <= tt <= self.num_timesteps:
                     raise ValueError('p_losses: t must lie in [1, %d] (got %d)' % (self.num_timesteps, tt))
                 gamma = torch.FloatTensor(np.full(b, self.sqrt_alphas_cumprod_prev[tt]))

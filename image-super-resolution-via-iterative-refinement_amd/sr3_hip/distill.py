@@ -26,7 +26,8 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .diffusion import EngineDiffusion, prediction_coefs, sampler_walk
+from .diffusion import EngineDiffusion
+from .schedules import prediction_coefs, sampler_walk
 
 
 def halve_walk(tau):

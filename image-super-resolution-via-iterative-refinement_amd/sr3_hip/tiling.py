@@ -3,6 +3,10 @@
 Pure Python / numpy, no device.  An image larger than the size the UNet was trained at is sampled as ONE chain whose eps comes from
 overlapping tiles of the training size (EngineDiffusion.p_sample_loop_tiled); this module decides the tiles and the blend weights,
 csrc/tiled.hip applies them.
+
+Tiling (engine extension, `"tiling": {"tile": 128 | [th, tw], "overlap": 32, "batch": 8}` next to "sampler", or `set_tiling`): an image larger
+than the tile is sampled as one chain whose eps comes from overlapping tiles of that size -- per step: sr3_tile_gather + UNet forward
+per chunk of tiles, then sr3_tiled_step (blend + p_sample update + counter decrement) on the whole image (`p_sample_loop_tiled`).
 """
 import numpy as np
 

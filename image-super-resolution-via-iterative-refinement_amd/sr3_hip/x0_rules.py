@@ -3,8 +3,22 @@
 A rule owns the whole tail of a reverse step (a HIP entry built on csrc/step_tail.h's frame): consistency (the block-mean projection,
 sr3_consistent_step), guidance (classifier-free guidance and the threshold on x0, sr3_guided_step), back-projection (iterative
 back-projection under Pillow's resize, sr3_backproject_step).  RULES is the ordered table EngineDiffusion loops over -- in
-set_new_noise_schedule, in its one compatibility check, in _loop_state, _one_step, _capture and _sample_loop.  The rules exclude one
-another and tiling (each owns the tail); a new rule on x0 is one entry here and one kernel.
+set_new_noise_schedule, in its one settings check (_check_settings, which calls check_rule below), in _loop_state (the key, the buffers,
+the step form), in _capture (warm_on_capture_stream) and in _sample_shape / _begin_chain (the targets).  The rules exclude one another
+and tiling (each owns the tail); a new rule on x0 is one entry here and one kernel.
+
+The config keys (engine extensions, next to "sampler" / "tiling" in the schedule dict, or the setters).  Per step: UNet forward with the
+output stored, then the rule's entry in place of the fused tail.
+  `"consistency": {"block": 8, "strength": 1.0}` / `set_consistency`: every step shifts each block x block block of x0 so that its mean is
+    the target's -- the block means of the conditioning image, or `consistency_target=` (the range / null-space projection for an
+    average pool; sr3_consistent_step).
+  `"guidance": {"scale": 1.5, "threshold": "dynamic", "percentile": 0.995}` / `set_guidance` (`"cond_drop": p` in model.diffusion, or
+    `set_cond_drop`, trains a model for it): classifier-free guidance -- two forwards per step, on the conditioning image and on a zero
+    one, combined as out_u + scale (out_c - out_u) before x0 is formed -- and what is done to x0 where it leaves [-1, 1]: the static
+    clamp, nothing, or dynamic thresholding (each image's x0 divided by its own percentile of |x0|; sr3_guided_step).
+  `"backprojection": {"scale": 8, "iterations": 2, "strength": 1.0, "resample": "bicubic"}` / `set_backprojection`: `iterations` rounds of
+    x0 <- x0 + strength * U(y - D(x0)), D / U = Pillow's antialiased resize down / up by `scale` (`resample_tables`), y = the LR image
+    (`backprojection_target=`) or the down-sampled conditioning image (sr3_backproject_step).  A contraction, not a projection.
 
 A Rule supplies: `name` (the config key, the attribute of EngineDiffusion, the state key and the _loop_state keyword), `noun` (in
 messages), `setter`, `entry`; `parse(spec)` -- the config key -> the setter's arguments; `validate(diff, *args)` -- the setter's body ->
