@@ -83,10 +83,11 @@ int sr3_conv_f32(const float* src0, int C0, const float* src1, int C1, int B, in
   c.res0 = res0; c.res1 = res1; c.RC0 = res0 ? RC0 : 0; c.RC1 = res1 ? RC1 : 0;
   c.out = out; c.ostat = out_stats;
   const TileCode t = tile_decode(tile_cfg);
-  c.wino_split = t.wino_split; c.wino_full = t.wino_full; c.igemm_split = t.igemm_split; tile_cfg = t.tile;
+  c.wino_split = t.wino_split; c.wino_full = t.wino_full; c.igemm_split = t.igemm_split; c.gemm_epi = t.gemm_epi; tile_cfg = t.tile;
   if (t.wpre) {
     // the weights pre-split into bf16 planes (what a plan does, in its derived buffer): derived here
-    if (tile_cfg == 22 && !gemm1x1_fits(c, 2)) { set_error("conv: the 1x1 GEMM kernel (tile 22) does not fit this problem"); return SR3_E_UNSUPPORTED; }
+    // (the rows fill the tile that runs: 32 or 64)
+    if (tile_cfg == 22 && !gemm1x1_fits(c, gemm1x1_rows(c) / 32)) { set_error("conv: the 1x1 GEMM kernel (tile 22) does not fit this problem"); return SR3_E_UNSUPPORTED; }
     float* q = nullptr;
     if (const int rc = derive_behind_slabs(c, tile_cfg, ksplit, DERIVE_IGEMM_WSPLIT, scratch, &scratch_bytes, st, &q)) return rc;
     c.w_split = q;
@@ -158,6 +159,14 @@ unsigned sr3_dropout_threshold(float drop_p, float* scale_out) {
   if (drop_p > 0.f && drop_p < 1.f) dropout_consts(drop_p, &t, &s);
   if (scale_out) *scale_out = s;
   return t;
+}
+int sr3_gemm_tile(int B, int Ho, int Wo, int Cin, int Cout, int ksize, int* rows, int* cols) {
+  if (ksize != 1 && ksize != 3) return 0;
+  const ConvParams c = ksize == 3 ? conv_shape(B, 2 * Ho, 2 * Wo, 0, 2, 3, Cin, 0, Cout) : conv_shape(B, Ho, Wo, 0, 1, 1, Cin, 0, Cout);
+  if (B <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || !gemm1x1_fits(c, gemm1x1_rows(c) / 32)) return 0;
+  if (rows) *rows = gemm1x1_rows(c);
+  if (cols) *cols = gemm1x1_cols(c);
+  return 1;
 }
 size_t sr3_conv_scratch_bytes(int B, int Ho, int Wo, int Cin, int Cout, int ksize, int tile_cfg, int ksplit) {
   const TileCode t = tile_decode(tile_cfg);

@@ -58,8 +58,14 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 // gradients towards 64 / 192 channels) -- the four waves sit 2 (M) x 2 (N): a wave owns ONE 32-column block and the MI m blocks of its half of
 // the rows; the workgroup stages MQ = MI * WM m blocks per k-step (the staging arithmetic per MFMA doubles: these layers are bound by their A
 // rows from HBM, not by the matrix pipe).
-template <int MI, bool ACT, bool S2 = false, int WM = 1>
+// EPI (plan option gemm_epi; tiles 27 / 28 / 29 at the ABI): the form of the epilogue, same bits under all three.
+//   0: every lane stores the 4-byte elements of its accumulator registers (64 dword stores per block row group: the form up to round 7);
+//   1: each wave transposes its 32 x 32 accumulator blocks through the (by then dead) staging LDS so that a lane owns FOUR consecutive
+//      output channels of one row -- bias, FiLM row, residual and the store are 16 bytes wide, one wave instruction covers 8 rows x 128 bytes;
+//   2: ... and those stores are written through L2 (store16 with sc1, sr3_common.h; the host clears it where store_wt_fits says no).
+template <int MI, bool ACT, bool S2 = false, int WM = 1, int EPI = 0>
 __global__ __launch_bounds__(256, 2) void k_gemm1x1_split(const ConvParams p) {
+  static_assert(EPI >= 0 && EPI <= 2, "epilogue form");
   static_assert(!(ACT && S2), "the stride-2 form has no GroupNorm affine");
   static_assert(WM == 1 || WM == 2, "waves along M");
   constexpr int NWN = 4 / WM;                   // waves side by side along N
@@ -309,6 +315,50 @@ __global__ __launch_bounds__(256, 2) void k_gemm1x1_split(const ConvParams p) {
   // ---- epilogue: D layout of the 32x32 MFMA: reg r of lane l -> row (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), col l & 31 ----------
   const bool direct = p.ksplit == 1;
   float* dst = direct ? p.out : p.partial + (size_t)blockIdx.y * M * p.Cout;
+  if constexpr (EPI != 0) {
+    // The wave's block goes through LDS as [32 rows][32 floats], no padding (4 KB per wave, 16 KB per workgroup: the host sizes the
+    // dynamic LDS for it).  Writes: register r of every lane is one ds_write_b32, the lanes of a half-wave fill one row contiguously --
+    // conflict-free.  Reads: lane l takes the 16 bytes at row 8 g + (l >> 3), floats 4 (l & 7): the four 16-lane groups of a
+    // ds_read_b128 each cover four rows x four 16-byte slots that fall on the 16 distinct slots of the 256-byte bank row -- conflict-free
+    // too (rows are 128 bytes: even and odd rows sit on opposite halves of the bank row, and a group takes the first half of one row
+    // and the second half of the other on either side).  A wave reads only what it wrote itself: LDS operations of one wave complete in order, so no barrier between
+    // the blocks -- the one below separates the K loop's last fragment reads from the first transpose write.
+    __syncthreads();
+    float* T = reinterpret_cast<float*>(smem) + wave * 1024;
+    float* Tw = T + (lane >> 5) * 128 + (lane & 31);
+    const float* Tr = T + (lane >> 3) * 32 + (lane & 7) * 4;
+    const int n4 = tile_n * (32 * NWN) + wn * 32 + (lane & 7) * 4;
+    const WtDst wd = wt_dst(dst, (size_t)M * p.Cout * sizeof(float), EPI == 2);      // the output, or this split's slab
+    f32x4 bn4 = {0.f, 0.f, 0.f, 0.f};
+    if (direct && p.bias) bn4 = *reinterpret_cast<const f32x4*>(p.bias + n4);
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      const int mblk = tile_m * BM + 32 * (wm * MI + i);       // wave-uniform; a 32-row block never straddles an image (HoWo % 32 == 0)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) Tw[((r & 3) + 8 * (r >> 2)) * 32] = acc[i][r];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      f32x4 fb = bn4;
+      if (direct && p.film) fb += *reinterpret_cast<const f32x4*>(p.film + (size_t)(mblk / HoWo) * p.film_stride + n4);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int m = mblk + 8 * g + (lane >> 3);
+        f32x4 v = *reinterpret_cast<const f32x4*>(Tr + g * 256);
+        if (direct) {
+          v += fb;
+          if (p.res0) {        // (RC0 % 4 == 0, host: a lane's four channels come from one source)
+            const float* rp = (n4 < p.RC0) ? p.res0 + (size_t)m * p.RC0 + n4 : p.res1 + (size_t)m * p.RC1 + (n4 - p.RC0);
+            v += *reinterpret_cast<const f32x4*>(rp);
+          }
+        }
+        store16(wd, (size_t)m * p.Cout + n4, v);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+    return;
+  }
   const int n = tile_n * (32 * NWN) + wn * 32 + (lane & 31);
   float bn = 0.f;
   if (direct && p.bias) bn = p.bias[n];
@@ -363,32 +413,57 @@ int gemm1x1_rows(const ConvParams& p) {
 }
 
 int gemm1x1_forward(const ConvParams& p, int mi, hipStream_t st) {
-  if (!gemm1x1_fits(p, mi) || !p.w_split) { set_error("conv: the 1x1 GEMM kernel (tile 22) does not fit this problem"); return SR3_E_UNSUPPORTED; }
+  // (the rows must fill the tile that RUNS -- 32 or 64: the planners ask gemm1x1_fits for 64, the per-op entry for the tile's own)
+  if (!gemm1x1_fits(p, gemm1x1_rows(p) / 32) || !p.w_split) { set_error("conv: the 1x1 GEMM kernel (tile 22) does not fit this problem"); return SR3_E_UNSUPPORTED; }
   if (p.act == 1 && !p.ss) { set_error("conv: act needs ss"); return SR3_E_BADARG; }
   const int M = p.B * p.Ho * p.Wo;
   const int rows = gemm1x1_rows(p), cols = gemm1x1_cols(p);
   mi = rows / 32;
   dim3 grid((M / rows) * (p.Cout / cols), p.ksplit);
-  const int smem = 2 * 2 * mi * 3 * 1024;
-  static std::atomic<uint64_t> done[9];
+  // the epilogue's form: ConvParams::gemm_epi names one (1 + form), 0 leaves it to the library's default
+  int form = p.gemm_epi ? p.gemm_epi - 1 : GEMM_EPI_DEFAULT;
+  if (form < 0 || form > 2) { set_error("conv: gemm_epi form %d: 0 (4-byte epilogue), 1 (16-byte) or 2 (16-byte, written through)", form); return SR3_E_BADARG; }
+  if (form) {
+    // 16-byte loads and stores: a lane's four channels come from one residual source, every row it touches is 16-byte aligned.  A form
+    // that was NAMED (tiles 28 / 29, plan option gemm_epi) refuses a problem that does not meet this; the library's default (tile 22
+    // outside a plan) runs it on the 4-byte epilogue, as it always did
+    const bool named = p.gemm_epi != 0;
+    const uintptr_t al = (uintptr_t)p.bias | (uintptr_t)p.film | (uintptr_t)p.res0 | (uintptr_t)p.res1 | (uintptr_t)(p.ksplit == 1 ? p.out : p.partial);
+    const bool rc_off = p.res0 && ((p.RC0 | p.RC1) & 3), film_off = p.film && (p.film_stride & 3), misaligned = (al & 15) != 0;
+    if (!named && (rc_off || film_off || misaligned)) form = 0;
+    else if (rc_off) { set_error("conv: the 16-byte epilogue of the GEMM kernel (gemm_epi %d) needs RC0 %% 4 == 0 (RC0 = %d)", form, p.RC0); return SR3_E_UNSUPPORTED; }
+    else if (film_off) { set_error("conv: the 16-byte epilogue of the GEMM kernel (gemm_epi %d) needs film_stride %% 4 == 0 (%d)", form, p.film_stride); return SR3_E_UNSUPPORTED; }
+    else if (misaligned) { set_error("misaligned pointer (GEMM epilogue, gemm_epi %d: bias, film, residual, out: 16 B)", form); return SR3_E_ALIGN; }
+    // (write-through stores are buffer stores with 32-bit offsets: sr3_common.h)
+    if (form == 2 && !store_wt_fits((size_t)p.ksplit * M * p.Cout * sizeof(float))) form = 1;
+  }
+  // the K loop's two stages; the 16-byte epilogue transposes through 4 KB per wave of the same block (the 32-row tile's 12 KB grow to 16)
+  const int stage_bytes = 2 * 2 * mi * 3 * 1024;
+  const int smem = form && stage_bytes < 4 * 4096 ? 4 * 4096 : stage_bytes;
+  static std::atomic<uint64_t> done[9][3];
   auto go = [&](auto kern, std::atomic<uint64_t>& d) -> int {
     if (int rc = ensure_max_lds(reinterpret_cast<const void*>(kern), smem, d)) return rc;
     hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, p);
     SR3_LAUNCH_CHECK("k_gemm1x1_split");
     return SR3_OK;
   };
+  // one instantiation per (tile, activation, stride-2) x epilogue form: both arms of an A/B live in one library
+#define SR3_G1_GO(IDX, ...)                                                      \
+  (form == 2 ? go(k_gemm1x1_split<__VA_ARGS__, 2>, done[IDX][2])                 \
+             : form == 1 ? go(k_gemm1x1_split<__VA_ARGS__, 1>, done[IDX][1]) : go(k_gemm1x1_split<__VA_ARGS__, 0>, done[IDX][0]))
   // (MI = 4, a 128-row tile with half the weight traffic per row, was built and dropped: at 256 registers it spills, and the weight
   // traffic is not what bounds this kernel -- profiles/r06_gemm1x1.txt)
   if (p.ksize == 3 && p.act) { set_error("conv: the stride-2 form of the GEMM kernel takes no activation"); return SR3_E_UNSUPPORTED; }
   if (cols == 64) {      // 64 x 64 tile, waves 2 x 2 (one m block per wave)
-    if (p.ksize == 3) return go(k_gemm1x1_split<1, false, true, 2>, done[6]);
-    return p.act ? go(k_gemm1x1_split<1, true, false, 2>, done[7]) : go(k_gemm1x1_split<1, false, false, 2>, done[8]);
+    if (p.ksize == 3) return SR3_G1_GO(6, 1, false, true, 2);
+    return p.act ? SR3_G1_GO(7, 1, true, false, 2) : SR3_G1_GO(8, 1, false, false, 2);
   }
   if (p.ksize == 3) {
-    return mi == 2 ? go(k_gemm1x1_split<2, false, true>, done[4]) : go(k_gemm1x1_split<1, false, true>, done[5]);
+    return mi == 2 ? SR3_G1_GO(4, 2, false, true, 1) : SR3_G1_GO(5, 1, false, true, 1);
   }
-  if (mi == 2) return p.act ? go(k_gemm1x1_split<2, true>, done[0]) : go(k_gemm1x1_split<2, false>, done[1]);
-  if (mi == 1) return p.act ? go(k_gemm1x1_split<1, true>, done[2]) : go(k_gemm1x1_split<1, false>, done[3]);
+  if (mi == 2) return p.act ? SR3_G1_GO(0, 2, true, false, 1) : SR3_G1_GO(1, 2, false, false, 1);
+  if (mi == 1) return p.act ? SR3_G1_GO(2, 1, true, false, 1) : SR3_G1_GO(3, 1, false, false, 1);
+#undef SR3_G1_GO
   set_error("conv: bad 1x1 GEMM tile");
   return SR3_E_BADARG;
 }

@@ -855,6 +855,7 @@ int run_forward(sr3_plan* P, bool train, const float* x, const float* cond, int 
         c.out = bind<float>(ws, v.out);
         c.ostat = bind<double>(stats, v.ostat);
         c.store_wt = P->store_wt;
+        c.gemm_epi = 1 + P->launch_gemm_epi();
         if (drop && v.has_drop && drop->thresh != 0) {
           c.drop_seed = drop_layer_seed(drop->seed, v.drop_key); c.drop_thresh = drop->thresh; c.drop_scale = drop->scale;
         }
@@ -1036,6 +1037,10 @@ int sr3_plan_set_option(sr3_plan* plan, const char* key, int value) {
   else if (!strcmp(key, "store_wt")) {   // no rebuild (read at launch)
     if (value < 0 || value > STORE_WT_ALL) { set_error("store_wt %d: a mask of bits 0-2 (0 .. %d)", value, (int)STORE_WT_ALL); return SR3_E_BADARG; }
     const int prev = plan->store_wt; plan->store_wt = value; return prev;
+  }
+  else if (!strcmp(key, "gemm_epi")) {   // no rebuild (read at launch)
+    if (value < 0 || value > 2) { set_error("gemm_epi %d: 0 (4-byte epilogue), 1 (16-byte stores) or 2 (16-byte stores written through L2)", value); return SR3_E_BADARG; }
+    const int prev = plan->gemm_epi; plan->gemm_epi = value; plan->gemm_epi_named = true; return prev;
   }
   else if (!strcmp(key, "attn_long")) slot = &plan->attn_long;
   else if (!strcmp(key, "gemm_split")) slot = &plan->gemm_split;

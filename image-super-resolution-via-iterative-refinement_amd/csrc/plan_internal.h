@@ -224,6 +224,13 @@ struct sr3_plan {
   int store_wt = 3;          // STORE_WT_* bits (sr3_common.h), one per kernel family: its 16-byte epilogue stores are written through L2 (sc1), so the
                              // kernel boundary behind it has no dirty lines to write back.  Same bits under every value; read at launch, no rebuild;
                              // 0 = plain stores everywhere.  Default: the families that measured faster (profiles/store_wt_ab.txt)
+  int gemm_epi = GEMM_EPI_DEFAULT;   // the epilogue of the GEMM kernel (tile 22; gemm1x1.hip): 0 = 4-byte stores, one per accumulator register; 1 = the
+                             // accumulator blocks transposed through LDS, 16-byte loads and stores; 2 = ... written through L2 as store_wt's families
+                             // are.  Same bits under every value; read at launch, no rebuild; the training forward and the data gradients on that
+                             // kernel follow it.  Default: the fastest form that cleared the bar (profiles/gemm_epi_ab.txt)
+  bool gemm_epi_named = false;       // sr3_plan_set_option set it: a named form refuses a problem its 16-byte accesses cannot take, the untouched default
+                             // runs such a problem on form 0 (gemm1x1_forward); launch_gemm_epi() is what a launch passes on
+  int launch_gemm_epi() const { return gemm_epi_named ? gemm_epi : -1; }      // (ConvParams::gemm_epi = 1 + this: 0 = the library's default)
   int train_geom = 0;        // training follows the plan's geometry (sr3_plan_set_geometry) too: sr3_train_workspace_bytes / sr3_train_step build the
                              // training plan at plan_height x plan_width.  0: training is refused at any geometry but image_size x image_size.
                              // Off by default ONLY because tests pin that refusal text; at the native geometry both values build the same plan

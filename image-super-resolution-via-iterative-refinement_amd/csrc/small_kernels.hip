@@ -591,9 +591,22 @@ int conv_in_nchw(const float* a, int Ca, const float* b, int Cb, int B, int H, i
 // channel chunk it stages the (10x34) halo tile *after* GN+SiLU in LDS (each element transformed
 // once, zero padding applied after the activation as the reference does), then every thread
 // accumulates its pixel's Cout outputs from LDS.  Writes NCHW (the public layout of eps).
+// A chunk is 16 channels, half a 128-byte line of a pixel's row; with every resident tile's working set far above an XCD's 4 MB of
+// L2 the second half of a line has been evicted by the time its chunk comes round, and every line comes from memory twice
+// (FETCH_SIZE 87 MB raw per launch at the flagship, 2x the input).  -DSR3_CONV_OUT_LINES (A/B builds only) stages 32 channels = whole
+// lines: same bits (the accumulation order stays 16-channel sub-chunks in ascending order, then (tap, quad, element)), LDS stride 36
+// floats (the 16 lanes of a ds_read_b128 group, consecutive pixels, on 16 distinct 16-byte slots, as stride 20), 48 KB and 129
+// registers, three workgroups per CU.  Measured: FETCH_SIZE 87.1 -> 45.6 MB as predicted, but the kernel 50.9 -> 76.9 us and the step
+// +0.026 ms -- the kernel is not bound by its HBM reads but by the staging round (SiLU + LDS write of 2720 quads between two
+// barriers, with half the workgroups per CU to overlap it); profiles/gemm_epi_ab.txt blocks 2-4.  So the 16-channel chunk stays.
 // ---------------------------------------------------------------------------------------------
+#ifdef SR3_CONV_OUT_LINES
+constexpr int OT_H = 8, OT_W = 32, OT_CK = 32, OT_LD = 36;
+#else
 constexpr int OT_H = 8, OT_W = 32, OT_CK = 16, OT_LD = 20;
-// COUT: output channels (1..4; 6 and 8, the learned-variance heads 2C of C = 3 / 4, without FUSE: no tail is fused onto them); FULL: C is a multiple of the 16-channel chunk (no per-quad bound checks)
+#endif
+constexpr int OT_Q = OT_CK / 4, OT_SUB = OT_CK / 16;      // quads per staged pixel; 16-channel sub-chunks per chunk
+// COUT: output channels (1..4; 6 and 8, the learned-variance heads 2C of C = 3 / 4, without FUSE: no tail is fused onto them); FULL: C is a multiple of the staged chunk (no per-quad bound checks)
 // FUSE (sr3_reverse_step): the reverse-step update of the image this eps belongs to in the epilogue -- the element a thread produces IS the
 // element of eps the elementwise update needs, in the same NCHW position -- step_tail (sr3_common.h), as k_p_sample_update runs it
 // (bit-identical to the two-kernel form), and the loop counter's decrement by one thread
@@ -618,8 +631,8 @@ __global__ __launch_bounds__(256) void k_conv_out_nchw(const float* __restrict__
   constexpr int NPIX = (OT_H + 2) * (OT_W + 2);
   for (int c0 = 0; c0 < C; c0 += OT_CK) {
     __syncthreads();
-    for (int i = tid; i < NPIX * 4; i += 256) {
-      const int pix = i >> 2, q = i & 3;
+    for (int i = tid; i < NPIX * OT_Q; i += 256) {
+      const int pix = i / OT_Q, q = i % OT_Q;
       const int py = pix / (OT_W + 2), px = pix - py * (OT_W + 2);
       const int ih = h0 + py - 1, iw = w0 + px - 1;
       const int c = c0 + q * 4;
@@ -635,21 +648,25 @@ __global__ __launch_bounds__(256) void k_conv_out_nchw(const float* __restrict__
     __syncthreads();
     // The filter taps are the same for every lane: they are read through workgroup-uniform addresses, i.e. scalar loads into
     // SGPRs that feed the FMAs directly (round 3; the LDS copy of the weights cost 4 broadcast ds_read_b128 per tile read and
-    // made the kernel LDS-instruction bound: 62 -> measured in profiles/archive/r03*).  Same FMA order as before: (tap, quad, element).
+    // made the kernel LDS-instruction bound: 62 -> measured in profiles/archive/r03*).  Same FMA order as before: per 16-channel
+    // sub-chunk (tap, quad, element).
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const float* tp = tile + ((ty + tap / 3) * (OT_W + 2) + tx + tap % 3) * OT_LD;
+    for (int sub = 0; sub < OT_SUB; ++sub) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (FULL || c0 + q * 4 < C) {                             // uniform
-          const f32x4 v = *reinterpret_cast<const f32x4*>(tp + q * 4);
+      for (int tap = 0; tap < 9; ++tap) {
+        const float* tp = tile + ((ty + tap / 3) * (OT_W + 2) + tx + tap % 3) * OT_LD + sub * 16;
 #pragma unroll
-          for (int co = 0; co < COUT; ++co) {
-            const float* wr = w + ((size_t)co * 9 + tap) * C + c0 + q * 4;
-            acc[co] = fmaf(v[0], wr[0], acc[co]);
-            acc[co] = fmaf(v[1], wr[1], acc[co]);
-            acc[co] = fmaf(v[2], wr[2], acc[co]);
-            acc[co] = fmaf(v[3], wr[3], acc[co]);
+        for (int q = 0; q < 4; ++q) {
+          if (FULL || c0 + sub * 16 + q * 4 < C) {                  // uniform
+            const f32x4 v = *reinterpret_cast<const f32x4*>(tp + q * 4);
+#pragma unroll
+            for (int co = 0; co < COUT; ++co) {
+              const float* wr = w + ((size_t)co * 9 + tap) * C + c0 + sub * 16 + q * 4;
+              acc[co] = fmaf(v[0], wr[0], acc[co]);
+              acc[co] = fmaf(v[1], wr[1], acc[co]);
+              acc[co] = fmaf(v[2], wr[2], acc[co]);
+              acc[co] = fmaf(v[3], wr[3], acc[co]);
+            }
           }
         }
       }

@@ -230,7 +230,12 @@ struct ConvParams {
                        // 0: the UP instantiation of conv3x3_wino2.hip, which skips the seven positions whose operand is exactly zero
   int store_wt;        // STORE_WT_* bits (above): which kernels of this conv write their 16-byte stores through L2; 0: plain stores everywhere.
                        // Set per launch from the plan option; conv_forward clears the write-through bits where store_wt_fits says no
+  int gemm_epi;        // the GEMM kernel's epilogue (gemm1x1.hip, template parameter EPI): 0 = the library's default form (GEMM_EPI_DEFAULT: tile_cfg
+                       // 22 at the ABI), 1 + form names one: 1 = the 4-byte epilogue, 2 = 16-byte stores, 3 = 16-byte stores written through L2
+                       // (tile_cfg 27 / 28 / 29; plan option gemm_epi = form).  gemm1x1_forward drops form 2 to 1 where store_wt_fits says no
 };
+// the form ConvParams::gemm_epi == 0 and a fresh plan run: what measured fastest (profiles/gemm_epi_ab.txt)
+constexpr int GEMM_EPI_DEFAULT = 2;
 
 __device__ __forceinline__ unsigned hash32(unsigned x) {
   x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;

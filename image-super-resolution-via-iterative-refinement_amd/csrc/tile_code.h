@@ -11,8 +11,9 @@ namespace sr3 {
 //   14-17: im2col tiles 1-4 with ConvParams::igemm_split (3 x bf16 split); 18-21: ... with pre-split weights (ConvParams::w_split)
 //   25, 26: 13 / 23 with ConvParams::wino_full (the sixteen-position loop even where ups = 1 would select the nine-position one; same bits)
 //   22: the plain GEMM kernel of gemm1x1.hip (always split, always pre-split weights); 24: attention ops only (attention_long.hip), passes through
+//   27, 28, 29: 22 with ConvParams::gemm_epi 1, 2, 3 (the epilogue of plan option gemm_epi = 0 / 1 / 2 named; 22 itself leaves it to the default)
 // The only place in the library that knows the numbers; the one other copy is the TILE name table of tools/dump_plan.py.
-struct TileCode { int tile; int wino_split; int igemm_split; bool wpre; int wino_full = 0; };
+struct TileCode { int tile; int wino_split; int igemm_split; bool wpre; int wino_full = 0; int gemm_epi = 0; };
 inline TileCode tile_decode(int abi_tile) {
   if (abi_tile == 12 || abi_tile == 13) return {11, abi_tile - 11, 0, false};
   if (abi_tile == 23) return {11, 3, 0, false};
@@ -20,6 +21,7 @@ inline TileCode tile_decode(int abi_tile) {
   if (abi_tile >= 14 && abi_tile <= 17) return {abi_tile - 13, 0, 1, false};
   if (abi_tile >= 18 && abi_tile <= 21) return {abi_tile - 17, 0, 1, true};
   if (abi_tile == 22) return {22, 0, 1, true};
+  if (abi_tile >= 27 && abi_tile <= 29) return {22, 0, 1, true, 0, abi_tile - 26};
   return {abi_tile, 0, 0, false};
 }
 inline int tile_encode(int tile, int wino_split, int igemm_split, bool has_wsplit, int wino_full = 0) {

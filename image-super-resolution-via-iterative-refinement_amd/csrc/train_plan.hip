@@ -292,7 +292,7 @@ struct TrainCtx {
 
 // dOut [B,H,W,Cg] --(conv with flipped-transposed weights)--> dA [B,H,W,Cin], on the kernel choose_dgrad chose; the arena holds
 // `Cout_w` <= Cg of the Cg filters (the output conv's padding).  stride 2: dOut is [B,Ho,Wo,Cg] and is zero-inserted first
-int dgrad_conv(const Dgrad& d, int stride, int Ho, int Wo, const float* g, const float* w, int Cout_w, float* dA, const DgradBufs& b,
+int dgrad_conv(const Dgrad& d, int stride, int Ho, int Wo, const float* g, const float* w, int Cout_w, float* dA, const DgradBufs& b, int gemm_epi,
                hipStream_t st) {
   ConvParams c = d.c;
   int rc;
@@ -304,6 +304,7 @@ int dgrad_conv(const Dgrad& d, int stride, int Ho, int Wo, const float* g, const
   rc = w_flip_transpose(w, Cout_w, c.ksize * c.ksize, c.Cout, c.C0, b.wt, st);
   if (rc) return rc;
   c.src0 = g; c.w = b.wt; c.out = dA;
+  c.gemm_epi = 1 + gemm_epi;      // (plan option gemm_epi, read at launch: the data gradients on the GEMM kernel follow it; -1: not set)
   if (d.wu == WU_GEMM) { rc = igemm_split_weights(b.wt, c.Cout, 1, c.C0, b.wu, st); c.w_split = b.wu; }
   else if (d.wu != WU_NONE) { rc = wino_transform_weights(b.wt, c.Cout, c.C0, b.wu, st, d.wu == WU_WINO_SPLIT); c.wino_u = b.wu; }
   if (rc) return rc;
@@ -389,7 +390,7 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
       // bias (3 of the 4 padded columns are real -- 6 of 8 with a variance head; arena slots are 4-float aligned)
       rc = colsums(geps, B, S2, OUT_PAD, part, grads + s.bias, nullptr, 0, st);
       if (rc) return rc;
-      rc = dgrad_conv(r.dx, 1, r.dw.Ho, r.dw.Wo, geps, params + s.w, P->out_ch, dA, X.dgrad_bufs(), st);
+      rc = dgrad_conv(r.dx, 1, r.dw.Ho, r.dw.Wo, geps, params + s.w, P->out_ch, dA, X.dgrad_bufs(), P->launch_gemm_epi(), st);
       if (rc) return rc;
       rc = act_bwd(dA, X.act(s.x0), nullptr, C, 0, B, S2, X.at<float>(P->t_regions.ss_off + r.ss_off),
                    X.at<float>(P->t_regions.mr_off + r.mr_off), G, s.act, params + r.gamma, part, gs, grads + r.gamma,
@@ -446,7 +447,7 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
       // 3. fused res_conv segment
       if (has_q) {
         float* dq = X.at<float>(P->t_dq_off);
-        rc = dgrad_conv(r.dq, 1, Ho, Wo, g, params + s.qw, Cout, dq, X.dgrad_bufs(), st);
+        rc = dgrad_conv(r.dq, 1, Ho, Wo, g, params + s.qw, Cout, dq, X.dgrad_bufs(), P->launch_gemm_epi(), st);
         if (rc) return rc;
         rc = grad_route(dq, r.dqw.C0, r.dqw.C1, B, Ho, Wo, 0, X.grad(s.q0), X.grad(s.q1), st, r.acc_q0, r.acc_q1);
         if (rc) return rc;
@@ -454,7 +455,7 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
         if (rc) return rc;
       }
       // 4. main segment: data gradient
-      rc = dgrad_conv(r.dx, s.stride, Ho, Wo, g, params + s.w, Cout, dA, X.dgrad_bufs(), st);
+      rc = dgrad_conv(r.dx, s.stride, Ho, Wo, g, params + s.w, Cout, dA, X.dgrad_bufs(), P->launch_gemm_epi(), st);
       if (rc) return rc;
       if (s.act) {
         const bool dropped = s.drop_key >= 0 && dc.thresh != 0;
@@ -577,7 +578,7 @@ int sr3_conv_dgrad_f32(sr3_plan* plan, const float* dy, const float* w_ohwi, int
   if (tile_out) *tile_out = tile_encode(tile, d.c.wino_split, d.c.igemm_split, false);
   if (ksplit_out) *ksplit_out = ks;
   if (derived_kind_out) *derived_kind_out = d.wu;
-  return dgrad_conv(d, stride, f.Ho, f.Wo, dy, w_ohwi, Cout_w, dA, bufs, static_cast<hipStream_t>(stream));
+  return dgrad_conv(d, stride, f.Ho, f.Wo, dy, w_ohwi, Cout_w, dA, bufs, plan->launch_gemm_epi(), static_cast<hipStream_t>(stream));
 }
 
 size_t sr3_train_workspace_bytes(sr3_plan* plan, int batch, int cond_channels) {

@@ -74,6 +74,7 @@ SIGNATURES = {
     'sr3_plan_forward_flops': (C.c_double, [_P, _I]),
     'sr3_plan_set_option': (_I, [_P, C.c_char_p, _I]),
     'sr3_store_wt_fits': (_I, [_Z]),
+    'sr3_gemm_tile': (_I, [_I, _I, _I, _I, _I, _I, _PI, _PI]),
     'sr3_plan_num_taps': (_I, [_P]),
     'sr3_plan_tap_info': (_I, [_P, _I, C.c_char_p, _I, C.POINTER(_Z), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     'sr3_workspace_bytes': (_Z, [_P, _I]),

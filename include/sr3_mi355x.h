@@ -101,9 +101,13 @@ double sr3_plan_forward_flops(sr3_plan* plan, int batch);
 /* host predicate of plan option store_wt: may a tensor (or a set of split-K slabs) of `bytes` bytes be written with write-through buffer
  * stores (32-bit offsets: bytes < 4 GiB)?  1 yes, 0: plain stores. */
 int sr3_store_wt_fits(size_t bytes);
+/* host query: the workgroup tile the plain GEMM kernel (tile 22 / 27-29) runs this problem on -- *rows 32 or 64, *cols 64 (four waves
+ * 2 x 2) or 128 (four waves side by side) -- for a 1x1 stride-1 (ksize 1) or 3x3 stride-2 (ksize 3) conv with B x Ho x Wo output
+ * pixels.  Returns 1, or 0 when the kernel does not take the problem (then *rows and *cols are left alone).  Either pointer may be NULL. */
+int sr3_gemm_tile(int B, int Ho, int Wo, int Cin, int Cout, int ksize, int* rows, int* cols);
 /* tuning knobs: key in {"fuse_stats", "fuse_res", "tile_cfg", "ksplit", "keep_all", "split_bf16", "winograd",
  * "wino_split", "wino_split8", "wino2", "wino_ragged", "wino_up", "gemm_split", "gemm2", "gemm_s2", "gemm_n64", "fork_side", "gemm_wpre", "gemm_tile", "fold_fuse", "wgrad_split", "attn_split",
- * "attn_long", "store_wt", "train_geom", "loss_l2", "var_channels", "attn_heads", "attn_head_dim"};
+ * "attn_long", "store_wt", "gemm_epi", "train_geom", "loss_l2", "var_channels", "attn_heads", "attn_head_dim"};
  * returns previous value.
  * wino_split (default 1): the Winograd convolutions that run on the kernel's one-image tile (maps >= 16x16) use its 3 x bf16
  *   split instantiation: every fp32 operand as x = h + m + l (three bf16 terms, each residual exact in fp32), every product as
@@ -173,10 +177,20 @@ int sr3_store_wt_fits(size_t bytes);
  *   With both at their defaults every launch and bit is the single-head one.  Rebuilds the launch list.
  * store_wt (default 3; a mask, 0 .. 7): which kernels write their 16-byte epilogue stores THROUGH L2 (buffer stores with sc1) instead of
  *   leaving the lines dirty for the kernel boundary to write back: 1 the two-workgroup Winograd kernel (outputs and split-K slabs),
- *   2 the 8-wave Winograd kernel, 4 the split-K reduce kernels (k_rows_fold, k_splitk_reduce).  The other 16-byte epilogues of the
- *   flagship plan do not exist: the plain GEMM and the input conv store 4 bytes per lane, attention 8 at its batch-16 shape.
+ *   2 the 8-wave Winograd kernel, 4 the split-K reduce kernels (k_rows_fold, k_splitk_reduce).  The plain GEMM has an option of its
+ *   own (gemm_epi, below); the input conv stores 4 bytes per lane, attention 8 at its batch-16 shape.
  *   Every value gives the same bits; read at launch, no rebuild of the plan.  A
  *   tensor or slab set of 4 GiB or more keeps plain stores (sr3_store_wt_fits).  What was measured: DESIGN.md section 3.2c.
+ * gemm_epi (default 2; 0, 1 or 2, SR3_E_BADARG otherwise): the epilogue of the plain GEMM kernel (tile 22: gemm2, gemm_s2, gemm_n64; the training
+ *   forward and the 1x1 / stride-2 data gradients on that kernel too).  0: every lane stores its accumulator registers as 4-byte
+ *   elements.  1: each wave transposes its 32 x 32 accumulator blocks through LDS, so that a lane owns four consecutive output
+ *   channels of a row: bias, FiLM row, residual and the store are 16 bytes wide (needs RC0 % 4 == 0, film_stride % 4 == 0 and 16-byte
+ *   aligned bias / film / residual / out: once the option has been SET, or under tiles 28 / 29, a launch that does not meet them is
+ *   SR3_E_UNSUPPORTED / SR3_E_ALIGN; a plan whose option was never set, and tile 22, run such a launch on form 0 instead).  2: ... and those stores are written through L2
+ *   as store_wt's families are (outputs and split-K slabs; 4 GiB or more keep plain stores).  Every value gives the same bits (the
+ *   additions per element keep their order); read at launch, no rebuild: launch list, workspace and derived buffer do not depend on
+ *   it, and the ops still report tile 22.  The per-op entries name the forms as tiles 27 / 28 / 29 (= gemm_epi 0 / 1 / 2); tile 22
+ *   there is the form a fresh plan runs.  The default and what was measured: DESIGN.md section 3.2c, profiles/gemm_epi_ab.txt.
  * train_geom (default 0; training): sr3_train_workspace_bytes and sr3_train_step follow sr3_plan_set_geometry like the forward does: the
  *   training plan is built for the plan's height x width (hr / cond / z are [B, C, height, width]) and cached by (batch, cond_channels,
  *   height, width).  Its forward picks every conv through the inference planner's rule (the ragged Winograd tile 23 included, for the convs
@@ -884,9 +898,11 @@ int sr3_adam_ema_step_scaled(float* params, const float* grads, float* exp_avg, 
  * gemm_wpre, default off: a plan keeps the planes in its derived buffer; this entry point derives them into `scratch`; results
  * are bit-identical to 14-17); 22 = the plain GEMM kernel of gemm1x1.hip (what plan options gemm2 / gemm_s2 -- default on -- select: 1x1
  * stride 1, or 3x3 stride 2 with one source, act 0 and an even map; no upsampling, Cout % 64 == 0, C0 and C1 % 32 == 0,
- * B * Ho * Wo % 64 == 0, Ho * Wo % 32 == 0, act 0 | 1; anything else is refused with "does not fit"; same pre-split weights as
- * 18-21, derived into `scratch`).
- * scratch: split-K slabs (+ the Winograd filters for tile_cfg 11-13 and 23, the pre-split weights for 18-22), sized by
+ * Ho * Wo % 32 == 0, B * Ho * Wo a multiple of the tile's rows (sr3_gemm_tile: 64, or 32 where the 32-row tile runs), act 0 | 1; anything else is refused with "does not fit"; same pre-split weights as
+ * 18-21, derived into `scratch`), with the epilogue a fresh plan runs; 27 / 28 / 29 = 22 with the epilogue of plan option
+ * gemm_epi = 0 / 1 / 2 named explicitly (4-byte stores / 16-byte loads and stores behind a transpose through LDS / those stores
+ * written through L2; same bits; 28 and 29 need RC0 % 4 == 0, film_stride % 4 == 0 and 16-byte aligned bias, film, res0, res1, out).
+ * scratch: split-K slabs (+ the Winograd filters for tile_cfg 11-13 and 23, the pre-split weights for 18-22 and 27-29), sized by
  * sr3_conv_scratch_bytes, 256-byte aligned (SR3_E_ALIGN otherwise, for the three conv entries).  For this and every per-op scratch
  * below the buffer contract at sr3_workspace_bytes holds: exactly the queried bytes, nothing outside them written, prior contents
  * irrelevant (split-K slabs, statistics slices and padded lanes are written before they are read). */

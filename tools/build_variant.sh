@@ -2,6 +2,10 @@
 # A/B builds of ONE csrc source: tools/build_variant.sh <name> <source without .hip> [extra hipcc flags]
 #   -> tools/bin/libsr3_<name>.so = the default library's objects (csrc/build/) with that one source recompiled with the flags;
 #      run with SR3_LIBRARY=$PWD/tools/bin/libsr3_<name>.so.  Also prints the static loop statistics of kernel $SR3_VARIANT_KERNEL.
+# The whole-line staging of the output conv (k_conv_out_nchw with a 32-channel chunk; measured slower) exists only as such a
+# variant, so the suite's default build does not reach it.  Build and check it with the tests of that kernel:
+#   tools/build_variant.sh lines small_kernels -DSR3_CONV_OUT_LINES
+#   SR3_LIBRARY=$PWD/tools/bin/libsr3_lines.so python -m pytest -m gpu tests/test_gpu_conv_out_lines.py tests/test_gpu_step_tail.py
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 CS=$ROOT/image-super-resolution-via-iterative-refinement_amd/csrc

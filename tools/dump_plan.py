@@ -24,7 +24,9 @@ TILE = {1: 'im2col 128x128', 2: 'im2col 128x64', 3: 'im2col 64x64', 4: 'im2col 6
         21: 'im2col 64x128 3 x bf16 split, pre-split weights', 22: 'GEMM 64x128 / 64x64 3 x bf16 split (gemm1x1.hip)',
         23: 'Winograd F(2x2,3x3) 3 x bf16 split (4 waves, ragged)', 24: 'attention, key-blocked (attention_long.hip)',
         25: 'Winograd F(2x2,3x3) 3 x bf16 split (4 waves), all 16 positions on an upsampled map',
-        26: 'Winograd F(2x2,3x3) 3 x bf16 split (4 waves, ragged), all 16 positions on an upsampled map'}
+        26: 'Winograd F(2x2,3x3) 3 x bf16 split (4 waves, ragged), all 16 positions on an upsampled map',
+        27: 'GEMM (gemm1x1.hip), 4-byte epilogue (gemm_epi 0)', 28: 'GEMM (gemm1x1.hip), 16-byte epilogue (gemm_epi 1)',
+        29: 'GEMM (gemm1x1.hip), 16-byte epilogue written through L2 (gemm_epi 2)'}
 # (names of the public tile_cfg numbers: the one copy outside the codec of csrc/tile_code.h)
 
 
