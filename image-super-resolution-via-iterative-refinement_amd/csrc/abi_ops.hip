@@ -198,8 +198,9 @@ int sr3_conv_stats_slices(int B, int Hs, int Ws, int ups, int Cin, int Cout, int
   const TileCode t = tile_decode(tile_cfg);
   c.wino_split = t.wino_split; c.igemm_split = t.igemm_split; tile_cfg = t.tile;
   if (tile_cfg == 22) c.igemm_split = 0;      // THIS ENTRY: the GEMM kernel's number leaves igemm_split clear
-  conv_pick(c, tile_cfg, ksplit);
-  if (ksplit > 1) {
+  const ConvPick pk = conv_pick(c, tile_cfg, ksplit);
+  tile_cfg = pk.tile;
+  if (pk.ksplit > 1) {
     const int rpb = splitk_rows_per_block(c, true);
     return rpb > 0 ? (c.Ho * c.Wo) / rpb : 0;
   }

@@ -1081,7 +1081,7 @@ int conv3x3_wino_forward(const ConvParams& p, const float* ufrag, hipStream_t st
   const int nch = wino_chunks(p);
   if ((nch + p.ksplit - 1) / p.ksplit > wino_max_chunks_per_split(g)) { set_error("conv: the Winograd kernel takes at most %d input channels per K split here (%d chunks over %d splits)", wino_max_chunks_per_split(g) * WCK, nch, p.ksplit); return SR3_E_UNSUPPORTED; }
   if (g.NB != 1 && p.ksplit < 2) { set_error("conv: the four-image Winograd tile (8 x 8 maps) is split-K only"); return SR3_E_UNSUPPORTED; }
-  if (p.ksplit > 1 && (long)(p.ksplit - 1) * ((nch + p.ksplit - 1) / p.ksplit) >= nch) { set_error("conv: ksplit %d leaves an empty split over %d chunks", p.ksplit, nch); return SR3_E_BADARG; }
+  if (split_leaves_empty(nch, p.ksplit)) { set_error("conv: ksplit %d leaves an empty split over %d chunks", p.ksplit, nch); return SR3_E_BADARG; }
   // persistent workgroups: one per CU (8 waves, 157 KB of LDS), each walking its share of the tile list
   static const int n_cu = [] {
     int dev = 0, n = 0;

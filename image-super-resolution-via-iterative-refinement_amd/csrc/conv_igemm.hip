@@ -26,8 +26,6 @@
 // (64 bytes, no padding), their four 16-byte segments XOR-swizzled with (row >> 2) & 3 (conv3x3_halo.hip's MODE 1 layout:
 // 8-byte staging writes and 16-byte fragment reads both conflict-free).  The 128 x 128 tile single-buffers its 48 KB stage
 // (two workgroups per CU; the second barrier of a k-step is covered by the other workgroup), the smaller tiles double-buffer.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "sr3_common.h"
@@ -361,72 +359,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm(const ConvParams p) {
   }
 }
 
-// ---- split-K reduction + epilogue (+ optional partial GroupNorm statistics of the output) -------
-// A block owns `rpb` consecutive output rows (pixels) -- inside one image when statistics are
-// requested -- lanes run along channel quads (coalesced 16-byte accesses), the 4 waves along rows.
-__global__ __launch_bounds__(256) void k_splitk_reduce(const ConvParams p, int rpb) {
-  __shared__ double red[4 * 64 * 8];
-  const int HoWo = p.Ho * p.Wo;
-  const size_t M = (size_t)p.B * HoWo;
-  const int nq = p.Cout >> 2;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const size_t row0 = (size_t)blockIdx.x * rpb;
-  const WtDst wdst = wt_dst(p.out, M * p.Cout * sizeof(float), (p.store_wt & STORE_WT_REDUCE) != 0);    // plan option store_wt (sr3_common.h)
-  for (int q0 = 0; q0 < nq; q0 += 64) {
-    const int q = q0 + lane;
-    const int n = q * 4;
-    double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-    if (q < nq) {
-      f32x4 cb = {0.f, 0.f, 0.f, 0.f};
-      if (p.bias) cb += *reinterpret_cast<const f32x4*>(p.bias + n);
-      if (p.x2_w && p.x2_bias) cb += *reinterpret_cast<const f32x4*>(p.x2_bias + n);
-      for (int r = wave; r < rpb; r += 4) {
-        const size_t m = row0 + r;
-        if (m >= M) break;
-        f32x4 v = cb;
-        // four slabs in flight (round 6; one load per iteration made the wave wait for each slab in turn); same order of additions
-        auto slab = [&](int s) { return *reinterpret_cast<const f32x4*>(p.partial + ((size_t)s * M + m) * p.Cout + n); };
-        int s = 0;
-        for (; s + 4 <= p.ksplit; s += 4) {
-          const f32x4 a0 = slab(s), a1 = slab(s + 1), a2 = slab(s + 2), a3 = slab(s + 3);
-          v += a0; v += a1; v += a2; v += a3;
-        }
-        for (; s < p.ksplit; ++s) v += slab(s);
-        const int b = (int)(m / HoWo);
-        if (p.film) v += *reinterpret_cast<const f32x4*>(p.film + (size_t)b * p.film_stride + n);
-        if (p.res0) {
-          if (n < p.RC0) v += *reinterpret_cast<const f32x4*>(p.res0 + m * p.RC0 + n);
-          else v += *reinterpret_cast<const f32x4*>(p.res1 + m * p.RC1 + (n - p.RC0));
-        }
-        store16(wdst, m * p.Cout + n, v);
-        if (p.ostat) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { const double dv = (double)v[e]; s1[e] += dv; s2[e] += dv * dv; }
-        }
-      }
-    }
-    if (p.ostat) {      // uniform branch: fixed-order reduction over the 4 row lanes, one plain store
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { red[(wave * 64 + lane) * 8 + e] = s1[e]; red[(wave * 64 + lane) * 8 + 4 + e] = s2[e]; }
-      __syncthreads();
-      if (wave == 0 && q < nq && row0 < M) {
-        const int b = (int)(row0 / HoWo);
-        const int T = HoWo / rpb;
-        const int slice = (int)(row0 - (size_t)b * HoWo) / rpb;
-        double* o = p.ostat + (((size_t)b * T + slice) * p.Cout + n) * 2;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          double a1 = 0.0, a2 = 0.0;
-#pragma unroll
-          for (int w = 0; w < 4; ++w) { a1 += red[(w * 64 + lane) * 8 + e]; a2 += red[(w * 64 + lane) * 8 + 4 + e]; }
-          o[2 * e] = a1; o[2 * e + 1] = a2;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
 // ---- pre-split weights of the SPLIT instantiations (ConvParams::w_split) --------------------------------------------------------
 // out[n block][it = chunk * taps + tap][K = 16 step 2][plane 3][lane 64][8 bf16]: lane l of a fragment holds W[n = 32 nb + (l & 31)]
 // [tap][c = 32 chunk + 16 ks + 8 (l >> 5) .. + 7] -- the B operand of v_mfma_f32_32x32x16_bf16 in the k order the kernel's A
@@ -470,12 +402,9 @@ int igemm_split_weights(const float* w, int Cout, int taps, int Cin, float* out,
 
 // ---- host side --------------------------------------------------------------------------------
 namespace {
-struct TileCfg { int bm, bn; };
-const TileCfg kCfgs[5] = {{0, 0}, {128, 128}, {128, 64}, {64, 64}, {64, 128}};
-
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-template <int BM, int BN, int TAPS, int SPLIT = 0>
+template <int BM, int BN, int TAPS, int SPLIT>
 int launch_conv(const ConvParams& p, hipStream_t st) {
   static std::atomic<uint64_t> attr_done{0};
   constexpr int smem = SPLIT == 2 ? 2 * BM * 192 : SPLIT ? ((BM + BN > 192) ? 1 : 2) * (BM + BN) * 192 : 2 * (BM + BN) * 36 * 4;
@@ -487,230 +416,18 @@ int launch_conv(const ConvParams& p, hipStream_t st) {
   SR3_LAUNCH_CHECK("k_conv_igemm");
   return SR3_OK;
 }
+// every instantiation: [split form: 0 fp32 MFMA, 1 split while staged, 2 pre-split weights][tile 1..4][taps 1 / 9]
+typedef int (*Launcher)(const ConvParams&, hipStream_t);
+#define SR3_TILE(S, BM, BN) {launch_conv<BM, BN, 1, S>, launch_conv<BM, BN, 9, S>}
+#define SR3_FORM(S) {SR3_TILE(S, 128, 128), SR3_TILE(S, 128, 64), SR3_TILE(S, 64, 64), SR3_TILE(S, 64, 128)}
+constexpr Launcher kLaunch[3][4][2] = {SR3_FORM(0), SR3_FORM(1), SR3_FORM(2)};
+#undef SR3_FORM
+#undef SR3_TILE
 }  // namespace
 
-static thread_local hipEvent_t g_mid_event = nullptr;
-void conv_set_mid_event(hipEvent_t ev) { g_mid_event = ev; }
-
-void conv_pick(const ConvParams& p, int& tile_cfg, int& ksplit) {
-  const int M = p.B * p.Ho * p.Wo;
-  const int Cin = p.C0 + p.C1;
-  const int taps = p.ksize * p.ksize;
-  const int nchunks = cdiv(Cin, 32);
-  static const bool no_wide = getenv("SR3_NO_WIDE") != nullptr;     // A/B knob: never pick the 8-wave 256x128 tile
-  if (tile_cfg == 0) {
-    HaloGeom g;
-    if (p.ksize == 3 && p.stride == 1) {
-      if (p.Cout <= 64 && halo_geometry(p, 6, &g)) tile_cfg = 6;
-      else if (p.Cout > 64 && !no_wide && halo_geometry(p, 9, &g) &&
-               (long)cdiv(p.Cout, 128) * g.tiles_w * g.tiles_h * cdiv(p.B, g.NB) >= 256)
-        tile_cfg = 9;     // 8-wave 256x128 tile: half the weight traffic, when it still fills every CU
-      else if (halo_geometry(p, 5, &g)) tile_cfg = 5;
-    }
-  }
-  // 3 x bf16 split instantiations: the 64x64 tile as well.  In isolation (warm operands) the larger split tiles win on most
-  // layer shapes (128x128: qkv 71 vs 94 us), but INSIDE the forward -- activations just written by the previous kernel, weights
-  // from HBM -- they lose by up to 2.5x on the short-K layers (one round of 384-512 workgroups loads, computes and stores in
-  // lock step), and per-launch timing of the whole forward with every tile forced in turn (plan option gemm_tile,
-  // profiles/r04f_gemm_split_sweep.txt) gives 64x64 2.31 / 1.96 / 1.59 / 2.02 ms for tiles 1-4 (fp32 MFMA: 2.59 / 2.27 / 1.86 / 2.34)
-  if (tile_cfg == 0 && p.igemm_split && (p.ksize == 1 || p.stride == 2)) tile_cfg = 3;
-  if (tile_cfg == 0 && p.ksize == 1) tile_cfg = 3;   // 1x1 convs: the 64x64 tile measured fastest on every layer shape of the
-                                                     // BASELINE networks (76-81 vs 58-64 TF at 16x16, 78 vs 69 at 128x128)
-  if (tile_cfg == 0) {
-    // im2col kernel: largest tile that still gives >= ~2 workgroups per CU
-    const int order_wide[3] = {1, 2, 3};
-    const int order_narrow[2] = {2, 3};
-    const int* order = p.Cout > 64 ? order_wide : order_narrow;
-    const int norder = p.Cout > 64 ? 3 : 2;
-    tile_cfg = order[norder - 1];
-    for (int k = 0; k < norder; ++k) {
-      const TileCfg c = kCfgs[order[k]];
-      if ((long)cdiv(M, c.bm) * cdiv(p.Cout, c.bn) >= 448) { tile_cfg = order[k]; break; }
-    }
-  }
-  if (tile_cfg == 22) {
-    // 1x1 GEMM kernel (gemm1x1.hip; two workgroups per CU): split K below one round of workgroups, >= 4 k-steps (128 channels) per split
-    if (ksplit == 0) {
-      const long tiles = (long)(M / gemm1x1_rows(p)) * (p.Cout / gemm1x1_cols(p));
-      int ks = 1;
-#ifndef SR3_G1_SPLIT_BELOW
-#define SR3_G1_SPLIT_BELOW 128
-#endif
-#ifndef SR3_G1_S2_SPLIT_BELOW
-#define SR3_G1_S2_SPLIT_BELOW 512
-#endif
-      // the stride-2 form walks 9 k-steps per 32-channel chunk: K is long (>= 36 steps at 128 channels) and the maps are small, so it
-      // splits whenever the tiles do not fill the 512 slots, >= 8 k-steps per split
-      const int ksteps = nchunks * taps;
-      const int below = taps == 9 ? SR3_G1_S2_SPLIT_BELOW : SR3_G1_SPLIT_BELOW;
-      if (tiles < below && tiles > 0) {
-        ks = (int)((512 + tiles - 1) / tiles);
-        const int cap = taps == 9 ? (ksteps / 8 > 1 ? ksteps / 8 : 1) : (nchunks / 4 > 1 ? nchunks / 4 : 1);
-        if (ks > cap) ks = cap;
-        if (ks > 16) ks = 16;
-      }
-      while (ks > 1 && (long)(ks - 1) * cdiv(ksteps, ks) >= ksteps) --ks;
-      ksplit = ks;
-    }
-    return;
-  }
-  if (ksplit == 0 && tile_cfg == 11) {
-    // Winograd kernel: one 8-wave workgroup per CU, so one full round of 256 is the target (512 for the four-wave workgroups of
-    // conv3x3_wino2.hip, two per CU); a split keeps >= 4 chunks (64 input channels)
-    WinoGeom wg;
-    if (!wino_geometry(p, &wg)) { ksplit = 1; return; }
-    const long tiles = wino_workgroups(p, wg);
-    const int units = wino_chunks(p);
-    const int maxck = wino_max_chunks_per_split(wg);
-    const long round = p.wino_split >= 2 ? 512 : 256;
-    // (tried in round 6: no split from half a round on for the 8 x 16 tile -- 11 reduce launches fewer, the convs 0.13-0.24 ms slower:
-    // a wash, profiles/r06_wino2_experiments.txt)
-    int ks = 1;
-    if (tiles < round) {
-      ks = (int)((round + tiles - 1) / tiles);
-      const int cap = units / 4 > 1 ? units / 4 : 1;
-      if (ks > cap) ks = cap;
-      if (ks > 16) ks = 16;
-    }
-    if (wg.NB != 1 && ks < 2 && units >= 2) ks = 2;          // the four-image tile (8 x 8 maps) has no direct epilogue
-    if (cdiv(units, ks) > maxck) ks = cdiv(units, maxck);    // chunks per split the kernel's LDS block of GroupNorm pairs holds
-    while (ks > 1 && (long)(ks - 1) * cdiv(units, ks) >= units) --ks;
-    ksplit = ks;
-    return;
-  }
-  if (ksplit == 0) {
-    long tiles;
-    int units, min_units;
-    if (tile_cfg >= 5) {
-      HaloGeom g;
-      if (!halo_geometry(p, tile_cfg, &g)) { ksplit = 1; return; }
-      const int bn = halo_cfg_bn(tile_cfg);
-      tiles = (long)cdiv(p.Cout, bn) * g.tiles_w * g.tiles_h * cdiv(p.B, g.NB);
-      units = nchunks; min_units = 2;
-    } else {
-      const TileCfg c = kCfgs[tile_cfg];
-      tiles = (long)cdiv(M, c.bm) * cdiv(p.Cout, c.bn);
-      units = nchunks * taps; min_units = 6;
-    }
-    int ks = 1;
-    // split K until the grid gives ~2 workgroups per CU (in-run A/B on MI355X: threshold 384 -> 14.87 ms per
-    // step, 256 -> 14.96 ms; SR3_KSPLIT_TILES overrides)
-    static const long split_below_env = getenv("SR3_KSPLIT_TILES") ? atol(getenv("SR3_KSPLIT_TILES")) : 384;
-    // the 8-wave tiles run one workgroup per CU: one full round of 256 is the target there
-    const bool wide = halo_cfg_one_wg_per_cu(tile_cfg);
-    const long split_below = wide ? 256 : split_below_env;
-    if (tiles < split_below) {
-      ks = (int)(((wide ? 256 : 512) + tiles - 1) / tiles);
-      const int cap = units / min_units > 1 ? units / min_units : 1;
-      if (ks > cap) ks = cap;
-      if (ks > 16) ks = 16;
-    }
-    while (ks > 1 && (long)(ks - 1) * cdiv(units, ks) >= units) --ks;   // no empty split
-    ksplit = ks;
-  }
-}
-
-// rows per block of the split-K reduce kernel; with statistics it must divide Ho*Wo (0: cannot fuse)
-int splitk_rows_per_block(const ConvParams& p, bool stats) {
-  const long M = (long)p.B * p.Ho * p.Wo;
-  const int HoWo = p.Ho * p.Wo;
-  int rpb = 64;
-  while (rpb > 4 && M / rpb < 1024) rpb >>= 1;
-  if (stats) {
-    while (rpb > 1 && HoWo % rpb) rpb >>= 1;
-    if (HoWo % rpb || HoWo / rpb > 256) return 0;
-  }
-  return rpb;
-}
-
-size_t conv_splitk_bytes(const ConvParams& p, int tile_cfg, int ksplit) {
-  conv_pick(p, tile_cfg, ksplit);
-  if (ksplit <= 1) return 0;
-  return (size_t)ksplit * p.B * p.Ho * p.Wo * p.Cout * sizeof(float);
-}
-
-int conv_forward(const ConvParams& pin, int tile_cfg, int ksplit, float* scratch, size_t scratch_bytes,
-                 hipStream_t st) {
-  ConvParams p = pin;
-  const int Cin = p.C0 + p.C1;
-  if ((p.C0 & 3) || (p.C1 & 3) || (p.Cout & 3)) { set_error("conv: channel counts must be multiples of 4 (C0=%d C1=%d Cout=%d)", p.C0, p.C1, p.Cout); return SR3_E_UNSUPPORTED; }
-  if (p.ksize != 1 && p.ksize != 3) { set_error("conv: ksize %d unsupported", p.ksize); return SR3_E_UNSUPPORTED; }
-  if (p.stride != 1 && p.stride != 2) { set_error("conv: stride %d unsupported", p.stride); return SR3_E_UNSUPPORTED; }
-  if (p.act != 0 && !p.ss) { set_error("conv: act needs ss"); return SR3_E_BADARG; }
-  if (p.drop_thresh != 0 && (p.C1 != 0 || p.ups != 0 || p.act == 0)) { set_error("conv: dropout needs a single-source, non-upsampled, activated input"); return SR3_E_UNSUPPORTED; }
-  if (p.C1 > 0 && !p.src1) { set_error("conv: C1 > 0 needs src1"); return SR3_E_BADARG; }
-  if (p.res0 && p.RC0 + p.RC1 != p.Cout) { set_error("conv: residual channels %d+%d != Cout %d", p.RC0, p.RC1, p.Cout); return SR3_E_BADARG; }
-  const int pad = p.ksize / 2;
-  const int Hi = p.Hs << p.ups, Wi = p.Ws << p.ups;
-  if ((Hi + 2 * pad - p.ksize) / p.stride + 1 != p.Ho || (Wi + 2 * pad - p.ksize) / p.stride + 1 != p.Wo) {
-    set_error("conv: output dims %dx%d inconsistent with input %dx%d k%d s%d", p.Ho, p.Wo, Hi, Wi, p.ksize, p.stride);
-    return SR3_E_BADARG;
-  }
-  {
-    const double lim = 2147483647.0;
-    const double e_in = (double)p.B * p.Hs * p.Ws * (double)(p.C0 > p.C1 ? p.C0 : p.C1);
-    const double e_w = (double)p.Cout * p.ksize * p.ksize * (double)Cin;
-    const double e_ss = (double)p.B * Cin * 2.0;
-    if (e_in >= lim || e_w >= lim || e_ss >= lim) { set_error("conv: tensor exceeds 2^31 elements (32-bit offsets)"); return SR3_E_UNSUPPORTED; }
-  }
-  conv_pick(p, tile_cfg, ksplit);
-  p.ksplit = ksplit;
-  // write-through stores are buffer stores with 32-bit offsets: an output, or a set of slabs, of 4 GiB or more keeps plain stores
-  if (!store_wt_fits((size_t)ksplit * p.B * p.Ho * p.Wo * p.Cout * sizeof(float))) p.store_wt = 0;
-  if (p.ostat && ksplit == 1 && (tile_cfg < 5 || tile_cfg >= 22)) { set_error("conv: fused output statistics need the halo kernel or split-K"); return SR3_E_UNSUPPORTED; }
-  if (p.ostat && ksplit > 1 && splitk_rows_per_block(p, true) == 0) { set_error("conv: Ho*Wo does not allow fused split-K statistics"); return SR3_E_UNSUPPORTED; }
-  { static const char* e = getenv("SR3_CONV_DBG"); p.dbg = e ? atoi(e) : 0; }
-  if (ksplit > 1) {
-    const size_t need = (size_t)ksplit * p.B * p.Ho * p.Wo * p.Cout * sizeof(float);
-    if (!scratch || scratch_bytes < need) { set_error("conv: split-K scratch too small (%zu < %zu)", scratch_bytes, need); return SR3_E_NOMEM; }
-    p.partial = scratch;
-  }
-  int rc;
-  const bool k3 = p.ksize == 3;
-  if (p.x2_w && (tile_cfg < 5 || tile_cfg == 11 || tile_cfg >= 22 || p.ups)) { set_error("conv: the fused 1x1 segment needs the halo kernel without upsampling"); return SR3_E_UNSUPPORTED; }
-  if (p.x2_w && ((p.x2_C0 & 3) || (p.x2_C1 & 3) || !p.x2_src0 || (p.x2_C1 > 0 && !p.x2_src1))) { set_error("conv: bad x2 segment"); return SR3_E_BADARG; }
-  if (tile_cfg == 22) {
-    rc = gemm1x1_forward(p, 2, st);
-  } else if (tile_cfg == 11) {
-    rc = conv3x3_wino_forward(p, p.wino_u, st);
-  } else if (tile_cfg >= 5) {
-    HaloGeom g;
-    if (tile_cfg > 10 || !halo_geometry(p, tile_cfg, &g)) { set_error("conv: halo tile_cfg %d does not fit this problem", tile_cfg); return SR3_E_UNSUPPORTED; }
-    const int nchunks = cdiv(Cin, 32);
-    if ((long)(ksplit - 1) * cdiv(nchunks, ksplit) >= nchunks && ksplit > 1) { set_error("conv: ksplit %d leaves an empty split over %d chunks", ksplit, nchunks); return SR3_E_BADARG; }
-    rc = conv3x3_halo_forward(p, tile_cfg, g, st);
-  } else
-  if (p.igemm_split && p.w_split) switch (tile_cfg) {
-    case 1: rc = k3 ? launch_conv<128, 128, 9, 2>(p, st) : launch_conv<128, 128, 1, 2>(p, st); break;
-    case 2: rc = k3 ? launch_conv<128, 64, 9, 2>(p, st) : launch_conv<128, 64, 1, 2>(p, st); break;
-    case 3: rc = k3 ? launch_conv<64, 64, 9, 2>(p, st) : launch_conv<64, 64, 1, 2>(p, st); break;
-    case 4: rc = k3 ? launch_conv<64, 128, 9, 2>(p, st) : launch_conv<64, 128, 1, 2>(p, st); break;
-    default: set_error("conv: bad tile_cfg %d", tile_cfg); return SR3_E_BADARG;
-  } else
-  if (p.igemm_split) switch (tile_cfg) {
-    case 1: rc = k3 ? launch_conv<128, 128, 9, 1>(p, st) : launch_conv<128, 128, 1, 1>(p, st); break;
-    case 2: rc = k3 ? launch_conv<128, 64, 9, 1>(p, st) : launch_conv<128, 64, 1, 1>(p, st); break;
-    case 3: rc = k3 ? launch_conv<64, 64, 9, 1>(p, st) : launch_conv<64, 64, 1, 1>(p, st); break;
-    case 4: rc = k3 ? launch_conv<64, 128, 9, 1>(p, st) : launch_conv<64, 128, 1, 1>(p, st); break;
-    default: set_error("conv: bad tile_cfg %d", tile_cfg); return SR3_E_BADARG;
-  } else
-  switch (tile_cfg) {
-    case 1: rc = k3 ? launch_conv<128, 128, 9>(p, st) : launch_conv<128, 128, 1>(p, st); break;
-    case 2: rc = k3 ? launch_conv<128, 64, 9>(p, st) : launch_conv<128, 64, 1>(p, st); break;
-    case 3: rc = k3 ? launch_conv<64, 64, 9>(p, st) : launch_conv<64, 64, 1>(p, st); break;
-    case 4: rc = k3 ? launch_conv<64, 128, 9>(p, st) : launch_conv<64, 128, 1>(p, st); break;
-    default: set_error("conv: bad tile_cfg %d", tile_cfg); return SR3_E_BADARG;
-  }
-  if (rc) return rc;
-  if (ksplit > 1) {
-    if (g_mid_event) { SR3_HIP(hipEventRecord(g_mid_event, st)); g_mid_event = nullptr; }
-    if (p.fold) return splitk_reduce_fold(p, *p.fold, st);      // the reduce per (image, consumer group) + the next op's GroupNorm fold
-    const int rpb = splitk_rows_per_block(p, p.ostat != nullptr);
-    const long M = (long)p.B * p.Ho * p.Wo;
-    hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((M + rpb - 1) / rpb)), dim3(256), 0, st, p, rpb);
-    SR3_LAUNCH_CHECK("k_splitk_reduce");
-  }
-  return SR3_OK;
+int conv_igemm_forward(const ConvParams& p, int tile, hipStream_t st) {
+  if (tile < 1 || tile > 4) { set_error("conv: bad tile_cfg %d", tile); return SR3_E_BADARG; }
+  return kLaunch[p.igemm_split ? (p.w_split ? 2 : 1) : 0][tile - 1][p.ksize == 3](p, st);
 }
 
 }  // namespace sr3

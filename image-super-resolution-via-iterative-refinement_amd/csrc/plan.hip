@@ -315,7 +315,7 @@ enum ChoiceRule { RULE_FULL, RULE_HEAD };
 static ConvChoice choose_conv(const sr3_plan* P, ConvParams c, size_t w, bool has_q, bool has_drop, bool train, ChoiceRule rule = RULE_FULL) {
   ConvChoice ch = {P->tile_cfg, P->ksplit, 0, 0, 0, 0, false, 0};
   const bool full = rule == RULE_FULL;
-  auto repick = [&](int tile) { ch.tile_cfg = tile; ch.ksplit = P->ksplit; conv_pick(c, ch.tile_cfg, ch.ksplit); };
+  auto repick = [&](int tile) { const ConvPick pk = conv_pick(c, tile, P->ksplit); ch.tile_cfg = pk.tile; ch.ksplit = pk.ksplit; };
   // opt-in: the 3 x bf16 split MFMA instantiation of the 8-wave tile wherever it fits (inference plans only)
   HaloGeom sg; WinoGeom wg;
   if (full && P->split_bf16 && !train && ch.tile_cfg == 0 && c.ksize == 3 && c.stride == 1 && c.Cout > 64 && halo_geometry(c, 10, &sg)) ch.tile_cfg = 10;
@@ -334,7 +334,7 @@ static ConvChoice choose_conv(const sr3_plan* P, ConvParams c, size_t w, bool ha
     // (... unless the plain GEMM kernel takes the layer on its 64-column tile: plan options gemm2 + gemm_s2 + gemm_n64, below)
     if (P->gemm_split && P->gemm2 && P->gemm_s2 && P->gemm_n64 && c.ksize == 3 && c.stride == 2 && P->wsplit_of.count(w) && gemm1x1_fits(c, 2)) c.igemm_split = 1;
   }
-  conv_pick(c, ch.tile_cfg, ch.ksplit);
+  repick(ch.tile_cfg);
   ch.wino_split = c.wino_split;
   // plan option wino_up = 0 (A/B knob): Upsample's conv keeps all sixteen positions on the two-workgroup kernel (reported as tile 25 / 26)
   ch.wino_full = (ch.tile_cfg == 11 && c.wino_split >= 2 && c.ups == 1 && !P->wino_up) ? 1 : 0;
@@ -882,10 +882,9 @@ int run_forward(sr3_plan* P, bool train, const float* x, const float* cond, int 
           }
           c.w_split = P->derived_ptr + ch.wsplit_off;
         }
-        if (mid && ch.ksplit > 1) conv_set_mid_event(mid[op_index - 1]);
         FoldTail ft;
         if (o.fold_fused) { ft = make_fold_tail(o.tail, d.norm_groups, params, ws, R); c.fold = &ft; }
-        rc = conv_forward(c, ch.tile_cfg, ch.ksplit, bind<float>(ws, R.scratch_off), R.scratch_bytes, st);
+        rc = conv_forward(c, ch.tile_cfg, ch.ksplit, bind<float>(ws, R.scratch_off), R.scratch_bytes, st, mid ? mid[op_index - 1] : nullptr);
         break;
       }
       case OP_ATTN: {
@@ -1298,21 +1297,8 @@ int sr3_unet_forward_profile(sr3_plan* plan, const float* x_nchw, const float* c
       if (o.kind == OP_CONV) {
         const ConvParams& c = o.conv.cp;
         const int tile = o.conv.ch.tile_cfg;
-        // 51-54 im2col kernel tile configs; 55/56 halo-tile 3x3 kernel (57/58: with the fused 1x1 segment)
-        //        155-158: the same four on the opt-in split-bf16 instantiations; 255/257: the 8-wave 256x128 tile
-        //        (cfg 9), 355/357: its split-bf16 twin (cfg 10); 455: the Winograd F(2x2,3x3) kernel (cfg 11), 465: its four-image
-        //        tile of the 8x8 maps, 555: its 3 x bf16 split instantiation (plan option wino_split)
-        {
-          static const int base[13] = {0, 1, 2, 3, 4, 5, 6, 105, 106, 205, 305, 405, 505};
-          if (tile == 22) kind += 182;                                               // 232: the 1x1 GEMM kernel (gemm1x1.hip)
-          else
-          kind += base[(tile == 11 && c.wino_split) ? 12 : tile] + ((tile >= 5 && o.conv.x2_src0 != NO_OFF) ? 2 : 0);
-          if (tile == 11 && c.wino_split == 2) kind += 20;                         // 575: the two-workgroups-per-CU split kernel (conv3x3_wino2.hip)
-          if (tile == 11 && c.wino_split == 3) kind += 30;                         // 585: ... its ragged instantiation
-          if (tile >= 1 && tile <= 4 && c.igemm_split) kind += 600;           // 651-654: the im2col tiles on their 3 x bf16 split instantiation
-          WinoGeom wg;
-          if (tile == 11 && wino_geometry(c, &wg) && wg.NB != 1) kind += 10;      // 465: the four-image 8x8 tile
-        }
+        WinoGeom wg;
+        kind = profile_kind(tile, c.wino_split, c.igemm_split, tile == 11 && wino_geometry(c, &wg) && wg.NB != 1, o.conv.x2_src0 != NO_OFF);      // (tile_code.h)
         fl = conv_flops(c);
         if (o.conv.ch.ksplit > 1) {      // split the op into its GEMM kernel and its split-K reduce kernel
           float a = 0.f;

@@ -279,6 +279,72 @@ __global__ __launch_bounds__(256) void k_rows_fold(const ConvParams p, const Fol
   }
 }
 
+// ---- split-K reduction + epilogue (+ optional partial GroupNorm statistics of the output) -------
+// A block owns `rpb` consecutive output rows (pixels) -- inside one image when statistics are
+// requested -- lanes run along channel quads (coalesced 16-byte accesses), the 4 waves along rows.
+__global__ __launch_bounds__(256) void k_splitk_reduce(const ConvParams p, int rpb) {
+  __shared__ double red[4 * 64 * 8];
+  const int HoWo = p.Ho * p.Wo;
+  const size_t M = (size_t)p.B * HoWo;
+  const int nq = p.Cout >> 2;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t row0 = (size_t)blockIdx.x * rpb;
+  const WtDst wdst = wt_dst(p.out, M * p.Cout * sizeof(float), (p.store_wt & STORE_WT_REDUCE) != 0);    // plan option store_wt (sr3_common.h)
+  for (int q0 = 0; q0 < nq; q0 += 64) {
+    const int q = q0 + lane;
+    const int n = q * 4;
+    double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+    if (q < nq) {
+      f32x4 cb = {0.f, 0.f, 0.f, 0.f};
+      if (p.bias) cb += *reinterpret_cast<const f32x4*>(p.bias + n);
+      if (p.x2_w && p.x2_bias) cb += *reinterpret_cast<const f32x4*>(p.x2_bias + n);
+      for (int r = wave; r < rpb; r += 4) {
+        const size_t m = row0 + r;
+        if (m >= M) break;
+        f32x4 v = cb;
+        // four slabs in flight (round 6; one load per iteration made the wave wait for each slab in turn); same order of additions
+        auto slab = [&](int s) { return *reinterpret_cast<const f32x4*>(p.partial + ((size_t)s * M + m) * p.Cout + n); };
+        int s = 0;
+        for (; s + 4 <= p.ksplit; s += 4) {
+          const f32x4 a0 = slab(s), a1 = slab(s + 1), a2 = slab(s + 2), a3 = slab(s + 3);
+          v += a0; v += a1; v += a2; v += a3;
+        }
+        for (; s < p.ksplit; ++s) v += slab(s);
+        const int b = (int)(m / HoWo);
+        if (p.film) v += *reinterpret_cast<const f32x4*>(p.film + (size_t)b * p.film_stride + n);
+        if (p.res0) {
+          if (n < p.RC0) v += *reinterpret_cast<const f32x4*>(p.res0 + m * p.RC0 + n);
+          else v += *reinterpret_cast<const f32x4*>(p.res1 + m * p.RC1 + (n - p.RC0));
+        }
+        store16(wdst, m * p.Cout + n, v);
+        if (p.ostat) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { const double dv = (double)v[e]; s1[e] += dv; s2[e] += dv * dv; }
+        }
+      }
+    }
+    if (p.ostat) {      // uniform branch: fixed-order reduction over the 4 row lanes, one plain store
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { red[(wave * 64 + lane) * 8 + e] = s1[e]; red[(wave * 64 + lane) * 8 + 4 + e] = s2[e]; }
+      __syncthreads();
+      if (wave == 0 && q < nq && row0 < M) {
+        const int b = (int)(row0 / HoWo);
+        const int T = HoWo / rpb;
+        const int slice = (int)(row0 - (size_t)b * HoWo) / rpb;
+        double* o = p.ostat + (((size_t)b * T + slice) * p.Cout + n) * 2;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          double a1 = 0.0, a2 = 0.0;
+#pragma unroll
+          for (int w = 0; w < 4; ++w) { a1 += red[(w * 64 + lane) * 8 + e]; a2 += red[(w * 64 + lane) * 8 + 4 + e]; }
+          o[2 * e] = a1; o[2 * e + 1] = a2;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 // the group grid covers this tensor in whole channel quads, a group has at most 128 channels (LDS table) and at most 64 of them per
 // source side (lanes: 16 quads here, 128 threads for the other source)
 bool fold_tail_fits(int C, int Ctot, int c_off, int groups) {
@@ -297,11 +363,19 @@ int chan_stats_fold(const float* x, int B, int HW, int C, double* stat, const Fo
   return SR3_OK;
 }
 
-int splitk_reduce_fold(const ConvParams& p, const FoldTail& f, hipStream_t st) {
-  if (!fold_tail_fits(p.Cout, f.Ctot, f.c_off, f.groups) || !p.ostat) { set_error("splitk_reduce_fold: grouping does not fit"); return SR3_E_UNSUPPORTED; }
-  hipLaunchKernelGGL(k_rows_fold<true>, dim3(p.B * f.groups), dim3(256), 0, st, p, f, static_cast<const float*>(nullptr), p.Cout,
-                     p.Ho * p.Wo, p.ostat);
-  SR3_LAUNCH_CHECK("k_rows_fold");
+int splitk_reduce(const ConvParams& p, hipStream_t st) {
+  if (p.fold) {      // the reduce per (image, consumer group) + the next op's GroupNorm fold
+    const FoldTail& f = *p.fold;
+    if (!fold_tail_fits(p.Cout, f.Ctot, f.c_off, f.groups) || !p.ostat) { set_error("splitk_reduce_fold: grouping does not fit"); return SR3_E_UNSUPPORTED; }
+    hipLaunchKernelGGL(k_rows_fold<true>, dim3(p.B * f.groups), dim3(256), 0, st, p, f, static_cast<const float*>(nullptr), p.Cout,
+                       p.Ho * p.Wo, p.ostat);
+    SR3_LAUNCH_CHECK("k_rows_fold");
+    return SR3_OK;
+  }
+  const int rpb = splitk_rows_per_block(p, p.ostat != nullptr);
+  const long M = (long)p.B * p.Ho * p.Wo;
+  hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((M + rpb - 1) / rpb)), dim3(256), 0, st, p, rpb);
+  SR3_LAUNCH_CHECK("k_splitk_reduce");
   return SR3_OK;
 }
 

@@ -168,8 +168,6 @@ struct FoldTail {
 bool fold_tail_fits(int C, int Ctot, int c_off, int groups);
 // stand-alone form: statistics of x [B][HW][C] (partials [B][1][C][2] into `stat`) + the fold
 int chan_stats_fold(const float* x, int B, int HW, int C, double* stat, const FoldTail& f, hipStream_t st);
-struct ConvParams;
-int splitk_reduce_fold(const ConvParams& p, const FoldTail& f, hipStream_t st);
 
 // ---- convolution (implicit GEMM on v_mfma_f32_32x32x2_f32) --------------------------------
 // Activations are NHWC fp32.  The input is the *virtual* channel concat of up to two sources,
@@ -245,15 +243,34 @@ __device__ __forceinline__ float drop_mask(unsigned seed, unsigned idx, unsigned
   return hash32(idx * 0x9E3779B9U + seed) >= thresh ? scale : 0.f;
 }
 
-// tile_cfg: 0 = auto; im2col-staged implicit GEMM: 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 64x128 (ConvParams::igemm_split
-// selects the 3 x bf16 split instantiation of the same tiles);
-// halo-tile 3x3 stride-1 kernel: 5 = 128x128, 6 = 256(M)x64(N).  ksplit: 0 = auto
-int conv_forward(const ConvParams& p, int tile_cfg, int ksplit, float* splitk_scratch,
-                 size_t splitk_scratch_bytes, hipStream_t st);
+// ---- conv dispatch (conv_dispatch.hip) over the five kernel families: im2col (conv_igemm.hip), halo, Winograd 8-wave, Winograd
+// two-workgroup, plain GEMM.  tile_cfg is the kernel tile itself (tile_code.h has the numbers), 0 = conv_pick chooses; ksplit 0 = auto
+struct ConvPick { int tile, ksplit; };
+ConvPick conv_pick(const ConvParams& p, int tile_cfg, int ksplit);
+// mid (profiling): recorded between the conv kernel and the split-K reduce, when the conv splits
+int conv_forward(const ConvParams& p, int tile_cfg, int ksplit, float* splitk_scratch, size_t splitk_scratch_bytes, hipStream_t st,
+                 hipEvent_t mid = nullptr);
 // scratch bytes the auto heuristic may ask for (upper bound) for this problem
 size_t conv_splitk_bytes(const ConvParams& p, int tile_cfg, int ksplit);
-void conv_pick(const ConvParams& p, int& tile_cfg, int& ksplit);
 int splitk_rows_per_block(const ConvParams& p, bool stats);
+// the reduce behind a split-K conv (small_kernels.hip): k_rows_fold where p.fold is set, k_splitk_reduce otherwise
+int splitk_reduce(const ConvParams& p, hipStream_t st);
+// THE split-K rule: `units` k-steps (or chunks) over ks splits of cdiv(units, ks) each.  Below `below` workgroups, as many splits as
+// fill `round` workgroup slots, at least min_units per split, at most 16, and none of them empty
+inline bool split_leaves_empty(int units, int ks) { return ks > 1 && (long)(ks - 1) * ((units + ks - 1) / ks) >= units; }
+inline int split_shrink(int units, int ks) { while (split_leaves_empty(units, ks)) --ks; return ks; }
+inline int split_k(long tiles, long below, long round, int units, int min_units) {
+  int ks = 1;
+  if (tiles < below && tiles > 0) {
+    ks = (int)((round + tiles - 1) / tiles);
+    const int cap = units / min_units > 1 ? units / min_units : 1;
+    if (ks > cap) ks = cap;
+    if (ks > 16) ks = 16;
+  }
+  return split_shrink(units, ks);
+}
+// the im2col kernel on tile 1-4 (conv_igemm.hip); p.igemm_split / p.w_split select the 3 x bf16 split instantiations
+int conv_igemm_forward(const ConvParams& p, int tile, hipStream_t st);
 // pre-split weights of the im2col SPLIT instantiations: floats of the derived block for `numel` weights, and the transform
 size_t igemm_wsplit_floats(int Cout, int taps, int Cin);
 int igemm_split_weights(const float* w, int Cout, int taps, int Cin, float* out, hipStream_t st);
@@ -262,9 +279,6 @@ bool gemm1x1_fits(const ConvParams& p, int mi);
 int gemm1x1_cols(const ConvParams& p);      // 128, or 64 (waves 2 x 2) where Cout % 128 != 0
 int gemm1x1_forward(const ConvParams& p, int mi, hipStream_t st);
 int gemm1x1_rows(const ConvParams& p);      // 64, or 32 where 64-row tiles would leave workgroup slots empty
-// profiling aid: when non-null, conv_forward records this event between the GEMM kernel and the
-// split-K reduce kernel (then resets the pointer).  Thread-local.
-void conv_set_mid_event(hipEvent_t ev);
 struct HaloGeom {
   int TH, TW, NB;          // spatial tile per image, images per workgroup tile (TH*TW*NB = BM)
   int log_tw, log_thw;     // log2(TW), log2(TH*TW)

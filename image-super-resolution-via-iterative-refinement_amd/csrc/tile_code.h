@@ -30,6 +30,20 @@ inline int tile_encode(int tile, int wino_split, int igemm_split, bool has_wspli
   if (tile >= 1 && tile <= 4 && igemm_split) return (has_wsplit ? 17 : 13) + tile;
   return tile;
 }
+// ... and the number sr3_unet_forward_profile reports for a conv's kernel (op_kind; 59 is the split-K reduce behind a conv):
+//   51-54 im2col kernel tiles, 651-654 the same on their 3 x bf16 split instantiation; 55 / 56 halo-tile 3x3 kernel (57 / 58: with the fused
+//   1x1 segment), 155-158 the same four on the opt-in split-bf16 instantiations, 255 / 257 the 8-wave 256x128 tile (cfg 9), 355 / 357 its
+//   split-bf16 twin (cfg 10); 455 the Winograd F(2x2,3x3) kernel (cfg 11), 555 its 3 x bf16 split instantiation (plan option wino_split),
+//   575 the two-workgroups-per-CU split kernel (conv3x3_wino2.hip), 585 its ragged instantiation, each + 10 on the four-image tile of the
+//   8x8 maps (465, 565); 232 the 1x1 GEMM kernel (gemm1x1.hip)
+inline int profile_kind(int tile, int wino_split, int igemm_split, bool four_image, bool fused_segment) {
+  static const int base[13] = {0, 1, 2, 3, 4, 5, 6, 105, 106, 205, 305, 405, 505};
+  if (tile == 22) return 232;
+  int kind = 50 + base[(tile == 11 && wino_split) ? 12 : tile] + ((tile >= 5 && fused_segment) ? 2 : 0);
+  if (tile == 11) kind += (wino_split == 2 ? 20 : wino_split == 3 ? 30 : 0) + (four_image ? 10 : 0);
+  if (tile >= 1 && tile <= 4 && igemm_split) kind += 600;
+  return kind;
+}
 
 // ConvParams with the shape fields alone: everything else zero, ksplit 1 (conv_forward sets the real one)
 inline ConvParams conv_shape(int B, int Hs, int Ws, int ups, int stride, int ksize, int C0, int C1, int Cout) {

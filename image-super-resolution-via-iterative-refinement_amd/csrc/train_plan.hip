@@ -102,8 +102,7 @@ void choose_dgrad(const sr3_plan* P, Dgrad& d, size_t wu_cap, size_t slab_cap) {
   // filters into the region the Winograd data gradients use for theirs
   d.wu = WU_GEMM;
   if (c.igemm_split && P->gemm2 && gemm1x1_fits(c, 2) && (!(c.Cout & 127) || P->gemm_n64) && wu_bytes(d) <= wu_cap) {
-    int t = 22, ks = 0;
-    conv_pick(c, t, ks);
+    const int ks = conv_pick(c, 22, 0).ksplit;
     if (ks == 1 || (size_t)ks * c.B * c.Ho * c.Wo * c.Cout * sizeof(float) <= slab_cap) { d.tile = 22; d.ksplit = ks; return; }
   }
   d.wu = WU_NONE;
@@ -573,10 +572,9 @@ int sr3_conv_dgrad_f32(sr3_plan* plan, const float* dy, const float* w_ohwi, int
   // query.  (choose_dgrad above is capped by the unrounded room, so a scratch less than 256 bytes short of the rounded size is refused
   // here instead of running: such a caller is below the query either way)
   if (bufs.slab_bytes < al256(slabs)) { set_error("%s: scratch too small (%zu < %zu)", who, scratch_bytes, lay.slabs + al256(slabs)); return SR3_E_NOMEM; }
-  int tile = d.tile, ks = d.ksplit;
-  conv_pick(d.c, tile, ks);                            // (what conv_forward resolves tile 0 / ksplit 0 to)
-  if (tile_out) *tile_out = tile_encode(tile, d.c.wino_split, d.c.igemm_split, false);
-  if (ksplit_out) *ksplit_out = ks;
+  const ConvPick pk = conv_pick(d.c, d.tile, d.ksplit);      // (what conv_forward resolves tile 0 / ksplit 0 to)
+  if (tile_out) *tile_out = tile_encode(pk.tile, d.c.wino_split, d.c.igemm_split, false);
+  if (ksplit_out) *ksplit_out = pk.ksplit;
   if (derived_kind_out) *derived_kind_out = d.wu;
   return dgrad_conv(d, stride, f.Ho, f.Wo, dy, w_ohwi, Cout_w, dA, bufs, plan->launch_gemm_epi(), static_cast<hipStream_t>(stream));
 }
