@@ -28,8 +28,6 @@ int zero_insert(const float* g, int B, int Ho, int Wo, int C, float* z, hipStrea
 int w_flip_transpose(const float* w, int Cout, int taps, int Cin, int CoutP, float* wt, hipStream_t st);
 int colsums(const float* g, int B, int HW, int C, double* part, float* dbias, float* dfilm, int film_stride,
             hipStream_t st);
-int l1_loss_grad(const float* z, const float* e, int B, int Cc, int HW, int CP, float scale, bool l2, float* g_nhwc,
-                 double* loss_part, float* loss_out, hipStream_t st);
 // The training objective of one step (sr3_train_step_ex / sr3_loss_grad_f32): per-image target coefficients and weight (device, all
 // three or none: target z, weight 1) and the pixel loss
 enum { LOSS_L1 = 0, LOSS_L2 = 1, LOSS_HUBER = 2 };
@@ -49,13 +47,12 @@ struct Objective {
 enum { HYB_A = 0, HYB_B, HYB_C1, HYB_C2, HYB_LOG_BETA, HYB_LOG_BETA_TILDE, HYB_LAST, HYB_STRIDE = 8 };
 int check_objective_args(const char* who, const float* tgt_z, const float* tgt_x0, const float* weight, int loss_kind, int min_kind,
                          float huber_delta);
-// loss sum and its gradient g [B,HW,CP] under `o`: l1_loss_grad's launch for target z / weight 1 / L1 or L2, else k_loss_grad
-int objective_loss_grad(const float* z, const float* hr, const float* e, const Objective& o, int B, int Cc, int HW, int CP, float scale,
-                        float* g_nhwc, double* loss_part, float* loss_out, hipStream_t st);
-// the hybrid loss L_simple + lambda L_vlb of a network with a variance head (e: [B, 2 Cc, HW]; x_t: [B, Cc, HW]): g [B, HW, CP >= 2 Cc],
-// loss_out[0] = sum w rho(d) + lambda sum vlb, vlb_out[0] (may be null) = sum vlb in bits.  loss_part: 2 * LOSS_GRAD_BLOCKS doubles
-int hybrid_loss_grad(const float* z, const float* hr, const float* xt, const float* e, const Objective& o, int B, int Cc, int HW, int CP,
-                     float scale, float* g_nhwc, double* loss_part, float* loss_out, float* vlb_out, hipStream_t st);
+// the tensors of the loss: z, hr, e [B, Cc, HW] (hr read only with tgt_x0 or o.hyb), g [B, HW, CP], LOSS_GRAD_BLOCKS doubles of loss_part.
+// With o.hyb (a variance head): e [B, 2 Cc, HW], x_t [B, Cc, HW], CP >= 2 Cc, twice the doubles, vlb_out (may be null) = sum vlb in bits
+struct LossTensors { const float* z; const float* hr; const float* xt; const float* e; float* g_nhwc; double* loss_part; float* loss_out; float* vlb_out; };
+// loss sum and its gradient under `o`: the plain form of k_loss_grad for target z / weight 1 / L1 or L2, else the objective's; with
+// o.hyb the hybrid loss L_simple + lambda L_vlb, loss_out[0] = sum w rho(d) + lambda sum vlb
+int objective_loss_grad(const LossTensors& t, const Objective& o, int B, int Cc, int HW, int CP, float scale, hipStream_t st);
 int nchw_to_nhwc_pad(const float* a, int Ca, const float* b, int Cb, int B, int HW, int CP, float* out, hipStream_t st);
 // Per-image terms of the variational bound (vlb_eval.hip): vb_out / mse_out [b * ostride] (rows: a row index per image;
 // step2: the device step counter, one row for all images and row j of [table_rows, B] outputs; both null: image b reads row b) = the
@@ -65,6 +62,22 @@ int vlb_terms(const float* x0, const float* xt, const float* out, const float* t
 size_t vlb_terms_scratch(int batch);
 // sr3_train_step_ex3: where the step's per-image terms go (out null: none are computed), and the rows' table where the objective has none
 struct PerImage { float* out = nullptr; double* part = nullptr; const float* scal = nullptr; };
+// Everything one training step is given (train_plan.hip): each sr3_train_step* entry fills it by name, train_step_checked refuses or
+// settles it, run_train launches it.  As an entry fills it the fields hold the caller's arguments as they came (obj.kind -1: the plan's
+// loss; obj.hyb: step_scalars; obj.vlb_w: vlb_weight; pi.out / pi.part: per_image_out / scratch, pi.scal unset)
+struct TrainStep {
+  const float* hr = nullptr; const float* cond = nullptr; int cond_channels = 0; const float* z = nullptr;
+  const float* q_ca = nullptr; const float* q_cb = nullptr;      // q_sample's coefficients, per image
+  const float* level = nullptr; const int64_t* tstep = nullptr;  // the SR3 variant's noise level / the DDPM variant's timestep
+  const float* freq = nullptr; const float* params = nullptr; float* grads = nullptr;
+  void* workspace = nullptr; size_t workspace_bytes = 0;
+  float* loss_sum_out = nullptr; float grad_scale = 1.f;
+  float dropout_p = 0.f; unsigned dropout_seed = 0;
+  int n_marks = 0; const size_t* mark_offsets = nullptr; void* const* mark_events = nullptr;      // gradient-ready marks
+  int batch = 0; hipStream_t stream = nullptr;
+  Objective obj; float* vlb_sum_out = nullptr;
+  PerImage pi; size_t pi_scratch_bytes = 0;
+};
 
 // Weight gradient of a conv (wgrad.hip): dw[n][tap][c] = sum_m dy[m][n] * a_tap[m][c], a = prologue(x0|x1)
 // recomputed on the fly (same ConvParams geometry as the forward; p.out / p.w unused).

@@ -260,92 +260,45 @@ __global__ __launch_bounds__(256) void k_w_flip_transpose(const float* __restric
   }
 }
 
-// T11: the pixel loss of set_loss (diffusion.py:84-90,245) and its gradient w.r.t. eps_hat, written NHWC with the
-// channel dim padded to CP.  L1 (nn.L1Loss(reduction='sum'), what define_G configures): loss_part[block] = sum |z - e|,
-// g = -sign(z - e) * scale.  L2 (nn.MSELoss(reduction='sum'), loss_type 'l2'): sum (z - e)^2, g = -2 (z - e) * scale.
-template <bool L2>
-__global__ __launch_bounds__(256) void k_l1_loss_grad(const float* __restrict__ z, const float* __restrict__ e, int B,
-                                                       int Cc, int HW, int CP, float scale, float* __restrict__ g_nhwc,
-                                                       double* __restrict__ loss_part) {
-  __shared__ double red[256];
-  double s = 0.0;
-  const size_t total = (size_t)B * HW;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t b = i / HW, p = i - b * HW;
-    for (int c = 0; c < CP; ++c) {
-      float gv = 0.f;
-      if (c < Cc) {
-        const size_t idx = (b * Cc + c) * HW + p;
-        const float d = z[idx] - e[idx];
-        if (L2) {
-          s += (double)d * (double)d;
-          gv = -2.f * d * scale;
-        } else {
-          s += (double)fabsf(d);
-          gv = d > 0.f ? -scale : (d < 0.f ? scale : 0.f);
-        }
-      }
-      g_nhwc[i * CP + c] = gv;
-    }
-  }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int k = 128; k >= 1; k >>= 1) {
-    if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss_part[blockIdx.x] = red[0];
-}
-// T11b: the generalised objective (v- / x0-prediction, Min-SNR weights, Huber).  Per image b the regression target is
-// ta[b] z + tb[b] hr and the weight w[b] (NULL tables: target z, weight 1; hr is read only with tb):
-//   d = (ta z + tb hr) - e ;  loss_part[block] = sum w rho(d) ;  g = -w rho'(d) scale
-// with rho = |d| (KIND 0, rho' = sign, 0 at 0), d^2 (1, 2d) or Huber(delta) (2: d^2 / 2 inside |d| <= delta, delta (|d| - delta / 2)
-// outside, rho' = clamp(d, -delta, delta)).  Geometry, layout of g and the reduction are k_l1_loss_grad's.
+// T11: the loss of one step and its gradient w.r.t. the network's output, written NHWC with the channel dim padded to CP -- ONE kernel
+// template, k_loss_grad<KIND, FORM> (below), over ONE lane, ONE block reduction and ONE launch (objective_loss_grad).
+// THE lane: rho(d) is added to `acc` in double and g = -ws rho'(d) returned, with rho = |d| (KIND 0: nn.L1Loss(reduction='sum'), what
+// define_G configures; rho' = sign, 0 at 0), d^2 (1: nn.MSELoss(reduction='sum'), loss_type 'l2'; 2d) or Huber(delta) (2: d^2 / 2 inside
+// |d| <= delta, delta (|d| - delta / 2) outside, rho' = clamp(d, -delta, delta)); ws = weight * scale
 template <int KIND>
-__global__ __launch_bounds__(256) void k_loss_grad(const float* __restrict__ z, const float* __restrict__ hr,
-                                                    const float* __restrict__ e, const float* __restrict__ ta,
-                                                    const float* __restrict__ tb, const float* __restrict__ w, int B, int Cc,
-                                                    int HW, int CP, float scale, float delta, float* __restrict__ g_nhwc,
-                                                    double* __restrict__ loss_part) {
-  __shared__ double red[256];
-  double s = 0.0;
-  const size_t total = (size_t)B * HW;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t b = i / HW, p = i - b * HW;
-    const float az = ta ? ta[b] : 1.f, ax = tb ? tb[b] : 0.f, wb = w ? w[b] : 1.f;
-    const float ws = wb * scale;
-    double sp = 0.0;                            // this pixel's sum of rho(d): weighted once
-    for (int c = 0; c < CP; ++c) {
-      float gv = 0.f;
-      if (c < Cc) {
-        const size_t idx = (b * Cc + c) * HW + p;
-        const float d = (az * z[idx] + (tb ? ax * hr[idx] : 0.f)) - e[idx];
-        if (KIND == 1) {
-          sp += (double)d * (double)d;
-          gv = -2.f * d * ws;
-        } else if (KIND == 2) {
-          const double a = (double)fabsf(d), dl = (double)delta;
-          sp += a <= dl ? 0.5 * a * a : dl * (a - 0.5 * dl);
-          gv = -fminf(fmaxf(d, -delta), delta) * ws;
-        } else {
-          sp += (double)fabsf(d);
-          gv = d > 0.f ? -ws : (d < 0.f ? ws : 0.f);
-        }
-      }
-      g_nhwc[i * CP + c] = gv;
-    }
-    s += (double)wb * sp;
+__device__ __forceinline__ float loss_lane(float d, float ws, float delta, double& acc) {
+  if (KIND == LOSS_L2) {
+    acc += (double)d * (double)d;
+    return -2.f * d * ws;
   }
-  red[threadIdx.x] = s;
+  if (KIND == LOSS_HUBER) {
+    const double a = (double)fabsf(d), dl = (double)delta;
+    acc += a <= dl ? 0.5 * a * a : dl * (a - 0.5 * dl);
+    return -fminf(fmaxf(d, -delta), delta) * ws;
+  }
+  acc += (double)fabsf(d);
+  return d > 0.f ? -ws : (d < 0.f ? ws : 0.f);
+}
+// THE block reduction of the loss kernels: the 256 threads' doubles summed in a fixed tree, thread 0 stores the sum.  Ends behind a
+// barrier every thread has passed, so `red` can be reused at once
+__device__ __forceinline__ void block_sum_256(double* red, double v, double* out) {
+  red[threadIdx.x] = v;
   __syncthreads();
   for (int k = 128; k >= 1; k >>= 1) {
     if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
     __syncthreads();
   }
-  if (threadIdx.x == 0) loss_part[blockIdx.x] = red[0];
+  if (threadIdx.x == 0) *out = red[0];
 }
+// The three forms of the kernel.  Behaviour is bits, so each keeps its own expression of d and its own grouping of the double sum:
+//   PLAIN      sr3_train_step's objective (target z, weight 1, L1 / L2): d = z - e, every channel's rho added straight into the thread's sum
+//   OBJECTIVE  T11b, v- / x0-prediction, Min-SNR weights, Huber: per image b the regression target is ta[b] z + tb[b] hr
+//              and the weight w[b] (NULL tables: target z, weight 1; hr is read only with tb):  d = (ta z + tb hr) - e, a pixel's channels
+//              summed first and weighted once.  With NULL tables d differs from PLAIN's in the sign of a zero (-0.f + 0.f is +0.f), which
+//              for L2 reaches g; the sum differs in its rounding (tests/test_gpu_loss_bits.py pins both)
+//   HYBRID     T11c, OBJECTIVE on the prediction rows plus lambda L_vlb on the variance rows
 // T11c: the hybrid loss of a learned reverse-process variance (Nichol & Dhariwal 2021).  e is [B, 2 Cc, HW]: channels
-// 0 .. Cc - 1 the prediction, under k_loss_grad's objective, term for term (the same d, rho, g: bit-identical lanes); channels Cc ..
+// 0 .. Cc - 1 the prediction, under the OBJECTIVE form's lanes (the same d, rho, g: one piece of code); channels Cc ..
 // 2 Cc - 1 the raw variance head v.  Per image the scalars of the drawn step (train.h: HYB_*).  Per element, all fp32:
 //   x0^ = a x_t - b out (no clamp) ; mu_theta = c1 x0^ + c2 x_t, a constant here: no L_vlb gradient reaches the prediction lanes
 //   f = (v + 1) / 2 ; lv = f log beta + (1 - f) log beta~                         log sigma_theta^2
@@ -388,63 +341,46 @@ __device__ __forceinline__ float vlb_elem(const VlbScal& k, float x0, float xt, 
   *dv = open ? -(darg / arg) * dlv * RLN2 : 0.f;
   return -logf(open ? arg : 1e-12f) * RLN2;
 }
-template <int KIND>
-__global__ __launch_bounds__(256) void k_hybrid_loss_grad(const float* __restrict__ z, const float* __restrict__ hr,
-                                                           const float* __restrict__ xt, const float* __restrict__ e,
-                                                           const float* __restrict__ ta, const float* __restrict__ tb,
-                                                           const float* __restrict__ w, const float* __restrict__ hyb, int B, int Cc,
-                                                           int HW, int CP, float scale, float delta, float lambda,
-                                                           float* __restrict__ g_nhwc, double* __restrict__ loss_part,
-                                                           const float* __restrict__ vw) {
+enum { LOSS_PLAIN = 0, LOSS_OBJECTIVE, LOSS_HYBRID };
+template <int KIND, int FORM>
+__global__ __launch_bounds__(256) void k_loss_grad(const LossTensors t, const Objective o, int B, int Cc, int HW, int CP, float scale) {
   __shared__ double red[256];
   double s = 0.0, sv = 0.0;
+  const int Ce = FORM == LOSS_HYBRID ? 2 * Cc : Cc;      // channels of e
   const size_t total = (size_t)B * HW;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const size_t b = i / HW, p = i - b * HW;
-    const float az = ta ? ta[b] : 1.f, ax = tb ? tb[b] : 0.f, wb = w ? w[b] : 1.f;
-    const float lam = vw ? lambda * vw[b] : lambda;      // (vw: a per-image weight of L_vlb; null: lambda as it is -- the same operations)
-    const float ws = wb * scale, ls = lam * scale;
-    const float* hs = hyb + b * HYB_STRIDE;
-    const VlbScal k = {hs[HYB_A], hs[HYB_B], hs[HYB_C1], hs[HYB_C2], hs[HYB_LOG_BETA], hs[HYB_LOG_BETA_TILDE], hs[HYB_LAST] != 0.f};
-    double sp = 0.0, vp = 0.0;
+    float az = 1.f, ax = 0.f, wb = 1.f, lam = 0.f;
+    VlbScal k = {};
+    if (FORM != LOSS_PLAIN) {
+      az = o.tgt_z ? o.tgt_z[b] : 1.f; ax = o.tgt_x0 ? o.tgt_x0[b] : 0.f; wb = o.weight ? o.weight[b] : 1.f;
+    }
+    if (FORM == LOSS_HYBRID) {
+      lam = o.vlb_w ? o.lambda * o.vlb_w[b] : o.lambda;      // (vw: a per-image weight of L_vlb; null: lambda as it is -- the same operations)
+      const float* hs = o.hyb + b * HYB_STRIDE;
+      k = {hs[HYB_A], hs[HYB_B], hs[HYB_C1], hs[HYB_C2], hs[HYB_LOG_BETA], hs[HYB_LOG_BETA_TILDE], hs[HYB_LAST] != 0.f};
+    }
+    const float ws = FORM == LOSS_PLAIN ? scale : wb * scale, ls = lam * scale;
+    double sp = 0.0, vp = 0.0;                  // this pixel's sums of rho(d) and of vlb: weighted once
     for (int c = 0; c < CP; ++c) {
       float gv = 0.f;
-      if (c < Cc) {                             // (k_loss_grad's lane, term for term)
-        const size_t idx = (b * 2 * Cc + c) * HW + p, ix = (b * Cc + c) * HW + p;
-        const float d = (az * z[ix] + (tb ? ax * hr[ix] : 0.f)) - e[idx];
-        if (KIND == 1) {
-          sp += (double)d * (double)d;
-          gv = -2.f * d * ws;
-        } else if (KIND == 2) {
-          const double a = (double)fabsf(d), dl = (double)delta;
-          sp += a <= dl ? 0.5 * a * a : dl * (a - 0.5 * dl);
-          gv = -fminf(fmaxf(d, -delta), delta) * ws;
-        } else {
-          sp += (double)fabsf(d);
-          gv = d > 0.f ? -ws : (d < 0.f ? ws : 0.f);
-        }
-      } else if (c < 2 * Cc) {
-        const int ci = c - Cc;
-        const size_t ix = (b * Cc + ci) * HW + p;
+      if (c < Cc) {
+        const size_t ie = (b * Ce + c) * HW + p, ix = (b * Cc + c) * HW + p;
+        if (FORM == LOSS_PLAIN) gv = loss_lane<KIND>(t.z[ix] - t.e[ie], ws, o.huber_delta, s);
+        else gv = loss_lane<KIND>((az * t.z[ix] + (o.tgt_x0 ? ax * t.hr[ix] : 0.f)) - t.e[ie], ws, o.huber_delta, sp);
+      } else if (FORM == LOSS_HYBRID && c < 2 * Cc) {
+        const size_t ix = (b * Cc + (c - Cc)) * HW + p;
         float dv;
-        vp += (double)vlb_elem(k, hr[ix], xt[ix], e[(b * 2 * Cc + ci) * HW + p], e[(b * 2 * Cc + c) * HW + p], &dv);
+        vp += (double)vlb_elem(k, t.hr[ix], t.xt[ix], t.e[(b * Ce + (c - Cc)) * HW + p], t.e[(b * Ce + c) * HW + p], &dv);
         gv = ls * dv;
       }
-      g_nhwc[i * CP + c] = gv;
+      t.g_nhwc[i * CP + c] = gv;
     }
-    s += (double)wb * sp + (double)lam * vp;
-    sv += vp;
+    if (FORM == LOSS_OBJECTIVE) s += (double)wb * sp;
+    if (FORM == LOSS_HYBRID) { s += (double)wb * sp + (double)lam * vp; sv += vp; }
   }
-  for (int pass = 0; pass < 2; ++pass) {
-    __syncthreads();
-    red[threadIdx.x] = pass ? sv : s;
-    __syncthreads();
-    for (int m = 128; m >= 1; m >>= 1) {
-      if ((int)threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) loss_part[pass * gridDim.x + blockIdx.x] = red[0];
-  }
+  block_sum_256(red, s, t.loss_part + blockIdx.x);
+  if (FORM == LOSS_HYBRID) block_sum_256(red, sv, t.loss_part + gridDim.x + blockIdx.x);
 }
 __global__ __launch_bounds__(64) void k_sum_parts(const double* __restrict__ part, int n, float* __restrict__ out) {
   double s = 0.0;
@@ -587,16 +523,6 @@ int colsums(const float* g, int B, int HW, int C, double* part, float* dbias, fl
   }
   return SR3_OK;
 }
-int l1_loss_grad(const float* z, const float* e, int B, int Cc, int HW, int CP, float scale, bool l2, float* g_nhwc,
-                 double* loss_part, float* loss_out, hipStream_t st) {
-  const int blocks = 256;
-  if (l2) hipLaunchKernelGGL(k_l1_loss_grad<true>, dim3(blocks), dim3(256), 0, st, z, e, B, Cc, HW, CP, scale, g_nhwc, loss_part);
-  else hipLaunchKernelGGL(k_l1_loss_grad<false>, dim3(blocks), dim3(256), 0, st, z, e, B, Cc, HW, CP, scale, g_nhwc, loss_part);
-  SR3_LAUNCH_CHECK("k_l1_loss_grad");
-  hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(64), 0, st, loss_part, blocks, loss_out);
-  SR3_LAUNCH_CHECK("k_sum_parts");
-  return SR3_OK;
-}
 // The refusals of the objective arguments of sr3_train_step_ex / sr3_loss_grad_f32 under the entry's own name (min_kind: -1 where a
 // plan's loss_l2 can stand in).  Nothing has been launched when this returns non-zero.
 int check_objective_args(const char* who, const float* tgt_z, const float* tgt_x0, const float* weight, int loss_kind, int min_kind,
@@ -610,31 +536,24 @@ int check_objective_args(const char* who, const float* tgt_z, const float* tgt_x
   }
   return SR3_OK;
 }
-// THE place that picks the loss kernel: target z, weight 1 and L1 / L2 is l1_loss_grad's launch as it always was; everything else
-// the generalised kernel on the same grid and the same two-stage sum
-int objective_loss_grad(const float* z, const float* hr, const float* e, const Objective& o, int B, int Cc, int HW, int CP, float scale,
-                        float* g_nhwc, double* loss_part, float* loss_out, hipStream_t st) {
-  if (!o.tgt_z && o.kind != LOSS_HUBER) return l1_loss_grad(z, e, B, Cc, HW, CP, scale, o.kind == LOSS_L2, g_nhwc, loss_part, loss_out, st);
+// THE launch of the loss kernels, and THE place that picks the form.  A variance head (o.hyb): the hybrid form.  Otherwise plain against
+// general: target z, weight 1 and L1 / L2 is the plain form as it always was; everything else the objective's form on the same grid.
+// Then k_sum_parts over each run of block partials that has a destination (loss_out; the hybrid form's vlb_out, which may be null)
+int objective_loss_grad(const LossTensors& t, const Objective& o, int B, int Cc, int HW, int CP, float scale, hipStream_t st) {
+  using Kernel = void (*)(const LossTensors, const Objective, int, int, int, int, float);
+  static constexpr Kernel kernels[3][3] = {
+      {k_loss_grad<LOSS_L1, LOSS_PLAIN>, k_loss_grad<LOSS_L2, LOSS_PLAIN>, nullptr},      // (Huber has no plain form)
+      {k_loss_grad<LOSS_L1, LOSS_OBJECTIVE>, k_loss_grad<LOSS_L2, LOSS_OBJECTIVE>, k_loss_grad<LOSS_HUBER, LOSS_OBJECTIVE>},
+      {k_loss_grad<LOSS_L1, LOSS_HYBRID>, k_loss_grad<LOSS_L2, LOSS_HYBRID>, k_loss_grad<LOSS_HUBER, LOSS_HYBRID>}};
+  static const char* const names[3] = {"k_l1_loss_grad", "k_loss_grad", "k_hybrid_loss_grad"};      // (a launch failure names the form as it always did)
+  const int form = o.hyb ? LOSS_HYBRID : (!o.tgt_z && o.kind != LOSS_HUBER ? LOSS_PLAIN : LOSS_OBJECTIVE);
   const int blocks = LOSS_GRAD_BLOCKS;
-  static constexpr decltype(&k_loss_grad<0>) kernels[3] = {k_loss_grad<0>, k_loss_grad<1>, k_loss_grad<2>};
-  hipLaunchKernelGGL(kernels[o.kind], dim3(blocks), dim3(256), 0, st, z, hr, e, o.tgt_z, o.tgt_x0, o.weight, B, Cc, HW, CP, scale,
-                     o.huber_delta, g_nhwc, loss_part);
-  SR3_LAUNCH_CHECK("k_loss_grad");
-  hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(64), 0, st, loss_part, blocks, loss_out);
-  SR3_LAUNCH_CHECK("k_sum_parts");
-  return SR3_OK;
-}
-int hybrid_loss_grad(const float* z, const float* hr, const float* xt, const float* e, const Objective& o, int B, int Cc, int HW, int CP,
-                     float scale, float* g_nhwc, double* loss_part, float* loss_out, float* vlb_out, hipStream_t st) {
-  const int blocks = LOSS_GRAD_BLOCKS;
-  static constexpr decltype(&k_hybrid_loss_grad<0>) kernels[3] = {k_hybrid_loss_grad<0>, k_hybrid_loss_grad<1>, k_hybrid_loss_grad<2>};
-  hipLaunchKernelGGL(kernels[o.kind], dim3(blocks), dim3(256), 0, st, z, hr, xt, e, o.tgt_z, o.tgt_x0, o.weight, o.hyb, B, Cc, HW, CP,
-                     scale, o.huber_delta, o.lambda, g_nhwc, loss_part, o.vlb_w);
-  SR3_LAUNCH_CHECK("k_hybrid_loss_grad");
-  hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(64), 0, st, loss_part, blocks, loss_out);
-  SR3_LAUNCH_CHECK("k_sum_parts");
-  if (vlb_out) {
-    hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(64), 0, st, loss_part + blocks, blocks, vlb_out);
+  hipLaunchKernelGGL(kernels[form][o.kind], dim3(blocks), dim3(256), 0, st, t, o, B, Cc, HW, CP, scale);
+  SR3_LAUNCH_CHECK(names[form]);
+  float* const sums[2] = {t.loss_out, o.hyb ? t.vlb_out : nullptr};
+  for (int k = 0; k < 2; ++k) {
+    if (!sums[k]) continue;
+    hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(64), 0, st, t.loss_part + k * blocks, blocks, sums[k]);
     SR3_LAUNCH_CHECK("k_sum_parts");
   }
   return SR3_OK;
@@ -721,22 +640,36 @@ extern "C" int sr3_colsums_f32(const float* g, int B, int HW, int C, float* dbia
   return colsums(g, B, HW, C, static_cast<double*>(scratch), dbias, dfilm, film_stride, static_cast<hipStream_t>(stream));
 }
 
+// ---- the loss ops.  Their argument checks are the same but for the names of the required pointers, in one order: required pointers,
+// the objective, hr with tgt_x0 (the hybrid op requires hr outright), the shape, vlb_lambda (the hybrid op's; null: none), the scratch ----
+namespace {
+struct LossOpShape { int batch, channels, pixels; };
+int check_loss_op(const char* who, bool missing, const char* required, const sr3::Objective& o, const float* hr_nchw, const LossOpShape& s,
+                  const float* vlb_lambda, const void* scratch) {
+  using namespace sr3;
+  if (missing) { set_error("%s: %s is NULL", who, required); return SR3_E_BADARG; }
+  if (const int rc = check_objective_args(who, o.tgt_z, o.tgt_x0, o.weight, o.kind, 0, o.huber_delta)) return rc;
+  if (o.tgt_x0 && !hr_nchw) { set_error("%s: hr_nchw is NULL with tgt_x0 given", who); return SR3_E_BADARG; }
+  if (s.batch <= 0 || s.pixels <= 0) { set_error("%s: batch %d and pixels %d must be positive", who, s.batch, s.pixels); return SR3_E_BADARG; }
+  if (s.channels < 1 || s.channels > 4) { set_error("%s: channels %d is outside 1..4", who, s.channels); return SR3_E_BADARG; }
+  if (vlb_lambda && !(isfinite(*vlb_lambda) && *vlb_lambda >= 0.f)) { set_error("%s: vlb_lambda %g must be finite and >= 0", who, (double)*vlb_lambda); return SR3_E_BADARG; }
+  if ((uintptr_t)scratch & 7) { set_error("%s: scratch is not 8-byte aligned", who); return SR3_E_ALIGN; }
+  return SR3_OK;
+}
+}  // namespace
+
 extern "C" size_t sr3_loss_grad_scratch_bytes(void) { return sr3::LOSS_GRAD_BLOCKS * sizeof(double); }
 extern "C" int sr3_loss_grad_f32(const float* z_nchw, const float* out_nchw, const float* hr_nchw, const float* tgt_z, const float* tgt_x0,
                                  const float* weight, int batch, int channels, int pixels, int loss_kind, float huber_delta, float scale,
                                  float* g_nhwc4, float* loss_sum_out, void* scratch, void* stream) {
   using namespace sr3;
-  const char* who = "sr3_loss_grad_f32";
-  if (!z_nchw || !out_nchw || !g_nhwc4 || !loss_sum_out || !scratch) { set_error("%s: z_nchw / out_nchw / g_nhwc4 / loss_sum_out / scratch is NULL", who); return SR3_E_BADARG; }
-  if (const int rc = check_objective_args(who, tgt_z, tgt_x0, weight, loss_kind, 0, huber_delta)) return rc;
-  if (tgt_x0 && !hr_nchw) { set_error("%s: hr_nchw is NULL with tgt_x0 given", who); return SR3_E_BADARG; }
-  if (batch <= 0 || pixels <= 0) { set_error("%s: batch %d and pixels %d must be positive", who, batch, pixels); return SR3_E_BADARG; }
-  if (channels < 1 || channels > 4) { set_error("%s: channels %d is outside 1..4", who, channels); return SR3_E_BADARG; }
-  if ((uintptr_t)scratch & 7) { set_error("%s: scratch is not 8-byte aligned", who); return SR3_E_ALIGN; }
   Objective o;
   o.tgt_z = tgt_z; o.tgt_x0 = tgt_x0; o.weight = weight; o.kind = loss_kind; o.huber_delta = huber_delta;
-  return objective_loss_grad(z_nchw, hr_nchw, out_nchw, o, batch, channels, pixels, 4, scale, g_nhwc4, static_cast<double*>(scratch),
-                             loss_sum_out, static_cast<hipStream_t>(stream));
+  if (const int rc = check_loss_op("sr3_loss_grad_f32", !z_nchw || !out_nchw || !g_nhwc4 || !loss_sum_out || !scratch,
+                                   "z_nchw / out_nchw / g_nhwc4 / loss_sum_out / scratch", o, hr_nchw, {batch, channels, pixels}, nullptr, scratch))
+    return rc;
+  return objective_loss_grad({z_nchw, hr_nchw, nullptr, out_nchw, g_nhwc4, static_cast<double*>(scratch), loss_sum_out, nullptr}, o, batch,
+                             channels, pixels, 4, scale, static_cast<hipStream_t>(stream));
 }
 
 extern "C" size_t sr3_hybrid_loss_grad_scratch_bytes(void) { return 2 * sr3::LOSS_GRAD_BLOCKS * sizeof(double); }
@@ -745,19 +678,14 @@ extern "C" int sr3_hybrid_loss_grad_f32(const float* z_nchw, const float* out_nc
                                         float vlb_lambda, int batch, int channels, int pixels, int loss_kind, float huber_delta, float scale,
                                         float* g_nhwc8, float* loss_sum_out, float* vlb_sum_out, void* scratch, void* stream) {
   using namespace sr3;
-  const char* who = "sr3_hybrid_loss_grad_f32";
-  if (!z_nchw || !out_nchw || !hr_nchw || !xt_nchw || !step_scalars || !g_nhwc8 || !loss_sum_out || !scratch) {
-    set_error("%s: z_nchw / out_nchw / hr_nchw / xt_nchw / step_scalars / g_nhwc8 / loss_sum_out / scratch is NULL", who);
-    return SR3_E_BADARG;
-  }
-  if (const int rc = check_objective_args(who, tgt_z, tgt_x0, weight, loss_kind, 0, huber_delta)) return rc;
-  if (batch <= 0 || pixels <= 0) { set_error("%s: batch %d and pixels %d must be positive", who, batch, pixels); return SR3_E_BADARG; }
-  if (channels < 1 || channels > 4) { set_error("%s: channels %d is outside 1..4", who, channels); return SR3_E_BADARG; }
-  if (!(isfinite(vlb_lambda) && vlb_lambda >= 0.f)) { set_error("%s: vlb_lambda %g must be finite and >= 0", who, (double)vlb_lambda); return SR3_E_BADARG; }
-  if ((uintptr_t)scratch & 7) { set_error("%s: scratch is not 8-byte aligned", who); return SR3_E_ALIGN; }
   Objective o;
   o.tgt_z = tgt_z; o.tgt_x0 = tgt_x0; o.weight = weight; o.kind = loss_kind; o.huber_delta = huber_delta;
   o.hyb = step_scalars; o.lambda = vlb_lambda;
-  return hybrid_loss_grad(z_nchw, hr_nchw, xt_nchw, out_nchw, o, batch, channels, pixels, 8, scale, g_nhwc8, static_cast<double*>(scratch),
-                          loss_sum_out, vlb_sum_out, static_cast<hipStream_t>(stream));
+  if (const int rc = check_loss_op("sr3_hybrid_loss_grad_f32",
+                                   !z_nchw || !out_nchw || !hr_nchw || !xt_nchw || !step_scalars || !g_nhwc8 || !loss_sum_out || !scratch,
+                                   "z_nchw / out_nchw / hr_nchw / xt_nchw / step_scalars / g_nhwc8 / loss_sum_out / scratch", o, hr_nchw,
+                                   {batch, channels, pixels}, &vlb_lambda, scratch))
+    return rc;
+  return objective_loss_grad({z_nchw, hr_nchw, xt_nchw, out_nchw, g_nhwc8, static_cast<double*>(scratch), loss_sum_out, vlb_sum_out}, o, batch,
+                             channels, pixels, 8, scale, static_cast<hipStream_t>(stream));
 }

@@ -33,7 +33,7 @@ namespace {
 // (nchw_to_nhwc_pad): 8 up to 8 input channels -- every model without self-conditioning keeps its workspace bytes -- 16 above
 // (the plan accepts in_channel <= 16)
 inline int in_pad(int in_channel) { return in_channel <= 8 ? 8 : 16; }
-// the output conv's gradients read dOut with its channels padded to a multiple of 4 (l1_loss_grad): 4 up to 4 output rows -- every
+// the output conv's gradients read dOut with its channels padded to a multiple of 4 (k_loss_grad): 4 up to 4 output rows -- every
 // model without a variance head keeps its launches and its workspace bytes -- 8 above (6 or 8 rows: a prediction and its variance head)
 inline int out_pad(const sr3_plan* P) { return P->out_ch <= 4 ? 4 : 8; }
 
@@ -325,42 +325,42 @@ int wgrad_call(const TrainCtx& X, ConvParams c, const float* src0, const float* 
 }
 }  // namespace
 
-int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels, const float* z, const float* q_ca,
-              const float* q_cb, const float* level, const int64_t* tstep, const float* freq, const float* params,
-              float* grads, char* ws, float* loss_out, float grad_scale, int B, hipStream_t st, float dropout_p,
-              unsigned seed, int n_marks, const size_t* marks, void* const* mark_events, const Objective& obj, float* vlb_out,
-              const PerImage& pi = PerImage()) {
+// one step as train_step_checked settled it: nothing is refused from here on
+int run_train(sr3_plan* P, const TrainStep& t) {
   const sr3_unet_desc& d = P->d;
+  const float* params = t.params; float* grads = t.grads; char* ws = static_cast<char*>(t.workspace);
+  const int B = t.batch;
+  hipStream_t st = t.stream;
   // image geometry of this step: build_train built the plan for it (the native one unless plan option train_geom)
   const int IH = P->train_h, IW = P->train_w, S2 = IH * IW, G = d.norm_groups;
-  const int xc = d.in_channel - cond_channels;
+  const int xc = d.in_channel - t.cond_channels;
   TrainCtx X{P, ws, params, grads, B, st};
   int rc;
   // ---- q_sample + forward ----
   float* x_noisy = X.at<float>(P->t_xnoisy_off);
   float* eps = X.at<float>(P->t_eps_off);
-  rc = q_sample(hr, z, q_ca, q_cb, B, xc * S2, x_noisy, st);
+  rc = q_sample(t.hr, t.z, t.q_ca, t.q_cb, B, xc * S2, x_noisy, st);
   if (rc) return rc;
   DropCfg dc;
-  dc.seed = seed;
-  dropout_consts(dropout_p, &dc.thresh, &dc.scale);
-  rc = run_forward(P, true, x_noisy, cond, cond_channels, level, tstep, freq, nullptr, nullptr, params, ws, eps, B, st, nullptr,
+  dc.seed = t.dropout_seed;
+  dropout_consts(t.dropout_p, &dc.thresh, &dc.scale);
+  rc = run_forward(P, true, x_noisy, t.cond, t.cond_channels, t.level, t.tstep, t.freq, nullptr, nullptr, params, ws, eps, B, st, nullptr,
                    nullptr, &dc);
   if (rc) return rc;
   // ---- loss and its gradient (NHWC, channel dim padded to 4) ----
   float* geps = X.at<float>(P->t_geps_off);
   double* lparts = X.at<double>(P->t_dwtmp_off);
-  // (target z, weight 1 and L1 / L2 -- sr3_train_step's objective -- is l1_loss_grad's launch: objective_loss_grad)
+  // (target z, weight 1 and L1 / L2 -- sr3_train_step's objective -- is the plain form of the loss kernel: objective_loss_grad)
+  // (obj.hyb, a variance head: L_simple on the prediction rows + lambda L_vlb on the variance rows, the same kernel; without one
+  // the image's channels are all of out_ch)
   const int OUT_PAD = out_pad(P);
-  if (obj.hyb)      // a variance head: L_simple on the prediction rows + lambda L_vlb on the variance rows, one kernel (train_kernels.hip)
-    rc = hybrid_loss_grad(z, hr, x_noisy, eps, obj, B, plan_image_channels(P), S2, OUT_PAD, grad_scale, geps, lparts, loss_out, vlb_out, st);
-  else
-    rc = objective_loss_grad(z, hr, eps, obj, B, P->out_ch, S2, OUT_PAD, grad_scale, geps, lparts, loss_out, st);
+  rc = objective_loss_grad({t.z, t.hr, x_noisy, eps, geps, lparts, t.loss_sum_out, t.vlb_sum_out}, t.obj, B, plan_image_channels(P), S2, OUT_PAD,
+                           t.grad_scale, st);
   if (rc) return rc;
-  if (pi.out) {     // sr3_train_step_ex3: the per-image terms of the bound on the step's own x_noisy and output, while both are live
+  if (t.pi.out) {     // sr3_train_step_ex3: the per-image terms of the bound on the step's own x_noisy and output, while both are live
     const int Cc = plan_image_channels(P);
-    rc = vlb_terms(hr, x_noisy, eps, pi.scal, B, nullptr, nullptr, obj.hyb ? 0 : 1, false, B, Cc, obj.hyb ? 2 * Cc : Cc, S2, pi.out, pi.out + 1, 2,
-                   pi.part, st);
+    rc = vlb_terms(t.hr, x_noisy, eps, t.pi.scal, B, nullptr, nullptr, t.obj.hyb ? 0 : 1, false, B, Cc, t.obj.hyb ? 2 * Cc : Cc, S2, t.pi.out, t.pi.out + 1, 2,
+                   t.pi.part, st);
     if (rc) return rc;
   }
   // ---- the backward walk: the records in reverse, each as build_train resolved it.  The activation-gradient mirror is not zeroed
@@ -377,8 +377,8 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
   int next_mark = 0;
   for (int ri = (int)P->recs.size() - 1; ri >= 0; --ri) {
     // gradient-ready marks: every parameter at arena offset >= marks[k] has its gradient enqueued
-    while (next_mark < n_marks && P->t_unproc_max[ri + 1] <= marks[next_mark]) {
-      SR3_HIP(hipEventRecord(static_cast<hipEvent_t>(mark_events[next_mark]), st));
+    while (next_mark < t.n_marks && P->t_unproc_max[ri + 1] <= t.mark_offsets[next_mark]) {
+      SR3_HIP(hipEventRecord(static_cast<hipEvent_t>(t.mark_events[next_mark]), st));
       ++next_mark;
     }
     const Rec& r = P->recs[ri];
@@ -407,10 +407,10 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
     } else if (r.kind == R_CONV_IN) {
       const int Cout = r.dw.Cout;
       float* inpad = X.at<float>(P->t_inpad_off);
-      const float* a = cond_channels > 0 ? cond : x_noisy;
-      const int Ca = cond_channels > 0 ? cond_channels : xc;
-      const float* b2 = cond_channels > 0 ? x_noisy : nullptr;
-      const int Cb = cond_channels > 0 ? xc : 0;
+      const float* a = t.cond_channels > 0 ? t.cond : x_noisy;
+      const int Ca = t.cond_channels > 0 ? t.cond_channels : xc;
+      const float* b2 = t.cond_channels > 0 ? x_noisy : nullptr;
+      const int Cb = t.cond_channels > 0 ? xc : 0;
       const int CP = in_pad(d.in_channel);
       rc = nchw_to_nhwc_pad(a, Ca, b2, Cb, B, S2, CP, inpad, st);
       if (rc) return rc;
@@ -472,14 +472,14 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
       if (rc) return rc;
     }
   }
-  while (next_mark < n_marks && P->t_unproc_max[0] <= marks[next_mark]) {
-    SR3_HIP(hipEventRecord(static_cast<hipEvent_t>(mark_events[next_mark]), st));
+  while (next_mark < t.n_marks && P->t_unproc_max[0] <= t.mark_offsets[next_mark]) {
+    SR3_HIP(hipEventRecord(static_cast<hipEvent_t>(t.mark_events[next_mark]), st));
     ++next_mark;
   }
   // ---- embedding MLP and FiLM projections ----
   EmbedBwdParams e;
   memset(&e, 0, sizeof(e));
-  e.variant = d.variant; e.B = B; e.inner = d.inner_channel; e.F = P->F; e.level = level; e.tstep = tstep; e.freq = freq;
+  e.variant = d.variant; e.B = B; e.inner = d.inner_channel; e.F = P->F; e.level = t.level; e.tstep = t.tstep; e.freq = t.freq;
   e.w1 = params + P->emb_w1; e.b1 = params + P->emb_b1; e.w2 = params + P->emb_w2; e.b2 = params + P->emb_b2;
   e.wf = params + P->film_w; e.dfilm = dfilm;
   e.dw1 = grads + P->emb_w1; e.db1 = grads + P->emb_b1; e.dw2 = grads + P->emb_w2; e.db2 = grads + P->emb_b2;
@@ -487,8 +487,8 @@ int run_train(sr3_plan* P, const float* hr, const float* cond, int cond_channels
   e.scratch = X.at<float>(P->t_embscr_off);
   rc = embed_backward(e, st);
   if (rc) return rc;
-  while (next_mark < n_marks) {       // whatever is left becomes ready with the head block
-    SR3_HIP(hipEventRecord(static_cast<hipEvent_t>(mark_events[next_mark]), st));
+  while (next_mark < t.n_marks) {       // whatever is left becomes ready with the head block
+    SR3_HIP(hipEventRecord(static_cast<hipEvent_t>(t.mark_events[next_mark]), st));
     ++next_mark;
   }
   return SR3_OK;
@@ -585,56 +585,65 @@ size_t sr3_train_workspace_bytes(sr3_plan* plan, int batch, int cond_channels) {
   return plan->t_ws_bytes;
 }
 
-// the body of sr3_train_step_ex (step_scalars null) and sr3_train_step_ex2: `who` names the entry in the objective's refusals
-static int train_step_body(const char* who, sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels, const float* z_nchw,
-                           const float* q_ca, const float* q_cb, const float* noise_level, const int64_t* timestep,
-                           const float* freq, const float* params, float* grads, void* workspace, size_t workspace_bytes,
-                           float* loss_sum_out, float grad_scale, float dropout_p, unsigned dropout_seed, int n_marks,
-                           const size_t* mark_offsets, void* const* mark_events, int batch, const float* tgt_z, const float* tgt_x0,
-                           const float* weight, int loss_kind, float huber_delta, const float* step_scalars, float vlb_lambda,
-                           float* vlb_sum_out, void* stream, bool ex3 = false, float* per_image_out = nullptr, void* pi_scratch = nullptr,
-                           size_t pi_scratch_bytes = 0, const float* vlb_weight = nullptr) {
-  if (!plan || !hr_nchw || !z_nchw || !q_ca || !q_cb || !freq || !params || !grads || !workspace || !loss_sum_out) {
+// what an entry asks of the request it filled: sr3_train_step_ex ignores the hybrid and per-image fields (it leaves them unset),
+// _ex2 needs step_scalars, _ex3 needs them too and takes the per-image terms -- on a plan without a variance head for those alone
+enum TrainForm { TRAIN_EX, TRAIN_EX2, TRAIN_EX3 };
+
+// THE checks of a training step, in the order the refusals are pinned in (tests/test_train_refusals_cpu.py); nothing has been launched
+// when this returns non-zero without reaching run_train.  `who` names the entry in its refusals
+static int train_step_checked(const char* who, sr3_plan* plan, TrainStep t, TrainForm form) {
+  if (form != TRAIN_EX && !t.obj.hyb) { set_error("%s: step_scalars is NULL", who); return SR3_E_BADARG; }
+  if (!plan || !t.hr || !t.z || !t.q_ca || !t.q_cb || !t.freq || !t.params || !t.grads || !t.workspace || !t.loss_sum_out) {
     set_error("null argument");
     return SR3_E_BADARG;
   }
-  if (const int rc = check_objective_args(who, tgt_z, tgt_x0, weight, loss_kind, -1, huber_delta)) return rc;
-  if (!cond_nchw) cond_channels = 0;
-  const int rc = build_train(plan, batch, cond_channels);
+  Objective& obj = t.obj;
+  if (const int rc = check_objective_args(who, obj.tgt_z, obj.tgt_x0, obj.weight, obj.kind, -1, obj.huber_delta)) return rc;
+  if (!t.cond) t.cond_channels = 0;
+  const int rc = build_train(plan, t.batch, t.cond_channels);
   if (rc) return rc;
-  if (workspace_bytes < plan->t_ws_bytes) { set_error("train workspace too small: %zu < %zu", workspace_bytes, plan->t_ws_bytes); return SR3_E_NOMEM; }
-  if (((uintptr_t)workspace & 255) || ((uintptr_t)params & 15) || ((uintptr_t)grads & 15)) { set_error("misaligned pointer"); return SR3_E_ALIGN; }
-  if (plan->d.variant == SR3_VARIANT_SR3 && !noise_level) { set_error("SR3 variant needs noise_level"); return SR3_E_BADARG; }
-  if (plan->d.variant == SR3_VARIANT_DDPM && !timestep) { set_error("DDPM variant needs timestep"); return SR3_E_BADARG; }
-  if (dropout_p < 0.f || dropout_p >= 1.f) { set_error("dropout_p out of range"); return SR3_E_BADARG; }
-  PerImage pi;
-  if (ex3 && per_image_out) {
-    if (!pi_scratch) { set_error("%s: scratch is NULL with per_image_out given", who); return SR3_E_BADARG; }
-    const size_t need = vlb_terms_scratch(batch);
-    if (pi_scratch_bytes < need) { set_error("%s: scratch too small (%zu < %zu)", who, pi_scratch_bytes, need); return SR3_E_NOMEM; }
-    if (overlaps(per_image_out, (size_t)batch * 2 * sizeof(float), pi_scratch, need)) { set_error("%s: per_image_out overlaps scratch", who); return SR3_E_BADARG; }
-    if (overlaps(workspace, plan->t_ws_bytes, per_image_out, (size_t)batch * 2 * sizeof(float)) || overlaps(workspace, plan->t_ws_bytes, pi_scratch, need)) {
+  if (t.workspace_bytes < plan->t_ws_bytes) { set_error("train workspace too small: %zu < %zu", t.workspace_bytes, plan->t_ws_bytes); return SR3_E_NOMEM; }
+  if (((uintptr_t)t.workspace & 255) || ((uintptr_t)t.params & 15) || ((uintptr_t)t.grads & 15)) { set_error("misaligned pointer"); return SR3_E_ALIGN; }
+  if (plan->d.variant == SR3_VARIANT_SR3 && !t.level) { set_error("SR3 variant needs noise_level"); return SR3_E_BADARG; }
+  if (plan->d.variant == SR3_VARIANT_DDPM && !t.tstep) { set_error("DDPM variant needs timestep"); return SR3_E_BADARG; }
+  if (t.dropout_p < 0.f || t.dropout_p >= 1.f) { set_error("dropout_p out of range"); return SR3_E_BADARG; }
+  if (form == TRAIN_EX3 && t.pi.out) {
+    const size_t out_bytes = (size_t)t.batch * 2 * sizeof(float), need = vlb_terms_scratch(t.batch);
+    if (!t.pi.part) { set_error("%s: scratch is NULL with per_image_out given", who); return SR3_E_BADARG; }
+    if (t.pi_scratch_bytes < need) { set_error("%s: scratch too small (%zu < %zu)", who, t.pi_scratch_bytes, need); return SR3_E_NOMEM; }
+    if (overlaps(t.pi.out, out_bytes, t.pi.part, need)) { set_error("%s: per_image_out overlaps scratch", who); return SR3_E_BADARG; }
+    if (overlaps(t.workspace, plan->t_ws_bytes, t.pi.out, out_bytes) || overlaps(t.workspace, plan->t_ws_bytes, t.pi.part, need)) {
       set_error("%s: per_image_out / scratch overlaps the workspace", who);
       return SR3_E_BADARG;
     }
-    if ((uintptr_t)pi_scratch & 7) { set_error("%s: scratch is not 8-byte aligned", who); return SR3_E_ALIGN; }
-    pi.out = per_image_out; pi.part = static_cast<double*>(pi_scratch); pi.scal = step_scalars;
+    if ((uintptr_t)t.pi.part & 7) { set_error("%s: scratch is not 8-byte aligned", who); return SR3_E_ALIGN; }
+    t.pi.scal = obj.hyb;
+  } else {
+    t.pi = PerImage();
   }
-  if (ex3 && plan->var_channels == 0) step_scalars = nullptr;      // no variance head: sr3_train_step_ex's objective; the rows serve the terms alone
-  if ((plan->var_channels > 0) != (step_scalars != nullptr)) {
+  if (form == TRAIN_EX3 && plan->var_channels == 0) obj.hyb = nullptr;      // no variance head: sr3_train_step_ex's objective; the rows serve the terms alone
+  if ((plan->var_channels > 0) != (obj.hyb != nullptr)) {
     set_error("%s: the plan's variance rows (var_channels %d) and step_scalars go together (sr3_train_step_ex2 trains them)", who, plan->var_channels);
     return SR3_E_BADARG;
   }
-  if (step_scalars && !(isfinite(vlb_lambda) && vlb_lambda >= 0.f)) { set_error("%s: vlb_lambda %g must be finite and >= 0", who, (double)vlb_lambda); return SR3_E_BADARG; }
-  Objective obj;
-  obj.hyb = step_scalars; obj.lambda = vlb_lambda;
-  obj.vlb_w = step_scalars ? vlb_weight : nullptr;      // (a plan without a variance head has no L_vlb to weight)
-  obj.tgt_z = tgt_z; obj.tgt_x0 = tgt_x0; obj.weight = weight; obj.huber_delta = huber_delta;
-  obj.kind = loss_kind < 0 ? (plan->loss_l2 != 0 ? LOSS_L2 : LOSS_L1) : loss_kind;      // -1: the plan's loss_l2
-  return run_train(plan, hr_nchw, cond_nchw, cond_channels, z_nchw, q_ca, q_cb, noise_level, timestep, freq, params, grads,
-                   static_cast<char*>(workspace), loss_sum_out, grad_scale, batch, static_cast<hipStream_t>(stream), dropout_p,
-                   dropout_seed, (mark_offsets && mark_events) ? n_marks : 0, mark_offsets, mark_events, obj, vlb_sum_out, pi);
+  if (obj.hyb && !(isfinite(obj.lambda) && obj.lambda >= 0.f)) { set_error("%s: vlb_lambda %g must be finite and >= 0", who, (double)obj.lambda); return SR3_E_BADARG; }
+  if (!obj.hyb) obj.vlb_w = nullptr;      // (a plan without a variance head has no L_vlb to weight)
+  if (obj.kind < 0) obj.kind = plan->loss_l2 != 0 ? LOSS_L2 : LOSS_L1;      // -1: the plan's loss_l2
+  if (!t.mark_offsets || !t.mark_events) t.n_marks = 0;
+  return run_train(plan, t);
 }
+
+// the arguments all four sr3_train_step* entries have (_COMMON) and the objective's, which the three _ex entries have (_OBJECTIVE), under
+// the names every prototype gives them (include/sr3_mi355x.h), into the request `t`
+#define SR3_TRAIN_STEP_COMMON(t)                                                                                                      \
+  t.hr = hr_nchw; t.cond = cond_nchw; t.cond_channels = cond_channels; t.z = z_nchw; t.q_ca = q_ca; t.q_cb = q_cb;                    \
+  t.level = noise_level; t.tstep = timestep; t.freq = freq; t.params = params; t.grads = grads;                                       \
+  t.workspace = workspace; t.workspace_bytes = workspace_bytes; t.loss_sum_out = loss_sum_out; t.grad_scale = grad_scale;             \
+  t.dropout_p = dropout_p; t.dropout_seed = dropout_seed;                                                                             \
+  t.n_marks = n_marks; t.mark_offsets = mark_offsets; t.mark_events = mark_events;                                                    \
+  t.batch = batch; t.stream = static_cast<hipStream_t>(stream)
+#define SR3_TRAIN_STEP_OBJECTIVE(t) \
+  t.obj.tgt_z = tgt_z; t.obj.tgt_x0 = tgt_x0; t.obj.weight = weight; t.obj.kind = loss_kind; t.obj.huber_delta = huber_delta
 
 int sr3_train_step_ex(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels, const float* z_nchw,
                       const float* q_ca, const float* q_cb, const float* noise_level, const int64_t* timestep,
@@ -642,9 +651,10 @@ int sr3_train_step_ex(sr3_plan* plan, const float* hr_nchw, const float* cond_nc
                       float* loss_sum_out, float grad_scale, float dropout_p, unsigned dropout_seed, int n_marks,
                       const size_t* mark_offsets, void* const* mark_events, int batch, const float* tgt_z, const float* tgt_x0,
                       const float* weight, int loss_kind, float huber_delta, void* stream) {
-  return train_step_body("sr3_train_step_ex", plan, hr_nchw, cond_nchw, cond_channels, z_nchw, q_ca, q_cb, noise_level, timestep, freq, params,
-                         grads, workspace, workspace_bytes, loss_sum_out, grad_scale, dropout_p, dropout_seed, n_marks, mark_offsets,
-                         mark_events, batch, tgt_z, tgt_x0, weight, loss_kind, huber_delta, nullptr, 0.f, nullptr, stream);
+  TrainStep t;
+  SR3_TRAIN_STEP_COMMON(t);
+  SR3_TRAIN_STEP_OBJECTIVE(t);
+  return train_step_checked("sr3_train_step_ex", plan, t, TRAIN_EX);
 }
 
 // ... of a plan with a variance head (plan option var_channels): the hybrid loss (sr3_hybrid_loss_grad_f32) in place of the pixel loss
@@ -655,10 +665,11 @@ int sr3_train_step_ex2(sr3_plan* plan, const float* hr_nchw, const float* cond_n
                        const size_t* mark_offsets, void* const* mark_events, int batch, const float* tgt_z, const float* tgt_x0,
                        const float* weight, int loss_kind, float huber_delta, const float* step_scalars, float vlb_lambda,
                        float* vlb_sum_out, void* stream) {
-  if (!step_scalars) { set_error("sr3_train_step_ex2: step_scalars is NULL"); return SR3_E_BADARG; }
-  return train_step_body("sr3_train_step_ex2", plan, hr_nchw, cond_nchw, cond_channels, z_nchw, q_ca, q_cb, noise_level, timestep, freq, params,
-                         grads, workspace, workspace_bytes, loss_sum_out, grad_scale, dropout_p, dropout_seed, n_marks, mark_offsets,
-                         mark_events, batch, tgt_z, tgt_x0, weight, loss_kind, huber_delta, step_scalars, vlb_lambda, vlb_sum_out, stream);
+  TrainStep t;
+  SR3_TRAIN_STEP_COMMON(t);
+  SR3_TRAIN_STEP_OBJECTIVE(t);
+  t.obj.hyb = step_scalars; t.obj.lambda = vlb_lambda; t.vlb_sum_out = vlb_sum_out;
+  return train_step_checked("sr3_train_step_ex2", plan, t, TRAIN_EX2);
 }
 
 // sr3_train_step_ex2 (a plan with a variance head) or sr3_train_step_ex (one without: fixed small variance) with the per-image terms of
@@ -671,21 +682,26 @@ int sr3_train_step_ex3(sr3_plan* plan, const float* hr_nchw, const float* cond_n
                        const float* weight, int loss_kind, float huber_delta, const float* step_scalars, float vlb_lambda,
                        float* vlb_sum_out, float* per_image_out, void* scratch, size_t scratch_bytes, const float* vlb_weight,
                        void* stream) {
-  if (!step_scalars) { set_error("sr3_train_step_ex3: step_scalars is NULL"); return SR3_E_BADARG; }
-  return train_step_body("sr3_train_step_ex3", plan, hr_nchw, cond_nchw, cond_channels, z_nchw, q_ca, q_cb, noise_level, timestep, freq, params,
-                         grads, workspace, workspace_bytes, loss_sum_out, grad_scale, dropout_p, dropout_seed, n_marks, mark_offsets,
-                         mark_events, batch, tgt_z, tgt_x0, weight, loss_kind, huber_delta, step_scalars, vlb_lambda, vlb_sum_out, stream, true,
-                         per_image_out, scratch, scratch_bytes, vlb_weight);
+  TrainStep t;
+  SR3_TRAIN_STEP_COMMON(t);
+  SR3_TRAIN_STEP_OBJECTIVE(t);
+  t.obj.hyb = step_scalars; t.obj.lambda = vlb_lambda; t.vlb_sum_out = vlb_sum_out;
+  t.obj.vlb_w = vlb_weight;
+  t.pi.out = per_image_out; t.pi.part = static_cast<double*>(scratch); t.pi_scratch_bytes = scratch_bytes;
+  return train_step_checked("sr3_train_step_ex3", plan, t, TRAIN_EX3);
 }
-
+// sr3_train_step_ex with its own objective: target z, weight 1, the plan's loss (refusals under that entry's name, as ever)
 int sr3_train_step(sr3_plan* plan, const float* hr_nchw, const float* cond_nchw, int cond_channels, const float* z_nchw,
                    const float* q_ca, const float* q_cb, const float* noise_level, const int64_t* timestep,
                    const float* freq, const float* params, float* grads, void* workspace, size_t workspace_bytes,
                    float* loss_sum_out, float grad_scale, float dropout_p, unsigned dropout_seed, int n_marks,
                    const size_t* mark_offsets, void* const* mark_events, int batch, void* stream) {
-  return sr3_train_step_ex(plan, hr_nchw, cond_nchw, cond_channels, z_nchw, q_ca, q_cb, noise_level, timestep, freq, params, grads,
-                           workspace, workspace_bytes, loss_sum_out, grad_scale, dropout_p, dropout_seed, n_marks, mark_offsets,
-                           mark_events, batch, nullptr, nullptr, nullptr, -1, 0.f, stream);
+  TrainStep t;
+  SR3_TRAIN_STEP_COMMON(t);
+  t.obj.kind = -1; t.obj.huber_delta = 0.f;
+  return train_step_checked("sr3_train_step_ex", plan, t, TRAIN_EX);
 }
+#undef SR3_TRAIN_STEP_COMMON
+#undef SR3_TRAIN_STEP_OBJECTIVE
 
 }  // extern "C"

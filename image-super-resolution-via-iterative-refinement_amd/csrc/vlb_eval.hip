@@ -2,7 +2,7 @@
 // Nichol & Dhariwal 2021, "Improved DDPM"): what the evaluation walk (calc_bpd_loop) measures per step and what the
 // loss-aware timestep sampler reads back from a training step (sr3_train_step_ex3).
 //
-// The per-element term is k_hybrid_loss_grad's vlb (train_kernels.hip), restated here without its gradient and with the sampler's clamp
+// The per-element term is the hybrid loss kernel's vlb (vlb_elem, train_kernels.hip), restated here without its gradient and with the sampler's clamp
 // of x0^ -- the training kernel is left as it is.  With the row {a, b, c1, c2, lb = log beta, lt = log beta~, last} of the step, all fp32:
 //
 //   x0^ = a x_t - b out_c ; clamp(-1, 1) if clip_denoised

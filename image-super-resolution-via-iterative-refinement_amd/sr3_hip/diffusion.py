@@ -1167,10 +1167,29 @@ class EngineDiffusion(nn.Module):
         b, c, h, w = x_start.shape
         dev = x_start.device
         un = self.denoise_fn           # (a CPU tensor is refused by the engine call: there is no CPU fallback)
+        # the draws, in the order that is the step's behaviour: the t_sampler's probabilities, the step, z, then the conditioning's
+        gamma, ca, cb, level, tstep, hyb_t, ts_p = self._draw_step(b, dev, gamma, t)
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        cond = self._train_cond(x_in, x_start, noise, (ca, cb, level, tstep, gamma), cond_keep, cond_level, cond_noise, self_cond)
+        objective, kw = self._step_objective(b, dev, tstep, gamma, hyb_t, ts_p)
+        loss = un.train_step(x_start, cond, noise.contiguous(), ca.contiguous(), cb.contiguous(), level, tstep,
+                             grad_scale=1.0 / float(b * c * h * w), drop_seed=drop_seed, objective=objective, **kw)
+        if self.learned_variance is not None:
+            self.last_vlb = un.last_vlb / float(b * c * h * w)      # bits per dimension (the sum is over every rank's batch: see model.py)
+        if self.t_sampler is not None:
+            self._t_pending = (hyb_t, un.last_per_image)
+        return loss
+
+    def _draw_step(self, b, dev, gamma, t):
+        """The step of a training batch, drawn as the reference draws it unless `gamma` / `t` inject it -> (gamma, ca, cb, level, tstep,
+        hyb_t, ts_p): the SR3 levels on the host (None for DDPM), q_sample's coefficients, the network's level or timestep argument (the
+        other None), under learned_variance / t_sampler the drawn step of every image, 0-based, on the schedule's grid (else None), and
+        the t_sampler's probabilities (None without one)."""
         level = tstep = None
         lv = self.learned_variance
-        hyb_t = None                   # under the key: the drawn step of every image, 0-based, on the schedule's grid
-        ts = self.t_sampler
+        hyb_t = None
+        ts, ts_p = self.t_sampler, None
         if ts is not None:
             self.flush_t_sampler()     # (a caller that never read the last step's terms: they enter the history before p is formed)
             ts_p = ts.probabilities()
@@ -1205,9 +1224,14 @@ class EngineDiffusion(nn.Module):
             tstep = t.long().to(dev)
             ca, cb = self.sqrt_alphas_cumprod[tstep], self.sqrt_one_minus_alphas_cumprod[tstep]
             hyb_t = tstep if lv is not None or ts is not None else None
+        return gamma, ca, cb, level, tstep, hyb_t, ts_p
 
-        if noise is None:
-            noise = torch.randn_like(x_start)
+    def _train_cond(self, x_in, x_start, noise, step, cond_keep, cond_level, cond_noise, self_cond):
+        """The conditioning tensor of a training step (None: an unconditional model without self-conditioning): x_in['SR'] through
+        cond_drop, cond_augment and self-conditioning, each drawing what was not injected -- cond_drop's flags, cond_augment's levels
+        then noise, self-conditioning's flags, in that order.  `step`: (ca, cb, level, tstep, gamma) of _draw_step."""
+        b = x_start.shape[0]
+        dev = x_start.device
         cond = x_in['SR'].contiguous() if self.conditional else None
         keep = None
         if cond_keep is not None or self.cond_drop > 0.0:
@@ -1226,19 +1250,23 @@ class EngineDiffusion(nn.Module):
             L.check(L.load().sr3_cond_drop_f32(L.ptr(cond), L.ptr(keep), b, cond[0].numel(), L.ptr(buf), self._stream(dev)))
             cond = buf
         if self_cond is not None or self.self_condition is not None:
-            cond = self._self_condition_input(x_start, cond, noise, ca, cb, level, tstep, gamma, self_cond)
+            cond = self._self_condition_input(x_start, cond, noise, *step, self_cond)
+        return cond
+
+    def _step_objective(self, b, dev, tstep, gamma, hyb_t, ts_p):
+        """-> (objective, the hybrid / per_image / vlb_weight keywords) of `train_step` for the drawn step: `_train_objective`, and under
+        learned_variance / t_sampler the step's scalars and the sampler's weights."""
+        lv, ts = self.learned_variance, self.t_sampler
+        objective = self._train_objective(tstep, gamma, dev)
+        kw = {}
         if lv is None and ts is None:
-            return un.train_step(x_start, cond, noise.contiguous(), ca.contiguous(), cb.contiguous(), level, tstep,
-                                 grad_scale=1.0 / float(b * c * h * w), drop_seed=drop_seed,
-                                 objective=self._train_objective(tstep, gamma, dev))
+            return objective, kw
         # the hybrid loss: per image the scalars of its step -- the x0 rule, the posterior's coefficients, log beta, log beta~ (clipped),
         # the last-step flag -- from the walk over all T steps (`ancestral_tables`, float64, rounded once), gathered on the device
         if self._hyb_table is None or self._hyb_table.device != dev:
             tabs = ancestral_tables(self._alphas_cumprod64, self.num_timesteps, prediction=self.prediction)
             self._hyb_table = torch.tensor(hybrid_step_scalars(tabs, np.arange(self.num_timesteps)), dtype=torch.float32).to(dev)
         scal = self._hyb_table[hyb_t].contiguous()
-        objective = self._train_objective(tstep, gamma, dev)
-        kw = {}
         if ts is not None:
             # the loss of a step drawn with p_t is weighted by 1 / (T p_t): into the per-image weight table, which is made here where
             # the objective had none (target z, weight 1, the configured loss)
@@ -1253,13 +1281,7 @@ class EngineDiffusion(nn.Module):
             kw['hybrid'] = (scal, lv['lambda'])
             if ts is not None:             # ... and into L_vlb's own table: the objective's `weight` reaches L_simple alone
                 kw['vlb_weight'] = wt
-        loss = un.train_step(x_start, cond, noise.contiguous(), ca.contiguous(), cb.contiguous(), level, tstep,
-                             grad_scale=1.0 / float(b * c * h * w), drop_seed=drop_seed, objective=objective, **kw)
-        if lv is not None:
-            self.last_vlb = un.last_vlb / float(b * c * h * w)      # bits per dimension (the sum is over every rank's batch: see model.py)
-        if ts is not None:
-            self._t_pending = (hyb_t, un.last_per_image)
-        return loss
+        return objective, kw
 
     def _cond_augment_input(self, cond, keep, cond_level, cond_noise):
         """The conditioning tensor of a training step under noise conditioning augmentation, [B, Cl (+ 1), H, W] in a buffer this module

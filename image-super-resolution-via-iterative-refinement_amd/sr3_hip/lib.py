@@ -40,6 +40,10 @@ _Z = C.c_size_t
 # name -> (restype, argtypes): every symbol include/sr3_mi355x.h and include/sr3_io_mi355x.h declare
 _F = C.c_float
 _PI = C.POINTER(C.c_int)
+# what the four sr3_train_step* entries share: plan .. batch (sr3_train_step's own arguments without its stream), then the objective's
+# tgt_z, tgt_x0, weight, loss_kind, huber_delta; every entry ends in its stream
+_TRAIN_STEP = [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _F, _F, C.c_uint, _I, _P, _P, _I]
+_TRAIN_STEP_EX = _TRAIN_STEP + [_P, _P, _P, _I, _F]
 SIGNATURES = {
     'sr3_tensor2img': (_I, [_P, _I, _I, _I, _I, _F, _F, _I, _I, _I, _P, _PI, _PI, _PI, _P]),
     'sr3_sse_u8': (_I, [_P, _P, _I, _Z, _P, _P]),
@@ -114,14 +118,10 @@ SIGNATURES = {
     'sr3_distill_target_f32': (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     'sr3_q_sample': (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     'sr3_train_workspace_bytes': (_Z, [_P, _I, _I]),
-    'sr3_train_step': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, C.c_float, C.c_float, C.c_uint,
-                            _I, _P, _P, _I, _P]),
-    'sr3_train_step_ex': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, C.c_float, C.c_float, C.c_uint,
-                               _I, _P, _P, _I, _P, _P, _P, _I, C.c_float, _P]),
-    'sr3_train_step_ex2': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, C.c_float, C.c_float, C.c_uint,
-                                _I, _P, _P, _I, _P, _P, _P, _I, C.c_float, _P, C.c_float, _P, _P]),
-    'sr3_train_step_ex3': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, C.c_float, C.c_float, C.c_uint,
-                                _I, _P, _P, _I, _P, _P, _P, _I, C.c_float, _P, C.c_float, _P, _P, _P, _Z, _P, _P]),
+    'sr3_train_step': (_I, _TRAIN_STEP + [_P]),
+    'sr3_train_step_ex': (_I, _TRAIN_STEP_EX + [_P]),
+    'sr3_train_step_ex2': (_I, _TRAIN_STEP_EX + [_P, _F, _P, _P]),                     # + step_scalars, vlb_lambda, vlb_sum_out
+    'sr3_train_step_ex3': (_I, _TRAIN_STEP_EX + [_P, _F, _P, _P, _P, _Z, _P, _P]),     # ... per_image_out, scratch, scratch_bytes, vlb_weight
     'sr3_vlb_terms_partials_bytes': (_Z, [_I]),
     'sr3_vlb_terms_f32': (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
     'sr3_prior_bpd_f32': (_I, [_P, _I, _I, C.c_float, C.c_float, C.c_float, _P, _P, _Z, _P]),

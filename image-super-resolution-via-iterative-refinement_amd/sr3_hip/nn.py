@@ -417,44 +417,33 @@ class EngineUNet(nn.Module):
         for t in (tgt_z, tgt_x0, weight):
             if t is not None and (t.device != dev or t.dtype != torch.float32 or t.numel() != B or not t.is_contiguous()):
                 raise L.Sr3Error('training: tgt_z / tgt_x0 / weight must be contiguous fp32 tensors of %d elements on %s' % (B, dev))
-        if per_image is not None:      # the step's per-image terms of the bound too: sr3_train_step_ex3 (with or without a variance head)
-            scal, out, vw = (tuple(per_image) + (None,))[:3]
-            if tuple(out.shape) != (B, 2) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
-                raise L.Sr3Error('training: per_image_out must be a contiguous fp32 [%d, 2] tensor on %s' % (B, dev))
-            if vw is not None and (hybrid is None or vw.device != dev or vw.dtype != torch.float32 or vw.numel() != B or not vw.is_contiguous()):
-                raise L.Sr3Error('training: vlb_weight goes with hybrid and must be a contiguous fp32 tensor of %d elements on %s' % (B, dev))
+        # the entry: sr3_train_step_ex; a learned-variance network's hybrid loss, _ex2; with the step's per-image terms of the bound
+        # (with or without a variance head), _ex3.  Each takes the common arguments, then its own tail, then the stream
+        entry, tail = plan.lib.sr3_train_step_ex, ()
+        if per_image is not None or hybrid is not None:
+            scal = (hybrid if per_image is None else per_image)[0]
             lam, vlb = (0.0, None) if hybrid is None else hybrid[1:]
+            if per_image is not None:
+                out, vw = (tuple(per_image) + (None,))[1:3]
+                if tuple(out.shape) != (B, 2) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+                    raise L.Sr3Error('training: per_image_out must be a contiguous fp32 [%d, 2] tensor on %s' % (B, dev))
+                if vw is not None and (hybrid is None or vw.device != dev or vw.dtype != torch.float32 or vw.numel() != B or not vw.is_contiguous()):
+                    raise L.Sr3Error('training: vlb_weight goes with hybrid and must be a contiguous fp32 tensor of %d elements on %s' % (B, dev))
             if scal.device != dev or scal.dtype != torch.float32 or tuple(scal.shape) != (B, 8) or not scal.is_contiguous():
                 raise L.Sr3Error('training: step_scalars must be a contiguous fp32 [%d, 8] tensor on %s' % (B, dev))
-            if hybrid is not None and hybrid[0] is not scal:
-                raise L.Sr3Error('training: per_image and hybrid must share one step_scalars tensor')
-            nb = int(plan.lib.sr3_vlb_terms_partials_bytes(B))
-            sc = getattr(self, '_vlb_scratch', None)
-            if sc is None or sc.numel() != nb // 8 or sc.device != dev:
-                sc = self._vlb_scratch = torch.empty(nb // 8, dtype=torch.float64, device=dev)
-            L.check(plan.lib.sr3_train_step_ex3(plan.handle, L.ptr(hr), L.ptr(cond), cc, L.ptr(z), L.ptr(ca), L.ptr(cb),
-                                                L.ptr(level), L.ptr(tstep), L.ptr(self.freq), L.ptr(self.arena.data),
-                                                L.ptr(self.grad_arena), L.ptr(wsv), need, L.ptr(loss), C.c_float(grad_scale),
-                                                C.c_float(p_drop), C.c_uint(drop_seed & 0xFFFFFFFF), n_marks, offs, evs, B,
-                                                L.ptr(tgt_z), L.ptr(tgt_x0), L.ptr(weight), int(kind), C.c_float(delta),
-                                                L.ptr(scal), C.c_float(lam), L.ptr(vlb), L.ptr(out), L.ptr(sc), nb, L.ptr(vw), stream))
-            return
-        if hybrid is not None:         # a learned-variance network: the hybrid loss, sr3_train_step_ex2
-            scal, lam, vlb = hybrid
-            if scal.device != dev or scal.dtype != torch.float32 or tuple(scal.shape) != (B, 8) or not scal.is_contiguous():
-                raise L.Sr3Error('training: step_scalars must be a contiguous fp32 [%d, 8] tensor on %s' % (B, dev))
-            L.check(plan.lib.sr3_train_step_ex2(plan.handle, L.ptr(hr), L.ptr(cond), cc, L.ptr(z), L.ptr(ca), L.ptr(cb),
-                                                L.ptr(level), L.ptr(tstep), L.ptr(self.freq), L.ptr(self.arena.data),
-                                                L.ptr(self.grad_arena), L.ptr(wsv), need, L.ptr(loss), C.c_float(grad_scale),
-                                                C.c_float(p_drop), C.c_uint(drop_seed & 0xFFFFFFFF), n_marks, offs, evs, B,
-                                                L.ptr(tgt_z), L.ptr(tgt_x0), L.ptr(weight), int(kind), C.c_float(delta),
-                                                L.ptr(scal), C.c_float(lam), L.ptr(vlb), stream))
-            return
-        L.check(plan.lib.sr3_train_step_ex(plan.handle, L.ptr(hr), L.ptr(cond), cc, L.ptr(z), L.ptr(ca), L.ptr(cb),
-                                           L.ptr(level), L.ptr(tstep), L.ptr(self.freq), L.ptr(self.arena.data),
-                                           L.ptr(self.grad_arena), L.ptr(wsv), need, L.ptr(loss), C.c_float(grad_scale),
-                                           C.c_float(p_drop), C.c_uint(drop_seed & 0xFFFFFFFF), n_marks, offs, evs, B,
-                                           L.ptr(tgt_z), L.ptr(tgt_x0), L.ptr(weight), int(kind), C.c_float(delta), stream))
+            entry, tail = plan.lib.sr3_train_step_ex2, (L.ptr(scal), C.c_float(lam), L.ptr(vlb))
+            if per_image is not None:
+                if hybrid is not None and hybrid[0] is not scal:
+                    raise L.Sr3Error('training: per_image and hybrid must share one step_scalars tensor')
+                nb = int(plan.lib.sr3_vlb_terms_partials_bytes(B))
+                sc = getattr(self, '_vlb_scratch', None)
+                if sc is None or sc.numel() != nb // 8 or sc.device != dev:
+                    sc = self._vlb_scratch = torch.empty(nb // 8, dtype=torch.float64, device=dev)
+                entry, tail = plan.lib.sr3_train_step_ex3, tail + (L.ptr(out), L.ptr(sc), nb, L.ptr(vw))
+        L.check(entry(plan.handle, L.ptr(hr), L.ptr(cond), cc, L.ptr(z), L.ptr(ca), L.ptr(cb), L.ptr(level), L.ptr(tstep), L.ptr(self.freq),
+                      L.ptr(self.arena.data), L.ptr(self.grad_arena), L.ptr(wsv), need, L.ptr(loss), C.c_float(grad_scale), C.c_float(p_drop),
+                      C.c_uint(drop_seed & 0xFFFFFFFF), n_marks, offs, evs, B, L.ptr(tgt_z), L.ptr(tgt_x0), L.ptr(weight), int(kind),
+                      C.c_float(delta), *tail, stream))
 
     def named_gradients(self):
         """(reference key, gradient view in the reference shape) after a train_step."""
