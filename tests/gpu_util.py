@@ -94,6 +94,56 @@ def wino_expected_refusal(B, Cin, H, W, ups, tile, ksplit, k=3, stride=1):
     return None
 
 
+def halo_expected_refusal(B, Cin, H, W, ups, tile, ksplit, k=3, stride=1):
+    """Which error message the halo kernel (tiles 5, 6, 9: conv3x3_halo.hip) MUST raise for this problem, or None when it must run --
+    halo_geometry and the order of checks in conv_forward restated, as wino_expected_refusal restates the Winograd rules: 3x3 stride 1;
+    an output at least 16 wide in 16-wide tiles of height BM / 16 (BM 128 for tile 5, 256 for tiles 6 and 9), an output 8 wide in
+    8 x 8 tiles of two images each (tile 5 only; an odd batch leaves the last tile's second image absent), nothing else; whole tiles
+    in both directions; then the split, over 32-channel chunks, must leave no split empty."""
+    assert tile in (5, 6, 9), tile
+    Ho, Wo = H << ups, W << ups
+    if k != 3 or stride != 1:
+        return 'does not fit'
+    BM = 128 if tile == 5 else 256
+    if Wo >= 16:
+        TW, TH = 16, BM // 16
+    elif Wo == 8 and tile == 5:
+        TW, TH = 8, 8
+    else:
+        return 'does not fit'
+    if Ho % TH or Wo % TW:
+        return 'does not fit'
+    chunks = -(-Cin // 32)
+    if ksplit > 1 and (ksplit - 1) * -(-chunks // ksplit) >= chunks:
+        return 'empty split'
+    return None
+
+
+def auto_halo_tile(B, Cin, Cout, H, W, ups, k=3, stride=1):
+    """The halo tile conv_pick chooses for tile_cfg 0 (None: it goes to another kernel): 6 for Cout <= 64; 9 where it fits and still
+    fills a round of 256 workgroups; else 5."""
+    fits = lambda t: halo_expected_refusal(B, Cin, H, W, ups, t, 0, k, stride) is None
+    if Cout <= 64 and fits(6):
+        return 6
+    if Cout > 64 and fits(9) and -(-Cout // 128) * ((W << ups) // 16) * ((H << ups) // 16) * B >= 256:
+        return 9
+    return 5 if fits(5) else None
+
+
+def conv_expected_refusal(B, Cin, Cout, H, W, ups, tile, ksplit, k=3, stride=1):
+    """The message a conv on `tile` must be refused with, None where it must run: the halo rule for tiles 5, 6, 9 (and for the halo
+    tile conv_pick takes under tile 0), the Winograd rule for tiles 11-13; the im2col tiles (1-4, 14-21) refuse no shape and no split
+    (a split past the last k-step writes a slab of zeros)."""
+    if tile == 0:
+        tile = auto_halo_tile(B, Cin, Cout, H, W, ups, k, stride) or 0
+    tile = {7: 5, 8: 6, 10: 9}.get(tile, tile)          # (the experiment tiles share the geometry of 5, 6 and 9)
+    if tile in (5, 6, 9):
+        return halo_expected_refusal(B, Cin, H, W, ups, tile, ksplit, k, stride)
+    if tile in (11, 12, 13):
+        return wino_expected_refusal(B, Cin, H, W, ups, tile, ksplit, k, stride)
+    return None
+
+
 def conv_ref(src0, src1, w, bias=None, ss=None, act=0, film=None, res0=None, res1=None, ups=0, stride=1):
     """float64 reference of the same fused op."""
     x = src0 if src1 is None else torch.cat([src0, src1], 1)

@@ -147,15 +147,16 @@ def _make_case(case, seed=1):
                                              (14, 1), (15, 1), (16, 1), (17, 1), (14, 3), (16, 2)])
 def test_conv(case, tile_cfg, ksplit):
     src0, src1, w, kw = _make_case(case)
-    total = ((src0.shape[1] + (0 if src1 is None else src1.shape[1]) + 31) // 32) * w.shape[2] * w.shape[3]
-    if ksplit > total:
-        pytest.skip('more splits than k-steps')
-    try:
-        got, _ = G.conv_call(src0, src1, w, tile_cfg=tile_cfg, ksplit=ksplit, **kw)
-    except L.Sr3Error as e:
-        if tile_cfg >= 5 and ('does not fit' in str(e) or 'empty split' in str(e)):
-            pytest.skip('halo kernel does not cover this shape')
-        raise
+    # a refusal is asserted, never skipped on: the halo and Winograd tiles by their restated rules (gpu_util); the im2col tiles refuse
+    # nothing -- with more splits than k-steps (conv_igemm_forward launches them all) the splits past the last k-step write zero slabs
+    # and the reduce still gives the conv
+    why = G.conv_expected_refusal(src0.shape[0], w.shape[1], w.shape[0], src0.shape[2], src0.shape[3], kw['ups'], tile_cfg, ksplit,
+                                  k=w.shape[2], stride=kw['stride'])
+    if why:
+        with pytest.raises(L.Sr3Error, match=why):
+            G.conv_call(src0, src1, w, tile_cfg=tile_cfg, ksplit=ksplit, **kw)
+        return
+    got, _ = G.conv_call(src0, src1, w, tile_cfg=tile_cfg, ksplit=ksplit, **kw)
     ref = G.conv_ref(src0, src1, w, **kw)
     assert not torch.isnan(got).any()
     G.assert_close(got, ref, what=case[0])
@@ -176,18 +177,14 @@ def test_conv_fused_output_stats(ksplit, tile_cfg, case):
         with pytest.raises(L.Sr3Error):
             G.conv_call(src0, src1, w, ksplit=ksplit, tile_cfg=tile_cfg, want_stats=True, **kw)
         return
-    if tile_cfg in (11, 12, 13):       # the Winograd tiles: a refusal is asserted, never skipped on
-        why = G.wino_expected_refusal(src0.shape[0], w.shape[1], src0.shape[2], src0.shape[3], kw['ups'], tile_cfg, ksplit)
-        if why:
-            with pytest.raises(L.Sr3Error, match=why):
-                G.conv_call(src0, src1, w, ksplit=ksplit, tile_cfg=tile_cfg, want_stats=True, **kw)
-            return
-    try:
-        got, st = G.conv_call(src0, src1, w, ksplit=ksplit, tile_cfg=tile_cfg, want_stats=True, **kw)
-    except L.Sr3Error as e:
-        if (5 <= tile_cfg <= 10 and 'does not fit' in str(e)) or (tile_cfg <= 10 and ksplit > 1 and 'empty split' in str(e)):
-            pytest.skip(str(e))         # halo tiles (not on the default inference plan): geometry-restricted; an explicit split-K
-        raise                           # that the problem's K cannot fill
+    # every tile: a refusal is asserted, never skipped on (the halo tiles are geometry-restricted, and an explicit split-K that the
+    # problem's K cannot fill is refused on them and on the Winograd tiles; tile 0 takes the halo tile conv_pick chooses)
+    why = G.conv_expected_refusal(src0.shape[0], w.shape[1], w.shape[0], src0.shape[2], src0.shape[3], kw['ups'], tile_cfg, ksplit)
+    if why:
+        with pytest.raises(L.Sr3Error, match=why):
+            G.conv_call(src0, src1, w, ksplit=ksplit, tile_cfg=tile_cfg, want_stats=True, **kw)
+        return
+    got, st = G.conv_call(src0, src1, w, ksplit=ksplit, tile_cfg=tile_cfg, want_stats=True, **kw)
     ref = G.conv_ref(src0, src1, w, **kw)
     G.assert_close(got, ref)
     s1 = got.double().sum(dim=(2, 3))
@@ -370,8 +367,7 @@ def test_gemm_split_error_not_above_fp32_mfma(case, tile, ksplit):
     weights pre-split into bf16 planes, which is what a plan runs): on the 1x1 / stride-2 layer
     shapes of the BASELINE networks the error against float64 is not above the exact-fp32 instantiation's (tile 3) on the
     same data, and the stated tolerance holds.  (0, 0) is the ABI's auto pick, which stays on the fp32 MFMA."""
-    if tile in (14, 17, 18, 21) and case[6] <= 64:
-        pytest.skip('128-wide tiles are not used for Cout <= 64')
+    # (no plan uses a 128-wide tile for Cout <= 64, but the kernel takes it: half of each tile's columns hang over Cout and are masked)
     src0, src1, w, kw = _make_case(case, seed=11)
     if tile == 22 and not _gemm1x1_fits(case[7], case[8], case[6], case[3], case[10]):
         # tile 22 = the plain GEMM kernel of gemm1x1.hip (plan option gemm2): 1x1 stride 1 or 3x3 stride 2, Cout % 128 == 0 only -- asserted, not skipped
@@ -516,11 +512,12 @@ def test_block_conv_with_fused_res_conv(shape, tile_cfg, ksplit):
                                 L.ptr(dv['w2']), L.ptr(dv['b2']), L.ptr(out), None, tile_cfg, ksplit, L.ptr(scratch),
                                 nb, G.stream())
     torch.cuda.synchronize()
-    if rc != 0:
-        msg = lib.sr3_last_error().decode()
-        if tile_cfg >= 5 and ('does not fit' in msg or 'empty split' in msg):
-            pytest.skip(msg)            # halo tiles (not on the default inference plan): geometry-restricted
-        L.check(rc)
+    why = G.conv_expected_refusal(B, C0 + C1, Cout, H, W, 0, tile_cfg, ksplit)      # the halo tiles are geometry-restricted: asserted
+    if why:
+        with pytest.raises(L.Sr3Error, match=why):
+            L.check(rc)
+        return
+    L.check(rc)
     G.assert_close(G.nchw(out).cpu(), ref, what='block conv + res_conv')
 
 

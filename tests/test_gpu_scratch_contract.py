@@ -11,54 +11,14 @@ pytestmark = pytest.mark.gpu
 
 import gpu_util as G                                             # noqa: E402
 import guarded as GD                                             # noqa: E402
-from guarded import Guarded                                      # noqa: E402
+from guarded import same_bits                                    # noqa: E402
 from scratch_rows import ROWS                                    # noqa: E402
 from sr3_hip import lib as L                                     # noqa: E402
 
 
-def same_bits(a, b):
-    return torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
-
-
 @pytest.mark.parametrize('row', ROWS, ids=[r.id for r in ROWS])
 def test_per_op_scratch_contract(row):
-    lib, d = L.load(), G.dev()
-    spec = row.spec()
-    nb = spec['query'](lib)
-    assert nb > 0, 'the row has nothing in scratch'
-    if spec.get('expect') is not None:
-        assert nb == spec['expect'], (nb, spec['expect'])
-    ins = {k: GD.tensor_in(v, d)[0] for k, v in spec['ins'].items()}
-    results = []
-    for name, byte in GD.FILLS:
-        scratch = Guarded(nb, byte, d)
-        guards = dict(ins, scratch=scratch)
-        outs = {}
-        for k, o in spec['outs'].items():
-            if torch.is_tensor(o):          # in / out: starts from the row's value
-                guards[k], outs[k] = GD.tensor_out(tuple(o.shape), d, dtype=o.dtype)
-                outs[k].copy_(o)
-            else:
-                guards[k], outs[k] = GD.tensor_out(o[0], d, dtype=o[1])
-        if spec.get('derived'):
-            guards['derived'] = Guarded(spec['derived'], byte, d)
-        P = {k: g.ptr for k, g in guards.items() if k != 'scratch'}
-        rc = spec['call'](lib, P, scratch.ptr, nb, G.stream())
-        assert rc == 0, lib.sr3_last_error()
-        torch.cuda.synchronize()
-        for k, g in guards.items():
-            assert g.intact(), '%s: a kernel wrote outside `%s` (scratch fill %s)' % (row.id, k, name)
-        for k, v in outs.items():
-            if v.is_floating_point():
-                assert bool(torch.isfinite(v).all()), '%s: %d non-finite elements in `%s` (scratch fill %s)' % (row.id, int((~torch.isfinite(v)).sum()), k, name)
-        for k, v in spec['ins'].items():
-            assert same_bits(ins[k].view(v.dtype, tuple(v.shape)).cpu(), v), '%s: input `%s` was modified' % (row.id, k)
-        results.append({k: v.cpu() for k, v in outs.items()})
-    for (name, _), got in zip(GD.FILLS[1:], results[1:]):
-        for k in got:
-            assert same_bits(got[k], results[0][k]), '%s: scratch fill %s changes `%s`: %d of %d elements differ' % (
-                row.id, name, k, int((got[k] != results[0][k]).sum()), got[k].numel())
-    spec['check'](results[0])
+    GD.run_row(row, L.load(), G.dev(), G.stream(), fills=GD.FILLS, operands=False)          # (shared with tests/test_gpu_edge_operands.py)
 
 
 @pytest.mark.parametrize('tile_cfg,ksplit', [(13, 2), (12, 2), (22, 2)])
