@@ -1,5 +1,5 @@
 // Per-op C entry points (include/sr3_mi355x.h): one kernel on caller-owned tensors, outside any plan -- reverse-step update, q_sample, the conv
-// entries and their scratch / slice queries, GroupNorm, attention, embedding, the NCHW convs.  Plans and the sr3_plan_* entries: plan.hip.
+// entries and their scratch / slice queries, GroupNorm, attention, embedding, the NCHW convs.  Plans and the sr3_plan_* entries: plan_abi.hip.
 #include "plan_internal.h"
 #include "tile_code.h"
 

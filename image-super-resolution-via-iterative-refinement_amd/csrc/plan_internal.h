@@ -1,4 +1,5 @@
-// Internal plan structures shared by plan.hip (inference driver) and train_plan.hip (training step).
+// Internal plan structures shared by plan_build.hip (planner), plan_run.hip (forward driver), plan_abi.hip (C ABI) and train_plan.hip
+// (training step).
 #pragma once
 #include <map>
 #include <string>
@@ -41,14 +42,14 @@ struct Layer {
   ResLayer res;
 };
 
-// an optional workspace / arena offset that is absent (run_forward binds a null pointer for it)
+// an optional workspace / arena offset that is absent (plan_run.hip binds a null pointer for it)
 static constexpr size_t NO_OFF = ~(size_t)0;
 
-// The kernel one conv of a plan runs on, as choose_conv (plan.hip) decided it
+// The kernel one conv of a plan runs on, as choose_conv (plan_build.hip) decided it
 struct ConvChoice {
   int tile_cfg, ksplit;            // what conv_forward is called with
   int wino_split, igemm_split;     // the ConvParams fields of these names
-  int wino_mode;                   // 0: the Winograd rule did not take the conv; 1 / 2: wino_mode (plan.hip)
+  int wino_mode;                   // 0: the Winograd rule did not take the conv; 1 / 2: wino_mode (plan_build.hip)
   size_t wino_off;                 // tile_cfg 11: float offset of this conv's transformed filters in the derived buffer
   bool has_wsplit;                 // im2col SPLIT tile / tile 22: its weights pre-split into bf16 planes sit in the derived buffer ...
   size_t wsplit_off;               // ... at this float offset (ConvParams::w_split)
@@ -120,11 +121,15 @@ struct Regions {
   size_t stats_off = 0, ss_off = 0, mr_off = 0, temb_off = 0, film_off = 0, scratch_off = 0, scratch_bytes = 0;
 };
 
+// What one GroupNorm fold of the forward walk wrote (Builder::fold returns it): its tables, as Op::ss_rel / mr_rel, and its parameters
+struct FoldOut { size_t ss_rel = 0, mr_rel = 0, gamma = 0, beta = 0; };
+
 // One conv of the forward, for Builder::conv: sources and residuals are tensor handles (-1: absent), parameters arena offsets
 struct ConvSpec {
   int x0 = -1, x1 = -1;            // source: the virtual concat (x0|x1)
   int Cout = 0, ksize = 3, stride = 1, ups = 0;
-  int act = 0;                     // ConvParams::act: what the prologue does with the GroupNorm fold in front of this conv
+  int act = 0;                     // ConvParams::act: what the prologue does with the GroupNorm fold in front of this conv ...
+  FoldOut gn;                      // ... and that fold (act == 0: none, the op's ss_rel is 0)
   size_t w = 0, bias = NO_OFF;
   int film_row = -1;               // first row of the FiLM table added to the output
   int r0 = -1, r1 = -1;            // residual: the concat view (r0|r1)
@@ -167,22 +172,12 @@ inline unsigned drop_layer_seed(unsigned seed, unsigned key) { return seed + (ke
 
 using namespace sr3;
 
-struct sr3_plan {
-  sr3_unet_desc d;
-  std::vector<sr3_param_info> params;
-  std::map<std::string, int> pindex;
-  size_t param_floats = 0;
-  int F = 0;
-  size_t film_w = 0, film_b = 0;
-  size_t emb_w1 = 0, emb_b1 = 0, emb_w2 = 0, emb_b2 = 0;
-  std::vector<Layer> downs, mid, ups;
-  size_t fin_gn_w = 0, fin_gn_b = 0, fin_w = 0, fin_b = 0;
-  int fin_cin = 0, out_ch = 0;
+// Every plan option (sr3_plan_set_option), held as sr3_plan::opt.  PLAN_OPTIONS below says what setting each one does
+struct PlanOptions {
   int var_channels = 0;      // learned reverse-process variance (plan option var_channels): the last var_channels of the out_ch filter rows
                              // are the variance head v, the first out_ch - var_channels the prediction.  0 or out_ch / 2.  Inference
                              // forwards and every step tail run the prediction rows alone (the filters are [co][9][C]: the first rows of
                              // the same buffer) unless the caller asks for all rows; the training forward always runs all of them
-  // options
   int fuse_stats = 1, fuse_res = 1, tile_cfg = 0, ksplit = 0, keep_all = 0, split_bf16 = 0;
   int winograd = 1;          // 3x3 stride-1 convs of the inference plan on the Winograd F(2x2,3x3) kernel (conv3x3_wino.hip)
   int wino2 = 1;             // wino_split convs of the one-image tile without dropout on the two-workgroups-per-CU kernel (conv3x3_wino2.hip,
@@ -218,7 +213,7 @@ struct sr3_plan {
                              // its 64-column tile (waves 2 x 2); 0: they keep the im2col kernel
   int wino_ragged = 1;       // inference plans at a geometry other than image_size x image_size: 3x3 stride-1 convs on maps that are not whole
                              // multiples of the 8 x 16 tile on the two-workgroup kernel's RAGGED instantiation (tile_cfg 23) where the measured rule
-                             // (wino_ragged_wins, plan.hip) says so; 0: they fall back to the general kernels (A/B knob)
+                             // (wino_ragged_wins, plan_build.hip) says so; 0: they fall back to the general kernels (A/B knob)
   int wino_up = 1;           // Upsample's conv (ups = 1) on the two-workgroup Winograd kernel: its UP instantiation, which skips the seven of the sixteen
                              // positions whose operand is exactly zero on a nearest x2 map (same bits); 0: all sixteen (tile_cfg 25 / 26; A/B knob)
   int store_wt = 3;          // STORE_WT_* bits (sr3_common.h), one per kernel family: its 16-byte epilogue stores are written through L2 (sc1), so the
@@ -234,8 +229,74 @@ struct sr3_plan {
   int train_geom = 0;        // training follows the plan's geometry (sr3_plan_set_geometry) too: sr3_train_workspace_bytes / sr3_train_step build the
                              // training plan at plan_height x plan_width.  0: training is refused at any geometry but image_size x image_size.
                              // Off by default ONLY because tests pin that refusal text; at the native geometry both values build the same plan
-  int geo_h = 0, geo_w = 0;  // sr3_plan_set_geometry: image height / width of the next forward (0: image_size)
   int fork_side = 0;         // res_conv (and the embedding MLP) on a side stream beside block1's conv: see Op::side_id; A/B knob
+  int loss_l2 = 0;           // training loss: 0 = L1 (sum), 1 = L2 (sum)  (set_loss, diffusion.py:84-90)
+};
+
+// What setting an option does, beyond storing the value (sr3_plan_set_option, plan_abi.hip, applies exactly these)
+enum OptionEffect {
+  OPT_FORWARD = 1,         // the compiled forward is dropped (even when the value did not change)
+  OPT_TRAIN = 2,           // ... and the training plan
+  OPT_REBUILD = OPT_FORWARD | OPT_TRAIN,
+  OPT_STALE = 4,           // which convs read transformed filters depends on it: a forward must not run on filters prepared for another choice
+  OPT_RELAY = 8,           // the derived buffer's layout depends on it: laid out again when the value changed (re-bind and re-prepare)
+  OPT_EXPERIMENT = 16,     // selects an experiment kernel: a value other than 0 needs a library built with -DSR3_EXPERIMENTS
+};
+// a key's own check of a value (null: every int is taken): SR3_OK, or the code with the error text set
+typedef int (*OptionCheck)(const sr3_plan* plan, const char* key, int value);
+int check_store_wt(const sr3_plan*, const char*, int);
+int check_gemm_epi(const sr3_plan*, const char*, int);
+int check_var_channels(const sr3_plan*, const char*, int);
+int check_attn_heads(const sr3_plan*, const char*, int);      // attn_heads and attn_head_dim
+struct OptionRow { const char* name; int PlanOptions::*slot; unsigned effects; OptionCheck check; };
+// One row per key.  No effect flags: read at launch (store_wt, gemm_epi, attn_split) or where the training step is run (wgrad_split: the
+// slabs are sized for both values; loss_l2), no rebuild
+static const OptionRow PLAN_OPTIONS[] = {
+  {"fuse_stats", &PlanOptions::fuse_stats, OPT_REBUILD, nullptr},
+  {"tile_cfg", &PlanOptions::tile_cfg, OPT_REBUILD | OPT_STALE, nullptr},
+  {"ksplit", &PlanOptions::ksplit, OPT_REBUILD, nullptr},
+  {"keep_all", &PlanOptions::keep_all, OPT_REBUILD, nullptr},
+  {"fuse_res", &PlanOptions::fuse_res, OPT_REBUILD, nullptr},
+  {"split_bf16", &PlanOptions::split_bf16, OPT_REBUILD | OPT_STALE | OPT_EXPERIMENT, nullptr},
+  {"winograd", &PlanOptions::winograd, OPT_REBUILD | OPT_STALE, nullptr},
+  {"wino_split", &PlanOptions::wino_split, OPT_REBUILD | OPT_RELAY, nullptr},
+  {"wino_split8", &PlanOptions::wino_split8, OPT_REBUILD, nullptr},
+  {"wgrad_split", &PlanOptions::wgrad_split, 0, nullptr},
+  {"attn_split", &PlanOptions::attn_split, 0, nullptr},
+  {"store_wt", &PlanOptions::store_wt, 0, check_store_wt},
+  {"gemm_epi", &PlanOptions::gemm_epi, 0, check_gemm_epi},
+  {"attn_long", &PlanOptions::attn_long, OPT_REBUILD, nullptr},
+  {"gemm_split", &PlanOptions::gemm_split, OPT_REBUILD | OPT_RELAY, nullptr},
+  {"gemm_wpre", &PlanOptions::gemm_wpre, OPT_REBUILD | OPT_RELAY, nullptr},
+  {"gemm2", &PlanOptions::gemm2, OPT_REBUILD | OPT_RELAY, nullptr},
+  {"gemm_s2", &PlanOptions::gemm_s2, OPT_REBUILD | OPT_RELAY, nullptr},
+  {"fork_side", &PlanOptions::fork_side, OPT_REBUILD, nullptr},
+  {"gemm_n64", &PlanOptions::gemm_n64, OPT_REBUILD | OPT_RELAY, nullptr},
+  {"fold_fuse", &PlanOptions::fold_fuse, OPT_REBUILD, nullptr},
+  {"gemm_tile", &PlanOptions::gemm_tile, OPT_REBUILD, nullptr},
+  {"wino2", &PlanOptions::wino2, OPT_REBUILD, nullptr},
+  {"wino_ragged", &PlanOptions::wino_ragged, OPT_REBUILD, nullptr},
+  {"wino_up", &PlanOptions::wino_up, OPT_REBUILD, nullptr},
+  {"train_geom", &PlanOptions::train_geom, OPT_REBUILD, nullptr},
+  {"loss_l2", &PlanOptions::loss_l2, 0, nullptr},
+  {"var_channels", &PlanOptions::var_channels, OPT_REBUILD, check_var_channels},
+  {"attn_heads", &PlanOptions::attn_heads, OPT_REBUILD, check_attn_heads},
+  {"attn_head_dim", &PlanOptions::attn_head_dim, OPT_REBUILD, check_attn_heads},
+};
+
+struct sr3_plan {
+  sr3_unet_desc d;
+  std::vector<sr3_param_info> params;
+  std::map<std::string, int> pindex;
+  size_t param_floats = 0;
+  int F = 0;
+  size_t film_w = 0, film_b = 0;
+  size_t emb_w1 = 0, emb_b1 = 0, emb_w2 = 0, emb_b2 = 0;
+  std::vector<Layer> downs, mid, ups;
+  size_t fin_gn_w = 0, fin_gn_b = 0, fin_w = 0, fin_b = 0;
+  int fin_cin = 0, out_ch = 0;
+  PlanOptions opt;
+  int geo_h = 0, geo_w = 0;  // sr3_plan_set_geometry: image height / width of the next forward (0: image_size)
   hipStream_t side_stream = nullptr;          // fork_side: created at the first forked forward, on the device current then
   std::vector<hipEvent_t> fork_ev, join_ev;   // one pair per forked op of the compiled forward
   ~sr3_plan() {
@@ -255,7 +316,6 @@ struct sr3_plan {
   float* derived_ptr = nullptr;
   size_t derived_bound_bytes = 0;
   const float* derived_from = nullptr;   // the arena sr3_plan_prepare_derived last ran on (null: never / invalidated)
-  int loss_l2 = 0;           // training loss: 0 = L1 (sum), 1 = L2 (sum)  (set_loss, diffusion.py:84-90)
   // compiled forward
   int built_batch = -1;
   int built_cond = -1;
@@ -289,21 +349,36 @@ struct Builder;
 inline int plan_height(const sr3_plan* P) { return P->geo_h > 0 ? P->geo_h : P->d.image_size; }
 inline int plan_width(const sr3_plan* P) { return P->geo_w > 0 ? P->geo_w : P->d.image_size; }
 // heads of an attention level of `channels` channels (plan options attn_heads / attn_head_dim)
-inline int plan_attn_heads(const sr3_plan* P, int channels) { return P->attn_head_dim > 0 ? channels / P->attn_head_dim : P->attn_heads; }
-inline int plan_image_channels(const sr3_plan* P) { return P->out_ch - P->var_channels; }      // channels of x, z, eps of a step
+inline int plan_attn_heads(const sr3_plan* P, int channels) { return P->opt.attn_head_dim > 0 ? channels / P->opt.attn_head_dim : P->opt.attn_heads; }
+inline int plan_image_channels(const sr3_plan* P) { return P->out_ch - P->opt.var_channels; }      // channels of x, z, eps of a step
 // more than 4 output rows exist only as a prediction with its variance head: refused where a launch list is built
 inline int check_out_rows(const sr3_plan* P) {
-  if (P->out_ch > 4 && P->var_channels == 0) { set_error("out_channel %d > 4 unsupported", P->out_ch); return SR3_E_UNSUPPORTED; }
+  if (P->out_ch > 4 && P->opt.var_channels == 0) { set_error("out_channel %d > 4 unsupported", P->out_ch); return SR3_E_UNSUPPORTED; }
   return SR3_OK;
 }
 inline bool plan_native_geometry(const sr3_plan* P) { return plan_height(P) == P->d.image_size && plan_width(P) == P->d.image_size; }
-// replays P->ops over P->regions, or (train) P->tops over P->t_regions
-int run_forward(sr3_plan* P, bool train, const float* x, const float* cond, int cond_channels, const float* level,
-                const int64_t* tstep, const float* freq, const float* level_table, const int* step_dev,
-                const float* params, char* ws, float* eps_out, int B, hipStream_t st, hipEvent_t* ev, hipEvent_t* mid,
-                const DropCfg* drop = nullptr, const StepFuse* fuse = nullptr, const int* t_map = nullptr, bool full_out = false);
-// (full_out: eps_out takes all out_ch rows of the output conv -- the variance head too; the training forward always does)
-// The forward walk in train mode (plan.hip): fills P->tops, P->ttens and P->recs (every activation kept, persistent GroupNorm
+// One forward, as its caller asks for it: the inference entries (plan_abi.hip) and run_train fill it by name; fields named as TrainStep's
+struct ForwardCall {
+  // inputs.  SR3: level, or step_dev indexing level_table; DDPM: tstep, or step_dev (through t_map where given)
+  const float* x = nullptr; const float* cond = nullptr; int cond_channels = 0;
+  const float* level = nullptr; const int64_t* tstep = nullptr; const float* freq = nullptr;
+  const float* level_table = nullptr; const int* step_dev = nullptr; const int* t_map = nullptr;
+  // buffers
+  const float* params = nullptr; void* workspace = nullptr; size_t workspace_bytes = 0;
+  float* eps_out = nullptr; int batch = 0; hipStream_t stream = nullptr;
+  // optional parts: per-op timing (n + 1 events around the ops, one per split-K op), train-mode dropout, the reverse step's tail inside
+  // the output conv, all out_ch rows of the output conv in eps_out (the variance head too), the training plan's forward (P->tops)
+  hipEvent_t* ev = nullptr; hipEvent_t* mid = nullptr; const DropCfg* drop = nullptr; const StepFuse* fuse = nullptr;
+  bool full_out = false, train = false;
+};
+// replays P->ops over P->regions, or (f.train) P->tops over P->t_regions.  A plan whose derived buffer is missing or stale is refused
+// before the first launch
+int run_forward(sr3_plan* P, const ForwardCall& f);
+// ... with a HIP event around every op, then sr3_unet_forward_profile's table (plan_run.hip)
+int profile_forward(sr3_plan* plan, ForwardCall f, int max_ops, float* op_ms, int* op_kind, double* op_flops, int* n_ops);
+int build_structure(sr3_plan* P);                              // plan_build.hip: topology and parameter table of a new plan
+int build_forward(sr3_plan* P, int B, int cond_channels);      // plan_build.hip: the launch list (cached by batch, cond_channels, geometry)
+// The forward walk in train mode (plan_build.hip): fills P->tops, P->ttens and P->recs (every activation kept, persistent GroupNorm
 // tables) and returns what build_train lays the workspace out by
 struct TrainWalk {
   size_t act_high = 0;                               // high-water mark of the activation arena
@@ -317,6 +392,6 @@ bool wino_ragged_wins(const ConvParams& c);
 // Does a conv that lands on the im2col kernel run its 3 x bf16 split instantiation (plan option gemm_split)?  The 9-tap layers
 // with Cout <= 64 (Downsample of the first level) stay on the fp32 MFMA, which is faster there (67 vs 81 us in the forward).  ONE
 // rule for choose_conv (the forward) and choose_dgrad (the data gradients)
-inline int igemm_split_rule(const sr3_plan* P, const ConvParams& c) { return (P->gemm_split && !(c.ksize == 3 && c.Cout <= 64)) ? 1 : 0; }
+inline int igemm_split_rule(const sr3_plan* P, const ConvParams& c) { return (P->opt.gemm_split && !(c.ksize == 3 && c.Cout <= 64)) ? 1 : 0; }
 void layout_derived(sr3_plan* P);
 }  // namespace sr3

@@ -1,4 +1,4 @@
-// Shared by plan.hip (the planner) and abi_ops.hip (the per-op entries): the codec of the public tile_cfg numbers, the shape-only ConvParams.
+// Shared by plan_build.hip (the planner), plan_run.hip / plan_abi.hip (the profile's and the op list's tile numbers) and abi_ops.hip (the per-op entries): the codec of the public tile_cfg numbers, the shape-only ConvParams.
 #pragma once
 #include <string.h>
 #include "sr3_common.h"

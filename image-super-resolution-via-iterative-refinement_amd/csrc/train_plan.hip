@@ -61,19 +61,19 @@ ConvParams dgrad_shape(const ConvParams& f) { return conv_shape(f.B, f.Hs << f.u
 bool dgrad_wino(const sr3_plan* P, ConvParams& g, WinoGeom* wg, bool* split_filters) {
   g.wino_split = 0;
   *split_filters = false;
-  if (!P->winograd || g.ksize != 3) return false;
+  if (!P->opt.winograd || g.ksize != 3) return false;
   // the data gradient has neither a prologue nor dropout, so every 3x3 stride-1 / zero-inserted stride-2 layer with H, W multiples
   // of 16 qualifies (and the four-image 8 x 8 tile); the one-image tile on its 3 x bf16 split instantiation, as the forward
   if (wino_geometry(g, wg)) {
-    *split_filters = P->wino_split && wg->NB == 1;
-    g.wino_split = *split_filters ? (P->wino2 ? 2 : 1) : 0;      // (2: the 8 x 16 tile of conv3x3_wino2.hip)
+    *split_filters = P->opt.wino_split && wg->NB == 1;
+    g.wino_split = *split_filters ? (P->opt.wino2 ? 2 : 1) : 0;      // (2: the 8 x 16 tile of conv3x3_wino2.hip)
     return true;
   }
   // off the native geometry (plan option train_geom): the two-workgroup kernel on the maps that rule refuses, plain where the map is a
   // whole multiple of its 8 x 16 tile, ragged where wino_ragged_wins -- wino_mode's rule for the forward
-  if (!P->train_geom || plan_native_geometry(P) || !P->wino_split || !P->wino2) return false;
+  if (!P->opt.train_geom || plan_native_geometry(P) || !P->opt.wino_split || !P->opt.wino2) return false;
   g.wino_split = wino2_fits(g) ? 2 : 3;
-  if ((g.wino_split == 3 && !(P->wino_ragged && wino_ragged_wins(g))) || !wino_geometry(g, wg)) { g.wino_split = 0; return false; }
+  if ((g.wino_split == 3 && !(P->opt.wino_ragged && wino_ragged_wins(g))) || !wino_geometry(g, wg)) { g.wino_split = 0; return false; }
   *split_filters = true;
   return true;
 }
@@ -101,7 +101,7 @@ void choose_dgrad(const sr3_plan* P, Dgrad& d, size_t wu_cap, size_t slab_cap) {
   // 1x1: the plain GEMM kernel where it fits (plan option gemm2; gemm1x1.hip), its pre-split weights derived from the transposed
   // filters into the region the Winograd data gradients use for theirs
   d.wu = WU_GEMM;
-  if (c.igemm_split && P->gemm2 && gemm1x1_fits(c, 2) && (!(c.Cout & 127) || P->gemm_n64) && wu_bytes(d) <= wu_cap) {
+  if (c.igemm_split && P->opt.gemm2 && gemm1x1_fits(c, 2) && (!(c.Cout & 127) || P->opt.gemm_n64) && wu_bytes(d) <= wu_cap) {
     const int ks = conv_pick(c, 22, 0).ksplit;
     if (ks == 1 || (size_t)ks * c.B * c.Ho * c.Wo * c.Cout * sizeof(float) <= slab_cap) { d.tile = 22; d.ksplit = ks; return; }
   }
@@ -156,7 +156,7 @@ int resolve_backward(sr3_plan* P, int B) {
 
 int build_train(sr3_plan* P, int B, int cond_channels) {
   if (const int rc = check_out_rows(P)) return rc;
-  if (!P->train_geom && !plan_native_geometry(P)) {
+  if (!P->opt.train_geom && !plan_native_geometry(P)) {
     set_error("training runs at image_size x image_size only: the plan's geometry is %d x %d (sr3_plan_set_geometry(plan, 0, 0) restores %d x %d)",
               plan_height(P), plan_width(P), P->d.image_size, P->d.image_size);
     return SR3_E_UNSUPPORTED;
@@ -315,7 +315,7 @@ int dgrad_conv(const Dgrad& d, int stride, int Ho, int Wo, const float* g, const
 int wgrad_call(const TrainCtx& X, ConvParams c, const float* src0, const float* src1, const float* dy, float* dw) {
   WgradParams wp;
   c.src0 = src0; c.src1 = src1;
-  c.wgrad_split = X.P->wgrad_split;
+  c.wgrad_split = X.P->opt.wgrad_split;
   wp.c = c;
   wp.dy = dy;
   wp.dw = dw;
@@ -344,8 +344,9 @@ int run_train(sr3_plan* P, const TrainStep& t) {
   DropCfg dc;
   dc.seed = t.dropout_seed;
   dropout_consts(t.dropout_p, &dc.thresh, &dc.scale);
-  rc = run_forward(P, true, x_noisy, t.cond, t.cond_channels, t.level, t.tstep, t.freq, nullptr, nullptr, params, ws, eps, B, st, nullptr,
-                   nullptr, &dc);
+  const ForwardCall fwd = {.x = x_noisy, .cond = t.cond, .cond_channels = t.cond_channels, .level = t.level, .tstep = t.tstep, .freq = t.freq,
+                           .params = params, .workspace = ws, .eps_out = eps, .batch = B, .stream = st, .drop = &dc, .train = true};
+  rc = run_forward(P, fwd);
   if (rc) return rc;
   // ---- loss and its gradient (NHWC, channel dim padded to 4) ----
   float* geps = X.at<float>(P->t_geps_off);
@@ -389,7 +390,7 @@ int run_train(sr3_plan* P, const TrainStep& t) {
       // bias (3 of the 4 padded columns are real -- 6 of 8 with a variance head; arena slots are 4-float aligned)
       rc = colsums(geps, B, S2, OUT_PAD, part, grads + s.bias, nullptr, 0, st);
       if (rc) return rc;
-      rc = dgrad_conv(r.dx, 1, r.dw.Ho, r.dw.Wo, geps, params + s.w, P->out_ch, dA, X.dgrad_bufs(), P->launch_gemm_epi(), st);
+      rc = dgrad_conv(r.dx, 1, r.dw.Ho, r.dw.Wo, geps, params + s.w, P->out_ch, dA, X.dgrad_bufs(), P->opt.launch_gemm_epi(), st);
       if (rc) return rc;
       rc = act_bwd(dA, X.act(s.x0), nullptr, C, 0, B, S2, X.at<float>(P->t_regions.ss_off + r.ss_off),
                    X.at<float>(P->t_regions.mr_off + r.mr_off), G, s.act, params + r.gamma, part, gs, grads + r.gamma,
@@ -446,7 +447,7 @@ int run_train(sr3_plan* P, const TrainStep& t) {
       // 3. fused res_conv segment
       if (has_q) {
         float* dq = X.at<float>(P->t_dq_off);
-        rc = dgrad_conv(r.dq, 1, Ho, Wo, g, params + s.qw, Cout, dq, X.dgrad_bufs(), P->launch_gemm_epi(), st);
+        rc = dgrad_conv(r.dq, 1, Ho, Wo, g, params + s.qw, Cout, dq, X.dgrad_bufs(), P->opt.launch_gemm_epi(), st);
         if (rc) return rc;
         rc = grad_route(dq, r.dqw.C0, r.dqw.C1, B, Ho, Wo, 0, X.grad(s.q0), X.grad(s.q1), st, r.acc_q0, r.acc_q1);
         if (rc) return rc;
@@ -454,7 +455,7 @@ int run_train(sr3_plan* P, const TrainStep& t) {
         if (rc) return rc;
       }
       // 4. main segment: data gradient
-      rc = dgrad_conv(r.dx, s.stride, Ho, Wo, g, params + s.w, Cout, dA, X.dgrad_bufs(), P->launch_gemm_epi(), st);
+      rc = dgrad_conv(r.dx, s.stride, Ho, Wo, g, params + s.w, Cout, dA, X.dgrad_bufs(), P->opt.launch_gemm_epi(), st);
       if (rc) return rc;
       if (s.act) {
         const bool dropped = s.drop_key >= 0 && dc.thresh != 0;
@@ -576,7 +577,7 @@ int sr3_conv_dgrad_f32(sr3_plan* plan, const float* dy, const float* w_ohwi, int
   if (tile_out) *tile_out = tile_encode(pk.tile, d.c.wino_split, d.c.igemm_split, false);
   if (ksplit_out) *ksplit_out = pk.ksplit;
   if (derived_kind_out) *derived_kind_out = d.wu;
-  return dgrad_conv(d, stride, f.Ho, f.Wo, dy, w_ohwi, Cout_w, dA, bufs, plan->launch_gemm_epi(), static_cast<hipStream_t>(stream));
+  return dgrad_conv(d, stride, f.Ho, f.Wo, dy, w_ohwi, Cout_w, dA, bufs, plan->opt.launch_gemm_epi(), static_cast<hipStream_t>(stream));
 }
 
 size_t sr3_train_workspace_bytes(sr3_plan* plan, int batch, int cond_channels) {
@@ -621,14 +622,14 @@ static int train_step_checked(const char* who, sr3_plan* plan, TrainStep t, Trai
   } else {
     t.pi = PerImage();
   }
-  if (form == TRAIN_EX3 && plan->var_channels == 0) obj.hyb = nullptr;      // no variance head: sr3_train_step_ex's objective; the rows serve the terms alone
-  if ((plan->var_channels > 0) != (obj.hyb != nullptr)) {
-    set_error("%s: the plan's variance rows (var_channels %d) and step_scalars go together (sr3_train_step_ex2 trains them)", who, plan->var_channels);
+  if (form == TRAIN_EX3 && plan->opt.var_channels == 0) obj.hyb = nullptr;      // no variance head: sr3_train_step_ex's objective; the rows serve the terms alone
+  if ((plan->opt.var_channels > 0) != (obj.hyb != nullptr)) {
+    set_error("%s: the plan's variance rows (var_channels %d) and step_scalars go together (sr3_train_step_ex2 trains them)", who, plan->opt.var_channels);
     return SR3_E_BADARG;
   }
   if (obj.hyb && !(isfinite(obj.lambda) && obj.lambda >= 0.f)) { set_error("%s: vlb_lambda %g must be finite and >= 0", who, (double)obj.lambda); return SR3_E_BADARG; }
   if (!obj.hyb) obj.vlb_w = nullptr;      // (a plan without a variance head has no L_vlb to weight)
-  if (obj.kind < 0) obj.kind = plan->loss_l2 != 0 ? LOSS_L2 : LOSS_L1;      // -1: the plan's loss_l2
+  if (obj.kind < 0) obj.kind = plan->opt.loss_l2 != 0 ? LOSS_L2 : LOSS_L1;      // -1: the plan's loss_l2
   if (!t.mark_offsets || !t.mark_events) t.n_marks = 0;
   return run_train(plan, t);
 }

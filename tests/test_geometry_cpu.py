@@ -18,7 +18,7 @@ B = 16
 
 
 def ragged_rule(h, w):
-    """The committed rule of wino_mode / wino_ragged_wins (what choose_conv asks first: csrc/plan.hip) for a 3x3 stride-1 conv
+    """The committed rule of wino_mode / wino_ragged_wins (what choose_conv asks first: csrc/plan_build.hip) for a 3x3 stride-1 conv
     on an h x w map of a plan that is NOT at its native geometry: which tile it must be reported on."""
     if w % 16 == 0 and h % 16 == 0:
         return (13,)                  # the tiles of today's rules
