@@ -11,7 +11,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
 if [ "${1:-}" = "--clean" ]; then rm -rf "$BUILD"; shift; fi
 mkdir -p "$BUILD"
-SRCS="conv_igemm conv_dispatch gemm1x1 conv3x3_halo conv3x3_wino conv3x3_wino2 small_kernels attention attention_long attention_heads plan_build plan_run plan_abi abi_ops tiled consistency backproject guidance selfcond cond_augment learned_var vlb_eval distill train_kernels train_small wgrad attention_bwd train_plan optim io_metrics resize degrade"
+SRCS="conv_igemm conv_dispatch gemm1x1 conv3x3_halo conv3x3_wino conv3x3_wino2 small_kernels attention attention_long attention_heads plan_build plan_run plan_abi abi_ops tiled consistency restore backproject guidance selfcond cond_augment learned_var vlb_eval distill train_kernels train_small wgrad attention_bwd train_plan optim io_metrics resize degrade"
 pids=()
 for f in $SRCS; do
   o=$BUILD/$f.o

@@ -159,11 +159,28 @@ class DDPM(BaseModel):
             return None
         return lr
 
+    def _restore_target(self):
+        """Under the "restore" key: the batch's own target -- (data['known'], data['mask']) for the mask operator, data['gray'] for the
+        gray operator -- or None (the gray operator's default; the mask operator then says what it needs) when the key is off or the
+        batch carries none."""
+        rs = getattr(self.netG, 'restore', None)
+        data = getattr(self, 'data', None)
+        data = data if isinstance(data, dict) else {}
+        if rs is None:
+            return None
+        if rs['operator'] == 'mask':
+            known, mask = data.get('known'), data.get('mask')
+            return (known, mask) if torch.is_tensor(known) and torch.is_tensor(mask) else None
+        gray = data.get('gray')
+        return gray if torch.is_tensor(gray) else None
+
     def test(self, continous=False):
         self.netG.eval()
         with torch.no_grad(), self._sampling_weights():
             wave = self.data.get('_dp_wave') if isinstance(self.data, dict) else None
-            if wave is not None:
+            if getattr(self.netG, 'restore', None) is not None:      # (a restoring chain runs on the batch as it was fed)
+                self.SR = self.netG.super_resolution(self.data['SR'], continous, restore_target=self._restore_target())
+            elif wave is not None:
                 # the validation loader groups consecutive items into waves (sr3_hip.dist.ValWave): the chains of a wave run once,
                 # a rank's items as one batch (and, data parallel, dealt over the ranks); every caller gets its item's image back
                 self.SR = wave.result(self.netG, self.data['_dp_pos'], continous)
@@ -187,7 +204,9 @@ class DDPM(BaseModel):
     def sample(self, batch_size=1, continous=False):
         self.netG.eval()
         with torch.no_grad(), self._sampling_weights():
-            if _dist.dp_active():
+            if getattr(self.netG, 'restore', None) is not None:
+                self.SR = self.netG.sample(batch_size, continous, restore_target=self._restore_target())
+            elif _dist.dp_active():
                 if self._sam_wave is None:
                     self._sam_wave = _dist.SampleWave()
                 self.SR = self._sam_wave.next(self.netG, batch_size, continous)

@@ -40,7 +40,8 @@ respaced walk -- q_sample at the step (sr3_q_sample_step_f32), one inference-mod
 or SR3 under learned_variance.
 
 The samplers' and the objective's tables (`set_sampler`, `set_prediction` / `set_objective`) are sr3_hip/schedules.py, the tile layout
-(`set_tiling`) sr3_hip/tiling.py, the rules on x0 (`set_consistency`, `set_guidance`, `set_backprojection`) sr3_hip/x0_rules.py.
+(`set_tiling`) sr3_hip/tiling.py, the rules on x0 (`set_consistency`, `set_guidance`, `set_backprojection`, `set_restore`)
+sr3_hip/x0_rules.py.
 """
 import collections
 import ctypes as C
@@ -56,6 +57,7 @@ from . import tiling as TL
 from . import x0_rules as X
 from .x0_rules import (BACKPROJECTION_KEYS, CONSISTENCY_BLOCKS, RESAMPLES, THRESHOLDS, backprojection_error, block_means,      # noqa: F401
                        quantile_rank, resample_f32, resample_tables)                                                          # (their old home)
+from .x0_rules import gray_f32, gray_weights, restore_error, travel_tables, travel_walk                                      # noqa: F401
 from .schedules import (COND_AUGMENT_KEYS, LEARNED_VARIANCE_LAMBDA, LOSS_TYPES, LOSS_WEIGHTS, PREDICTIONS, SAMPLER_KINDS,     # noqa: F401
                         SELF_CONDITION_PROB, WALKS, _BUFFERS, _SAMPLER_TABLES, _check_prediction, _check_sampler_kind, _positive,
                         ancestral_tables, cond_level_coefs, hybrid_step_scalars, loss_weights, make_beta_schedule, parse_cond_augment,
@@ -88,6 +90,7 @@ class EngineDiffusion(nn.Module):
         self.consistency = None        # None: the network's x0 as it is; else {'block': r, 'strength': s} (set_consistency)
         self.guidance = None           # None: one forward, the fused tail; else {'scale': w, 'threshold': mode, 'percentile': p} (set_guidance)
         self.backprojection = None     # None: the network's x0 as it is; else {'scale': s, 'iterations': K, 'strength': l, 'resample': f} (set_backprojection)
+        self.restore = None            # None: the network's x0 as it is; else {'operator', 'strength', 'weights', 'pinv', 'travel'} (set_restore)
         self.cond_drop = 0.0           # training: the probability that an image's conditioning is replaced by zeros (set_cond_drop)
         self._cond_drop_buf = None     # ... and the buffer the dropped conditioning is written to
         self.self_condition = None     # None: off; else {'prob': p}: the network reads its own last x0 as extra input channels (set_self_condition)
@@ -285,8 +288,23 @@ class EngineDiffusion(nn.Module):
         not a projection: the LR residual shrinks with every round and does not vanish."""
         self._set_rule(X.BACKPROJECTION, scale, iterations, strength, resample)
 
+    def set_restore(self, operator=None, strength=1.0, weights='mean', travel=None):
+        """Zero-shot restoration with a trained model: every reverse step projects the predicted x0 onto what is known of the image
+        before the posterior mix (the range / null-space step of DDNM; sr3_restore_step) -- or, operator None, go back to the network's
+        x0 as it is.  operator 'mask' (inpainting, outpainting, a trusted patch): x0' = w y + (1 - w) x0 with w = strength * mask, towards
+        `restore_target=(known, mask)` of p_sample_loop / super_resolution / sample -- the known image [B, C, H, W] and a mask [B, 1 or
+        C, H, W] in [0, 1], 1 = known; with a hard mask and strength 1 the result's known pixels are the known image's, bit for bit.
+        operator 'gray' (colourisation): x0'_c = x0_c + strength * p_c (y - a . x0), a = `weights` ('mean', 'rec601' or a list of
+        `channels` <= 4 numbers), p = a / |a|^2, towards `restore_target=` a gray image [B, 1, H, W] or a colour image (reduced with
+        `gray_f32`); on a conditional model the default is the conditioning image's gray.  strength in (0, 1].  travel = {'length': l,
+        'repeats': r}: the resampled walk (RePaint's jumps, DDNM's time travel) -- every segment of l step indices runs r times, and
+        between two runs the chain is diffused back up to the segment's top (sr3_travel_back_f32): S r forwards for S steps.  Runs under
+        the ancestral loop and DDIM, on the DDPM variant too.  Not built (NotImplementedError): with tiling, another rule on x0,
+        self-conditioning or the learned-variance ancestral sampler; travel under dpmpp_2m."""
+        self._set_rule(X.RESTORE, operator, strength, weights, travel)
+
     def _set_rule(self, rule, *args):
-        """the body of set_consistency / set_guidance / set_backprojection: the rule's validation, the compatibility check, the attribute"""
+        """the body of set_consistency / set_guidance / set_backprojection / set_restore: the rule's validation, the compatibility check, the attribute"""
         cfg = rule.validate(self, *args)
         if cfg is not None:
             self._check_settings(**{rule.name: cfg})
@@ -462,6 +480,20 @@ class EngineDiffusion(nn.Module):
                                       'set_self_condition(None))')
         for r in X.RULES:                      # "X with tiling", "X with Y", "X of the DDPM variant under a sampler"
             X.check_rule(r, s, ddpm_sampler, tiling)
+        rs = s['restore']
+        if rs is not None:
+            off = 'switch restore off (set_restore(None))'
+            if rs['travel'] is not None and s['sampler'] == 'dpmpp_2m':
+                raise NotImplementedError('restore travel under dpmpp_2m: the multistep history is the x0 of a step the chain has jumped '
+                                          'away from, stale after every jump; sample with {"type": "ddim"} (set_sampler), drop "travel" or %s' % off)
+            if selfc:
+                raise NotImplementedError('restore with self-conditioning: the x0 fed back is the network\'s own, taken in front of the '
+                                          'projection, and no model was measured with the two together; switch one of them off '
+                                          '(set_restore(None) / set_self_condition(None))')
+            if ddpm_sampler and self.learned_variance is not None:
+                raise NotImplementedError('restore of a learned-variance DDPM model under a sampler: sr3_unet_forward_full stores the '
+                                          'variance rows too, which sr3_restore_step does not read; use the ancestral loop of a '
+                                          'fixed-variance model or %s' % off)
         if before is not None and before[0] == 'self_condition':
             before[1]()
         if selfc:
@@ -588,21 +620,22 @@ class EngineDiffusion(nn.Module):
         return new
 
     def _loop_state(self, shape, cond_shape, dev, item_streams=False, tiles=None, consistency=None, guidance=None, backprojection=None,
-                    self_condition=False, cond_augment=False):
+                    self_condition=False, cond_augment=False, restore=None):
         # the buffers of a chain, a workspace private to the state and the captured graph, under a key of everything the graph bakes in.
         # item_streams: one torch generator per image of the batch (`item_seeds` of p_sample_loop) -- the generators are
         # registered with the captured graph, so they belong to the state and are re-seeded per loop
-        cfgs = dict(consistency=consistency, guidance=guidance, backprojection=backprojection)
+        cfgs = dict(consistency=consistency, guidance=guidance, backprojection=backprojection, restore=restore)
         key = (tuple(shape), None if cond_shape is None else tuple(cond_shape), *self._cache_env(dev), bool(item_streams),
                None if self.sampler is None else (self.sampler['steps'], self.sampler['eta'], self.sampler['type'],
                                                   self.sampler.get('walk', 'time') if isinstance(self.sampler.get('walk', 'time'), str)
                                                   else tuple(self.sampler['walk'])),
-               *[r.key(cfgs[r.name]) for r in reversed(X.RULES)],      # back-projection, guidance, consistency
+               *[r.key(cfgs[r.name]) for r in reversed(X.RULES) if not r.key_appended],      # back-projection, guidance, consistency
                None if tiles is None else tiles['key'])      # tiled loop: ((tile_h, tile_w), overlap, tile_batch); the geometry is the tile's
         if self_condition:                     # (appended, so that a plain model's key stays what it was)
             key += ('self_condition',)
         if cond_augment:                       # (appended too: the state's cond is the augmented tensor, made once per chain)
             key += ('cond_augment',)
+        key += tuple(r.key(cfgs[r.name]) for r in X.RULES if r.key_appended and cfgs[r.name] is not None)      # (and a later rule's)
         st = self._cached(key)
         if st is not None:
             return st
@@ -731,11 +764,13 @@ class EngineDiffusion(nn.Module):
         output in st['eps'] (level / timestep from the device counter, which only the tail's last kernel moves), then the rule's tail
         on the whole image in place of the fused one: what it does to x0, the p_sample update and the counter decrement."""
         tables, level, t_map, c3, _ = rule
-        assert t_map is None and st.get('grid') is None      # (_check_settings refused both)
+        assert (t_map is None or x0_rule.takes_t_map) and st.get('grid') is None      # (_check_settings refused both)
         img = st['img']
+        # a sampler's walk on the DDPM variant: sr3_unet_forward_full, the plain forward without a variance head, takes the map
+        kw = {} if t_map is None else dict(full=True, t_map=t_map)
 
         def forward(cond, out):
-            self.denoise_fn(img, None, cond=cond, level_table=level, step_dev=st['step'][1:], out=out, ws=st['ws'])
+            self.denoise_fn(img, None, cond=cond, level_table=level, step_dev=st['step'][1:], out=out, ws=st['ws'], **kw)
         forward(st['cond'], st['eps'])
         x0_rule.tail(st, st[x0_rule.name], z, tables, c3, hist, forward)
 
@@ -847,20 +882,23 @@ class EngineDiffusion(nn.Module):
 
     @torch.no_grad()
     def p_sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None, consistency_target=None,
-                      backprojection_target=None, cond_noise=None):
+                      backprojection_target=None, cond_noise=None, restore_target=None):
         """The reverse loop (`_sample_loop`); with tiling set (set_tiling / the "tiling" key) an input larger than the tile on either axis
         goes through the tiled loop instead.  consistency_target: under set_consistency, the [B, C, H / block, W / block] block means to
         steer towards instead of the conditioning image's (the dataset's real LR image when block is the scale factor).
         backprojection_target: under set_backprojection, the [B, C, H / scale, W / scale] LR image, in the model's range, to steer
         towards instead of the down-sampled conditioning image (the dataset's real LR image).  cond_noise: under set_cond_augment, the
-        noise added to the conditioning image at sample_level, injected instead of drawn."""
+        noise added to the conditioning image at sample_level, injected instead of drawn.  restore_target: under set_restore, the pair
+        (known, mask) of the mask operator, or the gray operator's gray image [B, 1, H, W] (a colour image [B, C, H, W] is reduced
+        first) instead of the conditioning image's gray."""
         t = self.tiling
         if t is not None:
             shape = tuple(x_in) if not self.conditional else tuple(x_in.shape)
             if not (len(shape) == 4 and (shape[2] > t['tile'][0] or shape[3] > t['tile'][1])):
                 t = None                       # (an input the tile covers takes the whole-image loop)
         return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, tiling=t,
-                                 consistency_target=consistency_target, backprojection_target=backprojection_target, cond_noise=cond_noise)
+                                 consistency_target=consistency_target, backprojection_target=backprojection_target, cond_noise=cond_noise,
+                                 restore_target=restore_target)
 
     @torch.no_grad()
     def p_sample_loop_tiled(self, x_in, continous=False, *, tile, overlap, tile_batch=None, x_T=None, noise_seq=None, item_seeds=None,
@@ -875,7 +913,7 @@ class EngineDiffusion(nn.Module):
         return self._sample_loop(x_in, continous, x_T=x_T, noise_seq=noise_seq, item_seeds=item_seeds, tiling=t, cond_noise=cond_noise)
 
     def _sample_loop(self, x_in, continous=False, *, x_T=None, noise_seq=None, item_seeds=None, tiling=None, consistency_target=None,
-                     backprojection_target=None, cond_noise=None):
+                     backprojection_target=None, cond_noise=None, restore_target=None):
         """sr3 diffusion.py:176-200 / ddpm :200-230.  Extensions: `x_T` injects the initial draw, `noise_seq[i]` the noise
         consumed at step i (the parity tests); `item_seeds` (one int per image of the batch) gives every image its own noise
         stream -- x_T and every step's z of image i come from a generator seeded with item_seeds[i], so the image's chain does
@@ -886,9 +924,9 @@ class EngineDiffusion(nn.Module):
         cond is built once per chain, after x_T is drawn, from the clean conditioning image at sample_level (sr3_cond_augment_f32; the
         noise from the chain's own source -- the per-item generators, torch.randn, or `cond_noise`); the first snapshot and the rules'
         targets are the clean image's.  Three parts: `_sample_shape` checks and sizes, `_begin_chain` fills the state, `_run_steps`
-        runs it."""
+        runs it -- once, or under set_restore's travel once per pass of the travelled walk (`_run_travel`)."""
         cfgs = {r.name: getattr(self, r.name) for r in X.RULES}
-        targets = dict(consistency=consistency_target, backprojection=backprojection_target)
+        targets = dict(consistency=consistency_target, backprojection=backprojection_target, restore=restore_target)
         cond, shape, cond_shape, tiles, item_seeds = self._sample_shape(x_in, cfgs, targets, tiling, noise_seq, item_seeds, cond_noise)
         dev, selfc, aug = self.betas.device, self.self_condition is not None, self.cond_augment
         T = self.num_timesteps if self.sampler is None else self.sampler['steps']      # iterations of the loop
@@ -906,10 +944,30 @@ class EngineDiffusion(nn.Module):
                 ret[k[0] * B:(k[0] + 1) * B].copy_(st['img'])
                 k[0] += 1
         z_of = None if noise_seq is None else (lambda i: noise_seq[i] if i > 0 or self.variant == 'ddpm' else None)
-        self._run_steps(st, T, self._one_step, z_of, snapshot, progress=self.show_progress)
+        if cfgs['restore'] is not None and cfgs['restore']['travel'] is not None:
+            self._run_travel(st, T, cfgs['restore'], snapshot)
+        else:
+            self._run_steps(st, T, self._one_step, z_of, snapshot, progress=self.show_progress)
         if (not self.conditional) and self.variant == 'ddpm':
             return st['img'].clone()            # ddpm diffusion.py:215 returns img, ignoring `continous`
         return ret if continous else ret[-1]
+
+    def _run_travel(self, st, T, cfg, snapshot):
+        """The travelled walk of set_restore (x0_rules.travel_walk): every pass is `_run_steps` on the state's one captured step graph;
+        where a pass does not start at the counter the one before it ended on, the chain is diffused back up first -- z drawn eagerly
+        from the chain's own source (the default generator, or the per-item generators), then one sr3_travel_back_f32 launch, which
+        moves the device counter up to the pass's top.  abar of the step indices: alphas_cumprod for the ancestral loop, the sampler's
+        own walk under a sampler.  A snapshot is taken on an index's last visit only."""
+        abar = self._alphas_cumprod64 if self.sampler is None else self._alphas_cumprod64[self._sampler_tau.cpu().numpy()]
+        walk = X.RESTORE.travel_state(st, cfg, T, abar, st['img'].device)
+        at = T - 1
+        for k, (top, n) in enumerate(walk):
+            if top != at:
+                self._draw(st['z'], st['gens'])
+                X.RESTORE.jump(st, T)
+            last = all(t != top for t, _ in walk[k + 1:])
+            self._run_steps(st, n, self._one_step, None, (lambda i, b=top - n + 1: snapshot(b + i)) if last else None)
+            at = top - n
 
     def _sample_shape(self, x_in, cfgs, targets, tiling, noise_seq, item_seeds, cond_noise):
         """The first part of `_sample_loop`: everything is validated here, before anything is written -- the targets, the settings against
@@ -923,9 +981,13 @@ class EngineDiffusion(nn.Module):
 
         def own():                            # (the loop's own refusals stand in front of the last clause, as they always have)
             for r in X.RULES:
-                if cfgs[r.name] is not None and r.target_kw is not None and not self.conditional and targets[r.name] is None:
-                    raise NotImplementedError('%s on an unconditional model needs %s=: there is no conditioning image to %s'
-                                              % (r.noun, r.target_kw, r.target_from))
+                if cfgs[r.name] is not None and r.target_kw is not None and targets[r.name] is None:
+                    why = r.missing_target(cfgs[r.name], self.conditional)
+                    if why is not None:
+                        raise NotImplementedError(why)
+            if noise_seq is not None and cfgs['restore'] is not None and cfgs['restore']['travel'] is not None:
+                raise L.Sr3Error('p_sample_loop: noise_seq with restore travel: a step index is visited more than once, so one noise '
+                                 'per index does not say what each visit draws; use item_seeds')
             if cond_noise is not None and aug is None:
                 raise ValueError('cond_noise is given but noise conditioning augmentation is off (set_cond_augment / the "cond_augment" key)')
             if dev.type != 'cuda':
@@ -1016,14 +1078,15 @@ class EngineDiffusion(nn.Module):
                                               dst.shape[1], 0, B, Cl, H, W, self._stream(dev)))
 
     @torch.no_grad()
-    def sample(self, batch_size=1, continous=False, *, item_seeds=None):
-        return self.p_sample_loop((batch_size, self.channels, self.image_size, self.image_size), continous, item_seeds=item_seeds)
+    def sample(self, batch_size=1, continous=False, *, item_seeds=None, restore_target=None):
+        return self.p_sample_loop((batch_size, self.channels, self.image_size, self.image_size), continous, item_seeds=item_seeds,
+                                  restore_target=restore_target)
 
     @torch.no_grad()
     def super_resolution(self, x_in, continous=False, *, item_seeds=None, consistency_target=None, backprojection_target=None,
-                         cond_noise=None):
+                         cond_noise=None, restore_target=None):
         return self.p_sample_loop(x_in, continous, item_seeds=item_seeds, consistency_target=consistency_target,
-                                  backprojection_target=backprojection_target, cond_noise=cond_noise)
+                                  backprojection_target=backprojection_target, cond_noise=cond_noise, restore_target=restore_target)
 
     # ---- the variational bound by timestep ----------------------------------------------------------
     def _bpd_state(self, shape, cond_shape, dev, S, clip, item_streams):

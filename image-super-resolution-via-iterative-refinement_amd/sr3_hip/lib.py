@@ -103,6 +103,9 @@ SIGNATURES = {
     'sr3_tiled_step_hist': (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     'sr3_block_mean_f32': (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     'sr3_consistent_step': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    'sr3_gray_f32': (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    'sr3_restore_step': (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    'sr3_travel_back_f32': (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P]),
     'sr3_resample_f32': (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
     'sr3_backproject_scratch_bytes': (_Z, [_I, _I, _I, _I, _I]),
     'sr3_backproject_step': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _I,

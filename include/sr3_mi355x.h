@@ -457,6 +457,57 @@ int sr3_consistent_step(float* x_nchw, const float* eps_nchw, const float* z_nch
                         const float* tab_c2, const float* tab_sigma, int* step2_dev, int clip_denoised, const float* tab_c3,
                         float* hist_nchw, void* stream);
 
+/* ---- zero-shot restoration (engine extension; no reference counterpart) --------------------------
+ * Inpainting and colourisation with a trained model and no training (RePaint, Lugmayr et al. 2022; DDNM, Wang et al. 2022): the range /
+ * null-space projection of the predicted x0 for a pixel mask or a channel sum, in the tail of a reverse step, and the forward jump of
+ * the resampled walk.  Every entry checks its arguments on the host, names the offending one in sr3_last_error and launches nothing on
+ * a refusal; everything a call writes is checked against every other argument.  No host synchronisation, no allocation: capturable.
+ * Any alignment (width % 4 != 0 -- elems_per_image % 4 != 0 for the jump -- or a pointer off a 16-byte boundary takes the
+ * one-element-per-thread form, the same bits).  Every fp32 product, sum and difference is rounded separately, in the order written:
+ * bitwise reproducible, and bit-identical to the same expression in IEEE fp32 anywhere. */
+
+/* dst_nchw[b, 0, y, x] = ((a0 src[b, 0, y, x] + a1 src[b, 1, y, x]) + a2 src[b, 2, y, x]) + a3 src[b, 3, y, x] over the `channels` <= 4
+ * planes of src_nchw [batch, channels, height, width]; gray_a_host: `channels` floats on the HOST, read during the call.  What the
+ * gray operator's target is made with from a colour image, and what measures a result's error.  One launch.
+ * SR3_E_BADARG: NULL pointer, non-positive size, channels > 4, a weight that is not finite, dst_nchw overlapping src_nchw;
+ * SR3_E_UNSUPPORTED: batch * channels * height * width >= 2^31. */
+int sr3_gray_f32(const float* src_nchw, int batch, int channels, int height, int width, const float* gray_a_host, float* dst_nchw,
+                 void* stream);
+
+/* The tail of one restoring reverse step, in place on x_nchw [batch, channels, height, width], with j = step2_dev[1] on entry and
+ * l = strength:
+ *   x0 = a[j] x - b[j] eps ; clamp(-1, 1) if clip_denoised                    (clamp first, then project, as sr3_consistent_step)
+ *   op 0 (mask):  w = l m ;  x0' = (w y) + ((1 - w) x0)                        y = target [batch, channels, height, width] the known image,
+ *                 m = mask [batch, mask_channels, height, width], mask_channels 1 (one plane for all channels) or channels, values
+ *                 in [0, 1], 1 = known.  The lerp form: w = 1 gives y exactly, w = 0 gives x0 exactly.
+ *   op 1 (gray):  g = ((a0 x0_0 + a1 x0_1) + a2 x0_2) + a3 x0_3 ;  r = y - g ;  x0'_c = x0_c + ((l p[c]) r)
+ *                 y = target [batch, 1, height, width]; a = gray_a_host, p = gray_p_host = a / sum a^2 (the pseudo-inverse; the host
+ *                 computes it in double and rounds once): `channels` <= 4 floats each on the HOST, read during the call and handed
+ *                 to the kernel by value.  mask / mask_channels are not read.
+ *   x  = ((c1[j] x0' + c2[j] x) + c3[j] hist) + sigma[j] z ; hist <- x0'       (sr3_p_sample_step_hist's operations and association;
+ *                                                                              tab_c3 / hist_nchw both NULL: no history term)
+ * step2_dev[1] = j - 1 on completion (step2_dev[0] is scratch, as in sr3_tiled_step).  eps_nchw is the network's output for this step;
+ * z_nchw: the step's noise or NULL (= 0); tab_*: as sr3_reverse_step.  Two launches.
+ * SR3_E_BADARG (the message names the argument): NULL required pointer (op 0: mask; op 1: the weights), op not 0 or 1, non-positive
+ * size, mask_channels not 1 or channels (op 0), channels > 4 (op 1), strength NaN or outside (0, 1], only one of tab_c3 / hist_nchw,
+ * hist_nchw overlapping x_nchw or eps_nchw, anything written (x_nchw, hist_nchw, step2_dev) overlapping another argument, a weight that
+ * is not finite; SR3_E_UNSUPPORTED: batch * channels * height * width >= 2^31. */
+int sr3_restore_step(float* x_nchw, const float* eps_nchw, const float* z_nchw, int op, const float* target, const float* mask,
+                     int mask_channels, const float* gray_a_host, const float* gray_p_host, int batch, int channels, int height,
+                     int width, float strength, const float* tab_a, const float* tab_b, const float* tab_c1, const float* tab_c2,
+                     const float* tab_sigma, int* step2_dev, int clip_denoised, const float* tab_c3, float* hist_nchw, void* stream);
+
+/* The jump of a resampled walk (RePaint's "jump", DDNM's "time travel"): with c = step2_dev[1] on entry, c in [-1, rows - 2], and
+ * r = c + 1, every one of the batch * elems_per_image values becomes  x = (ra[r] x) + (rs[r] z)  and step2_dev[1] = to[r]: the chain
+ * is diffused forward from the level of counter c to that of counter to[r] > c (ra = sqrt(abar(to) / abar(c)), rs = sqrt(1 - ra^2),
+ * the host's, in double, rounded once).  tab_ra / tab_rs (float) and tab_to (int): `rows` entries each on the device; a row at which
+ * no jump is defined holds ra = 1, rs = 0, to = c, so a launch there changes nothing; a counter outside [-1, rows - 2] touches
+ * nothing at all.  z is required.  step2_dev[0] is scratch.  Two launches.
+ * SR3_E_BADARG: NULL pointer, non-positive rows / batch / elems_per_image, x or step2_dev overlapping another argument;
+ * SR3_E_UNSUPPORTED: batch * elems_per_image >= 2^31. */
+int sr3_travel_back_f32(float* x, const float* z, const float* tab_ra, const float* tab_rs, const int* tab_to, int rows, int* step2_dev,
+                        int batch, int elems_per_image, void* stream);
+
 /* ---- back-projection sampling (engine extension; no reference counterpart) -----------------------
  * Iterative back-projection (Irani & Peleg 1991; the low-pass swap of ILVR, Choi et al. 2021, applied to x0) in the tail of a reverse
  * step, under the resize the datasets are made with: Pillow's antialiased bicubic / bilinear resample, as fp32 planes.  A resample of
