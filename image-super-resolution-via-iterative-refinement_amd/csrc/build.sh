@@ -15,7 +15,7 @@ SRCS="conv_igemm conv_dispatch gemm1x1 conv3x3_halo conv3x3_wino conv3x3_wino2 s
 pids=()
 for f in $SRCS; do
   o=$BUILD/$f.o
-  if [ ! -f $o ] || [ $f.hip -nt $o ] || [ sr3_common.h -nt $o ] || [ train.h -nt $o ] || [ plan_internal.h -nt $o ] || [ tile_code.h -nt $o ] || [ attention_core.h -nt $o ] || [ step_tail.h -nt $o ] || [ ../../include/sr3_mi355x.h -nt $o ] || [ ../../include/sr3_io_mi355x.h -nt $o ]; then
+  if [ ! -f $o ] || [ $f.hip -nt $o ] || [ sr3_common.h -nt $o ] || [ train.h -nt $o ] || [ plan_internal.h -nt $o ] || [ tile_code.h -nt $o ] || [ attention_core.h -nt $o ] || [ step_tail.h -nt $o ] || [ conv_prologue.h -nt $o ] || [ wino_common.h -nt $o ] || [ ../../include/sr3_mi355x.h -nt $o ] || [ ../../include/sr3_io_mi355x.h -nt $o ]; then
     $HIPCC $FLAGS "$@" -c $f.hip -o $o &
     pids+=($!)
   fi

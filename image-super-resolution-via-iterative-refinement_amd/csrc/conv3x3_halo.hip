@@ -27,12 +27,10 @@
 
 #include <type_traits>
 
+#include "conv_prologue.h"
 #include "sr3_common.h"
 
 namespace sr3 {
-
-__device__ __forceinline__ float silu_h(float v) { return SR3_SILU(v); }
-
 
 // MODE 0: exact-fp32 MFMA (v_mfma_f32_32x32x2_f32).  MODE 1 (opt-in, experimental): every fp32 operand is
 // split into three bf16 terms in the staging step and each product is evaluated as the six bf16 MFMA products
@@ -136,6 +134,7 @@ void k_conv3x3_halo(const ConvParams p, const HaloGeom g) {
     cur_c = c;
     cur_act = seg2 ? 0 : p.act;
     const int ce = hvalid ? c : 0;
+    // mirrors concat_quad of conv_prologue.h, over the segment's pair of sources (through the call the selects come out in another order)
     const bool second = ce >= C0S;
     const float* sp = seg2 ? (second ? p.x2_src1 : p.x2_src0) : (second ? p.src1 : p.src0);
     const int sC = seg2 ? (second ? p.x2_C1 : p.x2_C0) : (second ? p.C1 : p.C0);
@@ -164,15 +163,10 @@ void k_conv3x3_halo(const ConvParams p, const HaloGeom g) {
       if (hp < g.HP) {
         f32x4 v = rh[j];
         if (cur_act != 0) {
-          const f32x4 sa = himg[j] ? ssa[1] : ssa[0];
-          const f32x4 sb = himg[j] ? ssb[1] : ssb[0];
-          v.x = fmaf(v.x, sa.x, sa.y);
-          v.y = fmaf(v.y, sa.z, sa.w);
-          v.z = fmaf(v.z, sb.x, sb.y);
-          v.w = fmaf(v.w, sb.z, sb.w);
-          if (cur_act == 2) { v.x = silu_h(v.x); v.y = silu_h(v.y); v.z = silu_h(v.z); v.w = silu_h(v.w); }
-          if (DROP) {                    // segment 1 only (cur_act != 0), single source => linear NHWC index
-            const unsigned i0 = (unsigned)(hpix[j] * p.C0 + cur_c);
+          v = gn_affine4(v, himg[j] ? ssa[1] : ssa[0], himg[j] ? ssb[1] : ssb[0]);
+          if (cur_act == 2) v = silu4_libm(v);
+          if (DROP) {                    // segment 1 only (cur_act != 0)
+            const unsigned i0 = drop_index(hpix[j], p.C0, cur_c);
             v.x *= drop_mask(p.drop_seed, i0, p.drop_thresh, p.drop_scale);
             v.y *= drop_mask(p.drop_seed, i0 + 1, p.drop_thresh, p.drop_scale);
             v.z *= drop_mask(p.drop_seed, i0 + 2, p.drop_thresh, p.drop_scale);

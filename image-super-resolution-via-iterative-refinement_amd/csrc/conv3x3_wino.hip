@@ -37,7 +37,9 @@
 
 #include <algorithm>
 
+#include "conv_prologue.h"
 #include "sr3_common.h"
+#include "wino_common.h"
 
 #ifndef SR3_WINO_PRE
 #define SR3_WINO_PRE 0
@@ -54,12 +56,7 @@ typedef double double2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
-constexpr int WBN = 64;         // output channels per workgroup
-constexpr int WCK = 16;         // input channels per chunk
-constexpr int WRS = 20;         // LDS pixel stride (floats) of the raw halo: 16 channels + 4 pad
-constexpr int WROW = 18 * WRS + 8;   // LDS row stride of the raw halo (18 pixels + 8 pad); every second ROW PAIR is shifted by
-constexpr int WSHIFT = 4;            // 4 floats more: with this layout the transform's ds_read_b128 (lane = tile of a 4 x 8
-                                     // tile block, two channel quads) hit 16 distinct bank quads per 16-lane group
+constexpr int WROW = 18 * WRS + 8;   // LDS row stride of the raw halo (18 pixels + 8 pad; WRS, WSHIFT and the cout block / chunk sizes: wino_common.h)
 constexpr int WNT = 512;        // threads (8 waves)
 // Tile geometry.  NB4 = false: 64 Winograd tiles = 16 x 16 output pixels of ONE image, raw halo 18 x 18.  NB4 = true (8 x 8 maps):
 // the 64 tiles are FOUR images of 8 x 8 pixels laid out as a 2 x 2 grid of 10 x 10 halos (each image keeps its own zero
@@ -88,18 +85,6 @@ static_assert(2 * W_RAW_F <= W_EXCH_F && W_RAW_F == WGeo<false>::RAW_F && 2 * WG
               "the raw tiles live inside the exchange block's footprint");
 constexpr int W_SMEM = (W_EXCH_F + 2 * W_CST_F) * 4;   // 143,360 + 16,896 of the CU's 163,840 bytes
 static_assert(W_SMEM <= 163840, "LDS");
-
-// x * sigmoid(x) with the hardware exp2 (v_exp_f32 on x * log2 e) and the hardware reciprocal: ~1e-7 relative error on silu,
-// three instructions instead of libm expf's twelve -- every staged element pays for this once per output-channel block.  The
-// other kernels use libm expf (SR3_SILU); the difference is below what the parity tests resolve.
-__device__ __forceinline__ float silu_w(float v) {
-#ifdef SR3_EXACT_ACT
-  return SR3_SILU(v);
-#else
-  return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f));
-#endif
-}
-constexpr int WUS = 3 * 64 * 8;          // SPLIT: bf16 elements of one (position, n block) fragment group: 3 planes x 64 lanes x 8
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -152,12 +137,7 @@ __global__ __launch_bounds__(256) void k_wino_weights(const float* __restrict__ 
   }
 }
 
-// The same filters for the SPLIT kernel: every U value as three bf16 terms, laid out as the B operand of
-// v_mfma_f32_32x32x16_bf16 (one MFMA = a whole 16-channel chunk):
-//   ufrag_s[cout_blk][chunk][pos][nblk 2][plane 3 (h, m, l)][lane 64][8 bf16]
-//   lane l holds U_pos[n = cout_blk*64 + nblk*32 + (l & 31)] for the 8 channels k = 0..7 of its half hq = l >> 5:
-//   channel = chunk*16 + (k < 4 ? 4 hq + k : 8 + 4 hq + (k - 4))  -- the order in which the kernel's transform lanes hold
-//   their channels (quad hq of either half chunk), so V needs no shuffle.  One thread per (n, chunk, hq).
+// The same filters for the SPLIT kernels, in the ufrag_s layout of wino_common.h.  One thread per (n, chunk, hq).
 __global__ __launch_bounds__(256) void k_wino_weights_split(const float* __restrict__ w, int Cout, int Cin, int nchunks,
                                                              int ncb, __bf16* __restrict__ ufrag) {
   const long total = (long)ncb * WBN * nchunks * 2;
@@ -273,37 +253,20 @@ __global__ __launch_bounds__(WNT, 1) void k_conv3x3_wino(const ConvParams p, con
   const int Cin = p.C0 + p.C1;
   const int H = p.Ho, W = p.Wo;
   // Persistent workgroups: workgroup b walks the tile list b, b + gridDim.x, ... (one 8-wave workgroup fits a CU; what a tile
-  // needs before its main loop is fetched during the previous tile's epilogue, its stores drain under the next main loop).
-  // XCD-aware order: consecutive workgroup ids go round-robin to the 8 XCDs; give each XCD one contiguous range of the
-  // (cout block major) tile list so that the U fragments of a cout block stay inside one L2 (gridDim.x is a multiple of 8
-  // whenever the tile count is, so a workgroup's tiles stay on its XCD's range).
+  // needs before its main loop is fetched during the previous tile's epilogue, its stores drain under the next main loop),
+  // in the XCD-aware order of wino_decode_tile.
   const int sp_tiles = g.tiles_w * g.tiles_h * g.nbt;            // nbt: batch tiles (B, or B / 4 for the four-image tile)
   const int ntiles = ((p.Cout + WBN - 1) / WBN) * sp_tiles;
   int cb = 0, tw_i = 0, th_i = 0, b0 = 0, h0 = 0, w0 = 0;
   auto decode_tile = [&](int v) {
-    int bid = v;
-    if ((ntiles & 7) == 0) bid = (bid & 7) * (ntiles >> 3) + (bid >> 3);
-    // bid / sp_tiles by a host-side magic number (0: one tile per cout block, the quotient is bid itself)
-    cb = g.sp_magic ? (int)(((unsigned long long)(unsigned)bid * g.sp_magic) >> 32) : bid;
-    int sp = bid - cb * sp_tiles;
-    if (g.pow2) {
-      tw_i = sp & (g.tiles_w - 1);
-      th_i = (sp >> g.log_tw) & (g.tiles_h - 1);
-      b0 = sp >> (g.log_tw + g.log_th);
-    } else {
-      tw_i = sp % g.tiles_w;
-      sp /= g.tiles_w;
-      th_i = sp % g.tiles_h;
-      b0 = sp / g.tiles_h;
-    }
+    const WinoTile t = wino_decode_tile(v, ntiles, sp_tiles, g);
+    cb = t.cb; tw_i = t.tw_i; th_i = t.th_i; b0 = t.b0;
     h0 = th_i * 16; w0 = tw_i * 16;               // one image per tile
     if (NB4) { b0 *= 4; h0 = 0; w0 = 0; }         // ... or four whole 8 x 8 images: b0 is the first of them
   };
 
-  const int nch = (Cin + WCK - 1) / WCK;
-  const int cper = (nch + p.ksplit - 1) / p.ksplit;
-  const int c_begin = blockIdx.y * cper;
-  const int c_end = min(nch, c_begin + cper);
+  const WinoKRange kr = wino_k_range(Cin, p.ksplit, blockIdx.y);
+  const int nch = kr.nch, c_begin = kr.c_begin, c_end = kr.c_end;
   const int nck = c_end - c_begin;                // 1 .. W_MAX_CK (host)
   const bool direct = !NB4 && p.ksplit == 1;      // (the four-image tile is split-K only: host)
 
@@ -373,16 +336,13 @@ __global__ __launch_bounds__(WNT, 1) void k_conv3x3_wino(const ConvParams p, con
   auto load_raw = [&](int chunk, f32x4 (&r)[WHI], int j0 = 0, int j1 = GE::WHI) {
     const int c = chunk * WCK + kq * 4;
     const int ce = c < Cin ? c : 0;
-    const bool second = ce >= p.C0;
-    const float* sp_ = second ? p.src1 : p.src0;
-    const int sC = second ? p.C1 : p.C0;
-    const int cs = second ? ce - p.C0 : ce;
+    const auto src = concat_quad(p.src0, p.C0, p.src1, p.C1, ce);
 #pragma unroll
     for (int j = 0; j < WHI; ++j) {
       if (j < j0 || j >= j1) continue;
       const int hp_ = hpx(j);
-      const int off = hp_ >= 0 ? hp_ * sC + cs : 0;
-      r[j] = *reinterpret_cast<const f32x4*>(sp_ + off);
+      const int off = hp_ >= 0 ? hp_ * src.C + src.c : 0;
+      r[j] = *reinterpret_cast<const f32x4*>(src.base + off);
     }
   };
   // GroupNorm (scale, shift) of the tile's image for the channels of this workgroup's chunk range live in LDS (cst + 64 of the
@@ -423,13 +383,10 @@ __global__ __launch_bounds__(WNT, 1) void k_conv3x3_wino(const ConvParams p, con
           ssb = *reinterpret_cast<const f32x4*>(q + 4);
         }
         if (p.act != 0 && !(DBG & 2)) {
-          v.x = fmaf(v.x, ssa.x, ssa.y);
-          v.y = fmaf(v.y, ssa.z, ssa.w);
-          v.z = fmaf(v.z, ssb.x, ssb.y);
-          v.w = fmaf(v.w, ssb.z, ssb.w);
-          if (p.act == 2) { v.x = silu_w(v.x); v.y = silu_w(v.y); v.z = silu_w(v.z); v.w = silu_w(v.w); }
-          if (DROP) {                                       // single source, no upsampling (host): linear NHWC index
-            const unsigned i0 = (unsigned)(hpx(j) * p.C0 + chunk * WCK + kq * 4);
+          v = gn_affine4(v, ssa, ssb);
+          if (p.act == 2) v = silu4_exp2(v);
+          if (DROP) {
+            const unsigned i0 = drop_index(hpx(j), p.C0, chunk * WCK + kq * 4);
             v.x *= drop_mask(p.drop_seed, i0, p.drop_thresh, p.drop_scale);
             v.y *= drop_mask(p.drop_seed, i0 + 1, p.drop_thresh, p.drop_scale);
             v.z *= drop_mask(p.drop_seed, i0 + 2, p.drop_thresh, p.drop_scale);

@@ -25,20 +25,18 @@
 
 #include <algorithm>
 
+#include "conv_prologue.h"
 #include "sr3_common.h"
+#include "wino_common.h"
 
 namespace sr3 {
 
 typedef int vint2 __attribute__((ext_vector_type(2)));
 
 namespace {
-constexpr int VBN = 64;          // output channels per workgroup
-constexpr int VCK = 16;          // input channels per chunk
-constexpr int VRS = 20;          // LDS pixel stride (floats): 16 channels + 4 pad
 constexpr int VTW = 18;          // raw halo pixels per row
 constexpr int VTH = 10;          // raw halo rows
-constexpr int VROW = VTW * VRS + 8;
-constexpr int VSHIFT = 4;        // every second row pair is shifted by 4 floats (conflict-free transform reads, as in the 8-wave kernel)
+constexpr int VROW = VTW * WRS + 8;   // (pixel stride, row-pair shift, cout block and chunk sizes, filter layout: wino_common.h)
 constexpr int VNT = 256;         // threads (4 waves)
 constexpr int VHP = VTH * VTW;   // 180 raw halo pixels
 constexpr int VHI = (VHP * 4 + VNT - 1) / VNT;       // 3 float4 staging items per thread
@@ -50,19 +48,10 @@ constexpr int VEPL = 32 * VETS + 4;                   // floats per plane (32 ch
 constexpr int VEXCH_F = 4 * 2 * VEPL;                 // 4 waves x 2 (p) planes of one 32-channel round
 constexpr int VPR = 264;                              // statistics parking: doubles per row (256 threads + 8)
 constexpr int V_MAX_CK = 64;                          // chunks of one workgroup's K range (1024 input channels; more: split-K)
-constexpr int VCST_F = 64 + V_MAX_CK * 2 * VCK;       // per-tile constants (bias + FiLM of 64 channels, (scale, shift) pairs), two of them
+constexpr int VCST_F = 64 + V_MAX_CK * 2 * WCK;       // per-tile constants (bias + FiLM of 64 channels, (scale, shift) pairs), two of them
 static_assert(2 * VRAW_F + VTAB_F <= VWORK_F && VEXCH_F <= VWORK_F && (16 * VPR + 256) * 2 <= VWORK_F, "raw tiles + item table, exchange block, statistics tree");
 constexpr int V_SMEM = (VWORK_F + 2 * VCST_F) * 4;    // 54,912 bytes: two workgroups per CU
 static_assert(V_SMEM <= 81920, "LDS: two workgroups per CU");
-constexpr int VUS = 3 * 64 * 8;  // bf16 elements of one (position, n block) fragment group (conv3x3_wino.hip: WUS)
-
-__device__ __forceinline__ float silu_v(float v) {      // (conv3x3_wino.hip: silu_w)
-#ifdef SR3_EXACT_ACT
-  return SR3_SILU(v);
-#else
-  return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f));
-#endif
-}
 }  // namespace
 
 // DBG (profiling only, env SR3_WINO_DBG, library built with -DSR3_WINO_ABLATIONS; 0 in production): 1 skip the MFMAs, 4 skip the input
@@ -101,30 +90,16 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
   const int H = p.Ho, W = p.Wo;
   // persistent workgroups, one contiguous range of the (cout block major) tile list per XCD: conv3x3_wino.hip
   const int sp_tiles = g.tiles_w * g.tiles_h * g.nbt;
-  const int ntiles = ((p.Cout + VBN - 1) / VBN) * sp_tiles;
+  const int ntiles = ((p.Cout + WBN - 1) / WBN) * sp_tiles;
   int cb = 0, tw_i = 0, th_i = 0, b0 = 0, h0 = 0, w0 = 0;
   auto decode_tile = [&](int v) {
-    int bid = v;
-    if ((ntiles & 7) == 0) bid = (bid & 7) * (ntiles >> 3) + (bid >> 3);
-    cb = g.sp_magic ? (int)(((unsigned long long)(unsigned)bid * g.sp_magic) >> 32) : bid;
-    int sp = bid - cb * sp_tiles;
-    if (g.pow2) {
-      tw_i = sp & (g.tiles_w - 1);
-      th_i = (sp >> g.log_tw) & (g.tiles_h - 1);
-      b0 = sp >> (g.log_tw + g.log_th);
-    } else {
-      tw_i = sp % g.tiles_w;
-      sp /= g.tiles_w;
-      th_i = sp % g.tiles_h;
-      b0 = sp / g.tiles_h;
-    }
+    const WinoTile t = wino_decode_tile(v, ntiles, sp_tiles, g);
+    cb = t.cb; tw_i = t.tw_i; th_i = t.th_i; b0 = t.b0;
     h0 = th_i * 8; w0 = tw_i * 16;
   };
 
-  const int nch = (Cin + VCK - 1) / VCK;
-  const int cper = (nch + p.ksplit - 1) / p.ksplit;
-  const int c_begin = blockIdx.y * cper;
-  const int c_end = min(nch, c_begin + cper);
+  const WinoKRange kr = wino_k_range(Cin, p.ksplit, blockIdx.y);
+  const int nch = kr.nch, c_begin = kr.c_begin, c_end = kr.c_end;
   const int nck = c_end - c_begin;                // 1 .. V_MAX_CK (host)
   const bool direct = p.ksplit == 1;
 
@@ -138,7 +113,7 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
     for (int j = 0; j < VHI; ++j) {
       const int hp = (t_ >> 2) + (VNT / 4) * j;
       const int hy = hp / VTW, hx = hp - hy * VTW;
-      hinfo_r[j] = hp < VHP ? (hy * VROW + ((hy >> 1) & 1) * VSHIFT + hx * VRS) : -1;
+      hinfo_r[j] = hp < VHP ? (hy * VROW + ((hy >> 1) & 1) * WSHIFT + hx * WRS) : -1;
       const int ih = h0 + hy - 1, iw = w0 + hx - 1;
       const bool ok = hp < VHP && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
       hpix[j] = ok ? (b0 * p.Hs + (ih >> p.ups)) * p.Ws + (iw >> p.ups) : -1;
@@ -162,27 +137,24 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
   auto load_raw = [&](int chunk, f32x4 (&r)[VHI]) {
     const int t_ = tid_now();
     const int kq = t_ & 3;
-    const int c = chunk * VCK + kq * 4;
+    const int c = chunk * WCK + kq * 4;
     const int ce = c < Cin ? c : 0;
-    const bool second = ce >= p.C0;
-    const float* sp_ = second ? p.src1 : p.src0;
-    const int sC = second ? p.C1 : p.C0;
-    const int cs = second ? ce - p.C0 : ce;
+    const auto src = concat_quad(p.src0, p.C0, p.src1, p.C1, ce);
 #pragma unroll
     for (int j = 0; j < VHI; ++j) {
       const int hp_ = hpix[j];
-      const int off = hp_ >= 0 ? hp_ * sC + cs : 0;
-      r[j] = *reinterpret_cast<const f32x4*>(sp_ + off);
+      const int off = hp_ >= 0 ? hp_ * src.C + src.c : 0;
+      r[j] = *reinterpret_cast<const f32x4*>(src.base + off);
     }
   };
   auto store_raw = [&](float* raw, int chunk, const f32x4 (&r)[VHI], const float* cs_) {
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     const int t_ = tid_now();
     const int kq = t_ & 3;
-    const bool hvalid = chunk * VCK + kq * 4 < Cin;
+    const bool hvalid = chunk * WCK + kq * 4 < Cin;
     f32x4 ssa = zero, ssb = zero;
     if (p.act != 0) {
-      const float* q = cs_ + 64 + (chunk - c_begin) * (2 * VCK) + kq * 8;
+      const float* q = cs_ + 64 + (chunk - c_begin) * (2 * WCK) + kq * 8;
       ssa = *reinterpret_cast<const f32x4*>(q);
       ssb = *reinterpret_cast<const f32x4*>(q + 4);
     }
@@ -191,11 +163,8 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
       if (hinfo_r[j] >= 0) {
         f32x4 v = r[j];
         if (p.act != 0) {
-          v.x = fmaf(v.x, ssa.x, ssa.y);
-          v.y = fmaf(v.y, ssa.z, ssa.w);
-          v.z = fmaf(v.z, ssb.x, ssb.y);
-          v.w = fmaf(v.w, ssb.z, ssb.w);
-          if (p.act == 2) { v.x = silu_v(v.x); v.y = silu_v(v.y); v.z = silu_v(v.z); v.w = silu_v(v.w); }
+          v = gn_affine4(v, ssa, ssb);
+          if (p.act == 2) v = silu4_exp2(v);
         }
         v = (hvalid && hpix[j] >= 0) ? v : zero;
         *reinterpret_cast<f32x4*>(&raw[hinfo_r[j] + kq * 4]) = v;
@@ -208,7 +177,7 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
   f32x4 creg[4];
   auto load_consts = [&]() {
     const int t_ = tid_now();
-    const int n = cb * VBN + (t_ & 15) * 4;
+    const int n = cb * WBN + (t_ & 15) * 4;
     const int ne = n < p.Cout ? n : 0;
     creg[0] = *reinterpret_cast<const f32x4*>((direct && p.bias ? p.bias : dummy) + ne);
     creg[1] = *reinterpret_cast<const f32x4*>(direct && p.film ? p.film + (size_t)b0 * p.film_stride + ne : dummy);
@@ -216,7 +185,7 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int e = t_ + VNT * k;                                // 4 floats = 2 channels
-      const int ch = c_begin * VCK + e * 2;
+      const int ch = c_begin * WCK + e * 2;
       creg[2 + k] = *reinterpret_cast<const f32x4*>(q + (p.act != 0 && ch < Cin ? (size_t)ch * 2 : 0));
     }
   };
@@ -224,7 +193,7 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     const int t_ = tid_now();
     if (t_ < 16) {
-      const int n = cb * VBN + t_ * 4;
+      const int n = cb * WBN + t_ * 4;
       f32x4 v = zero;
       if (direct && n < p.Cout) v = (p.bias ? creg[0] : zero) + (p.film ? creg[1] : zero);
       *reinterpret_cast<f32x4*>(cs_ + t_ * 4) = v;
@@ -232,8 +201,8 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int e = t_ + VNT * k;
-      const int n8 = nck * (2 * VCK) / 4;
-      const int ch = c_begin * VCK + e * 2;
+      const int n8 = nck * (2 * WCK) / 4;
+      const int ch = c_begin * WCK + e * 2;
       if (e < n8) *reinterpret_cast<f32x4*>(cs_ + 64 + e * 4) = (p.act != 0 && ch < Cin) ? creg[2 + k] : zero;
     }
   };
@@ -248,9 +217,9 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
   const float sb = (wave == 1) ? 1.f : -1.f;
   const int tl = lane & 31, hq = lane >> 5;
   const int tyl = tl >> 3, tx = tl & 7;
-  const int base01 = (2 * tyl) * VROW + (tyl & 1) * VSHIFT + 2 * tx * VRS + hq * 4;             // patch rows 0, 1
-  const int base23 = (2 * tyl + 2) * VROW + ((tyl + 1) & 1) * VSHIFT + 2 * tx * VRS + hq * 4;   // patch rows 2, 3
-  const int offa01 = base01 + ca * VRS, offb01 = base01 + cb_ * VRS, offa23 = base23 + ca * VRS, offb23 = base23 + cb_ * VRS;
+  const int base01 = (2 * tyl) * VROW + (tyl & 1) * WSHIFT + 2 * tx * WRS + hq * 4;             // patch rows 0, 1
+  const int base23 = (2 * tyl + 2) * VROW + ((tyl + 1) & 1) * WSHIFT + 2 * tx * WRS + hq * 4;   // patch rows 2, 3
+  const int offa01 = base01 + ca * WRS, offb01 = base01 + cb_ * WRS, offa23 = base23 + ca * WRS, offb23 = base23 + cb_ * WRS;
   // One position (row i of this wave's column) and half chunk kk: four LDS reads -- patch rows (ra, rb) x patch columns (ca, cb) -- and
   // V_i = (d[ra][ca] + sb d[ra][cb]) +- (d[rb][ca] + sb d[rb][cb]).  The rows are compile-time (immediate offsets of the reads), the
   // columns wave-uniform (in the four lane bases).  16 more reads per chunk than a column pass shared by the four positions, but
@@ -295,11 +264,11 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
   const __bf16* ubase_s = nullptr;                  // set per tile (cout block), wave-uniform
   auto load_us = [&](int chunk, int i, int slot) {
     if ((DBG & 16) && chunk != c_begin) return;
-    const char* q = reinterpret_cast<const char*>(ubase_s + (size_t)chunk * 16 * (2 * VUS) + (size_t)(4 * i) * (2 * VUS));
+    const char* q = reinterpret_cast<const char*>(ubase_s + (size_t)chunk * 16 * (2 * WUS) + (size_t)(4 * i) * (2 * WUS));
     const unsigned vo = (unsigned)lane_now() * 16u;                  // scalar base + 32-bit lane offset (the saddr form of the load)
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
-      const char* qn = q + n * (VUS * 2);
+      const char* qn = q + n * (WUS * 2);
       asm volatile("" : "+s"(qn));
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl)               // (explicitly global: a laundered pointer would become a flat load)
@@ -368,7 +337,7 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
   for (;;) {
     // ================================ prologue ================================
     const float* cs_ = cst + par * VCST_F;
-    ubase_s = ufrag + (size_t)cb * nch * 16 * (2 * VUS) + (size_t)wave * (2 * VUS);
+    ubase_s = ufrag + (size_t)cb * nch * 16 * (2 * WUS) + (size_t)wave * (2 * WUS);
     const bool computes = !UP || wave != 2;                          // (wave-uniform; UP: wave 2 takes ONE branch around everything it skips)
     auto stage_first = [&]() {
       park_items();
@@ -501,7 +470,7 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
     f32x4 addv[2][4];
 #pragma unroll
     for (int nblk = 0; nblk < 2; ++nblk) {
-      const int n = e_cb * VBN + nblk * 32 + nq * 4;
+      const int n = e_cb * WBN + nblk * 32 + nq * 4;
       const int ne = n < p.Cout ? n : 0;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -550,7 +519,7 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
     float* wbase = exch + (wave * 2) * VEPL + wn * VETS + (wn >> 4) * 4 + 4 * (elane >> 5);
 #pragma unroll
     for (int nblk = 0; nblk < 2; ++nblk) {
-      const int n = e_cb * VBN + nblk * 32 + nq * 4;
+      const int n = e_cb * WBN + nblk * 32 + nq * 4;
       const bool nok = n < p.Cout;
       if (computes) {
         // (UP: row 2 is zero -- R_0 = M_0 + M_1, R_1 = M_1 - M_3, the remaining additions in the order they always had)
@@ -628,7 +597,7 @@ __global__ __launch_bounds__(VNT, 2) void k_conv3x3_wino2(const ConvParams p, co
         const int cq = t_ & 7, e = t_ >> 3;             // e = which * 8 + nb2 * 4 + k
         const double a = part[16 * VPR + t_] + part[16 * VPR + 128 + t_];
         const int which = e >> 3, c = ((e >> 2) & 1) * 32 + cq * 4 + (e & 3);
-        const int nn = e_cb * VBN + c;
+        const int nn = e_cb * WBN + c;
         if (nn < p.Cout) p.ostat[(((size_t)e_b0 * T + e_tix) * p.Cout + nn) * 2 + which] = a;
       }
       __syncthreads();                                  // the parked sums are read: LDS is free for the next tile

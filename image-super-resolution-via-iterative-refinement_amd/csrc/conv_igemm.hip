@@ -28,14 +28,10 @@
 // (two workgroups per CU; the second barrier of a k-step is covered by the other workgroup), the smaller tiles double-buffer.
 #include <type_traits>
 
+#include "conv_prologue.h"
 #include "sr3_common.h"
 
 namespace sr3 {
-
-__device__ __forceinline__ float silu_f(float v) {
-  // x * sigmoid(x); exp is the accurate libm one, reciprocal is v_rcp_f32 (1 ulp)
-  return SR3_SILU(v);
-}
 
 // SPLIT: 0 = fp32 MFMA, 1 = 3 x bf16 split with both operands split while staged, 2 = the same with the WEIGHTS pre-split AND laid out
 // as the MFMA's B fragments (ConvParams::w_split, written once per weight change by igemm_split_weights -- a plan keeps them in its
@@ -115,19 +111,16 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm(const ConvParams p) {
     const int c = chunk * BK + kq * 4;
     const bool cvalid = c < Cin;
     const int ce = cvalid ? c : 0;
-    const bool second = ce >= p.C0;
-    const float* sp = second ? p.src1 : p.src0;
-    const int sC = second ? p.C1 : p.C0;
-    const int cs = second ? ce - p.C0 : ce;
+    const auto src = concat_quad(p.src0, p.C0, p.src1, p.C1, ce);
 #pragma unroll
     for (int i = 0; i < AR; ++i) {
       const int ih = rih[i] + fr, iw = riw[i] + fs;
       const bool ok = cvalid && rb[i] >= 0 && (unsigned)ih < (unsigned)Hi && (unsigned)iw < (unsigned)Wi;
       aok[S][i] = ok;
       const int pix = (rb[i] * p.Hs + (ih >> p.ups)) * p.Ws + (iw >> p.ups);
-      const int off = ok ? pix * sC + cs : 0;
+      const int off = ok ? (int)drop_index(pix, src.C, src.c) : 0;     // (the element offset in a single source IS its mask index)
       aoff[S][i] = off;
-      ra[S][i] = *reinterpret_cast<const f32x4*>(sp + off);
+      ra[S][i] = *reinterpret_cast<const f32x4*>(src.base + off);
     }
     if constexpr (!WPRE) {
 #pragma unroll
@@ -181,11 +174,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm(const ConvParams p) {
     for (int i = 0; i < AR; ++i) {
       f32x4 v = ra[S][i];
       if (p.act != 0) {
-        v.x = fmaf(v.x, ssa[i].x, ssa[i].y);
-        v.y = fmaf(v.y, ssa[i].z, ssa[i].w);
-        v.z = fmaf(v.z, ssb[i].x, ssb[i].y);
-        v.w = fmaf(v.w, ssb[i].z, ssb[i].w);
-        if (p.act == 2) { v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); }
+        v = gn_affine4(v, ssa[i], ssb[i]);
+        if (p.act == 2) v = silu4_libm(v);
         if (p.drop_thresh != 0) {
           const unsigned i0 = (unsigned)aoff[S][i];
           v.x *= drop_mask(p.drop_seed, i0, p.drop_thresh, p.drop_scale);

@@ -20,6 +20,7 @@
 // What bounds it, and the scheduling variants that changed nothing: profiles/r06_gemm1x1.txt, DESIGN.md section 3.1g.
 #include <stdlib.h>
 
+#include "conv_prologue.h"
 #include "sr3_common.h"
 
 #pragma clang diagnostic ignored "-Wpass-failed"      // (the slice loops of `step` are unrolled by a later pass than the one that warns)
@@ -140,10 +141,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm1x1_split(const ConvParams p) {
       return;
     }
     const int c = it << 5;
-    const bool second = c >= p.C0;          // wave-uniform
-    const float* sp = second ? p.src1 : p.src0;
+    const auto src = concat_quad(p.src0, p.C0, p.src1, p.C1, c);          // wave-uniform; the rows' offsets in either source: aoff0 / aoff1
 #pragma unroll
-    for (int i = 0; i < MQ; ++i) ra[s][i] = *reinterpret_cast<const f32x4*>(sp + (second ? aoff1[i] : aoff0[i]) + c);
+    for (int i = 0; i < MQ; ++i) ra[s][i] = *reinterpret_cast<const f32x4*>(src.base + (src.second ? aoff1[i] : aoff0[i]) + c);
   };
   auto load_b = [&](int s, int rel) {
     const bf16x8* q = bq + (size_t)rel * (6 * 64);
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm1x1_split(const ConvParams p) {
     for (int i = 0; i < MQ; ++i) {
       f32x4 v = ra[s][i];
       if constexpr (S2) { if (pad[s] & (1 << i)) v = f32x4{0.f, 0.f, 0.f, 0.f}; }
-      if constexpr (ACT) {
+      if constexpr (ACT) {                   // gn_affine4 (conv_prologue.h) with every lane opaque: the slices below are hand-placed
         v.x = opaque(fmaf(v.x, ssa[i].x, ssa[i].y));
         v.y = opaque(fmaf(v.y, ssa[i].z, ssa[i].w));
         v.z = opaque(fmaf(v.z, ssb[i].x, ssb[i].y));

@@ -3,11 +3,10 @@
 // timestep embedding with every FiLM projection, and the fused reverse-step / q_sample updates.
 #include <string.h>
 
+#include "conv_prologue.h"
 #include "step_tail.h"
 
 namespace sr3 {
-
-__device__ __forceinline__ float silu_s(float v) { return SR3_SILU(v); }
 
 // ---------------------------------------------------------------------------------------------
 // GroupNorm statistics (nn.GroupNorm, model/sr3_modules/unet.py:84,119) as PARTIAL per-(image,
@@ -715,7 +714,7 @@ __global__ __launch_bounds__(256) void k_conv_out_nchw(const float* __restrict__
         v = *reinterpret_cast<const f32x4*>(x + (((size_t)b * H + ih) * W + iw) * C + c);
         const float* s = ss + ((size_t)b * C + c) * 2;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = silu_s(fmaf(v[e], s[2 * e], s[2 * e + 1]));
+        for (int e = 0; e < 4; ++e) v[e] = silu_libm(fmaf(v[e], s[2 * e], s[2 * e + 1]));
       }
       *reinterpret_cast<f32x4*>(tile + pix * OT_LD + q * 4) = v;
     }
@@ -835,14 +834,14 @@ __global__ __launch_bounds__(256) void k_embed(const EmbedParams p) {
     float s = p.b1[j];
     const float* wr = p.w1 + (size_t)j * p.inner;
     for (int k = 0; k < p.inner; ++k) s = fmaf(wr[k], enc[k], s);
-    hid[j] = silu_s(s);
+    hid[j] = silu_libm(s);
   }
   __syncthreads();
   for (int j = tid; j < p.inner; j += 256) {
     float s = p.b2[j];
     const float* wr = p.w2 + (size_t)j * hdim;
     for (int k = 0; k < hdim; ++k) s = fmaf(wr[k], hid[k], s);
-    p.temb[(size_t)b * p.inner + j] = (p.variant == 1) ? silu_s(s) : s;
+    p.temb[(size_t)b * p.inner + j] = (p.variant == 1) ? silu_libm(s) : s;
   }
 }
 

@@ -173,7 +173,8 @@ int chan_stats_fold(const float* x, int B, int HW, int C, double* stat, const Fo
 // Activations are NHWC fp32.  The input is the *virtual* channel concat of up to two sources,
 // optionally nearest-upsampled x2 (gather in the address math), optionally strided.
 // Prologue (per input element, before zero padding): none | x*scale+shift | silu(x*scale+shift)
-// with (scale, shift) per (image, input channel) = GroupNorm folded with its affine.
+// with (scale, shift) per (image, input channel) = GroupNorm folded with its affine; then the train-mode dropout mask.
+// conv_prologue.h is its definition: the source select, the affine, the two SiLU forms and the mask index every kernel stages through.
 // Epilogue: + bias[n] + film[b][n] + residual[m][n] (residual is itself a two-source concat view).
 struct ConvParams {
   const float* src0;

@@ -9,6 +9,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include "conv_prologue.h"
 #include "sr3_common.h"
 #include "train.h"
 
@@ -23,8 +24,6 @@ double meant_double(float f) {
   }
   return (double)f;
 }
-
-__device__ __forceinline__ float sigmoid_t(float v) { return SR3_SIGMOID(v); }
 
 // ---------------------------------------------------------------------------------------------
 // T1: activation backward + partial sums.  For the virtual concat x = (x0|x1) with u = x*scale+shift,
@@ -52,9 +51,7 @@ __global__ __launch_bounds__(256) void k_act_bwd_reduce(float* __restrict__ dA, 
   double s[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
   if (q < nq) {
     const int c = q * 4;
-    const bool second = c >= C0;
-    const float* xs = second ? x1 : x0;
-    const int Cs = second ? C1 : C0, cs = second ? c - C0 : c;
+    const auto src = concat_quad(x0, C0, x1, C1, c);
     float sc[4], sh[4], mu[4], rs[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -67,17 +64,18 @@ __global__ __launch_bounds__(256) void k_act_bwd_reduce(float* __restrict__ dA, 
     for (int p = p0 + pl; p < p1; p += PP) {
       const size_t pix = (size_t)b * HW + p;
       f32x4 g4 = *reinterpret_cast<const f32x4*>(dA + pix * C + c);
-      const f32x4 xv = *reinterpret_cast<const f32x4*>(xs + pix * Cs + cs);
+      const f32x4 xv = *reinterpret_cast<const f32x4*>(src.base + pix * src.C + src.c);
       f32x4 a4;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float du = g4[e];
         float dm = 1.0f;
+        // mirrors drop_index(pix, C, c, e) of conv_prologue.h, spelled out: behind the call this loop's set-up is scheduled differently
         if (drop_thresh != 0) { dm = drop_mask(drop_seed, (unsigned)(pix * C + c + e), drop_thresh, drop_scale); du *= dm; }
         const float u = fmaf(xv[e], sc[e], sh[e]);
         float av = u;
         if (act == 2) {
-          const float sg = sigmoid_t(u);
+          const float sg = SR3_SIGMOID(u);     // (av below: silu_libm(u), sharing the sigmoid with the derivative)
           du *= sg * (1.0f + u * (1.0f - sg));
           av = u * sg;
         }
@@ -175,15 +173,13 @@ __global__ __launch_bounds__(256) void k_gn_bwd_apply(const float* __restrict__ 
     const size_t pix = i / nq;
     const int c = (int)(i - pix * nq) * 4;
     const int b = (int)(pix / HW);
-    const bool second = c >= C0;
-    const float* xs = second ? x1 : x0;
-    float* ds = second ? dx1 : dx0;
-    const int Cs = second ? C1 : C0, cs = second ? c - C0 : c;
+    const auto src = concat_quad(x0, C0, x1, C1, c);
+    const auto dst = concat_quad(dx0, C0, dx1, C1, c);
     const f32x4 g4 = *reinterpret_cast<const f32x4*>(du + pix * C + c);
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(xs + pix * Cs + cs);
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(src.base + pix * src.C + src.c);
     // (acc == 0: this is the first contribution to that gradient tensor in the backward walk -- a plain store, the mirror is not zeroed)
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
-    if (second ? acc1 : acc0) o = *reinterpret_cast<const f32x4*>(ds + pix * Cs + cs);
+    if (dst.second ? acc1 : acc0) o = *reinterpret_cast<const f32x4*>(dst.base + pix * dst.C + dst.c);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int g = (c + e) / cpg;
@@ -192,7 +188,7 @@ __global__ __launch_bounds__(256) void k_gn_bwd_apply(const float* __restrict__ 
       const double xh = ((double)xv[e] - mu) * rs;
       o[e] += (float)(rs * ((double)gamma[c + e] * (double)g4[e] - (S1 + xh * S2) * inv_n));
     }
-    *reinterpret_cast<f32x4*>(ds + pix * Cs + cs) = o;
+    *reinterpret_cast<f32x4*>(dst.base + pix * dst.C + dst.c) = o;
   }
 }
 
@@ -207,9 +203,7 @@ __global__ __launch_bounds__(256) void k_grad_route(const float* __restrict__ g,
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.x * blockDim.x) {
     const size_t pix = i / nq;                  // source pixel (b, y, x)
     const int c = (int)(i - pix * nq) * 4;
-    const bool second = c >= C0;
-    float* ds = second ? d1 : d0;
-    const int Cs = second ? C1 : C0, cs = second ? c - C0 : c;
+    const auto dst = concat_quad(d0, C0, d1, C1, c);
     f32x4 acc;
     if (ups) {
       const int x = (int)(pix % Ws);
@@ -225,8 +219,8 @@ __global__ __launch_bounds__(256) void k_grad_route(const float* __restrict__ g,
       acc = *reinterpret_cast<const f32x4*>(g + pix * C + c);
     }
     f32x4 o = acc;
-    if (second ? acc1 : acc0) o += *reinterpret_cast<const f32x4*>(ds + pix * Cs + cs);
-    *reinterpret_cast<f32x4*>(ds + pix * Cs + cs) = o;
+    if (dst.second ? acc1 : acc0) o += *reinterpret_cast<const f32x4*>(dst.base + pix * dst.C + dst.c);
+    *reinterpret_cast<f32x4*>(dst.base + pix * dst.C + dst.c) = o;
   }
 }
 
@@ -416,20 +410,15 @@ __global__ __launch_bounds__(256) void k_apply_act(const float* __restrict__ x0,
     const size_t pix = i / nq;
     const int c = (int)(i - pix * nq) * 4;
     const int b = (int)(pix / HW);
-    const bool second = c >= C0;
-    const float* xs = second ? x1 : x0;
-    const int Cs = second ? C1 : C0, cs = second ? c - C0 : c;
-    f32x4 v = *reinterpret_cast<const f32x4*>(xs + pix * Cs + cs);
+    const auto src = concat_quad(x0, C0, x1, C1, c);
+    f32x4 v = *reinterpret_cast<const f32x4*>(src.base + pix * src.C + src.c);
     const f32x4 s0 = *reinterpret_cast<const f32x4*>(ss + ((size_t)b * C + c) * 2);
     const f32x4 s1 = *reinterpret_cast<const f32x4*>(ss + ((size_t)b * C + c) * 2 + 4);
-    v.x = fmaf(v.x, s0.x, s0.y); v.y = fmaf(v.y, s0.z, s0.w); v.z = fmaf(v.z, s1.x, s1.y); v.w = fmaf(v.w, s1.z, s1.w);
-    if (act == 2) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = v[e] * sigmoid_t(v[e]);
-    }
+    v = gn_affine4(v, s0, s1);
+    if (act == 2) v = silu4_libm(v);
     if (drop_thresh != 0) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] *= drop_mask(drop_seed, (unsigned)(pix * C + c + e), drop_thresh, drop_scale);
+      for (int e = 0; e < 4; ++e) v[e] *= drop_mask(drop_seed, drop_index(pix, C, c, e), drop_thresh, drop_scale);
     }
     *reinterpret_cast<f32x4*>(out + pix * C + c) = v;
   }

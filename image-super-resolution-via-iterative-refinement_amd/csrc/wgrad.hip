@@ -12,12 +12,11 @@
 
 #include <string.h>
 
+#include "conv_prologue.h"
 #include "sr3_common.h"
 #include "train.h"
 
 namespace sr3 {
-
-__device__ __forceinline__ float silu_w(float v) { return SR3_SILU(v); }
 
 template <int TN, int TC>
 __global__ __launch_bounds__(256, 2) void k_conv_wgrad(const ConvParams p, const float* __restrict__ dy,
@@ -56,10 +55,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad(const ConvParams p, const
     const bool nv = (lq * 4 < TN) && n < p.Cout;
     const bool cv = (lq * 4 < TC) && c < Cin;
     const int ce = cv ? c : 0;
-    const bool second = ce >= p.C0;
-    const float* sp = second ? p.src1 : p.src0;
-    const int sC = second ? p.C1 : p.C0;
-    const int cs = second ? ce - p.C0 : ce;
+    const auto src = concat_quad(p.src0, p.C0, p.src1, p.C1, ce);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int m = chunk * 32 + lpx + 8 * i;
@@ -81,7 +77,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad(const ConvParams p, const
       const bool ok = mv && cv && (unsigned)ih < (unsigned)Hi && (unsigned)iw < (unsigned)Wi;
       aok[i] = ok;
       const int pix = (b * p.Hs + (ih >> p.ups)) * p.Ws + (iw >> p.ups);
-      ra[i] = *reinterpret_cast<const f32x4*>(sp + (ok ? pix * sC + cs : 0));
+      ra[i] = *reinterpret_cast<const f32x4*>(src.base + (ok ? pix * src.C + src.c : 0));
       if (p.act != 0) {
         const float* q = p.ss + (b * Cin + ce) * 2;
         sa[i] = *reinterpret_cast<const f32x4*>(q);
@@ -99,11 +95,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad(const ConvParams p, const
       if (lq * 4 < TC) {
         f32x4 v = ra[i];
         if (p.act != 0) {
-          v.x = fmaf(v.x, sa[i].x, sa[i].y);
-          v.y = fmaf(v.y, sa[i].z, sa[i].w);
-          v.z = fmaf(v.z, sb[i].x, sb[i].y);
-          v.w = fmaf(v.w, sb[i].z, sb[i].w);
-          if (p.act == 2) { v.x = silu_w(v.x); v.y = silu_w(v.y); v.z = silu_w(v.z); v.w = silu_w(v.w); }
+          v = gn_affine4(v, sa[i], sb[i]);
+          if (p.act == 2) v = silu4_libm(v);
         }
         *reinterpret_cast<f32x4*>(&As[px * LDC + lq * 4]) = aok[i] ? v : zero;
       }
@@ -221,10 +214,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_split(const ConvParams p,
     const int c = tile_c * TC + uq * 4;
     const bool nv = n < p.Cout, cv = c < Cin;
     const int ce = cv ? c : 0;
-    const bool second = ce >= p.C0;
-    const float* sp = second ? p.src1 : p.src0;
-    const int sC = second ? p.C1 : p.C0;
-    const int cs = second ? ce - p.C0 : ce;
+    const auto src = concat_quad(p.src0, p.C0, p.src1, p.C1, ce);
     // power-of-two maps at least PX wide: the unit's PX pixels lie in one image row -- decode the first, step the column (round 6: the
     // per-pixel decode was a third of this kernel's 6 VALU instructions per MFMA)
     int ub = 0, uoh = 0, uow = 0;
@@ -260,7 +250,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_split(const ConvParams p,
         const bool ok = mv && cv && (unsigned)ih < (unsigned)Hi && (unsigned)iw < (unsigned)Wi;
         rok[i] = ok;
         const int pix = (b * p.Hs + (ih >> p.ups)) * p.Ws + (iw >> p.ups);
-        rv[i] = *reinterpret_cast<const f32x4*>(sp + (ok ? pix * sC + cs : 0));
+        rv[i] = *reinterpret_cast<const f32x4*>(src.base + (ok ? pix * src.C + src.c : 0));
         if constexpr (ACT) {
           const float* q = p.ss + (b * Cin + ce) * 2;
           sa[i] = *reinterpret_cast<const f32x4*>(q);
@@ -275,11 +265,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_split(const ConvParams p,
     for (int i = 0; i < PX; ++i) {
       v[i] = rv[i];
       if constexpr (ACT) if (is_act) {
-        v[i].x = fmaf(v[i].x, sa[i].x, sa[i].y);
-        v[i].y = fmaf(v[i].y, sa[i].z, sa[i].w);
-        v[i].z = fmaf(v[i].z, sb[i].x, sb[i].y);
-        v[i].w = fmaf(v[i].w, sb[i].z, sb[i].w);
-        if (p.act == 2) { v[i].x = silu_w(v[i].x); v[i].y = silu_w(v[i].y); v[i].z = silu_w(v[i].z); v[i].w = silu_w(v[i].w); }
+        v[i] = gn_affine4(v[i], sa[i], sb[i]);
+        if (p.act == 2) v[i] = silu4_libm(v[i]);
       }
       if (!rok[i]) v[i] = zero;
     }
