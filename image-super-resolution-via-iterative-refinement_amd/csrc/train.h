@@ -86,10 +86,9 @@ struct WgradParams {
   ConvParams c;        // forward geometry + src0/src1/ss/act (+ ups/stride/ksize)
   const float* dy;     // [B,Ho,Wo,Cout]
   float* dw;           // [Cout][taps][Cin]
-  float* slabs;        // [msplit][Cout][taps][Cin]
-  int msplit;
+  float* slabs;        // [msplit][Cout][taps][Cin], wgrad_slab_bytes(c) of them (read only where the layer's pixel split is > 1)
 };
-size_t wgrad_slab_bytes(const ConvParams& c, int* msplit_out);
+size_t wgrad_slab_bytes(const ConvParams& c);
 int conv_wgrad(const WgradParams& p, hipStream_t st);
 
 // Attention backward (attention_bwd.hip): qkv [B][N][3C], dout [B][N][C] -> dqkv [B][N][3C] (overwritten)

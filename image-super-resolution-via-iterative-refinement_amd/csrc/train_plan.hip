@@ -193,7 +193,7 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
       continue;
     }
     const ConvParams& w = r.dw;
-    raise(max_slab, wgrad_slab_bytes(w, nullptr));
+    raise(max_slab, wgrad_slab_bytes(w));
     raise(max_part, (size_t)B * chan_stats_slices(B, w.Ho * w.Wo, w.Cout) * w.Cout * 2 * sizeof(double));      // colsums of dOut
     if (r.kind != R_CONV) raise(max_dwtmp, (size_t)w.Cout * 9 * w.C0 * sizeof(float));       // padded filters, compacted into the arena
     if (r.kind == R_CONV_IN) continue;
@@ -210,7 +210,7 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
       raise(max_wu, wu_bytes(r.dx));
     }
     if (r.s.q0 >= 0) {
-      raise(max_slab, wgrad_slab_bytes(r.dqw, nullptr));
+      raise(max_slab, wgrad_slab_bytes(r.dqw));
       raise(max_dq, fbytes(r.dq.c, r.dq.c.Cout));
       raise(max_wt, (size_t)r.dq.c.C0 * r.dq.c.Cout * sizeof(float));
       raise(max_bscratch, conv_splitk_bytes(r.dq.c, 0, 0));
@@ -310,8 +310,8 @@ int dgrad_conv(const Dgrad& d, int stride, int Ho, int Wo, const float* g, const
   return conv_forward(c, d.tile, d.ksplit, b.slabs, b.slab_bytes, st);
 }
 
-// weight gradient of the shape `c` over the sources src0 | src1.  wgrad_split is a no-rebuild option (the slabs are sized for both
-// values), so msplit is computed here
+// weight gradient of the shape `c` over the sources src0 | src1.  wgrad_split is a no-rebuild option: the slabs are sized for both
+// values, and conv_wgrad picks the kernel and the pixel split at launch
 int wgrad_call(const TrainCtx& X, ConvParams c, const float* src0, const float* src1, const float* dy, float* dw) {
   WgradParams wp;
   c.src0 = src0; c.src1 = src1;
@@ -320,7 +320,6 @@ int wgrad_call(const TrainCtx& X, ConvParams c, const float* src0, const float* 
   wp.dy = dy;
   wp.dw = dw;
   wp.slabs = X.at<float>(X.P->t_slab_off);
-  wgrad_slab_bytes(c, &wp.msplit);
   return conv_wgrad(wp, X.st);
 }
 }  // namespace

@@ -102,22 +102,23 @@ def attn_errors(got, ref, C, heads):
 
 # ---- weight gradient on heavy-tailed operands ---------------------------------------------------------------------------------------
 
-# The kernel each case lands on, by wgrad_use_split (split asked for, Cout > 64 and Cin > 64) and the 9-tap rule of wgrad.hip (3 x 3,
-# stride 1, no upsample, one source, NO fused activation, a map 8 | W wide): k_conv_wgrad<TN, TC> is the generic one-tap-per-workgroup
-# fp32-MFMA kernel (128 x 128 where both channel counts exceed 64, else 64 x 64), k_conv_wgrad_split<128, 128> the 3 x bf16 one.
+# The kernel each case lands on, by wgrad_pick of csrc/wgrad.hip: the split kernel where split is asked for and Cout > 64 and Cin > 64;
+# else the 9-tap kernel (3 x 3, stride 1, no upsample, one source, NO fused activation, a map 8 | W wide); else k_conv_wgrad<TN, TC>, the
+# generic one-tap-per-workgroup fp32-MFMA kernel (128 x 128 where both channel counts exceed 64, else 64 x 64).  k_conv_wgrad_split<ACT>
+# is the 3 x bf16 one (128 x 128, with or without the fused prologue).
 WGRAD_CASES = [
     # name, B, C0, C1, H, W, Cout, k, stride, ups, act, amp of the (scale, shift) pairs
     # the fused activation keeps it off the 9-tap kernel: k_conv_wgrad<64, 64> under either `split`
     ('w3_64to64_silu', 2, 64, 0, 16, 16, 64, 3, 1, 0, 2, 30.0),
-    # split 0: k_conv_wgrad<128, 128>; split 1: k_conv_wgrad_split<128, 128, act>
+    # split 0: k_conv_wgrad<128, 128>; split 1: k_conv_wgrad_split<true>
     ('w3_128to128_silu', 2, 128, 0, 16, 16, 128, 3, 1, 0, 2, 30.0),
     # 100 pixels (ragged last 32-pixel chunk), 136 and 200 channels (ragged tiles): k_conv_wgrad<128, 128> / k_conv_wgrad_split
     ('w3_ragged_M100_136to200_affine', 1, 136, 0, 10, 10, 200, 3, 1, 0, 1, 300.0),
     # Cout = 64: k_conv_wgrad<64, 64> under either `split`; the concat seam at channel 96 and the in-kernel affine prologue
     ('w1_concat96+32to64_affine', 2, 96, 32, 16, 16, 64, 1, 1, 0, 1, 300.0),
-    # stride 2 on the raw features: k_conv_wgrad<128, 128> / k_conv_wgrad_split<128, 128, no act>
+    # stride 2 on the raw features: k_conv_wgrad<128, 128> / k_conv_wgrad_split<false>
     ('w3_s2_128to128_raw', 2, 128, 0, 16, 16, 128, 3, 2, 0, 0, None),
-    # the x2-upsampled address: k_conv_wgrad<128, 128> / k_conv_wgrad_split<128, 128, no act>
+    # the x2-upsampled address: k_conv_wgrad<128, 128> / k_conv_wgrad_split<false>
     ('w3_up_128to128_raw', 2, 128, 0, 8, 8, 128, 3, 1, 1, 0, None),
     # no activation, one source, stride 1, 32 | W: the one shape here the 9-tap rule accepts -- k_conv_wgrad9 under either `split`
     ('w3_64to64_raw_9tap', 2, 64, 0, 32, 32, 64, 3, 1, 0, 0, None),
@@ -130,7 +131,7 @@ WGRAD_CMP_RATIO = 0.25      # torch's fp32 autograd on the same data must stay b
 
 
 def wgrad_runs_split(case, split):
-    """wgrad_use_split of wgrad.hip"""
+    """where wgrad_pick (csrc/wgrad.hip) takes the split kernel"""
     _, B, C0, C1, H, W, Cout, k, stride, ups, act, amp = case
     return bool(split) and Cout > 64 and C0 + C1 > 64
 

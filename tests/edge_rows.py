@@ -342,6 +342,52 @@ def attention_bwd_row(B, N, Cc, with_out):
     return Row('attention_bwd_%dx%dx%d%s' % (B, N, Cc, '_fwd' if with_out else ''), None, 'sr3_attention_bwd_f32', build)
 
 
+# ---- sr3_conv_wgrad_f32 (tests/test_gpu_ops.py::test_conv_weight_gradient_per_op: float64 autograd of F.conv2d, normwise 2e-6) --------------
+
+def wgrad_edge(kernel, B, Hs, Ws, C0, C1, Cout, act, split, msplit, ups=0):
+    """One row per compute kernel of csrc/wgrad.hip, 3x3 stride 1, at the smallest shape where that kernel has every ragged edge.
+    `msplit`: the pixel split wgrad_pick gives the shape (asserted through the query, as scratch_rows.wgrad_row does: the slabs of both
+    `split` values have this size at these shapes); the scratch is 16-byte aligned by contract."""
+    Cin = C0 + C1
+
+    def build():
+        Ho, Wo = Hs << ups, Ws << ups
+        x0, x1 = rand(B, C0, Hs, Ws, seed=31), (rand(B, C1, Hs, Ws, seed=32) if C1 else None)
+        dy = rand(B, Cout, Ho, Wo, seed=35)
+        ins = {'src0': nhwc(x0), 'dy': nhwc(dy)}
+        if C1:
+            ins['src1'] = nhwc(x1)
+        ss = None
+        if act:
+            ss = ins['ss'] = torch.stack([rand(B, Cin, seed=33) * 0.3 + 1.0, rand(B, Cin, seed=34) * 0.3], dim=2).contiguous()
+
+        def call(lib, P, scratch, nbytes, stream):
+            return lib.sr3_conv_wgrad_f32(P['src0'], C0, P.get('src1'), C1, B, Hs, Ws, ups, 1, 3, Cout, P.get('ss'), act, P['dy'], P['dw'], split,
+                                          scratch, nbytes, stream)
+
+        def grad():
+            a = (x0 if x1 is None else torch.cat([x0, x1], 1)).double()
+            if act:
+                a = a * ss[:, :, 0].double()[:, :, None, None] + ss[:, :, 1].double()[:, :, None, None]
+                if act == 2:
+                    a = a * torch.sigmoid(a)
+            if ups:
+                a = F.interpolate(a, scale_factor=2, mode='nearest')
+            w = torch.zeros(Cout, Cin, 3, 3, dtype=torch.float64, requires_grad=True)
+            F.conv2d(a, w, None, stride=1, padding=1).backward(dy.double())
+            return w.grad.permute(0, 2, 3, 1).reshape(Cout, 9, Cin).contiguous()
+        ref = cached(grad)
+
+        def check(got):
+            e = relerr(got['dw'], ref())
+            assert e < 2e-6, (kernel, e)
+        return dict(ins=ins, outs={'dw': ((Cout, 9, Cin), torch.float32)}, call=call, check=check, expect=msplit * Cout * 9 * Cin * 4,
+                    query=lambda lib: int(lib.sr3_conv_wgrad_scratch_bytes(B, Hs, Ws, ups, 1, 3, C0, C1, Cout, split)),
+                    exact=lambda: {'dw': ref().float()}, tol={'dw': 2e-6 * float(ref().norm())})
+    rid = 'wgrad_%s_%dx%dx%d_%d+%dto%d%s_act%d_split%d' % (kernel, B, Hs, Ws, C0, C1, Cout, '_up' if ups else '', act, split)
+    return Row(rid, 'sr3_conv_wgrad_scratch_bytes', 'sr3_conv_wgrad_f32', build, align=16)
+
+
 # ---- the small entries -----------------------------------------------------------------------------------------------------------------------------
 
 def gn_stats_row(B, HW, Cc):
@@ -563,6 +609,14 @@ OTHER_ROWS += [attention_row(B, N, Cc, mode) for (B, N, Cc) in ((2, 100, 48), (3
 OTHER_ROWS += [attention_row(B, N, Cc, mode, heads=2) for (B, N, Cc, modes) in ((3, 16, 64, (0, 1)), (2, 100, 96, (0, 1)), (2, 100, 128, (0, 1, 4, 5)))
                for mode in modes]
 OTHER_ROWS += [attention_bwd_row(2, 100, 48, False), attention_bwd_row(2, 64, 32, False), attention_bwd_row(1, 512, 128, True)]
+# the weight gradient, one row per compute instantiation.  15 x 15: 225 pixels, 8 chunks whose last holds one pixel, the division decode;
+# 36 + 12 -> 40: the seam inside the only 64-channel tile, both tile tails, the in-kernel affine prologue; 40 + 32 -> 68: ragged 128
+# tiles on both sides, on the fp32 and on the split kernel with its prologue; 8 x 9 upsampled: 288 pixels, 9 chunks (5 + 4), the
+# upsampled address off the power-of-two maps; 2 x 4 x 24: chunks of 4 rows x 8 columns, three side by side, a ragged 64 x 64 tile
+WGRAD_ROWS = [wgrad_edge('fp32_64', 1, 15, 15, 36, 12, 40, 1, 0, 2), wgrad_edge('fp32_128', 1, 15, 15, 40, 32, 68, 2, 0, 2),
+              wgrad_edge('split_act', 1, 15, 15, 40, 32, 68, 2, 1, 2), wgrad_edge('split_raw', 1, 8, 9, 40, 32, 68, 0, 1, 2, ups=1),
+              wgrad_edge('nine_tap', 2, 4, 24, 20, 0, 12, 0, 1, 3)]
+OTHER_ROWS += WGRAD_ROWS
 OTHER_ROWS += [gn_stats_row(3, 100, 24), gn_stats_row(1, 16, 1024), gn_fold_row(3, 100, 24), gn_fold_row(1, 16, 1024)]
 OTHER_ROWS += [film_embed_row(0), film_embed_row(1)]
 # the two smallest cases of test_grad_route's list with a concat seam, one accumulate flag each way

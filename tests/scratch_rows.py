@@ -155,7 +155,7 @@ def conv_dropout_row(tile, ks, B, H, W, Cin, Cout):
 # ---- sr3_conv_wgrad_scratch_bytes ---------------------------------------------------------------------------------------------------
 
 def wgrad_row(name, B, Hs, Ws, k, Cin, Cout, split, msplit):
-    """`msplit`: the pixel split csrc/wgrad.hip's wgrad_geometry gives this shape (> 1: the slabs are really used) -- the query must
+    """`msplit`: the pixel split csrc/wgrad.hip's wgrad_pick gives this shape (> 1: the slabs are really used) -- the query must
     return exactly that many slabs."""
     def build():
         x, dy = rand(B, Cin, Hs, Ws, seed=31), rand(B, Cout, Hs, Ws, seed=35)
@@ -596,7 +596,7 @@ ROWS = [
     # the fused res_conv segment under split-K: one x2 source on an 8 x 8 map, a concat x2 source over several tiles
     block_conv_row(5, 2, 1, 8, 8, 64, 64, 64, 0), block_conv_row(5, 2, 2, 16, 16, 64, 128, 96, 32),
     conv_dropout_row(11, 2, 1, 16, 16, 64, 64), conv_dropout_row(12, 2, 1, 16, 16, 64, 64),
-    # one shape per kernel of wgrad.hip at which msplit > 1 (wgrad_geometry)
+    # one shape per kernel of wgrad.hip at which msplit > 1 (wgrad_pick)
     wgrad_row('fp32_64x64_tile', 2, 16, 16, 1, 64, 64, 0, 4), wgrad_row('fp32_128x128_tile', 2, 16, 16, 1, 128, 128, 0, 4),
     wgrad_row('split_kernel', 2, 16, 16, 1, 128, 128, 1, 4), wgrad_row('nine_tap_kernel', 2, 8, 24, 3, 64, 64, 1, 6),
     dgrad_row('winograd', {}, 1, 16, 16, 32, 32, 3, 1, 13, 2, None), dgrad_row('gemm_tile22_slabs', {}, 1, 8, 8, 128, 256, 1, 1, 22, 3, True),

@@ -46,7 +46,7 @@ def test_wgrad_data_is_heavy_and_fp32_autograd_is_inside_a_quarter_of_the_bound(
 
 
 def test_wgrad_cases_cover_the_kernels():
-    """wgrad_use_split restated: the split kernel runs on four of the cases under `split` = 1 and on none under `split` = 0"""
+    """wgrad_pick's split condition restated: the split kernel runs on four of the cases under `split` = 1 and on none under `split` = 0"""
     assert [c[0] for c in S.WGRAD_CASES if S.wgrad_runs_split(c, 1)] == ['w3_128to128_silu', 'w3_ragged_M100_136to200_affine', 'w3_s2_128to128_raw',
                                                                          'w3_up_128to128_raw']
     assert not any(S.wgrad_runs_split(c, 0) for c in S.WGRAD_CASES)

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import gpu_util as G
-from edge_rows import CONV_ROWS, ROWS
+from edge_rows import CONV_ROWS, ROWS, WGRAD_ROWS
 
 
 def test_row_ids_are_unique_and_tiles_are_the_default_library_s():
@@ -54,6 +54,13 @@ def test_every_conv_row_must_run(row):
     nb = spec['query'](lib)
     if spec.get('expect') is not None:
         assert nb == spec['expect'], (nb, spec['expect'])
+
+
+@pytest.mark.parametrize('row', WGRAD_ROWS, ids=[r.id for r in WGRAD_ROWS])
+def test_every_wgrad_row_has_the_pixel_split_it_names(row):
+    from sr3_hip import lib as L
+    spec = row.spec()
+    assert spec['expect'] > 0 and spec['query'](L.load()) == spec['expect']
 
 
 def _moved(t, flat, delta):

@@ -197,7 +197,7 @@ def test_weight_gradient_on_non_power_of_two_maps(H, W, cin, cout):
     ref = w.grad
     xd, dyd = G.nhwc(x).to(d), G.nhwc(dy).to(d)
     nb = int(lib.sr3_conv_wgrad_scratch_bytes(B, H, W, 0, 1, 3, cin, 0, cout, 1))
-    # the layer runs on the 9-tap kernel, not on the one-tap fallback: its pixel split is that kernel's (wgrad_geometry, csrc/wgrad.hip:
+    # the layer runs on the 9-tap kernel, not on the one-tap fallback: its pixel split is that kernel's row of wgrad_pick (csrc/wgrad.hip:
     # 512 workgroups aimed at, at least two 32-pixel chunks per split; the fallback's rule gives half as many splits on these shapes)
     tiles, nchunks = -(-cout // 64) * -(-cin // 64), B * H * W // 32
     per = -(-nchunks // min(-(-512 // tiles), max(nchunks // 2, 1)))
