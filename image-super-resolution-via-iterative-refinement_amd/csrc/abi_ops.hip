@@ -224,6 +224,23 @@ int sr3_groupnorm_fold_mr_f32(const double* stat0, int C0, int T0, const double*
   return gn_finalize(stat0, C0, T0, stat1, stat1 ? C1 : 0, stat1 ? T1 : 0, B, HW, groups, gamma, beta, eps, ss,
                      static_cast<hipStream_t>(stream), mr);
 }
+// ... with the scale-shift modulation of the pairs (fold_modulate, small_kernels.hip); mr may be NULL.  Nothing is launched on a refusal
+int sr3_groupnorm_fold_mod_f32(const double* stat0, int C0, int T0, const double* stat1, int C1, int T1, int B, int HW,
+                               int groups, const float* gamma, const float* beta, float eps, float* ss, float* mr, const float* mod,
+                               int mod_stride, void* stream) {
+  const char* who = "sr3_groupnorm_fold_mod_f32";
+  if (!stat0 || !gamma || !beta || !ss || !mod) { set_error("%s: stat0 / gamma / beta / ss / mod is NULL", who); return SR3_E_BADARG; }
+  if (!stat1) C1 = T1 = 0;
+  if (B <= 0 || HW <= 0 || C0 <= 0 || C1 < 0 || T0 <= 0 || (stat1 && T1 <= 0) || groups <= 0) {
+    set_error("%s: batch %d, pixels %d, channels %d | %d, partials %d | %d and groups %d must be positive (C1 >= 0)", who, B, HW, C0, C1, T0, T1, groups);
+    return SR3_E_BADARG;
+  }
+  const int C = C0 + C1;
+  if ((C0 & 3) || (C1 & 3)) { set_error("%s: channel counts must be multiples of 4 (C0 %d, C1 %d)", who, C0, C1); return SR3_E_UNSUPPORTED; }
+  if (C % groups) { set_error("%s: %d channels do not divide into %d groups", who, C, groups); return SR3_E_UNSUPPORTED; }
+  if (mod_stride < 2 * C) { set_error("%s: mod_stride %d is below the 2 x %d values of an image", who, mod_stride, C); return SR3_E_BADARG; }
+  return gn_finalize(stat0, C0, T0, stat1, C1, T1, B, HW, groups, gamma, beta, eps, ss, static_cast<hipStream_t>(stream), mr, mod, mod_stride);
+}
 int sr3_attention_f32(const float* qkv, int B, int N, int C, float* out, void* stream) {
   if (!qkv || !out) { set_error("null argument"); return SR3_E_BADARG; }
   return attention_forward(qkv, B, N, C, out, static_cast<hipStream_t>(stream));

@@ -84,8 +84,10 @@ int sr3_selftest_split3(int* scratch_dev, int* mismatches, void* stream) {
   return SR3_OK;
 }
 
-int sr3_plan_create(const sr3_unet_desc* desc, sr3_plan** out) {
+int sr3_plan_create(const sr3_unet_desc* desc, sr3_plan** out) { return sr3_plan_create_ex(desc, 0u, out); }
+int sr3_plan_create_ex(const sr3_unet_desc* desc, unsigned flags, sr3_plan** out) {
   if (!desc || !out) { set_error("null argument"); return SR3_E_BADARG; }
+  if (flags & ~SR3_UNET_FLAGS_ALL) { set_error("sr3_plan_create_ex: unknown flag bits 0x%x", flags & ~SR3_UNET_FLAGS_ALL); *out = nullptr; return SR3_E_BADARG; }
   sr3_plan* P = new (std::nothrow) sr3_plan();
   if (!P) { set_error("out of host memory"); return SR3_E_NOMEM; }
 #ifdef SR3_EXPERIMENTS
@@ -94,6 +96,7 @@ int sr3_plan_create(const sr3_unet_desc* desc, sr3_plan** out) {
   { const char* e = getenv("SR3_WINO2"); if (e) P->opt.wino2 = atoi(e); }
 #endif
   P->d = *desc;
+  P->scale_shift = (flags & SR3_UNET_SCALE_SHIFT_NORM) != 0;
   const int rc = build_structure(P);
   if (rc) { delete P; *out = nullptr; return rc; }
   *out = P;
@@ -147,6 +150,16 @@ int sr3_plan_op_side(sr3_plan* plan, int batch, int index, int* side_id, int* wa
   if (index < 0 || index >= (int)plan->ops.size()) { set_error("op index out of range"); return SR3_E_BADARG; }
   if (side_id) *side_id = plan->ops[index].side_id;
   if (wait_id) *wait_id = plan->ops[index].wait_id;
+  return SR3_OK;
+}
+int sr3_plan_op_fold(sr3_plan* plan, int batch, int index, int* fold, int* mod_row) {
+  if (!plan) { set_error("null argument"); return SR3_E_BADARG; }
+  if (const int rc = build_inspected(plan, batch)) return rc;
+  if (index < 0 || index >= (int)plan->ops.size()) { set_error("op index out of range"); return SR3_E_BADARG; }
+  const Op& o = plan->ops[index];
+  const bool own = o.kind == OP_FOLD;
+  if (fold) *fold = own ? 1 : (!o.fold_fused ? 0 : (o.kind == OP_CONV ? 2 : 3));
+  if (mod_row) *mod_row = own ? o.fold.mod_row : (o.fold_fused ? o.tail.mod_row : -1);
   return SR3_OK;
 }
 double sr3_plan_forward_flops(sr3_plan* plan, int batch) {

@@ -118,9 +118,10 @@ int build_structure(sr3_plan* P) {
   auto count_f = [&](const std::vector<Proto>& v) { for (auto& p : v) if (p.kind == L_RES) F += p.cout; };
   count_f(pd); count_f(pm); count_f(pu);
   P->F = F;
-  P->film_w = cur; cur += (size_t)F * inner;
+  const int fmul = P->scale_shift ? 2 : 1;      // rows per output channel of a block's projection
+  P->film_w = cur; cur += (size_t)P->film_rows() * inner;
   cur = (cur + 3) & ~(size_t)3;
-  P->film_b = cur; cur += (size_t)F;
+  P->film_b = cur; cur += (size_t)P->film_rows();
   int frow = 0;
 
   const char* emb = ddpm ? "time_mlp" : "noise_level_mlp";
@@ -160,12 +161,12 @@ int build_structure(sr3_plan* P) {
           std::string wn = rb + (ddpm ? ".mlp.1.weight" : ".noise_func.noise_func.0.weight");
           std::string bn = rb + (ddpm ? ".mlp.1.bias" : ".noise_func.noise_func.0.bias");
           snprintf(pi.name, sizeof(pi.name), "%s", wn.c_str());
-          pi.ndim = 2; pi.shape[0] = pr.cout; pi.shape[1] = inner; pi.pack = 0;
-          pi.numel = (size_t)pr.cout * inner; pi.offset = P->film_w + (size_t)frow * inner;
+          pi.ndim = 2; pi.shape[0] = fmul * pr.cout; pi.shape[1] = inner; pi.pack = 0;
+          pi.numel = (size_t)fmul * pr.cout * inner; pi.offset = P->film_w + (size_t)fmul * frow * inner;
           P->pindex[wn] = (int)P->params.size(); P->params.push_back(pi);
           memset(&pi, 0, sizeof(pi));
           snprintf(pi.name, sizeof(pi.name), "%s", bn.c_str());
-          pi.ndim = 1; pi.shape[0] = pr.cout; pi.pack = 0; pi.numel = (size_t)pr.cout; pi.offset = P->film_b + frow;
+          pi.ndim = 1; pi.shape[0] = fmul * pr.cout; pi.pack = 0; pi.numel = (size_t)fmul * pr.cout; pi.offset = P->film_b + fmul * frow;
           P->pindex[bn] = (int)P->params.size(); P->params.push_back(pi);
         }
         frow += pr.cout;
@@ -385,7 +386,7 @@ struct Builder {
   }
   int last_conv_op = -1, last_conv_out = -1, last_stats_op = -1, last_stats_h = -1;
   // plan option fold_fuse: can the kernel that completes `fresh` (one of x0 / x1) also do this fold?  Fills the op's `tail`.
-  bool fuse_fold_into(Op& L, int fresh, int x0, int x1, size_t gamma, size_t beta, size_t ss_rel, size_t mr_rel, bool has_mr) {
+  bool fuse_fold_into(Op& L, int fresh, int x0, int x1, size_t gamma, size_t beta, size_t ss_rel, size_t mr_rel, bool has_mr, int mod_row) {
     const int other = fresh == x0 ? x1 : x0;
     const int Cf = T[x0].C + (x1 >= 0 ? T[x1].C : 0);
     const int c_off = fresh == x0 ? 0 : T[x0].C;
@@ -395,13 +396,13 @@ struct Builder {
     FoldSpec& f = L.tail;
     f.Ctot = Cf; f.c_off = c_off;
     if (other >= 0) { f.ostat = T[other].stat_off; f.oC = T[other].C; f.oT = T[other].stat_T; f.o_off = fresh == x0 ? T[x0].C : 0; }
-    f.gamma = gamma; f.beta = beta; f.ss_rel = ss_rel; f.mr_rel = mr_rel; f.has_mr = has_mr;
+    f.gamma = gamma; f.beta = beta; f.ss_rel = ss_rel; f.mr_rel = mr_rel; f.has_mr = has_mr; f.mod_row = mod_row;
     T[fresh].stat_T = 1;              // the fused kernel holds whole-image sums: one partial per image
     return true;
   }
   // the GroupNorm fold of the virtual concat (x0|x1), as a launch of its own or the tail of the op that completes its last source;
-  // returns what the conv behind it reads (ConvSpec::gn)
-  FoldOut fold(int x0, int x1, size_t gamma, size_t beta) {
+  // returns what the conv behind it reads (ConvSpec::gn).  mod_row: the rows of the FiLM table that modulate the pairs (Op::Fold::mod_row)
+  FoldOut fold(int x0, int x1, size_t gamma, size_t beta, int mod_row = -1) {
     const int Cf = T[x0].C + (x1 >= 0 ? T[x1].C : 0);
     // the tables this fold writes, whichever kernel does it: per-GroupNorm slots in training, the one shared region (offset 0) in inference
     size_t ss_rel = 0, mr_rel = 0;
@@ -409,25 +410,25 @@ struct Builder {
       ss_rel = gn_cursor; gn_cursor += ((size_t)B * Cf * 2 * sizeof(float) + 255) & ~(size_t)255;
       mr_rel = mr_cursor; mr_cursor += ((size_t)B * P->d.norm_groups * 2 * sizeof(float) + 255) & ~(size_t)255;
     }
-    const FoldOut done = {ss_rel, mr_rel, gamma, beta};
+    const FoldOut done = {ss_rel, mr_rel, gamma, beta, mod_row};
     max_cin = std::max(max_cin, Cf);
     if (P->opt.fold_fuse && !ops.empty()) {
       // (a) the op just emitted is a split-K conv whose reduce writes the statistics of x0 / x1: its reduce folds too
       Op& L = ops.back();
       if (last_conv_op == (int)ops.size() - 1 && L.kind == OP_CONV && L.conv.ch.ksplit > 1 && L.conv.ostat != NO_OFF && (last_conv_out == x0 || last_conv_out == x1) &&
-          fuse_fold_into(L, last_conv_out, x0, x1, gamma, beta, ss_rel, mr_rel, train)) return done;
+          fuse_fold_into(L, last_conv_out, x0, x1, gamma, beta, ss_rel, mr_rel, train, mod_row)) return done;
     }
     ensure_stats(x0);
     if (x1 >= 0) ensure_stats(x1);
     // (b) ... or a stand-alone statistics pass of x0 / x1: it folds too
     if (P->opt.fold_fuse && !ops.empty() && last_stats_op == (int)ops.size() - 1 && (last_stats_h == x0 || last_stats_h == x1) &&
-        fuse_fold_into(ops.back(), last_stats_h, x0, x1, gamma, beta, ss_rel, mr_rel, train)) return done;
+        fuse_fold_into(ops.back(), last_stats_h, x0, x1, gamma, beta, ss_rel, mr_rel, train, mod_row)) return done;
     Op o; o.kind = OP_FOLD;
     Op::Fold& f = o.fold;
     f.stat0 = T[x0].stat_off; f.C0 = T[x0].C; f.T0 = T[x0].stat_T;
     if (x1 >= 0) { f.stat1 = T[x1].stat_off; f.C1 = T[x1].C; f.T1 = T[x1].stat_T; }
     f.pixels = T[x0].H * T[x0].W;
-    f.gamma = gamma; f.beta = beta; f.has_mr = train;
+    f.gamma = gamma; f.beta = beta; f.has_mr = train; f.mod_row = mod_row;
     o.ss_rel = ss_rel; o.mr_rel = mr_rel;
     ops.push_back(o);
     return done;
@@ -443,7 +444,7 @@ struct Builder {
     c = conv_shape(B, T[x0].H, T[x0].W, s.ups, s.stride, s.ksize, T[x0].C, x1 >= 0 ? T[x1].C : 0, Cout);
     const int Ho = c.Ho, Wo = c.Wo;
     const int out = make(Cout, Ho, Wo);
-    c.act = s.act; c.film_stride = P->F;
+    c.act = s.act; c.film_stride = P->film_rows();
     c.RC0 = s.r0 >= 0 ? T[s.r0].C : 0; c.RC1 = s.r1 >= 0 ? T[s.r1].C : 0;
     v.src0 = T[x0].off; v.src1 = off(x1);
     v.w = s.w; v.bias = s.bias;
@@ -509,8 +510,10 @@ struct Builder {
       r_side = conv(res_conv);
       if (ops.back().kind == OP_CONV && ops.back().conv.ch.ksplit == 1) { r_id = n_side++; ops.back().side_id = r_id; }
     }
-    const int h1 = conv({.x0 = x0, .x1 = x1, .Cout = R.cout, .act = 2, .gn = gn1, .w = R.c1_w, .bias = R.c1_b, .film_row = R.film_off, .want_stats = true});
-    const FoldOut gn2 = fold(h1, -1, R.gn2_w, R.gn2_b);
+    // the block's rows of the FiLM table: added to conv1's output, or (scale_shift: 2 Cout rows at 2 * film_off) modulating GN2's fold
+    const bool ssn = P->scale_shift;
+    const int h1 = conv({.x0 = x0, .x1 = x1, .Cout = R.cout, .act = 2, .gn = gn1, .w = R.c1_w, .bias = R.c1_b, .film_row = ssn ? -1 : R.film_off, .want_stats = true});
+    const FoldOut gn2 = fold(h1, -1, R.gn2_w, R.gn2_b, ssn ? 2 * R.film_off : -1);
     // block2's conv; what it adds: res_conv's output (its own launch), res_conv as a fused K-segment over the block input, or the input itself
     ConvSpec block2 = {.x0 = h1, .Cout = R.cout, .act = 2, .gn = gn2, .w = R.c2_w, .bias = R.c2_b, .want_stats = true, .drop_key = R.film_off};
     int out;
@@ -569,7 +572,7 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
   const int IH = geo ? plan_height(P) : d.image_size, IW = geo ? plan_width(P) : d.image_size;
 
   { Op o; o.kind = OP_EMBED; ops.push_back(o); }
-  bld.flops += 2.0 * B * (2.0 * 4 * inner * inner + (double)P->F * inner);
+  bld.flops += 2.0 * B * (2.0 * 4 * inner * inner + (double)P->film_rows() * inner);
 
   auto tap = [&](const std::string& name, int h) {
     if (!bld.train) P->taps.push_back({name, bld.T[h].off, bld.T[h].C, bld.T[h].H, bld.T[h].W});
@@ -702,10 +705,10 @@ int build_forward(sr3_plan* P, int B, int cond_channels) {
     return SR3_E_UNSUPPORTED;
   }
   if (P->opt.fork_side && !P->ops.empty() && P->ops[0].kind == OP_EMBED) {
-    // ... and the embedding MLP + FiLM projections (first op, reads only the noise level): beside the input conv, joined by the first conv that
-    // adds a FiLM row
+    // ... and the embedding MLP + FiLM projections (first op, reads only the noise level): beside the input conv, joined by the first op that
+    // reads the FiLM table (op_reads_film: a conv that adds a row, or a fold -- fused or its own launch -- that a row modulates)
     for (Op& o : P->ops)
-      if (o.kind == OP_CONV && o.conv.film_row >= 0) {
+      if (op_reads_film(o)) {
         if (o.wait_id < 0) { o.wait_id = bld.n_side; P->ops[0].side_id = bld.n_side++; }
         break;
       }
@@ -716,7 +719,7 @@ int build_forward(sr3_plan* P, int B, int cond_channels) {
   R.stats_off = off; off += (bld.stats_cursor + 255) & ~(size_t)255;
   R.ss_off = off; off += ((size_t)B * std::max(bld.max_cin, 4) * 2 * sizeof(float) + 255) & ~(size_t)255;
   R.temb_off = off; off += ((size_t)B * inner * sizeof(float) + 255) & ~(size_t)255;
-  R.film_off = off; off += ((size_t)B * P->F * sizeof(float) + 255) & ~(size_t)255;
+  R.film_off = off; off += ((size_t)B * P->film_rows() * sizeof(float) + 255) & ~(size_t)255;
   R.scratch_off = off; R.scratch_bytes = bld.max_scratch; off += (bld.max_scratch + 255) & ~(size_t)255;
   P->ws_bytes = off;
   P->flops = bld.flops;

@@ -27,7 +27,8 @@ struct ResLayer {
   std::string name;     // e.g. "downs.1"
   int cin, cout, skip;  // cin includes skip
   bool attn;
-  int film_off;         // row offset in the FiLM table
+  int film_off;         // channel offset among the res blocks: the sum of Cout of the blocks in front.  The block's first row of the FiLM
+                        // table (2 * film_off under scale_shift, where a block has 2 * Cout rows) and its dropout key
   size_t gn1_w, gn1_b, c1_w, c1_b, gn2_w, gn2_b, c2_w, c2_b, rc_w, rc_b;
   bool has_rc;
   size_t an_w, an_b, qkv_w, ao_w, ao_b;
@@ -65,6 +66,7 @@ struct FoldSpec {
   size_t gamma = 0, beta = 0;      // float offsets into the parameter arena
   size_t ss_rel = 0, mr_rel = 0;   // the consumer's tables, as Op::ss_rel / mr_rel
   bool has_mr = false;
+  int mod_row = -1;                // first row of the FiLM table that modulates the pairs (scale_shift; -1: none), as Op::Fold::mod_row
 };
 
 // numeric values are part of sr3_unet_forward_profile's op_kind encoding (kind * 10)
@@ -84,6 +86,8 @@ struct Op {
     int C0 = 0, C1 = 0, T0 = 0, T1 = 0, pixels = 0;      // channels, partials per image of either source
     size_t gamma = 0, beta = 0;
     bool has_mr = false;
+    int mod_row = -1;                // scale_shift: first row of the FiLM table that modulates the pairs -- the consumer's channel count of
+                                     // scales, then as many shifts (-1: none)
   } fold;
   struct Conv {
     ConvParams cp = {};              // geometry (pointers filled at launch)
@@ -107,6 +111,14 @@ struct Op {
   int side_id = -1, wait_id = -1;
 };
 
+// Does this op read the FiLM table the embed op writes?  A conv that adds a row to its output; a GroupNorm fold a row modulates, as a
+// launch of its own or as the tail of a split-K conv / a statistics pass.  THE rule the embed op's join is derived from (fork_side)
+inline bool op_reads_film(const Op& o) {
+  if (o.kind == OP_CONV && o.conv.film_row >= 0) return true;
+  if (o.kind == OP_FOLD && o.fold.mod_row >= 0) return true;
+  return (o.kind == OP_CONV || o.kind == OP_STATS) && o.fold_fused && o.tail.mod_row >= 0;
+}
+
 // every term is an integer far below 2^53: the sums over a launch list are exact in any order
 inline double conv_flops(const ConvParams& c) {
   return 2.0 * c.B * c.Ho * c.Wo * (double)c.Cout * ((double)(c.C0 + c.C1) * c.ksize * c.ksize + (c.x2_C0 + c.x2_C1));
@@ -122,7 +134,7 @@ struct Regions {
 };
 
 // What one GroupNorm fold of the forward walk wrote (Builder::fold returns it): its tables, as Op::ss_rel / mr_rel, and its parameters
-struct FoldOut { size_t ss_rel = 0, mr_rel = 0, gamma = 0, beta = 0; };
+struct FoldOut { size_t ss_rel = 0, mr_rel = 0, gamma = 0, beta = 0; int mod_row = -1; };      // mod_row: as Op::Fold::mod_row
 
 // One conv of the forward, for Builder::conv: sources and residuals are tensor handles (-1: absent), parameters arena offsets
 struct ConvSpec {
@@ -289,7 +301,10 @@ struct sr3_plan {
   std::vector<sr3_param_info> params;
   std::map<std::string, int> pindex;
   size_t param_floats = 0;
-  int F = 0;
+  int F = 0;                 // sum of Cout over the res blocks: what ResLayer::film_off and the dropout keys count in
+  bool scale_shift = false;  // SR3_UNET_SCALE_SHIFT_NORM (sr3_plan_create_ex): a block's projection has 2 Cout rows, scales then shifts, which
+                             // modulate its second GroupNorm -- GN2(h) (1 + scale) + shift -- in place of a row added to conv1's output
+  int film_rows() const { return scale_shift ? 2 * F : F; }      // rows of the FiLM weight, bias, table and gradient table
   size_t film_w = 0, film_b = 0;
   size_t emb_w1 = 0, emb_b1 = 0, emb_w2 = 0, emb_b2 = 0;
   std::vector<Layer> downs, mid, ups;

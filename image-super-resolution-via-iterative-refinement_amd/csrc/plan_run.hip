@@ -32,6 +32,7 @@ static FoldTail make_fold_tail(const FoldSpec& s, const Bound& b) {
   f.gamma = b.params + s.gamma; f.beta = b.params + s.beta; f.eps = 1e-5f;
   f.ss = reinterpret_cast<float*>(b.ws + b.R.ss_off + s.ss_rel);
   f.mr = s.has_mr ? reinterpret_cast<float*>(b.ws + b.R.mr_off + s.mr_rel) : nullptr;
+  if (s.mod_row >= 0) { f.mod = b.film + s.mod_row; f.mod_stride = b.P->film_rows(); }
   return f;
 }
 
@@ -74,7 +75,7 @@ static int launch_embed(const Op&, const Bound& b) {
   e.level = f.level; e.tstep = f.tstep; e.level_table = f.level_table; e.step_dev = f.step_dev; e.t_map = f.t_map; e.freq = f.freq;
   e.step_out = f.fuse ? const_cast<int*>(f.fuse->step_cur) : nullptr;
   e.w1 = b.params + P->emb_w1; e.b1 = b.params + P->emb_b1; e.w2 = b.params + P->emb_w2; e.b2 = b.params + P->emb_b2;
-  e.wf = b.params + P->film_w; e.bf = b.params + P->film_b; e.F = P->F;
+  e.wf = b.params + P->film_w; e.bf = b.params + P->film_b; e.F = P->film_rows();
   e.temb = reinterpret_cast<float*>(b.ws + b.R.temb_off); e.film = b.film;
   return embed_forward(e, b.st);
 }
@@ -104,7 +105,7 @@ static int launch_fold(const Op& o, const Bound& b) {
   const Op::Fold& v = o.fold;
   return gn_finalize(bind<const double>(b.stats, v.stat0), v.C0, v.T0, bind<const double>(b.stats, v.stat1), v.C1, v.T1, b.f.batch, v.pixels,
                      b.P->d.norm_groups, b.params + v.gamma, b.params + v.beta, 1e-5f, bind<float>(b.ws, b.R.ss_off + o.ss_rel), b.st,
-                     v.has_mr ? bind<float>(b.ws, b.R.mr_off + o.mr_rel) : nullptr);
+                     v.has_mr ? bind<float>(b.ws, b.R.mr_off + o.mr_rel) : nullptr, v.mod_row >= 0 ? b.film + v.mod_row : nullptr, b.P->film_rows());
 }
 
 static int launch_conv(const Op& o, const Bound& b) {

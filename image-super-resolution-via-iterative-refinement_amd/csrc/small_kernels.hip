@@ -3,6 +3,8 @@
 // timestep embedding with every FiLM projection, and the fused reverse-step / q_sample updates.
 #include <string.h>
 
+#include <type_traits>
+
 #include "conv_prologue.h"
 #include "step_tail.h"
 
@@ -88,11 +90,24 @@ int chan_stats(const float* x, int B, int HW, int C, double* stat, hipStream_t s
 // virtual concat [src0 | src1] in a fixed order, then writes scale = rstd * gamma and
 // shift = beta - mean * scale per channel.  Biased variance, eps inside the sqrt (torch GroupNorm).
 // ---------------------------------------------------------------------------------------------
+// Scale-shift modulation of a folded GroupNorm (ADM's use_scale_shift_norm: GN(h) (1 + s) + t as one affine per (image, channel)):
+// sc' = sc m, sh' = sh m + t with m = 1 + s, every step rounded on its own in this order -- THE definition, shared by the three kernels
+// that write pairs (k_gn_finalize, both forms of k_rows_fold), which therefore write the same bits.  mod_b: image b's scales [C] then
+// shifts [C]
+__device__ __forceinline__ void fold_modulate(float& sc, float& sh, const float* __restrict__ mod_b, int C, int c) {
+  const float m = add_rn(1.0f, mod_b[c]);
+  sc = mul_rn(sc, m);
+  sh = fmaf(sh, m, mod_b[C + c]);
+}
+
+// MOD: the pairs are modulated by mod (fold_modulate); the plain instantiation reads neither mod nor mod_stride
+template <bool MOD>
 __global__ __launch_bounds__(64) void k_gn_finalize(const double* __restrict__ st0, int C0, int T0,
                                                      const double* __restrict__ st1, int C1, int T1, int HW,
                                                      int groups, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, float eps,
-                                                     float* __restrict__ ss, float* __restrict__ mr) {
+                                                     float* __restrict__ ss, float* __restrict__ mr,
+                                                     const float* __restrict__ mod, int mod_stride) {
   const int C = C0 + C1;
   const int b = blockIdx.x / groups, g = blockIdx.x - b * groups;
   const int cpg = C / groups;
@@ -133,19 +148,28 @@ __global__ __launch_bounds__(64) void k_gn_finalize(const double* __restrict__ s
   if (mr && lane == 0) { mr[((size_t)b * groups + g) * 2] = (float)mean; mr[((size_t)b * groups + g) * 2 + 1] = rstd; }
   for (int k = lane; k < cpg; k += 64) {
     const int c = g * cpg + k;
-    const float sc = rstd * gamma[c];
-    float* o = ss + ((size_t)b * C + c) * 2;
-    o[0] = sc;
-    o[1] = beta[c] - (float)mean * sc;
+    if constexpr (MOD) {
+      float sc = rstd * gamma[c];
+      float sh = beta[c] - (float)mean * sc;
+      fold_modulate(sc, sh, mod + (size_t)b * mod_stride, C, c);
+      float* o = ss + ((size_t)b * C + c) * 2;
+      o[0] = sc;
+      o[1] = sh;
+    } else {
+      const float sc = rstd * gamma[c];
+      float* o = ss + ((size_t)b * C + c) * 2;
+      o[0] = sc;
+      o[1] = beta[c] - (float)mean * sc;
+    }
   }
 }
 
 int gn_finalize(const double* stat0, int C0, int T0, const double* stat1, int C1, int T1, int B, int HW, int groups,
-                const float* gamma, const float* beta, float eps, float* ss, hipStream_t st, float* mr) {
+                const float* gamma, const float* beta, float eps, float* ss, hipStream_t st, float* mr, const float* mod, int mod_stride) {
   const int C = C0 + C1;
   if (groups <= 0 || C % groups) { set_error("gn_finalize: C=%d not divisible by groups=%d", C, groups); return SR3_E_BADARG; }
-  hipLaunchKernelGGL(k_gn_finalize, dim3(B * groups), dim3(64), 0, st, stat0, C0, T0, stat1, C1, T1, HW, groups,
-                     gamma, beta, eps, ss, mr);
+  hipLaunchKernelGGL(mod ? k_gn_finalize<true> : k_gn_finalize<false>, dim3(B * groups), dim3(64), 0, st, stat0, C0, T0, stat1, C1, T1, HW, groups,
+                     gamma, beta, eps, ss, mr, mod, mod_stride);
   SR3_LAUNCH_CHECK("k_gn_finalize");
   return SR3_OK;
 }
@@ -158,9 +182,10 @@ int gn_finalize(const double* stat0, int C0, int T0, const double* stat1, int C1
 // them as the tensor's partials (T = 1), adds the group's channels of the OTHER concat source from its partials, and writes the
 // consumer's (scale, shift) pairs: what k_gn_finalize would have done in a launch of its own.
 // ---------------------------------------------------------------------------------------------
-template <bool REDUCE>
-__global__ __launch_bounds__(256) void k_rows_fold(const ConvParams p, const FoldTail f, const float* __restrict__ x, int C, int HW,
-                                                    double* __restrict__ stat) {
+// MOD: the pairs are modulated (fold_modulate; f is then the FoldTail with its rows).  The plain instantiations take the plain struct
+template <bool REDUCE, bool MOD>
+__global__ __launch_bounds__(256) void k_rows_fold(const ConvParams p, const std::conditional_t<MOD, FoldTail, FoldTailPlain> f,
+                                                    const float* __restrict__ x, int C, int HW, double* __restrict__ stat) {
   __shared__ double red[256 * 8];
   __shared__ double chs[2 * 128];       // per-channel {sum, sumsq} of the group, concat order
   __shared__ float mrs[2];
@@ -271,10 +296,19 @@ __global__ __launch_bounds__(256) void k_rows_fold(const ConvParams p, const Fol
   __syncthreads();
   if (tid < cpg) {
     const int c = glo + tid;
-    const float sc = mrs[1] * f.gamma[c];
-    float* o = f.ss + ((size_t)b * f.Ctot + c) * 2;
-    o[0] = sc;
-    o[1] = f.beta[c] - mrs[0] * sc;
+    if constexpr (MOD) {
+      float sc = mrs[1] * f.gamma[c];
+      float sh = f.beta[c] - mrs[0] * sc;
+      fold_modulate(sc, sh, f.mod + (size_t)b * f.mod_stride, f.Ctot, c);
+      float* o = f.ss + ((size_t)b * f.Ctot + c) * 2;
+      o[0] = sc;
+      o[1] = sh;
+    } else {
+      const float sc = mrs[1] * f.gamma[c];
+      float* o = f.ss + ((size_t)b * f.Ctot + c) * 2;
+      o[0] = sc;
+      o[1] = f.beta[c] - mrs[0] * sc;
+    }
   }
 }
 
@@ -357,7 +391,8 @@ int chan_stats_fold(const float* x, int B, int HW, int C, double* stat, const Fo
   ConvParams p;
   memset(&p, 0, sizeof(p));
   p.B = B;
-  hipLaunchKernelGGL(k_rows_fold<false>, dim3(B * f.groups), dim3(256), 0, st, p, f, x, C, HW, stat);
+  if (f.mod) hipLaunchKernelGGL((k_rows_fold<false, true>), dim3(B * f.groups), dim3(256), 0, st, p, f, x, C, HW, stat);
+  else hipLaunchKernelGGL((k_rows_fold<false, false>), dim3(B * f.groups), dim3(256), 0, st, p, static_cast<const FoldTailPlain&>(f), x, C, HW, stat);
   SR3_LAUNCH_CHECK("k_rows_fold");
   return SR3_OK;
 }
@@ -366,8 +401,10 @@ int splitk_reduce(const ConvParams& p, hipStream_t st) {
   if (p.fold) {      // the reduce per (image, consumer group) + the next op's GroupNorm fold
     const FoldTail& f = *p.fold;
     if (!fold_tail_fits(p.Cout, f.Ctot, f.c_off, f.groups) || !p.ostat) { set_error("splitk_reduce_fold: grouping does not fit"); return SR3_E_UNSUPPORTED; }
-    hipLaunchKernelGGL(k_rows_fold<true>, dim3(p.B * f.groups), dim3(256), 0, st, p, f, static_cast<const float*>(nullptr), p.Cout,
-                       p.Ho * p.Wo, p.ostat);
+    if (f.mod) hipLaunchKernelGGL((k_rows_fold<true, true>), dim3(p.B * f.groups), dim3(256), 0, st, p, f, static_cast<const float*>(nullptr), p.Cout,
+                                  p.Ho * p.Wo, p.ostat);
+    else hipLaunchKernelGGL((k_rows_fold<true, false>), dim3(p.B * f.groups), dim3(256), 0, st, p, static_cast<const FoldTailPlain&>(f),
+                            static_cast<const float*>(nullptr), p.Cout, p.Ho * p.Wo, p.ostat);
     SR3_LAUNCH_CHECK("k_rows_fold");
     return SR3_OK;
   }

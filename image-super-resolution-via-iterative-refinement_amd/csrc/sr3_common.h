@@ -155,7 +155,7 @@ inline void dropout_consts(float p, unsigned* thresh, float* scale) {
 // or as the stand-alone statistics pass -- so a workgroup holds the whole-image sums of its group's channels: it writes them as this
 // tensor's partials (one per image: T = 1), adds the other concat source's channels of the group from ITS partials, and writes the
 // consumer's (scale, shift) pairs.  No atomics, fixed summation order; one launch instead of two (reduce / statistics + fold).
-struct FoldTail {
+struct FoldTailPlain {
   int groups, Ctot, c_off;     // the consumer's GroupNorm: `groups` over Ctot channels; this tensor is channels [c_off, c_off + C) of them
   const double* ostat;         // the other concat source's partials [B][oT][oC][2], its channels at [o_off, o_off + oC); null: single source
   int oC, oT, o_off;
@@ -164,6 +164,13 @@ struct FoldTail {
   float eps;
   float* ss;                   // out: [B][Ctot][2]
   float* mr;                   // out: [B][groups][2] (mean, rstd) or null (training keeps them for the backward)
+};
+// ... with a scale-shift modulation of the consumer's GroupNorm (plan flag SR3_UNET_SCALE_SHIFT_NORM; fold_modulate, small_kernels.hip):
+// image b's scales [Ctot] then shifts [Ctot] at mod + b * mod_stride; null: none.  The kernels without a modulation take the plain
+// struct, so their argument layout is what it was
+struct FoldTail : FoldTailPlain {
+  const float* mod;
+  int mod_stride;
 };
 bool fold_tail_fits(int C, int Ctot, int c_off, int groups);
 // stand-alone form: statistics of x [B][HW][C] (partials [B][1][C][2] into `stat`) + the fold
@@ -330,7 +337,8 @@ int chan_stats_slices(int B, int HW, int C);
 int chan_stats(const float* x, int B, int HW, int C, double* stat, hipStream_t st);
 // GroupNorm fold: partial stats of up to two concat sources + gamma/beta -> ss[B][C0+C1][2]
 int gn_finalize(const double* stat0, int C0, int T0, const double* stat1, int C1, int T1, int B, int HW, int groups,
-                const float* gamma, const float* beta, float eps, float* ss, hipStream_t st, float* mr = nullptr);
+                const float* gamma, const float* beta, float eps, float* ss, hipStream_t st, float* mr = nullptr,
+                const float* mod = nullptr, int mod_stride = 0);      // mod: scale-shift modulation rows (fold_modulate), null: none
 // partials per image the halo conv writes into ConvParams::ostat for this geometry
 int halo_stats_slices(const HaloGeom& g);
 // first conv of the UNet: NCHW inputs (virtual concat of a: Ca, b: Cb channels), 3x3 pad 1,

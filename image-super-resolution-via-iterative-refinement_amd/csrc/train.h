@@ -12,10 +12,13 @@ inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 // GroupNorm(+SiLU) backward over the virtual concat (x0|x1): dA (grad w.r.t. the activated input) is
 // overwritten with du, partial sums go to `part`, group sums to gs[B][G][2], parameter gradients to
 // dgamma/dbeta[C], and dx0/dx1 (+=) receive the input gradient.  mr[B][G][2] = (mean, rstd).
+// ... of a GroupNorm folded under a scale-shift modulation (fold_modulate, small_kernels.hip): the rows (image b's scales [C] then shifts
+// [C] at mod + b * stride), the GroupNorm's beta, and where the rows' gradients go (dmod: the layout and stride of mod)
+struct ModBwd { const float* mod; int stride; const float* beta; float* dmod; };
 int act_bwd(float* dA, const float* x0, const float* x1, int C0, int C1, int B, int HW, const float* ss, const float* mr,
             int groups, int act, const float* gamma, double* part, double* gs, float* dgamma, float* dbeta, float* dx0,
             float* dx1, hipStream_t st, unsigned drop_seed = 0, unsigned drop_thresh = 0, float drop_scale = 1.f,
-            float* aout = nullptr, bool acc0 = true, bool acc1 = true);      // aout: also write a = dropout(act(x*scale+shift)) (what apply_act would, in the same pass; round 6)
+            float* aout = nullptr, bool acc0 = true, bool acc1 = true, const ModBwd* md = nullptr);      // aout: also write a = dropout(act(x*scale+shift)) (what apply_act would, in the same pass; round 6)
 // a = dropout(act(x*scale+shift)) over the virtual concat, materialised for the weight-gradient GEMM
 int apply_act(const float* x0, const float* x1, int C0, int C1, int B, int HW, const float* ss, int act, unsigned drop_seed,
               unsigned drop_thresh, float drop_scale, float* out, hipStream_t st);

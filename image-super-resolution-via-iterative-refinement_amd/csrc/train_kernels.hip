@@ -105,9 +105,16 @@ __global__ __launch_bounds__(256) void k_act_bwd_reduce(float* __restrict__ dA, 
   }
 }
 
+// The factor a scale-shift modulation puts on gamma_c for image b (fold_modulate, small_kernels.hip): m = 1 + s as the forward rounded
+// it.  mod_b: image b's scales [C] then shifts [C].  The MOD instantiations of the kernels below use gamma_c m where the plain ones use
+// gamma_c, in double; the plain ones read neither mod nor mod_stride
+__device__ __forceinline__ double mod_factor(const float* __restrict__ mod_b, int c) { return (double)add_rn(1.0f, mod_b[c]); }
+
 // T2a: per (image, group): S1 = sum_c gamma_c * A_c, S2 = sum_c gamma_c * B_c  -> gs[B][G][2] (double)
+template <bool MOD>
 __global__ __launch_bounds__(64) void k_gn_bwd_group(const double* __restrict__ part, int C, int T, int groups,
-                                                      const float* __restrict__ gamma, double* __restrict__ gs) {
+                                                      const float* __restrict__ gamma, double* __restrict__ gs,
+                                                      const float* __restrict__ mod, int mod_stride) {
   const int b = blockIdx.x / groups, g = blockIdx.x - b * groups;
   const int cpg = C / groups;
   const int lane = threadIdx.x;
@@ -116,7 +123,8 @@ __global__ __launch_bounds__(64) void k_gn_bwd_group(const double* __restrict__ 
     const int k = idx / T, t = idx - k * T;
     const int c = g * cpg + k;
     const double* q = part + (((size_t)b * T + t) * C + c) * 2;
-    const double gm = (double)gamma[c];
+    double gm = (double)gamma[c];
+    if constexpr (MOD) gm *= mod_factor(mod + (size_t)b * mod_stride, c);
     a += gm * q[0]; bb += gm * q[1];
   }
 #pragma unroll
@@ -125,14 +133,23 @@ __global__ __launch_bounds__(64) void k_gn_bwd_group(const double* __restrict__ 
 }
 
 // T2b / T8: per channel: out0[c] (+)= sum_{b,t} part[..][c][0] ; out1[c] (+)= sum part[..][c][1]  (either may be null)
+// MOD: image b's partials weighted by mod_factor (the gradients of gamma and beta under a scale-shift modulation); a factor of exactly
+// 1 -- a zero scale row -- gives the plain sums' bits
+template <bool MOD>
 __global__ __launch_bounds__(64) void k_part_colsum(const double* __restrict__ part, int B, int C, int T,
-                                                     float* __restrict__ out0, float* __restrict__ out1) {
+                                                     float* __restrict__ out0, float* __restrict__ out1,
+                                                     const float* __restrict__ mod, int mod_stride) {
   const int c = blockIdx.x;
   const int lane = threadIdx.x;
   double a = 0.0, bb = 0.0;
   for (int idx = lane; idx < B * T; idx += 64) {
     const double* q = part + ((size_t)idx * C + c) * 2;
-    a += q[0]; bb += q[1];
+    if constexpr (MOD) {
+      const double m = mod_factor(mod + (size_t)(idx / T) * mod_stride, c);
+      a += m * q[0]; bb += m * q[1];
+    } else {
+      a += q[0]; bb += q[1];
+    }
   }
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) { a += __shfl_xor(a, m); bb += __shfl_xor(bb, m); }
@@ -153,16 +170,41 @@ __global__ __launch_bounds__(256) void k_part_imgsum(const double* __restrict__ 
   out[(size_t)b * stride + c] = (float)a;
 }
 
+// The gradients of a scale-shift modulation's rows, from the partials {sum du, sum du xhat}: per (image, channel), in double, rounded once,
+//   d shift = sum_t part[0] ;  d scale = sum du GN(x) = gamma_c sum_t part[1] + beta_c sum_t part[0]      (GN(x) = xhat gamma + beta)
+// into dmod_b[c] (scales) and dmod_b[C + c] (shifts), the layout of mod
+__global__ __launch_bounds__(256) void k_part_modgrad(const double* __restrict__ part, int B, int C, int T, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, float* __restrict__ dmod, int mod_stride) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= B * C) return;
+  const int b = idx / C, c = idx - b * C;
+  double a = 0.0, bb = 0.0;
+  for (int t = 0; t < T; ++t) {
+    const double* q = part + (((size_t)b * T + t) * C + c) * 2;
+    a += q[0]; bb += q[1];
+  }
+  float* o = dmod + (size_t)b * mod_stride;
+  o[c] = (float)((double)gamma[c] * bb + (double)beta[c] * a);
+  o[C + c] = (float)a;
+}
+
 // T3: dx(src) += rstd * (gamma*du - (S1 + xhat*S2)/n), routed to the two concat sources.
 // The two terms cancel heavily (GroupNorm's backward projects the x-hat and the constant component out of du), so the
 // per-(image, group) coefficients stay in double and the expression is evaluated in double and rounded once -- what
 // torch's CPU GroupNorm backward does (acc_type<float> = double for its c1 / c2 / c3 coefficients).  With fp32
 // coefficients the rounding of S2 is a perturbation along x-hat that is coherent over a whole (image, group) and is
 // amplified by sqrt(B H W) in the weight gradient of the conv that produced x (measured 1.2e-4 normwise at B = 64).
+// GAMMA: the plain pointer, or GammaMod -- gamma_c mod_factor stands where gamma_c does, in double.  (A type in gamma's own slot, not
+// arguments behind the others as in the kernels above: this kernel's grid-stride loop reads the launch dimensions, which sit behind
+// the explicit arguments, so the plain instantiation keeps its argument block -- and its instruction stream -- only this way)
+struct GammaMod { const float* gamma; const float* mod; int mod_stride; };
+__device__ __forceinline__ double gamma_at(const float* __restrict__ gamma, int, int c) { return (double)gamma[c]; }
+__device__ __forceinline__ double gamma_at(const GammaMod& g, int b, int c) { return (double)g.gamma[c] * mod_factor(g.mod + (size_t)b * g.mod_stride, c); }
+template <class GAMMA>
 __global__ __launch_bounds__(256) void k_gn_bwd_apply(const float* __restrict__ du, const float* __restrict__ x0,
                                                        const float* __restrict__ x1, int C0, int C1, int HW,
                                                        const float* __restrict__ mr, const double* __restrict__ gs,
-                                                       int groups, const float* __restrict__ gamma,
+                                                       int groups, const GAMMA gamma,
                                                        float* __restrict__ dx0, float* __restrict__ dx1,
                                                        size_t total4, int acc0, int acc1) {
   const int C = C0 + C1;
@@ -186,7 +228,7 @@ __global__ __launch_bounds__(256) void k_gn_bwd_apply(const float* __restrict__ 
       const double mu = (double)mr[((size_t)b * groups + g) * 2], rs = (double)mr[((size_t)b * groups + g) * 2 + 1];
       const double S1 = gs[((size_t)b * groups + g) * 2], S2 = gs[((size_t)b * groups + g) * 2 + 1];
       const double xh = ((double)xv[e] - mu) * rs;
-      o[e] += (float)(rs * ((double)gamma[c + e] * (double)g4[e] - (S1 + xh * S2) * inv_n));
+      o[e] += (float)(rs * (gamma_at(gamma, b, c + e) * (double)g4[e] - (S1 + xh * S2) * inv_n));
     }
     *reinterpret_cast<f32x4*>(dst.base + pix * dst.C + dst.c) = o;
   }
@@ -444,7 +486,8 @@ static void stats_geometry(int B, int HW, int C, int* LQ_, int* cblocks_, int* p
 
 int act_bwd(float* dA, const float* x0, const float* x1, int C0, int C1, int B, int HW, const float* ss, const float* mr,
             int groups, int act, const float* gamma, double* part, double* gs, float* dgamma, float* dbeta, float* dx0,
-            float* dx1, hipStream_t st, unsigned drop_seed, unsigned drop_thresh, float drop_scale, float* aout, bool acc0, bool acc1) {
+            float* dx1, hipStream_t st, unsigned drop_seed, unsigned drop_thresh, float drop_scale, float* aout, bool acc0, bool acc1,
+            const ModBwd* md) {
   const int C = C0 + C1;
   if ((C0 & 3) || (C1 & 3)) { set_error("act_bwd: channels %% 4"); return SR3_E_UNSUPPORTED; }
   int LQ, cblocks, ppb, T;
@@ -452,13 +495,22 @@ int act_bwd(float* dA, const float* x0, const float* x1, int C0, int C1, int B, 
   hipLaunchKernelGGL(k_act_bwd_reduce, dim3(T, cblocks, B), dim3(256), 0, st, dA, x0, x1, C0, C1, HW, LQ, ppb, ss, mr,
                      groups, act, drop_seed, drop_thresh, drop_scale, part, aout);
   SR3_LAUNCH_CHECK("k_act_bwd_reduce");
-  hipLaunchKernelGGL(k_gn_bwd_group, dim3(B * groups), dim3(64), 0, st, part, C, T, groups, gamma, gs);
+  // md: the GroupNorm was folded under a scale-shift modulation (the MOD instantiations), whose rows' gradients come out of the same partials
+  const float* mod = md ? md->mod : nullptr;
+  const int mstride = md ? md->stride : 0;
+  hipLaunchKernelGGL(md ? k_gn_bwd_group<true> : k_gn_bwd_group<false>, dim3(B * groups), dim3(64), 0, st, part, C, T, groups, gamma, gs, mod, mstride);
   SR3_LAUNCH_CHECK("k_gn_bwd_group");
-  hipLaunchKernelGGL(k_part_colsum, dim3(C), dim3(64), 0, st, part, B, C, T, dbeta, dgamma);
+  hipLaunchKernelGGL(md ? k_part_colsum<true> : k_part_colsum<false>, dim3(C), dim3(64), 0, st, part, B, C, T, dbeta, dgamma, mod, mstride);
   SR3_LAUNCH_CHECK("k_part_colsum");
+  if (md) {
+    hipLaunchKernelGGL(k_part_modgrad, dim3((B * C + 255) / 256), dim3(256), 0, st, part, B, C, T, gamma, md->beta, md->dmod, mstride);
+    SR3_LAUNCH_CHECK("k_part_modgrad");
+  }
   const size_t total4 = (size_t)B * HW * (C >> 2);
-  hipLaunchKernelGGL(k_gn_bwd_apply, dim3(ew_blocks(total4)), dim3(256), 0, st, dA, x0, x1, C0, C1, HW, mr, gs, groups,
-                     gamma, dx0, dx1, total4, acc0 ? 1 : 0, acc1 ? 1 : 0);
+  if (md) hipLaunchKernelGGL(k_gn_bwd_apply<GammaMod>, dim3(ew_blocks(total4)), dim3(256), 0, st, dA, x0, x1, C0, C1, HW, mr, gs, groups,
+                             GammaMod{gamma, mod, mstride}, dx0, dx1, total4, acc0 ? 1 : 0, acc1 ? 1 : 0);
+  else hipLaunchKernelGGL(k_gn_bwd_apply<const float* __restrict__>, dim3(ew_blocks(total4)), dim3(256), 0, st, dA, x0, x1, C0, C1, HW, mr, gs, groups,
+                          gamma, dx0, dx1, total4, acc0 ? 1 : 0, acc1 ? 1 : 0);
   SR3_LAUNCH_CHECK("k_gn_bwd_apply");
   return SR3_OK;
 }
@@ -503,7 +555,7 @@ int colsums(const float* g, int B, int HW, int C, double* part, float* dbias, fl
   if (rc) return rc;
   const int T = chan_stats_slices(B, HW, C);
   if (dbias) {
-    hipLaunchKernelGGL(k_part_colsum, dim3(C), dim3(64), 0, st, part, B, C, T, dbias, (float*)nullptr);
+    hipLaunchKernelGGL(k_part_colsum<false>, dim3(C), dim3(64), 0, st, part, B, C, T, dbias, (float*)nullptr, (const float*)nullptr, 0);
     SR3_LAUNCH_CHECK("k_part_colsum");
   }
   if (dfilm) {
@@ -573,12 +625,14 @@ extern "C" size_t sr3_groupnorm_act_bwd_scratch_bytes(int B, int HW, int C, int 
   if (check_gn_bwd_shape("sr3_groupnorm_act_bwd_scratch_bytes", C, 0, B, HW, groups)) return 0;
   return al256(act_bwd_part_bytes(B, HW, C)) + (size_t)B * groups * 2 * sizeof(double);
 }
-extern "C" int sr3_groupnorm_act_bwd_f32(float* dA, const float* x0, int C0, const float* x1, int C1, int B, int HW, const float* ss,
-                                         const float* mr, int groups, int act, const float* gamma, unsigned drop_seed, float drop_p,
-                                         float* dgamma, float* dbeta, float* dx0, int acc0, float* dx1, int acc1, float* aout,
-                                         void* scratch, size_t scratch_bytes, void* stream) {
+namespace {
+// sr3_groupnorm_act_bwd_f32 (md null) and sr3_groupnorm_act_bwd_mod_f32: one list of checks, then act_bwd
+int gn_act_bwd_entry(const char* who, float* dA, const float* x0, int C0, const float* x1, int C1, int B, int HW, const float* ss,
+                     const float* mr, int groups, int act, const float* gamma, unsigned drop_seed, float drop_p,
+                     float* dgamma, float* dbeta, float* dx0, int acc0, float* dx1, int acc1, float* aout,
+                     void* scratch, size_t scratch_bytes, const sr3::ModBwd* md, void* stream) {
   using namespace sr3;
-  const char* who = "sr3_groupnorm_act_bwd_f32";
+  if (md && (!md->mod || !md->dmod || !md->beta)) { set_error("%s: beta / mod / dmod is NULL", who); return SR3_E_BADARG; }
   if (!dA || !x0 || !ss || !mr || !gamma || !dgamma || !dbeta || !dx0 || !scratch || (C1 > 0 && (!x1 || !dx1))) {
     set_error("%s: dA / x0 / ss / mr / gamma / dgamma / dbeta / dx0 / scratch (or x1 / dx1 with C1 > 0) is NULL", who);
     return SR3_E_BADARG;
@@ -592,9 +646,30 @@ extern "C" int sr3_groupnorm_act_bwd_f32(float* dA, const float* x0, int C0, con
   unsigned thresh;
   float scale;
   dropout_consts(drop_p, &thresh, &scale);       // the step's mapping p -> (threshold, scale)
+  if (md && md->stride < 2 * (C0 + C1)) { set_error("%s: mod_stride %d is below the 2 x %d values of an image", who, md->stride, C0 + C1); return SR3_E_BADARG; }
   char* s = static_cast<char*>(scratch);
   return act_bwd(dA, x0, x1, C0, C1, B, HW, ss, mr, groups, act, gamma, reinterpret_cast<double*>(s), reinterpret_cast<double*>(s + part),
-                 dgamma, dbeta, dx0, dx1, static_cast<hipStream_t>(stream), drop_seed, thresh, scale, aout, acc0 != 0, acc1 != 0);
+                 dgamma, dbeta, dx0, dx1, static_cast<hipStream_t>(stream), drop_seed, thresh, scale, aout, acc0 != 0, acc1 != 0, md);
+}
+}  // namespace
+extern "C" int sr3_groupnorm_act_bwd_f32(float* dA, const float* x0, int C0, const float* x1, int C1, int B, int HW, const float* ss,
+                                         const float* mr, int groups, int act, const float* gamma, unsigned drop_seed, float drop_p,
+                                         float* dgamma, float* dbeta, float* dx0, int acc0, float* dx1, int acc1, float* aout,
+                                         void* scratch, size_t scratch_bytes, void* stream) {
+  return gn_act_bwd_entry("sr3_groupnorm_act_bwd_f32", dA, x0, C0, x1, C1, B, HW, ss, mr, groups, act, gamma, drop_seed, drop_p, dgamma, dbeta, dx0,
+                          acc0, dx1, acc1, aout, scratch, scratch_bytes, nullptr, stream);
+}
+// ... of a GroupNorm folded under a scale-shift modulation (sr3_groupnorm_fold_mod_f32): ss holds the modulated pairs; beta and the rows
+// `mod` give the gradients of the rows, dmod (same layout and stride; only the 2 C entries per image are written).  The scratch is the
+// plain entry's (sr3_groupnorm_act_bwd_scratch_bytes)
+extern "C" int sr3_groupnorm_act_bwd_mod_f32(float* dA, const float* x0, int C0, const float* x1, int C1, int B, int HW, const float* ss,
+                                             const float* mr, int groups, int act, const float* gamma, unsigned drop_seed, float drop_p,
+                                             float* dgamma, float* dbeta, float* dx0, int acc0, float* dx1, int acc1, float* aout,
+                                             void* scratch, size_t scratch_bytes, const float* beta, const float* mod, int mod_stride,
+                                             float* dmod, void* stream) {
+  const sr3::ModBwd md = {mod, mod_stride, beta, dmod};
+  return gn_act_bwd_entry("sr3_groupnorm_act_bwd_mod_f32", dA, x0, C0, x1, C1, B, HW, ss, mr, groups, act, gamma, drop_seed, drop_p, dgamma, dbeta,
+                          dx0, acc0, dx1, acc1, aout, scratch, scratch_bytes, &md, stream);
 }
 
 extern "C" int sr3_grad_route_f32(const float* g, int C0, int C1, int B, int Hs, int Ws, int ups, float* d0, int acc0, float* d1, int acc1,

@@ -224,7 +224,7 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
   R.ss_off = off; off += al(fw.gn_bytes);                  // per-GroupNorm scale / shift tables, kept for the backward
   R.mr_off = off; off += al(fw.mr_bytes);                  // ... and mean / rstd tables
   R.temb_off = off; off += al((size_t)B * inner * sizeof(float));
-  R.film_off = off; off += al((size_t)B * P->F * sizeof(float));
+  R.film_off = off; off += al((size_t)B * P->film_rows() * sizeof(float));
   R.scratch_bytes = std::max(fw.max_scratch, max_bscratch);      // the forward's split-K region doubles as the backward's
   R.scratch_off = off; off += al(R.scratch_bytes);
   P->t_dA_off = off; off += al(max_dA);
@@ -236,7 +236,7 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
   P->t_slab_off = off; off += al(max_slab);
   P->t_part_off = off; off += al(max_part);
   P->t_gs_off = off; off += al((size_t)B * G * 2 * sizeof(double));
-  P->t_dfilm_off = off; off += al((size_t)B * P->F * sizeof(float));
+  P->t_dfilm_off = off; off += al((size_t)B * P->film_rows() * sizeof(float));
   P->t_xnoisy_off = off; off += al((size_t)B * (d.in_channel - cond_channels) * S2 * sizeof(float));
   P->t_eps_off = off; off += al((size_t)B * P->out_ch * S2 * sizeof(float));
   P->t_geps_off = off; off += al((size_t)B * S2 * out_pad(P) * sizeof(float));
@@ -252,7 +252,7 @@ int build_train(sr3_plan* P, int B, int cond_channels) {
   // embedding block at the arena head, which is written last)
   const size_t nrec = P->recs.size();
   P->t_unproc_max.assign(nrec + 1, 0);
-  size_t run = std::max(P->emb_b2 + (size_t)inner, P->film_b + (size_t)P->F);
+  size_t run = std::max(P->emb_b2 + (size_t)inner, P->film_b + (size_t)P->film_rows());
   for (size_t k = 0; k < nrec; ++k) {
     P->t_unproc_max[k] = run;
     run = std::max(run, P->recs[k].param_end);
@@ -365,9 +365,12 @@ int run_train(sr3_plan* P, const TrainStep& t) {
   }
   // ---- the backward walk: the records in reverse, each as build_train resolved it.  The activation-gradient mirror is not zeroed
   // (Rec::acc_*).  The FiLM gradient table is, as a precaution only: every row of it belongs to exactly one conv, whose colsums below
-  // stores it, so with today's walk no element of the table is read before it is written ----
+  // stores it -- or (scale_shift) to the one GroupNorm it modulates, whose act_bwd stores it -- so with today's walk no element of the
+  // table is read before it is written ----
+  const int FR = P->film_rows();
   float* dfilm = X.at<float>(P->t_dfilm_off);
-  SR3_HIP(hipMemsetAsync(dfilm, 0, (size_t)B * P->F * sizeof(float), st));
+  const float* film = X.at<float>(P->t_regions.film_off);      // the forward's FiLM table (the modulation rows of scale_shift)
+  SR3_HIP(hipMemsetAsync(dfilm, 0, (size_t)B * FR * sizeof(float), st));
 
   float* dA = X.at<float>(P->t_dA_off);
   double* part = X.at<double>(P->t_part_off);
@@ -432,7 +435,7 @@ int run_train(sr3_plan* P, const TrainStep& t) {
       // 1. bias and FiLM gradients: column sums of dOut
       if (bias_grad || s.film_row >= 0 || has_q) {
         rc = colsums(g, B, Ho * Wo, Cout, part, bias_grad ? grads + s.bias : nullptr,
-                     s.film_row >= 0 ? dfilm + s.film_row : nullptr, P->F, st);
+                     s.film_row >= 0 ? dfilm + s.film_row : nullptr, FR, st);
         if (rc) return rc;
         if (has_q)        // res_conv bias sees the same sums
           SR3_HIP(hipMemcpyAsync(grads + s.qb, grads + s.bias, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -459,9 +462,13 @@ int run_train(sr3_plan* P, const TrainStep& t) {
       if (s.act) {
         const bool dropped = s.drop_key >= 0 && dc.thresh != 0;
         const unsigned lseed = drop_layer_seed(dc.seed, (unsigned)(s.drop_key >= 0 ? s.drop_key : 0));
+        // scale_shift: this conv's GroupNorm was folded under the block's rows of the FiLM table; their gradients go to the same rows of dfilm
+        const int mrow = s.gn.mod_row;
+        const ModBwd md = {film + (mrow >= 0 ? mrow : 0), FR, params + r.beta, dfilm + (mrow >= 0 ? mrow : 0)};
         rc = act_bwd(dA, x0p, x1p, C0, C1, B, x0.H * x0.W, X.at<float>(P->t_regions.ss_off + r.ss_off),
                      X.at<float>(P->t_regions.mr_off + r.mr_off), G, s.act, params + r.gamma, part, gs, grads + r.gamma,
-                     grads + r.beta, X.grad(s.x0), X.grad(s.x1), st, lseed, dropped ? dc.thresh : 0u, dc.scale, abuf, r.acc_x0, r.acc_x1);
+                     grads + r.beta, X.grad(s.x0), X.grad(s.x1), st, lseed, dropped ? dc.thresh : 0u, dc.scale, abuf, r.acc_x0, r.acc_x1,
+                     mrow >= 0 ? &md : nullptr);
       } else {
         rc = grad_route(dA, C0, C1, B, x0.H, x0.W, s.ups, X.grad(s.x0), X.grad(s.x1), st, r.acc_x0, r.acc_x1);
       }
@@ -479,7 +486,7 @@ int run_train(sr3_plan* P, const TrainStep& t) {
   // ---- embedding MLP and FiLM projections ----
   EmbedBwdParams e;
   memset(&e, 0, sizeof(e));
-  e.variant = d.variant; e.B = B; e.inner = d.inner_channel; e.F = P->F; e.level = t.level; e.tstep = t.tstep; e.freq = t.freq;
+  e.variant = d.variant; e.B = B; e.inner = d.inner_channel; e.F = FR; e.level = t.level; e.tstep = t.tstep; e.freq = t.freq;
   e.w1 = params + P->emb_w1; e.b1 = params + P->emb_b1; e.w2 = params + P->emb_w2; e.b2 = params + P->emb_b2;
   e.wf = params + P->film_w; e.dfilm = dfilm;
   e.dw1 = grads + P->emb_w1; e.db1 = grads + P->emb_b1; e.dw2 = grads + P->emb_w2; e.db2 = grads + P->emb_b2;

@@ -44,6 +44,17 @@ def define_G(opt):
     heads = {k: int(u[k]) for k in ('n_head', 'head_dim') if u.get(k) is not None}
     if len(heads) == 2:
         raise ValueError('model.unet.n_head (%d) and model.unet.head_dim (%d) are mutually exclusive: set one' % (heads['n_head'], heads['head_dim']))
+    # engine key model.unet.scale_shift_norm: true -- the time / noise embedding enters a res block as (scale, shift) of its second GroupNorm,
+    # GN2(h) (1 + scale) + shift (ADM's use_scale_shift_norm), not as a row added to conv1's output.  Absent or false: the reference's
+    # blocks.  The projection's shapes double, so a checkpoint of the other form fails to load on the shape; the config carries the key
+    ssn = u.get('scale_shift_norm', False)
+    if not isinstance(ssn, bool):
+        raise ValueError('model.unet.scale_shift_norm must be true or false (got %r)' % (ssn,))
+    if u.get('use_affine_level'):
+        raise NotImplementedError('model.unet.use_affine_level is not built (the reference\'s constructors never forward it); '
+                                  'model.unet.scale_shift_norm: true modulates the second GroupNorm of every res block instead')
+    if ssn:
+        heads['scale_shift_norm'] = True
     denoiser = unet.UNet(
         **heads,
         in_channel=u['in_channel'], out_channel=u['out_channel'], norm_groups=u['norm_groups'],

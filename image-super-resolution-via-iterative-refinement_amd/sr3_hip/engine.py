@@ -38,7 +38,7 @@ class Plan(object):
     """Owns an sr3_plan*; exposes the parameter table."""
 
     def __init__(self, variant, in_channel, out_channel, inner_channel, norm_groups, channel_mults, attn_res,
-                 res_blocks, image_size):
+                 res_blocks, image_size, scale_shift_norm=False):
         self.lib = L.load()
         self.variant = variant
         self.inner = int(inner_channel)
@@ -48,8 +48,14 @@ class Plan(object):
         self.var_channels = 0      # plan option var_channels: the last rows of the output conv that are a learned-variance head
         self.desc = make_desc(variant, in_channel, out_channel, inner_channel, norm_groups, channel_mults,
                               attn_res, res_blocks, image_size)
+        # scale-shift time conditioning (SR3_UNET_SCALE_SHIFT_NORM): a res block's projection has 2 Cout rows, (scale, shift) of its second
+        # GroupNorm -- GN2(h) (1 + scale) + shift -- in place of a row added to conv1's output
+        self.scale_shift_norm = bool(scale_shift_norm)
         h = C.c_void_p()
-        L.check(self.lib.sr3_plan_create(C.byref(self.desc), C.byref(h)))
+        if self.scale_shift_norm:
+            L.check(self.lib.sr3_plan_create_ex(C.byref(self.desc), L.UNET_SCALE_SHIFT_NORM, C.byref(h)))
+        else:
+            L.check(self.lib.sr3_plan_create(C.byref(self.desc), C.byref(h)))
         self.handle = h
         self.options = {}          # plan options set through set_option (key -> value)
         self.generation = 0        # identifies the launch list: changes with every set_option and with the geometry -- part of the
@@ -137,6 +143,16 @@ class Plan(object):
             if side.value >= 0 or wait.value >= 0:      # plan option fork_side: ops on the side stream / the consumers that join them
                 o['side_id'], o['wait_id'] = side.value, wait.value
             out.append(o)
+        return out
+
+    def fold_list(self, batch):
+        """Per op of op_list(batch): (fold, mod_row) of sr3_plan_op_fold -- fold 0 none, 1 a fold launch, 2 the tail of this split-K conv's
+        reduce, 3 the tail of this statistics pass; mod_row >= 0: the FiLM-table rows that modulate the pairs (scale_shift_norm), else -1."""
+        fold, row = C.c_int(), C.c_int()
+        out = []
+        for i in range(self.num_ops(batch)):
+            L.check(self.lib.sr3_plan_op_fold(self.handle, int(batch), i, C.byref(fold), C.byref(row)))
+            out.append((fold.value, row.value))
         return out
 
     def taps(self):

@@ -33,6 +33,8 @@ class OpInfo(C.Structure):
                 ('fused_res_conv_cin', C.c_int), ('fused_output_stats', C.c_int), ('flops', C.c_double)]
 
 
+UNET_SCALE_SHIFT_NORM = 1      # sr3_plan_create_ex's flag SR3_UNET_SCALE_SHIFT_NORM
+
 _P = C.c_void_p
 _I = C.c_int
 _Z = C.c_size_t
@@ -68,12 +70,14 @@ SIGNATURES = {
     'sr3_selftest_split3': (_I, [_P, C.POINTER(C.c_int), _P]),
     'sr3_last_error': (C.c_char_p, []),
     'sr3_plan_create': (_I, [C.POINTER(UnetDesc), C.POINTER(_P)]),
+    'sr3_plan_create_ex': (_I, [C.POINTER(UnetDesc), C.c_uint, C.POINTER(_P)]),
     'sr3_plan_destroy': (None, [_P]),
     'sr3_plan_num_params': (_I, [_P]),
     'sr3_plan_param_info': (_I, [_P, _I, C.POINTER(ParamInfo)]),
     'sr3_plan_param_floats': (_Z, [_P]),
     'sr3_plan_op_info': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(OpInfo)]),
     'sr3_plan_op_side': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'sr3_plan_op_fold': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'sr3_plan_num_ops': (_I, [_P, _I]),
     'sr3_plan_forward_flops': (C.c_double, [_P, _I]),
     'sr3_plan_set_option': (_I, [_P, C.c_char_p, _I]),
@@ -152,9 +156,12 @@ SIGNATURES = {
     'sr3_conv_stats_slices': (_I, [_I, _I, _I, _I, _I, _I, _I, _I]),
     'sr3_groupnorm_fold_f32': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, C.c_float, _P, _P]),
     'sr3_groupnorm_fold_mr_f32': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, C.c_float, _P, _P, _P]),
+    'sr3_groupnorm_fold_mod_f32': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, C.c_float, _P, _P, _P, _I, _P]),
     'sr3_groupnorm_act_bwd_scratch_bytes': (_Z, [_I, _I, _I, _I]),
     'sr3_groupnorm_act_bwd_f32': (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _I, _I, _P, C.c_uint, C.c_float, _P, _P, _P, _I, _P, _I, _P,
                                        _P, _Z, _P]),
+    'sr3_groupnorm_act_bwd_mod_f32': (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _I, _I, _P, C.c_uint, C.c_float, _P, _P, _P, _I, _P, _I, _P,
+                                           _P, _Z, _P, _P, _I, _P, _P]),
     'sr3_conv_dgrad_scratch_bytes': (_Z, [_P, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),
     'sr3_conv_dgrad_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _Z, _P, _Z, _PI, _PI, _PI, _P]),
     'sr3_grad_route_f32': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P]),

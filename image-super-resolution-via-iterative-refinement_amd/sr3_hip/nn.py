@@ -25,13 +25,24 @@ class EngineUNet(nn.Module):
 
     def __init__(self, in_channel=6, out_channel=3, inner_channel=32, norm_groups=32,
                  channel_mults=(1, 2, 4, 8, 8), attn_res=(8), res_blocks=3, dropout=0,
-                 with_noise_level_emb=True, image_size=128, *, long_attention=False, learned_variance=False, n_head=1, head_dim=None):
+                 with_noise_level_emb=True, image_size=128, *, long_attention=False, learned_variance=False, n_head=1, head_dim=None,
+                 scale_shift_norm=False, use_affine_level=False):
         super().__init__()
+        if use_affine_level:
+            raise NotImplementedError('use_affine_level=True (an affine of conv1\'s output in front of the second GroupNorm) is not built; '
+                                      'scale_shift_norm=True (config key model.unet.scale_shift_norm) modulates the second GroupNorm instead')
+        if not isinstance(scale_shift_norm, bool):
+            raise ValueError('scale_shift_norm must be true or false (got %r)' % (scale_shift_norm,))
         if not with_noise_level_emb:
             raise NotImplementedError('the engine always conditions on the noise level / timestep '
                                       '(define_G never disables it: model/networks.py:91-101)')
+        # config key model.unet.scale_shift_norm (plan flag SR3_UNET_SCALE_SHIFT_NORM; ADM's use_scale_shift_norm): the time / noise embedding
+        # enters a res block as (scale, shift) of its second GroupNorm, GN2(h) (1 + scale) + shift, not as a row added to conv1's output.
+        # The projection's keys keep their names, their shapes become [2 Cout, inner] / [2 Cout]: a checkpoint of the other form fails
+        # to load on the shape, with the key named
+        self.scale_shift_norm = scale_shift_norm
         self.plan = E.Plan(self.variant, in_channel, out_channel, inner_channel, norm_groups, channel_mults,
-                           attn_res, res_blocks, image_size)
+                           attn_res, res_blocks, image_size, scale_shift_norm=scale_shift_norm)
         # config key model.unet.long_attention (plan option attn_long): attention levels with more tokens than the score-strip
         # kernels hold in LDS run on the key-blocked kernel instead of refusing the image size
         self.long_attention = bool(long_attention)
@@ -453,8 +464,8 @@ class EngineUNet(nn.Module):
     def extra_repr(self):
         d = self.plan.desc
         heads = 'head_dim=%d' % self.head_dim if self.head_dim is not None else 'n_head=%d' % self.n_head
-        return 'variant=%s, in=%d, out=%d, inner=%d, groups=%d, mults=%s, attn_res=%s, %s, res_blocks=%d, image=%d, ' \
+        return 'variant=%s, in=%d, out=%d, inner=%d, groups=%d, mults=%s, attn_res=%s, %s, scale_shift_norm=%s, res_blocks=%d, image=%d, ' \
                'params=%d (packed arena, libsr3_mi355x)' % (
                    self.variant, d.in_channel, d.out_channel, d.inner_channel, d.norm_groups,
-                   list(d.channel_mults[:d.n_mults]), list(d.attn_res[:d.n_attn_res]), heads, d.res_blocks, d.image_size,
+                   list(d.channel_mults[:d.n_mults]), list(d.attn_res[:d.n_attn_res]), heads, self.scale_shift_norm, d.res_blocks, d.image_size,
                    sum(e['numel'] for e in self.plan.table))

@@ -73,6 +73,15 @@ int sr3_selftest_split3(int* scratch_dev, int* mismatches, void* stream);
 /* UNet construction (model/sr3_modules/unet.py:162-233): builds the layer list, the parameter
  * table and the activation plan.  No device work. */
 int sr3_plan_create(const sr3_unet_desc* desc, sr3_plan** out);
+/* ... with architecture flags (sr3_plan_create is flags 0).  An unknown bit: SR3_E_BADARG, the bits named.
+ * SR3_UNET_SCALE_SHIFT_NORM (config key model.unet.scale_shift_norm; ADM's use_scale_shift_norm): a res block's projection of the
+ * time / noise embedding has 2 Cout rows -- its keys keep their names, their shapes become [2 Cout, inner] and [2 Cout] -- read as
+ * (scale, shift) = (rows [0, Cout), rows [Cout, 2 Cout)), and the block computes
+ *   h = conv1(silu(GN1(x)))  (no row is added);  out = conv2(dropout(silu(GN2(h) (1 + scale) + shift))) + res(x)
+ * in place of h = conv1(...) + row.  Every entry that takes the plan follows. */
+#define SR3_UNET_SCALE_SHIFT_NORM 1u
+#define SR3_UNET_FLAGS_ALL 1u
+int sr3_plan_create_ex(const sr3_unet_desc* desc, unsigned flags, sr3_plan** out);
 void sr3_plan_destroy(sr3_plan* plan);
 int sr3_plan_num_params(const sr3_plan* plan);
 int sr3_plan_param_info(const sr3_plan* plan, int index, sr3_param_info* out);
@@ -96,6 +105,10 @@ int sr3_plan_op_info(sr3_plan* plan, int batch, int index, sr3_op_info* out);
  * where the op sits in the list; *wait_id >= 0 -- the caller's stream waits for the side op of that id before this op (its consumer).
  * Both -1 for every op of a plan without the option.  Host-only. */
 int sr3_plan_op_side(sr3_plan* plan, int batch, int index, int* side_id, int* wait_id);
+/* The GroupNorm fold op `index` does: *fold 0 none, 1 the op is a fold launch (kind 40), 2 the split-K reduce of this conv folds the next
+ * op's GroupNorm too, 3 this statistics pass does (plan option fold_fuse); *mod_row >= 0: the first row of the FiLM table whose 2 C
+ * values per image -- scales, then shifts -- modulate the pairs that fold writes (SR3_UNET_SCALE_SHIFT_NORM), -1: none.  Host-only. */
+int sr3_plan_op_fold(sr3_plan* plan, int batch, int index, int* fold, int* mod_row);
 /* algorithmic FLOPs (contractions only) of one forward for `batch` images */
 double sr3_plan_forward_flops(sr3_plan* plan, int batch);
 /* host predicate of plan option store_wt: may a tensor (or a set of split-K slabs) of `bytes` bytes be written with write-through buffer
@@ -1046,6 +1059,14 @@ int sr3_conv_wgrad_f32(const float* src0, int C0, const float* src1, int C1, int
  * for the GroupNorm backward below. */
 int sr3_groupnorm_fold_mr_f32(const double* stat0, int C0, int T0, const double* stat1, int C1, int T1, int B, int HW,
                               int groups, const float* gamma, const float* beta, float eps, float* ss, float* mr, void* stream);
+/* ... under a scale-shift modulation (SR3_UNET_SCALE_SHIFT_NORM): mod + b * mod_stride points at image b's 2 C values, C = C0 + C1
+ * scales s then C shifts t (mod_stride >= 2 C), and the pairs written are those of GN(x) (1 + s) + t:
+ *   sc = rstd gamma_c ; sh = beta_c - mean sc ; m = 1 + s_bc ; ss = (sc m, fma(sh, m, t_bc)), each step rounded to fp32 in this order
+ * -- the same bits a plan's fused folds write.  mr may be NULL.  Host checks as the backward entries below (NULL mod, mod_stride
+ * < 2 C: SR3_E_BADARG; C0 / C1 % 4, C % groups: SR3_E_UNSUPPORTED); nothing is launched on a refusal. */
+int sr3_groupnorm_fold_mod_f32(const double* stat0, int C0, int T0, const double* stat1, int C1, int T1, int B, int HW,
+                               int groups, const float* gamma, const float* beta, float eps, float* ss, float* mr, const float* mod,
+                               int mod_stride, void* stream);
 
 /* ---- the training backward's own kernels, per op (autograd of `l_pix.backward()`, model/model.py:50-54): each entry runs the
  * functions sr3_train_step's backward walk runs, on caller-owned tensors.  Every entry checks its arguments on the host and launches
@@ -1068,6 +1089,17 @@ int sr3_groupnorm_act_bwd_f32(float* dA, const float* x0, int C0, const float* x
                               const float* mr, int groups, int act, const float* gamma, unsigned drop_seed, float drop_p,
                               float* dgamma, float* dbeta, float* dx0, int acc0, float* dx1, int acc1, float* aout,
                               void* scratch, size_t scratch_bytes, void* stream);
+/* ... of a GroupNorm folded under a scale-shift modulation (sr3_groupnorm_fold_mod_f32: ss holds the modulated pairs, mod / mod_stride
+ * are that call's).  gamma_c (1 + s_bc) stands where gamma_c does in dx; dgamma_c = sum_b (1 + s_bc) sum du xhat, dbeta_c = sum_b
+ * (1 + s_bc) sum du; and the rows' gradients go to dmod, in the layout and stride of mod (only the 2 C entries per image are written):
+ *   d shift_bc = sum du ;  d scale_bc = sum du GN(x) = gamma_c sum du xhat + beta_c sum du      (all in double, rounded once)
+ * which is why this entry takes beta too (GN(x) cannot be recovered from the pairs where 1 + s = 0).  Rows of zeros give the plain
+ * entry's dx, dgamma and dbeta bits.  The scratch is the plain entry's: sr3_groupnorm_act_bwd_scratch_bytes. */
+int sr3_groupnorm_act_bwd_mod_f32(float* dA, const float* x0, int C0, const float* x1, int C1, int B, int HW, const float* ss,
+                                  const float* mr, int groups, int act, const float* gamma, unsigned drop_seed, float drop_p,
+                                  float* dgamma, float* dbeta, float* dx0, int acc0, float* dx1, int acc1, float* aout,
+                                  void* scratch, size_t scratch_bytes, const float* beta, const float* mod, int mod_stride,
+                                  float* dmod, void* stream);
 
 /* Data gradient of one convolution, the "main segment" of the backward walk: dy [B, Ho, Wo, CoutP] (the forward conv's output
  * gradient; Ho x Wo from Hs, Ws, ups, stride, ksize as in sr3_conv_f32) -> dA [B, Hs << ups, Ws << ups, Cin], the gradient w.r.t.
