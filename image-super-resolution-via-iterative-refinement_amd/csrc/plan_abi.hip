@@ -67,6 +67,16 @@ int check_attn_heads(const sr3_plan* plan, const char* key, int value) {
     }
   return SR3_OK;
 }
+// feat_cache = d: the shallow forward is the first d entries of downs and the last d res blocks of ups, which must all sit on the top
+// resolution level -- the shallow part never crosses a Downsample or an Upsample
+static int check_feat_cache(const sr3_plan* plan, int value) {
+  if (value != 0 && (value < 1 || value > plan->d.res_blocks + 1)) {
+    set_error("feat_cache %d: the depth of the shallow forward is 1 .. %d (res_blocks + 1: it stays on the top resolution level), or 0 for off",
+              value, plan->d.res_blocks + 1);
+    return SR3_E_UNSUPPORTED;
+  }
+  return SR3_OK;
+}
 
 // ---- C ABI -------------------------------------------------------------------------------------
 extern "C" {
@@ -116,11 +126,33 @@ int sr3_plan_num_ops(sr3_plan* plan, int batch) {
   if (!plan) return 0;
   return build_inspected(plan, batch) ? -1 : (int)plan->ops.size();
 }
+// the shallow list of plan option feat_cache (the _cached inspection twins): refused on a plan without the option
+static int build_inspected_shallow(sr3_plan* plan, int batch) {
+  if (!plan->opt.feat_cache) { set_error("the plan has no shallow forward: plan option feat_cache is off"); return SR3_E_BADARG; }
+  return build_inspected(plan, batch);
+}
+static int op_info(const std::vector<Op>& ops, int batch, int index, sr3_op_info* out);
 int sr3_plan_op_info(sr3_plan* plan, int batch, int index, sr3_op_info* out) {
   if (!plan || !out) { set_error("null argument"); return SR3_E_BADARG; }
   if (const int rc = build_inspected(plan, batch)) return rc;
-  if (index < 0 || index >= (int)plan->ops.size()) { set_error("op index out of range"); return SR3_E_BADARG; }
-  const Op& o = plan->ops[index];
+  return op_info(plan->ops, batch, index, out);
+}
+int sr3_plan_num_ops_cached(sr3_plan* plan, int batch) {
+  if (!plan) return 0;
+  return build_inspected_shallow(plan, batch) ? -1 : (int)plan->sops.size();
+}
+int sr3_plan_op_info_cached(sr3_plan* plan, int batch, int index, sr3_op_info* out) {
+  if (!plan || !out) { set_error("null argument"); return SR3_E_BADARG; }
+  if (const int rc = build_inspected_shallow(plan, batch)) return rc;
+  return op_info(plan->sops, batch, index, out);
+}
+size_t sr3_feature_cache_bytes(sr3_plan* plan, int batch) {
+  if (!plan || !plan->opt.feat_cache) return 0;
+  return build_inspected(plan, batch) ? 0 : plan->cache_bytes;
+}
+static int op_info(const std::vector<Op>& ops, int batch, int index, sr3_op_info* out) {
+  if (index < 0 || index >= (int)ops.size()) { set_error("op index out of range"); return SR3_E_BADARG; }
+  const Op& o = ops[index];
   memset(out, 0, sizeof(*out));
   out->kind = (int)o.kind * 10;
   if (o.kind == OP_CONV) {
@@ -186,10 +218,20 @@ int sr3_plan_set_option(sr3_plan* plan, const char* key, int value) {
   const int prev = slot;
   slot = value;
   if (row->slot == &PlanOptions::gemm_epi) plan->opt.gemm_epi_named = true;
-  if (row->effects & OPT_FORWARD) plan->built_batch = -1;
+  if (row->effects & OPT_FORWARD) { plan->built_batch = -1; plan->cache_filled = nullptr; }      // (a feature cache is one launch list's)
   if (row->effects & OPT_TRAIN) plan->train_batch = -1;
   if (row->effects & OPT_STALE) plan->derived_from = nullptr;
   if ((row->effects & OPT_RELAY) && prev != value) layout_derived(plan);     // (the buffer has to be re-bound and re-prepared)
+  return prev;
+}
+// plan option feat_cache through its own entry: validate, store, drop the compiled forward (and with it what a cache was filled for)
+int sr3_plan_set_feature_cache(sr3_plan* plan, int depth) {
+  if (!plan) { set_error("null plan"); return SR3_E_BADARG; }
+  if (const int rc = check_feat_cache(plan, depth)) return rc;
+  const int prev = plan->opt.feat_cache;
+  plan->opt.feat_cache = depth;
+  plan->built_batch = -1;
+  plan->cache_filled = nullptr;
   return prev;
 }
 int sr3_plan_num_taps(sr3_plan* plan) { return plan ? (int)plan->taps.size() : 0; }
@@ -325,14 +367,66 @@ int sr3_unet_forward_full(sr3_plan* plan, const float* x_nchw, const float* cond
   return run_forward(plan, f);
 }
 
+// What the _cached entries check behind check_forward_call, in this order, before anything is launched: the cache pointer, its size and
+// alignment; refresh = 0: the option, then that the last refresh filled THIS cache at this batch and geometry.  What a refresh filled
+// is recorded behind its forward (run_cached)
+static int check_feature_cache(sr3_plan* plan, ForwardCall& f, void* cache, size_t cache_bytes, int refresh) {
+  if (!refresh && !plan->opt.feat_cache) {
+    set_error("a cached forward (refresh = 0) needs a plan built with option feat_cache");
+    return SR3_E_BADARG;
+  }
+  if (!plan->opt.feat_cache) return SR3_OK;      // (refresh = 1 on a plan without the option: the plain forward, the cache is not looked at)
+  if (!cache) { set_error("null feature cache"); return SR3_E_BADARG; }
+  if (cache_bytes < plan->cache_bytes) { set_error("feature cache too small: %zu < %zu", cache_bytes, plan->cache_bytes); return SR3_E_NOMEM; }
+  if ((uintptr_t)cache & 255) { set_error("misaligned feature cache (256 B)"); return SR3_E_ALIGN; }
+  const int h = plan_height(plan), w = plan_width(plan);
+  if (!refresh && (plan->cache_filled != cache || plan->cache_batch != f.batch || plan->cache_h != h || plan->cache_w != w)) {
+    if (!plan->cache_filled) set_error("the feature cache was never filled: run a refresh (refresh = 1) first");
+    else set_error("the feature cache was filled at batch %d, geometry %d x %d%s: a cached forward at batch %d, geometry %d x %d needs a refresh first",
+                   plan->cache_batch, plan->cache_h, plan->cache_w, plan->cache_filled != cache ? " in another buffer" : "", f.batch, h, w);
+    return SR3_E_BADARG;
+  }
+  f.cache = cache; f.shallow = !refresh;
+  return SR3_OK;
+}
+// the forward of a _cached entry.  A refresh that went through records what it filled; one that was refused behind the checks above (a
+// missing or stale derived buffer) or whose launch failed leaves no fill on record: nothing trustworthy is in the cache then
+static int run_cached(sr3_plan* plan, const ForwardCall& f) {
+  const int rc = run_forward(plan, f);
+  if (f.cache && !f.shallow) {
+    plan->cache_filled = rc == SR3_OK ? f.cache : nullptr;
+    plan->cache_batch = f.batch; plan->cache_h = plan_height(plan); plan->cache_w = plan_width(plan);
+  }
+  return rc;
+}
+
+// sr3_unet_forward_full on a plan under option feat_cache: refresh = 1 the full list, which leaves the branch tensor in feat_cache;
+// refresh = 0 the shallow list, which reads it
+int sr3_unet_forward_cached(sr3_plan* plan, const float* x_nchw, const float* cond_nchw, int cond_channels,
+                            const float* noise_level, const int64_t* timestep, const float* freq, const float* level_table,
+                            const int* step_dev, const float* params, void* workspace, size_t workspace_bytes,
+                            float* eps_out_nchw, int batch, void* stream, const int* t_map, void* feat_cache, size_t feat_cache_bytes,
+                            int refresh) {
+  if (t_map && !step_dev) { set_error("sr3_unet_forward_cached: t_map goes with step_dev"); return SR3_E_BADARG; }
+  ForwardCall f = {.x = x_nchw, .cond = cond_nchw, .cond_channels = cond_channels, .level = noise_level, .tstep = timestep, .freq = freq,
+                   .level_table = level_table, .step_dev = step_dev, .t_map = t_map, .params = params, .workspace = workspace,
+                   .workspace_bytes = workspace_bytes, .eps_out = eps_out_nchw, .batch = batch, .stream = static_cast<hipStream_t>(stream),
+                   .full_out = true};
+  if (const int rc = check_forward_call(plan, f, 0)) return rc;
+  if (const int rc = check_feature_cache(plan, f, feat_cache, feat_cache_bytes, refresh)) return rc;
+  return run_cached(plan, f);
+}
+
 // One whole reverse step (include/sr3_mi355x.h): the forward above with the p_sample update and the counter decrement inside the
 // output conv's kernel -- two graph nodes fewer per step than sr3_unet_forward + sr3_p_sample_step + sr3_step_decrement.
 // _hist: the multistep tail (tab_c3 and the history buffer, both or neither); _ex forwards here with neither.
-int sr3_reverse_step_hist(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,
-                          const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
-                          const float* z_nchw, const float* ta, const float* tb, const float* tc1, const float* tc2, const float* tsig,
-                          int clip_denoised, float* eps_out_nchw, int batch, void* stream, const int* t_map, const float* tc3,
-                          float* hist_nchw) {
+// _cached: the same step on a plan under option feat_cache -- refresh = 1 the full forward (writes the cache), 0 the shallow one (reads
+// it); have_cache = false: the plain entries, which a plan under the option refuses (run_forward)
+static int reverse_step(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,
+                        const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
+                        const float* z_nchw, const float* ta, const float* tb, const float* tc1, const float* tc2, const float* tsig,
+                        int clip_denoised, float* eps_out_nchw, int batch, void* stream, const int* t_map, const float* tc3,
+                        float* hist_nchw, bool have_cache, void* feat_cache, size_t feat_cache_bytes, int refresh) {
   // the embedding kernel reads t from slot 1 and copies it to slot 0; the tail reads slot 0 and writes t - 1 to slot 1: no kernel
   // both reads and writes a slot, so no launch of the step races with another block of itself
   ForwardCall f = {.x = x_nchw, .cond = cond_nchw, .cond_channels = cond_channels, .freq = freq, .level_table = level_table,
@@ -341,11 +435,30 @@ int sr3_reverse_step_hist(sr3_plan* plan, float* x_nchw, const float* cond_nchw,
   if (const int rc = check_forward_call(plan, f, FC_STEP, step2_dev && ta && tb && tc1 && tc2 && tsig, z_nchw)) return rc;
   const size_t image_bytes = (size_t)batch * (plan->d.out_channel - plan->opt.var_channels) * plan_height(plan) * plan_width(plan) * sizeof(float);
   if (const int rc = check_step_history("reverse_step", tc3, hist_nchw, x_nchw, eps_out_nchw, image_bytes, true)) return rc;
+  if (have_cache)
+    if (const int rc = check_feature_cache(plan, f, feat_cache, feat_cache_bytes, refresh)) return rc;
   StepFuse tail;
   tail.x = x_nchw; tail.z = z_nchw; tail.tb = StepTables{ta, tb, tc1, tc2, tsig};
   tail.step_cur = step2_dev; tail.step_next = step2_dev + 1; tail.clip = clip_denoised; tail.c3 = tc3; tail.hist = hist_nchw;
   f.fuse = &tail;
-  return run_forward(plan, f);
+  return run_cached(plan, f);
+}
+int sr3_reverse_step_hist(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,
+                          const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
+                          const float* z_nchw, const float* ta, const float* tb, const float* tc1, const float* tc2, const float* tsig,
+                          int clip_denoised, float* eps_out_nchw, int batch, void* stream, const int* t_map, const float* tc3,
+                          float* hist_nchw) {
+  return reverse_step(plan, x_nchw, cond_nchw, cond_channels, freq, level_table, step2_dev, params, workspace, workspace_bytes, z_nchw, ta, tb,
+                      tc1, tc2, tsig, clip_denoised, eps_out_nchw, batch, stream, t_map, tc3, hist_nchw, false, nullptr, 0, 1);
+}
+int sr3_reverse_step_cached(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,
+                            const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
+                            const float* z_nchw, const float* ta, const float* tb, const float* tc1, const float* tc2, const float* tsig,
+                            int clip_denoised, float* eps_out_nchw, int batch, void* stream, const int* t_map, const float* tc3,
+                            float* hist_nchw, void* feat_cache, size_t feat_cache_bytes, int refresh) {
+  return reverse_step(plan, x_nchw, cond_nchw, cond_channels, freq, level_table, step2_dev, params, workspace, workspace_bytes, z_nchw, ta, tb,
+                      tc1, tc2, tsig, clip_denoised, eps_out_nchw, batch, stream, t_map, tc3, hist_nchw, true, feat_cache, feat_cache_bytes,
+                      refresh);
 }
 
 int sr3_reverse_step_ex(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,

@@ -352,27 +352,42 @@ struct Builder {
   bool train = false;
   size_t gn_cursor = 0, mr_cursor = 0;     // train: persistent per-GroupNorm tables
   Builder(sr3_plan* p, int b, bool tr = false) : P(p), B(b), ops(tr ? p->tops : p->ops), train(tr) {}
+  Builder(sr3_plan* p, int b, std::vector<Op>& list) : P(p), B(b), ops(list) {}      // (the shallow list of plan option feat_cache)
+  size_t cache_cursor = 0;        // plan option feat_cache: bytes of the feature cache laid out so far (the branch tensor, its partials)
 
-  int make(int C, int H, int W) {
+  // cached: the tensor lives in the caller's feature cache (CACHE_TAG offsets), outside the arena -- the one branch tensor of a list
+  int make(int C, int H, int W, bool cached = false) {
     Tensor t;
     t.C = C; t.H = H; t.W = W;
     t.bytes = (size_t)B * H * W * C * sizeof(float);
-    t.off = act.alloc(t.bytes);
+    if (cached) {
+      t.off = CACHE_TAG | cache_cursor;
+      cache_cursor += (t.bytes + 255) & ~(size_t)255;
+      t.cached = true;
+    } else {
+      t.off = act.alloc(t.bytes);
+    }
     t.valid = true;
+    T.push_back(t);
+    return (int)T.size() - 1;
+  }
+  // the shallow list's branch source: the tensor the full list left in the cache, statistics partials included
+  int adopt(const Tensor& t) {
     T.push_back(t);
     return (int)T.size() - 1;
   }
   void drop(int h) {
     if (h < 0 || !T[h].valid) return;
     if (train) return;                     // the backward needs every activation
-    if (!P->opt.keep_all) act.release(T[h].off, T[h].bytes);
+    if (!P->opt.keep_all && !T[h].cached) act.release(T[h].off, T[h].bytes);
     T[h].valid = false;
   }
   void stat_slot(int h, int parts) {
     Tensor& t = T[h];
     t.stat_T = parts;
-    t.stat_off = stats_cursor;
-    stats_cursor += (size_t)B * parts * t.C * 2 * sizeof(double);
+    const size_t bytes = (size_t)B * parts * t.C * 2 * sizeof(double);
+    if (t.cached) { t.stat_off = CACHE_TAG | cache_cursor; cache_cursor += (bytes + 255) & ~(size_t)255; }      // kept with the tensor
+    else { t.stat_off = stats_cursor; stats_cursor += bytes; }
     t.stats_done = true;
   }
   void ensure_stats(int h) {
@@ -443,7 +458,7 @@ struct Builder {
     ConvParams& c = v.cp;
     c = conv_shape(B, T[x0].H, T[x0].W, s.ups, s.stride, s.ksize, T[x0].C, x1 >= 0 ? T[x1].C : 0, Cout);
     const int Ho = c.Ho, Wo = c.Wo;
-    const int out = make(Cout, Ho, Wo);
+    const int out = make(Cout, Ho, Wo, s.to_cache);
     c.act = s.act; c.film_stride = P->film_rows();
     c.RC0 = s.r0 >= 0 ? T[s.r0].C : 0; c.RC1 = s.r1 >= 0 ? T[s.r1].C : 0;
     v.src0 = T[x0].off; v.src1 = off(x1);
@@ -499,7 +514,8 @@ struct Builder {
   }
   std::string refused;     // inference: the first layer no kernel can run at this geometry (build_forward refuses the plan with it)
   int n_side = 0;          // plan option fork_side: ops handed to the side stream so far (Op::side_id)
-  int res_block(int x0, int x1, const ResLayer& R) {
+  // to_cache (plan option feat_cache): the block's output -- block2's conv, or the attention's out projection -- is the branch tensor
+  int res_block(int x0, int x1, const ResLayer& R, bool to_cache = false) {
     const FoldOut gn1 = fold(x0, x1, R.gn1_w, R.gn1_b);
     // plan option fork_side (inference): res_conv reads only the block input, so it is emitted HERE -- behind the fold, in front of block1's
     // conv -- and launched on the side stream; block2's conv, which adds it as its residual, waits for it.  Only unsplit: a split-K res_conv
@@ -515,7 +531,8 @@ struct Builder {
     const int h1 = conv({.x0 = x0, .x1 = x1, .Cout = R.cout, .act = 2, .gn = gn1, .w = R.c1_w, .bias = R.c1_b, .film_row = ssn ? -1 : R.film_off, .want_stats = true});
     const FoldOut gn2 = fold(h1, -1, R.gn2_w, R.gn2_b, ssn ? 2 * R.film_off : -1);
     // block2's conv; what it adds: res_conv's output (its own launch), res_conv as a fused K-segment over the block input, or the input itself
-    ConvSpec block2 = {.x0 = h1, .Cout = R.cout, .act = 2, .gn = gn2, .w = R.c2_w, .bias = R.c2_b, .want_stats = true, .drop_key = R.film_off};
+    ConvSpec block2 = {.x0 = h1, .Cout = R.cout, .act = 2, .gn = gn2, .w = R.c2_w, .bias = R.c2_b, .want_stats = true, .to_cache = to_cache && !R.attn,
+                        .drop_key = R.film_off};
     int out;
     if (r_side >= 0) {
       block2.r0 = r_side;
@@ -553,7 +570,8 @@ struct Builder {
       if (train) { Rec r; r.kind = R_ATTN; r.qkv = qkv; r.o = o; r.heads = a.attn.heads; P->recs.push_back(r); }
       flops += attn_flops(B, tokens, R.cout);
       drop(qkv);
-      const int out2 = conv({.x0 = o, .Cout = R.cout, .ksize = 1, .w = R.ao_w, .bias = R.ao_b, .r0 = out, .want_stats = true});
+      const int out2 = conv({.x0 = o, .Cout = R.cout, .ksize = 1, .w = R.ao_w, .bias = R.ao_b, .r0 = out, .want_stats = true,
+                             .to_cache = to_cache});
       drop(o);
       drop(out);
       out = out2;
@@ -562,8 +580,10 @@ struct Builder {
   }
 };
 
-// the UNet.forward walk (downs -> mid -> ups -> final), emitting ops through the builder
-static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
+// the UNet.forward walk (downs -> mid -> ups -> final), emitting ops through the builder.  Plan option feat_cache = d (inference): the full
+// walk binds the tensor that enters the d-th last up block -- the branch tensor -- and its statistics partials to the feature cache;
+// shallow = d walks the shallow forward instead: the first d entries of downs, then the last d up blocks from the cached branch tensor
+static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels, int shallow = 0) {
   const sr3_unet_desc& d = P->d;
   std::vector<Op>& ops = bld.ops;
   const int B = bld.B;
@@ -574,12 +594,17 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
   { Op o; o.kind = OP_EMBED; ops.push_back(o); }
   bld.flops += 2.0 * B * (2.0 * 4 * inner * inner + (double)P->film_rows() * inner);
 
+  // (taps are the full list's workspace offsets: the branch tensor, which lives in the cache, has none)
   auto tap = [&](const std::string& name, int h) {
-    if (!bld.train) P->taps.push_back({name, bld.T[h].off, bld.T[h].C, bld.T[h].H, bld.T[h].W});
+    if (!bld.train && !shallow && !bld.T[h].cached) P->taps.push_back({name, bld.T[h].off, bld.T[h].C, bld.T[h].H, bld.T[h].W});
   };
+  const int cache_d = bld.train ? 0 : (shallow ? shallow : P->opt.feat_cache);
+  const int first_up = (int)P->ups.size() - cache_d;      // the first up block of the shallow forward (check_feat_cache: never negative)
+  int n_down = 0, branch = -1;
   std::vector<int> feats;
   int cur = -1;
   for (auto& L : P->downs) {
+    if (shallow && n_down++ == shallow) break;
     if (L.kind == L_CONV_IN) {
       cur = bld.make(L.cout, IH, IW);
       Op o; o.kind = OP_CONV_IN;
@@ -604,27 +629,37 @@ static void walk_forward(sr3_plan* P, Builder& bld, int cond_channels) {
   // `cur` is feats.back() here: skip features are released by the up block that consumes them
   bool cur_is_skip = true;
   for (auto& L : P->mid) {
-    const int nxt = bld.res_block(cur, -1, L.res);
+    if (shallow) break;
+    const int nxt = bld.res_block(cur, -1, L.res, cache_d && first_up == 0 && &L == &P->mid.back());
     if (!cur_is_skip) bld.drop(cur);
     cur = nxt;
     cur_is_skip = false;
     tap(L.name, cur);
   }
+  int n_up = 0;
   for (auto& L : P->ups) {
+    const int i = n_up++;
+    if (shallow && i < first_up) continue;
+    if (cache_d && i == first_up) {
+      if (shallow) cur = bld.adopt(P->branch);
+      branch = cur;
+    }
+    const bool to_cache = cache_d && !shallow && i + 1 == first_up;      // this entry's output enters the first shallow up block
     int nxt;
     if (L.kind == L_RES) {
       const int skip = feats.back();
       feats.pop_back();
-      nxt = bld.res_block(cur, skip, L.res);
+      nxt = bld.res_block(cur, skip, L.res, to_cache);
       bld.drop(cur);
       bld.drop(skip);
     } else {
-      nxt = bld.conv({.x0 = cur, .Cout = L.cout, .ups = 1, .w = L.w, .bias = L.b, .want_stats = true});
+      nxt = bld.conv({.x0 = cur, .Cout = L.cout, .ups = 1, .w = L.w, .bias = L.b, .want_stats = true, .to_cache = to_cache});
       bld.drop(cur);
     }
     cur = nxt;
     tap(L.name, cur);
   }
+  if (cache_d && !shallow) P->branch = bld.T[branch];      // (its partials are laid out by now: the first shallow up block's fold read them)
   const FoldOut gnf = bld.fold(cur, -1, P->fin_gn_w, P->fin_gn_b);
   {
     Op o; o.kind = OP_CONV_OUT;
@@ -692,36 +727,52 @@ int build_forward(sr3_plan* P, int B, int cond_channels) {
   if (B <= 0) { set_error("batch must be > 0"); return SR3_E_BADARG; }
   if (cond_channels < 0 || cond_channels >= d.in_channel) { set_error("cond_channels %d out of range (in_channel %d)", cond_channels, d.in_channel); return SR3_E_BADARG; }
   P->ops.clear();
+  P->sops.clear();
   P->taps.clear();
+  P->cache_bytes = 0;
   P->built_batch = -1;
-  Builder bld(P, B);
   const int inner = d.inner_channel;
-  walk_forward(P, bld, cond_channels);
-  if (!bld.refused.empty()) {
-    // a geometry no kernel can run is refused HERE, when the launch list is built: never after a launch has been enqueued
-    set_error("geometry %d x %d unsupported: %s", plan_height(P), plan_width(P), bld.refused.c_str());
-    P->ops.clear();
-    P->taps.clear();
-    return SR3_E_UNSUPPORTED;
+  // one launch list -- the full forward, or (plan option feat_cache) the shallow one -- and its regions; returns the workspace it needs
+  auto compile = [&](Builder& bld, std::vector<Op>& ops, Regions& R, int shallow, size_t* ws_bytes) {
+    walk_forward(P, bld, cond_channels, shallow);
+    if (!bld.refused.empty()) {
+      // a geometry no kernel can run is refused HERE, when the launch list is built: never after a launch has been enqueued
+      set_error("geometry %d x %d unsupported: %s", plan_height(P), plan_width(P), bld.refused.c_str());
+      P->ops.clear();
+      P->sops.clear();
+      P->taps.clear();
+      return SR3_E_UNSUPPORTED;
+    }
+    if (P->opt.fork_side && !ops.empty() && ops[0].kind == OP_EMBED) {
+      // ... and the embedding MLP + FiLM projections (first op, reads only the noise level): beside the input conv, joined by the first op that
+      // reads the FiLM table (op_reads_film: a conv that adds a row, or a fold -- fused or its own launch -- that a row modulates)
+      for (Op& o : ops)
+        if (op_reads_film(o)) {
+          if (o.wait_id < 0) { o.wait_id = bld.n_side; ops[0].side_id = bld.n_side++; }
+          break;
+        }
+    }
+    // ---- fixed regions after the activation arena (high-water mark) ----
+    size_t off = (bld.act.high + 255) & ~(size_t)255;
+    // (no mean / rstd tables in inference: mr_off stays 0, no op has_mr)
+    R.stats_off = off; off += (bld.stats_cursor + 255) & ~(size_t)255;
+    R.ss_off = off; off += ((size_t)B * std::max(bld.max_cin, 4) * 2 * sizeof(float) + 255) & ~(size_t)255;
+    R.temb_off = off; off += ((size_t)B * inner * sizeof(float) + 255) & ~(size_t)255;
+    R.film_off = off; off += ((size_t)B * P->film_rows() * sizeof(float) + 255) & ~(size_t)255;
+    R.scratch_off = off; R.scratch_bytes = bld.max_scratch; off += (bld.max_scratch + 255) & ~(size_t)255;
+    *ws_bytes = off;
+    return (int)SR3_OK;
+  };
+  Builder bld(P, B);
+  if (const int rc = compile(bld, P->ops, P->regions, 0, &P->ws_bytes)) return rc;
+  if (P->opt.feat_cache) {
+    // the shallow list: its own arena and regions inside the same workspace (sized for the larger list); nothing of the cache lives there
+    P->cache_bytes = bld.cache_cursor;
+    Builder sb(P, B, P->sops);
+    size_t shallow_bytes = 0;
+    if (const int rc = compile(sb, P->sops, P->sregions, P->opt.feat_cache, &shallow_bytes)) return rc;
+    P->ws_bytes = std::max(P->ws_bytes, shallow_bytes);
   }
-  if (P->opt.fork_side && !P->ops.empty() && P->ops[0].kind == OP_EMBED) {
-    // ... and the embedding MLP + FiLM projections (first op, reads only the noise level): beside the input conv, joined by the first op that
-    // reads the FiLM table (op_reads_film: a conv that adds a row, or a fold -- fused or its own launch -- that a row modulates)
-    for (Op& o : P->ops)
-      if (op_reads_film(o)) {
-        if (o.wait_id < 0) { o.wait_id = bld.n_side; P->ops[0].side_id = bld.n_side++; }
-        break;
-      }
-  }
-  // ---- fixed regions after the activation arena (high-water mark) ----
-  size_t off = (bld.act.high + 255) & ~(size_t)255;
-  Regions& R = P->regions;           // (no mean / rstd tables in inference: mr_off stays 0, no op has_mr)
-  R.stats_off = off; off += (bld.stats_cursor + 255) & ~(size_t)255;
-  R.ss_off = off; off += ((size_t)B * std::max(bld.max_cin, 4) * 2 * sizeof(float) + 255) & ~(size_t)255;
-  R.temb_off = off; off += ((size_t)B * inner * sizeof(float) + 255) & ~(size_t)255;
-  R.film_off = off; off += ((size_t)B * P->film_rows() * sizeof(float) + 255) & ~(size_t)255;
-  R.scratch_off = off; R.scratch_bytes = bld.max_scratch; off += (bld.max_scratch + 255) & ~(size_t)255;
-  P->ws_bytes = off;
   P->flops = bld.flops;
   P->built_batch = B;
   P->built_cond = cond_channels;

@@ -21,6 +21,7 @@ struct Tensor {
   int stat_T = 0;       // partials per image
   bool stats_done = false;
   bool valid = false;
+  bool cached = false;  // plan option feat_cache: the branch tensor -- off and stat_off are CACHE_TAG offsets into the caller's feature cache
 };
 
 struct ResLayer {
@@ -45,6 +46,9 @@ struct Layer {
 
 // an optional workspace / arena offset that is absent (plan_run.hip binds a null pointer for it)
 static constexpr size_t NO_OFF = ~(size_t)0;
+// plan option feat_cache: an activation / statistics offset with this bit set counts from the start of the caller-owned feature cache,
+// not from the workspace (plan_run.hip resolves it; NO_OFF is tested first).  Without the option no offset of a launch list carries it
+static constexpr size_t CACHE_TAG = (size_t)1 << 62;
 
 // The kernel one conv of a plan runs on, as choose_conv (plan_build.hip) decided it
 struct ConvChoice {
@@ -146,6 +150,7 @@ struct ConvSpec {
   int film_row = -1;               // first row of the FiLM table added to the output
   int r0 = -1, r1 = -1;            // residual: the concat view (r0|r1)
   bool want_stats = false;         // a GroupNorm reads the output: fuse its statistics where the kernel can
+  bool to_cache = false;           // plan option feat_cache: the output is the branch tensor, bound to the feature cache
   int q0 = -1, q1 = -1; size_t qw = 0, qb = 0;       // fused 1x1 segment (res_conv) over (q0|q1); caller checked fuses_res_conv()
   int drop_key = -1;               // train-mode dropout on the activated input: the layer's key (drop_layer_seed)
 };
@@ -243,6 +248,11 @@ struct PlanOptions {
                              // Off by default ONLY because tests pin that refusal text; at the native geometry both values build the same plan
   int fork_side = 0;         // res_conv (and the embedding MLP) on a side stream beside block1's conv: see Op::side_id; A/B knob
   int loss_l2 = 0;           // training loss: 0 = L1 (sum), 1 = L2 (sum)  (set_loss, diffusion.py:84-90)
+  int feat_cache = 0;        // inference plans: d in 1 .. res_blocks + 1 compiles a second, shallow launch list -- the embedding, the first d entries
+                             // of downs, the last d res blocks of ups, the output conv -- whose first up block reads the tensor entering it
+                             // (the branch tensor) and its GroupNorm partials from a caller-owned feature cache, which the full list writes
+                             // (sr3_unet_forward_cached / sr3_reverse_step_cached).  0: off, one list, no cache.  Set by
+                             // sr3_plan_set_feature_cache, an entry of its own: no row of PLAN_OPTIONS
 };
 
 // What setting an option does, beyond storing the value (sr3_plan_set_option, plan_abi.hip, applies exactly these)
@@ -340,6 +350,14 @@ struct sr3_plan {
   size_t ws_bytes = 0;
   Regions regions;
   double flops = 0;
+  // ---- plan option feat_cache: the shallow forward and the feature cache (built by build_forward behind the full list) ----
+  std::vector<Op> sops;              // the shallow launch list
+  Regions sregions;                  // ... and its regions inside the same workspace (ws_bytes covers both lists)
+  sr3::Tensor branch;                // the branch tensor as the full list leaves it: CACHE_TAG offsets, partials per image
+  size_t cache_bytes = 0;            // the feature cache: the branch tensor, then its statistics partials
+  // what the last refresh filled (host bookkeeping; a cached forward is refused on anything else)
+  const void* cache_filled = nullptr;
+  int cache_batch = -1, cache_h = 0, cache_w = 0;
   // ---- training step (train_plan.hip) ----
   int train_batch = -1, train_cond = -1;
   int train_h = 0, train_w = 0;      // geometry the training plan was built for (with batch and cond_channels: its key; options reset train_batch)
@@ -385,6 +403,8 @@ struct ForwardCall {
   // the output conv, all out_ch rows of the output conv in eps_out (the variance head too), the training plan's forward (P->tops)
   hipEvent_t* ev = nullptr; hipEvent_t* mid = nullptr; const DropCfg* drop = nullptr; const StepFuse* fuse = nullptr;
   bool full_out = false, train = false;
+  // plan option feat_cache: the caller's feature cache; shallow: replay P->sops over P->sregions, reading it (else the full list writes it)
+  void* cache = nullptr; bool shallow = false;
 };
 // replays P->ops over P->regions, or (f.train) P->tops over P->t_regions.  A plan whose derived buffer is missing or stale is refused
 // before the first launch

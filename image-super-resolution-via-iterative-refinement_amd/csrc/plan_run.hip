@@ -9,8 +9,7 @@
 namespace sr3 {
 
 // ---- binding -----------------------------------------------------------------------------------
-// pointer into the workspace / the arena for an optional offset (NO_OFF: null)
-template <typename T> static T* bind(char* base, size_t off) { return off == NO_OFF ? nullptr : reinterpret_cast<T*>(base + off); }
+// pointer into the arena for an optional offset (NO_OFF: null)
 static const float* bind(const float* params, size_t off) { return off == NO_OFF ? nullptr : params + off; }
 
 // What one call binds every op of its list to: the per-call pointers, and the stream / split-K mid event of the op being launched
@@ -22,13 +21,21 @@ struct Bound {
   const float* params;
   hipStream_t st = nullptr;                // the caller's stream, or the plan's side stream (fork_side)
   hipEvent_t mid = nullptr;                // per-op timing: recorded between a split-K conv's GEMM kernel and its reduce
+  char* cache = nullptr;                   // plan option feat_cache: the caller's feature cache
 };
+
+// pointer for an optional activation / statistics offset (NO_OFF: null): into `base` -- the workspace, or its statistics region -- or,
+// a CACHE_TAG offset, into the feature cache (the branch tensor and its partials: run_forward refused a list that has one without a cache)
+template <typename T> static T* bind(const Bound& b, char* base, size_t off) {
+  if (off == NO_OFF) return nullptr;
+  return reinterpret_cast<T*>((off & CACHE_TAG) ? b.cache + (off & ~CACHE_TAG) : base + off);
+}
 
 static FoldTail make_fold_tail(const FoldSpec& s, const Bound& b) {
   FoldTail f;
   memset(&f, 0, sizeof(f));
   f.groups = b.P->d.norm_groups; f.Ctot = s.Ctot; f.c_off = s.c_off;
-  f.ostat = bind<const double>(b.stats, s.ostat); f.oC = s.oC; f.oT = s.oT; f.o_off = s.o_off;
+  f.ostat = bind<const double>(b, b.stats, s.ostat); f.oC = s.oC; f.oT = s.oT; f.o_off = s.o_off;
   f.gamma = b.params + s.gamma; f.beta = b.params + s.beta; f.eps = 1e-5f;
   f.ss = reinterpret_cast<float*>(b.ws + b.R.ss_off + s.ss_rel);
   f.mr = s.has_mr ? reinterpret_cast<float*>(b.ws + b.R.mr_off + s.mr_rel) : nullptr;
@@ -88,24 +95,24 @@ static int launch_conv_in(const Op& o, const Bound& b) {
   const int Ca = f.cond_channels > 0 ? f.cond_channels : v.x_channels;
   const float* a1 = f.cond_channels > 0 ? f.x : nullptr;
   const int Cb = f.cond_channels > 0 ? v.x_channels : 0;
-  return conv_in_nchw(a0, Ca, a1, Cb, f.batch, v.H, v.W, b.params + v.w, b.params + v.bias, v.Cout, bind<float>(b.ws, v.out),
-                      bind<double>(b.stats, v.ostat), b.st);
+  return conv_in_nchw(a0, Ca, a1, Cb, f.batch, v.H, v.W, b.params + v.w, b.params + v.bias, v.Cout, bind<float>(b, b.ws, v.out),
+                      bind<double>(b, b.stats, v.ostat), b.st);
 }
 
 static int launch_stats(const Op& o, const Bound& b) {
   const Op::Stats& v = o.stats;
   if (o.fold_fused) {
     FoldTail ft = make_fold_tail(o.tail, b);
-    return chan_stats_fold(bind<const float>(b.ws, v.src), b.f.batch, v.pixels, v.channels, bind<double>(b.stats, v.stat), ft, b.st);
+    return chan_stats_fold(bind<const float>(b, b.ws, v.src), b.f.batch, v.pixels, v.channels, bind<double>(b, b.stats, v.stat), ft, b.st);
   }
-  return chan_stats(bind<const float>(b.ws, v.src), b.f.batch, v.pixels, v.channels, bind<double>(b.stats, v.stat), b.st);
+  return chan_stats(bind<const float>(b, b.ws, v.src), b.f.batch, v.pixels, v.channels, bind<double>(b, b.stats, v.stat), b.st);
 }
 
 static int launch_fold(const Op& o, const Bound& b) {
   const Op::Fold& v = o.fold;
-  return gn_finalize(bind<const double>(b.stats, v.stat0), v.C0, v.T0, bind<const double>(b.stats, v.stat1), v.C1, v.T1, b.f.batch, v.pixels,
-                     b.P->d.norm_groups, b.params + v.gamma, b.params + v.beta, 1e-5f, bind<float>(b.ws, b.R.ss_off + o.ss_rel), b.st,
-                     v.has_mr ? bind<float>(b.ws, b.R.mr_off + o.mr_rel) : nullptr, v.mod_row >= 0 ? b.film + v.mod_row : nullptr, b.P->film_rows());
+  return gn_finalize(bind<const double>(b, b.stats, v.stat0), v.C0, v.T0, bind<const double>(b, b.stats, v.stat1), v.C1, v.T1, b.f.batch, v.pixels,
+                     b.P->d.norm_groups, b.params + v.gamma, b.params + v.beta, 1e-5f, bind<float>(b, b.ws, b.R.ss_off + o.ss_rel), b.st,
+                     v.has_mr ? bind<float>(b, b.ws, b.R.mr_off + o.mr_rel) : nullptr, v.mod_row >= 0 ? b.film + v.mod_row : nullptr, b.P->film_rows());
 }
 
 static int launch_conv(const Op& o, const Bound& b) {
@@ -113,24 +120,24 @@ static int launch_conv(const Op& o, const Bound& b) {
   const ConvChoice& ch = v.ch;
   const DropCfg* drop = b.f.drop;
   ConvParams c = v.cp;
-  c.src0 = bind<const float>(b.ws, v.src0);
-  c.src1 = bind<const float>(b.ws, v.src1);
+  c.src0 = bind<const float>(b, b.ws, v.src0);
+  c.src1 = bind<const float>(b, b.ws, v.src1);
   c.w = b.params + v.w;
   c.bias = bind(b.params, v.bias);
-  c.ss = c.act ? bind<const float>(b.ws, b.R.ss_off + o.ss_rel) : nullptr;
+  c.ss = c.act ? bind<const float>(b, b.ws, b.R.ss_off + o.ss_rel) : nullptr;
   c.film = v.film_row >= 0 ? b.film + v.film_row : nullptr;
-  c.res0 = bind<const float>(b.ws, v.res0);
-  c.res1 = bind<const float>(b.ws, v.res1);
-  c.out = bind<float>(b.ws, v.out);
-  c.ostat = bind<double>(b.stats, v.ostat);
+  c.res0 = bind<const float>(b, b.ws, v.res0);
+  c.res1 = bind<const float>(b, b.ws, v.res1);
+  c.out = bind<float>(b, b.ws, v.out);
+  c.ostat = bind<double>(b, b.stats, v.ostat);
   c.store_wt = b.P->opt.store_wt;
   c.gemm_epi = 1 + b.P->opt.launch_gemm_epi();
   if (drop && v.has_drop && drop->thresh != 0) {
     c.drop_seed = drop_layer_seed(drop->seed, v.drop_key); c.drop_thresh = drop->thresh; c.drop_scale = drop->scale;
   }
   if (v.x2_src0 != NO_OFF) {
-    c.x2_src0 = bind<const float>(b.ws, v.x2_src0);
-    c.x2_src1 = bind<const float>(b.ws, v.x2_src1);
+    c.x2_src0 = bind<const float>(b, b.ws, v.x2_src0);
+    c.x2_src1 = bind<const float>(b, b.ws, v.x2_src1);
     c.x2_w = b.params + v.x2_w;
     c.x2_bias = b.params + v.x2_bias;
   }
@@ -138,13 +145,13 @@ static int launch_conv(const Op& o, const Bound& b) {
   if (reads_wsplit(v)) c.w_split = b.P->derived_ptr + ch.wsplit_off;
   FoldTail ft;
   if (o.fold_fused) { ft = make_fold_tail(o.tail, b); c.fold = &ft; }
-  return conv_forward(c, ch.tile_cfg, ch.ksplit, bind<float>(b.ws, b.R.scratch_off), b.R.scratch_bytes, b.st, b.mid);
+  return conv_forward(c, ch.tile_cfg, ch.ksplit, bind<float>(b, b.ws, b.R.scratch_off), b.R.scratch_bytes, b.st, b.mid);
 }
 
 static int launch_attn(const Op& o, const Bound& b) {
   const Op::Attn& v = o.attn;
   // (one head: attention_forward's launches; more: attention_heads.hip)
-  return attention_forward_heads(bind<const float>(b.ws, v.qkv), b.f.batch, v.tokens, v.channels, v.heads, bind<float>(b.ws, v.out), b.st,
+  return attention_forward_heads(bind<const float>(b, b.ws, v.qkv), b.f.batch, v.tokens, v.channels, v.heads, bind<float>(b, b.ws, v.out), b.st,
                                  (b.P->opt.attn_split ? 1 : 0) | (v.tile_cfg == 24 ? 2 : 0));
 }
 
@@ -152,7 +159,7 @@ static int launch_conv_out(const Op& o, const Bound& b) {
   const Op::ConvOut& v = o.conv_out;
   // the prediction rows alone -- the first rows of the same filters and bias -- unless all rows are asked for
   const int rows = (b.f.train || b.f.full_out) ? v.out_ch : v.out_ch - b.P->opt.var_channels;
-  return conv_out_nchw(bind<const float>(b.ws, v.src), bind<const float>(b.ws, b.R.ss_off + o.ss_rel), b.f.batch, v.H, v.W, v.channels,
+  return conv_out_nchw(bind<const float>(b, b.ws, v.src), bind<const float>(b, b.ws, b.R.ss_off + o.ss_rel), b.f.batch, v.H, v.W, v.channels,
                        b.params + v.w, b.params + v.bias, rows, b.f.eps_out, b.st, b.f.fuse);
 }
 
@@ -183,11 +190,17 @@ static int join_op(sr3_plan* P, const Op& o, hipStream_t st) {
 
 // ---- the launch loop ---------------------------------------------------------------------------
 int run_forward(sr3_plan* P, const ForwardCall& f) {
-  const std::vector<Op>& ops = f.train ? P->tops : P->ops;
-  const Regions& R = f.train ? P->t_regions : P->regions;
+  const std::vector<Op>& ops = f.train ? P->tops : f.shallow ? P->sops : P->ops;
+  const Regions& R = f.train ? P->t_regions : f.shallow ? P->sregions : P->regions;
   if (const int rc = check_derived(P, ops, f.params)) return rc;
+  if (!f.train && P->opt.feat_cache && !f.cache) {
+    // the full list of such a plan writes the branch tensor into the cache: without one there is nowhere to put it
+    set_error("plan option feat_cache is on: the forward needs a feature cache (sr3_unet_forward_cached / sr3_reverse_step_cached)");
+    return SR3_E_BADARG;
+  }
   char* const ws = static_cast<char*>(f.workspace);
   Bound b = {P, f, R, ws, ws + R.stats_off, reinterpret_cast<float*>(ws + R.film_off), f.params};
+  b.cache = static_cast<char*>(f.cache);
   const bool forking = !f.ev && !f.train;      // under per-op timing everything stays on one stream
   size_t i = 0;
   for (const Op& o : ops) {

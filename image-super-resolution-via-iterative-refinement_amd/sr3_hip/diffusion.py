@@ -60,7 +60,7 @@ from .x0_rules import (BACKPROJECTION_KEYS, CONSISTENCY_BLOCKS, RESAMPLES, THRES
 from .x0_rules import gray_f32, gray_weights, restore_error, travel_tables, travel_walk                                      # noqa: F401
 from .schedules import (COND_AUGMENT_KEYS, LEARNED_VARIANCE_LAMBDA, LOSS_TYPES, LOSS_WEIGHTS, PREDICTIONS, SAMPLER_KINDS,     # noqa: F401
                         SELF_CONDITION_PROB, WALKS, _BUFFERS, _SAMPLER_TABLES, _check_prediction, _check_sampler_kind, _positive,
-                        ancestral_tables, cond_level_coefs, hybrid_step_scalars, loss_weights, make_beta_schedule, parse_cond_augment,
+                        ancestral_tables, cond_level_coefs, feature_cache_refresh, hybrid_step_scalars, loss_weights, make_beta_schedule, parse_cond_augment, parse_feature_cache,
                         parse_learned_variance, parse_self_condition, prediction_coefs, sampler_tables, sampler_walk,
                         widen_for_learned_variance)                                                                           # (theirs too)
 
@@ -99,6 +99,7 @@ class EngineDiffusion(nn.Module):
         self._cond_aug_buf = None      # training: the [B, Cl (+ 1), H, W] augmented conditioning tensor
         self.learned_variance = None   # None: off; else {'lambda': l}: the network's last `channels` output rows are the variance head (set_learned_variance)
         self._hyb_table = None         # training: per-timestep rows of sr3_train_step_ex2's step_scalars on the device, built on first use
+        self.feature_cache = None      # None: every step runs the whole UNet; else {'interval': N, 'depth': d, 'full_last': k} (set_feature_cache)
         self.last_vlb = None           # the last p_losses' L_vlb in bits per dimension (0-dim device tensor) under the key
         self.t_sampler = None          # None: t is drawn uniformly; else a t_sampler.LossSecondMomentResampler (set_t_sampler)
         self._t_pending = None         # under t_sampler: (the drawn steps, the step's per-image terms on the device) not yet in the history
@@ -177,6 +178,36 @@ class EngineDiffusion(nn.Module):
         for r in X.RULES:
             spec = schedule_opt.get(r.name) if hasattr(schedule_opt, 'get') else None
             getattr(self, r.setter)(*(() if spec is None else r.parse(spec)))
+        # and "feature_cache": {"interval": 3, "depth": 1, "full_last": 0} next to "sampler"; absent / null: every step runs the whole UNet
+        self.set_feature_cache(**parse_feature_cache(schedule_opt.get('feature_cache') if hasattr(schedule_opt, 'get') else None))
+
+    def set_feature_cache(self, interval=None, depth=1, full_last=0):
+        """Feature-cached sampling (DeepCache, Ma et al. 2023): the chain's first step and every `interval`-th behind it run the whole
+        UNet and keep the tensor that enters the `depth`-th last up block; every other step runs only the shallow forward of that depth
+        -- the input conv, the first depth - 1 down blocks, the last depth up blocks, the output conv, all on the top resolution level
+        (depth in 1 .. res_blocks + 1) -- on the kept tensor (plan option feat_cache; `schedules.feature_cache_refresh` is the
+        schedule).  The last `full_last` steps run whole as well.  An approximation: the result is not the uncached chain's, and
+        interval 1 is that chain bit for bit.  interval None: off.  Runs on the fused step under the ancestral loop, DDIM and
+        DPM-Solver++(2M), both variants, with cond_augment.  Not built (NotImplementedError, here or where the other is set): tiling, a
+        rule on x0 (consistency, guidance, backprojection, restore), self-conditioning, the learned-variance ancestral sampler,
+        calc_bpd_loop, train.distill."""
+        plan = self.denoise_fn.plan
+        if interval is None:
+            cfg = None
+        else:
+            for name, v, lo in (('interval', interval, 1), ('depth', depth, 1), ('full_last', full_last, 0)):
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+                    raise ValueError('feature_cache %s must be an integer >= %d (got %r)' % (name, lo, v))
+            cfg = dict(interval=int(interval), depth=int(depth), full_last=int(full_last))
+            if cfg['depth'] > plan.desc.res_blocks + 1:
+                raise ValueError('feature_cache depth must lie in 1 .. %d (res_blocks + 1: the shallow forward stays on the top resolution '
+                                 'level; got %r)' % (plan.desc.res_blocks + 1, depth))
+            self._check_settings(feature_cache=cfg)
+        want = 0 if cfg is None else cfg['depth']
+        if plan.options.get('feat_cache', 0) != want:      # (a plan that never had the option is not touched: its launch list stays what it is)
+            plan.set_option('feat_cache', want)
+            self._loop_cache = {}                          # (another interval or full_last keeps the states: their graphs do not depend on either)
+        self.feature_cache = cfg
 
     def set_sampler(self, steps=None, eta=0.0, *, kind='ddim', walk=None):
         """Sample in `steps` reverse steps over a strided walk through the current schedule (DDIM; eta = 0: deterministic, eta = 1 and
@@ -454,7 +485,8 @@ class EngineDiffusion(nn.Module):
         the DDPM variant.  before = (clause, call): the caller's own validation, made in front of that clause ('self_condition' |
         'tiled_sampler') where its place among the refusals is a promise (tests/settings_matrix.json)."""
         s = dict({r.name: getattr(self, r.name) for r in X.RULES}, sampler=None if self.sampler is None else self.sampler['type'],
-                 tiling=self.tiling, self_condition=self.self_condition is not None, cond_augment=self.cond_augment)
+                 tiling=self.tiling, self_condition=self.self_condition is not None, cond_augment=self.cond_augment,
+                 feature_cache=self.feature_cache)
         assert set(override) <= set(s), override
         s.update(override)
         tiling, selfc, aug = s['tiling'], s['self_condition'], s['cond_augment']
@@ -515,6 +547,26 @@ class EngineDiffusion(nn.Module):
             raise NotImplementedError('tiled sampling of the DDPM variant under a sampler (DDIM, DPM-Solver++): the tiles run through sr3_unet_forward, '
                                       'which has no step-index -> timestep map (t_map); use the ancestral sampler (set_sampler(None)) '
                                       'or whole-image steps (set_tiling(None))')
+        if s['feature_cache'] is not None:     # (the last clause: every older refusal stands in front of it)
+            off = 'switch feature_cache off (set_feature_cache(None))'
+            if tiling is not None:
+                raise NotImplementedError('feature_cache with tiling: every chunk of tiles would need a cache of its own, refreshed in step '
+                                          'with the others; use whole-image steps (set_tiling(None)) or %s' % off)
+            for r in X.RULES:
+                if s[r.name] is not None:
+                    raise NotImplementedError('feature_cache with %s: the rule\'s step runs its forward through sr3_unet_forward, not the cached '
+                                              'entries%s; switch it off (%s(None)) or %s'
+                                              % (r.name, ', and guidance runs two forwards, which need two caches' if r.name == 'guidance' else
+                                                 ', and a travelled walk jumps away from the step the cache was filled at'
+                                                 if r.name == 'restore' and s[r.name].get('travel') is not None else '', r.setter, off))
+            if selfc:
+                raise NotImplementedError('feature_cache with self-conditioning: the self-conditioned step runs its forward through '
+                                          'sr3_unet_forward, and the x0 it feeds back enters at the input conv, above the cut; switch '
+                                          'self-conditioning off (set_self_condition(None)) or %s' % off)
+            if s['sampler'] == 'ancestral':
+                raise NotImplementedError('feature_cache with the learned-variance ancestral sampler: its step stores the variance rows and '
+                                          'draws in sr3_learned_var_step, outside the fused step; sample with {"type": "ddim", "steps": S, '
+                                          '"eta": e} (set_sampler) or %s' % off)
 
     # ---- small reference helpers (API completeness; not on the hot path) -------------------------
     def predict_start_from_noise(self, x_t, t, noise):
@@ -636,6 +688,9 @@ class EngineDiffusion(nn.Module):
         if cond_augment:                       # (appended too: the state's cond is the augmented tensor, made once per chain)
             key += ('cond_augment',)
         key += tuple(r.key(cfgs[r.name]) for r in X.RULES if r.key_appended and cfgs[r.name] is not None)      # (and a later rule's)
+        fc = self.feature_cache
+        if fc is not None:                     # (appended too.  The depth alone: neither graph depends on the schedule, which `_run_steps` reads)
+            key += (('feature_cache', fc['depth']),)
         st = self._cached(key)
         if st is not None:
             return st
@@ -652,6 +707,11 @@ class EngineDiffusion(nn.Module):
             self._tile_buffers(st, tiles, shape, cond_shape, dev)
         st['self_condition'] = bool(self_condition)      # cond is [B, Cl + C, H, W]: the LR channels, then the last step's x0
         st['cond_augment'] = bool(cond_augment)          # cond holds the augmented LR channels (and the level plane behind them)
+        if fc is not None:
+            # the cache the full step writes and the cached step reads (never part of the workspace), the second captured graph (made
+            # when the schedule first names it), which of the two forms `_step_fused` runs next, and how often each graph was replayed
+            st['feat_cache'] = self.denoise_fn.plan.new_feature_cache(shape[0], dev)
+            st['graph_cached'], st['refresh'], st['fc_replays'] = None, True, [0, 0]
         for r in X.RULES:                  # the setting the state (and its captured graph) was built for, and the rule's buffers
             if cfgs[r.name] is not None:
                 st[r.name] = dict(cfgs[r.name])
@@ -776,10 +836,12 @@ class EngineDiffusion(nn.Module):
 
     def _step_fused(self, st, rule, z, hist, x0_rule):
         """The plain step, one engine call (sr3_reverse_step): UNet forward with the p_sample update and the counter decrement inside
-        the output conv's kernel."""
+        the output conv's kernel.  A feature-cached state (set_feature_cache): the full step, which refills the state's cache, or -- st['refresh']
+        False -- the cached one (sr3_reverse_step_cached)."""
         tables, level, t_map, c3, _ = rule
         self.denoise_fn.reverse_step(st['img'], z, tables, st['step'], cond=st['cond'], level_table=level, clip_denoised=True,
-                                     eps_out=st['eps'], ws=st['ws'], t_map=t_map, c3=c3, hist=hist)
+                                     eps_out=st['eps'], ws=st['ws'], t_map=t_map, c3=c3, hist=hist, feat_cache=st.get('feat_cache'),
+                                     refresh=st.get('refresh', True))
 
     def _step_tiled(self, st, rule, z, hist, x0_rule):
         """A state with a grid (the tiled loop): per chunk of tiles a gather out of the running image (sr3_tile_gather) and one UNet
@@ -799,8 +861,8 @@ class EngineDiffusion(nn.Module):
                                              *[L.ptr(t) for t in tables], L.ptr(st['step']), 1, L.ptr(st['eps']),
                                              self._stream(img.device), L.ptr(c3), L.ptr(hist)))
 
-    def _capture(self, st, step=None):
-        """st['graph'] <- one `step(st)` (None: `_one_step`) captured as a hipGraph.  One eager step first (lazy kernel attributes,
+    def _capture(self, st, step=None, slot='graph'):
+        """st[slot] <- one `step(st)` (None: `_one_step`) captured as a hipGraph.  One eager step first (lazy kernel attributes,
         allocator warm-up) on a side stream -- or, where a rule asks for it, on the stream the capture runs on (torch's shared capture
         stream): see x0_rules.Backprojection -- behind which the tensors the state declares dirty, the default RNG state and the
         per-item generators are put back, so a seed reproduces the reference's draw sequence."""
@@ -832,15 +894,37 @@ class EngineDiffusion(nn.Module):
         with (cap if cap is not None else torch.cuda.graph(g)):
             step(st)
         # capture does not execute; state is untouched
-        st['graph'] = g
+        st[slot] = g
 
     def _run_steps(self, st, n, step, z_of=None, after=None, progress=False):
         """The n iterations i = n - 1 .. 0 of a chain on a state whose counter stands at n - 1: replays of the state's graph (captured
         here on first use) under use_graph, else eager calls of `step`; z_of (the injected noise of the parity tests: i -> step i's z,
-        or None for zeros) makes the loop eager and the step draw nothing.  after(i): what the caller does behind each step."""
+        or None for zeros) makes the loop eager and the step draw nothing.  after(i): what the caller does behind each step.  A
+        feature-cached state holds two graphs, the full step and the cached one, and `feature_cache_refresh` names each iteration's."""
         use_graph = self.use_graph and z_of is None
+        fc = self.feature_cache if st.get('feat_cache') is not None else None
+        if fc is not None:
+            # what a warm-up step leaves in the cache is never read: a chain's first step refills it
+            assert feature_cache_refresh(0, n, fc['interval'], fc['full_last'])
         if use_graph and st['graph'] is None:
+            if fc is not None:
+                st['refresh'] = True
             self._capture(st, step)
+        if use_graph and fc is not None and st['graph_cached'] is None and \
+                not all(feature_cache_refresh(k, n, fc['interval'], fc['full_last']) for k in range(n)):
+            # the cached step, captured when a schedule first names it.  Its warm-up reads the cache: refilled here by an eager full step
+            # on the state as it stands (a chain may have run since the full graph's warm-up), which `_capture` then puts back
+            st['refresh'] = True
+            keep = [(st[k], st[k].clone()) for k in st['dirty']]
+            rng, gstate = torch.cuda.get_rng_state(st['step'].device), [g.get_state() for g in st['gens'] or []]
+            step(st)
+            for t, saved in keep:
+                t.copy_(saved)
+            torch.cuda.set_rng_state(rng, st['step'].device)
+            for gen, gs in zip(st['gens'] or [], gstate):
+                gen.set_state(gs)
+            st['refresh'] = False
+            self._capture(st, step, 'graph_cached')
         it = reversed(range(n))
         if progress:
             try:
@@ -849,8 +933,15 @@ class EngineDiffusion(nn.Module):
             except ImportError:
                 pass
         for i in it:
+            if fc is not None:
+                st['refresh'] = feature_cache_refresh(n - 1 - i, n, fc['interval'], fc['full_last'])
             if use_graph:
-                st['graph'].replay()
+                if fc is None or st['refresh']:
+                    st['graph'].replay()
+                else:
+                    st['graph_cached'].replay()
+                if fc is not None:
+                    st['fc_replays'][0 if st['refresh'] else 1] += 1
                 if 'replays' in st:
                     st['replays'] += 1
             elif z_of is not None:
@@ -1154,6 +1245,10 @@ class EngineDiffusion(nn.Module):
                                       'by this loop')
         if self.tiling is not None:
             raise NotImplementedError('calc_bpd_loop with tiling: the bound is the whole-image model\'s; evaluate with set_tiling(None)')
+        if self.feature_cache is not None:
+            raise NotImplementedError('calc_bpd_loop with feature_cache: every step of this walk starts from a fresh x_t ~ q(x_t | x0), so no '
+                                      'step is the neighbour a cache could come from, and the bound is the whole network\'s; evaluate with '
+                                      'set_feature_cache(None)')
         aug = self.cond_augment
         dev = self.betas.device
         if dev.type != 'cuda':

@@ -112,6 +112,15 @@ def _refuse_cond_augment(student, teacher):
                                       'same one); switch noise conditioning augmentation off (set_cond_augment(None)) on the %s' % what)
 
 
+def _refuse_feature_cache(student, teacher):
+    """feature-cached sampling is a setting of the sampling loop (refused like cond_augment: when a Distiller is made, and at every step)"""
+    for what, m in (('student', student), ('teacher', teacher)):
+        if getattr(m, 'feature_cache', None) is not None:
+            raise NotImplementedError('feature_cache with train.distill: the teacher\'s two steps are the whole network\'s at two nodes of '
+                                      'its walk, with no step between them to take a cache from, and the student trains through the training '
+                                      'plan, which has no shallow form; switch it off (set_feature_cache(None)) on the %s' % what)
+
+
 class Distiller(object):
     """One round of progressive distillation: `step` trains `student` (an EngineDiffusion on a GPU) to do in one DDIM step what the
     frozen `teacher` -- a second network of the same variant, geometry and conditioning, with its own plan, arena and derived weights --
@@ -127,6 +136,7 @@ class Distiller(object):
                                           'first pass and write no x0 back (sr3_teacher_step_f32, sr3_distill_target_f32); switch '
                                           'self-conditioning off (set_self_condition(None)) on the %s' % what)
         _refuse_cond_augment(student, teacher)
+        _refuse_feature_cache(student, teacher)
         for what, m in (('student', student), ('teacher', teacher)):
             if not isinstance(m, EngineDiffusion) or getattr(m, '_alphas_cumprod64', None) is None:
                 raise ValueError('Distiller: the %s must be an EngineDiffusion with a noise schedule' % what)
@@ -197,6 +207,7 @@ class Distiller(object):
         student's grad_arena, exactly as p_losses does."""
         st, te = self.student, self.teacher
         _refuse_cond_augment(st, te)
+        _refuse_feature_cache(st, te)
         dev = self.device
         x_start = data['HR']
         if not torch.is_tensor(x_start) or x_start.device != dev or x_start.dim() != 4 or x_start.dtype != torch.float32:

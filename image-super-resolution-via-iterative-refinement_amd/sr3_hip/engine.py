@@ -58,6 +58,7 @@ class Plan(object):
             L.check(self.lib.sr3_plan_create(C.byref(self.desc), C.byref(h)))
         self.handle = h
         self.options = {}          # plan options set through set_option (key -> value)
+        self._own_cache = None     # plan option feat_cache: the feature cache of the forwards that are handed none (own_feature_cache)
         self.generation = 0        # identifies the launch list: changes with every set_option and with the geometry -- part of the
                                    # reverse-loop graph cache key.  A geometry seen before (under the same options) gets its old value back
         self.options_epoch = 0     # bumped by set_option only: what the derived filters depend on (the geometry does not touch them)
@@ -82,7 +83,10 @@ class Plan(object):
             pass
 
     def set_option(self, key, value):
-        rc = self.lib.sr3_plan_set_option(self.handle, key.encode(), int(value))
+        if key == 'feat_cache':        # (a plan option with an entry of its own: the depth of the shallow forward, 0 = off)
+            rc = self.lib.sr3_plan_set_feature_cache(self.handle, int(value))
+        else:
+            rc = self.lib.sr3_plan_set_option(self.handle, key.encode(), int(value))
         if rc < 0:
             L.check(rc)
         self.options[key] = int(value)
@@ -124,6 +128,40 @@ class Plan(object):
         if n == 0:
             raise L.Sr3Error('sr3_workspace_bytes failed: %s' % L.hint((self.lib.sr3_last_error() or b'').decode()))
         return n
+
+    def feature_cache_bytes(self, batch):
+        """Bytes of the feature cache for `batch` images at the plan's geometry (sr3_feature_cache_bytes); 0 without plan option feat_cache."""
+        return int(self.lib.sr3_feature_cache_bytes(self.handle, int(batch)))
+
+    def new_feature_cache(self, batch, device):
+        """A 256-byte aligned uint8 tensor of feature_cache_bytes(batch) on `device`, or None without plan option feat_cache."""
+        need = self.feature_cache_bytes(batch)
+        if need == 0:
+            return None
+        buf = torch.empty(need + 256, dtype=torch.uint8, device=device)
+        off = (-buf.data_ptr()) % 256
+        return buf[off:off + need]
+
+    def own_feature_cache(self, batch, device):
+        """Under plan option feat_cache every forward writes the branch tensor somewhere: the cache of the calls that bring none of their
+        own (a plain forward, p_sample) -- never one a sampling loop's cached steps read."""
+        need = self.feature_cache_bytes(batch)
+        c = self._own_cache
+        if c is None or c.numel() < need or c.device != device:
+            c = self._own_cache = self.new_feature_cache(batch, device)
+        return c
+
+    def shallow_op_list(self, batch):
+        """The launch list of a cached forward (plan option feat_cache; sr3_plan_op_info_cached), as op_list's entries.  Host only."""
+        n = int(self.lib.sr3_plan_num_ops_cached(self.handle, int(batch)))
+        if n < 0:
+            raise L.Sr3Error('sr3_plan_num_ops_cached failed: %s' % (self.lib.sr3_last_error() or b'').decode())
+        info = L.OpInfo()
+        out = []
+        for i in range(n):
+            L.check(self.lib.sr3_plan_op_info_cached(self.handle, int(batch), i, C.byref(info)))
+            out.append({k: getattr(info, k) for k, _ in L.OpInfo._fields_})
+        return out
 
     def forward_flops(self, batch):
         return float(self.lib.sr3_plan_forward_flops(self.handle, int(batch)))
@@ -207,14 +245,32 @@ def _check_same_size(x, cond):
         raise L.Sr3Error('conditioning image %s and input %s differ in batch or size' % (tuple(cond.shape), tuple(x.shape)))
 
 
+def _feature_cache(plan, feat_cache, refresh, batch, device):
+    """The cache a forward runs with: none on a plan without option feat_cache (a cached step is refused there); else the caller's, or --
+    a refresh only -- the plan's own."""
+    if not plan.options.get('feat_cache'):
+        if not refresh:
+            raise L.Sr3Error('a cached step (refresh=False) needs plan option feat_cache')
+        return None
+    if feat_cache is None:
+        if not refresh:
+            raise L.Sr3Error('a cached step (refresh=False) needs the feature cache the refresh filled')
+        return plan.own_feature_cache(batch, device)
+    if feat_cache.dtype != torch.uint8 or not feat_cache.is_contiguous() or feat_cache.device != device:
+        raise L.Sr3Error('feat_cache must be a contiguous uint8 tensor on the device of x (Plan.new_feature_cache)')
+    return feat_cache
+
+
 def reverse_step(plan, arena, freq, ws, x, z, tables, step2, cond=None, level_table=None, clip_denoised=True, eps_out=None,
-                 t_map=None, c3=None, hist=None):
+                 t_map=None, c3=None, hist=None, feat_cache=None, refresh=True):
     """One whole reverse step in place on `x` (sr3_reverse_step_hist): eps = UNet(cat([cond, x], 1), level(t)); x <- p_sample update;
     t <- t - 1, with t = step2[1] (int32 tensor of two).  `tables` = (a, b, c1, c2, sigma) schedule tables on the device, indexed
     by t like `level_table`.  `z` None: no noise is read (= 0).  `t_map` (int32 device tensor, one entry per value t takes): the
     timestep the DDPM UNet is conditioned on at counter value t -- a sampler's walk through a subset of the timesteps; None: t.
     `c3`, `hist` (both or neither): a multistep sampler's table of the previous x0's coefficient and the buffer, shaped like `x`, that
-    carries that x0 from step to step (x <- ... + c3[t] hist; hist <- this step's x0)."""
+    carries that x0 from step to step (x <- ... + c3[t] hist; hist <- this step's x0).  Plan option feat_cache
+    (sr3_reverse_step_cached): `feat_cache` (Plan.new_feature_cache) is written by a step with refresh=True, the full forward, and read
+    by one with refresh=False, the shallow forward; None: the plan's own cache, full steps only."""
     if not x.is_cuda or not x.is_contiguous() or x.dtype != torch.float32:
         raise L.Sr3Error('reverse_step needs a contiguous fp32 GPU tensor (got %s, %s); there is no CPU fallback' % (x.device, x.dtype))
     B = x.shape[0]
@@ -236,18 +292,23 @@ def reverse_step(plan, arena, freq, ws, x, z, tables, step2, cond=None, level_ta
         raise L.Sr3Error('t_map must be a contiguous int32 tensor on the device of x')
     if hist is not None and (hist.dtype != torch.float32 or not hist.is_contiguous() or hist.device != x.device or hist.shape != x.shape):
         raise L.Sr3Error('hist must be a contiguous fp32 tensor of the shape and on the device of x')
-    L.check(plan.lib.sr3_reverse_step_hist(plan.handle, L.ptr(x), L.ptr(cond), cc, L.ptr(freq), L.ptr(level_table), L.ptr(step2),
-                                           L.ptr(arena), L.ptr(wsbuf), need, L.ptr(z), L.ptr(a), L.ptr(b), L.ptr(c1), L.ptr(c2), L.ptr(sg),
-                                           1 if clip_denoised else 0, L.ptr(eps_out), B, C.c_void_p(stream), L.ptr(t_map), L.ptr(c3),
-                                           L.ptr(hist)))
+    args = (plan.handle, L.ptr(x), L.ptr(cond), cc, L.ptr(freq), L.ptr(level_table), L.ptr(step2), L.ptr(arena), L.ptr(wsbuf), need,
+            L.ptr(z), L.ptr(a), L.ptr(b), L.ptr(c1), L.ptr(c2), L.ptr(sg), 1 if clip_denoised else 0, L.ptr(eps_out), B, C.c_void_p(stream),
+            L.ptr(t_map), L.ptr(c3), L.ptr(hist))
+    cache = _feature_cache(plan, feat_cache, refresh, B, x.device)
+    if cache is None:
+        L.check(plan.lib.sr3_reverse_step_hist(*args))
+    else:
+        L.check(plan.lib.sr3_reverse_step_cached(*args, L.ptr(cache), cache.numel(), 1 if refresh else 0))
     return x
 
 
 def unet_forward(plan, arena, freq, ws, x, cond=None, noise_level=None, timestep=None, level_table=None,
-                 step_dev=None, out=None, full=False, t_map=None):
+                 step_dev=None, out=None, full=False, t_map=None, feat_cache=None, refresh=True):
     """eps = UNet(cat([cond, x], 1), level)   (all tensors on the GPU, fp32, NCHW contiguous).  `full` (a plan with a variance head,
     option var_channels): all out_channel rows -- the prediction, then the variance head (sr3_unet_forward_full); otherwise the
-    prediction rows alone.  `t_map` (with `full` and step_dev, DDPM variant): the timestep is t_map[*step_dev]."""
+    prediction rows alone.  `t_map` (with `full` and step_dev, DDPM variant): the timestep is t_map[*step_dev].  `feat_cache`,
+    `refresh`: as reverse_step's (sr3_unet_forward_cached; on a plan without a variance head its rows are sr3_unet_forward's)."""
     if not x.is_cuda:
         raise L.Sr3Error('the MI355X engine only runs on a GPU tensor (got %s); there is no CPU fallback' % x.device)
     B = x.shape[0]
@@ -280,6 +341,15 @@ def unet_forward(plan, arena, freq, ws, x, cond=None, noise_level=None, timestep
     stream = torch.cuda.current_stream(x.device).cuda_stream
     if t_map is not None and (not full or t_map.dtype != torch.int32 or not t_map.is_contiguous() or t_map.device != x.device):
         raise L.Sr3Error('t_map goes with full=True and must be a contiguous int32 tensor on the device of x')
+    cache = _feature_cache(plan, feat_cache, refresh, B, x.device)
+    if cache is not None:
+        if not full and plan.var_channels:
+            raise L.Sr3Error('plan option feat_cache on a learned-variance plan: the forward takes full=True (sr3_unet_forward_cached stores every row)')
+        L.check(plan.lib.sr3_unet_forward_cached(plan.handle, L.ptr(x), L.ptr(cond), cc, L.ptr(noise_level), L.ptr(timestep),
+                                                 L.ptr(freq), L.ptr(level_table), L.ptr(step_dev), L.ptr(arena), L.ptr(wsbuf),
+                                                 need, L.ptr(out), B, C.c_void_p(stream), L.ptr(t_map), L.ptr(cache), cache.numel(),
+                                                 1 if refresh else 0))
+        return out
     if full:
         L.check(plan.lib.sr3_unet_forward_full(plan.handle, L.ptr(x), L.ptr(cond), cc, L.ptr(noise_level), L.ptr(timestep),
                                                L.ptr(freq), L.ptr(level_table), L.ptr(step_dev), L.ptr(arena), L.ptr(wsbuf),

@@ -80,6 +80,12 @@ SIGNATURES = {
     'sr3_plan_op_fold': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'sr3_plan_num_ops': (_I, [_P, _I]),
     'sr3_plan_forward_flops': (C.c_double, [_P, _I]),
+    'sr3_plan_num_ops_cached': (_I, [_P, _I]),
+    'sr3_plan_op_info_cached': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(OpInfo)]),
+    'sr3_plan_set_feature_cache': (_I, [_P, _I]),
+    'sr3_feature_cache_bytes': (_Z, [_P, _I]),
+    'sr3_unet_forward_cached': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _I, _P, _P, _P, _Z, _I]),
+    'sr3_reverse_step_cached': (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _Z, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _Z, _I]),
     'sr3_plan_set_option': (_I, [_P, C.c_char_p, _I]),
     'sr3_store_wt_fits': (_I, [_Z]),
     'sr3_gemm_tile': (_I, [_I, _I, _I, _I, _I, _I, _PI, _PI]),

@@ -276,12 +276,14 @@ class EngineUNet(nn.Module):
                     unexpected_keys.append(k)
 
     # ---- forward ---------------------------------------------------------------------------
-    def forward(self, x, time, *, cond=None, level_table=None, step_dev=None, out=None, ws=None, full=False, t_map=None):
+    def forward(self, x, time, *, cond=None, level_table=None, step_dev=None, out=None, ws=None, full=False, t_map=None, feat_cache=None,
+                refresh=True):
         """eps = UNet(x, time).  `x` may already contain the conditioning channels (reference call
         convention `denoise_fn(torch.cat([cond, x], 1), level)`), or they can be passed separately as
         `cond`, which the input conv reads as a virtual concat (nothing is materialised).  `ws`: a caller-owned
         engine.Workspace (the captured reverse loop keeps its own so no other call can move the buffer its graph
-        has baked in).  `full`: a learned-variance network's variance rows too, [B, 2C, H, W] (engine.unet_forward)."""
+        has baked in).  `full`: a learned-variance network's variance rows too, [B, 2C, H, W] (engine.unet_forward).  `feat_cache`,
+        `refresh` (plan option feat_cache): the feature cache a full forward writes and a cached one (refresh=False) reads."""
         self.ensure_derived()
         kw = {}
         if full:
@@ -292,16 +294,16 @@ class EngineUNet(nn.Module):
             else:
                 kw['timestep'] = time
         return E.unet_forward(self.plan, self.weights(), self.freq, self._ws if ws is None else ws, x, cond=cond,
-                              level_table=level_table, step_dev=step_dev, out=out, **kw)
+                              level_table=level_table, step_dev=step_dev, out=out, feat_cache=feat_cache, refresh=refresh, **kw)
 
     def reverse_step(self, x, z, tables, step2, *, cond=None, level_table=None, clip_denoised=True, eps_out=None, ws=None,
-                     t_map=None, c3=None, hist=None):
+                     t_map=None, c3=None, hist=None, feat_cache=None, refresh=True):
         """One whole iteration of the reverse loop in place on `x` (engine.reverse_step): what `GaussianDiffusion.p_sample_loop`
-        captures into its hipGraph."""
+        captures into its hipGraph.  `feat_cache`, `refresh`: as forward's."""
         self.ensure_derived()
         return E.reverse_step(self.plan, self.weights(), self.freq, self._ws if ws is None else ws, x, z, tables, step2,
                               cond=cond, level_table=level_table, clip_denoised=clip_denoised, eps_out=eps_out, t_map=t_map, c3=c3,
-                              hist=hist)
+                              hist=hist, feat_cache=feat_cache, refresh=refresh)
 
     # ---- training step (forward + backward inside the engine) ------------------------------------
     def train_step(self, hr, cond, z, ca, cb, level, tstep, grad_scale, drop_seed=None, objective=None, hybrid=None, per_image=None,

@@ -167,6 +167,36 @@ def parse_self_condition(spec):
     return SELF_CONDITION_PROB if p is None else p
 
 
+FEATURE_CACHE_KEYS = ('interval', 'depth', 'full_last')
+
+
+def parse_feature_cache(spec):
+    """The config key "feature_cache" of a phase's beta_schedule block -> the keyword arguments of set_feature_cache: {"interval": N,
+    "depth": d, "full_last": k} ("interval" required; depth 1 and full_last 0 where absent), absent / null -> interval None (off)."""
+    if spec is None:
+        return dict(interval=None)
+    if not hasattr(spec, 'get') or not hasattr(spec, 'keys'):
+        raise ValueError('feature_cache: a dict with "interval" is expected (got %r)' % (spec,))
+    for k in spec.keys():
+        if k not in FEATURE_CACHE_KEYS:
+            raise ValueError('feature_cache: unknown key %r (known: %s)' % (k, ', '.join('"%s"' % n for n in FEATURE_CACHE_KEYS)))
+    if spec.get('interval') is None:
+        raise ValueError('feature_cache: "interval" is required')
+    return dict(interval=spec['interval'], depth=spec.get('depth', 1), full_last=spec.get('full_last', 0))
+
+
+def feature_cache_refresh(k, total, interval, full_last=0):
+    """THE refresh schedule of feature-cached sampling: does step k of a chain of `total` steps (k = 0 the chain's first, at the highest
+    noise) run the full forward and refill the cache?  The first step and every interval-th behind it, and the last full_last steps;
+    every other step runs the shallow forward on the cache of the last full one.  interval 1: every step is full."""
+    k, total, interval, full_last = int(k), int(total), int(interval), int(full_last)
+    if not 0 <= k < total:
+        raise ValueError('feature_cache_refresh: step %d outside a chain of %d steps' % (k, total))
+    if interval < 1 or full_last < 0:
+        raise ValueError('feature_cache_refresh: interval >= 1 and full_last >= 0 are expected (got %d, %d)' % (interval, full_last))
+    return k % interval == 0 or k >= total - full_last
+
+
 COND_AUGMENT_KEYS = ('max_level', 'sample_level', 'level_channel')
 
 

@@ -109,6 +109,10 @@ int sr3_plan_op_side(sr3_plan* plan, int batch, int index, int* side_id, int* wa
  * op's GroupNorm too, 3 this statistics pass does (plan option fold_fuse); *mod_row >= 0: the first row of the FiLM table whose 2 C
  * values per image -- scales, then shifts -- modulate the pairs that fold writes (SR3_UNET_SCALE_SHIFT_NORM), -1: none.  Host-only. */
 int sr3_plan_op_fold(sr3_plan* plan, int batch, int index, int* fold, int* mod_row);
+/* The same two for the shallow launch list of a plan under option feat_cache (below): what sr3_unet_forward_cached /
+ * sr3_reverse_step_cached launch with refresh = 0.  Host-only.  On a plan without the option: -1 / SR3_E_BADARG. */
+int sr3_plan_num_ops_cached(sr3_plan* plan, int batch);
+int sr3_plan_op_info_cached(sr3_plan* plan, int batch, int index, sr3_op_info* out);
 /* algorithmic FLOPs (contractions only) of one forward for `batch` images */
 double sr3_plan_forward_flops(sr3_plan* plan, int batch);
 /* host predicate of plan option store_wt: may a tensor (or a set of split-K slabs) of `bytes` bytes be written with write-through buffer
@@ -391,6 +395,42 @@ int sr3_reverse_step_hist(sr3_plan* plan, float* x_nchw, const float* cond_nchw,
                           const float* z_nchw, const float* tab_a, const float* tab_b, const float* tab_c1, const float* tab_c2,
                           const float* tab_sigma, int clip_denoised, float* eps_out_nchw, int batch, void* stream, const int* t_map,
                           const float* tab_c3, float* hist_nchw);
+
+/* ---- feature-cached forward (engine extension; plan option feat_cache; DeepCache, Ma et al. 2023) --------------------------
+ * Consecutive reverse steps feed the network almost the same input, and what lies below the top resolution level moves little between
+ * them: a cached step recomputes only the shallow forward of the option's depth and reads everything deeper, as one tensor, from the
+ * last full step.  An approximation the caller opts into; how often to refresh is the caller's schedule.
+ * sr3_plan_set_feature_cache: plan option feat_cache = depth (default 0 = off; inference plans), set through this entry rather than as a
+ *   key of sr3_plan_set_option; returns the previous value like it.  depth d in 1 .. res_blocks + 1 (SR3_E_UNSUPPORTED otherwise, the
+ *   range named) compiles a second, shallow launch list next to the full one -- the embedding, the first d entries of downs (the input
+ *   conv and d - 1 res blocks), the last d res blocks of ups with their attention, the output conv: all on the top resolution level --
+ *   whose first up block reads the tensor that enters it in the full forward (the branch tensor) and its GroupNorm partials from a
+ *   caller-owned feature cache.  The full list of such a plan runs the ops, kernels and bits of a plan without the option, with the
+ *   branch tensor's producer writing into the cache; it runs through the two _cached entries alone (every other forward entry refuses a
+ *   plan under the option: it has no cache to write).  sr3_workspace_bytes covers both lists.  The training plan does not look at it.
+ * sr3_feature_cache_bytes: the size of the cache for `batch` images at the plan's geometry (the branch tensor, then its GroupNorm
+ *   partials); 0 on a plan without the option.  The cache is the caller's, 256-byte aligned, and no part of the workspace: the
+ *   workspace may hold anything between a refresh and the cached forwards behind it, the cache must be left alone.
+ * sr3_unet_forward_cached: sr3_unet_forward_full's call.  refresh = 1: the full forward, which also leaves the branch tensor in
+ *   feat_cache -- eps bit-identical to sr3_unet_forward_full on a plan without the option.  refresh = 0: the shallow forward on
+ *   (x, level) reading feat_cache.
+ * sr3_reverse_step_cached: sr3_reverse_step_hist's call, the tail and the counter decrement in the output conv as there.
+ * Checked before any launch, behind the checks of the plain entry: feat_cache NULL (SR3_E_BADARG), feat_cache_bytes too small
+ * (SR3_E_NOMEM), not 256-byte aligned (SR3_E_ALIGN); refresh = 0 on a plan without the option, on a cache no refresh has filled, or at
+ * a batch / geometry / buffer other than the last refresh's (SR3_E_BADARG).  The bookkeeping is the host's, made when the call is
+ * issued (or captured).  refresh = 1 on a plan without the option is the plain forward; the cache is not looked at. */
+int sr3_plan_set_feature_cache(sr3_plan* plan, int depth);
+size_t sr3_feature_cache_bytes(sr3_plan* plan, int batch);
+int sr3_unet_forward_cached(sr3_plan* plan, const float* x_nchw, const float* cond_nchw, int cond_channels,
+                            const float* noise_level, const int64_t* timestep, const float* freq,
+                            const float* level_table, const int* step_dev, const float* params,
+                            void* workspace, size_t workspace_bytes, float* eps_out_nchw, int batch,
+                            void* stream, const int* t_map, void* feat_cache, size_t feat_cache_bytes, int refresh);
+int sr3_reverse_step_cached(sr3_plan* plan, float* x_nchw, const float* cond_nchw, int cond_channels, const float* freq,
+                            const float* level_table, int* step2_dev, const float* params, void* workspace, size_t workspace_bytes,
+                            const float* z_nchw, const float* tab_a, const float* tab_b, const float* tab_c1, const float* tab_c2,
+                            const float* tab_sigma, int clip_denoised, float* eps_out_nchw, int batch, void* stream, const int* t_map,
+                            const float* tab_c3, float* hist_nchw, void* feat_cache, size_t feat_cache_bytes, int refresh);
 
 /* ---- tiled sampling (engine extension; no reference counterpart) ------------------------------
  * An image larger than the training size is sampled as ONE chain whose eps comes from overlapping tiles of the training size: per
